@@ -13,8 +13,10 @@ on.  Multi-GPU is weak scaling over independent (batch, head) problems: every ra
 b=4 shard (N=8 is BASELINE configs[4]'s b=32), no data-path collective; the only
 communication is the timing barrier and a MAX all-reduce of the elapsed time.
 
-Prints ONE JSON line on rank 0 (contract in the task statement): `value` = whole-job
-TFLOP/s using the ALGORITHMIC FLOPs of SURVEY.md §8(d) (4*b*h*sq*sk*d, x1/2 causal),
+Prints ONE JSON line on rank 0: `value` = whole-job TFLOP/s using the ALGORITHMIC FLOPs of
+SURVEY.md §8(d) (4*b*h*sq*sk*d, x1/2 causal), `ms_per_step` = wall milliseconds of one timed step.
+A plain run does nothing else: set-up, W warm-up steps, K timed steps, the line.  `--dump-outputs DIR`
+writes what the last timed step computed as DIR/<name>.npy (dump_outputs).  With `--full` the line also carries
 `roofline` for the dominant kernel (the forward kernel) from HIP-event timing on the launch stream,
 `cpu_baseline` = the CPU oracle (oracle/, the checker, never the product) timed on a bounded
 sample on rank 0 at N=1, plus PyTorch SDPA's CPU math path at BASELINE configs[0] as the
@@ -639,6 +641,36 @@ def contract_fields(workload, world):
                        "flops_def": "4*b*h*sq*sk*d (x0.5 causal) [SURVEY.md 8d]"}}
 
 
+def headline_fields(args, dist, backward, flops_rank, wall, comm_backend, capi, prop):
+    """The result line of every run: the headline rate of the K timed steps and what names it (a --full run adds its measurements to it)"""
+    value = flops_rank * dist.world / (wall / args.steps) / 1e12
+    return {"metric": "attention_fwd_tflops" if not backward else "attention_fwd_bwd_tflops",
+            "value": value, "unit": "TFLOP/s", "n_gpus": dist.world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": wall / args.steps * 1e3, **contract_fields(args.workload, dist.world),
+            "frac_of_fp16_mfma_peak": value / (PEAK_DENSE_FP16_TFLOPS * dist.world),
+            "comm_backend": comm_backend, "library": capi.lib().fa_build_info().decode(), "git_commit": build_commit(),
+            "device": {"name": prop.name or getattr(prop, "gcnArchName", ""), "arch": getattr(prop, "gcnArchName", ""), "cus": prop.multi_processor_count,
+                       "hbm_gib": prop.total_memory / 2**30, "peak_used_tflops": PEAK_DENSE_FP16_TFLOPS}}
+
+
+DUMP_BUDGET_ELEMS = 15 << 20      # --dump-outputs: 60 MiB of float32 over all arrays
+
+
+def dump_outputs(torch, outdir, tensors):
+    """--dump-outputs: every tensor as outdir/<name>.npy in float32.  One larger than its share of DUMP_BUDGET_ELEMS is sampled: a fixed set of rows of its
+    last dimension (seeded permutation, sorted), the same in every run with the same arguments, saved as a (rows, last dim) array."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_BUDGET_ELEMS // len(tensors)
+    for name, x in tensors.items():
+        if x.numel() > share:
+            rows = x.reshape(-1, x.shape[-1])
+            pick = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(0))[:share // x.shape[-1]].sort().values
+            x = rows.index_select(0, pick.to(x.device))
+        np.save(os.path.join(outdir, name + ".npy"), x.float().cpu().numpy())
+
+
 def c5_weak_config(world):
     """BASELINE configs[4] as the N > 1 runs carry it in `extra.c5_weak_noncausal_16k`: b = 4 per rank, i.e. the configuration's b = 32 at N = 8"""
     eb, es, eh, _, ed, edt, ec, _ = WORKLOADS["c5shard"]
@@ -719,11 +751,21 @@ def main():
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--fake-step", action="store_true", help="CPU-only harness self-test (no kernels)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other BASELINE configs")
-    ap.add_argument("--n1-consistency", action="store_true", help="with --no-extra: still run the N = 1 row of the strong-scaling sweep beside the headline (extra.n1_consistency)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline, cpu_baseline, the other BASELINE configs, sweeps, ceiling probes (without it: warm-up, "
+                         "the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the arrays the last timed step computed (rank 0) as DIR/<name>.npy, float32; arrays too large for the 60 MiB budget "
+                         "as a fixed, seeded sample of their rows")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the other BASELINE configs")
+    ap.add_argument("--n1-consistency", action="store_true", help="with --full --no-extra: still run the N = 1 row of the strong-scaling sweep beside the headline (extra.n1_consistency)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-seq", type=int, default=4096)
     args = ap.parse_args()
+    if args.n1_consistency and not args.full:
+        ap.error("--n1-consistency is a measurement of --full")
+    if args.dump_outputs and args.fake_step:
+        ap.error("--dump-outputs needs the kernels: --fake-step computes nothing")
 
     dist = Dist(args.backend)
     if dist.world != args.gpus and dist.world > 1:
@@ -763,12 +805,24 @@ def main():
 
     sync = lambda: torch.cuda.synchronize(device)
     flops_rank = fwd_flops(b, s, s, h, d, causal) * (3.5 if backward else 1.0)
+    outputs = {n: t[n] for n in (("o", "lse", "dq", "dk", "dv") if backward else ("o", "lse"))}      # what a caller of the step receives
+    prop = torch.cuda.get_device_properties(device)
+    if not args.full:
+        wall, _ = timed_region(step, args.steps, args.warmup, dist, sync, device)
+        if args.dump_outputs and dist.rank == 0:
+            dump_outputs(torch, args.dump_outputs, outputs)
+        if dist.rank == 0:
+            print(json.dumps(headline_fields(args, dist, backward, flops_rank, wall, comm_backend, capi, prop)))
+        dist.close()
+        return
     # the power-capped MFMA rate of this box, >= 1 s at settled power, BEFORE the timed region (and again after it, below): the box-independent denominator
     pm_before = power_capped_mfma_rate() if (dist.rank == 0 and dist.world == 1 and not args.no_extra) else None
     region_events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
     with PowerSampler(device.index) as sampler:
         wall, _ = timed_region(step, args.steps, args.warmup, dist, sync, device, events=region_events)
         t_reg1 = time.perf_counter()
+        if args.dump_outputs and dist.rank == 0:
+            dump_outputs(torch, args.dump_outputs, outputs)      # (before the sustained launches below run the step again)
         power_timed = sampler.summary(t_reg1 - wall, t_reg1, f"the timed region itself ({args.steps} steps, {wall * 1e3:.0f} ms)")
         # the timed region of the default command is ~0.15 s; >= 2 s of the same step, every step between its own HIP events, gives the
         # sensors time to settle and the steady-state figure (median / min) SURVEY 8(d) asks for
@@ -785,7 +839,6 @@ def main():
         t_s1 = time.perf_counter()
         power_sustained = sampler.summary(t_s0 + 0.5, t_s1, "2 s of back-to-back launches of the same step right after the timed region (first 0.5 s dropped)")
     ms_per_step = wall / args.steps * 1e3
-    value = flops_rank * dist.world / (wall / args.steps) / 1e12
     region_event_ms = region_events[0].elapsed_time(region_events[1]) / args.steps      # device-side ms per step of the timed region
     import statistics as _stats
     sus = [a.elapsed_time(b) for a, b in sustained_evs][len(sustained_evs) // 4:]      # (first quarter dropped: the ramp)
@@ -805,7 +858,6 @@ def main():
     k_dist = launch_time_distribution(torch, fwd_only, max(30, args.steps))
     traffic, traffic_source, prof_digest, prof_commit = hbm_traffic_from_profile(args.workload, fwd_kernel) if dist.rank == 0 else (None, None, None, None)
     lib_digest = library_source_digest(capi)
-    prop = torch.cuda.get_device_properties(device)
     sclk_ghz = max(capi.device_clock_khz(device.index), 0) / 1e6     # hipDeviceAttributeClockRate (torch's props carry no clock)
     roofline = {"bound": "mfma", "kernel": fwd_kernel, "achieved": k_tflops, "peak": PEAK_DENSE_FP16_TFLOPS,
                 "unit": "TFLOP/s", "frac": k_tflops / PEAK_DENSE_FP16_TFLOPS,
@@ -1043,17 +1095,11 @@ def main():
         roofline["warning"] = (f"roofline.traffic comes from a profile of library build src={prof_digest}, this run timed src={lib_digest}: "
                                "re-run tools/round_evidence.sh on the current kernels")
     if dist.rank == 0:
-        out = {
-            "metric": "attention_fwd_tflops" if not backward else "attention_fwd_bwd_tflops",
-            "value": value, "unit": "TFLOP/s", "n_gpus": dist.world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, **contract_fields(args.workload, dist.world),
-            "frac_of_fp16_mfma_peak": value / (PEAK_DENSE_FP16_TFLOPS * dist.world),
+        out = headline_fields(args, dist, backward, flops_rank, wall, comm_backend, capi, prop)
+        out.update({
             "tflops_at_median_launch": roofline["tflops_at_median_launch"] * dist.world,      # whole-job rate at the MEDIAN launch of a separate 30+ launch loop (less box noise than the K-step mean)
-            "comm_backend": comm_backend, "library": capi.lib().fa_build_info().decode(), "git_commit": build_commit(),
             "roofline": roofline, "cpu_baseline": cpu, "extra": extra,
-            "device": {"name": prop.name or getattr(prop, "gcnArchName", ""), "arch": getattr(prop, "gcnArchName", ""), "cus": prop.multi_processor_count, "hbm_gib": prop.total_memory / 2**30,
-                       "peak_used_tflops": PEAK_DENSE_FP16_TFLOPS},
-        }
+        })
         print(json.dumps(out))
     dist.close()
 

@@ -240,3 +240,32 @@ def test_driver_scale_command_line_at_eight_ranks():
     timing = {"value", "ms_per_step", "local_ms", "extra", "comm_backend", "subgroup_collectives"}
     assert {k: v for k, v in a.items() if k not in timing} == {k: v for k, v in b.items() if k not in timing}
     assert a["n_gpus"] == b["n_gpus"] == 1 and a["config"]["global_batch"] == 4 and "c5_weak_noncausal_16k" not in a["extra"]
+
+
+def test_dump_outputs_writes_float32_the_same_rows_every_run_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per output.  A tensor over its share of the budget is sampled by rows, the same sorted rows in every run
+    (two builds compare file for file); one within its share is written whole; the whole dump of the five backward outputs stays under 64 MB"""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    o = torch.randn(2, 4096, 32, 128, generator=torch.Generator().manual_seed(1))
+    o.view(-1, 128)[:, 0] = torch.arange(2 * 4096 * 32, dtype=torch.float32)          # row r carries r: a sampled row names itself
+    lse = torch.randn(2, 32, 4096, generator=torch.Generator().manual_seed(2))
+    outs = {"o": o, "lse": lse, "dq": o.half(), "dk": o.bfloat16(), "dv": o.half()}
+    for run in ("a", "b"):
+        bench.dump_outputs(torch, str(tmp_path / run), outs)
+    assert sorted(os.listdir(tmp_path / "a")) == ["dk.npy", "dq.npy", "dv.npy", "lse.npy", "o.npy"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in outs}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert all(np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy")) for n in outs)
+    assert np.array_equal(got["lse"], lse.numpy())
+    share = bench.DUMP_BUDGET_ELEMS // len(outs)
+    assert got["o"].shape == (share // 128, 128)
+    rows = got["o"][:, 0].astype(np.int64)
+    assert (np.diff(rows) > 0).all() and rows[0] < 1000 and rows[-1] > 2 * 4096 * 32 - 1000       # sorted, spread over the whole tensor
+    for n in ("o", "dq", "dk", "dv"):
+        assert np.array_equal(got[n], outs[n].view(-1, 128)[torch.from_numpy(rows)].float().numpy()), n
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64e6

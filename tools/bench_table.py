@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Markdown rows for DESIGN.md section 4 / README from a bench.py JSON line.  Usage: bench_table.py BENCH.json"""
+"""Markdown rows for DESIGN.md section 4 / README from a `bench.py --full` JSON line.  Usage: bench_table.py BENCH.json"""
 import json
 import sys
 

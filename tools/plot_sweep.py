@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Bar charts of the seqlen sweep in a bench.py JSON line, in the spirit of the reference README's figures (its utils/plot_kernels.py
+"""Bar charts of the seqlen sweep in a `bench.py --full` JSON line, in the spirit of the reference README's figures (its utils/plot_kernels.py
 draws speed-up over PyTorch and throughput per sequence length): speed-up of the forward over torch's fused SDPA on the same GPU
 and forward TFLOP/s, causal and non-causal.  Usage: plot_sweep.py BENCH.json OUT_PREFIX  -> OUT_PREFIX_speedup.png, OUT_PREFIX_tflops.png"""
 import json

@@ -90,7 +90,7 @@ def main():
     c4 = {k: v for k, v in st4.items() if k.startswith("fa_")}
     summary = {
         **tagline,
-        "what": "one MI355X box, one lease, in this order: plain bench.py; rocprofv3 --kernel-trace --stats of bench.py (c3) and of bench.py --workload c4; "
+        "what": "one MI355X box, one lease, in this order: bench.py --full; rocprofv3 --kernel-trace --stats of bench.py --full (c3) and of bench.py --workload c4 --full; "
                 "FETCH_SIZE / WRITE_SIZE passes; three SQ counter passes (tools/round_evidence.sh)",
         "bench_line": {k: b[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "frac_of_fp16_mfma_peak")},
         "roofline_from_bench_hip_events": {k: b["roofline"][k] for k in ("kernel", "achieved", "frac", "avg_launch_ms", "launch_ms_distribution", "power_and_sclk")},
