@@ -54,12 +54,11 @@ int check_common(int b, int sq, int sk, int h, int hk, int d, int dtype) {
 // ABI 4: the caller's struct -> a zeroed local one, min(caller's size, ours) bytes.  Fields appended after the caller's header was
 // written stay 0 / NULL ("not given"); a struct without the {size, magic} header (ABI 1-3 callers) or longer than ours is an error.
 template <typename P>
-int import_params(const P* user, P& local, const char* what) {
+int import_params(const P* user, P& local, const char* what, size_t base = offsetof(P, total_q)) {   // base: everything up to the first appended (optional) field is mandatory
     if (user == nullptr) return fail(FA_ERR_NULL_POINTER, "params is NULL");
     if (user->magic != FA_PARAMS_MAGIC)
         return fail(FA_ERR_BAD_ABI, "%s: no {struct_size, magic} header - caller was compiled against an ABI < 4 header; recompile against include/flash_attn_gfx950.h (ABI %d)",
                     what, FA_ABI_VERSION);
-    const size_t base = offsetof(P, total_q);           // everything up to the first appended (optional) field is mandatory
     if (user->struct_size < base || user->struct_size > sizeof(P))
         return fail(FA_ERR_BAD_ABI, "%s: struct_size %u outside [%zu, %zu] - header / library mismatch", what, user->struct_size, base, sizeof(P));
     memset(&local, 0, sizeof(P));
@@ -330,6 +329,78 @@ int fa_mha_varlen_bwd(const void* q, const void* k, const void* v, const void* o
     p.q_stride = fa_strides{0, (int64_t)h * d, d}; p.o_stride = p.do_stride = p.dq_stride = p.q_stride;
     p.k_stride = fa_strides{0, (int64_t)hk * d, d}; p.v_stride = p.dk_stride = p.dv_stride = p.k_stride;
     return fa_run_mha_bwd(&p, stream);
+}
+
+// with_workspace = false: the `workspace` fields are not looked at (fa_kvcache_workspace_bytes)
+static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& kp, fa_kvcache_params& local, bool with_workspace) {
+    int rc = import_params(user, local, "fa_kvcache_params", sizeof(fa_kvcache_params));
+    if (rc) return rc;
+    const fa_kvcache_params* p = &local;
+    if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0 || p->seqlen_new < 0 || p->h <= 0 || p->h_k <= 0)
+        return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d seqlen_new=%d h=%d h_k=%d", p->b, p->seqlen_q, p->seqlen_cache,
+                    p->seqlen_new, p->h, p->h_k);
+    if ((rc = check_common(p->b, p->seqlen_q, p->seqlen_cache, p->h, p->h_k, p->d, p->dtype))) return rc;
+    if (p->seqlen_new > p->seqlen_cache)
+        return fail(FA_ERR_BAD_SHAPE, "seqlen_new (%d) exceeds the cache capacity seqlen_cache (%d)", p->seqlen_new, p->seqlen_cache);
+    if ((p->k_new == nullptr) != (p->v_new == nullptr)) return fail(FA_ERR_NULL_POINTER, "k_new and v_new must both be given or both be NULL");
+    if (p->k_new != nullptr && p->cache_seqlens == nullptr)
+        return fail(FA_ERR_NULL_POINTER, "k_new / v_new need cache_seqlens (the rows they are appended at)");
+    if (p->k_new == nullptr && p->seqlen_new != 0) return fail(FA_ERR_BAD_SHAPE, "seqlen_new = %d without k_new / v_new", p->seqlen_new);
+    if (p->num_splits < 0) return fail(FA_ERR_BAD_SHAPE, "num_splits must be >= 0 (0 = the library's choice), got %d", p->num_splits);
+    if (with_workspace && p->workspace_bytes < 0) return fail(FA_ERR_BAD_SHAPE, "workspace_bytes must be >= 0");
+    if (with_workspace && p->workspace != nullptr && (reinterpret_cast<uintptr_t>(p->workspace) & 15u) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
+    if (p->b > 0) {
+        if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
+        if ((rc = check_tensor("q", p->q, p->q_stride, p->seqlen_q, p->d, false))) return rc;
+        if ((rc = check_tensor("o", p->o, p->o_stride, p->seqlen_q, p->d, false))) return rc;
+        if ((rc = check_tensor("k_cache", p->k_cache, p->k_cache_stride, p->seqlen_cache, p->d, false))) return rc;
+        if ((rc = check_tensor("v_cache", p->v_cache, p->v_cache_stride, p->seqlen_cache, p->d, false))) return rc;
+        if (p->k_new != nullptr) {
+            if ((rc = check_tensor("k_new", p->k_new, p->k_new_stride, p->seqlen_new, p->d, false))) return rc;
+            if ((rc = check_tensor("v_new", p->v_new, p->v_new_stride, p->seqlen_new, p->d, false))) return rc;
+        }
+    }
+    memset(&kp, 0, sizeof(kp));
+    kp.q_ptr = p->q; kp.k_cache = p->k_cache; kp.v_cache = p->v_cache; kp.k_new = p->k_new; kp.v_new = p->v_new;
+    kp.o_ptr = p->o; kp.lse_ptr = p->lse; kp.cache_seqlens = p->cache_seqlens;
+    kp.q = conv(p->q_stride); kp.kc = conv(p->k_cache_stride); kp.vc = conv(p->v_cache_stride);
+    kp.kn = conv(p->k_new_stride); kp.vn = conv(p->v_new_stride); kp.o = conv(p->o_stride);
+    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_cache = p->seqlen_cache; kp.seqlen_new = p->k_new != nullptr ? p->seqlen_new : 0;
+    kp.h = p->h; kp.h_k = p->h_k; kp.h_ratio = p->h / p->h_k; kp.d = p->d;
+    kp.is_causal = p->is_causal ? 1 : 0;
+    kp.scale = 1.0f / sqrtf((float)p->d);
+    kp.scale_log2e = kp.scale * 1.4426950408889634f;
+    return FA_OK;
+}
+
+int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* user) {
+    fa::KvcacheKernelParams kp;
+    fa_kvcache_params local;
+    int rc = fill_kvcache(user, kp, local, false);
+    if (rc) return rc;
+    if (kp.b == 0) return 0;
+    return fa::kvcache_workspace_bytes(kp, fa::kvcache_split(kp, -1, local.num_splits));
+}
+
+int32_t fa_kvcache_num_splits(const fa_kvcache_params* user) {
+    fa::KvcacheKernelParams kp;
+    fa_kvcache_params local;
+    int rc = fill_kvcache(user, kp, local, true);
+    if (rc) return rc;
+    if (kp.b == 0) return 1;
+    return fa::kvcache_split(kp, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits);
+}
+
+int fa_run_mha_fwd_kvcache(const fa_kvcache_params* user, void* stream) {
+    fa::KvcacheKernelParams kp;
+    fa_kvcache_params local;
+    int rc = fill_kvcache(user, kp, local, true);
+    if (rc) return rc;
+    if (kp.b == 0) return FA_OK;
+    kp.n_split = fa::kvcache_split(kp, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits);
+    kp.ws_o = kp.n_split > 1 ? (float*)local.workspace : nullptr;
+    return hip_status(fa::launch_fwd_kvcache(kp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache launch");
 }
 
 }  // extern "C"

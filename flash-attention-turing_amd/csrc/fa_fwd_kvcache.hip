@@ -1,0 +1,399 @@
+// fa_fwd_kvcache.hip — decode attention over a KV cache (fa_run_mha_fwd_kvcache, include/flash_attn_gfx950.h).
+//
+// Decode reads every K/V byte of the valid cache prefix once per step: the work is HBM-bound, and the prefill kernels are the wrong shape
+// for it (256 query rows per workgroup, one workgroup per query head).  Here:
+//   * the seqlen_q x (h / h_k) query rows of one KV head are PACKED into row tiles of 16 (packed row r = t * h_ratio + j: query position t,
+//     query head kv_head * h_ratio + j), so K/V are read once per KV head and row tile, not once per query head;
+//   * the key range is split over workgroups (fixed multiples of kKvcStep over seqlen_cache, sized by the host from the capacity) so that
+//     batch 1 fills the chip; the splits leave fp32 partial O / LSE in a workspace and a combine kernel merges them by their LSE in fixed order;
+//   * one workgroup = 4 waves; wave w takes the 32-key steps w, w + 4, ... of its split with a private online softmax and the waves are
+//     merged through LDS at the end.
+// Per 32-key step a wave computes S^T = K Q^T with v_mfma_f32_16x16x32 (A = K rows straight from HBM: 16-byte loads per lane, B = Q^T held in
+// registers for the whole split) and O^T += V^T P^T (B = P^T straight from the S^T accumulator, A = V^T through a per-wave LDS image read with
+// ds_read_b64_tr_b16 - the one place the operand layout needs LDS).  With the scores transposed, a lane owns ONE query row (lane & 15) and
+// four keys per 16-key block, so the row statistics stay per lane and O^T comes out with the row on the lane as well.
+//   S^T (16 keys x 16 rows), block kb:  lane l holds key 16 kb + 4 (l >> 4) + r, row l & 15   (r = 0..3)
+//   P^T k-slots of a step:              slot 8 g + j  <->  key 4 g + j (j < 4), 16 + 4 g + j - 4 (j >= 4)       (g = l >> 4)
+//   O^T block c:                        lane l holds column 16 c + 4 g + r of row l & 15
+// Next step's K and V are loaded into a second register set before the current step is computed (two sets, no copies).  K/V rows are
+// addressed through buffer descriptors whose range ends at the sequence's valid length L: rows at or past L read as zeros (V zeros matter:
+// 0 x NaN from an uninitialised cache row would poison O), and the scores of keys past L or behind the causal limit are masked to -inf.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "fa_device.hpp"
+#include "fa_params.hpp"
+
+namespace fa {
+
+namespace {
+
+constexpr int kKvcWaves = 4;
+constexpr int kKvcThreads = 64 * kKvcWaves;
+constexpr int kKvcMaxSplits = 128;
+constexpr int kKvcMinStepsPerSplit = 8;      // 256 keys: two steps per wave before a split pays its prologue and merge
+constexpr int kKvcCombineThreads = 256;
+
+template <int D>
+struct KvcLds {
+    static constexpr int kVStage = 32 * D * 2;                                  // one wave's V image: 32 rows x D 16-bit
+    static constexpr int kOPitch = D + 4;                                       // fp32 merge rows, padded by 16 bytes
+    static constexpr int kMerge = kKvcWaves * kKvcRows * kOPitch * 4 + 2 * kKvcWaves * kKvcRows * 4;
+    static constexpr int kBytes = kKvcWaves * kVStage > kMerge ? kKvcWaves * kVStage : kMerge;
+};
+
+FA_DEV int kvc_len(const KvcacheKernelParams& p, int bidx) {
+    int L = p.seqlen_cache;
+    if (p.cache_seqlens != nullptr) {
+        const int cs = p.cache_seqlens[bidx];
+        L = min((cs > 0 ? cs : 0) + p.seqlen_new, p.seqlen_cache);
+    }
+    return __builtin_amdgcn_readfirstlane(L);
+}
+
+template <typename T, int D, bool CAUSAL>
+__global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_kernel(const KvcacheKernelParams p) {
+    constexpr int NC = D / 32;          // 16x16x32 MFMAs per 16 keys of S^T (d chunks)
+    constexpr int NO = D / 16;          // O^T blocks of 16 columns
+    constexpr int SLOTS = D / 8;        // 16-byte slots per row
+    constexpr int VRPL = 64 / SLOTS;    // V rows per wave-wide 16-byte load
+    constexpr int NV = kKvcStep / VRPL; // V loads per lane and step
+    __shared__ __attribute__((aligned(16))) char smem[KvcLds<D>::kBytes];
+
+    const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, n16 = lane & 15;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int id = blockIdx.x;
+    const int split = id % p.n_split, rest = id / p.n_split;
+    const int tile = rest % p.n_row_tiles, bh = rest / p.n_row_tiles;
+    const int bidx = bh / p.h_k, kvh = bh - bidx * p.h_k;
+    const int L = kvc_len(p, bidx);
+    const int k_begin = split * p.split_keys;
+    const int k_end = min(k_begin + p.split_keys, L);
+    const int rows_tile = p.seqlen_q * p.h_ratio;
+    const float c = p.scale_log2e;
+
+    if (p.n_split > 1 && k_begin >= k_end) {        // nothing to read in this split: an empty partial (LSE = -inf), O is never looked at
+        if (tid < kKvcRows) {
+            const int pr = tile * kKvcRows + tid;
+            if (pr < rows_tile) {
+                const int t = pr / p.h_ratio, hq = kvh * p.h_ratio + (pr - t * p.h_ratio);
+                p.ws_lse[(int64_t)split * p.rows_total + ((int64_t)bidx * p.h + hq) * p.seqlen_q + t] = -INFINITY;
+            }
+        }
+        return;
+    }
+
+    // ---- this lane's query row: Q^T fragments for the whole split, visible-key limit -------------------------------------------------
+    const int pr = tile * kKvcRows + n16;
+    const bool row_ok = pr < rows_tile;
+    const int t = row_ok ? pr / p.h_ratio : 0;
+    const int hq = kvh * p.h_ratio + (row_ok ? pr - t * p.h_ratio : 0);
+    int lim = row_ok ? L : 0;
+    if (CAUSAL && row_ok) lim = min(L, L - p.seqlen_q + t + 1);
+    u32x4 qf[NC];
+    {
+        const char* qrow = (const char*)p.q_ptr + 2 * ((int64_t)bidx * p.q.batch + (int64_t)t * p.q.row + (int64_t)hq * p.q.head);
+        static_for<0, NC>([&](auto cc) {
+            constexpr int ci = decltype(cc)::value;
+            qf[ci] = row_ok ? *(const u32x4*)(qrow + 2 * (32 * ci + 8 * g)) : u32x4{0u, 0u, 0u, 0u};
+        });
+    }
+
+    // ---- K / V of this (batch, KV head): descriptors end at row L ------------------------------------------------------------------
+    const uint32_t krow_b = (uint32_t)(p.kc.row * 2), vrow_b = (uint32_t)(p.vc.row * 2);
+    const char* kbase = uniform_ptr((const char*)p.k_cache + 2 * ((int64_t)bidx * p.kc.batch + (int64_t)kvh * p.kc.head));
+    const char* vbase = uniform_ptr((const char*)p.v_cache + 2 * ((int64_t)bidx * p.vc.batch + (int64_t)kvh * p.vc.head));
+    const rsrc_t krs = make_rsrc(kbase, L > 0 ? (uint32_t)(L - 1) * krow_b + 2 * D : 0u);
+    const rsrc_t vrs = make_rsrc(vbase, L > 0 ? (uint32_t)(L - 1) * vrow_b + 2 * D : 0u);
+    // (row indices are clamped to L: a row at L is past the descriptor's range, and (L) x row stride < 2^31 by the host checks)
+    auto load_step = [&](int key0, u32x4 (&kf)[2][NC], u32x4 (&vf)[NV]) __attribute__((always_inline)) {
+        static_for<0, 2>([&](auto kb) {
+            constexpr int b = decltype(kb)::value;
+            const uint32_t off = (uint32_t)min(key0 + 16 * b + n16, L) * krow_b + 2 * 8 * g;
+            static_for<0, NC>([&](auto cc) {
+                constexpr int ci = decltype(cc)::value;
+                kf[b][ci] = buf_load16(krs, off + 2 * 32 * ci);
+            });
+        });
+        static_for<0, NV>([&](auto iv) {
+            constexpr int i = decltype(iv)::value;
+            const uint32_t off = (uint32_t)min(key0 + i * VRPL + lane / SLOTS, L) * vrow_b + 16 * (lane % SLOTS);
+            vf[i] = buf_load16(vrs, off);
+        });
+    };
+
+    FA_LDS char* vstage = (FA_LDS char*)smem + wave * KvcLds<D>::kVStage;
+    // transposed-read addresses of this lane (fa_device.hpp lds_tile_off image): block c, half hh -> rows hh * 16 + 4 g + q, columns 16 c + 4 p
+    const int q4 = n16 >> 2, p4 = n16 & 3;
+
+    f32x4 oacc[NO];
+    // (the empty asm pins the zeros here: sunk into the path that skips the loop, they were laid out straight behind the loop's last MFMA,
+    // which the conservative hazard scan of tests/_mfma_hazards.py reads as a write to a result still in flight)
+    static_for<0, NO>([&](auto cc) {
+        oacc[decltype(cc)::value] = f32x4{0.f, 0.f, 0.f, 0.f};
+        asm volatile("" : "+v"(oacc[decltype(cc)::value]));
+    });
+    float m_run = kNegBig, l_run = 0.f;
+
+    auto compute_step = [&](int key0, const u32x4 (&kf)[2][NC], const u32x4 (&vf)[NV]) __attribute__((always_inline)) {
+        f32x4 s[2];
+        static_for<0, 2>([&](auto kb) {
+            constexpr int b = decltype(kb)::value;
+            s[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+            static_for<0, NC>([&](auto cc) { s[b] = LP<T>::mfma16(kf[b][decltype(cc)::value], qf[decltype(cc)::value], s[b]); });
+        });
+        // V -> this wave's LDS image while the MFMAs run
+        static_for<0, NV>([&](auto iv) {
+            constexpr int i = decltype(iv)::value;
+            *(FA_LDS u32x4*)(vstage + lds_tile_off<D>(i * VRPL + lane / SLOTS, lane % SLOTS)) = vf[i];
+        });
+        float mx = -INFINITY;
+        static_for<0, 2>([&](auto kb) {
+            constexpr int b = decltype(kb)::value;
+            static_for<0, 4>([&](auto rr) {
+                constexpr int r = decltype(rr)::value;
+                const int key = key0 + 16 * b + 4 * g + r;
+                s[b][r] = key < lim ? s[b][r] : -INFINITY;
+                mx = fmaxf(mx, s[b][r]);
+            });
+        });
+        mx = max_four_groups(mx);
+        const float m_new = fmaxf(m_run, mx);
+        const float alpha = fast_exp2((m_run - m_new) * c);
+        m_run = m_new;
+        const float mc = m_new * c;
+        float pe[8];
+        float ps = 0.f;
+        static_for<0, 8>([&](auto jj) {
+            constexpr int j = decltype(jj)::value;
+            pe[j] = fast_exp2(__builtin_fmaf(s[j >> 2][j & 3], c, -mc));
+            ps += pe[j];
+        });
+        l_run = l_run * alpha + ps;
+        const u32x4 pf = u32x4{LP<T>::pack2(pe[0], pe[1]), LP<T>::pack2(pe[2], pe[3]), LP<T>::pack2(pe[4], pe[5]), LP<T>::pack2(pe[6], pe[7])};
+        static_for<0, NO>([&](auto cc) {
+            constexpr int ci = decltype(cc)::value;
+            oacc[ci] *= alpha;
+        });
+        asm volatile("" ::: "memory");      // the image written above is read back below (same wave: LDS keeps the order)
+        static_for<0, NO>([&](auto cc) {
+            constexpr int ci = decltype(cc)::value;
+            const uint32_t a0 = lds_tile_off<D>(4 * g + q4, 2 * ci + (p4 >> 1)) + 8 * (p4 & 1);
+            const uint32_t a1 = lds_tile_off<D>(16 + 4 * g + q4, 2 * ci + (p4 >> 1)) + 8 * (p4 & 1);
+            const u32x2 v0 = lds_read_tr8(vstage, a0), v1 = lds_read_tr8(vstage, a1);
+            oacc[ci] = LP<T>::mfma16(u32x4{v0.x, v0.y, v1.x, v1.y}, pf, oacc[ci]);
+        });
+        asm volatile("" ::: "memory");      // ... before the next step overwrites it
+    };
+
+    // ---- the split's 32-key steps, interleaved over the waves; two register sets in turn -----------------------------------------
+    {
+        u32x4 ka[2][NC], kb2[2][NC], va[NV], vb[NV];
+        int key = k_begin + wave * kKvcStep;
+        const int stride = kKvcWaves * kKvcStep;
+        if (key < k_end) load_step(key, ka, va);
+        for (; key < k_end; key += 2 * stride) {
+            const int k1 = key + stride;
+            if (k1 < k_end) load_step(k1, kb2, vb);
+            compute_step(key, ka, va);
+            if (k1 < k_end) {
+                if (k1 + stride < k_end) load_step(k1 + stride, ka, va);
+                compute_step(k1, kb2, vb);
+            }
+        }
+    }
+
+    // ---- merge the four waves through LDS --------------------------------------------------------------------------------------
+    l_run = sum_four_groups(l_run);
+    __syncthreads();                               // every wave is done with its V image (the merge planes overlay them)
+    FA_LDS float* ow_l = (FA_LDS float*)smem;
+    FA_LDS float* mw_l = ow_l + kKvcWaves * kKvcRows * KvcLds<D>::kOPitch;
+    FA_LDS float* lw_l = mw_l + kKvcWaves * kKvcRows;
+    static_for<0, NO>([&](auto cc) {
+        constexpr int ci = decltype(cc)::value;
+        *(FA_LDS f32x4*)(ow_l + (wave * kKvcRows + n16) * KvcLds<D>::kOPitch + 16 * ci + 4 * g) = oacc[ci];
+    });
+    if (g == 0) {
+        mw_l[wave * kKvcRows + n16] = m_run;
+        lw_l[wave * kKvcRows + n16] = l_run;
+    }
+    __syncthreads();
+
+    constexpr int CPT = D / 16;                    // output columns per thread: 16 threads per row
+    const int row = tid >> 4, col = (tid & 15) * CPT;
+    const int opr = tile * kKvcRows + row;
+    if (opr >= rows_tile) return;
+    float mrow = kNegBig;
+    static_for<0, kKvcWaves>([&](auto ww) { mrow = fmaxf(mrow, mw_l[decltype(ww)::value * kKvcRows + row]); });
+    float lsum = 0.f, acc[CPT];
+    static_for<0, CPT>([&](auto jj) { acc[decltype(jj)::value] = 0.f; });
+    static_for<0, kKvcWaves>([&](auto ww) {
+        constexpr int w = decltype(ww)::value;
+        const float a = fast_exp2((mw_l[w * kKvcRows + row] - mrow) * c);
+        lsum += lw_l[w * kKvcRows + row] * a;
+        static_for<0, CPT / 4>([&](auto qq) {
+            constexpr int qi = decltype(qq)::value;
+            const f32x4 x = *(const FA_LDS f32x4*)(ow_l + (w * kKvcRows + row) * KvcLds<D>::kOPitch + col + 4 * qi);
+            static_for<0, 4>([&](auto ee) { acc[4 * qi + decltype(ee)::value] += a * x[decltype(ee)::value]; });
+        });
+    });
+    const int ot = opr / p.h_ratio, ohq = kvh * p.h_ratio + (opr - ot * p.h_ratio);
+    const bool live = lsum > 0.f;
+    const float inv = live ? 1.0f / lsum : 0.f;
+    const float lse = live ? mrow * p.scale + logf(lsum) : (p.n_split > 1 ? -INFINITY : 0.f);
+    const int64_t R = ((int64_t)bidx * p.h + ohq) * p.seqlen_q + ot;
+    if (p.n_split == 1) {
+        char* orow = (char*)p.o_ptr + 2 * ((int64_t)bidx * p.o.batch + (int64_t)ot * p.o.row + (int64_t)ohq * p.o.head + col);
+        uint32_t w[CPT / 2];
+        static_for<0, CPT / 2>([&](auto jj) {
+            constexpr int j = decltype(jj)::value;
+            w[j] = LP<T>::pack2(acc[2 * j] * inv, acc[2 * j + 1] * inv);
+        });
+        if constexpr (CPT == 8) *(u32x4*)orow = u32x4{w[0], w[1], w[2], w[3]};
+        else *(u32x2*)orow = u32x2{w[0], w[1]};
+        if ((tid & 15) == 0) p.lse_ptr[R] = lse;
+    } else {
+        float* prow = p.ws_o + ((int64_t)split * p.rows_total + R) * D + col;
+        if (live) {
+            static_for<0, CPT / 4>([&](auto qq) {
+                constexpr int qi = decltype(qq)::value;
+                *(f32x4*)(prow + 4 * qi) = f32x4{acc[4 * qi] * inv, acc[4 * qi + 1] * inv, acc[4 * qi + 2] * inv, acc[4 * qi + 3] * inv};
+            });
+        }
+        if ((tid & 15) == 0) p.ws_lse[(int64_t)split * p.rows_total + R] = lse;
+    }
+}
+
+// One pass per output row over the splits, in split order (deterministic): O = sum_s exp(lse_s - M) O_s / sum_s exp(lse_s - M),
+// LSE = M + log(sum); splits with LSE = -inf saw no key of the row and are skipped (their O plane was never written); a row no split saw
+// is a dead row: O = 0, LSE = 0.
+template <typename T, int D>
+__global__ __launch_bounds__(kKvcCombineThreads) void fa_kvcache_combine_kernel(const KvcacheKernelParams p) {
+    constexpr int TPR = D / 8;                              // threads per row, 8 columns each
+    const int tid = threadIdx.x;
+    const int64_t R = (int64_t)blockIdx.x * (kKvcCombineThreads / TPR) + tid / TPR;
+    if (R >= p.rows_total) return;
+    const int col = (tid % TPR) * 8;
+    const int ns = p.n_split;
+    float M = -INFINITY;
+    for (int s = 0; s < ns; ++s) M = fmaxf(M, p.ws_lse[(int64_t)s * p.rows_total + R]);
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float sum = 0.f;
+    if (M != -INFINITY) {
+        for (int s = 0; s < ns; ++s) {
+            const float ls = p.ws_lse[(int64_t)s * p.rows_total + R];
+            if (ls == -INFINITY) continue;
+            const float w = __expf(ls - M);
+            sum += w;
+            const f32x4* src = (const f32x4*)(p.ws_o + ((int64_t)s * p.rows_total + R) * D + col);
+            const f32x4 x0 = src[0], x1 = src[1];
+            static_for<0, 4>([&](auto ee) {
+                constexpr int e = decltype(ee)::value;
+                acc[e] += w * x0[e];
+                acc[4 + e] += w * x1[e];
+            });
+        }
+    }
+    const float inv = sum > 0.f ? 1.0f / sum : 0.f;
+    const int t = (int)(R % p.seqlen_q);
+    const int64_t bhq = R / p.seqlen_q;
+    const int hq = (int)(bhq % p.h), bidx = (int)(bhq / p.h);
+    char* orow = (char*)p.o_ptr + 2 * ((int64_t)bidx * p.o.batch + (int64_t)t * p.o.row + (int64_t)hq * p.o.head + col);
+    *(u32x4*)orow = u32x4{LP<T>::pack2(acc[0] * inv, acc[1] * inv), LP<T>::pack2(acc[2] * inv, acc[3] * inv),
+                          LP<T>::pack2(acc[4] * inv, acc[5] * inv), LP<T>::pack2(acc[6] * inv, acc[7] * inv)};
+    if (tid % TPR == 0) p.lse_ptr[R] = sum > 0.f ? M + logf(sum) : 0.f;
+}
+
+// k_new / v_new (b, seqlen_new, h_k, d) -> cache rows cache_seqlens[i] .. + seqlen_new - 1; rows at or past seqlen_cache are dropped
+// (a caller that breaks the documented precondition loses the rows that do not fit, nothing is written outside the cache).
+template <int D>
+__global__ __launch_bounds__(256) void fa_kvcache_append_kernel(const KvcacheKernelParams p) {
+    constexpr int SLOTS = D / 8;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = (int64_t)p.b * p.seqlen_new * p.h_k * SLOTS;
+    if (i >= n) return;
+    const int slot = (int)(i % SLOTS);
+    int64_t r = i / SLOTS;
+    const int kvh = (int)(r % p.h_k);
+    r /= p.h_k;
+    const int t = (int)(r % p.seqlen_new);
+    const int bidx = (int)(r / p.seqlen_new);
+    const int cs = p.cache_seqlens[bidx];
+    const int row = (cs > 0 ? cs : 0) + t;
+    if (row >= p.seqlen_cache) return;
+    const u32x4 kx = *(const u32x4*)((const char*)p.k_new + 2 * ((int64_t)bidx * p.kn.batch + (int64_t)t * p.kn.row + (int64_t)kvh * p.kn.head + 8 * slot));
+    const u32x4 vx = *(const u32x4*)((const char*)p.v_new + 2 * ((int64_t)bidx * p.vn.batch + (int64_t)t * p.vn.row + (int64_t)kvh * p.vn.head + 8 * slot));
+    *(u32x4*)((char*)p.k_cache + 2 * ((int64_t)bidx * p.kc.batch + (int64_t)row * p.kc.row + (int64_t)kvh * p.kc.head + 8 * slot)) = kx;
+    *(u32x4*)((char*)p.v_cache + 2 * ((int64_t)bidx * p.vc.batch + (int64_t)row * p.vc.row + (int64_t)kvh * p.vc.head + 8 * slot)) = vx;
+}
+
+template <typename T, int D>
+hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s) {
+    if (kp.k_new != nullptr && kp.seqlen_new > 0) {
+        const int64_t n = (int64_t)kp.b * kp.seqlen_new * kp.h_k * (D / 8);
+        hipLaunchKernelGGL((fa_kvcache_append_kernel<D>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kp);
+    }
+    const int64_t grid = (int64_t)kp.b * kp.h_k * kp.n_row_tiles * kp.n_split;
+    if (kp.is_causal) hipLaunchKernelGGL((fa_fwd_kvcache_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+    else hipLaunchKernelGGL((fa_fwd_kvcache_kernel<T, D, false>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+    if (kp.n_split > 1) {
+        const int64_t rows_per_block = kKvcCombineThreads / (D / 8);
+        hipLaunchKernelGGL((fa_kvcache_combine_kernel<T, D>), dim3((unsigned)((kp.rows_total + rows_per_block - 1) / rows_per_block)),
+                           dim3(kKvcCombineThreads), 0, s, kp);
+    }
+    return hipGetLastError();
+}
+
+int64_t kvcache_steps(const KvcacheKernelParams& kp) { return ((int64_t)kp.seqlen_cache + kKvcStep - 1) / kKvcStep; }
+
+}  // namespace
+
+// Split count: the host knows the capacity, not the lengths (they live on the device), so the split is sized from seqlen_cache.  A launch
+// of b x h_k x row tiles workgroups that already brings one per compute unit is not split; otherwise the key range is split until the
+// launch holds two workgroups per unit (the occupancy of the attention kernel), keeping at least kKvcMinStepsPerSplit steps per split and
+// at most kKvcMaxSplits splits.  An explicit request overrides the rule (never more splits than 32-key steps); a workspace smaller than
+// the choice needs caps it (avail_bytes < 0: unlimited).
+int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_t requested) {
+    const int64_t steps = kvcache_steps(kp);
+    if (steps <= 1) return 1;
+    int64_t n;
+    if (requested > 0) {
+        n = requested < steps ? requested : steps;
+    } else {
+        const int64_t wgs = (int64_t)kp.b * kp.h_k * (((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
+        const int64_t cus = device_cu_count();
+        if (wgs <= 0 || wgs >= cus) return 1;
+        n = (2 * cus + wgs - 1) / wgs;
+        const int64_t cap = steps / kKvcMinStepsPerSplit;
+        if (n > cap) n = cap;
+        if (n > kKvcMaxSplits) n = kKvcMaxSplits;
+        if (n < 1) n = 1;
+    }
+    if (avail_bytes >= 0)
+        while (n > 1 && kvcache_workspace_bytes(kp, (int32_t)n) > avail_bytes) --n;
+    return (int32_t)n;
+}
+
+int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split) {
+    if (n_split <= 1) return 0;
+    const int64_t rows = (int64_t)kp.b * kp.h * kp.seqlen_q;
+    const int64_t o_bytes = (int64_t)n_split * rows * kp.d * 4;
+    const int64_t l_bytes = ((int64_t)n_split * rows * 4 + 15) / 16 * 16;
+    return o_bytes + l_bytes;
+}
+
+hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s) {
+    kp.n_row_tiles = (int32_t)(((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
+    kp.rows_total = (int64_t)kp.b * kp.h * kp.seqlen_q;
+    const int64_t steps = kvcache_steps(kp);
+    if (kp.n_split < 1) kp.n_split = 1;
+    kp.split_keys = (int32_t)(((steps + kp.n_split - 1) / kp.n_split) * kKvcStep);
+    if (kp.split_keys <= 0) kp.split_keys = kKvcStep;
+    if (kp.n_split > 1) {
+        kp.ws_lse = kp.ws_o + (int64_t)kp.n_split * kp.rows_total * kp.d;
+    }
+    if (dtype == 0) return kp.d == 64 ? launch_kvcache_t<_Float16, 64>(kp, s) : launch_kvcache_t<_Float16, 128>(kp, s);
+    return kp.d == 64 ? launch_kvcache_t<__bf16, 64>(kp, s) : launch_kvcache_t<__bf16, 128>(kp, s);
+}
+
+}  // namespace fa

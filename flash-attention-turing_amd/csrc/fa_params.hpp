@@ -115,6 +115,35 @@ inline uint32_t causal_group_heads(bool causal, int64_t compact_b, int64_t n_bh,
     return g <= 1 ? 0u : (uint32_t)(g < per_xcd ? g : per_xcd);
 }
 
+// Decode attention over a KV cache (fa_fwd_kvcache.hip, fa_run_mha_fwd_kvcache).  The seqlen_q x h_ratio query rows of one KV head are packed
+// into row tiles of kKvcRows; a workgroup serves one (batch, KV head, row tile, key split).
+struct KvcacheKernelParams {
+    const void* q_ptr;
+    void* k_cache;
+    void* v_cache;
+    const void* k_new;          // NULL: no append
+    const void* v_new;
+    void* o_ptr;
+    float* lse_ptr;             // (b, h, seqlen_q)
+    const int32_t* cache_seqlens;   // (b,) or NULL = every sequence is seqlen_cache long
+    TStride q, kc, vc, kn, vn, o;
+    int32_t b, seqlen_q, seqlen_cache, seqlen_new, h, h_k, h_ratio, d;
+    int32_t is_causal;
+    int32_t n_row_tiles;        // filled by the launcher
+    int32_t n_split;            // key splits (1: the attention kernel writes o / lse itself)
+    int32_t split_keys;         // keys per split, a multiple of kKvcStep
+    int64_t rows_total;         // b * h * seqlen_q: rows of the partial planes
+    float* ws_o;                // n_split x rows_total x d fp32 partial O (normalised), n_split > 1 only
+    float* ws_lse;              // n_split x rows_total partial LSE (natural log, -inf = no visible key in the split)
+    float scale_log2e;
+    float scale;
+};
+constexpr int kKvcRows = 16;    // packed query rows of a workgroup (one 16x16x32 MFMA tile)
+constexpr int kKvcStep = 32;    // keys of one wave step (the split granularity)
+int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_t requested);   // key splits of a launch (>= 1)
+int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split);
+hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t stream);
+
 // query-head group split chosen for a dK/dV launch (1 = none) and the workspace it needs
 int32_t dkdv_split(const BwdKernelParams& kp, int64_t avail_bytes);
 int64_t dkdv_workspace_bytes(const BwdKernelParams& kp, int32_t n_split);

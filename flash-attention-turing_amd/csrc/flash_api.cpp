@@ -261,6 +261,71 @@ std::vector<at::Tensor> mha_varlen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
     return {dq, dk, dv};
 }
 
+// Decode attention over a KV cache (upstream flash-attn's flash_attn_with_kvcache; the reference has no counterpart).  k_cache / v_cache are
+// used in place with their own strides (no copy: k_new / v_new are appended INTO them); cache_seqlens stays on the device (no host sync, the
+// call can be captured in a graph).  The split workspace comes from the caching allocator.
+std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, c10::optional<at::Tensor> k_new_,
+                                        c10::optional<at::Tensor> v_new_, c10::optional<at::Tensor> cache_seqlens_, bool is_causal,
+                                        int64_t num_splits) {
+    TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4, "q, k_cache, v_cache must be rank-4 tensors");
+    check_qkv_common(q, k_cache, v_cache);
+    const int64_t batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), head_size = q.size(3);
+    const int64_t seqlen_cache = k_cache.size(1), num_heads_k = k_cache.size(2);
+    TORCH_CHECK(seqlen_q >= 1, "seqlen_q must be >= 1");
+    TORCH_CHECK(k_cache.size(0) == batch_size && v_cache.size(0) == batch_size, "k_cache/v_cache batch size must match q");
+    TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "k_cache and v_cache must have the same shape");
+    TORCH_CHECK(k_cache.size(3) == head_size, "q/k_cache/v_cache head_dim must match");
+    TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "num_heads_q must be divisible by num_heads_k for GQA/MQA");
+    TORCH_CHECK(k_cache.stride(3) == 1 && v_cache.stride(3) == 1, "k_cache/v_cache: last dimension must be contiguous");
+    TORCH_CHECK(num_splits >= 0, "num_splits must be >= 0 (0 = automatic)");
+    TORCH_CHECK(k_new_.has_value() == v_new_.has_value(), "k and v must both be given or both be None");
+    at::Tensor k_new, v_new, cache_seqlens;
+    if (cache_seqlens_.has_value()) {
+        cache_seqlens = *cache_seqlens_;
+        check_same_device(q, cache_seqlens, "cache_seqlens");
+        TORCH_CHECK(cache_seqlens.scalar_type() == torch::kInt32, "cache_seqlens must be an int32 tensor");
+        TORCH_CHECK(cache_seqlens.dim() == 1 && cache_seqlens.size(0) == batch_size && cache_seqlens.is_contiguous(),
+                    "cache_seqlens must be a contiguous tensor of shape [batch_size]");
+    }
+    c10::DeviceGuard guard(q.device());
+    if (k_new_.has_value()) {
+        TORCH_CHECK(cache_seqlens.defined(), "cache_seqlens is required when k and v are appended");
+        k_new = *k_new_; v_new = *v_new_;
+        TORCH_CHECK(k_new.dim() == 4 && v_new.dim() == 4, "k and v must be rank-4 tensors");
+        check_same_device(q, k_new, "k"); check_same_device(q, v_new, "v");
+        TORCH_CHECK(k_new.scalar_type() == q.scalar_type() && v_new.scalar_type() == q.scalar_type(), "k and v must have the dtype of q");
+        TORCH_CHECK(k_new.size(0) == batch_size && k_new.size(2) == num_heads_k && k_new.size(3) == head_size && v_new.sizes() == k_new.sizes(),
+                    "k and v must have shape [batch_size, seqlen_new, num_heads_k, head_dim]");
+        TORCH_CHECK(k_new.size(1) <= seqlen_cache, "seqlen_new must not exceed the cache capacity");
+        k_new = dense_last(k_new); v_new = dense_last(v_new);
+    }
+    q = dense_last(q);
+    at::Tensor o = torch::empty(q.sizes(), q.options());
+    at::Tensor l = torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(torch::kFloat32));
+
+    fa_kvcache_params p;
+    FA_PARAMS_INIT(p);
+    p.q = q.data_ptr(); p.k_cache = k_cache.data_ptr(); p.v_cache = v_cache.data_ptr(); p.o = o.data_ptr(); p.lse = l.data_ptr<float>();
+    p.cache_seqlens = cache_seqlens.defined() ? cache_seqlens.data_ptr<int32_t>() : nullptr;
+    p.b = (int32_t)batch_size; p.seqlen_q = (int32_t)seqlen_q; p.seqlen_cache = (int32_t)seqlen_cache;
+    p.h = (int32_t)num_heads; p.h_k = (int32_t)num_heads_k; p.d = (int32_t)head_size;
+    p.dtype = fa_dtype_of(q); p.is_causal = is_causal; p.num_splits = (int32_t)num_splits;
+    p.q_stride = strides4(q); p.k_cache_stride = strides4(k_cache); p.v_cache_stride = strides4(v_cache); p.o_stride = strides4(o);
+    if (k_new.defined()) {
+        p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr(); p.seqlen_new = (int32_t)k_new.size(1);
+        p.k_new_stride = strides4(k_new); p.v_new_stride = strides4(v_new);
+    }
+    at::Tensor workspace;
+    const int64_t ws_bytes = fa_kvcache_workspace_bytes(&p);
+    if (ws_bytes < 0) check_status((int)ws_bytes);
+    if (ws_bytes > 0) {
+        workspace = torch::empty({ws_bytes / 4}, q.options().dtype(torch::kFloat32));
+        p.workspace = workspace.data_ptr(); p.workspace_bytes = ws_bytes;
+    }
+    check_status(fa_run_mha_fwd_kvcache(&p, current_stream(q)));
+    return {o, l};
+}
+
 // ---- autograd nodes in C++ ------------------------------------------------------------------------------------------------------
 // The reference ships the four raw functions only; its README's flash_attn_func is an older Python-level API.  The differentiable wrappers
 // of this package used to be torch.autograd.Function subclasses in Python: ~85 us of host time per forward + backward, more than the GPU
@@ -311,6 +376,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("bwd", &mha_bwd, "Backward pass");
     m.def("varlen_fwd", &mha_varlen_fwd, "Varlen forward pass");
     m.def("varlen_bwd", &mha_varlen_bwd, "Varlen backward pass");
+    m.def("fwd_kvcache", &mha_fwd_kvcache, "Decode forward over a KV cache (in-place append of k / v, split-KV attention)", py::arg("q"),
+          py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
+          py::arg("is_causal") = false, py::arg("num_splits") = 0);
     m.def("attn_autograd", &attn_autograd, "differentiable forward (C++ autograd node over fwd / bwd)");
     m.def("attn_varlen_autograd", &attn_varlen_autograd, "differentiable packed forward (C++ autograd node over varlen_fwd / varlen_bwd)");
     m.def("abi_version", []() { return fa_abi_version(); });

@@ -28,18 +28,19 @@ if not _os.path.exists(LIBRARY_PATH) or not _os.path.exists(EXTENSION_PATH):
 import torch as _torch  # noqa: E402,F401  (libtorch must be loaded before _C)
 
 from . import _C  # noqa: E402
-from ._C import fwd, bwd, varlen_fwd, varlen_bwd  # noqa: E402,F401
+from ._C import fwd, bwd, varlen_fwd, varlen_bwd, fwd_kvcache  # noqa: E402,F401
 from .interface import (  # noqa: E402,F401
     flash_attn_func,
     flash_attn_varlen_func,
+    flash_attn_with_kvcache,
     FlashAttnFunc,
     FlashAttnVarlenFunc,
 )
 from .sharding import ShardPlan, plan_shards, shard_tensor, problem_policy  # noqa: E402,F401
 
 __all__ = [
-    "fwd", "bwd", "varlen_fwd", "varlen_bwd",
-    "flash_attn_func", "flash_attn_varlen_func", "FlashAttnFunc", "FlashAttnVarlenFunc",
+    "fwd", "bwd", "varlen_fwd", "varlen_bwd", "fwd_kvcache",
+    "flash_attn_func", "flash_attn_varlen_func", "flash_attn_with_kvcache", "FlashAttnFunc", "FlashAttnVarlenFunc",
     "ShardPlan", "plan_shards", "shard_tensor", "problem_policy", "LIBRARY_PATH", "EXTENSION_PATH",
     "set_kernel_policy", "kernel_name",
 ]

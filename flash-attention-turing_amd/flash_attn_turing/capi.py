@@ -66,6 +66,16 @@ class BwdParams(_Params):
                 ("workspace", _vp), ("workspace_bytes", ctypes.c_int64)]
 
 
+class KvcacheParams(_Params):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("q", _vp), ("k_cache", _vp), ("v_cache", _vp), ("k_new", _vp), ("v_new", _vp),
+                ("o", _vp), ("lse", _vp), ("cache_seqlens", _vp),
+                ("b", _i32), ("seqlen_q", _i32), ("seqlen_cache", _i32), ("seqlen_new", _i32), ("h", _i32), ("h_k", _i32), ("d", _i32),
+                ("dtype", _i32), ("is_causal", _i32), ("num_splits", _i32),
+                ("q_stride", Strides), ("k_cache_stride", Strides), ("v_cache_stride", Strides), ("k_new_stride", Strides), ("v_new_stride", Strides),
+                ("o_stride", Strides),
+                ("workspace", _vp), ("workspace_bytes", ctypes.c_int64)]
+
+
 _lib = None
 
 
@@ -96,6 +106,12 @@ def lib():
         L.fa_bwd_dkdv.argtypes = [ctypes.POINTER(BwdParams), _vp]
         L.fa_bwd_workspace_bytes.argtypes = [ctypes.POINTER(BwdParams)]
         L.fa_bwd_workspace_bytes.restype = ctypes.c_int64
+        L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(KvcacheParams), _vp]
+        L.fa_run_mha_fwd_kvcache.restype = ctypes.c_int
+        L.fa_kvcache_workspace_bytes.argtypes = [ctypes.POINTER(KvcacheParams)]
+        L.fa_kvcache_workspace_bytes.restype = ctypes.c_int64
+        L.fa_kvcache_num_splits.argtypes = [ctypes.POINTER(KvcacheParams)]
+        L.fa_kvcache_num_splits.restype = ctypes.c_int32
         L.fa_mha_fwd.argtypes = [_vp] * 5 + [_i32] * 8 + [_vp]
         L.fa_mha_bwd.argtypes = [_vp] * 10 + [_i32] * 8 + [_vp]
         L.fa_mha_varlen_fwd.argtypes = [_vp] * 7 + [_i32] * 8 + [_vp]
@@ -269,3 +285,43 @@ def run_fwd(params, stream=None):
 
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     check(lib().fa_run_mha_fwd(ctypes.byref(params), s))
+
+
+def kvcache_params(q, k_cache, v_cache, o, lse, cache_seqlens=None, k_new=None, v_new=None, causal=False, num_splits=0):
+    """fa_kvcache_params for (b, s, h, d) torch tensors with arbitrary batch / row / head strides (caches may be views of larger buffers)"""
+    b, sq, h, d = q.shape
+    p = KvcacheParams()
+    p.q, p.k_cache, p.v_cache, p.o, p.lse = (t.data_ptr() for t in (q, k_cache, v_cache, o, lse))
+    p.cache_seqlens = None if cache_seqlens is None else cache_seqlens.data_ptr()
+    p.b, p.seqlen_q, p.seqlen_cache, p.h, p.h_k, p.d = b, sq, k_cache.shape[1], h, k_cache.shape[2], d
+    p.dtype, p.is_causal, p.num_splits = dtype_code(q.dtype), int(causal), int(num_splits)
+    tensors = [("q_stride", q), ("k_cache_stride", k_cache), ("v_cache_stride", v_cache), ("o_stride", o)]
+    if k_new is not None:
+        p.k_new, p.v_new, p.seqlen_new = k_new.data_ptr(), v_new.data_ptr(), k_new.shape[1]
+        tensors += [("k_new_stride", k_new), ("v_new_stride", v_new)]
+    for name, t in tensors:
+        setattr(p, name, Strides(t.stride(0), t.stride(1), t.stride(2)))
+    return p
+
+
+def kvcache_workspace_bytes(params) -> int:
+    """fa_kvcache_workspace_bytes: fp32 scratch the split the library would choose needs (0: one split)"""
+    n = lib().fa_kvcache_workspace_bytes(ctypes.byref(params))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def kvcache_num_splits(params) -> int:
+    """fa_kvcache_num_splits: key splits the launch of these params would use (their workspace fields included)"""
+    n = lib().fa_kvcache_num_splits(ctypes.byref(params))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def run_fwd_kvcache(params, stream=None):
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    check(lib().fa_run_mha_fwd_kvcache(ctypes.byref(params), s))

@@ -72,3 +72,24 @@ def flash_attn_func(q, k, v, *legacy_dims, causal=False, return_lse=False):
 
 def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, causal=False):
     return _C.attn_varlen_autograd(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), bool(causal))
+
+
+def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, causal=False, num_splits=0, return_softmax_lse=False):
+    """Decode attention over a KV cache (upstream flash-attn's ``flash_attn_with_kvcache`` conventions; forward only).
+
+    q: (batch, seqlen_q, nheads, d); k_cache, v_cache: (batch, seqlen_cache, nheads_k, d), any batch / row / head strides (used in place).
+    cache_seqlens: int32 tensor (batch,) on q's device, a Python int (broadcast), or None (every sequence is seqlen_cache long).
+    k, v (optional, both or neither): (batch, seqlen_new, nheads_k, d), written INTO the caches at rows cache_seqlens[i] ..
+    cache_seqlens[i] + seqlen_new - 1 before attention runs over the first cache_seqlens[i] + seqlen_new keys; cache_seqlens is not
+    updated (the caller advances it).  causal masks key j for query t when j > L_i - seqlen_q + t.  Scale is 1/sqrt(d).
+    num_splits: 0 = chosen by the library, > 0 forces the key split.  Returns out (like q), and lse (batch, nheads, seqlen_q) fp32 if
+    ``return_softmax_lse``.  Precondition: cache_seqlens[i] + seqlen_new <= seqlen_cache.
+    """
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v)):
+        raise RuntimeError("flash_attn_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
+    if (k is None) != (v is None):
+        raise ValueError("k and v must both be given or both be None")
+    if isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=q.device)
+    out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits))
+    return (out, lse) if return_softmax_lse else out

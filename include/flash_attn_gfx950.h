@@ -145,6 +145,47 @@ typedef struct fa_bwd_params {
     int64_t workspace_bytes;
 } fa_bwd_params;
 
+/* Decode attention over a KV cache (flash-attn's flash_attn_with_kvcache conventions; no counterpart in the reference).  Same ABI 4 header
+ * rule as the structs above (FA_PARAMS_INIT); fields appended later will be optional.  The presence of fa_run_mha_fwd_kvcache is how a caller
+ * detects the feature (FA_ABI_VERSION is unchanged).
+ *   q (b, seqlen_q, h, d), seqlen_q >= 1; k_cache / v_cache (b, seqlen_cache, h_k, d), each with its own strides;
+ *   cache_seqlens: int32 DEVICE array (b,), or NULL = every sequence is seqlen_cache long;
+ *   k_new / v_new (b, seqlen_new, h_k, d), both or neither: written IN PLACE into the cache at rows cache_seqlens[i] .. + seqlen_new - 1
+ *   (cache_seqlens is required then and is not updated), after which attention runs over the first L_i = cache_seqlens[i] + seqlen_new
+ *   keys; without them over L_i = cache_seqlens[i].  causal masks key j for query t when j > L_i - seqlen_q + t.
+ *   o like q, lse (b, h, seqlen_q) fp32 natural log; rows with no visible key: o = 0, lse = 0.
+ * Precondition (like max_seqlen for varlen, the library cannot check device values without synchronising): cache_seqlens[i] + seqlen_new
+ * <= seqlen_cache.  Broken, nothing is read or written outside the cache: lengths are clamped to seqlen_cache and appended rows that do not
+ * fit are dropped.  No host synchronisation: the call can be captured in a graph and replayed with new cache_seqlens values.
+ * workspace: fp32 scratch for the key split (fa_kvcache_workspace_bytes), 16-byte aligned; a smaller buffer caps the split, none (NULL / 0)
+ * means one split.  num_splits > 0 overrides the library's choice (capped by the 32-key tiles of seqlen_cache and by the workspace).
+ * Results are deterministic for a given split count. */
+typedef struct fa_kvcache_params {
+    uint32_t struct_size;       /* sizeof(fa_kvcache_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const void* q;
+    void* k_cache;
+    void* v_cache;
+    const void* k_new;          /* NULL: no append */
+    const void* v_new;
+    void* o;
+    float* lse;
+    const int32_t* cache_seqlens;
+    int32_t b;
+    int32_t seqlen_q;
+    int32_t seqlen_cache;
+    int32_t seqlen_new;         /* rows of k_new / v_new (0 without them) */
+    int32_t h;
+    int32_t h_k;
+    int32_t d;
+    int32_t dtype;
+    int32_t is_causal;
+    int32_t num_splits;         /* 0 = the library's choice */
+    fa_strides q_stride, k_cache_stride, v_cache_stride, k_new_stride, v_new_stride, o_stride;
+    void* workspace;
+    int64_t workspace_bytes;
+} fa_kvcache_params;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -193,6 +234,16 @@ int fa_bwd_dkdv(const fa_bwd_params* params, void* stream);
  * `workspace_bytes` fields of the argument are ignored (a stale or unaligned pointer left in a reused struct is not an error here).
  * Host-only arithmetic; the split target follows the CU count of the current device (256 when there is none).  Negative = error code. */
 int64_t fa_bwd_workspace_bytes(const fa_bwd_params* params);
+
+/* ---- decode over a KV cache (fa_kvcache_params above) ----------------------------------------- */
+/* Append (if k_new / v_new), split-KV attention, and the combine of the splits: up to three launches on `stream`, no host synchronisation. */
+int fa_run_mha_fwd_kvcache(const fa_kvcache_params* params, void* stream);
+/* Bytes of workspace the launch would use with the split the library chooses (or num_splits, if set); 0 = one split.  The `workspace` /
+ * `workspace_bytes` fields are ignored.  Host-only arithmetic; the split target follows the CU count of the current device (256 without one).
+ * Negative = error code. */
+int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* params);
+/* Key splits the launch of these params would use, workspace fields included (NULL / 0 -> 1).  Host-only.  Negative = error code. */
+int32_t fa_kvcache_num_splits(const fa_kvcache_params* params);
 
 /* ---- measurement helpers ----------------------------------------------------------------- */
 /* Algorithmic FLOPs of one forward call (4*b*h*sq*sk*d, causal counts only visible pairs);
