@@ -238,7 +238,9 @@ __global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_kernel(const Kv
         });
     });
     const int ot = opr / p.h_ratio, ohq = kvh * p.h_ratio + (opr - ot * p.h_ratio);
-    const bool live = lsum > 0.f;
+    // dead = saw no key (lsum == 0); a NaN or +inf score leaves lsum = NaN, which is live: O and LSE come out NaN as in fp32 math, and a
+    // split partial is written so that the combine propagates it
+    const bool live = !(lsum == 0.f);
     const float inv = live ? 1.0f / lsum : 0.f;
     const float lse = live ? mrow * p.scale + logf(lsum) : (p.n_split > 1 ? -INFINITY : 0.f);
     const int64_t R = ((int64_t)bidx * p.h + ohq) * p.seqlen_q + ot;
@@ -266,7 +268,8 @@ __global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_kernel(const Kv
 
 // One pass per output row over the splits, in split order (deterministic): O = sum_s exp(lse_s - M) O_s / sum_s exp(lse_s - M),
 // LSE = M + log(sum); splits with LSE = -inf saw no key of the row and are skipped (their O plane was never written); a row no split saw
-// is a dead row: O = 0, LSE = 0.
+// is a dead row: O = 0, LSE = 0.  A NaN partial (a NaN or +inf score in its split; its O plane is written) makes the row NaN, O and LSE,
+// as one pass over all keys would: fmaxf drops NaN from M, so it is tracked on the side.
 template <typename T, int D>
 __global__ __launch_bounds__(kKvcCombineThreads) void fa_kvcache_combine_kernel(const KvcacheKernelParams p) {
     constexpr int TPR = D / 8;                              // threads per row, 8 columns each
@@ -276,7 +279,12 @@ __global__ __launch_bounds__(kKvcCombineThreads) void fa_kvcache_combine_kernel(
     const int col = (tid % TPR) * 8;
     const int ns = p.n_split;
     float M = -INFINITY;
-    for (int s = 0; s < ns; ++s) M = fmaxf(M, p.ws_lse[(int64_t)s * p.rows_total + R]);
+    bool nan_part = false;
+    for (int s = 0; s < ns; ++s) {
+        const float ls = p.ws_lse[(int64_t)s * p.rows_total + R];
+        nan_part |= __builtin_isnan(ls);
+        M = fmaxf(M, ls);
+    }
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float sum = 0.f;
     if (M != -INFINITY) {
@@ -294,14 +302,16 @@ __global__ __launch_bounds__(kKvcCombineThreads) void fa_kvcache_combine_kernel(
             });
         }
     }
-    const float inv = sum > 0.f ? 1.0f / sum : 0.f;
+    if (nan_part) sum = __builtin_nanf("");
+    const bool live = !(sum == 0.f);
+    const float inv = live ? 1.0f / sum : 0.f;
     const int t = (int)(R % p.seqlen_q);
     const int64_t bhq = R / p.seqlen_q;
     const int hq = (int)(bhq % p.h), bidx = (int)(bhq / p.h);
     char* orow = (char*)p.o_ptr + 2 * ((int64_t)bidx * p.o.batch + (int64_t)t * p.o.row + (int64_t)hq * p.o.head + col);
     *(u32x4*)orow = u32x4{LP<T>::pack2(acc[0] * inv, acc[1] * inv), LP<T>::pack2(acc[2] * inv, acc[3] * inv),
                           LP<T>::pack2(acc[4] * inv, acc[5] * inv), LP<T>::pack2(acc[6] * inv, acc[7] * inv)};
-    if (tid % TPR == 0) p.lse_ptr[R] = sum > 0.f ? M + logf(sum) : 0.f;
+    if (tid % TPR == 0) p.lse_ptr[R] = live ? M + logf(sum) : 0.f;
 }
 
 // k_new / v_new (b, seqlen_new, h_k, d) -> cache rows cache_seqlens[i] .. + seqlen_new - 1; rows at or past seqlen_cache are dropped

@@ -84,6 +84,9 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     updated (the caller advances it).  causal masks key j for query t when j > L_i - seqlen_q + t.  Scale is 1/sqrt(d).
     num_splits: 0 = chosen by the library, > 0 forces the key split.  Returns out (like q), and lse (batch, nheads, seqlen_q) fp32 if
     ``return_softmax_lse``.  Precondition: cache_seqlens[i] + seqlen_new <= seqlen_cache.
+    Non-finite inputs follow fp32 math over the valid prefix, for every num_splits: a NaN query row, or a NaN / +inf score from a visible K row,
+    gives NaN in that row's O and LSE; a row that sees no key is O = 0, LSE = 0.  Cache rows at or past L_i and heads the
+    cache views skip are never read into a result.
     """
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v)):
         raise RuntimeError("flash_attn_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")

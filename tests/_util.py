@@ -188,6 +188,25 @@ def assert_close(x, ref, dtype, name, scale=1.0, sk=None, oracle=None, exact=Non
     return raw
 
 
+
+def check_kvcache_rows(out, lse, q, k_cache, v_cache, lens, causal, dtname, tag, scale=1.0):
+    """decode over a KV cache: every batch entry against the C oracle (the reference's rounding points) on its valid prefix k_cache[i, :L_i];
+    the relative metric against exact fp64 math for kernel and oracle alike (assert_close).  An empty entry must be exactly O = 0, LSE = 0."""
+    import torch
+    from oracle import attn_oracle as A
+
+    mode = A.ROUND_FP16 if dtname == "fp16" else A.ROUND_BF16
+    for i, L in enumerate(lens):
+        if L == 0:
+            assert (out[i] == 0).all().item() and (lse[i] == 0).all().item(), f"{tag}: empty sequence {i} must give O = 0, LSE = 0"
+            continue
+        qi, ki, vi = (t.detach().double().cpu().numpy() for t in (q[i:i + 1], k_cache[i:i + 1, :L], v_cache[i:i + 1, :L]))
+        o_ref, lse_ref = A.attn_fwd(qi, ki, vi, causal=causal, round_mode=mode)
+        xo, _ = torch_attention_ref(q[i:i + 1], k_cache[i:i + 1, :L], v_cache[i:i + 1, :L], causal=causal, device="cpu", dtype=torch.float64)
+        assert_close(out[i:i + 1].float().cpu().numpy(), o_ref, dtname, f"kvcache O {tag} b{i} L{L}", scale=scale, sk=L, oracle=o_ref, exact=xo.numpy())
+        err = float(np.abs(lse[i:i + 1].cpu().numpy() - lse_ref).max())
+        assert err <= LSE_TOL, f"{tag}: LSE b{i} L{L} err {err}"
+
 def golden_names(varlen=None):
     names = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz")))
     if varlen is True:

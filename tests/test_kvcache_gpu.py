@@ -4,7 +4,6 @@ Expectations: the fp32 PyTorch statement of the contract (_util.torch_attention_
 with _util.assert_close (the repo's tolerance rules).  Dead rows (no visible key) must be exactly O = 0, LSE = 0."""
 import statistics
 
-import numpy as np
 import pytest
 import torch
 
@@ -21,22 +20,7 @@ def _rand(shape, dt, gen, dev):
     return torch.randn(*shape, device=dev, dtype=torch.float32, generator=gen).to(dt)
 
 
-def _check_rows(out, lse, q, k_cache, v_cache, lens, causal, dtname, tag):
-    """every batch entry against the C oracle (the reference's rounding points) on its valid prefix k_cache[i, :L_i]; the relative metric
-    against exact fp64 math for kernel and oracle alike (tests/_util.py:assert_close)"""
-    from oracle import attn_oracle as A
-
-    mode = A.ROUND_FP16 if dtname == "fp16" else A.ROUND_BF16
-    for i, L in enumerate(lens):
-        if L == 0:
-            assert (out[i] == 0).all().item() and (lse[i] == 0).all().item(), f"{tag}: empty sequence {i} must give O = 0, LSE = 0"
-            continue
-        qi, ki, vi = (t.detach().double().cpu().numpy() for t in (q[i:i + 1], k_cache[i:i + 1, :L], v_cache[i:i + 1, :L]))
-        o_ref, lse_ref = A.attn_fwd(qi, ki, vi, causal=causal, round_mode=mode)
-        xo, _ = U.torch_attention_ref(q[i:i + 1], k_cache[i:i + 1, :L], v_cache[i:i + 1, :L], causal=causal, device="cpu", dtype=torch.float64)
-        U.assert_close(out[i:i + 1].float().cpu().numpy(), o_ref, dtname, f"kvcache O {tag} b{i} L{L}", sk=L, oracle=o_ref, exact=xo.numpy())
-        err = float(np.abs(lse[i:i + 1].cpu().numpy() - lse_ref).max())
-        assert err <= U.LSE_TOL, f"{tag}: LSE b{i} L{L} err {err}"
+_check_rows = U.check_kvcache_rows
 
 
 @pytest.mark.parametrize("dtname", ["fp16", "bf16"])
