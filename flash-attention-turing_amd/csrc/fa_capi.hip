@@ -333,13 +333,29 @@ int fa_mha_varlen_bwd(const void* q, const void* k, const void* v, const void* o
 
 // with_workspace = false: the `workspace` fields are not looked at (fa_kvcache_workspace_bytes)
 static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& kp, fa_kvcache_params& local, bool with_workspace) {
-    int rc = import_params(user, local, "fa_kvcache_params", sizeof(fa_kvcache_params));
+    // the paged-cache fields are optional: a caller built before them passes struct_size = offsetof(block_table) and gets NULL / 0
+    int rc = import_params(user, local, "fa_kvcache_params", offsetof(fa_kvcache_params, block_table));
     if (rc) return rc;
     const fa_kvcache_params* p = &local;
+    const bool paged = p->block_table != nullptr;
     if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0 || p->seqlen_new < 0 || p->h <= 0 || p->h_k <= 0)
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d seqlen_new=%d h=%d h_k=%d", p->b, p->seqlen_q, p->seqlen_cache,
                     p->seqlen_new, p->h, p->h_k);
     if ((rc = check_common(p->b, p->seqlen_q, p->seqlen_cache, p->h, p->h_k, p->d, p->dtype))) return rc;
+    if (paged) {
+        const int P = p->page_block_size;
+        if (P == 0) return fail(FA_ERR_BAD_SHAPE, "block_table given without page_block_size");
+        if (P < 0 || P % 16 != 0) return fail(FA_ERR_BAD_SHAPE, "page_block_size %d must be a positive multiple of 16", P);
+        if (p->num_blocks < 1) return fail(FA_ERR_BAD_SHAPE, "num_blocks %d: a paged cache needs at least one page", p->num_blocks);
+        if (p->seqlen_cache <= 0 || p->seqlen_cache % P != 0)
+            return fail(FA_ERR_BAD_SHAPE, "seqlen_cache (%d) must be a positive multiple of page_block_size (%d) with block_table", p->seqlen_cache, P);
+        if (p->block_table_stride < p->seqlen_cache / P)
+            return fail(FA_ERR_BAD_STRIDE, "block_table_stride %lld is below the table's %d columns (seqlen_cache / page_block_size)",
+                        (long long)p->block_table_stride, p->seqlen_cache / P);
+        if ((reinterpret_cast<uintptr_t>(p->block_table) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "block_table must be 4-byte aligned");
+    } else if (p->page_block_size != 0) {
+        return fail(FA_ERR_NULL_POINTER, "page_block_size = %d given without block_table", p->page_block_size);
+    }
     if (p->seqlen_new > p->seqlen_cache)
         return fail(FA_ERR_BAD_SHAPE, "seqlen_new (%d) exceeds the cache capacity seqlen_cache (%d)", p->seqlen_new, p->seqlen_cache);
     if ((p->k_new == nullptr) != (p->v_new == nullptr)) return fail(FA_ERR_NULL_POINTER, "k_new and v_new must both be given or both be NULL");
@@ -354,8 +370,10 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
         if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
         if ((rc = check_tensor("q", p->q, p->q_stride, p->seqlen_q, p->d, false))) return rc;
         if ((rc = check_tensor("o", p->o, p->o_stride, p->seqlen_q, p->d, false))) return rc;
-        if ((rc = check_tensor("k_cache", p->k_cache, p->k_cache_stride, p->seqlen_cache, p->d, false))) return rc;
-        if ((rc = check_tensor("v_cache", p->v_cache, p->v_cache_stride, p->seqlen_cache, p->d, false))) return rc;
+        // paged: the descriptors span at most one page, so the 2^31-byte limit applies per page (page offsets are 64-bit)
+        const int64_t cache_rows = paged ? p->page_block_size : p->seqlen_cache;
+        if ((rc = check_tensor("k_cache", p->k_cache, p->k_cache_stride, cache_rows, p->d, false))) return rc;
+        if ((rc = check_tensor("v_cache", p->v_cache, p->v_cache_stride, cache_rows, p->d, false))) return rc;
         if (p->k_new != nullptr) {
             if ((rc = check_tensor("k_new", p->k_new, p->k_new_stride, p->seqlen_new, p->d, false))) return rc;
             if ((rc = check_tensor("v_new", p->v_new, p->v_new_stride, p->seqlen_new, p->d, false))) return rc;
@@ -371,6 +389,10 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
     kp.is_causal = p->is_causal ? 1 : 0;
     kp.scale = 1.0f / sqrtf((float)p->d);
     kp.scale_log2e = kp.scale * 1.4426950408889634f;
+    if (paged) {
+        kp.block_table = p->block_table; kp.bt_stride = p->block_table_stride;
+        kp.page_size = p->page_block_size; kp.num_blocks = p->num_blocks;
+    }
     return FA_OK;
 }
 

@@ -51,8 +51,9 @@ FA_DEV int kvc_len(const KvcacheKernelParams& p, int bidx) {
     return __builtin_amdgcn_readfirstlane(L);
 }
 
-template <typename T, int D, bool CAUSAL>
-__global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_kernel(const KvcacheKernelParams p) {
+// The attention body of both cache layouts; PAGED changes how K / V rows are addressed (load_step), nothing else.
+template <typename T, int D, bool CAUSAL, bool PAGED>
+FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
     constexpr int NC = D / 32;          // 16x16x32 MFMAs per 16 keys of S^T (d chunks)
     constexpr int NO = D / 16;          // O^T blocks of 16 columns
     constexpr int SLOTS = D / 8;        // 16-byte slots per row
@@ -101,25 +102,84 @@ __global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_kernel(const Kv
 
     // ---- K / V of this (batch, KV head): descriptors end at row L ------------------------------------------------------------------
     const uint32_t krow_b = (uint32_t)(p.kc.row * 2), vrow_b = (uint32_t)(p.vc.row * 2);
-    const char* kbase = uniform_ptr((const char*)p.k_cache + 2 * ((int64_t)bidx * p.kc.batch + (int64_t)kvh * p.kc.head));
-    const char* vbase = uniform_ptr((const char*)p.v_cache + 2 * ((int64_t)bidx * p.vc.batch + (int64_t)kvh * p.vc.head));
+    const char* kbase = uniform_ptr((const char*)p.k_cache + 2 * ((int64_t)(PAGED ? 0 : bidx) * p.kc.batch + (int64_t)kvh * p.kc.head));
+    const char* vbase = uniform_ptr((const char*)p.v_cache + 2 * ((int64_t)(PAGED ? 0 : bidx) * p.vc.batch + (int64_t)kvh * p.vc.head));
     const rsrc_t krs = make_rsrc(kbase, L > 0 ? (uint32_t)(L - 1) * krow_b + 2 * D : 0u);
     const rsrc_t vrs = make_rsrc(vbase, L > 0 ? (uint32_t)(L - 1) * vrow_b + 2 * D : 0u);
+    // Paged cache: a step's two 16-key blocks each lie in one page (page_size is a multiple of 16).  Every block gets its own descriptors,
+    // based at the block's first row in its page and ending at the sequence's last valid row in the block (rows at or past L read as
+    // zeros, as above; a block wholly past L has an empty range, so whatever its table entry says is never read).  The table entries of
+    // the step after the one being loaded are fetched (scalar loads) together with that load, one compute step before they are needed;
+    // the fetch cursor (column, row in page) moves by the wave stride without a division.  Columns are clamped to the table row,
+    // entries to the pool: min((uint32_t)entry, num_blocks - 1).  Page offsets are 64-bit; in-page offsets < 2^31 by the host checks.
+    const int P = p.page_size;
+    // (read through the constant address space: the table is not written while the kernel runs, and so the compiler issues scalar loads
+    // that only a later lgkmcnt wait depends on; as a plain global pointer it gets vector loads that wait behind the K / V loads in flight)
+    typedef const __attribute__((address_space(4))) int32_t* const_i32_ptr;
+    const const_i32_ptr tbl = PAGED ? (const_i32_ptr)(p.block_table + (int64_t)bidx * p.bt_stride) : nullptr;
+    const int last_col = PAGED ? p.seqlen_cache / P - 1 : 0;
+    uint32_t pg[2] = {0u, 0u};                  // table entries (unclamped: consumed by the next load_step) of the next step's blocks
+    int rw[2] = {0, 0};                         // ... and the blocks' first rows in their pages
+    int f_col = 0, f_row = 0, st_col = 0, st_row = 0;
+    auto fetch_pages = [&]() __attribute__((always_inline)) {
+        int c1 = f_col, r1 = f_row + 16;
+        if (r1 >= P) { r1 -= P; c1 += 1; }
+        pg[0] = (uint32_t)tbl[min(f_col, last_col)]; rw[0] = f_row;
+        pg[1] = (uint32_t)tbl[min(c1, last_col)]; rw[1] = r1;
+        f_col += st_col; f_row += st_row;
+        if (f_row >= P) { f_row -= P; f_col += 1; }
+    };
+    if constexpr (PAGED) {
+        const int key_first = __builtin_amdgcn_readfirstlane(k_begin + wave * kKvcStep);
+        f_col = __builtin_amdgcn_readfirstlane(key_first / P);
+        f_row = key_first - f_col * P;
+        st_col = __builtin_amdgcn_readfirstlane(kKvcWaves * kKvcStep / P);
+        st_row = kKvcWaves * kKvcStep - st_col * P;
+        fetch_pages();
+    }
     // (row indices are clamped to L: a row at L is past the descriptor's range, and (L) x row stride < 2^31 by the host checks)
     auto load_step = [&](int key0, u32x4 (&kf)[2][NC], u32x4 (&vf)[NV]) __attribute__((always_inline)) {
-        static_for<0, 2>([&](auto kb) {
-            constexpr int b = decltype(kb)::value;
-            const uint32_t off = (uint32_t)min(key0 + 16 * b + n16, L) * krow_b + 2 * 8 * g;
-            static_for<0, NC>([&](auto cc) {
-                constexpr int ci = decltype(cc)::value;
-                kf[b][ci] = buf_load16(krs, off + 2 * 32 * ci);
+        if constexpr (PAGED) {
+            rsrc_t kr[2], vr[2];
+            static_for<0, 2>([&](auto kb) {
+                constexpr int b = decltype(kb)::value;
+                const int valid = min(max(L - (key0 + 16 * b), 0), 16);
+                const int64_t page = min(pg[b], (uint32_t)(p.num_blocks - 1));
+                const int64_t pk = page * p.kc.batch + (int64_t)rw[b] * p.kc.row;
+                const int64_t pv = page * p.vc.batch + (int64_t)rw[b] * p.vc.row;
+                kr[b] = make_rsrc(uniform_ptr(kbase + 2 * pk), valid > 0 ? (uint32_t)(valid - 1) * krow_b + 2 * D : 0u);
+                vr[b] = make_rsrc(uniform_ptr(vbase + 2 * pv), valid > 0 ? (uint32_t)(valid - 1) * vrow_b + 2 * D : 0u);
             });
-        });
-        static_for<0, NV>([&](auto iv) {
-            constexpr int i = decltype(iv)::value;
-            const uint32_t off = (uint32_t)min(key0 + i * VRPL + lane / SLOTS, L) * vrow_b + 16 * (lane % SLOTS);
-            vf[i] = buf_load16(vrs, off);
-        });
+            static_for<0, 2>([&](auto kb) {
+                constexpr int b = decltype(kb)::value;
+                const uint32_t off = (uint32_t)n16 * krow_b + 2 * 8 * g;
+                static_for<0, NC>([&](auto cc) {
+                    constexpr int ci = decltype(cc)::value;
+                    kf[b][ci] = buf_load16(kr[b], off + 2 * 32 * ci);
+                });
+            });
+            static_for<0, NV>([&](auto iv) {
+                constexpr int i = decltype(iv)::value;
+                constexpr int b = (i * VRPL) / 16;
+                const uint32_t off = (uint32_t)((i * VRPL) % 16 + lane / SLOTS) * vrow_b + 16 * (lane % SLOTS);
+                vf[i] = buf_load16(vr[b], off);
+            });
+            fetch_pages();                          // the table entries of the step after this one
+        } else {
+            static_for<0, 2>([&](auto kb) {
+                constexpr int b = decltype(kb)::value;
+                const uint32_t off = (uint32_t)min(key0 + 16 * b + n16, L) * krow_b + 2 * 8 * g;
+                static_for<0, NC>([&](auto cc) {
+                    constexpr int ci = decltype(cc)::value;
+                    kf[b][ci] = buf_load16(krs, off + 2 * 32 * ci);
+                });
+            });
+            static_for<0, NV>([&](auto iv) {
+                constexpr int i = decltype(iv)::value;
+                const uint32_t off = (uint32_t)min(key0 + i * VRPL + lane / SLOTS, L) * vrow_b + 16 * (lane % SLOTS);
+                vf[i] = buf_load16(vrs, off);
+            });
+        }
     };
 
     FA_LDS char* vstage = (FA_LDS char*)smem + wave * KvcLds<D>::kVStage;
@@ -266,6 +326,16 @@ __global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_kernel(const Kv
     }
 }
 
+template <typename T, int D, bool CAUSAL>
+__global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_kernel(const KvcacheKernelParams p) {
+    kvcache_attn<T, D, CAUSAL, false>(p);
+}
+
+template <typename T, int D, bool CAUSAL>
+__global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_paged_kernel(const KvcacheKernelParams p) {
+    kvcache_attn<T, D, CAUSAL, true>(p);
+}
+
 // One pass per output row over the splits, in split order (deterministic): O = sum_s exp(lse_s - M) O_s / sum_s exp(lse_s - M),
 // LSE = M + log(sum); splits with LSE = -inf saw no key of the row and are skipped (their O plane was never written); a row no split saw
 // is a dead row: O = 0, LSE = 0.  A NaN partial (a NaN or +inf score in its split; its O plane is written) makes the row NaN, O and LSE,
@@ -337,15 +407,48 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_kernel(const KvcacheKer
     *(u32x4*)((char*)p.v_cache + 2 * ((int64_t)bidx * p.vc.batch + (int64_t)row * p.vc.row + (int64_t)kvh * p.vc.head + 8 * slot)) = vx;
 }
 
+// The same through the block table of a paged cache: row cache_seqlens[i] + t is row (.) % page_size of page
+// min((uint32_t)block_table[i][(.) / page_size], num_blocks - 1); rows at or past the capacity seqlen_cache are dropped, so the column
+// read is always inside the table row, and whatever a needed entry holds, nothing is written outside the pool.
+template <int D>
+__global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(const KvcacheKernelParams p) {
+    constexpr int SLOTS = D / 8;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = (int64_t)p.b * p.seqlen_new * p.h_k * SLOTS;
+    if (i >= n) return;
+    const int slot = (int)(i % SLOTS);
+    int64_t r = i / SLOTS;
+    const int kvh = (int)(r % p.h_k);
+    r /= p.h_k;
+    const int t = (int)(r % p.seqlen_new);
+    const int bidx = (int)(r / p.seqlen_new);
+    const int cs = p.cache_seqlens[bidx];
+    const int row = (cs > 0 ? cs : 0) + t;
+    if (row >= p.seqlen_cache) return;
+    const int col = row / p.page_size, prow = row - col * p.page_size;
+    const int64_t page = (int64_t)min((uint32_t)p.block_table[(int64_t)bidx * p.bt_stride + col], (uint32_t)(p.num_blocks - 1));
+    const u32x4 kx = *(const u32x4*)((const char*)p.k_new + 2 * ((int64_t)bidx * p.kn.batch + (int64_t)t * p.kn.row + (int64_t)kvh * p.kn.head + 8 * slot));
+    const u32x4 vx = *(const u32x4*)((const char*)p.v_new + 2 * ((int64_t)bidx * p.vn.batch + (int64_t)t * p.vn.row + (int64_t)kvh * p.vn.head + 8 * slot));
+    *(u32x4*)((char*)p.k_cache + 2 * (page * p.kc.batch + (int64_t)prow * p.kc.row + (int64_t)kvh * p.kc.head + 8 * slot)) = kx;
+    *(u32x4*)((char*)p.v_cache + 2 * (page * p.vc.batch + (int64_t)prow * p.vc.row + (int64_t)kvh * p.vc.head + 8 * slot)) = vx;
+}
+
 template <typename T, int D>
 hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s) {
+    const bool paged = kp.block_table != nullptr;
     if (kp.k_new != nullptr && kp.seqlen_new > 0) {
         const int64_t n = (int64_t)kp.b * kp.seqlen_new * kp.h_k * (D / 8);
-        hipLaunchKernelGGL((fa_kvcache_append_kernel<D>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kp);
+        if (paged) hipLaunchKernelGGL((fa_kvcache_append_paged_kernel<D>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kp);
+        else hipLaunchKernelGGL((fa_kvcache_append_kernel<D>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kp);
     }
     const int64_t grid = (int64_t)kp.b * kp.h_k * kp.n_row_tiles * kp.n_split;
-    if (kp.is_causal) hipLaunchKernelGGL((fa_fwd_kvcache_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
-    else hipLaunchKernelGGL((fa_fwd_kvcache_kernel<T, D, false>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+    if (paged) {
+        if (kp.is_causal) hipLaunchKernelGGL((fa_fwd_kvcache_paged_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+        else hipLaunchKernelGGL((fa_fwd_kvcache_paged_kernel<T, D, false>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+    } else {
+        if (kp.is_causal) hipLaunchKernelGGL((fa_fwd_kvcache_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+        else hipLaunchKernelGGL((fa_fwd_kvcache_kernel<T, D, false>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+    }
     if (kp.n_split > 1) {
         const int64_t rows_per_block = kKvcCombineThreads / (D / 8);
         hipLaunchKernelGGL((fa_kvcache_combine_kernel<T, D>), dim3((unsigned)((kp.rows_total + rows_per_block - 1) / rows_per_block)),

@@ -137,6 +137,12 @@ struct KvcacheKernelParams {
     float* ws_lse;              // n_split x rows_total partial LSE (natural log, -inf = no visible key in the split)
     float scale_log2e;
     float scale;
+    // paged cache (block_table != NULL): k_cache / v_cache are pools of num_blocks pages of page_size rows, kc.batch / vc.batch the page
+    // strides; logical key j of sequence i is row j % page_size of page block_table[i * bt_stride + j / page_size] (clamped to the pool)
+    const int32_t* block_table;
+    int64_t bt_stride;
+    int32_t page_size;          // a multiple of 16: the 16 keys of an MFMA block share a page
+    int32_t num_blocks;
 };
 constexpr int kKvcRows = 16;    // packed query rows of a workgroup (one 16x16x32 MFMA tile)
 constexpr int kKvcStep = 32;    // keys of one wave step (the split granularity)

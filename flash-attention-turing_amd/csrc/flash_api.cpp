@@ -263,16 +263,29 @@ std::vector<at::Tensor> mha_varlen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
 
 // Decode attention over a KV cache (upstream flash-attn's flash_attn_with_kvcache; the reference has no counterpart).  k_cache / v_cache are
 // used in place with their own strides (no copy: k_new / v_new are appended INTO them); cache_seqlens stays on the device (no host sync, the
-// call can be captured in a graph).  The split workspace comes from the caching allocator.
+// call can be captured in a graph).  The split workspace comes from the caching allocator.  With block_table (int32, (b, max_blocks_per_seq))
+// k_cache / v_cache are page pools (num_blocks, page_block_size, h_k, d), addressed through the table in place as well.
 std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, c10::optional<at::Tensor> k_new_,
                                         c10::optional<at::Tensor> v_new_, c10::optional<at::Tensor> cache_seqlens_, bool is_causal,
-                                        int64_t num_splits) {
+                                        int64_t num_splits, c10::optional<at::Tensor> block_table_) {
     TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4, "q, k_cache, v_cache must be rank-4 tensors");
     check_qkv_common(q, k_cache, v_cache);
     const int64_t batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), head_size = q.size(3);
-    const int64_t seqlen_cache = k_cache.size(1), num_heads_k = k_cache.size(2);
+    const int64_t num_heads_k = k_cache.size(2);
+    int64_t seqlen_cache = k_cache.size(1);
     TORCH_CHECK(seqlen_q >= 1, "seqlen_q must be >= 1");
-    TORCH_CHECK(k_cache.size(0) == batch_size && v_cache.size(0) == batch_size, "k_cache/v_cache batch size must match q");
+    at::Tensor block_table;
+    if (block_table_.has_value()) {
+        block_table = *block_table_;
+        check_same_device(q, block_table, "block_table");
+        TORCH_CHECK(block_table.scalar_type() == torch::kInt32, "block_table must be an int32 tensor");
+        TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == batch_size, "block_table must have shape [batch_size, max_blocks_per_seq]");
+        TORCH_CHECK(block_table.stride(1) == 1 || block_table.size(1) <= 1, "block_table: last dimension must be contiguous");
+        seqlen_cache = block_table.size(1) * k_cache.size(1);       // the capacity: max_blocks_per_seq pages of page_block_size rows
+        TORCH_CHECK(k_cache.size(0) <= INT32_MAX && seqlen_cache <= INT32_MAX, "block_table: pool pages and capacity must fit in int32");
+    } else {
+        TORCH_CHECK(k_cache.size(0) == batch_size && v_cache.size(0) == batch_size, "k_cache/v_cache batch size must match q");
+    }
     TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "k_cache and v_cache must have the same shape");
     TORCH_CHECK(k_cache.size(3) == head_size, "q/k_cache/v_cache head_dim must match");
     TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "num_heads_q must be divisible by num_heads_k for GQA/MQA");
@@ -311,6 +324,12 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
     p.h = (int32_t)num_heads; p.h_k = (int32_t)num_heads_k; p.d = (int32_t)head_size;
     p.dtype = fa_dtype_of(q); p.is_causal = is_causal; p.num_splits = (int32_t)num_splits;
     p.q_stride = strides4(q); p.k_cache_stride = strides4(k_cache); p.v_cache_stride = strides4(v_cache); p.o_stride = strides4(o);
+    if (block_table.defined()) {
+        p.block_table = block_table.data_ptr<int32_t>();
+        // (a one-row table's row stride is never used; a view may report anything there)
+        p.block_table_stride = batch_size > 1 ? block_table.stride(0) : std::max<int64_t>(block_table.stride(0), block_table.size(1));
+        p.page_block_size = (int32_t)k_cache.size(1); p.num_blocks = (int32_t)k_cache.size(0);
+    }
     if (k_new.defined()) {
         p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr(); p.seqlen_new = (int32_t)k_new.size(1);
         p.k_new_stride = strides4(k_new); p.v_new_stride = strides4(v_new);
@@ -378,7 +397,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("varlen_bwd", &mha_varlen_bwd, "Varlen backward pass");
     m.def("fwd_kvcache", &mha_fwd_kvcache, "Decode forward over a KV cache (in-place append of k / v, split-KV attention)", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
-          py::arg("is_causal") = false, py::arg("num_splits") = 0);
+          py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("block_table") = py::none());
     m.def("attn_autograd", &attn_autograd, "differentiable forward (C++ autograd node over fwd / bwd)");
     m.def("attn_varlen_autograd", &attn_varlen_autograd, "differentiable packed forward (C++ autograd node over varlen_fwd / varlen_bwd)");
     m.def("abi_version", []() { return fa_abi_version(); });

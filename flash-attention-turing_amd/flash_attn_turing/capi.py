@@ -73,7 +73,8 @@ class KvcacheParams(_Params):
                 ("dtype", _i32), ("is_causal", _i32), ("num_splits", _i32),
                 ("q_stride", Strides), ("k_cache_stride", Strides), ("v_cache_stride", Strides), ("k_new_stride", Strides), ("v_new_stride", Strides),
                 ("o_stride", Strides),
-                ("workspace", _vp), ("workspace_bytes", ctypes.c_int64)]
+                ("workspace", _vp), ("workspace_bytes", ctypes.c_int64),
+                ("block_table", _vp), ("block_table_stride", ctypes.c_int64), ("page_block_size", _i32), ("num_blocks", _i32)]
 
 
 _lib = None
@@ -287,13 +288,18 @@ def run_fwd(params, stream=None):
     check(lib().fa_run_mha_fwd(ctypes.byref(params), s))
 
 
-def kvcache_params(q, k_cache, v_cache, o, lse, cache_seqlens=None, k_new=None, v_new=None, causal=False, num_splits=0):
-    """fa_kvcache_params for (b, s, h, d) torch tensors with arbitrary batch / row / head strides (caches may be views of larger buffers)"""
+def kvcache_params(q, k_cache, v_cache, o, lse, cache_seqlens=None, k_new=None, v_new=None, causal=False, num_splits=0, block_table=None):
+    """fa_kvcache_params for (b, s, h, d) torch tensors with arbitrary batch / row / head strides (caches may be views of larger buffers);
+    with block_table (int32 (b, max_blocks_per_seq)) the caches are page pools (num_blocks, page_block_size, h_k, d)"""
     b, sq, h, d = q.shape
     p = KvcacheParams()
     p.q, p.k_cache, p.v_cache, p.o, p.lse = (t.data_ptr() for t in (q, k_cache, v_cache, o, lse))
     p.cache_seqlens = None if cache_seqlens is None else cache_seqlens.data_ptr()
     p.b, p.seqlen_q, p.seqlen_cache, p.h, p.h_k, p.d = b, sq, k_cache.shape[1], h, k_cache.shape[2], d
+    if block_table is not None:
+        p.block_table, p.block_table_stride = block_table.data_ptr(), block_table.stride(0)
+        p.page_block_size, p.num_blocks = k_cache.shape[1], k_cache.shape[0]
+        p.seqlen_cache = block_table.shape[1] * k_cache.shape[1]
     p.dtype, p.is_causal, p.num_splits = dtype_code(q.dtype), int(causal), int(num_splits)
     tensors = [("q_stride", q), ("k_cache_stride", k_cache), ("v_cache_stride", v_cache), ("o_stride", o)]
     if k_new is not None:

@@ -74,7 +74,8 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
     return _C.attn_varlen_autograd(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), bool(causal))
 
 
-def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, causal=False, num_splits=0, return_softmax_lse=False):
+def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, causal=False, num_splits=0, return_softmax_lse=False, *,
+                            block_table=None):
     """Decode attention over a KV cache (upstream flash-attn's ``flash_attn_with_kvcache`` conventions; forward only).
 
     q: (batch, seqlen_q, nheads, d); k_cache, v_cache: (batch, seqlen_cache, nheads_k, d), any batch / row / head strides (used in place).
@@ -87,6 +88,13 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     Non-finite inputs follow fp32 math over the valid prefix, for every num_splits: a NaN query row, or a NaN / +inf score from a visible K row,
     gives NaN in that row's O and LSE; a row that sees no key is O = 0, LSE = 0.  Cache rows at or past L_i and heads the
     cache views skip are never read into a result.
+
+    block_table (keyword, optional): a paged cache.  k_cache, v_cache are then page pools (num_blocks, page_block_size, nheads_k, d), any
+    page / row / head strides, page_block_size a multiple of 16; block_table is an int32 tensor (batch, max_blocks_per_seq) on q's device
+    with a contiguous last dim: logical key j of sequence i is row j % page_block_size of page block_table[i, j // page_block_size].  The
+    capacity is max_blocks_per_seq * page_block_size and takes the part of seqlen_cache above; the append writes through the table.
+    Entries past the pages a sequence needs are never read.  A needed entry outside [0, num_blocks) breaks the precondition: it is
+    clamped, min(uint32(entry), num_blocks - 1), so it reads (or the append writes) page num_blocks - 1 and nothing outside the pool.
     """
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v)):
         raise RuntimeError("flash_attn_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
@@ -94,5 +102,5 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
         raise ValueError("k and v must both be given or both be None")
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=q.device)
-    out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits))
+    out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table)
     return (out, lse) if return_softmax_lse else out

@@ -159,7 +159,18 @@ typedef struct fa_bwd_params {
  * fit are dropped.  No host synchronisation: the call can be captured in a graph and replayed with new cache_seqlens values.
  * workspace: fp32 scratch for the key split (fa_kvcache_workspace_bytes), 16-byte aligned; a smaller buffer caps the split, none (NULL / 0)
  * means one split.  num_splits > 0 overrides the library's choice (capped by the 32-key tiles of seqlen_cache and by the workspace).
- * Results are deterministic for a given split count. */
+ * Results are deterministic for a given split count.
+ * Paged cache (optional fields after workspace_bytes; block_table == NULL = the contiguous cache above): k_cache / v_cache are pools of
+ * num_blocks pages of page_block_size rows (a positive multiple of 16), k_cache_stride.batch / v_cache_stride.batch the page strides.
+ * block_table: int32 DEVICE array, row i (at block_table + i * block_table_stride, block_table_stride >= seqlen_cache / page_block_size)
+ * lists the pages of sequence i: logical key j is row j % page_block_size of page block_table[i][j / page_block_size].  seqlen_cache is
+ * the per-sequence capacity, a positive multiple of page_block_size (the table has seqlen_cache / page_block_size columns); it plays the
+ * same part as above (split, causal alignment, precondition).  The append writes through the table.  Pool rows at or past L_i, table
+ * entries of pages at or past ceil(L_i / page_block_size) and pages no sequence references are never read into a result.  Pages may be
+ * shared between sequences for reading.  Precondition: every entry a sequence needs lies in [0, num_blocks).  Broken, nothing outside the
+ * pool is read or written: every entry the kernels use goes through min((uint32_t)entry, num_blocks - 1), so a bad entry reads (or, for
+ * the append, writes) page num_blocks - 1.  A caller built against the header before these fields (struct_size = offsetof(block_table))
+ * gets the contiguous cache. */
 typedef struct fa_kvcache_params {
     uint32_t struct_size;       /* sizeof(fa_kvcache_params) in the caller's translation unit */
     uint32_t magic;             /* FA_PARAMS_MAGIC */
@@ -184,6 +195,10 @@ typedef struct fa_kvcache_params {
     fa_strides q_stride, k_cache_stride, v_cache_stride, k_new_stride, v_new_stride, o_stride;
     void* workspace;
     int64_t workspace_bytes;
+    const int32_t* block_table;     /* optional: paged cache (see above); NULL = contiguous */
+    int64_t block_table_stride;     /* elements between table rows */
+    int32_t page_block_size;        /* rows per page; 0 without block_table */
+    int32_t num_blocks;             /* pages in the pool */
 } fa_kvcache_params;
 
 /* ---- library info ---------------------------------------------------------------------- */

@@ -5,7 +5,11 @@ ms per call of both paths, the bytes the decode path moves (valid K/V prefix rea
 written and read once), its effective TB/s, that as a fraction of 6.3 TB/s achievable and 8 TB/s peak HBM, the split count, the speedup.
 
 Every point rotates over enough distinct caches that the working set exceeds 256 MiB, so that K/V come from HBM and not from the 256 MiB
-Infinity Cache.  Usage: python tools/kvcache_bench.py [--quick] [--rounds N]"""
+Infinity Cache.  Usage: python tools/kvcache_bench.py [--quick] [--rounds N] [--paged P ...]
+
+--paged P (repeatable) measures a paged cache instead: per grid point and page size P, the paged call (block_table over a pool whose pages
+are assigned by a random permutation) against the contiguous call on the same data (the pool gathered into (b, L, h_k, d)), interleaved,
+medians; ms and TB/s of both and paged / contiguous."""
 import argparse
 import itertools
 import json
@@ -82,6 +86,46 @@ def run_point(pt, rounds):
                 speedup_vs_fwd=round(ms_fw / ms_kv, 2))
 
 
+def run_paged_point(pt, page, rounds):
+    dev = torch.device("cuda:0")
+    b, h, hk, d, L, sq, dt = pt["b"], pt["h"], pt["h_k"], pt["d"], pt["L"], pt["seqlen_q"], pt["dtype"]
+    assert L % page == 0, (L, page)
+    kv_bytes = 2 * b * L * hk * d * 2
+    n = max(1, min(512, math.ceil(WORKING_SET / kv_bytes)))
+    nb = b * (L // page)
+    gen = torch.Generator(device="cpu").manual_seed(page)
+    sets = []
+    for _ in range(n):
+        kp = torch.empty(nb, page, hk, d, device=dev, dtype=dt).uniform_(-2, 2)
+        vp = torch.empty(nb, page, hk, d, device=dev, dtype=dt).uniform_(-2, 2)
+        table = torch.randperm(nb, generator=gen).view(b, L // page).to(device=dev, dtype=torch.int32)
+        idx = table.long()
+        kc, vc = kp[idx].reshape(b, L, hk, d), vp[idx].reshape(b, L, hk, d)
+        sets.append((kp, vp, table, kc, vc))
+    q = torch.randn(b, sq, h, d, device=dev, dtype=dt)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    pg = lambda i: F.flash_attn_with_kvcache(q, sets[i][0], sets[i][1], cache_seqlens=cs, block_table=sets[i][2])
+    ct = lambda i: F.flash_attn_with_kvcache(q, sets[i][3], sets[i][4], cache_seqlens=cs)
+    assert torch.equal(pg(0), ct(0))
+    torch.cuda.synchronize()
+    t_pg, t_ct = [], []
+    for _ in range(rounds):
+        t_pg.append(time_rotation(pg, n, 20))
+        t_ct.append(time_rotation(ct, n, 20))
+    ms_pg, ms_ct = statistics.median(t_pg), statistics.median(t_ct)
+    p = capi.kvcache_params(q, sets[0][3], sets[0][4], torch.empty_like(q), torch.empty(b, h, sq, device=dev), cache_seqlens=cs)
+    ws = capi.kvcache_workspace_bytes(p)
+    n_split = max(1, ws and capi.kvcache_num_splits(_with_ws(p, ws)))
+    rows = b * h * sq
+    moved = kv_bytes + 2 * rows * d * 2 + rows * 4 + (2 * n_split * rows * (d + 1) * 4 if n_split > 1 else 0)
+    del sets
+    torch.cuda.empty_cache()
+    return dict(b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=sq, dtype=str(dt).replace("torch.", ""), page_block_size=page, caches_rotated=n,
+                ms_paged=round(ms_pg, 5), ms_contiguous=round(ms_ct, 5), bytes=moved, kv_gb=round(kv_bytes / 1e9, 3),
+                tbps_paged=round(moved / (ms_pg * 1e-3) / 1e12, 3), tbps_contiguous=round(moved / (ms_ct * 1e-3) / 1e12, 3), n_split=n_split,
+                paged_over_contiguous=round(ms_pg / ms_ct, 3))
+
+
 def _with_ws(p, ws):
     buf = torch.empty(ws // 4, device="cuda:0", dtype=torch.float32)
     p.workspace, p.workspace_bytes = buf.data_ptr(), ws
@@ -93,12 +137,17 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--quick", action="store_true", help="b in {1, 8}, L = 32k only")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--paged", type=int, action="append", metavar="P", help="page size (a multiple of 16); repeat for several")
     a = ap.parse_args()
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
           flush=True)
     with torch.no_grad():
         for pt in grid(a.quick):
-            print(json.dumps(run_point(pt, a.rounds)), flush=True)
+            if a.paged:
+                for page in a.paged:
+                    print(json.dumps(run_paged_point(pt, page, a.rounds)), flush=True)
+            else:
+                print(json.dumps(run_point(pt, a.rounds)), flush=True)
 
 
 if __name__ == "__main__":
