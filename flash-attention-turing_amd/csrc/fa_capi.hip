@@ -396,33 +396,57 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
     return FA_OK;
 }
 
-int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* user) {
+// fa_kvcache_options (NULL = none) -> the window fields of kp, normalised: right = 0 under causal, and a side that cannot bind is -1 (left >=
+// seqlen_cache - 1: lo_t <= L - 1 - left <= 0 for every row; right >= seqlen_q - 1: lim_t >= L for every row).  A window whose left side is
+// unbounded and whose right side is unbounded or the causal limit is exactly the plain call: is_local stays 0 (the plain kernels, split and bits).
+static int fill_kvcache_options(const fa_kvcache_options* user, fa::KvcacheKernelParams& kp) {
+    if (user == nullptr) return FA_OK;
+    fa_kvcache_options o;
+    int rc = import_params(user, o, "fa_kvcache_options", offsetof(fa_kvcache_options, window_size_right) + sizeof(int32_t));
+    if (rc) return rc;
+    if (!o.is_local) return FA_OK;
+    if (o.window_size_left < -1 || o.window_size_right < -1)
+        return fail(FA_ERR_BAD_SHAPE, "window_size (%d, %d): each side must be >= -1 (-1 = unbounded)", o.window_size_left, o.window_size_right);
+    int left = o.window_size_left, right = kp.is_causal ? 0 : o.window_size_right;
+    if (left >= kp.seqlen_cache - 1) left = -1;
+    if (right >= kp.seqlen_q - 1) right = -1;
+    kp.is_local = (left >= 0 || (right >= 0 && !kp.is_causal)) ? 1 : 0;
+    kp.window_left = kp.is_local ? left : -1;
+    kp.window_right = kp.is_local ? right : -1;
+    return FA_OK;
+}
+
+int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
     int rc = fill_kvcache(user, kp, local, false);
-    if (rc) return rc;
+    if (rc || (rc = fill_kvcache_options(options, kp))) return rc;
     if (kp.b == 0) return 0;
     return fa::kvcache_workspace_bytes(kp, fa::kvcache_split(kp, -1, local.num_splits));
 }
 
-int32_t fa_kvcache_num_splits(const fa_kvcache_params* user) {
+int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
     int rc = fill_kvcache(user, kp, local, true);
-    if (rc) return rc;
+    if (rc || (rc = fill_kvcache_options(options, kp))) return rc;
     if (kp.b == 0) return 1;
     return fa::kvcache_split(kp, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits);
 }
 
-int fa_run_mha_fwd_kvcache(const fa_kvcache_params* user, void* stream) {
+int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* user, const fa_kvcache_options* options, void* stream) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
     int rc = fill_kvcache(user, kp, local, true);
-    if (rc) return rc;
+    if (rc || (rc = fill_kvcache_options(options, kp))) return rc;
     if (kp.b == 0) return FA_OK;
     kp.n_split = fa::kvcache_split(kp, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits);
     kp.ws_o = kp.n_split > 1 ? (float*)local.workspace : nullptr;
     return hip_status(fa::launch_fwd_kvcache(kp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache launch");
 }
+
+int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* user) { return fa_kvcache_workspace_bytes_ex(user, nullptr); }
+int32_t fa_kvcache_num_splits(const fa_kvcache_params* user) { return fa_kvcache_num_splits_ex(user, nullptr); }
+int fa_run_mha_fwd_kvcache(const fa_kvcache_params* user, void* stream) { return fa_run_mha_fwd_kvcache_ex(user, nullptr, stream); }
 
 }  // extern "C"

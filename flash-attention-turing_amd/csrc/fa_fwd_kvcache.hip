@@ -18,6 +18,9 @@
 // Next step's K and V are loaded into a second register set before the current step is computed (two sets, no copies).  K/V rows are
 // addressed through buffer descriptors whose range ends at the sequence's valid length L: rows at or past L read as zeros (V zeros matter:
 // 0 x NaN from an uninitialised cache row would poison O), and the scores of keys past L or behind the causal limit are masked to -inf.
+// Sliding window (the _local kernels, KvcacheKernelParams::is_local): each lane's row sees keys lo_t <= key < lim_t, and a workgroup's key range
+// starts at the 32-aligned base below the first row w0 its tile sees; its descriptors start at w0, so rows below w0 read as zeros like rows
+// at or past L.  The plain kernels are the same template with LOCAL = false: their code does not change.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -52,7 +55,7 @@ FA_DEV int kvc_len(const KvcacheKernelParams& p, int bidx) {
 }
 
 // The attention body of both cache layouts; PAGED changes how K / V rows are addressed (load_step), nothing else.
-template <typename T, int D, bool CAUSAL, bool PAGED>
+template <typename T, int D, bool CAUSAL, bool PAGED, bool LOCAL = false>
 FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
     constexpr int NC = D / 32;          // 16x16x32 MFMAs per 16 keys of S^T (d chunks)
     constexpr int NO = D / 16;          // O^T blocks of 16 columns
@@ -68,9 +71,17 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
     const int tile = rest % p.n_row_tiles, bh = rest / p.n_row_tiles;
     const int bidx = bh / p.h_k, kvh = bh - bidx * p.h_k;
     const int L = kvc_len(p, bidx);
-    const int k_begin = split * p.split_keys;
-    const int k_end = min(k_begin + p.split_keys, L);
     const int rows_tile = p.seqlen_q * p.h_ratio;
+    // window bounds of query position tq (LOCAL): lo_t = L - seqlen_q + t - left (any negative value = no lower bound), lim_t = min(L, L -
+    // seqlen_q + t + right + 1); written so that nothing overflows for any L and left < seqlen_cache, right < seqlen_q - 1 (host-normalised)
+    auto win_lo = [&](int tq) { return p.window_left >= 0 ? max(L - p.window_left, 0) - (p.seqlen_q - tq) : 0; };
+    auto win_lim = [&](int tq) { return p.window_right >= 0 ? L - max(p.seqlen_q - 1 - tq - p.window_right, 0) : L; };
+    // LOCAL: w0 = the first key the tile's first row (the smallest lo) sees; the splits start at w0 rounded down to a step and end at the
+    // largest lim of the tile (its last row's).  Plain: w0 = 0, the splits cover [0, L).
+    const int w0 = LOCAL ? __builtin_amdgcn_readfirstlane(max(win_lo(tile * kKvcRows / p.h_ratio), 0)) : 0;
+    const int k_hi = LOCAL ? __builtin_amdgcn_readfirstlane(win_lim((min((tile + 1) * kKvcRows, rows_tile) - 1) / p.h_ratio)) : L;
+    const int k_begin = (w0 & ~(kKvcStep - 1)) + split * p.split_keys;
+    const int k_end = min(k_begin + p.split_keys, k_hi);
     const float c = p.scale_log2e;
 
     if (p.n_split > 1 && k_begin >= k_end) {        // nothing to read in this split: an empty partial (LSE = -inf), O is never looked at
@@ -91,6 +102,8 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
     const int hq = kvh * p.h_ratio + (row_ok ? pr - t * p.h_ratio : 0);
     int lim = row_ok ? L : 0;
     if (CAUSAL && row_ok) lim = min(L, L - p.seqlen_q + t + 1);
+    if (LOCAL && row_ok) lim = win_lim(t);
+    const int lo = LOCAL ? win_lo(t) : 0;
     u32x4 qf[NC];
     {
         const char* qrow = (const char*)p.q_ptr + 2 * ((int64_t)bidx * p.q.batch + (int64_t)t * p.q.row + (int64_t)hq * p.q.head);
@@ -101,17 +114,22 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
     }
 
     // ---- K / V of this (batch, KV head): descriptors end at row L ------------------------------------------------------------------
+    // (contiguous LOCAL: they start at row w0 <= L, and a row is addressed as min((uint32_t)(key - w0), L - w0): rows below w0 and at or
+    // past L both fall outside the range)
     const uint32_t krow_b = (uint32_t)(p.kc.row * 2), vrow_b = (uint32_t)(p.vc.row * 2);
-    const char* kbase = uniform_ptr((const char*)p.k_cache + 2 * ((int64_t)(PAGED ? 0 : bidx) * p.kc.batch + (int64_t)kvh * p.kc.head));
-    const char* vbase = uniform_ptr((const char*)p.v_cache + 2 * ((int64_t)(PAGED ? 0 : bidx) * p.vc.batch + (int64_t)kvh * p.vc.head));
-    const rsrc_t krs = make_rsrc(kbase, L > 0 ? (uint32_t)(L - 1) * krow_b + 2 * D : 0u);
-    const rsrc_t vrs = make_rsrc(vbase, L > 0 ? (uint32_t)(L - 1) * vrow_b + 2 * D : 0u);
+    const int wb = PAGED ? 0 : w0;
+    const char* kbase = uniform_ptr((const char*)p.k_cache + 2 * ((int64_t)(PAGED ? 0 : bidx) * p.kc.batch + (int64_t)kvh * p.kc.head + (int64_t)wb * p.kc.row));
+    const char* vbase = uniform_ptr((const char*)p.v_cache + 2 * ((int64_t)(PAGED ? 0 : bidx) * p.vc.batch + (int64_t)kvh * p.vc.head + (int64_t)wb * p.vc.row));
+    const rsrc_t krs = make_rsrc(kbase, L > wb ? (uint32_t)(L - wb - 1) * krow_b + 2 * D : 0u);
+    const rsrc_t vrs = make_rsrc(vbase, L > wb ? (uint32_t)(L - wb - 1) * vrow_b + 2 * D : 0u);
     // Paged cache: a step's two 16-key blocks each lie in one page (page_size is a multiple of 16).  Every block gets its own descriptors,
     // based at the block's first row in its page and ending at the sequence's last valid row in the block (rows at or past L read as
     // zeros, as above; a block wholly past L has an empty range, so whatever its table entry says is never read).  The table entries of
     // the step after the one being loaded are fetched (scalar loads) together with that load, one compute step before they are needed;
     // the fetch cursor (column, row in page) moves by the wave stride without a division.  Columns are clamped to the table row,
     // entries to the pool: min((uint32_t)entry, num_blocks - 1).  Page offsets are 64-bit; in-page offsets < 2^31 by the host checks.
+    // LOCAL: a block's descriptors start at its first row at or past w0 (skip rows in) and the rows are addressed like the contiguous case,
+    // min((uint32_t)(row - skip), valid - skip): rows below w0 read as zeros, and a block wholly below w0 reads nothing.
     const int P = p.page_size;
     // (read through the constant address space: the table is not written while the kernel runs, and so the compiler issues scalar loads
     // that only a later lgkmcnt wait depends on; as a plain global pointer it gets vector loads that wait behind the K / V loads in flight)
@@ -138,21 +156,31 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
         fetch_pages();
     }
     // (row indices are clamped to L: a row at L is past the descriptor's range, and (L) x row stride < 2^31 by the host checks)
+    auto crow = [&](int key) __attribute__((always_inline)) {
+        return LOCAL ? min((uint32_t)(key - w0), (uint32_t)(L - w0)) : (uint32_t)min(key, L);
+    };
     auto load_step = [&](int key0, u32x4 (&kf)[2][NC], u32x4 (&vf)[NV]) __attribute__((always_inline)) {
         if constexpr (PAGED) {
             rsrc_t kr[2], vr[2];
+            int skip[2], nrow[2];
             static_for<0, 2>([&](auto kb) {
                 constexpr int b = decltype(kb)::value;
                 const int valid = min(max(L - (key0 + 16 * b), 0), 16);
+                skip[b] = LOCAL ? min(max(w0 - (key0 + 16 * b), 0), 16) : 0;     // <= valid (w0 <= L)
+                nrow[b] = valid - skip[b];
                 const int64_t page = min(pg[b], (uint32_t)(p.num_blocks - 1));
-                const int64_t pk = page * p.kc.batch + (int64_t)rw[b] * p.kc.row;
-                const int64_t pv = page * p.vc.batch + (int64_t)rw[b] * p.vc.row;
-                kr[b] = make_rsrc(uniform_ptr(kbase + 2 * pk), valid > 0 ? (uint32_t)(valid - 1) * krow_b + 2 * D : 0u);
-                vr[b] = make_rsrc(uniform_ptr(vbase + 2 * pv), valid > 0 ? (uint32_t)(valid - 1) * vrow_b + 2 * D : 0u);
+                const int64_t pk = page * p.kc.batch + (int64_t)(rw[b] + skip[b]) * p.kc.row;
+                const int64_t pv = page * p.vc.batch + (int64_t)(rw[b] + skip[b]) * p.vc.row;
+                kr[b] = make_rsrc(uniform_ptr(kbase + 2 * pk), nrow[b] > 0 ? (uint32_t)(nrow[b] - 1) * krow_b + 2 * D : 0u);
+                vr[b] = make_rsrc(uniform_ptr(vbase + 2 * pv), nrow[b] > 0 ? (uint32_t)(nrow[b] - 1) * vrow_b + 2 * D : 0u);
             });
+            // row r of block b within its descriptor
+            auto brow = [&](int b, int r) __attribute__((always_inline)) {
+                return LOCAL ? min((uint32_t)(r - skip[b]), (uint32_t)nrow[b]) : (uint32_t)r;
+            };
             static_for<0, 2>([&](auto kb) {
                 constexpr int b = decltype(kb)::value;
-                const uint32_t off = (uint32_t)n16 * krow_b + 2 * 8 * g;
+                const uint32_t off = brow(b, n16) * krow_b + 2 * 8 * g;
                 static_for<0, NC>([&](auto cc) {
                     constexpr int ci = decltype(cc)::value;
                     kf[b][ci] = buf_load16(kr[b], off + 2 * 32 * ci);
@@ -161,14 +189,14 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
             static_for<0, NV>([&](auto iv) {
                 constexpr int i = decltype(iv)::value;
                 constexpr int b = (i * VRPL) / 16;
-                const uint32_t off = (uint32_t)((i * VRPL) % 16 + lane / SLOTS) * vrow_b + 16 * (lane % SLOTS);
+                const uint32_t off = brow(b, (i * VRPL) % 16 + lane / SLOTS) * vrow_b + 16 * (lane % SLOTS);
                 vf[i] = buf_load16(vr[b], off);
             });
             fetch_pages();                          // the table entries of the step after this one
         } else {
             static_for<0, 2>([&](auto kb) {
                 constexpr int b = decltype(kb)::value;
-                const uint32_t off = (uint32_t)min(key0 + 16 * b + n16, L) * krow_b + 2 * 8 * g;
+                const uint32_t off = crow(key0 + 16 * b + n16) * krow_b + 2 * 8 * g;
                 static_for<0, NC>([&](auto cc) {
                     constexpr int ci = decltype(cc)::value;
                     kf[b][ci] = buf_load16(krs, off + 2 * 32 * ci);
@@ -176,7 +204,7 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
             });
             static_for<0, NV>([&](auto iv) {
                 constexpr int i = decltype(iv)::value;
-                const uint32_t off = (uint32_t)min(key0 + i * VRPL + lane / SLOTS, L) * vrow_b + 16 * (lane % SLOTS);
+                const uint32_t off = crow(key0 + i * VRPL + lane / SLOTS) * vrow_b + 16 * (lane % SLOTS);
                 vf[i] = buf_load16(vrs, off);
             });
         }
@@ -213,7 +241,7 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
             static_for<0, 4>([&](auto rr) {
                 constexpr int r = decltype(rr)::value;
                 const int key = key0 + 16 * b + 4 * g + r;
-                s[b][r] = key < lim ? s[b][r] : -INFINITY;
+                s[b][r] = (key < lim && (!LOCAL || key >= lo)) ? s[b][r] : -INFINITY;
                 mx = fmaxf(mx, s[b][r]);
             });
         });
@@ -336,6 +364,12 @@ __global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_paged_kernel(co
     kvcache_attn<T, D, CAUSAL, true>(p);
 }
 
+// Sliding window over either layout (the causal limit arrives as window_right = 0)
+template <typename T, int D, bool PAGED>
+__global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_local_kernel(const KvcacheKernelParams p) {
+    kvcache_attn<T, D, false, PAGED, true>(p);
+}
+
 // One pass per output row over the splits, in split order (deterministic): O = sum_s exp(lse_s - M) O_s / sum_s exp(lse_s - M),
 // LSE = M + log(sum); splits with LSE = -inf saw no key of the row and are skipped (their O plane was never written); a row no split saw
 // is a dead row: O = 0, LSE = 0.  A NaN partial (a NaN or +inf score in its split; its O plane is written) makes the row NaN, O and LSE,
@@ -442,7 +476,10 @@ hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s) {
         else hipLaunchKernelGGL((fa_kvcache_append_kernel<D>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kp);
     }
     const int64_t grid = (int64_t)kp.b * kp.h_k * kp.n_row_tiles * kp.n_split;
-    if (paged) {
+    if (kp.is_local) {
+        if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_local_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+        else hipLaunchKernelGGL((fa_fwd_kvcache_local_kernel<T, D, false>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+    } else if (paged) {
         if (kp.is_causal) hipLaunchKernelGGL((fa_fwd_kvcache_paged_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
         else hipLaunchKernelGGL((fa_fwd_kvcache_paged_kernel<T, D, false>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
     } else {
@@ -457,11 +494,21 @@ hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s) {
     return hipGetLastError();
 }
 
-int64_t kvcache_steps(const KvcacheKernelParams& kp) { return ((int64_t)kp.seqlen_cache + kKvcStep - 1) / kKvcStep; }
+// 32-key steps the splits of a launch must cover.  A window with a left edge bounds what one workgroup reads from its base: the tile's
+// largest lim minus its smallest lo is at most left + seqlen_q + max(right, 0), plus up to kKvcStep - 1 keys of the base's alignment.
+int64_t kvcache_steps(const KvcacheKernelParams& kp) {
+    int64_t keys = kp.seqlen_cache;
+    if (kp.is_local && kp.window_left >= 0) {
+        const int64_t span = (int64_t)kp.window_left + kp.seqlen_q + (kp.window_right > 0 ? kp.window_right : 0) + kKvcStep - 1;
+        if (span < keys) keys = span;
+    }
+    return (keys + kKvcStep - 1) / kKvcStep;
+}
 
 }  // namespace
 
-// Split count: the host knows the capacity, not the lengths (they live on the device), so the split is sized from seqlen_cache.  A launch
+// Split count: the host knows the capacity, not the lengths (they live on the device), so the split is sized from seqlen_cache (with a
+// window: from the window's span, kvcache_steps; never more steps than without it, so the split and workspace never grow).  A launch
 // of b x h_k x row tiles workgroups that already brings one per compute unit is not split; otherwise the key range is split until the
 // launch holds two workgroups per unit (the occupancy of the attention kernel), keeping at least kKvcMinStepsPerSplit steps per split and
 // at most kKvcMaxSplits splits.  An explicit request overrides the rule (never more splits than 32-key steps); a workspace smaller than

@@ -143,6 +143,12 @@ struct KvcacheKernelParams {
     int64_t bt_stride;
     int32_t page_size;          // a multiple of 16: the 16 keys of an MFMA block share a page
     int32_t num_blocks;
+    // sliding window (fa_kvcache_options; is_local = 0: the plain kernels, the two fields are not read).  Key j is visible to query t of a
+    // sequence of length L when L - seqlen_q + t - window_left <= j <= L - seqlen_q + t + window_right; -1 = unbounded on that side.
+    // Normalised by the host: window_right is 0 under causal, and a side that cannot bind (left >= seqlen_cache - 1, right >= seqlen_q - 1) is -1.
+    int32_t is_local;
+    int32_t window_left;
+    int32_t window_right;
 };
 constexpr int kKvcRows = 16;    // packed query rows of a workgroup (one 16x16x32 MFMA tile)
 constexpr int kKvcStep = 32;    // keys of one wave step (the split granularity)

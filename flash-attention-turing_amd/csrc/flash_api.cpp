@@ -264,10 +264,12 @@ std::vector<at::Tensor> mha_varlen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
 // Decode attention over a KV cache (upstream flash-attn's flash_attn_with_kvcache; the reference has no counterpart).  k_cache / v_cache are
 // used in place with their own strides (no copy: k_new / v_new are appended INTO them); cache_seqlens stays on the device (no host sync, the
 // call can be captured in a graph).  The split workspace comes from the caching allocator.  With block_table (int32, (b, max_blocks_per_seq))
-// k_cache / v_cache are page pools (num_blocks, page_block_size, h_k, d), addressed through the table in place as well.
+// k_cache / v_cache are page pools (num_blocks, page_block_size, h_k, d), addressed through the table in place as well.  window_size_left /
+// _right: a sliding window (fa_kvcache_options; (-1, -1) = none, the plain entry points).
 std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, c10::optional<at::Tensor> k_new_,
                                         c10::optional<at::Tensor> v_new_, c10::optional<at::Tensor> cache_seqlens_, bool is_causal,
-                                        int64_t num_splits, c10::optional<at::Tensor> block_table_) {
+                                        int64_t num_splits, c10::optional<at::Tensor> block_table_, int64_t window_size_left,
+                                        int64_t window_size_right) {
     TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4, "q, k_cache, v_cache must be rank-4 tensors");
     check_qkv_common(q, k_cache, v_cache);
     const int64_t batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), head_size = q.size(3);
@@ -291,6 +293,8 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
     TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "num_heads_q must be divisible by num_heads_k for GQA/MQA");
     TORCH_CHECK(k_cache.stride(3) == 1 && v_cache.stride(3) == 1, "k_cache/v_cache: last dimension must be contiguous");
     TORCH_CHECK(num_splits >= 0, "num_splits must be >= 0 (0 = automatic)");
+    TORCH_CHECK(window_size_left >= -1 && window_size_right >= -1 && window_size_left <= INT32_MAX && window_size_right <= INT32_MAX,
+                "window_size: each side must be an int32 >= -1 (-1 = unbounded)");
     TORCH_CHECK(k_new_.has_value() == v_new_.has_value(), "k and v must both be given or both be None");
     at::Tensor k_new, v_new, cache_seqlens;
     if (cache_seqlens_.has_value()) {
@@ -334,14 +338,19 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
         p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr(); p.seqlen_new = (int32_t)k_new.size(1);
         p.k_new_stride = strides4(k_new); p.v_new_stride = strides4(v_new);
     }
+    fa_kvcache_options opt;
+    FA_PARAMS_INIT(opt);
+    opt.is_local = window_size_left != -1 || window_size_right != -1;
+    opt.window_size_left = (int32_t)window_size_left; opt.window_size_right = (int32_t)window_size_right;
+    const fa_kvcache_options* opts = opt.is_local ? &opt : nullptr;
     at::Tensor workspace;
-    const int64_t ws_bytes = fa_kvcache_workspace_bytes(&p);
+    const int64_t ws_bytes = fa_kvcache_workspace_bytes_ex(&p, opts);
     if (ws_bytes < 0) check_status((int)ws_bytes);
     if (ws_bytes > 0) {
         workspace = torch::empty({ws_bytes / 4}, q.options().dtype(torch::kFloat32));
         p.workspace = workspace.data_ptr(); p.workspace_bytes = ws_bytes;
     }
-    check_status(fa_run_mha_fwd_kvcache(&p, current_stream(q)));
+    check_status(fa_run_mha_fwd_kvcache_ex(&p, opts, current_stream(q)));
     return {o, l};
 }
 
@@ -397,7 +406,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("varlen_bwd", &mha_varlen_bwd, "Varlen backward pass");
     m.def("fwd_kvcache", &mha_fwd_kvcache, "Decode forward over a KV cache (in-place append of k / v, split-KV attention)", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
-          py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("block_table") = py::none());
+          py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("block_table") = py::none(), py::arg("window_size_left") = -1,
+          py::arg("window_size_right") = -1);
     m.def("attn_autograd", &attn_autograd, "differentiable forward (C++ autograd node over fwd / bwd)");
     m.def("attn_varlen_autograd", &attn_varlen_autograd, "differentiable packed forward (C++ autograd node over varlen_fwd / varlen_bwd)");
     m.def("abi_version", []() { return fa_abi_version(); });

@@ -77,6 +77,12 @@ class KvcacheParams(_Params):
                 ("block_table", _vp), ("block_table_stride", ctypes.c_int64), ("page_block_size", _i32), ("num_blocks", _i32)]
 
 
+class KvcacheOptions(_Params):
+    """fa_kvcache_options: options of a decode call beyond fa_kvcache_params (the _ex entry points); zeroed = none"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("is_local", _i32), ("window_size_left", _i32),
+                ("window_size_right", _i32)]
+
+
 _lib = None
 
 
@@ -113,6 +119,13 @@ def lib():
         L.fa_kvcache_workspace_bytes.restype = ctypes.c_int64
         L.fa_kvcache_num_splits.argtypes = [ctypes.POINTER(KvcacheParams)]
         L.fa_kvcache_num_splits.restype = ctypes.c_int32
+        _op = ctypes.POINTER(KvcacheOptions)
+        L.fa_run_mha_fwd_kvcache_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op, _vp]
+        L.fa_run_mha_fwd_kvcache_ex.restype = ctypes.c_int
+        L.fa_kvcache_workspace_bytes_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op]
+        L.fa_kvcache_workspace_bytes_ex.restype = ctypes.c_int64
+        L.fa_kvcache_num_splits_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op]
+        L.fa_kvcache_num_splits_ex.restype = ctypes.c_int32
         L.fa_mha_fwd.argtypes = [_vp] * 5 + [_i32] * 8 + [_vp]
         L.fa_mha_bwd.argtypes = [_vp] * 10 + [_i32] * 8 + [_vp]
         L.fa_mha_varlen_fwd.argtypes = [_vp] * 7 + [_i32] * 8 + [_vp]
@@ -310,24 +323,37 @@ def kvcache_params(q, k_cache, v_cache, o, lse, cache_seqlens=None, k_new=None, 
     return p
 
 
-def kvcache_workspace_bytes(params) -> int:
-    """fa_kvcache_workspace_bytes: fp32 scratch the split the library would choose needs (0: one split)"""
-    n = lib().fa_kvcache_workspace_bytes(ctypes.byref(params))
+def kvcache_options(window_size=(-1, -1)):
+    """fa_kvcache_options with a sliding window (left, right); (-1, -1) gives a zeroed struct (no window)"""
+    o = KvcacheOptions()
+    left, right = window_size
+    if (left, right) != (-1, -1):
+        o.is_local, o.window_size_left, o.window_size_right = 1, int(left), int(right)
+    return o
+
+
+def kvcache_workspace_bytes(params, options=None) -> int:
+    """fa_kvcache_workspace_bytes[_ex]: fp32 scratch the split the library would choose needs (0: one split); options = KvcacheOptions"""
+    n = lib().fa_kvcache_workspace_bytes(ctypes.byref(params)) if options is None else lib().fa_kvcache_workspace_bytes_ex(ctypes.byref(params), ctypes.byref(options))
     if n < 0:
         check(int(n))
     return int(n)
 
 
-def kvcache_num_splits(params) -> int:
-    """fa_kvcache_num_splits: key splits the launch of these params would use (their workspace fields included)"""
-    n = lib().fa_kvcache_num_splits(ctypes.byref(params))
+def kvcache_num_splits(params, options=None) -> int:
+    """fa_kvcache_num_splits[_ex]: key splits the launch of these params would use (their workspace fields included)"""
+    n = lib().fa_kvcache_num_splits(ctypes.byref(params)) if options is None else lib().fa_kvcache_num_splits_ex(ctypes.byref(params), ctypes.byref(options))
     if n < 0:
         check(int(n))
     return int(n)
 
 
-def run_fwd_kvcache(params, stream=None):
+def run_fwd_kvcache(params, stream=None, options=None):
+    """fa_run_mha_fwd_kvcache, or fa_run_mha_fwd_kvcache_ex with options (KvcacheOptions)"""
     import torch
 
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    check(lib().fa_run_mha_fwd_kvcache(ctypes.byref(params), s))
+    if options is None:
+        check(lib().fa_run_mha_fwd_kvcache(ctypes.byref(params), s))
+    else:
+        check(lib().fa_run_mha_fwd_kvcache_ex(ctypes.byref(params), ctypes.byref(options), s))

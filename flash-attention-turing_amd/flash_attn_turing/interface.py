@@ -5,6 +5,8 @@ The reference ships only the four raw functions; its README (README.md:28-48) do
 ``flash_attn_func`` here accepts both that legacy call (the four ints are validated against
 the tensor shapes and otherwise ignored) and the modern ``flash_attn_func(q, k, v, causal=False)``.
 """
+import numbers
+
 import torch
 
 from . import _C
@@ -74,8 +76,22 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
     return _C.attn_varlen_autograd(q, k, v, cu_seqlens_q, cu_seqlens_k, int(max_seqlen_q), int(max_seqlen_k), bool(causal))
 
 
+def _window_pair(window_size):
+    """(left, right) as two ints >= -1; anything else is a ValueError"""
+    try:
+        left, right = window_size
+    except (TypeError, ValueError):
+        raise ValueError(f"window_size must be a pair of ints (left, right), got {window_size!r}") from None
+    if any(isinstance(x, bool) or not isinstance(x, numbers.Integral) for x in (left, right)):
+        raise ValueError(f"window_size must be a pair of ints (left, right), got {window_size!r}")
+    left, right = int(left), int(right)
+    if left < -1 or right < -1 or left > 2**31 - 1 or right > 2**31 - 1:
+        raise ValueError(f"window_size {tuple(window_size)!r}: each side must be >= -1 (-1 = unbounded) and fit in int32")
+    return left, right
+
+
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, causal=False, num_splits=0, return_softmax_lse=False, *,
-                            block_table=None):
+                            block_table=None, window_size=(-1, -1)):
     """Decode attention over a KV cache (upstream flash-attn's ``flash_attn_with_kvcache`` conventions; forward only).
 
     q: (batch, seqlen_q, nheads, d); k_cache, v_cache: (batch, seqlen_cache, nheads_k, d), any batch / row / head strides (used in place).
@@ -95,12 +111,25 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     capacity is max_blocks_per_seq * page_block_size and takes the part of seqlen_cache above; the append writes through the table.
     Entries past the pages a sequence needs are never read.  A needed entry outside [0, num_blocks) breaks the precondition: it is
     clamped, min(uint32(entry), num_blocks - 1), so it reads (or the append writes) page num_blocks - 1 and nothing outside the pool.
+
+    window_size (keyword, (left, right) ints >= -1): sliding-window (local) attention, upstream flash-attn's convention.  Key j of sequence i
+    is visible to query t when L_i - seqlen_q + t - left <= j <= L_i - seqlen_q + t + right (and j < L_i); -1 = unbounded on that side,
+    (-1, -1) = no window.  ``causal`` sets the right edge to 0 and ``right`` is then ignored: window_size=(W - 1, 0) with causal=True is the
+    usual "last W keys" window.  A row that sees no key is O = 0, LSE = 0.  Lengths stay on the device and the window is a host value, so a
+    windowed call needs no synchronisation and can be captured in a graph and replayed with new cache_seqlens.  A window with a left edge
+    reads only the keys it can see: the split is sized from left + seqlen_q + right instead of the capacity (never more splits or workspace
+    than without the window).  Cache rows below max(0, L_i - seqlen_q - left) and at or past L_i - in a paged cache, and the table entries of
+    pages that lie wholly outside that range - are never read into a result.  The NaN contract above holds within the window.  Like under
+    causal with seqlen_q > 1, the query rows of a call share K / V reads: the seqlen_q x (nheads / nheads_k) rows of a KV head go through the
+    kernels in tiles of 16, and a non-finite V element in a row that another query row of the same tile sees, but this row does not, can make
+    this row's O NaN (its weight for that row is 0, and 0 x NaN is NaN).
     """
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v)):
         raise RuntimeError("flash_attn_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
     if (k is None) != (v is None):
         raise ValueError("k and v must both be given or both be None")
+    left, right = _window_pair(window_size)
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=q.device)
-    out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table)
+    out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right)
     return (out, lse) if return_softmax_lse else out

@@ -201,6 +201,28 @@ typedef struct fa_kvcache_params {
     int32_t num_blocks;             /* pages in the pool */
 } fa_kvcache_params;
 
+/* Options of a decode call that fa_kvcache_params does not carry (its layout is fixed; the _ex entry points below take both).  Same ABI 4
+ * header rule (FA_PARAMS_INIT): a zeroed struct means today's behaviour, and options appended later (decode softmax scale, softcap, rotary
+ * embedding on append) will be optional fields after these.  A NULL options pointer is the same as a zeroed struct.
+ * Sliding window (upstream flash-attn's window_size; is_local = 0: no window, the two sizes are not read).  Key j of sequence i (valid
+ * length L_i as above) is visible to query t when
+ *     L_i - seqlen_q + t - window_size_left <= j <= L_i - seqlen_q + t + window_size_right,
+ * with -1 = unbounded on that side and j < L_i always; values below -1 are FA_ERR_BAD_SHAPE.  is_causal sets the right edge to 0 (the right
+ * size is then ignored): (W - 1, 0) with is_causal is the usual "last W keys" window, and (0, 0) is a legitimate window of one key.  A
+ * window that cannot bind (both sides -1, left >= seqlen_cache - 1 with right -1 or causal, ...) runs exactly the call without it (same
+ * kernels, split, workspace and bits).  Cache rows below max(0, L_i - seqlen_q - left) and at or past L_i, and table entries of pages that
+ * lie wholly outside [that row, L_i), are never read into a result.  A window with a left edge sizes the split from its span instead of the
+ * capacity: the split and the workspace are never larger than without the window.  A row that sees no key gives o = 0, lse = 0.  A
+ * non-finite V element in a row that another query row of the same KV head and row tile sees (the seqlen_q x h / h_k rows of a KV head go
+ * through the kernels in tiles of 16) but this row does not can make this row's o NaN, as under causal with seqlen_q > 1. */
+typedef struct fa_kvcache_options {
+    uint32_t struct_size;       /* sizeof(fa_kvcache_options) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    int32_t is_local;           /* != 0: the window below applies */
+    int32_t window_size_left;   /* >= -1 */
+    int32_t window_size_right;  /* >= -1; ignored under is_causal */
+} fa_kvcache_options;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -259,6 +281,11 @@ int fa_run_mha_fwd_kvcache(const fa_kvcache_params* params, void* stream);
 int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* params);
 /* Key splits the launch of these params would use, workspace fields included (NULL / 0 -> 1).  Host-only.  Negative = error code. */
 int32_t fa_kvcache_num_splits(const fa_kvcache_params* params);
+/* The same three with options (fa_kvcache_options above; NULL = the plain calls).  Their presence is how a caller detects the window.
+ * Options are validated before anything is launched: a bad header is FA_ERR_BAD_ABI, a window size below -1 FA_ERR_BAD_SHAPE. */
+int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* params, const fa_kvcache_options* options, void* stream);
+int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);
+int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);
 
 /* ---- measurement helpers ----------------------------------------------------------------- */
 /* Algorithmic FLOPs of one forward call (4*b*h*sq*sk*d, causal counts only visible pairs);

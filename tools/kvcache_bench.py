@@ -9,8 +9,17 @@ Infinity Cache.  Usage: python tools/kvcache_bench.py [--quick] [--rounds N] [--
 
 --paged P (repeatable) measures a paged cache instead: per grid point and page size P, the paged call (block_table over a pool whose pages
 are assigned by a random permutation) against the contiguous call on the same data (the pool gathered into (b, L, h_k, d)), interleaved,
-medians; ms and TB/s of both and paged / contiguous."""
+medians; ms and TB/s of both and paged / contiguous.
+
+--window LEFT (repeatable) measures a sliding window instead: per grid point, the windowed call (causal, window_size=(LEFT, 0)) against the
+unwindowed causal call on the same caches and against the unwindowed causal call on caches of the window's length (LEFT + 1 rows),
+interleaved, medians.  TB/s counts the bytes the window actually reads.  Caches rotate until the windows alone exceed 256 MiB.
+
+--baseline-library PATH records an interleaved A/B of the plain (no window) call through the C ABI of this build and of the library at
+PATH (e.g. a build of the parent commit), on the same data; the outputs must agree bit for bit.  --length L (repeatable) replaces the
+grid's cache lengths."""
 import argparse
+import ctypes
 import itertools
 import json
 import math
@@ -29,10 +38,12 @@ HBM_ACHIEVABLE, HBM_PEAK = 6.3e12, 8.0e12
 WORKING_SET = 256 << 20
 
 
-def grid(quick):
+def grid(quick, lengths=None):
     bs, heads, ds, ls, sqs = (1, 8, 32), ((32, 32), (32, 8), (32, 1)), (64, 128), (4096, 32768, 131072), (1, 4)
     if quick:
         bs, ls = (1, 8), (32768,)
+    if lengths:
+        ls = tuple(lengths)
     for b, (h, hk), d, L, sq in itertools.product(bs, heads, ds, ls, sqs):
         for dt in ((torch.float16, torch.bfloat16) if d == 128 else (torch.float16,)):
             yield dict(b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=sq, dtype=dt)
@@ -126,6 +137,106 @@ def run_paged_point(pt, page, rounds):
                 paged_over_contiguous=round(ms_pg / ms_ct, 3))
 
 
+def _rotation(kv_bytes, read_bytes, budget=32 << 30):
+    """caches to rotate over: enough that the bytes one call reads, summed over the rotation, exceed the working set (at most 512, and no
+    more than the memory budget allows)"""
+    n = max(1, min(512, math.ceil(WORKING_SET / max(read_bytes, 1))))
+    return max(1, min(n, budget // max(kv_bytes, 1)))
+
+
+def run_window_point(pt, left, rounds):
+    dev = torch.device("cuda:0")
+    b, h, hk, d, L, sq, dt = pt["b"], pt["h"], pt["h_k"], pt["d"], pt["L"], pt["seqlen_q"], pt["dtype"]
+    lw = min(L, left + 1)                                     # rows of the short cache: the window's length
+    keys = min(L, left + sq)                                  # keys the window reads per (batch, KV head): lo of row 0 .. L
+    kv_bytes, win_bytes, short_bytes = (2 * b * n_ * hk * d * 2 for n_ in (L, keys, lw))
+    n = _rotation(kv_bytes, win_bytes)
+    n_s = _rotation(short_bytes, short_bytes)
+    mk = lambda rows: (torch.empty(b, rows, hk, d, device=dev, dtype=dt).uniform_(-2, 2), torch.empty(b, rows, hk, d, device=dev, dtype=dt).uniform_(-2, 2))
+    big = [mk(L) for _ in range(n)]
+    short = [mk(lw) for _ in range(n_s)]
+    q = torch.randn(b, sq, h, d, device=dev, dtype=dt)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    cs_s = torch.full((b,), lw, dtype=torch.int32, device=dev)
+    win = lambda i: F.flash_attn_with_kvcache(q, big[i % n][0], big[i % n][1], cache_seqlens=cs, causal=True, window_size=(left, 0))
+    full = lambda i: F.flash_attn_with_kvcache(q, big[i % n][0], big[i % n][1], cache_seqlens=cs, causal=True)
+    sh = lambda i: F.flash_attn_with_kvcache(q, short[i % n_s][0], short[i % n_s][1], cache_seqlens=cs_s, causal=True)
+    win(0), full(0), sh(0)
+    torch.cuda.synchronize()
+    t_w, t_f, t_s = [], [], []
+    for _ in range(rounds):
+        t_w.append(time_rotation(win, n, 20))
+        t_f.append(time_rotation(full, n, 20))
+        t_s.append(time_rotation(sh, n_s, 20))
+    ms_w, ms_f, ms_s = statistics.median(t_w), statistics.median(t_f), statistics.median(t_s)
+    p = capi.kvcache_params(q, big[0][0], big[0][1], torch.empty_like(q), torch.empty(b, h, sq, device=dev), cache_seqlens=cs, causal=True)
+    opt = capi.kvcache_options((left, 0))
+    ws = capi.kvcache_workspace_bytes(p, opt)
+    n_split = max(1, ws and capi.kvcache_num_splits(_with_ws(p, ws), opt))
+    ws_f = capi.kvcache_workspace_bytes(p)
+    n_split_f = max(1, ws_f and capi.kvcache_num_splits(_with_ws(p, ws_f)))
+    rows = b * h * sq
+    moved = win_bytes + 2 * rows * d * 2 + rows * 4 + (2 * n_split * rows * (d + 1) * 4 if n_split > 1 else 0)
+    del big, short
+    torch.cuda.empty_cache()
+    return dict(b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=sq, dtype=str(dt).replace("torch.", ""), window=[left, 0], causal=True,
+                caches_rotated=[n, n_s], ms_window=round(ms_w, 5), ms_unwindowed=round(ms_f, 5), ms_short_cache=round(ms_s, 5),
+                window_bytes=moved, tbps_window=round(moved / (ms_w * 1e-3) / 1e12, 3), n_split_window=n_split, n_split_unwindowed=n_split_f,
+                unwindowed_over_window=round(ms_f / ms_w, 2), window_over_short=round(ms_w / ms_s, 3))
+
+
+def _baseline_lib(path):
+    L = ctypes.CDLL(os.path.abspath(path))
+    L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
+    L.fa_run_mha_fwd_kvcache.restype = ctypes.c_int
+    L.fa_kvcache_workspace_bytes.argtypes = [ctypes.POINTER(capi.KvcacheParams)]
+    L.fa_kvcache_workspace_bytes.restype = ctypes.c_int64
+    L.fa_build_info.restype = ctypes.c_char_p
+    return L
+
+
+def run_ab_point(pt, base, rounds):
+    """the plain call through this build's C ABI (A) and the baseline library's (B), interleaved, on the same caches"""
+    dev = torch.device("cuda:0")
+    b, h, hk, d, L, sq, dt = pt["b"], pt["h"], pt["h_k"], pt["d"], pt["L"], pt["seqlen_q"], pt["dtype"]
+    kv_bytes = 2 * b * L * hk * d * 2
+    n = _rotation(kv_bytes, kv_bytes)
+    caches = [(torch.empty(b, L, hk, d, device=dev, dtype=dt).uniform_(-2, 2), torch.empty(b, L, hk, d, device=dev, dtype=dt).uniform_(-2, 2))
+              for _ in range(n)]
+    q = torch.randn(b, sq, h, d, device=dev, dtype=dt)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    outs = {}
+    libs = {"A": capi.lib(), "B": base}
+    params = {}
+    for tag, lib in libs.items():
+        o, lse = torch.empty_like(q), torch.empty(b, h, sq, device=dev)
+        ps = [capi.kvcache_params(q, kc, vc, o, lse, cache_seqlens=cs) for kc, vc in caches]
+        ws = int(lib.fa_kvcache_workspace_bytes(ctypes.byref(ps[0])))
+        buf = torch.empty(max(ws, 16) // 4, device=dev, dtype=torch.float32)
+        for p in ps:
+            p.workspace, p.workspace_bytes = (buf.data_ptr(), ws) if ws > 0 else (None, 0)
+        params[tag] = (ps, o, lse, buf)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call(tag):
+        lib, (ps, _, _, _) = libs[tag], params[tag]
+        return lambda i: capi.check(lib.fa_run_mha_fwd_kvcache(ctypes.byref(ps[i]), stream))
+
+    fa, fb = call("A"), call("B")
+    fa(0), fb(0)
+    torch.cuda.synchronize()
+    same = torch.equal(params["A"][1], params["B"][1]) and torch.equal(params["A"][2], params["B"][2])
+    t_a, t_b = [], []
+    for _ in range(rounds):
+        t_a.append(time_rotation(fa, n, 20))
+        t_b.append(time_rotation(fb, n, 20))
+    ms_a, ms_b = statistics.median(t_a), statistics.median(t_b)
+    del caches, params
+    torch.cuda.empty_cache()
+    return dict(b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=sq, dtype=str(dt).replace("torch.", ""), kv_gb=round(kv_bytes / 1e9, 3), caches_rotated=n,
+                ms_this=round(ms_a, 5), ms_baseline=round(ms_b, 5), this_over_baseline=round(ms_a / ms_b, 4), bit_identical=bool(same))
+
+
 def _with_ws(p, ws):
     buf = torch.empty(ws // 4, device="cuda:0", dtype=torch.float32)
     p.workspace, p.workspace_bytes = buf.data_ptr(), ws
@@ -138,12 +249,23 @@ def main():
     ap.add_argument("--quick", action="store_true", help="b in {1, 8}, L = 32k only")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--paged", type=int, action="append", metavar="P", help="page size (a multiple of 16); repeat for several")
+    ap.add_argument("--window", type=int, action="append", metavar="LEFT", help="sliding window (LEFT, 0), causal; repeat for several")
+    ap.add_argument("--baseline-library", metavar="PATH", help="A/B of the plain call against this libflash_attn_gfx950.so")
+    ap.add_argument("--length", type=int, action="append", metavar="L", help="cache length(s) instead of the grid's")
     a = ap.parse_args()
+    base = _baseline_lib(a.baseline_library) if a.baseline_library else None
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
           flush=True)
+    if base is not None:
+        print(json.dumps({"baseline_library": base.fa_build_info().decode()}), flush=True)
     with torch.no_grad():
-        for pt in grid(a.quick):
-            if a.paged:
+        for pt in grid(a.quick, a.length):
+            if base is not None:
+                print(json.dumps(run_ab_point(pt, base, a.rounds)), flush=True)
+            elif a.window:
+                for left in a.window:
+                    print(json.dumps(run_window_point(pt, left, a.rounds)), flush=True)
+            elif a.paged:
                 for page in a.paged:
                     print(json.dumps(run_paged_point(pt, page, a.rounds)), flush=True)
             else:
