@@ -32,6 +32,17 @@
  *   device arrays of length batch+1, lse padded to (batch, nheads, max_seqlen_q).
  *   head_dim in {64, 128} (static_switch.h:29-38); unlike the reference an unsupported
  *   head_dim is an error, not a silent no-op.
+ *   Non-finite Q / K (forward): a NaN in a query row, or a NaN or +inf score (NaN or inf in a
+ *   K row the query sees) gives that row o = NaN and lse = NaN, never +-inf; a -inf score only
+ *   drops its key; a row that sees no key stays o = 0, lse = 0.  Rows the bad value does not
+ *   reach keep their bits, except the other rows of a +inf row's 32-row wave: the running max
+ *   is refreshed per wave, so they round P differently (within the usual tolerances).
+ *   Non-finite V and a non-finite backward are unspecified: a masked P = 0 still multiplies V
+ *   within a key tile, and 0 x NaN is NaN.
+ *   Memory: views are never read or written outside their extent (strides may leave gaps
+ *   between rows, heads and batch entries).  Packed: rows of q / k / v / dout past
+ *   cu_seqlens[b] (up to total_q / total_k) are never read, and the padded lse entries
+ *   (t >= seqlen of the sequence) and the padding rows of o / dq / dk / dv are never written.
  *
  * Every function returns FA_OK (0) or a negative FA_ERR_* code; positive values are
  * hipError_t codes from the launch.  fa_last_error() gives a human readable message for

@@ -207,6 +207,76 @@ def check_kvcache_rows(out, lse, q, k_cache, v_cache, lens, causal, dtname, tag,
         err = float(np.abs(lse[i:i + 1].cpu().numpy() - lse_ref).max())
         assert err <= LSE_TOL, f"{tag}: LSE b{i} L{L} err {err}"
 
+
+# ---- edge-case helpers shared by the edges suites (tests/test_kvcache_edges_gpu.py, tests/test_attention_edges_gpu.py) ------------------
+
+POISON = (float("nan"), float("inf"), float("-inf"), 65504.0)
+SENT16 = 0x7E5A          # an fp16 / bf16 NaN payload nobody computes
+
+
+def bits(t):
+    """the bit pattern of a 16- or 32-bit tensor, for exact comparisons (NaN payloads included)"""
+    return t.view(torch_int(t.element_size()))
+
+
+def torch_int(nbytes):
+    import torch
+
+    return {2: torch.int16, 4: torch.int32}[nbytes]
+
+
+def poison_(t):
+    """fill t (any view) with NaN, +inf, -inf and 65504, cycling along the last dim"""
+    import torch
+
+    vals = torch.tensor(POISON, dtype=torch.float32, device=t.device).to(t.dtype)
+    idx = torch.arange(t.shape[-1], device=t.device) % len(POISON)
+    t.copy_(vals[idx].expand(t.shape))
+    return t
+
+
+def guarded(shape, dt, dev, pad, fill=SENT16):
+    """a buffer filled with the 16-bit pattern `fill` (fill=None: the POISON cycle) with `pad` extra elements on every dim, and the view
+    of `shape` into it (offset by pad // 2 on every dim but the last, 8 elements on the last: rows stay 16-byte aligned); returns
+    (buffer, view, index of the view)"""
+    import torch
+
+    full = [s + p for s, p in zip(shape, pad)]
+    if fill is None:
+        buf = poison_(torch.empty(full, dtype=dt, device=dev))
+    else:
+        buf = torch.full(full, fill, dtype=torch.int16, device=dev).view(dt)
+    sl = tuple(slice(p // 2, p // 2 + s) for s, p in zip(shape[:-1], pad[:-1])) + (slice(8, 8 + shape[-1]),)
+    return buf, buf[sl], sl
+
+
+def fp64_math(q, k, v, causal, device="cpu"):
+    """plain fp64 attention of ONE batch entry, no special cases beyond the contract's dead rows: q (sq, h, d), k / v (L, hk, d) ->
+    O (sq, h, d), LSE (h, sq), on `device`.  NaN / inf propagate as IEEE arithmetic makes them (max and exp included).  The causal mask
+    is bottom-right aligned: key j is hidden from query t when j > L - sq + t."""
+    import math
+
+    import torch
+
+    q, k, v = (t.detach().to(device=device, dtype=torch.float64) for t in (q, k, v))
+    sq, h, d = q.shape
+    L, hk = k.shape[0], k.shape[1]
+    kt, vt = k.repeat_interleave(h // hk, dim=1), v.repeat_interleave(h // hk, dim=1)
+    s = torch.einsum("thd,jhd->htj", q, kt) / math.sqrt(d)
+    if causal:
+        t = torch.arange(sq, device=device).view(-1, 1)
+        j = torch.arange(L, device=device).view(1, -1)
+        s = s.masked_fill((j > L - sq + t).unsqueeze(0), float("-inf"))
+    m = s.amax(dim=-1) if L > 0 else torch.full((h, sq), float("-inf"), dtype=torch.float64, device=device)
+    dead = m == float("-inf")
+    p = torch.exp(s - torch.where(dead, torch.zeros_like(m), m).unsqueeze(-1))
+    l = p.sum(dim=-1)
+    lse = torch.where(dead, torch.zeros_like(m), m + torch.log(l))
+    o = torch.einsum("htj,jhd->thd", p, vt) / l.t().unsqueeze(-1)
+    o = torch.where(dead.t().unsqueeze(-1), torch.zeros_like(o), o)
+    return o, lse
+
+
 def golden_names(varlen=None):
     names = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz")))
     if varlen is True:

@@ -189,8 +189,9 @@ def _layouts(b, s_q, s_k, h, hk, d, tdt, gpu, gen):
         return t.permute(1, 0, 2, 3).contiguous().permute(1, 0, 2, 3)
 
     def padded(t, ps, ph, pd, off):
+        # the gaps hold NaN, +-inf and 65504: a kernel that read one into a score or weighted it with P = 0 would change the result
         bb, ss, hh, dd = t.shape
-        buf = torch.zeros(bb, ss + ps + off, hh + ph, dd + pd, device=t.device, dtype=t.dtype)
+        buf = U.poison_(torch.empty(bb, ss + ps + off, hh + ph, dd + pd, device=t.device, dtype=t.dtype))
         view = buf[:, off:off + ss, :hh, :dd]
         view.copy_(t)
         return view

@@ -8,7 +8,6 @@ math (_util.check_kvcache_rows, _util.assert_close, _util.LSE_TOL).  On top of t
     workspace) is never read into a result and never written;
   * split boundaries, the split cap, long contexts, odd query-row packings, softmax extremes across waves and splits, 64-bit batch offsets,
     batch invariances and a decode loop replayed from a graph."""
-import math
 
 import pytest
 import torch
@@ -22,23 +21,13 @@ pytestmark = pytest.mark.gpu
 DT = {"fp16": torch.float16, "bf16": torch.bfloat16}
 STEP = 32                # keys per wave step, the split granularity (kKvcStep)
 MAX_SPLITS = 128         # the automatic rule's cap (kKvcMaxSplits)
-POISON = (float("nan"), float("inf"), float("-inf"), 65504.0)
 
 
 def _rand(shape, dt, gen, dev):
     return torch.randn(*shape, device=dev, dtype=torch.float32, generator=gen).to(dt)
 
 
-def _bits(t):
-    return t.view(torch.int16) if t.element_size() == 2 else t.view(torch.int32)
-
-
-def _poison_(t):
-    """fill t (any view) with NaN, +inf, -inf and 65504, cycling along the last dim"""
-    vals = torch.tensor(POISON, dtype=torch.float32, device=t.device).to(t.dtype)
-    idx = torch.arange(t.shape[-1], device=t.device) % len(POISON)
-    t.copy_(vals[idx].expand(t.shape))
-    return t
+_bits, _poison_ = U.bits, U.poison_
 
 
 def _ws(nbytes, dev, fill=float("nan"), guard=64):
@@ -70,26 +59,7 @@ def _run(q, kc, vc, o, lse, cs, causal=False, num_splits=0, k_new=None, v_new=No
 
 # ---- 1. non-finite inputs ------------------------------------------------------------------------------------------------------------
 
-def _fp64_math(q, k, v, causal):
-    """plain fp64 attention of ONE batch entry, no special cases beyond the contract's dead rows: q (sq, h, d), k / v (L, hk, d) ->
-    O (sq, h, d), LSE (h, sq).  NaN / inf propagate as IEEE arithmetic makes them (max and exp included)."""
-    q, k, v = (t.detach().double().cpu() for t in (q, k, v))
-    sq, h, d = q.shape
-    L, hk = k.shape[0], k.shape[1]
-    kt, vt = k.repeat_interleave(h // hk, dim=1), v.repeat_interleave(h // hk, dim=1)
-    s = torch.einsum("thd,jhd->htj", q, kt) / math.sqrt(d)
-    if causal:
-        t = torch.arange(sq).view(-1, 1)
-        j = torch.arange(L).view(1, -1)
-        s = s.masked_fill((j > L - sq + t).unsqueeze(0), float("-inf"))
-    m = s.amax(dim=-1) if L > 0 else torch.full((h, sq), float("-inf"), dtype=torch.float64)
-    dead = m == float("-inf")
-    p = torch.exp(s - torch.where(dead, torch.zeros_like(m), m).unsqueeze(-1))
-    l = p.sum(dim=-1)
-    lse = torch.where(dead, torch.zeros_like(m), m + torch.log(l))
-    o = torch.einsum("htj,jhd->thd", p, vt) / l.t().unsqueeze(-1)
-    o = torch.where(dead.t().unsqueeze(-1), torch.zeros_like(o), o)
-    return o, lse
+_fp64_math = U.fp64_math
 
 
 @pytest.mark.parametrize("num_splits", [1, 2, 0])
@@ -206,16 +176,7 @@ def test_prefilled_outputs_and_workspace_are_fully_written(gpu, num_splits):
         U.check_kvcache_rows(o, lse, q, k_cache, v_cache, lens, causal, "fp16", f"prefilled causal={causal} n{n}")
 
 
-SENT16 = 0x7E5A          # an fp16 / bf16 NaN payload nobody computes
-
-
-def _guarded(shape, dt, dev, pad):
-    """a sentinel-filled buffer with `pad` extra elements on every dim, and the view of `shape` into it (offset by pad // 2 on every dim
-    but the last, 8 elements on the last: rows stay 16-byte aligned)"""
-    full = [s + p for s, p in zip(shape, pad)]
-    buf = torch.full(full, SENT16, dtype=torch.int16, device=dev).view(dt)
-    sl = tuple(slice(p // 2, p // 2 + s) for s, p in zip(shape[:-1], pad[:-1])) + (slice(8, 8 + shape[-1]),)
-    return buf, buf[sl], sl
+_guarded = U.guarded
 
 
 @pytest.mark.parametrize("causal", [False, True])

@@ -489,7 +489,7 @@ def test_dkdv_head_group_split_matches_single_pass(gpu, h, hk, d, causal):
         assert need > 0 and need % (2 * b * s * hk * d * 4) == 0, need        # whole planes: 2 tensors x n_split x rows x h_k x d fp32
         if mode != "none":
             n = need if mode != "half" else need // 2
-            ws = torch.empty(n // 4, device=gpu, dtype=torch.float32)
+            ws = torch.full((n // 4,), float("nan"), device=gpu, dtype=torch.float32)      # contents are unspecified: nothing may be read before written
             p.workspace, p.workspace_bytes = ws.data_ptr(), n
         capi.check(capi.lib().fa_run_mha_bwd(ctypes.byref(p), torch.cuda.current_stream().cuda_stream))
         torch.cuda.synchronize()
@@ -518,8 +518,10 @@ def test_dkdv_split_on_packed_sequences_with_padding_rows(gpu):
     total = int(cu[-1])
     q, do = _rand(gpu, (total, h, d), torch.float16, 5), _rand(gpu, (total, h, d), torch.float16, 6)
     k, v = _rand(gpu, (total + 64, hk, d), torch.float16, 7), _rand(gpu, (total + 64, hk, d), torch.float16, 8)   # 64 padding rows
+    U.poison_(k[total:]); U.poison_(v[total:])          # NaN, +-inf, 65504: never read into a sequence's result
     o, lse = F.varlen_fwd(q, k, v, cu, cu, max(lens), max(lens), True)
     dq, dk, dv = F.varlen_bwd(q, k, v, o, lse, do, cu, cu, max(lens), max(lens), True)
+    assert (dk[total:] == 0).all().item() and (dv[total:] == 0).all().item(), "padding rows of dK / dV: the host module's zero fill"
     for i, n in enumerate(lens):
         a, e = int(cu[i]), int(cu[i + 1])
         _, _, dq_r, dk_r, dv_r = U.torch_attention_ref(q[a:e][None], k[a:e][None], v[a:e][None], do[a:e][None], True)
