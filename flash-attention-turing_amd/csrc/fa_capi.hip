@@ -42,6 +42,18 @@ int check_tensor(const char* name, const void* ptr, const fa_strides& st, int64_
     return FA_OK;
 }
 
+// The same for an 8-bit (e4m3) cache, strides in 1-byte elements: the kernels keep 16-byte loads, so everything is a multiple of 16 elements.
+int check_cache8(const char* name, const void* ptr, const fa_strides& st, int64_t rows, int d) {
+    if (ptr == nullptr) return fail(FA_ERR_NULL_POINTER, "%s is NULL", name);
+    if (((uintptr_t)ptr & 15) != 0) return fail(FA_ERR_BAD_STRIDE, "%s base pointer must be 16-byte aligned", name);
+    if (st.row < d || st.head < 0 || (st.row % 16) != 0 || (st.head % 16) != 0 || (st.batch % 16) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "%s (8-bit cache) strides (batch=%lld,row=%lld,head=%lld) must be multiples of 16 elements (16-byte loads) with row >= head_dim",
+                    name, (long long)st.batch, (long long)st.row, (long long)st.head);
+    if (rows * st.row >= ((int64_t)1 << 31))
+        return fail(FA_ERR_BAD_STRIDE, "%s: one sequence spans %lld bytes (limit 2^31)", name, (long long)(rows * st.row));
+    return FA_OK;
+}
+
 int check_common(int b, int sq, int sk, int h, int hk, int d, int dtype) {
     if (b < 0 || sq < 0 || sk < 0 || h <= 0 || hk <= 0)
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d seqlen_k=%d h=%d h_k=%d", b, sq, sk, h, hk);
@@ -331,8 +343,28 @@ int fa_mha_varlen_bwd(const void* q, const void* k, const void* v, const void* o
     return fa_run_mha_bwd(&p, stream);
 }
 
+// The options pointer of the _ex entry points -> a zeroed fa_kvcache_options_v2 filled with what the caller's struct carries: struct_size says
+// which of the two layouts it is (fa_kvcache_options: the window alone; fa_kvcache_options_v2: plus the 8-bit cache fields).  NULL = all zero.
+static int import_kvcache_options(const fa_kvcache_options* user, fa_kvcache_options_v2& o) {
+    memset(&o, 0, sizeof(o));
+    if (user == nullptr) return FA_OK;
+    if (user->magic != FA_PARAMS_MAGIC)
+        return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: no {struct_size, magic} header (FA_PARAMS_INIT); recompile against include/flash_attn_gfx950.h (ABI %d)", FA_ABI_VERSION);
+    if (user->struct_size != sizeof(fa_kvcache_options) && user->struct_size != sizeof(fa_kvcache_options_v2))
+        return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: struct_size %u is neither sizeof(fa_kvcache_options) = %zu nor sizeof(fa_kvcache_options_v2) = %zu - header / library mismatch",
+                    user->struct_size, sizeof(fa_kvcache_options), sizeof(fa_kvcache_options_v2));
+    memcpy(&o, user, user->struct_size);
+    if (o.cache_dtype != 0 && o.cache_dtype != FA_CACHE_FP8_E4M3)
+        return fail(FA_ERR_BAD_DTYPE, "cache_dtype %d unsupported (0 = the dtype of q, %d = FA_CACHE_FP8_E4M3; e4m3fnuz and e5m2 caches are not supported)", o.cache_dtype,
+                    FA_CACHE_FP8_E4M3);
+    if (o.cache_dtype == 0 && (o.k_descale != nullptr || o.v_descale != nullptr))
+        return fail(FA_ERR_BAD_DTYPE, "k_descale / v_descale need cache_dtype = FA_CACHE_FP8_E4M3 (a 16-bit cache has no descale)");
+    return FA_OK;
+}
+
 // with_workspace = false: the `workspace` fields are not looked at (fa_kvcache_workspace_bytes)
-static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& kp, fa_kvcache_params& local, bool with_workspace) {
+static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& kp, fa_kvcache_params& local, bool with_workspace,
+                        const fa_kvcache_options_v2& o) {
     // the paged-cache fields are optional: a caller built before them passes struct_size = offsetof(block_table) and gets NULL / 0
     int rc = import_params(user, local, "fa_kvcache_params", offsetof(fa_kvcache_params, block_table));
     if (rc) return rc;
@@ -372,8 +404,14 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
         if ((rc = check_tensor("o", p->o, p->o_stride, p->seqlen_q, p->d, false))) return rc;
         // paged: the descriptors span at most one page, so the 2^31-byte limit applies per page (page offsets are 64-bit)
         const int64_t cache_rows = paged ? p->page_block_size : p->seqlen_cache;
-        if ((rc = check_tensor("k_cache", p->k_cache, p->k_cache_stride, cache_rows, p->d, false))) return rc;
-        if ((rc = check_tensor("v_cache", p->v_cache, p->v_cache_stride, cache_rows, p->d, false))) return rc;
+        if (o.cache_dtype == FA_CACHE_FP8_E4M3) {
+            if ((rc = check_cache8("k_cache", p->k_cache, p->k_cache_stride, cache_rows, p->d))) return rc;
+            if ((rc = check_cache8("v_cache", p->v_cache, p->v_cache_stride, cache_rows, p->d))) return rc;
+            if (((uintptr_t)o.k_descale & 3) != 0 || ((uintptr_t)o.v_descale & 3) != 0) return fail(FA_ERR_BAD_STRIDE, "k_descale / v_descale must be 4-byte aligned");
+        } else {
+            if ((rc = check_tensor("k_cache", p->k_cache, p->k_cache_stride, cache_rows, p->d, false))) return rc;
+            if ((rc = check_tensor("v_cache", p->v_cache, p->v_cache_stride, cache_rows, p->d, false))) return rc;
+        }
         if (p->k_new != nullptr) {
             if ((rc = check_tensor("k_new", p->k_new, p->k_new_stride, p->seqlen_new, p->d, false))) return rc;
             if ((rc = check_tensor("v_new", p->v_new, p->v_new_stride, p->seqlen_new, p->d, false))) return rc;
@@ -393,17 +431,18 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
         kp.block_table = p->block_table; kp.bt_stride = p->block_table_stride;
         kp.page_size = p->page_block_size; kp.num_blocks = p->num_blocks;
     }
+    if (o.cache_dtype == FA_CACHE_FP8_E4M3) {
+        kp.cache_fp8 = 1;
+        kp.k_descale = o.k_descale; kp.kds_batch = o.k_descale_batch_stride; kp.kds_head = o.k_descale_head_stride;
+        kp.v_descale = o.v_descale; kp.vds_batch = o.v_descale_batch_stride; kp.vds_head = o.v_descale_head_stride;
+    }
     return FA_OK;
 }
 
 // fa_kvcache_options (NULL = none) -> the window fields of kp, normalised: right = 0 under causal, and a side that cannot bind is -1 (left >=
 // seqlen_cache - 1: lo_t <= L - 1 - left <= 0 for every row; right >= seqlen_q - 1: lim_t >= L for every row).  A window whose left side is
 // unbounded and whose right side is unbounded or the causal limit is exactly the plain call: is_local stays 0 (the plain kernels, split and bits).
-static int fill_kvcache_options(const fa_kvcache_options* user, fa::KvcacheKernelParams& kp) {
-    if (user == nullptr) return FA_OK;
-    fa_kvcache_options o;
-    int rc = import_params(user, o, "fa_kvcache_options", offsetof(fa_kvcache_options, window_size_right) + sizeof(int32_t));
-    if (rc) return rc;
+static int fill_kvcache_window(const fa_kvcache_options_v2& o, fa::KvcacheKernelParams& kp) {
     if (!o.is_local) return FA_OK;
     if (o.window_size_left < -1 || o.window_size_right < -1)
         return fail(FA_ERR_BAD_SHAPE, "window_size (%d, %d): each side must be >= -1 (-1 = unbounded)", o.window_size_left, o.window_size_right);
@@ -416,11 +455,30 @@ static int fill_kvcache_options(const fa_kvcache_options* user, fa::KvcacheKerne
     return FA_OK;
 }
 
+// Params first, as before the options existed (their errors win), except that the cache tensors are checked under the cache dtype the
+// options state; then the options' own values.
+static int fill_kvcache_all(const fa_kvcache_params* user, const fa_kvcache_options* options, fa::KvcacheKernelParams& kp, fa_kvcache_params& local,
+                            fa_kvcache_options_v2& o, bool with_workspace) {
+    fa_kvcache_options_v2 none;
+    memset(&none, 0, sizeof(none));
+    const int orc = import_kvcache_options(options, o);
+    char oerr[sizeof(g_err)];
+    memcpy(oerr, g_err, sizeof(oerr));
+    int rc = fill_kvcache(user, kp, local, with_workspace, orc ? none : o);
+    if (rc) return rc;
+    if (orc) {
+        memcpy(g_err, oerr, sizeof(g_err));
+        return orc;
+    }
+    return fill_kvcache_window(o, kp);
+}
+
 int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    int rc = fill_kvcache(user, kp, local, false);
-    if (rc || (rc = fill_kvcache_options(options, kp))) return rc;
+    fa_kvcache_options_v2 o;
+    int rc = fill_kvcache_all(user, options, kp, local, o, false);
+    if (rc) return rc;
     if (kp.b == 0) return 0;
     return fa::kvcache_workspace_bytes(kp, fa::kvcache_split(kp, -1, local.num_splits));
 }
@@ -428,8 +486,9 @@ int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* user, const fa_kv
 int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    int rc = fill_kvcache(user, kp, local, true);
-    if (rc || (rc = fill_kvcache_options(options, kp))) return rc;
+    fa_kvcache_options_v2 o;
+    int rc = fill_kvcache_all(user, options, kp, local, o, true);
+    if (rc) return rc;
     if (kp.b == 0) return 1;
     return fa::kvcache_split(kp, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits);
 }
@@ -437,8 +496,9 @@ int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* user, const fa_kvcache
 int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* user, const fa_kvcache_options* options, void* stream) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    int rc = fill_kvcache(user, kp, local, true);
-    if (rc || (rc = fill_kvcache_options(options, kp))) return rc;
+    fa_kvcache_options_v2 o;
+    int rc = fill_kvcache_all(user, options, kp, local, o, true);
+    if (rc) return rc;
     if (kp.b == 0) return FA_OK;
     kp.n_split = fa::kvcache_split(kp, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits);
     kp.ws_o = kp.n_split > 1 ? (float*)local.workspace : nullptr;

@@ -21,8 +21,14 @@
 // Sliding window (the _local kernels, KvcacheKernelParams::is_local): each lane's row sees keys lo_t <= key < lim_t, and a workgroup's key range
 // starts at the 32-aligned base below the first row w0 its tile sees; its descriptors start at w0, so rows below w0 read as zeros like rows
 // at or past L.  The plain kernels are the same template with LOCAL = false: their code does not change.
+// 8-bit cache (the _fp8 kernels, KvcacheKernelParams::cache_fp8; template parameter ES = 1): K / V hold e4m3 codes, one byte per element.  The
+// loads stay 16 bytes per lane (so a K load carries two chunks' worth of a key and the d-elements of a k-slot are permuted, in Q alike; a V
+// load covers 16 elements of a row), the codes are widened to T in registers - exactly - in front of the same MFMAs and the same LDS image,
+// and the (batch, KV head) descales fold into the softmax scale (K) and the final normalisation (V).  The append quantises k_new / v_new.
 #include <hip/hip_runtime.h>
 #include <math.h>
+
+#include <type_traits>
 
 #include "fa_device.hpp"
 #include "fa_params.hpp"
@@ -36,6 +42,11 @@ constexpr int kKvcThreads = 64 * kKvcWaves;
 constexpr int kKvcMaxSplits = 128;
 constexpr int kKvcMinStepsPerSplit = 8;      // 256 keys: two steps per wave before a split pays its prologue and merge
 constexpr int kKvcCombineThreads = 256;
+// How the 8-bit kernels load K (DESIGN.md "FP8 KV cache"): 0 = 16 bytes per lane, the d-elements of a k-slot permuted (Q is loaded with the
+// same permutation); 1 = 8 bytes per lane and chunk in the 16-bit kernels' mapping.  The experiment switch of the measurement; 0 ships.
+#ifndef FA_KVC_FP8_KLOAD8
+#define FA_KVC_FP8_KLOAD8 0
+#endif
 
 template <int D>
 struct KvcLds {
@@ -54,21 +65,59 @@ FA_DEV int kvc_len(const KvcacheKernelParams& p, int bidx) {
     return __builtin_amdgcn_readfirstlane(L);
 }
 
+// Eight e4m3 codes (two words, bytes in element order) -> eight T: exact, every finite e4m3 value is a T value; the NaN codes become NaN.
+template <typename T>
+FA_DEV u32x4 widen8(uint32_t w0, uint32_t w1) {
+    if constexpr (sizeof(T) == 2 && __is_same(T, _Float16)) {
+        return u32x4{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, false)),
+                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, true)),
+                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, false)),
+                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, true))};
+    } else {
+        return u32x4{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false)),
+                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true)),
+                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false)),
+                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true))};
+    }
+}
+
 // The attention body of both cache layouts; PAGED changes how K / V rows are addressed (load_step), nothing else.
-template <typename T, int D, bool CAUSAL, bool PAGED, bool LOCAL = false>
+// ES = bytes per cache element: 2 = the dtype of q (T), 1 = FP8 e4m3 codes, widened to T in registers (widen8: exact) in front of the same
+// MFMAs; the descales of the (batch, KV head) fold into the softmax scale (K) and the final normalisation (V).  ES is a template
+// parameter: the ES = 2 instantiations are the code they were before the 8-bit cache existed.
+template <typename T, int D, bool CAUSAL, bool PAGED, bool LOCAL = false, int ES = 2>
 FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
+    static_assert(ES == 1 || ES == 2, "cache elements are 16-bit (the dtype of q) or 8-bit (e4m3)");
     constexpr int NC = D / 32;          // 16x16x32 MFMAs per 16 keys of S^T (d chunks)
     constexpr int NO = D / 16;          // O^T blocks of 16 columns
-    constexpr int SLOTS = D / 8;        // 16-byte slots per row
+    constexpr int SLOTS = D * ES / 16;  // 16-byte slots per cache row
     constexpr int VRPL = 64 / SLOTS;    // V rows per wave-wide 16-byte load
     constexpr int NV = kKvcStep / VRPL; // V loads per lane and step
+    constexpr bool K8 = ES == 1 && FA_KVC_FP8_KLOAD8;
+    constexpr int NK = K8 ? NC : NC * ES / 2;     // K loads per lane and 16-key block (16 bytes each; K8: 8 bytes)
+    using kfrag_t = std::conditional_t<K8, u32x2, u32x4>;
     __shared__ __attribute__((aligned(16))) char smem[KvcLds<D>::kBytes];
 
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, n16 = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int id = blockIdx.x;
-    const int split = id % p.n_split, rest = id / p.n_split;
-    const int tile = rest % p.n_row_tiles, bh = rest / p.n_row_tiles;
+    int split = id % p.n_split, rest = id / p.n_split;
+    int tile = rest % p.n_row_tiles, bh = rest / p.n_row_tiles;
+    // 8-bit head_dim 64: a (key, head) row is 64 bytes, half a 128-byte line whose other half belongs to the neighbouring KV head.  That
+    // head's workgroup is n_split x n_row_tiles launch slots away - for an unsplit launch on the next XCD (workgroup i runs on XCD i % 8),
+    // behind another L2, so every line comes from memory twice.  With an even h_k the two heads of a pair are therefore made neighbours in
+    // time on ONE XCD: workgroups i and i + 8 of every 16 take the two heads of a pair, and the pairs run through (split, tile, pair) in the
+    // usual order.  Only the order of the workgroups changes, not what any of them computes; the last gridDim.x % 16 keep their places
+    // among themselves.
+    if constexpr (ES * D < 128) {
+        if ((p.h_k & 1) == 0) {
+            const int l = id < (int)(gridDim.x & ~15u) ? ((id & ~15) | ((id & 7) << 1) | ((id >> 3) & 1)) : id;
+            int r = l >> 1;
+            split = r % p.n_split; r /= p.n_split;
+            tile = r % p.n_row_tiles;
+            bh = 2 * (r / p.n_row_tiles) + (l & 1);
+        }
+    }
     const int bidx = bh / p.h_k, kvh = bh - bidx * p.h_k;
     const int L = kvc_len(p, bidx);
     const int rows_tile = p.seqlen_q * p.h_ratio;
@@ -82,7 +131,14 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
     const int k_hi = LOCAL ? __builtin_amdgcn_readfirstlane(win_lim((min((tile + 1) * kKvcRows, rows_tile) - 1) / p.h_ratio)) : L;
     const int k_begin = (w0 & ~(kKvcStep - 1)) + split * p.split_keys;
     const int k_end = min(k_begin + p.split_keys, k_hi);
-    const float c = p.scale_log2e;
+    // 8-bit cache: S = (Q . K codes) x k_descale, so the descale rides on the softmax scale; O = (P . V codes) x v_descale / l
+    float kd = 1.f, vd = 1.f;
+    if constexpr (ES == 1) {
+        if (p.k_descale != nullptr) kd = p.k_descale[(int64_t)bidx * p.kds_batch + (int64_t)kvh * p.kds_head];
+        if (p.v_descale != nullptr) vd = p.v_descale[(int64_t)bidx * p.vds_batch + (int64_t)kvh * p.vds_head];
+    }
+    const float c = ES == 1 ? p.scale_log2e * kd : p.scale_log2e;
+    const float sc = ES == 1 ? p.scale * kd : p.scale;
 
     if (p.n_split > 1 && k_begin >= k_end) {        // nothing to read in this split: an empty partial (LSE = -inf), O is never looked at
         if (tid < kKvcRows) {
@@ -109,19 +165,23 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
         const char* qrow = (const char*)p.q_ptr + 2 * ((int64_t)bidx * p.q.batch + (int64_t)t * p.q.row + (int64_t)hq * p.q.head);
         static_for<0, NC>([&](auto cc) {
             constexpr int ci = decltype(cc)::value;
-            qf[ci] = row_ok ? *(const u32x4*)(qrow + 2 * (32 * ci + 8 * g)) : u32x4{0u, 0u, 0u, 0u};
+            // ES = 1: a 16-byte K load brings d-elements 64 li + 16 g .. + 15, which feed chunks 2 li and 2 li + 1 eight by eight; the dot
+            // product over d does not care which d-elements a k-slot carries as long as Q carries the same ones
+            constexpr int d0 = (ES == 2 || K8) ? 32 * ci : 64 * (ci / 2) + 8 * (ci & 1);
+            constexpr int dg = (ES == 2 || K8) ? 8 : 16;
+            qf[ci] = row_ok ? *(const u32x4*)(qrow + 2 * (d0 + dg * g)) : u32x4{0u, 0u, 0u, 0u};
         });
     }
 
     // ---- K / V of this (batch, KV head): descriptors end at row L ------------------------------------------------------------------
     // (contiguous LOCAL: they start at row w0 <= L, and a row is addressed as min((uint32_t)(key - w0), L - w0): rows below w0 and at or
     // past L both fall outside the range)
-    const uint32_t krow_b = (uint32_t)(p.kc.row * 2), vrow_b = (uint32_t)(p.vc.row * 2);
+    const uint32_t krow_b = (uint32_t)(p.kc.row * ES), vrow_b = (uint32_t)(p.vc.row * ES);
     const int wb = PAGED ? 0 : w0;
-    const char* kbase = uniform_ptr((const char*)p.k_cache + 2 * ((int64_t)(PAGED ? 0 : bidx) * p.kc.batch + (int64_t)kvh * p.kc.head + (int64_t)wb * p.kc.row));
-    const char* vbase = uniform_ptr((const char*)p.v_cache + 2 * ((int64_t)(PAGED ? 0 : bidx) * p.vc.batch + (int64_t)kvh * p.vc.head + (int64_t)wb * p.vc.row));
-    const rsrc_t krs = make_rsrc(kbase, L > wb ? (uint32_t)(L - wb - 1) * krow_b + 2 * D : 0u);
-    const rsrc_t vrs = make_rsrc(vbase, L > wb ? (uint32_t)(L - wb - 1) * vrow_b + 2 * D : 0u);
+    const char* kbase = uniform_ptr((const char*)p.k_cache + ES * ((int64_t)(PAGED ? 0 : bidx) * p.kc.batch + (int64_t)kvh * p.kc.head + (int64_t)wb * p.kc.row));
+    const char* vbase = uniform_ptr((const char*)p.v_cache + ES * ((int64_t)(PAGED ? 0 : bidx) * p.vc.batch + (int64_t)kvh * p.vc.head + (int64_t)wb * p.vc.row));
+    const rsrc_t krs = make_rsrc(kbase, L > wb ? (uint32_t)(L - wb - 1) * krow_b + ES * D : 0u);
+    const rsrc_t vrs = make_rsrc(vbase, L > wb ? (uint32_t)(L - wb - 1) * vrow_b + ES * D : 0u);
     // Paged cache: a step's two 16-key blocks each lie in one page (page_size is a multiple of 16).  Every block gets its own descriptors,
     // based at the block's first row in its page and ending at the sequence's last valid row in the block (rows at or past L read as
     // zeros, as above; a block wholly past L has an empty range, so whatever its table entry says is never read).  The table entries of
@@ -159,7 +219,12 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
     auto crow = [&](int key) __attribute__((always_inline)) {
         return LOCAL ? min((uint32_t)(key - w0), (uint32_t)(L - w0)) : (uint32_t)min(key, L);
     };
-    auto load_step = [&](int key0, u32x4 (&kf)[2][NC], u32x4 (&vf)[NV]) __attribute__((always_inline)) {
+    auto load_k = [&](rsrc_t r, uint32_t off, int ci) __attribute__((always_inline)) {
+        if constexpr (K8) return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, off + 32 * ci, 0, 0));
+        else return buf_load16(r, off + 64 * ci);
+    };
+    constexpr int kKG = K8 ? 8 : 16;    // bytes per lane group g within a K load
+    auto load_step = [&](int key0, kfrag_t (&kf)[2][NK], u32x4 (&vf)[NV]) __attribute__((always_inline)) {
         if constexpr (PAGED) {
             rsrc_t kr[2], vr[2];
             int skip[2], nrow[2];
@@ -171,8 +236,8 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
                 const int64_t page = min(pg[b], (uint32_t)(p.num_blocks - 1));
                 const int64_t pk = page * p.kc.batch + (int64_t)(rw[b] + skip[b]) * p.kc.row;
                 const int64_t pv = page * p.vc.batch + (int64_t)(rw[b] + skip[b]) * p.vc.row;
-                kr[b] = make_rsrc(uniform_ptr(kbase + 2 * pk), nrow[b] > 0 ? (uint32_t)(nrow[b] - 1) * krow_b + 2 * D : 0u);
-                vr[b] = make_rsrc(uniform_ptr(vbase + 2 * pv), nrow[b] > 0 ? (uint32_t)(nrow[b] - 1) * vrow_b + 2 * D : 0u);
+                kr[b] = make_rsrc(uniform_ptr(kbase + ES * pk), nrow[b] > 0 ? (uint32_t)(nrow[b] - 1) * krow_b + ES * D : 0u);
+                vr[b] = make_rsrc(uniform_ptr(vbase + ES * pv), nrow[b] > 0 ? (uint32_t)(nrow[b] - 1) * vrow_b + ES * D : 0u);
             });
             // row r of block b within its descriptor
             auto brow = [&](int b, int r) __attribute__((always_inline)) {
@@ -180,10 +245,10 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
             };
             static_for<0, 2>([&](auto kb) {
                 constexpr int b = decltype(kb)::value;
-                const uint32_t off = brow(b, n16) * krow_b + 2 * 8 * g;
-                static_for<0, NC>([&](auto cc) {
+                const uint32_t off = brow(b, n16) * krow_b + kKG * g;
+                static_for<0, NK>([&](auto cc) {
                     constexpr int ci = decltype(cc)::value;
-                    kf[b][ci] = buf_load16(kr[b], off + 2 * 32 * ci);
+                    kf[b][ci] = load_k(kr[b], off, ci);
                 });
             });
             static_for<0, NV>([&](auto iv) {
@@ -196,10 +261,10 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
         } else {
             static_for<0, 2>([&](auto kb) {
                 constexpr int b = decltype(kb)::value;
-                const uint32_t off = crow(key0 + 16 * b + n16) * krow_b + 2 * 8 * g;
-                static_for<0, NC>([&](auto cc) {
+                const uint32_t off = crow(key0 + 16 * b + n16) * krow_b + kKG * g;
+                static_for<0, NK>([&](auto cc) {
                     constexpr int ci = decltype(cc)::value;
-                    kf[b][ci] = buf_load16(krs, off + 2 * 32 * ci);
+                    kf[b][ci] = load_k(krs, off, ci);
                 });
             });
             static_for<0, NV>([&](auto iv) {
@@ -223,17 +288,32 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
     });
     float m_run = kNegBig, l_run = 0.f;
 
-    auto compute_step = [&](int key0, const u32x4 (&kf)[2][NC], const u32x4 (&vf)[NV]) __attribute__((always_inline)) {
+    auto compute_step = [&](int key0, const kfrag_t (&kf)[2][NK], const u32x4 (&vf)[NV]) __attribute__((always_inline)) {
         f32x4 s[2];
         static_for<0, 2>([&](auto kb) {
             constexpr int b = decltype(kb)::value;
             s[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-            static_for<0, NC>([&](auto cc) { s[b] = LP<T>::mfma16(kf[b][decltype(cc)::value], qf[decltype(cc)::value], s[b]); });
+            static_for<0, NC>([&](auto cc) {
+                constexpr int ci = decltype(cc)::value;
+                if constexpr (ES == 2) {
+                    s[b] = LP<T>::mfma16(kf[b][ci], qf[ci], s[b]);
+                } else if constexpr (K8) {
+                    s[b] = LP<T>::mfma16(widen8<T>(kf[b][ci].x, kf[b][ci].y), qf[ci], s[b]);
+                } else {
+                    const u32x4 k8 = kf[b][ci / 2];
+                    s[b] = LP<T>::mfma16((ci & 1) ? widen8<T>(k8.z, k8.w) : widen8<T>(k8.x, k8.y), qf[ci], s[b]);
+                }
+            });
         });
-        // V -> this wave's LDS image while the MFMAs run
+        // V -> this wave's LDS image while the MFMAs run (ES = 1: widened to T first, so the image and its transposed reads stay as they are)
         static_for<0, NV>([&](auto iv) {
             constexpr int i = decltype(iv)::value;
-            *(FA_LDS u32x4*)(vstage + lds_tile_off<D>(i * VRPL + lane / SLOTS, lane % SLOTS)) = vf[i];
+            if constexpr (ES == 2) {
+                *(FA_LDS u32x4*)(vstage + lds_tile_off<D>(i * VRPL + lane / SLOTS, lane % SLOTS)) = vf[i];
+            } else {
+                *(FA_LDS u32x4*)(vstage + lds_tile_off<D>(i * VRPL + lane / SLOTS, 2 * (lane % SLOTS))) = widen8<T>(vf[i].x, vf[i].y);
+                *(FA_LDS u32x4*)(vstage + lds_tile_off<D>(i * VRPL + lane / SLOTS, 2 * (lane % SLOTS) + 1)) = widen8<T>(vf[i].z, vf[i].w);
+            }
         });
         float mx = -INFINITY;
         static_for<0, 2>([&](auto kb) {
@@ -276,7 +356,8 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
 
     // ---- the split's 32-key steps, interleaved over the waves; two register sets in turn -----------------------------------------
     {
-        u32x4 ka[2][NC], kb2[2][NC], va[NV], vb[NV];
+        kfrag_t ka[2][NK], kb2[2][NK];
+        u32x4 va[NV], vb[NV];
         int key = k_begin + wave * kKvcStep;
         const int stride = kKvcWaves * kKvcStep;
         if (key < k_end) load_step(key, ka, va);
@@ -329,8 +410,8 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
     // dead = saw no key (lsum == 0); a NaN or +inf score leaves lsum = NaN, which is live: O and LSE come out NaN as in fp32 math, and a
     // split partial is written so that the combine propagates it
     const bool live = !(lsum == 0.f);
-    const float inv = live ? 1.0f / lsum : 0.f;
-    const float lse = live ? mrow * p.scale + logf(lsum) : (p.n_split > 1 ? -INFINITY : 0.f);
+    const float inv = live ? (ES == 1 ? vd / lsum : 1.0f / lsum) : 0.f;
+    const float lse = live ? mrow * sc + logf(lsum) : (p.n_split > 1 ? -INFINITY : 0.f);
     const int64_t R = ((int64_t)bidx * p.h + ohq) * p.seqlen_q + ot;
     if (p.n_split == 1) {
         char* orow = (char*)p.o_ptr + 2 * ((int64_t)bidx * p.o.batch + (int64_t)ot * p.o.row + (int64_t)ohq * p.o.head + col);
@@ -368,6 +449,22 @@ __global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_paged_kernel(co
 template <typename T, int D, bool PAGED>
 __global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_local_kernel(const KvcacheKernelParams p) {
     kvcache_attn<T, D, false, PAGED, true>(p);
+}
+
+// The same three over an 8-bit (e4m3) cache
+template <typename T, int D, bool CAUSAL>
+__global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_fp8_kernel(const KvcacheKernelParams p) {
+    kvcache_attn<T, D, CAUSAL, false, false, 1>(p);
+}
+
+template <typename T, int D, bool CAUSAL>
+__global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_fp8_paged_kernel(const KvcacheKernelParams p) {
+    kvcache_attn<T, D, CAUSAL, true, false, 1>(p);
+}
+
+template <typename T, int D, bool PAGED>
+__global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_fp8_local_kernel(const KvcacheKernelParams p) {
+    kvcache_attn<T, D, false, PAGED, true, 1>(p);
 }
 
 // One pass per output row over the splits, in split order (deterministic): O = sum_s exp(lse_s - M) O_s / sum_s exp(lse_s - M),
@@ -467,6 +564,106 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(const Kvca
     *(u32x4*)((char*)p.v_cache + 2 * (page * p.vc.batch + (int64_t)prow * p.vc.row + (int64_t)kvh * p.vc.head + 8 * slot)) = vx;
 }
 
+// One 16-bit element of k_new / v_new -> its e4m3 code under the (batch, KV head) descale: e4m3_rne(clamp(x / descale, -448, 448)).  The
+// quotient is the correctly rounded fp32 one (no fast-math), the clamp is explicit so that nothing depends on the conversion's saturation
+// mode, +-inf saturate with it; NaN keeps its sign and becomes 0x7f / 0xff.
+template <typename T>
+FA_DEV uint32_t quant_pair_e4m3(uint32_t w, float descale, uint32_t old, bool high) {
+    float x[2];
+    if constexpr (__is_same(T, _Float16)) {
+        x[0] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xffffu));
+        x[1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
+    } else {
+        x[0] = __builtin_bit_cast(float, w << 16);
+        x[1] = __builtin_bit_cast(float, w & 0xffff0000u);
+    }
+    float y[2];
+    static_for<0, 2>([&](auto ee) {
+        constexpr int e = decltype(ee)::value;
+        const float qv = x[e] / descale;
+        y[e] = __builtin_isnan(qv) ? qv : fminf(fmaxf(qv, -448.f), 448.f);
+    });
+    uint32_t r = high ? (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], (int)old, true)
+                      : (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], (int)old, false);
+    const int sh = high ? 16 : 0;
+    static_for<0, 2>([&](auto ee) {
+        constexpr int e = decltype(ee)::value;
+        if (__builtin_isnan(y[e])) {
+            const uint32_t code = 0x7fu | ((__builtin_bit_cast(uint32_t, x[e]) >> 24) & 0x80u);
+            r = (r & ~(0xffu << (sh + 8 * e))) | (code << (sh + 8 * e));
+        }
+    });
+    return r;
+}
+
+template <typename T>
+FA_DEV u32x2 quant8_e4m3(u32x4 x, float descale) {
+    u32x2 r;
+    r.x = quant_pair_e4m3<T>(x.x, descale, 0u, false);
+    r.x = quant_pair_e4m3<T>(x.y, descale, r.x, true);
+    r.y = quant_pair_e4m3<T>(x.z, descale, 0u, false);
+    r.y = quant_pair_e4m3<T>(x.w, descale, r.y, true);
+    return r;
+}
+
+// The append into an 8-bit cache, both layouts: 8 elements per thread, quantised as above (16 bytes read, 8 written).  Rows and pages are
+// found exactly as in the 16-bit kernels above.
+template <typename T, int D, bool PAGED>
+__global__ __launch_bounds__(256) void fa_kvcache_append_fp8_kernel(const KvcacheKernelParams p) {
+    constexpr int SLOTS = D / 8;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = (int64_t)p.b * p.seqlen_new * p.h_k * SLOTS;
+    if (i >= n) return;
+    const int slot = (int)(i % SLOTS);
+    int64_t r = i / SLOTS;
+    const int kvh = (int)(r % p.h_k);
+    r /= p.h_k;
+    const int t = (int)(r % p.seqlen_new);
+    const int bidx = (int)(r / p.seqlen_new);
+    const int cs = p.cache_seqlens[bidx];
+    const int row = (cs > 0 ? cs : 0) + t;
+    if (row >= p.seqlen_cache) return;
+    int64_t blk = bidx, prow = row;
+    if constexpr (PAGED) {
+        const int col = row / p.page_size;
+        prow = row - col * p.page_size;
+        blk = (int64_t)min((uint32_t)p.block_table[(int64_t)bidx * p.bt_stride + col], (uint32_t)(p.num_blocks - 1));
+    }
+    const float kd = p.k_descale != nullptr ? p.k_descale[(int64_t)bidx * p.kds_batch + (int64_t)kvh * p.kds_head] : 1.f;
+    const float vd = p.v_descale != nullptr ? p.v_descale[(int64_t)bidx * p.vds_batch + (int64_t)kvh * p.vds_head] : 1.f;
+    const u32x4 kx = *(const u32x4*)((const char*)p.k_new + 2 * ((int64_t)bidx * p.kn.batch + (int64_t)t * p.kn.row + (int64_t)kvh * p.kn.head + 8 * slot));
+    const u32x4 vx = *(const u32x4*)((const char*)p.v_new + 2 * ((int64_t)bidx * p.vn.batch + (int64_t)t * p.vn.row + (int64_t)kvh * p.vn.head + 8 * slot));
+    *(u32x2*)((char*)p.k_cache + (blk * p.kc.batch + prow * p.kc.row + (int64_t)kvh * p.kc.head + 8 * slot)) = quant8_e4m3<T>(kx, kd);
+    *(u32x2*)((char*)p.v_cache + (blk * p.vc.batch + prow * p.vc.row + (int64_t)kvh * p.vc.head + 8 * slot)) = quant8_e4m3<T>(vx, vd);
+}
+
+template <typename T, int D>
+hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s) {
+    const bool paged = kp.block_table != nullptr;
+    if (kp.k_new != nullptr && kp.seqlen_new > 0) {
+        const int64_t n = (int64_t)kp.b * kp.seqlen_new * kp.h_k * (D / 8);
+        if (paged) hipLaunchKernelGGL((fa_kvcache_append_fp8_kernel<T, D, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kp);
+        else hipLaunchKernelGGL((fa_kvcache_append_fp8_kernel<T, D, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kp);
+    }
+    const int64_t grid = (int64_t)kp.b * kp.h_k * kp.n_row_tiles * kp.n_split;
+    if (kp.is_local) {
+        if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_fp8_local_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+        else hipLaunchKernelGGL((fa_fwd_kvcache_fp8_local_kernel<T, D, false>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+    } else if (paged) {
+        if (kp.is_causal) hipLaunchKernelGGL((fa_fwd_kvcache_fp8_paged_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+        else hipLaunchKernelGGL((fa_fwd_kvcache_fp8_paged_kernel<T, D, false>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+    } else {
+        if (kp.is_causal) hipLaunchKernelGGL((fa_fwd_kvcache_fp8_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+        else hipLaunchKernelGGL((fa_fwd_kvcache_fp8_kernel<T, D, false>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
+    }
+    if (kp.n_split > 1) {
+        const int64_t rows_per_block = kKvcCombineThreads / (D / 8);
+        hipLaunchKernelGGL((fa_kvcache_combine_kernel<T, D>), dim3((unsigned)((kp.rows_total + rows_per_block - 1) / rows_per_block)),
+                           dim3(kKvcCombineThreads), 0, s, kp);
+    }
+    return hipGetLastError();
+}
+
 template <typename T, int D>
 hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s) {
     const bool paged = kp.block_table != nullptr;
@@ -551,6 +748,10 @@ hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s) 
     if (kp.split_keys <= 0) kp.split_keys = kKvcStep;
     if (kp.n_split > 1) {
         kp.ws_lse = kp.ws_o + (int64_t)kp.n_split * kp.rows_total * kp.d;
+    }
+    if (kp.cache_fp8) {
+        if (dtype == 0) return kp.d == 64 ? launch_kvcache_fp8_t<_Float16, 64>(kp, s) : launch_kvcache_fp8_t<_Float16, 128>(kp, s);
+        return kp.d == 64 ? launch_kvcache_fp8_t<__bf16, 64>(kp, s) : launch_kvcache_fp8_t<__bf16, 128>(kp, s);
     }
     if (dtype == 0) return kp.d == 64 ? launch_kvcache_t<_Float16, 64>(kp, s) : launch_kvcache_t<_Float16, 128>(kp, s);
     return kp.d == 64 ? launch_kvcache_t<__bf16, 64>(kp, s) : launch_kvcache_t<__bf16, 128>(kp, s);

@@ -149,6 +149,13 @@ struct KvcacheKernelParams {
     int32_t is_local;
     int32_t window_left;
     int32_t window_right;
+    // 8-bit cache (fa_kvcache_options.cache_dtype = FA_CACHE_FP8_E4M3; cache_fp8 = 0: the 16-bit kernels, the fields below are not read).
+    // k_cache / v_cache hold e4m3 codes and kc / vc are strides in those 1-byte elements; element (i, j, g, :) stands for
+    // code x k_descale[i * kds_batch + g * kds_head] (fp32 device arrays, NULL = 1.0), likewise V.
+    int32_t cache_fp8;
+    const float* k_descale;
+    const float* v_descale;
+    int64_t kds_batch, kds_head, vds_batch, vds_head;
 };
 constexpr int kKvcRows = 16;    // packed query rows of a workgroup (one 16x16x32 MFMA tile)
 constexpr int kKvcStep = 32;    // keys of one wave step (the split granularity)

@@ -265,13 +265,22 @@ std::vector<at::Tensor> mha_varlen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
 // used in place with their own strides (no copy: k_new / v_new are appended INTO them); cache_seqlens stays on the device (no host sync, the
 // call can be captured in a graph).  The split workspace comes from the caching allocator.  With block_table (int32, (b, max_blocks_per_seq))
 // k_cache / v_cache are page pools (num_blocks, page_block_size, h_k, d), addressed through the table in place as well.  window_size_left /
-// _right: a sliding window (fa_kvcache_options; (-1, -1) = none, the plain entry points).
+// _right: a sliding window (fa_kvcache_options; (-1, -1) = none, the plain entry points).  A torch.float8_e4m3fn cache is the 8-bit cache of
+// fa_kvcache_options_v2 with its optional fp32 (batch, h_k) descales (any strides, read on the device); a cache is never copied, so a view
+// that breaks the alignment rule of the 8-bit loads is an error.
 std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, c10::optional<at::Tensor> k_new_,
                                         c10::optional<at::Tensor> v_new_, c10::optional<at::Tensor> cache_seqlens_, bool is_causal,
                                         int64_t num_splits, c10::optional<at::Tensor> block_table_, int64_t window_size_left,
-                                        int64_t window_size_right) {
+                                        int64_t window_size_right, c10::optional<at::Tensor> k_descale_, c10::optional<at::Tensor> v_descale_) {
     TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4, "q, k_cache, v_cache must be rank-4 tensors");
-    check_qkv_common(q, k_cache, v_cache);
+    TORCH_CHECK(q.is_cuda() && k_cache.is_cuda() && v_cache.is_cuda(), "q, k, v must be GPU (HIP) tensors");
+    TORCH_CHECK(k_cache.device() == q.device() && v_cache.device() == q.device(), "q, k, v must be on the same device");
+    TORCH_CHECK(k_cache.scalar_type() == v_cache.scalar_type(), "k_cache and v_cache must have the same dtype");
+    const bool fp8 = k_cache.scalar_type() == at::kFloat8_e4m3fn;
+    TORCH_CHECK(fp8 || k_cache.scalar_type() == q.scalar_type(),
+                "k_cache / v_cache must have the dtype of q or be torch.float8_e4m3fn (OCP e4m3; float8_e4m3fnuz, float8_e5m2 and other dtypes are not supported), got ",
+                k_cache.scalar_type());
+    TORCH_CHECK(fp8 || (!k_descale_.has_value() && !v_descale_.has_value()), "k_descale / v_descale need a torch.float8_e4m3fn cache");
     const int64_t batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), head_size = q.size(3);
     const int64_t num_heads_k = k_cache.size(2);
     int64_t seqlen_cache = k_cache.size(1);
@@ -338,11 +347,25 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
         p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr(); p.seqlen_new = (int32_t)k_new.size(1);
         p.k_new_stride = strides4(k_new); p.v_new_stride = strides4(v_new);
     }
-    fa_kvcache_options opt;
+    fa_kvcache_options_v2 opt;
     FA_PARAMS_INIT(opt);
     opt.is_local = window_size_left != -1 || window_size_right != -1;
     opt.window_size_left = (int32_t)window_size_left; opt.window_size_right = (int32_t)window_size_right;
-    const fa_kvcache_options* opts = opt.is_local ? &opt : nullptr;
+    at::Tensor k_descale, v_descale;
+    if (fp8) {
+        opt.cache_dtype = FA_CACHE_FP8_E4M3;
+        auto descale = [&](const c10::optional<at::Tensor>& t_, const char* name, at::Tensor& keep, const float*& ptr, int64_t& sb, int64_t& sh) {
+            if (!t_.has_value()) return;
+            keep = *t_;
+            check_same_device(q, keep, name);
+            TORCH_CHECK(keep.scalar_type() == torch::kFloat32, name, " must be a float32 tensor");
+            TORCH_CHECK(keep.dim() == 2 && keep.size(0) == batch_size && keep.size(1) == num_heads_k, name, " must have shape [batch_size, num_heads_k]");
+            ptr = keep.data_ptr<float>(); sb = keep.stride(0); sh = keep.stride(1);
+        };
+        descale(k_descale_, "k_descale", k_descale, opt.k_descale, opt.k_descale_batch_stride, opt.k_descale_head_stride);
+        descale(v_descale_, "v_descale", v_descale, opt.v_descale, opt.v_descale_batch_stride, opt.v_descale_head_stride);
+    }
+    const fa_kvcache_options* opts = (opt.is_local || fp8) ? (const fa_kvcache_options*)&opt : nullptr;
     at::Tensor workspace;
     const int64_t ws_bytes = fa_kvcache_workspace_bytes_ex(&p, opts);
     if (ws_bytes < 0) check_status((int)ws_bytes);
@@ -407,7 +430,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fwd_kvcache", &mha_fwd_kvcache, "Decode forward over a KV cache (in-place append of k / v, split-KV attention)", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
           py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("block_table") = py::none(), py::arg("window_size_left") = -1,
-          py::arg("window_size_right") = -1);
+          py::arg("window_size_right") = -1, py::kw_only(), py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none());
     m.def("attn_autograd", &attn_autograd, "differentiable forward (C++ autograd node over fwd / bwd)");
     m.def("attn_varlen_autograd", &attn_varlen_autograd, "differentiable packed forward (C++ autograd node over varlen_fwd / varlen_bwd)");
     m.def("abi_version", []() { return fa_abi_version(); });

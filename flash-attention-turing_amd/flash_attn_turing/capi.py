@@ -83,6 +83,16 @@ class KvcacheOptions(_Params):
                 ("window_size_right", _i32)]
 
 
+class KvcacheOptionsV2(_Params):
+    """fa_kvcache_options_v2: fa_kvcache_options plus the 8-bit cache fields (passed to the _ex entry points through the same pointer)"""
+    _fields_ = KvcacheOptions._fields_ + [("cache_dtype", _i32), ("k_descale", _vp), ("v_descale", _vp),
+                                          ("k_descale_batch_stride", ctypes.c_int64), ("k_descale_head_stride", ctypes.c_int64),
+                                          ("v_descale_batch_stride", ctypes.c_int64), ("v_descale_head_stride", ctypes.c_int64)]
+
+
+FA_CACHE_FP8_E4M3 = 1
+
+
 _lib = None
 
 
@@ -119,7 +129,7 @@ def lib():
         L.fa_kvcache_workspace_bytes.restype = ctypes.c_int64
         L.fa_kvcache_num_splits.argtypes = [ctypes.POINTER(KvcacheParams)]
         L.fa_kvcache_num_splits.restype = ctypes.c_int32
-        _op = ctypes.POINTER(KvcacheOptions)
+        _op = ctypes.c_void_p                       # fa_kvcache_options or fa_kvcache_options_v2 (told apart by struct_size)
         L.fa_run_mha_fwd_kvcache_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op, _vp]
         L.fa_run_mha_fwd_kvcache_ex.restype = ctypes.c_int
         L.fa_kvcache_workspace_bytes_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op]
@@ -323,12 +333,20 @@ def kvcache_params(q, k_cache, v_cache, o, lse, cache_seqlens=None, k_new=None, 
     return p
 
 
-def kvcache_options(window_size=(-1, -1)):
-    """fa_kvcache_options with a sliding window (left, right); (-1, -1) gives a zeroed struct (no window)"""
-    o = KvcacheOptions()
+def kvcache_options(window_size=(-1, -1), cache_dtype=0, k_descale=None, v_descale=None):
+    """fa_kvcache_options with a sliding window (left, right); (-1, -1) gives a zeroed struct (no window).  With cache_dtype
+    (FA_CACHE_FP8_E4M3) or a descale (float32 (b, h_k) torch tensors, any strides) the struct is fa_kvcache_options_v2."""
+    v2 = cache_dtype != 0 or k_descale is not None or v_descale is not None
+    o = KvcacheOptionsV2() if v2 else KvcacheOptions()
     left, right = window_size
     if (left, right) != (-1, -1):
         o.is_local, o.window_size_left, o.window_size_right = 1, int(left), int(right)
+    if v2:
+        o.cache_dtype = int(cache_dtype)
+        if k_descale is not None:
+            o.k_descale, o.k_descale_batch_stride, o.k_descale_head_stride = k_descale.data_ptr(), k_descale.stride(0), k_descale.stride(1)
+        if v_descale is not None:
+            o.v_descale, o.v_descale_batch_stride, o.v_descale_head_stride = v_descale.data_ptr(), v_descale.stride(0), v_descale.stride(1)
     return o
 
 

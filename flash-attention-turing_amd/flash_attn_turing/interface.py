@@ -90,8 +90,28 @@ def _window_pair(window_size):
     return left, right
 
 
+def _check_cache_dtype(q, k_cache, v_cache, k_descale, v_descale):
+    """the cache has q's dtype, or is an FP8 e4m3fn cache with optional float32 (batch, nheads_k) descales on q's device"""
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError(f"k_cache and v_cache must have the same dtype, got {k_cache.dtype} and {v_cache.dtype}")
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if not fp8 and k_cache.dtype != q.dtype:
+        raise ValueError(f"k_cache / v_cache must have the dtype of q ({q.dtype}) or be torch.float8_e4m3fn, got {k_cache.dtype}")
+    for name, t in (("k_descale", k_descale), ("v_descale", v_descale)):
+        if t is None:
+            continue
+        if not fp8:
+            raise ValueError(f"{name} needs a torch.float8_e4m3fn cache (the cache is {k_cache.dtype})")
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be a float32 tensor")
+        if k_cache.dim() != 4 or tuple(t.shape) != (q.shape[0], k_cache.shape[2]):
+            raise ValueError(f"{name} must have shape (batch, nheads_k) = ({q.shape[0]}, {k_cache.shape[2] if k_cache.dim() == 4 else '?'}), got {tuple(t.shape)}")
+        if t.device != q.device:
+            raise ValueError(f"{name} must be on q's device ({q.device}), got {t.device}")
+
+
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, causal=False, num_splits=0, return_softmax_lse=False, *,
-                            block_table=None, window_size=(-1, -1)):
+                            block_table=None, window_size=(-1, -1), k_descale=None, v_descale=None):
     """Decode attention over a KV cache (upstream flash-attn's ``flash_attn_with_kvcache`` conventions; forward only).
 
     q: (batch, seqlen_q, nheads, d); k_cache, v_cache: (batch, seqlen_cache, nheads_k, d), any batch / row / head strides (used in place).
@@ -123,13 +143,33 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     causal with seqlen_q > 1, the query rows of a call share K / V reads: the seqlen_q x (nheads / nheads_k) rows of a KV head go through the
     kernels in tiles of 16, and a non-finite V element in a row that another query row of the same tile sees, but this row does not, can make
     this row's O NaN (its weight for that row is 0, and 0 x NaN is NaN).
+
+    8-bit cache: k_cache, v_cache of dtype ``torch.float8_e4m3fn`` (OCP e4m3; both the same), contiguous or a page pool as above, with
+    k_descale, v_descale (keyword, optional): float32 tensors (batch, nheads_k) on q's device, any strides (an ``expand()``-ed scalar is
+    fine), None = 1.0.  q, k, v, out stay fp16 / bf16 and lse fp32.  The call equals the 16-bit call on the dequantised cache
+    ``K[i, j, g, :] = float(k_cache[i, j, g, :]) * k_descale[i, g]`` (V likewise) in exact arithmetic: the codes are widened to q's dtype
+    without rounding in front of the same matrix instructions, k_descale folds into the softmax scale and v_descale into the final
+    normalisation, in fp32; Q and P are never quantised.  Descales are read on the device: no synchronisation, and a captured call
+    replays with the descale values (and lengths) then in memory.  Precondition, not checked: descales are finite and positive.  k / v
+    rows are quantised into the cache in place, ``code = e4m3_rne(clamp(float(x) / descale, -448, 448))`` (correctly rounded fp32
+    quotient, round to nearest even into the subnormals too, NaN stays NaN (0x7f / 0xff), +-inf saturate to +-448), and attention runs
+    over the quantised rows - what the next call will see.  Everything above carries over: block_table (same page size rule, same
+    clamping of bad entries), window_size, causal, GQA / MQA, num_splits (the split count and workspace are those of a 16-bit cache of
+    the same shape), dead rows O = 0, LSE = 0, determinism per split count, and the rows, pages and heads that are never read; a NaN code
+    in a visible K row makes that row's O and LSE NaN (e4m3fn has no inf); paged and contiguous calls over the same logical cache give
+    the same bits.  Alignment (the kernels keep 16-byte loads): the row, head and batch / page strides of an 8-bit cache are multiples of
+    16 elements and its storage offset a multiple of 16 bytes; a view that breaks this is rejected (RuntimeError), never copied.
+    ``float8_e4m3fnuz``, ``float8_e5m2`` and any other cache dtype that is not q's are a ValueError, as is a descale with a 16-bit cache
+    or one of the wrong dtype, shape or device.
     """
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v)):
         raise RuntimeError("flash_attn_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
     if (k is None) != (v is None):
         raise ValueError("k and v must both be given or both be None")
+    _check_cache_dtype(q, k_cache, v_cache, k_descale, v_descale)
     left, right = _window_pair(window_size)
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=q.device)
-    out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right)
+    out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right,
+                              k_descale=k_descale, v_descale=v_descale)
     return (out, lse) if return_softmax_lse else out

@@ -225,7 +225,31 @@ typedef struct fa_kvcache_params {
  * lie wholly outside [that row, L_i), are never read into a result.  A window with a left edge sizes the split from its span instead of the
  * capacity: the split and the workspace are never larger than without the window.  A row that sees no key gives o = 0, lse = 0.  A
  * non-finite V element in a row that another query row of the same KV head and row tile sees (the seqlen_q x h / h_k rows of a KV head go
- * through the kernels in tiles of 16) but this row does not can make this row's o NaN, as under causal with seqlen_q > 1. */
+ * through the kernels in tiles of 16) but this row does not can make this row's o NaN, as under causal with seqlen_q > 1.
+ *
+ * 8-bit cache: fa_kvcache_options_v2 below is fa_kvcache_options with optional fields appended after window_size_right; the _ex entry points
+ * take either through the same pointer and tell them apart by struct_size (sizeof(fa_kvcache_options): the window alone, as before;
+ * sizeof(fa_kvcache_options_v2): all fields; anything else is FA_ERR_BAD_ABI).  fa_kvcache_options itself keeps its layout, so a caller
+ * built against it keeps working, and it and a v2 struct with a zeroed tail get the 16-bit cache.  FA_ABI_VERSION is unchanged.  cache_dtype =
+ * FA_CACHE_FP8_E4M3: k_cache / v_cache hold OCP e4m3fn codes (one byte per element; torch.float8_e4m3fn - not the fnuz format, not e5m2)
+ * and the k_cache_stride / v_cache_stride of fa_kvcache_params count those 1-byte elements.  q, k_new, v_new, o keep `dtype` (fp16 / bf16),
+ * lse stays fp32.  k_descale / v_descale: fp32 DEVICE arrays, element (i, g) at [i * batch_stride + g * head_stride] (strides in
+ * elements, 0 allowed: one value for all), NULL = 1.0.  The call equals the 16-bit call over the dequantised cache
+ *     K[i, j, g, :] = float(k_cache[i, j, g, :]) * k_descale[i, g],   V likewise,
+ * in exact arithmetic: the codes are widened to `dtype` without rounding (every finite e4m3 value is an fp16 and a bf16 value) in front of
+ * the same matrix instructions, k_descale folds into the softmax scale of its (batch, KV head) and v_descale into the final 1 / l
+ * normalisation, both in fp32; Q and P are never quantised.  Descales are read on the device (no host synchronisation; a captured call
+ * replays with the values then in memory).  Precondition (not checked, it would need a synchronisation): descales are finite and > 0.
+ * Append: k_new / v_new rows are quantised into the cache, code = e4m3_rne(clamp(float(x) / descale, -448, 448)) with a correctly rounded
+ * fp32 quotient, round to nearest even (into the e4m3 subnormals too), NaN -> 0x7f / 0xff, +-inf saturate to +-448; attention then runs
+ * over the quantised rows.  Everything stated above for the 16-bit cache holds unchanged: contiguous and paged layout (same page size
+ * rule, same clamping of table entries), the window, causal, GQA / MQA, num_splits and the workspace (split count and workspace bytes are
+ * those of a 16-bit cache of the same shape: they follow the capacity, not the element size), rows without a visible key o = 0, lse = 0,
+ * determinism per split count, rows / pages / heads that are never read.  NaN: a NaN code (0x7f / 0xff) in a visible K row makes that row's
+ * o and lse NaN (e4m3fn has no inf).  Paged and contiguous calls over the same logical cache give the same bits.
+ * Alignment of an 8-bit cache (the kernels keep 16-byte loads): base pointers 16-byte aligned; row, head and batch / page strides multiples
+ * of 16 elements, row stride >= d; one sequence (one page) spans less than 2^31 bytes.  Anything else is FA_ERR_BAD_STRIDE - a cache is
+ * never copied.  An unknown cache_dtype, or a descale pointer without FA_CACHE_FP8_E4M3, is FA_ERR_BAD_DTYPE. */
 typedef struct fa_kvcache_options {
     uint32_t struct_size;       /* sizeof(fa_kvcache_options) in the caller's translation unit */
     uint32_t magic;             /* FA_PARAMS_MAGIC */
@@ -233,6 +257,19 @@ typedef struct fa_kvcache_options {
     int32_t window_size_left;   /* >= -1 */
     int32_t window_size_right;  /* >= -1; ignored under is_causal */
 } fa_kvcache_options;
+#define FA_CACHE_FP8_E4M3 1
+typedef struct fa_kvcache_options_v2 {      /* FA_PARAMS_INIT(o); then fa_..._ex(&p, (const fa_kvcache_options*)&o, ...) */
+    uint32_t struct_size;       /* sizeof(fa_kvcache_options_v2) */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    int32_t is_local;           /* the five fields of fa_kvcache_options, same offsets */
+    int32_t window_size_left;
+    int32_t window_size_right;
+    int32_t cache_dtype;        /* optional: 0 = the dtype of q, FA_CACHE_FP8_E4M3 = 8-bit codes (see above) */
+    const float* k_descale;     /* optional: fp32 device array, NULL = 1.0; FA_CACHE_FP8_E4M3 only */
+    const float* v_descale;
+    int64_t k_descale_batch_stride, k_descale_head_stride;   /* in elements */
+    int64_t v_descale_batch_stride, v_descale_head_stride;
+} fa_kvcache_options_v2;
 
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
@@ -293,7 +330,8 @@ int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* params);
 /* Key splits the launch of these params would use, workspace fields included (NULL / 0 -> 1).  Host-only.  Negative = error code. */
 int32_t fa_kvcache_num_splits(const fa_kvcache_params* params);
 /* The same three with options (fa_kvcache_options above; NULL = the plain calls).  Their presence is how a caller detects the window.
- * Options are validated before anything is launched: a bad header is FA_ERR_BAD_ABI, a window size below -1 FA_ERR_BAD_SHAPE. */
+ * Options are validated before anything is launched: a bad header is FA_ERR_BAD_ABI, a window size below -1 FA_ERR_BAD_SHAPE, an unknown
+ * cache_dtype or a descale without FA_CACHE_FP8_E4M3 FA_ERR_BAD_DTYPE, an 8-bit cache view that breaks the alignment rule FA_ERR_BAD_STRIDE. */
 int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* params, const fa_kvcache_options* options, void* stream);
 int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);
 int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);

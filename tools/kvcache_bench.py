@@ -15,6 +15,10 @@ medians; ms and TB/s of both and paged / contiguous.
 unwindowed causal call on the same caches and against the unwindowed causal call on caches of the window's length (LEFT + 1 rows),
 interleaved, medians.  TB/s counts the bytes the window actually reads.  Caches rotate until the windows alone exceed 256 MiB.
 
+--kv-dtype fp8 measures the 8-bit (torch.float8_e4m3fn) cache instead: per grid point, the 8-bit call with per-(batch, head) descales against
+the 16-bit call on the same logical cache (the 8-bit codes widened, which is exact), interleaved, medians; ms of both, TB/s of each over the
+bytes it really reads, the fraction of 6.3 TB/s, and the ratio.  Caches rotate until the 8-bit K/V alone exceed 256 MiB.
+
 --baseline-library PATH records an interleaved A/B of the plain (no window) call through the C ABI of this build and of the library at
 PATH (e.g. a build of the parent commit), on the same data; the outputs must agree bit for bit.  --length L (repeatable) replaces the
 grid's cache lengths."""
@@ -185,6 +189,48 @@ def run_window_point(pt, left, rounds):
                 unwindowed_over_window=round(ms_f / ms_w, 2), window_over_short=round(ms_w / ms_s, 3))
 
 
+def run_fp8_point(pt, rounds):
+    """the 8-bit call (A) and the 16-bit call on the same logical cache (B), interleaved"""
+    dev = torch.device("cuda:0")
+    b, h, hk, d, L, sq, dt = pt["b"], pt["h"], pt["h_k"], pt["d"], pt["L"], pt["seqlen_q"], pt["dtype"]
+    kv16, kv8 = 2 * b * L * hk * d * 2, 2 * b * L * hk * d
+    n = _rotation(kv16 + kv8, kv8)                            # the smaller working set (the 8-bit one) must exceed the cache too
+    f8 = torch.float8_e4m3fn
+
+    def mk():
+        c8, c16 = torch.empty(b, L, hk, d, device=dev, dtype=f8), torch.empty(b, L, hk, d, device=dev, dtype=dt)
+        for i in range(b):                                    # (per batch entry: bounds the fp32 temporaries of the conversion)
+            c8[i] = torch.empty(L, hk, d, device=dev, dtype=dt).uniform_(-2, 2).to(f8)
+            c16[i] = c8[i].to(dt)
+        return c8, c16
+
+    sets = [mk() + mk() for _ in range(n)]                    # (k8, k16, v8, v16)
+    q = torch.randn(b, sq, h, d, device=dev, dtype=dt)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    kds, vds = torch.empty(b, hk, device=dev).uniform_(0.5, 2.0), torch.empty(b, hk, device=dev).uniform_(0.5, 2.0)
+    f_8 = lambda i: F.flash_attn_with_kvcache(q, sets[i][0], sets[i][2], cache_seqlens=cs, k_descale=kds, v_descale=vds)
+    f_16 = lambda i: F.flash_attn_with_kvcache(q, sets[i][1], sets[i][3], cache_seqlens=cs)
+    f_8(0), f_16(0)
+    torch.cuda.synchronize()
+    t_8, t_16 = [], []
+    for _ in range(rounds):
+        t_8.append(time_rotation(f_8, n, 20))
+        t_16.append(time_rotation(f_16, n, 20))
+    ms_8, ms_16 = statistics.median(t_8), statistics.median(t_16)
+    p = capi.kvcache_params(q, sets[0][1], sets[0][3], torch.empty_like(q), torch.empty(b, h, sq, device=dev), cache_seqlens=cs)
+    ws = capi.kvcache_workspace_bytes(p)
+    n_split = max(1, ws and capi.kvcache_num_splits(_with_ws(p, ws)))
+    rows = b * h * sq
+    other = 2 * rows * d * 2 + rows * 4 + (2 * n_split * rows * (d + 1) * 4 if n_split > 1 else 0)
+    tb8, tb16 = (kv8 + other + 2 * b * hk * 4) / (ms_8 * 1e-3) / 1e12, (kv16 + other) / (ms_16 * 1e-3) / 1e12
+    del sets
+    torch.cuda.empty_cache()
+    return dict(b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=sq, dtype=str(dt).replace("torch.", ""), kv_gb_16bit=round(kv16 / 1e9, 3), caches_rotated=n,
+                ms_fp8=round(ms_8, 5), ms_16bit=round(ms_16, 5), bytes_fp8=kv8 + other + 2 * b * hk * 4, bytes_16bit=kv16 + other,
+                tbps_fp8=round(tb8, 3), tbps_16bit=round(tb16, 3), frac_of_6p3_fp8=round(tb8 * 1e12 / HBM_ACHIEVABLE, 3),
+                frac_of_6p3_16bit=round(tb16 * 1e12 / HBM_ACHIEVABLE, 3), n_split=n_split, fp8_over_16bit=round(ms_8 / ms_16, 3))
+
+
 def _baseline_lib(path):
     L = ctypes.CDLL(os.path.abspath(path))
     L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
@@ -251,6 +297,7 @@ def main():
     ap.add_argument("--paged", type=int, action="append", metavar="P", help="page size (a multiple of 16); repeat for several")
     ap.add_argument("--window", type=int, action="append", metavar="LEFT", help="sliding window (LEFT, 0), causal; repeat for several")
     ap.add_argument("--baseline-library", metavar="PATH", help="A/B of the plain call against this libflash_attn_gfx950.so")
+    ap.add_argument("--kv-dtype", choices=("fp16", "fp8"), default="fp16", help="fp8: the 8-bit cache against the 16-bit call on the same logical cache")
     ap.add_argument("--length", type=int, action="append", metavar="L", help="cache length(s) instead of the grid's")
     a = ap.parse_args()
     base = _baseline_lib(a.baseline_library) if a.baseline_library else None
@@ -262,6 +309,8 @@ def main():
         for pt in grid(a.quick, a.length):
             if base is not None:
                 print(json.dumps(run_ab_point(pt, base, a.rounds)), flush=True)
+            elif a.kv_dtype == "fp8":
+                print(json.dumps(run_fp8_point(pt, a.rounds)), flush=True)
             elif a.window:
                 for left in a.window:
                     print(json.dumps(run_window_point(pt, left, a.rounds)), flush=True)
