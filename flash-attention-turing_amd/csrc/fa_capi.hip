@@ -343,16 +343,17 @@ int fa_mha_varlen_bwd(const void* q, const void* k, const void* v, const void* o
     return fa_run_mha_bwd(&p, stream);
 }
 
-// The options pointer of the _ex entry points -> a zeroed fa_kvcache_options_v2 filled with what the caller's struct carries: struct_size says
-// which of the two layouts it is (fa_kvcache_options: the window alone; fa_kvcache_options_v2: plus the 8-bit cache fields).  NULL = all zero.
-static int import_kvcache_options(const fa_kvcache_options* user, fa_kvcache_options_v2& o) {
+// The options pointer of the _ex entry points -> a zeroed fa_kvcache_options_v3 filled with what the caller's struct carries: struct_size says
+// which of the three layouts it is (fa_kvcache_options: the window alone; fa_kvcache_options_v2: plus the 8-bit cache fields;
+// fa_kvcache_options_v3: plus the rotary fields).  NULL = all zero.
+static int import_kvcache_options(const fa_kvcache_options* user, fa_kvcache_options_v3& o) {
     memset(&o, 0, sizeof(o));
     if (user == nullptr) return FA_OK;
     if (user->magic != FA_PARAMS_MAGIC)
         return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: no {struct_size, magic} header (FA_PARAMS_INIT); recompile against include/flash_attn_gfx950.h (ABI %d)", FA_ABI_VERSION);
-    if (user->struct_size != sizeof(fa_kvcache_options) && user->struct_size != sizeof(fa_kvcache_options_v2))
-        return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: struct_size %u is neither sizeof(fa_kvcache_options) = %zu nor sizeof(fa_kvcache_options_v2) = %zu - header / library mismatch",
-                    user->struct_size, sizeof(fa_kvcache_options), sizeof(fa_kvcache_options_v2));
+    if (user->struct_size != sizeof(fa_kvcache_options) && user->struct_size != sizeof(fa_kvcache_options_v2) && user->struct_size != sizeof(fa_kvcache_options_v3))
+        return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: struct_size %u is none of sizeof(fa_kvcache_options) = %zu, sizeof(fa_kvcache_options_v2) = %zu, sizeof(fa_kvcache_options_v3) = %zu - header / library mismatch",
+                    user->struct_size, sizeof(fa_kvcache_options), sizeof(fa_kvcache_options_v2), sizeof(fa_kvcache_options_v3));
     memcpy(&o, user, user->struct_size);
     if (o.cache_dtype != 0 && o.cache_dtype != FA_CACHE_FP8_E4M3)
         return fail(FA_ERR_BAD_DTYPE, "cache_dtype %d unsupported (0 = the dtype of q, %d = FA_CACHE_FP8_E4M3; e4m3fnuz and e5m2 caches are not supported)", o.cache_dtype,
@@ -364,7 +365,7 @@ static int import_kvcache_options(const fa_kvcache_options* user, fa_kvcache_opt
 
 // with_workspace = false: the `workspace` fields are not looked at (fa_kvcache_workspace_bytes)
 static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& kp, fa_kvcache_params& local, bool with_workspace,
-                        const fa_kvcache_options_v2& o) {
+                        const fa_kvcache_options_v3& o) {
     // the paged-cache fields are optional: a caller built before them passes struct_size = offsetof(block_table) and gets NULL / 0
     int rc = import_params(user, local, "fa_kvcache_params", offsetof(fa_kvcache_params, block_table));
     if (rc) return rc;
@@ -442,7 +443,7 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
 // fa_kvcache_options (NULL = none) -> the window fields of kp, normalised: right = 0 under causal, and a side that cannot bind is -1 (left >=
 // seqlen_cache - 1: lo_t <= L - 1 - left <= 0 for every row; right >= seqlen_q - 1: lim_t >= L for every row).  A window whose left side is
 // unbounded and whose right side is unbounded or the causal limit is exactly the plain call: is_local stays 0 (the plain kernels, split and bits).
-static int fill_kvcache_window(const fa_kvcache_options_v2& o, fa::KvcacheKernelParams& kp) {
+static int fill_kvcache_window(const fa_kvcache_options_v3& o, fa::KvcacheKernelParams& kp) {
     if (!o.is_local) return FA_OK;
     if (o.window_size_left < -1 || o.window_size_right < -1)
         return fail(FA_ERR_BAD_SHAPE, "window_size (%d, %d): each side must be >= -1 (-1 = unbounded)", o.window_size_left, o.window_size_right);
@@ -455,11 +456,34 @@ static int fill_kvcache_window(const fa_kvcache_options_v2& o, fa::KvcacheKernel
     return FA_OK;
 }
 
+// The rotary fields of the options (rotary_cos = rotary_sin = NULL: off, rp.cos stays NULL and nothing else is looked at) -> rp, validated.
+// The query-position rule is decided from what the caller stated (is_causal, a window other than (-1, -1)), not from the normalised window.
+static int fill_kvcache_rotary(const fa_kvcache_options_v3& o, const fa::KvcacheKernelParams& kp, fa::KvcacheRotaryParams& rp) {
+    memset(&rp, 0, sizeof(rp));
+    if (o.rotary_cos == nullptr && o.rotary_sin == nullptr) return FA_OK;
+    if (o.rotary_cos == nullptr || o.rotary_sin == nullptr) return fail(FA_ERR_BAD_SHAPE, "rotary_cos and rotary_sin must both be given or both be NULL");
+    if (o.rotary_dim < 16 || o.rotary_dim > kp.d || o.rotary_dim % 16 != 0)
+        return fail(FA_ERR_BAD_SHAPE, "rotary_dim %d must be a multiple of 16 with 16 <= rotary_dim <= head_dim (%d)", o.rotary_dim, kp.d);
+    if (o.seqlen_ro < 1 || o.seqlen_ro < kp.seqlen_cache)
+        return fail(FA_ERR_BAD_SHAPE, "seqlen_ro (%d rows of rotary_cos / rotary_sin) must be >= 1 and cover the cache capacity seqlen_cache (%d)", o.seqlen_ro, kp.seqlen_cache);
+    if (kp.k_new == nullptr)
+        return fail(FA_ERR_BAD_SHAPE, "rotary_cos / rotary_sin need k_new / v_new (the rotation is applied to q and to the appended rows)");
+    if (((uintptr_t)o.rotary_cos & 15) != 0 || ((uintptr_t)o.rotary_sin & 15) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "rotary_cos / rotary_sin base pointers must be 16-byte aligned");
+    if (o.rotary_row_stride % 8 != 0 || (o.seqlen_ro > 1 && o.rotary_row_stride < o.rotary_dim / 2))
+        return fail(FA_ERR_BAD_STRIDE, "rotary_row_stride %lld must be a multiple of 8 elements (16-byte loads) and at least rotary_dim / 2 = %d", (long long)o.rotary_row_stride,
+                    o.rotary_dim / 2);
+    rp.cos = o.rotary_cos; rp.sin = o.rotary_sin; rp.row_stride = o.rotary_row_stride;
+    rp.seqlen_ro = o.seqlen_ro; rp.rotary_dim = o.rotary_dim; rp.interleaved = o.rotary_interleaved ? 1 : 0;
+    rp.q_pos_per_row = (kp.is_causal || (o.is_local && (o.window_size_left != -1 || o.window_size_right != -1))) ? 1 : 0;
+    return FA_OK;
+}
+
 // Params first, as before the options existed (their errors win), except that the cache tensors are checked under the cache dtype the
 // options state; then the options' own values.
 static int fill_kvcache_all(const fa_kvcache_params* user, const fa_kvcache_options* options, fa::KvcacheKernelParams& kp, fa_kvcache_params& local,
-                            fa_kvcache_options_v2& o, bool with_workspace) {
-    fa_kvcache_options_v2 none;
+                            fa_kvcache_options_v3& o, fa::KvcacheRotaryParams& rp, bool with_workspace) {
+    fa_kvcache_options_v3 none;
     memset(&none, 0, sizeof(none));
     const int orc = import_kvcache_options(options, o);
     char oerr[sizeof(g_err)];
@@ -470,38 +494,69 @@ static int fill_kvcache_all(const fa_kvcache_params* user, const fa_kvcache_opti
         memcpy(g_err, oerr, sizeof(g_err));
         return orc;
     }
-    return fill_kvcache_window(o, kp);
+    if ((rc = fill_kvcache_window(o, kp))) return rc;
+    return fill_kvcache_rotary(o, kp, rp);
+}
+
+// Workspace left for the split partials of a rotary call once the image of the rotated q has taken its part; a workspace that cannot hold
+// the image is an error (the attention kernels read q from it: there is no path without it)
+static int64_t rotary_split_bytes(const fa::KvcacheKernelParams& kp, const fa_kvcache_params& local) {
+    const int64_t need = fa::kvcache_rotary_image_bytes(kp);
+    const int64_t have = local.workspace != nullptr ? local.workspace_bytes : 0;
+    if (have < need)
+        return fail(FA_ERR_BAD_SHAPE, "rotary: the workspace (%lld bytes) cannot hold the image of the rotated q: %lld bytes needed (fa_kvcache_workspace_bytes_ex)", (long long)have,
+                    (long long)need);
+    return have - need;
 }
 
 int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    fa_kvcache_options_v2 o;
-    int rc = fill_kvcache_all(user, options, kp, local, o, false);
+    fa_kvcache_options_v3 o;
+    fa::KvcacheRotaryParams rp;
+    int rc = fill_kvcache_all(user, options, kp, local, o, rp, false);
     if (rc) return rc;
     if (kp.b == 0) return 0;
-    return fa::kvcache_workspace_bytes(kp, fa::kvcache_split(kp, -1, local.num_splits));
+    return (rp.cos != nullptr ? fa::kvcache_rotary_image_bytes(kp) : 0) + fa::kvcache_workspace_bytes(kp, fa::kvcache_split(kp, -1, local.num_splits));
 }
 
 int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    fa_kvcache_options_v2 o;
-    int rc = fill_kvcache_all(user, options, kp, local, o, true);
+    fa_kvcache_options_v3 o;
+    fa::KvcacheRotaryParams rp;
+    int rc = fill_kvcache_all(user, options, kp, local, o, rp, true);
     if (rc) return rc;
     if (kp.b == 0) return 1;
-    return fa::kvcache_split(kp, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits);
+    int64_t avail = local.workspace != nullptr ? local.workspace_bytes : 0;
+    if (rp.cos != nullptr && (avail = rotary_split_bytes(kp, local)) < 0) return (int32_t)avail;
+    return fa::kvcache_split(kp, avail, local.num_splits);
 }
 
 int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* user, const fa_kvcache_options* options, void* stream) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    fa_kvcache_options_v2 o;
-    int rc = fill_kvcache_all(user, options, kp, local, o, true);
+    fa_kvcache_options_v3 o;
+    fa::KvcacheRotaryParams rp;
+    int rc = fill_kvcache_all(user, options, kp, local, o, rp, true);
     if (rc) return rc;
     if (kp.b == 0) return FA_OK;
-    kp.n_split = fa::kvcache_split(kp, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits);
-    kp.ws_o = kp.n_split > 1 ? (float*)local.workspace : nullptr;
+    int64_t avail = local.workspace != nullptr ? local.workspace_bytes : 0;
+    char* ws = (char*)local.workspace;
+    if (rp.cos != nullptr) {
+        // the fused rotary launch takes the place of the append: it writes the cache rows and the image of the rotated q at the head of the
+        // workspace; the attention kernels then run as without rotary, with the image as their q and nothing left to append
+        if ((avail = rotary_split_bytes(kp, local)) < 0) return (int)avail;
+        rp.kp = kp;
+        rp.q_image = ws;
+        ws += fa::kvcache_rotary_image_bytes(kp);
+        if ((rc = hip_status(fa::launch_kvcache_rotary(rp, local.dtype, (hipStream_t)stream), "fa_kvcache_rotary launch"))) return rc;
+        kp.q_ptr = rp.q_image;
+        kp.q = conv(contiguous_bshd(kp.seqlen_q, kp.h, kp.d));
+        kp.k_new = kp.v_new = nullptr;          // (seqlen_new stays: the appended rows count into the valid length)
+    }
+    kp.n_split = fa::kvcache_split(kp, avail, local.num_splits);
+    kp.ws_o = kp.n_split > 1 ? (float*)ws : nullptr;
     return hip_status(fa::launch_fwd_kvcache(kp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache launch");
 }
 

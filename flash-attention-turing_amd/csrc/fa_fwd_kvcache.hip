@@ -25,12 +25,15 @@
 // loads stay 16 bytes per lane (so a K load carries two chunks' worth of a key and the d-elements of a k-slot are permuted, in Q alike; a V
 // load covers 16 elements of a row), the codes are widened to T in registers - exactly - in front of the same MFMAs and the same LDS image,
 // and the (batch, KV head) descales fold into the softmax scale (K) and the final normalisation (V).  The append quantises k_new / v_new.
+// Rotary embedding (fa_kvcache_options_v3) is not in this file: fa_kvcache_rotary.hip replaces the append launch by a fused one that also leaves
+// the rotated q in an image these kernels read as their q (k_new = NULL then: nothing left to append, seqlen_new still counts into the length).
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include <type_traits>
 
 #include "fa_device.hpp"
+#include "fa_kvcache_quant.hpp"
 #include "fa_params.hpp"
 
 namespace fa {
@@ -564,49 +567,7 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_paged_kernel(const Kvca
     *(u32x4*)((char*)p.v_cache + 2 * (page * p.vc.batch + (int64_t)prow * p.vc.row + (int64_t)kvh * p.vc.head + 8 * slot)) = vx;
 }
 
-// One 16-bit element of k_new / v_new -> its e4m3 code under the (batch, KV head) descale: e4m3_rne(clamp(x / descale, -448, 448)).  The
-// quotient is the correctly rounded fp32 one (no fast-math), the clamp is explicit so that nothing depends on the conversion's saturation
-// mode, +-inf saturate with it; NaN keeps its sign and becomes 0x7f / 0xff.
-template <typename T>
-FA_DEV uint32_t quant_pair_e4m3(uint32_t w, float descale, uint32_t old, bool high) {
-    float x[2];
-    if constexpr (__is_same(T, _Float16)) {
-        x[0] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xffffu));
-        x[1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16));
-    } else {
-        x[0] = __builtin_bit_cast(float, w << 16);
-        x[1] = __builtin_bit_cast(float, w & 0xffff0000u);
-    }
-    float y[2];
-    static_for<0, 2>([&](auto ee) {
-        constexpr int e = decltype(ee)::value;
-        const float qv = x[e] / descale;
-        y[e] = __builtin_isnan(qv) ? qv : fminf(fmaxf(qv, -448.f), 448.f);
-    });
-    uint32_t r = high ? (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], (int)old, true)
-                      : (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], (int)old, false);
-    const int sh = high ? 16 : 0;
-    static_for<0, 2>([&](auto ee) {
-        constexpr int e = decltype(ee)::value;
-        if (__builtin_isnan(y[e])) {
-            const uint32_t code = 0x7fu | ((__builtin_bit_cast(uint32_t, x[e]) >> 24) & 0x80u);
-            r = (r & ~(0xffu << (sh + 8 * e))) | (code << (sh + 8 * e));
-        }
-    });
-    return r;
-}
-
-template <typename T>
-FA_DEV u32x2 quant8_e4m3(u32x4 x, float descale) {
-    u32x2 r;
-    r.x = quant_pair_e4m3<T>(x.x, descale, 0u, false);
-    r.x = quant_pair_e4m3<T>(x.y, descale, r.x, true);
-    r.y = quant_pair_e4m3<T>(x.z, descale, 0u, false);
-    r.y = quant_pair_e4m3<T>(x.w, descale, r.y, true);
-    return r;
-}
-
-// The append into an 8-bit cache, both layouts: 8 elements per thread, quantised as above (16 bytes read, 8 written).  Rows and pages are
+// The append into an 8-bit cache, both layouts: 8 elements per thread, quantised by quant8_e4m3 of fa_kvcache_quant.hpp (16 bytes read, 8 written).  Rows and pages are
 // found exactly as in the 16-bit kernels above.
 template <typename T, int D, bool PAGED>
 __global__ __launch_bounds__(256) void fa_kvcache_append_fp8_kernel(const KvcacheKernelParams p) {

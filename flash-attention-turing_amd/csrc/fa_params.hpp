@@ -163,6 +163,24 @@ int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_
 int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split);
 hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t stream);
 
+// Rotary embedding on a decode call (fa_kvcache_rotary.hip, fa_kvcache_options_v3).  One fused launch takes the place of the append: it
+// rotates k_new into the cache, copies / quantises v_new, and writes the rotated q into `q_image`, a contiguous (b, seqlen_q, h, d) buffer of
+// q's dtype at the head of the caller's workspace; the attention kernels then read that image as their q.  A block of its own and not
+// fields of KvcacheKernelParams: the kernarg segment of the attention, append and combine kernels stays what it was.
+struct KvcacheRotaryParams {
+    KvcacheKernelParams kp;     // the call as the append kernels see it (q_ptr / q: the caller's q)
+    const void* cos;            // (seqlen_ro, rotary_dim / 2), q's dtype, rows `row_stride` elements apart
+    const void* sin;
+    int64_t row_stride;
+    void* q_image;
+    int32_t seqlen_ro;          // >= 1; positions are clamped to seqlen_ro - 1
+    int32_t rotary_dim;         // a multiple of 16 in [16, d]
+    int32_t interleaved;        // 0: pairs (i, i + rotary_dim / 2) (GPT-NeoX), else (2 i, 2 i + 1) (GPT-J)
+    int32_t q_pos_per_row;      // query row t sits at cache_seqlens[i] + t (causal or windowed call), else every row at cache_seqlens[i]
+};
+int64_t kvcache_rotary_image_bytes(const KvcacheKernelParams& kp);     // bytes of q_image, rounded up to 16
+hipError_t launch_kvcache_rotary(const KvcacheRotaryParams& rp, int dtype, hipStream_t stream);
+
 // query-head group split chosen for a dK/dV launch (1 = none) and the workspace it needs
 int32_t dkdv_split(const BwdKernelParams& kp, int64_t avail_bytes);
 int64_t dkdv_workspace_bytes(const BwdKernelParams& kp, int32_t n_split);

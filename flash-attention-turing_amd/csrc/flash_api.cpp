@@ -267,11 +267,14 @@ std::vector<at::Tensor> mha_varlen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
 // k_cache / v_cache are page pools (num_blocks, page_block_size, h_k, d), addressed through the table in place as well.  window_size_left /
 // _right: a sliding window (fa_kvcache_options; (-1, -1) = none, the plain entry points).  A torch.float8_e4m3fn cache is the 8-bit cache of
 // fa_kvcache_options_v2 with its optional fp32 (batch, h_k) descales (any strides, read on the device); a cache is never copied, so a view
-// that breaks the alignment rule of the 8-bit loads is an error.
+// that breaks the alignment rule of the 8-bit loads is an error.  rotary_cos / rotary_sin ((seqlen_ro, rotary_dim / 2), q's dtype): rotary
+// embedding of q and of the appended k (fa_kvcache_options_v3), fused into the append launch; the image of the rotated q lives in the
+// workspace, whose size fa_kvcache_workspace_bytes_ex states, so the allocation below serves it as well.
 std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, c10::optional<at::Tensor> k_new_,
                                         c10::optional<at::Tensor> v_new_, c10::optional<at::Tensor> cache_seqlens_, bool is_causal,
                                         int64_t num_splits, c10::optional<at::Tensor> block_table_, int64_t window_size_left,
-                                        int64_t window_size_right, c10::optional<at::Tensor> k_descale_, c10::optional<at::Tensor> v_descale_) {
+                                        int64_t window_size_right, c10::optional<at::Tensor> k_descale_, c10::optional<at::Tensor> v_descale_,
+                                        c10::optional<at::Tensor> rotary_cos_, c10::optional<at::Tensor> rotary_sin_, bool rotary_interleaved) {
     TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4, "q, k_cache, v_cache must be rank-4 tensors");
     TORCH_CHECK(q.is_cuda() && k_cache.is_cuda() && v_cache.is_cuda(), "q, k, v must be GPU (HIP) tensors");
     TORCH_CHECK(k_cache.device() == q.device() && v_cache.device() == q.device(), "q, k, v must be on the same device");
@@ -347,7 +350,7 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
         p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr(); p.seqlen_new = (int32_t)k_new.size(1);
         p.k_new_stride = strides4(k_new); p.v_new_stride = strides4(v_new);
     }
-    fa_kvcache_options_v2 opt;
+    fa_kvcache_options_v3 opt;
     FA_PARAMS_INIT(opt);
     opt.is_local = window_size_left != -1 || window_size_right != -1;
     opt.window_size_left = (int32_t)window_size_left; opt.window_size_right = (int32_t)window_size_right;
@@ -365,7 +368,24 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
         descale(k_descale_, "k_descale", k_descale, opt.k_descale, opt.k_descale_batch_stride, opt.k_descale_head_stride);
         descale(v_descale_, "v_descale", v_descale, opt.v_descale, opt.v_descale_batch_stride, opt.v_descale_head_stride);
     }
-    const fa_kvcache_options* opts = (opt.is_local || fp8) ? (const fa_kvcache_options*)&opt : nullptr;
+    TORCH_CHECK(rotary_cos_.has_value() == rotary_sin_.has_value(), "rotary_cos and rotary_sin must both be given or both be None");
+    at::Tensor rotary_cos, rotary_sin;
+    if (rotary_cos_.has_value()) {
+        rotary_cos = *rotary_cos_; rotary_sin = *rotary_sin_;
+        TORCH_CHECK(k_new.defined(), "rotary_cos / rotary_sin are only applicable if k and v are passed in");
+        check_same_device(q, rotary_cos, "rotary_cos"); check_same_device(q, rotary_sin, "rotary_sin");
+        TORCH_CHECK(rotary_cos.scalar_type() == q.scalar_type() && rotary_sin.scalar_type() == q.scalar_type(), "rotary_cos / rotary_sin must have the dtype of q");
+        TORCH_CHECK(rotary_cos.dim() == 2 && rotary_sin.sizes() == rotary_cos.sizes(), "rotary_cos / rotary_sin must both have shape [seqlen_ro, rotary_dim / 2]");
+        TORCH_CHECK(rotary_cos.size(0) <= INT32_MAX && rotary_cos.size(1) <= INT32_MAX / 2, "rotary_cos / rotary_sin: sizes must fit in int32");
+        TORCH_CHECK(rotary_cos.stride(1) == 1 && rotary_sin.stride(1) == 1, "rotary_cos / rotary_sin: last dimension must be contiguous");
+        // one row stride serves both tables in the C ABI; a table whose row stride differs from the other's is made dense (tables are small)
+        if (rotary_cos.size(0) > 1 && rotary_cos.stride(0) != rotary_sin.stride(0)) { rotary_cos = rotary_cos.contiguous(); rotary_sin = rotary_sin.contiguous(); }
+        opt.rotary_cos = rotary_cos.data_ptr(); opt.rotary_sin = rotary_sin.data_ptr();
+        opt.rotary_row_stride = rotary_cos.size(0) > 1 ? rotary_cos.stride(0) : rotary_cos.size(1);
+        opt.seqlen_ro = (int32_t)rotary_cos.size(0); opt.rotary_dim = (int32_t)(2 * rotary_cos.size(1));
+        opt.rotary_interleaved = rotary_interleaved ? 1 : 0;
+    }
+    const fa_kvcache_options* opts = (opt.is_local || fp8 || rotary_cos.defined()) ? (const fa_kvcache_options*)&opt : nullptr;
     at::Tensor workspace;
     const int64_t ws_bytes = fa_kvcache_workspace_bytes_ex(&p, opts);
     if (ws_bytes < 0) check_status((int)ws_bytes);
@@ -430,7 +450,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fwd_kvcache", &mha_fwd_kvcache, "Decode forward over a KV cache (in-place append of k / v, split-KV attention)", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
           py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("block_table") = py::none(), py::arg("window_size_left") = -1,
-          py::arg("window_size_right") = -1, py::kw_only(), py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none());
+          py::arg("window_size_right") = -1, py::kw_only(), py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none(),
+          py::arg("rotary_cos") = py::none(), py::arg("rotary_sin") = py::none(), py::arg("rotary_interleaved") = true);
     m.def("attn_autograd", &attn_autograd, "differentiable forward (C++ autograd node over fwd / bwd)");
     m.def("attn_varlen_autograd", &attn_varlen_autograd, "differentiable packed forward (C++ autograd node over varlen_fwd / varlen_bwd)");
     m.def("abi_version", []() { return fa_abi_version(); });

@@ -90,6 +90,12 @@ class KvcacheOptionsV2(_Params):
                                           ("v_descale_batch_stride", ctypes.c_int64), ("v_descale_head_stride", ctypes.c_int64)]
 
 
+class KvcacheOptionsV3(_Params):
+    """fa_kvcache_options_v3: fa_kvcache_options_v2 plus the rotary embedding fields (same pointer, told apart by struct_size)"""
+    _fields_ = KvcacheOptionsV2._fields_ + [("rotary_cos", _vp), ("rotary_sin", _vp), ("rotary_row_stride", ctypes.c_int64), ("seqlen_ro", _i32),
+                                            ("rotary_dim", _i32), ("rotary_interleaved", _i32), ("reserved_", _i32)]
+
+
 FA_CACHE_FP8_E4M3 = 1
 
 
@@ -129,7 +135,7 @@ def lib():
         L.fa_kvcache_workspace_bytes.restype = ctypes.c_int64
         L.fa_kvcache_num_splits.argtypes = [ctypes.POINTER(KvcacheParams)]
         L.fa_kvcache_num_splits.restype = ctypes.c_int32
-        _op = ctypes.c_void_p                       # fa_kvcache_options or fa_kvcache_options_v2 (told apart by struct_size)
+        _op = ctypes.c_void_p                       # fa_kvcache_options, fa_kvcache_options_v2 or fa_kvcache_options_v3 (told apart by struct_size)
         L.fa_run_mha_fwd_kvcache_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op, _vp]
         L.fa_run_mha_fwd_kvcache_ex.restype = ctypes.c_int
         L.fa_kvcache_workspace_bytes_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op]
@@ -333,11 +339,13 @@ def kvcache_params(q, k_cache, v_cache, o, lse, cache_seqlens=None, k_new=None, 
     return p
 
 
-def kvcache_options(window_size=(-1, -1), cache_dtype=0, k_descale=None, v_descale=None):
+def kvcache_options(window_size=(-1, -1), cache_dtype=0, k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True):
     """fa_kvcache_options with a sliding window (left, right); (-1, -1) gives a zeroed struct (no window).  With cache_dtype
-    (FA_CACHE_FP8_E4M3) or a descale (float32 (b, h_k) torch tensors, any strides) the struct is fa_kvcache_options_v2."""
-    v2 = cache_dtype != 0 or k_descale is not None or v_descale is not None
-    o = KvcacheOptionsV2() if v2 else KvcacheOptions()
+    (FA_CACHE_FP8_E4M3) or a descale (float32 (b, h_k) torch tensors, any strides) the struct is fa_kvcache_options_v2; with rotary_cos /
+    rotary_sin ((seqlen_ro, rotary_dim / 2) torch tensors of q's dtype with one row stride) it is fa_kvcache_options_v3."""
+    v3 = rotary_cos is not None or rotary_sin is not None
+    v2 = v3 or cache_dtype != 0 or k_descale is not None or v_descale is not None
+    o = KvcacheOptionsV3() if v3 else KvcacheOptionsV2() if v2 else KvcacheOptions()
     left, right = window_size
     if (left, right) != (-1, -1):
         o.is_local, o.window_size_left, o.window_size_right = 1, int(left), int(right)
@@ -347,6 +355,12 @@ def kvcache_options(window_size=(-1, -1), cache_dtype=0, k_descale=None, v_desca
             o.k_descale, o.k_descale_batch_stride, o.k_descale_head_stride = k_descale.data_ptr(), k_descale.stride(0), k_descale.stride(1)
         if v_descale is not None:
             o.v_descale, o.v_descale_batch_stride, o.v_descale_head_stride = v_descale.data_ptr(), v_descale.stride(0), v_descale.stride(1)
+    if v3:
+        t = rotary_cos if rotary_cos is not None else rotary_sin
+        o.rotary_cos = None if rotary_cos is None else rotary_cos.data_ptr()
+        o.rotary_sin = None if rotary_sin is None else rotary_sin.data_ptr()
+        o.rotary_row_stride, o.seqlen_ro, o.rotary_dim = t.stride(0), t.shape[0], 2 * t.shape[1]
+        o.rotary_interleaved = int(bool(rotary_interleaved))
     return o
 
 

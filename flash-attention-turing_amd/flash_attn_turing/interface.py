@@ -110,8 +110,40 @@ def _check_cache_dtype(q, k_cache, v_cache, k_descale, v_descale):
             raise ValueError(f"{name} must be on q's device ({q.device}), got {t.device}")
 
 
+def _check_rotary(q, k_cache, k, block_table, rotary_cos, rotary_sin, rotary_interleaved):
+    """rotary_cos / rotary_sin: both or neither, (seqlen_ro, rotary_dim / 2) of q's dtype on q's device, last dim contiguous, rotary_dim a
+    multiple of 16 in [16, d], seqlen_ro at least the cache capacity; they need k / v"""
+    if not isinstance(rotary_interleaved, bool):
+        raise ValueError(f"rotary_interleaved must be a bool, got {rotary_interleaved!r}")
+    if rotary_cos is None and rotary_sin is None:
+        return
+    if rotary_cos is None or rotary_sin is None:
+        raise ValueError("rotary_cos and rotary_sin must both be given or both be None")
+    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if not isinstance(t, torch.Tensor) or t.dtype != q.dtype:
+            raise ValueError(f"{name} must be a tensor of q's dtype ({q.dtype}; fp32 tables are not supported), got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 2:
+            raise ValueError(f"{name} must have shape (seqlen_ro, rotary_dim / 2), got {tuple(t.shape)}")
+        if t.device != q.device:
+            raise ValueError(f"{name} must be on q's device ({q.device}), got {t.device}")
+    if rotary_cos.shape != rotary_sin.shape:
+        raise ValueError(f"rotary_cos and rotary_sin must have the same shape, got {tuple(rotary_cos.shape)} and {tuple(rotary_sin.shape)}")
+    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if t.stride(1) != 1:
+            raise ValueError(f"{name}: the last dimension must be contiguous")
+    rotary_dim = 2 * rotary_cos.shape[1]
+    if rotary_dim < 16 or rotary_dim % 16 != 0 or rotary_dim > q.shape[-1]:
+        raise ValueError(f"rotary_dim (2 x rotary_cos.shape[1] = {rotary_dim}) must be a multiple of 16 with 16 <= rotary_dim <= head_dim ({q.shape[-1]})")
+    if k is None:
+        raise ValueError("rotary_cos / rotary_sin are only applicable if k and v are passed in")
+    capacity = k_cache.shape[1] * block_table.shape[1] if block_table is not None else k_cache.shape[1]
+    if rotary_cos.shape[0] < max(capacity, 1):
+        raise ValueError(f"seqlen_ro ({rotary_cos.shape[0]} rows of rotary_cos / rotary_sin) must be at least the cache capacity ({capacity})")
+
+
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, causal=False, num_splits=0, return_softmax_lse=False, *,
-                            block_table=None, window_size=(-1, -1), k_descale=None, v_descale=None):
+                            block_table=None, window_size=(-1, -1), k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None,
+                            rotary_interleaved=True):
     """Decode attention over a KV cache (upstream flash-attn's ``flash_attn_with_kvcache`` conventions; forward only).
 
     q: (batch, seqlen_q, nheads, d); k_cache, v_cache: (batch, seqlen_cache, nheads_k, d), any batch / row / head strides (used in place).
@@ -161,6 +193,23 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     16 elements and its storage offset a multiple of 16 bytes; a view that breaks this is rejected (RuntimeError), never copied.
     ``float8_e4m3fnuz``, ``float8_e5m2`` and any other cache dtype that is not q's are a ValueError, as is a descale with a 16-bit cache
     or one of the wrong dtype, shape or device.
+
+    Rotary embedding: rotary_cos, rotary_sin (keyword, optional, both or neither): (seqlen_ro, rotary_dim / 2) tensors of q's dtype (not
+    fp32) on q's device, last dim contiguous, any row stride; rotary_dim a multiple of 16 with 16 <= rotary_dim <= d (elements rotary_dim ..
+    d - 1 pass through), seqlen_ro at least the cache capacity.  Only applicable if k and v are passed in (upstream's rule).  The appended
+    row s of sequence i is rotated at position cache_seqlens[i] + s before it is written to the cache; query row t at cache_seqlens[i] + t if
+    ``causal`` or a ``window_size`` other than (-1, -1) was passed, else every query row at cache_seqlens[i] (upstream's rule; decided from
+    the arguments as passed).  rotary_interleaved (keyword, bool, default True as upstream): True pairs (x[2i], x[2i+1]) (GPT-J), False pairs
+    (x[i], x[i + rotary_dim / 2]) (GPT-NeoX).  With c = cos[p, i], s = sin[p, i]: ``y_a = x_a * c - x_b * s``, ``y_b = x_b * c + x_a * s``
+    in fp32 (each operation rounded on its own), rounded once to q's dtype - so the call equals, bit for bit in out, lse and every cache
+    byte, the call without rotary on ``q_rot`` / ``k_rot`` computed that way with torch (v is appended as is), for the same num_splits.
+    With an FP8 cache the rotated row (already in q's dtype) goes through the quantiser above.  Everything else carries over unchanged:
+    block_table, window_size, causal, GQA / MQA (the query heads of a token share its position), seqlen_q > 1, dead rows, the NaN rules,
+    what is never read, determinism per split count, the split count itself.  q, k, v and the tables are not written; table rows other
+    than the positions used are never read, and on the device a position is clamped to seqlen_ro - 1.  The rotation is fused into the
+    append launch (no extra launch, no host synchronisation: a captured call replays with the lengths then in memory); the rotated q
+    passes through an image in the call's workspace.  Wrong dtype, rank, shape, device, rotary_dim or seqlen_ro, one table without the
+    other, tables without k / v, or a rotary_interleaved that is not a bool: ValueError.
     """
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v)):
         raise RuntimeError("flash_attn_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
@@ -168,8 +217,9 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
         raise ValueError("k and v must both be given or both be None")
     _check_cache_dtype(q, k_cache, v_cache, k_descale, v_descale)
     left, right = _window_pair(window_size)
+    _check_rotary(q, k_cache, k, block_table, rotary_cos, rotary_sin, rotary_interleaved)
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=q.device)
     out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right,
-                              k_descale=k_descale, v_descale=v_descale)
+                              k_descale=k_descale, v_descale=v_descale, rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved)
     return (out, lse) if return_softmax_lse else out

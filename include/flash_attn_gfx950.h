@@ -213,8 +213,8 @@ typedef struct fa_kvcache_params {
 } fa_kvcache_params;
 
 /* Options of a decode call that fa_kvcache_params does not carry (its layout is fixed; the _ex entry points below take both).  Same ABI 4
- * header rule (FA_PARAMS_INIT): a zeroed struct means today's behaviour, and options appended later (decode softmax scale, softcap, rotary
- * embedding on append) will be optional fields after these.  A NULL options pointer is the same as a zeroed struct.
+ * header rule (FA_PARAMS_INIT): a zeroed struct means today's behaviour, and options appended later (decode softmax scale, softcap) will be
+ * optional fields after these (the 8-bit cache and the rotary embedding on append arrived that way, below).  A NULL options pointer is the same as a zeroed struct.
  * Sliding window (upstream flash-attn's window_size; is_local = 0: no window, the two sizes are not read).  Key j of sequence i (valid
  * length L_i as above) is visible to query t when
  *     L_i - seqlen_q + t - window_size_left <= j <= L_i - seqlen_q + t + window_size_right,
@@ -249,7 +249,31 @@ typedef struct fa_kvcache_params {
  * o and lse NaN (e4m3fn has no inf).  Paged and contiguous calls over the same logical cache give the same bits.
  * Alignment of an 8-bit cache (the kernels keep 16-byte loads): base pointers 16-byte aligned; row, head and batch / page strides multiples
  * of 16 elements, row stride >= d; one sequence (one page) spans less than 2^31 bytes.  Anything else is FA_ERR_BAD_STRIDE - a cache is
- * never copied.  An unknown cache_dtype, or a descale pointer without FA_CACHE_FP8_E4M3, is FA_ERR_BAD_DTYPE. */
+ * never copied.  An unknown cache_dtype, or a descale pointer without FA_CACHE_FP8_E4M3, is FA_ERR_BAD_DTYPE.
+ *
+ * Rotary embedding (FA_HAS_KVCACHE_ROTARY): fa_kvcache_options_v3 below is fa_kvcache_options_v2 with optional fields appended; the _ex entry
+ * points accept exactly the three sizes, and a v3 struct with a zeroed tail is a v2 call.  FA_ABI_VERSION is unchanged.  rotary_cos /
+ * rotary_sin (both or neither; NULL = off): DEVICE tables (seqlen_ro, rotary_dim / 2) of `dtype` (the dtype of q - not fp32), last dim
+ * contiguous, rows rotary_row_stride elements apart.  rotary_dim is a multiple of 16 with 16 <= rotary_dim <= d; elements rotary_dim .. d - 1
+ * of a row pass through.  seqlen_ro >= seqlen_cache.  Rotary needs k_new / v_new (the rotation belongs to the append).  With
+ * c = cos[p, i], s = sin[p, i], i < rotary_dim / 2, a row x at position p becomes y with, for the pair (a, b) = (i, i + rotary_dim / 2)
+ * (rotary_interleaved = 0, GPT-NeoX) or (2 i, 2 i + 1) (rotary_interleaved != 0, GPT-J),
+ *     y_a = x_a * c - x_b * s,    y_b = x_b * c + x_a * s,
+ * every operation in fp32, rounded on its own (no contraction), and y rounded once, to nearest even, to `dtype`.  Position of appended row s
+ * of sequence i: max(cache_seqlens[i], 0) + s, its cache row.  Position of query row t: max(cache_seqlens[i], 0) + t when is_causal != 0 or
+ * the options carry a window other than (-1, -1) - as the caller states them, before a window that cannot bind is normalised away - else
+ * max(cache_seqlens[i], 0) for every t.  On the device a position is clamped to seqlen_ro - 1: no value of cache_seqlens reads outside the
+ * tables.  THE CONTRACT: the call equals, bit for bit in o, lse and every cache byte, the same call without rotary on q and k_new rotated by
+ * the formula above (v_new is appended as is), for the same num_splits; with an 8-bit cache the rotated row, already rounded to `dtype`,
+ * goes through the quantiser above.  So everything stated for the plain call carries over.  q, k_new, v_new and the tables are not written;
+ * table rows other than the positions above are never read.  One fused launch takes the place of the append (rotate k_new into the cache,
+ * copy / quantise v_new, write the rotated q into an image); the call stays at up to three launches.  The image comes out of the workspace:
+ * fa_kvcache_workspace_bytes_ex returns align16(b * seqlen_q * h * d * 2) plus what it returns without rotary; the image sits first, the
+ * split partials behind it, and "a smaller workspace caps the split" applies to what remains.  Split count and split workspace are those of
+ * the same call without rotary.  A workspace too small for the image is FA_ERR_BAD_SHAPE (there is no path without the image).  One table
+ * without the other, rotary_dim not a multiple of 16 or outside [16, d], seqlen_ro < max(seqlen_cache, 1), rotary without k_new / v_new:
+ * FA_ERR_BAD_SHAPE; a table pointer that is not 16-byte aligned, or a row stride that is not a multiple of 8 elements or is below
+ * rotary_dim / 2 (with more than one row): FA_ERR_BAD_STRIDE. */
 typedef struct fa_kvcache_options {
     uint32_t struct_size;       /* sizeof(fa_kvcache_options) in the caller's translation unit */
     uint32_t magic;             /* FA_PARAMS_MAGIC */
@@ -270,6 +294,26 @@ typedef struct fa_kvcache_options_v2 {      /* FA_PARAMS_INIT(o); then fa_..._ex
     int64_t k_descale_batch_stride, k_descale_head_stride;   /* in elements */
     int64_t v_descale_batch_stride, v_descale_head_stride;
 } fa_kvcache_options_v2;
+#define FA_HAS_KVCACHE_ROTARY 1
+typedef struct fa_kvcache_options_v3 {      /* FA_PARAMS_INIT(o); then fa_..._ex(&p, (const fa_kvcache_options*)&o, ...) */
+    uint32_t struct_size;       /* sizeof(fa_kvcache_options_v3) */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    int32_t is_local;           /* the fields of fa_kvcache_options_v2, same offsets */
+    int32_t window_size_left;
+    int32_t window_size_right;
+    int32_t cache_dtype;
+    const float* k_descale;
+    const float* v_descale;
+    int64_t k_descale_batch_stride, k_descale_head_stride;
+    int64_t v_descale_batch_stride, v_descale_head_stride;
+    const void* rotary_cos;     /* optional: device table (seqlen_ro, rotary_dim / 2) of `dtype`; NULL = no rotary (the fields below are not read) */
+    const void* rotary_sin;
+    int64_t rotary_row_stride;  /* elements between table rows (both tables) */
+    int32_t seqlen_ro;          /* table rows, >= seqlen_cache */
+    int32_t rotary_dim;         /* a multiple of 16 in [16, d] */
+    int32_t rotary_interleaved; /* 0: pairs (i, i + rotary_dim / 2); != 0: pairs (2 i, 2 i + 1) */
+    int32_t reserved_;          /* 0 (pads the struct to a multiple of 8 bytes) */
+} fa_kvcache_options_v3;
 
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
@@ -329,9 +373,11 @@ int fa_run_mha_fwd_kvcache(const fa_kvcache_params* params, void* stream);
 int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* params);
 /* Key splits the launch of these params would use, workspace fields included (NULL / 0 -> 1).  Host-only.  Negative = error code. */
 int32_t fa_kvcache_num_splits(const fa_kvcache_params* params);
-/* The same three with options (fa_kvcache_options above; NULL = the plain calls).  Their presence is how a caller detects the window.
+/* The same three with options (fa_kvcache_options / _v2 / _v3 above; NULL = the plain calls).  Their presence is how a caller detects the window.
  * Options are validated before anything is launched: a bad header is FA_ERR_BAD_ABI, a window size below -1 FA_ERR_BAD_SHAPE, an unknown
- * cache_dtype or a descale without FA_CACHE_FP8_E4M3 FA_ERR_BAD_DTYPE, an 8-bit cache view that breaks the alignment rule FA_ERR_BAD_STRIDE. */
+ * cache_dtype or a descale without FA_CACHE_FP8_E4M3 FA_ERR_BAD_DTYPE, an 8-bit cache view that breaks the alignment rule FA_ERR_BAD_STRIDE,
+ * the rotary fields as listed with fa_kvcache_options_v3.  With rotary, fa_kvcache_num_splits_ex answers for the workspace behind the image
+ * (a workspace that cannot hold the image is FA_ERR_BAD_SHAPE there as in the launch). */
 int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* params, const fa_kvcache_options* options, void* stream);
 int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);
 int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);

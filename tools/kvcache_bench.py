@@ -19,6 +19,12 @@ interleaved, medians.  TB/s counts the bytes the window actually reads.  Caches 
 the 16-bit call on the same logical cache (the 8-bit codes widened, which is exact), interleaved, medians; ms of both, TB/s of each over the
 bytes it really reads, the fraction of 6.3 TB/s, and the ratio.  Caches rotate until the 8-bit K/V alone exceed 256 MiB.
 
+--rotary [DIM] measures the rotary embedding instead (DIM = rotary_dim, default head_dim; --rotary-neox for the non-interleaved pairing): per
+grid point with seqlen_q = seqlen_new = 1, appending at the cache's last row, (A) the rotary call; (B) the plain call with append on
+pre-rotated q / k - the same work minus the rotation, the floor - timed TWICE (B, B2), so that the spread of one thing measured twice in the
+same run stands next to A / B; (C) what a caller does without the feature: torch ops on the GPU (cos / sin rows gathered by cache_seqlens on
+the device, the rotation of q and k in fp32) followed by the plain call.  All four interleaved, medians.  A and C must agree bit for bit.
+
 --baseline-library PATH records an interleaved A/B of the plain (no window) call through the C ABI of this build and of the library at
 PATH (e.g. a build of the parent commit), on the same data; the outputs must agree bit for bit.  --length L (repeatable) replaces the
 grid's cache lengths."""
@@ -231,6 +237,59 @@ def run_fp8_point(pt, rounds):
                 frac_of_6p3_16bit=round(tb16 * 1e12 / HBM_ACHIEVABLE, 3), n_split=n_split, fp8_over_16bit=round(ms_8 / ms_16, 3))
 
 
+def torch_rotate(x, cos, sin, pos, interleaved):
+    """the rotation with torch ops on x's device: x (b, s, heads, d), pos (b,) long - every row of sequence i at pos[i] (s = 1 here)"""
+    rd = 2 * cos.shape[1]
+    c, s = cos[pos].float()[:, None, None, :], sin[pos].float()[:, None, None, :]
+    xf = x.float()
+    if interleaved:
+        xa, xb = xf[..., 0:rd:2], xf[..., 1:rd:2]
+        y = torch.stack((xa * c - xb * s, xb * c + xa * s), dim=-1).flatten(-2)
+    else:
+        xa, xb = xf[..., :rd // 2], xf[..., rd // 2:rd]
+        y = torch.cat((xa * c - xb * s, xb * c + xa * s), dim=-1)
+    y = y.to(x.dtype)
+    return y if rd == x.shape[-1] else torch.cat((y, x[..., rd:]), dim=-1)
+
+
+def run_rotary_point(pt, rotary_dim, interleaved, rounds):
+    """(A) the rotary call, (B, B2) the plain call with append on pre-rotated inputs, twice, (C) torch rotation + the plain call; interleaved"""
+    dev = torch.device("cuda:0")
+    b, h, hk, d, L, dt = pt["b"], pt["h"], pt["h_k"], pt["d"], pt["L"], pt["dtype"]
+    rd = min(rotary_dim or d, d)
+    kv_bytes = 2 * b * L * hk * d * 2
+    n = _rotation(kv_bytes, kv_bytes)
+    caches = [(torch.empty(b, L, hk, d, device=dev, dtype=dt).uniform_(-2, 2), torch.empty(b, L, hk, d, device=dev, dtype=dt).uniform_(-2, 2))
+              for _ in range(n)]
+    q, k, v = (torch.randn(b, 1, hh, d, device=dev, dtype=dt) for hh in (h, hk, hk))
+    cs = torch.full((b,), L - 1, dtype=torch.int32, device=dev)
+    inv = 10000.0 ** (-torch.arange(0, rd, 2, dtype=torch.float64, device=dev) / rd)
+    ang = torch.arange(L, dtype=torch.float64, device=dev)[:, None] * inv[None, :]
+    cos, sin = ang.cos().to(dt), ang.sin().to(dt)
+    pos = cs.long()
+    q_rot, k_rot = torch_rotate(q, cos, sin, pos, interleaved), torch_rotate(k, cos, sin, pos, interleaved)
+    f_a = lambda i: F.flash_attn_with_kvcache(q, caches[i][0], caches[i][1], k=k, v=v, cache_seqlens=cs, rotary_cos=cos, rotary_sin=sin, rotary_interleaved=interleaved)
+    f_b = lambda i: F.flash_attn_with_kvcache(q_rot, caches[i][0], caches[i][1], k=k_rot, v=v, cache_seqlens=cs)
+    f_c = lambda i: F.flash_attn_with_kvcache(torch_rotate(q, cos, sin, cs.long(), interleaved), caches[i][0], caches[i][1],
+                                              k=torch_rotate(k, cos, sin, cs.long(), interleaved), v=v, cache_seqlens=cs)
+    o_a, o_b, o_c = f_a(0), f_b(0), f_c(0)
+    torch.cuda.synchronize()
+    same = torch.equal(o_a.view(torch.int16), o_b.view(torch.int16)) and torch.equal(o_a.view(torch.int16), o_c.view(torch.int16))
+    t = {"a": [], "b": [], "b2": [], "c": []}
+    for _ in range(rounds):
+        t["a"].append(time_rotation(f_a, n, 20))
+        t["b"].append(time_rotation(f_b, n, 20))
+        t["c"].append(time_rotation(f_c, n, 20))
+        t["b2"].append(time_rotation(f_b, n, 20))
+    ms = {k_: statistics.median(v_) for k_, v_ in t.items()}
+    del caches
+    torch.cuda.empty_cache()
+    return dict(b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=1, seqlen_new=1, dtype=str(dt).replace("torch.", ""), rotary_dim=rd, interleaved=bool(interleaved),
+                kv_gb=round(kv_bytes / 1e9, 3), caches_rotated=n, ms_rotary=round(ms["a"], 5), ms_prerotated=round(ms["b"], 5), ms_prerotated_again=round(ms["b2"], 5),
+                ms_torch_rotation=round(ms["c"], 5), rotary_over_prerotated=round(ms["a"] / ms["b"], 4), prerotated_again_over_prerotated=round(ms["b2"] / ms["b"], 4),
+                torch_rotation_over_rotary=round(ms["c"] / ms["a"], 3), bit_identical=bool(same))
+
+
 def _baseline_lib(path):
     L = ctypes.CDLL(os.path.abspath(path))
     L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
@@ -299,6 +358,9 @@ def main():
     ap.add_argument("--baseline-library", metavar="PATH", help="A/B of the plain call against this libflash_attn_gfx950.so")
     ap.add_argument("--kv-dtype", choices=("fp16", "fp8"), default="fp16", help="fp8: the 8-bit cache against the 16-bit call on the same logical cache")
     ap.add_argument("--length", type=int, action="append", metavar="L", help="cache length(s) instead of the grid's")
+    ap.add_argument("--rotary", type=int, nargs="?", const=0, default=None, metavar="DIM",
+                    help="the rotary call against the plain call on pre-rotated inputs and against a torch rotation (seqlen_q = 1 points; DIM = rotary_dim, default head_dim)")
+    ap.add_argument("--rotary-neox", action="store_true", help="with --rotary: the non-interleaved (GPT-NeoX) pairing instead of the interleaved default")
     a = ap.parse_args()
     base = _baseline_lib(a.baseline_library) if a.baseline_library else None
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
@@ -309,6 +371,9 @@ def main():
         for pt in grid(a.quick, a.length):
             if base is not None:
                 print(json.dumps(run_ab_point(pt, base, a.rounds)), flush=True)
+            elif a.rotary is not None:
+                if pt["seqlen_q"] == 1:
+                    print(json.dumps(run_rotary_point(pt, a.rotary, not a.rotary_neox, a.rounds)), flush=True)
             elif a.kv_dtype == "fp8":
                 print(json.dumps(run_fp8_point(pt, a.rounds)), flush=True)
             elif a.window:
