@@ -343,17 +343,18 @@ int fa_mha_varlen_bwd(const void* q, const void* k, const void* v, const void* o
     return fa_run_mha_bwd(&p, stream);
 }
 
-// The options pointer of the _ex entry points -> a zeroed fa_kvcache_options_v3 filled with what the caller's struct carries: struct_size says
-// which of the three layouts it is (fa_kvcache_options: the window alone; fa_kvcache_options_v2: plus the 8-bit cache fields;
-// fa_kvcache_options_v3: plus the rotary fields).  NULL = all zero.
-static int import_kvcache_options(const fa_kvcache_options* user, fa_kvcache_options_v3& o) {
+// The options pointer of the _ex entry points -> a zeroed fa_kvcache_options_v4 filled with what the caller's struct carries: struct_size says
+// which of the four layouts it is (fa_kvcache_options: the window alone; fa_kvcache_options_v2: plus the 8-bit cache fields;
+// fa_kvcache_options_v3: plus the rotary fields; fa_kvcache_options_v4: plus the ragged-batch fields).  NULL = all zero.
+static int import_kvcache_options(const fa_kvcache_options* user, fa_kvcache_options_v4& o) {
     memset(&o, 0, sizeof(o));
     if (user == nullptr) return FA_OK;
     if (user->magic != FA_PARAMS_MAGIC)
         return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: no {struct_size, magic} header (FA_PARAMS_INIT); recompile against include/flash_attn_gfx950.h (ABI %d)", FA_ABI_VERSION);
-    if (user->struct_size != sizeof(fa_kvcache_options) && user->struct_size != sizeof(fa_kvcache_options_v2) && user->struct_size != sizeof(fa_kvcache_options_v3))
-        return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: struct_size %u is none of sizeof(fa_kvcache_options) = %zu, sizeof(fa_kvcache_options_v2) = %zu, sizeof(fa_kvcache_options_v3) = %zu - header / library mismatch",
-                    user->struct_size, sizeof(fa_kvcache_options), sizeof(fa_kvcache_options_v2), sizeof(fa_kvcache_options_v3));
+    if (user->struct_size != sizeof(fa_kvcache_options) && user->struct_size != sizeof(fa_kvcache_options_v2) && user->struct_size != sizeof(fa_kvcache_options_v3) &&
+        user->struct_size != sizeof(fa_kvcache_options_v4))
+        return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: struct_size %u is none of sizeof(fa_kvcache_options) = %zu, sizeof(fa_kvcache_options_v2) = %zu, sizeof(fa_kvcache_options_v3) = %zu, sizeof(fa_kvcache_options_v4) = %zu - header / library mismatch",
+                    user->struct_size, sizeof(fa_kvcache_options), sizeof(fa_kvcache_options_v2), sizeof(fa_kvcache_options_v3), sizeof(fa_kvcache_options_v4));
     memcpy(&o, user, user->struct_size);
     if (o.cache_dtype != 0 && o.cache_dtype != FA_CACHE_FP8_E4M3)
         return fail(FA_ERR_BAD_DTYPE, "cache_dtype %d unsupported (0 = the dtype of q, %d = FA_CACHE_FP8_E4M3; e4m3fnuz and e5m2 caches are not supported)", o.cache_dtype,
@@ -365,12 +366,13 @@ static int import_kvcache_options(const fa_kvcache_options* user, fa_kvcache_opt
 
 // with_workspace = false: the `workspace` fields are not looked at (fa_kvcache_workspace_bytes)
 static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& kp, fa_kvcache_params& local, bool with_workspace,
-                        const fa_kvcache_options_v3& o) {
+                        const fa_kvcache_options_v4& o) {
     // the paged-cache fields are optional: a caller built before them passes struct_size = offsetof(block_table) and gets NULL / 0
     int rc = import_params(user, local, "fa_kvcache_params", offsetof(fa_kvcache_params, block_table));
     if (rc) return rc;
     const fa_kvcache_params* p = &local;
     const bool paged = p->block_table != nullptr;
+    const bool ragged = o.cu_seqlens_q != nullptr;      // q, o, k_new, v_new are packed: their batch strides are not read (seqlen_q = max_seqlen_q)
     if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0 || p->seqlen_new < 0 || p->h <= 0 || p->h_k <= 0)
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d seqlen_new=%d h=%d h_k=%d", p->b, p->seqlen_q, p->seqlen_cache,
                     p->seqlen_new, p->h, p->h_k);
@@ -401,8 +403,8 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
         return fail(FA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
     if (p->b > 0) {
         if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
-        if ((rc = check_tensor("q", p->q, p->q_stride, p->seqlen_q, p->d, false))) return rc;
-        if ((rc = check_tensor("o", p->o, p->o_stride, p->seqlen_q, p->d, false))) return rc;
+        if ((rc = check_tensor("q", p->q, p->q_stride, p->seqlen_q, p->d, ragged))) return rc;
+        if ((rc = check_tensor("o", p->o, p->o_stride, p->seqlen_q, p->d, ragged))) return rc;
         // paged: the descriptors span at most one page, so the 2^31-byte limit applies per page (page offsets are 64-bit)
         const int64_t cache_rows = paged ? p->page_block_size : p->seqlen_cache;
         if (o.cache_dtype == FA_CACHE_FP8_E4M3) {
@@ -414,8 +416,8 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
             if ((rc = check_tensor("v_cache", p->v_cache, p->v_cache_stride, cache_rows, p->d, false))) return rc;
         }
         if (p->k_new != nullptr) {
-            if ((rc = check_tensor("k_new", p->k_new, p->k_new_stride, p->seqlen_new, p->d, false))) return rc;
-            if ((rc = check_tensor("v_new", p->v_new, p->v_new_stride, p->seqlen_new, p->d, false))) return rc;
+            if ((rc = check_tensor("k_new", p->k_new, p->k_new_stride, p->seqlen_new, p->d, ragged))) return rc;
+            if ((rc = check_tensor("v_new", p->v_new, p->v_new_stride, p->seqlen_new, p->d, ragged))) return rc;
         }
     }
     memset(&kp, 0, sizeof(kp));
@@ -443,7 +445,7 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
 // fa_kvcache_options (NULL = none) -> the window fields of kp, normalised: right = 0 under causal, and a side that cannot bind is -1 (left >=
 // seqlen_cache - 1: lo_t <= L - 1 - left <= 0 for every row; right >= seqlen_q - 1: lim_t >= L for every row).  A window whose left side is
 // unbounded and whose right side is unbounded or the causal limit is exactly the plain call: is_local stays 0 (the plain kernels, split and bits).
-static int fill_kvcache_window(const fa_kvcache_options_v3& o, fa::KvcacheKernelParams& kp) {
+static int fill_kvcache_window(const fa_kvcache_options_v4& o, fa::KvcacheKernelParams& kp) {
     if (!o.is_local) return FA_OK;
     if (o.window_size_left < -1 || o.window_size_right < -1)
         return fail(FA_ERR_BAD_SHAPE, "window_size (%d, %d): each side must be >= -1 (-1 = unbounded)", o.window_size_left, o.window_size_right);
@@ -458,7 +460,7 @@ static int fill_kvcache_window(const fa_kvcache_options_v3& o, fa::KvcacheKernel
 
 // The rotary fields of the options (rotary_cos = rotary_sin = NULL: off, rp.cos stays NULL and nothing else is looked at) -> rp, validated.
 // The query-position rule is decided from what the caller stated (is_causal, a window other than (-1, -1)), not from the normalised window.
-static int fill_kvcache_rotary(const fa_kvcache_options_v3& o, const fa::KvcacheKernelParams& kp, fa::KvcacheRotaryParams& rp) {
+static int fill_kvcache_rotary(const fa_kvcache_options_v4& o, const fa::KvcacheKernelParams& kp, fa::KvcacheRotaryParams& rp) {
     memset(&rp, 0, sizeof(rp));
     if (o.rotary_cos == nullptr && o.rotary_sin == nullptr) return FA_OK;
     if (o.rotary_cos == nullptr || o.rotary_sin == nullptr) return fail(FA_ERR_BAD_SHAPE, "rotary_cos and rotary_sin must both be given or both be NULL");
@@ -479,11 +481,39 @@ static int fill_kvcache_rotary(const fa_kvcache_options_v3& o, const fa::Kvcache
     return FA_OK;
 }
 
+// The ragged-batch fields of the options (cu_seqlens_q = NULL: off, rg.cu_q stays NULL and only a stray cu_seqlens_k_new is looked at) -> rg,
+// validated.  rg.kp is left to the caller (the launch takes the finished kp).
+static int fill_kvcache_ragged(const fa_kvcache_options_v4& o, const fa::KvcacheKernelParams& kp, const fa::KvcacheRotaryParams& rp, fa::KvcacheRaggedParams& rg) {
+    memset(&rg, 0, sizeof(rg));
+    if (o.cu_seqlens_q == nullptr) {
+        if (o.cu_seqlens_k_new != nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_k_new given without cu_seqlens_q (packed k_new / v_new belong to a ragged call)");
+        return FA_OK;
+    }
+    if (rp.cos != nullptr)
+        return fail(FA_ERR_BAD_SHAPE, "rotary_cos / rotary_sin together with cu_seqlens_q are not supported (rotary with ragged queries is out of scope of this library version)");
+    if (o.cu_seqlens_k_new != nullptr && kp.k_new == nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_k_new given without k_new / v_new");
+    if (kp.k_new != nullptr && o.cu_seqlens_k_new == nullptr)
+        return fail(FA_ERR_NULL_POINTER, "k_new / v_new in a ragged call (cu_seqlens_q) are packed and need cu_seqlens_k_new");
+    if (o.total_q < 0 || o.total_k_new < 0)
+        return fail(FA_ERR_BAD_SHAPE, "total_q (%lld) and total_k_new (%lld) must be >= 0", (long long)o.total_q, (long long)o.total_k_new);
+    if (((uintptr_t)o.cu_seqlens_q & 3) != 0 || ((uintptr_t)o.cu_seqlens_k_new & 3) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "cu_seqlens_q / cu_seqlens_k_new must be 4-byte aligned");
+    // the attention grid is slots x h_k x n_split workgroups (n_split <= 128) and a tile index is an int
+    if (o.total_q * kp.h_ratio >= ((int64_t)1 << 31) || (fa::kvcache_ragged_slots(kp, o.total_q, nullptr) * kp.h_k) >= ((int64_t)1 << 24))
+        return fail(FA_ERR_BAD_SHAPE, "ragged call too large: total_q = %lld rows x %d heads per KV head over %d sequences exceeds the launch grid", (long long)o.total_q,
+                    kp.h_ratio, kp.b);
+    rg.cu_q = o.cu_seqlens_q;
+    rg.cu_kn = kp.k_new != nullptr ? o.cu_seqlens_k_new : nullptr;
+    rg.total_q = o.total_q;
+    rg.total_kn = kp.k_new != nullptr ? o.total_k_new : 0;
+    return FA_OK;
+}
+
 // Params first, as before the options existed (their errors win), except that the cache tensors are checked under the cache dtype the
 // options state; then the options' own values.
 static int fill_kvcache_all(const fa_kvcache_params* user, const fa_kvcache_options* options, fa::KvcacheKernelParams& kp, fa_kvcache_params& local,
-                            fa_kvcache_options_v3& o, fa::KvcacheRotaryParams& rp, bool with_workspace) {
-    fa_kvcache_options_v3 none;
+                            fa_kvcache_options_v4& o, fa::KvcacheRotaryParams& rp, fa::KvcacheRaggedParams& rg, bool with_workspace) {
+    fa_kvcache_options_v4 none;
     memset(&none, 0, sizeof(none));
     const int orc = import_kvcache_options(options, o);
     char oerr[sizeof(g_err)];
@@ -495,7 +525,8 @@ static int fill_kvcache_all(const fa_kvcache_params* user, const fa_kvcache_opti
         return orc;
     }
     if ((rc = fill_kvcache_window(o, kp))) return rc;
-    return fill_kvcache_rotary(o, kp, rp);
+    if ((rc = fill_kvcache_rotary(o, kp, rp))) return rc;
+    return fill_kvcache_ragged(o, kp, rp, rg);
 }
 
 // Workspace left for the split partials of a rotary call once the image of the rotated q has taken its part; a workspace that cannot hold
@@ -512,37 +543,49 @@ static int64_t rotary_split_bytes(const fa::KvcacheKernelParams& kp, const fa_kv
 int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    fa_kvcache_options_v3 o;
+    fa_kvcache_options_v4 o;
     fa::KvcacheRotaryParams rp;
-    int rc = fill_kvcache_all(user, options, kp, local, o, rp, false);
+    fa::KvcacheRaggedParams rg;
+    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, false);
     if (rc) return rc;
     if (kp.b == 0) return 0;
-    return (rp.cos != nullptr ? fa::kvcache_rotary_image_bytes(kp) : 0) + fa::kvcache_workspace_bytes(kp, fa::kvcache_split(kp, -1, local.num_splits));
+    const int64_t total_q = rg.cu_q != nullptr ? rg.total_q : -1;
+    return (rp.cos != nullptr ? fa::kvcache_rotary_image_bytes(kp) : 0) +
+           fa::kvcache_workspace_bytes(kp, fa::kvcache_split(kp, -1, local.num_splits, total_q), total_q);
 }
 
 int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    fa_kvcache_options_v3 o;
+    fa_kvcache_options_v4 o;
     fa::KvcacheRotaryParams rp;
-    int rc = fill_kvcache_all(user, options, kp, local, o, rp, true);
+    fa::KvcacheRaggedParams rg;
+    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, true);
     if (rc) return rc;
     if (kp.b == 0) return 1;
     int64_t avail = local.workspace != nullptr ? local.workspace_bytes : 0;
     if (rp.cos != nullptr && (avail = rotary_split_bytes(kp, local)) < 0) return (int32_t)avail;
-    return fa::kvcache_split(kp, avail, local.num_splits);
+    return fa::kvcache_split(kp, avail, local.num_splits, rg.cu_q != nullptr ? rg.total_q : -1);
 }
 
 int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* user, const fa_kvcache_options* options, void* stream) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    fa_kvcache_options_v3 o;
+    fa_kvcache_options_v4 o;
     fa::KvcacheRotaryParams rp;
-    int rc = fill_kvcache_all(user, options, kp, local, o, rp, true);
+    fa::KvcacheRaggedParams rg;
+    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, true);
     if (rc) return rc;
     if (kp.b == 0) return FA_OK;
     int64_t avail = local.workspace != nullptr ? local.workspace_bytes : 0;
     char* ws = (char*)local.workspace;
+    if (rg.cu_q != nullptr) {
+        // ragged queries: the append, attention and combine kernels of fa_fwd_kvcache_ragged.hip (no rotary: refused above)
+        kp.n_split = fa::kvcache_split(kp, avail, local.num_splits, rg.total_q);
+        kp.ws_o = kp.n_split > 1 ? (float*)ws : nullptr;
+        rg.kp = kp;
+        return hip_status(fa::launch_fwd_kvcache_ragged(rg, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache (ragged) launch");
+    }
     if (rp.cos != nullptr) {
         // the fused rotary launch takes the place of the append: it writes the cache rows and the image of the rotated q at the head of the
         // workspace; the attention kernels then run as without rotary, with the image as their q and nothing left to append

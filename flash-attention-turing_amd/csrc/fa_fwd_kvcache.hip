@@ -68,6 +68,63 @@ FA_DEV int kvc_len(const KvcacheKernelParams& p, int bidx) {
     return __builtin_amdgcn_readfirstlane(L);
 }
 
+// Ragged query batches (KvcacheRaggedParams): the length of sequence `seq` with its own appended rows sn = cu_kn[seq + 1] - cu_kn[seq] in
+// place of seqlen_new.
+FA_DEV int kvc_len_ragged(const KvcacheRaggedParams& rg, int seq) {
+    const KvcacheKernelParams& p = rg.kp;
+    int L = p.seqlen_cache;
+    if (p.cache_seqlens != nullptr) {
+        const int cs = p.cache_seqlens[seq];
+        const int sn = rg.cu_kn != nullptr ? max(rg.cu_kn[seq + 1] - rg.cu_kn[seq], 0) : 0;
+        L = min((cs > 0 ? cs : 0) + sn, p.seqlen_cache);
+    }
+    return __builtin_amdgcn_readfirstlane(L);
+}
+
+// Tile slot of the compact ragged grid -> (sequence, row tile inside it); false = a slack slot past the last tile (the workgroup exits).
+// varlen_slot_lookup (fa_device.hpp) with tiles of packed rows, ceil(sq_i * h_ratio / kKvcRows), and without its batch limit: the sequences
+// are taken kVarlenMaxBatch at a time (one round of independent loads and a wave prefix sum each), so a batch of up to 512 costs what the
+// prefill lookup costs and a larger one a further round per 512 sequences.  Every wave computes the same answer from the same data.
+FA_DEV bool kvc_slot_lookup(const int32_t* cu, int b, int h_ratio, uint32_t slot, int& seq, int& tile) {
+    const int lane = threadIdx.x & 63;
+    for (int b0 = 0; b0 < b; b0 += kVarlenMaxBatch) {
+        const int b1 = min(b0 + kVarlenMaxBatch, b);
+        const int per = (b1 - b0 + 63) >> 6;                         // sequences per lane, <= kVarlenSeqPerLane
+        const int i0 = b0 + lane * per;
+        int c[kVarlenSeqPerLane + 1];
+#pragma unroll
+        for (int j = 0; j <= kVarlenSeqPerLane; ++j) c[j] = cu[min(i0 + min(j, per), b1)];
+        uint32_t t[kVarlenSeqPerLane], mine = 0;
+#pragma unroll
+        for (int j = 0; j < kVarlenSeqPerLane; ++j) {
+            t[j] = (j < per) ? (uint32_t)((max(c[j + 1] - c[j], 0) * h_ratio + kKvcRows - 1) / kKvcRows) : 0u;
+            mine += t[j];
+        }
+        uint32_t incl = mine;                                        // inclusive prefix over the 64 lanes
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t y = (uint32_t)__shfl_up((int)incl, off);
+            if (lane >= off) incl += y;
+        }
+        uint32_t run = incl - mine;
+        int f_seq = -1, f_tile = 0;
+#pragma unroll
+        for (int j = 0; j < kVarlenSeqPerLane; ++j) {
+            if (slot >= run && slot < run + t[j]) { f_seq = i0 + j; f_tile = (int)(slot - run); }
+            run += t[j];
+        }
+        const uint64_t m = __ballot(f_seq >= 0);
+        if (m != 0) {
+            const int src = __ffsll((long long)m) - 1;
+            seq = __builtin_amdgcn_readlane(f_seq, src);
+            tile = __builtin_amdgcn_readlane(f_tile, src);
+            return true;
+        }
+        slot -= (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);  // the tiles of this round of sequences
+    }
+    return false;
+}
+
 // Eight e4m3 codes (two words, bytes in element order) -> eight T: exact, every finite e4m3 value is a T value; the NaN codes become NaN.
 template <typename T>
 FA_DEV u32x4 widen8(uint32_t w0, uint32_t w1) {
@@ -88,8 +145,13 @@ FA_DEV u32x4 widen8(uint32_t w0, uint32_t w1) {
 // ES = bytes per cache element: 2 = the dtype of q (T), 1 = FP8 e4m3 codes, widened to T in registers (widen8: exact) in front of the same
 // MFMAs; the descales of the (batch, KV head) fold into the softmax scale (K) and the final normalisation (V).  ES is a template
 // parameter: the ES = 2 instantiations are the code they were before the 8-bit cache existed.
-template <typename T, int D, bool CAUSAL, bool PAGED, bool LOCAL = false, int ES = 2>
-FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
+// RAGGED (fa_fwd_kvcache_ragged.hip; `rg` is read only then): the workgroup's (sequence, row tile) comes from a tile slot of a grid sized by the
+// tokens present, the sequence brings its own sq rows at packed rows q0 .. q0 + sq - 1 of q / o and its own appended length, and rows of the
+// LSE and of the partial planes are (head, packed row).  Everything behind those few values is the code below as it is: a tile never spans two
+// sequences, so a sequence of a ragged call goes through exactly the steps of the dense call on it alone.  RAGGED is a template parameter:
+// the dense instantiations are the code they were.
+template <typename T, int D, bool CAUSAL, bool PAGED, bool LOCAL = false, int ES = 2, bool RAGGED = false>
+FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams* rg = nullptr) {
     static_assert(ES == 1 || ES == 2, "cache elements are 16-bit (the dtype of q) or 8-bit (e4m3)");
     constexpr int NC = D / 32;          // 16x16x32 MFMAs per 16 keys of S^T (d chunks)
     constexpr int NO = D / 16;          // O^T blocks of 16 columns
@@ -104,8 +166,10 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, n16 = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int id = blockIdx.x;
+    int n_tiles = p.n_row_tiles;                // RAGGED: the tile slots of a KV head, and `bh` below is the KV head
+    if constexpr (RAGGED) n_tiles = rg->slots;
     int split = id % p.n_split, rest = id / p.n_split;
-    int tile = rest % p.n_row_tiles, bh = rest / p.n_row_tiles;
+    int tile = rest % n_tiles, bh = rest / n_tiles;
     // 8-bit head_dim 64: a (key, head) row is 64 bytes, half a 128-byte line whose other half belongs to the neighbouring KV head.  That
     // head's workgroup is n_split x n_row_tiles launch slots away - for an unsplit launch on the next XCD (workgroup i runs on XCD i % 8),
     // behind another L2, so every line comes from memory twice.  With an even h_k the two heads of a pair are therefore made neighbours in
@@ -117,17 +181,42 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
             const int l = id < (int)(gridDim.x & ~15u) ? ((id & ~15) | ((id & 7) << 1) | ((id >> 3) & 1)) : id;
             int r = l >> 1;
             split = r % p.n_split; r /= p.n_split;
-            tile = r % p.n_row_tiles;
-            bh = 2 * (r / p.n_row_tiles) + (l & 1);
+            tile = r % n_tiles;
+            bh = 2 * (r / n_tiles) + (l & 1);
         }
     }
-    const int bidx = bh / p.h_k, kvh = bh - bidx * p.h_k;
-    const int L = kvc_len(p, bidx);
-    const int rows_tile = p.seqlen_q * p.h_ratio;
+    int bidx = bh / p.h_k, kvh = bh - bidx * p.h_k;
+    int sq = p.seqlen_q;                        // query rows of this sequence
+    int64_t q0 = 0;                             // RAGGED: its first packed row
+    if constexpr (RAGGED) {
+        kvh = bh;
+        if (rg->compact) {
+            const int slot = tile;
+            if (!kvc_slot_lookup(rg->cu_q, p.b, p.h_ratio, (uint32_t)slot, bidx, tile)) return;     // a slack slot: nothing to write
+        } else {
+            bidx = tile / p.n_row_tiles;        // (n_row_tiles = tiles of max_seqlen_q here)
+            tile -= bidx * p.n_row_tiles;
+        }
+        const int c0 = rg->cu_q[bidx];
+        sq = __builtin_amdgcn_readfirstlane(rg->cu_q[bidx + 1] - c0);
+        q0 = __builtin_amdgcn_readfirstlane(c0);
+        if (tile * kKvcRows >= sq * p.h_ratio) return;      // (plain slots of a sequence shorter than max_seqlen_q)
+    }
+    const int L = RAGGED ? kvc_len_ragged(*rg, bidx) : kvc_len(p, bidx);
+    const int rows_tile = sq * p.h_ratio;
     // window bounds of query position tq (LOCAL): lo_t = L - seqlen_q + t - left (any negative value = no lower bound), lim_t = min(L, L -
     // seqlen_q + t + right + 1); written so that nothing overflows for any L and left < seqlen_cache, right < seqlen_q - 1 (host-normalised)
-    auto win_lo = [&](int tq) { return p.window_left >= 0 ? max(L - p.window_left, 0) - (p.seqlen_q - tq) : 0; };
-    auto win_lim = [&](int tq) { return p.window_right >= 0 ? L - max(p.seqlen_q - 1 - tq - p.window_right, 0) : L; };
+    auto win_lo = [&](int tq) { return p.window_left >= 0 ? max(L - p.window_left, 0) - (sq - tq) : 0; };
+    auto win_lim = [&](int tq) { return p.window_right >= 0 ? L - max(sq - 1 - tq - p.window_right, 0) : L; };
+    // row (hq_, t_) of the LSE and of the partial planes; element offset of its row in q / o (st = p.q or p.o)
+    auto row_index = [&](int hq_, int t_) __attribute__((always_inline)) -> int64_t {
+        if constexpr (RAGGED) return (int64_t)hq_ * rg->total_q + q0 + t_;
+        else return ((int64_t)bidx * p.h + hq_) * p.seqlen_q + t_;
+    };
+    auto row_off = [&](const TStride& st, int hq_, int t_) __attribute__((always_inline)) -> int64_t {
+        if constexpr (RAGGED) return (q0 + t_) * st.row + (int64_t)hq_ * st.head;
+        else return (int64_t)bidx * st.batch + (int64_t)t_ * st.row + (int64_t)hq_ * st.head;
+    };
     // LOCAL: w0 = the first key the tile's first row (the smallest lo) sees; the splits start at w0 rounded down to a step and end at the
     // largest lim of the tile (its last row's).  Plain: w0 = 0, the splits cover [0, L).
     const int w0 = LOCAL ? __builtin_amdgcn_readfirstlane(max(win_lo(tile * kKvcRows / p.h_ratio), 0)) : 0;
@@ -148,7 +237,7 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
             const int pr = tile * kKvcRows + tid;
             if (pr < rows_tile) {
                 const int t = pr / p.h_ratio, hq = kvh * p.h_ratio + (pr - t * p.h_ratio);
-                p.ws_lse[(int64_t)split * p.rows_total + ((int64_t)bidx * p.h + hq) * p.seqlen_q + t] = -INFINITY;
+                p.ws_lse[(int64_t)split * p.rows_total + row_index(hq, t)] = -INFINITY;
             }
         }
         return;
@@ -160,12 +249,12 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
     const int t = row_ok ? pr / p.h_ratio : 0;
     const int hq = kvh * p.h_ratio + (row_ok ? pr - t * p.h_ratio : 0);
     int lim = row_ok ? L : 0;
-    if (CAUSAL && row_ok) lim = min(L, L - p.seqlen_q + t + 1);
+    if (CAUSAL && row_ok) lim = min(L, L - sq + t + 1);
     if (LOCAL && row_ok) lim = win_lim(t);
     const int lo = LOCAL ? win_lo(t) : 0;
     u32x4 qf[NC];
     {
-        const char* qrow = (const char*)p.q_ptr + 2 * ((int64_t)bidx * p.q.batch + (int64_t)t * p.q.row + (int64_t)hq * p.q.head);
+        const char* qrow = (const char*)p.q_ptr + 2 * row_off(p.q, hq, t);
         static_for<0, NC>([&](auto cc) {
             constexpr int ci = decltype(cc)::value;
             // ES = 1: a 16-byte K load brings d-elements 64 li + 16 g .. + 15, which feed chunks 2 li and 2 li + 1 eight by eight; the dot
@@ -415,9 +504,9 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
     const bool live = !(lsum == 0.f);
     const float inv = live ? (ES == 1 ? vd / lsum : 1.0f / lsum) : 0.f;
     const float lse = live ? mrow * sc + logf(lsum) : (p.n_split > 1 ? -INFINITY : 0.f);
-    const int64_t R = ((int64_t)bidx * p.h + ohq) * p.seqlen_q + ot;
+    const int64_t R = row_index(ohq, ot);
     if (p.n_split == 1) {
-        char* orow = (char*)p.o_ptr + 2 * ((int64_t)bidx * p.o.batch + (int64_t)ot * p.o.row + (int64_t)ohq * p.o.head + col);
+        char* orow = (char*)p.o_ptr + 2 * (row_off(p.o, ohq, ot) + col);
         uint32_t w[CPT / 2];
         static_for<0, CPT / 2>([&](auto jj) {
             constexpr int j = decltype(jj)::value;
@@ -438,6 +527,8 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p) {
     }
 }
 
+// (fa_fwd_kvcache_ragged.hip includes this file for the body above and kvcache_steps below; the dense kernels and launchers are this file's own)
+#ifndef FA_KVC_RAGGED_TU
 template <typename T, int D, bool CAUSAL>
 __global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_kernel(const KvcacheKernelParams p) {
     kvcache_attn<T, D, CAUSAL, false>(p);
@@ -651,6 +742,7 @@ hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s) {
     }
     return hipGetLastError();
 }
+#endif  // FA_KVC_RAGGED_TU
 
 // 32-key steps the splits of a launch must cover.  A window with a left edge bounds what one workgroup reads from its base: the tile's
 // largest lim minus its smallest lo is at most left + seqlen_q + max(right, 0), plus up to kKvcStep - 1 keys of the base's alignment.
@@ -671,14 +763,25 @@ int64_t kvcache_steps(const KvcacheKernelParams& kp) {
 // launch holds two workgroups per unit (the occupancy of the attention kernel), keeping at least kKvcMinStepsPerSplit steps per split and
 // at most kKvcMaxSplits splits.  An explicit request overrides the rule (never more splits than 32-key steps); a workspace smaller than
 // the choice needs caps it (avail_bytes < 0: unlimited).
-int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_t requested) {
+// A ragged call (total_q >= 0) counts the tile slots of its grid, kvcache_ragged_slots, in place of b x row tiles, and its partial planes
+// have h x total_q rows.
+#ifndef FA_KVC_RAGGED_TU
+int64_t kvcache_ragged_slots(const KvcacheKernelParams& kp, int64_t total_q, int32_t* compact) {
+    const int64_t packed = (total_q * kp.h_ratio + kKvcRows - 1) / kKvcRows + kp.b;
+    const int64_t plain = (int64_t)kp.b * (((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
+    if (compact != nullptr) *compact = packed < plain ? 1 : 0;
+    return packed < plain ? packed : plain;
+}
+
+int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_t requested, int64_t total_q) {
     const int64_t steps = kvcache_steps(kp);
     if (steps <= 1) return 1;
     int64_t n;
     if (requested > 0) {
         n = requested < steps ? requested : steps;
     } else {
-        const int64_t wgs = (int64_t)kp.b * kp.h_k * (((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
+        const int64_t wgs = total_q >= 0 ? kp.h_k * kvcache_ragged_slots(kp, total_q, nullptr)
+                                         : (int64_t)kp.b * kp.h_k * (((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
         const int64_t cus = device_cu_count();
         if (wgs <= 0 || wgs >= cus) return 1;
         n = (2 * cus + wgs - 1) / wgs;
@@ -688,13 +791,13 @@ int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_
         if (n < 1) n = 1;
     }
     if (avail_bytes >= 0)
-        while (n > 1 && kvcache_workspace_bytes(kp, (int32_t)n) > avail_bytes) --n;
+        while (n > 1 && kvcache_workspace_bytes(kp, (int32_t)n, total_q) > avail_bytes) --n;
     return (int32_t)n;
 }
 
-int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split) {
+int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split, int64_t total_q) {
     if (n_split <= 1) return 0;
-    const int64_t rows = (int64_t)kp.b * kp.h * kp.seqlen_q;
+    const int64_t rows = total_q >= 0 ? kp.h * total_q : (int64_t)kp.b * kp.h * kp.seqlen_q;
     const int64_t o_bytes = (int64_t)n_split * rows * kp.d * 4;
     const int64_t l_bytes = ((int64_t)n_split * rows * 4 + 15) / 16 * 16;
     return o_bytes + l_bytes;
@@ -717,5 +820,6 @@ hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s) 
     if (dtype == 0) return kp.d == 64 ? launch_kvcache_t<_Float16, 64>(kp, s) : launch_kvcache_t<_Float16, 128>(kp, s);
     return kp.d == 64 ? launch_kvcache_t<__bf16, 64>(kp, s) : launch_kvcache_t<__bf16, 128>(kp, s);
 }
+#endif  // FA_KVC_RAGGED_TU
 
 }  // namespace fa

@@ -159,9 +159,29 @@ struct KvcacheKernelParams {
 };
 constexpr int kKvcRows = 16;    // packed query rows of a workgroup (one 16x16x32 MFMA tile)
 constexpr int kKvcStep = 32;    // keys of one wave step (the split granularity)
-int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_t requested);   // key splits of a launch (>= 1)
-int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split);
+// total_q >= 0: a ragged call (below) with that many packed query rows - the partial planes have h * total_q rows and the automatic split
+// counts the compact grid's tile slots in place of b x row tiles; -1: the dense call
+int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_t requested, int64_t total_q = -1);   // key splits of a launch (>= 1)
+int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split, int64_t total_q = -1);
 hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t stream);
+
+// Ragged query batches (fa_fwd_kvcache_ragged.hip, fa_kvcache_options_v4): q / o are packed (total_q, h, d), sequence i owns rows cu_q[i] ..
+// cu_q[i + 1] - 1 and is tiled on its own (packed row r = t * h_ratio + j in tiles of kKvcRows from the sequence's first row), k_new / v_new are
+// packed the same way under cu_kn.  In kp: b = sequences, seqlen_q = max_seqlen_q (sizes the launch and the split, never what a row sees),
+// seqlen_new = the largest append allowed, rows_total = h * total_q, lse_ptr (h, total_q); the batch strides of q, o, kn, vn are not read.  A block
+// of its own and not fields of KvcacheKernelParams: the kernarg segment of the dense kernels stays what it was.
+struct KvcacheRaggedParams {
+    KvcacheKernelParams kp;
+    const int32_t* cu_q;        // (b + 1,)
+    const int32_t* cu_kn;       // (b + 1,) or NULL = nothing appended
+    int64_t total_q;            // rows of q / o (>= cu_q[b]; the rows past it are never touched)
+    int64_t total_kn;           // rows of k_new / v_new
+    int32_t slots;              // filled by the launcher: tile slots per KV head of the attention grid
+    int32_t compact;            // filled by the launcher: 1 = slots are looked up in cu_q (kvc_slot_lookup), 0 = slot = sequence x tiles(max_seqlen_q) + tile
+};
+// tile slots per KV head of a ragged launch: min(ceil(total_q * h_ratio / kKvcRows) + b, b * tiles(max_seqlen_q)); *compact says which
+int64_t kvcache_ragged_slots(const KvcacheKernelParams& kp, int64_t total_q, int32_t* compact);
+hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t stream);
 
 // Rotary embedding on a decode call (fa_kvcache_rotary.hip, fa_kvcache_options_v3).  One fused launch takes the place of the append: it
 // rotates k_new into the cache, copies / quantises v_new, and writes the rotated q into `q_image`, a contiguous (b, seqlen_q, h, d) buffer of

@@ -269,12 +269,43 @@ std::vector<at::Tensor> mha_varlen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
 // fa_kvcache_options_v2 with its optional fp32 (batch, h_k) descales (any strides, read on the device); a cache is never copied, so a view
 // that breaks the alignment rule of the 8-bit loads is an error.  rotary_cos / rotary_sin ((seqlen_ro, rotary_dim / 2), q's dtype): rotary
 // embedding of q and of the appended k (fa_kvcache_options_v3), fused into the append launch; the image of the rotated q lives in the
-// workspace, whose size fa_kvcache_workspace_bytes_ex states, so the allocation below serves it as well.
+// workspace, whose size fa_kvcache_workspace_bytes_ex states, so the allocation below serves it as well.  cu_seqlens_q (int32 (b + 1,)): a ragged
+// batch (fa_kvcache_options_v4) - q is packed (total_q, h, d), k_new / v_new (total_new, h_k, d) under cu_seqlens_k_new, max_seqlen_q sizes the
+// launch; out comes back packed and lse as (h, total_q).  The cu_seqlens tensors stay on the device like cache_seqlens.
 std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, c10::optional<at::Tensor> k_new_,
                                         c10::optional<at::Tensor> v_new_, c10::optional<at::Tensor> cache_seqlens_, bool is_causal,
                                         int64_t num_splits, c10::optional<at::Tensor> block_table_, int64_t window_size_left,
                                         int64_t window_size_right, c10::optional<at::Tensor> k_descale_, c10::optional<at::Tensor> v_descale_,
-                                        c10::optional<at::Tensor> rotary_cos_, c10::optional<at::Tensor> rotary_sin_, bool rotary_interleaved) {
+                                        c10::optional<at::Tensor> rotary_cos_, c10::optional<at::Tensor> rotary_sin_, bool rotary_interleaved,
+                                        c10::optional<at::Tensor> cu_seqlens_q_, int64_t max_seqlen_q, c10::optional<at::Tensor> cu_seqlens_k_new_) {
+    const bool ragged = cu_seqlens_q_.has_value();
+    at::Tensor cu_seqlens_q, cu_seqlens_k_new;
+    auto cu_tensor = [&](const at::Tensor& t, const char* name) {
+        TORCH_CHECK(t.device() == q.device(), name, " must be on the same device as q");
+        TORCH_CHECK(t.scalar_type() == torch::kInt32, name, " must be an int32 tensor");
+        TORCH_CHECK(t.dim() == 1 && t.size(0) >= 1 && t.is_contiguous(), name, " must be a contiguous tensor of shape [batch_size + 1]");
+    };
+    if (ragged) {
+        // packed q (total_q, h, d) -> a batch of one with total_q rows: the strides and the output shape below follow, the batch is the cu's
+        TORCH_CHECK(q.dim() == 3, "q must be a packed rank-3 tensor (total_q, nheads, head_dim) with cu_seqlens_q");
+        TORCH_CHECK(max_seqlen_q >= 1 && max_seqlen_q <= INT32_MAX, "max_seqlen_q must be an int32 >= 1 with cu_seqlens_q");
+        TORCH_CHECK(!rotary_cos_.has_value() && !rotary_sin_.has_value(), "rotary_cos / rotary_sin together with cu_seqlens_q are not supported");
+        cu_seqlens_q = *cu_seqlens_q_;
+        cu_tensor(cu_seqlens_q, "cu_seqlens_q");
+        q = q.unsqueeze(0);
+        if (k_new_.has_value() && v_new_.has_value()) {
+            TORCH_CHECK(k_new_->dim() == 3 && v_new_->dim() == 3, "k and v must be packed rank-3 tensors (total_new, nheads_k, head_dim) with cu_seqlens_q");
+            TORCH_CHECK(cu_seqlens_k_new_.has_value(), "packed k and v need cu_seqlens_k_new");
+            cu_seqlens_k_new = *cu_seqlens_k_new_;
+            cu_tensor(cu_seqlens_k_new, "cu_seqlens_k_new");
+            TORCH_CHECK(cu_seqlens_k_new.size(0) == cu_seqlens_q.size(0), "cu_seqlens_k_new must have the shape of cu_seqlens_q");
+            k_new_ = k_new_->unsqueeze(0); v_new_ = v_new_->unsqueeze(0);
+        } else {
+            TORCH_CHECK(!cu_seqlens_k_new_.has_value(), "cu_seqlens_k_new given without k and v");
+        }
+    } else {
+        TORCH_CHECK(!cu_seqlens_k_new_.has_value(), "cu_seqlens_k_new given without cu_seqlens_q");
+    }
     TORCH_CHECK(q.dim() == 4 && k_cache.dim() == 4 && v_cache.dim() == 4, "q, k_cache, v_cache must be rank-4 tensors");
     TORCH_CHECK(q.is_cuda() && k_cache.is_cuda() && v_cache.is_cuda(), "q, k, v must be GPU (HIP) tensors");
     TORCH_CHECK(k_cache.device() == q.device() && v_cache.device() == q.device(), "q, k, v must be on the same device");
@@ -284,7 +315,8 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
                 "k_cache / v_cache must have the dtype of q or be torch.float8_e4m3fn (OCP e4m3; float8_e4m3fnuz, float8_e5m2 and other dtypes are not supported), got ",
                 k_cache.scalar_type());
     TORCH_CHECK(fp8 || (!k_descale_.has_value() && !v_descale_.has_value()), "k_descale / v_descale need a torch.float8_e4m3fn cache");
-    const int64_t batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), head_size = q.size(3);
+    const int64_t total_q = q.size(1);         // (ragged: the packed rows)
+    const int64_t batch_size = ragged ? cu_seqlens_q.size(0) - 1 : q.size(0), seqlen_q = ragged ? max_seqlen_q : q.size(1), num_heads = q.size(2), head_size = q.size(3);
     const int64_t num_heads_k = k_cache.size(2);
     int64_t seqlen_cache = k_cache.size(1);
     TORCH_CHECK(seqlen_q >= 1, "seqlen_q must be >= 1");
@@ -323,14 +355,15 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
         TORCH_CHECK(k_new.dim() == 4 && v_new.dim() == 4, "k and v must be rank-4 tensors");
         check_same_device(q, k_new, "k"); check_same_device(q, v_new, "v");
         TORCH_CHECK(k_new.scalar_type() == q.scalar_type() && v_new.scalar_type() == q.scalar_type(), "k and v must have the dtype of q");
-        TORCH_CHECK(k_new.size(0) == batch_size && k_new.size(2) == num_heads_k && k_new.size(3) == head_size && v_new.sizes() == k_new.sizes(),
-                    "k and v must have shape [batch_size, seqlen_new, num_heads_k, head_dim]");
-        TORCH_CHECK(k_new.size(1) <= seqlen_cache, "seqlen_new must not exceed the cache capacity");
+        TORCH_CHECK((ragged || k_new.size(0) == batch_size) && k_new.size(2) == num_heads_k && k_new.size(3) == head_size && v_new.sizes() == k_new.sizes(),
+                    ragged ? "k and v must have shape [total_new, num_heads_k, head_dim]" : "k and v must have shape [batch_size, seqlen_new, num_heads_k, head_dim]");
+        TORCH_CHECK(ragged || k_new.size(1) <= seqlen_cache, "seqlen_new must not exceed the cache capacity");
         k_new = dense_last(k_new); v_new = dense_last(v_new);
     }
     q = dense_last(q);
     at::Tensor o = torch::empty(q.sizes(), q.options());
-    at::Tensor l = torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(torch::kFloat32));
+    at::Tensor l = ragged ? torch::empty({num_heads, total_q}, q.options().dtype(torch::kFloat32))
+                          : torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(torch::kFloat32));
 
     fa_kvcache_params p;
     FA_PARAMS_INIT(p);
@@ -347,11 +380,16 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
         p.page_block_size = (int32_t)k_cache.size(1); p.num_blocks = (int32_t)k_cache.size(0);
     }
     if (k_new.defined()) {
-        p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr(); p.seqlen_new = (int32_t)k_new.size(1);
+        // (ragged: the largest append the call allows - no sequence can append more rows than there are, or than its capacity holds)
+        p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr(); p.seqlen_new = (int32_t)(ragged ? std::min<int64_t>(k_new.size(1), seqlen_cache) : k_new.size(1));
         p.k_new_stride = strides4(k_new); p.v_new_stride = strides4(v_new);
     }
-    fa_kvcache_options_v3 opt;
+    fa_kvcache_options_v4 opt;
     FA_PARAMS_INIT(opt);
+    if (ragged) {
+        opt.cu_seqlens_q = cu_seqlens_q.data_ptr<int32_t>(); opt.total_q = total_q;
+        if (k_new.defined()) { opt.cu_seqlens_k_new = cu_seqlens_k_new.data_ptr<int32_t>(); opt.total_k_new = k_new.size(1); }
+    }
     opt.is_local = window_size_left != -1 || window_size_right != -1;
     opt.window_size_left = (int32_t)window_size_left; opt.window_size_right = (int32_t)window_size_right;
     at::Tensor k_descale, v_descale;
@@ -385,7 +423,7 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
         opt.seqlen_ro = (int32_t)rotary_cos.size(0); opt.rotary_dim = (int32_t)(2 * rotary_cos.size(1));
         opt.rotary_interleaved = rotary_interleaved ? 1 : 0;
     }
-    const fa_kvcache_options* opts = (opt.is_local || fp8 || rotary_cos.defined()) ? (const fa_kvcache_options*)&opt : nullptr;
+    const fa_kvcache_options* opts = (opt.is_local || fp8 || rotary_cos.defined() || ragged) ? (const fa_kvcache_options*)&opt : nullptr;
     at::Tensor workspace;
     const int64_t ws_bytes = fa_kvcache_workspace_bytes_ex(&p, opts);
     if (ws_bytes < 0) check_status((int)ws_bytes);
@@ -394,6 +432,7 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
         p.workspace = workspace.data_ptr(); p.workspace_bytes = ws_bytes;
     }
     check_status(fa_run_mha_fwd_kvcache_ex(&p, opts, current_stream(q)));
+    if (ragged) return {o.squeeze(0), l};
     return {o, l};
 }
 
@@ -447,11 +486,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("bwd", &mha_bwd, "Backward pass");
     m.def("varlen_fwd", &mha_varlen_fwd, "Varlen forward pass");
     m.def("varlen_bwd", &mha_varlen_bwd, "Varlen backward pass");
-    m.def("fwd_kvcache", &mha_fwd_kvcache, "Decode forward over a KV cache (in-place append of k / v, split-KV attention)", py::arg("q"),
+    // two overloads: the signature as it was (every existing call, positional or keyword, resolves to it), and the one that continues it with the
+    // ragged-batch keywords after rotary_interleaved
+    m.def("fwd_kvcache",
+          [](at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, c10::optional<at::Tensor> k_new, c10::optional<at::Tensor> v_new, c10::optional<at::Tensor> cache_seqlens,
+             bool is_causal, int64_t num_splits, c10::optional<at::Tensor> block_table, int64_t window_size_left, int64_t window_size_right,
+             c10::optional<at::Tensor> k_descale, c10::optional<at::Tensor> v_descale, c10::optional<at::Tensor> rotary_cos, c10::optional<at::Tensor> rotary_sin,
+             bool rotary_interleaved) {
+              return mha_fwd_kvcache(q, k_cache, v_cache, k_new, v_new, cache_seqlens, is_causal, num_splits, block_table, window_size_left, window_size_right, k_descale,
+                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, c10::nullopt, 0, c10::nullopt);
+          },
+          "Decode forward over a KV cache (in-place append of k / v, split-KV attention)", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
           py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("block_table") = py::none(), py::arg("window_size_left") = -1,
           py::arg("window_size_right") = -1, py::kw_only(), py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none(),
           py::arg("rotary_cos") = py::none(), py::arg("rotary_sin") = py::none(), py::arg("rotary_interleaved") = true);
+    m.def("fwd_kvcache", &mha_fwd_kvcache, "The same with a ragged query batch: packed q / k / v under cu_seqlens_q / cu_seqlens_k_new", py::arg("q"),
+          py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
+          py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("block_table") = py::none(), py::arg("window_size_left") = -1,
+          py::arg("window_size_right") = -1, py::kw_only(), py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none(),
+          py::arg("rotary_cos") = py::none(), py::arg("rotary_sin") = py::none(), py::arg("rotary_interleaved") = true,
+          py::arg("cu_seqlens_q") = py::none(), py::arg("max_seqlen_q") = 0, py::arg("cu_seqlens_k_new") = py::none());
     m.def("attn_autograd", &attn_autograd, "differentiable forward (C++ autograd node over fwd / bwd)");
     m.def("attn_varlen_autograd", &attn_varlen_autograd, "differentiable packed forward (C++ autograd node over varlen_fwd / varlen_bwd)");
     m.def("abi_version", []() { return fa_abi_version(); });

@@ -96,6 +96,11 @@ class KvcacheOptionsV3(_Params):
                                             ("rotary_dim", _i32), ("rotary_interleaved", _i32), ("reserved_", _i32)]
 
 
+class KvcacheOptionsV4(_Params):
+    """fa_kvcache_options_v4: fa_kvcache_options_v3 plus the ragged-batch fields (same pointer, told apart by struct_size)"""
+    _fields_ = KvcacheOptionsV3._fields_ + [("cu_seqlens_q", _vp), ("cu_seqlens_k_new", _vp), ("total_q", ctypes.c_int64), ("total_k_new", ctypes.c_int64)]
+
+
 FA_CACHE_FP8_E4M3 = 1
 
 
@@ -135,7 +140,7 @@ def lib():
         L.fa_kvcache_workspace_bytes.restype = ctypes.c_int64
         L.fa_kvcache_num_splits.argtypes = [ctypes.POINTER(KvcacheParams)]
         L.fa_kvcache_num_splits.restype = ctypes.c_int32
-        _op = ctypes.c_void_p                       # fa_kvcache_options, fa_kvcache_options_v2 or fa_kvcache_options_v3 (told apart by struct_size)
+        _op = ctypes.c_void_p                       # fa_kvcache_options, _v2, _v3 or _v4 (told apart by struct_size)
         L.fa_run_mha_fwd_kvcache_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op, _vp]
         L.fa_run_mha_fwd_kvcache_ex.restype = ctypes.c_int
         L.fa_kvcache_workspace_bytes_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op]
@@ -317,9 +322,14 @@ def run_fwd(params, stream=None):
     check(lib().fa_run_mha_fwd(ctypes.byref(params), s))
 
 
-def kvcache_params(q, k_cache, v_cache, o, lse, cache_seqlens=None, k_new=None, v_new=None, causal=False, num_splits=0, block_table=None):
+def kvcache_params(q, k_cache, v_cache, o, lse, cache_seqlens=None, k_new=None, v_new=None, causal=False, num_splits=0, block_table=None, *,
+                   cu_seqlens_q=None, max_seqlen_q=None):
     """fa_kvcache_params for (b, s, h, d) torch tensors with arbitrary batch / row / head strides (caches may be views of larger buffers);
-    with block_table (int32 (b, max_blocks_per_seq)) the caches are page pools (num_blocks, page_block_size, h_k, d)"""
+    with block_table (int32 (b, max_blocks_per_seq)) the caches are page pools (num_blocks, page_block_size, h_k, d).  With cu_seqlens_q
+    (a ragged call; pass the same tensor to kvcache_options) q / o are packed (total_q, h, d), k_new / v_new (total_new, h_k, d), lse is
+    (h, total_q), b = len(cu_seqlens_q) - 1 and seqlen_q = max_seqlen_q."""
+    if cu_seqlens_q is not None:
+        return _kvcache_params_ragged(q, k_cache, v_cache, o, lse, cache_seqlens, k_new, v_new, causal, num_splits, block_table, cu_seqlens_q, max_seqlen_q)
     b, sq, h, d = q.shape
     p = KvcacheParams()
     p.q, p.k_cache, p.v_cache, p.o, p.lse = (t.data_ptr() for t in (q, k_cache, v_cache, o, lse))
@@ -339,13 +349,43 @@ def kvcache_params(q, k_cache, v_cache, o, lse, cache_seqlens=None, k_new=None, 
     return p
 
 
-def kvcache_options(window_size=(-1, -1), cache_dtype=0, k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True):
+def _kvcache_params_ragged(q, k_cache, v_cache, o, lse, cache_seqlens, k_new, v_new, causal, num_splits, block_table, cu_seqlens_q, max_seqlen_q):
+    total_q, h, d = q.shape
+    p = KvcacheParams()
+    p.q, p.k_cache, p.v_cache, p.o, p.lse = (t.data_ptr() for t in (q, k_cache, v_cache, o, lse))
+    p.cache_seqlens = None if cache_seqlens is None else cache_seqlens.data_ptr()
+    p.b, p.seqlen_q, p.seqlen_cache, p.h, p.h_k, p.d = cu_seqlens_q.shape[0] - 1, int(max_seqlen_q), k_cache.shape[1], h, k_cache.shape[2], d
+    if block_table is not None:
+        p.block_table, p.block_table_stride = block_table.data_ptr(), block_table.stride(0)
+        p.page_block_size, p.num_blocks = k_cache.shape[1], k_cache.shape[0]
+        p.seqlen_cache = block_table.shape[1] * k_cache.shape[1]
+    p.dtype, p.is_causal, p.num_splits = dtype_code(q.dtype), int(causal), int(num_splits)
+    for name, t in (("k_cache_stride", k_cache), ("v_cache_stride", v_cache)):
+        setattr(p, name, Strides(t.stride(0), t.stride(1), t.stride(2)))
+    packed = [("q_stride", q), ("o_stride", o)]
+    if k_new is not None:
+        p.k_new, p.v_new, p.seqlen_new = k_new.data_ptr(), v_new.data_ptr(), min(k_new.shape[0], p.seqlen_cache)
+        packed += [("k_new_stride", k_new), ("v_new_stride", v_new)]
+    for name, t in packed:
+        setattr(p, name, Strides(0, t.stride(0), t.stride(1)))         # (the batch stride of a packed tensor is not read)
+    return p
+
+
+def kvcache_options(window_size=(-1, -1), cache_dtype=0, k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, *,
+                    cu_seqlens_q=None, cu_seqlens_k_new=None, total_q=0, total_k_new=0):
     """fa_kvcache_options with a sliding window (left, right); (-1, -1) gives a zeroed struct (no window).  With cache_dtype
     (FA_CACHE_FP8_E4M3) or a descale (float32 (b, h_k) torch tensors, any strides) the struct is fa_kvcache_options_v2; with rotary_cos /
-    rotary_sin ((seqlen_ro, rotary_dim / 2) torch tensors of q's dtype with one row stride) it is fa_kvcache_options_v3."""
+    rotary_sin ((seqlen_ro, rotary_dim / 2) torch tensors of q's dtype with one row stride) it is fa_kvcache_options_v3; with cu_seqlens_q /
+    cu_seqlens_k_new (int32 (b + 1,) torch tensors) and the packed row counts total_q / total_k_new it is fa_kvcache_options_v4."""
+    v4 = cu_seqlens_q is not None or cu_seqlens_k_new is not None
     v3 = rotary_cos is not None or rotary_sin is not None
     v2 = v3 or cache_dtype != 0 or k_descale is not None or v_descale is not None
-    o = KvcacheOptionsV3() if v3 else KvcacheOptionsV2() if v2 else KvcacheOptions()
+    o = KvcacheOptionsV4() if v4 else KvcacheOptionsV3() if v3 else KvcacheOptionsV2() if v2 else KvcacheOptions()
+    if v4:
+        o.cu_seqlens_q = None if cu_seqlens_q is None else cu_seqlens_q.data_ptr()
+        o.cu_seqlens_k_new = None if cu_seqlens_k_new is None else cu_seqlens_k_new.data_ptr()
+        o.total_q, o.total_k_new = int(total_q), int(total_k_new)
+        v2 = True
     left, right = window_size
     if (left, right) != (-1, -1):
         o.is_local, o.window_size_left, o.window_size_right = 1, int(left), int(right)

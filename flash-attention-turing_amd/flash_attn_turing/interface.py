@@ -90,8 +90,10 @@ def _window_pair(window_size):
     return left, right
 
 
-def _check_cache_dtype(q, k_cache, v_cache, k_descale, v_descale):
-    """the cache has q's dtype, or is an FP8 e4m3fn cache with optional float32 (batch, nheads_k) descales on q's device"""
+def _check_cache_dtype(q, k_cache, v_cache, k_descale, v_descale, batch=None):
+    """the cache has q's dtype, or is an FP8 e4m3fn cache with optional float32 (batch, nheads_k) descales on q's device (batch: q.shape[0],
+    or the sequences of a ragged call)"""
+    batch = q.shape[0] if batch is None else batch
     if k_cache.dtype != v_cache.dtype:
         raise ValueError(f"k_cache and v_cache must have the same dtype, got {k_cache.dtype} and {v_cache.dtype}")
     fp8 = k_cache.dtype == torch.float8_e4m3fn
@@ -104,8 +106,8 @@ def _check_cache_dtype(q, k_cache, v_cache, k_descale, v_descale):
             raise ValueError(f"{name} needs a torch.float8_e4m3fn cache (the cache is {k_cache.dtype})")
         if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
             raise ValueError(f"{name} must be a float32 tensor")
-        if k_cache.dim() != 4 or tuple(t.shape) != (q.shape[0], k_cache.shape[2]):
-            raise ValueError(f"{name} must have shape (batch, nheads_k) = ({q.shape[0]}, {k_cache.shape[2] if k_cache.dim() == 4 else '?'}), got {tuple(t.shape)}")
+        if k_cache.dim() != 4 or tuple(t.shape) != (batch, k_cache.shape[2]):
+            raise ValueError(f"{name} must have shape (batch, nheads_k) = ({batch}, {k_cache.shape[2] if k_cache.dim() == 4 else '?'}), got {tuple(t.shape)}")
         if t.device != q.device:
             raise ValueError(f"{name} must be on q's device ({q.device}), got {t.device}")
 
@@ -141,9 +143,54 @@ def _check_rotary(q, k_cache, k, block_table, rotary_cos, rotary_sin, rotary_int
         raise ValueError(f"seqlen_ro ({rotary_cos.shape[0]} rows of rotary_cos / rotary_sin) must be at least the cache capacity ({capacity})")
 
 
+def _check_cu_seqlens(name, t, q, batch=None):
+    """a cu_seqlens tensor: int32, shape (b + 1,), contiguous, on q's device"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+        raise ValueError(f"{name} must be an int32 tensor, got {getattr(t, 'dtype', type(t))}")
+    if t.dim() != 1 or t.shape[0] < 1 or (batch is not None and t.shape[0] != batch + 1):
+        raise ValueError(f"{name} must have shape (batch + 1,){'' if batch is None else f' = ({batch + 1},)'}, got {tuple(t.shape)}")
+    if t.device != q.device:
+        raise ValueError(f"{name} must be on q's device ({q.device}), got {t.device}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def _check_ragged(q, k_cache, k, v, cache_seqlens, block_table, k_descale, v_descale, rotary_cos, rotary_sin, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new):
+    """the arguments of a ragged call (cu_seqlens_q given): packed q / k / v, the batch of every per-sequence tensor, no rotary"""
+    if rotary_cos is not None or rotary_sin is not None:
+        raise ValueError("rotary_cos / rotary_sin together with cu_seqlens_q are not supported (rotary with ragged queries is out of scope)")
+    _check_cu_seqlens("cu_seqlens_q", cu_seqlens_q, q)
+    b = cu_seqlens_q.shape[0] - 1
+    if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, numbers.Integral) or max_seqlen_q < 1 or max_seqlen_q > 2**31 - 1:
+        raise ValueError(f"max_seqlen_q must be a Python int >= 1 with cu_seqlens_q, got {max_seqlen_q!r}")
+    if q.dim() != 3:
+        raise ValueError(f"q must be packed (total_q, nheads, d) with cu_seqlens_q, got shape {tuple(q.shape)}")
+    if k is not None:
+        if k.dim() == 4 or v.dim() == 4:
+            raise ValueError("k and v must be packed (total_new, nheads_k, d) with cu_seqlens_q (a 4-D k belongs to the dense call)")
+        if k.dim() != 3 or v.dim() != 3:
+            raise ValueError(f"k and v must be packed (total_new, nheads_k, d) with cu_seqlens_q, got shapes {tuple(k.shape)} and {tuple(v.shape)}")
+        if cu_seqlens_k_new is None:
+            raise ValueError("packed k and v need cu_seqlens_k_new (it may be the same tensor as cu_seqlens_q)")
+        _check_cu_seqlens("cu_seqlens_k_new", cu_seqlens_k_new, q, b)
+    elif cu_seqlens_k_new is not None:
+        raise ValueError("cu_seqlens_k_new given without k and v")
+    if isinstance(cache_seqlens, torch.Tensor) and tuple(cache_seqlens.shape) != (b,):
+        raise ValueError(f"cache_seqlens must have shape (batch,) = ({b},) (batch = len(cu_seqlens_q) - 1), got {tuple(cache_seqlens.shape)}")
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dim() != 2 or block_table.shape[0] != b:
+            raise ValueError(f"block_table must have shape (batch, max_blocks_per_seq) with batch = len(cu_seqlens_q) - 1 = {b}, got {tuple(getattr(block_table, 'shape', ()))}")
+    elif k_cache.dim() == 4 and k_cache.shape[0] != b:
+        raise ValueError(f"k_cache / v_cache must have batch = len(cu_seqlens_q) - 1 = {b}, got {k_cache.shape[0]}")
+    for name, t in (("k_descale", k_descale), ("v_descale", v_descale)):
+        if isinstance(t, torch.Tensor) and t.dim() == 2 and t.shape[0] != b:
+            raise ValueError(f"{name} must have shape (batch, nheads_k) with batch = len(cu_seqlens_q) - 1 = {b}, got {tuple(t.shape)}")
+    return b
+
+
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, causal=False, num_splits=0, return_softmax_lse=False, *,
                             block_table=None, window_size=(-1, -1), k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None,
-                            rotary_interleaved=True):
+                            rotary_interleaved=True, cu_seqlens_q=None, max_seqlen_q=None, cu_seqlens_k_new=None):
     """Decode attention over a KV cache (upstream flash-attn's ``flash_attn_with_kvcache`` conventions; forward only).
 
     q: (batch, seqlen_q, nheads, d); k_cache, v_cache: (batch, seqlen_cache, nheads_k, d), any batch / row / head strides (used in place).
@@ -210,16 +257,54 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     append launch (no extra launch, no host synchronisation: a captured call replays with the lengths then in memory); the rotated q
     passes through an image in the call's workspace.  Wrong dtype, rank, shape, device, rotary_dim or seqlen_ro, one table without the
     other, tables without k / v, or a rotary_interleaved that is not a bool: ValueError.
+
+    Ragged query batches: cu_seqlens_q (keyword, optional): int32 tensor (batch + 1,) on q's device, contiguous, non-decreasing from 0.  q is
+    then PACKED, (total_q, nheads, d): sequence i owns rows cu_seqlens_q[i] .. cu_seqlens_q[i + 1] - 1 (sq_i rows, 0 allowed), one scheduler
+    step with decoding, speculating and prompt-chunk sequences as ONE call.  batch = len(cu_seqlens_q) - 1 is what cache_seqlens,
+    block_table, a contiguous k_cache and the descales are checked against.  total_q may exceed cu_seqlens_q[-1]: the rows past it are
+    never read and their out / lse entries are never written.  max_seqlen_q (Python int >= 1, required): precondition sq_i <=
+    max_seqlen_q (a device value, not checked); it only sizes the launch and the key split, never which keys a row sees.  k, v (both or
+    neither) are packed as well, (total_new, nheads_k, d), under cu_seqlens_k_new (same rules; it may be the very same tensor as
+    cu_seqlens_q): sequence i appends its sn_i rows at cache rows cache_seqlens[i] .. cache_seqlens[i] + sn_i - 1 - through the table when
+    paged, quantised into an FP8 cache - before attention runs; rows that would land at or past the capacity are dropped.  With L_i =
+    min(max(cache_seqlens[i], 0) + sn_i, capacity), row t of sequence i sees key j < L_i; under ``causal`` only j <= L_i - sq_i + t; under
+    window_size only L_i - sq_i + t - left <= j <= L_i - sq_i + t + right: the formulas above with sq_i in place of seqlen_q.  Returns
+    out (total_q, nheads, d) and, with ``return_softmax_lse``, lse (nheads, total_q) fp32 (entry [head, cu_seqlens_q[i] + t]).  THE
+    CONTRACT: sequence i of a ragged call equals, bit for bit in out, lse and every cache byte, the dense call on that sequence alone
+    (batch 1, seqlen_q = sq_i) - for num_splits=1 always, and for a forced num_splits=n whenever both calls cut the keys at the same
+    places: always without a left-bounded window, and with one for the sequences with sq_i == max_seqlen_q (the split of a windowed call
+    is sized from left + max_seqlen_q + right).  Each sequence is tiled on its own (a 16-row tile never spans two sequences), and the
+    launch is sized by the tokens present, not by batch x max_seqlen_q.  Everything above carries over: both cache layouts and the
+    clamping of table entries, GQA / MQA, fp16 / bf16, head_dim 64 / 128, the FP8 cache and its descales, window_size, causal, num_splits,
+    the NaN rules, dead rows O = 0, LSE = 0, determinism per split count, what is never read, and no host synchronisation - a captured
+    call replays with the cu_seqlens, lengths, tables and descales then in memory (total_q, total_new, batch and max_seqlen_q are baked
+    in).  Not supported, a ValueError: rotary_cos / rotary_sin together with cu_seqlens_q.  Also ValueErrors: cu_seqlens_k_new without
+    k / v or without cu_seqlens_q, packed k without it, a 4-D q or k with cu_seqlens_q, a missing or non-positive max_seqlen_q, a
+    cu_seqlens tensor of the wrong dtype, shape, device or layout, a per-sequence tensor of another batch.
     """
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v)):
         raise RuntimeError("flash_attn_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
     if (k is None) != (v is None):
         raise ValueError("k and v must both be given or both be None")
-    _check_cache_dtype(q, k_cache, v_cache, k_descale, v_descale)
+    if cu_seqlens_q is not None:
+        _check_cu_seqlens("cu_seqlens_q", cu_seqlens_q, q)
+    _check_cache_dtype(q, k_cache, v_cache, k_descale, v_descale, None if cu_seqlens_q is None else cu_seqlens_q.shape[0] - 1)
     left, right = _window_pair(window_size)
-    _check_rotary(q, k_cache, k, block_table, rotary_cos, rotary_sin, rotary_interleaved)
+    if cu_seqlens_q is None:
+        if cu_seqlens_k_new is not None:
+            raise ValueError("cu_seqlens_k_new given without cu_seqlens_q (packed k / v belong to a ragged call)")
+        if max_seqlen_q is not None:
+            raise ValueError("max_seqlen_q given without cu_seqlens_q")
+        _check_rotary(q, k_cache, k, block_table, rotary_cos, rotary_sin, rotary_interleaved)
+        if isinstance(cache_seqlens, int):
+            cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=q.device)
+        out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right,
+                                  k_descale=k_descale, v_descale=v_descale, rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved)
+        return (out, lse) if return_softmax_lse else out
+    b = _check_ragged(q, k_cache, k, v, cache_seqlens, block_table, k_descale, v_descale, rotary_cos, rotary_sin, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new)
     if isinstance(cache_seqlens, int):
-        cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=q.device)
+        cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
     out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right,
-                              k_descale=k_descale, v_descale=v_descale, rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved)
+                              k_descale=k_descale, v_descale=v_descale, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=int(max_seqlen_q),
+                              cu_seqlens_k_new=cu_seqlens_k_new)
     return (out, lse) if return_softmax_lse else out

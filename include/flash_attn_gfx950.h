@@ -315,6 +315,54 @@ typedef struct fa_kvcache_options_v3 {      /* FA_PARAMS_INIT(o); then fa_..._ex
     int32_t reserved_;          /* 0 (pads the struct to a multiple of 8 bytes) */
 } fa_kvcache_options_v3;
 
+/* Ragged query batches (FA_HAS_KVCACHE_RAGGED): fa_kvcache_options_v4 below is fa_kvcache_options_v3 with optional fields appended; the _ex
+ * entry points accept exactly the four sizes (20, 72, 112, 144 bytes), and a v4 struct with a zeroed tail is a v3 call.  FA_ABI_VERSION is
+ * unchanged.  cu_seqlens_q (int32 DEVICE array (b + 1,), non-decreasing from 0; NULL = off, the fields below are not read): q and o are PACKED,
+ * (total_q, h, d) with row and head strides (q_stride.batch / o_stride.batch are ignored), sequence i owns rows cu_seqlens_q[i] ..
+ * cu_seqlens_q[i + 1] - 1 (sq_i rows, 0 allowed), and lse is (h, total_q): entry [hq * total_q + cu_seqlens_q[i] + t].  In fa_kvcache_params,
+ * b is the number of sequences (cache_seqlens, block_table rows, the contiguous cache's batch, the descales), seqlen_q carries max_seqlen_q
+ * (>= 1; precondition sq_i <= max_seqlen_q, a device value and not checked - it sizes the launch and the split, never which keys a row sees);
+ * total_q below is the rows of q / o: it may exceed cu_seqlens_q[b]; the rows past it are never read and their o / lse entries are never written.
+ * k_new / v_new, if given, are packed as well, (total_k_new, h_k, d) under cu_seqlens_k_new (same rules; it may be the same array as
+ * cu_seqlens_q), k_new_stride.batch / v_new_stride.batch are ignored and seqlen_new carries the largest sn_i allowed (<= seqlen_cache).
+ * Sequence i appends its sn_i rows at cache rows max(cache_seqlens[i], 0) .. + sn_i - 1 (through the table when paged, quantised into an 8-bit
+ * cache); rows that would land at or past seqlen_cache are dropped, nothing is written outside the sequence's capacity or the pool.  Then
+ * L_i = min(max(cache_seqlens[i], 0) + sn_i, seqlen_cache) and row t of sequence i sees key j < L_i, under is_causal only j <= L_i - sq_i + t,
+ * under a window only L_i - sq_i + t - left <= j <= L_i - sq_i + t + right: the formulas above with sq_i in place of seqlen_q.  THE CONTRACT:
+ * sequence i of a ragged call equals, bit for bit in o, lse and every cache byte, the dense call on that sequence alone (b = 1, seqlen_q = sq_i)
+ * with the same key split (num_splits = 1 always; a forced num_splits = n cuts the keys at the same places unless a window with a left edge
+ * shortens the span, which the ragged call sizes from max_seqlen_q).  Everything stated above carries over: both cache layouts, the clamping of
+ * table entries, GQA / MQA, the 8-bit cache, windows, rows without a visible key o = 0, lse = 0, the NaN rules, determinism per split count,
+ * no host synchronisation, what is never read.  The automatic split counts the tile slots of the launch in place of b x row tiles:
+ * min(ceil(total_q * (h / h_k) / 16) + b, b * ceil(max_seqlen_q * (h / h_k) / 16)) per KV head; the workspace is that of h * total_q rows.
+ * Errors: cu_seqlens_k_new without cu_seqlens_q or without k_new, k_new in a ragged call without cu_seqlens_k_new: FA_ERR_NULL_POINTER;
+ * total_q < 0, total_k_new < 0, a grid past 2^31 - 1 workgroups, rotary together with cu_seqlens_q (not supported): FA_ERR_BAD_SHAPE; a
+ * cu_seqlens pointer that is not 4-byte aligned: FA_ERR_BAD_STRIDE. */
+#define FA_HAS_KVCACHE_RAGGED 1
+typedef struct fa_kvcache_options_v4 {      /* FA_PARAMS_INIT(o); then fa_..._ex(&p, (const fa_kvcache_options*)&o, ...) */
+    uint32_t struct_size;       /* sizeof(fa_kvcache_options_v4) */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    int32_t is_local;           /* the fields of fa_kvcache_options_v3, same offsets */
+    int32_t window_size_left;
+    int32_t window_size_right;
+    int32_t cache_dtype;
+    const float* k_descale;
+    const float* v_descale;
+    int64_t k_descale_batch_stride, k_descale_head_stride;
+    int64_t v_descale_batch_stride, v_descale_head_stride;
+    const void* rotary_cos;
+    const void* rotary_sin;
+    int64_t rotary_row_stride;
+    int32_t seqlen_ro;
+    int32_t rotary_dim;
+    int32_t rotary_interleaved;
+    int32_t reserved_;
+    const int32_t* cu_seqlens_q;        /* optional: device array (b + 1,); NULL = the dense call (the fields below are not read) */
+    const int32_t* cu_seqlens_k_new;    /* device array (b + 1,) for packed k_new / v_new; NULL without them */
+    int64_t total_q;                    /* packed rows of q / o */
+    int64_t total_k_new;                /* packed rows of k_new / v_new */
+} fa_kvcache_options_v4;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -373,7 +421,7 @@ int fa_run_mha_fwd_kvcache(const fa_kvcache_params* params, void* stream);
 int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* params);
 /* Key splits the launch of these params would use, workspace fields included (NULL / 0 -> 1).  Host-only.  Negative = error code. */
 int32_t fa_kvcache_num_splits(const fa_kvcache_params* params);
-/* The same three with options (fa_kvcache_options / _v2 / _v3 above; NULL = the plain calls).  Their presence is how a caller detects the window.
+/* The same three with options (fa_kvcache_options / _v2 / _v3 / _v4 above; NULL = the plain calls).  Their presence is how a caller detects the window.
  * Options are validated before anything is launched: a bad header is FA_ERR_BAD_ABI, a window size below -1 FA_ERR_BAD_SHAPE, an unknown
  * cache_dtype or a descale without FA_CACHE_FP8_E4M3 FA_ERR_BAD_DTYPE, an 8-bit cache view that breaks the alignment rule FA_ERR_BAD_STRIDE,
  * the rotary fields as listed with fa_kvcache_options_v3.  With rotary, fa_kvcache_num_splits_ex answers for the workspace behind the image

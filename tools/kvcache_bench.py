@@ -25,6 +25,15 @@ pre-rotated q / k - the same work minus the rotation, the floor - timed TWICE (B
 same run stands next to A / B; (C) what a caller does without the feature: torch ops on the GPU (cos / sin rows gathered by cache_seqlens on
 the device, the rotation of q and k in fp32) followed by the plain call.  All four interleaved, medians.  A and C must agree bit for bit.
 
+--ragged measures ragged query batches (cu_seqlens_q) instead, three families of points, one JSON line each (`ragged` names the family):
+"uniform" - the ragged call with every sq_i = 1 against the dense call of the same shape (same bytes, same math), the dense call timed TWICE
+so that the spread of one thing measured twice stands next to ragged / dense; 16-bit and FP8, contiguous and paged; outputs must agree bit for
+bit.  "mixed" - one scheduler step (e.g. 60 x sq 1 + 3 x sq 4 + 1 x sq 256, lengths 1k-32k, paged) as ONE ragged call against what a caller
+does without the feature: one dense call per distinct sq on gathered q rows / cache_seqlens / block_table rows (the gathers run on the device
+and are counted; scattering the outputs back is not).  "chunk" - one sequence of sq = 128 / 512 / 2048 rows over 8k keys, causal, as a ragged
+call against fwd on the same prefix: where the decode tiling (K / V re-read once per 16 packed rows) stops paying.  All arms interleaved,
+medians.
+
 --baseline-library PATH records an interleaved A/B of the plain (no window) call through the C ABI of this build and of the library at
 PATH (e.g. a build of the parent commit), on the same data; the outputs must agree bit for bit.  --length L (repeatable) replaces the
 grid's cache lengths."""
@@ -290,6 +299,139 @@ def run_rotary_point(pt, rotary_dim, interleaved, rounds):
                 torch_rotation_over_rotary=round(ms["c"] / ms["a"], 3), bit_identical=bool(same))
 
 
+def _interleaved(fns, n, rounds):
+    """median ms per call of each arm, the arms taken in turn within every round"""
+    t = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, f in fns.items():
+            t[k].append(time_rotation(f, n, 20))
+    return {k: statistics.median(v) for k, v in t.items()}
+
+
+def _bits_equal(a, b):
+    return a.shape == b.shape and torch.equal(a.view(torch.int16), b.view(torch.int16))
+
+
+def run_ragged_uniform_point(b, h, hk, d, L, dt, fp8, page, rounds):
+    """every sq_i = 1: the ragged call against the dense call of the same shape, the dense call twice"""
+    dev = torch.device("cuda:0")
+    es = 1 if fp8 else 2
+    kv_bytes = 2 * b * L * hk * d * es
+    n = _rotation(kv_bytes, kv_bytes)
+    cdt = torch.float8_e4m3fn if fp8 else dt
+    sets = []
+    for i in range(n):
+        shape = (b * (L // page), page, hk, d) if page else (b, L, hk, d)
+        mk = lambda: (torch.empty(shape, device=dev, dtype=dt).uniform_(-2, 2).to(cdt) if not fp8 else
+                      torch.randint(0, 0x78, shape, device=dev, dtype=torch.uint8).view(cdt))
+        table = torch.randperm(b * (L // page), generator=torch.Generator().manual_seed(i)).view(b, L // page).to(device=dev, dtype=torch.int32) if page else None
+        sets.append((mk(), mk(), table))
+    q = torch.randn(b, 1, h, d, device=dev, dtype=dt)
+    qp = q.view(b, h, d)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    cu = torch.arange(b + 1, dtype=torch.int32, device=dev)
+    kw = dict(k_descale=torch.empty(b, hk, device=dev).uniform_(0.5, 2.0), v_descale=torch.empty(b, hk, device=dev).uniform_(0.5, 2.0)) if fp8 else {}
+    dense = lambda i: F.flash_attn_with_kvcache(q, sets[i][0], sets[i][1], cache_seqlens=cs, block_table=sets[i][2], **kw)
+    ragged = lambda i: F.flash_attn_with_kvcache(qp, sets[i][0], sets[i][1], cache_seqlens=cs, block_table=sets[i][2], cu_seqlens_q=cu, max_seqlen_q=1, **kw)
+    same = _bits_equal(dense(0).view(b, h, d), ragged(0))
+    torch.cuda.synchronize()
+    ms = _interleaved({"dense": dense, "ragged": ragged, "dense2": dense}, n, rounds)
+    p = capi.kvcache_params(q, sets[0][0], sets[0][1], torch.empty_like(q), torch.empty(b, h, 1, device=dev), cache_seqlens=cs, block_table=sets[0][2])
+    opt = capi.kvcache_options(cache_dtype=capi.FA_CACHE_FP8_E4M3) if fp8 else None
+    ws = capi.kvcache_workspace_bytes(p, opt)
+    n_split = max(1, ws and capi.kvcache_num_splits(_with_ws(p, ws), opt))
+    del sets
+    torch.cuda.empty_cache()
+    return dict(ragged="uniform", b=b, h=h, h_k=hk, d=d, L=L, dtype=str(dt).replace("torch.", ""), kv="fp8" if fp8 else "16bit", page_block_size=page or 0,
+                kv_gb=round(kv_bytes / 1e9, 3), caches_rotated=n, n_split_dense=n_split, ms_dense=round(ms["dense"], 5), ms_ragged=round(ms["ragged"], 5),
+                ms_dense_again=round(ms["dense2"], 5), ragged_over_dense=round(ms["ragged"] / ms["dense"], 4), dense_again_over_dense=round(ms["dense2"] / ms["dense"], 4),
+                tbps_ragged=round(kv_bytes / (ms["ragged"] * 1e-3) / 1e12, 3), bit_identical=bool(same))
+
+
+def run_ragged_mixed_point(name, sq, h, hk, d, dt, page, rounds):
+    """one scheduler step as ONE ragged call against one dense call per distinct sq on gathered inputs; paged cache, lengths 1k .. 32k"""
+    dev = torch.device("cuda:0")
+    b, total, cap = len(sq), sum(sq), 32768
+    g = torch.Generator().manual_seed(len(sq) + total)
+    lens = [int(x) for x in torch.randint(1024, cap - max(sq), (b,), generator=g)]
+    lens = [max(L, s) for L, s in zip(lens, sq)]
+    cols = cap // page
+    kv_bytes = 2 * sum(lens) * hk * d * 2
+    n = max(1, min(_rotation(2 * b * cap * hk * d * 2, kv_bytes), 4))
+    sets = []
+    for i in range(n):
+        kp = torch.empty(b * cols, page, hk, d, device=dev, dtype=dt).uniform_(-2, 2)
+        vp = torch.empty(b * cols, page, hk, d, device=dev, dtype=dt).uniform_(-2, 2)
+        table = torch.randperm(b * cols, generator=torch.Generator().manual_seed(i)).view(b, cols).to(device=dev, dtype=torch.int32)
+        sets.append((kp, vp, table))
+    q = torch.randn(total, h, d, device=dev, dtype=dt)
+    cs = torch.tensor(lens, dtype=torch.int32, device=dev)
+    cu_l = [0]
+    for s_ in sq:
+        cu_l.append(cu_l[-1] + s_)
+    cu = torch.tensor(cu_l, dtype=torch.int32, device=dev)
+    groups = []
+    for s_ in sorted(set(sq)):
+        idx = [i for i in range(b) if sq[i] == s_]
+        rows = torch.tensor([[cu_l[i] + t for t in range(s_)] for i in idx], device=dev)
+        groups.append((s_, torch.tensor(idx, device=dev), rows))
+    ragged = lambda i: F.flash_attn_with_kvcache(q, sets[i][0], sets[i][1], cache_seqlens=cs, causal=True, block_table=sets[i][2], cu_seqlens_q=cu, max_seqlen_q=max(sq))
+
+    def loop(i):
+        outs = []
+        for s_, idx, rows in groups:             # the gathers a caller needs today, on the device: q rows, lengths, table rows
+            outs.append(F.flash_attn_with_kvcache(q[rows], sets[i][0], sets[i][1], cache_seqlens=cs[idx], causal=True, block_table=sets[i][2][idx]))
+        return outs
+
+    o_r, o_l = ragged(0), loop(0)
+    same = all(_bits_equal(o_r[rows], o) for (_, _, rows), o in zip(groups, o_l))
+    torch.cuda.synchronize()
+    ms = _interleaved({"loop": loop, "ragged": ragged, "loop2": loop}, n, rounds)
+    del sets
+    torch.cuda.empty_cache()
+    return dict(ragged="mixed", step=name, b=b, total_q=total, distinct_sq=len(groups), h=h, h_k=hk, d=d, dtype=str(dt).replace("torch.", ""), page_block_size=page,
+                kv_gb=round(kv_bytes / 1e9, 3), caches_rotated=n, ms_ragged=round(ms["ragged"], 5), ms_dense_loop=round(ms["loop"], 5), ms_dense_loop_again=round(ms["loop2"], 5),
+                loop_over_ragged=round(ms["loop"] / ms["ragged"], 3), loop_again_over_loop=round(ms["loop2"] / ms["loop"], 4), bit_identical=bool(same))
+
+
+def run_ragged_chunk_point(sq, h, hk, d, dt, rounds, L=8192):
+    """one sequence bringing a chunk of sq rows over L keys, causal: the ragged decode call against fwd on the same prefix"""
+    dev = torch.device("cuda:0")
+    kv_bytes = 2 * L * hk * d * 2
+    n = _rotation(kv_bytes, kv_bytes)
+    caches = [(torch.empty(1, L, hk, d, device=dev, dtype=dt).uniform_(-2, 2), torch.empty(1, L, hk, d, device=dev, dtype=dt).uniform_(-2, 2)) for _ in range(n)]
+    q = torch.randn(sq, h, d, device=dev, dtype=dt)
+    q4 = q[None]
+    cs = torch.tensor([L], dtype=torch.int32, device=dev)
+    cu = torch.tensor([0, sq], dtype=torch.int32, device=dev)
+    ragged = lambda i: F.flash_attn_with_kvcache(q, caches[i][0], caches[i][1], cache_seqlens=cs, causal=True, cu_seqlens_q=cu, max_seqlen_q=sq)
+    fw = lambda i: F.fwd(q4, caches[i][0], caches[i][1], True)
+    err = float((ragged(0).float() - fw(0)[0][0].float()).abs().max())
+    torch.cuda.synchronize()
+    ms = _interleaved({"fwd": fw, "ragged": ragged, "fwd2": fw}, n, rounds)
+    del caches
+    torch.cuda.empty_cache()
+    return dict(ragged="chunk", sq=sq, L=L, h=h, h_k=hk, d=d, dtype=str(dt).replace("torch.", ""), caches_rotated=n, ms_ragged=round(ms["ragged"], 5),
+                ms_fwd=round(ms["fwd"], 5), ms_fwd_again=round(ms["fwd2"], 5), ragged_over_fwd=round(ms["ragged"] / ms["fwd"], 3),
+                fwd_again_over_fwd=round(ms["fwd2"] / ms["fwd"], 4), max_abs_diff=round(err, 5))
+
+
+def run_ragged(quick, rounds):
+    dt = torch.float16
+    for b, L, d in itertools.product((1, 8, 64), (4096, 32768), (64, 128)):
+        if quick and (b, L) not in ((8, 32768), (64, 4096)):
+            continue
+        for fp8, page in ((False, None), (True, None), (False, 256)) if d == 128 else ((False, None),):
+            yield run_ragged_uniform_point(b, 32, 8, d, L, dt, fp8, page, rounds)
+    yield run_ragged_mixed_point("60x1+3x4+1x256", [1] * 60 + [4] * 3 + [256], 32, 8, 128, dt, 256, rounds)
+    yield run_ragged_mixed_point("32x1+32x5", [1, 5] * 32, 32, 8, 128, dt, 256, rounds)
+    if not quick:
+        yield run_ragged_mixed_point("24x1+4x2+3x4+1x8", [1] * 24 + [2] * 4 + [4] * 3 + [8], 32, 8, 128, dt, 256, rounds)
+        yield run_ragged_mixed_point("60x1+3x4+1x256 d64", [1] * 60 + [4] * 3 + [256], 32, 8, 64, dt, 256, rounds)
+    for sq in (128, 512, 2048):
+        yield run_ragged_chunk_point(sq, 32, 8, 128, dt, rounds)
+
+
 def _baseline_lib(path):
     L = ctypes.CDLL(os.path.abspath(path))
     L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
@@ -361,6 +503,8 @@ def main():
     ap.add_argument("--rotary", type=int, nargs="?", const=0, default=None, metavar="DIM",
                     help="the rotary call against the plain call on pre-rotated inputs and against a torch rotation (seqlen_q = 1 points; DIM = rotary_dim, default head_dim)")
     ap.add_argument("--rotary-neox", action="store_true", help="with --rotary: the non-interleaved (GPT-NeoX) pairing instead of the interleaved default")
+    ap.add_argument("--ragged", action="store_true", help="ragged query batches (cu_seqlens_q): uniform batches against the dense call, mixed steps against a loop of dense calls, "
+                                                          "long chunks against fwd")
     a = ap.parse_args()
     base = _baseline_lib(a.baseline_library) if a.baseline_library else None
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
@@ -368,6 +512,10 @@ def main():
     if base is not None:
         print(json.dumps({"baseline_library": base.fa_build_info().decode()}), flush=True)
     with torch.no_grad():
+        if a.ragged and base is None:
+            for line in run_ragged(a.quick, a.rounds):
+                print(json.dumps(line), flush=True)
+            return
         for pt in grid(a.quick, a.length):
             if base is not None:
                 print(json.dumps(run_ab_point(pt, base, a.rounds)), flush=True)
