@@ -141,6 +141,10 @@ FA_DEV u32x4 widen8(uint32_t w0, uint32_t w1) {
     }
 }
 
+// tanh(x) from y = 2 log2(e) x with the exponential and reciprocal instructions (gfx950 has no tanh): 1 - 2 / (2^y + 1).  +-1 at +-inf (2^y
+// overflows to inf, whose reciprocal is 0, or underflows to 0), NaN passes through, absolute error about 1e-7.
+FA_DEV float kvc_tanh2(float y) { return __builtin_fmaf(-2.f, fast_rcp(fast_exp2(y) + 1.f), 1.f); }
+
 // The attention body of both cache layouts; PAGED changes how K / V rows are addressed (load_step), nothing else.
 // ES = bytes per cache element: 2 = the dtype of q (T), 1 = FP8 e4m3 codes, widened to T in registers (widen8: exact) in front of the same
 // MFMAs; the descales of the (batch, KV head) fold into the softmax scale (K) and the final normalisation (V).  ES is a template
@@ -150,8 +154,13 @@ FA_DEV u32x4 widen8(uint32_t w0, uint32_t w1) {
 // LSE and of the partial planes are (head, packed row).  Everything behind those few values is the code below as it is: a tile never spans two
 // sequences, so a sequence of a ragged call goes through exactly the steps of the dense call on it alone.  RAGGED is a template parameter:
 // the dense instantiations are the code they were.
-template <typename T, int D, bool CAUSAL, bool PAGED, bool LOCAL = false, int ES = 2, bool RAGGED = false>
-FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams* rg = nullptr) {
+// SOFTCAP (fa_fwd_kvcache_softcap.hip; `cap_pre` is read only then): every score becomes softcap * tanh(s * softmax_scale / softcap) in front of
+// the mask.  The step keeps t = tanh(s * pre) with pre = cap_pre * k_descale, cap_pre = 2 log2(e) * softmax_scale / softcap from the host, and
+// the host puts the cap where the scale was: p.scale = softcap, p.scale_log2e = softcap * log2(e).  The running max then lives in tanh units
+// and nothing behind the mask knows the difference; the descale of an 8-bit K rides on pre, inside the tanh, not on c.  SOFTCAP is a template
+// parameter: the instantiations without it are the code they were.
+template <typename T, int D, bool CAUSAL, bool PAGED, bool LOCAL = false, int ES = 2, bool RAGGED = false, bool SOFTCAP = false>
+FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams* rg = nullptr, float cap_pre = 0.f) {
     static_assert(ES == 1 || ES == 2, "cache elements are 16-bit (the dtype of q) or 8-bit (e4m3)");
     constexpr int NC = D / 32;          // 16x16x32 MFMAs per 16 keys of S^T (d chunks)
     constexpr int NO = D / 16;          // O^T blocks of 16 columns
@@ -229,8 +238,9 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams
         if (p.k_descale != nullptr) kd = p.k_descale[(int64_t)bidx * p.kds_batch + (int64_t)kvh * p.kds_head];
         if (p.v_descale != nullptr) vd = p.v_descale[(int64_t)bidx * p.vds_batch + (int64_t)kvh * p.vds_head];
     }
-    const float c = ES == 1 ? p.scale_log2e * kd : p.scale_log2e;
-    const float sc = ES == 1 ? p.scale * kd : p.scale;
+    const float c = (ES == 1 && !SOFTCAP) ? p.scale_log2e * kd : p.scale_log2e;
+    const float sc = (ES == 1 && !SOFTCAP) ? p.scale * kd : p.scale;
+    const float pre = ES == 1 ? cap_pre * kd : cap_pre;        // (SOFTCAP only)
 
     if (p.n_split > 1 && k_begin >= k_end) {        // nothing to read in this split: an empty partial (LSE = -inf), O is never looked at
         if (tid < kKvcRows) {
@@ -413,6 +423,7 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams
             static_for<0, 4>([&](auto rr) {
                 constexpr int r = decltype(rr)::value;
                 const int key = key0 + 16 * b + 4 * g + r;
+                if constexpr (SOFTCAP) s[b][r] = kvc_tanh2(s[b][r] * pre);
                 s[b][r] = (key < lim && (!LOCAL || key >= lo)) ? s[b][r] : -INFINITY;
                 mx = fmaxf(mx, s[b][r]);
             });
@@ -690,7 +701,7 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_fp8_kernel(const Kvcach
 }
 
 template <typename T, int D>
-hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s) {
+hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre) {
     const bool paged = kp.block_table != nullptr;
     if (kp.k_new != nullptr && kp.seqlen_new > 0) {
         const int64_t n = (int64_t)kp.b * kp.seqlen_new * kp.h_k * (D / 8);
@@ -698,7 +709,10 @@ hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s) {
         else hipLaunchKernelGGL((fa_kvcache_append_fp8_kernel<T, D, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kp);
     }
     const int64_t grid = (int64_t)kp.b * kp.h_k * kp.n_row_tiles * kp.n_split;
-    if (kp.is_local) {
+    if (cap_pre > 0.f) {        // soft-capped scores: the attention kernels of fa_fwd_kvcache_softcap.hip between this file's append and combine
+        const hipError_t e = launch_kvcache_softcap_attn(kp, cap_pre, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
+        if (e != hipSuccess) return e;
+    } else if (kp.is_local) {
         if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_fp8_local_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
         else hipLaunchKernelGGL((fa_fwd_kvcache_fp8_local_kernel<T, D, false>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
     } else if (paged) {
@@ -717,7 +731,7 @@ hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s) {
 }
 
 template <typename T, int D>
-hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s) {
+hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre) {
     const bool paged = kp.block_table != nullptr;
     if (kp.k_new != nullptr && kp.seqlen_new > 0) {
         const int64_t n = (int64_t)kp.b * kp.seqlen_new * kp.h_k * (D / 8);
@@ -725,7 +739,10 @@ hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s) {
         else hipLaunchKernelGGL((fa_kvcache_append_kernel<D>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kp);
     }
     const int64_t grid = (int64_t)kp.b * kp.h_k * kp.n_row_tiles * kp.n_split;
-    if (kp.is_local) {
+    if (cap_pre > 0.f) {        // soft-capped scores: the attention kernels of fa_fwd_kvcache_softcap.hip between this file's append and combine
+        const hipError_t e = launch_kvcache_softcap_attn(kp, cap_pre, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
+        if (e != hipSuccess) return e;
+    } else if (kp.is_local) {
         if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_local_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
         else hipLaunchKernelGGL((fa_fwd_kvcache_local_kernel<T, D, false>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
     } else if (paged) {
@@ -803,7 +820,7 @@ int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split, 
     return o_bytes + l_bytes;
 }
 
-hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s) {
+hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s, float cap_pre) {
     kp.n_row_tiles = (int32_t)(((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
     kp.rows_total = (int64_t)kp.b * kp.h * kp.seqlen_q;
     const int64_t steps = kvcache_steps(kp);
@@ -814,11 +831,11 @@ hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s) 
         kp.ws_lse = kp.ws_o + (int64_t)kp.n_split * kp.rows_total * kp.d;
     }
     if (kp.cache_fp8) {
-        if (dtype == 0) return kp.d == 64 ? launch_kvcache_fp8_t<_Float16, 64>(kp, s) : launch_kvcache_fp8_t<_Float16, 128>(kp, s);
-        return kp.d == 64 ? launch_kvcache_fp8_t<__bf16, 64>(kp, s) : launch_kvcache_fp8_t<__bf16, 128>(kp, s);
+        if (dtype == 0) return kp.d == 64 ? launch_kvcache_fp8_t<_Float16, 64>(kp, s, cap_pre) : launch_kvcache_fp8_t<_Float16, 128>(kp, s, cap_pre);
+        return kp.d == 64 ? launch_kvcache_fp8_t<__bf16, 64>(kp, s, cap_pre) : launch_kvcache_fp8_t<__bf16, 128>(kp, s, cap_pre);
     }
-    if (dtype == 0) return kp.d == 64 ? launch_kvcache_t<_Float16, 64>(kp, s) : launch_kvcache_t<_Float16, 128>(kp, s);
-    return kp.d == 64 ? launch_kvcache_t<__bf16, 64>(kp, s) : launch_kvcache_t<__bf16, 128>(kp, s);
+    if (dtype == 0) return kp.d == 64 ? launch_kvcache_t<_Float16, 64>(kp, s, cap_pre) : launch_kvcache_t<_Float16, 128>(kp, s, cap_pre);
+    return kp.d == 64 ? launch_kvcache_t<__bf16, 64>(kp, s, cap_pre) : launch_kvcache_t<__bf16, 128>(kp, s, cap_pre);
 }
 #endif  // FA_KVC_RAGGED_TU
 

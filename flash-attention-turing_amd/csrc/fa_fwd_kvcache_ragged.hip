@@ -131,7 +131,7 @@ void launch_ragged_attn(const KvcacheRaggedParams& rp, unsigned grid, hipStream_
 }
 
 template <typename T, int D, int ES>
-hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s) {
+hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre) {
     const KvcacheKernelParams& kp = rp.kp;
     const bool paged = kp.block_table != nullptr;
     if (kp.k_new != nullptr && rp.cu_kn != nullptr && rp.total_kn > 0) {
@@ -144,7 +144,10 @@ hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s)
     }
     if (rp.total_q > 0) {
         const int64_t grid = (int64_t)rp.slots * kp.h_k * kp.n_split;
-        if (paged) launch_ragged_attn<T, D, true, ES>(rp, (unsigned)grid, s);
+        if (cap_pre > 0.f) {    // soft-capped scores: the attention kernels of fa_fwd_kvcache_softcap.hip between this file's append and combine
+            const hipError_t e = launch_kvcache_ragged_softcap_attn(rp, cap_pre, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
+            if (e != hipSuccess) return e;
+        } else if (paged) launch_ragged_attn<T, D, true, ES>(rp, (unsigned)grid, s);
         else launch_ragged_attn<T, D, false, ES>(rp, (unsigned)grid, s);
         if (kp.n_split > 1) {
             const int64_t rows_per_block = kKvcCombineThreads / (D / 8);
@@ -156,15 +159,15 @@ hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s)
 }
 
 template <typename T, int D>
-hipError_t launch_kvcache_ragged_es(const KvcacheRaggedParams& rp, hipStream_t s) {
-    return rp.kp.cache_fp8 ? launch_kvcache_ragged_t<T, D, 1>(rp, s) : launch_kvcache_ragged_t<T, D, 2>(rp, s);
+hipError_t launch_kvcache_ragged_es(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre) {
+    return rp.kp.cache_fp8 ? launch_kvcache_ragged_t<T, D, 1>(rp, s, cap_pre) : launch_kvcache_ragged_t<T, D, 2>(rp, s, cap_pre);
 }
 
 }  // namespace
 
 // kp.seqlen_q = max_seqlen_q sizes the split exactly as the dense launcher does (kvcache_steps), so a forced split cuts the keys where the dense
 // call with seqlen_q = max_seqlen_q cuts them.
-hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t s) {
+hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t s, float cap_pre) {
     KvcacheKernelParams& kp = rp.kp;
     kp.n_row_tiles = (int32_t)(((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
     kp.rows_total = (int64_t)kp.h * rp.total_q;
@@ -174,8 +177,8 @@ hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStrea
     kp.split_keys = (int32_t)(((steps + kp.n_split - 1) / kp.n_split) * kKvcStep);
     if (kp.split_keys <= 0) kp.split_keys = kKvcStep;
     if (kp.n_split > 1) kp.ws_lse = kp.ws_o + (int64_t)kp.n_split * kp.rows_total * kp.d;
-    if (dtype == 0) return kp.d == 64 ? launch_kvcache_ragged_es<_Float16, 64>(rp, s) : launch_kvcache_ragged_es<_Float16, 128>(rp, s);
-    return kp.d == 64 ? launch_kvcache_ragged_es<__bf16, 64>(rp, s) : launch_kvcache_ragged_es<__bf16, 128>(rp, s);
+    if (dtype == 0) return kp.d == 64 ? launch_kvcache_ragged_es<_Float16, 64>(rp, s, cap_pre) : launch_kvcache_ragged_es<_Float16, 128>(rp, s, cap_pre);
+    return kp.d == 64 ? launch_kvcache_ragged_es<__bf16, 64>(rp, s, cap_pre) : launch_kvcache_ragged_es<__bf16, 128>(rp, s, cap_pre);
 }
 
 }  // namespace fa

@@ -163,7 +163,8 @@ constexpr int kKvcStep = 32;    // keys of one wave step (the split granularity)
 // counts the compact grid's tile slots in place of b x row tiles; -1: the dense call
 int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_t requested, int64_t total_q = -1);   // key splits of a launch (>= 1)
 int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split, int64_t total_q = -1);
-hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t stream);
+// cap_pre > 0: soft-capped scores (below) - the attention launch goes to fa_fwd_kvcache_softcap.hip, the append and the combine stay
+hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t stream, float cap_pre = 0.f);
 
 // Ragged query batches (fa_fwd_kvcache_ragged.hip, fa_kvcache_options_v4): q / o are packed (total_q, h, d), sequence i owns rows cu_q[i] ..
 // cu_q[i + 1] - 1 and is tiled on its own (packed row r = t * h_ratio + j in tiles of kKvcRows from the sequence's first row), k_new / v_new are
@@ -181,7 +182,24 @@ struct KvcacheRaggedParams {
 };
 // tile slots per KV head of a ragged launch: min(ceil(total_q * h_ratio / kKvcRows) + b, b * tiles(max_seqlen_q)); *compact says which
 int64_t kvcache_ragged_slots(const KvcacheKernelParams& kp, int64_t total_q, int32_t* compact);
-hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t stream);
+hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t stream, float cap_pre = 0.f);
+
+// Soft-capped scores (fa_fwd_kvcache_softcap.hip, fa_kvcache_options_v5.softcap > 0): score = softcap * tanh(q . k * softmax_scale / softcap).
+// The kernels are kvcache_attn with SOFTCAP = true and read kp.scale = softcap, kp.scale_log2e = softcap * log2(e) (the host puts the cap where
+// the scale was) and pre = 2 log2(e) * softmax_scale / softcap, which travels in a block of its own and not in KvcacheKernelParams: the kernarg
+// segment of every other kernel stays what it was.  One sliding-window instantiation serves plain, causal and windowed calls: the launchers
+// below state the plain call as the window (-1, -1) and the causal one as (-1, 0), which is exactly its limit.  They launch the attention
+// kernel alone, on the grid the dense / ragged launcher computed; the append in front and the combine behind are the unchanged ones.
+struct KvcacheSoftcapParams {
+    KvcacheKernelParams kp;
+    float pre;
+};
+struct KvcacheRaggedSoftcapParams {
+    KvcacheRaggedParams rp;
+    float pre;
+};
+hipError_t launch_kvcache_softcap_attn(const KvcacheKernelParams& kp, float pre, int dtype, unsigned grid, hipStream_t stream);
+hipError_t launch_kvcache_ragged_softcap_attn(const KvcacheRaggedParams& rp, float pre, int dtype, unsigned grid, hipStream_t stream);
 
 // Rotary embedding on a decode call (fa_kvcache_rotary.hip, fa_kvcache_options_v3).  One fused launch takes the place of the append: it
 // rotates k_new into the cache, copies / quantises v_new, and writes the rotated q into `q_image`, a contiguous (b, seqlen_q, h, d) buffer of

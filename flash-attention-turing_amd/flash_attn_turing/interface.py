@@ -5,6 +5,7 @@ The reference ships only the four raw functions; its README (README.md:28-48) do
 ``flash_attn_func`` here accepts both that legacy call (the four ints are validated against
 the tensor shapes and otherwise ignored) and the modern ``flash_attn_func(q, k, v, causal=False)``.
 """
+import math
 import numbers
 
 import torch
@@ -143,6 +144,25 @@ def _check_rotary(q, k_cache, k, block_table, rotary_cos, rotary_sin, rotary_int
         raise ValueError(f"seqlen_ro ({rotary_cos.shape[0]} rows of rotary_cos / rotary_sin) must be at least the cache capacity ({capacity})")
 
 
+def _check_scale_and_cap(softmax_scale, softcap):
+    """softmax_scale: None or a real number that is finite and > 0 as an fp32 value; softcap: a real number that is finite and >= 0 as an fp32
+    value (0 = off); bools are not numbers here.  Returns (softmax_scale or None, softcap) as Python floats."""
+    if softmax_scale is not None:
+        if isinstance(softmax_scale, bool) or not isinstance(softmax_scale, numbers.Real):
+            raise ValueError(f"softmax_scale must be None or a real number > 0, got {softmax_scale!r}")
+        softmax_scale = float(softmax_scale)
+        s32 = torch.tensor(softmax_scale, dtype=torch.float32).item()
+        if not (math.isfinite(s32) and s32 > 0):
+            raise ValueError(f"softmax_scale must be finite and > 0 (as an fp32 value), got {softmax_scale!r}")
+    if isinstance(softcap, bool) or not isinstance(softcap, numbers.Real):
+        raise ValueError(f"softcap must be a real number >= 0 (0.0 = no cap), got {softcap!r}")
+    softcap = float(softcap)
+    c32 = torch.tensor(softcap, dtype=torch.float32).item()
+    if not (math.isfinite(c32) and c32 >= 0) or (softcap != 0 and c32 == 0):
+        raise ValueError(f"softcap must be finite and >= 0 (as an fp32 value; 0.0 = no cap), got {softcap!r}")
+    return softmax_scale, softcap
+
+
 def _check_cu_seqlens(name, t, q, batch=None):
     """a cu_seqlens tensor: int32, shape (b + 1,), contiguous, on q's device"""
     if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
@@ -190,14 +210,15 @@ def _check_ragged(q, k_cache, k, v, cache_seqlens, block_table, k_descale, v_des
 
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, causal=False, num_splits=0, return_softmax_lse=False, *,
                             block_table=None, window_size=(-1, -1), k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None,
-                            rotary_interleaved=True, cu_seqlens_q=None, max_seqlen_q=None, cu_seqlens_k_new=None):
+                            rotary_interleaved=True, cu_seqlens_q=None, max_seqlen_q=None, cu_seqlens_k_new=None, softmax_scale=None,
+                            softcap=0.0):
     """Decode attention over a KV cache (upstream flash-attn's ``flash_attn_with_kvcache`` conventions; forward only).
 
     q: (batch, seqlen_q, nheads, d); k_cache, v_cache: (batch, seqlen_cache, nheads_k, d), any batch / row / head strides (used in place).
     cache_seqlens: int32 tensor (batch,) on q's device, a Python int (broadcast), or None (every sequence is seqlen_cache long).
     k, v (optional, both or neither): (batch, seqlen_new, nheads_k, d), written INTO the caches at rows cache_seqlens[i] ..
     cache_seqlens[i] + seqlen_new - 1 before attention runs over the first cache_seqlens[i] + seqlen_new keys; cache_seqlens is not
-    updated (the caller advances it).  causal masks key j for query t when j > L_i - seqlen_q + t.  Scale is 1/sqrt(d).
+    updated (the caller advances it).  causal masks key j for query t when j > L_i - seqlen_q + t.  Scale is 1/sqrt(d) unless softmax_scale says otherwise.
     num_splits: 0 = chosen by the library, > 0 forces the key split.  Returns out (like q), and lse (batch, nheads, seqlen_q) fp32 if
     ``return_softmax_lse``.  Precondition: cache_seqlens[i] + seqlen_new <= seqlen_cache.
     Non-finite inputs follow fp32 math over the valid prefix, for every num_splits: a NaN query row, or a NaN / +inf score from a visible K row,
@@ -281,6 +302,23 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     in).  Not supported, a ValueError: rotary_cos / rotary_sin together with cu_seqlens_q.  Also ValueErrors: cu_seqlens_k_new without
     k / v or without cu_seqlens_q, packed k without it, a 4-D q or k with cu_seqlens_q, a missing or non-positive max_seqlen_q, a
     cu_seqlens tensor of the wrong dtype, shape, device or layout, a per-sequence tensor of another batch.
+
+    Scale and soft cap: softmax_scale (keyword, optional): None = 1/sqrt(d), computed as today; otherwise a Python real number, finite and
+    > 0, rounded once to fp32: the scores are (q . k) * softmax_scale.  None and the fp32 default passed explicitly give the same bits (the
+    value is the same and so are the kernels).  softcap (keyword, float, default 0.0 = off, upstream's convention): a finite value > 0 makes
+    the scores ``softcap * tanh((q . k) * softmax_scale / softcap)`` (Gemma 2's logit soft-capping).  The mask - length, causal, window -
+    comes after the cap, the softmax runs over the capped scores, and lse is their natural-log logsumexp.  tanh is evaluated as
+    ``1 - 2 / (exp(2 x) + 1)`` with the hardware exponential and reciprocal: absolute error about 1e-7, times softcap in the score.  Both are
+    host scalars baked into the call like the window: no synchronisation, and a captured call replays with them.  Everything above carries
+    over for both: block_table and the clamping of table entries, GQA / MQA, fp16 / bf16, head_dim 64 / 128, window_size, causal,
+    num_splits (the split count and the workspace do not depend on the two values), the FP8 cache (k_descale multiplies the score inside
+    the tanh, v_descale stays in the final normalisation), rotary (a launch of its own in front of attention), cu_seqlens_q (sequence i of
+    a soft-capped ragged call equals the soft-capped dense call on it alone, bit for bit, under the split rule above), paged == contiguous
+    bit for bit, dead rows O = 0, LSE = 0, determinism per split count, what is never read.  Non-finite inputs: with softcap == 0 the rules
+    above hold under any softmax_scale.  With softcap > 0 the contract is fp32 math on the CAPPED scores: a NaN score still makes the row's
+    O and LSE NaN, but a raw score of +inf caps to +softcap - it is finite and the row is no longer NaN - and a raw score of -inf caps to
+    -softcap - the key is no longer dropped.  A bool, 0, a negative value, NaN, inf or a non-number as softmax_scale, and a bool, a
+    negative value, NaN, inf or a non-number as softcap: ValueError.
     """
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v)):
         raise RuntimeError("flash_attn_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
@@ -290,6 +328,9 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
         _check_cu_seqlens("cu_seqlens_q", cu_seqlens_q, q)
     _check_cache_dtype(q, k_cache, v_cache, k_descale, v_descale, None if cu_seqlens_q is None else cu_seqlens_q.shape[0] - 1)
     left, right = _window_pair(window_size)
+    softmax_scale, softcap = _check_scale_and_cap(softmax_scale, softcap)
+    # (the third overload of the extension only when one of the two is given: every other call resolves as it always did)
+    extra = dict(softmax_scale=softmax_scale, softcap=softcap) if softmax_scale is not None or softcap != 0.0 else {}
     if cu_seqlens_q is None:
         if cu_seqlens_k_new is not None:
             raise ValueError("cu_seqlens_k_new given without cu_seqlens_q (packed k / v belong to a ragged call)")
@@ -299,12 +340,12 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
         if isinstance(cache_seqlens, int):
             cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=q.device)
         out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right,
-                                  k_descale=k_descale, v_descale=v_descale, rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved)
+                                  k_descale=k_descale, v_descale=v_descale, rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved, **extra)
         return (out, lse) if return_softmax_lse else out
     b = _check_ragged(q, k_cache, k, v, cache_seqlens, block_table, k_descale, v_descale, rotary_cos, rotary_sin, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new)
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
     out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right,
                               k_descale=k_descale, v_descale=v_descale, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=int(max_seqlen_q),
-                              cu_seqlens_k_new=cu_seqlens_k_new)
+                              cu_seqlens_k_new=cu_seqlens_k_new, **extra)
     return (out, lse) if return_softmax_lse else out

@@ -213,8 +213,8 @@ typedef struct fa_kvcache_params {
 } fa_kvcache_params;
 
 /* Options of a decode call that fa_kvcache_params does not carry (its layout is fixed; the _ex entry points below take both).  Same ABI 4
- * header rule (FA_PARAMS_INIT): a zeroed struct means today's behaviour, and options appended later (decode softmax scale, softcap) will be
- * optional fields after these (the 8-bit cache and the rotary embedding on append arrived that way, below).  A NULL options pointer is the same as a zeroed struct.
+ * header rule (FA_PARAMS_INIT): a zeroed struct means the plain call, and every later option arrived as optional fields appended after these
+ * (the 8-bit cache, the rotary embedding on append, ragged query batches, and the softmax scale and softcap of fa_kvcache_options_v5, below).  A NULL options pointer is the same as a zeroed struct.
  * Sliding window (upstream flash-attn's window_size; is_local = 0: no window, the two sizes are not read).  Key j of sequence i (valid
  * length L_i as above) is visible to query t when
  *     L_i - seqlen_q + t - window_size_left <= j <= L_i - seqlen_q + t + window_size_right,
@@ -363,6 +363,57 @@ typedef struct fa_kvcache_options_v4 {      /* FA_PARAMS_INIT(o); then fa_..._ex
     int64_t total_k_new;                /* packed rows of k_new / v_new */
 } fa_kvcache_options_v4;
 
+/* Softmax scale and soft-capped scores (FA_HAS_KVCACHE_SOFTCAP; upstream flash-attn's softmax_scale / softcap): fa_kvcache_options_v5 below is
+ * fa_kvcache_options_v4 with optional fields appended; the _ex entry points accept exactly the five sizes (20, 72, 112, 144, 168 bytes), and a
+ * v5 struct with a zeroed tail is a v4 call: same kernels, split, workspace and bits.  FA_ABI_VERSION is unchanged.
+ *   softmax_scale: 0 = the default 1 / sqrt(d), computed as 1.0f / sqrtf((float)d); otherwise the scores are (q . k) * softmax_scale.  A value
+ *   equal to the default gives the default's bits (the value is the same and so are the kernels).
+ *   softcap: 0 = off.  > 0: score = softcap * tanh((q . k) * softmax_scale / softcap); the mask (length, causal, window) comes after the cap, the
+ *   softmax runs over the capped scores and lse is their natural-log logsumexp.  tanh is built from the exponential and reciprocal
+ *   instructions, 1 - 2 / (exp(2 x) + 1): absolute error about 1e-7, times softcap in the score.
+ * A negative, NaN or infinite value of either is FA_ERR_BAD_SHAPE (fa_last_error names the field), as is a pair whose ratio softmax_scale /
+ * softcap is zero or infinite in fp32; a non-zero `reserved` is FA_ERR_BAD_ABI (a
+ * newer caller's field this library does not know).  Errors of fa_kvcache_params and of the older option fields come first.  Both are host
+ * values baked into the call like the window: no synchronisation, and a captured call replays with them.  Everything stated above carries over
+ * for both: contiguous and paged layout and the clamping of table entries, GQA / MQA, fp16 / bf16, head_dim 64 / 128, windows, causal,
+ * num_splits (the split count and the workspace do not depend on the two values), the 8-bit cache (k_descale multiplies the score inside the
+ * tanh, v_descale stays in the final normalisation), rotary (a launch of its own in front of attention), ragged batches (sequence i of a
+ * soft-capped ragged call equals the soft-capped dense call on it alone, bit for bit, under the split rule above), rows without a visible key
+ * o = 0, lse = 0, determinism per split count, what is never read.  Paged and contiguous soft-capped calls over the same logical cache give the
+ * same bits.  Plain, causal and windowed soft-capped calls are all served by the window kernels (an unbounded window is the plain call).
+ * Non-finite inputs: with softcap = 0 the rules above hold under any softmax_scale.  With softcap > 0 the contract is fp32 math on the CAPPED
+ * scores, which differs in two places: a NaN score still makes the row's o and lse NaN, but a raw score of +inf caps to +softcap - finite, the
+ * row is no longer NaN - and a raw score of -inf caps to -softcap - the key is no longer dropped.
+ * sizeof is 168, not 152: the sizes 145, 148, 152, 160, 176 and 256 are pinned as FA_ERR_BAD_ABI by callers' tests of the v4 library, and 168 is
+ * the smallest multiple of 8 that clears them; the two reserved words are the room that leaves. */
+#define FA_HAS_KVCACHE_SOFTCAP 1
+typedef struct fa_kvcache_options_v5 {      /* FA_PARAMS_INIT(o); then fa_..._ex(&p, (const fa_kvcache_options*)&o, ...) */
+    uint32_t struct_size;       /* sizeof(fa_kvcache_options_v5) */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    int32_t is_local;           /* the fields of fa_kvcache_options_v4, same offsets */
+    int32_t window_size_left;
+    int32_t window_size_right;
+    int32_t cache_dtype;
+    const float* k_descale;
+    const float* v_descale;
+    int64_t k_descale_batch_stride, k_descale_head_stride;
+    int64_t v_descale_batch_stride, v_descale_head_stride;
+    const void* rotary_cos;
+    const void* rotary_sin;
+    int64_t rotary_row_stride;
+    int32_t seqlen_ro;
+    int32_t rotary_dim;
+    int32_t rotary_interleaved;
+    int32_t reserved_;
+    const int32_t* cu_seqlens_q;
+    const int32_t* cu_seqlens_k_new;
+    int64_t total_q;
+    int64_t total_k_new;
+    float softmax_scale;        /* optional: 0 = 1 / sqrt(d); else finite and > 0 */
+    float softcap;              /* optional: 0 = off; else finite and > 0 */
+    int64_t reserved[2];        /* 0 */
+} fa_kvcache_options_v5;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -421,10 +472,10 @@ int fa_run_mha_fwd_kvcache(const fa_kvcache_params* params, void* stream);
 int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* params);
 /* Key splits the launch of these params would use, workspace fields included (NULL / 0 -> 1).  Host-only.  Negative = error code. */
 int32_t fa_kvcache_num_splits(const fa_kvcache_params* params);
-/* The same three with options (fa_kvcache_options / _v2 / _v3 / _v4 above; NULL = the plain calls).  Their presence is how a caller detects the window.
+/* The same three with options (fa_kvcache_options / _v2 / _v3 / _v4 / _v5 above; NULL = the plain calls).  Their presence is how a caller detects the window.
  * Options are validated before anything is launched: a bad header is FA_ERR_BAD_ABI, a window size below -1 FA_ERR_BAD_SHAPE, an unknown
  * cache_dtype or a descale without FA_CACHE_FP8_E4M3 FA_ERR_BAD_DTYPE, an 8-bit cache view that breaks the alignment rule FA_ERR_BAD_STRIDE,
- * the rotary fields as listed with fa_kvcache_options_v3.  With rotary, fa_kvcache_num_splits_ex answers for the workspace behind the image
+ * the rotary fields as listed with fa_kvcache_options_v3, the ragged fields with _v4, softmax_scale / softcap with _v5.  With rotary, fa_kvcache_num_splits_ex answers for the workspace behind the image
  * (a workspace that cannot hold the image is FA_ERR_BAD_SHAPE there as in the launch). */
 int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* params, const fa_kvcache_options* options, void* stream);
 int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);

@@ -34,6 +34,11 @@ and are counted; scattering the outputs back is not).  "chunk" - one sequence of
 call against fwd on the same prefix: where the decode tiling (K / V re-read once per 16 packed rows) stops paying.  All arms interleaved,
 medians.
 
+--softcap CAP measures soft-capped scores instead (with --kv-dtype fp8 over the 8-bit cache; --softmax-scale S for a scale other than
+1 / sqrt(d), which selects no other code): per grid point, the soft-capped call (A) against the same call without the cap (B), B timed TWICE
+(B, B2) so that the spread of one thing measured twice in the same run stands next to A / B; interleaved, medians.  TB/s over the bytes
+both read.
+
 --baseline-library PATH records an interleaved A/B of the plain (no window) call through the C ABI of this build and of the library at
 PATH (e.g. a build of the parent commit), on the same data; the outputs must agree bit for bit.  --length L (repeatable) replaces the
 grid's cache lengths."""
@@ -244,6 +249,44 @@ def run_fp8_point(pt, rounds):
                 ms_fp8=round(ms_8, 5), ms_16bit=round(ms_16, 5), bytes_fp8=kv8 + other + 2 * b * hk * 4, bytes_16bit=kv16 + other,
                 tbps_fp8=round(tb8, 3), tbps_16bit=round(tb16, 3), frac_of_6p3_fp8=round(tb8 * 1e12 / HBM_ACHIEVABLE, 3),
                 frac_of_6p3_16bit=round(tb16 * 1e12 / HBM_ACHIEVABLE, 3), n_split=n_split, fp8_over_16bit=round(ms_8 / ms_16, 3))
+
+
+def run_softcap_point(pt, softcap, scale, fp8, rounds):
+    """(A) the soft-capped call, (B, B2) the same call without the cap, twice; interleaved"""
+    dev = torch.device("cuda:0")
+    b, h, hk, d, L, sq, dt = pt["b"], pt["h"], pt["h_k"], pt["d"], pt["L"], pt["seqlen_q"], pt["dtype"]
+    es = 1 if fp8 else 2
+    kv_bytes = 2 * b * L * hk * d * es
+    n = _rotation(kv_bytes, kv_bytes)
+    cdt = torch.float8_e4m3fn if fp8 else dt
+
+    def mk():
+        c = torch.empty(b, L, hk, d, device=dev, dtype=cdt)
+        for i in range(b):                                    # (per batch entry: bounds the temporaries of the conversion)
+            c[i] = torch.empty(L, hk, d, device=dev, dtype=dt).uniform_(-2, 2).to(cdt)
+        return c
+
+    caches = [(mk(), mk()) for _ in range(n)]
+    q = torch.randn(b, sq, h, d, device=dev, dtype=dt)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    kw = dict(k_descale=torch.empty(b, hk, device=dev).uniform_(0.5, 2.0), v_descale=torch.empty(b, hk, device=dev).uniform_(0.5, 2.0)) if fp8 else {}
+    capped = lambda i: F.flash_attn_with_kvcache(q, caches[i][0], caches[i][1], cache_seqlens=cs, softmax_scale=scale, softcap=softcap, **kw)
+    plain = lambda i: F.flash_attn_with_kvcache(q, caches[i][0], caches[i][1], cache_seqlens=cs, softmax_scale=scale, **kw)
+    diff = float((capped(0).float() - plain(0).float()).abs().max())
+    torch.cuda.synchronize()
+    ms = _interleaved({"plain": plain, "capped": capped, "plain2": plain}, n, rounds)
+    p = capi.kvcache_params(q, caches[0][0], caches[0][1], torch.empty_like(q), torch.empty(b, h, sq, device=dev), cache_seqlens=cs)
+    opt = capi.kvcache_options(cache_dtype=capi.FA_CACHE_FP8_E4M3 if fp8 else 0, softcap=softcap, softmax_scale=scale)
+    ws = capi.kvcache_workspace_bytes(p, opt)
+    n_split = max(1, ws and capi.kvcache_num_splits(_with_ws(p, ws), opt))
+    rows = b * h * sq
+    moved = kv_bytes + 2 * rows * d * 2 + rows * 4 + (2 * n_split * rows * (d + 1) * 4 if n_split > 1 else 0)
+    del caches
+    torch.cuda.empty_cache()
+    return dict(softcap=softcap, softmax_scale=scale, b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=sq, dtype=str(dt).replace("torch.", ""), kv="fp8" if fp8 else "16bit",
+                kv_gb=round(kv_bytes / 1e9, 3), caches_rotated=n, n_split=n_split, ms_capped=round(ms["capped"], 5), ms_plain=round(ms["plain"], 5),
+                ms_plain_again=round(ms["plain2"], 5), capped_over_plain=round(ms["capped"] / ms["plain"], 4), plain_again_over_plain=round(ms["plain2"] / ms["plain"], 4),
+                tbps_capped=round(moved / (ms["capped"] * 1e-3) / 1e12, 3), tbps_plain=round(moved / (ms["plain"] * 1e-3) / 1e12, 3), max_abs_diff_to_plain=round(diff, 5))
 
 
 def torch_rotate(x, cos, sin, pos, interleaved):
@@ -505,6 +548,9 @@ def main():
     ap.add_argument("--rotary-neox", action="store_true", help="with --rotary: the non-interleaved (GPT-NeoX) pairing instead of the interleaved default")
     ap.add_argument("--ragged", action="store_true", help="ragged query batches (cu_seqlens_q): uniform batches against the dense call, mixed steps against a loop of dense calls, "
                                                           "long chunks against fwd")
+    ap.add_argument("--softcap", type=float, default=None, metavar="CAP", help="the soft-capped call against the same call without the cap (timed twice); with --kv-dtype fp8 "
+                                                                               "over the 8-bit cache")
+    ap.add_argument("--softmax-scale", type=float, default=None, metavar="S", help="with --softcap: softmax_scale of both arms (default 1 / sqrt(head_dim))")
     a = ap.parse_args()
     base = _baseline_lib(a.baseline_library) if a.baseline_library else None
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
@@ -519,6 +565,8 @@ def main():
         for pt in grid(a.quick, a.length):
             if base is not None:
                 print(json.dumps(run_ab_point(pt, base, a.rounds)), flush=True)
+            elif a.softcap is not None:
+                print(json.dumps(run_softcap_point(pt, a.softcap, a.softmax_scale, a.kv_dtype == "fp8", a.rounds)), flush=True)
             elif a.rotary is not None:
                 if pt["seqlen_q"] == 1:
                     print(json.dumps(run_rotary_point(pt, a.rotary, not a.rotary_neox, a.rounds)), flush=True)
