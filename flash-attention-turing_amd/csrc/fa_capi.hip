@@ -54,11 +54,14 @@ int check_cache8(const char* name, const void* ptr, const fa_strides& st, int64_
     return FA_OK;
 }
 
-int check_common(int b, int sq, int sk, int h, int hk, int d, int dtype) {
+// kvcache: the decode call, which has head_dim 256 as well (fa_fwd_kvcache_d256.hip); fwd / bwd / varlen have 64 and 128
+int check_common(int b, int sq, int sk, int h, int hk, int d, int dtype, bool kvcache = false) {
     if (b < 0 || sq < 0 || sk < 0 || h <= 0 || hk <= 0)
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d seqlen_k=%d h=%d h_k=%d", b, sq, sk, h, hk);
     if (h % hk != 0) return fail(FA_ERR_BAD_GQA, "num_heads_q (%d) must be divisible by num_heads_k (%d) for GQA/MQA", h, hk);
-    if (d != 64 && d != 128) return fail(FA_ERR_BAD_HEADDIM, "head_dim %d unsupported (64 or 128)", d);
+    if (kvcache) {
+        if (d != 64 && d != 128 && d != 256) return fail(FA_ERR_BAD_HEADDIM, "head_dim %d unsupported (64, 128 or 256 over a KV cache)", d);
+    } else if (d != 64 && d != 128) return fail(FA_ERR_BAD_HEADDIM, "head_dim %d unsupported (64 or 128)", d);
     if (dtype != FA_FP16 && dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", dtype);
     return FA_OK;
 }
@@ -378,7 +381,7 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
     if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0 || p->seqlen_new < 0 || p->h <= 0 || p->h_k <= 0)
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d seqlen_new=%d h=%d h_k=%d", p->b, p->seqlen_q, p->seqlen_cache,
                     p->seqlen_new, p->h, p->h_k);
-    if ((rc = check_common(p->b, p->seqlen_q, p->seqlen_cache, p->h, p->h_k, p->d, p->dtype))) return rc;
+    if ((rc = check_common(p->b, p->seqlen_q, p->seqlen_cache, p->h, p->h_k, p->d, p->dtype, true))) return rc;
     if (paged) {
         const int P = p->page_block_size;
         if (P == 0) return fail(FA_ERR_BAD_SHAPE, "block_table given without page_block_size");

@@ -172,6 +172,14 @@ FA_DEV uint32_t lds_tile_off(uint32_t row, uint32_t slot /* 16-byte slot in row,
     if constexpr (D == 128) {
         uint32_t s = slot ^ (((row & 3) << 2) | ((row >> 2) & 3));
         return row * 256u + (s << 4);
+    } else if constexpr (D == 256) {
+        // (decode over a KV cache only, fa_fwd_kvcache_d256.hip) 32 slots per 512-byte row: two 256-byte bank rows.  Both patterns above are
+        // counted modulo one bank row, and slot bit 4 only picks which of a row's two bank rows is touched, so the D = 128 swizzle on the
+        // low four slot bits carries over as it is: (1) 16 rows distinct mod 16 at one slot index land in 16 different 16-byte bank groups of
+        // whichever bank row; (2) the 4 rows x 64 contiguous bytes of a transposed read share slot bits 4..2 (64 bytes = 4 aligned slots)
+        // and the swizzle's top two bits put each row into another 64-byte bank quarter.  The row pitch, a multiple of 256, adds nothing.
+        uint32_t s = slot ^ (((row & 3) << 2) | ((row >> 2) & 3));
+        return row * 512u + (s << 4);
     } else {
         static_assert(D == 64, "head_dim must be 64 or 128");
         // 8 slots per row. bits: slot = (c1 c0 | w) with chunk pairs; use row bits 1..3.
@@ -186,6 +194,7 @@ FA_DEV uint32_t lds_tile_off(uint32_t row, uint32_t slot /* 16-byte slot in row,
 template <int D>
 FA_DEV uint32_t lds_tile_logical_slot(uint32_t row, uint32_t phys) {
     if constexpr (D == 128) return phys ^ (((row & 3) << 2) | ((row >> 2) & 3));
+    else if constexpr (D == 256) return phys ^ (((row & 3) << 2) | ((row >> 2) & 3));      // (the low four bits, as in lds_tile_off)
     else return phys ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3));
 }
 

@@ -523,7 +523,10 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams
             constexpr int j = decltype(jj)::value;
             w[j] = LP<T>::pack2(acc[2 * j] * inv, acc[2 * j + 1] * inv);
         });
-        if constexpr (CPT == 8) *(u32x4*)orow = u32x4{w[0], w[1], w[2], w[3]};
+        if constexpr (CPT == 16) {         // (head_dim 256, fa_fwd_kvcache_d256.hip: 32 bytes of the row per thread)
+            *(u32x4*)orow = u32x4{w[0], w[1], w[2], w[3]};
+            *(u32x4*)(orow + 16) = u32x4{w[4], w[5], w[6], w[7]};
+        } else if constexpr (CPT == 8) *(u32x4*)orow = u32x4{w[0], w[1], w[2], w[3]};
         else *(u32x2*)orow = u32x2{w[0], w[1]};
         if ((tid & 15) == 0) p.lse_ptr[R] = lse;
     } else {
@@ -538,8 +541,9 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams
     }
 }
 
-// (fa_fwd_kvcache_ragged.hip includes this file for the body above and kvcache_steps below; the dense kernels and launchers are this file's own)
-#ifndef FA_KVC_RAGGED_TU
+// (fa_fwd_kvcache_ragged.hip includes this file for the body above and kvcache_steps below; the dense kernels and launchers are this file's own.
+// fa_fwd_kvcache_d256.hip instantiates the combine and append templates at head_dim 256 and sets FA_KVC_D256_TU to see them)
+#if !defined(FA_KVC_RAGGED_TU) || defined(FA_KVC_D256_TU)
 template <typename T, int D, bool CAUSAL>
 __global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_kernel(const KvcacheKernelParams p) {
     kvcache_attn<T, D, CAUSAL, false>(p);
@@ -759,7 +763,7 @@ hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s, float 
     }
     return hipGetLastError();
 }
-#endif  // FA_KVC_RAGGED_TU
+#endif  // !FA_KVC_RAGGED_TU || FA_KVC_D256_TU
 
 // 32-key steps the splits of a launch must cover.  A window with a left edge bounds what one workgroup reads from its base: the tile's
 // largest lim minus its smallest lo is at most left + seqlen_q + max(right, 0), plus up to kKvcStep - 1 keys of the base's alignment.
@@ -830,6 +834,7 @@ hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s, 
     if (kp.n_split > 1) {
         kp.ws_lse = kp.ws_o + (int64_t)kp.n_split * kp.rows_total * kp.d;
     }
+    if (kp.d == 256) return launch_kvcache_d256(kp, dtype, s, cap_pre);
     if (kp.cache_fp8) {
         if (dtype == 0) return kp.d == 64 ? launch_kvcache_fp8_t<_Float16, 64>(kp, s, cap_pre) : launch_kvcache_fp8_t<_Float16, 128>(kp, s, cap_pre);
         return kp.d == 64 ? launch_kvcache_fp8_t<__bf16, 64>(kp, s, cap_pre) : launch_kvcache_fp8_t<__bf16, 128>(kp, s, cap_pre);

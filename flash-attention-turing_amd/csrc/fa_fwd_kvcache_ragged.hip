@@ -165,6 +165,7 @@ hipError_t launch_kvcache_ragged_es(const KvcacheRaggedParams& rp, hipStream_t s
 
 }  // namespace
 
+#ifndef FA_KVC_D256_TU      // (fa_fwd_kvcache_d256.hip includes this file for the templates above)
 // kp.seqlen_q = max_seqlen_q sizes the split exactly as the dense launcher does (kvcache_steps), so a forced split cuts the keys where the dense
 // call with seqlen_q = max_seqlen_q cuts them.
 hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t s, float cap_pre) {
@@ -177,8 +178,10 @@ hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStrea
     kp.split_keys = (int32_t)(((steps + kp.n_split - 1) / kp.n_split) * kKvcStep);
     if (kp.split_keys <= 0) kp.split_keys = kKvcStep;
     if (kp.n_split > 1) kp.ws_lse = kp.ws_o + (int64_t)kp.n_split * kp.rows_total * kp.d;
+    if (kp.d == 256) return launch_kvcache_ragged_d256(rp, dtype, s, cap_pre);
     if (dtype == 0) return kp.d == 64 ? launch_kvcache_ragged_es<_Float16, 64>(rp, s, cap_pre) : launch_kvcache_ragged_es<_Float16, 128>(rp, s, cap_pre);
     return kp.d == 64 ? launch_kvcache_ragged_es<__bf16, 64>(rp, s, cap_pre) : launch_kvcache_ragged_es<__bf16, 128>(rp, s, cap_pre);
 }
+#endif  // FA_KVC_D256_TU
 
 }  // namespace fa

@@ -159,13 +159,16 @@ hipError_t launch_rotary_t(const KvcacheRotaryParams& rp, hipStream_t s) {
 
 }  // namespace
 
+#ifndef FA_KVC_D256_TU      // (fa_fwd_kvcache_d256.hip includes this file for the kernel and launch_rotary_t above)
 int64_t kvcache_rotary_image_bytes(const KvcacheKernelParams& kp) {
     return ((int64_t)kp.b * kp.seqlen_q * kp.h * kp.d * 2 + 15) / 16 * 16;
 }
 
 hipError_t launch_kvcache_rotary(const KvcacheRotaryParams& rp, int dtype, hipStream_t s) {
+    if (rp.kp.d == 256) return launch_kvcache_rotary_d256(rp, dtype, s);
     if (dtype == 0) return rp.kp.d == 64 ? launch_rotary_t<_Float16, 64>(rp, s) : launch_rotary_t<_Float16, 128>(rp, s);
     return rp.kp.d == 64 ? launch_rotary_t<__bf16, 64>(rp, s) : launch_rotary_t<__bf16, 128>(rp, s);
 }
+#endif  // FA_KVC_D256_TU
 
 }  // namespace fa

@@ -219,6 +219,13 @@ struct KvcacheRotaryParams {
 int64_t kvcache_rotary_image_bytes(const KvcacheKernelParams& kp);     // bytes of q_image, rounded up to 16
 hipError_t launch_kvcache_rotary(const KvcacheRotaryParams& rp, int dtype, hipStream_t stream);
 
+// head_dim 256 (fa_fwd_kvcache_d256.hip): every kernel of a decode call at d = 256 - attention, append, combine, rotary - lives in that file, built
+// for ONE workgroup per compute unit.  The three launchers above finish kp / rp exactly as for 64 / 128 (row tiles, slots, split,
+// workspace planes) and hand over here where they would pick their own instantiations.
+hipError_t launch_kvcache_d256(const KvcacheKernelParams& kp, int dtype, hipStream_t stream, float cap_pre);
+hipError_t launch_kvcache_ragged_d256(const KvcacheRaggedParams& rp, int dtype, hipStream_t stream, float cap_pre);
+hipError_t launch_kvcache_rotary_d256(const KvcacheRotaryParams& rp, int dtype, hipStream_t stream);
+
 // query-head group split chosen for a dK/dV launch (1 = none) and the workspace it needs
 int32_t dkdv_split(const BwdKernelParams& kp, int64_t avail_bytes);
 int64_t dkdv_workspace_bytes(const BwdKernelParams& kp, int32_t n_split);

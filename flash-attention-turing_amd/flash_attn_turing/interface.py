@@ -163,6 +163,12 @@ def _check_scale_and_cap(softmax_scale, softcap):
     return softmax_scale, softcap
 
 
+def _check_kvcache_head_dim(q):
+    """decode over a KV cache has head_dim 64, 128 and 256 (fwd / bwd / varlen_*: 64 and 128)"""
+    if q.shape[-1] not in (64, 128, 256):
+        raise ValueError(f"head_dim {q.shape[-1]} unsupported: flash_attn_with_kvcache has head_dim 64, 128 and 256")
+
+
 def _check_cu_seqlens(name, t, q, batch=None):
     """a cu_seqlens tensor: int32, shape (b + 1,), contiguous, on q's device"""
     if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
@@ -224,6 +230,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     Non-finite inputs follow fp32 math over the valid prefix, for every num_splits: a NaN query row, or a NaN / +inf score from a visible K row,
     gives NaN in that row's O and LSE; a row that sees no key is O = 0, LSE = 0.  Cache rows at or past L_i and heads the
     cache views skip are never read into a result.
+
+    head_dim d: 64, 128 or 256; anything else is a ValueError.  d = 256 (Gemma 2 2B / 9B, Gemma 3) exists for this call only - fwd, bwd,
+    varlen_* and flash_attn_func stay at 64 / 128 - and supports everything below exactly as 128 does: the same tolerances and the same
+    bit-for-bit relations.  Its attention kernels run one workgroup per compute unit (a lane holds about 400 registers) where 64 / 128 run two.
 
     block_table (keyword, optional): a paged cache.  k_cache, v_cache are then page pools (num_blocks, page_block_size, nheads_k, d), any
     page / row / head strides, page_block_size a multiple of 16; block_table is an int32 tensor (batch, max_blocks_per_seq) on q's device
@@ -296,7 +306,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     places: always without a left-bounded window, and with one for the sequences with sq_i == max_seqlen_q (the split of a windowed call
     is sized from left + max_seqlen_q + right).  Each sequence is tiled on its own (a 16-row tile never spans two sequences), and the
     launch is sized by the tokens present, not by batch x max_seqlen_q.  Everything above carries over: both cache layouts and the
-    clamping of table entries, GQA / MQA, fp16 / bf16, head_dim 64 / 128, the FP8 cache and its descales, window_size, causal, num_splits,
+    clamping of table entries, GQA / MQA, fp16 / bf16, head_dim 64 / 128 / 256, the FP8 cache and its descales, window_size, causal, num_splits,
     the NaN rules, dead rows O = 0, LSE = 0, determinism per split count, what is never read, and no host synchronisation - a captured
     call replays with the cu_seqlens, lengths, tables and descales then in memory (total_q, total_new, batch and max_seqlen_q are baked
     in).  Not supported, a ValueError: rotary_cos / rotary_sin together with cu_seqlens_q.  Also ValueErrors: cu_seqlens_k_new without
@@ -310,7 +320,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     comes after the cap, the softmax runs over the capped scores, and lse is their natural-log logsumexp.  tanh is evaluated as
     ``1 - 2 / (exp(2 x) + 1)`` with the hardware exponential and reciprocal: absolute error about 1e-7, times softcap in the score.  Both are
     host scalars baked into the call like the window: no synchronisation, and a captured call replays with them.  Everything above carries
-    over for both: block_table and the clamping of table entries, GQA / MQA, fp16 / bf16, head_dim 64 / 128, window_size, causal,
+    over for both: block_table and the clamping of table entries, GQA / MQA, fp16 / bf16, head_dim 64 / 128 / 256, window_size, causal,
     num_splits (the split count and the workspace do not depend on the two values), the FP8 cache (k_descale multiplies the score inside
     the tanh, v_descale stays in the final normalisation), rotary (a launch of its own in front of attention), cu_seqlens_q (sequence i of
     a soft-capped ragged call equals the soft-capped dense call on it alone, bit for bit, under the split rule above), paged == contiguous
@@ -337,12 +347,14 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
         if max_seqlen_q is not None:
             raise ValueError("max_seqlen_q given without cu_seqlens_q")
         _check_rotary(q, k_cache, k, block_table, rotary_cos, rotary_sin, rotary_interleaved)
+        _check_kvcache_head_dim(q)
         if isinstance(cache_seqlens, int):
             cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=q.device)
         out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right,
                                   k_descale=k_descale, v_descale=v_descale, rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved, **extra)
         return (out, lse) if return_softmax_lse else out
     b = _check_ragged(q, k_cache, k, v, cache_seqlens, block_table, k_descale, v_descale, rotary_cos, rotary_sin, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new)
+    _check_kvcache_head_dim(q)
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
     out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right,

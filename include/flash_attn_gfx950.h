@@ -31,7 +31,8 @@
  *   varlen: q (total_q, nheads, d), k/v (total_k, nheads_k, d) packed, cu_seqlens int32
  *   device arrays of length batch+1, lse padded to (batch, nheads, max_seqlen_q).
  *   head_dim in {64, 128} (static_switch.h:29-38); unlike the reference an unsupported
- *   head_dim is an error, not a silent no-op.
+ *   head_dim is an error, not a silent no-op.  (Decode over a KV cache, fa_kvcache_params below, has
+ *   head_dim 256 as well: FA_HAS_KVCACHE_HEADDIM256.)
  *   Non-finite Q / K (forward): a NaN in a query row, or a NaN or +inf score (NaN or inf in a
  *   K row the query sees) gives that row o = NaN and lse = NaN, never +-inf; a -inf score only
  *   drops its key; a row that sees no key stays o = 0, lse = 0.  Rows the bad value does not
@@ -76,7 +77,7 @@ enum fa_status {
     FA_ERR_NULL_POINTER = -1,
     FA_ERR_BAD_SHAPE = -2,       /* rank/size disagreement (reference: TORCH_CHECKs flash_api.cpp:178-183) */
     FA_ERR_BAD_GQA = -3,         /* nheads % nheads_k != 0 (flash_api.cpp:183) */
-    FA_ERR_BAD_HEADDIM = -4,     /* head_dim not in {64,128} */
+    FA_ERR_BAD_HEADDIM = -4,     /* head_dim not in {64,128} (decode over a KV cache: {64,128,256}) */
     FA_ERR_BAD_DTYPE = -5,
     FA_ERR_BAD_STRIDE = -6,      /* last dim not contiguous, misaligned rows, or extent > 2^31 bytes per sequence */
     FA_ERR_NO_DEVICE = -7,
@@ -181,7 +182,14 @@ typedef struct fa_bwd_params {
  * shared between sequences for reading.  Precondition: every entry a sequence needs lies in [0, num_blocks).  Broken, nothing outside the
  * pool is read or written: every entry the kernels use goes through min((uint32_t)entry, num_blocks - 1), so a bad entry reads (or, for
  * the append, writes) page num_blocks - 1.  A caller built against the header before these fields (struct_size = offsetof(block_table))
- * gets the contiguous cache. */
+ * gets the contiguous cache.
+ * head_dim (FA_HAS_KVCACHE_HEADDIM256): d is 64, 128 or 256; anything else is FA_ERR_BAD_HEADDIM.  d = 256 (Gemma 2 2B / 9B, Gemma 3) exists for
+ * the three kvcache entry points and their _ex forms ONLY - fa_run_mha_fwd / _bwd and the varlen entry points keep rejecting it - and supports
+ * everything stated here and for the options below exactly as d = 128 does: both dtypes, both layouts, GQA / MQA, causal, windows, the 8-bit cache,
+ * rotary (rotary_dim up to 256), ragged batches, softmax_scale and softcap, num_splits, graph capture; same tolerances, same bit-for-bit
+ * relations (paged = contiguous, ragged sequence = dense call, rotary = pre-rotated), same workspace formula (it is written in d).  Its
+ * attention kernels run one workgroup per compute unit where 64 / 128 run two (a lane holds about 390 registers at d = 256). */
+#define FA_HAS_KVCACHE_HEADDIM256 1
 typedef struct fa_kvcache_params {
     uint32_t struct_size;       /* sizeof(fa_kvcache_params) in the caller's translation unit */
     uint32_t magic;             /* FA_PARAMS_MAGIC */
@@ -375,7 +383,7 @@ typedef struct fa_kvcache_options_v4 {      /* FA_PARAMS_INIT(o); then fa_..._ex
  * softcap is zero or infinite in fp32; a non-zero `reserved` is FA_ERR_BAD_ABI (a
  * newer caller's field this library does not know).  Errors of fa_kvcache_params and of the older option fields come first.  Both are host
  * values baked into the call like the window: no synchronisation, and a captured call replays with them.  Everything stated above carries over
- * for both: contiguous and paged layout and the clamping of table entries, GQA / MQA, fp16 / bf16, head_dim 64 / 128, windows, causal,
+ * for both: contiguous and paged layout and the clamping of table entries, GQA / MQA, fp16 / bf16, head_dim 64 / 128 / 256, windows, causal,
  * num_splits (the split count and the workspace do not depend on the two values), the 8-bit cache (k_descale multiplies the score inside the
  * tanh, v_descale stays in the final normalisation), rotary (a launch of its own in front of attention), ragged batches (sequence i of a
  * soft-capped ragged call equals the soft-capped dense call on it alone, bit for bit, under the split rule above), rows without a visible key

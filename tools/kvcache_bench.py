@@ -39,6 +39,12 @@ medians.
 (B, B2) so that the spread of one thing measured twice in the same run stands next to A / B; interleaved, medians.  TB/s over the bytes
 both read.
 
+--head-dim D (repeatable) replaces the grid's head dims (64, 128).  head_dim 256 exists for the decode call only: its points carry no fwd arm.
+--equal-bytes (with --head-dim 256) measures the head_dim-256 call against its yardstick instead: per grid point with one query, (A) the
+d-256 call; (B, B2) the d-128 call on the same b and L with twice the KV heads and twice the query heads - the same cache bytes (the very
+same buffers, viewed as (b, L, 2 h_k, 128)), the same FLOPs, the same row-tile count - timed TWICE so that the scatter of one thing measured
+twice in the same run stands next to A / B; interleaved, medians.  `hbm_bound` marks the points whose K/V are at least 1 GB.
+
 --baseline-library PATH records an interleaved A/B of the plain (no window) call through the C ABI of this build and of the library at
 PATH (e.g. a build of the parent commit), on the same data; the outputs must agree bit for bit.  --length L (repeatable) replaces the
 grid's cache lengths."""
@@ -62,14 +68,16 @@ HBM_ACHIEVABLE, HBM_PEAK = 6.3e12, 8.0e12
 WORKING_SET = 256 << 20
 
 
-def grid(quick, lengths=None):
+def grid(quick, lengths=None, head_dims=None):
     bs, heads, ds, ls, sqs = (1, 8, 32), ((32, 32), (32, 8), (32, 1)), (64, 128), (4096, 32768, 131072), (1, 4)
     if quick:
         bs, ls = (1, 8), (32768,)
     if lengths:
         ls = tuple(lengths)
+    if head_dims:
+        ds = tuple(head_dims)
     for b, (h, hk), d, L, sq in itertools.product(bs, heads, ds, ls, sqs):
-        for dt in ((torch.float16, torch.bfloat16) if d == 128 else (torch.float16,)):
+        for dt in ((torch.float16, torch.bfloat16) if d >= 128 else (torch.float16,)):
             yield dict(b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=sq, dtype=dt)
 
 
@@ -103,12 +111,13 @@ def run_point(pt, rounds):
     n_split = max(1, ws and capi.kvcache_num_splits(_with_ws(p, ws)))
     kv = lambda i: F.flash_attn_with_kvcache(q, caches[i][0], caches[i][1], cache_seqlens=cs)
     fw = lambda i: F.fwd(q, caches[i][0][:, :L], caches[i][1][:, :L], False)
-    kv(0), fw(0)
+    has_fwd = d <= 128                                        # (head_dim 256: the decode call only)
+    kv(0), has_fwd and fw(0)
     torch.cuda.synchronize()
     t_kv, t_fw = [], []
     for _ in range(rounds):
         t_kv.append(time_rotation(kv, n, 20))
-        t_fw.append(time_rotation(fw, n, 20))
+        t_fw.append(time_rotation(fw, n, 20) if has_fwd else float("nan"))
     ms_kv, ms_fw = statistics.median(t_kv), statistics.median(t_fw)
     rows = b * h * sq
     moved = kv_bytes + 2 * rows * d * 2 + rows * 4 + (2 * n_split * rows * (d + 1) * 4 if n_split > 1 else 0)
@@ -116,9 +125,42 @@ def run_point(pt, rounds):
     del caches
     torch.cuda.empty_cache()
     return dict(b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=sq, dtype=str(dt).replace("torch.", ""), caches_rotated=n,
-                ms_kvcache=round(ms_kv, 5), ms_fwd=round(ms_fw, 5), bytes=moved, tbps=round(tbps, 3),
+                ms_kvcache=round(ms_kv, 5), ms_fwd=round(ms_fw, 5) if has_fwd else None, bytes=moved, tbps=round(tbps, 3),
                 frac_of_6p3=round(tbps * 1e12 / HBM_ACHIEVABLE, 3), frac_of_8=round(tbps * 1e12 / HBM_PEAK, 3), n_split=n_split,
-                speedup_vs_fwd=round(ms_fw / ms_kv, 2))
+                speedup_vs_fwd=round(ms_fw / ms_kv, 2) if has_fwd else None)
+
+
+def run_equal_bytes_point(pt, rounds):
+    """(A) the head_dim-256 call, (B, B2) the head_dim-128 call with twice the heads on the SAME buffers, twice; interleaved"""
+    dev = torch.device("cuda:0")
+    b, h, hk, d, L, dt = pt["b"], pt["h"], pt["h_k"], pt["d"], pt["L"], pt["dtype"]
+    assert d == 256 and pt["seqlen_q"] == 1
+    kv_bytes = 2 * b * L * hk * d * 2
+    n = _rotation(kv_bytes, kv_bytes)
+    caches = [(torch.empty(b, L, hk, d, device=dev, dtype=dt).uniform_(-2, 2), torch.empty(b, L, hk, d, device=dev, dtype=dt).uniform_(-2, 2)) for _ in range(n)]
+    halves = [(kc.view(b, L, 2 * hk, 128), vc.view(b, L, 2 * hk, 128)) for kc, vc in caches]
+    q = torch.randn(b, 1, h, d, device=dev, dtype=dt)
+    q128 = q.view(b, 1, 2 * h, 128)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    f256 = lambda i: F.flash_attn_with_kvcache(q, caches[i][0], caches[i][1], cache_seqlens=cs)
+    f128 = lambda i: F.flash_attn_with_kvcache(q128, halves[i][0], halves[i][1], cache_seqlens=cs)
+    f256(0), f128(0)
+    torch.cuda.synchronize()
+    ms = _interleaved({"d128": f128, "d256": f256, "d128_again": f128}, n, rounds)
+    splits = []
+    for qq, (kc, vc), hh in ((q, caches[0], h), (q128, halves[0], 2 * h)):
+        p = capi.kvcache_params(qq, kc, vc, torch.empty_like(qq), torch.empty(b, hh, 1, device=dev), cache_seqlens=cs)
+        ws = capi.kvcache_workspace_bytes(p)
+        splits.append(max(1, ws and capi.kvcache_num_splits(_with_ws(p, ws))))
+    del caches, halves
+    torch.cuda.empty_cache()
+    tb = lambda t: round(kv_bytes / (t * 1e-3) / 1e12, 3)
+    lo, hi = sorted((ms["d128"], ms["d128_again"]))
+    return dict(equal_bytes=True, b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=1, dtype=str(dt).replace("torch.", ""), kv_gb=round(kv_bytes / 1e9, 3), hbm_bound=kv_bytes >= 1e9,
+                caches_rotated=n, n_split_d256=splits[0], n_split_d128=splits[1], ms_d256=round(ms["d256"], 5), ms_d128=round(ms["d128"], 5),
+                ms_d128_again=round(ms["d128_again"], 5), d256_over_d128=round(ms["d256"] / ms["d128"], 4), d128_again_over_d128=round(ms["d128_again"] / ms["d128"], 4),
+                inside_scatter=bool(lo <= ms["d256"] <= hi), tbps_d256=tb(ms["d256"]), tbps_d128=tb(ms["d128"]),
+                frac_of_6p3_d256=round(kv_bytes / (ms["d256"] * 1e-3) / HBM_ACHIEVABLE, 3), frac_of_6p3_d128=round(kv_bytes / (ms["d128"] * 1e-3) / HBM_ACHIEVABLE, 3))
 
 
 def run_paged_point(pt, page, rounds):
@@ -551,6 +593,8 @@ def main():
     ap.add_argument("--softcap", type=float, default=None, metavar="CAP", help="the soft-capped call against the same call without the cap (timed twice); with --kv-dtype fp8 "
                                                                                "over the 8-bit cache")
     ap.add_argument("--softmax-scale", type=float, default=None, metavar="S", help="with --softcap: softmax_scale of both arms (default 1 / sqrt(head_dim))")
+    ap.add_argument("--head-dim", type=int, action="append", metavar="D", choices=(64, 128, 256), help="head dim(s) instead of the grid's 64 and 128 (256: the decode call only)")
+    ap.add_argument("--equal-bytes", action="store_true", help="with --head-dim 256: the d-256 call against the d-128 call with twice the heads on the same buffers (timed twice)")
     a = ap.parse_args()
     base = _baseline_lib(a.baseline_library) if a.baseline_library else None
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
@@ -562,8 +606,11 @@ def main():
             for line in run_ragged(a.quick, a.rounds):
                 print(json.dumps(line), flush=True)
             return
-        for pt in grid(a.quick, a.length):
-            if base is not None:
+        for pt in grid(a.quick, a.length, a.head_dim):
+            if a.equal_bytes:
+                if pt["d"] == 256 and pt["seqlen_q"] == 1:
+                    print(json.dumps(run_equal_bytes_point(pt, a.rounds)), flush=True)
+            elif base is not None:
                 print(json.dumps(run_ab_point(pt, base, a.rounds)), flush=True)
             elif a.softcap is not None:
                 print(json.dumps(run_softcap_point(pt, a.softcap, a.softmax_scale, a.kv_dtype == "fp8", a.rounds)), flush=True)
