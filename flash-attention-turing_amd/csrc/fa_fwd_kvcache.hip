@@ -159,8 +159,14 @@ FA_DEV float kvc_tanh2(float y) { return __builtin_fmaf(-2.f, fast_rcp(fast_exp2
 // the host puts the cap where the scale was: p.scale = softcap, p.scale_log2e = softcap * log2(e).  The running max then lives in tanh units
 // and nothing behind the mask knows the difference; the descale of an 8-bit K rides on pre, inside the tanh, not on c.  SOFTCAP is a template
 // parameter: the instantiations without it are the code they were.
-template <typename T, int D, bool CAUSAL, bool PAGED, bool LOCAL = false, int ES = 2, bool RAGGED = false, bool SOFTCAP = false>
-FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams* rg = nullptr, float cap_pre = 0.f) {
+// SINK (fa_fwd_kvcache_sink.hip; `sinks` / `sinks_stride` are read only then, and only by an unsplit launch): query head hq has a learned logit
+// sinks[hq * sinks_stride] that joins the softmax denominator and brings no value.  It enters once per row in the epilogue, behind the merge
+// of the four waves and in front of inv and lse, as one more key whose score, in natural-log units, is the sink and whose V row is zero: the
+// 32-key loop does not know it.  A split launch (n_split > 1) writes the partials of the call without sinks - the sink combine of
+// fa_fwd_kvcache_sink.hip adds the term there.  SINK is a template parameter: the instantiations without it are the code they were.
+template <typename T, int D, bool CAUSAL, bool PAGED, bool LOCAL = false, int ES = 2, bool RAGGED = false, bool SOFTCAP = false, bool SINK = false>
+FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams* rg = nullptr, float cap_pre = 0.f, const float* sinks = nullptr,
+                         int64_t sinks_stride = 0) {
     static_assert(ES == 1 || ES == 2, "cache elements are 16-bit (the dtype of q) or 8-bit (e4m3)");
     constexpr int NC = D / 32;          // 16x16x32 MFMAs per 16 keys of S^T (d chunks)
     constexpr int NO = D / 16;          // O^T blocks of 16 columns
@@ -510,11 +516,35 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams
         });
     });
     const int ot = opr / p.h_ratio, ohq = kvh * p.h_ratio + (opr - ot * p.h_ratio);
+    [[maybe_unused]] float sink_top = 0.f;      // SINK: the sink where it is the row's maximum (on_sink)
+    [[maybe_unused]] bool on_sink = false;
+    if constexpr (SINK) {
+        // M = max(row max, sink), compared in natural-log units.  The sink on top: the row's sums move down onto it and it counts 1.  Otherwise
+        // it adds exp(sink - max) to the sum, which is + 0.0f for a sink of -inf (the guard keeps -inf - -inf out of the exponential): the
+        // bits of the call without sinks.  A row that saw no key (lsum = 0, mrow = kNegBig) goes the first way under a finite sink: lsum = 1,
+        // O = 0, LSE = the sink exactly.  A NaN sink fails the comparison and makes the sum NaN: O and LSE of the head's rows are NaN.
+        if (p.n_split == 1) {
+            const float sk = sinks[(int64_t)ohq * sinks_stride];
+            const float ms = mrow * sc;
+            if (sk > ms) {
+                const float a = fast_exp2((ms - sk) * 1.4426950408889634f);
+                lsum = __builtin_fmaf(lsum, a, 1.f);
+                static_for<0, CPT>([&](auto jj) { acc[decltype(jj)::value] *= a; });
+                sink_top = sk;
+                on_sink = true;
+            } else {
+                lsum += sk == -INFINITY ? 0.f : fast_exp2((sk - ms) * 1.4426950408889634f);
+            }
+        }
+    }
     // dead = saw no key (lsum == 0); a NaN or +inf score leaves lsum = NaN, which is live: O and LSE come out NaN as in fp32 math, and a
     // split partial is written so that the combine propagates it
     const bool live = !(lsum == 0.f);
     const float inv = live ? (ES == 1 ? vd / lsum : 1.0f / lsum) : 0.f;
-    const float lse = live ? mrow * sc + logf(lsum) : (p.n_split > 1 ? -INFINITY : 0.f);
+    float lse = live ? mrow * sc + logf(lsum) : (p.n_split > 1 ? -INFINITY : 0.f);
+    if constexpr (SINK) {
+        if (on_sink) lse = sink_top + logf(lsum);
+    }
     const int64_t R = row_index(ohq, ot);
     if (p.n_split == 1) {
         char* orow = (char*)p.o_ptr + 2 * (row_off(p.o, ohq, ot) + col);
@@ -705,7 +735,7 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_fp8_kernel(const Kvcach
 }
 
 template <typename T, int D>
-hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre) {
+hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre, const KvcacheSink& sink) {
     const bool paged = kp.block_table != nullptr;
     if (kp.k_new != nullptr && kp.seqlen_new > 0) {
         const int64_t n = (int64_t)kp.b * kp.seqlen_new * kp.h_k * (D / 8);
@@ -715,6 +745,9 @@ hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, fl
     const int64_t grid = (int64_t)kp.b * kp.h_k * kp.n_row_tiles * kp.n_split;
     if (cap_pre > 0.f) {        // soft-capped scores: the attention kernels of fa_fwd_kvcache_softcap.hip between this file's append and combine
         const hipError_t e = launch_kvcache_softcap_attn(kp, cap_pre, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
+        if (e != hipSuccess) return e;
+    } else if (sink.ptr != nullptr && kp.n_split == 1) {    // sinks, unsplit: the attention kernels of fa_fwd_kvcache_sink.hip (a split call runs the kernels below)
+        const hipError_t e = launch_kvcache_sink_attn(kp, sink, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
         if (e != hipSuccess) return e;
     } else if (kp.is_local) {
         if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_fp8_local_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
@@ -727,6 +760,8 @@ hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, fl
         else hipLaunchKernelGGL((fa_fwd_kvcache_fp8_kernel<T, D, false>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
     }
     if (kp.n_split > 1) {
+        // (sinks: the combine of fa_fwd_kvcache_sink.hip, which adds the sink as one more term of the merge)
+        if (sink.ptr != nullptr) return launch_kvcache_sink_combine(kp, sink, std::is_same_v<T, _Float16> ? 0 : 1, s);
         const int64_t rows_per_block = kKvcCombineThreads / (D / 8);
         hipLaunchKernelGGL((fa_kvcache_combine_kernel<T, D>), dim3((unsigned)((kp.rows_total + rows_per_block - 1) / rows_per_block)),
                            dim3(kKvcCombineThreads), 0, s, kp);
@@ -735,7 +770,7 @@ hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, fl
 }
 
 template <typename T, int D>
-hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre) {
+hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre, const KvcacheSink& sink) {
     const bool paged = kp.block_table != nullptr;
     if (kp.k_new != nullptr && kp.seqlen_new > 0) {
         const int64_t n = (int64_t)kp.b * kp.seqlen_new * kp.h_k * (D / 8);
@@ -745,6 +780,9 @@ hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s, float 
     const int64_t grid = (int64_t)kp.b * kp.h_k * kp.n_row_tiles * kp.n_split;
     if (cap_pre > 0.f) {        // soft-capped scores: the attention kernels of fa_fwd_kvcache_softcap.hip between this file's append and combine
         const hipError_t e = launch_kvcache_softcap_attn(kp, cap_pre, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
+        if (e != hipSuccess) return e;
+    } else if (sink.ptr != nullptr && kp.n_split == 1) {    // sinks, unsplit: the attention kernels of fa_fwd_kvcache_sink.hip (a split call runs the kernels below)
+        const hipError_t e = launch_kvcache_sink_attn(kp, sink, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
         if (e != hipSuccess) return e;
     } else if (kp.is_local) {
         if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_local_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
@@ -757,6 +795,8 @@ hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s, float 
         else hipLaunchKernelGGL((fa_fwd_kvcache_kernel<T, D, false>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
     }
     if (kp.n_split > 1) {
+        // (sinks: the combine of fa_fwd_kvcache_sink.hip, which adds the sink as one more term of the merge)
+        if (sink.ptr != nullptr) return launch_kvcache_sink_combine(kp, sink, std::is_same_v<T, _Float16> ? 0 : 1, s);
         const int64_t rows_per_block = kKvcCombineThreads / (D / 8);
         hipLaunchKernelGGL((fa_kvcache_combine_kernel<T, D>), dim3((unsigned)((kp.rows_total + rows_per_block - 1) / rows_per_block)),
                            dim3(kKvcCombineThreads), 0, s, kp);
@@ -824,7 +864,7 @@ int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split, 
     return o_bytes + l_bytes;
 }
 
-hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s, float cap_pre) {
+hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s, float cap_pre, KvcacheSink sink) {
     kp.n_row_tiles = (int32_t)(((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
     kp.rows_total = (int64_t)kp.b * kp.h * kp.seqlen_q;
     const int64_t steps = kvcache_steps(kp);
@@ -836,11 +876,11 @@ hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s, 
     }
     if (kp.d == 256) return launch_kvcache_d256(kp, dtype, s, cap_pre);
     if (kp.cache_fp8) {
-        if (dtype == 0) return kp.d == 64 ? launch_kvcache_fp8_t<_Float16, 64>(kp, s, cap_pre) : launch_kvcache_fp8_t<_Float16, 128>(kp, s, cap_pre);
-        return kp.d == 64 ? launch_kvcache_fp8_t<__bf16, 64>(kp, s, cap_pre) : launch_kvcache_fp8_t<__bf16, 128>(kp, s, cap_pre);
+        if (dtype == 0) return kp.d == 64 ? launch_kvcache_fp8_t<_Float16, 64>(kp, s, cap_pre, sink) : launch_kvcache_fp8_t<_Float16, 128>(kp, s, cap_pre, sink);
+        return kp.d == 64 ? launch_kvcache_fp8_t<__bf16, 64>(kp, s, cap_pre, sink) : launch_kvcache_fp8_t<__bf16, 128>(kp, s, cap_pre, sink);
     }
-    if (dtype == 0) return kp.d == 64 ? launch_kvcache_t<_Float16, 64>(kp, s, cap_pre) : launch_kvcache_t<_Float16, 128>(kp, s, cap_pre);
-    return kp.d == 64 ? launch_kvcache_t<__bf16, 64>(kp, s, cap_pre) : launch_kvcache_t<__bf16, 128>(kp, s, cap_pre);
+    if (dtype == 0) return kp.d == 64 ? launch_kvcache_t<_Float16, 64>(kp, s, cap_pre, sink) : launch_kvcache_t<_Float16, 128>(kp, s, cap_pre, sink);
+    return kp.d == 64 ? launch_kvcache_t<__bf16, 64>(kp, s, cap_pre, sink) : launch_kvcache_t<__bf16, 128>(kp, s, cap_pre, sink);
 }
 #endif  // FA_KVC_RAGGED_TU
 

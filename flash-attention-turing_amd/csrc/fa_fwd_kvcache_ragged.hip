@@ -131,7 +131,7 @@ void launch_ragged_attn(const KvcacheRaggedParams& rp, unsigned grid, hipStream_
 }
 
 template <typename T, int D, int ES>
-hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre) {
+hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre, const KvcacheSink& sink) {
     const KvcacheKernelParams& kp = rp.kp;
     const bool paged = kp.block_table != nullptr;
     if (kp.k_new != nullptr && rp.cu_kn != nullptr && rp.total_kn > 0) {
@@ -147,9 +147,14 @@ hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s,
         if (cap_pre > 0.f) {    // soft-capped scores: the attention kernels of fa_fwd_kvcache_softcap.hip between this file's append and combine
             const hipError_t e = launch_kvcache_ragged_softcap_attn(rp, cap_pre, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
             if (e != hipSuccess) return e;
+        } else if (sink.ptr != nullptr && kp.n_split == 1) {    // sinks, unsplit: the attention kernels of fa_fwd_kvcache_sink.hip
+            const hipError_t e = launch_kvcache_ragged_sink_attn(rp, sink, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
+            if (e != hipSuccess) return e;
         } else if (paged) launch_ragged_attn<T, D, true, ES>(rp, (unsigned)grid, s);
         else launch_ragged_attn<T, D, false, ES>(rp, (unsigned)grid, s);
         if (kp.n_split > 1) {
+            // (sinks: the combine of fa_fwd_kvcache_sink.hip, which adds the sink as one more term of the merge)
+            if (sink.ptr != nullptr) return launch_kvcache_ragged_sink_combine(rp, sink, std::is_same_v<T, _Float16> ? 0 : 1, s);
             const int64_t rows_per_block = kKvcCombineThreads / (D / 8);
             hipLaunchKernelGGL((fa_kvcache_combine_ragged_kernel<T, D>), dim3((unsigned)((kp.rows_total + rows_per_block - 1) / rows_per_block)),
                                dim3(kKvcCombineThreads), 0, s, rp);
@@ -159,8 +164,8 @@ hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s,
 }
 
 template <typename T, int D>
-hipError_t launch_kvcache_ragged_es(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre) {
-    return rp.kp.cache_fp8 ? launch_kvcache_ragged_t<T, D, 1>(rp, s, cap_pre) : launch_kvcache_ragged_t<T, D, 2>(rp, s, cap_pre);
+hipError_t launch_kvcache_ragged_es(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre, const KvcacheSink& sink) {
+    return rp.kp.cache_fp8 ? launch_kvcache_ragged_t<T, D, 1>(rp, s, cap_pre, sink) : launch_kvcache_ragged_t<T, D, 2>(rp, s, cap_pre, sink);
 }
 
 }  // namespace
@@ -168,7 +173,7 @@ hipError_t launch_kvcache_ragged_es(const KvcacheRaggedParams& rp, hipStream_t s
 #ifndef FA_KVC_D256_TU      // (fa_fwd_kvcache_d256.hip includes this file for the templates above)
 // kp.seqlen_q = max_seqlen_q sizes the split exactly as the dense launcher does (kvcache_steps), so a forced split cuts the keys where the dense
 // call with seqlen_q = max_seqlen_q cuts them.
-hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t s, float cap_pre) {
+hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t s, float cap_pre, KvcacheSink sink) {
     KvcacheKernelParams& kp = rp.kp;
     kp.n_row_tiles = (int32_t)(((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
     kp.rows_total = (int64_t)kp.h * rp.total_q;
@@ -179,8 +184,8 @@ hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStrea
     if (kp.split_keys <= 0) kp.split_keys = kKvcStep;
     if (kp.n_split > 1) kp.ws_lse = kp.ws_o + (int64_t)kp.n_split * kp.rows_total * kp.d;
     if (kp.d == 256) return launch_kvcache_ragged_d256(rp, dtype, s, cap_pre);
-    if (dtype == 0) return kp.d == 64 ? launch_kvcache_ragged_es<_Float16, 64>(rp, s, cap_pre) : launch_kvcache_ragged_es<_Float16, 128>(rp, s, cap_pre);
-    return kp.d == 64 ? launch_kvcache_ragged_es<__bf16, 64>(rp, s, cap_pre) : launch_kvcache_ragged_es<__bf16, 128>(rp, s, cap_pre);
+    if (dtype == 0) return kp.d == 64 ? launch_kvcache_ragged_es<_Float16, 64>(rp, s, cap_pre, sink) : launch_kvcache_ragged_es<_Float16, 128>(rp, s, cap_pre, sink);
+    return kp.d == 64 ? launch_kvcache_ragged_es<__bf16, 64>(rp, s, cap_pre, sink) : launch_kvcache_ragged_es<__bf16, 128>(rp, s, cap_pre, sink);
 }
 #endif  // FA_KVC_D256_TU
 

@@ -163,8 +163,15 @@ constexpr int kKvcStep = 32;    // keys of one wave step (the split granularity)
 // counts the compact grid's tile slots in place of b x row tiles; -1: the dense call
 int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_t requested, int64_t total_q = -1);   // key splits of a launch (>= 1)
 int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split, int64_t total_q = -1);
+// Attention sinks (fa_fwd_kvcache_sink.hip, fa_kvcache_options_v6.sinks): query head hq has the logit ptr[hq * stride] (fp32, device memory,
+// natural-log units of the final scores) in the softmax denominator; ptr = NULL: off.
+struct KvcacheSink {
+    const float* ptr;
+    int64_t stride;             // in elements
+};
 // cap_pre > 0: soft-capped scores (below) - the attention launch goes to fa_fwd_kvcache_softcap.hip, the append and the combine stay
-hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t stream, float cap_pre = 0.f);
+// sink.ptr != NULL: attention sinks (below) - an unsplit attention launch and the combine of a split one go to fa_fwd_kvcache_sink.hip
+hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t stream, float cap_pre = 0.f, KvcacheSink sink = KvcacheSink{nullptr, 0});
 
 // Ragged query batches (fa_fwd_kvcache_ragged.hip, fa_kvcache_options_v4): q / o are packed (total_q, h, d), sequence i owns rows cu_q[i] ..
 // cu_q[i + 1] - 1 and is tiled on its own (packed row r = t * h_ratio + j in tiles of kKvcRows from the sequence's first row), k_new / v_new are
@@ -182,7 +189,7 @@ struct KvcacheRaggedParams {
 };
 // tile slots per KV head of a ragged launch: min(ceil(total_q * h_ratio / kKvcRows) + b, b * tiles(max_seqlen_q)); *compact says which
 int64_t kvcache_ragged_slots(const KvcacheKernelParams& kp, int64_t total_q, int32_t* compact);
-hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t stream, float cap_pre = 0.f);
+hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t stream, float cap_pre = 0.f, KvcacheSink sink = KvcacheSink{nullptr, 0});
 
 // Soft-capped scores (fa_fwd_kvcache_softcap.hip, fa_kvcache_options_v5.softcap > 0): score = softcap * tanh(q . k * softmax_scale / softcap).
 // The kernels are kvcache_attn with SOFTCAP = true and read kp.scale = softcap, kp.scale_log2e = softcap * log2(e) (the host puts the cap where
@@ -200,6 +207,25 @@ struct KvcacheRaggedSoftcapParams {
 };
 hipError_t launch_kvcache_softcap_attn(const KvcacheKernelParams& kp, float pre, int dtype, unsigned grid, hipStream_t stream);
 hipError_t launch_kvcache_ragged_softcap_attn(const KvcacheRaggedParams& rp, float pre, int dtype, unsigned grid, hipStream_t stream);
+
+// Attention sinks (fa_fwd_kvcache_sink.hip): out = sum_j exp(s_j - M) v_j / (sum_j exp(s_j - M) + exp(sink - M)) with M = max(max_j s_j, sink), and
+// the LSE includes the sink.  Unsplit (n_split = 1): the kernels are kvcache_attn with SINK = true, which adds the term in the per-row epilogue;
+// as with the soft cap one sliding-window instantiation serves plain, causal and windowed calls.  Split: the attention launch is the one of the
+// call without sinks - same kernels, same partial planes - and the sink combine adds the term once per row as one more part of the merge.  The
+// sink travels in blocks of their own and not in KvcacheKernelParams: the kernarg segment of every other kernel stays what it was.  The four
+// launchers take kp / rp as the dense / ragged launcher finished them; sinks with a soft cap or at head_dim 256 are refused by the C ABI.
+struct KvcacheSinkParams {
+    KvcacheKernelParams kp;
+    KvcacheSink sink;
+};
+struct KvcacheRaggedSinkParams {
+    KvcacheRaggedParams rp;
+    KvcacheSink sink;
+};
+hipError_t launch_kvcache_sink_attn(const KvcacheKernelParams& kp, const KvcacheSink& sink, int dtype, unsigned grid, hipStream_t stream);
+hipError_t launch_kvcache_ragged_sink_attn(const KvcacheRaggedParams& rp, const KvcacheSink& sink, int dtype, unsigned grid, hipStream_t stream);
+hipError_t launch_kvcache_sink_combine(const KvcacheKernelParams& kp, const KvcacheSink& sink, int dtype, hipStream_t stream);
+hipError_t launch_kvcache_ragged_sink_combine(const KvcacheRaggedParams& rp, const KvcacheSink& sink, int dtype, hipStream_t stream);
 
 // Rotary embedding on a decode call (fa_kvcache_rotary.hip, fa_kvcache_options_v3).  One fused launch takes the place of the append: it
 // rotates k_new into the cache, copies / quantises v_new, and writes the rotated q into `q_image`, a contiguous (b, seqlen_q, h, d) buffer of

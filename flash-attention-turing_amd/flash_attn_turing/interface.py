@@ -163,6 +163,24 @@ def _check_scale_and_cap(softmax_scale, softcap):
     return softmax_scale, softcap
 
 
+def _check_sinks(sinks, q, softcap):
+    """sinks: a 1-D tensor (nheads,) on q's device, float32 or q's dtype, any stride; not with a soft cap, not at head_dim 256.  Returns it as
+    float32 (q's dtype is widened with a torch op: exact, asynchronous, capturable)."""
+    if not isinstance(sinks, torch.Tensor):
+        raise ValueError(f"sinks must be None or a tensor of shape (nheads,), got {type(sinks).__name__}")
+    if sinks.dtype != torch.float32 and sinks.dtype != q.dtype:
+        raise ValueError(f"sinks must be float32 or have q's dtype ({q.dtype}), got {sinks.dtype}")
+    if sinks.dim() != 1 or sinks.shape[0] != q.shape[-2]:
+        raise ValueError(f"sinks must have shape (nheads,) = ({q.shape[-2]},): one logit per query head, got {tuple(sinks.shape)}")
+    if sinks.device != q.device:
+        raise ValueError(f"sinks must be on q's device ({q.device}), got {sinks.device}")
+    if softcap != 0.0:
+        raise ValueError("sinks together with softcap > 0 are not supported")
+    if q.shape[-1] == 256:
+        raise ValueError("sinks at head_dim 256 are not supported: flash_attn_with_kvcache has sinks at head_dim 64 and 128")
+    return sinks if sinks.dtype == torch.float32 else sinks.float()
+
+
 def _check_kvcache_head_dim(q):
     """decode over a KV cache has head_dim 64, 128 and 256 (fwd / bwd / varlen_*: 64 and 128)"""
     if q.shape[-1] not in (64, 128, 256):
@@ -217,7 +235,7 @@ def _check_ragged(q, k_cache, k, v, cache_seqlens, block_table, k_descale, v_des
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, causal=False, num_splits=0, return_softmax_lse=False, *,
                             block_table=None, window_size=(-1, -1), k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None,
                             rotary_interleaved=True, cu_seqlens_q=None, max_seqlen_q=None, cu_seqlens_k_new=None, softmax_scale=None,
-                            softcap=0.0):
+                            softcap=0.0, sinks=None):
     """Decode attention over a KV cache (upstream flash-attn's ``flash_attn_with_kvcache`` conventions; forward only).
 
     q: (batch, seqlen_q, nheads, d); k_cache, v_cache: (batch, seqlen_cache, nheads_k, d), any batch / row / head strides (used in place).
@@ -329,8 +347,28 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     O and LSE NaN, but a raw score of +inf caps to +softcap - it is finite and the row is no longer NaN - and a raw score of -inf caps to
     -softcap - the key is no longer dropped.  A bool, 0, a negative value, NaN, inf or a non-number as softmax_scale, and a bool, a
     negative value, NaN, inf or a non-number as softcap: ValueError.
+
+    Attention sinks: sinks (keyword, optional; ``sinks`` of transformers / the gpt-oss reference, ``s_aux`` of vLLM's flash-attn): a 1-D tensor
+    (nheads,) on q's device, any stride, float32 or q's dtype (widened to float32 with a torch op: exact, no synchronisation,
+    graph-capturable).  sinks[h] is one learned logit of QUERY head h in the units of the final scores - after softmax_scale and k_descale;
+    it is never scaled.  It joins the softmax denominator and contributes no value: with the visible scores s_j of a row and
+    M = max(max_j s_j, sinks[h]), in fp32 math ``out = sum_j exp(s_j - M) v_j / (sum_j exp(s_j - M) + exp(sinks[h] - M))`` and
+    ``lse = M + log(sum_j exp(s_j - M) + exp(sinks[h] - M))``.  The returned LSE INCLUDES the sink, so ``exp(s_j - lse)`` are the
+    probabilities actually used (they sum to less than 1; the rest sits on the sink).  The maximum covers the sink: a sink far above every
+    score gives out near 0 and lse near sinks[h] without overflow, one far below gives the call without sinks.  The values are read on the
+    device like the descales: no synchronisation, and a captured call replays with the sink values then in memory.  A row that sees no key
+    has O = 0 and LSE = sinks[h] exactly (the sink holds all the mass); under sinks[h] = -inf it is dead as ever, O = 0, LSE = 0.
+    sinks[h] = -inf for every head gives the call without sinks bit for bit, out and lse, for every num_splits.  A NaN sink makes the rows
+    of its head NaN in O and LSE and leaves the other heads' bits alone; +inf breaks the precondition (unspecified result, nothing read or
+    written out of bounds); the NaN / +inf score rules above are unchanged.  Everything above carries over: block_table and the clamping of
+    table entries, GQA / MQA (the sink belongs to the query head), fp16 / bf16, head_dim 64 / 128, causal, window_size, num_splits (the
+    split count and the workspace do not depend on sinks), the FP8 cache (k_descale does not touch the sink, v_descale stays in the final
+    normalisation), softmax_scale, rotary (its own launch in front of attention), cu_seqlens_q (sequence i of a ragged sink call equals the
+    dense sink call on it alone, bit for bit, under the split rule above), paged == contiguous bit for bit, determinism per split count,
+    what is never read.  Not supported, a ValueError: sinks together with softcap > 0, and sinks at head_dim 256.  Also ValueErrors: a
+    sinks of the wrong rank, length, device or dtype, or a non-tensor.
     """
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v)):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v, sinks if isinstance(sinks, torch.Tensor) else None)):
         raise RuntimeError("flash_attn_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
     if (k is None) != (v is None):
         raise ValueError("k and v must both be given or both be None")
@@ -341,6 +379,11 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     softmax_scale, softcap = _check_scale_and_cap(softmax_scale, softcap)
     # (the third overload of the extension only when one of the two is given: every other call resolves as it always did)
     extra = dict(softmax_scale=softmax_scale, softcap=softcap) if softmax_scale is not None or softcap != 0.0 else {}
+    # (sinks: the extension's function of its own, which continues the third overload's arguments; every call without sinks goes where it always went)
+    fwd_kvcache = _C.fwd_kvcache
+    if sinks is not None:
+        extra = dict(extra, sinks=_check_sinks(sinks, q, softcap))
+        fwd_kvcache = _C.fwd_kvcache_sinks
     if cu_seqlens_q is None:
         if cu_seqlens_k_new is not None:
             raise ValueError("cu_seqlens_k_new given without cu_seqlens_q (packed k / v belong to a ragged call)")
@@ -350,14 +393,14 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
         _check_kvcache_head_dim(q)
         if isinstance(cache_seqlens, int):
             cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=q.device)
-        out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right,
+        out, lse = fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right,
                                   k_descale=k_descale, v_descale=v_descale, rotary_cos=rotary_cos, rotary_sin=rotary_sin, rotary_interleaved=rotary_interleaved, **extra)
         return (out, lse) if return_softmax_lse else out
     b = _check_ragged(q, k_cache, k, v, cache_seqlens, block_table, k_descale, v_descale, rotary_cos, rotary_sin, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new)
     _check_kvcache_head_dim(q)
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
-    out, lse = _C.fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right,
+    out, lse = fwd_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, bool(causal), int(num_splits), block_table, left, right,
                               k_descale=k_descale, v_descale=v_descale, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=int(max_seqlen_q),
                               cu_seqlens_k_new=cu_seqlens_k_new, **extra)
     return (out, lse) if return_softmax_lse else out

@@ -222,7 +222,7 @@ typedef struct fa_kvcache_params {
 
 /* Options of a decode call that fa_kvcache_params does not carry (its layout is fixed; the _ex entry points below take both).  Same ABI 4
  * header rule (FA_PARAMS_INIT): a zeroed struct means the plain call, and every later option arrived as optional fields appended after these
- * (the 8-bit cache, the rotary embedding on append, ragged query batches, and the softmax scale and softcap of fa_kvcache_options_v5, below).  A NULL options pointer is the same as a zeroed struct.
+ * (the 8-bit cache, the rotary embedding on append, ragged query batches, the softmax scale and softcap of fa_kvcache_options_v5, and the attention sinks of fa_kvcache_options_v6, below).  A NULL options pointer is the same as a zeroed struct.
  * Sliding window (upstream flash-attn's window_size; is_local = 0: no window, the two sizes are not read).  Key j of sequence i (valid
  * length L_i as above) is visible to query t when
  *     L_i - seqlen_q + t - window_size_left <= j <= L_i - seqlen_q + t + window_size_right,
@@ -422,6 +422,65 @@ typedef struct fa_kvcache_options_v5 {      /* FA_PARAMS_INIT(o); then fa_..._ex
     int64_t reserved[2];        /* 0 */
 } fa_kvcache_options_v5;
 
+/* Attention sinks (FA_HAS_KVCACHE_SINKS; `sinks` of transformers / the gpt-oss reference, `s_aux` of vLLM's flash-attn): fa_kvcache_options_v6
+ * below is fa_kvcache_options_v5 with optional fields appended; the _ex entry points accept exactly the six sizes (20, 72, 112, 144, 168, 200
+ * bytes), and a v6 struct with a zeroed tail is a v5 call: same kernels, split, workspace and bits.  FA_ABI_VERSION is unchanged.
+ *   sinks: NULL = off.  Otherwise fp32 device memory, 4-byte aligned (else FA_ERR_BAD_STRIDE), one logit per QUERY head: head hq reads
+ *   sinks[hq * sinks_stride] (elements; any value, 0 broadcasts one logit).  The logit is in the units of the final scores - behind softmax_scale
+ *   and k_descale, natural-log - and is never scaled.  It joins the softmax denominator and contributes no value: with the visible scores s_j
+ *   of a row and M = max(max_j s_j, sink), in fp32 math
+ *       o = sum_j exp(s_j - M) v_j / (sum_j exp(s_j - M) + exp(sink - M)),   lse = M + log(sum_j exp(s_j - M) + exp(sink - M)).
+ *   The returned lse INCLUDES the sink, so exp(s_j - lse) are the probabilities actually used (they sum to less than 1: the rest sits on the
+ *   sink).  The maximum covers the sink: a sink far above every score gives o near 0 and lse near the sink without overflow, one far below
+ *   gives the call without sinks.  The values are read on the device like the descales: no synchronisation, and a captured call replays with
+ *   the values then in memory.
+ *   Rows that see no key: a finite sink holds all the mass, o = 0 and lse = the sink exactly; with a sink of -inf the row is dead as ever, o =
+ *   0, lse = 0.  A sink of -inf on every head gives the call without sinks bit for bit, o and lse, for every num_splits.  A NaN sink makes the
+ *   rows of its head NaN in o and lse and leaves the other heads' bits alone; +inf breaks the precondition: the result is unspecified, nothing
+ *   is read or written out of bounds.  The NaN / +inf score rules are unchanged.
+ * Everything stated above carries over: contiguous and paged layout and the clamping of table entries, GQA / MQA (packed row r of a KV head's
+ * tile belongs to query head kv_head * h_ratio + r % h_ratio), fp16 / bf16, head_dim 64 / 128, windows, causal, num_splits (the split count and
+ * the workspace do not depend on sinks: a split call runs the attention kernels of the call without sinks and a combine that adds the sink as
+ * one more term of the merge), the 8-bit cache (k_descale does not touch the sink, v_descale stays in the final normalisation), softmax_scale,
+ * rotary (a launch of its own in front of attention), ragged batches (sequence i of a ragged sink call equals the dense sink call on it alone,
+ * bit for bit, under the split rule above), paged == contiguous bit for bit, determinism per split count, what is never read.  Plain, causal and
+ * windowed unsplit sink calls are all served by the window kernels (an unbounded window is the plain call).
+ * Not supported, FA_ERR_BAD_SHAPE with the field named by fa_last_error: sinks together with softcap > 0 (no model has both), and sinks at d =
+ * 256.  A non-zero `reserved2` is FA_ERR_BAD_ABI (a newer caller's field this library does not know).  Errors of fa_kvcache_params and of the
+ * older option fields come first, then those of sinks, then reserved2.
+ * sizeof is 200: the sizes 169 .. 192 and 256 are pinned as FA_ERR_BAD_ABI by callers' tests of the v5 library, and 200 is the next multiple of
+ * 8 that clears them; the two reserved words are the room that leaves. */
+#define FA_HAS_KVCACHE_SINKS 1
+typedef struct fa_kvcache_options_v6 {      /* FA_PARAMS_INIT(o); then fa_..._ex(&p, (const fa_kvcache_options*)&o, ...) */
+    uint32_t struct_size;       /* sizeof(fa_kvcache_options_v6) */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    int32_t is_local;           /* the fields of fa_kvcache_options_v5, same offsets */
+    int32_t window_size_left;
+    int32_t window_size_right;
+    int32_t cache_dtype;
+    const float* k_descale;
+    const float* v_descale;
+    int64_t k_descale_batch_stride, k_descale_head_stride;
+    int64_t v_descale_batch_stride, v_descale_head_stride;
+    const void* rotary_cos;
+    const void* rotary_sin;
+    int64_t rotary_row_stride;
+    int32_t seqlen_ro;
+    int32_t rotary_dim;
+    int32_t rotary_interleaved;
+    int32_t reserved_;
+    const int32_t* cu_seqlens_q;
+    const int32_t* cu_seqlens_k_new;
+    int64_t total_q;
+    int64_t total_k_new;
+    float softmax_scale;
+    float softcap;
+    int64_t reserved[2];        /* 0 */
+    const float* sinks;         /* optional: NULL = off; (h,) fp32 on the device, one logit per query head */
+    int64_t sinks_stride;       /* elements between consecutive heads' logits */
+    int64_t reserved2[2];       /* 0 */
+} fa_kvcache_options_v6;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -480,10 +539,10 @@ int fa_run_mha_fwd_kvcache(const fa_kvcache_params* params, void* stream);
 int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* params);
 /* Key splits the launch of these params would use, workspace fields included (NULL / 0 -> 1).  Host-only.  Negative = error code. */
 int32_t fa_kvcache_num_splits(const fa_kvcache_params* params);
-/* The same three with options (fa_kvcache_options / _v2 / _v3 / _v4 / _v5 above; NULL = the plain calls).  Their presence is how a caller detects the window.
+/* The same three with options (fa_kvcache_options / _v2 / _v3 / _v4 / _v5 / _v6 above; NULL = the plain calls).  Their presence is how a caller detects the window.
  * Options are validated before anything is launched: a bad header is FA_ERR_BAD_ABI, a window size below -1 FA_ERR_BAD_SHAPE, an unknown
  * cache_dtype or a descale without FA_CACHE_FP8_E4M3 FA_ERR_BAD_DTYPE, an 8-bit cache view that breaks the alignment rule FA_ERR_BAD_STRIDE,
- * the rotary fields as listed with fa_kvcache_options_v3, the ragged fields with _v4, softmax_scale / softcap with _v5.  With rotary, fa_kvcache_num_splits_ex answers for the workspace behind the image
+ * the rotary fields as listed with fa_kvcache_options_v3, the ragged fields with _v4, softmax_scale / softcap with _v5, sinks with _v6.  With rotary, fa_kvcache_num_splits_ex answers for the workspace behind the image
  * (a workspace that cannot hold the image is FA_ERR_BAD_SHAPE there as in the launch). */
 int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* params, const fa_kvcache_options* options, void* stream);
 int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);

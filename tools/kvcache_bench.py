@@ -39,6 +39,14 @@ medians.
 (B, B2) so that the spread of one thing measured twice in the same run stands next to A / B; interleaved, medians.  TB/s over the bytes
 both read.
 
+--sinks measures attention sinks instead, on a grid of its own - the gpt-oss shape: head_dim 64, 64 query heads over 8 KV heads, one query,
+b in {1, 8, 64} x L in {4k, 32k, 128k}, each point as the 128-token sliding-window layer (causal, window (127, 0)) and as the full-causal
+layer; with --kv-dtype fp8 over the 8-bit cache, with --paged P through a block table of P-row pages (the first P given).  Per point, the
+sink call (A) against the same call without sinks (B), B timed TWICE (B, B2) so that the spread of one thing measured twice in the same run
+stands next to A / B; interleaved, medians.  `hbm_bound` marks the points whose K/V read is at least 1 GB, `inside_scatter` whether A lies
+between B and B2.  With --baseline-library PATH it becomes an A / B of the sink call itself through the C ABI of this build (A) and of the
+library at PATH (B), e.g. tools/abl/libfa_sinkplain.so built with -DFA_KVC_SINK_PLAIN=1; A is timed twice; the outputs must agree bit for bit.
+
 --head-dim D (repeatable) replaces the grid's head dims (64, 128).  head_dim 256 exists for the decode call only: its points carry no fwd arm.
 --equal-bytes (with --head-dim 256) measures the head_dim-256 call against its yardstick instead: per grid point with one query, (A) the
 d-256 call; (B, B2) the d-128 call on the same b and L with twice the KV heads and twice the query heads - the same cache bytes (the very
@@ -331,6 +339,125 @@ def run_softcap_point(pt, softcap, scale, fp8, rounds):
                 tbps_capped=round(moved / (ms["capped"] * 1e-3) / 1e12, 3), tbps_plain=round(moved / (ms["plain"] * 1e-3) / 1e12, 3), max_abs_diff_to_plain=round(diff, 5))
 
 
+def sinks_grid(quick, lengths=None):
+    bs, ls = ((1, 8), (32768, 131072)) if quick else ((1, 8, 64), (4096, 32768, 131072))
+    if lengths:
+        ls = tuple(lengths)
+    for b, L, layer in itertools.product(bs, ls, ("window", "causal")):
+        if b * L <= 8 * 131072:                               # (64 x 128k is 17 GB of K / V: left out)
+            yield dict(b=b, h=64, h_k=8, d=64, L=L, seqlen_q=1, dtype=torch.bfloat16, layer=layer)
+
+
+def run_sinks_point(pt, fp8, page, rounds):
+    """(A) the sink call, (B, B2) the same call without sinks, twice; interleaved.  layer "window": causal with window (127, 0), "causal": full"""
+    dev = torch.device("cuda:0")
+    b, h, hk, d, L, sq, dt = pt["b"], pt["h"], pt["h_k"], pt["d"], pt["L"], pt["seqlen_q"], pt["dtype"]
+    window = (127, 0) if pt["layer"] == "window" else (-1, -1)
+    es = 1 if fp8 else 2
+    kv_bytes = 2 * b * L * hk * d * es
+    read_bytes = 2 * b * min(L, 127 + sq) * hk * d * es if pt["layer"] == "window" else kv_bytes
+    n = _rotation(kv_bytes, read_bytes)
+    cdt = torch.float8_e4m3fn if fp8 else dt
+    rows_c = page if page else L                              # a cache of (b, L, ...) rows, or a pool of b * L / page pages
+    nb = b * (L // page) if page else b
+
+    def mk():
+        c = torch.empty(nb, rows_c, hk, d, device=dev, dtype=cdt)
+        step = max(1, nb // b)
+        for i in range(0, nb, step):                          # (in pieces: bounds the temporaries of the conversion)
+            c[i:i + step] = torch.empty(min(step, nb - i), rows_c, hk, d, device=dev, dtype=dt).uniform_(-2, 2).to(cdt)
+        return c
+
+    caches = [(mk(), mk()) for _ in range(n)]
+    gen = torch.Generator(device="cpu").manual_seed(page or 1)
+    tables = [torch.randperm(nb, generator=gen).view(b, L // page).to(device=dev, dtype=torch.int32) for _ in range(n)] if page else None
+    q = torch.randn(b, sq, h, d, device=dev, dtype=dt)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    sinks = torch.empty(h, device=dev).uniform_(0.0, 6.0)
+    kw = dict(k_descale=torch.empty(b, hk, device=dev).uniform_(0.5, 2.0), v_descale=torch.empty(b, hk, device=dev).uniform_(0.5, 2.0)) if fp8 else {}
+    call = lambda i, **extra: F.flash_attn_with_kvcache(q, caches[i][0], caches[i][1], cache_seqlens=cs, causal=True, window_size=window,
+                                                        **(dict(block_table=tables[i]) if page else {}), **kw, **extra)
+    with_sinks = lambda i: call(i, sinks=sinks)
+    plain = lambda i: call(i)
+    diff = float((with_sinks(0).float() - plain(0).float()).abs().max())
+    torch.cuda.synchronize()
+    ms = _interleaved({"plain": plain, "sinks": with_sinks, "plain2": plain}, n, rounds)
+    if page:
+        p = capi.kvcache_params(q, caches[0][0], caches[0][1], torch.empty_like(q), torch.empty(b, h, sq, device=dev), cache_seqlens=cs, causal=True, block_table=tables[0])
+    else:
+        p = capi.kvcache_params(q, caches[0][0], caches[0][1], torch.empty_like(q), torch.empty(b, h, sq, device=dev), cache_seqlens=cs, causal=True)
+    opt = capi.kvcache_options(window, cache_dtype=capi.FA_CACHE_FP8_E4M3 if fp8 else 0, sinks=sinks)
+    ws = capi.kvcache_workspace_bytes(p, opt)
+    n_split = max(1, ws and capi.kvcache_num_splits(_with_ws(p, ws), opt))
+    del caches
+    torch.cuda.empty_cache()
+    lo, hi = sorted((ms["plain"], ms["plain2"]))
+    return dict(sinks=True, layer=pt["layer"], b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=sq, dtype=str(dt).replace("torch.", ""), kv="fp8" if fp8 else "16bit",
+                page_block_size=page or None, read_gb=round(read_bytes / 1e9, 4), hbm_bound=read_bytes >= 1e9, caches_rotated=n, n_split=n_split,
+                ms_sinks=round(ms["sinks"], 5), ms_plain=round(ms["plain"], 5), ms_plain_again=round(ms["plain2"], 5),
+                sinks_over_plain=round(ms["sinks"] / ms["plain"], 4), plain_again_over_plain=round(ms["plain2"] / ms["plain"], 4),
+                inside_scatter=bool(lo <= ms["sinks"] <= hi), tbps_sinks=round(read_bytes / (ms["sinks"] * 1e-3) / 1e12, 3),
+                tbps_plain=round(read_bytes / (ms["plain"] * 1e-3) / 1e12, 3), max_abs_diff_to_plain=round(diff, 5))
+
+
+def run_sinks_ab_point(pt, base, fp8, page, rounds):
+    """the sink call through this build's C ABI (A, A2: timed twice) and through the baseline library's (B), interleaved, on the same caches"""
+    dev = torch.device("cuda:0")
+    b, h, hk, d, L, sq, dt = pt["b"], pt["h"], pt["h_k"], pt["d"], pt["L"], pt["seqlen_q"], pt["dtype"]
+    window = (127, 0) if pt["layer"] == "window" else (-1, -1)
+    es = 1 if fp8 else 2
+    kv_bytes = 2 * b * L * hk * d * es
+    read_bytes = 2 * b * min(L, 127 + sq) * hk * d * es if pt["layer"] == "window" else kv_bytes
+    n = _rotation(kv_bytes, read_bytes)
+    cdt = torch.float8_e4m3fn if fp8 else dt
+    rows_c, nb = (page, b * (L // page)) if page else (L, b)
+    mk = lambda: torch.empty(nb, rows_c, hk, d, device=dev, dtype=torch.float16).uniform_(-2, 2).to(cdt)
+    caches = [(mk(), mk()) for _ in range(n)]
+    gen = torch.Generator(device="cpu").manual_seed(page or 1)
+    tables = [torch.randperm(nb, generator=gen).view(b, L // page).to(device=dev, dtype=torch.int32) if page else None for _ in range(n)]
+    q = torch.randn(b, sq, h, d, device=dev, dtype=dt)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    sinks = torch.empty(h, device=dev).uniform_(0.0, 6.0)
+    kds, vds = (torch.empty(b, hk, device=dev).uniform_(0.5, 2.0) for _ in range(2)) if fp8 else (None, None)
+    opt = capi.kvcache_options(window, cache_dtype=capi.FA_CACHE_FP8_E4M3 if fp8 else 0, k_descale=kds, v_descale=vds, sinks=sinks)
+    libs = {"A": capi.lib(), "B": base}
+    for lib in libs.values():
+        lib.fa_run_mha_fwd_kvcache_ex.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p, ctypes.c_void_p]
+        lib.fa_run_mha_fwd_kvcache_ex.restype = ctypes.c_int
+        lib.fa_kvcache_workspace_bytes_ex.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
+        lib.fa_kvcache_workspace_bytes_ex.restype = ctypes.c_int64
+    params = {}
+    for tag, lib in libs.items():
+        o, lse = torch.empty_like(q), torch.empty(b, h, sq, device=dev)
+        ps = [capi.kvcache_params(q, kc, vc, o, lse, cache_seqlens=cs, causal=True, **(dict(block_table=tables[i]) if page else {})) for i, (kc, vc) in enumerate(caches)]
+        ws = int(lib.fa_kvcache_workspace_bytes_ex(ctypes.byref(ps[0]), ctypes.byref(opt)))
+        assert ws >= 0, ws
+        buf = torch.empty(max(ws, 16) // 4, device=dev, dtype=torch.float32)
+        for p in ps:
+            p.workspace, p.workspace_bytes = (buf.data_ptr(), ws) if ws > 0 else (None, 0)
+        params[tag] = (ps, o, lse, buf, ws)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call(tag):
+        lib, ps = libs[tag], params[tag][0]
+        return lambda i: capi.check(lib.fa_run_mha_fwd_kvcache_ex(ctypes.byref(ps[i]), ctypes.byref(opt), stream))
+
+    fa, fb = call("A"), call("B")
+    fa(0), fb(0)
+    torch.cuda.synchronize()
+    same = torch.equal(params["A"][1].view(torch.int16), params["B"][1].view(torch.int16)) and torch.equal(params["A"][2].view(torch.int32), params["B"][2].view(torch.int32))
+    ms = _interleaved({"this": fa, "baseline": fb, "this2": fa}, n, rounds)
+    split = params["A"][4] > 0
+    del caches, params
+    torch.cuda.empty_cache()
+    lo, hi = sorted((ms["this"], ms["this2"]))
+    return dict(sinks=True, ab=True, layer=pt["layer"], b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=sq, dtype=str(dt).replace("torch.", ""), kv="fp8" if fp8 else "16bit",
+                page_block_size=page or None, read_gb=round(read_bytes / 1e9, 4), hbm_bound=read_bytes >= 1e9, caches_rotated=n, split=bool(split),
+                ms_this=round(ms["this"], 5), ms_baseline=round(ms["baseline"], 5), ms_this_again=round(ms["this2"], 5),
+                this_over_baseline=round(ms["this"] / ms["baseline"], 4), this_again_over_this=round(ms["this2"] / ms["this"], 4),
+                baseline_inside_scatter=bool(lo <= ms["baseline"] <= hi), bit_identical=bool(same))
+
+
 def torch_rotate(x, cos, sin, pos, interleaved):
     """the rotation with torch ops on x's device: x (b, s, heads, d), pos (b,) long - every row of sequence i at pos[i] (s = 1 here)"""
     rd = 2 * cos.shape[1]
@@ -593,6 +720,8 @@ def main():
     ap.add_argument("--softcap", type=float, default=None, metavar="CAP", help="the soft-capped call against the same call without the cap (timed twice); with --kv-dtype fp8 "
                                                                                "over the 8-bit cache")
     ap.add_argument("--softmax-scale", type=float, default=None, metavar="S", help="with --softcap: softmax_scale of both arms (default 1 / sqrt(head_dim))")
+    ap.add_argument("--sinks", action="store_true", help="attention sinks on the gpt-oss shape (d 64, h 64 / h_k 8, window (127, 0) and full causal): the sink call against the "
+                                                         "same call without sinks (timed twice); with --kv-dtype fp8 over the 8-bit cache, with --paged P through a block table")
     ap.add_argument("--head-dim", type=int, action="append", metavar="D", choices=(64, 128, 256), help="head dim(s) instead of the grid's 64 and 128 (256: the decode call only)")
     ap.add_argument("--equal-bytes", action="store_true", help="with --head-dim 256: the d-256 call against the d-128 call with twice the heads on the same buffers (timed twice)")
     a = ap.parse_args()
@@ -605,6 +734,12 @@ def main():
         if a.ragged and base is None:
             for line in run_ragged(a.quick, a.rounds):
                 print(json.dumps(line), flush=True)
+            return
+        if a.sinks:
+            for pt in sinks_grid(a.quick, a.length):
+                page = a.paged[0] if a.paged else 0
+                row = run_sinks_point(pt, a.kv_dtype == "fp8", page, a.rounds) if base is None else run_sinks_ab_point(pt, base, a.kv_dtype == "fp8", page, a.rounds)
+                print(json.dumps(row), flush=True)
             return
         for pt in grid(a.quick, a.length, a.head_dim):
             if a.equal_bytes:
