@@ -346,20 +346,22 @@ int fa_mha_varlen_bwd(const void* q, const void* k, const void* v, const void* o
     return fa_run_mha_bwd(&p, stream);
 }
 
-// The options pointer of the _ex entry points -> a zeroed fa_kvcache_options_v6 filled with what the caller's struct carries: struct_size says
-// which of the six layouts it is (fa_kvcache_options: the window alone; fa_kvcache_options_v2: plus the 8-bit cache fields;
+// The options pointer of the _ex entry points -> a zeroed fa_kvcache_options_v7 filled with what the caller's struct carries: struct_size says
+// which of the seven layouts it is (fa_kvcache_options: the window alone; fa_kvcache_options_v2: plus the 8-bit cache fields;
 // fa_kvcache_options_v3: plus the rotary fields; fa_kvcache_options_v4: plus the ragged-batch fields; fa_kvcache_options_v5: plus softmax_scale
-// and softcap; fa_kvcache_options_v6: plus the attention sinks).  NULL = all zero.
-static int import_kvcache_options(const fa_kvcache_options* user, fa_kvcache_options_v6& o) {
+// and softcap; fa_kvcache_options_v6: plus the attention sinks;
+// fa_kvcache_options_v7: plus the tree mask).  NULL = all zero.
+static int import_kvcache_options(const fa_kvcache_options* user, fa_kvcache_options_v7& o) {
     memset(&o, 0, sizeof(o));
     if (user == nullptr) return FA_OK;
     if (user->magic != FA_PARAMS_MAGIC)
         return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: no {struct_size, magic} header (FA_PARAMS_INIT); recompile against include/flash_attn_gfx950.h (ABI %d)", FA_ABI_VERSION);
     if (user->struct_size != sizeof(fa_kvcache_options) && user->struct_size != sizeof(fa_kvcache_options_v2) && user->struct_size != sizeof(fa_kvcache_options_v3) &&
-        user->struct_size != sizeof(fa_kvcache_options_v4) && user->struct_size != sizeof(fa_kvcache_options_v5) && user->struct_size != sizeof(fa_kvcache_options_v6))
-        return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: struct_size %u is none of sizeof(fa_kvcache_options) = %zu, sizeof(fa_kvcache_options_v2) = %zu, sizeof(fa_kvcache_options_v3) = %zu, sizeof(fa_kvcache_options_v4) = %zu, sizeof(fa_kvcache_options_v5) = %zu, sizeof(fa_kvcache_options_v6) = %zu - header / library mismatch",
+        user->struct_size != sizeof(fa_kvcache_options_v4) && user->struct_size != sizeof(fa_kvcache_options_v5) && user->struct_size != sizeof(fa_kvcache_options_v6) &&
+        user->struct_size != sizeof(fa_kvcache_options_v7))
+        return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: struct_size %u is none of sizeof(fa_kvcache_options) = %zu, sizeof(fa_kvcache_options_v2) = %zu, sizeof(fa_kvcache_options_v3) = %zu, sizeof(fa_kvcache_options_v4) = %zu, sizeof(fa_kvcache_options_v5) = %zu, sizeof(fa_kvcache_options_v6) = %zu, sizeof(fa_kvcache_options_v7) = %zu - header / library mismatch",
                     user->struct_size, sizeof(fa_kvcache_options), sizeof(fa_kvcache_options_v2), sizeof(fa_kvcache_options_v3), sizeof(fa_kvcache_options_v4),
-                    sizeof(fa_kvcache_options_v5), sizeof(fa_kvcache_options_v6));
+                    sizeof(fa_kvcache_options_v5), sizeof(fa_kvcache_options_v6), sizeof(fa_kvcache_options_v7));
     memcpy(&o, user, user->struct_size);
     if (o.cache_dtype != 0 && o.cache_dtype != FA_CACHE_FP8_E4M3)
         return fail(FA_ERR_BAD_DTYPE, "cache_dtype %d unsupported (0 = the dtype of q, %d = FA_CACHE_FP8_E4M3; e4m3fnuz and e5m2 caches are not supported)", o.cache_dtype,
@@ -371,7 +373,7 @@ static int import_kvcache_options(const fa_kvcache_options* user, fa_kvcache_opt
 
 // with_workspace = false: the `workspace` fields are not looked at (fa_kvcache_workspace_bytes)
 static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& kp, fa_kvcache_params& local, bool with_workspace,
-                        const fa_kvcache_options_v6& o) {
+                        const fa_kvcache_options_v7& o) {
     // the paged-cache fields are optional: a caller built before them passes struct_size = offsetof(block_table) and gets NULL / 0
     int rc = import_params(user, local, "fa_kvcache_params", offsetof(fa_kvcache_params, block_table));
     if (rc) return rc;
@@ -450,7 +452,7 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
 // fa_kvcache_options (NULL = none) -> the window fields of kp, normalised: right = 0 under causal, and a side that cannot bind is -1 (left >=
 // seqlen_cache - 1: lo_t <= L - 1 - left <= 0 for every row; right >= seqlen_q - 1: lim_t >= L for every row).  A window whose left side is
 // unbounded and whose right side is unbounded or the causal limit is exactly the plain call: is_local stays 0 (the plain kernels, split and bits).
-static int fill_kvcache_window(const fa_kvcache_options_v6& o, fa::KvcacheKernelParams& kp) {
+static int fill_kvcache_window(const fa_kvcache_options_v7& o, fa::KvcacheKernelParams& kp) {
     if (!o.is_local) return FA_OK;
     if (o.window_size_left < -1 || o.window_size_right < -1)
         return fail(FA_ERR_BAD_SHAPE, "window_size (%d, %d): each side must be >= -1 (-1 = unbounded)", o.window_size_left, o.window_size_right);
@@ -465,7 +467,7 @@ static int fill_kvcache_window(const fa_kvcache_options_v6& o, fa::KvcacheKernel
 
 // The rotary fields of the options (rotary_cos = rotary_sin = NULL: off, rp.cos stays NULL and nothing else is looked at) -> rp, validated.
 // The query-position rule is decided from what the caller stated (is_causal, a window other than (-1, -1)), not from the normalised window.
-static int fill_kvcache_rotary(const fa_kvcache_options_v6& o, const fa::KvcacheKernelParams& kp, fa::KvcacheRotaryParams& rp) {
+static int fill_kvcache_rotary(const fa_kvcache_options_v7& o, const fa::KvcacheKernelParams& kp, fa::KvcacheRotaryParams& rp) {
     memset(&rp, 0, sizeof(rp));
     if (o.rotary_cos == nullptr && o.rotary_sin == nullptr) return FA_OK;
     if (o.rotary_cos == nullptr || o.rotary_sin == nullptr) return fail(FA_ERR_BAD_SHAPE, "rotary_cos and rotary_sin must both be given or both be NULL");
@@ -488,7 +490,7 @@ static int fill_kvcache_rotary(const fa_kvcache_options_v6& o, const fa::Kvcache
 
 // The ragged-batch fields of the options (cu_seqlens_q = NULL: off, rg.cu_q stays NULL and only a stray cu_seqlens_k_new is looked at) -> rg,
 // validated.  rg.kp is left to the caller (the launch takes the finished kp).
-static int fill_kvcache_ragged(const fa_kvcache_options_v6& o, const fa::KvcacheKernelParams& kp, const fa::KvcacheRotaryParams& rp, fa::KvcacheRaggedParams& rg) {
+static int fill_kvcache_ragged(const fa_kvcache_options_v7& o, const fa::KvcacheKernelParams& kp, const fa::KvcacheRotaryParams& rp, fa::KvcacheRaggedParams& rg) {
     memset(&rg, 0, sizeof(rg));
     if (o.cu_seqlens_q == nullptr) {
         if (o.cu_seqlens_k_new != nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_k_new given without cu_seqlens_q (packed k_new / v_new belong to a ragged call)");
@@ -517,7 +519,7 @@ static int fill_kvcache_ragged(const fa_kvcache_options_v6& o, const fa::Kvcache
 // softmax_scale / softcap of the options -> kp.scale / kp.scale_log2e and cap_pre (0 = no cap: the kernels, hence the bits, of the call without
 // the two fields whenever the scale is the default's value).  With a cap the attention kernels of fa_fwd_kvcache_softcap.hip keep tanh(s * pre)
 // and read the cap where the scale was: scale = softcap, scale_log2e = softcap * log2(e), cap_pre = 2 log2(e) * softmax_scale / softcap.
-static int fill_kvcache_softcap(const fa_kvcache_options_v6& o, fa::KvcacheKernelParams& kp, float& cap_pre) {
+static int fill_kvcache_softcap(const fa_kvcache_options_v7& o, fa::KvcacheKernelParams& kp, float& cap_pre) {
     cap_pre = 0.f;
     if (!(o.softmax_scale >= 0.f) || isinf(o.softmax_scale))
         return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default 1 / sqrt(head_dim))", (double)o.softmax_scale);
@@ -540,7 +542,7 @@ static int fill_kvcache_softcap(const fa_kvcache_options_v6& o, fa::KvcacheKerne
 
 // The sink fields of the options (sinks = NULL: off, sink.ptr stays NULL and only the reserved words are looked at - a v6 struct
 // with a zeroed tail is a v5 call) -> sink, validated; behind every older field.  Sinks with a soft cap and sinks at head_dim 256 have no kernels.
-static int fill_kvcache_sinks(const fa_kvcache_options_v6& o, const fa::KvcacheKernelParams& kp, float cap_pre, fa::KvcacheSink& sink) {
+static int fill_kvcache_sinks(const fa_kvcache_options_v7& o, const fa::KvcacheKernelParams& kp, float cap_pre, fa::KvcacheSink& sink) {
     sink.ptr = nullptr;
     sink.stride = 0;
     if (o.sinks != nullptr) {
@@ -555,11 +557,41 @@ static int fill_kvcache_sinks(const fa_kvcache_options_v6& o, const fa::KvcacheK
     return FA_OK;
 }
 
+// The tree-mask fields of the options (tree_mask = NULL: off, tree.ptr stays NULL and only the reserved words are looked at - a v7 struct with a
+// zeroed tail is a v6 call) -> tree, validated; behind every older field.  The mask is a select of its own: it does not combine with the causal
+// limit, a window, a soft cap, sinks or rotary (a node's position is its depth, not its index: the engine rotates), has no head_dim-256 kernels,
+// and a row's word holds 64 draft tokens.  What the caller stated decides, not the normalised window.
+static int fill_kvcache_tree(const fa_kvcache_options_v7& o, const fa::KvcacheKernelParams& kp, const fa::KvcacheRotaryParams& rp, float cap_pre,
+                             const fa::KvcacheSink& sink, fa::KvcacheTree& tree) {
+    tree.ptr = nullptr;
+    tree.batch_stride = tree.row_stride = 0;
+    if (o.tree_mask != nullptr) {
+        if (((uintptr_t)o.tree_mask & 7) != 0) return fail(FA_ERR_BAD_STRIDE, "tree_mask must be 8-byte aligned (int64 words, one per query row)");
+        if (kp.is_causal) return fail(FA_ERR_BAD_SHAPE, "tree_mask together with is_causal is not supported (the lower-triangle mask is the causal call)");
+        if (o.is_local && (o.window_size_left != -1 || o.window_size_right != -1))
+            return fail(FA_ERR_BAD_SHAPE, "tree_mask together with window_size (%d, %d) is not supported", o.window_size_left, o.window_size_right);
+        if (cap_pre > 0.f) return fail(FA_ERR_BAD_SHAPE, "tree_mask together with softcap > 0 is not supported");
+        if (sink.ptr != nullptr) return fail(FA_ERR_BAD_SHAPE, "tree_mask together with sinks is not supported");
+        if (rp.cos != nullptr)
+            return fail(FA_ERR_BAD_SHAPE, "tree_mask together with rotary_cos / rotary_sin is not supported (a node's position is its depth: rotate before the call)");
+        if (kp.d == 256) return fail(FA_ERR_BAD_SHAPE, "tree_mask at head_dim d = 256 is not supported (d must be 64 or 128 with tree_mask)");
+        if (kp.seqlen_q > 64)
+            return fail(FA_ERR_BAD_SHAPE, "tree_mask: seqlen_q (ragged: max_seqlen_q) = %d exceeds 64, the draft tokens one mask word holds", kp.seqlen_q);
+        tree.ptr = o.tree_mask;
+        tree.batch_stride = o.tree_mask_batch_stride;
+        tree.row_stride = o.tree_mask_row_stride;
+    }
+    if (o.reserved3[0] != 0 || o.reserved3[1] != 0)
+        return fail(FA_ERR_BAD_ABI, "fa_kvcache_options_v7: reserved3 fields are not zero (a field of a newer header that this library does not know)");
+    return FA_OK;
+}
+
 // Params first, as before the options existed (their errors win), except that the cache tensors are checked under the cache dtype the
 // options state; then the options' own values.
 static int fill_kvcache_all(const fa_kvcache_params* user, const fa_kvcache_options* options, fa::KvcacheKernelParams& kp, fa_kvcache_params& local,
-                            fa_kvcache_options_v6& o, fa::KvcacheRotaryParams& rp, fa::KvcacheRaggedParams& rg, float& cap_pre, fa::KvcacheSink& sink, bool with_workspace) {
-    fa_kvcache_options_v6 none;
+                            fa_kvcache_options_v7& o, fa::KvcacheRotaryParams& rp, fa::KvcacheRaggedParams& rg, float& cap_pre, fa::KvcacheSink& sink, fa::KvcacheTree& tree,
+                            bool with_workspace) {
+    fa_kvcache_options_v7 none;
     memset(&none, 0, sizeof(none));
     const int orc = import_kvcache_options(options, o);
     char oerr[sizeof(g_err)];
@@ -574,7 +606,8 @@ static int fill_kvcache_all(const fa_kvcache_params* user, const fa_kvcache_opti
     if ((rc = fill_kvcache_rotary(o, kp, rp))) return rc;
     if ((rc = fill_kvcache_ragged(o, kp, rp, rg))) return rc;
     if ((rc = fill_kvcache_softcap(o, kp, cap_pre))) return rc;
-    return fill_kvcache_sinks(o, kp, cap_pre, sink);
+    if ((rc = fill_kvcache_sinks(o, kp, cap_pre, sink))) return rc;
+    return fill_kvcache_tree(o, kp, rp, cap_pre, sink, tree);
 }
 
 // Workspace left for the split partials of a rotary call once the image of the rotated q has taken its part; a workspace that cannot hold
@@ -591,12 +624,13 @@ static int64_t rotary_split_bytes(const fa::KvcacheKernelParams& kp, const fa_kv
 int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    fa_kvcache_options_v6 o;
+    fa_kvcache_options_v7 o;
     fa::KvcacheRotaryParams rp;
     fa::KvcacheRaggedParams rg;
     float cap_pre;
     fa::KvcacheSink sink;
-    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, false);
+    fa::KvcacheTree tree;
+    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, false);
     if (rc) return rc;
     if (kp.b == 0) return 0;
     const int64_t total_q = rg.cu_q != nullptr ? rg.total_q : -1;
@@ -607,12 +641,13 @@ int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* user, const fa_kv
 int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    fa_kvcache_options_v6 o;
+    fa_kvcache_options_v7 o;
     fa::KvcacheRotaryParams rp;
     fa::KvcacheRaggedParams rg;
     float cap_pre;
     fa::KvcacheSink sink;
-    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, true);
+    fa::KvcacheTree tree;
+    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, true);
     if (rc) return rc;
     if (kp.b == 0) return 1;
     int64_t avail = local.workspace != nullptr ? local.workspace_bytes : 0;
@@ -623,12 +658,13 @@ int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* user, const fa_kvcache
 int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* user, const fa_kvcache_options* options, void* stream) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    fa_kvcache_options_v6 o;
+    fa_kvcache_options_v7 o;
     fa::KvcacheRotaryParams rp;
     fa::KvcacheRaggedParams rg;
     float cap_pre;
     fa::KvcacheSink sink;
-    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, true);
+    fa::KvcacheTree tree;
+    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, true);
     if (rc) return rc;
     if (kp.b == 0) return FA_OK;
     int64_t avail = local.workspace != nullptr ? local.workspace_bytes : 0;
@@ -638,7 +674,7 @@ int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* user, const fa_kvcache_op
         kp.n_split = fa::kvcache_split(kp, avail, local.num_splits, rg.total_q);
         kp.ws_o = kp.n_split > 1 ? (float*)ws : nullptr;
         rg.kp = kp;
-        return hip_status(fa::launch_fwd_kvcache_ragged(rg, local.dtype, (hipStream_t)stream, cap_pre, sink), "fa_fwd_kvcache (ragged) launch");
+        return hip_status(fa::launch_fwd_kvcache_ragged(rg, local.dtype, (hipStream_t)stream, cap_pre, sink, tree), "fa_fwd_kvcache (ragged) launch");
     }
     if (rp.cos != nullptr) {
         // the fused rotary launch takes the place of the append: it writes the cache rows and the image of the rotated q at the head of the
@@ -654,7 +690,7 @@ int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* user, const fa_kvcache_op
     }
     kp.n_split = fa::kvcache_split(kp, avail, local.num_splits);
     kp.ws_o = kp.n_split > 1 ? (float*)ws : nullptr;
-    return hip_status(fa::launch_fwd_kvcache(kp, local.dtype, (hipStream_t)stream, cap_pre, sink), "fa_fwd_kvcache launch");
+    return hip_status(fa::launch_fwd_kvcache(kp, local.dtype, (hipStream_t)stream, cap_pre, sink, tree), "fa_fwd_kvcache launch");
 }
 
 int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* user) { return fa_kvcache_workspace_bytes_ex(user, nullptr); }

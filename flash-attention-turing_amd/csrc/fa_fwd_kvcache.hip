@@ -50,6 +50,12 @@ constexpr int kKvcCombineThreads = 256;
 #ifndef FA_KVC_FP8_KLOAD8
 #define FA_KVC_FP8_KLOAD8 0
 #endif
+// How the tree-mask kernels (TREE, fa_fwd_kvcache_tree.hip) select: 0 = every step tests the row's bits; 1 = a step that lies wholly in the
+// prefix (a wave-uniform comparison) takes the plain select and only the steps that overlap the draft tokens test bits.  Same values either
+// way.  The experiment switch of DESIGN.md 3.11; 0 ships.
+#ifndef FA_KVC_TREE_UNIFORM
+#define FA_KVC_TREE_UNIFORM 0
+#endif
 
 template <int D>
 struct KvcLds {
@@ -164,10 +170,18 @@ FA_DEV float kvc_tanh2(float y) { return __builtin_fmaf(-2.f, fast_rcp(fast_exp2
 // of the four waves and in front of inv and lse, as one more key whose score, in natural-log units, is the sink and whose V row is zero: the
 // 32-key loop does not know it.  A split launch (n_split > 1) writes the partials of the call without sinks - the sink combine of
 // fa_fwd_kvcache_sink.hip adds the term there.  SINK is a template parameter: the instantiations without it are the code they were.
-template <typename T, int D, bool CAUSAL, bool PAGED, bool LOCAL = false, int ES = 2, bool RAGGED = false, bool SOFTCAP = false, bool SINK = false>
+// TREE (fa_fwd_kvcache_tree.hip; `tree` is read only then): the last sq keys of a sequence are the draft tokens of a speculation tree, and query
+// row t sees key j < L iff j < base = L - sq or bit j - base of its 64-bit word (tree->ptr[batch * batch_stride + t * row_stride]; ragged:
+// ptr[(q0 + t) * row_stride]) is set.  The lane owns one query row for the whole split, so it loads the word once in the prologue, next to lim,
+// and the select of the step tests a bit where the plain kernels compare with lim.  Steps, splits, loads, softmax and epilogue are the code of
+// the plain kernels over [0, L): the lower-triangle mask gives the causal call's bits and the full mask the non-causal call's.  TREE is a
+// template parameter (with CAUSAL = LOCAL = SOFTCAP = SINK = false): the instantiations without it are the code they were.
+template <typename T, int D, bool CAUSAL, bool PAGED, bool LOCAL = false, int ES = 2, bool RAGGED = false, bool SOFTCAP = false, bool SINK = false,
+          bool TREE = false>
 FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams* rg = nullptr, float cap_pre = 0.f, const float* sinks = nullptr,
-                         int64_t sinks_stride = 0) {
+                         int64_t sinks_stride = 0, const KvcacheTree* tree = nullptr) {
     static_assert(ES == 1 || ES == 2, "cache elements are 16-bit (the dtype of q) or 8-bit (e4m3)");
+    static_assert(!TREE || (!CAUSAL && !LOCAL && !SOFTCAP && !SINK), "a tree mask stands alone: no causal limit, window, soft cap or sinks");
     constexpr int NC = D / 32;          // 16x16x32 MFMAs per 16 keys of S^T (d chunks)
     constexpr int NO = D / 16;          // O^T blocks of 16 columns
     constexpr int SLOTS = D * ES / 16;  // 16-byte slots per cache row
@@ -268,6 +282,13 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams
     if (CAUSAL && row_ok) lim = min(L, L - sq + t + 1);
     if (LOCAL && row_ok) lim = win_lim(t);
     const int lo = LOCAL ? win_lo(t) : 0;
+    // TREE: the row's mask word (a row past the tile sees nothing: lim = 0) and the first draft key; base < 0 where L < sq - the bits of keys
+    // below 0 are never asked for, since key >= 0
+    [[maybe_unused]] uint64_t tbits = 0;
+    [[maybe_unused]] const int tbase = L - sq;
+    if constexpr (TREE) {
+        if (row_ok) tbits = (uint64_t)(RAGGED ? tree->ptr[(q0 + t) * tree->row_stride] : tree->ptr[(int64_t)bidx * tree->batch_stride + (int64_t)t * tree->row_stride]);
+    }
     u32x4 qf[NC];
     {
         const char* qrow = (const char*)p.q_ptr + 2 * row_off(p.q, hq, t);
@@ -424,13 +445,22 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams
             }
         });
         float mx = -INFINITY;
+        [[maybe_unused]] const bool tree_step = !(TREE && FA_KVC_TREE_UNIFORM) || key0 + kKvcStep > tbase;     // (key0, tbase: wave-uniform)
         static_for<0, 2>([&](auto kb) {
             constexpr int b = decltype(kb)::value;
             static_for<0, 4>([&](auto rr) {
                 constexpr int r = decltype(rr)::value;
                 const int key = key0 + 16 * b + 4 * g + r;
                 if constexpr (SOFTCAP) s[b][r] = kvc_tanh2(s[b][r] * pre);
-                s[b][r] = (key < lim && (!LOCAL || key >= lo)) ? s[b][r] : -INFINITY;
+                if constexpr (TREE) {
+                    // u = key - tbase: the draft token this key is.  u < 0: the prefix; 0 <= u < sq <= 64: bit u; the count is masked to 0 .. 63 so
+                    // that the shift is defined for every u, and u >= sq only where key >= L, which lim (= L, 0 for a row past the tile) cuts
+                    const int u = key - tbase;
+                    if (tree_step) s[b][r] = (key < lim && (u < 0 || ((tbits >> (u & 63)) & 1) != 0)) ? s[b][r] : -INFINITY;
+                    else s[b][r] = key < lim ? s[b][r] : -INFINITY;
+                } else {
+                    s[b][r] = (key < lim && (!LOCAL || key >= lo)) ? s[b][r] : -INFINITY;
+                }
                 mx = fmaxf(mx, s[b][r]);
             });
         });
@@ -735,7 +765,7 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_fp8_kernel(const Kvcach
 }
 
 template <typename T, int D>
-hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre, const KvcacheSink& sink) {
+hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre, const KvcacheSink& sink, const KvcacheTree& tree) {
     const bool paged = kp.block_table != nullptr;
     if (kp.k_new != nullptr && kp.seqlen_new > 0) {
         const int64_t n = (int64_t)kp.b * kp.seqlen_new * kp.h_k * (D / 8);
@@ -748,6 +778,9 @@ hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, fl
         if (e != hipSuccess) return e;
     } else if (sink.ptr != nullptr && kp.n_split == 1) {    // sinks, unsplit: the attention kernels of fa_fwd_kvcache_sink.hip (a split call runs the kernels below)
         const hipError_t e = launch_kvcache_sink_attn(kp, sink, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
+        if (e != hipSuccess) return e;
+    } else if (tree.ptr != nullptr) {      // a tree mask: the attention kernels of fa_fwd_kvcache_tree.hip between this file's append and combine
+        const hipError_t e = launch_kvcache_tree_attn(kp, tree, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
         if (e != hipSuccess) return e;
     } else if (kp.is_local) {
         if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_fp8_local_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
@@ -770,7 +803,7 @@ hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, fl
 }
 
 template <typename T, int D>
-hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre, const KvcacheSink& sink) {
+hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre, const KvcacheSink& sink, const KvcacheTree& tree) {
     const bool paged = kp.block_table != nullptr;
     if (kp.k_new != nullptr && kp.seqlen_new > 0) {
         const int64_t n = (int64_t)kp.b * kp.seqlen_new * kp.h_k * (D / 8);
@@ -783,6 +816,9 @@ hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s, float 
         if (e != hipSuccess) return e;
     } else if (sink.ptr != nullptr && kp.n_split == 1) {    // sinks, unsplit: the attention kernels of fa_fwd_kvcache_sink.hip (a split call runs the kernels below)
         const hipError_t e = launch_kvcache_sink_attn(kp, sink, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
+        if (e != hipSuccess) return e;
+    } else if (tree.ptr != nullptr) {      // a tree mask: the attention kernels of fa_fwd_kvcache_tree.hip between this file's append and combine
+        const hipError_t e = launch_kvcache_tree_attn(kp, tree, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
         if (e != hipSuccess) return e;
     } else if (kp.is_local) {
         if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_local_kernel<T, D, true>), dim3((unsigned)grid), dim3(kKvcThreads), 0, s, kp);
@@ -864,7 +900,7 @@ int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split, 
     return o_bytes + l_bytes;
 }
 
-hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s, float cap_pre, KvcacheSink sink) {
+hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s, float cap_pre, KvcacheSink sink, KvcacheTree tree) {
     kp.n_row_tiles = (int32_t)(((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
     kp.rows_total = (int64_t)kp.b * kp.h * kp.seqlen_q;
     const int64_t steps = kvcache_steps(kp);
@@ -876,11 +912,11 @@ hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s, 
     }
     if (kp.d == 256) return launch_kvcache_d256(kp, dtype, s, cap_pre);
     if (kp.cache_fp8) {
-        if (dtype == 0) return kp.d == 64 ? launch_kvcache_fp8_t<_Float16, 64>(kp, s, cap_pre, sink) : launch_kvcache_fp8_t<_Float16, 128>(kp, s, cap_pre, sink);
-        return kp.d == 64 ? launch_kvcache_fp8_t<__bf16, 64>(kp, s, cap_pre, sink) : launch_kvcache_fp8_t<__bf16, 128>(kp, s, cap_pre, sink);
+        if (dtype == 0) return kp.d == 64 ? launch_kvcache_fp8_t<_Float16, 64>(kp, s, cap_pre, sink, tree) : launch_kvcache_fp8_t<_Float16, 128>(kp, s, cap_pre, sink, tree);
+        return kp.d == 64 ? launch_kvcache_fp8_t<__bf16, 64>(kp, s, cap_pre, sink, tree) : launch_kvcache_fp8_t<__bf16, 128>(kp, s, cap_pre, sink, tree);
     }
-    if (dtype == 0) return kp.d == 64 ? launch_kvcache_t<_Float16, 64>(kp, s, cap_pre, sink) : launch_kvcache_t<_Float16, 128>(kp, s, cap_pre, sink);
-    return kp.d == 64 ? launch_kvcache_t<__bf16, 64>(kp, s, cap_pre, sink) : launch_kvcache_t<__bf16, 128>(kp, s, cap_pre, sink);
+    if (dtype == 0) return kp.d == 64 ? launch_kvcache_t<_Float16, 64>(kp, s, cap_pre, sink, tree) : launch_kvcache_t<_Float16, 128>(kp, s, cap_pre, sink, tree);
+    return kp.d == 64 ? launch_kvcache_t<__bf16, 64>(kp, s, cap_pre, sink, tree) : launch_kvcache_t<__bf16, 128>(kp, s, cap_pre, sink, tree);
 }
 #endif  // FA_KVC_RAGGED_TU
 

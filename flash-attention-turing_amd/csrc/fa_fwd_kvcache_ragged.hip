@@ -131,7 +131,7 @@ void launch_ragged_attn(const KvcacheRaggedParams& rp, unsigned grid, hipStream_
 }
 
 template <typename T, int D, int ES>
-hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre, const KvcacheSink& sink) {
+hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre, const KvcacheSink& sink, const KvcacheTree& tree) {
     const KvcacheKernelParams& kp = rp.kp;
     const bool paged = kp.block_table != nullptr;
     if (kp.k_new != nullptr && rp.cu_kn != nullptr && rp.total_kn > 0) {
@@ -150,6 +150,9 @@ hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s,
         } else if (sink.ptr != nullptr && kp.n_split == 1) {    // sinks, unsplit: the attention kernels of fa_fwd_kvcache_sink.hip
             const hipError_t e = launch_kvcache_ragged_sink_attn(rp, sink, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
             if (e != hipSuccess) return e;
+        } else if (tree.ptr != nullptr) {      // a tree mask: the attention kernels of fa_fwd_kvcache_tree.hip
+            const hipError_t e = launch_kvcache_ragged_tree_attn(rp, tree, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
+            if (e != hipSuccess) return e;
         } else if (paged) launch_ragged_attn<T, D, true, ES>(rp, (unsigned)grid, s);
         else launch_ragged_attn<T, D, false, ES>(rp, (unsigned)grid, s);
         if (kp.n_split > 1) {
@@ -164,8 +167,8 @@ hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s,
 }
 
 template <typename T, int D>
-hipError_t launch_kvcache_ragged_es(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre, const KvcacheSink& sink) {
-    return rp.kp.cache_fp8 ? launch_kvcache_ragged_t<T, D, 1>(rp, s, cap_pre, sink) : launch_kvcache_ragged_t<T, D, 2>(rp, s, cap_pre, sink);
+hipError_t launch_kvcache_ragged_es(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre, const KvcacheSink& sink, const KvcacheTree& tree) {
+    return rp.kp.cache_fp8 ? launch_kvcache_ragged_t<T, D, 1>(rp, s, cap_pre, sink, tree) : launch_kvcache_ragged_t<T, D, 2>(rp, s, cap_pre, sink, tree);
 }
 
 }  // namespace
@@ -173,7 +176,7 @@ hipError_t launch_kvcache_ragged_es(const KvcacheRaggedParams& rp, hipStream_t s
 #ifndef FA_KVC_D256_TU      // (fa_fwd_kvcache_d256.hip includes this file for the templates above)
 // kp.seqlen_q = max_seqlen_q sizes the split exactly as the dense launcher does (kvcache_steps), so a forced split cuts the keys where the dense
 // call with seqlen_q = max_seqlen_q cuts them.
-hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t s, float cap_pre, KvcacheSink sink) {
+hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t s, float cap_pre, KvcacheSink sink, KvcacheTree tree) {
     KvcacheKernelParams& kp = rp.kp;
     kp.n_row_tiles = (int32_t)(((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
     kp.rows_total = (int64_t)kp.h * rp.total_q;
@@ -184,8 +187,8 @@ hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStrea
     if (kp.split_keys <= 0) kp.split_keys = kKvcStep;
     if (kp.n_split > 1) kp.ws_lse = kp.ws_o + (int64_t)kp.n_split * kp.rows_total * kp.d;
     if (kp.d == 256) return launch_kvcache_ragged_d256(rp, dtype, s, cap_pre);
-    if (dtype == 0) return kp.d == 64 ? launch_kvcache_ragged_es<_Float16, 64>(rp, s, cap_pre, sink) : launch_kvcache_ragged_es<_Float16, 128>(rp, s, cap_pre, sink);
-    return kp.d == 64 ? launch_kvcache_ragged_es<__bf16, 64>(rp, s, cap_pre, sink) : launch_kvcache_ragged_es<__bf16, 128>(rp, s, cap_pre, sink);
+    if (dtype == 0) return kp.d == 64 ? launch_kvcache_ragged_es<_Float16, 64>(rp, s, cap_pre, sink, tree) : launch_kvcache_ragged_es<_Float16, 128>(rp, s, cap_pre, sink, tree);
+    return kp.d == 64 ? launch_kvcache_ragged_es<__bf16, 64>(rp, s, cap_pre, sink, tree) : launch_kvcache_ragged_es<__bf16, 128>(rp, s, cap_pre, sink, tree);
 }
 #endif  // FA_KVC_D256_TU
 

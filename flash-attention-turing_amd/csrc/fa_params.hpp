@@ -169,9 +169,18 @@ struct KvcacheSink {
     const float* ptr;
     int64_t stride;             // in elements
 };
+// Tree attention mask (fa_fwd_kvcache_tree.hip, fa_kvcache_options_v7.tree_mask): query row t of sequence i reads the 64-bit word
+// ptr[i * batch_stride + t * row_stride] (ragged: ptr[(packed row) * row_stride]); bit u = "sees draft token u", the key L_i - sq_i + u.
+// ptr = NULL: off.
+struct KvcacheTree {
+    const int64_t* ptr;
+    int64_t batch_stride, row_stride;   // in elements
+};
 // cap_pre > 0: soft-capped scores (below) - the attention launch goes to fa_fwd_kvcache_softcap.hip, the append and the combine stay
 // sink.ptr != NULL: attention sinks (below) - an unsplit attention launch and the combine of a split one go to fa_fwd_kvcache_sink.hip
-hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t stream, float cap_pre = 0.f, KvcacheSink sink = KvcacheSink{nullptr, 0});
+// tree.ptr != NULL: a tree mask (below) - the attention launch goes to fa_fwd_kvcache_tree.hip, the append and the combine stay
+hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t stream, float cap_pre = 0.f, KvcacheSink sink = KvcacheSink{nullptr, 0},
+                              KvcacheTree tree = KvcacheTree{nullptr, 0, 0});
 
 // Ragged query batches (fa_fwd_kvcache_ragged.hip, fa_kvcache_options_v4): q / o are packed (total_q, h, d), sequence i owns rows cu_q[i] ..
 // cu_q[i + 1] - 1 and is tiled on its own (packed row r = t * h_ratio + j in tiles of kKvcRows from the sequence's first row), k_new / v_new are
@@ -189,7 +198,8 @@ struct KvcacheRaggedParams {
 };
 // tile slots per KV head of a ragged launch: min(ceil(total_q * h_ratio / kKvcRows) + b, b * tiles(max_seqlen_q)); *compact says which
 int64_t kvcache_ragged_slots(const KvcacheKernelParams& kp, int64_t total_q, int32_t* compact);
-hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t stream, float cap_pre = 0.f, KvcacheSink sink = KvcacheSink{nullptr, 0});
+hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t stream, float cap_pre = 0.f, KvcacheSink sink = KvcacheSink{nullptr, 0},
+                                     KvcacheTree tree = KvcacheTree{nullptr, 0, 0});
 
 // Soft-capped scores (fa_fwd_kvcache_softcap.hip, fa_kvcache_options_v5.softcap > 0): score = softcap * tanh(q . k * softmax_scale / softcap).
 // The kernels are kvcache_attn with SOFTCAP = true and read kp.scale = softcap, kp.scale_log2e = softcap * log2(e) (the host puts the cap where
@@ -226,6 +236,22 @@ hipError_t launch_kvcache_sink_attn(const KvcacheKernelParams& kp, const Kvcache
 hipError_t launch_kvcache_ragged_sink_attn(const KvcacheRaggedParams& rp, const KvcacheSink& sink, int dtype, unsigned grid, hipStream_t stream);
 hipError_t launch_kvcache_sink_combine(const KvcacheKernelParams& kp, const KvcacheSink& sink, int dtype, hipStream_t stream);
 hipError_t launch_kvcache_ragged_sink_combine(const KvcacheRaggedParams& rp, const KvcacheSink& sink, int dtype, hipStream_t stream);
+
+// Tree attention masks (fa_fwd_kvcache_tree.hip): the kernels are kvcache_attn with TREE = true - the plain (non-causal) body over the steps
+// [0, L) whose select tests a bit of the row's mask word for the last sq keys.  They launch the attention kernel alone, split or not, on the grid
+// the dense / ragged launcher computed: the append in front, the partial planes and the combine behind are the unchanged ones, so the split count
+// and the workspace do not know about the mask.  The mask travels in blocks of their own and not in KvcacheKernelParams: the kernarg segment of
+// every other kernel stays what it was.  A tree mask with causal, a window, a soft cap, sinks, rotary or head_dim 256 is refused by the C ABI.
+struct KvcacheTreeParams {
+    KvcacheKernelParams kp;
+    KvcacheTree tree;
+};
+struct KvcacheRaggedTreeParams {
+    KvcacheRaggedParams rp;
+    KvcacheTree tree;
+};
+hipError_t launch_kvcache_tree_attn(const KvcacheKernelParams& kp, const KvcacheTree& tree, int dtype, unsigned grid, hipStream_t stream);
+hipError_t launch_kvcache_ragged_tree_attn(const KvcacheRaggedParams& rp, const KvcacheTree& tree, int dtype, unsigned grid, hipStream_t stream);
 
 // Rotary embedding on a decode call (fa_kvcache_rotary.hip, fa_kvcache_options_v3).  One fused launch takes the place of the append: it
 // rotates k_new into the cache, copies / quantises v_new, and writes the rotated q into `q_image`, a contiguous (b, seqlen_q, h, d) buffer of

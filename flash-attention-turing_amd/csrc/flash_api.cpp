@@ -273,14 +273,16 @@ std::vector<at::Tensor> mha_varlen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
 // batch (fa_kvcache_options_v4) - q is packed (total_q, h, d), k_new / v_new (total_new, h_k, d) under cu_seqlens_k_new, max_seqlen_q sizes the
 // launch; out comes back packed and lse as (h, total_q).  The cu_seqlens tensors stay on the device like cache_seqlens.  softmax_scale (None = 1 /
 // sqrt(d)) and softcap (0 = off) are the two host scalars of fa_kvcache_options_v5; they are validated by the library.  sinks (float32 (nheads,), any stride): the
-// attention sinks of fa_kvcache_options_v6, one logit per query head, read on the device like the descales.
+// attention sinks of fa_kvcache_options_v6, one logit per query head, read on the device like the descales.  tree_mask (int64 (batch, seqlen_q), ragged
+// (total_q,), any strides): the tree attention mask of fa_kvcache_options_v7, one word per query row, read on the device in place.
 std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, c10::optional<at::Tensor> k_new_,
                                         c10::optional<at::Tensor> v_new_, c10::optional<at::Tensor> cache_seqlens_, bool is_causal,
                                         int64_t num_splits, c10::optional<at::Tensor> block_table_, int64_t window_size_left,
                                         int64_t window_size_right, c10::optional<at::Tensor> k_descale_, c10::optional<at::Tensor> v_descale_,
                                         c10::optional<at::Tensor> rotary_cos_, c10::optional<at::Tensor> rotary_sin_, bool rotary_interleaved,
                                         c10::optional<at::Tensor> cu_seqlens_q_, int64_t max_seqlen_q, c10::optional<at::Tensor> cu_seqlens_k_new_,
-                                        c10::optional<double> softmax_scale, double softcap, c10::optional<at::Tensor> sinks_) {
+                                        c10::optional<double> softmax_scale, double softcap, c10::optional<at::Tensor> sinks_,
+                                        c10::optional<at::Tensor> tree_mask_) {
     const bool ragged = cu_seqlens_q_.has_value();
     at::Tensor cu_seqlens_q, cu_seqlens_k_new;
     auto cu_tensor = [&](const at::Tensor& t, const char* name) {
@@ -387,7 +389,7 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
         p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr(); p.seqlen_new = (int32_t)(ragged ? std::min<int64_t>(k_new.size(1), seqlen_cache) : k_new.size(1));
         p.k_new_stride = strides4(k_new); p.v_new_stride = strides4(v_new);
     }
-    fa_kvcache_options_v6 opt;
+    fa_kvcache_options_v7 opt;
     FA_PARAMS_INIT(opt);
     // (rounded once to fp32; 0 means "the default" in the C ABI, so a given scale that is or rounds to 0 is refused here)
     TORCH_CHECK(!softmax_scale.has_value() || (std::isfinite(*softmax_scale) && (float)*softmax_scale > 0.f && std::isfinite((float)*softmax_scale)),
@@ -442,7 +444,21 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
         TORCH_CHECK(sinks.dim() == 1 && sinks.size(0) == num_heads, "sinks must have shape [num_heads]");
         opt.sinks = sinks.data_ptr<float>(); opt.sinks_stride = num_heads > 1 ? sinks.stride(0) : 1;
     }
-    const fa_kvcache_options* opts = (opt.is_local || fp8 || rotary_cos.defined() || ragged || scaled || sinks.defined()) ? (const fa_kvcache_options*)&opt : nullptr;
+    at::Tensor tree_mask;
+    if (tree_mask_.has_value()) {
+        tree_mask = *tree_mask_;
+        check_same_device(q, tree_mask, "tree_mask");
+        TORCH_CHECK(tree_mask.scalar_type() == torch::kInt64, "tree_mask must be an int64 tensor");
+        if (ragged) {
+            TORCH_CHECK(tree_mask.dim() == 1 && tree_mask.size(0) == total_q, "tree_mask must have shape [total_q] with cu_seqlens_q");
+            opt.tree_mask_row_stride = tree_mask.stride(0);
+        } else {
+            TORCH_CHECK(tree_mask.dim() == 2 && tree_mask.size(0) == batch_size && tree_mask.size(1) == seqlen_q, "tree_mask must have shape [batch_size, seqlen_q]");
+            opt.tree_mask_batch_stride = tree_mask.stride(0); opt.tree_mask_row_stride = tree_mask.stride(1);
+        }
+        opt.tree_mask = tree_mask.data_ptr<int64_t>();
+    }
+    const fa_kvcache_options* opts = (opt.is_local || fp8 || rotary_cos.defined() || ragged || scaled || sinks.defined() || tree_mask.defined()) ? (const fa_kvcache_options*)&opt : nullptr;
     at::Tensor workspace;
     const int64_t ws_bytes = fa_kvcache_workspace_bytes_ex(&p, opts);
     if (ws_bytes < 0) check_status((int)ws_bytes);
@@ -513,7 +529,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              c10::optional<at::Tensor> k_descale, c10::optional<at::Tensor> v_descale, c10::optional<at::Tensor> rotary_cos, c10::optional<at::Tensor> rotary_sin,
              bool rotary_interleaved) {
               return mha_fwd_kvcache(q, k_cache, v_cache, k_new, v_new, cache_seqlens, is_causal, num_splits, block_table, window_size_left, window_size_right, k_descale,
-                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, c10::nullopt, 0, c10::nullopt, c10::nullopt, 0.0, c10::nullopt);
+                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, c10::nullopt, 0, c10::nullopt, c10::nullopt, 0.0, c10::nullopt, c10::nullopt);
           },
           "Decode forward over a KV cache (in-place append of k / v, split-KV attention)", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
@@ -526,7 +542,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              c10::optional<at::Tensor> k_descale, c10::optional<at::Tensor> v_descale, c10::optional<at::Tensor> rotary_cos, c10::optional<at::Tensor> rotary_sin,
              bool rotary_interleaved, c10::optional<at::Tensor> cu_seqlens_q, int64_t max_seqlen_q, c10::optional<at::Tensor> cu_seqlens_k_new) {
               return mha_fwd_kvcache(q, k_cache, v_cache, k_new, v_new, cache_seqlens, is_causal, num_splits, block_table, window_size_left, window_size_right, k_descale,
-                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new, c10::nullopt, 0.0, c10::nullopt);
+                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new, c10::nullopt, 0.0, c10::nullopt, c10::nullopt);
           },
           "The same with a ragged query batch: packed q / k / v under cu_seqlens_q / cu_seqlens_k_new", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
@@ -541,7 +557,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              bool rotary_interleaved, c10::optional<at::Tensor> cu_seqlens_q, int64_t max_seqlen_q, c10::optional<at::Tensor> cu_seqlens_k_new,
              c10::optional<double> softmax_scale, double softcap) {
               return mha_fwd_kvcache(q, k_cache, v_cache, k_new, v_new, cache_seqlens, is_causal, num_splits, block_table, window_size_left, window_size_right, k_descale,
-                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new, softmax_scale, softcap, c10::nullopt);
+                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new, softmax_scale, softcap, c10::nullopt, c10::nullopt);
           },
           "The same with a softmax scale other than 1 / sqrt(head_dim) and / or soft-capped scores", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
@@ -552,13 +568,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("softmax_scale") = py::none(), py::arg("softcap") = 0.0);
     // Attention sinks: the same arguments continued by `sinks`.  A function of its own and not a fourth overload of fwd_kvcache - the overload set
     // of that name is what its callers resolve against, and it stays the three signatures it was: a call without sinks never comes here.
-    m.def("fwd_kvcache_sinks", &mha_fwd_kvcache, "fwd_kvcache with attention sinks: one float32 logit per query head in the softmax denominator", py::arg("q"),
+    m.def("fwd_kvcache_sinks",
+          [](at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, c10::optional<at::Tensor> k_new, c10::optional<at::Tensor> v_new, c10::optional<at::Tensor> cache_seqlens,
+             bool is_causal, int64_t num_splits, c10::optional<at::Tensor> block_table, int64_t window_size_left, int64_t window_size_right,
+             c10::optional<at::Tensor> k_descale, c10::optional<at::Tensor> v_descale, c10::optional<at::Tensor> rotary_cos, c10::optional<at::Tensor> rotary_sin,
+             bool rotary_interleaved, c10::optional<at::Tensor> cu_seqlens_q, int64_t max_seqlen_q, c10::optional<at::Tensor> cu_seqlens_k_new,
+             c10::optional<double> softmax_scale, double softcap, c10::optional<at::Tensor> sinks) {
+              return mha_fwd_kvcache(q, k_cache, v_cache, k_new, v_new, cache_seqlens, is_causal, num_splits, block_table, window_size_left, window_size_right, k_descale,
+                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new, softmax_scale, softcap, sinks, c10::nullopt);
+          },
+          "fwd_kvcache with attention sinks: one float32 logit per query head in the softmax denominator", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
           py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("block_table") = py::none(), py::arg("window_size_left") = -1,
           py::arg("window_size_right") = -1, py::kw_only(), py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none(),
           py::arg("rotary_cos") = py::none(), py::arg("rotary_sin") = py::none(), py::arg("rotary_interleaved") = true,
           py::arg("cu_seqlens_q") = py::none(), py::arg("max_seqlen_q") = 0, py::arg("cu_seqlens_k_new") = py::none(),
           py::arg("softmax_scale") = py::none(), py::arg("softcap") = 0.0, py::arg("sinks") = py::none());
+    // Tree attention masks: the same arguments continued by `tree_mask`, again on a function of its own - fwd_kvcache keeps its three overloads and
+    // fwd_kvcache_sinks its signature, and a call without tree_mask never comes here.
+    m.def("fwd_kvcache_tree", &mha_fwd_kvcache, "fwd_kvcache with a tree attention mask: one int64 word per query row over the last seqlen_q keys", py::arg("q"),
+          py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
+          py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("block_table") = py::none(), py::arg("window_size_left") = -1,
+          py::arg("window_size_right") = -1, py::kw_only(), py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none(),
+          py::arg("rotary_cos") = py::none(), py::arg("rotary_sin") = py::none(), py::arg("rotary_interleaved") = true,
+          py::arg("cu_seqlens_q") = py::none(), py::arg("max_seqlen_q") = 0, py::arg("cu_seqlens_k_new") = py::none(),
+          py::arg("softmax_scale") = py::none(), py::arg("softcap") = 0.0, py::arg("sinks") = py::none(), py::arg("tree_mask") = py::none());
     m.def("attn_autograd", &attn_autograd, "differentiable forward (C++ autograd node over fwd / bwd)");
     m.def("attn_varlen_autograd", &attn_varlen_autograd, "differentiable packed forward (C++ autograd node over varlen_fwd / varlen_bwd)");
     m.def("abi_version", []() { return fa_abi_version(); });

@@ -111,6 +111,12 @@ class KvcacheOptionsV6(_Params):
     _fields_ = KvcacheOptionsV5._fields_ + [("sinks", _vp), ("sinks_stride", ctypes.c_int64), ("reserved2", ctypes.c_int64 * 2)]
 
 
+class KvcacheOptionsV7(_Params):
+    """fa_kvcache_options_v7: fa_kvcache_options_v6 plus the tree mask - an int64 device pointer, its batch and row strides in elements - and two reserved words"""
+    _fields_ = KvcacheOptionsV6._fields_ + [("tree_mask", _vp), ("tree_mask_batch_stride", ctypes.c_int64), ("tree_mask_row_stride", ctypes.c_int64),
+                                            ("reserved3", ctypes.c_int64 * 2)]
+
+
 FA_CACHE_FP8_E4M3 = 1
 
 
@@ -150,7 +156,7 @@ def lib():
         L.fa_kvcache_workspace_bytes.restype = ctypes.c_int64
         L.fa_kvcache_num_splits.argtypes = [ctypes.POINTER(KvcacheParams)]
         L.fa_kvcache_num_splits.restype = ctypes.c_int32
-        _op = ctypes.c_void_p                       # fa_kvcache_options, _v2 .. _v6 (told apart by struct_size)
+        _op = ctypes.c_void_p                       # fa_kvcache_options, _v2 .. _v7 (told apart by struct_size)
         L.fa_run_mha_fwd_kvcache_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op, _vp]
         L.fa_run_mha_fwd_kvcache_ex.restype = ctypes.c_int
         L.fa_kvcache_workspace_bytes_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op]
@@ -382,19 +388,20 @@ def _kvcache_params_ragged(q, k_cache, v_cache, o, lse, cache_seqlens, k_new, v_
 
 
 def kvcache_options(window_size=(-1, -1), cache_dtype=0, k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, *,
-                    cu_seqlens_q=None, cu_seqlens_k_new=None, total_q=0, total_k_new=0, softmax_scale=None, softcap=None, sinks=None):
+                    cu_seqlens_q=None, cu_seqlens_k_new=None, total_q=0, total_k_new=0, softmax_scale=None, softcap=None, sinks=None, tree_mask=None):
     """fa_kvcache_options with a sliding window (left, right); (-1, -1) gives a zeroed struct (no window).  With cache_dtype
     (FA_CACHE_FP8_E4M3) or a descale (float32 (b, h_k) torch tensors, any strides) the struct is fa_kvcache_options_v2; with rotary_cos /
     rotary_sin ((seqlen_ro, rotary_dim / 2) torch tensors of q's dtype with one row stride) it is fa_kvcache_options_v3; with cu_seqlens_q /
     cu_seqlens_k_new (int32 (b + 1,) torch tensors) and the packed row counts total_q / total_k_new it is fa_kvcache_options_v4; with softmax_scale or
     softcap (Python floats; None = not given) it is fa_kvcache_options_v5; with sinks (a float32 (nheads,) torch tensor, any stride) it is
-    fa_kvcache_options_v6."""
-    v6 = sinks is not None
+    fa_kvcache_options_v6; with tree_mask (an int64 torch tensor, (b, seqlen_q) or, ragged, (total_q,), any strides) it is fa_kvcache_options_v7."""
+    v7 = tree_mask is not None
+    v6 = v7 or sinks is not None
     v5 = v6 or softmax_scale is not None or softcap is not None
     v4 = v5 or cu_seqlens_q is not None or cu_seqlens_k_new is not None
     v3 = rotary_cos is not None or rotary_sin is not None
     v2 = v3 or cache_dtype != 0 or k_descale is not None or v_descale is not None
-    o = KvcacheOptionsV6() if v6 else KvcacheOptionsV5() if v5 else KvcacheOptionsV4() if v4 else KvcacheOptionsV3() if v3 else KvcacheOptionsV2() if v2 else KvcacheOptions()
+    o = KvcacheOptionsV7() if v7 else KvcacheOptionsV6() if v6 else KvcacheOptionsV5() if v5 else KvcacheOptionsV4() if v4 else KvcacheOptionsV3() if v3 else KvcacheOptionsV2() if v2 else KvcacheOptions()
     if v4:
         o.cu_seqlens_q = None if cu_seqlens_q is None else cu_seqlens_q.data_ptr()
         o.cu_seqlens_k_new = None if cu_seqlens_k_new is None else cu_seqlens_k_new.data_ptr()
@@ -403,8 +410,11 @@ def kvcache_options(window_size=(-1, -1), cache_dtype=0, k_descale=None, v_desca
     if v5:
         o.softmax_scale = 0.0 if softmax_scale is None else float(softmax_scale)
         o.softcap = 0.0 if softcap is None else float(softcap)
-    if v6:
+    if v6 and sinks is not None:
         o.sinks, o.sinks_stride = sinks.data_ptr(), sinks.stride(0)
+    if v7:
+        o.tree_mask = tree_mask.data_ptr()
+        o.tree_mask_batch_stride, o.tree_mask_row_stride = (0, tree_mask.stride(0)) if tree_mask.dim() == 1 else (tree_mask.stride(0), tree_mask.stride(1))
     left, right = window_size
     if (left, right) != (-1, -1):
         o.is_local, o.window_size_left, o.window_size_right = 1, int(left), int(right)

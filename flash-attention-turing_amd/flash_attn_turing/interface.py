@@ -181,6 +181,72 @@ def _check_sinks(sinks, q, softcap):
     return sinks if sinks.dtype == torch.float32 else sinks.float()
 
 
+def _check_tree_mask(tree_mask, q, causal, window, softcap, sinks, rotary_cos, rotary_sin, cu_seqlens_q, max_seqlen_q):
+    """tree_mask: an int64 tensor on q's device, (batch, seqlen_q) or, ragged, (total_q,), any strides; at most 64 query rows per sequence; not with
+    causal, a window, a soft cap, sinks, rotary or head_dim 256"""
+    if not isinstance(tree_mask, torch.Tensor):
+        raise ValueError(f"tree_mask must be None or an int64 tensor, got {type(tree_mask).__name__}")
+    if tree_mask.dtype != torch.int64:
+        raise ValueError(f"tree_mask must be an int64 tensor (one 64-bit word per query row), got {tree_mask.dtype}")
+    if cu_seqlens_q is None:
+        if q.dim() == 4 and tuple(tree_mask.shape) != tuple(q.shape[:2]):
+            raise ValueError(f"tree_mask must have shape (batch, seqlen_q) = {tuple(q.shape[:2])}, got {tuple(tree_mask.shape)}")
+        sq = q.shape[1] if q.dim() == 4 else 0
+    else:
+        if q.dim() == 3 and tuple(tree_mask.shape) != (q.shape[0],):
+            raise ValueError(f"tree_mask must have shape (total_q,) = ({q.shape[0]},) with cu_seqlens_q, got {tuple(tree_mask.shape)}")
+        sq = max_seqlen_q if isinstance(max_seqlen_q, numbers.Integral) and not isinstance(max_seqlen_q, bool) else 0
+    if tree_mask.device != q.device:
+        raise ValueError(f"tree_mask must be on q's device ({q.device}), got {tree_mask.device}")
+    if causal:
+        raise ValueError("tree_mask together with causal=True is not supported (the lower-triangle mask is the causal call)")
+    if window != (-1, -1):
+        raise ValueError(f"tree_mask together with window_size {window} is not supported")
+    if softcap != 0.0:
+        raise ValueError("tree_mask together with softcap > 0 is not supported")
+    if sinks is not None:
+        raise ValueError("tree_mask together with sinks is not supported")
+    if rotary_cos is not None or rotary_sin is not None:
+        raise ValueError("tree_mask together with rotary_cos / rotary_sin is not supported: a node's position is its depth, not its index - rotate q and k before the call")
+    if q.shape[-1] == 256:
+        raise ValueError("tree_mask at head_dim 256 is not supported: flash_attn_with_kvcache has tree masks at head_dim 64 and 128")
+    if sq > 64:
+        raise ValueError(f"tree_mask: seqlen_q (ragged: max_seqlen_q) must be at most 64, the draft tokens one mask word holds, got {sq}")
+    return tree_mask
+
+
+def pack_tree_mask(mask):
+    """bool (..., sq, sq) -> int64 (..., sq), the ``tree_mask`` of flash_attn_with_kvcache: bit u of word t is mask[..., t, u] ("draft token t sees
+    draft token u"), sq <= 64; column 63 lands in the sign bit.  Torch ops only, on mask's device."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool:
+        raise ValueError(f"mask must be a bool tensor, got {getattr(mask, 'dtype', type(mask).__name__)}")
+    if mask.dim() < 2 or mask.shape[-1] != mask.shape[-2] or mask.shape[-1] > 64:
+        raise ValueError(f"mask must have shape (..., sq, sq) with sq <= 64, got {tuple(mask.shape)}")
+    sq = mask.shape[-1]
+    # (1 << 63 wraps to the sign bit in int64 arithmetic, and the bits are disjoint: the sum is their OR)
+    weights = torch.ones((), dtype=torch.int64, device=mask.device) << torch.arange(sq, dtype=torch.int64, device=mask.device)
+    return (mask.to(torch.int64) * weights).sum(dim=-1)
+
+
+def tree_mask_from_parents(parents):
+    """int (..., sq) -> int64 (..., sq): parents[..., t] is the index of draft token t's parent, -1 for a root, always < t (a forest in topological
+    order, as draft trees are built).  Word t has the bits of t's ancestors and of t itself.  Torch ops only, on parents' device: sq steps, each
+    ORs a parent's finished word into its child's."""
+    if not isinstance(parents, torch.Tensor) or parents.dtype.is_floating_point or parents.dtype.is_complex or parents.dtype == torch.bool:
+        raise ValueError(f"parents must be an integer tensor, got {getattr(parents, 'dtype', type(parents).__name__)}")
+    if parents.dim() < 1 or parents.shape[-1] > 64:
+        raise ValueError(f"parents must have shape (..., sq) with sq <= 64, got {tuple(parents.shape)}")
+    sq = parents.shape[-1]
+    par = parents.to(torch.int64)
+    one = torch.ones((), dtype=torch.int64, device=parents.device)
+    words = torch.zeros(par.shape, dtype=torch.int64, device=parents.device)
+    for t in range(sq):
+        p = par[..., t]
+        up = torch.gather(words, -1, p.clamp(0, max(t - 1, 0)).unsqueeze(-1)).squeeze(-1) if t > 0 else torch.zeros_like(p)
+        words[..., t] = torch.where((p >= 0) & (p < t), up, torch.zeros_like(up)) | (one << t)
+    return words
+
+
 def _check_kvcache_head_dim(q):
     """decode over a KV cache has head_dim 64, 128 and 256 (fwd / bwd / varlen_*: 64 and 128)"""
     if q.shape[-1] not in (64, 128, 256):
@@ -235,7 +301,7 @@ def _check_ragged(q, k_cache, k, v, cache_seqlens, block_table, k_descale, v_des
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, causal=False, num_splits=0, return_softmax_lse=False, *,
                             block_table=None, window_size=(-1, -1), k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None,
                             rotary_interleaved=True, cu_seqlens_q=None, max_seqlen_q=None, cu_seqlens_k_new=None, softmax_scale=None,
-                            softcap=0.0, sinks=None):
+                            softcap=0.0, sinks=None, tree_mask=None):
     """Decode attention over a KV cache (upstream flash-attn's ``flash_attn_with_kvcache`` conventions; forward only).
 
     q: (batch, seqlen_q, nheads, d); k_cache, v_cache: (batch, seqlen_cache, nheads_k, d), any batch / row / head strides (used in place).
@@ -367,6 +433,28 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     dense sink call on it alone, bit for bit, under the split rule above), paged == contiguous bit for bit, determinism per split count,
     what is never read.  Not supported, a ValueError: sinks together with softcap > 0, and sinks at head_dim 256.  Also ValueErrors: a
     sinks of the wrong rank, length, device or dtype, or a non-tensor.
+
+    Tree attention masks: tree_mask (keyword, optional; the draft trees of EAGLE / Medusa / SpecInfer, the tree-attention backend of vLLM, the
+    custom mask of SGLang and FlashInfer): an int64 tensor on q's device, any strides, (batch, seqlen_q), or (total_q,) with cu_seqlens_q
+    (entries past cu_seqlens_q[-1] are never read).  The sq_i query rows of sequence i are the nodes of a draft tree and the last sq_i keys
+    of the sequence - in the usual call the rows just appended through k / v - are their K / V.  With base_i = L_i - sq_i, query row t sees
+    key j iff 0 <= j < L_i and (j < base_i or bit j - base_i of tree_mask[i, t] is set): every node sees the whole cached prefix, and bit u
+    of row t means "draft token t sees draft token u".  ``pack_tree_mask`` builds the words from a bool (sq, sq) matrix and
+    ``tree_mask_from_parents`` from parent indices (ancestors plus self).  Bits at or above sq_i are ignored, and so are bits whose key
+    index would be negative (L_i < sq_i).  Bit 63 is the sign bit and an ordinary bit.  Any bit pattern is legal: it need not be a tree,
+    and the diagonal need not be set.  A row that sees no key is O = 0, LSE = 0, as everywhere else.  The mask is read on the device: no
+    synchronisation, and a captured call replays with the mask words then in memory, like lengths and descales.  seqlen_q (ragged:
+    max_seqlen_q) must be at most 64.  Two relations hold BIT FOR BIT in out and lse, for every num_splits: the lower-triangle mask (bit u
+    of row t set iff u <= t) gives the causal=True call, and the mask with bits 0 .. sq - 1 all set gives the causal=False call - the tree
+    kernels run the same steps over [0, L_i) and differ only in which scores they keep.  Everything above carries over: block_table and the
+    clamping of table entries, GQA / MQA (the query heads of a token share its mask word), fp16 / bf16, head_dim 64 / 128, the FP8 cache
+    and its descales, softmax_scale, num_splits (the split count and the workspace do not depend on the mask: they are those of the call
+    without it), cu_seqlens_q (sequence i of a ragged tree call equals the dense tree call on it alone, bit for bit, under the split rule
+    above), paged == contiguous bit for bit, determinism per split count, the NaN rules over the visible keys (a NaN K row that no row
+    sees leaves every row finite; V rows below L_i must be finite, as under causal), and what is never read.  Not supported, a ValueError:
+    tree_mask together with causal=True, with a window_size other than (-1, -1), with softcap > 0, with sinks, with rotary_cos /
+    rotary_sin (a node's position is its depth, not its index: the engine rotates), at head_dim 256, and with seqlen_q / max_seqlen_q
+    above 64.  Also ValueErrors: a tree_mask that is not a tensor, not int64, of the wrong rank or shape, or on another device.
     """
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v, sinks if isinstance(sinks, torch.Tensor) else None)):
         raise RuntimeError("flash_attn_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
@@ -384,6 +472,10 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     if sinks is not None:
         extra = dict(extra, sinks=_check_sinks(sinks, q, softcap))
         fwd_kvcache = _C.fwd_kvcache_sinks
+    # (tree_mask: likewise a function of its own, which continues the arguments of fwd_kvcache_sinks)
+    if tree_mask is not None:
+        extra = dict(extra, tree_mask=_check_tree_mask(tree_mask, q, causal, (left, right), softcap, sinks, rotary_cos, rotary_sin, cu_seqlens_q, max_seqlen_q))
+        fwd_kvcache = _C.fwd_kvcache_tree
     if cu_seqlens_q is None:
         if cu_seqlens_k_new is not None:
             raise ValueError("cu_seqlens_k_new given without cu_seqlens_q (packed k / v belong to a ragged call)")

@@ -222,7 +222,7 @@ typedef struct fa_kvcache_params {
 
 /* Options of a decode call that fa_kvcache_params does not carry (its layout is fixed; the _ex entry points below take both).  Same ABI 4
  * header rule (FA_PARAMS_INIT): a zeroed struct means the plain call, and every later option arrived as optional fields appended after these
- * (the 8-bit cache, the rotary embedding on append, ragged query batches, the softmax scale and softcap of fa_kvcache_options_v5, and the attention sinks of fa_kvcache_options_v6, below).  A NULL options pointer is the same as a zeroed struct.
+ * (the 8-bit cache, the rotary embedding on append, ragged query batches, the softmax scale and softcap of fa_kvcache_options_v5, the attention sinks of fa_kvcache_options_v6, and the tree mask of fa_kvcache_options_v7, below).  A NULL options pointer is the same as a zeroed struct.
  * Sliding window (upstream flash-attn's window_size; is_local = 0: no window, the two sizes are not read).  Key j of sequence i (valid
  * length L_i as above) is visible to query t when
  *     L_i - seqlen_q + t - window_size_left <= j <= L_i - seqlen_q + t + window_size_right,
@@ -481,6 +481,74 @@ typedef struct fa_kvcache_options_v6 {      /* FA_PARAMS_INIT(o); then fa_..._ex
     int64_t reserved2[2];       /* 0 */
 } fa_kvcache_options_v6;
 
+/* Tree attention masks (FA_HAS_KVCACHE_TREE_MASK; the draft trees of EAGLE / Medusa / SpecInfer, the tree-attention backend of vLLM, the custom
+ * mask of SGLang and FlashInfer): fa_kvcache_options_v7 below is fa_kvcache_options_v6 with optional fields appended; the _ex entry points accept
+ * exactly the seven sizes (20, 72, 112, 144, 168, 200, 240 bytes), and a v7 struct with a zeroed tail is a v6 call: same kernels, split,
+ * workspace and bits.  FA_ABI_VERSION is unchanged.
+ *   tree_mask: NULL = off.  Otherwise int64 device memory, 8-byte aligned (else FA_ERR_BAD_STRIDE), one word per query row: row t of sequence i
+ *   reads tree_mask[i * tree_mask_batch_stride + t * tree_mask_row_stride] (elements, any values); a ragged call (cu_seqlens_q) reads
+ *   tree_mask[r * tree_mask_row_stride] for packed row r and uses tree_mask_row_stride only; rows at or past cu_seqlens_q[b] are never read.
+ *   With L_i the valid length, sq_i the query rows of the sequence (seqlen_q; ragged: cu_seqlens_q[i + 1] - cu_seqlens_q[i]) and base_i = L_i -
+ *   sq_i, query row t sees key j iff 0 <= j < L_i and
+ *       j < base_i   or   bit (j - base_i) of the row's word is set.
+ *   Bit u of row t means "draft token t sees draft token u": the draft tokens are the last sq_i keys of the sequence, in the usual call the
+ *   rows just appended through k_new / v_new, and every row sees the whole prefix in front of them.  Bits at or above sq_i are ignored, and so
+ *   are bits whose key index would be negative (L_i < sq_i: the first draft token the cache holds is key 0 and bit sq_i - L_i).  Bit 63 is the
+ *   sign bit and an ordinary bit.  Any bit pattern is legal: it need not be a tree, and the diagonal need not be set.  A row that sees no key
+ *   (L_i = 0, or no prefix and no bit set) is o = 0, lse = 0, as everywhere else.  The words are read on the device like lengths and descales:
+ *   no synchronisation, and a captured call replays with the words then in memory.  seqlen_q (ragged: the max_seqlen_q it carries) must be at
+ *   most 64.
+ *   Two relations hold bit for bit, o and lse, for every num_splits: the lower-triangle mask (bit u of row t set iff u <= t) gives the
+ *   is_causal call, and the mask with bits 0 .. sq - 1 all set gives the call with neither.  The tree kernels are the plain attention body
+ *   over the same 32-key steps [0, L_i); only the select of a score differs.
+ * Everything stated above carries over: contiguous and paged layout and the clamping of table entries, GQA / MQA (the query heads of a token
+ * share its mask word: packed row r of a KV head's tile reads the word of token r / h_ratio), fp16 / bf16, head_dim 64 / 128, the 8-bit cache and
+ * its descales, softmax_scale, num_splits (the split count and the workspace do not depend on the mask: they are those of the call without it;
+ * append, partial planes and combine are the unchanged kernels), ragged batches (sequence i of a ragged tree call equals the dense tree call on
+ * it alone, bit for bit, under the split rule above), paged == contiguous bit for bit, determinism per split count, the NaN rules over the
+ * visible keys (a NaN or +inf score a row sees makes the row NaN; a key no row of a tile sees cannot reach its rows, whatever K holds there,
+ * while V rows below L_i are multiplied by a probability of 0 and must be finite), what is never read (cache rows at or past L_i, table entries
+ * of blocks past L_i, mask words of rows a sequence does not have).
+ * Not supported, FA_ERR_BAD_SHAPE with the field named by fa_last_error: tree_mask together with is_causal, with a window other than (-1, -1),
+ * with softcap > 0, with sinks, with rotary_cos / rotary_sin (a node's position is its depth, not its index: the engine rotates), at d = 256,
+ * and with seqlen_q / max_seqlen_q above 64.  A non-zero `reserved3` is FA_ERR_BAD_ABI (a newer caller's field this library does not know).
+ * Errors of fa_kvcache_params and of the older option fields come first, then those of tree_mask, then reserved3.
+ * sizeof is 240: the sizes 201 .. 232 and 256 are pinned as FA_ERR_BAD_ABI by callers' tests of the v6 library, and 240 is the next multiple of
+ * 8 that clears them; the two reserved words are the room that leaves. */
+#define FA_HAS_KVCACHE_TREE_MASK 1
+typedef struct fa_kvcache_options_v7 {      /* FA_PARAMS_INIT(o); then fa_..._ex(&p, (const fa_kvcache_options*)&o, ...) */
+    uint32_t struct_size;       /* sizeof(fa_kvcache_options_v7) */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    int32_t is_local;           /* the fields of fa_kvcache_options_v6, same offsets */
+    int32_t window_size_left;
+    int32_t window_size_right;
+    int32_t cache_dtype;
+    const float* k_descale;
+    const float* v_descale;
+    int64_t k_descale_batch_stride, k_descale_head_stride;
+    int64_t v_descale_batch_stride, v_descale_head_stride;
+    const void* rotary_cos;
+    const void* rotary_sin;
+    int64_t rotary_row_stride;
+    int32_t seqlen_ro;
+    int32_t rotary_dim;
+    int32_t rotary_interleaved;
+    int32_t reserved_;
+    const int32_t* cu_seqlens_q;
+    const int32_t* cu_seqlens_k_new;
+    int64_t total_q;
+    int64_t total_k_new;
+    float softmax_scale;
+    float softcap;
+    int64_t reserved[2];        /* 0 */
+    const float* sinks;
+    int64_t sinks_stride;
+    int64_t reserved2[2];       /* 0 */
+    const int64_t* tree_mask;   /* optional: NULL = off; (b, seqlen_q) int64 on the device, ragged: (total_q,); one word per query row */
+    int64_t tree_mask_batch_stride, tree_mask_row_stride;       /* elements; a ragged call uses the row stride only */
+    int64_t reserved3[2];       /* 0 */
+} fa_kvcache_options_v7;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -539,10 +607,10 @@ int fa_run_mha_fwd_kvcache(const fa_kvcache_params* params, void* stream);
 int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* params);
 /* Key splits the launch of these params would use, workspace fields included (NULL / 0 -> 1).  Host-only.  Negative = error code. */
 int32_t fa_kvcache_num_splits(const fa_kvcache_params* params);
-/* The same three with options (fa_kvcache_options / _v2 / _v3 / _v4 / _v5 / _v6 above; NULL = the plain calls).  Their presence is how a caller detects the window.
+/* The same three with options (fa_kvcache_options / _v2 / _v3 / _v4 / _v5 / _v6 / _v7 above; NULL = the plain calls).  Their presence is how a caller detects the window.
  * Options are validated before anything is launched: a bad header is FA_ERR_BAD_ABI, a window size below -1 FA_ERR_BAD_SHAPE, an unknown
  * cache_dtype or a descale without FA_CACHE_FP8_E4M3 FA_ERR_BAD_DTYPE, an 8-bit cache view that breaks the alignment rule FA_ERR_BAD_STRIDE,
- * the rotary fields as listed with fa_kvcache_options_v3, the ragged fields with _v4, softmax_scale / softcap with _v5, sinks with _v6.  With rotary, fa_kvcache_num_splits_ex answers for the workspace behind the image
+ * the rotary fields as listed with fa_kvcache_options_v3, the ragged fields with _v4, softmax_scale / softcap with _v5, sinks with _v6, tree_mask with _v7.  With rotary, fa_kvcache_num_splits_ex answers for the workspace behind the image
  * (a workspace that cannot hold the image is FA_ERR_BAD_SHAPE there as in the launch). */
 int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* params, const fa_kvcache_options* options, void* stream);
 int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);

@@ -47,6 +47,14 @@ stands next to A / B; interleaved, medians.  `hbm_bound` marks the points whose 
 between B and B2.  With --baseline-library PATH it becomes an A / B of the sink call itself through the C ABI of this build (A) and of the
 library at PATH (B), e.g. tools/abl/libfa_sinkplain.so built with -DFA_KVC_SINK_PLAIN=1; A is timed twice; the outputs must agree bit for bit.
 
+--tree N (N in 8, 32, 64) measures tree attention masks instead: per point of the grid, with seqlen_q = N in place of the grid's query counts,
+(A) the tree call under the binary-heap tree (parent (t - 1) // 2; the words from tree_mask_from_parents) against (B) the causal=True call of
+the same shape - the same steps over the same keys, a compare in place of the bit test - B timed TWICE (B, B2) so that the spread of one thing
+measured twice in the same run stands next to A / B; interleaved, medians; with --kv-dtype fp8 over the 8-bit cache.  `hbm_bound` marks the
+points whose K/V are at least 1 GB, `inside_scatter` whether A lies between B and B2.  With --baseline-library PATH it becomes an A / B of the
+tree call itself through the C ABI of this build (A, timed twice) and of the library at PATH (B), e.g. tools/abl/libfa_treeuniform.so built with
+-DFA_KVC_TREE_UNIFORM=1; the outputs must agree bit for bit.
+
 --head-dim D (repeatable) replaces the grid's head dims (64, 128).  head_dim 256 exists for the decode call only: its points carry no fwd arm.
 --equal-bytes (with --head-dim 256) measures the head_dim-256 call against its yardstick instead: per grid point with one query, (A) the
 d-256 call; (B, B2) the d-128 call on the same b and L with twice the KV heads and twice the query heads - the same cache bytes (the very
@@ -458,6 +466,106 @@ def run_sinks_ab_point(pt, base, fp8, page, rounds):
                 baseline_inside_scatter=bool(lo <= ms["baseline"] <= hi), bit_identical=bool(same))
 
 
+def tree_grid(quick, n_tree, lengths=None, head_dims=None):
+    """the grid's points with seqlen_q = n_tree, each (b, heads, d, L, dtype) once"""
+    seen = set()
+    for pt in grid(quick, lengths, head_dims):
+        key = (pt["b"], pt["h"], pt["h_k"], pt["d"], pt["L"], pt["dtype"])
+        if key not in seen:
+            seen.add(key)
+            yield dict(pt, seqlen_q=n_tree)
+
+
+def _tree_setup(pt, fp8):
+    dev = torch.device("cuda:0")
+    b, h, hk, d, L, sq, dt = pt["b"], pt["h"], pt["h_k"], pt["d"], pt["L"], pt["seqlen_q"], pt["dtype"]
+    kv_bytes = 2 * b * L * hk * d * (1 if fp8 else 2)
+    n = _rotation(kv_bytes, kv_bytes)
+    cdt = torch.float8_e4m3fn if fp8 else dt
+
+    def mk():
+        c = torch.empty(b, L, hk, d, device=dev, dtype=cdt)
+        for i in range(b):                                    # (per batch entry: bounds the temporaries of the conversion)
+            c[i] = torch.empty(L, hk, d, device=dev, dtype=dt).uniform_(-2, 2).to(cdt)
+        return c
+
+    caches = [(mk(), mk()) for _ in range(n)]
+    q = torch.randn(b, sq, h, d, device=dev, dtype=dt)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    parents = torch.tensor([-1] + [(t - 1) // 2 for t in range(1, sq)], device=dev)
+    words = F.tree_mask_from_parents(parents).expand(b, sq).contiguous()
+    kds, vds = (torch.empty(b, hk, device=dev).uniform_(0.5, 2.0) for _ in range(2)) if fp8 else (None, None)
+    return dev, kv_bytes, n, caches, q, cs, words, kds, vds
+
+
+def run_tree_point(pt, fp8, rounds):
+    """(A) the tree call under the binary-heap tree, (B, B2) the causal call of the same shape, twice; interleaved"""
+    b, h, hk, d, L, sq, dt = pt["b"], pt["h"], pt["h_k"], pt["d"], pt["L"], pt["seqlen_q"], pt["dtype"]
+    dev, kv_bytes, n, caches, q, cs, words, kds, vds = _tree_setup(pt, fp8)
+    kw = dict(k_descale=kds, v_descale=vds) if fp8 else {}
+    tree = lambda i: F.flash_attn_with_kvcache(q, caches[i][0], caches[i][1], cache_seqlens=cs, tree_mask=words, **kw)
+    causal = lambda i: F.flash_attn_with_kvcache(q, caches[i][0], caches[i][1], cache_seqlens=cs, causal=True, **kw)
+    diff = float((tree(0).float() - causal(0).float()).abs().max())
+    torch.cuda.synchronize()
+    ms = _interleaved({"causal": causal, "tree": tree, "causal2": causal}, n, rounds)
+    p = capi.kvcache_params(q, caches[0][0], caches[0][1], torch.empty_like(q), torch.empty(b, h, sq, device=dev), cache_seqlens=cs)
+    opt = capi.kvcache_options(cache_dtype=capi.FA_CACHE_FP8_E4M3 if fp8 else 0, tree_mask=words)
+    ws = capi.kvcache_workspace_bytes(p, opt)
+    n_split = max(1, ws and capi.kvcache_num_splits(_with_ws(p, ws), opt))
+    rows = b * h * sq
+    moved = kv_bytes + 2 * rows * d * 2 + rows * 4 + (2 * n_split * rows * (d + 1) * 4 if n_split > 1 else 0)
+    del caches
+    torch.cuda.empty_cache()
+    lo, hi = sorted((ms["causal"], ms["causal2"]))
+    return dict(tree=sq, b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=sq, dtype=str(dt).replace("torch.", ""), kv="fp8" if fp8 else "16bit", kv_gb=round(kv_bytes / 1e9, 3),
+                hbm_bound=kv_bytes >= 1e9, caches_rotated=n, n_split=n_split, ms_tree=round(ms["tree"], 5), ms_causal=round(ms["causal"], 5),
+                ms_causal_again=round(ms["causal2"], 5), tree_over_causal=round(ms["tree"] / ms["causal"], 4), causal_again_over_causal=round(ms["causal2"] / ms["causal"], 4),
+                inside_scatter=bool(lo <= ms["tree"] <= hi), tbps_tree=round(moved / (ms["tree"] * 1e-3) / 1e12, 3), tbps_causal=round(moved / (ms["causal"] * 1e-3) / 1e12, 3),
+                max_abs_diff_to_causal=round(diff, 5))
+
+
+def run_tree_ab_point(pt, base, fp8, rounds):
+    """the tree call through this build's C ABI (A, A2: timed twice) and through the baseline library's (B), interleaved, on the same caches"""
+    b, h, hk, d, L, sq, dt = pt["b"], pt["h"], pt["h_k"], pt["d"], pt["L"], pt["seqlen_q"], pt["dtype"]
+    dev, kv_bytes, n, caches, q, cs, words, kds, vds = _tree_setup(pt, fp8)
+    opt = capi.kvcache_options(cache_dtype=capi.FA_CACHE_FP8_E4M3 if fp8 else 0, k_descale=kds, v_descale=vds, tree_mask=words)
+    libs = {"A": capi.lib(), "B": base}
+    for lib in libs.values():
+        lib.fa_run_mha_fwd_kvcache_ex.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p, ctypes.c_void_p]
+        lib.fa_run_mha_fwd_kvcache_ex.restype = ctypes.c_int
+        lib.fa_kvcache_workspace_bytes_ex.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
+        lib.fa_kvcache_workspace_bytes_ex.restype = ctypes.c_int64
+    params = {}
+    for tag, lib in libs.items():
+        o, lse = torch.empty_like(q), torch.empty(b, h, sq, device=dev)
+        ps = [capi.kvcache_params(q, kc, vc, o, lse, cache_seqlens=cs) for kc, vc in caches]
+        ws = int(lib.fa_kvcache_workspace_bytes_ex(ctypes.byref(ps[0]), ctypes.byref(opt)))
+        assert ws >= 0, ws
+        buf = torch.empty(max(ws, 16) // 4, device=dev, dtype=torch.float32)
+        for p in ps:
+            p.workspace, p.workspace_bytes = (buf.data_ptr(), ws) if ws > 0 else (None, 0)
+        params[tag] = (ps, o, lse, buf, ws)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call(tag):
+        lib, ps = libs[tag], params[tag][0]
+        return lambda i: capi.check(lib.fa_run_mha_fwd_kvcache_ex(ctypes.byref(ps[i]), ctypes.byref(opt), stream))
+
+    fa, fb = call("A"), call("B")
+    fa(0), fb(0)
+    torch.cuda.synchronize()
+    same = torch.equal(params["A"][1].view(torch.int16), params["B"][1].view(torch.int16)) and torch.equal(params["A"][2].view(torch.int32), params["B"][2].view(torch.int32))
+    ms = _interleaved({"this": fa, "baseline": fb, "this2": fa}, n, rounds)
+    split = params["A"][4] > 0
+    del caches, params
+    torch.cuda.empty_cache()
+    lo, hi = sorted((ms["this"], ms["this2"]))
+    return dict(tree=sq, ab=True, b=b, h=h, h_k=hk, d=d, L=L, seqlen_q=sq, dtype=str(dt).replace("torch.", ""), kv="fp8" if fp8 else "16bit", kv_gb=round(kv_bytes / 1e9, 3),
+                hbm_bound=kv_bytes >= 1e9, caches_rotated=n, split=bool(split), ms_this=round(ms["this"], 5), ms_baseline=round(ms["baseline"], 5),
+                ms_this_again=round(ms["this2"], 5), this_over_baseline=round(ms["this"] / ms["baseline"], 4), this_again_over_this=round(ms["this2"] / ms["this"], 4),
+                baseline_inside_scatter=bool(lo <= ms["baseline"] <= hi), bit_identical=bool(same))
+
+
 def torch_rotate(x, cos, sin, pos, interleaved):
     """the rotation with torch ops on x's device: x (b, s, heads, d), pos (b,) long - every row of sequence i at pos[i] (s = 1 here)"""
     rd = 2 * cos.shape[1]
@@ -722,6 +830,8 @@ def main():
     ap.add_argument("--softmax-scale", type=float, default=None, metavar="S", help="with --softcap: softmax_scale of both arms (default 1 / sqrt(head_dim))")
     ap.add_argument("--sinks", action="store_true", help="attention sinks on the gpt-oss shape (d 64, h 64 / h_k 8, window (127, 0) and full causal): the sink call against the "
                                                          "same call without sinks (timed twice); with --kv-dtype fp8 over the 8-bit cache, with --paged P through a block table")
+    ap.add_argument("--tree", type=int, default=None, metavar="N", choices=(8, 32, 64), help="tree attention masks: the tree call under the binary-heap tree with seqlen_q = N against "
+                                                                                             "the causal call of the same shape (timed twice); with --kv-dtype fp8 over the 8-bit cache")
     ap.add_argument("--head-dim", type=int, action="append", metavar="D", choices=(64, 128, 256), help="head dim(s) instead of the grid's 64 and 128 (256: the decode call only)")
     ap.add_argument("--equal-bytes", action="store_true", help="with --head-dim 256: the d-256 call against the d-128 call with twice the heads on the same buffers (timed twice)")
     a = ap.parse_args()
@@ -740,6 +850,11 @@ def main():
                 page = a.paged[0] if a.paged else 0
                 row = run_sinks_point(pt, a.kv_dtype == "fp8", page, a.rounds) if base is None else run_sinks_ab_point(pt, base, a.kv_dtype == "fp8", page, a.rounds)
                 print(json.dumps(row), flush=True)
+            return
+        if a.tree is not None:
+            for pt in tree_grid(a.quick, a.tree, a.length, a.head_dim):
+                fp8 = a.kv_dtype == "fp8"
+                print(json.dumps(run_tree_point(pt, fp8, a.rounds) if base is None else run_tree_ab_point(pt, base, fp8, a.rounds)), flush=True)
             return
         for pt in grid(a.quick, a.length, a.head_dim):
             if a.equal_bytes:
