@@ -518,7 +518,13 @@ static at::Tensor attn_varlen_autograd(at::Tensor q, at::Tensor k, at::Tensor v,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "MI355X (gfx950) fused attention behind the flash_attn_turing surface";
     m.def("fwd", &mha_fwd, "Forward pass");
-    m.def("bwd", &mha_bwd, "Backward pass");
+    m.def("bwd", &mha_bwd,
+          "Backward pass.\n\n"
+          "Dynamic range: over the finite range the result is the reference algorithm with its two 16-bit rounding points (P and dS = P (dP - D),\n"
+          "rounded to nearest before the second GEMMs; D, dP and every sum in fp32; dQ, dK, dV rounded once at the end).  In fp16: while |dO|, |dP|\n"
+          "and the sums stay below 65504, and down to where dS underflows - subnormal inputs, subnormal dS and subnormal outputs are honoured, not\n"
+          "flushed (a dO of 1e-5 is made of fp16 subnormals).  bf16 keeps fp32's exponent range: scaling dO, V or the pair (q, 1 / k) by a power of\n"
+          "two scales the results by exactly that power, bit for bit.  A non-finite backward is unspecified (include/flash_attn_gfx950.h).");
     m.def("varlen_fwd", &mha_varlen_fwd, "Varlen forward pass");
     m.def("varlen_bwd", &mha_varlen_bwd, "Varlen backward pass");
     // three overloads: the signature as it was (every existing call, positional or keyword, resolves to it), the one that continues it with the

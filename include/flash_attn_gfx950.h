@@ -40,6 +40,16 @@
  *   is refreshed per wave, so they round P differently (within the usual tolerances).
  *   Non-finite V and a non-finite backward are unspecified: a masked P = 0 still multiplies V
  *   within a key tile, and 0 x NaN is NaN.
+ *   Dynamic range (backward): over the finite range the backward is the reference algorithm with
+ *   its two 16-bit rounding points (P and dS = P (dP - D), rounded to nearest before the second
+ *   GEMMs; D, dP and every sum in fp32; the outputs rounded once at the end).  In fp16 that means:
+ *   while |dO|, |dP| and the sums stay below 65504 (a loss scale of 2^12 on unit-variance data
+ *   does, 2^14 overflows dK), and down to where dS underflows - subnormal inputs, subnormal dS
+ *   and subnormal outputs are honoured, not flushed (every kernel runs with both float denorm
+ *   modes at 3), so a dO of 1e-5, which is made of fp16 subnormals, loses precision only as the
+ *   2^-24 grid dictates.  bf16 keeps fp32's exponent range, and there scaling dO, V or the pair
+ *   (q, 1 / k) by a power of two scales the results by exactly that power, bit for bit, as long
+ *   as no intermediate leaves fp32's normal range.
  *   Memory: views are never read or written outside their extent (strides may leave gaps
  *   between rows, heads and batch entries).  Packed: rows of q / k / v / dout past
  *   cu_seqlens[b] (up to total_q / total_k) are never read, and the padded lse entries

@@ -1,6 +1,7 @@
 """Compile a .hip file of the package to gfx950 assembly (hipcc cross-compiles without a GPU) and report, per kernel,
-the compiler's own resource usage (-Rpass-analysis=kernel-resource-usage) plus what sits INSIDE its MFMA loops:
-scratch (spill) traffic and v_accvgpr_* register shuffles.  Test infrastructure only."""
+the compiler's own resource usage (-Rpass-analysis=kernel-resource-usage), the float mode of its kernel descriptor
+(.amdhsa_float_denorm_mode_32 / _16_64) plus what sits INSIDE its MFMA loops: scratch (spill) traffic and v_accvgpr_* register
+shuffles.  Test infrastructure only."""
 import collections
 import os
 import re
@@ -15,6 +16,8 @@ import build as _build  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _mfma_hazards  # noqa: E402
+
+HIP_SOURCES = list(_build.HIP_SOURCES)      # every source of the library, in build order
 
 _KEYS = {"VGPRs": "vgprs", "AGPRs": "agprs", r"ScratchSize \[bytes/lane\]": "scratch_bytes", r"Occupancy \[waves/SIMD\]": "occupancy",
          r"LDS Size \[bytes/block\]": "lds_bytes"}
@@ -61,6 +64,12 @@ def analyse(hip_source, extra_flags=()):
             m = re.search(r"\s" + pat + r": (\d+)", line)
             if m:
                 cur[key] = int(m.group(1))
+    # the float mode each kernel starts in, from its kernel descriptor (3 = subnormals kept on input and output, 0 = flushed)
+    for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)\n(.*?)^\s*\.end_amdhsa_kernel", txt, re.M | re.S):
+        for key in ("float_denorm_mode_32", "float_denorm_mode_16_64"):
+            d = re.search(r"^\s*\.amdhsa_" + key + r" (\d+)", m.group(2), re.M)
+            if d:
+                kernels.setdefault(m.group(1), {})[key] = int(d.group(1))
     for name, info in kernels.items():
         if name + ":" not in txt:
             continue

@@ -6,7 +6,7 @@ backward on causal shapes, profiles/r1_bwd_causal_ab.log) because only the non-c
 compiles every kernel instantiation and fails on scratch traffic or accumulator shuffles inside any MFMA loop."""
 import pytest
 
-from _kernel_isa import analyse
+from _kernel_isa import HIP_SOURCES, analyse
 
 FILES = ["fa_fwd_pp.hip", "fa_fwd_pp16.hip", "fa_bwd.hip", "fa_bwd_dq16.hip", "fa_bwd_dkdv16.hip"]
 # whole-kernel scratch that is known, outside every loop (prologue / epilogue), and bounded here so growth is noticed
@@ -34,6 +34,32 @@ def test_every_kernel_was_analysed(kernels):
         # no vacuous passes: every MFMA kernel must have been seen WITH its MFMAs and at least one MFMA loop
         if "dot_do_o" not in name and "sum_splits" not in name:      # the two HBM-bound helpers hold no MFMA
             assert info.get("mfma_total", 0) >= 16 and info.get("loops"), (f, name, info.get("mfma_total"), info.get("loops"))
+
+
+@pytest.fixture(scope="module")
+def library_kernels(kernels):
+    """(source, kernel) -> analysis for every source of the library (HIP_SOURCES): the five FILES above plus the remaining ones, compiled four at a time"""
+    import concurrent.futures
+
+    rest = [f for f in HIP_SOURCES if f not in FILES]
+    out = dict(kernels)
+    with concurrent.futures.ThreadPoolExecutor(max_workers=4) as pool:
+        for f, ks in zip(rest, pool.map(analyse, rest)):
+            out.update({(f, name): info for name, info in ks.items()})
+    return out
+
+
+def test_every_kernel_keeps_subnormals(library_kernels):
+    """The contract honours subnormal inputs, dS and outputs (include/flash_attn_gfx950.h; tests/test_dynamic_range_gpu.py on the GPU): an fp16 dO
+    of 1e-5 is made of them.  Whether the conversions and the stores keep them is the kernel's float mode, which a build flag
+    (-fgpu-flush-denormals-to-zero: 32-bit mode 0) changes without a word: every kernel of every source of the library must start with
+    subnormals kept, 32-bit and 16/64-bit alike (mode 3)."""
+    modes = {k: (v["float_denorm_mode_32"], v["float_denorm_mode_16_64"]) for k, v in library_kernels.items() if "float_denorm_mode_32" in v}
+    # no vacuous pass: every source that holds a kernel was seen with its descriptors (fa_capi.hip is host code only)
+    assert {f for f, _ in modes} == set(HIP_SOURCES) - {"fa_capi.hip"}, sorted({f for f, _ in modes})
+    assert len(modes) >= 36, len(modes)                      # (one descriptor per instantiation; the sources hold 36 __global__ templates)
+    bad = {k: m for k, m in modes.items() if m != (3, 3)}
+    assert not bad, bad
 
 
 def test_no_spills_or_accumulator_shuffles_inside_mfma_loops(kernels):
