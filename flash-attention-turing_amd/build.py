@@ -32,7 +32,7 @@ LIB_NAME = "libflash_attn_gfx950.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
 EXT_PATH = os.path.join(PKG, "_C.so")
 
-HIP_SOURCES = ["fa_fwd_pp.hip", "fa_fwd_pp16.hip", "fa_bwd.hip", "fa_bwd_dq16.hip", "fa_bwd_dkdv16.hip", "fa_fwd_kvcache.hip", "fa_fwd_kvcache_ragged.hip", "fa_fwd_kvcache_softcap.hip", "fa_fwd_kvcache_sink.hip", "fa_fwd_kvcache_tree.hip", "fa_fwd_kvcache_d256.hip", "fa_kvcache_rotary.hip", "fa_capi.hip"]
+HIP_SOURCES = ["fa_fwd_pp.hip", "fa_fwd_pp16.hip", "fa_bwd.hip", "fa_bwd_dq16.hip", "fa_bwd_dkdv16.hip", "fa_fwd_kvcache.hip", "fa_fwd_kvcache_ragged.hip", "fa_fwd_kvcache_softcap.hip", "fa_fwd_kvcache_sink.hip", "fa_fwd_kvcache_tree.hip", "fa_fwd_kvcache_prefill.hip", "fa_fwd_kvcache_d256.hip", "fa_kvcache_rotary.hip", "fa_capi.hip"]
 # per-file extra flags.  fa_fwd_pp16.hip: hipcc's SLP vectoriser packs the softmax row-sum adds and the O rescale into v_pk_* on register
 # pairs it first has to assemble from the 4-register MFMA tiles: ~200 v_mov_b64 per three tiles and 44-116 bytes of spills on the hot path
 # fa_fwd_kvcache_d256.hip (one workgroup per compute unit, 256 VGPRs + 256 AGPRs a lane): the K / V prefetch sets may live in either half of the register file, O^T and
@@ -92,7 +92,7 @@ def debug_library_path(name):
     return os.path.join(DEBUG_DIR, f"libfa_{name}.so")
 
 
-M0_GUARD_SOURCES = ["fa_fwd_pp.hip", "fa_fwd_pp16.hip", "fa_bwd.hip", "fa_bwd_dq16.hip", "fa_bwd_dkdv16.hip", "fa_fwd_kvcache.hip", "fa_fwd_kvcache_ragged.hip", "fa_fwd_kvcache_softcap.hip", "fa_fwd_kvcache_sink.hip", "fa_fwd_kvcache_tree.hip", "fa_fwd_kvcache_d256.hip", "fa_kvcache_rotary.hip"]
+M0_GUARD_SOURCES = ["fa_fwd_pp.hip", "fa_fwd_pp16.hip", "fa_bwd.hip", "fa_bwd_dq16.hip", "fa_bwd_dkdv16.hip", "fa_fwd_kvcache.hip", "fa_fwd_kvcache_ragged.hip", "fa_fwd_kvcache_softcap.hip", "fa_fwd_kvcache_sink.hip", "fa_fwd_kvcache_tree.hip", "fa_fwd_kvcache_prefill.hip", "fa_fwd_kvcache_d256.hip", "fa_kvcache_rotary.hip"]
 
 
 def m0_uses_outside_asm(asm_text):

@@ -346,22 +346,22 @@ int fa_mha_varlen_bwd(const void* q, const void* k, const void* v, const void* o
     return fa_run_mha_bwd(&p, stream);
 }
 
-// The options pointer of the _ex entry points -> a zeroed fa_kvcache_options_v7 filled with what the caller's struct carries: struct_size says
-// which of the seven layouts it is (fa_kvcache_options: the window alone; fa_kvcache_options_v2: plus the 8-bit cache fields;
+// The options pointer of the _ex entry points -> a zeroed fa_kvcache_options_v8 filled with what the caller's struct carries: struct_size says
+// which of the eight layouts it is (fa_kvcache_options: the window alone; fa_kvcache_options_v2: plus the 8-bit cache fields;
 // fa_kvcache_options_v3: plus the rotary fields; fa_kvcache_options_v4: plus the ragged-batch fields; fa_kvcache_options_v5: plus softmax_scale
 // and softcap; fa_kvcache_options_v6: plus the attention sinks;
-// fa_kvcache_options_v7: plus the tree mask).  NULL = all zero.
-static int import_kvcache_options(const fa_kvcache_options* user, fa_kvcache_options_v7& o) {
+// fa_kvcache_options_v7: plus the tree mask; fa_kvcache_options_v8: plus row_tile).  NULL = all zero.
+static int import_kvcache_options(const fa_kvcache_options* user, fa_kvcache_options_v8& o) {
     memset(&o, 0, sizeof(o));
     if (user == nullptr) return FA_OK;
     if (user->magic != FA_PARAMS_MAGIC)
         return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: no {struct_size, magic} header (FA_PARAMS_INIT); recompile against include/flash_attn_gfx950.h (ABI %d)", FA_ABI_VERSION);
     if (user->struct_size != sizeof(fa_kvcache_options) && user->struct_size != sizeof(fa_kvcache_options_v2) && user->struct_size != sizeof(fa_kvcache_options_v3) &&
         user->struct_size != sizeof(fa_kvcache_options_v4) && user->struct_size != sizeof(fa_kvcache_options_v5) && user->struct_size != sizeof(fa_kvcache_options_v6) &&
-        user->struct_size != sizeof(fa_kvcache_options_v7))
-        return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: struct_size %u is none of sizeof(fa_kvcache_options) = %zu, sizeof(fa_kvcache_options_v2) = %zu, sizeof(fa_kvcache_options_v3) = %zu, sizeof(fa_kvcache_options_v4) = %zu, sizeof(fa_kvcache_options_v5) = %zu, sizeof(fa_kvcache_options_v6) = %zu, sizeof(fa_kvcache_options_v7) = %zu - header / library mismatch",
+        user->struct_size != sizeof(fa_kvcache_options_v7) && user->struct_size != sizeof(fa_kvcache_options_v8))
+        return fail(FA_ERR_BAD_ABI, "fa_kvcache_options: struct_size %u is none of sizeof(fa_kvcache_options) = %zu, sizeof(fa_kvcache_options_v2) = %zu, sizeof(fa_kvcache_options_v3) = %zu, sizeof(fa_kvcache_options_v4) = %zu, sizeof(fa_kvcache_options_v5) = %zu, sizeof(fa_kvcache_options_v6) = %zu, sizeof(fa_kvcache_options_v7) = %zu, sizeof(fa_kvcache_options_v8) = %zu - header / library mismatch",
                     user->struct_size, sizeof(fa_kvcache_options), sizeof(fa_kvcache_options_v2), sizeof(fa_kvcache_options_v3), sizeof(fa_kvcache_options_v4),
-                    sizeof(fa_kvcache_options_v5), sizeof(fa_kvcache_options_v6), sizeof(fa_kvcache_options_v7));
+                    sizeof(fa_kvcache_options_v5), sizeof(fa_kvcache_options_v6), sizeof(fa_kvcache_options_v7), sizeof(fa_kvcache_options_v8));
     memcpy(&o, user, user->struct_size);
     if (o.cache_dtype != 0 && o.cache_dtype != FA_CACHE_FP8_E4M3)
         return fail(FA_ERR_BAD_DTYPE, "cache_dtype %d unsupported (0 = the dtype of q, %d = FA_CACHE_FP8_E4M3; e4m3fnuz and e5m2 caches are not supported)", o.cache_dtype,
@@ -373,7 +373,7 @@ static int import_kvcache_options(const fa_kvcache_options* user, fa_kvcache_opt
 
 // with_workspace = false: the `workspace` fields are not looked at (fa_kvcache_workspace_bytes)
 static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& kp, fa_kvcache_params& local, bool with_workspace,
-                        const fa_kvcache_options_v7& o) {
+                        const fa_kvcache_options_v8& o) {
     // the paged-cache fields are optional: a caller built before them passes struct_size = offsetof(block_table) and gets NULL / 0
     int rc = import_params(user, local, "fa_kvcache_params", offsetof(fa_kvcache_params, block_table));
     if (rc) return rc;
@@ -452,7 +452,7 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
 // fa_kvcache_options (NULL = none) -> the window fields of kp, normalised: right = 0 under causal, and a side that cannot bind is -1 (left >=
 // seqlen_cache - 1: lo_t <= L - 1 - left <= 0 for every row; right >= seqlen_q - 1: lim_t >= L for every row).  A window whose left side is
 // unbounded and whose right side is unbounded or the causal limit is exactly the plain call: is_local stays 0 (the plain kernels, split and bits).
-static int fill_kvcache_window(const fa_kvcache_options_v7& o, fa::KvcacheKernelParams& kp) {
+static int fill_kvcache_window(const fa_kvcache_options_v8& o, fa::KvcacheKernelParams& kp) {
     if (!o.is_local) return FA_OK;
     if (o.window_size_left < -1 || o.window_size_right < -1)
         return fail(FA_ERR_BAD_SHAPE, "window_size (%d, %d): each side must be >= -1 (-1 = unbounded)", o.window_size_left, o.window_size_right);
@@ -467,7 +467,7 @@ static int fill_kvcache_window(const fa_kvcache_options_v7& o, fa::KvcacheKernel
 
 // The rotary fields of the options (rotary_cos = rotary_sin = NULL: off, rp.cos stays NULL and nothing else is looked at) -> rp, validated.
 // The query-position rule is decided from what the caller stated (is_causal, a window other than (-1, -1)), not from the normalised window.
-static int fill_kvcache_rotary(const fa_kvcache_options_v7& o, const fa::KvcacheKernelParams& kp, fa::KvcacheRotaryParams& rp) {
+static int fill_kvcache_rotary(const fa_kvcache_options_v8& o, const fa::KvcacheKernelParams& kp, fa::KvcacheRotaryParams& rp) {
     memset(&rp, 0, sizeof(rp));
     if (o.rotary_cos == nullptr && o.rotary_sin == nullptr) return FA_OK;
     if (o.rotary_cos == nullptr || o.rotary_sin == nullptr) return fail(FA_ERR_BAD_SHAPE, "rotary_cos and rotary_sin must both be given or both be NULL");
@@ -490,7 +490,7 @@ static int fill_kvcache_rotary(const fa_kvcache_options_v7& o, const fa::Kvcache
 
 // The ragged-batch fields of the options (cu_seqlens_q = NULL: off, rg.cu_q stays NULL and only a stray cu_seqlens_k_new is looked at) -> rg,
 // validated.  rg.kp is left to the caller (the launch takes the finished kp).
-static int fill_kvcache_ragged(const fa_kvcache_options_v7& o, const fa::KvcacheKernelParams& kp, const fa::KvcacheRotaryParams& rp, fa::KvcacheRaggedParams& rg) {
+static int fill_kvcache_ragged(const fa_kvcache_options_v8& o, const fa::KvcacheKernelParams& kp, const fa::KvcacheRotaryParams& rp, fa::KvcacheRaggedParams& rg) {
     memset(&rg, 0, sizeof(rg));
     if (o.cu_seqlens_q == nullptr) {
         if (o.cu_seqlens_k_new != nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_k_new given without cu_seqlens_q (packed k_new / v_new belong to a ragged call)");
@@ -519,7 +519,7 @@ static int fill_kvcache_ragged(const fa_kvcache_options_v7& o, const fa::Kvcache
 // softmax_scale / softcap of the options -> kp.scale / kp.scale_log2e and cap_pre (0 = no cap: the kernels, hence the bits, of the call without
 // the two fields whenever the scale is the default's value).  With a cap the attention kernels of fa_fwd_kvcache_softcap.hip keep tanh(s * pre)
 // and read the cap where the scale was: scale = softcap, scale_log2e = softcap * log2(e), cap_pre = 2 log2(e) * softmax_scale / softcap.
-static int fill_kvcache_softcap(const fa_kvcache_options_v7& o, fa::KvcacheKernelParams& kp, float& cap_pre) {
+static int fill_kvcache_softcap(const fa_kvcache_options_v8& o, fa::KvcacheKernelParams& kp, float& cap_pre) {
     cap_pre = 0.f;
     if (!(o.softmax_scale >= 0.f) || isinf(o.softmax_scale))
         return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default 1 / sqrt(head_dim))", (double)o.softmax_scale);
@@ -542,7 +542,7 @@ static int fill_kvcache_softcap(const fa_kvcache_options_v7& o, fa::KvcacheKerne
 
 // The sink fields of the options (sinks = NULL: off, sink.ptr stays NULL and only the reserved words are looked at - a v6 struct
 // with a zeroed tail is a v5 call) -> sink, validated; behind every older field.  Sinks with a soft cap and sinks at head_dim 256 have no kernels.
-static int fill_kvcache_sinks(const fa_kvcache_options_v7& o, const fa::KvcacheKernelParams& kp, float cap_pre, fa::KvcacheSink& sink) {
+static int fill_kvcache_sinks(const fa_kvcache_options_v8& o, const fa::KvcacheKernelParams& kp, float cap_pre, fa::KvcacheSink& sink) {
     sink.ptr = nullptr;
     sink.stride = 0;
     if (o.sinks != nullptr) {
@@ -561,7 +561,7 @@ static int fill_kvcache_sinks(const fa_kvcache_options_v7& o, const fa::KvcacheK
 // zeroed tail is a v6 call) -> tree, validated; behind every older field.  The mask is a select of its own: it does not combine with the causal
 // limit, a window, a soft cap, sinks or rotary (a node's position is its depth, not its index: the engine rotates), has no head_dim-256 kernels,
 // and a row's word holds 64 draft tokens.  What the caller stated decides, not the normalised window.
-static int fill_kvcache_tree(const fa_kvcache_options_v7& o, const fa::KvcacheKernelParams& kp, const fa::KvcacheRotaryParams& rp, float cap_pre,
+static int fill_kvcache_tree(const fa_kvcache_options_v8& o, const fa::KvcacheKernelParams& kp, const fa::KvcacheRotaryParams& rp, float cap_pre,
                              const fa::KvcacheSink& sink, fa::KvcacheTree& tree) {
     tree.ptr = nullptr;
     tree.batch_stride = tree.row_stride = 0;
@@ -586,12 +586,35 @@ static int fill_kvcache_tree(const fa_kvcache_options_v7& o, const fa::KvcacheKe
     return FA_OK;
 }
 
+// row_tile of the options (0: the 16-row kernels, and only the reserved words are looked at - a v8 struct with a zeroed tail is a v7 call) ->
+// row_tile as the launchers take it (kKvcRows / kKvcPrefillRows), validated; behind every older field.  The wide kernels are the plain and the
+// causal body alone: no window, soft cap, sinks, tree mask or rotary image, and no head_dim 256.  What the caller stated decides, not the normalised window.
+static int fill_kvcache_prefill(const fa_kvcache_options_v8& o, const fa::KvcacheKernelParams& kp, const fa::KvcacheRotaryParams& rp, float cap_pre,
+                                const fa::KvcacheSink& sink, const fa::KvcacheTree& tree, int32_t& row_tile) {
+    row_tile = fa::kKvcRows;
+    if (o.row_tile != 0) {
+        if (o.row_tile != fa::kKvcPrefillRows)
+            return fail(FA_ERR_BAD_SHAPE, "row_tile %d unsupported (0 = the 16-row kernels, 64 = the 64-row kernels for prompt chunks)", o.row_tile);
+        if (o.is_local && (o.window_size_left != -1 || o.window_size_right != -1))
+            return fail(FA_ERR_BAD_SHAPE, "row_tile = 64 together with window_size (%d, %d) is not supported", o.window_size_left, o.window_size_right);
+        if (cap_pre > 0.f) return fail(FA_ERR_BAD_SHAPE, "row_tile = 64 together with softcap > 0 is not supported");
+        if (sink.ptr != nullptr) return fail(FA_ERR_BAD_SHAPE, "row_tile = 64 together with sinks is not supported");
+        if (tree.ptr != nullptr) return fail(FA_ERR_BAD_SHAPE, "row_tile = 64 together with tree_mask is not supported");
+        if (rp.cos != nullptr) return fail(FA_ERR_BAD_SHAPE, "row_tile = 64 together with rotary_cos / rotary_sin is not supported");
+        if (kp.d == 256) return fail(FA_ERR_BAD_SHAPE, "row_tile = 64 at head_dim d = 256 is not supported (d must be 64 or 128 with row_tile = 64)");
+        row_tile = fa::kKvcPrefillRows;
+    }
+    if (o.reserved4_ != 0 || o.reserved4[0] != 0 || o.reserved4[1] != 0 || o.reserved4[2] != 0 || o.reserved4[3] != 0 || o.reserved4[4] != 0)
+        return fail(FA_ERR_BAD_ABI, "fa_kvcache_options_v8: reserved4 fields are not zero (a field of a newer header that this library does not know)");
+    return FA_OK;
+}
+
 // Params first, as before the options existed (their errors win), except that the cache tensors are checked under the cache dtype the
 // options state; then the options' own values.
 static int fill_kvcache_all(const fa_kvcache_params* user, const fa_kvcache_options* options, fa::KvcacheKernelParams& kp, fa_kvcache_params& local,
-                            fa_kvcache_options_v7& o, fa::KvcacheRotaryParams& rp, fa::KvcacheRaggedParams& rg, float& cap_pre, fa::KvcacheSink& sink, fa::KvcacheTree& tree,
-                            bool with_workspace) {
-    fa_kvcache_options_v7 none;
+                            fa_kvcache_options_v8& o, fa::KvcacheRotaryParams& rp, fa::KvcacheRaggedParams& rg, float& cap_pre, fa::KvcacheSink& sink, fa::KvcacheTree& tree,
+                            int32_t& row_tile, bool with_workspace) {
+    fa_kvcache_options_v8 none;
     memset(&none, 0, sizeof(none));
     const int orc = import_kvcache_options(options, o);
     char oerr[sizeof(g_err)];
@@ -607,7 +630,8 @@ static int fill_kvcache_all(const fa_kvcache_params* user, const fa_kvcache_opti
     if ((rc = fill_kvcache_ragged(o, kp, rp, rg))) return rc;
     if ((rc = fill_kvcache_softcap(o, kp, cap_pre))) return rc;
     if ((rc = fill_kvcache_sinks(o, kp, cap_pre, sink))) return rc;
-    return fill_kvcache_tree(o, kp, rp, cap_pre, sink, tree);
+    if ((rc = fill_kvcache_tree(o, kp, rp, cap_pre, sink, tree))) return rc;
+    return fill_kvcache_prefill(o, kp, rp, cap_pre, sink, tree, row_tile);
 }
 
 // Workspace left for the split partials of a rotary call once the image of the rotated q has taken its part; a workspace that cannot hold
@@ -624,57 +648,75 @@ static int64_t rotary_split_bytes(const fa::KvcacheKernelParams& kp, const fa_kv
 int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    fa_kvcache_options_v7 o;
+    fa_kvcache_options_v8 o;
     fa::KvcacheRotaryParams rp;
     fa::KvcacheRaggedParams rg;
     float cap_pre;
     fa::KvcacheSink sink;
     fa::KvcacheTree tree;
-    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, false);
+    int32_t row_tile;
+    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, row_tile, false);
     if (rc) return rc;
     if (kp.b == 0) return 0;
     const int64_t total_q = rg.cu_q != nullptr ? rg.total_q : -1;
     return (rp.cos != nullptr ? fa::kvcache_rotary_image_bytes(kp) : 0) +
-           fa::kvcache_workspace_bytes(kp, fa::kvcache_split(kp, -1, local.num_splits, total_q), total_q);
+           fa::kvcache_workspace_bytes(kp, fa::kvcache_split(kp, -1, local.num_splits, total_q, row_tile), total_q);
 }
 
 int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    fa_kvcache_options_v7 o;
+    fa_kvcache_options_v8 o;
     fa::KvcacheRotaryParams rp;
     fa::KvcacheRaggedParams rg;
     float cap_pre;
     fa::KvcacheSink sink;
     fa::KvcacheTree tree;
-    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, true);
+    int32_t row_tile;
+    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, row_tile, true);
     if (rc) return rc;
     if (kp.b == 0) return 1;
     int64_t avail = local.workspace != nullptr ? local.workspace_bytes : 0;
     if (rp.cos != nullptr && (avail = rotary_split_bytes(kp, local)) < 0) return (int32_t)avail;
-    return fa::kvcache_split(kp, avail, local.num_splits, rg.cu_q != nullptr ? rg.total_q : -1);
+    return fa::kvcache_split(kp, avail, local.num_splits, rg.cu_q != nullptr ? rg.total_q : -1, row_tile);
+}
+
+int32_t fa_kvcache_row_tile_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
+    fa::KvcacheKernelParams kp;
+    fa_kvcache_params local;
+    fa_kvcache_options_v8 o;
+    fa::KvcacheRotaryParams rp;
+    fa::KvcacheRaggedParams rg;
+    float cap_pre;
+    fa::KvcacheSink sink;
+    fa::KvcacheTree tree;
+    int32_t row_tile;
+    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, row_tile, false);
+    if (rc) return rc;
+    return row_tile;
 }
 
 int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* user, const fa_kvcache_options* options, void* stream) {
     fa::KvcacheKernelParams kp;
     fa_kvcache_params local;
-    fa_kvcache_options_v7 o;
+    fa_kvcache_options_v8 o;
     fa::KvcacheRotaryParams rp;
     fa::KvcacheRaggedParams rg;
     float cap_pre;
     fa::KvcacheSink sink;
     fa::KvcacheTree tree;
-    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, true);
+    int32_t row_tile;
+    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, row_tile, true);
     if (rc) return rc;
     if (kp.b == 0) return FA_OK;
     int64_t avail = local.workspace != nullptr ? local.workspace_bytes : 0;
     char* ws = (char*)local.workspace;
     if (rg.cu_q != nullptr) {
         // ragged queries: the append, attention and combine kernels of fa_fwd_kvcache_ragged.hip (no rotary: refused above)
-        kp.n_split = fa::kvcache_split(kp, avail, local.num_splits, rg.total_q);
+        kp.n_split = fa::kvcache_split(kp, avail, local.num_splits, rg.total_q, row_tile);
         kp.ws_o = kp.n_split > 1 ? (float*)ws : nullptr;
         rg.kp = kp;
-        return hip_status(fa::launch_fwd_kvcache_ragged(rg, local.dtype, (hipStream_t)stream, cap_pre, sink, tree), "fa_fwd_kvcache (ragged) launch");
+        return hip_status(fa::launch_fwd_kvcache_ragged(rg, local.dtype, (hipStream_t)stream, cap_pre, sink, tree, row_tile), "fa_fwd_kvcache (ragged) launch");
     }
     if (rp.cos != nullptr) {
         // the fused rotary launch takes the place of the append: it writes the cache rows and the image of the rotated q at the head of the
@@ -688,9 +730,9 @@ int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* user, const fa_kvcache_op
         kp.q = conv(contiguous_bshd(kp.seqlen_q, kp.h, kp.d));
         kp.k_new = kp.v_new = nullptr;          // (seqlen_new stays: the appended rows count into the valid length)
     }
-    kp.n_split = fa::kvcache_split(kp, avail, local.num_splits);
+    kp.n_split = fa::kvcache_split(kp, avail, local.num_splits, -1, row_tile);
     kp.ws_o = kp.n_split > 1 ? (float*)ws : nullptr;
-    return hip_status(fa::launch_fwd_kvcache(kp, local.dtype, (hipStream_t)stream, cap_pre, sink, tree), "fa_fwd_kvcache launch");
+    return hip_status(fa::launch_fwd_kvcache(kp, local.dtype, (hipStream_t)stream, cap_pre, sink, tree, row_tile), "fa_fwd_kvcache launch");
 }
 
 int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* user) { return fa_kvcache_workspace_bytes_ex(user, nullptr); }

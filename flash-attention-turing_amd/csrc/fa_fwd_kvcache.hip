@@ -765,7 +765,7 @@ __global__ __launch_bounds__(256) void fa_kvcache_append_fp8_kernel(const Kvcach
 }
 
 template <typename T, int D>
-hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre, const KvcacheSink& sink, const KvcacheTree& tree) {
+hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre, const KvcacheSink& sink, const KvcacheTree& tree, int32_t row_tile) {
     const bool paged = kp.block_table != nullptr;
     if (kp.k_new != nullptr && kp.seqlen_new > 0) {
         const int64_t n = (int64_t)kp.b * kp.seqlen_new * kp.h_k * (D / 8);
@@ -773,7 +773,10 @@ hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, fl
         else hipLaunchKernelGGL((fa_kvcache_append_fp8_kernel<T, D, false>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kp);
     }
     const int64_t grid = (int64_t)kp.b * kp.h_k * kp.n_row_tiles * kp.n_split;
-    if (cap_pre > 0.f) {        // soft-capped scores: the attention kernels of fa_fwd_kvcache_softcap.hip between this file's append and combine
+    if (row_tile == kKvcPrefillRows) {     // 64-row workgroups: the attention kernels of fa_fwd_kvcache_prefill.hip between this file's append and combine
+        const hipError_t e = launch_kvcache_prefill_attn(kp, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
+        if (e != hipSuccess) return e;
+    } else if (cap_pre > 0.f) {        // soft-capped scores: the attention kernels of fa_fwd_kvcache_softcap.hip between this file's append and combine
         const hipError_t e = launch_kvcache_softcap_attn(kp, cap_pre, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
         if (e != hipSuccess) return e;
     } else if (sink.ptr != nullptr && kp.n_split == 1) {    // sinks, unsplit: the attention kernels of fa_fwd_kvcache_sink.hip (a split call runs the kernels below)
@@ -803,7 +806,7 @@ hipError_t launch_kvcache_fp8_t(const KvcacheKernelParams& kp, hipStream_t s, fl
 }
 
 template <typename T, int D>
-hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre, const KvcacheSink& sink, const KvcacheTree& tree) {
+hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s, float cap_pre, const KvcacheSink& sink, const KvcacheTree& tree, int32_t row_tile) {
     const bool paged = kp.block_table != nullptr;
     if (kp.k_new != nullptr && kp.seqlen_new > 0) {
         const int64_t n = (int64_t)kp.b * kp.seqlen_new * kp.h_k * (D / 8);
@@ -811,7 +814,10 @@ hipError_t launch_kvcache_t(const KvcacheKernelParams& kp, hipStream_t s, float 
         else hipLaunchKernelGGL((fa_kvcache_append_kernel<D>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kp);
     }
     const int64_t grid = (int64_t)kp.b * kp.h_k * kp.n_row_tiles * kp.n_split;
-    if (cap_pre > 0.f) {        // soft-capped scores: the attention kernels of fa_fwd_kvcache_softcap.hip between this file's append and combine
+    if (row_tile == kKvcPrefillRows) {     // 64-row workgroups: the attention kernels of fa_fwd_kvcache_prefill.hip between this file's append and combine
+        const hipError_t e = launch_kvcache_prefill_attn(kp, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
+        if (e != hipSuccess) return e;
+    } else if (cap_pre > 0.f) {        // soft-capped scores: the attention kernels of fa_fwd_kvcache_softcap.hip between this file's append and combine
         const hipError_t e = launch_kvcache_softcap_attn(kp, cap_pre, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
         if (e != hipSuccess) return e;
     } else if (sink.ptr != nullptr && kp.n_split == 1) {    // sinks, unsplit: the attention kernels of fa_fwd_kvcache_sink.hip (a split call runs the kernels below)
@@ -862,23 +868,25 @@ int64_t kvcache_steps(const KvcacheKernelParams& kp) {
 // the choice needs caps it (avail_bytes < 0: unlimited).
 // A ragged call (total_q >= 0) counts the tile slots of its grid, kvcache_ragged_slots, in place of b x row tiles, and its partial planes
 // have h x total_q rows.
+// row_tile = the packed query rows of a workgroup: kKvcRows for the kernels of this file, kKvcPrefillRows for the 64-row kernels of
+// fa_fwd_kvcache_prefill.hip - the same rule over that grid's workgroup count, and the same slot formula in tiles of 64.
 #ifndef FA_KVC_RAGGED_TU
-int64_t kvcache_ragged_slots(const KvcacheKernelParams& kp, int64_t total_q, int32_t* compact) {
-    const int64_t packed = (total_q * kp.h_ratio + kKvcRows - 1) / kKvcRows + kp.b;
-    const int64_t plain = (int64_t)kp.b * (((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
+int64_t kvcache_ragged_slots(const KvcacheKernelParams& kp, int64_t total_q, int32_t* compact, int32_t row_tile) {
+    const int64_t packed = (total_q * kp.h_ratio + row_tile - 1) / row_tile + kp.b;
+    const int64_t plain = (int64_t)kp.b * (((int64_t)kp.seqlen_q * kp.h_ratio + row_tile - 1) / row_tile);
     if (compact != nullptr) *compact = packed < plain ? 1 : 0;
     return packed < plain ? packed : plain;
 }
 
-int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_t requested, int64_t total_q) {
+int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_t requested, int64_t total_q, int32_t row_tile) {
     const int64_t steps = kvcache_steps(kp);
     if (steps <= 1) return 1;
     int64_t n;
     if (requested > 0) {
         n = requested < steps ? requested : steps;
     } else {
-        const int64_t wgs = total_q >= 0 ? kp.h_k * kvcache_ragged_slots(kp, total_q, nullptr)
-                                         : (int64_t)kp.b * kp.h_k * (((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
+        const int64_t wgs = total_q >= 0 ? kp.h_k * kvcache_ragged_slots(kp, total_q, nullptr, row_tile)
+                                         : (int64_t)kp.b * kp.h_k * (((int64_t)kp.seqlen_q * kp.h_ratio + row_tile - 1) / row_tile);
         const int64_t cus = device_cu_count();
         if (wgs <= 0 || wgs >= cus) return 1;
         n = (2 * cus + wgs - 1) / wgs;
@@ -900,8 +908,9 @@ int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split, 
     return o_bytes + l_bytes;
 }
 
-hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s, float cap_pre, KvcacheSink sink, KvcacheTree tree) {
-    kp.n_row_tiles = (int32_t)(((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
+hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s, float cap_pre, KvcacheSink sink, KvcacheTree tree, int32_t row_tile) {
+    if (!kvcache_row_tile_ok(row_tile)) return hipErrorInvalidValue;
+    kp.n_row_tiles = (int32_t)(((int64_t)kp.seqlen_q * kp.h_ratio + row_tile - 1) / row_tile);
     kp.rows_total = (int64_t)kp.b * kp.h * kp.seqlen_q;
     const int64_t steps = kvcache_steps(kp);
     if (kp.n_split < 1) kp.n_split = 1;
@@ -912,11 +921,11 @@ hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t s, 
     }
     if (kp.d == 256) return launch_kvcache_d256(kp, dtype, s, cap_pre);
     if (kp.cache_fp8) {
-        if (dtype == 0) return kp.d == 64 ? launch_kvcache_fp8_t<_Float16, 64>(kp, s, cap_pre, sink, tree) : launch_kvcache_fp8_t<_Float16, 128>(kp, s, cap_pre, sink, tree);
-        return kp.d == 64 ? launch_kvcache_fp8_t<__bf16, 64>(kp, s, cap_pre, sink, tree) : launch_kvcache_fp8_t<__bf16, 128>(kp, s, cap_pre, sink, tree);
+        if (dtype == 0) return kp.d == 64 ? launch_kvcache_fp8_t<_Float16, 64>(kp, s, cap_pre, sink, tree, row_tile) : launch_kvcache_fp8_t<_Float16, 128>(kp, s, cap_pre, sink, tree, row_tile);
+        return kp.d == 64 ? launch_kvcache_fp8_t<__bf16, 64>(kp, s, cap_pre, sink, tree, row_tile) : launch_kvcache_fp8_t<__bf16, 128>(kp, s, cap_pre, sink, tree, row_tile);
     }
-    if (dtype == 0) return kp.d == 64 ? launch_kvcache_t<_Float16, 64>(kp, s, cap_pre, sink, tree) : launch_kvcache_t<_Float16, 128>(kp, s, cap_pre, sink, tree);
-    return kp.d == 64 ? launch_kvcache_t<__bf16, 64>(kp, s, cap_pre, sink, tree) : launch_kvcache_t<__bf16, 128>(kp, s, cap_pre, sink, tree);
+    if (dtype == 0) return kp.d == 64 ? launch_kvcache_t<_Float16, 64>(kp, s, cap_pre, sink, tree, row_tile) : launch_kvcache_t<_Float16, 128>(kp, s, cap_pre, sink, tree, row_tile);
+    return kp.d == 64 ? launch_kvcache_t<__bf16, 64>(kp, s, cap_pre, sink, tree, row_tile) : launch_kvcache_t<__bf16, 128>(kp, s, cap_pre, sink, tree, row_tile);
 }
 #endif  // FA_KVC_RAGGED_TU
 

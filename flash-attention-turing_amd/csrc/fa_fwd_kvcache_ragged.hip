@@ -131,7 +131,7 @@ void launch_ragged_attn(const KvcacheRaggedParams& rp, unsigned grid, hipStream_
 }
 
 template <typename T, int D, int ES>
-hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre, const KvcacheSink& sink, const KvcacheTree& tree) {
+hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre, const KvcacheSink& sink, const KvcacheTree& tree, int32_t row_tile) {
     const KvcacheKernelParams& kp = rp.kp;
     const bool paged = kp.block_table != nullptr;
     if (kp.k_new != nullptr && rp.cu_kn != nullptr && rp.total_kn > 0) {
@@ -144,7 +144,10 @@ hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s,
     }
     if (rp.total_q > 0) {
         const int64_t grid = (int64_t)rp.slots * kp.h_k * kp.n_split;
-        if (cap_pre > 0.f) {    // soft-capped scores: the attention kernels of fa_fwd_kvcache_softcap.hip between this file's append and combine
+        if (row_tile == kKvcPrefillRows) {     // 64-row workgroups: the attention kernels of fa_fwd_kvcache_prefill.hip
+            const hipError_t e = launch_kvcache_ragged_prefill_attn(rp, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
+            if (e != hipSuccess) return e;
+        } else if (cap_pre > 0.f) {    // soft-capped scores: the attention kernels of fa_fwd_kvcache_softcap.hip between this file's append and combine
             const hipError_t e = launch_kvcache_ragged_softcap_attn(rp, cap_pre, std::is_same_v<T, _Float16> ? 0 : 1, (unsigned)grid, s);
             if (e != hipSuccess) return e;
         } else if (sink.ptr != nullptr && kp.n_split == 1) {    // sinks, unsplit: the attention kernels of fa_fwd_kvcache_sink.hip
@@ -167,8 +170,8 @@ hipError_t launch_kvcache_ragged_t(const KvcacheRaggedParams& rp, hipStream_t s,
 }
 
 template <typename T, int D>
-hipError_t launch_kvcache_ragged_es(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre, const KvcacheSink& sink, const KvcacheTree& tree) {
-    return rp.kp.cache_fp8 ? launch_kvcache_ragged_t<T, D, 1>(rp, s, cap_pre, sink, tree) : launch_kvcache_ragged_t<T, D, 2>(rp, s, cap_pre, sink, tree);
+hipError_t launch_kvcache_ragged_es(const KvcacheRaggedParams& rp, hipStream_t s, float cap_pre, const KvcacheSink& sink, const KvcacheTree& tree, int32_t row_tile) {
+    return rp.kp.cache_fp8 ? launch_kvcache_ragged_t<T, D, 1>(rp, s, cap_pre, sink, tree, row_tile) : launch_kvcache_ragged_t<T, D, 2>(rp, s, cap_pre, sink, tree, row_tile);
 }
 
 }  // namespace
@@ -176,19 +179,20 @@ hipError_t launch_kvcache_ragged_es(const KvcacheRaggedParams& rp, hipStream_t s
 #ifndef FA_KVC_D256_TU      // (fa_fwd_kvcache_d256.hip includes this file for the templates above)
 // kp.seqlen_q = max_seqlen_q sizes the split exactly as the dense launcher does (kvcache_steps), so a forced split cuts the keys where the dense
 // call with seqlen_q = max_seqlen_q cuts them.
-hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t s, float cap_pre, KvcacheSink sink, KvcacheTree tree) {
+hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t s, float cap_pre, KvcacheSink sink, KvcacheTree tree, int32_t row_tile) {
+    if (!kvcache_row_tile_ok(row_tile)) return hipErrorInvalidValue;
     KvcacheKernelParams& kp = rp.kp;
-    kp.n_row_tiles = (int32_t)(((int64_t)kp.seqlen_q * kp.h_ratio + kKvcRows - 1) / kKvcRows);
+    kp.n_row_tiles = (int32_t)(((int64_t)kp.seqlen_q * kp.h_ratio + row_tile - 1) / row_tile);
     kp.rows_total = (int64_t)kp.h * rp.total_q;
-    rp.slots = (int32_t)kvcache_ragged_slots(kp, rp.total_q, &rp.compact);
+    rp.slots = (int32_t)kvcache_ragged_slots(kp, rp.total_q, &rp.compact, row_tile);
     const int64_t steps = kvcache_steps(kp);
     if (kp.n_split < 1) kp.n_split = 1;
     kp.split_keys = (int32_t)(((steps + kp.n_split - 1) / kp.n_split) * kKvcStep);
     if (kp.split_keys <= 0) kp.split_keys = kKvcStep;
     if (kp.n_split > 1) kp.ws_lse = kp.ws_o + (int64_t)kp.n_split * kp.rows_total * kp.d;
     if (kp.d == 256) return launch_kvcache_ragged_d256(rp, dtype, s, cap_pre);
-    if (dtype == 0) return kp.d == 64 ? launch_kvcache_ragged_es<_Float16, 64>(rp, s, cap_pre, sink, tree) : launch_kvcache_ragged_es<_Float16, 128>(rp, s, cap_pre, sink, tree);
-    return kp.d == 64 ? launch_kvcache_ragged_es<__bf16, 64>(rp, s, cap_pre, sink, tree) : launch_kvcache_ragged_es<__bf16, 128>(rp, s, cap_pre, sink, tree);
+    if (dtype == 0) return kp.d == 64 ? launch_kvcache_ragged_es<_Float16, 64>(rp, s, cap_pre, sink, tree, row_tile) : launch_kvcache_ragged_es<_Float16, 128>(rp, s, cap_pre, sink, tree, row_tile);
+    return kp.d == 64 ? launch_kvcache_ragged_es<__bf16, 64>(rp, s, cap_pre, sink, tree, row_tile) : launch_kvcache_ragged_es<__bf16, 128>(rp, s, cap_pre, sink, tree, row_tile);
 }
 #endif  // FA_KVC_D256_TU
 

@@ -159,9 +159,15 @@ struct KvcacheKernelParams {
 };
 constexpr int kKvcRows = 16;    // packed query rows of a workgroup (one 16x16x32 MFMA tile)
 constexpr int kKvcStep = 32;    // keys of one wave step (the split granularity)
+constexpr int kKvcPrefillRows = 64;     // packed query rows of a workgroup of the wide kernels (fa_fwd_kvcache_prefill.hip): 16 per wave
+// the row tiles a launch can be sized with; launch_fwd_kvcache / launch_fwd_kvcache_ragged return hipErrorInvalidValue for anything else,
+// so that a grid is never sized by one value and run by the kernels of another
+inline bool kvcache_row_tile_ok(int32_t row_tile) { return row_tile == kKvcRows || row_tile == kKvcPrefillRows; }
 // total_q >= 0: a ragged call (below) with that many packed query rows - the partial planes have h * total_q rows and the automatic split
 // counts the compact grid's tile slots in place of b x row tiles; -1: the dense call
-int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_t requested, int64_t total_q = -1);   // key splits of a launch (>= 1)
+// row_tile: the packed query rows of a workgroup the launch is sized with - kKvcRows, or kKvcPrefillRows for the 64-row kernels of
+// fa_fwd_kvcache_prefill.hip (fa_kvcache_options_v8.row_tile); the automatic split counts that grid's workgroups
+int32_t kvcache_split(const KvcacheKernelParams& kp, int64_t avail_bytes, int32_t requested, int64_t total_q = -1, int32_t row_tile = kKvcRows);   // key splits of a launch (>= 1)
 int64_t kvcache_workspace_bytes(const KvcacheKernelParams& kp, int32_t n_split, int64_t total_q = -1);
 // Attention sinks (fa_fwd_kvcache_sink.hip, fa_kvcache_options_v6.sinks): query head hq has the logit ptr[hq * stride] (fp32, device memory,
 // natural-log units of the final scores) in the softmax denominator; ptr = NULL: off.
@@ -179,8 +185,9 @@ struct KvcacheTree {
 // cap_pre > 0: soft-capped scores (below) - the attention launch goes to fa_fwd_kvcache_softcap.hip, the append and the combine stay
 // sink.ptr != NULL: attention sinks (below) - an unsplit attention launch and the combine of a split one go to fa_fwd_kvcache_sink.hip
 // tree.ptr != NULL: a tree mask (below) - the attention launch goes to fa_fwd_kvcache_tree.hip, the append and the combine stay
+// row_tile = kKvcPrefillRows: the attention launch goes to fa_fwd_kvcache_prefill.hip on a grid of 64-row tiles, the append and the combine stay
 hipError_t launch_fwd_kvcache(KvcacheKernelParams kp, int dtype, hipStream_t stream, float cap_pre = 0.f, KvcacheSink sink = KvcacheSink{nullptr, 0},
-                              KvcacheTree tree = KvcacheTree{nullptr, 0, 0});
+                              KvcacheTree tree = KvcacheTree{nullptr, 0, 0}, int32_t row_tile = kKvcRows);
 
 // Ragged query batches (fa_fwd_kvcache_ragged.hip, fa_kvcache_options_v4): q / o are packed (total_q, h, d), sequence i owns rows cu_q[i] ..
 // cu_q[i + 1] - 1 and is tiled on its own (packed row r = t * h_ratio + j in tiles of kKvcRows from the sequence's first row), k_new / v_new are
@@ -196,10 +203,10 @@ struct KvcacheRaggedParams {
     int32_t slots;              // filled by the launcher: tile slots per KV head of the attention grid
     int32_t compact;            // filled by the launcher: 1 = slots are looked up in cu_q (kvc_slot_lookup), 0 = slot = sequence x tiles(max_seqlen_q) + tile
 };
-// tile slots per KV head of a ragged launch: min(ceil(total_q * h_ratio / kKvcRows) + b, b * tiles(max_seqlen_q)); *compact says which
-int64_t kvcache_ragged_slots(const KvcacheKernelParams& kp, int64_t total_q, int32_t* compact);
+// tile slots per KV head of a ragged launch: min(ceil(total_q * h_ratio / row_tile) + b, b * tiles(max_seqlen_q)); *compact says which
+int64_t kvcache_ragged_slots(const KvcacheKernelParams& kp, int64_t total_q, int32_t* compact, int32_t row_tile = kKvcRows);
 hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t stream, float cap_pre = 0.f, KvcacheSink sink = KvcacheSink{nullptr, 0},
-                                     KvcacheTree tree = KvcacheTree{nullptr, 0, 0});
+                                     KvcacheTree tree = KvcacheTree{nullptr, 0, 0}, int32_t row_tile = kKvcRows);
 
 // Soft-capped scores (fa_fwd_kvcache_softcap.hip, fa_kvcache_options_v5.softcap > 0): score = softcap * tanh(q . k * softmax_scale / softcap).
 // The kernels are kvcache_attn with SOFTCAP = true and read kp.scale = softcap, kp.scale_log2e = softcap * log2(e) (the host puts the cap where
@@ -252,6 +259,14 @@ struct KvcacheRaggedTreeParams {
 };
 hipError_t launch_kvcache_tree_attn(const KvcacheKernelParams& kp, const KvcacheTree& tree, int dtype, unsigned grid, hipStream_t stream);
 hipError_t launch_kvcache_ragged_tree_attn(const KvcacheRaggedParams& rp, const KvcacheTree& tree, int dtype, unsigned grid, hipStream_t stream);
+
+// 64-row workgroups for prompt chunks (fa_fwd_kvcache_prefill.hip, fa_kvcache_options_v8.row_tile = 64): four waves of 16 rows each walk the same
+// 32-key steps over K / V images staged once per workgroup in LDS, double-buffered; no merge of waves, the epilogue writes o / lse or the partial
+// planes of the decode kernels.  The kernels read KvcacheKernelParams / KvcacheRaggedParams as they are, with n_row_tiles / slots counted in tiles
+// of kKvcPrefillRows.  They launch the attention kernel alone, split or not; the append in front and the combine behind are the unchanged ones.
+// A window, a soft cap, sinks, a tree mask, rotary and head_dim 256 are refused by the C ABI with row_tile = 64.
+hipError_t launch_kvcache_prefill_attn(const KvcacheKernelParams& kp, int dtype, unsigned grid, hipStream_t stream);
+hipError_t launch_kvcache_ragged_prefill_attn(const KvcacheRaggedParams& rp, int dtype, unsigned grid, hipStream_t stream);
 
 // Rotary embedding on a decode call (fa_kvcache_rotary.hip, fa_kvcache_options_v3).  One fused launch takes the place of the append: it
 // rotates k_new into the cache, copies / quantises v_new, and writes the rotated q into `q_image`, a contiguous (b, seqlen_q, h, d) buffer of

@@ -274,7 +274,8 @@ std::vector<at::Tensor> mha_varlen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
 // launch; out comes back packed and lse as (h, total_q).  The cu_seqlens tensors stay on the device like cache_seqlens.  softmax_scale (None = 1 /
 // sqrt(d)) and softcap (0 = off) are the two host scalars of fa_kvcache_options_v5; they are validated by the library.  sinks (float32 (nheads,), any stride): the
 // attention sinks of fa_kvcache_options_v6, one logit per query head, read on the device like the descales.  tree_mask (int64 (batch, seqlen_q), ragged
-// (total_q,), any strides): the tree attention mask of fa_kvcache_options_v7, one word per query row, read on the device in place.
+// (total_q,), any strides): the tree attention mask of fa_kvcache_options_v7, one word per query row, read on the device in place.  prefill: the
+// 64-row attention kernels for prompt chunks (fa_kvcache_options_v8.row_tile = 64); what they do not serve is refused by the library.
 std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, c10::optional<at::Tensor> k_new_,
                                         c10::optional<at::Tensor> v_new_, c10::optional<at::Tensor> cache_seqlens_, bool is_causal,
                                         int64_t num_splits, c10::optional<at::Tensor> block_table_, int64_t window_size_left,
@@ -282,7 +283,7 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
                                         c10::optional<at::Tensor> rotary_cos_, c10::optional<at::Tensor> rotary_sin_, bool rotary_interleaved,
                                         c10::optional<at::Tensor> cu_seqlens_q_, int64_t max_seqlen_q, c10::optional<at::Tensor> cu_seqlens_k_new_,
                                         c10::optional<double> softmax_scale, double softcap, c10::optional<at::Tensor> sinks_,
-                                        c10::optional<at::Tensor> tree_mask_) {
+                                        c10::optional<at::Tensor> tree_mask_, bool prefill) {
     const bool ragged = cu_seqlens_q_.has_value();
     at::Tensor cu_seqlens_q, cu_seqlens_k_new;
     auto cu_tensor = [&](const at::Tensor& t, const char* name) {
@@ -389,7 +390,7 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
         p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr(); p.seqlen_new = (int32_t)(ragged ? std::min<int64_t>(k_new.size(1), seqlen_cache) : k_new.size(1));
         p.k_new_stride = strides4(k_new); p.v_new_stride = strides4(v_new);
     }
-    fa_kvcache_options_v7 opt;
+    fa_kvcache_options_v8 opt;
     FA_PARAMS_INIT(opt);
     // (rounded once to fp32; 0 means "the default" in the C ABI, so a given scale that is or rounds to 0 is refused here)
     TORCH_CHECK(!softmax_scale.has_value() || (std::isfinite(*softmax_scale) && (float)*softmax_scale > 0.f && std::isfinite((float)*softmax_scale)),
@@ -458,7 +459,8 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
         }
         opt.tree_mask = tree_mask.data_ptr<int64_t>();
     }
-    const fa_kvcache_options* opts = (opt.is_local || fp8 || rotary_cos.defined() || ragged || scaled || sinks.defined() || tree_mask.defined()) ? (const fa_kvcache_options*)&opt : nullptr;
+    if (prefill) opt.row_tile = 64;
+    const fa_kvcache_options* opts = (opt.is_local || fp8 || rotary_cos.defined() || ragged || scaled || sinks.defined() || tree_mask.defined() || prefill) ? (const fa_kvcache_options*)&opt : nullptr;
     at::Tensor workspace;
     const int64_t ws_bytes = fa_kvcache_workspace_bytes_ex(&p, opts);
     if (ws_bytes < 0) check_status((int)ws_bytes);
@@ -535,7 +537,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              c10::optional<at::Tensor> k_descale, c10::optional<at::Tensor> v_descale, c10::optional<at::Tensor> rotary_cos, c10::optional<at::Tensor> rotary_sin,
              bool rotary_interleaved) {
               return mha_fwd_kvcache(q, k_cache, v_cache, k_new, v_new, cache_seqlens, is_causal, num_splits, block_table, window_size_left, window_size_right, k_descale,
-                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, c10::nullopt, 0, c10::nullopt, c10::nullopt, 0.0, c10::nullopt, c10::nullopt);
+                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, c10::nullopt, 0, c10::nullopt, c10::nullopt, 0.0, c10::nullopt, c10::nullopt, false);
           },
           "Decode forward over a KV cache (in-place append of k / v, split-KV attention)", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
@@ -548,7 +550,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              c10::optional<at::Tensor> k_descale, c10::optional<at::Tensor> v_descale, c10::optional<at::Tensor> rotary_cos, c10::optional<at::Tensor> rotary_sin,
              bool rotary_interleaved, c10::optional<at::Tensor> cu_seqlens_q, int64_t max_seqlen_q, c10::optional<at::Tensor> cu_seqlens_k_new) {
               return mha_fwd_kvcache(q, k_cache, v_cache, k_new, v_new, cache_seqlens, is_causal, num_splits, block_table, window_size_left, window_size_right, k_descale,
-                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new, c10::nullopt, 0.0, c10::nullopt, c10::nullopt);
+                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new, c10::nullopt, 0.0, c10::nullopt, c10::nullopt, false);
           },
           "The same with a ragged query batch: packed q / k / v under cu_seqlens_q / cu_seqlens_k_new", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
@@ -563,7 +565,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              bool rotary_interleaved, c10::optional<at::Tensor> cu_seqlens_q, int64_t max_seqlen_q, c10::optional<at::Tensor> cu_seqlens_k_new,
              c10::optional<double> softmax_scale, double softcap) {
               return mha_fwd_kvcache(q, k_cache, v_cache, k_new, v_new, cache_seqlens, is_causal, num_splits, block_table, window_size_left, window_size_right, k_descale,
-                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new, softmax_scale, softcap, c10::nullopt, c10::nullopt);
+                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new, softmax_scale, softcap, c10::nullopt, c10::nullopt, false);
           },
           "The same with a softmax scale other than 1 / sqrt(head_dim) and / or soft-capped scores", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
@@ -581,7 +583,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              bool rotary_interleaved, c10::optional<at::Tensor> cu_seqlens_q, int64_t max_seqlen_q, c10::optional<at::Tensor> cu_seqlens_k_new,
              c10::optional<double> softmax_scale, double softcap, c10::optional<at::Tensor> sinks) {
               return mha_fwd_kvcache(q, k_cache, v_cache, k_new, v_new, cache_seqlens, is_causal, num_splits, block_table, window_size_left, window_size_right, k_descale,
-                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new, softmax_scale, softcap, sinks, c10::nullopt);
+                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new, softmax_scale, softcap, sinks, c10::nullopt, false);
           },
           "fwd_kvcache with attention sinks: one float32 logit per query head in the softmax denominator", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
@@ -592,13 +594,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("softmax_scale") = py::none(), py::arg("softcap") = 0.0, py::arg("sinks") = py::none());
     // Tree attention masks: the same arguments continued by `tree_mask`, again on a function of its own - fwd_kvcache keeps its three overloads and
     // fwd_kvcache_sinks its signature, and a call without tree_mask never comes here.
-    m.def("fwd_kvcache_tree", &mha_fwd_kvcache, "fwd_kvcache with a tree attention mask: one int64 word per query row over the last seqlen_q keys", py::arg("q"),
+    m.def("fwd_kvcache_tree",
+          [](at::Tensor q, at::Tensor k_cache, at::Tensor v_cache, c10::optional<at::Tensor> k_new, c10::optional<at::Tensor> v_new, c10::optional<at::Tensor> cache_seqlens,
+             bool is_causal, int64_t num_splits, c10::optional<at::Tensor> block_table, int64_t window_size_left, int64_t window_size_right,
+             c10::optional<at::Tensor> k_descale, c10::optional<at::Tensor> v_descale, c10::optional<at::Tensor> rotary_cos, c10::optional<at::Tensor> rotary_sin,
+             bool rotary_interleaved, c10::optional<at::Tensor> cu_seqlens_q, int64_t max_seqlen_q, c10::optional<at::Tensor> cu_seqlens_k_new,
+             c10::optional<double> softmax_scale, double softcap, c10::optional<at::Tensor> sinks, c10::optional<at::Tensor> tree_mask) {
+              return mha_fwd_kvcache(q, k_cache, v_cache, k_new, v_new, cache_seqlens, is_causal, num_splits, block_table, window_size_left, window_size_right, k_descale,
+                                     v_descale, rotary_cos, rotary_sin, rotary_interleaved, cu_seqlens_q, max_seqlen_q, cu_seqlens_k_new, softmax_scale, softcap, sinks, tree_mask, false);
+          },
+          "fwd_kvcache with a tree attention mask: one int64 word per query row over the last seqlen_q keys", py::arg("q"),
           py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
           py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("block_table") = py::none(), py::arg("window_size_left") = -1,
           py::arg("window_size_right") = -1, py::kw_only(), py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none(),
           py::arg("rotary_cos") = py::none(), py::arg("rotary_sin") = py::none(), py::arg("rotary_interleaved") = true,
           py::arg("cu_seqlens_q") = py::none(), py::arg("max_seqlen_q") = 0, py::arg("cu_seqlens_k_new") = py::none(),
           py::arg("softmax_scale") = py::none(), py::arg("softcap") = 0.0, py::arg("sinks") = py::none(), py::arg("tree_mask") = py::none());
+    // 64-row kernels for prompt chunks: the same arguments continued by `prefill`, once more on a function of its own - fwd_kvcache keeps its three
+    // overloads, fwd_kvcache_sinks and fwd_kvcache_tree their signatures, and a call without prefill=True never comes here.
+    m.def("fwd_kvcache_prefill", &mha_fwd_kvcache, "fwd_kvcache on the 64-row attention kernels for prompt chunks (prefill=True)", py::arg("q"),
+          py::arg("k_cache"), py::arg("v_cache"), py::arg("k_new") = py::none(), py::arg("v_new") = py::none(), py::arg("cache_seqlens") = py::none(),
+          py::arg("is_causal") = false, py::arg("num_splits") = 0, py::arg("block_table") = py::none(), py::arg("window_size_left") = -1,
+          py::arg("window_size_right") = -1, py::kw_only(), py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none(),
+          py::arg("rotary_cos") = py::none(), py::arg("rotary_sin") = py::none(), py::arg("rotary_interleaved") = true,
+          py::arg("cu_seqlens_q") = py::none(), py::arg("max_seqlen_q") = 0, py::arg("cu_seqlens_k_new") = py::none(),
+          py::arg("softmax_scale") = py::none(), py::arg("softcap") = 0.0, py::arg("sinks") = py::none(), py::arg("tree_mask") = py::none(),
+          py::arg("prefill") = false);
     m.def("attn_autograd", &attn_autograd, "differentiable forward (C++ autograd node over fwd / bwd)");
     m.def("attn_varlen_autograd", &attn_varlen_autograd, "differentiable packed forward (C++ autograd node over varlen_fwd / varlen_bwd)");
     m.def("abi_version", []() { return fa_abi_version(); });

@@ -117,6 +117,11 @@ class KvcacheOptionsV7(_Params):
                                             ("reserved3", ctypes.c_int64 * 2)]
 
 
+class KvcacheOptionsV8(_Params):
+    """fa_kvcache_options_v8: fa_kvcache_options_v7 plus row_tile (0 = the 16-row kernels, 64 = the 64-row kernels for prompt chunks) and six reserved words"""
+    _fields_ = KvcacheOptionsV7._fields_ + [("row_tile", _i32), ("reserved4_", _i32), ("reserved4", ctypes.c_int64 * 5)]
+
+
 FA_CACHE_FP8_E4M3 = 1
 
 
@@ -156,13 +161,15 @@ def lib():
         L.fa_kvcache_workspace_bytes.restype = ctypes.c_int64
         L.fa_kvcache_num_splits.argtypes = [ctypes.POINTER(KvcacheParams)]
         L.fa_kvcache_num_splits.restype = ctypes.c_int32
-        _op = ctypes.c_void_p                       # fa_kvcache_options, _v2 .. _v7 (told apart by struct_size)
+        _op = ctypes.c_void_p                       # fa_kvcache_options, _v2 .. _v8 (told apart by struct_size)
         L.fa_run_mha_fwd_kvcache_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op, _vp]
         L.fa_run_mha_fwd_kvcache_ex.restype = ctypes.c_int
         L.fa_kvcache_workspace_bytes_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op]
         L.fa_kvcache_workspace_bytes_ex.restype = ctypes.c_int64
         L.fa_kvcache_num_splits_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op]
         L.fa_kvcache_num_splits_ex.restype = ctypes.c_int32
+        L.fa_kvcache_row_tile_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op]
+        L.fa_kvcache_row_tile_ex.restype = ctypes.c_int32
         L.fa_mha_fwd.argtypes = [_vp] * 5 + [_i32] * 8 + [_vp]
         L.fa_mha_bwd.argtypes = [_vp] * 10 + [_i32] * 8 + [_vp]
         L.fa_mha_varlen_fwd.argtypes = [_vp] * 7 + [_i32] * 8 + [_vp]
@@ -388,20 +395,22 @@ def _kvcache_params_ragged(q, k_cache, v_cache, o, lse, cache_seqlens, k_new, v_
 
 
 def kvcache_options(window_size=(-1, -1), cache_dtype=0, k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None, rotary_interleaved=True, *,
-                    cu_seqlens_q=None, cu_seqlens_k_new=None, total_q=0, total_k_new=0, softmax_scale=None, softcap=None, sinks=None, tree_mask=None):
+                    cu_seqlens_q=None, cu_seqlens_k_new=None, total_q=0, total_k_new=0, softmax_scale=None, softcap=None, sinks=None, tree_mask=None, row_tile=None):
     """fa_kvcache_options with a sliding window (left, right); (-1, -1) gives a zeroed struct (no window).  With cache_dtype
     (FA_CACHE_FP8_E4M3) or a descale (float32 (b, h_k) torch tensors, any strides) the struct is fa_kvcache_options_v2; with rotary_cos /
     rotary_sin ((seqlen_ro, rotary_dim / 2) torch tensors of q's dtype with one row stride) it is fa_kvcache_options_v3; with cu_seqlens_q /
     cu_seqlens_k_new (int32 (b + 1,) torch tensors) and the packed row counts total_q / total_k_new it is fa_kvcache_options_v4; with softmax_scale or
     softcap (Python floats; None = not given) it is fa_kvcache_options_v5; with sinks (a float32 (nheads,) torch tensor, any stride) it is
-    fa_kvcache_options_v6; with tree_mask (an int64 torch tensor, (b, seqlen_q) or, ragged, (total_q,), any strides) it is fa_kvcache_options_v7."""
-    v7 = tree_mask is not None
+    fa_kvcache_options_v6; with tree_mask (an int64 torch tensor, (b, seqlen_q) or, ragged, (total_q,), any strides) it is fa_kvcache_options_v7; with row_tile (a Python int; None = not given) it is
+    fa_kvcache_options_v8."""
+    v8 = row_tile is not None
+    v7 = v8 or tree_mask is not None
     v6 = v7 or sinks is not None
     v5 = v6 or softmax_scale is not None or softcap is not None
     v4 = v5 or cu_seqlens_q is not None or cu_seqlens_k_new is not None
     v3 = rotary_cos is not None or rotary_sin is not None
     v2 = v3 or cache_dtype != 0 or k_descale is not None or v_descale is not None
-    o = KvcacheOptionsV7() if v7 else KvcacheOptionsV6() if v6 else KvcacheOptionsV5() if v5 else KvcacheOptionsV4() if v4 else KvcacheOptionsV3() if v3 else KvcacheOptionsV2() if v2 else KvcacheOptions()
+    o = KvcacheOptionsV8() if v8 else KvcacheOptionsV7() if v7 else KvcacheOptionsV6() if v6 else KvcacheOptionsV5() if v5 else KvcacheOptionsV4() if v4 else KvcacheOptionsV3() if v3 else KvcacheOptionsV2() if v2 else KvcacheOptions()
     if v4:
         o.cu_seqlens_q = None if cu_seqlens_q is None else cu_seqlens_q.data_ptr()
         o.cu_seqlens_k_new = None if cu_seqlens_k_new is None else cu_seqlens_k_new.data_ptr()
@@ -412,7 +421,9 @@ def kvcache_options(window_size=(-1, -1), cache_dtype=0, k_descale=None, v_desca
         o.softcap = 0.0 if softcap is None else float(softcap)
     if v6 and sinks is not None:
         o.sinks, o.sinks_stride = sinks.data_ptr(), sinks.stride(0)
-    if v7:
+    if v8:
+        o.row_tile = int(row_tile)
+    if v7 and tree_mask is not None:
         o.tree_mask = tree_mask.data_ptr()
         o.tree_mask_batch_stride, o.tree_mask_row_stride = (0, tree_mask.stride(0)) if tree_mask.dim() == 1 else (tree_mask.stride(0), tree_mask.stride(1))
     left, right = window_size
@@ -444,6 +455,14 @@ def kvcache_workspace_bytes(params, options=None) -> int:
 def kvcache_num_splits(params, options=None) -> int:
     """fa_kvcache_num_splits[_ex]: key splits the launch of these params would use (their workspace fields included)"""
     n = lib().fa_kvcache_num_splits(ctypes.byref(params)) if options is None else lib().fa_kvcache_num_splits_ex(ctypes.byref(params), ctypes.byref(options))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def kvcache_row_tile(params, options=None) -> int:
+    """fa_kvcache_row_tile_ex: packed query rows per workgroup of the attention launch these params and options would make (16 or 64)"""
+    n = lib().fa_kvcache_row_tile_ex(ctypes.byref(params), None if options is None else ctypes.byref(options))
     if n < 0:
         check(int(n))
     return int(n)

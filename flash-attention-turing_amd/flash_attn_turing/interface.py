@@ -247,6 +247,22 @@ def tree_mask_from_parents(parents):
     return words
 
 
+def _check_prefill(q, window, softcap, sinks, tree_mask, rotary_cos, rotary_sin):
+    """prefill=True: the 64-row kernels serve the plain and the causal call; not a window, a soft cap, sinks, a tree mask, rotary or head_dim 256"""
+    if window != (-1, -1):
+        raise ValueError(f"prefill=True together with window_size {window} is not supported")
+    if softcap != 0.0:
+        raise ValueError("prefill=True together with softcap > 0 is not supported")
+    if sinks is not None:
+        raise ValueError("prefill=True together with sinks is not supported")
+    if tree_mask is not None:
+        raise ValueError("prefill=True together with tree_mask is not supported")
+    if rotary_cos is not None or rotary_sin is not None:
+        raise ValueError("prefill=True together with rotary_cos / rotary_sin is not supported")
+    if q.shape[-1] == 256:
+        raise ValueError("prefill=True at head_dim 256 is not supported: flash_attn_with_kvcache has the 64-row kernels at head_dim 64 and 128")
+
+
 def _check_kvcache_head_dim(q):
     """decode over a KV cache has head_dim 64, 128 and 256 (fwd / bwd / varlen_*: 64 and 128)"""
     if q.shape[-1] not in (64, 128, 256):
@@ -301,7 +317,7 @@ def _check_ragged(q, k_cache, k, v, cache_seqlens, block_table, k_descale, v_des
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, causal=False, num_splits=0, return_softmax_lse=False, *,
                             block_table=None, window_size=(-1, -1), k_descale=None, v_descale=None, rotary_cos=None, rotary_sin=None,
                             rotary_interleaved=True, cu_seqlens_q=None, max_seqlen_q=None, cu_seqlens_k_new=None, softmax_scale=None,
-                            softcap=0.0, sinks=None, tree_mask=None):
+                            softcap=0.0, sinks=None, tree_mask=None, prefill=False):
     """Decode attention over a KV cache (upstream flash-attn's ``flash_attn_with_kvcache`` conventions; forward only).
 
     q: (batch, seqlen_q, nheads, d); k_cache, v_cache: (batch, seqlen_cache, nheads_k, d), any batch / row / head strides (used in place).
@@ -455,6 +471,29 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     tree_mask together with causal=True, with a window_size other than (-1, -1), with softcap > 0, with sinks, with rotary_cos /
     rotary_sin (a node's position is its depth, not its index: the engine rotates), at head_dim 256, and with seqlen_q / max_seqlen_q
     above 64.  Also ValueErrors: a tree_mask that is not a tensor, not int64, of the wrong rank or shape, or on another device.
+
+    Prompt chunks: prefill (keyword, bool, default False).  By default the seqlen_q x (nheads / nheads_k) packed query rows of a KV head go
+    through the kernels in tiles of 16 and every tile streams the visible K / V of its head on its own: right for decode, wrong for a chunk
+    of a prompt (a 2048-token chunk at nheads / nheads_k = 4 is 512 tiles per KV head).  flash_attn_func / varlen cannot read a paged or 8-bit
+    cache, take lengths from the device or append; with prefill=True the attention launch of THIS call uses kernels whose workgroup serves 64
+    packed rows of one (sequence, KV head, key split): four waves of 16 rows each walk the same 32-key steps, and the K / V rows of a step
+    are loaded once per workgroup into shared memory.  The append in front and the split partials and their combine behind are the same code.
+    Each sequence is tiled on its own from its first packed row (a 64-row tile never spans two sequences); the automatic key split is the
+    same rule evaluated with the wide grid's workgroup count, a forced num_splits cuts the keys where it cuts them with prefill=False, and
+    under ``causal`` a tile reads no key past the last one its last row sees.  Supported: dense and cu_seqlens_q calls, contiguous and
+    paged caches, the FP8 cache with descales (read and append side), k / v append (packed or dense), causal, GQA / MQA, fp16 / bf16,
+    head_dim 64 / 128, softmax_scale, num_splits, return_softmax_lse, and graph capture - no host synchronisation: lengths, tables,
+    descales and cu_seqlens are read on the device.  Values: fp32 math over the visible keys, the tolerances of the 16-row path.  The bits
+    may differ from prefill=False because the summation order differs: NO bit relation between the two is promised.  Bit for bit: paged ==
+    contiguous over the same logical cache; sequence i of a ragged prefill call == the dense prefill call on it alone, in out, lse and
+    every cache byte, for num_splits=1 and for any forced split (there is no window, so the cuts coincide); run-to-run determinism per
+    split count.  Unchanged: a row that sees no key is O = 0, LSE = 0; a NaN query row, or a NaN / +inf score, gives a NaN row; cache rows
+    at or past L_i, packed rows past cu_seqlens_q[-1] and table entries of pages wholly past L_i never reach a result; a non-finite V
+    element that another row of the tile sees, but this row does not, can make this row NaN (0 x NaN), as above.  prefill applies to the
+    whole call: a decoding sequence in such a call fills 4 of 64 rows at nheads / nheads_k = 4.  Choosing the tile automatically, per call
+    or per sequence, is out of scope (it would change the bits of existing calls).  Not supported, a ValueError that names the argument:
+    prefill=True together with a window_size other than (-1, -1), with softcap > 0, with sinks, with tree_mask, with rotary_cos /
+    rotary_sin, and at head_dim 256; also a prefill that is not a bool.
     """
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k_cache, v_cache, k, v, sinks if isinstance(sinks, torch.Tensor) else None)):
         raise RuntimeError("flash_attn_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
@@ -476,6 +515,13 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     if tree_mask is not None:
         extra = dict(extra, tree_mask=_check_tree_mask(tree_mask, q, causal, (left, right), softcap, sinks, rotary_cos, rotary_sin, cu_seqlens_q, max_seqlen_q))
         fwd_kvcache = _C.fwd_kvcache_tree
+    # (prefill: likewise a function of its own, which continues the arguments of fwd_kvcache_tree)
+    if not isinstance(prefill, bool):
+        raise ValueError(f"prefill must be a bool, got {prefill!r}")
+    if prefill:
+        _check_prefill(q, (left, right), softcap, sinks, tree_mask, rotary_cos, rotary_sin)
+        extra = dict(extra, prefill=True)
+        fwd_kvcache = _C.fwd_kvcache_prefill
     if cu_seqlens_q is None:
         if cu_seqlens_k_new is not None:
             raise ValueError("cu_seqlens_k_new given without cu_seqlens_q (packed k / v belong to a ragged call)")

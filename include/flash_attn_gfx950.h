@@ -559,6 +559,72 @@ typedef struct fa_kvcache_options_v7 {      /* FA_PARAMS_INIT(o); then fa_..._ex
     int64_t reserved3[2];       /* 0 */
 } fa_kvcache_options_v7;
 
+/* 64-row workgroups for prompt chunks (FA_HAS_KVCACHE_PREFILL): fa_kvcache_options_v8 below is fa_kvcache_options_v7 with optional fields
+ * appended; the _ex entry points accept exactly the eight sizes (20, 72, 112, 144, 168, 200, 240, 288 bytes), and a v8 struct with a zeroed
+ * tail is a v7 call: same kernels, split, workspace and bits.  FA_ABI_VERSION is unchanged.
+ *   row_tile: 0 = the 16-row kernels (every call above), 64 = the wide kernels; anything else is FA_ERR_BAD_SHAPE.
+ *   The decode kernels cut the seqlen_q x (h / h_k) packed query rows of a KV head into tiles of 16, and every tile streams the visible K / V
+ *   of its head on its own: right for decode, wrong for a chunk of a prompt (a 2048-token chunk at h / h_k = 4 is 512 tiles per KV head).  With
+ *   row_tile = 64 the attention launch of the call uses kernels whose workgroup serves 64 packed rows of one (sequence, KV head, key split):
+ *   four waves of 16 rows each walk the same 32-key steps, and the K / V rows of a step are loaded once per workgroup into LDS images all four
+ *   read.  Everything in front (the append) and behind (the partial planes, the combine) is the existing code.  Each sequence is tiled on its
+ *   own from its first packed row; the ragged grid has min(ceil(total_q * h_ratio / 64) + b, b * tiles64(max_seqlen_q)) slots per KV head.  The
+ *   automatic key split is the existing rule evaluated with the wide grid's workgroup count; a forced num_splits cuts the keys where it cuts
+ *   them with row_tile = 0; the workspace formula is unchanged.  Under is_causal a tile's key range ends at the last key its last row sees.
+ *   Values: fp32 math over the visible keys, the tolerances of the 16-row path.  The bits may differ from row_tile = 0 (the summation order
+ *   differs); no bit relation between the two is promised.  Bit for bit: paged == contiguous over the same logical cache; sequence i of a
+ *   ragged row_tile = 64 call == the dense row_tile = 64 call on it alone, in o, lse and every cache byte, for num_splits = 1 and for any forced
+ *   split (there is no window, so the cuts coincide); run-to-run determinism per split count.  Unchanged: a row that sees no key is o = 0,
+ *   lse = 0; a NaN query row, or a NaN / +inf score, gives a NaN row; cache rows at or past L_i, packed rows past cu_seqlens_q[b] and table
+ *   entries of pages wholly past L_i never reach a result; a non-finite V element within the 16 keys of an MFMA block that another row of the
+ *   tile sees can make a row NaN that does not see it (0 x NaN), as with row_tile = 0.  row_tile applies to the whole call: a decoding
+ *   sequence in such a call fills 4 of 64 rows at h / h_k = 4.  Choosing the tile automatically is out of scope.
+ * Supported with row_tile = 64: dense and cu_seqlens_q calls, contiguous and paged caches, the 8-bit cache with descales (read and append side),
+ * k_new / v_new, is_causal, GQA / MQA, fp16 / bf16, d = 64 / 128, softmax_scale, num_splits; no host synchronisation (lengths, tables, descales
+ * and cu_seqlens are read on the device: a captured call replays with the values then in memory).
+ * Not supported, FA_ERR_BAD_SHAPE with the field named by fa_last_error: row_tile = 64 together with a window other than (-1, -1), with
+ * softcap > 0, with sinks, with tree_mask, with rotary_cos / rotary_sin, and at d = 256.  A non-zero `reserved4_` / `reserved4` is
+ * FA_ERR_BAD_ABI (a newer caller's field this library does not know).  Errors of fa_kvcache_params and of the older option fields come first,
+ * then those of row_tile, then the reserved words.
+ * sizeof is 288: the sizes 241 .. 280 and 1024 are pinned as FA_ERR_BAD_ABI by callers' tests of the v7 library, and 288 is the next multiple
+ * of 8 that clears them; the reserved words are the room that leaves. */
+#define FA_HAS_KVCACHE_PREFILL 1
+typedef struct fa_kvcache_options_v8 {      /* FA_PARAMS_INIT(o); then fa_..._ex(&p, (const fa_kvcache_options*)&o, ...) */
+    uint32_t struct_size;       /* sizeof(fa_kvcache_options_v8) */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    int32_t is_local;           /* the fields of fa_kvcache_options_v7, same offsets */
+    int32_t window_size_left;
+    int32_t window_size_right;
+    int32_t cache_dtype;
+    const float* k_descale;
+    const float* v_descale;
+    int64_t k_descale_batch_stride, k_descale_head_stride;
+    int64_t v_descale_batch_stride, v_descale_head_stride;
+    const void* rotary_cos;
+    const void* rotary_sin;
+    int64_t rotary_row_stride;
+    int32_t seqlen_ro;
+    int32_t rotary_dim;
+    int32_t rotary_interleaved;
+    int32_t reserved_;
+    const int32_t* cu_seqlens_q;
+    const int32_t* cu_seqlens_k_new;
+    int64_t total_q;
+    int64_t total_k_new;
+    float softmax_scale;
+    float softcap;
+    int64_t reserved[2];        /* 0 */
+    const float* sinks;
+    int64_t sinks_stride;
+    int64_t reserved2[2];       /* 0 */
+    const int64_t* tree_mask;
+    int64_t tree_mask_batch_stride, tree_mask_row_stride;
+    int64_t reserved3[2];       /* 0 */
+    int32_t row_tile;           /* optional: 0 = the 16-row kernels, 64 = the 64-row kernels for prompt chunks */
+    int32_t reserved4_;         /* 0 */
+    int64_t reserved4[5];       /* 0 */
+} fa_kvcache_options_v8;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -625,6 +691,9 @@ int32_t fa_kvcache_num_splits(const fa_kvcache_params* params);
 int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* params, const fa_kvcache_options* options, void* stream);
 int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);
 int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);
+/* Packed query rows per workgroup of the attention launch these params and options would make: 16, or 64 with fa_kvcache_options_v8.row_tile =
+ * 64 (FA_HAS_KVCACHE_PREFILL).  The `workspace` fields are ignored.  Host-only.  Negative = error code, exactly those of the launch. */
+int32_t fa_kvcache_row_tile_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);
 
 /* ---- measurement helpers ----------------------------------------------------------------- */
 /* Algorithmic FLOPs of one forward call (4*b*h*sq*sk*d, causal counts only visible pairs);

@@ -55,6 +55,12 @@ points whose K/V are at least 1 GB, `inside_scatter` whether A lies between B an
 tree call itself through the C ABI of this build (A, timed twice) and of the library at PATH (B), e.g. tools/abl/libfa_treeuniform.so built with
 -DFA_KVC_TREE_UNIFORM=1; the outputs must agree bit for bit.
 
+--prefill measures the 64-row kernels for prompt chunks instead, on a grid of its own: one causal chunk of sq in {64, 128, 512, 2048} rows over
+L in {8k, 32k} keys, h 32 / h_k 8, head_dim 128 and 64 (--head-dim / --length replace them), fp16; with --kv-dtype fp8 over the 8-bit cache, with
+--paged P through a block table of P-row pages (repeatable: one line per page size).  Per point, (A) the prefill=True call against (B) the
+prefill=False call on the same caches, B timed TWICE (B, B2) so that the spread of one thing measured twice in the same run stands next to
+A / B; on the 16-bit contiguous points also (C) fwd on the same prefix.  All arms interleaved, medians; `max_abs_diff` is A against B.
+
 --head-dim D (repeatable) replaces the grid's head dims (64, 128).  head_dim 256 exists for the decode call only: its points carry no fwd arm.
 --equal-bytes (with --head-dim 256) measures the head_dim-256 call against its yardstick instead: per grid point with one query, (A) the
 d-256 call; (B, B2) the d-128 call on the same b and L with twice the KV heads and twice the query heads - the same cache bytes (the very
@@ -752,6 +758,54 @@ def run_ragged(quick, rounds):
         yield run_ragged_chunk_point(sq, 32, 8, 128, dt, rounds)
 
 
+def run_prefill_point(sq, L, h, hk, d, dt, fp8, page, rounds):
+    """one sequence bringing a causal chunk of sq rows over L keys: prefill=True against prefill=False (timed twice) and, 16-bit contiguous, fwd"""
+    dev = torch.device("cuda:0")
+    es = 1 if fp8 else 2
+    kv_bytes = 2 * L * hk * d * es
+    n = _rotation(kv_bytes, kv_bytes)
+    cdt = torch.float8_e4m3fn if fp8 else dt
+    sets = []
+    for i in range(n):
+        shape = (L // page, page, hk, d) if page else (1, L, hk, d)
+        mk = lambda: (torch.empty(shape, device=dev, dtype=dt).uniform_(-2, 2) if not fp8 else torch.randint(0, 0x78, shape, device=dev, dtype=torch.uint8).view(cdt))
+        table = torch.randperm(L // page, generator=torch.Generator().manual_seed(i)).view(1, L // page).to(device=dev, dtype=torch.int32) if page else None
+        sets.append((mk(), mk(), table))
+    q = torch.randn(1, sq, h, d, device=dev, dtype=dt)
+    cs = torch.tensor([L], dtype=torch.int32, device=dev)
+    kw = dict(k_descale=torch.empty(1, hk, device=dev).uniform_(0.5, 2.0), v_descale=torch.empty(1, hk, device=dev).uniform_(0.5, 2.0)) if fp8 else {}
+    wide = lambda i: F.flash_attn_with_kvcache(q, sets[i][0], sets[i][1], cache_seqlens=cs, causal=True, block_table=sets[i][2], prefill=True, **kw)
+    narrow = lambda i: F.flash_attn_with_kvcache(q, sets[i][0], sets[i][1], cache_seqlens=cs, causal=True, block_table=sets[i][2], **kw)
+    arms = {"narrow": narrow, "wide": wide, "narrow2": narrow}
+    with_fwd = not fp8 and not page
+    if with_fwd:
+        arms["fwd"] = lambda i: F.fwd(q, sets[i][0], sets[i][1], True)
+    err = float((wide(0).float() - narrow(0).float()).abs().max())
+    torch.cuda.synchronize()
+    ms = _interleaved(arms, n, rounds)
+    p = capi.kvcache_params(q, sets[0][0], sets[0][1], torch.empty_like(q), torch.empty(1, h, sq, device=dev), cache_seqlens=cs, causal=True, block_table=sets[0][2])
+    splits = []
+    for rt in (None, 64):
+        opt = capi.kvcache_options(cache_dtype=capi.FA_CACHE_FP8_E4M3 if fp8 else 0, row_tile=rt)
+        ws = capi.kvcache_workspace_bytes(p, opt)
+        splits.append(max(1, ws and capi.kvcache_num_splits(_with_ws(p, ws), opt)))
+    del sets
+    torch.cuda.empty_cache()
+    row = dict(prefill="chunk", sq=sq, L=L, h=h, h_k=hk, d=d, dtype=str(dt).replace("torch.", ""), kv="fp8" if fp8 else "16bit", page_block_size=page or 0,
+               caches_rotated=n, n_split_16=splits[0], n_split_64=splits[1], ms_prefill=round(ms["wide"], 5), ms_16row=round(ms["narrow"], 5),
+               ms_16row_again=round(ms["narrow2"], 5), prefill_over_16row=round(ms["wide"] / ms["narrow"], 4),
+               again_over_16row=round(ms["narrow2"] / ms["narrow"], 4), max_abs_diff=round(err, 5))
+    if with_fwd:
+        row.update(ms_fwd=round(ms["fwd"], 5), prefill_over_fwd=round(ms["wide"] / ms["fwd"], 3))
+    return row
+
+
+def run_prefill(lengths, head_dims, fp8, pages, rounds):
+    for d, L, sq in itertools.product(tuple(head_dims or (128, 64)), tuple(lengths or (8192, 32768)), (64, 128, 512, 2048)):
+        for page in (pages or [None]):
+            yield run_prefill_point(sq, L, 32, 8, d, torch.float16, fp8, page, rounds)
+
+
 def _baseline_lib(path):
     L = ctypes.CDLL(os.path.abspath(path))
     L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
@@ -832,6 +886,8 @@ def main():
                                                          "same call without sinks (timed twice); with --kv-dtype fp8 over the 8-bit cache, with --paged P through a block table")
     ap.add_argument("--tree", type=int, default=None, metavar="N", choices=(8, 32, 64), help="tree attention masks: the tree call under the binary-heap tree with seqlen_q = N against "
                                                                                              "the causal call of the same shape (timed twice); with --kv-dtype fp8 over the 8-bit cache")
+    ap.add_argument("--prefill", action="store_true", help="the 64-row kernels for prompt chunks (prefill=True) against the 16-row kernels (timed twice) and, on the 16-bit "
+                                                           "contiguous points, fwd; with --kv-dtype fp8 / --paged P over those caches")
     ap.add_argument("--head-dim", type=int, action="append", metavar="D", choices=(64, 128, 256), help="head dim(s) instead of the grid's 64 and 128 (256: the decode call only)")
     ap.add_argument("--equal-bytes", action="store_true", help="with --head-dim 256: the d-256 call against the d-128 call with twice the heads on the same buffers (timed twice)")
     a = ap.parse_args()
@@ -843,6 +899,10 @@ def main():
     with torch.no_grad():
         if a.ragged and base is None:
             for line in run_ragged(a.quick, a.rounds):
+                print(json.dumps(line), flush=True)
+            return
+        if a.prefill:
+            for line in run_prefill(a.length, a.head_dim, a.kv_dtype == "fp8", a.paged, a.rounds):
                 print(json.dumps(line), flush=True)
             return
         if a.sinks:
