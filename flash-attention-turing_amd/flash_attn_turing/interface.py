@@ -329,7 +329,11 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     ``return_softmax_lse``.  Precondition: cache_seqlens[i] + seqlen_new <= seqlen_cache.
     Non-finite inputs follow fp32 math over the valid prefix, for every num_splits: a NaN query row, or a NaN / +inf score from a visible K row,
     gives NaN in that row's O and LSE; a row that sees no key is O = 0, LSE = 0.  Cache rows at or past L_i and heads the
-    cache views skip are never read into a result.
+    cache views skip are never read into a result.  Precondition, not checked: every finite score (q . k) * softmax_scale (* k_descale) has
+    |score| * log2(e) < 2^31 (about 1.5e9, which only bf16 inputs can reach).  The kernels take exp2(s * c - fl(m * c)), whose argument carries
+    the rounding residue of m * c: below the limit it is at most 64 and costs the LSE a relative 2^-24; from 2^32 on its exponential overflows
+    or underflows and the row's O and LSE are unspecified (nothing is read or written out of bounds).  A row that sees a single key returns that
+    V row bit for bit (over an FP8 cache: the fp32 product float(code) * v_descale rounded once to q's dtype); a V of -0 may come back as +0.
 
     head_dim d: 64, 128 or 256; anything else is a ValueError.  d = 256 (Gemma 2 2B / 9B, Gemma 3) exists for this call only - fwd, bwd,
     varlen_* and flash_attn_func stay at 64 / 128 - and supports everything below exactly as 128 does: the same tolerances and the same
