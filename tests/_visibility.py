@@ -1,0 +1,607 @@
+"""The visibility probe: decode the exact SET of keys every query row of an attention call sees.
+
+Every mask of this library is integer arithmetic on key indices, and a tolerance on floating-point values cannot see one key among
+hundreds.  The probe turns the question into integers:
+
+  * K = 0 everywhere (cache, appended k, fp8 code 0), q random and finite: every score is exactly 0 - also under softcap, whose
+    1 - 2 / (exp(0) + 1) is exactly 0, and under any k_descale.  Every visible key then has the unnormalised P = 1 exactly, so a live
+    row's LSE is log(n) (log(n + 1) with a sink of 0.0), n = the number of keys it sees: n_hat = round(exp(lse)).
+  * V[j, :] is a two-digit one-hot code of the key index j in base B = min(d / 2, 64): column j % B is 1 and column B + (j // B) % B
+    is 1, everything else 0 (d = 256: base 64 on the first 128 columns).  1 and 0 are exact in fp16, bf16 and as e4m3 codes (0x38, 0).
+    Then out[c] = m_c / n with m_c = the visible keys whose digit is c, and round(out[c] * n_hat) = m_c.
+  * Outside the keys a sequence owns (rows at or past L before an append, spare pages, other sequences' pages) V holds the BAD CODE, 1
+    in every column, and K stays 0: an extra key from there changes the count and every column.
+
+CONDITIONS, derived and asserted on the inputs (`check_conditions`), never used to drop a case:
+  * n <= 4096: |lse - log n| < 1 / (2 n + 1) decodes n; at 4096 that is 1.2e-4, a hundred times fp32's error on this sum;
+  * every expected m_c <= 64: bf16's half ulp (2^-9 relative) then puts at most 0.125 on out[c] * n, the reciprocal's ulp and the
+    LSE's error another 64 * (2^-23 + 4096 * 3e-7 / 4096) << 0.25;
+  * capacity <= B * B keys, so that the second digit is unique: 1024 keys at d = 64, 4096 at d = 128 and 256.
+
+WHAT IT DOES NOT SEE: two key sets with the same count and the same digit histogram (remove (a, b) and (c, e), add (a, e) and (c, b), in
+digits) - a swap invisible to both digits; the value path (V is 0 / 1); the backward.
+
+The expectation is `visible`, a pure integer model written from the README's formulas (no float in it, nothing taken from the kernels).
+This module holds the encoding, the model, the decoder, the condition asserts, the cache builders and the parameter tables of the GPU
+tests (tests/test_kvcache_visibility_gpu.py, tests/test_attention_visibility_gpu.py), which tests/test_visibility_cpu.py enumerates
+without a GPU."""
+import itertools
+from dataclasses import dataclass, replace
+from functools import lru_cache
+
+import numpy as np
+
+MAX_DIGIT = 64          # largest expected count per code column
+MAX_N = 4096            # largest count of visible keys
+BAD = 1                 # the bad code: this value in every column
+FP8_ONE = 0x38          # e4m3 code of 1.0
+K_DESCALE = 0.37        # multiplies a score of 0
+
+
+def base_of(d):
+    return min(d // 2, 64)
+
+
+def capacity_of(d):
+    return base_of(d) ** 2
+
+
+@lru_cache(maxsize=None)
+def codes(d, cap):
+    """int64 (cap, d): row j = the code of key j"""
+    B = base_of(d)
+    assert cap <= B * B, f"capacity {cap} > {B * B}: the second digit would repeat at d = {d}"
+    c = np.zeros((cap, d), dtype=np.int64)
+    j = np.arange(cap)
+    c[j, j % B] = 1
+    c[j, B + (j // B) % B] = 1
+    c.setflags(write=False)
+    return c
+
+
+@lru_cache(maxsize=None)
+def _prefix(d, cap):
+    p = np.zeros((cap + 1, d), dtype=np.int64)
+    np.cumsum(codes(d, cap), axis=0, out=p[1:])
+    return p
+
+
+# ---- the model --------------------------------------------------------------------------------------------------------------------------
+
+def visible(L, sq, t, causal=False, window=(-1, -1), tree_word=None):
+    """The keys query row t of a sequence with L keys and sq query rows sees, as (range, extras): the set is the range plus the tuple.
+    README: j < L; causal: j <= L - sq + t; window: L - sq + t - left <= j <= L - sq + t + right, -1 = unbounded, causal sets right = 0;
+    tree: j < L - sq, or bit j - (L - sq) of the row's word (an unsigned 64-bit int) with 0 <= j - (L - sq) < sq and j >= 0."""
+    L = max(int(L), 0)
+    base = L - sq
+    if tree_word is not None:
+        assert not causal and tuple(window) == (-1, -1) and 0 <= tree_word < 1 << 64
+        extras = tuple(base + u for u in range(min(sq, 64)) if (tree_word >> u) & 1 and 0 <= base + u < L)
+        return range(0, max(0, min(base, L))), extras
+    left, right = window
+    if causal:
+        right = 0
+    lo = 0 if left < 0 else max(0, base + t - left)
+    hi = L if right < 0 else min(L, base + t + right + 1)
+    return range(lo, max(lo, hi)), ()
+
+
+def visible_set(*a, **kw):
+    r, extras = visible(*a, **kw)
+    return set(r) | set(extras)
+
+
+def signature(d, cap, vis):
+    """(n, histogram int64 (d,)) of a (range, extras) pair"""
+    r, extras = vis
+    assert len(r) == 0 or (r.step == 1 and 0 <= r.start <= r.stop <= cap)
+    p = _prefix(d, cap)
+    h = p[r.stop] - p[r.start] if len(r) else np.zeros(d, dtype=np.int64)
+    if extras:
+        h = h + codes(d, cap)[list(extras)].sum(axis=0)
+    return len(r) + len(extras), h
+
+
+# ---- cases ------------------------------------------------------------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class Case:
+    """One flash_attn_with_kvcache call.  lens = L_i AFTER the append; sq = the query rows per sequence (dense calls: all equal); tree =
+    per sequence a tuple of sq_i unsigned 64-bit words; sink: None, "zero" (0.0 on every head), "ninf" (-inf on every head) or "mixed"
+    (0.0 on even heads, -inf on odd ones)."""
+    family: str
+    name: str
+    lens: tuple
+    sq: tuple
+    d: int = 64
+    dtype: str = "fp16"
+    fp8: bool = False
+    page: int = 0
+    h: int = 4
+    hk: int = 1
+    append: bool = False
+    causal: bool = False
+    window: tuple = (-1, -1)
+    splits: int = 1
+    softcap: float = 0.0
+    sink: str = None
+    tree: tuple = None
+    prefill: bool = False
+    ragged: bool = False
+    cap: int = 1024
+    v_scale: float = 1.0
+
+    @property
+    def ratio(self):
+        return self.h // self.hk
+
+    def sink_extra(self):
+        """per query head: 1 where a sink of 0.0 joins the denominator"""
+        return [0 if self.sink in (None, "ninf") or (self.sink == "mixed" and g % 2) else 1 for g in range(self.h)]
+
+
+def check_conditions(c):
+    """the derived conditions and the preconditions of the call, on the inputs"""
+    assert c.cap <= capacity_of(c.d) and c.cap <= MAX_N and c.cap % 16 == 0
+    assert len(c.lens) == len(c.sq) and len(c.lens) >= 1
+    assert c.ragged or len(set(c.sq)) == 1 and c.sq[0] >= 1, "a dense call has one seqlen_q"
+    assert all(0 <= L <= c.cap for L in c.lens)
+    assert not c.append or all(L >= s for L, s in zip(c.lens, c.sq)), "an append of sq rows leaves L >= sq"
+    assert c.page == 0 or (c.page % 16 == 0 and c.cap % c.page == 0)
+    assert c.h % c.hk == 0 and c.splits >= 0
+    assert c.v_scale == 1.0 or (c.fp8 and c.v_scale in (0.25, 0.5, 2.0, 4.0)), "v_descale: 1 or a power of two, over an FP8 cache"
+    if c.tree is not None:
+        assert max(c.sq) <= 64 and not c.causal and c.window == (-1, -1) and all(len(w) == s for w, s in zip(c.tree, c.sq))
+        assert all(0 <= x < 1 << 64 for w in c.tree for x in w)
+
+
+def expected(c):
+    """-> n int64 (R,), hist int64 (R, d), rows [(i, t)]: the model's signature of every (sequence, query row) in packed order"""
+    check_conditions(c)
+    rows = [(i, t) for i, s in enumerate(c.sq) for t in range(s)]
+    n = np.zeros(len(rows), dtype=np.int64)
+    hist = np.zeros((len(rows), c.d), dtype=np.int64)
+    for r, (i, t) in enumerate(rows):
+        vis = visible(c.lens[i], c.sq[i], t, c.causal, c.window, None if c.tree is None else c.tree[i][t])
+        n[r], hist[r] = signature(c.d, c.cap, vis)
+    assert n.max(initial=0) <= MAX_N and hist.max(initial=0) <= MAX_DIGIT, f"{c.name}: a count leaves the decodable range"
+    return n, hist, rows
+
+
+def row_sets(c):
+    return [visible_set(c.lens[i], c.sq[i], t, c.causal, c.window, None if c.tree is None else c.tree[i][t])
+            for i, s in enumerate(c.sq) for t in range(s)]
+
+
+# ---- the decoder (torch, on the tensors' own device; the CPU tests feed it emulated kernel outputs) ---------------------------------------
+
+def decode(out, lse, extra, v_scale=1.0):
+    """out (R, h, d) fp16 / bf16, lse (R, h) fp32, extra (h,) int = 1 where a sink of 0.0 sits in the denominator
+    -> n (R, h) int64 = the visible keys, hist (R, h, d) int64.  A dead row (O = 0, LSE = 0 exactly) decodes to n = 0; a row that sees one
+    key has LSE = 0 too and is told apart by its two ones."""
+    import torch
+
+    assert torch.isfinite(out.float()).all().item() and torch.isfinite(lse).all().item(), "non-finite output"
+    n_tot = torch.round(torch.exp(lse.double())).long()
+    hist = torch.round(out.double() / v_scale * n_tot.unsqueeze(-1).double()).long()
+    n = n_tot - extra.to(n_tot.device).long().unsqueeze(0)
+    dead = (out == 0).all(dim=-1) & (lse == 0)
+    n = torch.where(dead, torch.zeros_like(n), n)
+    return n, hist
+
+
+def assert_signature(c, n_dec, hist_dec, n_exp, hist_exp, rows):
+    """integer equality of the decoded and the expected signature on every (sequence, head, row).  The message names the first rows that differ with the digit columns that differ: which key was lost or gained."""
+    import torch
+
+    ne = torch.from_numpy(n_exp).to(n_dec.device).unsqueeze(1)
+    he = torch.from_numpy(hist_exp).to(n_dec.device).unsqueeze(1)
+    bad = (n_dec != ne) | (hist_dec != he).any(dim=-1)
+    if not bad.any().item():
+        return
+    B, msgs = base_of(c.d), []
+    for r, g in bad.nonzero()[:6].tolist():
+        i, t = rows[r]
+        diff = (hist_dec[r, g] - he[r, 0]).cpu().numpy()
+        cols = {(f"lo{k}" if k < B else f"hi{k - B}" if k < 2 * B else f"pad{k}"): (int(hist_exp[r, k]), int(hist_exp[r, k] + diff[k])) for k in np.flatnonzero(diff)[:12]}
+        msgs.append(f"seq {i} (L={c.lens[i]}, sq={c.sq[i]}) head {g} row {t}: expected n={int(n_exp[r])}, decoded n={int(n_dec[r, g])}; "
+                    f"digit counts (expected, decoded) that differ: {cols}")
+    raise AssertionError(f"{c.name}: {int(bad.sum())} (row, head) signatures differ from the model [{c}]\n  " + "\n  ".join(msgs))
+
+
+# ---- builders and the call --------------------------------------------------------------------------------------------------------------
+
+def torch_dtype(name):
+    import torch
+
+    return torch.float16 if name == "fp16" else torch.bfloat16
+
+
+def code_tensor(d, cap, dev):
+    import torch
+
+    return torch.from_numpy(codes(d, cap).copy()).to(dev).to(torch.uint8)
+
+
+def build_cache(c, dev, gen):
+    """K (all 0) and V of the call: good codes on the rows a sequence owns BEFORE the append, the bad code everywhere else (rows at or past
+    that length, spare pages).  Contiguous (b, cap, hk, d), or a pool under a random page permutation with spare pages.
+    -> k_cache, v_cache, block_table or None"""
+    import torch
+
+    b, cap, hk, d = len(c.lens), c.cap, c.hk, c.d
+    before = torch.tensor([L - s if c.append else L for L, s in zip(c.lens, c.sq)], device=dev)
+    good = torch.arange(cap, device=dev).unsqueeze(0) < before.unsqueeze(1)
+    v = torch.where(good.unsqueeze(-1), code_tensor(d, cap, dev).unsqueeze(0), torch.full((), BAD, dtype=torch.uint8, device=dev))
+    v = v.unsqueeze(2).expand(b, cap, hk, d).contiguous()
+    table = None
+    if c.page:
+        nblk, spare = cap // c.page, 5
+        perm = torch.randperm(b * nblk + spare, generator=gen)
+        table = perm[: b * nblk].view(b, nblk).to(device=dev, dtype=torch.int32)
+        pool = torch.full((b * nblk + spare, c.page, hk, d), BAD, dtype=torch.uint8, device=dev)
+        pool[table.flatten().long()] = v.view(b * nblk, c.page, hk, d)
+        v = pool
+    if c.fp8:
+        v = (v * FP8_ONE).view(torch.float8_e4m3fn)
+        k = torch.zeros(v.shape, dtype=torch.uint8, device=dev).view(torch.float8_e4m3fn)
+    else:
+        v = v.to(torch_dtype(c.dtype))
+        k = torch.zeros_like(v)
+    return k, v, table
+
+
+def run_kvcache(c, dev):
+    """build the probe's inputs for the case, call flash_attn_with_kvcache, -> out (R, h, d), lse (R, h) in packed (sequence, row) order"""
+    import torch
+
+    from flash_attn_turing import flash_attn_with_kvcache
+
+    check_conditions(c)
+    dt = torch_dtype(c.dtype)
+    gen = torch.Generator(device="cpu").manual_seed(len(c.name) * 7919 + sum(c.lens))
+    b, total = len(c.lens), sum(c.sq)
+    q = torch.randn(total, c.h, c.d, generator=gen).to(dev, dt)
+    k_cache, v_cache, table = build_cache(c, dev, gen)
+    kw = dict(cache_seqlens=torch.tensor([L - s if c.append else L for L, s in zip(c.lens, c.sq)], dtype=torch.int32, device=dev), causal=c.causal,
+              num_splits=c.splits, return_softmax_lse=True, block_table=table, window_size=c.window)
+    cu = torch.tensor([0] + list(itertools.accumulate(c.sq)), dtype=torch.int32, device=dev)
+    if c.append:
+        pos = torch.tensor([L - s + t for L, s in zip(c.lens, c.sq) for t in range(s)], dtype=torch.long, device=dev)
+        # (the logical V is v_scale x code: over an FP8 cache the appended 0 / v_scale quantise to the codes 0 / 0x38, exactly, v_scale a power of two)
+        v_new = (code_tensor(c.d, c.cap, dev)[pos].to(dt) * c.v_scale).unsqueeze(1).expand(total, c.hk, c.d).contiguous()
+        k_new = torch.zeros_like(v_new)
+        if not c.ragged:
+            k_new, v_new = (x.view(b, c.sq[0], c.hk, c.d) for x in (k_new, v_new))
+        else:
+            kw.update(cu_seqlens_k_new=cu)
+        kw.update(k=k_new, v=v_new)
+    if c.fp8:
+        kw.update(k_descale=torch.full((b, c.hk), K_DESCALE, dtype=torch.float32, device=dev),
+                  v_descale=torch.full((b, c.hk), c.v_scale, dtype=torch.float32, device=dev))
+    if c.ragged:
+        kw.update(cu_seqlens_q=cu, max_seqlen_q=max(max(c.sq), 1))
+    else:
+        q = q.view(b, c.sq[0], c.h, c.d)
+    if c.softcap:
+        kw.update(softcap=c.softcap)
+    if c.sink is not None:
+        kw.update(sinks=torch.tensor([0.0 if e else float("-inf") for e in c.sink_extra()], dtype=torch.float32, device=dev))
+    if c.tree is not None:
+        words = [x - (1 << 64) if x >= 1 << 63 else x for w in c.tree for x in w]
+        tm = torch.tensor(words, dtype=torch.int64, device=dev)
+        kw.update(tree_mask=tm if c.ragged else tm.view(b, c.sq[0]))
+    if c.prefill:
+        kw.update(prefill=True)
+    out, lse = flash_attn_with_kvcache(q, k_cache, v_cache, **kw)
+    if c.ragged:
+        assert out.shape == (total, c.h, c.d) and lse.shape == (c.h, total)
+        return out, lse.t()
+    assert out.shape == (b, c.sq[0], c.h, c.d) and lse.shape == (b, c.h, c.sq[0])
+    return out.reshape(total, c.h, c.d), lse.permute(0, 2, 1).reshape(total, c.h)
+
+
+def probe_kvcache(c, dev):
+    """run the case and assert that the decoded signature equals the model's -> n, hist decoded"""
+    import torch
+
+    out, lse = run_kvcache(c, dev)
+    n_dec, hist_dec = decode(out, lse, torch.tensor(c.sink_extra()), c.v_scale)
+    assert_signature(c, n_dec, hist_dec, *expected(c))
+    return n_dec, hist_dec
+
+
+# ---- parameter tables of tests/test_kvcache_visibility_gpu.py ----------------------------------------------------------------------------
+
+DTYPES = ("fp16", "bf16")
+PAGES = (0, 16, 48, 256)
+SPLITS = (1, 2, 3, 5, "steps", 0)
+RATIOS = (1, 3, 4, 5, 12, 16)
+SQS = (1, 2, 3, 5, 16, 17, 33)
+LEFTS = (0, 1, 15, 16, 31, 32, 33, 63, 64, 65, 100, 500, -1)
+RIGHTS = (-1, 0, 1, 2, 31, 32, 40)
+TREE_SQS = (1, 2, 17, 33, 63, 64)
+PREFILL_SQS = (1, 15, 16, 17, 63, 64, 65, 127, 129, 200)
+PREFILL_RATIOS = (1, 4, 5, 64)
+SOFTCAP = 30.0
+
+
+def _axes(i, ratios=RATIOS, d=None):
+    """the common axes, rotated through the cases of a family (not a cross-product): every value of every axis occurs within any six
+    consecutive i, which tests/test_visibility_cpu.py asserts per family"""
+    page = PAGES[(i + i // 4) % 4]
+    ratio = ratios[(5 * i + i // len(ratios)) % len(ratios)]
+    hk = 2 if ratio <= 5 else 1
+    cap = 1008 if page == 48 else 1024       # 21 pages of 48 rows: the largest paged capacity within 32 x 32 keys
+    splits = SPLITS[(i + i // 6) % 6]
+    return dict(dtype=DTYPES[i % 2], fp8=bool((i // 2) % 2), page=page, h=ratio * hk, hk=hk, cap=cap, splits=cap // 32 if splits == "steps" else splits,
+                append=bool((i // 3) % 2), d=d or (64, 64, 128)[i % 3])
+
+
+def band_lens(cap, sq=0, append=False):
+    """every L from 0 to 130, 250..262, 505..519 and the last 15 up to the capacity (1010..1024); an append of sq rows leaves L >= sq"""
+    lens = list(range(0, 131)) + list(range(250, 263)) + list(range(505, 520)) + list(range(cap - 14, cap + 1))
+    return tuple(L for L in lens if not append or L >= sq)
+
+
+def window_lens(cap, sq=0, append=False):
+    """three runs of more than 64 consecutive lengths - lo and lim of every row take every residue mod 32 at the start of the cache, around
+    key 512 (where a forced split of the capacity cuts) and at its end"""
+    lens = list(range(0, 71)) + list(range(480, 561)) + list(range(cap - 70, cap + 1))
+    return tuple(L for L in lens if not append or L >= sq)
+
+
+def _dense(family, name, lens, sq, **kw):
+    return Case(family=family, name=f"{family}/{name}", lens=tuple(lens), sq=(sq,) * len(lens), **kw)
+
+
+def _plain_cases(family="plain", thin=1, **extra):
+    out = []
+    for i, (sq, causal) in enumerate(itertools.product(SQS, (False, True))):
+        ax = _axes(i)
+        v_scale = 0.25 if ax["fp8"] and i % 4 == 2 else 1.0
+        out.append(_dense(family, f"sq{sq}-{'causal' if causal else 'full'}", band_lens(ax["cap"], sq, ax["append"])[::thin], sq, causal=causal, v_scale=v_scale, **ax, **extra))
+    return out
+
+
+def _window_cases(family="window", thin=1, **extra):
+    out = []
+    for i in range(16):
+        ax = _axes(i + 1)
+        left, right, causal, sq = LEFTS[i % 13], RIGHTS[i % 7], i % 4 == 3, SQS[(3 * i) % 7]
+        out.append(_dense(family, f"w{left}_{right}-{'causal-' if causal else ''}sq{sq}", window_lens(ax["cap"], sq, ax["append"])[::thin], sq, causal=causal,
+                          window=(left, right), **ax, **extra))
+    return out
+
+
+def _sink_cases():
+    out = []
+    for i, (mode, split, kind) in enumerate(itertools.product(("zero", "ninf", "mixed"), (False, True), ("causal", "window"))):
+        ax = _axes(i)
+        ax["splits"] = (2, 3, 5, ax["cap"] // 32, 0, 7)[(i // 4) * 2 + i % 2] if split else 1     # 0: the library's choice may be 1 at these sizes
+        sq = SQS[(2 * i) % 7]
+        if kind == "causal":
+            kw, lens = dict(causal=True), band_lens(ax["cap"], sq, ax["append"])
+        else:
+            kw, lens = dict(window=(LEFTS[(5 * i + 2) % 12], RIGHTS[i % 7]), causal=i % 3 == 0), window_lens(ax["cap"], sq, ax["append"])
+        out.append(_dense("sinks", f"{mode}-{'split' if split else 'unsplit'}-{kind}-sq{sq}", lens, sq, sink=mode, **kw, **ax))
+    return out
+
+
+def heap_words(sq):
+    """the words of tree_mask_from_parents for the binary-heap tree parents[t] = (t - 1) // 2: ancestors plus self"""
+    words = []
+    for t in range(sq):
+        w, u = 0, t
+        while u >= 0:
+            w |= 1 << u
+            u = (u - 1) // 2 if u > 0 else -1
+        words.append(w)
+    return tuple(words)
+
+
+def tree_entries(sq, cap, append, seed):
+    """(L, words) per sequence of one tree call: every mask kind at lengths below, at and above sq; the single-bit masks (row t sees draft
+    token (t + p) % sq only) at every shift p, two lengths each"""
+    rng = np.random.default_rng(seed)
+    full64 = (1 << 64) - 1
+    kinds = {
+        "empty": (0,) * sq,
+        "full": ((1 << sq) - 1,) * sq,
+        "full64": (full64,) * sq,                                                  # bits at or above sq are ignored
+        "tril": tuple((1 << (t + 1)) - 1 for t in range(sq)),
+        "bit63": (1 << 63,) * sq,                                                  # the sign bit: a key only at sq = 64
+        "heap": heap_words(sq),
+        "random": tuple(int(x) for x in rng.integers(0, 1 << 64, size=sq, dtype=np.uint64)),
+    }
+    lens = sorted({L for L in (0, sq // 2, sq - 1, sq, sq + 1, sq + 31, sq + 32, sq + 33, 200, 517, cap - 1, cap) if 0 <= L <= cap and (not append or L >= sq)})
+    entries = [(L, w) for w in kinds.values() for L in lens]
+    for p in range(sq):
+        for L in (lens[p % len(lens)], lens[-1 - p % 2]):
+            entries.append((L, tuple(1 << ((t + p) % sq) for t in range(sq))))
+    return entries
+
+
+def _tree_cases():
+    out = []
+    for i, sq in enumerate(TREE_SQS):
+        ax = _axes(i)
+        ent = tree_entries(sq, ax["cap"], ax["append"], 100 + sq)
+        out.append(_dense("tree", f"sq{sq}", [e[0] for e in ent], sq, tree=tuple(e[1] for e in ent), **ax))
+    for i, append in ((6, False), (7, True)):                                      # ragged: every sq of the table (and 0) in one call
+        ax = dict(_axes(i), append=append)
+        ent = [(s, e) for s in (0,) + TREE_SQS for e in (tree_entries(s, ax["cap"], append, 200 + s)[:: 5] if s else [(0, ()), (33, ()), (ax["cap"], ())])]
+        out.append(Case(family="tree", name=f"tree/ragged-{'append' if append else 'read'}", lens=tuple(e[0] for _, e in ent), sq=tuple(s for s, _ in ent),
+                        tree=tuple(e[1] for _, e in ent), ragged=True, **ax))
+    return out
+
+
+def prefill_lens(sq, cap, append, ratio):
+    lens = sorted({L for L in [0, 1, 2, sq // 2, sq - 1, sq, sq + 1, 2 * sq - 1, 2 * sq, 2 * sq + 1, cap - sq, cap - 1, cap] + list(range(30, 35)) + list(range(62, 67))
+                   + list(range(126, 131)) + list(range(250, 263, 2)) + list(range(505, 520)) + list(range(cap - 14, cap - 1, 3)) if 0 <= L <= cap and (not append or L >= sq)})
+    return tuple(lens[:: 3 if sq * ratio > 2048 else 1])
+
+
+def _prefill_cases():
+    out = []
+    for i, (sq, causal) in enumerate(itertools.product(PREFILL_SQS, (True, False))):
+        ax = _axes(i, ratios=PREFILL_RATIOS)
+        out.append(_dense("prefill", f"sq{sq}-{'causal' if causal else 'full'}", prefill_lens(sq, ax["cap"], ax["append"], ax["h"] // ax["hk"]), sq, causal=causal, prefill=True, **ax))
+    return out
+
+
+def _d256_cases():
+    out = []
+    kinds = (("full", {}), ("causal", dict(causal=True)), ("w33_2", dict(window=(33, 2))), ("w100-causal", dict(window=(100, 0), causal=True)))
+    for i, ((name, kw), fp8) in enumerate(itertools.product(kinds, (False, True))):
+        ax = dict(_axes(i, d=256), fp8=fp8)
+        sq = SQS[(i + 2) % 7]
+        lens = (window_lens if "window" in kw else band_lens)(ax["cap"], sq, ax["append"])[::2]
+        out.append(_dense("d256", f"{name}-{'fp8' if fp8 else '16bit'}-sq{sq}", lens, sq, **kw, **ax))
+    return out
+
+
+RAGGED_SQS = (0, 1, 2, 5, 16, 17, 40)
+
+
+def ragged_entries(cap, append, sqs=RAGGED_SQS):
+    """(sq_i, L_i): every sq_i with lengths on both sides of it"""
+    ent = []
+    for s in sqs:
+        for L in sorted({0, max(s - 1, 0), s, s + 1, s // 2, 31, 32, 33, 100, 517, cap - 1, cap}):
+            if not append or L >= s:
+                ent.append((s, L))
+    return ent
+
+
+def _ragged_cases():
+    kinds = (("mixed-causal", dict(causal=True), RAGGED_SQS), ("mixed-window", dict(window=(33, 1)), RAGGED_SQS), ("mixed-full", {}, RAGGED_SQS),
+             ("mixed-causal-prefill", dict(causal=True, prefill=True), RAGGED_SQS), ("mixed-full-prefill", dict(prefill=True), RAGGED_SQS),
+             ("uniform1-causal", dict(causal=True), (1,) * 7), ("uniform2-window", dict(window=(15, 0), causal=True), (2,) * 7),
+             ("uniform5-causal-prefill", dict(causal=True, prefill=True), (5,) * 7), ("mixed-window-causal", dict(window=(64, 0), causal=True), RAGGED_SQS))
+    out = []
+    for i, (name, kw, sqs) in enumerate(kinds):
+        ax = _axes(i)
+        ent = ragged_entries(ax["cap"], ax["append"], sqs)
+        out.append(Case(family="ragged", name=f"ragged/{name}", lens=tuple(e[1] for e in ent), sq=tuple(e[0] for e in ent), ragged=True, **kw, **ax))
+    # more than 512 sequences: the second round of the slot lookup's prefix sum
+    sqs = tuple((0, 1, 2, 5, 1, 17, 1, 3)[i % 8] for i in range(520))
+    lens = tuple(min(64, (7 * i) % 66 + (s if i % 3 else 0)) for i, s in enumerate(sqs))
+    lens = tuple(max(L, s) for L, s in zip(lens, sqs))
+    out.append(Case(family="ragged", name="ragged/520-sequences", lens=lens, sq=sqs, ragged=True, causal=True, append=True, cap=64, h=6, hk=2, dtype="bf16", splits=1))
+    return out
+
+
+@lru_cache(maxsize=None)
+def kv_families():
+    fams = {
+        "plain": _plain_cases(),
+        "window": _window_cases(),
+        "softcap": _plain_cases("softcap", thin=3, softcap=SOFTCAP) + _window_cases("softcap", thin=3, softcap=SOFTCAP),
+        "sinks": _sink_cases(),
+        "tree": _tree_cases(),
+        "prefill": _prefill_cases(),
+        "d256": _d256_cases(),
+        "ragged": _ragged_cases(),
+    }
+    names = [c.name for cs in fams.values() for c in cs]
+    assert len(names) == len(set(names))
+    return fams
+
+
+def kv_cases(family):
+    return kv_families()[family]
+
+
+# ---- sensitivity: one parameter moved by one, at the largest length of each family -------------------------------------------------------
+
+def sensitivity_pairs():
+    """(name, base case, moved case): the moved call must decode to the model of the MOVED parameters, and differ from the model of the base
+    exactly on the rows whose visible sets differ"""
+    cap = 1024
+    L = (cap - 1, cap - 2, 517, cap - 1)
+    pairs = []
+
+    def add(name, base, **moved):
+        pairs.append((name, base, replace(base, name=base.name + "+moved", **moved)))
+
+    def longer(c, i=0):
+        return dict(lens=tuple(x + (j == i) for j, x in enumerate(c.lens)))
+
+    def flip(c, i, t, bit):
+        return dict(tree=tuple(tuple(x ^ (1 << bit) if (j, u) == (i, t) else x for u, x in enumerate(w)) for j, w in enumerate(c.tree)))
+
+    base = _dense("sens", "plain", L, 5, h=4, hk=1, splits=3)
+    add("plain: one length + 1", base, **longer(base))
+    base = _dense("sens", "causal", L, 17, causal=True, h=3, hk=1, dtype="bf16", splits=0)
+    add("causal: one length + 1", base, **longer(base, 1))
+    base = _dense("sens", "window", L, 5, window=(500, 2), h=4, hk=2, splits=2)
+    add("window: left + 1", base, window=(501, 2))
+    add("window: right + 1", base, window=(500, 3))
+    base = _dense("sens", "window-causal", L, 3, window=(100, 0), causal=True, h=5, hk=1, dtype="bf16", fp8=True, page=16, splits=5)
+    add("causal window: left + 1", base, window=(101, 0))
+    base = _dense("sens", "softcap", L, 5, window=(500, 1), softcap=SOFTCAP, h=4, hk=1)
+    add("softcap: left + 1", base, window=(501, 1))
+    add("softcap: right + 1", base, window=(500, 2))
+    base = _dense("sens", "sinks-unsplit", L, 2, window=(500, 0), causal=True, sink="zero", h=4, hk=1)
+    add("sinks, unsplit: left + 1", base, window=(501, 0))
+    base = _dense("sens", "sinks-split", L, 2, causal=True, sink="zero", h=4, hk=1, splits=3, page=256)
+    add("sinks, split: one length + 1", base, **longer(base, 3))
+    base = _dense("sens", "tree", L, 33, tree=(heap_words(33),) * 4, h=4, hk=1, splits=2)
+    add("tree: one bit flipped", base, **flip(base, 0, 20, 7))
+    add("tree: one length + 1", base, **longer(base, 2))
+    base = _dense("sens", "prefill", L, 65, causal=True, prefill=True, h=4, hk=1, splits=3)
+    add("prefill: one length + 1", base, **longer(base))
+    base = _dense("sens", "d256", L, 5, d=256, window=(500, 2), h=4, hk=1, fp8=True)
+    add("d256: left + 1", base, window=(501, 2))
+    add("d256: right + 1", base, window=(500, 3))
+    base = Case(family="sens", name="sens/ragged", lens=L + (40, 1023), sq=(1, 5, 17, 0, 40, 2), ragged=True, window=(500, 1), h=4, hk=1)
+    add("ragged: left + 1", base, window=(501, 1))
+    add("ragged: one length + 1", base, **longer(base, 5))
+    return pairs
+
+
+# ---- parameter tables of tests/test_attention_visibility_gpu.py ---------------------------------------------------------------------------
+
+ATTN_SK = (1, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 513, 1023, 1024)
+ATTN_SQ = (1, 2, 63, 64, 65, 255, 256, 257, 300, 513)
+ATTN_HEADS = ((2, 2), (4, 1), (6, 1))           # h / h_k = 1, 4 and 6 / 1
+
+
+def attn_pairs(causal):
+    """causal: every (sq, sk) pair of the table, sq > sk included (its first rows are dead); non-causal: the table's diagonal, which visits
+    every sk and every sq"""
+    if causal:
+        return list(itertools.product(ATTN_SQ, ATTN_SK))
+    return [(ATTN_SQ[i % len(ATTN_SQ)], sk) for i, sk in enumerate(ATTN_SK)]
+
+
+def attn_case(sq, sk, causal, d, dtype, heads):
+    """fwd / varlen_fwd as a Case: L = sk for every sequence, no window, capacity = the code's"""
+    h, hk = heads
+    return Case(family="attn", name=f"attn/sq{sq}-sk{sk}-{'causal' if causal else 'full'}-d{d}-{dtype}-h{h}_{hk}", lens=(sk,), sq=(sq,), d=d, dtype=dtype,
+                h=h, hk=hk, causal=causal, cap=1024)
+
+
+def attn_packed(causal, d, dtype, heads, equal):
+    """one varlen_fwd call: the lengths of the tables as sequences, empty ones among them (skewed: the compact grid), or eight sequences of
+    64 x 64 (equal lengths: the plain grid)"""
+    h, hk = heads
+    if equal:
+        pairs = [(64, 64)] * 8
+    else:
+        pairs = attn_pairs(False) + [(0, 64), (65, 0), (0, 0), (513, 1), (300, 255), (2, 1024), (257, 256), (64, 65)]
+    return Case(family="attn", name=f"attn/packed-{'equal' if equal else 'skewed'}-{'causal' if causal else 'full'}-d{d}-{dtype}-h{h}_{hk}", lens=tuple(p[1] for p in pairs),
+                sq=tuple(p[0] for p in pairs), d=d, dtype=dtype, h=h, hk=hk, causal=causal, cap=1024, ragged=True)
+
+
+def all_gpu_cases():
+    """every Case the two GPU modules run, for the CPU tests"""
+    cases = [c for cs in kv_families().values() for c in cs]
+    for _, base, moved in sensitivity_pairs():
+        cases += [base, moved]
+    for i, (d, dtype) in enumerate(itertools.product((64, 128), DTYPES)):
+        for causal in (True, False):
+            cases += [attn_case(sq, sk, causal, d, dtype, ATTN_HEADS[(j + i) % 3]) for j, (sq, sk) in enumerate(attn_pairs(causal))]
+            cases += [attn_packed(causal, d, dtype, ATTN_HEADS[(i + causal + e) % 3], bool(e)) for e in (0, 1)]
+    return cases
