@@ -41,7 +41,7 @@ HIP_SOURCES = ["fa_fwd_pp.hip", "fa_fwd_pp16.hip", "fa_bwd.hip", "fa_bwd_dq16.hi
 # are placed first and the prefetch sets take the AGPRs: no moves, no scratch, 408-412 registers (16-bit cache) / 276-280 (8-bit)
 EXTRA_FLAGS = {"fa_fwd_pp16.hip": ["-fno-slp-vectorize"], "fa_bwd_dq16.hip": ["-fno-slp-vectorize"], "fa_bwd_dkdv16.hip": ["-fno-slp-vectorize"],
                "fa_fwd_kvcache_d256.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"]}
-HIP_HEADERS = ["fa_device.hpp", "fa_params.hpp", "fa_bwd_dkdv_common.hpp", "fa_kvcache_quant.hpp", os.path.join(INCLUDE, "flash_attn_gfx950.h")]
+HIP_HEADERS = ["fa_device.hpp", "fa_params.hpp", "fa_bwd_dkdv_common.hpp", "fa_kvcache_quant.hpp", "fa_kvcache_attn.hpp", "fa_kvcache_kernels.hpp", "fa_kvcache_launch.hpp", "fa_kvcache_rotary.hpp", os.path.join(INCLUDE, "flash_attn_gfx950.h")]
 # -amdgpu-mfma-vgpr-form: builtin MFMAs keep their result in VGPRs even in kernels that may use the
 # accumulator half of the register file (the dK/dV kernel parks its 128 long-lived accumulator
 # registers in AGPRs through LP<T>::mfma_agpr); without it hipcc selects the AGPR form for every MFMA

@@ -1,6 +1,6 @@
 // fa_fwd_kvcache_prefill.hip — attention over a KV cache for prompt chunks: 64-row workgroups (fa_kvcache_options_v8: row_tile = 64).
 //
-//   The decode kernels of fa_fwd_kvcache.hip cut the seqlen_q x (h / h_k) packed query rows of a KV head into tiles of 16, and every tile streams
+//   The decode kernels (kvcache_attn of fa_kvcache_attn.hpp) cut the seqlen_q x (h / h_k) packed query rows of a KV head into tiles of 16, and every tile streams
 //   the whole visible K / V of its head from memory on its own.  A chunk of a prompt - hundreds or thousands of rows over a paged or 8-bit cache,
 //   which fwd / varlen_fwd cannot read - brings hundreds of such tiles per KV head.  Here a workgroup serves 64 packed rows:
 //   * four waves, wave w owns rows 16 w .. 16 w + 15 of the tile with the per-row mapping of the decode kernel: S^T = K Q^T on
@@ -21,8 +21,7 @@
 //   * a wave whose 16 rows all lie past the sequence's rows takes part in staging and barriers only.
 //   One instantiation per (dtype, head_dim, causal, layout, cache element, dense / ragged): 64 attention kernels.  A window, a soft cap, sinks, a
 //   tree mask, rotary and head_dim 256 are refused by the C ABI with row_tile = 64: nothing here serves them.
-#define FA_KVC_RAGGED_TU 1
-#include "fa_fwd_kvcache.hip"
+#include "fa_kvcache_launch.hpp"
 
 namespace fa {
 
@@ -36,49 +35,6 @@ struct KvpLds {
     static constexpr int kStage = 2 * kImage;           // K image, then V image
     static constexpr int kBytes = 2 * kStage;           // two stages
 };
-
-// kvc_slot_lookup of fa_fwd_kvcache.hip with the rows of a tile as a parameter: tiles of a sequence = ceil(sq_i * h_ratio / ROWS).  A copy, so that
-// the existing kernels' code stays what it is; a change that may touch them should make the original the ROWS = kKvcRows instantiation of this.
-template <int ROWS>
-FA_DEV bool kvc_slot_lookup_rows(const int32_t* cu, int b, int h_ratio, uint32_t slot, int& seq, int& tile) {
-    const int lane = threadIdx.x & 63;
-    for (int b0 = 0; b0 < b; b0 += kVarlenMaxBatch) {
-        const int b1 = min(b0 + kVarlenMaxBatch, b);
-        const int per = (b1 - b0 + 63) >> 6;                         // sequences per lane, <= kVarlenSeqPerLane
-        const int i0 = b0 + lane * per;
-        int c[kVarlenSeqPerLane + 1];
-#pragma unroll
-        for (int j = 0; j <= kVarlenSeqPerLane; ++j) c[j] = cu[min(i0 + min(j, per), b1)];
-        uint32_t t[kVarlenSeqPerLane], mine = 0;
-#pragma unroll
-        for (int j = 0; j < kVarlenSeqPerLane; ++j) {
-            t[j] = (j < per) ? (uint32_t)((max(c[j + 1] - c[j], 0) * h_ratio + ROWS - 1) / ROWS) : 0u;
-            mine += t[j];
-        }
-        uint32_t incl = mine;                                        // inclusive prefix over the 64 lanes
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = (uint32_t)__shfl_up((int)incl, off);
-            if (lane >= off) incl += y;
-        }
-        uint32_t run = incl - mine;
-        int f_seq = -1, f_tile = 0;
-#pragma unroll
-        for (int j = 0; j < kVarlenSeqPerLane; ++j) {
-            if (slot >= run && slot < run + t[j]) { f_seq = i0 + j; f_tile = (int)(slot - run); }
-            run += t[j];
-        }
-        const uint64_t m = __ballot(f_seq >= 0);
-        if (m != 0) {
-            const int src = __ffsll((long long)m) - 1;
-            seq = __builtin_amdgcn_readlane(f_seq, src);
-            tile = __builtin_amdgcn_readlane(f_tile, src);
-            return true;
-        }
-        slot -= (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);  // the tiles of this round of sequences
-    }
-    return false;
-}
 
 template <typename T, int D, bool CAUSAL, bool PAGED, int ES, bool RAGGED>
 FA_DEV void kvcache_prefill_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams* rg) {
@@ -106,7 +62,7 @@ FA_DEV void kvcache_prefill_attn(const KvcacheKernelParams& p, const KvcacheRagg
         kvh = bh;
         if (rg->compact) {
             const int slot = tile;
-            if (!kvc_slot_lookup_rows<kKvpRows>(rg->cu_q, p.b, p.h_ratio, (uint32_t)slot, bidx, tile)) return;      // a slack slot: nothing to write
+            if (!kvc_slot_lookup<kKvpRows>(rg->cu_q, p.b, p.h_ratio, (uint32_t)slot, bidx, tile)) return;      // a slack slot: nothing to write
         } else {
             bidx = tile / p.n_row_tiles;        // (n_row_tiles = tiles of max_seqlen_q here)
             tile -= bidx * p.n_row_tiles;
@@ -380,46 +336,22 @@ __global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_ragged_prefill_
     kvcache_prefill_attn<T, D, CAUSAL, PAGED, ES, true>(rp.kp, &rp);
 }
 
-template <typename T, int D, bool CAUSAL, bool PAGED>
-void launch_prefill_es(const KvcacheKernelParams& kp, unsigned grid, hipStream_t s) {
-    if (kp.cache_fp8) hipLaunchKernelGGL((fa_fwd_kvcache_prefill_kernel<T, D, CAUSAL, PAGED, 1>), dim3(grid), dim3(kKvcThreads), 0, s, kp);
-    else hipLaunchKernelGGL((fa_fwd_kvcache_prefill_kernel<T, D, CAUSAL, PAGED, 2>), dim3(grid), dim3(kKvcThreads), 0, s, kp);
-}
-
-template <typename T, int D>
-void launch_prefill_t(const KvcacheKernelParams& kp, unsigned grid, hipStream_t s) {
-    const bool paged = kp.block_table != nullptr;
-    if (kp.is_causal) paged ? launch_prefill_es<T, D, true, true>(kp, grid, s) : launch_prefill_es<T, D, true, false>(kp, grid, s);
-    else paged ? launch_prefill_es<T, D, false, true>(kp, grid, s) : launch_prefill_es<T, D, false, false>(kp, grid, s);
-}
-
-template <typename T, int D, bool CAUSAL, bool PAGED>
-void launch_ragged_prefill_es(const KvcacheRaggedParams& rp, unsigned grid, hipStream_t s) {
-    if (rp.kp.cache_fp8) hipLaunchKernelGGL((fa_fwd_kvcache_ragged_prefill_kernel<T, D, CAUSAL, PAGED, 1>), dim3(grid), dim3(kKvcThreads), 0, s, rp);
-    else hipLaunchKernelGGL((fa_fwd_kvcache_ragged_prefill_kernel<T, D, CAUSAL, PAGED, 2>), dim3(grid), dim3(kKvcThreads), 0, s, rp);
-}
-
-template <typename T, int D>
-void launch_ragged_prefill_t(const KvcacheRaggedParams& rp, unsigned grid, hipStream_t s) {
-    const bool paged = rp.kp.block_table != nullptr;
-    if (rp.kp.is_causal) paged ? launch_ragged_prefill_es<T, D, true, true>(rp, grid, s) : launch_ragged_prefill_es<T, D, true, false>(rp, grid, s);
-    else paged ? launch_ragged_prefill_es<T, D, false, true>(rp, grid, s) : launch_ragged_prefill_es<T, D, false, false>(rp, grid, s);
+// p as the dense / ragged launcher finished it for 64-row tiles (row tiles or slots, split, partial planes)
+template <typename P>
+hipError_t launch_prefill_attn(const P& p, int dtype, unsigned grid, hipStream_t s) {
+    kvc_dispatch<64, 128>(kvc_kp(p), dtype, [&](auto leaf) {
+        using K = decltype(leaf);
+        using T = typename K::T;
+        if (kvc_kp(p).is_causal) kvc_launch_attn(kvc_pick<P>(fa_fwd_kvcache_prefill_kernel<T, K::D, true, K::PAGED, K::ES>, fa_fwd_kvcache_ragged_prefill_kernel<T, K::D, true, K::PAGED, K::ES>), grid, s, p);
+        else kvc_launch_attn(kvc_pick<P>(fa_fwd_kvcache_prefill_kernel<T, K::D, false, K::PAGED, K::ES>, fa_fwd_kvcache_ragged_prefill_kernel<T, K::D, false, K::PAGED, K::ES>), grid, s, p);
+    });
+    return hipGetLastError();
 }
 
 }  // namespace
 
-// kp as the dense launcher finished it for 64-row tiles (row tiles, split, partial planes); grid = b x h_k x row tiles x n_split
-hipError_t launch_kvcache_prefill_attn(const KvcacheKernelParams& kp, int dtype, unsigned grid, hipStream_t s) {
-    if (dtype == 0) kp.d == 64 ? launch_prefill_t<_Float16, 64>(kp, grid, s) : launch_prefill_t<_Float16, 128>(kp, grid, s);
-    else kp.d == 64 ? launch_prefill_t<__bf16, 64>(kp, grid, s) : launch_prefill_t<__bf16, 128>(kp, grid, s);
-    return hipGetLastError();
-}
-
-// rp as the ragged launcher finished it for 64-row tiles (slots, compact, split, partial planes); grid = slots x h_k x n_split
-hipError_t launch_kvcache_ragged_prefill_attn(const KvcacheRaggedParams& rp, int dtype, unsigned grid, hipStream_t s) {
-    if (dtype == 0) rp.kp.d == 64 ? launch_ragged_prefill_t<_Float16, 64>(rp, grid, s) : launch_ragged_prefill_t<_Float16, 128>(rp, grid, s);
-    else rp.kp.d == 64 ? launch_ragged_prefill_t<__bf16, 64>(rp, grid, s) : launch_ragged_prefill_t<__bf16, 128>(rp, grid, s);
-    return hipGetLastError();
-}
+// grid = b x h_k x row tiles x n_split (dense), slots x h_k x n_split (ragged)
+hipError_t launch_kvcache_prefill_attn(const KvcacheKernelParams& kp, int dtype, unsigned grid, hipStream_t s) { return launch_prefill_attn(kp, dtype, grid, s); }
+hipError_t launch_kvcache_prefill_attn(const KvcacheRaggedParams& rp, int dtype, unsigned grid, hipStream_t s) { return launch_prefill_attn(rp, dtype, grid, s); }
 
 }  // namespace fa

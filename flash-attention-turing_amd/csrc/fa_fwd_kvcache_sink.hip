@@ -4,8 +4,7 @@
 //   is never scaled).  With the visible scores s_j of a row and M = max(max_j s_j, sink):
 //       out = sum_j exp(s_j - M) v_j / (sum_j exp(s_j - M) + exp(sink - M)),   lse = M + log(sum_j exp(s_j - M) + exp(sink - M))
 //   - the sink is one more key of the row whose V row is zero, and the LSE includes it, so exp(s_j - lse) are the probabilities used.
-//   * Unsplit launch (n_split = 1): the attention body is kvcache_attn of fa_fwd_kvcache.hip with SINK = true (this file includes that one for it,
-//     with FA_KVC_RAGGED_TU set so that the dense kernels and launchers are not compiled a second time).  The sink enters in the per-row
+//   * Unsplit launch (n_split = 1): the attention body is kvcache_attn of fa_kvcache_attn.hpp with SINK = true.  The sink enters in the per-row
 //     epilogue, behind the merge of the four waves and in front of inv and lse: one load and a few fp32 operations per row; the 32-key loop is
 //     the loop of the call without sinks.
 //   * Split launch: the attention kernels are those of the call without sinks, launched by fa_fwd_kvcache.hip / fa_fwd_kvcache_ragged.hip as ever
@@ -19,8 +18,7 @@
 //     builds the plain and causal instantiations as well (64 more kernels) and sends calls without a window to them: the A / B of DESIGN.md
 //     3.10 (tools/build_variant.py sinkplain -DFA_KVC_SINK_PLAIN=1, then tools/kvcache_bench.py --sinks --baseline-library).
 //   * Sinks with a soft cap, and sinks at head_dim 256, are refused by the C ABI: nothing here serves them.
-#define FA_KVC_RAGGED_TU 1
-#include "fa_fwd_kvcache.hip"
+#include "fa_kvcache_launch.hpp"
 
 #ifndef FA_KVC_SINK_PLAIN
 #define FA_KVC_SINK_PLAIN 0
@@ -51,23 +49,12 @@ template <typename T, int D, bool CAUSAL, bool PAGED, int ES>
 __global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_ragged_sink_plain_kernel(const KvcacheRaggedSinkParams sp) {
     kvcache_attn<T, D, CAUSAL, PAGED, false, ES, true, false, true>(sp.rp.kp, &sp.rp, 0.f, sp.sink.ptr, sp.sink.stride);
 }
-
-template <typename T, int D, bool PAGED, int ES>
-void launch_sink_plain(const KvcacheSinkParams& sp, unsigned grid, hipStream_t s) {
-    if (sp.kp.is_causal) hipLaunchKernelGGL((fa_fwd_kvcache_sink_plain_kernel<T, D, true, PAGED, ES>), dim3(grid), dim3(kKvcThreads), 0, s, sp);
-    else hipLaunchKernelGGL((fa_fwd_kvcache_sink_plain_kernel<T, D, false, PAGED, ES>), dim3(grid), dim3(kKvcThreads), 0, s, sp);
-}
-
-template <typename T, int D, bool PAGED, int ES>
-void launch_ragged_sink_plain(const KvcacheRaggedSinkParams& sp, unsigned grid, hipStream_t s) {
-    if (sp.rp.kp.is_causal) hipLaunchKernelGGL((fa_fwd_kvcache_ragged_sink_plain_kernel<T, D, true, PAGED, ES>), dim3(grid), dim3(kKvcThreads), 0, s, sp);
-    else hipLaunchKernelGGL((fa_fwd_kvcache_ragged_sink_plain_kernel<T, D, false, PAGED, ES>), dim3(grid), dim3(kKvcThreads), 0, s, sp);
-}
 #endif
 
 // fa_kvcache_combine_kernel / fa_kvcache_combine_ragged_kernel with the sink of the row's query head as one more term: M covers it, and it adds
 // exp(sink - M) to the sum behind the splits' terms (in split order, as ever) and nothing to O.  The head of row R is found as those kernels find
 // it for the output address.  All partials -inf and a finite sink: sum = 1, O = 0, LSE = the sink.
+// (A third writing of the merge loop, like the two of fa_kvcache_kernels.hpp and for the reason given there.)
 template <typename T, int D, bool RAGGED>
 FA_DEV void kvcache_sink_combine(const KvcacheKernelParams& p, const KvcacheRaggedParams* rg, const KvcacheSink& sink) {
     constexpr int TPR = D / 8;                              // threads per row, 8 columns each
@@ -135,107 +122,46 @@ template <typename T, int D>
 __global__ __launch_bounds__(kKvcCombineThreads) void fa_kvcache_sink_combine_ragged_kernel(const KvcacheRaggedSinkParams sp) {
     kvcache_sink_combine<T, D, true>(sp.rp.kp, &sp.rp, sp.sink);
 }
+template <typename P>
+using KvcSinkBlock = std::conditional_t<kKvcIsRagged<P>, KvcacheRaggedSinkParams, KvcacheSinkParams>;
 
-// a call without a window as the window code sees it: both sides unbounded, or the causal limit on the right
-void sink_window(KvcacheKernelParams& kp) {
-    if (kp.is_local) return;
-    kp.window_left = -1;
-    kp.window_right = kp.is_causal ? 0 : -1;
-}
-
-template <typename T, int D>
-void launch_sink_t(const KvcacheSinkParams& sp, unsigned grid, hipStream_t s) {
-    const bool paged = sp.kp.block_table != nullptr;
+// p as the dense / ragged launcher finished it (row tiles or slots, n_split = 1)
+template <typename P>
+hipError_t launch_sink_attn(const P& p, const KvcacheSink& sink, int dtype, unsigned grid, hipStream_t s) {
+    const KvcSinkBlock<P> sp{as_window(p), sink};
+    kvc_dispatch<64, 128>(kvc_kp(p), dtype, [&](auto leaf) {
+        using K = decltype(leaf);
+        using T = typename K::T;
 #if FA_KVC_SINK_PLAIN
-    if (!sp.kp.is_local) {
-        if (sp.kp.cache_fp8) paged ? launch_sink_plain<T, D, true, 1>(sp, grid, s) : launch_sink_plain<T, D, false, 1>(sp, grid, s);
-        else paged ? launch_sink_plain<T, D, true, 2>(sp, grid, s) : launch_sink_plain<T, D, false, 2>(sp, grid, s);
-        return;
-    }
+        if (!kvc_kp(p).is_local) {
+            if (kvc_kp(p).is_causal) kvc_launch_attn(kvc_pick<P>(fa_fwd_kvcache_sink_plain_kernel<T, K::D, true, K::PAGED, K::ES>, fa_fwd_kvcache_ragged_sink_plain_kernel<T, K::D, true, K::PAGED, K::ES>), grid, s, sp);
+            else kvc_launch_attn(kvc_pick<P>(fa_fwd_kvcache_sink_plain_kernel<T, K::D, false, K::PAGED, K::ES>, fa_fwd_kvcache_ragged_sink_plain_kernel<T, K::D, false, K::PAGED, K::ES>), grid, s, sp);
+            return;
+        }
 #endif
-    if (sp.kp.cache_fp8) {
-        if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_sink_kernel<T, D, true, 1>), dim3(grid), dim3(kKvcThreads), 0, s, sp);
-        else hipLaunchKernelGGL((fa_fwd_kvcache_sink_kernel<T, D, false, 1>), dim3(grid), dim3(kKvcThreads), 0, s, sp);
-    } else {
-        if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_sink_kernel<T, D, true, 2>), dim3(grid), dim3(kKvcThreads), 0, s, sp);
-        else hipLaunchKernelGGL((fa_fwd_kvcache_sink_kernel<T, D, false, 2>), dim3(grid), dim3(kKvcThreads), 0, s, sp);
-    }
-}
-
-template <typename T, int D>
-void launch_ragged_sink_t(const KvcacheRaggedSinkParams& sp, unsigned grid, hipStream_t s) {
-    const bool paged = sp.rp.kp.block_table != nullptr;
-#if FA_KVC_SINK_PLAIN
-    if (!sp.rp.kp.is_local) {
-        if (sp.rp.kp.cache_fp8) paged ? launch_ragged_sink_plain<T, D, true, 1>(sp, grid, s) : launch_ragged_sink_plain<T, D, false, 1>(sp, grid, s);
-        else paged ? launch_ragged_sink_plain<T, D, true, 2>(sp, grid, s) : launch_ragged_sink_plain<T, D, false, 2>(sp, grid, s);
-        return;
-    }
-#endif
-    if (sp.rp.kp.cache_fp8) {
-        if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_ragged_sink_kernel<T, D, true, 1>), dim3(grid), dim3(kKvcThreads), 0, s, sp);
-        else hipLaunchKernelGGL((fa_fwd_kvcache_ragged_sink_kernel<T, D, false, 1>), dim3(grid), dim3(kKvcThreads), 0, s, sp);
-    } else {
-        if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_ragged_sink_kernel<T, D, true, 2>), dim3(grid), dim3(kKvcThreads), 0, s, sp);
-        else hipLaunchKernelGGL((fa_fwd_kvcache_ragged_sink_kernel<T, D, false, 2>), dim3(grid), dim3(kKvcThreads), 0, s, sp);
-    }
-}
-
-template <typename T, int D>
-void launch_sink_combine_t(const KvcacheSinkParams& sp, hipStream_t s) {
-    const int64_t rows_per_block = kKvcCombineThreads / (D / 8);
-    hipLaunchKernelGGL((fa_kvcache_sink_combine_kernel<T, D>), dim3((unsigned)((sp.kp.rows_total + rows_per_block - 1) / rows_per_block)),
-                       dim3(kKvcCombineThreads), 0, s, sp);
-}
-
-template <typename T, int D>
-void launch_ragged_sink_combine_t(const KvcacheRaggedSinkParams& sp, hipStream_t s) {
-    const int64_t rows_per_block = kKvcCombineThreads / (D / 8);
-    hipLaunchKernelGGL((fa_kvcache_sink_combine_ragged_kernel<T, D>), dim3((unsigned)((sp.rp.kp.rows_total + rows_per_block - 1) / rows_per_block)),
-                       dim3(kKvcCombineThreads), 0, s, sp);
-}
-
-}  // namespace
-
-// kp as the dense launcher finished it (row tiles, n_split = 1); grid = b x h_k x row tiles
-hipError_t launch_kvcache_sink_attn(const KvcacheKernelParams& kp, const KvcacheSink& sink, int dtype, unsigned grid, hipStream_t s) {
-    KvcacheSinkParams sp;
-    sp.kp = kp;
-    sp.sink = sink;
-    sink_window(sp.kp);
-    if (dtype == 0) kp.d == 64 ? launch_sink_t<_Float16, 64>(sp, grid, s) : launch_sink_t<_Float16, 128>(sp, grid, s);
-    else kp.d == 64 ? launch_sink_t<__bf16, 64>(sp, grid, s) : launch_sink_t<__bf16, 128>(sp, grid, s);
-    return hipGetLastError();
-}
-
-// rp as the ragged launcher finished it (slots, compact, n_split = 1); grid = slots x h_k
-hipError_t launch_kvcache_ragged_sink_attn(const KvcacheRaggedParams& rp, const KvcacheSink& sink, int dtype, unsigned grid, hipStream_t s) {
-    KvcacheRaggedSinkParams sp;
-    sp.rp = rp;
-    sp.sink = sink;
-    sink_window(sp.rp.kp);
-    if (dtype == 0) rp.kp.d == 64 ? launch_ragged_sink_t<_Float16, 64>(sp, grid, s) : launch_ragged_sink_t<_Float16, 128>(sp, grid, s);
-    else rp.kp.d == 64 ? launch_ragged_sink_t<__bf16, 64>(sp, grid, s) : launch_ragged_sink_t<__bf16, 128>(sp, grid, s);
+        kvc_launch_attn(kvc_pick<P>(fa_fwd_kvcache_sink_kernel<T, K::D, K::PAGED, K::ES>, fa_fwd_kvcache_ragged_sink_kernel<T, K::D, K::PAGED, K::ES>), grid, s, sp);
+    });
     return hipGetLastError();
 }
 
 // behind the attention launch of a split call (n_split > 1, the partial planes of the call without sinks)
-hipError_t launch_kvcache_sink_combine(const KvcacheKernelParams& kp, const KvcacheSink& sink, int dtype, hipStream_t s) {
-    KvcacheSinkParams sp;
-    sp.kp = kp;
-    sp.sink = sink;
-    if (dtype == 0) kp.d == 64 ? launch_sink_combine_t<_Float16, 64>(sp, s) : launch_sink_combine_t<_Float16, 128>(sp, s);
-    else kp.d == 64 ? launch_sink_combine_t<__bf16, 64>(sp, s) : launch_sink_combine_t<__bf16, 128>(sp, s);
+template <typename P>
+hipError_t launch_sink_combine(const P& p, const KvcacheSink& sink, int dtype, hipStream_t s) {
+    const KvcSinkBlock<P> sp{p, sink};
+    kvc_dispatch_td<64, 128>(dtype, kvc_kp(p).d, [&](auto leaf) {
+        using K = decltype(leaf);
+        using T = typename K::T;
+        kvc_launch_combine<K::D>(kvc_pick<P>(fa_kvcache_sink_combine_kernel<T, K::D>, fa_kvcache_sink_combine_ragged_kernel<T, K::D>), kvc_kp(p).rows_total, s, sp);
+    });
     return hipGetLastError();
 }
 
-hipError_t launch_kvcache_ragged_sink_combine(const KvcacheRaggedParams& rp, const KvcacheSink& sink, int dtype, hipStream_t s) {
-    KvcacheRaggedSinkParams sp;
-    sp.rp = rp;
-    sp.sink = sink;
-    if (dtype == 0) rp.kp.d == 64 ? launch_ragged_sink_combine_t<_Float16, 64>(sp, s) : launch_ragged_sink_combine_t<_Float16, 128>(sp, s);
-    else rp.kp.d == 64 ? launch_ragged_sink_combine_t<__bf16, 64>(sp, s) : launch_ragged_sink_combine_t<__bf16, 128>(sp, s);
-    return hipGetLastError();
-}
+}  // namespace
+
+// grid = b x h_k x row tiles (dense), slots x h_k (ragged)
+hipError_t launch_kvcache_sink_attn(const KvcacheKernelParams& kp, const KvcacheSink& sink, int dtype, unsigned grid, hipStream_t s) { return launch_sink_attn(kp, sink, dtype, grid, s); }
+hipError_t launch_kvcache_sink_attn(const KvcacheRaggedParams& rp, const KvcacheSink& sink, int dtype, unsigned grid, hipStream_t s) { return launch_sink_attn(rp, sink, dtype, grid, s); }
+hipError_t launch_kvcache_sink_combine(const KvcacheKernelParams& kp, const KvcacheSink& sink, int dtype, hipStream_t s) { return launch_sink_combine(kp, sink, dtype, s); }
+hipError_t launch_kvcache_sink_combine(const KvcacheRaggedParams& rp, const KvcacheSink& sink, int dtype, hipStream_t s) { return launch_sink_combine(rp, sink, dtype, s); }
 
 }  // namespace fa

@@ -4,8 +4,7 @@
 //   FlashInfer): the sq query rows of a sequence are the nodes of a tree, every node sees the whole cached prefix, and among the draft tokens -
 //   the last sq keys of the sequence, base = L - sq - a node sees only what its 64-bit word says.  Query row t sees key j iff 0 <= j < L and
 //       j < base   or   bit (j - base) of tree_mask[i, t] is set.
-//   * The attention body is kvcache_attn of fa_fwd_kvcache.hip with TREE = true (this file includes that one for it, with FA_KVC_RAGGED_TU set so
-//     that the dense kernels and launchers are not compiled a second time): the plain, non-causal instantiation - steps [0, L), lim = L - whose
+//   * The attention body is kvcache_attn of fa_kvcache_attn.hpp with TREE = true: the plain, non-causal instantiation - steps [0, L), lim = L - whose
 //     select tests the bit.  A lane owns one query row for the whole split and loads its word once in the prologue.  Nothing else differs, so
 //     the lower-triangle mask gives the causal call bit for bit and the full mask the non-causal call, for every split count.
 //   * The launchers run the attention kernel alone, split or not, on the grid the dense / ragged launcher computed.  Append, partial planes and
@@ -15,8 +14,7 @@
 //   * One instantiation per (dtype, head_dim, layout, cache element), dense and ragged: 32 attention kernels.  FA_KVC_TREE_UNIFORM = 1 builds
 //     them with a wave-uniform branch that leaves the steps wholly inside the prefix on the plain select.
 //   * A tree mask with causal, a window, a soft cap, sinks, rotary or head_dim 256 is refused by the C ABI: nothing here serves them.
-#define FA_KVC_RAGGED_TU 1
-#include "fa_fwd_kvcache.hip"
+#include "fa_kvcache_launch.hpp"
 
 namespace fa {
 
@@ -31,51 +29,22 @@ template <typename T, int D, bool PAGED, int ES>
 __global__ __launch_bounds__(kKvcThreads, 2) void fa_fwd_kvcache_ragged_tree_kernel(const KvcacheRaggedTreeParams tp) {
     kvcache_attn<T, D, false, PAGED, false, ES, true, false, false, true>(tp.rp.kp, &tp.rp, 0.f, nullptr, 0, &tp.tree);
 }
-
-template <typename T, int D>
-void launch_tree_t(const KvcacheTreeParams& tp, unsigned grid, hipStream_t s) {
-    const bool paged = tp.kp.block_table != nullptr;
-    if (tp.kp.cache_fp8) {
-        if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_tree_kernel<T, D, true, 1>), dim3(grid), dim3(kKvcThreads), 0, s, tp);
-        else hipLaunchKernelGGL((fa_fwd_kvcache_tree_kernel<T, D, false, 1>), dim3(grid), dim3(kKvcThreads), 0, s, tp);
-    } else {
-        if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_tree_kernel<T, D, true, 2>), dim3(grid), dim3(kKvcThreads), 0, s, tp);
-        else hipLaunchKernelGGL((fa_fwd_kvcache_tree_kernel<T, D, false, 2>), dim3(grid), dim3(kKvcThreads), 0, s, tp);
-    }
-}
-
-template <typename T, int D>
-void launch_ragged_tree_t(const KvcacheRaggedTreeParams& tp, unsigned grid, hipStream_t s) {
-    const bool paged = tp.rp.kp.block_table != nullptr;
-    if (tp.rp.kp.cache_fp8) {
-        if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_ragged_tree_kernel<T, D, true, 1>), dim3(grid), dim3(kKvcThreads), 0, s, tp);
-        else hipLaunchKernelGGL((fa_fwd_kvcache_ragged_tree_kernel<T, D, false, 1>), dim3(grid), dim3(kKvcThreads), 0, s, tp);
-    } else {
-        if (paged) hipLaunchKernelGGL((fa_fwd_kvcache_ragged_tree_kernel<T, D, true, 2>), dim3(grid), dim3(kKvcThreads), 0, s, tp);
-        else hipLaunchKernelGGL((fa_fwd_kvcache_ragged_tree_kernel<T, D, false, 2>), dim3(grid), dim3(kKvcThreads), 0, s, tp);
-    }
+// p as the dense / ragged launcher finished it (row tiles or slots, split, partial planes)
+template <typename P>
+hipError_t launch_tree_attn(const P& p, const KvcacheTree& tree, int dtype, unsigned grid, hipStream_t s) {
+    const std::conditional_t<kKvcIsRagged<P>, KvcacheRaggedTreeParams, KvcacheTreeParams> tp{p, tree};
+    kvc_dispatch<64, 128>(kvc_kp(p), dtype, [&](auto leaf) {
+        using K = decltype(leaf);
+        using T = typename K::T;
+        kvc_launch_attn(kvc_pick<P>(fa_fwd_kvcache_tree_kernel<T, K::D, K::PAGED, K::ES>, fa_fwd_kvcache_ragged_tree_kernel<T, K::D, K::PAGED, K::ES>), grid, s, tp);
+    });
+    return hipGetLastError();
 }
 
 }  // namespace
 
-// kp as the dense launcher finished it (row tiles, split, partial planes); grid = b x h_k x row tiles x n_split
-hipError_t launch_kvcache_tree_attn(const KvcacheKernelParams& kp, const KvcacheTree& tree, int dtype, unsigned grid, hipStream_t s) {
-    KvcacheTreeParams tp;
-    tp.kp = kp;
-    tp.tree = tree;
-    if (dtype == 0) kp.d == 64 ? launch_tree_t<_Float16, 64>(tp, grid, s) : launch_tree_t<_Float16, 128>(tp, grid, s);
-    else kp.d == 64 ? launch_tree_t<__bf16, 64>(tp, grid, s) : launch_tree_t<__bf16, 128>(tp, grid, s);
-    return hipGetLastError();
-}
-
-// rp as the ragged launcher finished it (slots, compact, split, partial planes); grid = slots x h_k x n_split
-hipError_t launch_kvcache_ragged_tree_attn(const KvcacheRaggedParams& rp, const KvcacheTree& tree, int dtype, unsigned grid, hipStream_t s) {
-    KvcacheRaggedTreeParams tp;
-    tp.rp = rp;
-    tp.tree = tree;
-    if (dtype == 0) rp.kp.d == 64 ? launch_ragged_tree_t<_Float16, 64>(tp, grid, s) : launch_ragged_tree_t<_Float16, 128>(tp, grid, s);
-    else rp.kp.d == 64 ? launch_ragged_tree_t<__bf16, 64>(tp, grid, s) : launch_ragged_tree_t<__bf16, 128>(tp, grid, s);
-    return hipGetLastError();
-}
+// grid = b x h_k x row tiles x n_split (dense), slots x h_k x n_split (ragged)
+hipError_t launch_kvcache_tree_attn(const KvcacheKernelParams& kp, const KvcacheTree& tree, int dtype, unsigned grid, hipStream_t s) { return launch_tree_attn(kp, tree, dtype, grid, s); }
+hipError_t launch_kvcache_tree_attn(const KvcacheRaggedParams& rp, const KvcacheTree& tree, int dtype, unsigned grid, hipStream_t s) { return launch_tree_attn(rp, tree, dtype, grid, s); }
 
 }  // namespace fa

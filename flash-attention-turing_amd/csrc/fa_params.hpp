@@ -208,6 +208,9 @@ int64_t kvcache_ragged_slots(const KvcacheKernelParams& kp, int64_t total_q, int
 hipError_t launch_fwd_kvcache_ragged(KvcacheRaggedParams rp, int dtype, hipStream_t stream, float cap_pre = 0.f, KvcacheSink sink = KvcacheSink{nullptr, 0},
                                      KvcacheTree tree = KvcacheTree{nullptr, 0, 0}, int32_t row_tile = kKvcRows);
 
+// The family files below each wrap instantiations of one attention body (kvcache_attn of fa_kvcache_attn.hpp, or the 64-row body of
+// fa_fwd_kvcache_prefill.hip) in kernels of their own and export the launch of their attention kernel, overloaded on the dense and the ragged
+// params; kvc_route_attn of fa_kvcache_launch.hpp calls them in the place of the caller's own attention launch.
 // Soft-capped scores (fa_fwd_kvcache_softcap.hip, fa_kvcache_options_v5.softcap > 0): score = softcap * tanh(q . k * softmax_scale / softcap).
 // The kernels are kvcache_attn with SOFTCAP = true and read kp.scale = softcap, kp.scale_log2e = softcap * log2(e) (the host puts the cap where
 // the scale was) and pre = 2 log2(e) * softmax_scale / softcap, which travels in a block of its own and not in KvcacheKernelParams: the kernarg
@@ -223,7 +226,7 @@ struct KvcacheRaggedSoftcapParams {
     float pre;
 };
 hipError_t launch_kvcache_softcap_attn(const KvcacheKernelParams& kp, float pre, int dtype, unsigned grid, hipStream_t stream);
-hipError_t launch_kvcache_ragged_softcap_attn(const KvcacheRaggedParams& rp, float pre, int dtype, unsigned grid, hipStream_t stream);
+hipError_t launch_kvcache_softcap_attn(const KvcacheRaggedParams& rp, float pre, int dtype, unsigned grid, hipStream_t stream);
 
 // Attention sinks (fa_fwd_kvcache_sink.hip): out = sum_j exp(s_j - M) v_j / (sum_j exp(s_j - M) + exp(sink - M)) with M = max(max_j s_j, sink), and
 // the LSE includes the sink.  Unsplit (n_split = 1): the kernels are kvcache_attn with SINK = true, which adds the term in the per-row epilogue;
@@ -240,9 +243,9 @@ struct KvcacheRaggedSinkParams {
     KvcacheSink sink;
 };
 hipError_t launch_kvcache_sink_attn(const KvcacheKernelParams& kp, const KvcacheSink& sink, int dtype, unsigned grid, hipStream_t stream);
-hipError_t launch_kvcache_ragged_sink_attn(const KvcacheRaggedParams& rp, const KvcacheSink& sink, int dtype, unsigned grid, hipStream_t stream);
+hipError_t launch_kvcache_sink_attn(const KvcacheRaggedParams& rp, const KvcacheSink& sink, int dtype, unsigned grid, hipStream_t stream);
 hipError_t launch_kvcache_sink_combine(const KvcacheKernelParams& kp, const KvcacheSink& sink, int dtype, hipStream_t stream);
-hipError_t launch_kvcache_ragged_sink_combine(const KvcacheRaggedParams& rp, const KvcacheSink& sink, int dtype, hipStream_t stream);
+hipError_t launch_kvcache_sink_combine(const KvcacheRaggedParams& rp, const KvcacheSink& sink, int dtype, hipStream_t stream);
 
 // Tree attention masks (fa_fwd_kvcache_tree.hip): the kernels are kvcache_attn with TREE = true - the plain (non-causal) body over the steps
 // [0, L) whose select tests a bit of the row's mask word for the last sq keys.  They launch the attention kernel alone, split or not, on the grid
@@ -258,7 +261,7 @@ struct KvcacheRaggedTreeParams {
     KvcacheTree tree;
 };
 hipError_t launch_kvcache_tree_attn(const KvcacheKernelParams& kp, const KvcacheTree& tree, int dtype, unsigned grid, hipStream_t stream);
-hipError_t launch_kvcache_ragged_tree_attn(const KvcacheRaggedParams& rp, const KvcacheTree& tree, int dtype, unsigned grid, hipStream_t stream);
+hipError_t launch_kvcache_tree_attn(const KvcacheRaggedParams& rp, const KvcacheTree& tree, int dtype, unsigned grid, hipStream_t stream);
 
 // 64-row workgroups for prompt chunks (fa_fwd_kvcache_prefill.hip, fa_kvcache_options_v8.row_tile = 64): four waves of 16 rows each walk the same
 // 32-key steps over K / V images staged once per workgroup in LDS, double-buffered; no merge of waves, the epilogue writes o / lse or the partial
@@ -266,7 +269,7 @@ hipError_t launch_kvcache_ragged_tree_attn(const KvcacheRaggedParams& rp, const 
 // of kKvcPrefillRows.  They launch the attention kernel alone, split or not; the append in front and the combine behind are the unchanged ones.
 // A window, a soft cap, sinks, a tree mask, rotary and head_dim 256 are refused by the C ABI with row_tile = 64.
 hipError_t launch_kvcache_prefill_attn(const KvcacheKernelParams& kp, int dtype, unsigned grid, hipStream_t stream);
-hipError_t launch_kvcache_ragged_prefill_attn(const KvcacheRaggedParams& rp, int dtype, unsigned grid, hipStream_t stream);
+hipError_t launch_kvcache_prefill_attn(const KvcacheRaggedParams& rp, int dtype, unsigned grid, hipStream_t stream);
 
 // Rotary embedding on a decode call (fa_kvcache_rotary.hip, fa_kvcache_options_v3).  One fused launch takes the place of the append: it
 // rotates k_new into the cache, copies / quantises v_new, and writes the rotated q into `q_image`, a contiguous (b, seqlen_q, h, d) buffer of
@@ -286,8 +289,8 @@ struct KvcacheRotaryParams {
 int64_t kvcache_rotary_image_bytes(const KvcacheKernelParams& kp);     // bytes of q_image, rounded up to 16
 hipError_t launch_kvcache_rotary(const KvcacheRotaryParams& rp, int dtype, hipStream_t stream);
 
-// head_dim 256 (fa_fwd_kvcache_d256.hip): every kernel of a decode call at d = 256 - attention, append, combine, rotary - lives in that file, built
-// for ONE workgroup per compute unit.  The three launchers above finish kp / rp exactly as for 64 / 128 (row tiles, slots, split,
+// head_dim 256 (fa_fwd_kvcache_d256.hip): every kernel of a decode call at d = 256 - attention, append, combine, rotary - is instantiated in that file
+// (from the same headers as at 64 / 128), built for ONE workgroup per compute unit.  The three launchers above finish kp / rp exactly as for 64 / 128 (row tiles, slots, split,
 // workspace planes) and hand over here where they would pick their own instantiations.
 hipError_t launch_kvcache_d256(const KvcacheKernelParams& kp, int dtype, hipStream_t stream, float cap_pre);
 hipError_t launch_kvcache_ragged_d256(const KvcacheRaggedParams& rp, int dtype, hipStream_t stream, float cap_pre);

@@ -24,7 +24,7 @@ digits) - a swap invisible to both digits; the value path (V is 0 / 1); the back
 The expectation is `visible`, a pure integer model written from the README's formulas (no float in it, nothing taken from the kernels).
 This module holds the encoding, the model, the decoder, the condition asserts, the cache builders and the parameter tables of the GPU
 tests (tests/test_kvcache_visibility_gpu.py, tests/test_attention_visibility_gpu.py), which tests/test_visibility_cpu.py enumerates
-without a GPU."""
+without a GPU, and the route table of tests/test_kvcache_routes_gpu.py (one case per leaf of the launch dispatch; tests/test_kvcache_routes_cpu.py)."""
 import itertools
 from dataclasses import dataclass, replace
 from functools import lru_cache
@@ -511,6 +511,58 @@ def kv_families():
 
 def kv_cases(family):
     return kv_families()[family]
+
+
+# ---- parameter tables of tests/test_kvcache_routes_gpu.py: one case per leaf of the launch dispatch --------------------------------------
+
+ROUTE_CAP = 96                          # three 32-key steps: a forced split of 2 is real
+ROUTE_LENS = (0, 31, 33, 70, 96)
+ROUTE_FAMILIES = ("plain", "causal", "window", "softcap", "sinks", "tree", "prefill", "prefill_causal", "d256_causal", "d256_window", "d256_softcap", "append")
+_ROUTE_KW = {
+    "plain": {}, "causal": dict(causal=True), "window": dict(window=(5, 0)), "softcap": dict(causal=True, softcap=SOFTCAP), "sinks": dict(causal=True, sink="zero"),
+    "tree": {}, "prefill": dict(prefill=True), "prefill_causal": dict(prefill=True, causal=True),
+    "d256_causal": dict(causal=True), "d256_window": dict(window=(5, 0)), "d256_softcap": dict(causal=True, softcap=SOFTCAP), "append": dict(causal=True, append=True),
+}
+
+
+@lru_cache(maxsize=None)
+def route_cases(family):
+    """The common axes CROSSED, where the families above rotate them: dense / ragged x dtype x head_dim x layout x cache width x num_splits, at
+    the smallest shapes at which a wrong leaf still shows - h / h_k = 2 / 1 (rows packed across heads), sq = 3 (ragged: 1 and 3; the 64-row
+    kernels: 63 and 65), every length of ROUTE_LENS in one call.  `append` is not a kernel family: the causal call with its rows appended,
+    for the leaves of the append launch."""
+    kw = _ROUTE_KW[family]
+    wide = "prefill" in family
+    out = []
+    for ragged, dtype, d, page, fp8, splits in itertools.product((False, True), DTYPES, (256,) if family.startswith("d256") else (64, 128), (0, 16), (False, True), (1, 2)):
+        # a ragged call carries both sq in its batch, a dense call has one
+        for sqs in ([(63, 65) if wide else (1, 3)] if ragged else [(63,), (65,)] if wide else [(3,)]):
+            pairs = [(L, s) for L in ROUTE_LENS for s in sqs]
+            if kw.get("append"):
+                pairs = [(max(L, s), s) for L, s in pairs]
+            tree = tuple(heap_words(s) for _, s in pairs) if family == "tree" else None
+            name = f"route-{family}/{'ragged' if ragged else 'dense'}-{dtype}-d{d}-{'paged' if page else 'contig'}-{'fp8' if fp8 else '16bit'}-splits{splits}" + ("" if ragged else f"-sq{sqs[0]}")
+            out.append(Case(family="route-" + family, name=name, lens=tuple(p[0] for p in pairs), sq=tuple(p[1] for p in pairs), d=d, dtype=dtype, fp8=fp8, page=page,
+                            h=2, hk=1, splits=splits, tree=tree, ragged=ragged, cap=ROUTE_CAP, **kw))
+    return out
+
+
+def route_leaf(c):
+    """the attention kernel a route case must run, as the launch layer keys it: (file, dense / ragged, dtype, head_dim, layout, cache width[, mode]).
+    mode is there only where the file has an instantiation per mask; a split call with sinks runs the causal kernel of the call without them."""
+    if c.d == 256:
+        file, mode = "d256", "softcap" if c.softcap else "window"
+    elif c.prefill:
+        file, mode = "prefill", c.causal
+    elif c.softcap:
+        file, mode = "softcap", None
+    elif c.sink is not None and c.splits == 1:
+        file, mode = "sinks", None
+    elif c.tree is not None:
+        file, mode = "tree", None
+    else:
+        file, mode = "ragged" if c.ragged else "dense", "window" if c.window != (-1, -1) else "causal" if c.causal else "plain"
+    return (file, c.ragged, c.dtype, c.d, bool(c.page), c.fp8, mode)
 
 
 # ---- sensitivity: one parameter moved by one, at the largest length of each family -------------------------------------------------------

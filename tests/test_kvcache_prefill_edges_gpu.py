@@ -463,7 +463,7 @@ def test_plain_ragged_grid(gpu, dtname, d, case):
 @pytest.mark.parametrize("b", [65, 130, 513, 600])
 @pytest.mark.parametrize("dtname,d,heads", [("fp16", 128, (32, 8)), ("bf16", 64, (6, 2))], ids=["fp16-d128-h32k8", "bf16-d64-h6k2"])
 def test_many_sequences(gpu, b, dtname, d, heads):
-    """kvc_slot_lookup_rows<64> with more than one sequence per lane (b > 64) and a second round of 512 (b > 512): sq_i from {0, 1, 3, 17, 64,
+    """kvc_slot_lookup<64> with more than one sequence per lane (b > 64) and a second round of 512 (b > 512): sq_i from {0, 1, 3, 17, 64,
     65} with empty sequences in the first 64 and past index 512, caches of 128 rows with lengths in [0, 128], causal, num_splits 1 and a forced
     2, on the compact grid (asserted).  Every sequence bit for bit against the dense prefill call (batched by sq: a dense batch entry is tiled
     like a sequence of the ragged call), a sample of at least 40 against fp64."""
