@@ -19,11 +19,11 @@ CONDITIONS, derived and asserted on the inputs (`check_conditions`), never used 
   * capacity <= B * B keys, so that the second digit is unique: 1024 keys at d = 64, 4096 at d = 128 and 256.
 
 WHAT IT DOES NOT SEE: two key sets with the same count and the same digit histogram (remove (a, b) and (c, e), add (a, e) and (c, b), in
-digits) - a swap invisible to both digits; the value path (V is 0 / 1); the backward.
+digits) - a swap invisible to both digits; the value path (V is 0 / 1).  The backward has a probe of its own, below (THE BACKWARD PROBE).
 
 The expectation is `visible`, a pure integer model written from the README's formulas (no float in it, nothing taken from the kernels).
 This module holds the encoding, the model, the decoder, the condition asserts, the cache builders and the parameter tables of the GPU
-tests (tests/test_kvcache_visibility_gpu.py, tests/test_attention_visibility_gpu.py), which tests/test_visibility_cpu.py enumerates
+tests (tests/test_kvcache_visibility_gpu.py, tests/test_attention_visibility_gpu.py, tests/test_attention_backward_visibility_gpu.py), which tests/test_visibility_cpu.py enumerates
 without a GPU, and the route table of tests/test_kvcache_routes_gpu.py (one case per leaf of the launch dispatch; tests/test_kvcache_routes_cpu.py)."""
 import itertools
 from dataclasses import dataclass, replace
@@ -656,4 +656,295 @@ def all_gpu_cases():
         for causal in (True, False):
             cases += [attn_case(sq, sk, causal, d, dtype, ATTN_HEADS[(j + i) % 3]) for j, (sq, sk) in enumerate(attn_pairs(causal))]
             cases += [attn_packed(causal, d, dtype, ATTN_HEADS[(i + causal + e) % 3], bool(e)) for e in (0, 1)]
+    return cases
+
+
+# ---- THE BACKWARD PROBE (tests/test_attention_backward_visibility_gpu.py) ---------------------------------------------
+#
+# bwd / varlen_bwd take O and LSE as ARGUMENTS, and the kernels use them in two places only: P = exp2(s * c - lse * log2e) and
+# D = rowsum(dO * O).  With lse = 0, O = 0 and every score exactly 0 (Q = 0 or K = 0), P is exactly 1 on every (row, key) pair a kernel
+# treats as visible and 0 elsewhere, D = 0 and dS = P * dP.  V = 1 in every column and dO_t = code(t), the two-digit one-hot code of the
+# query row's index in its sequence, make dP = dO_t . V_j = 2 exactly.  Two calls per case:
+#   A: Q = 0, K_j = code(j):  dQ_t = scale * 2 * hist_keys(t),  dV_j = sum over the group's hot query heads of hist_rows(j),  dK = 0
+#   B: K = 0, Q_t = code(t):  dK_j = scale * 2 * sum over the hot heads of hist_rows(j),  dV as in A,  dQ = 0
+# hist_keys(t) = the digit histogram of the keys row t sees (`visible`), hist_rows(j) = that of the rows that see key j (`rows_seeing`,
+# the transpose in closed form).  Every gradient is a small integer (times scale), held exactly by the fp32 accumulators.
+#
+# HOT HEADS.  hot = None: every query head carries dO (and Q in call B), every KV head K / V: a group's dK / dV is ratio x hist, which
+# pins that every head is counted once in total.  hot = g: query head g alone carries dO (and Q), its KV head alone K / V; every other
+# head holds zeros and must come back exactly 0, the hot ones exactly 1 x hist: which head, not only how many.
+#
+# The code is `codes(64, 1024)`, base 32, on the first 64 columns at EVERY head_dim (the other columns of d = 128 are 0 and must come
+# back 0): up to 1024 rows or keys, at most 32 of them share a digit, which keeps the integers small enough for bf16.
+#
+# CONDITIONS, derived and asserted on the inputs (`bwd_check_conditions`), never used to drop a case:
+#   * every expected integer (dQ: 2 m, dK: 2 x hot heads of the group x m, dV: hot heads x m; m <= 32 the largest digit count) is at most
+#     256 in bf16 and 2048 in fp16: every integer up to there is exact in the type, so a count one off cannot round back;
+#   * d = 64: scale = 1 / 8, a power of two - everything is exact and the outputs are compared as bits;
+#   * d = 128: scale = fp32(1 / sqrt(128)) is not a power of two.  A kernel returns x = round16(fp32(N * scale)) (one fp32 product, one
+#     rounding to 16 bits: the epilogues and fa_bwd_sum_splits_kernel), so |x / scale - N| <= (2^(e - p) + 2^(e - 24)) / scale with
+#     e = floor(log2(N * scale)) and p = 11 (fp16), 8 (bf16) significant bits; required below 0.25: N <= 724 in fp16, N <= 90 in bf16.
+# The tables choose hot = None where 2 x ratio x 32 meets these and rotate the single hot head through the group's positions where it
+# does not (bf16: ratio 6 at d = 64, ratios 4 and 6 at d = 128), so every (sq, sk) runs at every ratio in both types.
+#
+# WHAT IT DOES NOT SEE: swaps invisible to both digits (as in the forward); the value path (operands are 0 / 1 / 2); a use of O or LSE
+# other than the two above that cancels at O = 0, LSE = 0.
+
+BWD_BASE = 32
+BWD_CAP = 1024
+BWD_INT_EXACT = {"fp16": 2048, "bf16": 256}          # every integer up to here is exact in the type
+BWD_SIG_BITS = {"fp16": 11, "bf16": 8}
+BWD_GQA_HEADS = ((4, 1), (6, 1), (8, 2))             # the group split needs a group
+BWD_BATCH = 2
+
+
+def bwd_scale(d):
+    """the kernels' softmax scale, 1.0f / sqrtf((float)d), as a Python float"""
+    return float(np.float32(1.0) / np.sqrt(np.float32(d)))
+
+
+def bwd_decode_error(n, dtype, d):
+    """upper bound of |x / scale - n| for x = round16(fp32(n * scale)): 0 where scale is a power of two"""
+    import math
+
+    s = bwd_scale(d)
+    if n == 0 or math.frexp(s)[0] == 0.5:
+        return 0.0
+    e = math.floor(math.log2(n * s))
+    return (2.0 ** (e - BWD_SIG_BITS[dtype]) + 2.0 ** (e - 24)) / s
+
+
+@lru_cache(maxsize=None)
+def bwd_int_limit(dtype, d):
+    """the largest N such that every integer up to N is exact in the type and decodes with an error below 0.25"""
+    n = 0
+    while n < BWD_INT_EXACT[dtype] and bwd_decode_error(n + 1, dtype, d) < 0.25:
+        n += 1
+    return n
+
+
+@lru_cache(maxsize=None)
+def bwd_code(d):
+    """int64 (1024, d): row i = the code of query row or key i of its sequence"""
+    c = np.zeros((BWD_CAP, d), dtype=np.int64)
+    c[:, : 2 * BWD_BASE] = codes(2 * BWD_BASE, BWD_CAP)
+    c.setflags(write=False)
+    return c
+
+
+@lru_cache(maxsize=None)
+def _bwd_prefix(d):
+    p = np.zeros((BWD_CAP + 1, d), dtype=np.int64)
+    np.cumsum(bwd_code(d), axis=0, out=p[1:])
+    return p
+
+
+def rows_seeing(L, sq, j, causal=False):
+    """The transpose of `visible` without window or tree: the query rows of a sequence with L keys and sq rows that see key j, a range.
+    j < L, and under the bottom-right causal mask j <= L - sq + t, i.e. t >= j - (L - sq)."""
+    L = max(int(L), 0)
+    if not 0 <= j < L:
+        return range(0)
+    lo = max(0, j - (L - sq)) if causal else 0
+    return range(lo, max(lo, sq))
+
+
+@lru_cache(maxsize=32)
+def _seq_hists(L, sq, causal, d):
+    """hist_keys int64 (sq, d) and hist_rows int64 (L, d) of one sequence"""
+    p = _bwd_prefix(d)
+    vis = [visible(L, sq, t, causal)[0] for t in range(sq)]
+    seen = [rows_seeing(L, sq, j, causal) for j in range(L)]
+    hk = p[[r.stop for r in vis]] - p[[r.start for r in vis]] if sq else np.zeros((0, d), dtype=np.int64)
+    hr = p[[r.stop for r in seen]] - p[[r.start for r in seen]] if L else np.zeros((0, d), dtype=np.int64)
+    return hk, hr
+
+
+def bwd_head_weights(c, hot):
+    """wq int64 (h,): 1 on the hot query heads; cnt int64 (hk,): the hot query heads of each KV head's group"""
+    wq = np.ones(c.h, dtype=np.int64) if hot is None else np.eye(c.h, dtype=np.int64)[hot]
+    return wq, wq.reshape(c.hk, c.ratio).sum(axis=1)
+
+
+def bwd_check_conditions(c, hot, n_max):
+    """the preconditions of the probe and its derived conditions, on the inputs; n_max = (dQ, dK, dV) largest expected integers"""
+    assert c.d in (64, 128) and c.dtype in DTYPES and c.window == (-1, -1) and c.tree is None and not c.fp8 and c.cap == BWD_CAP
+    assert len(c.lens) == len(c.sq) and all(0 <= L <= BWD_CAP for L in c.lens) and all(0 <= s <= BWD_CAP for s in c.sq)
+    assert c.h % c.hk == 0 and (hot is None or 0 <= hot < c.h)
+    assert max(n_max) <= BWD_INT_EXACT[c.dtype], f"{c.name}: an expected integer {max(n_max)} is not exact in {c.dtype}"
+    err = bwd_decode_error(max(n_max[:2]), c.dtype, c.d)
+    assert err < 0.25, f"{c.name}: {max(n_max[:2])} x scale decodes with an error up to {err:.3f} in {c.dtype} at d = {c.d}"
+
+
+def expected_bwd(c, hot, call):
+    """-> (dQ int64 (Rq, h, d), dK int64 (Rk, hk, d), dV int64 (Rk, hk, d)), rows [(i, t)], keys [(i, j)]: the model's integers of call
+    "A" or "B" in packed (sequence, row) and (sequence, key) order; dQ and dK are in units of scale"""
+    hists = [_seq_hists(L, s, c.causal, c.d) for L, s in zip(c.lens, c.sq)]
+    hk = np.concatenate([x[0] for x in hists])
+    hr = np.concatenate([x[1] for x in hists])
+    wq, cnt = bwd_head_weights(c, hot)
+    dq = 2 * hk[:, None, :] * wq[None, :, None]
+    dk = 2 * hr[:, None, :] * cnt[None, :, None]
+    dv = hr[:, None, :] * cnt[None, :, None]
+    bwd_check_conditions(c, hot, (int(dq.max(initial=0)), int(dk.max(initial=0)), int(dv.max(initial=0))))
+    if call == "A":
+        dk = np.zeros_like(dk)
+    else:
+        assert call == "B"
+        dq = np.zeros_like(dq)
+    rows = [(i, t) for i, s in enumerate(c.sq) for t in range(s)]
+    keys = [(i, j) for i, L in enumerate(c.lens) for j in range(L)]
+    return (dq, dk, dv), rows, keys
+
+
+def decode_bwd(c, grads):
+    """(dQ, dK, dV) fp16 / bf16 -> int64 tensors: dQ and dK in units of scale"""
+    import torch
+
+    s = bwd_scale(c.d)
+    for name, x in zip(("dQ", "dK", "dV"), grads):
+        assert torch.isfinite(x.float()).all().item(), f"{c.name}: non-finite {name} (a read of NaN LSE padding or of memory outside the views)"
+    return tuple(torch.round(x.double() / m).long() for x, m in zip(grads, (s, s, 1.0)))
+
+
+def bwd_mismatch(c, grads, exp):
+    """per tensor a bool (R, heads): where the decoded integers differ from the model, an expected 0 is not an exact 0, or - where the
+    scale is a power of two - the bits differ"""
+    import math
+
+    import torch
+
+    s = bwd_scale(c.d)
+    out = []
+    for x, dec, e, m in zip(grads, decode_bwd(c, grads), exp, (s, s, 1.0)):
+        e = torch.from_numpy(e).to(x.device)
+        bad = ((dec != e) | ((e == 0) & (x != 0))).any(dim=-1)                  # (an expected 0 is an exact 0 at every scale)
+        if math.frexp(m)[0] == 0.5:
+            bad |= (x != (e.double() * m).to(x.dtype)).any(dim=-1)
+        out.append(bad)
+    return out
+
+
+def assert_bwd_signature(c, hot, call, grads, exp, rows, keys):
+    """integer (and, at a power-of-two scale, bit) equality of every gradient with the model on every (sequence, head, row or key).  The
+    message names the first rows / keys that differ with the digit columns that differ."""
+    bads = bwd_mismatch(c, grads, exp)
+    if not any(b.any().item() for b in bads):
+        return
+    dec = decode_bwd(c, grads)
+    msgs, total = [], 0
+    for name, what, index, lens, bad, x, d_int, e in zip(("dQ", "dK", "dV"), ("row", "key", "key"), (rows, keys, keys), (c.sq, c.lens, c.lens), bads, grads, dec, exp):
+        total += int(bad.sum())
+        for r, g in bad.nonzero()[:4].tolist():
+            i, t = index[r]
+            diff = np.flatnonzero(d_int[r, g].cpu().numpy() != e[r, g])[:12]
+            cols = {(f"lo{k}" if k < BWD_BASE else f"hi{k - BWD_BASE}" if k < 2 * BWD_BASE else f"pad{k}"): (int(e[r, g, k]), int(d_int[r, g, k])) for k in diff}
+            msgs.append(f"{name} seq {i} (L={c.lens[i]}, sq={c.sq[i]}) head {g} {what} {t}: digit counts (expected, decoded) that differ: {cols or 'none (the bits differ)'}")
+    raise AssertionError(f"{c.name} call {call} hot={hot}: {total} (row or key, head) signatures differ from the model [{c}]\n  " + "\n  ".join(msgs))
+
+
+def bwd_inputs(c, hot, call, dev):
+    """The probe's operands in packed order with three rows of the bad code behind each: q, do (Rq + 3, h, d) and k, v (Rk + 3, hk, d) in the
+    case's dtype.  Cold heads are 0.  (A dense call repeats the one sequence over its batch and slices the tail off per entry.)"""
+    import torch
+
+    dt = torch_dtype(c.dtype)
+    code = torch.from_numpy(bwd_code(c.d).copy()).to(dev).to(dt)
+    wq, cnt = bwd_head_weights(c, hot)
+    wq = torch.from_numpy(wq).to(dev).to(dt).view(1, c.h, 1)
+    wk = torch.from_numpy((cnt > 0).astype(np.int64)).to(dev).to(dt).view(1, c.hk, 1)
+    rq = torch.cat([torch.arange(s, device=dev) for s in c.sq] + [torch.zeros(0, dtype=torch.long, device=dev)])
+    rk = torch.cat([torch.arange(L, device=dev) for L in c.lens] + [torch.zeros(0, dtype=torch.long, device=dev)])
+
+    def behind(x):
+        return torch.cat([x, torch.full((3,) + tuple(x.shape[1:]), BAD, dtype=dt, device=dev)])
+
+    do = code[rq].unsqueeze(1) * wq
+    v = torch.ones(len(rk), 1, c.d, dtype=dt, device=dev) * wk
+    if call == "A":
+        q, k = torch.zeros_like(do), code[rk].unsqueeze(1) * wk
+    else:
+        q, k = do.clone(), torch.zeros_like(v)
+    return behind(q), behind(k), behind(v), behind(do)
+
+
+# ---- parameter tables of tests/test_attention_backward_visibility_gpu.py ------------------------------------------------------------------
+
+def bwd_hot(heads, dtype, d, j):
+    """None (every head hot) where the group sum 2 x ratio x 32 meets the derived conditions, else the single hot head, rotated by j"""
+    h, hk = heads
+    return None if 2 * (h // hk) * BWD_BASE <= bwd_int_limit(dtype, d) else j % h
+
+
+def _cfg(d, dtype):
+    return (d == 128) * 2 + DTYPES.index(dtype)
+
+
+def bwd_dense_cases(d, dtype, causal, gqa=False):
+    """[(Case, hot)].  gqa = False (bwd of the host module): every (sq, sk) of attn_pairs, h / h_k rotating through ATTN_HEADS.  gqa = True
+    (the C ABI with and without a workspace): every third pair, the phase rotated over (d, dtype, causal), h / h_k through BWD_GQA_HEADS."""
+    i = _cfg(d, dtype)
+    pairs = attn_pairs(causal)
+    if gqa:
+        pairs = pairs[(i + causal) % 3:: 3]
+    table = BWD_GQA_HEADS if gqa else ATTN_HEADS
+    out = []
+    for n, (sq, sk) in enumerate(pairs):
+        heads = table[(n + i) % 3]
+        out.append((attn_case(sq, sk, causal, d, dtype, heads), bwd_hot(heads, dtype, d, n // 3)))       # (n // 3: a shape recurs every third case)
+    return out
+
+
+def bwd_packed_case(d, dtype, causal, equal, gqa=False):
+    i = _cfg(d, dtype)
+    heads = (BWD_GQA_HEADS if gqa else ATTN_HEADS)[(i + causal + equal) % 3]
+    return attn_packed(causal, d, dtype, heads, equal), bwd_hot(heads, dtype, d, i + 2 * causal + equal)
+
+
+HEAD_SHAPES = ((2, 2), (4, 1), (6, 1), (8, 2))         # h / h_k = 1, 4, 6, and 4 over two KV heads
+
+
+def bwd_head_cases(d, dtype, causal, split):
+    """[(Case, hot)]: every head position of every shape hot once, on a dense call (three 128-key blocks, five 64-row tiles, a 44-key offset
+    of the diagonal) and on a packed one with an empty sequence on either side.  The group split needs a group: no h / h_k = 1 then."""
+    out = []
+    for heads in HEAD_SHAPES[1:] if split else HEAD_SHAPES:
+        for g in range(heads[0]):
+            out.append((attn_case(257, 301, causal, d, dtype, heads), g))
+            pairs = ((64, 65), (0, 64), (130, 257), (65, 0), (129, 70))
+            out.append((Case(family="attn", name=f"attn/head-packed-{'causal' if causal else 'full'}-d{d}-{dtype}-h{heads[0]}_{heads[1]}", lens=tuple(p[1] for p in pairs),
+                             sq=tuple(p[0] for p in pairs), d=d, dtype=dtype, h=heads[0], hk=heads[1], causal=causal, cap=1024, ragged=True), g))
+    return out
+
+
+def bwd_sensitivity_pairs():
+    """(name, base, moved, hot): one length moved by one at the largest shapes of the tables, packed with a second sequence"""
+    def mk(name, sqs, lens, causal, d, dtype, heads):
+        return Case(family="attn", name=f"attn/bwd-sens-{name}", lens=tuple(lens), sq=tuple(sqs), d=d, dtype=dtype, h=heads[0], hk=heads[1], causal=causal, cap=1024, ragged=True)
+
+    out = []
+    for k, (name, sqs, lens, moved_sq, moved_len, causal) in enumerate((
+            ("causal-key+1", (513, 300), (1023, 257), (513, 300), (1024, 257), True),
+            ("causal-key-1", (513, 300), (1023, 257), (513, 300), (1023, 256), True),
+            ("causal-row+1", (512, 257), (1024, 300), (513, 257), (1024, 300), True),
+            ("causal-row+1-dead", (512, 257), (1024, 256), (512, 258), (1024, 256), True),
+            ("full-key+1", (513, 64), (1023, 129), (513, 64), (1024, 129), False),
+            ("full-row+1", (512, 64), (1024, 129), (513, 64), (1024, 129), False))):
+        d, dtype = ((64, "fp16"), (128, "bf16"), (128, "fp16"), (64, "bf16"))[k % 4]
+        heads = ATTN_HEADS[k % 3]
+        out.append((name, mk(name, sqs, lens, causal, d, dtype, heads), mk(name + "-moved", moved_sq, moved_len, causal, d, dtype, heads), bwd_hot(heads, dtype, d, k)))
+    return out
+
+
+def all_bwd_gpu_cases():
+    """every (Case, hot) tests/test_attention_backward_visibility_gpu.py runs, for the CPU tests"""
+    cases = []
+    for d, dtype, causal in itertools.product((64, 128), DTYPES, (True, False)):
+        cases += bwd_dense_cases(d, dtype, causal) + bwd_dense_cases(d, dtype, causal, gqa=True)
+        for equal in (False, True):
+            cases += [bwd_packed_case(d, dtype, causal, equal), bwd_packed_case(d, dtype, causal, equal, gqa=True)]
+        for split in (False, True):
+            cases += bwd_head_cases(d, dtype, causal, split)
+    for _, base, moved, hot in bwd_sensitivity_pairs():
+        cases += [(base, hot), (moved, hot)]
     return cases

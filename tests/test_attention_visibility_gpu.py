@@ -6,7 +6,8 @@ of the visible keys' digits.  Every assertion is an integer equality with the mo
 causal mask).  Rows past each K / V extent hold the bad code (1 in every column).  Dead rows (causal with sq > sk, empty key sequences)
 are O = 0, LSE = 0 exactly, and the padded LSE entries of a packed call are exactly 0, as documented.
 
-The backward is out of scope: with uniform P, dK / dV are sums of dO / n_i over rows and do not decode to integers with this coding."""
+The backward has its own probe (tests/test_attention_backward_visibility_gpu.py): with the forward's uniform P, dK / dV are sums of
+dO / n_i over rows and do not decode, but bwd / varlen_bwd take O and LSE as arguments, and lse = 0 makes P exactly 0 / 1."""
 import itertools
 
 import numpy as np

@@ -210,3 +210,162 @@ def test_every_axis_value_occurs_in_every_family():
     assert any(c.v_scale != 1.0 for c in fams["plain"])
     for _, base, moved in V.sensitivity_pairs():
         assert [a != b for a, b in zip(V.row_sets(base), V.row_sets(moved))].count(True) >= 1
+
+
+# ---- the backward probe ------------------------------------------------------------------------------------------------------------------
+
+def pair_matrix(L, sq, causal):
+    """int64 (sq, L): 1 where the model's row t sees key j, from `visible` row by row"""
+    m = np.zeros((sq, max(L, 0)), dtype=np.int64)
+    for t in range(sq):
+        r, extras = V.visible(L, sq, t, causal)
+        assert not extras
+        m[t, r.start:r.stop] = 1
+    return m
+
+
+def pair_hists(m, d):
+    """fp32 sums over one sequence's pair weights m int64 (sq, L): (sq, d) = sum over the keys row t sees of code(j), (L, d) = sum over
+    the rows that see key j of code(t).  The integers stay far below 2^24: the sums are exact."""
+    code = torch.from_numpy(V.bwd_code(d).copy()).float()
+    w = torch.from_numpy(m).float()
+    hk, hr = w @ code[: m.shape[1]], w.t() @ code[: m.shape[0]]
+    assert max(float(x.max()) if x.numel() else 0.0 for x in (hk, hr)) < 2 ** 22
+    return hk, hr
+
+
+def emulate_bwd(c, wq, mats, call, hists=None):
+    """The backward's arithmetic on pair weights: mats[i] int64 (sq_i, L_i) = how often the kernels count pair (t, j) of sequence i (the
+    model: 0 / 1), wq int64 (h,) = how often each query head is counted.  fp32 sums of the integers dS = P x dP = 2 and P = 1 times the
+    0 / 1 codes, one fp32 product with scale, one rounding to the output type.  -> (dQ (Rq, h, d), dK, dV (Rk, hk, d)) in the output type"""
+    dt = V.torch_dtype(c.dtype)
+    scale = np.float32(V.bwd_scale(c.d))
+    hists = hists or [pair_hists(m, c.d) for m in mats]
+    hk, hr = torch.cat([x[0] for x in hists]), torch.cat([x[1] for x in hists])
+    wq = torch.from_numpy(np.asarray(wq)).float()
+    cnt = wq.view(c.hk, c.ratio).sum(dim=1)
+    dq = 2 * hk.unsqueeze(1) * wq.view(1, -1, 1)
+    dk = 2 * hr.unsqueeze(1) * cnt.view(1, -1, 1)
+    dv = hr.unsqueeze(1) * cnt.view(1, -1, 1)
+    if call == "A":
+        dk = torch.zeros_like(dk)
+    else:
+        dq = torch.zeros_like(dq)
+    return (dq * scale).to(dt), (dk * scale).to(dt), dv.to(dt)
+
+
+def test_rows_seeing_is_the_transpose_of_visible():
+    checked = 0
+    for L, sq, causal in itertools.product((0, 1, 2, 5, 9, 33, 40, 64, 65), (0, 1, 2, 5, 9, 17, 64, 70), (False, True)):
+        pairs = {(t, j) for t in range(sq) for j in V.visible_set(L, sq, t, causal)}
+        for j in range(-1, L + 2):
+            assert set(V.rows_seeing(L, sq, j, causal)) == {t for t, jj in pairs if jj == j}, (L, sq, j, causal)
+        checked += 1
+    assert checked == 144
+
+
+def test_backward_decoder_returns_the_model_on_every_gpu_case():
+    """the emulated kernel outputs of both calls of every case, built from the brute-force pair matrix, decode to the closed forms'
+    integers (which asserts the derived conditions on the real inputs), with no mismatch in integers or - at d = 64 - bits"""
+    cases = V.all_bwd_gpu_cases()
+    assert len(cases) > 1400
+    seen, pairs, hists = set(), 0, {}
+    for c, hot in cases:
+        key = (c.lens, c.sq, c.causal, c.d, c.dtype, c.h, c.hk, hot)
+        if key in seen:
+            continue                                                            # (the same call by another route: host module, C ABI with and without a workspace)
+        seen.add(key)
+        for L, s in zip(c.lens, c.sq):
+            if (L, s, c.causal, c.d) not in hists:
+                m = pair_matrix(L, s, c.causal)
+                hists[L, s, c.causal, c.d] = pair_hists(m, c.d) + (int(m.sum()),)
+        mats = [hists[L, s, c.causal, c.d] for L, s in zip(c.lens, c.sq)]
+        pairs += sum(x[2] for x in mats)
+        wq, _ = V.bwd_head_weights(c, hot)
+        for call in "AB":
+            exp, rows, keys = V.expected_bwd(c, hot, call)
+            grads = emulate_bwd(c, wq, None, call, hists=mats)
+            assert [g.shape for g in grads] == [(len(rows), c.h, c.d), (len(keys), c.hk, c.d), (len(keys), c.hk, c.d)]
+            V.assert_bwd_signature(c, hot, call, grads, exp, rows, keys)
+    assert len(seen) > 700 and pairs > 10 ** 7
+
+
+def test_backward_tables_cover_what_they_claim():
+    cases = V.all_bwd_gpu_cases()
+    for d, dtype, causal in itertools.product((64, 128), V.DTYPES, (True, False)):
+        dense = V.bwd_dense_cases(d, dtype, causal)
+        assert [(c.sq[0], c.lens[0]) for c, _ in dense] == V.attn_pairs(causal)
+        assert {c.ratio for c, _ in dense} == {1, 4, 6} and {c.ratio for c, _ in V.bwd_dense_cases(d, dtype, causal, gqa=True)} == {4, 6}
+        assert {c.hk for c, _ in V.bwd_dense_cases(d, dtype, causal, gqa=True)} == {1, 2}
+        for split in (False, True):
+            head = V.bwd_head_cases(d, dtype, causal, split)
+            for heads in V.HEAD_SHAPES[1:] if split else V.HEAD_SHAPES:         # every head position hot, dense and packed
+                for ragged in (False, True):
+                    assert sorted(g for c, g in head if (c.h, c.hk) == heads and c.ragged == ragged) == list(range(heads[0]))
+    # a single hot head only where the group sum would leave the decodable range; every position of the group hot where it does
+    for c, hot in cases:
+        if hot is None:
+            assert 2 * c.ratio * V.BWD_BASE <= V.bwd_int_limit(c.dtype, c.d)
+    assert [V.bwd_int_limit(t, d) for t, d in (("fp16", 64), ("bf16", 64), ("fp16", 128), ("bf16", 128))] == [2048, 256, 724, 90]
+    rotated = [(c, hot) for c, hot in V.bwd_dense_cases(128, "bf16", True) if c.ratio == 6]
+    assert {hot for _, hot in rotated} == set(range(6))
+    assert any(s > L for c, _ in cases for L, s in zip(c.lens, c.sq)) and any(s == 0 for c, _ in cases for s in c.sq) and any(L == 0 for c, _ in cases for L in c.lens)
+    for _, base, moved, _ in V.bwd_sensitivity_pairs():
+        assert sum(a != b for a, b in zip(base.lens + base.sq, moved.lens + moved.sq)) == 1
+
+
+def _bwd_signature(c, wq, mats):
+    sig = []
+    for call in "AB":
+        grads = emulate_bwd(c, wq, mats, call)
+        sig += [x.numpy() for x in V.decode_bwd(c, grads)]
+    return sig
+
+
+def _differs(a, b):
+    return any(x.shape != y.shape or not np.array_equal(x, y) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("dtype", V.DTYPES)
+@pytest.mark.parametrize("d", [64, 128])
+@pytest.mark.parametrize("heads", V.HEAD_SHAPES)
+def test_every_backward_mutation_changes_the_decoded_signature(d, dtype, heads):
+    """at the largest shape of the tables, 513 x 1024 under the causal mask: what a mask, tile or head-index bug can do to the pair
+    weights or to the head counts changes the decoded integers of call A or B"""
+    sq, L = 513, 1024
+    hot = V.bwd_hot(heads, dtype, d, 3)
+    c = V.attn_case(sq, L, True, d, dtype, heads)
+    wq, _ = V.bwd_head_weights(c, hot)
+    m0 = pair_matrix(L, sq, True)
+    base = _bwd_signature(c, wq, [m0])
+    exp = [V.expected_bwd(c, hot, call)[0] for call in "AB"]
+    assert not _differs(base, [x for e in exp for x in e])
+    t, lim = 300, L - sq + 300                                                  # row 300 sees keys 0 .. lim
+    jt = np.arange(sq)[:, None], np.arange(L)[None, :]
+    muts = {}
+
+    def mut(name, f):
+        m = m0.copy()
+        f(m)
+        muts[name] = ([m], wq)
+
+    mut("one pair dropped at the diagonal", lambda m: m.__setitem__((t, lim), 0))
+    mut("one pair dropped at a tile seam", lambda m: m.__setitem__((256, 128), 0))
+    mut("one pair added just outside the mask", lambda m: m.__setitem__((t, lim + 1), 1))
+    muts["the diagonal shifted by + 1"] = ([(jt[1] <= L - sq + jt[0] + 1).astype(np.int64)], wq)
+    muts["the diagonal shifted by - 1"] = ([(jt[1] <= L - sq + jt[0] - 1).astype(np.int64)], wq)
+    mut("a 64-row Q tile of one 128-key block skipped", lambda m: m.__setitem__((slice(64, 128), slice(128, 256)), 0))
+    mut("a 64-row Q tile of one 128-key block doubled", lambda m: m.__setitem__((slice(64, 128), slice(128, 256)), 2))
+    mut("the first Q tile of a diagonal key block skipped", lambda m: m.__setitem__((slice(128, 192), slice(640, 768)), 0))     # keys 640 .. 767 are seen from row 129 on
+    mut("a 128-key block skipped", lambda m: m.__setitem__((slice(None), slice(256, 384)), 0))
+    mut("a 128-key block doubled", lambda m: m.__setitem__((slice(None), slice(256, 384)), 2 * m0[:, 256:384]))
+    mut("a 64-key tile of one 256-row block skipped", lambda m: m.__setitem__((slice(256, 512), slice(64, 128)), 0))
+    hot_heads = np.flatnonzero(wq)
+    muts["a head counted twice"] = ([m0], wq + np.eye(c.h, dtype=np.int64)[hot_heads[0]])
+    muts["a head omitted"] = ([m0], wq - np.eye(c.h, dtype=np.int64)[hot_heads[-1]])
+    if hot is not None:
+        for other in sorted({(hot + 1) % c.h, (hot + c.ratio) % c.h} - {hot}):  # a neighbour in the group, the same position of the next group
+            muts[f"heads {hot} and {other} exchanged"] = ([m0], np.eye(c.h, dtype=np.int64)[other])
+    for name, (mats, w) in muts.items():
+        assert _differs(_bwd_signature(c, w, mats), base), f"{name} is invisible at d={d} {dtype} h={heads}"
+    assert len(muts) >= 13
