@@ -739,4 +739,103 @@ int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* user) { return fa_kv
 int32_t fa_kvcache_num_splits(const fa_kvcache_params* user) { return fa_kvcache_num_splits_ex(user, nullptr); }
 int fa_run_mha_fwd_kvcache(const fa_kvcache_params* user, void* stream) { return fa_run_mha_fwd_kvcache_ex(user, nullptr, stream); }
 
+// ---- MLA decode over a latent KV cache -------------------------------------------------------------------------------------------------------
+// fa_mla_params -> KvcacheMlaParams, validated.  kp.d = 512 is the width of V, of o and of the partial planes; the split and the workspace are the
+// decode call's rules over the grid of 64-row tiles.  with_workspace = false: the `workspace` fields are not looked at.
+static int fill_mla(const fa_mla_params* user, fa::KvcacheMlaParams& mp, fa_mla_params& local, bool with_workspace) {
+    int rc = import_params(user, local, "fa_mla_params", sizeof(fa_mla_params));
+    if (rc) return rc;
+    const fa_mla_params* p = &local;
+    const bool paged = p->block_table != nullptr;
+    if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0 || p->seqlen_new < 0 || p->h <= 0)
+        return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d seqlen_new=%d h=%d", p->b, p->seqlen_q, p->seqlen_cache, p->seqlen_new, p->h);
+    if (p->d_qk != 576) return fail(FA_ERR_BAD_HEADDIM, "d_qk %d unsupported (the latent row is 576 wide: 512 compressed + 64 rope elements)", p->d_qk);
+    if (p->d_v != 512) return fail(FA_ERR_BAD_HEADDIM, "d_v %d unsupported (the value is the first 512 elements of the latent row)", p->d_v);
+    if (p->dtype != FA_FP16 && p->dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", p->dtype);
+    if (paged) {
+        const int P = p->page_block_size;
+        if (P == 0) return fail(FA_ERR_BAD_SHAPE, "block_table given without page_block_size");
+        if (P < 0 || P % 16 != 0) return fail(FA_ERR_BAD_SHAPE, "page_block_size %d must be a positive multiple of 16", P);
+        if (p->num_blocks < 1) return fail(FA_ERR_BAD_SHAPE, "num_blocks %d: a paged cache needs at least one page", p->num_blocks);
+        if (p->seqlen_cache <= 0 || p->seqlen_cache % P != 0)
+            return fail(FA_ERR_BAD_SHAPE, "seqlen_cache (%d) must be a positive multiple of page_block_size (%d) with block_table", p->seqlen_cache, P);
+        if (p->block_table_stride < p->seqlen_cache / P)
+            return fail(FA_ERR_BAD_STRIDE, "block_table_stride %lld is below the table's %d columns (seqlen_cache / page_block_size)",
+                        (long long)p->block_table_stride, p->seqlen_cache / P);
+        if ((reinterpret_cast<uintptr_t>(p->block_table) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "block_table must be 4-byte aligned");
+    } else if (p->page_block_size != 0) {
+        return fail(FA_ERR_NULL_POINTER, "page_block_size = %d given without block_table", p->page_block_size);
+    }
+    if (p->seqlen_new > p->seqlen_cache)
+        return fail(FA_ERR_BAD_SHAPE, "seqlen_new (%d) exceeds the cache capacity seqlen_cache (%d)", p->seqlen_new, p->seqlen_cache);
+    if (p->kv_new != nullptr && p->cache_seqlens == nullptr) return fail(FA_ERR_NULL_POINTER, "kv_new needs cache_seqlens (the rows it is appended at)");
+    if (p->kv_new == nullptr && p->seqlen_new != 0) return fail(FA_ERR_BAD_SHAPE, "seqlen_new = %d without kv_new", p->seqlen_new);
+    if (p->num_splits < 0) return fail(FA_ERR_BAD_SHAPE, "num_splits must be >= 0 (0 = the library's choice), got %d", p->num_splits);
+    if (!(p->softmax_scale >= 0.f) || isinf(p->softmax_scale))
+        return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default 576 ** -0.5)", (double)p->softmax_scale);
+    if (p->reserved_ != 0) return fail(FA_ERR_BAD_ABI, "fa_mla_params: reserved_ is not zero (a field of a newer header that this library does not know)");
+    if (with_workspace && p->workspace_bytes < 0) return fail(FA_ERR_BAD_SHAPE, "workspace_bytes must be >= 0");
+    if (with_workspace && p->workspace != nullptr && (reinterpret_cast<uintptr_t>(p->workspace) & 15u) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
+    // the attention grid is b x 64-row tiles x n_split workgroups (n_split <= 128), and a packed row index is an int
+    const int64_t tiles = ((int64_t)p->seqlen_q * p->h + fa::kKvcPrefillRows - 1) / fa::kKvcPrefillRows;
+    if ((int64_t)p->seqlen_q * p->h >= ((int64_t)1 << 31) || (int64_t)p->b * tiles >= ((int64_t)1 << 24))
+        return fail(FA_ERR_BAD_SHAPE, "call too large: b = %d sequences x seqlen_q = %d rows x h = %d heads exceeds the launch grid", p->b, p->seqlen_q, p->h);
+    fa_strides kvc = p->kv_cache_stride, kvn = p->kv_new_stride;
+    kvc.head = kvn.head = 0;        // one KV head
+    if (p->b > 0) {
+        if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
+        if ((rc = check_tensor("q", p->q, p->q_stride, p->seqlen_q, p->d_qk, false))) return rc;
+        if ((rc = check_tensor("o", p->o, p->o_stride, p->seqlen_q, p->d_v, false))) return rc;
+        // paged: the descriptors span at most one page, so the 2^31-byte limit applies per page (page offsets are 64-bit)
+        if ((rc = check_tensor("kv_cache", p->kv_cache, kvc, paged ? p->page_block_size : p->seqlen_cache, p->d_qk, false))) return rc;
+        if (p->kv_new != nullptr && (rc = check_tensor("kv_new", p->kv_new, kvn, p->seqlen_new, p->d_qk, false))) return rc;
+    }
+    memset(&mp, 0, sizeof(mp));
+    fa::KvcacheKernelParams& kp = mp.kp;
+    mp.d_qk = p->d_qk;
+    kp.q_ptr = p->q; kp.k_cache = p->kv_cache; kp.v_cache = p->kv_cache; kp.k_new = p->kv_new; kp.v_new = p->kv_new;
+    kp.o_ptr = p->o; kp.lse_ptr = p->lse; kp.cache_seqlens = p->cache_seqlens;
+    kp.q = conv(p->q_stride); kp.kc = kp.vc = conv(kvc); kp.kn = kp.vn = conv(kvn); kp.o = conv(p->o_stride);
+    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_cache = p->seqlen_cache; kp.seqlen_new = p->kv_new != nullptr ? p->seqlen_new : 0;
+    kp.h = p->h; kp.h_k = 1; kp.h_ratio = p->h; kp.d = p->d_v;
+    kp.is_causal = p->is_causal ? 1 : 0;
+    kp.scale = p->softmax_scale > 0.f ? p->softmax_scale : 1.0f / sqrtf((float)p->d_qk);
+    kp.scale_log2e = kp.scale * 1.4426950408889634f;
+    if (paged) {
+        kp.block_table = p->block_table; kp.bt_stride = p->block_table_stride;
+        kp.page_size = p->page_block_size; kp.num_blocks = p->num_blocks;
+    }
+    return FA_OK;
+}
+
+int64_t fa_mla_workspace_bytes(const fa_mla_params* user) {
+    fa::KvcacheMlaParams mp;
+    fa_mla_params local;
+    int rc = fill_mla(user, mp, local, false);
+    if (rc) return rc;
+    if (mp.kp.b == 0) return 0;
+    return fa::kvcache_workspace_bytes(mp.kp, fa::kvcache_split(mp.kp, -1, local.num_splits, -1, fa::kKvcPrefillRows));
+}
+
+int32_t fa_mla_num_splits(const fa_mla_params* user) {
+    fa::KvcacheMlaParams mp;
+    fa_mla_params local;
+    int rc = fill_mla(user, mp, local, true);
+    if (rc) return rc;
+    if (mp.kp.b == 0) return 1;
+    return fa::kvcache_split(mp.kp, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits, -1, fa::kKvcPrefillRows);
+}
+
+int fa_run_mla_fwd_kvcache(const fa_mla_params* user, void* stream) {
+    fa::KvcacheMlaParams mp;
+    fa_mla_params local;
+    int rc = fill_mla(user, mp, local, true);
+    if (rc) return rc;
+    if (mp.kp.b == 0) return FA_OK;
+    mp.kp.n_split = fa::kvcache_split(mp.kp, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits, -1, fa::kKvcPrefillRows);
+    mp.kp.ws_o = mp.kp.n_split > 1 ? (float*)local.workspace : nullptr;
+    return hip_status(fa::launch_fwd_kvcache_mla(mp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache_mla launch");
+}
+
 }  // extern "C"

@@ -180,6 +180,14 @@ FA_DEV uint32_t lds_tile_off(uint32_t row, uint32_t slot /* 16-byte slot in row,
         // and the swizzle's top two bits put each row into another 64-byte bank quarter.  The row pitch, a multiple of 256, adds nothing.
         uint32_t s = slot ^ (((row & 3) << 2) | ((row >> 2) & 3));
         return row * 512u + (s << 4);
+    } else if constexpr (D == 512) {
+        // (MLA decode only, fa_fwd_kvcache_mla.hip: the 512 compressed columns of a latent row) 64 slots per 1024-byte row: four 256-byte bank rows.  The
+        // D = 256 argument, re-read for 64 slots per row: slot bits 5..4 only pick which of a row's four bank rows is touched, both patterns are
+        // counted modulo one bank row, and the swizzle touches the low four slot bits alone, so (1) and (2) hold word for word; the pitch, again a
+        // multiple of 256, adds nothing.  (A 1152-byte pitch - the whole 576-element latent row in one image - is no multiple of 256 and would
+        // shift every row by half a bank row: the rope columns therefore get an image of their own, at D = 64.)
+        uint32_t s = slot ^ (((row & 3) << 2) | ((row >> 2) & 3));
+        return row * 1024u + (s << 4);
     } else {
         static_assert(D == 64, "head_dim must be 64 or 128");
         // 8 slots per row. bits: slot = (c1 c0 | w) with chunk pairs; use row bits 1..3.

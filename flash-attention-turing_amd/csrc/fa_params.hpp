@@ -271,6 +271,17 @@ hipError_t launch_kvcache_tree_attn(const KvcacheRaggedParams& rp, const Kvcache
 hipError_t launch_kvcache_prefill_attn(const KvcacheKernelParams& kp, int dtype, unsigned grid, hipStream_t stream);
 hipError_t launch_kvcache_prefill_attn(const KvcacheRaggedParams& rp, int dtype, unsigned grid, hipStream_t stream);
 
+// Multi-head latent attention over a latent KV cache (fa_fwd_kvcache_mla.hip, fa_run_mla_fwd_kvcache): MQA over one KV head whose key is the d_qk = 576
+// wide latent row and whose value is the first kp.d = 512 columns of the same row.  In kp: k_cache = the latent cache (v_cache, vc, v_new, vn are not
+// read), k_new / kn the new rows, h_k = 1, h_ratio = h, d = 512 - the width of o and of the partial planes, which kvcache_split and
+// kvcache_workspace_bytes size (row_tile = kKvcPrefillRows).  A block of its own and not fields of KvcacheKernelParams: the kernarg segment of every
+// other kernel stays what it was.  The launcher fills row tiles, split keys and the LSE plane like launch_fwd_kvcache.
+struct KvcacheMlaParams {
+    KvcacheKernelParams kp;
+    int32_t d_qk;               // 576: 512 compressed columns, then 64 rope columns
+};
+hipError_t launch_fwd_kvcache_mla(KvcacheMlaParams mp, int dtype, hipStream_t stream);
+
 // Rotary embedding on a decode call (fa_kvcache_rotary.hip, fa_kvcache_options_v3).  One fused launch takes the place of the append: it
 // rotates k_new into the cache, copies / quantises v_new, and writes the rotated q into `q_image`, a contiguous (b, seqlen_q, h, d) buffer of
 // q's dtype at the head of the caller's workspace; the attention kernels then read that image as their q.  A block of its own and not

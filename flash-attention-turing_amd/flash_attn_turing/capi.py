@@ -122,6 +122,17 @@ class KvcacheOptionsV8(_Params):
     _fields_ = KvcacheOptionsV7._fields_ + [("row_tile", _i32), ("reserved4_", _i32), ("reserved4", ctypes.c_int64 * 5)]
 
 
+class MlaParams(_Params):
+    """fa_mla_params: MLA decode over a latent KV cache (fa_run_mla_fwd_kvcache)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("q", _vp), ("kv_cache", _vp), ("kv_new", _vp), ("o", _vp), ("lse", _vp),
+                ("cache_seqlens", _vp),
+                ("b", _i32), ("seqlen_q", _i32), ("seqlen_cache", _i32), ("seqlen_new", _i32), ("h", _i32), ("d_qk", _i32), ("d_v", _i32),
+                ("dtype", _i32), ("is_causal", _i32), ("num_splits", _i32), ("softmax_scale", ctypes.c_float), ("reserved_", _i32),
+                ("q_stride", Strides), ("kv_cache_stride", Strides), ("kv_new_stride", Strides), ("o_stride", Strides),
+                ("workspace", _vp), ("workspace_bytes", ctypes.c_int64),
+                ("block_table", _vp), ("block_table_stride", ctypes.c_int64), ("page_block_size", _i32), ("num_blocks", _i32)]
+
+
 FA_CACHE_FP8_E4M3 = 1
 
 
@@ -170,6 +181,12 @@ def lib():
         L.fa_kvcache_num_splits_ex.restype = ctypes.c_int32
         L.fa_kvcache_row_tile_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op]
         L.fa_kvcache_row_tile_ex.restype = ctypes.c_int32
+        L.fa_run_mla_fwd_kvcache.argtypes = [ctypes.POINTER(MlaParams), _vp]
+        L.fa_run_mla_fwd_kvcache.restype = ctypes.c_int
+        L.fa_mla_workspace_bytes.argtypes = [ctypes.POINTER(MlaParams)]
+        L.fa_mla_workspace_bytes.restype = ctypes.c_int64
+        L.fa_mla_num_splits.argtypes = [ctypes.POINTER(MlaParams)]
+        L.fa_mla_num_splits.restype = ctypes.c_int32
         L.fa_mha_fwd.argtypes = [_vp] * 5 + [_i32] * 8 + [_vp]
         L.fa_mha_bwd.argtypes = [_vp] * 10 + [_i32] * 8 + [_vp]
         L.fa_mha_varlen_fwd.argtypes = [_vp] * 7 + [_i32] * 8 + [_vp]
@@ -477,3 +494,50 @@ def run_fwd_kvcache(params, stream=None, options=None):
         check(lib().fa_run_mha_fwd_kvcache(ctypes.byref(params), s))
     else:
         check(lib().fa_run_mha_fwd_kvcache_ex(ctypes.byref(params), ctypes.byref(options), s))
+
+
+def mla_params(q, kv_cache, o, lse, cache_seqlens=None, kv_new=None, causal=False, num_splits=0, block_table=None, softmax_scale=None):
+    """fa_mla_params for q (b, sq, h, 576), kv_cache (b, capacity, 1, 576) - or, with block_table (int32 (b, max_blocks)), a page pool (num_blocks,
+    page_block_size, 1, 576) - kv_new (b, s_new, 1, 576) and o (b, sq, h, 512) torch tensors with arbitrary batch / row / head strides"""
+    b, sq, h, d_qk = q.shape
+    p = MlaParams()
+    p.q, p.kv_cache, p.o, p.lse = (t.data_ptr() for t in (q, kv_cache, o, lse))
+    p.cache_seqlens = None if cache_seqlens is None else cache_seqlens.data_ptr()
+    p.b, p.seqlen_q, p.seqlen_cache, p.h, p.d_qk, p.d_v = b, sq, kv_cache.shape[1], h, d_qk, o.shape[-1]
+    if block_table is not None:
+        p.block_table, p.block_table_stride = block_table.data_ptr(), block_table.stride(0)
+        p.page_block_size, p.num_blocks = kv_cache.shape[1], kv_cache.shape[0]
+        p.seqlen_cache = block_table.shape[1] * kv_cache.shape[1]
+    p.dtype, p.is_causal, p.num_splits = dtype_code(q.dtype), int(causal), int(num_splits)
+    p.softmax_scale = 0.0 if softmax_scale is None else float(softmax_scale)
+    tensors = [("q_stride", q), ("kv_cache_stride", kv_cache), ("o_stride", o)]
+    if kv_new is not None:
+        p.kv_new, p.seqlen_new = kv_new.data_ptr(), kv_new.shape[1]
+        tensors.append(("kv_new_stride", kv_new))
+    for name, t in tensors:
+        setattr(p, name, Strides(t.stride(0), t.stride(1), t.stride(2)))
+    return p
+
+
+def mla_workspace_bytes(params) -> int:
+    """fa_mla_workspace_bytes: fp32 scratch the split the library would choose (or num_splits) needs (0: one split)"""
+    n = lib().fa_mla_workspace_bytes(ctypes.byref(params))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def mla_num_splits(params) -> int:
+    """fa_mla_num_splits: key splits the launch of these params would use (their workspace fields included)"""
+    n = lib().fa_mla_num_splits(ctypes.byref(params))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def run_mla_fwd_kvcache(params, stream=None):
+    """fa_run_mla_fwd_kvcache"""
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    check(lib().fa_run_mla_fwd_kvcache(ctypes.byref(params), s))

@@ -546,3 +546,85 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
                               k_descale=k_descale, v_descale=v_descale, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=int(max_seqlen_q),
                               cu_seqlens_k_new=cu_seqlens_k_new, **extra)
     return (out, lse) if return_softmax_lse else out
+
+
+def flash_mla_with_kvcache(q, kv_cache, cache_seqlens, *, head_dim_v=512, kv_new=None, block_table=None, softmax_scale=None, causal=False, num_splits=0,
+                           return_softmax_lse=False):
+    """Multi-head latent attention (MLA) decode over a latent KV cache (DeepSeek-V2 / V3 / R1, Kimi K2; forward only).
+
+    After weight absorption an MLA decode step is MQA over one "KV head": each key is the 576-element latent row (512 compressed-KV elements,
+    then 64 rope elements) and each value is the first 512 elements of the SAME row.  The absorption matmuls and RoPE are the caller's.
+
+    q: (batch, seqlen_q, nheads, 576) fp16 / bf16; columns 0 .. 511 the absorbed no-rope part, 512 .. 575 the rope part (RoPE applied).  nheads and
+    seqlen_q are any value >= 1 (1 for decode, 2 - 4 for MTP verification).
+    kv_cache: (batch, capacity, 1, 576) in q's dtype, any batch / row strides, used in place; or, with block_table (int32 (batch, max_blocks) on q's
+    device, last dim contiguous), a page pool (num_blocks, page_block_size, 1, 576), page_block_size a multiple of 16, entries clamped
+    min(uint32(entry), num_blocks - 1) as in flash_attn_with_kvcache.
+    cache_seqlens: int32 tensor (batch,) on q's device, or a Python int (broadcast).
+    kv_new (keyword, optional): (batch, s_new, 1, 576), written INTO the cache at rows cache_seqlens[i] .. cache_seqlens[i] + s_new - 1 before
+    attention runs; cache_seqlens is not updated (the caller advances it); rows at or past the capacity are dropped.
+    In fp32 math over the visible keys, with L_i = cache_seqlens[i] (+ s_new): ``s_tj = (q_t . kv_j[0:576]) * softmax_scale``; key j is visible
+    iff j < L_i and, under ``causal``, j <= L_i - seqlen_q + t; ``out_t = softmax_j(s_tj) @ kv_j[0:512]``.  A row that sees no key is O = 0,
+    LSE = 0.  softmax_scale: None = 576 ** -0.5 rounded once to fp32 (None and that value passed explicitly give the same bits); models pass their
+    own, e.g. ``192 ** -0.5 * mscale``; validated like softmax_scale of flash_attn_with_kvcache.  head_dim_v must be 512.
+    Returns out (batch, seqlen_q, nheads, 512) in q's dtype and, with ``return_softmax_lse``, lse (batch, nheads, seqlen_q) fp32 (natural log).
+
+    What carries over from flash_attn_with_kvcache: no host synchronisation (lengths and tables are read on the device: the call can be captured in
+    a graph and replays with the values then in memory); a NaN in a query row, or a NaN / +inf score, makes that row's O and LSE NaN; cache rows
+    at or past L_i, pages wholly past L_i and pages no sequence references never reach a result; paged and contiguous calls over the same
+    logical cache give the same bits; run-to-run determinism per split count; num_splits (0 = chosen by the library over this call's grid of
+    batch x ceil(seqlen_q * nheads / 64) workgroups).  As there, the query rows of a call share the reads of a key, and the value is the key: a
+    non-finite element in columns 0 .. 511 of a row below L_i that ``causal`` hides from this query row but not from another row of the same
+    64-row tile can make this row NaN (0 x NaN).
+    Out of scope, and without a keyword here: an FP8 latent cache, cu_seqlens_q, window_size, softcap, sinks, tree_mask, rotary inside the call, other
+    head dims, any backward.  Wrong shapes, dtypes or values are a ValueError that names the argument.
+    """
+    for name, t in (("q", q), ("kv_cache", kv_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{name} must be a rank-4 tensor")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, kv_cache, kv_new if isinstance(kv_new, torch.Tensor) else None)):
+        raise RuntimeError("flash_mla_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"q must be fp16 or bf16, got {q.dtype}")
+    if q.shape[-1] != 576:
+        raise ValueError(f"q must be 576 wide (512 absorbed no-rope columns, then 64 rope columns), got head_dim {q.shape[-1]}")
+    if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int) or head_dim_v != 512:
+        raise ValueError(f"head_dim_v must be 512, got {head_dim_v!r}")
+    if q.shape[1] < 1 or q.shape[2] < 1:
+        raise ValueError(f"q needs seqlen_q >= 1 and nheads >= 1, got shape {tuple(q.shape)}")
+    if kv_cache.dtype != q.dtype:
+        raise ValueError(f"kv_cache must have q's dtype ({q.dtype}), got {kv_cache.dtype} (an FP8 latent cache is out of scope)")
+    if kv_cache.shape[2] != 1:
+        raise ValueError(f"kv_cache must have exactly one head (the latent row), got {kv_cache.shape[2]}")
+    if kv_cache.shape[3] != 576:
+        raise ValueError(f"kv_cache must be 576 wide, got {kv_cache.shape[3]}")
+    if kv_cache.device != q.device:
+        raise ValueError("kv_cache must be on q's device")
+    b = q.shape[0]
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
+            raise ValueError("block_table must be an int32 tensor")
+        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.device != q.device:
+            raise ValueError("block_table must have shape (batch, max_blocks_per_seq) on q's device")
+        if kv_cache.shape[1] < 1 or kv_cache.shape[1] % 16 != 0:
+            raise ValueError(f"page_block_size (kv_cache.shape[1] with block_table) must be a positive multiple of 16, got {kv_cache.shape[1]}")
+    elif kv_cache.shape[0] != b:
+        raise ValueError(f"kv_cache batch ({kv_cache.shape[0]}) must match q's ({b})")
+    if kv_new is not None:
+        if not isinstance(kv_new, torch.Tensor) or kv_new.dim() != 4 or kv_new.dtype != q.dtype or kv_new.device != q.device:
+            raise ValueError("kv_new must be a rank-4 tensor of q's dtype on q's device")
+        if kv_new.shape[0] != b or kv_new.shape[2] != 1 or kv_new.shape[3] != 576:
+            raise ValueError(f"kv_new must have shape (batch, s_new, 1, 576), got {tuple(kv_new.shape)}")
+    if isinstance(cache_seqlens, bool) or not isinstance(cache_seqlens, (int, torch.Tensor)):
+        raise ValueError("cache_seqlens must be an int32 tensor (batch,) on q's device or an int")
+    if isinstance(cache_seqlens, torch.Tensor) and (cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (b,) or cache_seqlens.device != q.device):
+        raise ValueError("cache_seqlens must be an int32 tensor (batch,) on q's device or an int")
+    softmax_scale, _ = _check_scale_and_cap(softmax_scale, 0.0)
+    if not isinstance(causal, bool):
+        raise ValueError(f"causal must be a bool, got {causal!r}")
+    if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
+        raise ValueError(f"num_splits must be an int >= 0 (0 = chosen by the library), got {num_splits!r}")
+    if isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
+    out, lse = _C.fwd_mla_kvcache(q, kv_cache, kv_new, cache_seqlens, causal, num_splits, block_table, softmax_scale, head_dim_v)
+    return (out, lse) if return_softmax_lse else out

@@ -625,6 +625,59 @@ typedef struct fa_kvcache_options_v8 {      /* FA_PARAMS_INIT(o); then fa_..._ex
     int64_t reserved4[5];       /* 0 */
 } fa_kvcache_options_v8;
 
+/* Multi-head latent attention (MLA) decode over a latent KV cache (FA_HAS_MLA_KVCACHE; DeepSeek-V2 / V3 / R1, Kimi K2; the FlashMLA call).  After
+ * weight absorption a decode step is MQA over ONE KV head whose key is the d_qk = 576 wide latent row (512 compressed-KV elements, then 64 rope
+ * elements, RoPE already applied) and whose value is the first d_v = 512 elements of the SAME row.  FA_ABI_VERSION is unchanged; the presence of
+ * fa_run_mla_fwd_kvcache is how a caller detects the feature.  The struct is versioned by its size (FA_PARAMS_INIT): every field below is
+ * mandatory in this version, fields appended later will be optional.
+ *   q (b, seqlen_q, h, 576), seqlen_q >= 1, h >= 1; kv_cache (b, seqlen_cache, 576) with batch and row strides (its head stride is not read), or with
+ *   block_table a pool (num_blocks, page_block_size, 576) exactly as in fa_kvcache_params: page_block_size a positive multiple of 16, seqlen_cache the
+ *   per-sequence capacity and a multiple of it, entries clamped min((uint32_t)entry, num_blocks - 1);
+ *   cache_seqlens: int32 DEVICE array (b,), or NULL = every sequence is seqlen_cache long;
+ *   kv_new (b, seqlen_new, 576) or NULL: written IN PLACE at rows cache_seqlens[i] .. + seqlen_new - 1 (cache_seqlens is required then and is not
+ *   updated; rows at or past seqlen_cache are dropped), after which L_i = cache_seqlens[i] + seqlen_new; without it L_i = cache_seqlens[i];
+ *   o (b, seqlen_q, h, 512), lse (b, h, seqlen_q) fp32 natural log.
+ * In fp32 math over the visible keys: s_tj = (q_t . kv_j[0:576]) * softmax_scale; key j is visible iff j < L_i and, under is_causal,
+ * j <= L_i - seqlen_q + t; o_t = softmax_j(s_tj) @ kv_j[0:512]; a row that sees no key is o = 0, lse = 0; a NaN query row, or a NaN / +inf
+ * score, gives a NaN row.  softmax_scale: finite and > 0, or 0 = the default 576 ** -0.5 (models pass their own, e.g. 192 ** -0.5 * mscale).
+ * workspace / num_splits as in fa_kvcache_params: fa_mla_workspace_bytes states n_split x rows x 512 x 4 + align16(n_split x rows x 4) bytes
+ * with rows = b * h * seqlen_q; the automatic split is the rule of fa_kvcache_num_splits over this grid's b x ceil(seqlen_q * h / 64) workgroups.
+ * No host synchronisation; paged == contiguous over the same logical cache bit for bit; deterministic per split count; rows at or past L_i,
+ * pages wholly past L_i and pages no sequence references never reach a result.
+ * Errors, the argument named by fa_last_error: d_qk != 576 or d_v != 512 FA_ERR_BAD_HEADDIM, dtype FA_ERR_BAD_DTYPE, sizes / page_block_size /
+ * softmax_scale / num_splits FA_ERR_BAD_SHAPE, pointers FA_ERR_NULL_POINTER, strides and alignment FA_ERR_BAD_STRIDE, the header FA_ERR_BAD_ABI.
+ * b == 0 is FA_OK without a launch.  No FP8 latent cache, window, softcap, sinks, tree mask, rotary or ragged batch: the struct has no field for them. */
+#define FA_HAS_MLA_KVCACHE 1
+typedef struct fa_mla_params {
+    uint32_t struct_size;       /* sizeof(fa_mla_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const void* q;
+    void* kv_cache;
+    const void* kv_new;         /* NULL: no append */
+    void* o;
+    float* lse;
+    const int32_t* cache_seqlens;
+    int32_t b;
+    int32_t seqlen_q;
+    int32_t seqlen_cache;
+    int32_t seqlen_new;         /* rows of kv_new (0 without it) */
+    int32_t h;
+    int32_t d_qk;               /* 576 */
+    int32_t d_v;                /* 512 */
+    int32_t dtype;
+    int32_t is_causal;
+    int32_t num_splits;         /* 0 = the library's choice */
+    float softmax_scale;        /* 0 = 576 ** -0.5 */
+    int32_t reserved_;          /* 0 */
+    fa_strides q_stride, kv_cache_stride, kv_new_stride, o_stride;     /* kv_cache_stride.head / kv_new_stride.head are not read */
+    void* workspace;
+    int64_t workspace_bytes;
+    const int32_t* block_table; /* paged cache; NULL = contiguous */
+    int64_t block_table_stride;
+    int32_t page_block_size;
+    int32_t num_blocks;
+} fa_mla_params;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -694,6 +747,14 @@ int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* params, const fa_kvcac
 /* Packed query rows per workgroup of the attention launch these params and options would make: 16, or 64 with fa_kvcache_options_v8.row_tile =
  * 64 (FA_HAS_KVCACHE_PREFILL).  The `workspace` fields are ignored.  Host-only.  Negative = error code, exactly those of the launch. */
 int32_t fa_kvcache_row_tile_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);
+
+/* ---- MLA decode over a latent KV cache (fa_mla_params above) ----------------------------------- */
+/* Append (if kv_new), split-KV attention, and the combine of the splits: up to three launches on `stream`, no host synchronisation. */
+int fa_run_mla_fwd_kvcache(const fa_mla_params* params, void* stream);
+/* Host-only, like fa_kvcache_workspace_bytes / fa_kvcache_num_splits: the bytes the split the library chooses (or num_splits) needs, the
+ * `workspace` fields ignored; and the splits the launch would use, the workspace fields included (NULL / 0 -> 1).  Negative = error code. */
+int64_t fa_mla_workspace_bytes(const fa_mla_params* params);
+int32_t fa_mla_num_splits(const fa_mla_params* params);
 
 /* ---- measurement helpers ----------------------------------------------------------------- */
 /* Algorithmic FLOPs of one forward call (4*b*h*sq*sk*d, causal counts only visible pairs);

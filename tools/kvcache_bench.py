@@ -67,6 +67,12 @@ d-256 call; (B, B2) the d-128 call on the same b and L with twice the KV heads a
 same buffers, viewed as (b, L, 2 h_k, 128)), the same FLOPs, the same row-tile count - timed TWICE so that the scatter of one thing measured
 twice in the same run stands next to A / B; interleaved, medians.  `hbm_bound` marks the points whose K/V are at least 1 GB.
 
+--mla measures MLA decode over a latent KV cache (flash_mla_with_kvcache): h in {16, 128}, seqlen_q 1, b in {1, 8, 64}, L in {4k, 32k, 128k} (--length
+replaces them), bf16, contiguous and, with --paged P, through a block table of P-row pages.  Per point, (A) the MLA call - time and
+b * L * 1152 B / time as a fraction of 6.3 TB/s; (B, B2) the yardstick, the head_dim-256 flash_attn_with_kvcache call with h_k = 1 and the same h, b and L
+(1024 B per key: nearly the same bytes, fewer FLOPs), timed TWICE so that the scatter of one thing measured twice in the same run stands next to
+A / B; interleaved, medians.
+
 --baseline-library PATH records an interleaved A/B of the plain (no window) call through the C ABI of this build and of the library at
 PATH (e.g. a build of the parent commit), on the same data; the outputs must agree bit for bit.  --length L (repeatable) replaces the
 grid's cache lengths."""
@@ -806,6 +812,51 @@ def run_prefill(lengths, head_dims, fp8, pages, rounds):
             yield run_prefill_point(sq, L, 32, 8, d, torch.float16, fp8, page, rounds)
 
 
+def run_mla_point(b, h, L, page, rounds):
+    """(A) flash_mla_with_kvcache over a bf16 latent cache, (B, B2) the d-256 decode call with one KV head on the same h, b, L, twice; interleaved"""
+    dev, dt = torch.device("cuda:0"), torch.bfloat16
+    mla_bytes, ref_bytes = b * L * 576 * 2, 2 * b * L * 256 * 2
+    n = _rotation(mla_bytes + ref_bytes, ref_bytes)
+    sets = []
+    for i in range(n):
+        if page:
+            nb = b * L // page
+            table = torch.randperm(nb, generator=torch.Generator().manual_seed(i)).view(b, L // page).to(device=dev, dtype=torch.int32)
+            shape = lambda d: (nb, page, 1, d)
+        else:
+            table, shape = None, lambda d: (b, L, 1, d)
+        sets.append((torch.empty(shape(576), device=dev, dtype=dt).uniform_(-2, 2), torch.empty(shape(256), device=dev, dtype=dt).uniform_(-2, 2),
+                     torch.empty(shape(256), device=dev, dtype=dt).uniform_(-2, 2), table))
+    q = torch.randn(b, 1, h, 576, device=dev, dtype=dt)
+    q256 = torch.randn(b, 1, h, 256, device=dev, dtype=dt)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    mla = lambda i: F.flash_mla_with_kvcache(q, sets[i][0], cs, block_table=sets[i][3])
+    ref = lambda i: F.flash_attn_with_kvcache(q256, sets[i][1], sets[i][2], cache_seqlens=cs, block_table=sets[i][3])
+    mla(0), ref(0)
+    torch.cuda.synchronize()
+    ms = _interleaved({"d256": ref, "mla": mla, "d256_again": ref}, n, rounds)
+    p = capi.mla_params(q, sets[0][0], torch.empty(b, 1, h, 512, device=dev, dtype=dt), torch.empty(b, h, 1, device=dev), cs, block_table=sets[0][3])
+    ws = capi.mla_workspace_bytes(p)
+    n_split = max(1, ws and capi.mla_num_splits(_with_ws(p, ws)))
+    p2 = capi.kvcache_params(q256, sets[0][1], sets[0][2], torch.empty_like(q256), torch.empty(b, h, 1, device=dev), cache_seqlens=cs, block_table=sets[0][3])
+    ws2 = capi.kvcache_workspace_bytes(p2)
+    n_split2 = max(1, ws2 and capi.kvcache_num_splits(_with_ws(p2, ws2)))
+    del sets
+    torch.cuda.empty_cache()
+    lo, hi = sorted((ms["d256"], ms["d256_again"]))
+    return dict(mla=True, b=b, h=h, L=L, seqlen_q=1, dtype="bfloat16", page_block_size=page or 0, caches_rotated=n, kv_gb=round(mla_bytes / 1e9, 3),
+                n_split_mla=n_split, n_split_d256=n_split2, ms_mla=round(ms["mla"], 5), ms_d256=round(ms["d256"], 5), ms_d256_again=round(ms["d256_again"], 5),
+                tbps_mla=round(mla_bytes / (ms["mla"] * 1e-3) / 1e12, 3), frac_of_6p3_mla=round(mla_bytes / (ms["mla"] * 1e-3) / HBM_ACHIEVABLE, 3),
+                frac_of_6p3_d256=round(ref_bytes / (ms["d256"] * 1e-3) / HBM_ACHIEVABLE, 3), mla_over_d256=round(ms["mla"] / ms["d256"], 4),
+                d256_again_over_d256=round(ms["d256_again"] / ms["d256"], 4), inside_scatter=bool(lo <= ms["mla"] <= hi))
+
+
+def run_mla(lengths, pages, rounds):
+    for h, b, L in itertools.product((16, 128), (1, 8, 64), tuple(lengths or (4096, 32768, 131072))):
+        for page in ([None] + list(pages or [])):
+            yield run_mla_point(b, h, L, page, rounds)
+
+
 def _baseline_lib(path):
     L = ctypes.CDLL(os.path.abspath(path))
     L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
@@ -890,6 +941,8 @@ def main():
                                                            "contiguous points, fwd; with --kv-dtype fp8 / --paged P over those caches")
     ap.add_argument("--head-dim", type=int, action="append", metavar="D", choices=(64, 128, 256), help="head dim(s) instead of the grid's 64 and 128 (256: the decode call only)")
     ap.add_argument("--equal-bytes", action="store_true", help="with --head-dim 256: the d-256 call against the d-128 call with twice the heads on the same buffers (timed twice)")
+    ap.add_argument("--mla", action="store_true", help="MLA decode over a latent KV cache (flash_mla_with_kvcache) against the head_dim-256 decode call with one KV head "
+                                                       "(timed twice); contiguous and, with --paged P, through a block table")
     a = ap.parse_args()
     base = _baseline_lib(a.baseline_library) if a.baseline_library else None
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
@@ -899,6 +952,10 @@ def main():
     with torch.no_grad():
         if a.ragged and base is None:
             for line in run_ragged(a.quick, a.rounds):
+                print(json.dumps(line), flush=True)
+            return
+        if a.mla:
+            for line in run_mla(a.length, a.paged, a.rounds):
                 print(json.dumps(line), flush=True)
             return
         if a.prefill:
