@@ -838,4 +838,111 @@ int fa_run_mla_fwd_kvcache(const fa_mla_params* user, void* stream) {
     return hip_status(fa::launch_fwd_kvcache_mla(mp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache_mla launch");
 }
 
+// ---- sparse MLA decode over a latent KV cache ------------------------------------------------------------------------------------------------
+// fa_mla_sparse_params -> KvcacheMlaSparseParams, validated: the checks and words of fill_mla without kv_new / is_causal, plus indices and topk.  split: what
+// kvcache_split / kvcache_workspace_bytes are asked with - the grid is b x seqlen_q x ceil(h / 64) workgroups a split and the split runs over the slots
+// [0, topk), so the copy states b x seqlen_q "sequences" of one token and topk in the place of seqlen_cache (rows = b * h * seqlen_q either way).
+static int fill_mla_sparse(const fa_mla_sparse_params* user, fa::KvcacheMlaSparseParams& sp, fa::KvcacheKernelParams& split, fa_mla_sparse_params& local, bool with_workspace) {
+    int rc = import_params(user, local, "fa_mla_sparse_params", sizeof(fa_mla_sparse_params));
+    if (rc) return rc;
+    const fa_mla_sparse_params* p = &local;
+    const bool paged = p->block_table != nullptr;
+    if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0 || p->h <= 0)
+        return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d h=%d", p->b, p->seqlen_q, p->seqlen_cache, p->h);
+    if (p->d_qk != 576) return fail(FA_ERR_BAD_HEADDIM, "d_qk %d unsupported (the latent row is 576 wide: 512 compressed + 64 rope elements)", p->d_qk);
+    if (p->d_v != 512) return fail(FA_ERR_BAD_HEADDIM, "d_v %d unsupported (the value is the first 512 elements of the latent row)", p->d_v);
+    if (p->dtype != FA_FP16 && p->dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", p->dtype);
+    if (p->topk < fa::kKvcStep || p->topk % fa::kKvcStep != 0)
+        return fail(FA_ERR_BAD_SHAPE, "topk %d must be a positive multiple of %d (pad the lists with -1)", p->topk, fa::kKvcStep);
+    if (paged) {
+        const int P = p->page_block_size;
+        if (P == 0) return fail(FA_ERR_BAD_SHAPE, "block_table given without page_block_size");
+        if (P < 0 || P % 16 != 0) return fail(FA_ERR_BAD_SHAPE, "page_block_size %d must be a positive multiple of 16", P);
+        if (p->num_blocks < 1) return fail(FA_ERR_BAD_SHAPE, "num_blocks %d: a paged cache needs at least one page", p->num_blocks);
+        if (p->seqlen_cache <= 0 || p->seqlen_cache % P != 0)
+            return fail(FA_ERR_BAD_SHAPE, "seqlen_cache (%d) must be a positive multiple of page_block_size (%d) with block_table", p->seqlen_cache, P);
+        if (p->block_table_stride < p->seqlen_cache / P)
+            return fail(FA_ERR_BAD_STRIDE, "block_table_stride %lld is below the table's %d columns (seqlen_cache / page_block_size)",
+                        (long long)p->block_table_stride, p->seqlen_cache / P);
+        if ((reinterpret_cast<uintptr_t>(p->block_table) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "block_table must be 4-byte aligned");
+    } else if (p->page_block_size != 0) {
+        return fail(FA_ERR_NULL_POINTER, "page_block_size = %d given without block_table", p->page_block_size);
+    }
+    if (p->num_splits < 0) return fail(FA_ERR_BAD_SHAPE, "num_splits must be >= 0 (0 = the library's choice), got %d", p->num_splits);
+    if (!(p->softmax_scale >= 0.f) || isinf(p->softmax_scale))
+        return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default 576 ** -0.5)", (double)p->softmax_scale);
+    if (p->reserved_ != 0) return fail(FA_ERR_BAD_ABI, "fa_mla_sparse_params: reserved_ is not zero (a field of a newer header that this library does not know)");
+    if (with_workspace && p->workspace_bytes < 0) return fail(FA_ERR_BAD_SHAPE, "workspace_bytes must be >= 0");
+    if (with_workspace && p->workspace != nullptr && (reinterpret_cast<uintptr_t>(p->workspace) & 15u) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
+    // the attention grid is b x seqlen_q x 64-head tiles x n_split workgroups (n_split <= 128), and a row index is an int
+    const int64_t tiles = ((int64_t)p->h + fa::kKvcPrefillRows - 1) / fa::kKvcPrefillRows;
+    if ((int64_t)p->seqlen_q * p->h >= ((int64_t)1 << 31) || (int64_t)p->b * p->seqlen_q * tiles >= ((int64_t)1 << 24))
+        return fail(FA_ERR_BAD_SHAPE, "call too large: b = %d sequences x seqlen_q = %d rows x h = %d heads exceeds the launch grid", p->b, p->seqlen_q, p->h);
+    fa_strides kvc = p->kv_cache_stride;
+    kvc.head = 0;        // one KV head
+    if (p->b > 0) {
+        if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
+        if (p->indices == nullptr) return fail(FA_ERR_NULL_POINTER, "indices is NULL");
+        if ((reinterpret_cast<uintptr_t>(p->indices) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "indices must be 4-byte aligned");
+        if (p->indices_batch_stride < 0 || p->indices_row_stride < 0)
+            return fail(FA_ERR_BAD_STRIDE, "indices strides (indices_batch_stride=%lld, indices_row_stride=%lld) must be >= 0 elements", (long long)p->indices_batch_stride,
+                        (long long)p->indices_row_stride);
+        if ((rc = check_tensor("q", p->q, p->q_stride, p->seqlen_q, p->d_qk, false))) return rc;
+        if ((rc = check_tensor("o", p->o, p->o_stride, p->seqlen_q, p->d_v, false))) return rc;
+        // paged: the descriptors span one cache row, page offsets are 64-bit; contiguous: one descriptor per sequence, below 2^31 bytes
+        if ((rc = check_tensor("kv_cache", p->kv_cache, kvc, paged ? p->page_block_size : p->seqlen_cache, p->d_qk, false))) return rc;
+    }
+    memset(&sp, 0, sizeof(sp));
+    fa::KvcacheKernelParams& kp = sp.kp;
+    sp.d_qk = p->d_qk; sp.topk = p->topk;
+    sp.indices = p->indices; sp.idx_batch = p->indices_batch_stride; sp.idx_row = p->indices_row_stride;
+    kp.q_ptr = p->q; kp.k_cache = const_cast<void*>(p->kv_cache); kp.v_cache = kp.k_cache;
+    kp.o_ptr = p->o; kp.lse_ptr = p->lse; kp.cache_seqlens = p->cache_seqlens;
+    kp.q = conv(p->q_stride); kp.kc = kp.vc = conv(kvc); kp.o = conv(p->o_stride);
+    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_cache = p->seqlen_cache;
+    kp.h = p->h; kp.h_k = 1; kp.h_ratio = p->h; kp.d = p->d_v;
+    kp.scale = p->softmax_scale > 0.f ? p->softmax_scale : 1.0f / sqrtf((float)p->d_qk);
+    kp.scale_log2e = kp.scale * 1.4426950408889634f;
+    if (paged) {
+        kp.block_table = p->block_table; kp.bt_stride = p->block_table_stride;
+        kp.page_size = p->page_block_size; kp.num_blocks = p->num_blocks;
+    }
+    split = kp;
+    split.b = p->b * p->seqlen_q; split.seqlen_q = 1; split.seqlen_cache = p->topk;
+    return FA_OK;
+}
+
+int64_t fa_mla_sparse_workspace_bytes(const fa_mla_sparse_params* user) {
+    fa::KvcacheMlaSparseParams sp;
+    fa::KvcacheKernelParams split;
+    fa_mla_sparse_params local;
+    int rc = fill_mla_sparse(user, sp, split, local, false);
+    if (rc) return rc;
+    if (sp.kp.b == 0) return 0;
+    return fa::kvcache_workspace_bytes(split, fa::kvcache_split(split, -1, local.num_splits, -1, fa::kKvcPrefillRows));
+}
+
+int32_t fa_mla_sparse_num_splits(const fa_mla_sparse_params* user) {
+    fa::KvcacheMlaSparseParams sp;
+    fa::KvcacheKernelParams split;
+    fa_mla_sparse_params local;
+    int rc = fill_mla_sparse(user, sp, split, local, true);
+    if (rc) return rc;
+    if (sp.kp.b == 0) return 1;
+    return fa::kvcache_split(split, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits, -1, fa::kKvcPrefillRows);
+}
+
+int fa_run_mla_sparse_fwd_kvcache(const fa_mla_sparse_params* user, void* stream) {
+    fa::KvcacheMlaSparseParams sp;
+    fa::KvcacheKernelParams split;
+    fa_mla_sparse_params local;
+    int rc = fill_mla_sparse(user, sp, split, local, true);
+    if (rc) return rc;
+    if (sp.kp.b == 0) return FA_OK;
+    sp.kp.n_split = fa::kvcache_split(split, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits, -1, fa::kKvcPrefillRows);
+    sp.kp.ws_o = sp.kp.n_split > 1 ? (float*)local.workspace : nullptr;
+    return hip_status(fa::launch_fwd_kvcache_mla_sparse(sp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache_mla_sparse launch");
+}
+
 }  // extern "C"

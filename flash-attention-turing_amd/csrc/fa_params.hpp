@@ -282,6 +282,19 @@ struct KvcacheMlaParams {
 };
 hipError_t launch_fwd_kvcache_mla(KvcacheMlaParams mp, int dtype, hipStream_t stream);
 
+// Sparse MLA decode (fa_fwd_kvcache_mla_sparse.hip, fa_run_mla_sparse_fwd_kvcache): the same latent cache, but query token t of sequence i attends to the
+// rows its list names: indices[i * idx_batch + t * idx_row + s], s < topk (a positive multiple of kKvcStep), a logical key position that is valid iff
+// 0 <= . < L_i.  kp as in KvcacheMlaParams without k_new / seqlen_new / is_causal; the split runs over the slots [0, topk) and the grid is
+// b x seqlen_q x ceil(h / kKvcPrefillRows) x n_split, which the launcher states to kvcache_split / finish_params as seqlen_q = 1, seqlen_cache = topk.
+struct KvcacheMlaSparseParams {
+    KvcacheKernelParams kp;
+    int32_t d_qk;               // 576
+    int32_t topk;
+    const int32_t* indices;
+    int64_t idx_batch, idx_row; // in elements
+};
+hipError_t launch_fwd_kvcache_mla_sparse(KvcacheMlaSparseParams sp, int dtype, hipStream_t stream);
+
 // Rotary embedding on a decode call (fa_kvcache_rotary.hip, fa_kvcache_options_v3).  One fused launch takes the place of the append: it
 // rotates k_new into the cache, copies / quantises v_new, and writes the rotated q into `q_image`, a contiguous (b, seqlen_q, h, d) buffer of
 // q's dtype at the head of the caller's workspace; the attention kernels then read that image as their q.  A block of its own and not

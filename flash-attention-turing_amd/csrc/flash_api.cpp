@@ -558,6 +558,82 @@ std::vector<at::Tensor> mha_fwd_mla_kvcache(at::Tensor q, at::Tensor kv_cache, c
     return {o, l};
 }
 
+// Sparse MLA decode over a latent KV cache (fa_run_mla_sparse_fwd_kvcache): q, kv_cache, block_table, cache_seqlens as in mha_fwd_mla_kvcache; indices
+// int32 (b, sq, topk), last dim contiguous, any batch / row strides: the logical key positions of each query token.  out (b, sq, h, 512) and lse (b, h, sq).
+// Indices, lengths and tables are read on the device.
+std::vector<at::Tensor> mha_fwd_mla_sparse_kvcache(at::Tensor q, at::Tensor kv_cache, at::Tensor indices, c10::optional<at::Tensor> cache_seqlens_, int64_t num_splits,
+                                                   c10::optional<at::Tensor> block_table_, c10::optional<double> softmax_scale, int64_t head_dim_v) {
+    TORCH_CHECK(q.dim() == 4 && kv_cache.dim() == 4, "q and kv_cache must be rank-4 tensors");
+    TORCH_CHECK(q.is_cuda() && kv_cache.is_cuda(), "q, kv_cache must be GPU (HIP) tensors");
+    TORCH_CHECK(kv_cache.device() == q.device(), "q, kv_cache must be on the same device");
+    TORCH_CHECK(kv_cache.scalar_type() == q.scalar_type(), "kv_cache must have the dtype of q, got ", kv_cache.scalar_type());
+    const int64_t batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), head_size = q.size(3);
+    TORCH_CHECK(seqlen_q >= 1 && num_heads >= 1, "seqlen_q and the number of heads must be >= 1");
+    TORCH_CHECK(kv_cache.size(2) == 1, "kv_cache must have exactly one head (the latent row)");
+    TORCH_CHECK(kv_cache.size(3) == head_size, "q / kv_cache head_dim must match");
+    TORCH_CHECK(kv_cache.stride(3) == 1, "kv_cache: last dimension must be contiguous");
+    TORCH_CHECK(num_splits >= 0 && num_splits <= INT32_MAX, "num_splits must be >= 0 (0 = automatic)");
+    TORCH_CHECK(head_dim_v >= 0 && head_dim_v <= INT32_MAX && head_size <= INT32_MAX, "head dims must fit in int32");
+    check_same_device(q, indices, "indices");
+    TORCH_CHECK(indices.scalar_type() == torch::kInt32, "indices must be an int32 tensor");
+    TORCH_CHECK(indices.dim() == 3 && indices.size(0) == batch_size && indices.size(1) == seqlen_q, "indices must have shape [batch_size, seqlen_q, topk]");
+    TORCH_CHECK(indices.size(2) >= 1 && indices.size(2) <= INT32_MAX && indices.stride(2) == 1, "indices: topk must be >= 1 and the last dimension contiguous");
+    int64_t seqlen_cache = kv_cache.size(1);
+    at::Tensor block_table;
+    if (block_table_.has_value()) {
+        block_table = *block_table_;
+        check_same_device(q, block_table, "block_table");
+        TORCH_CHECK(block_table.scalar_type() == torch::kInt32, "block_table must be an int32 tensor");
+        TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == batch_size, "block_table must have shape [batch_size, max_blocks_per_seq]");
+        TORCH_CHECK(block_table.stride(1) == 1 || block_table.size(1) <= 1, "block_table: last dimension must be contiguous");
+        seqlen_cache = block_table.size(1) * kv_cache.size(1);
+        TORCH_CHECK(kv_cache.size(0) <= INT32_MAX && seqlen_cache <= INT32_MAX, "block_table: pool pages and capacity must fit in int32");
+    } else {
+        TORCH_CHECK(kv_cache.size(0) == batch_size, "kv_cache batch size must match q");
+    }
+    at::Tensor cache_seqlens;
+    if (cache_seqlens_.has_value()) {
+        cache_seqlens = *cache_seqlens_;
+        check_same_device(q, cache_seqlens, "cache_seqlens");
+        TORCH_CHECK(cache_seqlens.scalar_type() == torch::kInt32, "cache_seqlens must be an int32 tensor");
+        TORCH_CHECK(cache_seqlens.dim() == 1 && cache_seqlens.size(0) == batch_size && cache_seqlens.is_contiguous(),
+                    "cache_seqlens must be a contiguous tensor of shape [batch_size]");
+    }
+    c10::DeviceGuard guard(q.device());
+    q = dense_last(q);
+    at::Tensor o = torch::empty({batch_size, seqlen_q, num_heads, head_dim_v}, q.options());
+    at::Tensor l = torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(torch::kFloat32));
+
+    fa_mla_sparse_params p;
+    FA_PARAMS_INIT(p);
+    p.q = q.data_ptr(); p.kv_cache = kv_cache.data_ptr(); p.o = o.data_ptr(); p.lse = l.data_ptr<float>();
+    p.cache_seqlens = cache_seqlens.defined() ? cache_seqlens.data_ptr<int32_t>() : nullptr;
+    p.indices = indices.data_ptr<int32_t>(); p.topk = (int32_t)indices.size(2);
+    p.indices_batch_stride = indices.stride(0); p.indices_row_stride = indices.stride(1);
+    p.b = (int32_t)batch_size; p.seqlen_q = (int32_t)seqlen_q; p.seqlen_cache = (int32_t)seqlen_cache;
+    p.h = (int32_t)num_heads; p.d_qk = (int32_t)head_size; p.d_v = (int32_t)head_dim_v;
+    p.dtype = fa_dtype_of(q); p.num_splits = (int32_t)num_splits;
+    // (rounded once to fp32; 0 means "the default" in the C ABI, so a given scale that is or rounds to 0 is refused here)
+    TORCH_CHECK(!softmax_scale.has_value() || (std::isfinite(*softmax_scale) && (float)*softmax_scale > 0.f && std::isfinite((float)*softmax_scale)),
+                "softmax_scale must be a finite fp32 value > 0 (or None = 576 ** -0.5)");
+    if (softmax_scale.has_value()) p.softmax_scale = (float)*softmax_scale;
+    p.q_stride = strides4(q); p.kv_cache_stride = strides4(kv_cache); p.o_stride = strides4(o);
+    if (block_table.defined()) {
+        p.block_table = block_table.data_ptr<int32_t>();
+        p.block_table_stride = batch_size > 1 ? block_table.stride(0) : std::max<int64_t>(block_table.stride(0), block_table.size(1));
+        p.page_block_size = (int32_t)kv_cache.size(1); p.num_blocks = (int32_t)kv_cache.size(0);
+    }
+    at::Tensor workspace;
+    const int64_t ws_bytes = fa_mla_sparse_workspace_bytes(&p);
+    if (ws_bytes < 0) check_status((int)ws_bytes);
+    if (ws_bytes > 0) {
+        workspace = torch::empty({ws_bytes / 4}, q.options().dtype(torch::kFloat32));
+        p.workspace = workspace.data_ptr(); p.workspace_bytes = ws_bytes;
+    }
+    check_status(fa_run_mla_sparse_fwd_kvcache(&p, current_stream(q)));
+    return {o, l};
+}
+
 // ---- autograd nodes in C++ ------------------------------------------------------------------------------------------------------
 // The reference ships the four raw functions only; its README's flash_attn_func is an older Python-level API.  The differentiable wrappers
 // of this package used to be torch.autograd.Function subclasses in Python: ~85 us of host time per forward + backward, more than the GPU
@@ -617,6 +693,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fwd_mla_kvcache", &mha_fwd_mla_kvcache, "MLA decode over a latent KV cache: q (b, sq, h, 576), kv_cache (b, capacity, 1, 576) -> [out (b, sq, h, 512), lse]",
           py::arg("q"), py::arg("kv_cache"), py::arg("kv_new") = py::none(), py::arg("cache_seqlens") = py::none(), py::arg("is_causal") = false,
           py::arg("num_splits") = 0, py::arg("block_table") = py::none(), py::arg("softmax_scale") = py::none(), py::arg("head_dim_v") = 512);
+    m.def("fwd_mla_sparse_kvcache", &mha_fwd_mla_sparse_kvcache,
+          "Sparse MLA decode over a latent KV cache: q (b, sq, h, 576), kv_cache (b, capacity, 1, 576), indices int32 (b, sq, topk) -> [out (b, sq, h, 512), lse]",
+          py::arg("q"), py::arg("kv_cache"), py::arg("indices"), py::arg("cache_seqlens") = py::none(), py::arg("num_splits") = 0,
+          py::arg("block_table") = py::none(), py::arg("softmax_scale") = py::none(), py::arg("head_dim_v") = 512);
     // three overloads: the signature as it was (every existing call, positional or keyword, resolves to it), the one that continues it with the
     // ragged-batch keywords after rotary_interleaved, and the one that continues that with softmax_scale / softcap
     m.def("fwd_kvcache",

@@ -133,6 +133,18 @@ class MlaParams(_Params):
                 ("block_table", _vp), ("block_table_stride", ctypes.c_int64), ("page_block_size", _i32), ("num_blocks", _i32)]
 
 
+class MlaSparseParams(_Params):
+    """fa_mla_sparse_params: sparse MLA decode over a latent KV cache (fa_run_mla_sparse_fwd_kvcache)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("q", _vp), ("kv_cache", _vp), ("o", _vp), ("lse", _vp),
+                ("cache_seqlens", _vp), ("indices", _vp),
+                ("b", _i32), ("seqlen_q", _i32), ("seqlen_cache", _i32), ("topk", _i32), ("h", _i32), ("d_qk", _i32), ("d_v", _i32),
+                ("dtype", _i32), ("num_splits", _i32), ("softmax_scale", ctypes.c_float), ("reserved_", ctypes.c_int64),
+                ("q_stride", Strides), ("kv_cache_stride", Strides), ("o_stride", Strides),
+                ("indices_batch_stride", ctypes.c_int64), ("indices_row_stride", ctypes.c_int64),
+                ("workspace", _vp), ("workspace_bytes", ctypes.c_int64),
+                ("block_table", _vp), ("block_table_stride", ctypes.c_int64), ("page_block_size", _i32), ("num_blocks", _i32)]
+
+
 FA_CACHE_FP8_E4M3 = 1
 
 
@@ -187,6 +199,12 @@ def lib():
         L.fa_mla_workspace_bytes.restype = ctypes.c_int64
         L.fa_mla_num_splits.argtypes = [ctypes.POINTER(MlaParams)]
         L.fa_mla_num_splits.restype = ctypes.c_int32
+        L.fa_run_mla_sparse_fwd_kvcache.argtypes = [ctypes.POINTER(MlaSparseParams), _vp]
+        L.fa_run_mla_sparse_fwd_kvcache.restype = ctypes.c_int
+        L.fa_mla_sparse_workspace_bytes.argtypes = [ctypes.POINTER(MlaSparseParams)]
+        L.fa_mla_sparse_workspace_bytes.restype = ctypes.c_int64
+        L.fa_mla_sparse_num_splits.argtypes = [ctypes.POINTER(MlaSparseParams)]
+        L.fa_mla_sparse_num_splits.restype = ctypes.c_int32
         L.fa_mha_fwd.argtypes = [_vp] * 5 + [_i32] * 8 + [_vp]
         L.fa_mha_bwd.argtypes = [_vp] * 10 + [_i32] * 8 + [_vp]
         L.fa_mha_varlen_fwd.argtypes = [_vp] * 7 + [_i32] * 8 + [_vp]
@@ -541,3 +559,47 @@ def run_mla_fwd_kvcache(params, stream=None):
 
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     check(lib().fa_run_mla_fwd_kvcache(ctypes.byref(params), s))
+
+
+def mla_sparse_params(q, kv_cache, o, lse, indices, cache_seqlens=None, num_splits=0, block_table=None, softmax_scale=None):
+    """fa_mla_sparse_params for q (b, sq, h, 576), kv_cache (b, capacity, 1, 576) - or, with block_table (int32 (b, max_blocks)), a page pool (num_blocks,
+    page_block_size, 1, 576) - indices int32 (b, sq, topk) with any batch / row strides, and o (b, sq, h, 512) torch tensors"""
+    b, sq, h, d_qk = q.shape
+    p = MlaSparseParams()
+    p.q, p.kv_cache, p.o, p.lse, p.indices = (t.data_ptr() for t in (q, kv_cache, o, lse, indices))
+    p.cache_seqlens = None if cache_seqlens is None else cache_seqlens.data_ptr()
+    p.b, p.seqlen_q, p.seqlen_cache, p.h, p.d_qk, p.d_v = b, sq, kv_cache.shape[1], h, d_qk, o.shape[-1]
+    p.topk, p.indices_batch_stride, p.indices_row_stride = indices.shape[-1], indices.stride(0), indices.stride(1)
+    if block_table is not None:
+        p.block_table, p.block_table_stride = block_table.data_ptr(), block_table.stride(0)
+        p.page_block_size, p.num_blocks = kv_cache.shape[1], kv_cache.shape[0]
+        p.seqlen_cache = block_table.shape[1] * kv_cache.shape[1]
+    p.dtype, p.num_splits = dtype_code(q.dtype), int(num_splits)
+    p.softmax_scale = 0.0 if softmax_scale is None else float(softmax_scale)
+    for name, t in (("q_stride", q), ("kv_cache_stride", kv_cache), ("o_stride", o)):
+        setattr(p, name, Strides(t.stride(0), t.stride(1), t.stride(2)))
+    return p
+
+
+def mla_sparse_workspace_bytes(params) -> int:
+    """fa_mla_sparse_workspace_bytes: fp32 scratch the split the library would choose (or num_splits) needs (0: one split)"""
+    n = lib().fa_mla_sparse_workspace_bytes(ctypes.byref(params))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def mla_sparse_num_splits(params) -> int:
+    """fa_mla_sparse_num_splits: slot splits the launch of these params would use (their workspace fields included)"""
+    n = lib().fa_mla_sparse_num_splits(ctypes.byref(params))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def run_mla_sparse_fwd_kvcache(params, stream=None):
+    """fa_run_mla_sparse_fwd_kvcache"""
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    check(lib().fa_run_mla_sparse_fwd_kvcache(ctypes.byref(params), s))

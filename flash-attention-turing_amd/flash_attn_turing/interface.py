@@ -628,3 +628,86 @@ def flash_mla_with_kvcache(q, kv_cache, cache_seqlens, *, head_dim_v=512, kv_new
         cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
     out, lse = _C.fwd_mla_kvcache(q, kv_cache, kv_new, cache_seqlens, causal, num_splits, block_table, softmax_scale, head_dim_v)
     return (out, lse) if return_softmax_lse else out
+
+
+def flash_mla_sparse_with_kvcache(q, kv_cache, cache_seqlens, indices, *, head_dim_v=512, block_table=None, softmax_scale=None, num_splits=0,
+                                  return_softmax_lse=False):
+    """Sparse MLA decode over a latent KV cache: each query token attends to the cache rows its own list of key positions names (DeepSeek-V3.2
+    "DeepSeek Sparse Attention", the sparse call of FlashMLA; forward only).
+
+    q, kv_cache, cache_seqlens, block_table, softmax_scale, head_dim_v, num_splits and return_softmax_lse are those of flash_mla_with_kvcache, checks
+    included: q (batch, seqlen_q, nheads, 576) fp16 / bf16; kv_cache (batch, capacity, 1, 576) in q's dtype, or with block_table (int32 (batch,
+    max_blocks)) a page pool (num_blocks, page_block_size, 1, 576), page_block_size a multiple of 16, entries clamped min(uint32(entry),
+    num_blocks - 1); cache_seqlens an int32 tensor (batch,) or an int; softmax_scale None = 576 ** -0.5 rounded once to fp32; head_dim_v must be 512.
+    indices: int32 tensor (batch, seqlen_q, topk) on q's device, last dim contiguous, any batch and row strides; topk a positive multiple of 32 (pad
+    with -1).  indices[i, t, s] is a LOGICAL key position of sequence i (it goes through block_table when the cache is paged).  The list belongs to
+    query token t: all heads of the token share it.
+    In fp32 math, with L_i = min(max(cache_seqlens[i], 0), capacity): slot s of row (i, t) is valid iff 0 <= indices[i, t, s] < L_i; the valid slots
+    form a multiset (a position listed twice counts twice; nothing is de-duplicated); ``s_ts = (q_t . kv[idx][0:576]) * softmax_scale``;
+    ``out_t = softmax over the valid slots @ kv[idx][0:512]``; lse is the natural-log logsumexp over the valid slots.  A row with no valid slot is
+    O = 0, LSE = 0.  The order of a list does not matter beyond rounding.  There is no ``causal``: the list is the mask.
+    Returns out (batch, seqlen_q, nheads, 512) in q's dtype and, with ``return_softmax_lse``, lse (batch, nheads, seqlen_q) fp32.
+
+    Never read (they may hold NaN or garbage): cache rows that no valid slot names, pages no valid slot reaches and their table entries; an invalid
+    entry of any value (-1, >= L_i, INT_MIN, INT_MAX) reads nothing and contributes exactly nothing.  A NaN in a query row makes that row NaN; a NaN /
+    +inf score of a valid slot makes the rows of that token NaN and no other token's (a workgroup never serves two tokens).  Indices, lengths and
+    tables are read on the device: no host synchronisation, and a captured call replays with the indices then in memory.  Run-to-run deterministic per
+    split count; paged and contiguous calls over the same logical cache give the same bits.  The list 0, 1, .., n - 1 followed by -1 gives the bits of
+    the non-causal flash_mla_with_kvcache call at cache_seqlens = n with num_splits = 1 (and with a forced num_splits when topk == capacity); the same
+    list cut at L_i - seqlen_q + t + 1 per token gives those of its causal call.  num_splits: 0 = chosen by the library over this call's grid of
+    batch x seqlen_q x ceil(nheads / 64) workgroups; the split runs over the slots of the list in multiples of 32.
+    Out of scope, and without a keyword here: kv_new (engines write the latent cache themselves), an FP8 latent cache, cu_seqlens_q, sinks, returning
+    max logits, physical (pool-wide) indices, any backward.  Wrong shapes, dtypes or values are a ValueError that names the argument.
+    """
+    for name, t in (("q", q), ("kv_cache", kv_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{name} must be a rank-4 tensor")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, kv_cache)):
+        raise RuntimeError("flash_mla_sparse_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"q must be fp16 or bf16, got {q.dtype}")
+    if q.shape[-1] != 576:
+        raise ValueError(f"q must be 576 wide (512 absorbed no-rope columns, then 64 rope columns), got head_dim {q.shape[-1]}")
+    if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int) or head_dim_v != 512:
+        raise ValueError(f"head_dim_v must be 512, got {head_dim_v!r}")
+    if q.shape[1] < 1 or q.shape[2] < 1:
+        raise ValueError(f"q needs seqlen_q >= 1 and nheads >= 1, got shape {tuple(q.shape)}")
+    if kv_cache.dtype != q.dtype:
+        raise ValueError(f"kv_cache must have q's dtype ({q.dtype}), got {kv_cache.dtype} (an FP8 latent cache is out of scope)")
+    if kv_cache.shape[2] != 1:
+        raise ValueError(f"kv_cache must have exactly one head (the latent row), got {kv_cache.shape[2]}")
+    if kv_cache.shape[3] != 576:
+        raise ValueError(f"kv_cache must be 576 wide, got {kv_cache.shape[3]}")
+    if kv_cache.device != q.device:
+        raise ValueError("kv_cache must be on q's device")
+    b, sq = q.shape[0], q.shape[1]
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
+            raise ValueError("block_table must be an int32 tensor")
+        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.device != q.device:
+            raise ValueError("block_table must have shape (batch, max_blocks_per_seq) on q's device")
+        if kv_cache.shape[1] < 1 or kv_cache.shape[1] % 16 != 0:
+            raise ValueError(f"page_block_size (kv_cache.shape[1] with block_table) must be a positive multiple of 16, got {kv_cache.shape[1]}")
+    elif kv_cache.shape[0] != b:
+        raise ValueError(f"kv_cache batch ({kv_cache.shape[0]}) must match q's ({b})")
+    if isinstance(cache_seqlens, bool) or not isinstance(cache_seqlens, (int, torch.Tensor)):
+        raise ValueError("cache_seqlens must be an int32 tensor (batch,) on q's device or an int")
+    if isinstance(cache_seqlens, torch.Tensor) and (cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (b,) or cache_seqlens.device != q.device):
+        raise ValueError("cache_seqlens must be an int32 tensor (batch,) on q's device or an int")
+    if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int32:
+        raise ValueError("indices must be an int32 tensor (batch, seqlen_q, topk)")
+    if indices.dim() != 3 or indices.shape[0] != b or indices.shape[1] != sq:
+        raise ValueError(f"indices must have shape (batch, seqlen_q, topk) = ({b}, {sq}, topk), got {tuple(indices.shape)}")
+    if indices.shape[2] < 32 or indices.shape[2] % 32 != 0:
+        raise ValueError(f"indices: topk must be a positive multiple of 32 (pad the lists with -1), got {indices.shape[2]}")
+    if indices.stride(2) != 1:
+        raise ValueError("indices: the last dimension must be contiguous")
+    if indices.device != q.device:
+        raise ValueError("indices must be on q's device")
+    softmax_scale, _ = _check_scale_and_cap(softmax_scale, 0.0)
+    if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
+        raise ValueError(f"num_splits must be an int >= 0 (0 = chosen by the library), got {num_splits!r}")
+    if isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
+    out, lse = _C.fwd_mla_sparse_kvcache(q, kv_cache, indices, cache_seqlens, num_splits, block_table, softmax_scale, head_dim_v)
+    return (out, lse) if return_softmax_lse else out

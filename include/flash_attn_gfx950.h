@@ -678,6 +678,56 @@ typedef struct fa_mla_params {
     int32_t num_blocks;
 } fa_mla_params;
 
+/* Sparse MLA decode over a latent KV cache (FA_HAS_MLA_SPARSE_KVCACHE; DeepSeek-V3.2 "DeepSeek Sparse Attention"; FlashMLA's sparse call).  The cache, q, o
+ * and lse are those of fa_mla_params above; in place of every key below L_i, query token t of sequence i attends to the rows its list names:
+ *   indices: int32 DEVICE array, entry (i, t, s) at indices[i * indices_batch_stride + t * indices_row_stride + s], s < topk (strides in elements, the last
+ *   dim contiguous); topk a positive multiple of 32 (callers pad with -1).  An entry is a LOGICAL key position of sequence i (it goes through block_table
+ *   when the cache is paged) and belongs to the token: all h heads share it.
+ * With L_i = min(max(cache_seqlens[i], 0), seqlen_cache) (cache_seqlens NULL: seqlen_cache), slot s of row (i, t) is valid iff 0 <= entry < L_i.  The
+ * valid slots form a multiset (a position listed twice counts twice).  In fp32 math: s_ts = (q_t . kv[entry][0:576]) * softmax_scale,
+ * o_t = softmax over the valid slots @ kv[entry][0:512], lse the natural-log logsumexp over them; a row without a valid slot is o = 0, lse = 0.  There is
+ * no is_causal: the list is the mask.  An invalid entry of any value (-1, >= L_i, INT32_MIN, INT32_MAX) reads nothing and contributes exactly nothing;
+ * cache rows, pages and table entries that no valid slot names are never read.  A NaN query row, or a NaN / +inf score of a valid slot, gives NaN rows for
+ * that token and no other.  No host synchronisation (indices, lengths and tables are read on the device); paged == contiguous bit for bit; deterministic per
+ * split count.  The list 0 .. n - 1 followed by -1 gives the bits of fa_run_mla_fwd_kvcache without is_causal at cache_seqlens = n for one split (and for a
+ * forced num_splits when topk == seqlen_cache).
+ * workspace / num_splits as in fa_mla_params: fa_mla_sparse_workspace_bytes states n_split x rows x 512 x 4 + align16(n_split x rows x 4) bytes with
+ * rows = b * h * seqlen_q; the split runs over the slots [0, topk) in multiples of 32 (a forced count is at most topk / 32), the automatic one by the rule
+ * of fa_kvcache_num_splits with topk in the place of seqlen_cache over this grid's b x seqlen_q x ceil(h / 64) workgroups.
+ * Errors as for fa_mla_params; indices NULL (b > 0) FA_ERR_NULL_POINTER, topk / the index strides FA_ERR_BAD_SHAPE / FA_ERR_BAD_STRIDE naming them.
+ * b == 0 is FA_OK without a launch.  No kv_new, FP8 latent cache, ragged batch, sinks or physical (pool-wide) indices: the struct has no field for them. */
+#define FA_HAS_MLA_SPARSE_KVCACHE 1
+typedef struct fa_mla_sparse_params {
+    uint32_t struct_size;       /* sizeof(fa_mla_sparse_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const void* q;
+    const void* kv_cache;
+    void* o;
+    float* lse;
+    const int32_t* cache_seqlens;
+    const int32_t* indices;
+    int32_t b;
+    int32_t seqlen_q;
+    int32_t seqlen_cache;
+    int32_t topk;               /* a positive multiple of 32 */
+    int32_t h;
+    int32_t d_qk;               /* 576 */
+    int32_t d_v;                /* 512 */
+    int32_t dtype;
+    int32_t num_splits;         /* 0 = the library's choice */
+    float softmax_scale;        /* 0 = 576 ** -0.5 */
+    int64_t reserved_;          /* 0 */
+    fa_strides q_stride, kv_cache_stride, o_stride;     /* kv_cache_stride.head is not read */
+    int64_t indices_batch_stride;
+    int64_t indices_row_stride;
+    void* workspace;
+    int64_t workspace_bytes;
+    const int32_t* block_table; /* paged cache; NULL = contiguous */
+    int64_t block_table_stride;
+    int32_t page_block_size;
+    int32_t num_blocks;
+} fa_mla_sparse_params;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -755,6 +805,13 @@ int fa_run_mla_fwd_kvcache(const fa_mla_params* params, void* stream);
  * `workspace` fields ignored; and the splits the launch would use, the workspace fields included (NULL / 0 -> 1).  Negative = error code. */
 int64_t fa_mla_workspace_bytes(const fa_mla_params* params);
 int32_t fa_mla_num_splits(const fa_mla_params* params);
+
+/* ---- sparse MLA decode over a latent KV cache (fa_mla_sparse_params above) ------------------- */
+/* Split attention over the token lists, and the combine of the splits: up to two launches on `stream`, no host synchronisation. */
+int fa_run_mla_sparse_fwd_kvcache(const fa_mla_sparse_params* params, void* stream);
+/* Host-only, like fa_mla_workspace_bytes / fa_mla_num_splits.  Negative = error code, exactly those of the launch. */
+int64_t fa_mla_sparse_workspace_bytes(const fa_mla_sparse_params* params);
+int32_t fa_mla_sparse_num_splits(const fa_mla_sparse_params* params);
 
 /* ---- measurement helpers ----------------------------------------------------------------- */
 /* Algorithmic FLOPs of one forward call (4*b*h*sq*sk*d, causal counts only visible pairs);

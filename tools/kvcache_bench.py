@@ -73,6 +73,12 @@ b * L * 1152 B / time as a fraction of 6.3 TB/s; (B, B2) the yardstick, the head
 (1024 B per key: nearly the same bytes, fewer FLOPs), timed TWICE so that the scatter of one thing measured twice in the same run stands next to
 A / B; interleaved, medians.
 
+--mla-sparse measures sparse MLA decode (flash_mla_sparse_with_kvcache): bf16, seqlen_q 1, h in {16, 128}, b in {1, 8, 64}, topk 2048, pages of 64 (--paged P
+replaces the page size).  The yardstick is the DENSE flash_mla_with_kvcache call at L = topk - the same rows, the same bytes - timed TWICE (B, B2: its own
+noise figure).  Against it, interleaved in one process: (i) the identity list 0 .. topk - 1 on the same caches; and per L in {32k, 128k} (--length replaces
+them) on one cache of that length, rotating over lists, (ii) 2048 random positions, sorted, (iii) the same positions unsorted.  At b in {1, 8} a second line
+per point records arm (i) under forced num_splits 8, 16, 32, 64 next to the automatic count, timed twice (profiles/kvcache_mla_sparse_bench.log).
+
 --baseline-library PATH records an interleaved A/B of the plain (no window) call through the C ABI of this build and of the library at
 PATH (e.g. a build of the parent commit), on the same data; the outputs must agree bit for bit.  --length L (repeatable) replaces the
 grid's cache lengths."""
@@ -857,6 +863,78 @@ def run_mla(lengths, pages, rounds):
             yield run_mla_point(b, h, L, page, rounds)
 
 
+def run_mla_sparse_point(b, h, lengths, page, rounds, topk=2048):
+    """the dense MLA call at L = topk twice (the yardstick and its noise), (i) the identity list on the same caches, and per L (ii) sorted / (iii) unsorted random
+    positions on one cache of L rows; then, at b <= 8, arm (i) under forced split counts"""
+    dev, dt = torch.device("cuda:0"), torch.bfloat16
+    read_bytes = b * topk * 576 * 2
+    n = _rotation(read_bytes, read_bytes, budget=8 << 30)
+
+    def cache(L, seed):
+        nb = b * L // page
+        table = torch.randperm(nb, generator=torch.Generator().manual_seed(seed)).view(b, L // page).to(device=dev, dtype=torch.int32)
+        return torch.empty(nb, page, 1, 576, device=dev, dtype=dt).uniform_(-2, 2), table
+
+    small = [cache(topk, i) for i in range(n)]
+    q = torch.randn(b, 1, h, 576, device=dev, dtype=dt)
+    cs = torch.full((b,), topk, dtype=torch.int32, device=dev)
+    ident = torch.arange(topk, dtype=torch.int32, device=dev).view(1, 1, topk).expand(b, 1, topk).contiguous()
+    dense = lambda i: F.flash_mla_with_kvcache(q, small[i % n][0], cs, block_table=small[i % n][1])
+    arm_i = lambda i, ns=0: F.flash_mla_sparse_with_kvcache(q, small[i % n][0], cs, ident, block_table=small[i % n][1], num_splits=ns)
+    assert _bits_equal(F.flash_mla_sparse_with_kvcache(q, small[0][0], cs, ident, block_table=small[0][1], num_splits=1),
+                       F.flash_mla_with_kvcache(q, small[0][0], cs, block_table=small[0][1], num_splits=1)), "the identity list is not the dense call"
+    arms = {"dense": dense, "sparse_identity": arm_i}
+    big, lists = {}, {}
+    n_lists = max(n, 4)
+    gen = torch.Generator().manual_seed(1234 + b + h)
+    for L in lengths:
+        big[L] = cache(L, 1000 + L)
+        pos = torch.stack([torch.stack([torch.randperm(L, generator=gen)[:topk] for _ in range(b)]) for _ in range(n_lists)]).to(torch.int32).unsqueeze(2)
+        lists[L] = (pos.sort(-1).values.to(dev), pos.to(dev))
+        csL = torch.full((b,), L, dtype=torch.int32, device=dev)
+        arms[f"sparse_sorted_L{L}"] = lambda i, L=L, csL=csL: F.flash_mla_sparse_with_kvcache(q, big[L][0], csL, lists[L][0][i % n_lists], block_table=big[L][1])
+        arms[f"sparse_unsorted_L{L}"] = lambda i, L=L, csL=csL: F.flash_mla_sparse_with_kvcache(q, big[L][0], csL, lists[L][1][i % n_lists], block_table=big[L][1])
+    arms["dense_again"] = dense
+    for f in arms.values():
+        f(0)
+    torch.cuda.synchronize()
+    ms = _interleaved(arms, max(n, n_lists), rounds)
+    o, lse = torch.empty(b, 1, h, 512, device=dev, dtype=dt), torch.empty(b, h, 1, device=dev)
+    ps = capi.mla_sparse_params(q, small[0][0], o, lse, ident, cs, block_table=small[0][1])
+    ws = capi.mla_sparse_workspace_bytes(ps)
+    n_split = max(1, ws and capi.mla_sparse_num_splits(_with_ws(ps, ws)))
+    pd = capi.mla_params(q, small[0][0], o, lse, cs, block_table=small[0][1])
+    wsd = capi.mla_workspace_bytes(pd)
+    n_split_d = max(1, wsd and capi.mla_num_splits(_with_ws(pd, wsd)))
+    lo, hi = sorted((ms["dense"], ms["dense_again"]))
+    line = dict(mla_sparse=True, b=b, h=h, topk=topk, seqlen_q=1, dtype="bfloat16", page_block_size=page, caches_rotated=n, lists_rotated=n_lists,
+                read_mb=round(read_bytes / 1e6, 2), n_split_sparse=n_split, n_split_dense=n_split_d,
+                ms={k: round(v, 5) for k, v in ms.items()}, dense_spread=round(hi / lo, 4),
+                over_dense={k: round(v / ms["dense"], 4) for k, v in ms.items() if k != "dense"},
+                frac_of_6p3={k: round(read_bytes / (v * 1e-3) / HBM_ACHIEVABLE, 4) for k, v in ms.items()})
+    yield line
+    if b <= 8:
+        forced = {"auto": arm_i}
+        for ns in (8, 16, 32, 64):
+            forced[f"splits{ns}"] = lambda i, ns=ns: arm_i(i, ns)
+        forced["auto_again"] = arm_i
+        for f in forced.values():
+            f(0)
+        torch.cuda.synchronize()
+        ms = _interleaved(forced, n, rounds)
+        lo, hi = sorted((ms["auto"], ms["auto_again"]))
+        best = min((k for k in ms if k.startswith("splits")), key=lambda k: ms[k])
+        yield dict(mla_sparse_forced_splits=True, b=b, h=h, topk=topk, page_block_size=page, n_split_auto=n_split, ms={k: round(v, 5) for k, v in ms.items()},
+                   auto_spread=round(hi / lo, 4), best_forced=best, auto_over_best=round(lo / ms[best], 4), beats_auto_beyond_spread=bool(ms[best] * (hi / lo) < lo))
+    del small, big, lists
+    torch.cuda.empty_cache()
+
+
+def run_mla_sparse(lengths, pages, rounds):
+    for h, b in itertools.product((16, 128), (1, 8, 64)):
+        yield from run_mla_sparse_point(b, h, tuple(lengths or (32768, 131072)), (pages or [64])[0], rounds)
+
+
 def _baseline_lib(path):
     L = ctypes.CDLL(os.path.abspath(path))
     L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
@@ -943,6 +1021,8 @@ def main():
     ap.add_argument("--equal-bytes", action="store_true", help="with --head-dim 256: the d-256 call against the d-128 call with twice the heads on the same buffers (timed twice)")
     ap.add_argument("--mla", action="store_true", help="MLA decode over a latent KV cache (flash_mla_with_kvcache) against the head_dim-256 decode call with one KV head "
                                                        "(timed twice); contiguous and, with --paged P, through a block table")
+    ap.add_argument("--mla-sparse", action="store_true", help="sparse MLA decode (flash_mla_sparse_with_kvcache, topk 2048, pages of 64 or --paged P) against the dense MLA call "
+                                                              "at L = topk (timed twice): the identity list, sorted and unsorted random positions of L in {32k, 128k}; forced splits")
     a = ap.parse_args()
     base = _baseline_lib(a.baseline_library) if a.baseline_library else None
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
@@ -952,6 +1032,10 @@ def main():
     with torch.no_grad():
         if a.ragged and base is None:
             for line in run_ragged(a.quick, a.rounds):
+                print(json.dumps(line), flush=True)
+            return
+        if a.mla_sparse:
+            for line in run_mla_sparse(a.length, a.paged, a.rounds):
                 print(json.dumps(line), flush=True)
             return
         if a.mla:
