@@ -81,6 +81,40 @@ int import_params(const P* user, P& local, const char* what, size_t base = offse
     return FA_OK;
 }
 
+// The MLA structs come in two sizes, fa_mla*_params and fa_mla*_params_v2 (kv_format appended), through one pointer: exactly those two sizes are
+// accepted, and the first arrives as a _v2 with kv_format = 0.  (The layouts share their prefix: static_asserts below.)
+template <typename P1, typename P2>
+int import_mla(const P1* user, P2& local, const char* what) {
+    static_assert(sizeof(P2) == sizeof(P1) + 8 && offsetof(P2, kv_format) == sizeof(P1), "the _v2 struct is the first one with two int32 appended");
+    if (user == nullptr) return fail(FA_ERR_NULL_POINTER, "params is NULL");
+    if (user->magic != FA_PARAMS_MAGIC)
+        return fail(FA_ERR_BAD_ABI, "%s: no {struct_size, magic} header - caller was compiled against an ABI < 4 header; recompile against include/flash_attn_gfx950.h (ABI %d)",
+                    what, FA_ABI_VERSION);
+    if (user->struct_size != sizeof(P1) && user->struct_size != sizeof(P2))
+        return fail(FA_ERR_BAD_ABI, "%s: struct_size %u is neither %zu nor %zu (%s_v2) - header / library mismatch", what, user->struct_size, sizeof(P1), sizeof(P2), what);
+    memset(&local, 0, sizeof(P2));
+    memcpy(&local, user, user->struct_size);
+    return FA_OK;
+}
+
+int check_mla_format(int32_t kv_format, int32_t reserved2) {
+    if (kv_format != FA_MLA_KV_16BIT && kv_format != FA_MLA_KV_FP8_ROWS656)
+        return fail(FA_ERR_BAD_SHAPE, "kv_format %d unknown (0 = a 16-bit latent cache, 1 = FP8 rows of 656 bytes)", kv_format);
+    if (reserved2 != 0) return fail(FA_ERR_BAD_SHAPE, "reserved2_ is not zero (%d)", reserved2);
+    return FA_OK;
+}
+
+// kv_cache of kv_format = FA_MLA_KV_FP8_ROWS656: strides in bytes, 16-byte loads and stores; one sequence (one page) fits a 32-bit byte offset
+int check_mla_cache8(const void* ptr, const fa_strides& st, int64_t rows) {
+    if (ptr == nullptr) return fail(FA_ERR_NULL_POINTER, "kv_cache is NULL");
+    if (((uintptr_t)ptr & 15) != 0) return fail(FA_ERR_BAD_STRIDE, "kv_cache base pointer must be 16-byte aligned");
+    if (st.row < 656 || (st.row % 16) != 0 || (st.batch % 16) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "kv_cache (FP8 rows of 656 bytes) strides (batch=%lld,row=%lld) must be multiples of 16 bytes with row >= 656", (long long)st.batch,
+                    (long long)st.row);
+    if (rows * st.row >= ((int64_t)1 << 31)) return fail(FA_ERR_BAD_STRIDE, "kv_cache: one sequence spans %lld bytes (limit 2^31)", (long long)(rows * st.row));
+    return FA_OK;
+}
+
 int hip_status(hipError_t e, const char* what) {
     if (e == hipSuccess) return FA_OK;
     fail((int)e, "%s: %s", what, hipGetErrorString(e));
@@ -742,10 +776,11 @@ int fa_run_mha_fwd_kvcache(const fa_kvcache_params* user, void* stream) { return
 // ---- MLA decode over a latent KV cache -------------------------------------------------------------------------------------------------------
 // fa_mla_params -> KvcacheMlaParams, validated.  kp.d = 512 is the width of V, of o and of the partial planes; the split and the workspace are the
 // decode call's rules over the grid of 64-row tiles.  with_workspace = false: the `workspace` fields are not looked at.
-static int fill_mla(const fa_mla_params* user, fa::KvcacheMlaParams& mp, fa_mla_params& local, bool with_workspace) {
-    int rc = import_params(user, local, "fa_mla_params", sizeof(fa_mla_params));
+static int fill_mla(const fa_mla_params* user, fa::KvcacheMlaParams& mp, fa_mla_params_v2& local, bool with_workspace) {
+    int rc = import_mla(user, local, "fa_mla_params");
     if (rc) return rc;
-    const fa_mla_params* p = &local;
+    const fa_mla_params_v2* p = &local;
+    const bool fp8 = p->kv_format == FA_MLA_KV_FP8_ROWS656;
     const bool paged = p->block_table != nullptr;
     if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0 || p->seqlen_new < 0 || p->h <= 0)
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d seqlen_new=%d h=%d", p->b, p->seqlen_q, p->seqlen_cache, p->seqlen_new, p->h);
@@ -774,6 +809,7 @@ static int fill_mla(const fa_mla_params* user, fa::KvcacheMlaParams& mp, fa_mla_
     if (!(p->softmax_scale >= 0.f) || isinf(p->softmax_scale))
         return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default 576 ** -0.5)", (double)p->softmax_scale);
     if (p->reserved_ != 0) return fail(FA_ERR_BAD_ABI, "fa_mla_params: reserved_ is not zero (a field of a newer header that this library does not know)");
+    if ((rc = check_mla_format(p->kv_format, p->reserved2_))) return rc;
     if (with_workspace && p->workspace_bytes < 0) return fail(FA_ERR_BAD_SHAPE, "workspace_bytes must be >= 0");
     if (with_workspace && p->workspace != nullptr && (reinterpret_cast<uintptr_t>(p->workspace) & 15u) != 0)
         return fail(FA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
@@ -788,7 +824,8 @@ static int fill_mla(const fa_mla_params* user, fa::KvcacheMlaParams& mp, fa_mla_
         if ((rc = check_tensor("q", p->q, p->q_stride, p->seqlen_q, p->d_qk, false))) return rc;
         if ((rc = check_tensor("o", p->o, p->o_stride, p->seqlen_q, p->d_v, false))) return rc;
         // paged: the descriptors span at most one page, so the 2^31-byte limit applies per page (page offsets are 64-bit)
-        if ((rc = check_tensor("kv_cache", p->kv_cache, kvc, paged ? p->page_block_size : p->seqlen_cache, p->d_qk, false))) return rc;
+        if (fp8 ? (rc = check_mla_cache8(p->kv_cache, kvc, paged ? p->page_block_size : p->seqlen_cache))
+                : (rc = check_tensor("kv_cache", p->kv_cache, kvc, paged ? p->page_block_size : p->seqlen_cache, p->d_qk, false))) return rc;
         if (p->kv_new != nullptr && (rc = check_tensor("kv_new", p->kv_new, kvn, p->seqlen_new, p->d_qk, false))) return rc;
     }
     memset(&mp, 0, sizeof(mp));
@@ -800,6 +837,7 @@ static int fill_mla(const fa_mla_params* user, fa::KvcacheMlaParams& mp, fa_mla_
     kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_cache = p->seqlen_cache; kp.seqlen_new = p->kv_new != nullptr ? p->seqlen_new : 0;
     kp.h = p->h; kp.h_k = 1; kp.h_ratio = p->h; kp.d = p->d_v;
     kp.is_causal = p->is_causal ? 1 : 0;
+    kp.cache_fp8 = fp8 ? 1 : 0;     // kc / vc are in bytes then
     kp.scale = p->softmax_scale > 0.f ? p->softmax_scale : 1.0f / sqrtf((float)p->d_qk);
     kp.scale_log2e = kp.scale * 1.4426950408889634f;
     if (paged) {
@@ -811,7 +849,7 @@ static int fill_mla(const fa_mla_params* user, fa::KvcacheMlaParams& mp, fa_mla_
 
 int64_t fa_mla_workspace_bytes(const fa_mla_params* user) {
     fa::KvcacheMlaParams mp;
-    fa_mla_params local;
+    fa_mla_params_v2 local;
     int rc = fill_mla(user, mp, local, false);
     if (rc) return rc;
     if (mp.kp.b == 0) return 0;
@@ -820,7 +858,7 @@ int64_t fa_mla_workspace_bytes(const fa_mla_params* user) {
 
 int32_t fa_mla_num_splits(const fa_mla_params* user) {
     fa::KvcacheMlaParams mp;
-    fa_mla_params local;
+    fa_mla_params_v2 local;
     int rc = fill_mla(user, mp, local, true);
     if (rc) return rc;
     if (mp.kp.b == 0) return 1;
@@ -829,12 +867,13 @@ int32_t fa_mla_num_splits(const fa_mla_params* user) {
 
 int fa_run_mla_fwd_kvcache(const fa_mla_params* user, void* stream) {
     fa::KvcacheMlaParams mp;
-    fa_mla_params local;
+    fa_mla_params_v2 local;
     int rc = fill_mla(user, mp, local, true);
     if (rc) return rc;
     if (mp.kp.b == 0) return FA_OK;
     mp.kp.n_split = fa::kvcache_split(mp.kp, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits, -1, fa::kKvcPrefillRows);
     mp.kp.ws_o = mp.kp.n_split > 1 ? (float*)local.workspace : nullptr;
+    if (mp.kp.cache_fp8) return hip_status(fa::launch_fwd_kvcache_mla_fp8(mp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache_mla_fp8 launch");
     return hip_status(fa::launch_fwd_kvcache_mla(mp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache_mla launch");
 }
 
@@ -842,10 +881,11 @@ int fa_run_mla_fwd_kvcache(const fa_mla_params* user, void* stream) {
 // fa_mla_sparse_params -> KvcacheMlaSparseParams, validated: the checks and words of fill_mla without kv_new / is_causal, plus indices and topk.  split: what
 // kvcache_split / kvcache_workspace_bytes are asked with - the grid is b x seqlen_q x ceil(h / 64) workgroups a split and the split runs over the slots
 // [0, topk), so the copy states b x seqlen_q "sequences" of one token and topk in the place of seqlen_cache (rows = b * h * seqlen_q either way).
-static int fill_mla_sparse(const fa_mla_sparse_params* user, fa::KvcacheMlaSparseParams& sp, fa::KvcacheKernelParams& split, fa_mla_sparse_params& local, bool with_workspace) {
-    int rc = import_params(user, local, "fa_mla_sparse_params", sizeof(fa_mla_sparse_params));
+static int fill_mla_sparse(const fa_mla_sparse_params* user, fa::KvcacheMlaSparseParams& sp, fa::KvcacheKernelParams& split, fa_mla_sparse_params_v2& local, bool with_workspace) {
+    int rc = import_mla(user, local, "fa_mla_sparse_params");
     if (rc) return rc;
-    const fa_mla_sparse_params* p = &local;
+    const fa_mla_sparse_params_v2* p = &local;
+    const bool fp8 = p->kv_format == FA_MLA_KV_FP8_ROWS656;
     const bool paged = p->block_table != nullptr;
     if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0 || p->h <= 0)
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d h=%d", p->b, p->seqlen_q, p->seqlen_cache, p->h);
@@ -872,6 +912,7 @@ static int fill_mla_sparse(const fa_mla_sparse_params* user, fa::KvcacheMlaSpars
     if (!(p->softmax_scale >= 0.f) || isinf(p->softmax_scale))
         return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default 576 ** -0.5)", (double)p->softmax_scale);
     if (p->reserved_ != 0) return fail(FA_ERR_BAD_ABI, "fa_mla_sparse_params: reserved_ is not zero (a field of a newer header that this library does not know)");
+    if ((rc = check_mla_format(p->kv_format, p->reserved2_))) return rc;
     if (with_workspace && p->workspace_bytes < 0) return fail(FA_ERR_BAD_SHAPE, "workspace_bytes must be >= 0");
     if (with_workspace && p->workspace != nullptr && (reinterpret_cast<uintptr_t>(p->workspace) & 15u) != 0)
         return fail(FA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
@@ -891,7 +932,8 @@ static int fill_mla_sparse(const fa_mla_sparse_params* user, fa::KvcacheMlaSpars
         if ((rc = check_tensor("q", p->q, p->q_stride, p->seqlen_q, p->d_qk, false))) return rc;
         if ((rc = check_tensor("o", p->o, p->o_stride, p->seqlen_q, p->d_v, false))) return rc;
         // paged: the descriptors span one cache row, page offsets are 64-bit; contiguous: one descriptor per sequence, below 2^31 bytes
-        if ((rc = check_tensor("kv_cache", p->kv_cache, kvc, paged ? p->page_block_size : p->seqlen_cache, p->d_qk, false))) return rc;
+        if (fp8 ? (rc = check_mla_cache8(p->kv_cache, kvc, paged ? p->page_block_size : p->seqlen_cache))
+                : (rc = check_tensor("kv_cache", p->kv_cache, kvc, paged ? p->page_block_size : p->seqlen_cache, p->d_qk, false))) return rc;
     }
     memset(&sp, 0, sizeof(sp));
     fa::KvcacheKernelParams& kp = sp.kp;
@@ -902,6 +944,7 @@ static int fill_mla_sparse(const fa_mla_sparse_params* user, fa::KvcacheMlaSpars
     kp.q = conv(p->q_stride); kp.kc = kp.vc = conv(kvc); kp.o = conv(p->o_stride);
     kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_cache = p->seqlen_cache;
     kp.h = p->h; kp.h_k = 1; kp.h_ratio = p->h; kp.d = p->d_v;
+    kp.cache_fp8 = fp8 ? 1 : 0;     // kc / vc are in bytes then
     kp.scale = p->softmax_scale > 0.f ? p->softmax_scale : 1.0f / sqrtf((float)p->d_qk);
     kp.scale_log2e = kp.scale * 1.4426950408889634f;
     if (paged) {
@@ -916,7 +959,7 @@ static int fill_mla_sparse(const fa_mla_sparse_params* user, fa::KvcacheMlaSpars
 int64_t fa_mla_sparse_workspace_bytes(const fa_mla_sparse_params* user) {
     fa::KvcacheMlaSparseParams sp;
     fa::KvcacheKernelParams split;
-    fa_mla_sparse_params local;
+    fa_mla_sparse_params_v2 local;
     int rc = fill_mla_sparse(user, sp, split, local, false);
     if (rc) return rc;
     if (sp.kp.b == 0) return 0;
@@ -926,7 +969,7 @@ int64_t fa_mla_sparse_workspace_bytes(const fa_mla_sparse_params* user) {
 int32_t fa_mla_sparse_num_splits(const fa_mla_sparse_params* user) {
     fa::KvcacheMlaSparseParams sp;
     fa::KvcacheKernelParams split;
-    fa_mla_sparse_params local;
+    fa_mla_sparse_params_v2 local;
     int rc = fill_mla_sparse(user, sp, split, local, true);
     if (rc) return rc;
     if (sp.kp.b == 0) return 1;
@@ -936,12 +979,13 @@ int32_t fa_mla_sparse_num_splits(const fa_mla_sparse_params* user) {
 int fa_run_mla_sparse_fwd_kvcache(const fa_mla_sparse_params* user, void* stream) {
     fa::KvcacheMlaSparseParams sp;
     fa::KvcacheKernelParams split;
-    fa_mla_sparse_params local;
+    fa_mla_sparse_params_v2 local;
     int rc = fill_mla_sparse(user, sp, split, local, true);
     if (rc) return rc;
     if (sp.kp.b == 0) return FA_OK;
     sp.kp.n_split = fa::kvcache_split(split, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits, -1, fa::kKvcPrefillRows);
     sp.kp.ws_o = sp.kp.n_split > 1 ? (float*)local.workspace : nullptr;
+    if (sp.kp.cache_fp8) return hip_status(fa::launch_fwd_kvcache_mla_sparse_fp8(sp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache_mla_sparse_fp8 launch");
     return hip_status(fa::launch_fwd_kvcache_mla_sparse(sp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache_mla_sparse launch");
 }
 

@@ -295,6 +295,12 @@ struct KvcacheMlaSparseParams {
 };
 hipError_t launch_fwd_kvcache_mla_sparse(KvcacheMlaSparseParams sp, int dtype, hipStream_t stream);
 
+// The two MLA calls over an FP8 latent cache of 656-byte rows (fa_fwd_kvcache_mla_fp8.hip, kv_format = FA_MLA_KV_FP8_ROWS656): 512 e4m3 codes, four fp32
+// scales (one per 128 codes), then the 64 rope elements in q's dtype.  The same params with kp.cache_fp8 = 1 and kp.kc in BYTES; k_new / kn stay 16-bit
+// rows of 576 elements, quantised by the append.  Split, workspace and partial planes are those of the 16-bit launchers above.
+hipError_t launch_fwd_kvcache_mla_fp8(KvcacheMlaParams mp, int dtype, hipStream_t stream);
+hipError_t launch_fwd_kvcache_mla_sparse_fp8(KvcacheMlaSparseParams sp, int dtype, hipStream_t stream);
+
 // Rotary embedding on a decode call (fa_kvcache_rotary.hip, fa_kvcache_options_v3).  One fused launch takes the place of the append: it
 // rotates k_new into the cache, copies / quantises v_new, and writes the rotated q into `q_image`, a contiguous (b, seqlen_q, h, d) buffer of
 // q's dtype at the head of the caller's workspace; the attention kernels then read that image as their q.  A block of its own and not

@@ -473,6 +473,11 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
     return {o, l};
 }
 
+// kv_cache of the two MLA calls below in the FP8 format (FA_MLA_KV_FP8_ROWS656): a 1-byte dtype and 656-byte rows; anything else is the 16-bit cache
+static bool mla_cache_is_fp8(const at::Tensor& kv_cache) {
+    return (kv_cache.scalar_type() == torch::kUInt8 || kv_cache.scalar_type() == at::ScalarType::Float8_e4m3fn) && kv_cache.dim() == 4 && kv_cache.size(3) == 656;
+}
+
 // MLA decode over a latent KV cache (fa_run_mla_fwd_kvcache): q (b, sq, h, 576), kv_cache (b, capacity, 1, 576) or a page pool (num_blocks,
 // page_block_size, 1, 576) with block_table, kv_new (b, s_new, 1, 576) appended in place; out (b, sq, h, 512) and lse (b, h, sq).  The cache is never
 // copied; lengths and tables are read on the device.  softmax_scale: rounded once to fp32, None = the library's default 576 ** -0.5.
@@ -482,11 +487,12 @@ std::vector<at::Tensor> mha_fwd_mla_kvcache(at::Tensor q, at::Tensor kv_cache, c
     TORCH_CHECK(q.dim() == 4 && kv_cache.dim() == 4, "q and kv_cache must be rank-4 tensors");
     TORCH_CHECK(q.is_cuda() && kv_cache.is_cuda(), "q, kv_cache must be GPU (HIP) tensors");
     TORCH_CHECK(kv_cache.device() == q.device(), "q, kv_cache must be on the same device");
-    TORCH_CHECK(kv_cache.scalar_type() == q.scalar_type(), "kv_cache must have the dtype of q, got ", kv_cache.scalar_type());
+    const bool fp8 = mla_cache_is_fp8(kv_cache);
+    TORCH_CHECK(fp8 || kv_cache.scalar_type() == q.scalar_type(), "kv_cache must have the dtype of q, got ", kv_cache.scalar_type());
     const int64_t batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), head_size = q.size(3);
     TORCH_CHECK(seqlen_q >= 1 && num_heads >= 1, "seqlen_q and the number of heads must be >= 1");
     TORCH_CHECK(kv_cache.size(2) == 1, "kv_cache must have exactly one head (the latent row)");
-    TORCH_CHECK(kv_cache.size(3) == head_size, "q / kv_cache head_dim must match");
+    TORCH_CHECK(fp8 || kv_cache.size(3) == head_size, "q / kv_cache head_dim must match");
     TORCH_CHECK(kv_cache.stride(3) == 1, "kv_cache: last dimension must be contiguous");
     TORCH_CHECK(num_splits >= 0 && num_splits <= INT32_MAX, "num_splits must be >= 0 (0 = automatic)");
     TORCH_CHECK(head_dim_v >= 0 && head_dim_v <= INT32_MAX && head_size <= INT32_MAX, "head dims must fit in int32");
@@ -526,8 +532,10 @@ std::vector<at::Tensor> mha_fwd_mla_kvcache(at::Tensor q, at::Tensor kv_cache, c
     at::Tensor o = torch::empty({batch_size, seqlen_q, num_heads, head_dim_v}, q.options());
     at::Tensor l = torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(torch::kFloat32));
 
-    fa_mla_params p;
-    FA_PARAMS_INIT(p);
+    fa_mla_params_v2 pv;
+    FA_PARAMS_INIT(pv);
+    pv.kv_format = fp8 ? FA_MLA_KV_FP8_ROWS656 : FA_MLA_KV_16BIT;     // (FP8: a 1-byte dtype, so strides4(kv_cache) is in bytes, as the format asks)
+    fa_mla_params& p = reinterpret_cast<fa_mla_params&>(pv);
     p.q = q.data_ptr(); p.kv_cache = kv_cache.data_ptr(); p.o = o.data_ptr(); p.lse = l.data_ptr<float>();
     p.cache_seqlens = cache_seqlens.defined() ? cache_seqlens.data_ptr<int32_t>() : nullptr;
     p.b = (int32_t)batch_size; p.seqlen_q = (int32_t)seqlen_q; p.seqlen_cache = (int32_t)seqlen_cache;
@@ -566,11 +574,12 @@ std::vector<at::Tensor> mha_fwd_mla_sparse_kvcache(at::Tensor q, at::Tensor kv_c
     TORCH_CHECK(q.dim() == 4 && kv_cache.dim() == 4, "q and kv_cache must be rank-4 tensors");
     TORCH_CHECK(q.is_cuda() && kv_cache.is_cuda(), "q, kv_cache must be GPU (HIP) tensors");
     TORCH_CHECK(kv_cache.device() == q.device(), "q, kv_cache must be on the same device");
-    TORCH_CHECK(kv_cache.scalar_type() == q.scalar_type(), "kv_cache must have the dtype of q, got ", kv_cache.scalar_type());
+    const bool fp8 = mla_cache_is_fp8(kv_cache);
+    TORCH_CHECK(fp8 || kv_cache.scalar_type() == q.scalar_type(), "kv_cache must have the dtype of q, got ", kv_cache.scalar_type());
     const int64_t batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), head_size = q.size(3);
     TORCH_CHECK(seqlen_q >= 1 && num_heads >= 1, "seqlen_q and the number of heads must be >= 1");
     TORCH_CHECK(kv_cache.size(2) == 1, "kv_cache must have exactly one head (the latent row)");
-    TORCH_CHECK(kv_cache.size(3) == head_size, "q / kv_cache head_dim must match");
+    TORCH_CHECK(fp8 || kv_cache.size(3) == head_size, "q / kv_cache head_dim must match");
     TORCH_CHECK(kv_cache.stride(3) == 1, "kv_cache: last dimension must be contiguous");
     TORCH_CHECK(num_splits >= 0 && num_splits <= INT32_MAX, "num_splits must be >= 0 (0 = automatic)");
     TORCH_CHECK(head_dim_v >= 0 && head_dim_v <= INT32_MAX && head_size <= INT32_MAX, "head dims must fit in int32");
@@ -604,8 +613,10 @@ std::vector<at::Tensor> mha_fwd_mla_sparse_kvcache(at::Tensor q, at::Tensor kv_c
     at::Tensor o = torch::empty({batch_size, seqlen_q, num_heads, head_dim_v}, q.options());
     at::Tensor l = torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(torch::kFloat32));
 
-    fa_mla_sparse_params p;
-    FA_PARAMS_INIT(p);
+    fa_mla_sparse_params_v2 pv;
+    FA_PARAMS_INIT(pv);
+    pv.kv_format = fp8 ? FA_MLA_KV_FP8_ROWS656 : FA_MLA_KV_16BIT;     // (FP8: a 1-byte dtype, so strides4(kv_cache) is in bytes, as the format asks)
+    fa_mla_sparse_params& p = reinterpret_cast<fa_mla_sparse_params&>(pv);
     p.q = q.data_ptr(); p.kv_cache = kv_cache.data_ptr(); p.o = o.data_ptr(); p.lse = l.data_ptr<float>();
     p.cache_seqlens = cache_seqlens.defined() ? cache_seqlens.data_ptr<int32_t>() : nullptr;
     p.indices = indices.data_ptr<int32_t>(); p.topk = (int32_t)indices.size(2);

@@ -145,6 +145,18 @@ class MlaSparseParams(_Params):
                 ("block_table", _vp), ("block_table_stride", ctypes.c_int64), ("page_block_size", _i32), ("num_blocks", _i32)]
 
 
+class MlaParamsV2(_Params):
+    """fa_mla_params_v2: fa_mla_params plus kv_format (same pointer, told apart by struct_size)"""
+    _fields_ = MlaParams._fields_ + [("kv_format", _i32), ("reserved2_", _i32)]
+
+
+class MlaSparseParamsV2(_Params):
+    """fa_mla_sparse_params_v2: fa_mla_sparse_params plus kv_format (same pointer, told apart by struct_size)"""
+    _fields_ = MlaSparseParams._fields_ + [("kv_format", _i32), ("reserved2_", _i32)]
+
+
+FA_MLA_KV_16BIT = 0
+FA_MLA_KV_FP8_ROWS656 = 1       # 656-byte latent rows: 512 e4m3 codes, four fp32 scales, 64 rope elements of q's dtype; kv_cache_stride in bytes
 FA_CACHE_FP8_E4M3 = 1
 
 
@@ -193,17 +205,18 @@ def lib():
         L.fa_kvcache_num_splits_ex.restype = ctypes.c_int32
         L.fa_kvcache_row_tile_ex.argtypes = [ctypes.POINTER(KvcacheParams), _op]
         L.fa_kvcache_row_tile_ex.restype = ctypes.c_int32
-        L.fa_run_mla_fwd_kvcache.argtypes = [ctypes.POINTER(MlaParams), _vp]
+        # (fa_mla_params or fa_mla_params_v2, fa_mla_sparse_params or its _v2, through the same pointer: void*)
+        L.fa_run_mla_fwd_kvcache.argtypes = [_vp, _vp]
         L.fa_run_mla_fwd_kvcache.restype = ctypes.c_int
-        L.fa_mla_workspace_bytes.argtypes = [ctypes.POINTER(MlaParams)]
+        L.fa_mla_workspace_bytes.argtypes = [_vp]
         L.fa_mla_workspace_bytes.restype = ctypes.c_int64
-        L.fa_mla_num_splits.argtypes = [ctypes.POINTER(MlaParams)]
+        L.fa_mla_num_splits.argtypes = [_vp]
         L.fa_mla_num_splits.restype = ctypes.c_int32
-        L.fa_run_mla_sparse_fwd_kvcache.argtypes = [ctypes.POINTER(MlaSparseParams), _vp]
+        L.fa_run_mla_sparse_fwd_kvcache.argtypes = [_vp, _vp]
         L.fa_run_mla_sparse_fwd_kvcache.restype = ctypes.c_int
-        L.fa_mla_sparse_workspace_bytes.argtypes = [ctypes.POINTER(MlaSparseParams)]
+        L.fa_mla_sparse_workspace_bytes.argtypes = [_vp]
         L.fa_mla_sparse_workspace_bytes.restype = ctypes.c_int64
-        L.fa_mla_sparse_num_splits.argtypes = [ctypes.POINTER(MlaSparseParams)]
+        L.fa_mla_sparse_num_splits.argtypes = [_vp]
         L.fa_mla_sparse_num_splits.restype = ctypes.c_int32
         L.fa_mha_fwd.argtypes = [_vp] * 5 + [_i32] * 8 + [_vp]
         L.fa_mha_bwd.argtypes = [_vp] * 10 + [_i32] * 8 + [_vp]
@@ -514,11 +527,22 @@ def run_fwd_kvcache(params, stream=None, options=None):
         check(lib().fa_run_mha_fwd_kvcache_ex(ctypes.byref(params), ctypes.byref(options), s))
 
 
+def mla_cache_is_fp8(kv_cache) -> bool:
+    """a latent cache in the FP8 format of the two MLA calls: uint8 or float8_e4m3fn, 656 bytes a row"""
+    import torch
+
+    return kv_cache.dtype in (torch.uint8, torch.float8_e4m3fn) and kv_cache.shape[-1] == 656
+
+
 def mla_params(q, kv_cache, o, lse, cache_seqlens=None, kv_new=None, causal=False, num_splits=0, block_table=None, softmax_scale=None):
     """fa_mla_params for q (b, sq, h, 576), kv_cache (b, capacity, 1, 576) - or, with block_table (int32 (b, max_blocks)), a page pool (num_blocks,
-    page_block_size, 1, 576) - kv_new (b, s_new, 1, 576) and o (b, sq, h, 512) torch tensors with arbitrary batch / row / head strides"""
+    page_block_size, 1, 576) - kv_new (b, s_new, 1, 576) and o (b, sq, h, 512) torch tensors with arbitrary batch / row / head strides.  An FP8 cache
+    (uint8 / float8_e4m3fn, 656 wide) gives a MlaParamsV2 with kv_format = FA_MLA_KV_FP8_ROWS656."""
     b, sq, h, d_qk = q.shape
     p = MlaParams()
+    if mla_cache_is_fp8(kv_cache):      # a 1-byte dtype: the strides below are in bytes, as the format asks
+        p = MlaParamsV2()
+        p.kv_format = FA_MLA_KV_FP8_ROWS656
     p.q, p.kv_cache, p.o, p.lse = (t.data_ptr() for t in (q, kv_cache, o, lse))
     p.cache_seqlens = None if cache_seqlens is None else cache_seqlens.data_ptr()
     p.b, p.seqlen_q, p.seqlen_cache, p.h, p.d_qk, p.d_v = b, sq, kv_cache.shape[1], h, d_qk, o.shape[-1]
@@ -563,9 +587,13 @@ def run_mla_fwd_kvcache(params, stream=None):
 
 def mla_sparse_params(q, kv_cache, o, lse, indices, cache_seqlens=None, num_splits=0, block_table=None, softmax_scale=None):
     """fa_mla_sparse_params for q (b, sq, h, 576), kv_cache (b, capacity, 1, 576) - or, with block_table (int32 (b, max_blocks)), a page pool (num_blocks,
-    page_block_size, 1, 576) - indices int32 (b, sq, topk) with any batch / row strides, and o (b, sq, h, 512) torch tensors"""
+    page_block_size, 1, 576) - indices int32 (b, sq, topk) with any batch / row strides, and o (b, sq, h, 512) torch tensors.  An FP8 cache (uint8 /
+    float8_e4m3fn, 656 wide) gives a MlaSparseParamsV2 with kv_format = FA_MLA_KV_FP8_ROWS656."""
     b, sq, h, d_qk = q.shape
     p = MlaSparseParams()
+    if mla_cache_is_fp8(kv_cache):      # a 1-byte dtype: the strides below are in bytes, as the format asks
+        p = MlaSparseParamsV2()
+        p.kv_format = FA_MLA_KV_FP8_ROWS656
     p.q, p.kv_cache, p.o, p.lse, p.indices = (t.data_ptr() for t in (q, kv_cache, o, lse, indices))
     p.cache_seqlens = None if cache_seqlens is None else cache_seqlens.data_ptr()
     p.b, p.seqlen_q, p.seqlen_cache, p.h, p.d_qk, p.d_v = b, sq, kv_cache.shape[1], h, d_qk, o.shape[-1]

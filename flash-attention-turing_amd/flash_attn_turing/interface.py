@@ -548,6 +548,70 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, cache_seqlens=N
     return (out, lse) if return_softmax_lse else out
 
 
+MLA_FP8_ROW_BYTES = 656     # one FP8 latent row: 512 e4m3 codes, four fp32 scales (one per 128 codes), 64 rope elements of q's dtype
+
+
+def _mla_cache_is_fp8(kv_cache):
+    """the FP8 latent cache of the two MLA calls: uint8 or float8_e4m3fn AND 656 bytes a row (anything else is judged as a 16-bit cache)"""
+    return kv_cache.dtype in (torch.uint8, torch.float8_e4m3fn) and kv_cache.shape[-1] == MLA_FP8_ROW_BYTES
+
+
+def _check_mla_fp8_view(kv_cache):
+    """the kernels read and write an FP8 latent row with 16-byte accesses: a view they cannot address is refused, never copied"""
+    if kv_cache.stride(3) != 1:
+        raise ValueError("kv_cache: the last dimension of an FP8 latent cache must be contiguous")
+    if kv_cache.stride(0) % 16 != 0 or kv_cache.stride(1) % 16 != 0 or kv_cache.stride(1) < MLA_FP8_ROW_BYTES:
+        raise ValueError(f"kv_cache: the batch / page and row strides of an FP8 latent cache must be multiples of 16 bytes with rows at least 656 bytes apart, "
+                         f"got strides {tuple(kv_cache.stride())}")
+    if kv_cache.storage_offset() % 16 != 0 or (kv_cache.device.type != "meta" and kv_cache.data_ptr() % 16 != 0):
+        raise ValueError(f"kv_cache: an FP8 latent cache must start at a multiple of 16 bytes, got storage offset {kv_cache.storage_offset()}")
+
+
+def quantize_mla_kv_cache(kv):
+    """(..., 576) fp16 / bf16 latent rows -> (..., 656) uint8 rows of the FP8 latent cache, by the rule of the quantising append of flash_mla_with_kvcache.
+
+    Per 128-column tile g of the first 512 columns: amax_g = max |x| over the tile's finite elements (NaN and +-inf skipped, 0 if none),
+    scale_g = max(amax_g, 2^-24) / 448 (the correctly rounded fp32 quotient), code = e4m3_rne(clamp(float(x) / scale_g, -448, 448)); NaN stays NaN with
+    its sign (0x7f / 0xff), +-inf saturate to +-448.  Bytes 0 .. 511 the codes, 512 .. 527 the four fp32 scales (little endian), 528 .. 655 the 64 rope
+    elements copied bit for bit.  Plain torch: runs on any device."""
+    if not isinstance(kv, torch.Tensor) or kv.dtype not in (torch.float16, torch.bfloat16) or kv.dim() < 1 or kv.shape[-1] != 576:
+        raise ValueError("kv must be an fp16 / bf16 tensor (..., 576)")
+    lead = kv.shape[:-1]
+    x = kv[..., :512].float().reshape(*lead, 4, 128)
+    finite = torch.isfinite(x)
+    amax = torch.where(finite, x.abs(), torch.zeros_like(x)).amax(dim=-1, keepdim=True)
+    scale = torch.clamp(amax, min=2.0 ** -24) / 448.0
+    y = torch.clamp(x / scale, min=-448.0, max=448.0)      # (NaN passes through clamp)
+    nan = torch.isnan(y)
+    codes = torch.where(nan, torch.zeros_like(y), y).to(torch.float8_e4m3fn).view(torch.uint8)
+    sign = ((x.view(torch.int32) >> 24) & 0x80).to(torch.uint8)
+    codes = torch.where(nan, sign | 0x7F, codes)
+    out = torch.empty(*lead, MLA_FP8_ROW_BYTES, dtype=torch.uint8, device=kv.device)
+    out[..., :512] = codes.reshape(*lead, 512)
+    out[..., 512:528] = scale.reshape(*lead, 4).contiguous().view(torch.uint8).reshape(*lead, 16)
+    out[..., 528:] = kv[..., 512:].contiguous().view(torch.uint8).reshape(*lead, 128)
+    return out
+
+
+def dequantize_mla_kv_cache(kv8, dtype):
+    """(..., 656) uint8 / float8_e4m3fn rows of the FP8 latent cache -> (..., 576) rows of ``dtype`` (fp16 / bf16): what the MLA calls compute with.
+
+    kv[c] = round_to_dtype(fp32(code[c]) * scale[c // 128]) for c < 512 - the fp32 product rounded once, to nearest-even - and kv[512 + r] the stored rope
+    element.  flash_mla_with_kvcache / flash_mla_sparse_with_kvcache on an FP8 cache equal the same call on this tensor bit for bit.  Plain torch."""
+    if not isinstance(kv8, torch.Tensor) or kv8.dtype not in (torch.uint8, torch.float8_e4m3fn) or kv8.dim() < 1 or kv8.shape[-1] != MLA_FP8_ROW_BYTES:
+        raise ValueError("kv8 must be a uint8 / float8_e4m3fn tensor (..., 656)")
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"dtype must be torch.float16 or torch.bfloat16, got {dtype}")
+    raw = kv8.contiguous().view(torch.uint8)
+    lead = raw.shape[:-1]
+    codes = raw[..., :512].contiguous().view(torch.float8_e4m3fn).float().reshape(*lead, 4, 128)
+    scale = raw[..., 512:528].contiguous().view(torch.float32).reshape(*lead, 4, 1)
+    out = torch.empty(*lead, 576, dtype=dtype, device=kv8.device)
+    out[..., :512] = (codes * scale).to(dtype).reshape(*lead, 512)
+    out[..., 512:] = raw[..., 528:].contiguous().view(dtype).reshape(*lead, 64)
+    return out
+
+
 def flash_mla_with_kvcache(q, kv_cache, cache_seqlens, *, head_dim_v=512, kv_new=None, block_table=None, softmax_scale=None, causal=False, num_splits=0,
                            return_softmax_lse=False):
     """Multi-head latent attention (MLA) decode over a latent KV cache (DeepSeek-V2 / V3 / R1, Kimi K2; forward only).
@@ -561,6 +625,12 @@ def flash_mla_with_kvcache(q, kv_cache, cache_seqlens, *, head_dim_v=512, kv_new
     device, last dim contiguous), a page pool (num_blocks, page_block_size, 1, 576), page_block_size a multiple of 16, entries clamped
     min(uint32(entry), num_blocks - 1) as in flash_attn_with_kvcache.
     cache_seqlens: int32 tensor (batch,) on q's device, or a Python int (broadcast).
+    FP8 latent cache: a kv_cache of dtype uint8 or float8_e4m3fn AND 656 wide - (batch, capacity, 1, 656) or a pool (num_blocks, page_block_size, 1, 656) -
+    holds rows of 512 e4m3 codes, four fp32 scales (one per 128 codes) and the 64 rope elements in q's dtype (quantize_mla_kv_cache /
+    dequantize_mla_kv_cache state the format).  The call equals the same call on dequantize_mla_kv_cache(kv_cache, q.dtype) BIT FOR BIT, for every
+    num_splits; kv_new stays (batch, s_new, 1, 576) in q's dtype and is quantised into the cache by the rule of quantize_mla_kv_cache (whole 656-byte
+    rows), attention running over the quantised rows.  Batch / page and row strides and the storage offset must be multiples of 16 bytes.  Scales are
+    used as they are; precondition: every fp32(code) * scale is zero or a normal fp32 number.
     kv_new (keyword, optional): (batch, s_new, 1, 576), written INTO the cache at rows cache_seqlens[i] .. cache_seqlens[i] + s_new - 1 before
     attention runs; cache_seqlens is not updated (the caller advances it); rows at or past the capacity are dropped.
     In fp32 math over the visible keys, with L_i = cache_seqlens[i] (+ s_new): ``s_tj = (q_t . kv_j[0:576]) * softmax_scale``; key j is visible
@@ -576,7 +646,7 @@ def flash_mla_with_kvcache(q, kv_cache, cache_seqlens, *, head_dim_v=512, kv_new
     batch x ceil(seqlen_q * nheads / 64) workgroups).  As there, the query rows of a call share the reads of a key, and the value is the key: a
     non-finite element in columns 0 .. 511 of a row below L_i that ``causal`` hides from this query row but not from another row of the same
     64-row tile can make this row NaN (0 x NaN).
-    Out of scope, and without a keyword here: an FP8 latent cache, cu_seqlens_q, window_size, softcap, sinks, tree_mask, rotary inside the call, other
+    Out of scope, and without a keyword here: cu_seqlens_q, window_size, softcap, sinks, tree_mask, rotary inside the call, other
     head dims, any backward.  Wrong shapes, dtypes or values are a ValueError that names the argument.
     """
     for name, t in (("q", q), ("kv_cache", kv_cache)):
@@ -592,12 +662,15 @@ def flash_mla_with_kvcache(q, kv_cache, cache_seqlens, *, head_dim_v=512, kv_new
         raise ValueError(f"head_dim_v must be 512, got {head_dim_v!r}")
     if q.shape[1] < 1 or q.shape[2] < 1:
         raise ValueError(f"q needs seqlen_q >= 1 and nheads >= 1, got shape {tuple(q.shape)}")
-    if kv_cache.dtype != q.dtype:
-        raise ValueError(f"kv_cache must have q's dtype ({q.dtype}), got {kv_cache.dtype} (an FP8 latent cache is out of scope)")
+    fp8 = _mla_cache_is_fp8(kv_cache)
+    if not fp8 and kv_cache.dtype != q.dtype:
+        raise ValueError(f"kv_cache must have q's dtype ({q.dtype}), got {kv_cache.dtype} (an FP8 latent cache is uint8 / float8_e4m3fn rows of 656 bytes)")
     if kv_cache.shape[2] != 1:
         raise ValueError(f"kv_cache must have exactly one head (the latent row), got {kv_cache.shape[2]}")
-    if kv_cache.shape[3] != 576:
+    if not fp8 and kv_cache.shape[3] != 576:
         raise ValueError(f"kv_cache must be 576 wide, got {kv_cache.shape[3]}")
+    if fp8:
+        _check_mla_fp8_view(kv_cache)
     if kv_cache.device != q.device:
         raise ValueError("kv_cache must be on q's device")
     b = q.shape[0]
@@ -656,7 +729,9 @@ def flash_mla_sparse_with_kvcache(q, kv_cache, cache_seqlens, indices, *, head_d
     the non-causal flash_mla_with_kvcache call at cache_seqlens = n with num_splits = 1 (and with a forced num_splits when topk == capacity); the same
     list cut at L_i - seqlen_q + t + 1 per token gives those of its causal call.  num_splits: 0 = chosen by the library over this call's grid of
     batch x seqlen_q x ceil(nheads / 64) workgroups; the split runs over the slots of the list in multiples of 32.
-    Out of scope, and without a keyword here: kv_new (engines write the latent cache themselves), an FP8 latent cache, cu_seqlens_q, sinks, returning
+    An FP8 latent cache (uint8 / float8_e4m3fn, 656 wide: see flash_mla_with_kvcache) is read in place and gives the bits of the same call on
+    dequantize_mla_kv_cache(kv_cache, q.dtype).
+    Out of scope, and without a keyword here: kv_new (engines write the latent cache themselves), cu_seqlens_q, sinks, returning
     max logits, physical (pool-wide) indices, any backward.  Wrong shapes, dtypes or values are a ValueError that names the argument.
     """
     for name, t in (("q", q), ("kv_cache", kv_cache)):
@@ -672,12 +747,15 @@ def flash_mla_sparse_with_kvcache(q, kv_cache, cache_seqlens, indices, *, head_d
         raise ValueError(f"head_dim_v must be 512, got {head_dim_v!r}")
     if q.shape[1] < 1 or q.shape[2] < 1:
         raise ValueError(f"q needs seqlen_q >= 1 and nheads >= 1, got shape {tuple(q.shape)}")
-    if kv_cache.dtype != q.dtype:
-        raise ValueError(f"kv_cache must have q's dtype ({q.dtype}), got {kv_cache.dtype} (an FP8 latent cache is out of scope)")
+    fp8 = _mla_cache_is_fp8(kv_cache)
+    if not fp8 and kv_cache.dtype != q.dtype:
+        raise ValueError(f"kv_cache must have q's dtype ({q.dtype}), got {kv_cache.dtype} (an FP8 latent cache is uint8 / float8_e4m3fn rows of 656 bytes)")
     if kv_cache.shape[2] != 1:
         raise ValueError(f"kv_cache must have exactly one head (the latent row), got {kv_cache.shape[2]}")
-    if kv_cache.shape[3] != 576:
+    if not fp8 and kv_cache.shape[3] != 576:
         raise ValueError(f"kv_cache must be 576 wide, got {kv_cache.shape[3]}")
+    if fp8:
+        _check_mla_fp8_view(kv_cache)
     if kv_cache.device != q.device:
         raise ValueError("kv_cache must be on q's device")
     b, sq = q.shape[0], q.shape[1]

@@ -646,7 +646,8 @@ typedef struct fa_kvcache_options_v8 {      /* FA_PARAMS_INIT(o); then fa_..._ex
  * pages wholly past L_i and pages no sequence references never reach a result.
  * Errors, the argument named by fa_last_error: d_qk != 576 or d_v != 512 FA_ERR_BAD_HEADDIM, dtype FA_ERR_BAD_DTYPE, sizes / page_block_size /
  * softmax_scale / num_splits FA_ERR_BAD_SHAPE, pointers FA_ERR_NULL_POINTER, strides and alignment FA_ERR_BAD_STRIDE, the header FA_ERR_BAD_ABI.
- * b == 0 is FA_OK without a launch.  No FP8 latent cache, window, softcap, sinks, tree mask, rotary or ragged batch: the struct has no field for them. */
+ * b == 0 is FA_OK without a launch.  No window, softcap, sinks, tree mask, rotary or ragged batch: the struct has no field for them.  An FP8 latent
+ * cache is fa_mla_params_v2 below. */
 #define FA_HAS_MLA_KVCACHE 1
 typedef struct fa_mla_params {
     uint32_t struct_size;       /* sizeof(fa_mla_params) in the caller's translation unit */
@@ -695,7 +696,8 @@ typedef struct fa_mla_params {
  * rows = b * h * seqlen_q; the split runs over the slots [0, topk) in multiples of 32 (a forced count is at most topk / 32), the automatic one by the rule
  * of fa_kvcache_num_splits with topk in the place of seqlen_cache over this grid's b x seqlen_q x ceil(h / 64) workgroups.
  * Errors as for fa_mla_params; indices NULL (b > 0) FA_ERR_NULL_POINTER, topk / the index strides FA_ERR_BAD_SHAPE / FA_ERR_BAD_STRIDE naming them.
- * b == 0 is FA_OK without a launch.  No kv_new, FP8 latent cache, ragged batch, sinks or physical (pool-wide) indices: the struct has no field for them. */
+ * b == 0 is FA_OK without a launch.  No kv_new, ragged batch, sinks or physical (pool-wide) indices: the struct has no field for them.  An FP8 latent
+ * cache is fa_mla_sparse_params_v2 below. */
 #define FA_HAS_MLA_SPARSE_KVCACHE 1
 typedef struct fa_mla_sparse_params {
     uint32_t struct_size;       /* sizeof(fa_mla_sparse_params) in the caller's translation unit */
@@ -727,6 +729,93 @@ typedef struct fa_mla_sparse_params {
     int32_t page_block_size;
     int32_t num_blocks;
 } fa_mla_sparse_params;
+
+/* FP8 latent cache for both MLA calls (FA_HAS_MLA_FP8_KVCACHE; the cache of DeepSeek-V3.2 / FlashMLA's sparse decode, vLLM's fp8_ds_mla).  The _v2 structs
+ * are fa_mla_params / fa_mla_sparse_params with kv_format appended; the same entry points take either struct through the same pointer and tell them apart
+ * by struct_size (any other size stays FA_ERR_BAD_ABI).  FA_ABI_VERSION is unchanged.
+ * kv_format = FA_MLA_KV_16BIT: exactly the call of the first struct.  kv_format = FA_MLA_KV_FP8_ROWS656: kv_cache holds 656-byte latent rows and
+ * kv_cache_stride is in BYTES (batch / page and row strides and the pointer multiples of 16, row >= 656; the head stride is not read):
+ *   bytes 0 .. 511    code[c], OCP e4m3 (float8_e4m3fn), columns 0 .. 511 of the latent row
+ *   bytes 512 .. 527  scale[g], four fp32 (little endian), g = c / 128
+ *   bytes 528 .. 655  columns 512 .. 575 (the rope part), 64 elements of `dtype`, unscaled
+ * The row means kv[c] = round_to_dtype(fp32(code[c]) * scale[c / 128]) for c < 512 - the fp32 product rounded once, to nearest-even - and kv[512 + r] =
+ * the stored rope element; everything else is the contract of the 16-bit call over kv, and the two calls agree BIT FOR BIT: a call on an FP8 cache
+ * equals the 16-bit call on the dequantised cache in o and lse for every split count.  A NaN code (0x7f / 0xff) is NaN.  Scales are used as they are and
+ * are not checked; precondition: every fp32(code) * scale is zero or a normal fp32 number (for fp16 a product beyond 65504 becomes inf by the rounding).
+ * Rows at or past L_i, pages wholly past L_i or unreferenced and (sparse) whatever no valid slot names are never read: they may hold 0xff bytes.
+ * kv_new (dense call) stays (b, seqlen_new, 576) of `dtype` with kv_new_stride in elements and is QUANTISED into whole 656-byte rows, drop and clamp rules
+ * unchanged; attention runs over the quantised rows.  Per tile g of a new row: amax_g = max |x_c| over the tile's finite elements (0 if none),
+ * scale_g = max(amax_g, 2^-24) / 448 (the correctly rounded fp32 quotient), code[c] = e4m3_rne(clamp(float(x_c) / scale_g, -448, 448)) with NaN kept
+ * (0x7f | sign) and +-inf saturating; the rope part is copied bit for bit.
+ * Workspace and split are those of kv_format = 0.  Errors: an unknown kv_format or a non-zero reserved2_ FA_ERR_BAD_SHAPE naming the field; a stride or
+ * pointer of the FP8 cache that is no multiple of 16 bytes FA_ERR_BAD_STRIDE. */
+#define FA_HAS_MLA_FP8_KVCACHE 1
+#define FA_MLA_KV_16BIT 0
+#define FA_MLA_KV_FP8_ROWS656 1
+typedef struct fa_mla_params_v2 {
+    uint32_t struct_size;       /* sizeof(fa_mla_params_v2) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const void* q;
+    void* kv_cache;
+    const void* kv_new;
+    void* o;
+    float* lse;
+    const int32_t* cache_seqlens;
+    int32_t b;
+    int32_t seqlen_q;
+    int32_t seqlen_cache;
+    int32_t seqlen_new;
+    int32_t h;
+    int32_t d_qk;
+    int32_t d_v;
+    int32_t dtype;
+    int32_t is_causal;
+    int32_t num_splits;
+    float softmax_scale;
+    int32_t reserved_;
+    fa_strides q_stride, kv_cache_stride, kv_new_stride, o_stride;
+    void* workspace;
+    int64_t workspace_bytes;
+    const int32_t* block_table;
+    int64_t block_table_stride;
+    int32_t page_block_size;
+    int32_t num_blocks;
+    int32_t kv_format;          /* FA_MLA_KV_16BIT / FA_MLA_KV_FP8_ROWS656 */
+    int32_t reserved2_;         /* 0 */
+} fa_mla_params_v2;
+
+typedef struct fa_mla_sparse_params_v2 {
+    uint32_t struct_size;       /* sizeof(fa_mla_sparse_params_v2) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const void* q;
+    const void* kv_cache;
+    void* o;
+    float* lse;
+    const int32_t* cache_seqlens;
+    const int32_t* indices;
+    int32_t b;
+    int32_t seqlen_q;
+    int32_t seqlen_cache;
+    int32_t topk;
+    int32_t h;
+    int32_t d_qk;
+    int32_t d_v;
+    int32_t dtype;
+    int32_t num_splits;
+    float softmax_scale;
+    int64_t reserved_;
+    fa_strides q_stride, kv_cache_stride, o_stride;
+    int64_t indices_batch_stride;
+    int64_t indices_row_stride;
+    void* workspace;
+    int64_t workspace_bytes;
+    const int32_t* block_table;
+    int64_t block_table_stride;
+    int32_t page_block_size;
+    int32_t num_blocks;
+    int32_t kv_format;          /* FA_MLA_KV_16BIT / FA_MLA_KV_FP8_ROWS656 */
+    int32_t reserved2_;         /* 0 */
+} fa_mla_sparse_params_v2;
 
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
@@ -799,7 +888,8 @@ int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* params, const fa_kvcac
 int32_t fa_kvcache_row_tile_ex(const fa_kvcache_params* params, const fa_kvcache_options* options);
 
 /* ---- MLA decode over a latent KV cache (fa_mla_params above) ----------------------------------- */
-/* Append (if kv_new), split-KV attention, and the combine of the splits: up to three launches on `stream`, no host synchronisation. */
+/* Append (if kv_new), split-KV attention, and the combine of the splits: up to three launches on `stream`, no host synchronisation.  The three entry
+ * points take a fa_mla_params or (cast to it) a fa_mla_params_v2, told apart by struct_size. */
 int fa_run_mla_fwd_kvcache(const fa_mla_params* params, void* stream);
 /* Host-only, like fa_kvcache_workspace_bytes / fa_kvcache_num_splits: the bytes the split the library chooses (or num_splits) needs, the
  * `workspace` fields ignored; and the splits the launch would use, the workspace fields included (NULL / 0 -> 1).  Negative = error code. */
@@ -807,7 +897,8 @@ int64_t fa_mla_workspace_bytes(const fa_mla_params* params);
 int32_t fa_mla_num_splits(const fa_mla_params* params);
 
 /* ---- sparse MLA decode over a latent KV cache (fa_mla_sparse_params above) ------------------- */
-/* Split attention over the token lists, and the combine of the splits: up to two launches on `stream`, no host synchronisation. */
+/* Split attention over the token lists, and the combine of the splits: up to two launches on `stream`, no host synchronisation.  The three entry points
+ * take a fa_mla_sparse_params or (cast to it) a fa_mla_sparse_params_v2, told apart by struct_size. */
 int fa_run_mla_sparse_fwd_kvcache(const fa_mla_sparse_params* params, void* stream);
 /* Host-only, like fa_mla_workspace_bytes / fa_mla_num_splits.  Negative = error code, exactly those of the launch. */
 int64_t fa_mla_sparse_workspace_bytes(const fa_mla_sparse_params* params);

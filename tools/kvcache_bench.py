@@ -73,6 +73,9 @@ b * L * 1152 B / time as a fraction of 6.3 TB/s; (B, B2) the yardstick, the head
 (1024 B per key: nearly the same bytes, fewer FLOPs), timed TWICE so that the scatter of one thing measured twice in the same run stands next to
 A / B; interleaved, medians.
 
+--mla --kv-dtype fp8 / --mla-sparse --kv-dtype fp8 measure the two MLA calls over an FP8 latent cache (656-byte rows) on the same grids: per point the FP8
+call against the same call over the dequantised bf16 cache (the two give the same bits: asserted), the bf16 call timed twice as its own noise figure;
+interleaved in one process, medians (profiles/kvcache_mla_fp8_bench.log).
 --mla-sparse measures sparse MLA decode (flash_mla_sparse_with_kvcache): bf16, seqlen_q 1, h in {16, 128}, b in {1, 8, 64}, topk 2048, pages of 64 (--paged P
 replaces the page size).  The yardstick is the DENSE flash_mla_with_kvcache call at L = topk - the same rows, the same bytes - timed TWICE (B, B2: its own
 noise figure).  Against it, interleaved in one process: (i) the identity list 0 .. topk - 1 on the same caches; and per L in {32k, 128k} (--length replaces
@@ -935,6 +938,101 @@ def run_mla_sparse(lengths, pages, rounds):
         yield from run_mla_sparse_point(b, h, tuple(lengths or (32768, 131072)), (pages or [64])[0], rounds)
 
 
+def _mla_fp8_cache(shape_lead, dt, dev, seed):
+    """(an FP8 latent cache (*lead, 1, 656) of random NaN-free codes under tile scales in [2^-8, 2^-6] with N(0, 1) rope elements, its dequantised 16-bit
+    twin (*lead, 1, 576)), built a million rows at a time to bound the temporaries"""
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    total = shape_lead[0] * shape_lead[1]
+    c8 = torch.empty(total, 656, device=dev, dtype=torch.uint8)
+    c16 = torch.empty(total, 576, device=dev, dtype=dt)
+    for r0 in range(0, total, 1 << 20):
+        rows = min(1 << 20, total - r0)
+        codes = torch.randint(0, 256, (rows, 512), device=dev, generator=gen, dtype=torch.int16)
+        codes = torch.where((codes & 0x7F) == 0x7F, codes ^ 0x41, codes).to(torch.uint8)
+        scale = torch.exp2(torch.rand(rows, 4, device=dev, generator=gen) * 2.0 - 8.0)
+        rope = torch.randn(rows, 64, device=dev, generator=gen).to(dt)
+        c8[r0:r0 + rows] = torch.cat([codes, scale.view(torch.uint8).view(rows, 16), rope.view(torch.uint8).view(rows, 128)], dim=-1)
+        c16[r0:r0 + rows] = F.dequantize_mla_kv_cache(c8[r0:r0 + rows], dt)
+    return c8.view(*shape_lead, 1, 656), c16.view(*shape_lead, 1, 576)
+
+
+def run_mla_fp8_point(b, h, L, page, rounds):
+    """(A) flash_mla_with_kvcache over an FP8 latent cache (656-byte rows), (B, B2) the same call over the dequantised bf16 cache, twice; interleaved.  The two
+    give the same bits (asserted on the first cache)."""
+    dev, dt = torch.device("cuda:0"), torch.bfloat16
+    b8, b16 = b * L * 656, b * L * 576 * 2
+    n = _rotation(b8 + b16, b8)
+    sets = []
+    for i in range(n):
+        if page:
+            nb = b * L // page
+            table = torch.randperm(nb, generator=torch.Generator().manual_seed(i)).view(b, L // page).to(device=dev, dtype=torch.int32)
+            sets.append(_mla_fp8_cache((nb, page), dt, dev, i) + (table,))
+        else:
+            sets.append(_mla_fp8_cache((b, L), dt, dev, i) + (None,))
+    q = torch.randn(b, 1, h, 576, device=dev, dtype=dt)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    fp8 = lambda i: F.flash_mla_with_kvcache(q, sets[i][0], cs, block_table=sets[i][2])
+    ref = lambda i: F.flash_mla_with_kvcache(q, sets[i][1], cs, block_table=sets[i][2])
+    assert _bits_equal(fp8(0), ref(0)), "the FP8 call is not the 16-bit call on the dequantised cache"
+    torch.cuda.synchronize()
+    ms = _interleaved({"bf16": ref, "fp8": fp8, "bf16_again": ref}, n, rounds)
+    p = capi.mla_params(q, sets[0][0], torch.empty(b, 1, h, 512, device=dev, dtype=dt), torch.empty(b, h, 1, device=dev), cs, block_table=sets[0][2])
+    ws = capi.mla_workspace_bytes(p)
+    n_split = max(1, ws and capi.mla_num_splits(_with_ws(p, ws)))
+    del sets
+    torch.cuda.empty_cache()
+    lo, hi = sorted((ms["bf16"], ms["bf16_again"]))
+    return dict(mla_fp8=True, b=b, h=h, L=L, seqlen_q=1, dtype="bfloat16", page_block_size=page or 0, caches_rotated=n, kv_gb_fp8=round(b8 / 1e9, 3),
+                kv_gb_bf16=round(b16 / 1e9, 3), n_split=n_split, ms_fp8=round(ms["fp8"], 5), ms_bf16=round(ms["bf16"], 5), ms_bf16_again=round(ms["bf16_again"], 5),
+                frac_of_6p3_fp8=round(b8 / (ms["fp8"] * 1e-3) / HBM_ACHIEVABLE, 3), frac_of_6p3_bf16=round(b16 / (ms["bf16"] * 1e-3) / HBM_ACHIEVABLE, 3),
+                fp8_over_bf16=round(ms["fp8"] / ms["bf16"], 4), bf16_again_over_bf16=round(ms["bf16_again"] / ms["bf16"], 4), inside_scatter=bool(lo <= ms["fp8"] <= hi))
+
+
+def run_mla_fp8(lengths, pages, rounds):
+    for h, b, L in itertools.product((16, 128), (1, 8, 64), tuple(lengths or (4096, 32768, 131072))):
+        for page in ([None] + list(pages or [])):
+            yield run_mla_fp8_point(b, h, L, page, rounds)
+
+
+def run_mla_sparse_fp8_point(b, h, lengths, page, rounds, topk=2048):
+    """per L, sorted and unsorted random lists of topk positions over one paged cache of L rows: the sparse call over the FP8 cache against the same call over
+    the dequantised bf16 cache, the bf16 sorted arm of the first L timed twice; interleaved.  The two give the same bits (asserted per L)."""
+    dev, dt = torch.device("cuda:0"), torch.bfloat16
+    n_lists = 4
+    gen = torch.Generator().manual_seed(1234 + b + h)
+    q = torch.randn(b, 1, h, 576, device=dev, dtype=dt)
+    arms, keep = {}, []
+    for L in lengths:
+        nb = b * L // page
+        table = torch.randperm(nb, generator=torch.Generator().manual_seed(1000 + L)).view(b, L // page).to(device=dev, dtype=torch.int32)
+        c8, c16 = _mla_fp8_cache((nb, page), dt, dev, L)
+        pos = torch.stack([torch.stack([torch.randperm(L, generator=gen)[:topk] for _ in range(b)]) for _ in range(n_lists)]).to(torch.int32).unsqueeze(2)
+        srt, uns = pos.sort(-1).values.to(dev), pos.to(dev)
+        csL = torch.full((b,), L, dtype=torch.int32, device=dev)
+        keep.append((c8, c16, table, srt, uns, csL))
+        for name, cache in (("bf16", c16), ("fp8", c8)):
+            arms[f"{name}_sorted_L{L}"] = lambda i, cache=cache, table=table, srt=srt, csL=csL: F.flash_mla_sparse_with_kvcache(q, cache, csL, srt[i % n_lists], block_table=table)
+            arms[f"{name}_unsorted_L{L}"] = lambda i, cache=cache, table=table, uns=uns, csL=csL: F.flash_mla_sparse_with_kvcache(q, cache, csL, uns[i % n_lists], block_table=table)
+        assert _bits_equal(arms[f"fp8_unsorted_L{L}"](0), arms[f"bf16_unsorted_L{L}"](0)), "the FP8 call is not the 16-bit call on the dequantised cache"
+    first = f"bf16_sorted_L{lengths[0]}"
+    arms["bf16_again"] = arms[first]
+    torch.cuda.synchronize()
+    ms = _interleaved(arms, n_lists, rounds)
+    lo, hi = sorted((ms[first], ms["bf16_again"]))
+    del keep
+    torch.cuda.empty_cache()
+    return dict(mla_sparse_fp8=True, b=b, h=h, topk=topk, seqlen_q=1, dtype="bfloat16", page_block_size=page, lists_rotated=n_lists,
+                read_mb_fp8=round(b * topk * 656 / 1e6, 2), read_mb_bf16=round(b * topk * 1152 / 1e6, 2), ms={k: round(v, 5) for k, v in ms.items()},
+                bf16_spread=round(hi / lo, 4),
+                fp8_over_bf16={k[4:]: round(ms[k] / ms["bf16" + k[3:]], 4) for k in ms if k.startswith("fp8_")})
+
+
+def run_mla_sparse_fp8(lengths, pages, rounds):
+    for h, b in itertools.product((16, 128), (1, 8, 64)):
+        yield run_mla_sparse_fp8_point(b, h, tuple(lengths or (32768, 131072)), (pages or [64])[0], rounds)
+
+
 def _baseline_lib(path):
     L = ctypes.CDLL(os.path.abspath(path))
     L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
@@ -1035,11 +1133,11 @@ def main():
                 print(json.dumps(line), flush=True)
             return
         if a.mla_sparse:
-            for line in run_mla_sparse(a.length, a.paged, a.rounds):
+            for line in (run_mla_sparse_fp8 if a.kv_dtype == "fp8" else run_mla_sparse)(a.length, a.paged, a.rounds):
                 print(json.dumps(line), flush=True)
             return
         if a.mla:
-            for line in run_mla(a.length, a.paged, a.rounds):
+            for line in (run_mla_fp8 if a.kv_dtype == "fp8" else run_mla)(a.length, a.paged, a.rounds):
                 print(json.dumps(line), flush=True)
             return
         if a.prefill:
