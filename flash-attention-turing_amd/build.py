@@ -48,7 +48,7 @@ EXTRA_FLAGS = {"fa_fwd_pp16.hip": ["-fno-slp-vectorize"], "fa_bwd_dq16.hip": ["-
                "fa_fwd_kvcache_mla_sparse.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"],
                # fa_fwd_kvcache_mla_fp8.hip: both bodies over the FP8 latent cache - only the staging differs (24 registers in place of 36), the same flag
                "fa_fwd_kvcache_mla_fp8.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"]}
-HIP_HEADERS = ["fa_device.hpp", "fa_params.hpp", "fa_bwd_dkdv_common.hpp", "fa_kvcache_quant.hpp", "fa_kvcache_attn.hpp", "fa_kvcache_kernels.hpp", "fa_kvcache_launch.hpp", "fa_kvcache_rotary.hpp", os.path.join(INCLUDE, "flash_attn_gfx950.h")]
+HIP_HEADERS = ["fa_device.hpp", "fa_params.hpp", "fa_bwd_dkdv_common.hpp", "fa_kvcache_quant.hpp", "fa_kvcache_attn.hpp", "fa_kvcache_kernels.hpp", "fa_kvcache_launch.hpp", "fa_kvcache_rotary.hpp", "fa_kvcache_stage_debug.hpp", os.path.join(INCLUDE, "flash_attn_gfx950.h")]
 # -amdgpu-mfma-vgpr-form: builtin MFMAs keep their result in VGPRs even in kernels that may use the
 # accumulator half of the register file (the dK/dV kernel parks its 128 long-lived accumulator
 # registers in AGPRs through LP<T>::mfma_agpr); without it hipcc selects the AGPR form for every MFMA
@@ -83,14 +83,22 @@ def _write_stamp(target, stamp_value):
         f.write(stamp_value)
 
 
-# Debug builds of the library for tests/test_dma_protocol_gpu.py (round 5): the LDS-DMA protocols of fa_fwd_pp16 and fa_bwd_dkdv16 under adversarial
-# timing.  Only the two sources that carry the switches are recompiled; everything else is the product's objects.  The product's ISA does not change.
-DEBUG_SOURCES = ["fa_fwd_pp16.hip", "fa_bwd_dkdv16.hip"]
+# Debug builds of the library for tests/test_dma_protocol_gpu.py and tests/test_stage_protocol_gpu.py: every kernel in which one wave reads LDS bytes another wave put
+# there, under adversarial timing.  A variant maps each source it REBUILDS to the switches that source gets (with the file's EXTRA_FLAGS); every other source is the
+# product's object.  The product's ISA does not change.
+_DMA_LATE = {"fa_fwd_pp16.hip": ["-DFA_PP16_DMA_DEBUG=1"], "fa_bwd_dkdv16.hip": ["-DFA_KV16_DMA_DEBUG=1"], "fa_fwd_pp.hip": ["-DFA_PP_DMA_DEBUG=1"],
+             "fa_bwd.hip": ["-DFA_BWD32_DMA_DEBUG=1"], "fa_bwd_dq16.hip": ["-DFA_DQ16_DMA_DEBUG=1"]}
+_DMA_SLEEPY = {s: [f[0][:-1] + "2"] for s, f in _DMA_LATE.items()}
+# the 64-row KV-cache bodies: four waves stage a quarter of a step each through registers into one of two LDS stages (fa_kvcache_stage_debug.hpp)
+STAGE_SOURCES = ["fa_fwd_kvcache_prefill.hip", "fa_fwd_kvcache_mla.hip", "fa_fwd_kvcache_mla_sparse.hip", "fa_fwd_kvcache_mla_fp8.hip"]
 DEBUG_VARIANTS = {
-    "dma_late": ["-DFA_PP16_DMA_DEBUG=1", "-DFA_KV16_DMA_DEBUG=1"],          # every request issued directly in front of the wait that retires it
-    "dma_sleepy": ["-DFA_PP16_DMA_DEBUG=2", "-DFA_KV16_DMA_DEBUG=2"],        # group B / waves 4-7 sleep ~4000 cycles in front of every request
-    "dma_racy": ["-DFA_PP16_ROLE_DMA=0", "-DFA_PP16_RACY=1"],                # the documented WRONG counted-wait form of round 4, normal timing
-    "dma_racy_late": ["-DFA_PP16_ROLE_DMA=0", "-DFA_PP16_RACY=1", "-DFA_PP16_DMA_DEBUG=1"],      # ... under late issue: must FAIL
+    "dma_late": _DMA_LATE,                  # every request issued directly in front of the wait that retires it
+    "dma_sleepy": _DMA_SLEEPY,              # group B / waves 4-7 sleep ~4000 cycles in front of every request
+    "dma_racy": {"fa_fwd_pp16.hip": ["-DFA_PP16_ROLE_DMA=0", "-DFA_PP16_RACY=1"]},          # the documented WRONG counted-wait form of round 4, normal timing
+    "dma_racy_late": {"fa_fwd_pp16.hip": ["-DFA_PP16_ROLE_DMA=0", "-DFA_PP16_RACY=1", "-DFA_PP16_DMA_DEBUG=1"]},       # ... under late issue: must FAIL
+    "stage_slow_reader": {s: ["-DFA_KVC_STAGE_DEBUG=1"] for s in STAGE_SOURCES},            # in step n wave n % 4 sleeps in front of its reads of the stage
+    "stage_slow_writer": {s: ["-DFA_KVC_STAGE_DEBUG=2"] for s in STAGE_SOURCES},            # in step n wave (n + 1) % 4 sleeps in front of its writes to the next stage
+    "stage_racy_slow_writer": {s: ["-DFA_KVC_STAGE_RACY=1", "-DFA_KVC_STAGE_DEBUG=2"] for s in STAGE_SOURCES},     # the barrier in FRONT of the writes: must FAIL
 }
 DEBUG_DIR = os.path.join(CSRC, "debug")
 
@@ -186,38 +194,50 @@ def build_kernels(force=False):
     return LIB_PATH
 
 
+def debug_compile_command(source, flags, out, assembly=False):
+    """the hipcc line of one (variant, rebuilt source) pair: the product's line of that source plus the variant's switches; assembly: device assembly instead of an object"""
+    cmd = [hipcc_path()] + HIPCC_FLAGS + EXTRA_FLAGS.get(source, []) + list(flags) + ["-I", CSRC, "-I", INCLUDE]
+    cmd += ["-Wno-unused-command-line-argument", "--cuda-device-only", "-S"] if assembly else ["-c"]
+    return cmd + [os.path.join(CSRC, source), "-o", out]
+
+
 def build_debug_variants(force=False):
-    """csrc/debug/libfa_<variant>.so: the product library with DEBUG_SOURCES rebuilt under a variant's switches (needs build_kernels() first)"""
+    """csrc/debug/libfa_<variant>.so: the product library with the variant's sources rebuilt under its switches (needs build_kernels() first)"""
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
     hdrs = [h if os.path.isabs(h) else os.path.join(CSRC, h) for h in HIP_HEADERS]
     base = _digest(srcs + hdrs, " ".join(HIPCC_FLAGS) + repr(sorted(EXTRA_FLAGS.items())))
     os.makedirs(DEBUG_DIR, exist_ok=True)
-    todo = [(n, f) for n, f in DEBUG_VARIANTS.items() if force or _stale(debug_library_path(n), base + repr(f))]
+    todo = [(n, f) for n, f in DEBUG_VARIANTS.items() if force or _stale(debug_library_path(n), base + repr(sorted(f.items())))]
     if not todo:
         print("[build] debug variants up to date")
         return
     # the variants link the PRODUCT's objects of every source they do not rebuild: an up-to-date library whose objects were cleaned (or never shipped) is rebuilt first
-    missing = [s for s in HIP_SOURCES if s not in DEBUG_SOURCES and not os.path.exists(os.path.join(CSRC, s[:-4] + ".o"))]
+    needed = {s for _, f in todo for s in HIP_SOURCES if s not in f}
+    missing = [s for s in HIP_SOURCES if s in needed and not os.path.exists(os.path.join(CSRC, s[:-4] + ".o"))]
     if missing:
         print(f"[build] product objects missing ({', '.join(missing)}): rebuilding the library before the debug variants")
         build_kernels(force=True)
     t0 = time.time()
-    procs = []
-    for n, flags in todo:
-        for s in DEBUG_SOURCES:
-            o = os.path.join(DEBUG_DIR, f"{n}_{s[:-4]}.o")
-            cmd = [hipcc_path()] + HIPCC_FLAGS + EXTRA_FLAGS.get(s, []) + flags + ["-I", CSRC, "-I", INCLUDE, "-c", os.path.join(CSRC, s), "-o", o]
-            procs.append(subprocess.Popen(cmd))
-    for p in procs:
-        if p.wait() != 0:
-            raise RuntimeError("hipcc failed (debug variant)")
-    for n, flags in todo:
-        objs = [os.path.join(DEBUG_DIR, f"{n}_{s[:-4]}.o") if s in DEBUG_SOURCES else os.path.join(CSRC, s[:-4] + ".o") for s in HIP_SOURCES]
+    jobs = [debug_compile_command(s, flags, os.path.join(DEBUG_DIR, f"{n}_{s[:-4]}.o")) for n, f in todo for s, flags in f.items()]
+    width = max(1, min(len(jobs), int(os.environ.get("MAX_JOBS", "0")) or os.cpu_count() or 1))      # (the MLA sources take minutes each: no more compilers than cores)
+    running = []
+    try:
+        while jobs or running:
+            while jobs and len(running) < width:
+                running.append(subprocess.Popen(jobs.pop(0)))
+            p = running.pop(0)
+            if p.wait() != 0:
+                raise RuntimeError("hipcc failed (debug variant)")
+    finally:
+        for p in running:
+            p.wait()
+    for n, f in todo:
+        objs = [os.path.join(DEBUG_DIR, f"{n}_{s[:-4]}.o") if s in f else os.path.join(CSRC, s[:-4] + ".o") for s in HIP_SOURCES]
         _run([hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", debug_library_path(n)] + objs)
-        _write_stamp(debug_library_path(n), base + repr(flags))
-        for s in DEBUG_SOURCES:
+        _write_stamp(debug_library_path(n), base + repr(sorted(f.items())))
+        for s in f:
             os.remove(os.path.join(DEBUG_DIR, f"{n}_{s[:-4]}.o"))
-    print(f"[build] {len(todo)} debug variant(s) built in {time.time() - t0:.1f}s")
+    print(f"[build] {len(todo)} debug variant(s), {sum(len(f) for _, f in todo)} compile(s), built in {time.time() - t0:.1f}s")
 
 
 def build_torch_module(force=False):
@@ -250,7 +270,7 @@ def build_torch_module(force=False):
 
 
 def build_all(force=False, torch_module=True, debug_variants=True):
-    """debug_variants: the four test builds of tests/test_dma_protocol_gpu.py (csrc/debug/, ~8 extra compiles; never packaged).  An in-tree developer / CI build wants
+    """debug_variants: the test builds of tests/test_dma_protocol_gpu.py and tests/test_stage_protocol_gpu.py (csrc/debug/, 24 extra compiles; never packaged).  An in-tree developer / CI build wants
     them (the GPU suite loads them), an installation does not: setup.py and `build.py --no-debug` leave them out."""
     build_kernels(force)
     if debug_variants:
@@ -263,7 +283,7 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--force", action="store_true")
     ap.add_argument("--no-torch", action="store_true", help="only build the C-ABI kernel library")
-    ap.add_argument("--no-debug", action="store_true", help="skip the test builds of csrc/debug/ (tests/test_dma_protocol_gpu.py needs them)")
+    ap.add_argument("--no-debug", action="store_true", help="skip the test builds of csrc/debug/ (tests/test_dma_protocol_gpu.py and tests/test_stage_protocol_gpu.py need them)")
     a = ap.parse_args()
     build_all(a.force, not a.no_torch, not a.no_debug)
     sys.exit(0)

@@ -100,6 +100,13 @@ template <typename T, int D, bool CAUSAL>
 #ifndef FA_DQ_STAGGER_DMA
 #define FA_DQ_STAGGER_DMA 1
 #endif
+// FA_BWD32_DMA_DEBUG (test builds only, tests/test_dma_protocol_gpu.py; the product is 0 and its ISA does not change): adversarial timing for the LDS-DMA of both
+// 32x32x16 kernels of this file - the K / V double buffer of fa_bwd_dq_kernel and the Q / dO ring of fa_bwd_dkdv_kernel.
+//   1 = LATE ISSUE: the next tile's request goes out directly in front of the vmcnt(0) that retires it (the end of the tile body / of the iteration), in all eight waves;
+//   2 = SLEEPY: waves 4-7 sleep ~4000 cycles (s_sleep 64, more than a tile period) in front of every request of the loop.
+#ifndef FA_BWD32_DMA_DEBUG
+#define FA_BWD32_DMA_DEBUG 0
+#endif
 #ifndef FA_DQ_NO_UNROLL
 #define FA_DQ_NO_UNROLL 0
 #endif
@@ -280,7 +287,12 @@ __global__ __launch_bounds__(kDqThreads, FA_DQ_MIN_WAVES(D)) void fa_bwd_dq_kern
         // theirs after the first 32-key half below, while waves 0-3 (which issue here) are in their MFMAs, instead of all eight at once
         const bool wave_active = !CAUSAL || (n0 <= wave_q_hi + delta);
         const bool dma_late = FA_DQ_STAGGER_DMA && wave >= 4 && wave_active;       // (a wave that skips this tile issues at once)
+#if FA_BWD32_DMA_DEBUG == 2
+        if (t + 1 < n_tiles && !dma_late && wave >= 4) asm volatile("s_sleep 64" ::: "memory");
+#endif
+#if FA_BWD32_DMA_DEBUG != 1
         if (t + 1 < n_tiles && !dma_late) dma_tiles(t + 1, BUF ^ 1);
+#endif
         if (wave_active) {
             // Masking is 2 VALU per score element (compare with an immediate + select), not 4: the key index of
             // element (bi, r) is n0 + 32*bi + (r&3) + 8*(r>>2) + 4*hi, so everything lane- or tile-dependent
@@ -327,7 +339,12 @@ __global__ __launch_bounds__(kDqThreads, FA_DQ_MIN_WAVES(D)) void fa_bwd_dq_kern
                         sacc[r] = pv * (dpacc[r] - dsum);
                     }
                 }
+#if FA_BWD32_DMA_DEBUG == 2
+                if (bi == 0 && dma_late && t + 1 < n_tiles) asm volatile("s_sleep 64" ::: "memory");
+#endif
+#if FA_BWD32_DMA_DEBUG != 1
                 if (bi == 0 && dma_late && t + 1 < n_tiles) dma_tiles(t + 1, BUF ^ 1);
+#endif
                 // dQ^T (D x 32 queries) += K^T (D x 32 keys) * dS^T (32 keys x 32 queries)
 #pragma unroll
                 for (int half = 0; half < 2; ++half) {
@@ -343,6 +360,10 @@ __global__ __launch_bounds__(kDqThreads, FA_DQ_MIN_WAVES(D)) void fa_bwd_dq_kern
                 }
             }
         }
+#if FA_BWD32_DMA_DEBUG == 1
+        (void)dma_late;
+        if (t + 1 < n_tiles) dma_tiles(t + 1, BUF ^ 1);
+#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile t+1 have landed
     };
     {
@@ -589,9 +610,13 @@ __global__ __launch_bounds__(kKvThreads, FA_KV_MIN_WAVES(D)) void fa_bwd_dkdv_ke
         FA_LDS char* sbuf = stat + buf * STATB;
         const bool more = (it + 1 < n_iters);
         FA_KV_STAMP(5);                                     // (loop edge + barrier exit)
+#if FA_BWD32_DMA_DEBUG != 1
         if (more && (!FA_KV_STAGGER_DMA || qh == 0)) issue_tile(buf ^ 1);          // ring slot buf^1 was last read in iteration it-1
+#endif
         const float st_next = load_stat(more);
+#if FA_BWD32_DMA_DEBUG != 1
         if (!FA_KV_STAGGER_DMA && more) pf_advance();
+#endif
         FA_KV_STAMP(0);                                     // DMA issue
 
         // wave-level causal skip: all 32 rows of this wave's half are above the diagonal for all its 32 keys
@@ -633,10 +658,15 @@ __global__ __launch_bounds__(kKvThreads, FA_KV_MIN_WAVES(D)) void fa_bwd_dkdv_ke
                 dpacc = LP<T>::mfma(da, vf, dpacc);                 // dP = dO V^T
             }
             FA_KV_STAMP(1);                                 // S / dP MFMAs
+#if FA_BWD32_DMA_DEBUG == 2
+            if (FA_KV_STAGGER_DMA && more && qh == 1) asm volatile("s_sleep 64" ::: "memory");
+#endif
+#if FA_BWD32_DMA_DEBUG != 1
             if constexpr (FA_KV_STAGGER_DMA) {    // waves 4-7 request their pieces HERE, while waves 0-3 are still in their S / dP MFMAs
                 if (more && qh == 1) issue_tile(buf ^ 1);
                 if (more) pf_advance();
             }
+#endif
             f32x16 pacc;
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
@@ -683,6 +713,9 @@ __global__ __launch_bounds__(kKvThreads, FA_KV_MIN_WAVES(D)) void fa_bwd_dkdv_ke
             }
         }
         FA_KV_STAMP(3);                                     // dV / dK MFMAs
+#if FA_BWD32_DMA_DEBUG == 1
+            if (more) { issue_tile(buf ^ 1); pf_advance(); }    // (the statistics load at the top of the iteration read the cursor before it moves, as in the product)
+#endif
             if (more && wave < 2) store_stat(st_next, buf ^ 1);
             asm volatile("" :: "v"(st_next));               // consumed on every path: hipcc never has to guard the register at the loop top
             // (timing-only ablations, profiles/r2_bwd_dkdv_lds_ab.log: without this wait -0.2 %, without wait AND barrier -5..-6 %)

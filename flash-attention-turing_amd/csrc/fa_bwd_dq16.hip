@@ -29,6 +29,12 @@ constexpr int kDq16BlockM = 256;
 #ifndef FA_DQ16_STAGGER_DMA
 #define FA_DQ16_STAGGER_DMA 1
 #endif
+// FA_DQ16_DMA_DEBUG (test builds only, tests/test_dma_protocol_gpu.py; the product is 0 and its ISA does not change): adversarial timing for the K / V double buffer.
+//   1 = LATE ISSUE: dma_tiles(t + 1, BUF ^ 1) goes out directly in front of the closing vmcnt(0) that retires it, in all eight waves;
+//   2 = SLEEPY: waves 4-7 sleep ~4000 cycles (s_sleep 64, more than a tile period) in front of every request of the loop.
+#ifndef FA_DQ16_DMA_DEBUG
+#define FA_DQ16_DMA_DEBUG 0
+#endif
 // (Round 6, measured and not kept: FA_DQ16_SKEW - waves 4-7 with their workgroup barrier in FRONT of the tile's last dQ phase, so that the two waves of a SIMD stay a phase
 // apart; three-slot K / V rings, loop unrolled x3, no spill in the loops: bit-identical, +1.7..+10 %, profiles/r6_dq_skew_ab.log.)
 
@@ -189,7 +195,12 @@ __global__ __launch_bounds__(kDq16Threads, FA_DQ16_MIN_WAVES(D)) void fa_bwd_dq1
         __syncthreads();      // tile t is in LDS (every wave waited for its pieces); the other buffer is free again
         const bool wave_active = !CAUSAL || (n0 <= wave_q_hi + delta);
         const bool dma_late = FA_DQ16_STAGGER_DMA && wave >= 4 && wave_active;       // (fa_bwd.hip: waves 4-7 issue after their first half)
+#if FA_DQ16_DMA_DEBUG == 2
+        if (t + 1 < n_tiles && !dma_late && wave >= 4) asm volatile("s_sleep 64" ::: "memory");
+#endif
+#if FA_DQ16_DMA_DEBUG != 1
         if (t + 1 < n_tiles && !dma_late) dma_tiles(t + 1, BUF ^ 1);
+#endif
         if (wave_active) {
             const bool need_mask = (n0 + kDq16BlockN > sk) || (CAUSAL && (n0 + kDq16BlockN - 1 > wave_q_lo + delta));
             int lim_loc[2];                           // key of element (kb, r) = n0 + 16*kb + 4*kPi2[g] + r: everything lane- or tile-dependent folded once
@@ -235,7 +246,12 @@ __global__ __launch_bounds__(kDq16Threads, FA_DQ16_MIN_WAVES(D)) void fa_bwd_dq1
                     dsf[qb].z = LP<T>::pack2(sacc[1][qb][0] * dpacc[1][qb][0], sacc[1][qb][1] * dpacc[1][qb][1]);
                     dsf[qb].w = LP<T>::pack2(sacc[1][qb][2] * dpacc[1][qb][2], sacc[1][qb][3] * dpacc[1][qb][3]);
                 }
+#if FA_DQ16_DMA_DEBUG == 2
+                if (cch == 0 && dma_late && t + 1 < n_tiles) asm volatile("s_sleep 64" ::: "memory");
+#endif
+#if FA_DQ16_DMA_DEBUG != 1
                 if (cch == 0 && dma_late && t + 1 < n_tiles) dma_tiles(t + 1, BUF ^ 1);
+#endif
                 // dQ^T (16-d blocks x 16 queries) += K^T (16 d x 32 keys) * dS^T (32 keys x 16 queries)
 #pragma unroll
                 for (int db = 0; db < DB; ++db) {
@@ -247,6 +263,10 @@ __global__ __launch_bounds__(kDq16Threads, FA_DQ16_MIN_WAVES(D)) void fa_bwd_dq1
                 }
             }
         }
+#if FA_DQ16_DMA_DEBUG == 1
+        (void)dma_late;
+        if (t + 1 < n_tiles) dma_tiles(t + 1, BUF ^ 1);
+#endif
 #if !(FA_DQ16_ABL & 1)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile t+1 have landed
 #endif

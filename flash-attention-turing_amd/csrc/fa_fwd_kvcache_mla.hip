@@ -19,6 +19,7 @@
 //   * The append copies the 72 16-byte slots of a kv_new row, contiguous or through the table, with the drop and clamp rules of the other appends.
 //   Kernels of this file: 8 attention ((fp16, bf16) x (causal, not) x (contiguous, paged)), 2 append, 2 combine.
 #include "fa_kvcache_launch.hpp"
+#include "fa_kvcache_stage_debug.hpp"
 
 namespace fa {
 
@@ -241,21 +242,35 @@ FA_DEV void kvcache_mla_attn(const KvcacheKernelParams& p) {
     // compute - every wave left that stage's reads (step n - 1) in front of the last barrier - and one barrier publishes them.  The loads of
     // step n + 2 are issued behind that barrier, so nothing is outstanding when it is reached.  k_end is the workgroup's: every wave meets
     // the same barriers.
+    // Test builds (FA_KVC_STAGE_DEBUG, fa_kvcache_stage_debug.hpp): the two helpers hold one wave back; FA_KVC_STAGE_RACY moves the step's barrier in front of store_step.
+    // Why the racy form can neither hang nor fault here: (1) the barrier only changes places inside the same `if (key0 + kKvcStep < k_end)`, whose
+    // condition is the workgroup's (k_begin, k_end and key0 are the same in every wave, `active` is not part of it), so every wave still meets the same
+    // number of barriers on every path; (2) the two images are read by compute_step alone, as MFMA operands (kf, v0 / v1): what comes out of them are
+    // scores and O, which reach compares, exponentials and stores of VALUES - every address (lds_tile_off of lane constants, row_off / row_index of the
+    // lane's row, the page cursor from block_table), every index and every loop bound comes from the parameters.  A stale image gives wrong numbers.
     {
         u32x4 st[NL];
         int key = k_begin;
         if (key < k_end) {
             load_step(key, st);
+            kvc_stage_slow_writer(-1, wave);
             store_step(std::integral_constant<int, 0>{}, st);
         }
         __syncthreads();
         if (key + kKvcStep < k_end) load_step(key + kKvcStep, st);
         auto step = [&](auto bufc, int key0) __attribute__((always_inline)) {
             constexpr int BUF = decltype(bufc)::value;
+            kvc_stage_slow_reader((key0 - k_begin) / kKvcStep, wave);
             if (active) compute_step(bufc, key0);
             if (key0 + kKvcStep < k_end) {
-                store_step(std::integral_constant<int, BUF ^ 1>{}, st);
+#if FA_KVC_STAGE_RACY
                 __syncthreads();
+#endif
+                kvc_stage_slow_writer((key0 - k_begin) / kKvcStep, wave);
+                store_step(std::integral_constant<int, BUF ^ 1>{}, st);
+#if !FA_KVC_STAGE_RACY
+                __syncthreads();
+#endif
                 if (key0 + 2 * kKvcStep < k_end) load_step(key0 + 2 * kKvcStep, st);
             }
         };

@@ -26,6 +26,7 @@
 //   4 append ((fp16, bf16) x (contiguous, paged)), 2 combine (fa_kvcache_combine_kernel at D = 512).
 #include "fa_kvcache_launch.hpp"
 #include "fa_kvcache_quant.hpp"
+#include "fa_kvcache_stage_debug.hpp"
 
 namespace fa {
 
@@ -348,6 +349,14 @@ FA_DEV void kvcache_mla8_attn(const KvcacheKernelParams& p, const int32_t* indic
     // compute - every wave left that stage's reads (step n - 1) in front of the last barrier - and one barrier publishes them.  The loads of
     // step n + 2 are issued behind that barrier, so nothing is outstanding when it is reached.  k_end is the workgroup's: every wave meets
     // the same barriers.  (SPARSE: k_begin < k_end always - topk >= 32 and an empty split has returned.)
+    // Test builds (FA_KVC_STAGE_DEBUG, fa_kvcache_stage_debug.hpp): the two helpers hold one wave back; FA_KVC_STAGE_RACY moves the step's barrier in front of store_step.
+    // Why the racy form can neither hang nor fault here, in the dense and in the sparse body: (1) the barrier only changes places inside the same
+    // `if (key0 + kKvcStep < k_end)`, whose condition is the workgroup's (k_begin, k_end and key0 are the same in every wave, `active` is not part of it),
+    // so every wave still meets the same number of barriers on every path; (2) the two images are read by compute_step alone, as MFMA operands (kf, v0 /
+    // v1): what comes out of them are scores and O, which reach compares, exponentials and stores of VALUES.  Codes, tile scales and rope words travel
+    // memory -> registers -> dequant8 -> image, never back; the sparse index words, masks, row offsets and page addresses live in registers and cross lanes
+    // by ds_bpermute (the crossbar; no LDS byte is read or written).  Every address, index and loop bound comes from the parameters, the list and the block
+    // table.  A stale image gives wrong numbers.
     {
         Mla8Stage st;
         int key = k_begin;
@@ -360,16 +369,24 @@ FA_DEV void kvcache_mla8_attn(const KvcacheKernelParams& p, const int32_t* indic
         }
         if (key < k_end) {
             load_step(std::integral_constant<int, 0>{}, key, st);
+            kvc_stage_slow_writer(-1, wave);
             store_step(std::integral_constant<int, 0>{}, st);
         }
         __syncthreads();
         if (key + kKvcStep < k_end) load_step(std::integral_constant<int, 1>{}, key + kKvcStep, st);
         auto step = [&](auto bufc, int key0) __attribute__((always_inline)) {
             constexpr int BUF = decltype(bufc)::value;
+            kvc_stage_slow_reader((key0 - k_begin) / kKvcStep, wave);
             if (active) compute_step(bufc, key0);
             if (key0 + kKvcStep < k_end) {
-                store_step(std::integral_constant<int, BUF ^ 1>{}, st);
+#if FA_KVC_STAGE_RACY
                 __syncthreads();
+#endif
+                kvc_stage_slow_writer((key0 - k_begin) / kKvcStep, wave);
+                store_step(std::integral_constant<int, BUF ^ 1>{}, st);
+#if !FA_KVC_STAGE_RACY
+                __syncthreads();
+#endif
                 if (key0 + 2 * kKvcStep < k_end) load_step(bufc, key0 + 2 * kKvcStep, st);
             }
         };

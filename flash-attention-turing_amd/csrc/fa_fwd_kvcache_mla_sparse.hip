@@ -24,6 +24,7 @@
 //     and its score is -inf before the max, where the dense kernel applies key < lim.
 //   Kernels of this file: 4 attention ((fp16, bf16) x (contiguous, paged)), 2 combine.  There is no append.
 #include "fa_kvcache_launch.hpp"
+#include "fa_kvcache_stage_debug.hpp"
 
 namespace fa {
 
@@ -239,6 +240,14 @@ FA_DEV void kvcache_mla_sparse_attn(const KvcacheMlaSparseParams& sp) {
     // ---- the split's 32-slot steps, all four waves together; two LDS stages in turn (the schedule of kvcache_mla_attn) -------------------------
     // Stage n & 1 holds step n.  While step n computes, the loads of step n + 1 are in flight; they are written to the other stage behind the
     // compute and one barrier publishes them; the loads of step n + 2 are issued behind that barrier.  k_end is the workgroup's.
+    // Test builds (FA_KVC_STAGE_DEBUG, fa_kvcache_stage_debug.hpp): the two helpers hold one wave back; FA_KVC_STAGE_RACY moves the step's barrier in front of store_step.
+    // Why the racy form can neither hang nor fault here: (1) the barrier only changes places inside the same `if (key0 + kKvcStep < k_end)`, whose
+    // condition is the workgroup's (k_begin, k_end and key0 are the same in every wave, `active` is not part of it), so every wave still meets the same
+    // number of barriers on every path; (2) the two images are read by compute_step alone, as MFMA operands (kf, v0 / v1): what comes out of them are
+    // scores and O, which reach compares, exponentials and stores of VALUES.  The gather does NOT go through them: the index words come from global memory
+    // into registers (load_idx), cross lanes by v_readlane / ds_bpermute (the crossbar; no LDS byte is read or written), and masks, row offsets, table
+    // columns and page addresses are computed from those registers.  Every address, index and loop bound comes from the parameters, the list and the
+    // block table.  A stale image gives wrong numbers.
     {
         u32x4 st[NL];
         int key = k_begin;
@@ -248,15 +257,23 @@ FA_DEV void kvcache_mla_sparse_attn(const KvcacheMlaSparseParams& sp) {
             load_idx(key + kKvcStep);
         }
         load_step(std::integral_constant<int, 0>{}, key, st);
+        kvc_stage_slow_writer(-1, wave);
         store_step(std::integral_constant<int, 0>{}, st);
         __syncthreads();
         if (key + kKvcStep < k_end) load_step(std::integral_constant<int, 1>{}, key + kKvcStep, st);
         auto step = [&](auto bufc, int key0) __attribute__((always_inline)) {
             constexpr int BUF = decltype(bufc)::value;
+            kvc_stage_slow_reader((key0 - k_begin) / kKvcStep, wave);
             if (active) compute_step(bufc);
             if (key0 + kKvcStep < k_end) {
-                store_step(std::integral_constant<int, BUF ^ 1>{}, st);
+#if FA_KVC_STAGE_RACY
                 __syncthreads();
+#endif
+                kvc_stage_slow_writer((key0 - k_begin) / kKvcStep, wave);
+                store_step(std::integral_constant<int, BUF ^ 1>{}, st);
+#if !FA_KVC_STAGE_RACY
+                __syncthreads();
+#endif
                 if (key0 + 2 * kKvcStep < k_end) load_step(bufc, key0 + 2 * kKvcStep, st);
             }
         };

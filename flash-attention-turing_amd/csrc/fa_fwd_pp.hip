@@ -65,6 +65,19 @@ constexpr float kPpDeferLog2 = 6.0f;
 #ifndef FA_FWD_D64_BN
 #define FA_FWD_D64_BN 0
 #endif
+// FA_PP_DMA_DEBUG (test builds only, tests/test_dma_protocol_gpu.py; the product is 0 and its ISA does not change): adversarial timing for the K / V rings, as
+// FA_PP16_DMA_DEBUG of fa_fwd_pp16.hip.
+//   1 = LATE ISSUE: K(u+2) and V(u+1) go out directly in front of the vmcnt(0) that ends S(u) and retires them - behind the softmax and behind the prefetch of
+//       M(u+1)'s first fragments, which reads V(u) and K(u+1) and neither of the two slots being filled;
+//   2 = SLEEPY GROUP: group B's waves sleep ~4000 cycles (s_sleep 64, more than a tile period) in front of every request.
+#ifndef FA_PP_DMA_DEBUG
+#define FA_PP_DMA_DEBUG 0
+#endif
+#if FA_PP_DMA_DEBUG == 2
+#define FA_PP_DMA_SLEEP() do { if (group == 1) asm volatile("s_sleep 64" ::: "memory"); } while (0)
+#else
+#define FA_PP_DMA_SLEEP() do { } while (0)
+#endif
 constexpr int kFwdD64WideMinKeys = 16384;     // (round 3: 2048.  With the round-4 causal dispatch order the 64-key shape is ahead up to 8k: profiles/r4_fwd_d64_shapes_after_reorder_ab.log)
 // Matrix phase = NPV P*V steps, then NQK QK^T steps.  P*V step j -> (output block db = j % DB, key sub-tile ts = j / DB): consecutive
 // MFMAs go to different accumulators (per accumulator the ts order, hence the result, is unchanged; 0.3-0.5 % over db-major at D = 128;
@@ -461,11 +474,21 @@ __global__ __launch_bounds__(kFwdThreads, FA_PP_MIN_WAVES(D, BN)) void fa_fwd_pp
         if constexpr (decltype(masked)::value) active = !CAUSAL || (u * kFwdBlockN <= wave_q_hi + delta);
         if (prev_active) pv_step();
         if (active) qk_step();
+#if FA_PP_DMA_DEBUG != 1
+        FA_PP_DMA_SLEEP();
         issue_dma_k(u);
         __syncthreads();
+        FA_PP_DMA_SLEEP();
         issue_dma_v(u);
+#else
+        __syncthreads();
+#endif
         if (active) softmax_step(u, masked);
         prev_active = active;
+#if FA_PP_DMA_DEBUG == 1
+        issue_dma_k(u);
+        issue_dma_v(u);
+#endif
         end_s_phase();
         advance_ring();
     };
@@ -499,11 +522,18 @@ __global__ __launch_bounds__(kFwdThreads, FA_PP_MIN_WAVES(D, BN)) void fa_fwd_pp
                 });
             }
             __syncthreads();
+#if FA_PP_DMA_DEBUG != 1
+            FA_PP_DMA_SLEEP();
             if (uu + 2 < n_tiles) dma_k_tile(k_srd, uu + 2, S_UM1);
             if (uu + 1 < n_tiles) dma_v_tile(v_srd, uu + 1, S_UP1);
+#endif
             softmax_step(uu, no{});
 #pragma unroll
             for (int j = 0; j < PF; ++j) pre[j] = m_frag_c(j, S_U, S_UP1);
+#if FA_PP_DMA_DEBUG == 1
+            if (uu + 2 < n_tiles) dma_k_tile(k_srd, uu + 2, S_UM1);
+            if (uu + 1 < n_tiles) dma_v_tile(v_srd, uu + 1, S_UP1);
+#endif
             end_s_phase();
         };
         using i0 = std::integral_constant<int, 0>;
@@ -520,10 +550,17 @@ __global__ __launch_bounds__(kFwdThreads, FA_PP_MIN_WAVES(D, BN)) void fa_fwd_pp
         for (; u < n_main; ++u) {                 // the last one or two steady-state tiles (all of them for D = 64)
             m_phase();
             __syncthreads();
+#if FA_PP_DMA_DEBUG != 1
+            FA_PP_DMA_SLEEP();
             issue_dma_k(u);
             issue_dma_v(u);
+#endif
             softmax_step(u, no{});
             m_prefetch(ring_u, ring_up1);         // first fragments of M(u+1): V(u) and K(u+1) landed one barrier ago
+#if FA_PP_DMA_DEBUG == 1
+            issue_dma_k(u);
+            issue_dma_v(u);
+#endif
             end_s_phase();
             advance_ring();
         }

@@ -8,7 +8,11 @@ front of the wait that retires them (`dma_late`), or behind a sleep longer than 
 does not care when the bytes land as long as its own waits and barriers are honoured, so both builds must reproduce the product BIT FOR BIT; a protocol
 that reads before the publishing barrier reads the slot's previous tenant and fails.  To show the method has teeth, the documented racy form is kept
 in the source behind a test-only switch (`dma_racy`: bit-identical at normal timing, as round 4 recorded) and must FAIL under late issue
-(`dma_racy_late`).  The debug libraries are built by flash-attention-turing_amd/build.py (DEBUG_VARIANTS) next to the product; the product's ISA is unchanged."""
+(`dma_racy_late`).  The debug libraries are built by flash-attention-turing_amd/build.py (DEBUG_VARIANTS) next to the product; the product's ISA is unchanged.
+
+The same two builds also carry the switches of the other LDS-DMA kernels: fa_bwd_dq16 (the 16x16x32 dQ, compared on the shapes above), and the 32x32x16
+set - fa_fwd_pp, fa_bwd_dq, fa_bwd_dkdv - which runs under a pinned policy on small shapes of its own (SHAPES32).  The register-staged decode kernels are
+in tests/test_stage_protocol_gpu.py; tests/test_debug_variants_cpu.py checks that every build differs from the product as it should."""
 import ctypes
 import importlib.util
 import os
@@ -33,6 +37,24 @@ SHAPES = [
 ]
 
 
+# The 32x32x16 set (fa_fwd_pp.hip, fa_bwd.hip) under a pinned policy: (name, b, sq, sk, h, hk, causal).  The smallest shapes that reach each steady loop, read
+# from the sources (256-row query blocks, 64-key tiles at both head dims below 16384 keys; n_main = key tiles every row of the block sees whole):
+#   fa_fwd_pp_kernel   head_dim 128: the constant-slot loop `for (; u + 3 <= n_main; u += 3)` from u = 1 needs n_main >= 4, the tail loop `for (; u < n_main; ++u)`
+#                      the tiles left over; head_dim 64 (64-key tiles): the tail loop alone, n_main >= 2.  Masked tiles run `iteration`, which carries the switch too.
+#   fa_bwd_dq_kernel   requests tile t + 1 while t + 1 < n_tiles; head_dim 128 walks two tiles a trip (`t + 2 <= n_tiles`) and one more if n_tiles is odd.
+#   fa_bwd_dkdv_kernel requests the next 64-row Q / dO tile while `it + 1 < n_iters`, n_iters = 64-row tiles x query heads of the KV head's group.
+# full: 3 query blocks (88 rows in the last), 11 key tiles (60 keys in the last), n_main = 10, n_iters = 10 x 4.  causal: sq != sk, delta = 257; block 0 has
+# n_main = 4 and two diagonal tiles, block 2 (8 rows) n_main = 12 of 13.  GQA 4 / 1 and 2 / 2.
+SHAPES32 = [
+    ("full_b2_sq600_sk700_gqa4", 2, 600, 700, 4, 1, False),
+    ("causal_b1_sq520_sk777_gqa4", 1, 520, 777, 4, 1, True),
+    ("causal_b2_sq600_sk600_h2", 2, 600, 600, 2, 2, True),
+]
+KERNELS32 = {"fwd": "fa_fwd_pp_kernel", "dq": "fa_bwd_dq_kernel", "dkdv": "fa_bwd_dkdv_kernel"}
+STAGE_CODES = {"fwd": 0, "dq": 1, "dkdv": 2}
+POLICY_MFMA32 = 0
+
+
 def _build_module():
     spec = importlib.util.spec_from_file_location("fa_build", os.path.join(ROOT, "flash-attention-turing_amd", "build.py"))
     m = importlib.util.module_from_spec(spec)
@@ -47,12 +69,14 @@ def libs(gpu):
     fa_build = _build_module()
     fa_build.build_debug_variants(force=False)          # a no-op when build() has run (the .so files travel with the tree); hipcc is on the GPU box otherwise
     out = {"product": capi.lib()}
-    for name in fa_build.DEBUG_VARIANTS:
+    for name in ("dma_late", "dma_sleepy", "dma_racy", "dma_racy_late"):
         L = ctypes.CDLL(fa_build.debug_library_path(name))
         L.fa_run_mha_fwd.argtypes = [ctypes.POINTER(capi.FwdParams), ctypes.c_void_p]
         L.fa_run_mha_bwd.argtypes = [ctypes.POINTER(capi.BwdParams), ctypes.c_void_p]
         L.fa_kernel_name_dtype.restype = ctypes.c_char_p
         L.fa_kernel_name_dtype.argtypes = [ctypes.c_int32] * 8
+        L.fa_set_kernel_policy.restype = ctypes.c_int32
+        L.fa_set_kernel_policy.argtypes = [ctypes.c_int32]
         out[name] = L
     return out
 
@@ -96,6 +120,8 @@ def test_product_protocol_is_bit_identical_under_adversarial_dma_timing(gpu, lib
     assert capi.kernel_name("fwd", b, sq, sk, h, d, causal, dtn) == "fa_fwd_pp16_kernel"
     # (head_dim 64 under a causal mask: dK/dV stays on the 32x32x16 kernel below 2^28 pairs per head - that shape is there for the forward)
     assert capi.kernel_name("dkdv", b, sq, sk, h, d, causal, dtn) == "fa_bwd_dkdv16_kernel" or (d == 64 and causal)
+    # fa_bwd_dq16.hip carries the switches too (FA_DQ16_DMA_DEBUG): the dQ compared below comes from it
+    assert capi.kernel_name("dq", b, sq, sk, h, d, causal, dtn) == "fa_bwd_dq16_kernel"
     q, k, v, do = _inputs(gpu, b, sq, sk, h, hk, dt, d)
     o, lse = _fwd(libs["product"], q, k, v, causal)
     assert torch.isfinite(o.float()).all() and torch.isfinite(lse).all()
@@ -107,6 +133,37 @@ def test_product_protocol_is_bit_identical_under_adversarial_dma_timing(gpu, lib
         g2 = _bwd(libs[name], q, k, v, o, lse, do, causal)
         for a, c, t in zip(grads, g2, ("dq", "dk", "dv")):
             assert torch.equal(a, c), (name, t, (a.float() - c.float()).abs().max().item())
+
+
+@pytest.mark.parametrize("dtn", ["fp16", "bf16"])
+@pytest.mark.parametrize("d", [64, 128])
+@pytest.mark.parametrize("shape", SHAPES32, ids=[s[0] for s in SHAPES32])
+def test_mfma32_set_is_bit_identical_under_adversarial_dma_timing(gpu, libs, shape, d, dtn):
+    """fa_fwd_pp.hip (the schedule the round-4 race lived in; small launches, smoke() included, run it) and both kernels of fa_bwd.hip, pinned through
+    fa_set_kernel_policy on EACH library (every .so has its own policy global) and asserted through that library's fa_kernel_name_dtype"""
+    _, b, sq, sk, h, hk, causal = shape
+    dt = torch.float16 if dtn == "fp16" else torch.bfloat16
+    names = ("product", "dma_late", "dma_sleepy")
+    prev = {n: libs[n].fa_set_kernel_policy(POLICY_MFMA32) for n in names}
+    try:
+        for n in names:
+            for stage, kernel in KERNELS32.items():
+                got = libs[n].fa_kernel_name_dtype(STAGE_CODES[stage], 0 if dtn == "fp16" else 1, b, sq, sk, h, d, int(causal)).decode()
+                assert got == kernel, (n, stage, got)
+        q, k, v, do = _inputs(gpu, b, sq, sk, h, hk, dt, d)
+        o, lse = _fwd(libs["product"], q, k, v, causal)
+        assert torch.isfinite(o.float()).all() and torch.isfinite(lse).all()
+        grads = _bwd(libs["product"], q, k, v, o, lse, do, causal)
+        for name in names[1:]:
+            for rep in range(2):
+                o2, lse2 = _fwd(libs[name], q, k, v, causal)
+                assert torch.equal(o, o2) and torch.equal(lse, lse2), (name, rep, (o.float() - o2.float()).abs().max().item())
+                g2 = _bwd(libs[name], q, k, v, o, lse, do, causal)
+                for a, c, t in zip(grads, g2, ("dq", "dk", "dv")):
+                    assert torch.equal(a, c), (name, rep, t, (a.float() - c.float()).abs().max().item())
+    finally:
+        for n in names:
+            libs[n].fa_set_kernel_policy(prev[n])
 
 
 def test_late_issue_catches_the_documented_racy_form(gpu, libs):
