@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "fa_params.hpp"
+#include "fa_mla_indexer.hpp"
 #include "flash_attn_gfx950.h"
 
 namespace {
@@ -94,6 +95,18 @@ int import_mla(const P1* user, P2& local, const char* what) {
         return fail(FA_ERR_BAD_ABI, "%s: struct_size %u is neither %zu nor %zu (%s_v2) - header / library mismatch", what, user->struct_size, sizeof(P1), sizeof(P2), what);
     memset(&local, 0, sizeof(P2));
     memcpy(&local, user, user->struct_size);
+    return FA_OK;
+}
+
+// The indexer structs (fa_mla_indexer_params, fa_mla_topk_params) have one size each: struct_size must be it.
+template <typename P>
+int import_exact(const P* user, P& local, const char* what) {
+    if (user == nullptr) return fail(FA_ERR_NULL_POINTER, "params is NULL");
+    if (user->magic != FA_PARAMS_MAGIC)
+        return fail(FA_ERR_BAD_ABI, "%s: magic is not FA_PARAMS_MAGIC - no {struct_size, magic} header; initialise the struct with FA_PARAMS_INIT (ABI %d)", what, FA_ABI_VERSION);
+    if (user->struct_size != sizeof(P))
+        return fail(FA_ERR_BAD_ABI, "%s: struct_size %u is not %zu - header / library mismatch", what, user->struct_size, sizeof(P));
+    memcpy(&local, user, sizeof(P));
     return FA_OK;
 }
 
@@ -987,6 +1000,116 @@ int fa_run_mla_sparse_fwd_kvcache(const fa_mla_sparse_params* user, void* stream
     sp.kp.ws_o = sp.kp.n_split > 1 ? (float*)local.workspace : nullptr;
     if (sp.kp.cache_fp8) return hip_status(fa::launch_fwd_kvcache_mla_sparse_fp8(sp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache_mla_sparse_fp8 launch");
     return hip_status(fa::launch_fwd_kvcache_mla_sparse(sp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache_mla_sparse launch");
+}
+
+// ---- the indexer in front of sparse MLA decode -------------------------------------------------------------------------------------------------
+static int fill_mla_indexer(const fa_mla_indexer_params* user, fa::MlaIndexerParams& ip, fa_mla_indexer_params& local) {
+    int rc = import_exact(user, local, "fa_mla_indexer_params");
+    if (rc) return rc;
+    const fa_mla_indexer_params* p = &local;
+    const bool paged = p->block_table != nullptr;
+    if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0)
+        return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d", p->b, p->seqlen_q, p->seqlen_cache);
+    if (p->h != 16 && p->h != 32 && p->h != 64) return fail(FA_ERR_BAD_HEADDIM, "h %d unsupported (16, 32 or 64 index heads)", p->h);
+    if (p->d != fa::kIdxD) return fail(FA_ERR_BAD_HEADDIM, "d %d unsupported (index heads and index keys are 128 wide)", p->d);
+    if (p->dtype != FA_FP16 && p->dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", p->dtype);
+    if (p->k_format != FA_MLA_KV_16BIT && p->k_format != FA_IDX_K_FP8_E4M3)
+        return fail(FA_ERR_BAD_DTYPE, "k_format %d unknown (0 = keys of dtype, 1 = OCP e4m3 codes)", p->k_format);
+    if (p->reserved_ != 0) return fail(FA_ERR_BAD_SHAPE, "fa_mla_indexer_params: reserved_ is not zero (a field of a newer header that this library does not know)");
+    if (paged) {
+        const int P = p->page_block_size;
+        if (P == 0) return fail(FA_ERR_BAD_SHAPE, "block_table given without page_block_size");
+        if (P < 0 || P % 16 != 0) return fail(FA_ERR_BAD_SHAPE, "page_block_size %d must be a positive multiple of 16", P);
+        if (p->num_blocks < 1) return fail(FA_ERR_BAD_SHAPE, "num_blocks %d: a paged cache needs at least one page", p->num_blocks);
+        if (p->seqlen_cache <= 0 || p->seqlen_cache % P != 0)
+            return fail(FA_ERR_BAD_SHAPE, "seqlen_cache (%d) must be a positive multiple of page_block_size (%d) with block_table", p->seqlen_cache, P);
+        if (p->block_table_stride < p->seqlen_cache / P)
+            return fail(FA_ERR_BAD_STRIDE, "block_table_stride %lld is below the table's %d columns (seqlen_cache / page_block_size)",
+                        (long long)p->block_table_stride, p->seqlen_cache / P);
+        if ((reinterpret_cast<uintptr_t>(p->block_table) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "block_table must be 4-byte aligned");
+    } else if (p->page_block_size != 0) {
+        return fail(FA_ERR_NULL_POINTER, "page_block_size = %d given without block_table", p->page_block_size);
+    }
+    // a workgroup's key range ends at most kIdxMaxWgKeys past the capacity, and the grid is one-dimensional
+    if (p->seqlen_cache > INT32_MAX - 2 * fa::kIdxMaxWgKeys) return fail(FA_ERR_BAD_SHAPE, "seqlen_cache %d too large", p->seqlen_cache);
+    if ((int64_t)p->b * p->seqlen_q >= ((int64_t)1 << 24))
+        return fail(FA_ERR_BAD_SHAPE, "call too large: b = %d sequences x seqlen_q = %d tokens exceeds the launch grid", p->b, p->seqlen_q);
+    const bool fp8 = p->k_format == FA_IDX_K_FP8_E4M3;
+    const int es = fp8 ? 1 : 2, unit = 16 / es;     // strides of the cache: bytes (FP8) or elements; 16-byte loads either way
+    if (p->b > 0) {
+        if (p->logits == nullptr) return fail(FA_ERR_NULL_POINTER, "logits is NULL");
+        if ((reinterpret_cast<uintptr_t>(p->logits) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "logits must be 4-byte aligned");
+        if (p->logits_row_stride < p->seqlen_cache || p->logits_batch_stride < 0)
+            return fail(FA_ERR_BAD_STRIDE, "logits strides (logits_batch_stride=%lld, logits_row_stride=%lld): rows must be at least seqlen_cache = %d elements apart",
+                        (long long)p->logits_batch_stride, (long long)p->logits_row_stride, p->seqlen_cache);
+        if (p->weights == nullptr) return fail(FA_ERR_NULL_POINTER, "weights is NULL");
+        if ((reinterpret_cast<uintptr_t>(p->weights) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "weights must be 4-byte aligned");
+        if (p->q_idx == nullptr) return fail(FA_ERR_NULL_POINTER, "q_idx is NULL");
+        const fa_strides& qs = p->q_idx_stride;
+        if ((reinterpret_cast<uintptr_t>(p->q_idx) & 15u) != 0) return fail(FA_ERR_BAD_STRIDE, "q_idx base pointer must be 16-byte aligned");
+        if (qs.head % 8 != 0 || qs.row % 8 != 0 || qs.batch % 8 != 0)
+            return fail(FA_ERR_BAD_STRIDE, "q_idx strides (batch=%lld,row=%lld,head=%lld) must be multiples of 8 elements", (long long)qs.batch, (long long)qs.row, (long long)qs.head);
+        if (p->k_idx_cache == nullptr) return fail(FA_ERR_NULL_POINTER, "k_idx_cache is NULL");
+        if ((reinterpret_cast<uintptr_t>(p->k_idx_cache) & 15u) != 0) return fail(FA_ERR_BAD_STRIDE, "k_idx_cache base pointer must be 16-byte aligned");
+        if (p->k_cache_row_stride < fa::kIdxD || p->k_cache_row_stride % unit != 0 || p->k_cache_batch_stride % unit != 0 || p->k_cache_batch_stride < 0)
+            return fail(FA_ERR_BAD_STRIDE, "k_idx_cache strides (k_cache_batch_stride=%lld, k_cache_row_stride=%lld) must be multiples of %d %s (16-byte loads) with rows at least 128 apart",
+                        (long long)p->k_cache_batch_stride, (long long)p->k_cache_row_stride, unit, fp8 ? "bytes" : "elements");
+        // one descriptor per sequence (per page): below 2^31 bytes, the prefetched step past the end included
+        const int64_t span = ((int64_t)(paged ? p->page_block_size : p->seqlen_cache) + 2 * fa::kIdxStep) * p->k_cache_row_stride * es;
+        if (span >= ((int64_t)1 << 31)) return fail(FA_ERR_BAD_STRIDE, "k_idx_cache: one %s spans %lld bytes (limit 2^31)", paged ? "page" : "sequence", (long long)span);
+        if (p->k_scale != nullptr && (reinterpret_cast<uintptr_t>(p->k_scale) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "k_scale must be 4-byte aligned");
+    }
+    memset(&ip, 0, sizeof(ip));
+    ip.q_ptr = p->q_idx; ip.w_ptr = p->weights; ip.k_cache = p->k_idx_cache; ip.k_scale = p->k_scale; ip.logits = p->logits;
+    ip.cache_seqlens = p->cache_seqlens; ip.block_table = p->block_table;
+    ip.q_batch = p->q_idx_stride.batch; ip.q_row = p->q_idx_stride.row; ip.q_head = p->q_idx_stride.head;
+    ip.w_batch = p->weights_stride.batch; ip.w_row = p->weights_stride.row; ip.w_head = p->weights_stride.head;
+    ip.k_batch = p->k_cache_batch_stride * es; ip.k_row = p->k_cache_row_stride * es;
+    ip.ks_batch = p->k_scale_batch_stride; ip.ks_row = p->k_scale_row_stride;
+    ip.lg_batch = p->logits_batch_stride; ip.lg_row = p->logits_row_stride;
+    ip.bt_stride = p->block_table_stride;
+    ip.b = p->b; ip.seqlen_q = p->seqlen_q; ip.seqlen_cache = p->seqlen_cache; ip.h = p->h;
+    ip.is_causal = p->is_causal ? 1 : 0; ip.cache_fp8 = fp8 ? 1 : 0;
+    ip.page_size = paged ? p->page_block_size : 0; ip.num_blocks = paged ? p->num_blocks : 0;
+    return FA_OK;
+}
+
+int fa_run_mla_indexer_logits(const fa_mla_indexer_params* user, void* stream) {
+    fa::MlaIndexerParams ip;
+    fa_mla_indexer_params local;
+    int rc = fill_mla_indexer(user, ip, local);
+    if (rc) return rc;
+    if (ip.b == 0 || ip.seqlen_cache == 0) return FA_OK;        // nothing to write
+    return hip_status(fa::launch_mla_indexer_logits(ip, local.dtype, (hipStream_t)stream), "fa_mla_indexer_logits launch");
+}
+
+int fa_run_mla_indexer_topk(const fa_mla_topk_params* user, void* stream) {
+    fa_mla_topk_params local;
+    int rc = import_exact(user, local, "fa_mla_topk_params");
+    if (rc) return rc;
+    const fa_mla_topk_params* p = &local;
+    if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0)
+        return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d", p->b, p->seqlen_q, p->seqlen_cache);
+    if (p->topk < 32 || p->topk % 32 != 0) return fail(FA_ERR_BAD_SHAPE, "topk %d must be a positive multiple of 32", p->topk);
+    if (p->reserved_ != 0) return fail(FA_ERR_BAD_SHAPE, "fa_mla_topk_params: reserved_ is not zero (a field of a newer header that this library does not know)");
+    if ((int64_t)p->b * p->seqlen_q >= ((int64_t)1 << 31))
+        return fail(FA_ERR_BAD_SHAPE, "call too large: b = %d sequences x seqlen_q = %d tokens exceeds the launch grid", p->b, p->seqlen_q);
+    if (p->b == 0) return FA_OK;
+    if (p->indices == nullptr) return fail(FA_ERR_NULL_POINTER, "indices is NULL");
+    if ((reinterpret_cast<uintptr_t>(p->indices) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "indices must be 4-byte aligned");
+    if (p->seqlen_cache > 0) {
+        if (p->logits == nullptr) return fail(FA_ERR_NULL_POINTER, "logits is NULL");
+        if ((reinterpret_cast<uintptr_t>(p->logits) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "logits must be 4-byte aligned");
+        if (p->logits_row_stride < 0 || p->logits_batch_stride < 0)
+            return fail(FA_ERR_BAD_STRIDE, "logits strides (logits_batch_stride=%lld, logits_row_stride=%lld) must be >= 0 elements", (long long)p->logits_batch_stride,
+                        (long long)p->logits_row_stride);
+    }
+    fa::MlaTopkParams tp;
+    memset(&tp, 0, sizeof(tp));
+    tp.logits = p->logits; tp.indices = p->indices; tp.cache_seqlens = p->cache_seqlens;
+    tp.lg_batch = p->logits_batch_stride; tp.lg_row = p->logits_row_stride;
+    tp.b = p->b; tp.seqlen_q = p->seqlen_q; tp.seqlen_cache = p->seqlen_cache; tp.topk = p->topk; tp.is_causal = p->is_causal ? 1 : 0;
+    return hip_status(fa::launch_mla_indexer_topk(tp, (hipStream_t)stream), "fa_mla_indexer_topk launch");
 }
 
 }  // extern "C"

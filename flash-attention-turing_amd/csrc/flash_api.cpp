@@ -645,6 +645,73 @@ std::vector<at::Tensor> mha_fwd_mla_sparse_kvcache(at::Tensor q, at::Tensor kv_c
     return {o, l};
 }
 
+// The DeepSeek-V3.2 indexer (fa_run_mla_indexer_logits / fa_run_mla_indexer_topk).  The Python layer has checked shapes and views; here the tensors become
+// pointers and strides.  logits (b, sq, capacity) fp32 is the caller's buffer: entries at or past a token's visible length are not written.
+void mla_indexer_logits(at::Tensor q_idx, at::Tensor weights, at::Tensor k_idx_cache, at::Tensor cache_seqlens, at::Tensor logits,
+                        c10::optional<at::Tensor> k_scale_, c10::optional<at::Tensor> block_table_, bool is_causal) {
+    TORCH_CHECK(q_idx.dim() == 4 && weights.dim() == 3 && k_idx_cache.dim() == 3 && logits.dim() == 3, "q_idx (b, sq, h, 128), weights (b, sq, h), k_idx_cache (b, capacity, 128), logits (b, sq, capacity)");
+    TORCH_CHECK(q_idx.is_cuda(), "q_idx must be a GPU (HIP) tensor");
+    for (const at::Tensor* t : {&weights, &k_idx_cache, &cache_seqlens, &logits}) TORCH_CHECK(t->device() == q_idx.device(), "every tensor must be on q_idx's device");
+    TORCH_CHECK(weights.scalar_type() == torch::kFloat32 && logits.scalar_type() == torch::kFloat32, "weights and logits must be float32");
+    TORCH_CHECK(cache_seqlens.scalar_type() == torch::kInt32 && cache_seqlens.dim() == 1 && cache_seqlens.size(0) == q_idx.size(0) && cache_seqlens.is_contiguous(),
+                "cache_seqlens must be a contiguous int32 tensor of shape [batch_size]");
+    const bool fp8 = k_idx_cache.element_size() == 1;
+    TORCH_CHECK(fp8 || k_idx_cache.scalar_type() == q_idx.scalar_type(), "k_idx_cache must have the dtype of q_idx or hold e4m3 codes");
+    TORCH_CHECK(q_idx.stride(3) == 1 && k_idx_cache.stride(2) == 1 && logits.stride(2) == 1, "q_idx, k_idx_cache, logits: last dimension must be contiguous");
+    const int64_t batch_size = q_idx.size(0), seqlen_q = q_idx.size(1);
+    int64_t seqlen_cache = k_idx_cache.size(1);
+    c10::DeviceGuard guard(q_idx.device());
+    fa_mla_indexer_params p;
+    FA_PARAMS_INIT(p);
+    if (block_table_.has_value()) {
+        const at::Tensor& bt = *block_table_;
+        check_same_device(q_idx, bt, "block_table");
+        TORCH_CHECK(bt.scalar_type() == torch::kInt32 && bt.dim() == 2 && bt.size(0) == batch_size, "block_table must be int32 [batch_size, max_blocks_per_seq]");
+        TORCH_CHECK(bt.stride(1) == 1 || bt.size(1) <= 1, "block_table: last dimension must be contiguous");
+        seqlen_cache = bt.size(1) * k_idx_cache.size(1);
+        TORCH_CHECK(k_idx_cache.size(0) <= INT32_MAX && seqlen_cache <= INT32_MAX, "block_table: pool pages and capacity must fit in int32");
+        p.block_table = bt.data_ptr<int32_t>();
+        p.block_table_stride = batch_size > 1 ? bt.stride(0) : std::max<int64_t>(bt.stride(0), bt.size(1));
+        p.page_block_size = (int32_t)k_idx_cache.size(1); p.num_blocks = (int32_t)k_idx_cache.size(0);
+    }
+    TORCH_CHECK(logits.size(0) == batch_size && logits.size(1) == seqlen_q && logits.size(2) == seqlen_cache, "logits must have shape [batch_size, seqlen_q, capacity]");
+    p.q_idx = q_idx.data_ptr(); p.weights = weights.data_ptr<float>(); p.k_idx_cache = k_idx_cache.data_ptr(); p.logits = logits.data_ptr<float>();
+    p.cache_seqlens = cache_seqlens.data_ptr<int32_t>();
+    if (k_scale_.has_value()) {
+        const at::Tensor& ks = *k_scale_;
+        check_same_device(q_idx, ks, "k_scale");
+        TORCH_CHECK(ks.scalar_type() == torch::kFloat32 && ks.dim() == 2, "k_scale must be a float32 tensor with one value per cached token");
+        p.k_scale = ks.data_ptr<float>(); p.k_scale_batch_stride = ks.stride(0); p.k_scale_row_stride = ks.stride(1);
+    }
+    p.b = (int32_t)batch_size; p.seqlen_q = (int32_t)seqlen_q; p.seqlen_cache = (int32_t)seqlen_cache;
+    p.h = (int32_t)q_idx.size(2); p.d = (int32_t)q_idx.size(3); p.dtype = fa_dtype_of(q_idx);
+    p.k_format = fp8 ? FA_IDX_K_FP8_E4M3 : FA_MLA_KV_16BIT; p.is_causal = is_causal;
+    p.q_idx_stride = strides4(q_idx);
+    p.weights_stride = fa_strides{weights.stride(0), weights.stride(1), weights.stride(2)};
+    p.k_cache_batch_stride = k_idx_cache.stride(0); p.k_cache_row_stride = k_idx_cache.stride(1);      // (FP8: a 1-byte dtype, so these are bytes, as the format asks)
+    p.logits_batch_stride = logits.stride(0); p.logits_row_stride = logits.stride(1);
+    check_status(fa_run_mla_indexer_logits(&p, current_stream(q_idx)));
+}
+
+void mla_indexer_topk(at::Tensor logits, at::Tensor cache_seqlens, at::Tensor indices, bool is_causal) {
+    TORCH_CHECK(logits.dim() == 3 && indices.dim() == 3 && logits.is_cuda(), "logits (b, sq, capacity) and indices (b, sq, topk) must be GPU (HIP) tensors");
+    TORCH_CHECK(indices.device() == logits.device() && cache_seqlens.device() == logits.device(), "every tensor must be on logits' device");
+    TORCH_CHECK(logits.scalar_type() == torch::kFloat32 && (logits.stride(2) == 1 || logits.size(2) <= 1), "logits must be float32 with a contiguous last dimension");
+    TORCH_CHECK(indices.scalar_type() == torch::kInt32 && indices.is_contiguous(), "indices must be a contiguous int32 tensor");
+    TORCH_CHECK(indices.size(0) == logits.size(0) && indices.size(1) == logits.size(1), "indices must have shape [batch_size, seqlen_q, topk]");
+    TORCH_CHECK(cache_seqlens.scalar_type() == torch::kInt32 && cache_seqlens.dim() == 1 && cache_seqlens.size(0) == logits.size(0) && cache_seqlens.is_contiguous(),
+                "cache_seqlens must be a contiguous int32 tensor of shape [batch_size]");
+    TORCH_CHECK(logits.size(2) <= INT32_MAX && indices.size(2) <= INT32_MAX, "capacity and topk must fit in int32");
+    c10::DeviceGuard guard(logits.device());
+    fa_mla_topk_params p;
+    FA_PARAMS_INIT(p);
+    p.logits = logits.data_ptr<float>(); p.indices = indices.data_ptr<int32_t>(); p.cache_seqlens = cache_seqlens.data_ptr<int32_t>();
+    p.b = (int32_t)logits.size(0); p.seqlen_q = (int32_t)logits.size(1); p.seqlen_cache = (int32_t)logits.size(2); p.topk = (int32_t)indices.size(2);
+    p.is_causal = is_causal;
+    p.logits_batch_stride = logits.stride(0); p.logits_row_stride = logits.stride(1);
+    check_status(fa_run_mla_indexer_topk(&p, current_stream(logits)));
+}
+
 // ---- autograd nodes in C++ ------------------------------------------------------------------------------------------------------
 // The reference ships the four raw functions only; its README's flash_attn_func is an older Python-level API.  The differentiable wrappers
 // of this package used to be torch.autograd.Function subclasses in Python: ~85 us of host time per forward + backward, more than the GPU
@@ -708,6 +775,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "Sparse MLA decode over a latent KV cache: q (b, sq, h, 576), kv_cache (b, capacity, 1, 576), indices int32 (b, sq, topk) -> [out (b, sq, h, 512), lse]",
           py::arg("q"), py::arg("kv_cache"), py::arg("indices"), py::arg("cache_seqlens") = py::none(), py::arg("num_splits") = 0,
           py::arg("block_table") = py::none(), py::arg("softmax_scale") = py::none(), py::arg("head_dim_v") = 512);
+    m.def("mla_indexer_logits", &mla_indexer_logits, "index logits of the DeepSeek-V3.2 indexer into the caller's fp32 buffer (b, sq, capacity)", py::arg("q_idx"), py::arg("weights"),
+          py::arg("k_idx_cache"), py::arg("cache_seqlens"), py::arg("logits"), py::arg("k_scale") = py::none(), py::arg("block_table") = py::none(), py::arg("is_causal") = true);
+    m.def("mla_indexer_topk", &mla_indexer_topk, "top-k positions of every logits row into the caller's int32 buffer (b, sq, topk)", py::arg("logits"), py::arg("cache_seqlens"),
+          py::arg("indices"), py::arg("is_causal") = true);
     // three overloads: the signature as it was (every existing call, positional or keyword, resolves to it), the one that continues it with the
     // ragged-batch keywords after rotary_interleaved, and the one that continues that with softmax_scale / softcap
     m.def("fwd_kvcache",

@@ -155,9 +155,29 @@ class MlaSparseParamsV2(_Params):
     _fields_ = MlaSparseParams._fields_ + [("kv_format", _i32), ("reserved2_", _i32)]
 
 
+class MlaIndexerParams(_Params):
+    """fa_mla_indexer_params: index logits of the DeepSeek-V3.2 indexer (fa_run_mla_indexer_logits)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("q_idx", _vp), ("weights", _vp), ("k_idx_cache", _vp), ("k_scale", _vp), ("logits", _vp),
+                ("cache_seqlens", _vp), ("block_table", _vp),
+                ("b", _i32), ("seqlen_q", _i32), ("seqlen_cache", _i32), ("h", _i32), ("d", _i32), ("dtype", _i32), ("k_format", _i32), ("is_causal", _i32),
+                ("page_block_size", _i32), ("num_blocks", _i32), ("reserved_", ctypes.c_int64),
+                ("q_idx_stride", Strides), ("weights_stride", Strides),
+                ("k_cache_batch_stride", ctypes.c_int64), ("k_cache_row_stride", ctypes.c_int64), ("k_scale_batch_stride", ctypes.c_int64),
+                ("k_scale_row_stride", ctypes.c_int64), ("logits_batch_stride", ctypes.c_int64), ("logits_row_stride", ctypes.c_int64),
+                ("block_table_stride", ctypes.c_int64)]
+
+
+class MlaTopkParams(_Params):
+    """fa_mla_topk_params: the top-k selection over index logits (fa_run_mla_indexer_topk)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("logits", _vp), ("indices", _vp), ("cache_seqlens", _vp),
+                ("b", _i32), ("seqlen_q", _i32), ("seqlen_cache", _i32), ("topk", _i32), ("is_causal", _i32), ("reserved_", _i32),
+                ("logits_batch_stride", ctypes.c_int64), ("logits_row_stride", ctypes.c_int64)]
+
+
 FA_MLA_KV_16BIT = 0
 FA_MLA_KV_FP8_ROWS656 = 1       # 656-byte latent rows: 512 e4m3 codes, four fp32 scales, 64 rope elements of q's dtype; kv_cache_stride in bytes
 FA_CACHE_FP8_E4M3 = 1
+FA_IDX_K_FP8_E4M3 = 1         # k_format of fa_mla_indexer_params: index keys as OCP e4m3 codes, strides in bytes
 
 
 _lib = None
@@ -218,6 +238,10 @@ def lib():
         L.fa_mla_sparse_workspace_bytes.restype = ctypes.c_int64
         L.fa_mla_sparse_num_splits.argtypes = [_vp]
         L.fa_mla_sparse_num_splits.restype = ctypes.c_int32
+        L.fa_run_mla_indexer_logits.argtypes = [ctypes.POINTER(MlaIndexerParams), _vp]
+        L.fa_run_mla_indexer_logits.restype = ctypes.c_int
+        L.fa_run_mla_indexer_topk.argtypes = [ctypes.POINTER(MlaTopkParams), _vp]
+        L.fa_run_mla_indexer_topk.restype = ctypes.c_int
         L.fa_mha_fwd.argtypes = [_vp] * 5 + [_i32] * 8 + [_vp]
         L.fa_mha_bwd.argtypes = [_vp] * 10 + [_i32] * 8 + [_vp]
         L.fa_mha_varlen_fwd.argtypes = [_vp] * 7 + [_i32] * 8 + [_vp]
@@ -631,3 +655,53 @@ def run_mla_sparse_fwd_kvcache(params, stream=None):
 
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     check(lib().fa_run_mla_sparse_fwd_kvcache(ctypes.byref(params), s))
+
+
+def mla_indexer_params(q_idx, weights, k_idx_cache, logits, cache_seqlens=None, k_scale=None, block_table=None, causal=True):
+    """fa_mla_indexer_params for q_idx (b, sq, h, 128), weights fp32 (b, sq, h), k_idx_cache (b, capacity, 128) in q_idx's dtype or uint8 / float8_e4m3fn
+    (e4m3 codes: a 1-byte dtype, so its strides are bytes, as the format asks) - or, with block_table, a pool (num_blocks, page_block_size, 128) - k_scale
+    fp32 (b, capacity) / (num_blocks, page_block_size) or None, and the caller's fp32 buffer logits (b, sq, capacity): torch tensors with arbitrary strides."""
+    b, sq, h, d = q_idx.shape
+    p = MlaIndexerParams()
+    p.q_idx, p.weights, p.k_idx_cache, p.logits = (t.data_ptr() for t in (q_idx, weights, k_idx_cache, logits))
+    p.cache_seqlens = None if cache_seqlens is None else cache_seqlens.data_ptr()
+    p.b, p.seqlen_q, p.seqlen_cache, p.h, p.d = b, sq, k_idx_cache.shape[1], h, d
+    p.dtype, p.is_causal = dtype_code(q_idx.dtype), int(causal)
+    p.k_format = FA_IDX_K_FP8_E4M3 if k_idx_cache.element_size() == 1 else FA_MLA_KV_16BIT
+    if block_table is not None:
+        p.block_table, p.block_table_stride = block_table.data_ptr(), block_table.stride(0)
+        p.page_block_size, p.num_blocks = k_idx_cache.shape[1], k_idx_cache.shape[0]
+        p.seqlen_cache = block_table.shape[1] * k_idx_cache.shape[1]
+    if k_scale is not None:
+        p.k_scale, p.k_scale_batch_stride, p.k_scale_row_stride = k_scale.data_ptr(), k_scale.stride(0), k_scale.stride(1)
+    p.q_idx_stride = Strides(q_idx.stride(0), q_idx.stride(1), q_idx.stride(2))
+    p.weights_stride = Strides(weights.stride(0), weights.stride(1), weights.stride(2))
+    p.k_cache_batch_stride, p.k_cache_row_stride = k_idx_cache.stride(0), k_idx_cache.stride(1)
+    p.logits_batch_stride, p.logits_row_stride = logits.stride(0), logits.stride(1)
+    return p
+
+
+def run_mla_indexer_logits(params, stream=None):
+    """fa_run_mla_indexer_logits"""
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    check(lib().fa_run_mla_indexer_logits(ctypes.byref(params), s))
+
+
+def mla_topk_params(logits, indices, cache_seqlens=None, causal=True):
+    """fa_mla_topk_params for logits fp32 (b, sq, capacity), any batch / row strides, and the contiguous int32 buffer indices (b, sq, topk)"""
+    p = MlaTopkParams()
+    p.logits, p.indices = logits.data_ptr(), indices.data_ptr()
+    p.cache_seqlens = None if cache_seqlens is None else cache_seqlens.data_ptr()
+    p.b, p.seqlen_q, p.seqlen_cache, p.topk, p.is_causal = logits.shape[0], logits.shape[1], logits.shape[2], indices.shape[-1], int(causal)
+    p.logits_batch_stride, p.logits_row_stride = logits.stride(0), logits.stride(1)
+    return p
+
+
+def run_mla_indexer_topk(params, stream=None):
+    """fa_run_mla_indexer_topk"""
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    check(lib().fa_run_mla_indexer_topk(ctypes.byref(params), s))

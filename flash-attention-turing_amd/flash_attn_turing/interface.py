@@ -789,3 +789,154 @@ def flash_mla_sparse_with_kvcache(q, kv_cache, cache_seqlens, indices, *, head_d
         cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
     out, lse = _C.fwd_mla_sparse_kvcache(q, kv_cache, indices, cache_seqlens, num_splits, block_table, softmax_scale, head_dim_v)
     return (out, lse) if return_softmax_lse else out
+
+
+# ---- the DeepSeek-V3.2 indexer: index logits and top-k selection in front of flash_mla_sparse_with_kvcache ----------------------------------------
+
+def _check_indexer_lengths(cache_seqlens, b, device, like="q_idx"):
+    if isinstance(cache_seqlens, bool) or not isinstance(cache_seqlens, (int, torch.Tensor)):
+        raise ValueError(f"cache_seqlens must be an int32 tensor (batch,) on {like}'s device or an int")
+    if isinstance(cache_seqlens, torch.Tensor) and (cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (b,) or cache_seqlens.device != device):
+        raise ValueError(f"cache_seqlens must be an int32 tensor (batch,) on {like}'s device or an int")
+    if isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((b,), max(min(cache_seqlens, 2 ** 31 - 1), -2 ** 31), dtype=torch.int32, device=device)
+    return cache_seqlens
+
+
+def _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, block_table, causal):
+    """the checks of flash_mla_indexer_logits; returns (q_idx with addressable strides, cache_seqlens as a tensor, capacity)"""
+    if not isinstance(q_idx, torch.Tensor) or q_idx.dim() != 4:
+        raise ValueError("q_idx must be a rank-4 tensor (batch, seqlen_q, index_heads, 128)")
+    if q_idx.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"q_idx must be fp16 or bf16, got {q_idx.dtype}")
+    b, sq, h, d = q_idx.shape
+    if d != 128:
+        raise ValueError(f"q_idx must be 128 wide, got head_dim {d}")
+    if h not in (16, 32, 64):
+        raise ValueError(f"q_idx must have 16, 32 or 64 index heads, got {h}")
+    if sq < 1:
+        raise ValueError(f"q_idx needs seqlen_q >= 1, got shape {tuple(q_idx.shape)}")
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32:
+        raise ValueError("weights must be a float32 tensor (batch, seqlen_q, index_heads)")
+    if tuple(weights.shape) != (b, sq, h) or weights.device != q_idx.device:
+        raise ValueError(f"weights must have shape (batch, seqlen_q, index_heads) = ({b}, {sq}, {h}) on q_idx's device, got {tuple(weights.shape)}")
+    if not isinstance(k_idx_cache, torch.Tensor) or k_idx_cache.dim() != 3:
+        raise ValueError("k_idx_cache must be a rank-3 tensor (batch, capacity, 128), or a page pool (num_blocks, page_block_size, 128) with block_table")
+    fp8 = k_idx_cache.dtype in (torch.uint8, torch.float8_e4m3fn)
+    if not fp8 and k_idx_cache.dtype != q_idx.dtype:
+        raise ValueError(f"k_idx_cache must have q_idx's dtype ({q_idx.dtype}) or hold e4m3 codes (float8_e4m3fn / uint8), got {k_idx_cache.dtype}")
+    if k_idx_cache.shape[2] != 128:
+        raise ValueError(f"k_idx_cache must be 128 wide, got {k_idx_cache.shape[2]}")
+    if k_idx_cache.device != q_idx.device:
+        raise ValueError("k_idx_cache must be on q_idx's device")
+    # the kernels read a key with 16-byte loads: a view they cannot address is refused, never copied
+    unit = 16 if fp8 else 8
+    what = "16 bytes" if fp8 else "8 elements"
+    if k_idx_cache.stride(2) != 1:
+        raise ValueError("k_idx_cache: the last dimension must be contiguous")
+    if k_idx_cache.stride(0) % unit != 0 or k_idx_cache.stride(1) % unit != 0 or k_idx_cache.stride(1) < 128 or k_idx_cache.stride(0) < 0:
+        raise ValueError(f"k_idx_cache: the batch / page and row strides must be multiples of {what} with rows at least 128 apart, got strides {tuple(k_idx_cache.stride())}")
+    if k_idx_cache.storage_offset() % unit != 0 or (k_idx_cache.device.type != "meta" and k_idx_cache.data_ptr() % 16 != 0):
+        raise ValueError(f"k_idx_cache must start at a multiple of {what}, got storage offset {k_idx_cache.storage_offset()}")
+    if block_table is not None:
+        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
+            raise ValueError("block_table must be an int32 tensor")
+        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.device != q_idx.device:
+            raise ValueError("block_table must have shape (batch, max_blocks_per_seq) on q_idx's device")
+        if k_idx_cache.shape[1] < 1 or k_idx_cache.shape[1] % 16 != 0:
+            raise ValueError(f"page_block_size (k_idx_cache.shape[1] with block_table) must be a positive multiple of 16, got {k_idx_cache.shape[1]}")
+        if block_table.shape[1] < 1:
+            raise ValueError("block_table needs at least one column")
+        capacity = block_table.shape[1] * k_idx_cache.shape[1]
+    else:
+        if k_idx_cache.shape[0] != b:
+            raise ValueError(f"k_idx_cache batch ({k_idx_cache.shape[0]}) must match q_idx's ({b})")
+        capacity = k_idx_cache.shape[1]
+    if capacity >= 2 ** 31 - 2 ** 14:
+        raise ValueError(f"k_idx_cache / block_table: a capacity of {capacity} keys does not fit")
+    if k_scale is not None:
+        if not isinstance(k_scale, torch.Tensor) or k_scale.dtype != torch.float32:
+            raise ValueError("k_scale must be a float32 tensor with one scale per cached token, or None")
+        if tuple(k_scale.shape) != tuple(k_idx_cache.shape[:2]) or k_scale.device != q_idx.device:
+            raise ValueError(f"k_scale must have shape {tuple(k_idx_cache.shape[:2])} (k_idx_cache without its last dimension) on q_idx's device, got {tuple(k_scale.shape)}")
+        if k_scale.device.type != "meta" and k_scale.data_ptr() % 4 != 0:
+            raise ValueError("k_scale must be 4-byte aligned")
+    cache_seqlens = _check_indexer_lengths(cache_seqlens, b, q_idx.device)
+    if not isinstance(causal, bool):
+        raise ValueError(f"causal must be a bool, got {causal!r}")
+    if q_idx.stride(3) != 1 or any(q_idx.stride(i) % 8 != 0 for i in range(3)) or q_idx.data_ptr() % 16 != 0:
+        q_idx = q_idx.contiguous()              # (a token's index queries are 16 KB: unlike the cache they may be copied)
+    return q_idx, cache_seqlens, capacity
+
+
+def flash_mla_indexer_logits(q_idx, weights, k_idx_cache, cache_seqlens, *, k_scale=None, block_table=None, causal=True):
+    """Index logits of the DeepSeek-V3.2 "lightning indexer": one fp32 logit per (query token, cached key), the input of flash_mla_indexer_topk.
+
+    q_idx: (batch, seqlen_q, index_heads, 128) fp16 / bf16, index_heads 16, 32 or 64.  RoPE and any scale of q are the caller's (fold a scale into weights).
+    weights: (batch, seqlen_q, index_heads) float32, any strides: the learned per-head weights of the token.
+    k_idx_cache: (batch, capacity, 128) in q_idx's dtype, or torch.float8_e4m3fn / torch.uint8 (OCP e4m3 codes), used in place; with block_table
+    (int32 (batch, max_blocks), last dim contiguous) a page pool (num_blocks, page_block_size, 128), page_block_size a multiple of 16, entries clamped
+    min(uint32(entry), num_blocks - 1).  Row and batch / page strides and the storage offset must be multiples of 16 bytes (8 elements of a 16-bit
+    cache): anything else is a ValueError, never a copy.
+    k_scale: None (= 1.0) or float32 (batch, capacity) / (num_blocks, page_block_size), one scale per cached token, any strided view - the values and
+    the scales of one buffer laid out block by block can be passed as two views of it.
+    cache_seqlens: int32 tensor (batch,) on q_idx's device, or an int.
+
+    With L_i = min(max(cache_seqlens[i], 0), capacity), token t sees the keys j < n_t, n_t = L_i without ``causal``, else
+    min(L_i, max(L_i - seqlen_q + t + 1, 0)) - the rule of flash_mla_with_kvcache.  In fp32 math, for j < n_t:
+    ``logits[i, t, j] = k_scale[j] * sum_h weights[t, h] * relu(q_idx[t, h, :] . k[j, :])``, relu(x) = x > 0 ? x : 0, k the element of a 16-bit cache or
+    float(code) of an FP8 one.  FP8 codes are widened exactly and multiplied with q_idx in q_idx's dtype; nothing is quantised.
+    Returns logits (batch, seqlen_q, capacity) float32, freshly allocated; entries at j >= n_t are NOT written (flash_mla_indexer_topk never reads them).
+    Never read, so they may hold NaN codes and NaN scales: cache rows and scales at or past L_i, pages wholly past L_i, pages no sequence references.
+    Non-finite inputs have no value contract (memory safety only).  No host synchronisation: lengths, tables and scales are read on the device and
+    a captured call replays with the values then in memory.  Deterministic; paged and contiguous calls over the same logical cache give the same bits.
+    Out of scope: FP8 q_idx, other head counts or widths, appending to the index cache, cu_seqlens_q.  Wrong shapes, dtypes or views are a ValueError
+    that names the argument."""
+    q_idx, cache_seqlens, capacity = _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, block_table, causal)
+    logits = torch.empty(q_idx.shape[0], q_idx.shape[1], capacity, dtype=torch.float32, device=q_idx.device)
+    _C.mla_indexer_logits(q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale, block_table, causal)
+    return logits
+
+
+def _check_topk(topk):
+    if isinstance(topk, bool) or not isinstance(topk, int) or topk < 32 or topk % 32 != 0:
+        raise ValueError(f"topk must be a positive multiple of 32, got {topk!r}")
+
+
+def flash_mla_indexer_topk(logits, cache_seqlens, topk, *, causal=True):
+    """The ``indices`` of flash_mla_sparse_with_kvcache from index logits: per query token the topk visible key positions with the largest logits.
+
+    logits: (batch, seqlen_q, capacity) float32, last dim contiguous, any batch / row strides (what flash_mla_indexer_logits returns, or a view).
+    cache_seqlens, causal: as in flash_mla_indexer_logits; they give n_t, the keys token t sees.  topk: a positive multiple of 32.
+    The selection is exact.  fp32 values are ordered by the integer key u(x) = bits(x) ^ (0xffffffff if the sign bit is set else 0x80000000): -0 < +0,
+    and a NaN with the sign bit clear is above +inf.  Row (i, t): if n_t <= topk it is 0, 1, .., n_t - 1 followed by -1; otherwise the topk
+    positions below n_t with the largest keys, ties at the threshold going to the lower positions, in ascending position order.  Entries at
+    j >= n_t are never read.  Returns indices (batch, seqlen_q, topk) int32, contiguous.  No host synchronisation; deterministic."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3 or logits.dtype != torch.float32:
+        raise ValueError("logits must be a float32 tensor (batch, seqlen_q, capacity)")
+    if logits.shape[1] < 1:
+        raise ValueError(f"logits needs seqlen_q >= 1, got shape {tuple(logits.shape)}")
+    if logits.shape[2] > 1 and logits.stride(2) != 1:
+        raise ValueError("logits: the last dimension must be contiguous")
+    if logits.stride(0) < 0 or logits.stride(1) < 0:
+        raise ValueError("logits: strides must not be negative")
+    _check_topk(topk)
+    cache_seqlens = _check_indexer_lengths(cache_seqlens, logits.shape[0], logits.device, like="logits")
+    if not isinstance(causal, bool):
+        raise ValueError(f"causal must be a bool, got {causal!r}")
+    indices = torch.empty(logits.shape[0], logits.shape[1], topk, dtype=torch.int32, device=logits.device)
+    _C.mla_indexer_topk(logits, cache_seqlens, indices, causal)
+    return indices
+
+
+def flash_mla_index_with_kvcache(q_idx, weights, k_idx_cache, cache_seqlens, topk, *, k_scale=None, block_table=None, causal=True, return_logits=False):
+    """flash_mla_indexer_logits followed by flash_mla_indexer_topk over a logits buffer allocated here: two launches, the bits of the two calls in
+    sequence.  Returns indices (batch, seqlen_q, topk) int32 - what flash_mla_sparse_with_kvcache takes as it is - and, with ``return_logits``, the
+    logits (batch, seqlen_q, capacity) float32 as well."""
+    _check_topk(topk)
+    q_idx, cache_seqlens, capacity = _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, block_table, causal)
+    logits = torch.empty(q_idx.shape[0], q_idx.shape[1], capacity, dtype=torch.float32, device=q_idx.device)
+    _C.mla_indexer_logits(q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale, block_table, causal)
+    indices = torch.empty(q_idx.shape[0], q_idx.shape[1], topk, dtype=torch.int32, device=q_idx.device)
+    _C.mla_indexer_topk(logits, cache_seqlens, indices, causal)
+    return (indices, logits) if return_logits else indices

@@ -817,6 +817,76 @@ typedef struct fa_mla_sparse_params_v2 {
     int32_t reserved2_;         /* 0 */
 } fa_mla_sparse_params_v2;
 
+/* The DeepSeek-V3.2 indexer in front of sparse MLA decode (FA_HAS_MLA_INDEXER): index logits over an index-key cache, and the top-k selection that
+ * turns them into the `indices` of fa_mla_sparse_params.  Two launches, two structs; both carry the {struct_size, magic} header, struct_size must be
+ * the struct's own size.  FA_ABI_VERSION is unchanged.
+ * Visibility, shared by both: L_i = min(max(cache_seqlens[i], 0), seqlen_cache) (cache_seqlens NULL: seqlen_cache); token t of sequence i sees the
+ * keys j < n_t, n_t = L_i without is_causal, else min(L_i, max(L_i - seqlen_q + t + 1, 0)): the rule of fa_mla_params.
+ * fa_mla_indexer_params.  q_idx (b, seqlen_q, h, 128) of `dtype`, h 16, 32 or 64, strides in elements (multiples of 8, pointer 16-byte aligned);
+ * weights fp32 (b, seqlen_q, h), any strides in elements; k_idx_cache (b, seqlen_cache, 128) - k_cache_batch_stride / k_cache_row_stride - or, with
+ * block_table, a pool (num_blocks, page_block_size, 128) whose page stride is k_cache_batch_stride, entries clamped min(uint32(entry), num_blocks - 1).
+ * k_format FA_MLA_KV_16BIT: elements of `dtype`, strides in elements, multiples of 8.  k_format FA_IDX_K_FP8_E4M3: OCP e4m3 codes, strides in BYTES,
+ * multiples of 16; pointer 16-byte aligned either way; one sequence (one page) spans less than 2^31 bytes.  k_scale: NULL (= 1.0) or one fp32 per
+ * cached token at k_scale[i * k_scale_batch_stride + j * k_scale_row_stride] (a page in the place of i when paged), strides in elements, any value.
+ * In fp32 math, for j < n_t:  logit[i, t, j] = k_scale[j] * sum_h weights[t, h] * relu(q_idx[t, h, :] . k[j, :]),  relu(x) = x > 0 ? x : 0, written to
+ * logits[i * logits_batch_stride + t * logits_row_stride + j] (strides in elements, 64-bit offsets).  An entry at j >= n_t is never written; cache rows
+ * and scales at or past L_i, pages wholly past L_i and pages no sequence references are never read.  FP8 codes are widened exactly and multiplied in
+ * `dtype`; nothing is quantised.  Non-finite inputs have no value contract.  No host synchronisation; paged == contiguous bit for bit; deterministic.
+ * fa_mla_topk_params.  logits as written above (seqlen_cache = its last dimension); indices int32 (b, seqlen_q, topk) contiguous, topk a positive
+ * multiple of 32.  fp32 values are ordered by u(x) = bits(x) ^ (bits(x) >> 31 ? 0xffffffff : 0x80000000).  Row (i, t): n_t <= topk gives 0, 1, ..,
+ * n_t - 1 followed by -1; otherwise the topk positions below n_t with the largest keys, ties at the threshold to the lower positions, in ascending
+ * position order.  Entries at j >= n_t are never read.  Exact and deterministic: what fa_run_mla_sparse_fwd_kvcache takes as it is.
+ * Errors name the field: NULL pointers FA_ERR_NULL_POINTER, h / d FA_ERR_BAD_HEADDIM, dtype / k_format FA_ERR_BAD_DTYPE, sizes, topk, paging and
+ * non-zero reserved words FA_ERR_BAD_SHAPE, strides and alignment FA_ERR_BAD_STRIDE, the header FA_ERR_BAD_ABI.  b == 0 is FA_OK without a launch. */
+#define FA_HAS_MLA_INDEXER 1
+#define FA_IDX_K_FP8_E4M3 1
+typedef struct fa_mla_indexer_params {
+    uint32_t struct_size;       /* sizeof(fa_mla_indexer_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const void* q_idx;
+    const float* weights;
+    const void* k_idx_cache;
+    const float* k_scale;       /* NULL = 1.0 */
+    float* logits;
+    const int32_t* cache_seqlens;
+    const int32_t* block_table; /* paged cache; NULL = contiguous */
+    int32_t b;
+    int32_t seqlen_q;
+    int32_t seqlen_cache;
+    int32_t h;                  /* 16, 32 or 64 */
+    int32_t d;                  /* 128 */
+    int32_t dtype;
+    int32_t k_format;           /* FA_MLA_KV_16BIT / FA_IDX_K_FP8_E4M3 */
+    int32_t is_causal;
+    int32_t page_block_size;
+    int32_t num_blocks;
+    int64_t reserved_;          /* 0 */
+    fa_strides q_idx_stride, weights_stride;
+    int64_t k_cache_batch_stride;
+    int64_t k_cache_row_stride;
+    int64_t k_scale_batch_stride;
+    int64_t k_scale_row_stride;
+    int64_t logits_batch_stride;
+    int64_t logits_row_stride;
+    int64_t block_table_stride;
+} fa_mla_indexer_params;
+
+typedef struct fa_mla_topk_params {
+    uint32_t struct_size;       /* sizeof(fa_mla_topk_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const float* logits;
+    int32_t* indices;
+    const int32_t* cache_seqlens;
+    int32_t b;
+    int32_t seqlen_q;
+    int32_t seqlen_cache;
+    int32_t topk;               /* a positive multiple of 32 */
+    int32_t is_causal;
+    int32_t reserved_;          /* 0 */
+    int64_t logits_batch_stride;
+    int64_t logits_row_stride;
+} fa_mla_topk_params;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -903,6 +973,11 @@ int fa_run_mla_sparse_fwd_kvcache(const fa_mla_sparse_params* params, void* stre
 /* Host-only, like fa_mla_workspace_bytes / fa_mla_num_splits.  Negative = error code, exactly those of the launch. */
 int64_t fa_mla_sparse_workspace_bytes(const fa_mla_sparse_params* params);
 int32_t fa_mla_sparse_num_splits(const fa_mla_sparse_params* params);
+
+/* ---- the indexer in front of sparse MLA decode (fa_mla_indexer_params / fa_mla_topk_params above) --- */
+/* One launch each on `stream`, no workspace, no host synchronisation: lengths, tables and scales are read on the device. */
+int fa_run_mla_indexer_logits(const fa_mla_indexer_params* params, void* stream);
+int fa_run_mla_indexer_topk(const fa_mla_topk_params* params, void* stream);
 
 /* ---- measurement helpers ----------------------------------------------------------------- */
 /* Algorithmic FLOPs of one forward call (4*b*h*sq*sk*d, causal counts only visible pairs);

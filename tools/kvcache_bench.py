@@ -82,6 +82,12 @@ noise figure).  Against it, interleaved in one process: (i) the identity list 0 
 them) on one cache of that length, rotating over lists, (ii) 2048 random positions, sorted, (iii) the same positions unsorted.  At b in {1, 8} a second line
 per point records arm (i) under forced num_splits 8, 16, 32, 64 next to the automatic count, timed twice (profiles/kvcache_mla_sparse_bench.log).
 
+--mla-indexer measures the DeepSeek-V3.2 indexer (flash_mla_indexer_logits / flash_mla_indexer_topk): bf16 q_idx, FP8 keys with per-token scales, 64 index
+heads, seqlen_q 1, topk 2048, pages of 64 (--paged P replaces the page size), b in {1, 8, 64} x L in {4k, 32k, 128k} (--length replaces them).  Per point,
+interleaved in one process: the logits call; the torch formulation of the logits (dequantise, einsum, relu, weighted sum, * k_scale; it reads the pool
+as a contiguous cache, i.e. without the gather a paged cache would cost it) timed TWICE as its own noise figure; the selection; torch.topk on the same
+logits.  The logits call is also stated against b * L * 132 B / time as a fraction of 6.3 TB/s.  Caches rotate over 256 MiB (profiles/kvcache_mla_indexer_bench.log).
+
 --baseline-library PATH records an interleaved A/B of the plain (no window) call through the C ABI of this build and of the library at
 PATH (e.g. a build of the parent commit), on the same data; the outputs must agree bit for bit.  --length L (repeatable) replaces the
 grid's cache lengths."""
@@ -1033,6 +1039,49 @@ def run_mla_sparse_fp8(lengths, pages, rounds):
         yield run_mla_sparse_fp8_point(b, h, tuple(lengths or (32768, 131072)), (pages or [64])[0], rounds)
 
 
+def run_mla_indexer_point(b, L, page, rounds, topk=2048, h=64):
+    """the logits call, the torch formulation of it (twice), the selection and torch.topk on the same logits; interleaved"""
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(b * 1000003 + L)
+    kbytes = b * L * 132
+    n = max(1, min(512, math.ceil(WORKING_SET / kbytes)))
+    cols = L // page
+    q = torch.randn(b, 1, h, 128, device=dev, generator=gen).to(torch.bfloat16)
+    w = torch.randn(b, 1, h, device=dev, generator=gen) * (h ** -0.5)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    sets = []
+    for _ in range(n):
+        pool = torch.randn(b * cols, page, 128, device=dev, generator=gen).to(torch.float8_e4m3fn)
+        scales = torch.rand(b * cols, page, device=dev, generator=gen) + 0.5
+        table = torch.randperm(b * cols, device=dev, generator=gen).to(torch.int32).view(b, cols)
+        sets.append((pool, scales, table))
+    ours = lambda i: F.flash_mla_indexer_logits(q, w, sets[i % n][0], cs, k_scale=sets[i % n][1], block_table=sets[i % n][2], causal=True)
+
+    def torch_logits(i):
+        pool, scales, _ = sets[i % n]
+        kf = pool.view(b, L, 128).to(torch.bfloat16)
+        s = torch.einsum("bthd,bjd->bthj", q, kf).float()
+        return torch.einsum("bth,bthj->btj", w, torch.relu(s)) * scales.view(b, 1, L)
+
+    logits = [ours(i) for i in range(min(n, 8))]
+    sel = lambda i: F.flash_mla_indexer_topk(logits[i % len(logits)], cs, topk, causal=True)
+    tsel = lambda i: torch.topk(logits[i % len(logits)], topk, dim=-1).indices
+    # what is timed computes the same thing: the selected sets agree wherever the logits have no equal entries at the threshold
+    same = bool(torch.equal(torch.sort(tsel(0), dim=-1).values.int(), sel(0)))
+    ms = _interleaved({"logits": ours, "torch_logits": torch_logits, "torch_logits_again": torch_logits, "topk": sel, "torch_topk": tsel}, n, rounds)
+    tbs = kbytes / (ms["logits"] * 1e-3) / 1e12
+    return dict(mla_indexer=True, b=b, L=L, h=h, topk=topk, seqlen_q=1, dtype="bfloat16", k_format="fp8_e4m3+scale", page_block_size=page, caches_rotated=n,
+                ms={k: round(v, 5) for k, v in ms.items()}, key_bytes=kbytes, logits_tb_s=round(tbs, 3), logits_fraction_of_6p3_tb_s=round(tbs * 1e12 / HBM_ACHIEVABLE, 3),
+                torch_logits_over_logits=round(ms["torch_logits"] / ms["logits"], 2), torch_noise=round(ms["torch_logits_again"] / ms["torch_logits"], 3),
+                torch_topk_over_topk=round(ms["torch_topk"] / ms["topk"], 2),
+                torch_total_over_total=round((ms["torch_logits"] + ms["torch_topk"]) / (ms["logits"] + ms["topk"]), 2), same_selection=same)
+
+
+def run_mla_indexer(lengths, pages, rounds):
+    for b, L in itertools.product((1, 8, 64), tuple(lengths or (4096, 32768, 131072))):
+        yield run_mla_indexer_point(b, L, (pages or [64])[0], rounds)
+
+
 def _baseline_lib(path):
     L = ctypes.CDLL(os.path.abspath(path))
     L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
@@ -1121,6 +1170,9 @@ def main():
                                                        "(timed twice); contiguous and, with --paged P, through a block table")
     ap.add_argument("--mla-sparse", action="store_true", help="sparse MLA decode (flash_mla_sparse_with_kvcache, topk 2048, pages of 64 or --paged P) against the dense MLA call "
                                                               "at L = topk (timed twice): the identity list, sorted and unsorted random positions of L in {32k, 128k}; forced splits")
+    ap.add_argument("--mla-indexer", action="store_true", help="the DeepSeek-V3.2 indexer (flash_mla_indexer_logits / flash_mla_indexer_topk; bf16, FP8 keys with scales, 64 heads, "
+                                                               "topk 2048, pages of 64 or --paged P): the logits call against its HBM bound and the torch formulation (timed twice), the "
+                                                               "selection against torch.topk")
     a = ap.parse_args()
     base = _baseline_lib(a.baseline_library) if a.baseline_library else None
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
@@ -1130,6 +1182,10 @@ def main():
     with torch.no_grad():
         if a.ragged and base is None:
             for line in run_ragged(a.quick, a.rounds):
+                print(json.dumps(line), flush=True)
+            return
+        if a.mla_indexer:
+            for line in run_mla_indexer(a.length, a.paged, a.rounds):
                 print(json.dumps(line), flush=True)
             return
         if a.mla_sparse:
