@@ -1112,4 +1112,57 @@ int fa_run_mla_indexer_topk(const fa_mla_topk_params* user, void* stream) {
     return hip_status(fa::launch_mla_indexer_topk(tp, (hipStream_t)stream), "fa_mla_indexer_topk launch");
 }
 
+// ---- MLA prefill attention -------------------------------------------------------------------------------------------------------------------
+// fa_mla_prefill_params -> MlaPrefillParams, validated.  The tensor checks are those of fa_run_mha_fwd (check_tensor: alignment, strides, the 2^31-byte
+// extent of one sequence); a packed call states no max_seqlen, so there the extent is the whole packed tensor's.
+int fa_run_mla_prefill_fwd(const fa_mla_prefill_params* user, void* stream) {
+    fa_mla_prefill_params local;
+    int rc = import_exact(user, local, "fa_mla_prefill_params");
+    if (rc) return rc;
+    const fa_mla_prefill_params* p = &local;
+    if (p->b < 0 || p->seqlen_q < 0 || p->seqlen_k < 0 || p->h <= 0 || p->h_k <= 0)
+        return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d seqlen_k=%d h=%d h_k=%d", p->b, p->seqlen_q, p->seqlen_k, p->h, p->h_k);
+    if (p->h % p->h_k != 0) return fail(FA_ERR_BAD_GQA, "h (%d) must be divisible by h_k (%d) for GQA/MQA", p->h, p->h_k);
+    if (p->d_qk != 192) return fail(FA_ERR_BAD_HEADDIM, "d_qk %d unsupported (q and k are 192 wide: 128 no-rope + 64 rope elements)", p->d_qk);
+    if (p->d_v != 128) return fail(FA_ERR_BAD_HEADDIM, "d_v %d unsupported (v and o are 128 wide)", p->d_v);
+    if (p->dtype != FA_FP16 && p->dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", p->dtype);
+    const bool packed = p->cu_seqlens_q != nullptr || p->cu_seqlens_k != nullptr;
+    if (packed && p->cu_seqlens_q == nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_q is NULL but cu_seqlens_k is given (both or neither)");
+    if (packed && p->cu_seqlens_k == nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_k is NULL but cu_seqlens_q is given (both or neither)");
+    if (packed && ((reinterpret_cast<uintptr_t>(p->cu_seqlens_q) | reinterpret_cast<uintptr_t>(p->cu_seqlens_k)) & 3u) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "cu_seqlens_q / cu_seqlens_k must be 4-byte aligned");
+    if (!(p->softmax_scale >= 0.f) || isinf(p->softmax_scale))
+        return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default 192 ** -0.5)", (double)p->softmax_scale);
+    if (packed && (p->total_q < 0 || p->total_k < 0))
+        return fail(FA_ERR_BAD_SHAPE, "total_q (%lld) / total_k (%lld) must be >= 0 with cu_seqlens", (long long)p->total_q, (long long)p->total_k);
+    const int64_t rows_q = packed ? p->total_q : p->seqlen_q, rows_k = packed ? p->total_k : p->seqlen_k;
+    // the attention grid is h_k x row tiles (dense: per batch entry; packed: of all rows, plus one slot per sequence), counted here in tiles of 64 rows - the
+    // smaller of the two tiles fa_fwd_mla_prefill.hip can be built with - and a packed row index is an int
+    const int64_t h_ratio = p->h / p->h_k;
+    const int64_t tiles = (rows_q * h_ratio + fa::kKvcPrefillRows - 1) / fa::kKvcPrefillRows;
+    if (rows_q * h_ratio >= ((int64_t)1 << 31) || rows_k >= ((int64_t)1 << 31) || (packed ? tiles + p->b : tiles * p->b) * p->h_k >= ((int64_t)1 << 31))
+        return fail(FA_ERR_BAD_SHAPE, "call too large: b = %d sequences, %lld query rows x h = %d heads, %lld keys exceed the launch grid", p->b, (long long)rows_q, p->h,
+                    (long long)rows_k);
+    if (p->b == 0 || rows_q == 0) return FA_OK;     // nothing to write
+    if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
+    if ((rc = check_tensor("q", p->q, p->q_stride, rows_q, p->d_qk, packed))) return rc;
+    if ((rc = check_tensor("o", p->o, p->o_stride, rows_q, p->d_v, packed))) return rc;
+    if (rows_k > 0) {
+        if ((rc = check_tensor("k", p->k, p->k_stride, rows_k, p->d_qk, packed))) return rc;
+        if ((rc = check_tensor("v", p->v, p->v_stride, rows_k, p->d_v, packed))) return rc;
+    }
+    fa::MlaPrefillParams kp;
+    memset(&kp, 0, sizeof(kp));
+    kp.q_ptr = p->q; kp.k_ptr = p->k; kp.v_ptr = p->v; kp.o_ptr = p->o; kp.lse_ptr = p->lse;
+    kp.cu_q = p->cu_seqlens_q; kp.cu_k = p->cu_seqlens_k;
+    kp.q = conv(p->q_stride); kp.k = conv(p->k_stride); kp.v = conv(p->v_stride); kp.o = conv(p->o_stride);
+    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_k = p->seqlen_k;
+    kp.h = p->h; kp.h_k = p->h_k; kp.h_ratio = (int32_t)h_ratio;
+    kp.is_causal = p->is_causal ? 1 : 0;
+    kp.total_q = packed ? p->total_q : 0; kp.total_k = packed ? p->total_k : 0;
+    kp.scale = p->softmax_scale > 0.f ? p->softmax_scale : 1.0f / sqrtf((float)p->d_qk);        // (= 192 ** -0.5 rounded once to fp32)
+    kp.scale_log2e = kp.scale * 1.4426950408889634f;
+    return hip_status(fa::launch_fwd_mla_prefill(kp, p->dtype, (hipStream_t)stream), "fa_fwd_mla_prefill launch");
+}
+
 }  // extern "C"

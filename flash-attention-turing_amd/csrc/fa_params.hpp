@@ -301,6 +301,30 @@ hipError_t launch_fwd_kvcache_mla_sparse(KvcacheMlaSparseParams sp, int dtype, h
 hipError_t launch_fwd_kvcache_mla_fp8(KvcacheMlaParams mp, int dtype, hipStream_t stream);
 hipError_t launch_fwd_kvcache_mla_sparse_fp8(KvcacheMlaSparseParams sp, int dtype, hipStream_t stream);
 
+// MLA prefill attention (fa_fwd_mla_prefill.hip, fa_run_mla_prefill_fwd): multi-head attention with 192-wide q / k (128 no-rope columns, then 64 rope
+// columns) and 128-wide v / o, before weight absorption.  Dense: q (b, seqlen_q, h, 192), k (b, seqlen_k, h_k, 192), v (b, seqlen_k, h_k, 128), lse
+// (b, h, seqlen_q).  Packed (cu_q != NULL): q (total_q, h, 192), k / v (total_k, h_k, .), sequence i owns rows cu_q[i] .. cu_q[i + 1] - 1 of q / o and
+// cu_k[i] .. cu_k[i + 1] - 1 of k / v, lse (h, total_q); seqlen_q / seqlen_k and the batch strides are not read.  The LDS-staged body of
+// fa_fwd_kvcache_prefill.hip over plain tensors: no cache, no append, no key split.  A block of its own: no other kernel's kernarg segment changes.
+struct MlaPrefillParams {
+    const void* q_ptr;
+    const void* k_ptr;
+    const void* v_ptr;
+    void* o_ptr;
+    float* lse_ptr;
+    const int32_t* cu_q;        // (b + 1,) or NULL = dense
+    const int32_t* cu_k;
+    TStride q, k, v, o;
+    int32_t b, seqlen_q, seqlen_k, h, h_k, h_ratio;
+    int32_t is_causal;
+    int32_t n_row_tiles;        // filled by the launcher (dense): row tiles of a (batch, KV head)
+    int32_t slots;              // filled by the launcher (packed): tile slots per KV head, ceil(total_q * h_ratio / rows of a tile) + b
+    int64_t total_q, total_k;   // packed: rows of q / o and of k / v (>= cu_q[b] / cu_k[b]; the rows past them are never touched)
+    float scale_log2e;
+    float scale;
+};
+hipError_t launch_fwd_mla_prefill(MlaPrefillParams p, int dtype, hipStream_t stream);
+
 // Rotary embedding on a decode call (fa_kvcache_rotary.hip, fa_kvcache_options_v3).  One fused launch takes the place of the append: it
 // rotates k_new into the cache, copies / quantises v_new, and writes the rotated q into `q_image`, a contiguous (b, seqlen_q, h, d) buffer of
 // q's dtype at the head of the caller's workspace; the attention kernels then read that image as their q.  A block of its own and not

@@ -566,6 +566,58 @@ std::vector<at::Tensor> mha_fwd_mla_kvcache(at::Tensor q, at::Tensor kv_cache, c
     return {o, l};
 }
 
+// MLA prefill attention (fa_run_mla_prefill_fwd): dense q (b, sq, h, 192), k (b, sk, h_k, 192), v (b, sk, h_k, 128) -> out (b, sq, h, 128), lse (b, h, sq);
+// packed (both cu_seqlens) q (total_q, h, 192), k (total_k, h_k, 192), v (total_k, h_k, 128) -> out (total_q, h, 128), lse (h, total_q).  Nothing is copied:
+// the tensors go to the library with the strides they have, and a view it cannot address is its error.  softmax_scale: rounded once to fp32, None =
+// the library's default 192 ** -0.5.
+std::vector<at::Tensor> mha_fwd_mla_prefill(at::Tensor q, at::Tensor k, at::Tensor v, c10::optional<at::Tensor> cu_seqlens_q_, c10::optional<at::Tensor> cu_seqlens_k_,
+                                            bool is_causal, c10::optional<double> softmax_scale) {
+    const bool packed = cu_seqlens_q_.has_value() || cu_seqlens_k_.has_value();
+    TORCH_CHECK(cu_seqlens_q_.has_value() == cu_seqlens_k_.has_value(), "cu_seqlens_q and cu_seqlens_k come both or neither");
+    const int64_t rank = packed ? 3 : 4;
+    TORCH_CHECK(q.dim() == rank && k.dim() == rank && v.dim() == rank, "q, k, v must be rank-", rank, " tensors");
+    check_qkv_common(q, k, v);
+    const int64_t batch_size = packed ? cu_seqlens_q_->numel() - 1 : q.size(0);
+    const int64_t rows_q = q.size(-3), rows_k = k.size(-3), num_heads = q.size(-2), num_heads_k = k.size(-2);
+    TORCH_CHECK(v.size(-3) == rows_k && v.size(-2) == num_heads_k, "k and v must agree in rows and heads");
+    TORCH_CHECK(packed || (k.size(0) == batch_size && v.size(0) == batch_size), "k/v batch size must match q");
+    TORCH_CHECK(k.size(-1) == q.size(-1), "q / k head_dim must match");
+    TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "num_heads_q must be divisible by num_heads_k for GQA/MQA");
+    TORCH_CHECK(batch_size <= INT32_MAX && (packed || (rows_q <= INT32_MAX && rows_k <= INT32_MAX)) && num_heads <= INT32_MAX && q.size(-1) <= INT32_MAX && v.size(-1) <= INT32_MAX,
+                "sizes must fit in int32");
+    at::Tensor cu_q, cu_k;
+    if (packed) {
+        cu_q = *cu_seqlens_q_; cu_k = *cu_seqlens_k_;
+        check_cu_seqlens(cu_q, cu_k);
+        check_same_device(q, cu_q, "cu_seqlens_q"); check_same_device(q, cu_k, "cu_seqlens_k");
+    }
+    c10::DeviceGuard guard(q.device());
+    // dense: every element of o and l is written (dead rows included); packed: the rows past cu_seqlens_q[-1] are not touched
+    at::Tensor o = packed ? torch::empty({rows_q, num_heads, v.size(-1)}, q.options()) : torch::empty({batch_size, rows_q, num_heads, v.size(-1)}, q.options());
+    at::Tensor l = packed ? torch::empty({num_heads, rows_q}, q.options().dtype(torch::kFloat32))
+                          : torch::empty({batch_size, num_heads, rows_q}, q.options().dtype(torch::kFloat32));
+
+    fa_mla_prefill_params p;
+    FA_PARAMS_INIT(p);
+    p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = o.data_ptr(); p.lse = l.data_ptr<float>();
+    p.b = (int32_t)batch_size; p.h = (int32_t)num_heads; p.h_k = (int32_t)num_heads_k; p.d_qk = (int32_t)q.size(-1); p.d_v = (int32_t)v.size(-1);
+    p.dtype = fa_dtype_of(q); p.is_causal = is_causal;
+    // (rounded once to fp32; 0 means "the default" in the C ABI, so a given scale that is or rounds to 0 is refused here)
+    TORCH_CHECK(!softmax_scale.has_value() || (std::isfinite(*softmax_scale) && (float)*softmax_scale > 0.f && std::isfinite((float)*softmax_scale)),
+                "softmax_scale must be a finite fp32 value > 0 (or None = 192 ** -0.5)");
+    if (softmax_scale.has_value()) p.softmax_scale = (float)*softmax_scale;
+    if (packed) {
+        p.cu_seqlens_q = cu_q.data_ptr<int32_t>(); p.cu_seqlens_k = cu_k.data_ptr<int32_t>();
+        p.total_q = rows_q; p.total_k = rows_k;
+        p.q_stride = strides3(q); p.k_stride = strides3(k); p.v_stride = strides3(v); p.o_stride = strides3(o);
+    } else {
+        p.seqlen_q = (int32_t)rows_q; p.seqlen_k = (int32_t)rows_k;
+        p.q_stride = strides4(q); p.k_stride = strides4(k); p.v_stride = strides4(v); p.o_stride = strides4(o);
+    }
+    check_status(fa_run_mla_prefill_fwd(&p, current_stream(q)));
+    return {o, l};
+}
+
 // Sparse MLA decode over a latent KV cache (fa_run_mla_sparse_fwd_kvcache): q, kv_cache, block_table, cache_seqlens as in mha_fwd_mla_kvcache; indices
 // int32 (b, sq, topk), last dim contiguous, any batch / row strides: the logical key positions of each query token.  out (b, sq, h, 512) and lse (b, h, sq).
 // Indices, lengths and tables are read on the device.
@@ -775,6 +827,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "Sparse MLA decode over a latent KV cache: q (b, sq, h, 576), kv_cache (b, capacity, 1, 576), indices int32 (b, sq, topk) -> [out (b, sq, h, 512), lse]",
           py::arg("q"), py::arg("kv_cache"), py::arg("indices"), py::arg("cache_seqlens") = py::none(), py::arg("num_splits") = 0,
           py::arg("block_table") = py::none(), py::arg("softmax_scale") = py::none(), py::arg("head_dim_v") = 512);
+    m.def("fwd_mla_prefill", &mha_fwd_mla_prefill,
+          "MLA prefill attention: q (b, sq, h, 192), k (b, sk, h_k, 192), v (b, sk, h_k, 128) -> [out (b, sq, h, 128), lse]; packed with both cu_seqlens",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens_q") = py::none(), py::arg("cu_seqlens_k") = py::none(), py::arg("is_causal") = false,
+          py::arg("softmax_scale") = py::none());
     m.def("mla_indexer_logits", &mla_indexer_logits, "index logits of the DeepSeek-V3.2 indexer into the caller's fp32 buffer (b, sq, capacity)", py::arg("q_idx"), py::arg("weights"),
           py::arg("k_idx_cache"), py::arg("cache_seqlens"), py::arg("logits"), py::arg("k_scale") = py::none(), py::arg("block_table") = py::none(), py::arg("is_causal") = true);
     m.def("mla_indexer_topk", &mla_indexer_topk, "top-k positions of every logits row into the caller's int32 buffer (b, sq, topk)", py::arg("logits"), py::arg("cache_seqlens"),

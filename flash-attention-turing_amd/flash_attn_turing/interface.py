@@ -940,3 +940,86 @@ def flash_mla_index_with_kvcache(q_idx, weights, k_idx_cache, cache_seqlens, top
     indices = torch.empty(q_idx.shape[0], q_idx.shape[1], topk, dtype=torch.int32, device=q_idx.device)
     _C.mla_indexer_topk(logits, cache_seqlens, indices, causal)
     return (indices, logits) if return_logits else indices
+
+
+def _check_prefill_view(name, t):
+    """a tensor the prefill kernels address as it is: the last dimension contiguous, every other stride and the storage offset a multiple of 8 elements"""
+    if t.shape[-1] > 1 and t.stride(-1) != 1:
+        raise ValueError(f"{name}: the last dimension must be contiguous, got strides {tuple(t.stride())}")
+    if any(s % 8 != 0 for s in t.stride()[:-1]) or t.storage_offset() % 8 != 0:
+        raise ValueError(f"{name}: strides {tuple(t.stride())} (but the last) and the storage offset {t.storage_offset()} must be multiples of 8 elements "
+                         "(16-byte loads); the view is not copied")
+
+
+def flash_mla_prefill_func(q, k, v, *, cu_seqlens_q=None, cu_seqlens_k=None, softmax_scale=None, causal=False, return_softmax_lse=False):
+    """MLA prefill attention (DeepSeek-V2 / V3 / R1, Kimi K2; forward only): multi-head attention with 192-wide queries and keys and 128-wide values.
+
+    Before weight absorption an MLA layer is ordinary multi-head attention whose q / k rows are 128 no-rope columns followed by 64 rope columns (RoPE
+    applied by the caller) and whose v rows are 128 wide.  This is the prompt side of flash_mla_with_kvcache.
+
+    dense:  q (batch, seqlen_q, nheads, 192), k (batch, seqlen_k, nheads_k, 192), v (batch, seqlen_k, nheads_k, 128)
+            -> out (batch, seqlen_q, nheads, 128) and, with ``return_softmax_lse``, lse (batch, nheads, seqlen_q) fp32 (natural log).
+    packed: q (total_q, nheads, 192), k (total_k, nheads_k, 192), v (total_k, nheads_k, 128) with cu_seqlens_q / cu_seqlens_k, int32 (batch + 1,) on
+            q's device, given both or neither -> out (total_q, nheads, 128), lse (nheads, total_q).  Sequence i owns rows cu_seqlens_q[i] ..
+            cu_seqlens_q[i + 1] - 1 of q and cu_seqlens_k[i] .. cu_seqlens_k[i + 1] - 1 of k / v.  There is no max_seqlen argument: the launch is
+            sized from total_q.  Rows of out / lse at or past cu_seqlens_q[-1] are not written (they hold whatever the allocation held).
+    fp16 / bf16, one dtype for all three; nheads % nheads_k == 0 (GQA / MQA).  The last dimension is contiguous, every other stride and the storage
+    offset are multiples of 8 elements; other views are refused, never copied.  One sequence (packed: the whole tensor) spans less than 2^31 bytes,
+    the limit of flash_attn_func.
+
+    In fp32 math over the visible keys, per sequence with sq_i rows and sk_i keys: ``s_tj = (q_t . k_j) * softmax_scale``; key j is visible to row t
+    iff j < sk_i and, under ``causal``, j <= sk_i - sq_i + t (bottom-right aligned); ``out_t = softmax_j(s_tj) @ v_j``.  A row that sees no key
+    (sq_i > sk_i under causal, sk_i = 0) is O = 0, LSE = 0; empty query sequences are allowed.  A NaN in a query row, or a NaN / +inf score, makes
+    that row's O and LSE NaN; a -inf score only drops the key.  Non-finite V has no contract: the rows of a 64-row tile share the reads of a key, so
+    a non-finite V row that ``causal`` hides from this query row but not from another row of the tile can make this row NaN (0 x NaN).
+    softmax_scale: None = 192 ** -0.5 rounded once to fp32 (None and that value passed explicitly give the same bits); validated like softmax_scale
+    of flash_mla_with_kvcache.
+
+    No host synchronisation (cu_seqlens are read on the device: the call can be captured in a graph and replays with the values then in memory), no
+    key split, so no workspace, and the call is deterministic.  Bit for bit: sequence i of a packed call equals the dense call on that sequence
+    alone (out and lse), a batch entry of a dense call equals the call on it alone, and a power of two moved between q and softmax_scale changes
+    nothing.  Chunked prefill over a cached prefix needs no further API: run the context part with causal=False and the new tokens with
+    causal=True and merge the two results by their LSE (README.md).
+    Out of scope, and without a keyword here: a backward, FP8 or paged inputs, other widths, window_size, softcap, sinks, a key split.  Wrong shapes,
+    dtypes, views or values are a ValueError that names the argument.
+    """
+    packed = cu_seqlens_q is not None or cu_seqlens_k is not None
+    if packed and (cu_seqlens_q is None or cu_seqlens_k is None):
+        raise ValueError("cu_seqlens_q and cu_seqlens_k come both or neither, got only " + ("cu_seqlens_q" if cu_seqlens_k is None else "cu_seqlens_k"))
+    rank = 3 if packed else 4
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != rank:
+            raise ValueError(f"{name} must be a rank-{rank} tensor ({'(total, nheads, head_dim) with cu_seqlens' if packed else '(batch, seqlen, nheads, head_dim)'})")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        bad = next(n for n, t in (("q", q), ("k", k), ("v", v)) if t.requires_grad)
+        raise ValueError(f"{bad} requires grad: flash_mla_prefill_func is forward-only (there is no backward); run it under torch.no_grad() or detach the inputs")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"q must be fp16 or bf16, got {q.dtype}")
+    for name, t in (("k", k), ("v", v)):
+        if t.dtype != q.dtype:
+            raise ValueError(f"{name} must have q's dtype ({q.dtype}), got {t.dtype}")
+        if t.device != q.device:
+            raise ValueError(f"{name} must be on q's device ({q.device}), got {t.device}")
+    if q.shape[-1] != 192:
+        raise ValueError(f"q must be 192 wide (128 no-rope columns, then 64 rope columns), got head_dim {q.shape[-1]}")
+    if k.shape[-1] != 192:
+        raise ValueError(f"k must be 192 wide (128 no-rope columns, then 64 rope columns), got head_dim {k.shape[-1]}")
+    if v.shape[-1] != 128:
+        raise ValueError(f"v must be 128 wide, got head_dim {v.shape[-1]}")
+    if k.shape[:-1] != v.shape[:-1]:
+        raise ValueError(f"k and v must agree in every dimension but the last, got {tuple(k.shape)} and {tuple(v.shape)}")
+    if not packed and k.shape[0] != q.shape[0]:
+        raise ValueError(f"k / v batch ({k.shape[0]}) must match q's ({q.shape[0]})")
+    h, h_k = q.shape[-2], k.shape[-2]
+    if h < 1 or h_k < 1 or h % h_k != 0:
+        raise ValueError(f"nheads of q ({h}) must be a positive multiple of nheads_k of k / v ({h_k})")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        _check_prefill_view(name, t)
+    if packed:
+        _check_cu_seqlens("cu_seqlens_q", cu_seqlens_q, q)
+        _check_cu_seqlens("cu_seqlens_k", cu_seqlens_k, q, batch=cu_seqlens_q.shape[0] - 1)
+    softmax_scale, _ = _check_scale_and_cap(softmax_scale, 0.0)
+    if not isinstance(causal, bool):
+        raise ValueError(f"causal must be a bool, got {causal!r}")
+    out, lse = _C.fwd_mla_prefill(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale)
+    return (out, lse) if return_softmax_lse else out

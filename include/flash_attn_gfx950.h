@@ -887,6 +887,54 @@ typedef struct fa_mla_topk_params {
     int64_t logits_row_stride;
 } fa_mla_topk_params;
 
+/* MLA prefill attention (FA_HAS_MLA_PREFILL; DeepSeek-V2 / V3 / R1, Kimi K2 before weight absorption; the (192, 128) forward of flash-attn and FlashMLA).
+ * Ordinary multi-head attention with d_qk = 192 wide queries and keys (128 no-rope columns, then 64 rope columns, RoPE already applied) and d_v = 128
+ * wide values.  FA_ABI_VERSION is unchanged; the presence of fa_run_mla_prefill_fwd is how a caller detects the feature.  struct_size must be
+ * sizeof(fa_mla_prefill_params) (FA_PARAMS_INIT).
+ *   dense (cu_seqlens_q = cu_seqlens_k = NULL): q (b, seqlen_q, h, 192), k (b, seqlen_k, h_k, 192), v (b, seqlen_k, h_k, 128), o (b, seqlen_q, h, 128),
+ *   lse (b, h, seqlen_q) fp32; total_q / total_k are not read.
+ *   packed (both cu_seqlens given: int32 DEVICE arrays (b + 1,), non-decreasing from a value >= 0): q (total_q, h, 192), k (total_k, h_k, 192), v (total_k,
+ *   h_k, 128), o (total_q, h, 128), lse (h, total_q); sequence i owns rows cu_seqlens_q[i] .. cu_seqlens_q[i + 1] - 1 of q / o and cu_seqlens_k[i] ..
+ *   cu_seqlens_k[i + 1] - 1 of k / v; seqlen_q / seqlen_k and the batch strides are not read; the launch is sized from total_q.  Rows of o / lse at or
+ *   past cu_seqlens_q[b] are left untouched; rows of k / v at or past cu_seqlens_k[b], or of another sequence, never reach a result.
+ *   h % h_k == 0 (GQA / MQA); strides in elements, multiples of 8, row strides at least the row widths, pointers 16-byte aligned; one sequence (packed: the
+ *   whole tensor, as no max_seqlen is stated) spans less than 2^31 bytes, the limit and the error of fa_fwd_params.
+ * In fp32 math over the visible keys, per sequence with sq_i query rows and sk_i keys: s_tj = (q_t . k_j) * softmax_scale; key j is visible to row t iff
+ * j < sk_i and, under is_causal, j <= sk_i - sq_i + t (bottom-right aligned); o_t = softmax_j(s_tj) @ v_j; lse the natural-log logsumexp.  A row that sees no
+ * key (sq_i > sk_i under is_causal, sk_i = 0) is o = 0, lse = 0; empty query sequences are allowed.  A NaN in a query row, or a NaN / +inf score, gives a NaN
+ * row; a -inf score only drops the key.  softmax_scale: finite and > 0, or 0 = the default 192 ** -0.5.
+ * One launch on `stream`, no workspace (there is no key split), no host synchronisation, deterministic.  Sequence i of a packed call equals the dense call
+ * on that sequence alone bit for bit, and so does a batch entry of a dense call.
+ * Errors, the argument named by fa_last_error: d_qk != 192 or d_v != 128 FA_ERR_BAD_HEADDIM, h % h_k FA_ERR_BAD_GQA, dtype FA_ERR_BAD_DTYPE, sizes /
+ * total_q / total_k / softmax_scale FA_ERR_BAD_SHAPE, pointers (one cu_seqlens without the other included) FA_ERR_NULL_POINTER, strides and alignment
+ * FA_ERR_BAD_STRIDE, the header FA_ERR_BAD_ABI.  b == 0 or no query row (total_q == 0; dense: seqlen_q == 0) is FA_OK without a launch.  No backward, FP8
+ * or paged inputs, other widths, window, softcap or sinks: the struct has no field for them. */
+#define FA_HAS_MLA_PREFILL 1
+typedef struct fa_mla_prefill_params {
+    uint32_t struct_size;       /* sizeof(fa_mla_prefill_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const void* q;
+    const void* k;
+    const void* v;
+    void* o;
+    float* lse;
+    const int32_t* cu_seqlens_q;    /* both NULL = dense */
+    const int32_t* cu_seqlens_k;
+    int32_t b;
+    int32_t seqlen_q;
+    int32_t seqlen_k;
+    int32_t h;
+    int32_t h_k;
+    int32_t d_qk;               /* 192 */
+    int32_t d_v;                /* 128 */
+    int32_t dtype;
+    int32_t is_causal;
+    float softmax_scale;        /* 0 = 192 ** -0.5 */
+    fa_strides q_stride, k_stride, v_stride, o_stride;     /* packed: the batch strides are not read */
+    int64_t total_q;            /* packed: rows of q / o */
+    int64_t total_k;            /* packed: rows of k / v */
+} fa_mla_prefill_params;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -978,6 +1026,10 @@ int32_t fa_mla_sparse_num_splits(const fa_mla_sparse_params* params);
 /* One launch each on `stream`, no workspace, no host synchronisation: lengths, tables and scales are read on the device. */
 int fa_run_mla_indexer_logits(const fa_mla_indexer_params* params, void* stream);
 int fa_run_mla_indexer_topk(const fa_mla_topk_params* params, void* stream);
+
+/* ---- MLA prefill attention (fa_mla_prefill_params above) -------------------------------------- */
+/* One launch on `stream`, no workspace, no host synchronisation: cu_seqlens are read on the device. */
+int fa_run_mla_prefill_fwd(const fa_mla_prefill_params* params, void* stream);
 
 /* ---- measurement helpers ----------------------------------------------------------------- */
 /* Algorithmic FLOPs of one forward call (4*b*h*sq*sk*d, causal counts only visible pairs);

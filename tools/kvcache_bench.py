@@ -88,6 +88,14 @@ interleaved in one process: the logits call; the torch formulation of the logits
 as a contiguous cache, i.e. without the gather a paged cache would cost it) timed TWICE as its own noise figure; the selection; torch.topk on the same
 logits.  The logits call is also stated against b * L * 132 B / time as a fraction of 6.3 TB/s.  Caches rotate over 256 MiB (profiles/kvcache_mla_indexer_bench.log).
 
+--mla-prefill measures MLA prefill attention (flash_mla_prefill_func: 192-wide q / k, 128-wide v) on a grid of its own: bf16, h = h_k in {16, 128}, b in
+{1, 4}; sq = sk in {512, 2048, 8192} causal, and a 2048-row chunk over an 8k and a 32k context, non-causal (--quick: b 1, and h 128 up to 2048 rows only).  Per
+point, interleaved in one process, medians: the new call against (a) fwd at head_dim 128 on the same b, s, h - 0.8 x the FLOPs - and (b) what a caller could
+do before: flash_attn_with_kvcache at head_dim 256 on zero-padded q / k / v with the same softmax_scale; each yardstick is timed TWICE as its own noise
+figure.  TFLOP/s of the new call at 2 sq sk h (192 + 128) per batch entry, halved under the mask, of fwd at its own 2 sq sk h (128 + 128)
+(profiles/mla_prefill_bench.log).  With --baseline-library PATH (e.g. tools/abl/libfa_mlap_rows32.so built with -DFA_MLAP_WAVE_ROWS=32) the point becomes an
+A / B of the new call itself through the C ABI of this build (A, timed twice) and of the library at PATH (B).
+
 --baseline-library PATH records an interleaved A/B of the plain (no window) call through the C ABI of this build and of the library at
 PATH (e.g. a build of the parent commit), on the same data; the outputs must agree bit for bit.  --length L (repeatable) replaces the
 grid's cache lengths."""
@@ -1082,6 +1090,86 @@ def run_mla_indexer(lengths, pages, rounds):
         yield run_mla_indexer_point(b, L, (pages or [64])[0], rounds)
 
 
+def _mlap_time(fns, rounds, iters=3):
+    """median ms per call of each arm, the arms taken in turn within every round, `iters` calls per timed batch"""
+    t = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, f in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                f()
+            e1.record()
+            e1.synchronize()
+            t[k].append(e0.elapsed_time(e1) / iters)
+    return {k: statistics.median(v) for k, v in t.items()}
+
+
+def run_mla_prefill_point(b, h, sq, sk, causal, rounds, base=None):
+    """flash_mla_prefill_func against fwd at head_dim 128 and against the zero-padded head_dim-256 KV-cache call, each yardstick twice; or, with a baseline
+    library, the C ABI call of this build (twice) against the baseline's"""
+    dev, dt = torch.device("cuda:0"), torch.bfloat16
+    scale = 192 ** -0.5
+    q, k, v = (torch.randn(b, s, h, d, device=dev, dtype=dt) for s, d in ((sq, 192), (sk, 192), (sk, 128)))
+    flops = 2.0 * sq * sk * h * (192 + 128) * b * (0.5 if causal else 1.0)
+    row = dict(mla_prefill=True, b=b, h=h, sq=sq, sk=sk, causal=bool(causal), dtype="bfloat16")
+    if base is not None:
+        o, lse = torch.empty(b, sq, h, 128, device=dev, dtype=dt), torch.empty(b, h, sq, device=dev)
+        o2, lse2 = torch.empty_like(o), torch.empty_like(lse)
+        p, p2 = capi.mla_prefill_params(q, k, v, o, lse, causal=causal), capi.mla_prefill_params(q, k, v, o2, lse2, causal=causal)
+        stream = torch.cuda.current_stream().cuda_stream
+        base.fa_run_mla_prefill_fwd.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        mine = lambda: capi.check(capi.lib().fa_run_mla_prefill_fwd(ctypes.byref(p), stream))
+        other = lambda: base.fa_run_mla_prefill_fwd(ctypes.byref(p2), stream)
+        mine(), other()
+        torch.cuda.synchronize()
+        err = float((o.float() - o2.float()).abs().max())
+        ms = _mlap_time({"this": mine, "baseline": other, "this_again": mine}, rounds)
+        row.update(ms_this=round(ms["this"], 5), ms_this_again=round(ms["this_again"], 5), ms_baseline=round(ms["baseline"], 5),
+                   baseline_over_this=round(ms["baseline"] / ms["this"], 4), again_over_this=round(ms["this_again"] / ms["this"], 4),
+                   tflops_this=round(flops / (ms["this"] * 1e-3) / 1e12, 1), tflops_baseline=round(flops / (ms["baseline"] * 1e-3) / 1e12, 1), max_abs_diff=round(err, 5))
+        return row
+    q1, k1, v1 = (torch.randn(b, s, h, 128, device=dev, dtype=dt) for s in (sq, sk, sk))
+    pad = lambda t: torch.nn.functional.pad(t, (0, 256 - t.shape[-1]))
+    q2, k2, v2 = pad(q), pad(k), pad(v)
+    new = lambda: F.flash_mla_prefill_func(q, k, v, causal=causal)
+    fwd = lambda: F.fwd(q1, k1, v1, causal)
+    old = lambda: F.flash_attn_with_kvcache(q2, k2, v2, causal=causal, softmax_scale=scale)
+    # (the padded call has limits of its own: one sequence of its cache must span less than 2^31 bytes, which h 128 x 256 columns reach at 32768 keys)
+    arms = {"fwd128": fwd, "pad256": old, "new": new, "fwd128_again": fwd, "pad256_again": old}
+    if sk * h * 256 * 2 >= 1 << 31:
+        arms = {k_: f for k_, f in arms.items() if not k_.startswith("pad256")}
+        err = float("nan")
+    else:
+        err = float((new().float() - old()[..., :128].float()).abs().max())
+    fwd(), new()
+    torch.cuda.synchronize()
+    ms = _mlap_time(arms, rounds)
+    del q2, k2, v2
+    torch.cuda.empty_cache()
+    if "pad256" not in ms:
+        row.update(ms_new=round(ms["new"], 5), ms_fwd128=round(ms["fwd128"], 5), ms_fwd128_again=round(ms["fwd128_again"], 5), ms_pad256=None,
+                   tflops_new=round(flops / (ms["new"] * 1e-3) / 1e12, 1), tflops_fwd128=round(0.8 * flops / (ms["fwd128"] * 1e-3) / 1e12, 1),
+                   new_over_fwd128=round(ms["new"] / ms["fwd128"], 4), fwd128_again_over_fwd128=round(ms["fwd128_again"] / ms["fwd128"], 4),
+                   pad256_refused="one sequence of the padded cache spans 2^31 bytes or more")
+        return row
+    row.update(ms_new=round(ms["new"], 5), ms_fwd128=round(ms["fwd128"], 5), ms_fwd128_again=round(ms["fwd128_again"], 5), ms_pad256=round(ms["pad256"], 5),
+               ms_pad256_again=round(ms["pad256_again"], 5), tflops_new=round(flops / (ms["new"] * 1e-3) / 1e12, 1),
+               tflops_fwd128=round(0.8 * flops / (ms["fwd128"] * 1e-3) / 1e12, 1), new_over_fwd128=round(ms["new"] / ms["fwd128"], 4),
+               fwd128_again_over_fwd128=round(ms["fwd128_again"] / ms["fwd128"], 4), new_over_pad256=round(ms["new"] / ms["pad256"], 4),
+               pad256_again_over_pad256=round(ms["pad256_again"] / ms["pad256"], 4), max_abs_diff_to_pad256=round(err, 5))
+    return row
+
+
+def run_mla_prefill(quick, rounds, base=None):
+    shapes = [(s, s, True) for s in (512, 2048, 8192)] + [(2048, 8192, False), (2048, 32768, False)]
+    for h, b in itertools.product((16, 128), (1,) if quick else (1, 4)):
+        for sq, sk, causal in shapes:
+            if quick and h == 128 and max(sq, sk) > 2048:
+                continue
+            yield run_mla_prefill_point(b, h, sq, sk, causal, rounds, base)
+
+
 def _baseline_lib(path):
     L = ctypes.CDLL(os.path.abspath(path))
     L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
@@ -1173,6 +1261,9 @@ def main():
     ap.add_argument("--mla-indexer", action="store_true", help="the DeepSeek-V3.2 indexer (flash_mla_indexer_logits / flash_mla_indexer_topk; bf16, FP8 keys with scales, 64 heads, "
                                                                "topk 2048, pages of 64 or --paged P): the logits call against its HBM bound and the torch formulation (timed twice), the "
                                                                "selection against torch.topk")
+    ap.add_argument("--mla-prefill", action="store_true", help="MLA prefill attention (flash_mla_prefill_func, bf16, h = h_k in {16, 128}) against fwd at head_dim 128 and "
+                                                               "against the zero-padded head_dim-256 KV-cache call, each yardstick timed twice; with --baseline-library an A / B of "
+                                                               "the call itself against that library")
     a = ap.parse_args()
     base = _baseline_lib(a.baseline_library) if a.baseline_library else None
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
@@ -1180,6 +1271,10 @@ def main():
     if base is not None:
         print(json.dumps({"baseline_library": base.fa_build_info().decode()}), flush=True)
     with torch.no_grad():
+        if a.mla_prefill:
+            for line in run_mla_prefill(a.quick, a.rounds, base):
+                print(json.dumps(line), flush=True)
+            return
         if a.ragged and base is None:
             for line in run_ragged(a.quick, a.rounds):
                 print(json.dumps(line), flush=True)
