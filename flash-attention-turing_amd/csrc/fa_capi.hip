@@ -1165,4 +1165,67 @@ int fa_run_mla_prefill_fwd(const fa_mla_prefill_params* user, void* stream) {
     return hip_status(fa::launch_fwd_mla_prefill(kp, p->dtype, (hipStream_t)stream), "fa_fwd_mla_prefill launch");
 }
 
+// fa_mla_prefill_bwd_params -> MlaPrefillBwdParams, validated: the forward's checks in the forward's order and words, then the tensors of the backward.
+int fa_run_mla_prefill_bwd(const fa_mla_prefill_bwd_params* user, void* stream) {
+    fa_mla_prefill_bwd_params local;
+    int rc = import_exact(user, local, "fa_mla_prefill_bwd_params");
+    if (rc) return rc;
+    const fa_mla_prefill_bwd_params* p = &local;
+    if (p->b < 0 || p->seqlen_q < 0 || p->seqlen_k < 0 || p->h <= 0 || p->h_k <= 0)
+        return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d seqlen_k=%d h=%d h_k=%d", p->b, p->seqlen_q, p->seqlen_k, p->h, p->h_k);
+    if (p->h % p->h_k != 0) return fail(FA_ERR_BAD_GQA, "h (%d) must be divisible by h_k (%d) for GQA/MQA", p->h, p->h_k);
+    if (p->d_qk != 192) return fail(FA_ERR_BAD_HEADDIM, "d_qk %d unsupported (q and k are 192 wide: 128 no-rope + 64 rope elements)", p->d_qk);
+    if (p->d_v != 128) return fail(FA_ERR_BAD_HEADDIM, "d_v %d unsupported (v and o are 128 wide)", p->d_v);
+    if (p->dtype != FA_FP16 && p->dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", p->dtype);
+    const bool packed = p->cu_seqlens_q != nullptr || p->cu_seqlens_k != nullptr;
+    if (packed && p->cu_seqlens_q == nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_q is NULL but cu_seqlens_k is given (both or neither)");
+    if (packed && p->cu_seqlens_k == nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_k is NULL but cu_seqlens_q is given (both or neither)");
+    if (packed && ((reinterpret_cast<uintptr_t>(p->cu_seqlens_q) | reinterpret_cast<uintptr_t>(p->cu_seqlens_k)) & 3u) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "cu_seqlens_q / cu_seqlens_k must be 4-byte aligned");
+    if (!(p->softmax_scale >= 0.f) || isinf(p->softmax_scale))
+        return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default 192 ** -0.5)", (double)p->softmax_scale);
+    if (packed && (p->total_q < 0 || p->total_k < 0))
+        return fail(FA_ERR_BAD_SHAPE, "total_q (%lld) / total_k (%lld) must be >= 0 with cu_seqlens", (long long)p->total_q, (long long)p->total_k);
+    if (p->phases < 0 || p->phases > 2) return fail(FA_ERR_BAD_SHAPE, "phases %d unknown (0 = both launches, 1 = dq, 2 = dk / dv)", p->phases);
+    if (p->reserved_ != 0) return fail(FA_ERR_BAD_SHAPE, "fa_mla_prefill_bwd_params: reserved_ is not zero (a field of a newer header that this library does not know)");
+    const int64_t rows_q = packed ? p->total_q : p->seqlen_q, rows_k = packed ? p->total_k : p->seqlen_k;
+    // both grids are h_k x tiles of 64 (dense: per batch entry; packed: of all rows or keys, plus one slot per sequence), and a packed row index is an int
+    const int64_t h_ratio = p->h / p->h_k;
+    const int64_t tiles = (rows_q * h_ratio + fa::kKvcPrefillRows - 1) / fa::kKvcPrefillRows, ktiles = (rows_k + fa::kKvcPrefillRows - 1) / fa::kKvcPrefillRows;
+    if (rows_q * h_ratio >= ((int64_t)1 << 31) || rows_k >= ((int64_t)1 << 31) || (packed ? tiles + p->b : tiles * p->b) * p->h_k >= ((int64_t)1 << 31) ||
+        (packed ? ktiles + p->b : ktiles * p->b) * p->h_k >= ((int64_t)1 << 31))
+        return fail(FA_ERR_BAD_SHAPE, "call too large: b = %d sequences, %lld query rows x h = %d heads, %lld keys exceed the launch grid", p->b, (long long)rows_q, p->h,
+                    (long long)rows_k);
+    if (p->b == 0 || rows_q == 0) return FA_OK;     // nothing to launch
+    if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
+    if (p->dsoftmax_sum == nullptr) return fail(FA_ERR_NULL_POINTER, "dsoftmax_sum is NULL");
+    if (((reinterpret_cast<uintptr_t>(p->lse) | reinterpret_cast<uintptr_t>(p->dsoftmax_sum)) & 3u) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "lse / dsoftmax_sum must be 4-byte aligned");
+    if ((rc = check_tensor("q", p->q, p->q_stride, rows_q, p->d_qk, packed))) return rc;
+    if ((rc = check_tensor("o", p->o, p->o_stride, rows_q, p->d_v, packed))) return rc;
+    if ((rc = check_tensor("dout", p->dout, p->dout_stride, rows_q, p->d_v, packed))) return rc;
+    if ((rc = check_tensor("dq", p->dq, p->dq_stride, rows_q, p->d_qk, packed))) return rc;
+    if (rows_k > 0) {
+        if ((rc = check_tensor("k", p->k, p->k_stride, rows_k, p->d_qk, packed))) return rc;
+        if ((rc = check_tensor("v", p->v, p->v_stride, rows_k, p->d_v, packed))) return rc;
+        if ((rc = check_tensor("dk", p->dk, p->dk_stride, rows_k, p->d_qk, packed))) return rc;
+        if ((rc = check_tensor("dv", p->dv, p->dv_stride, rows_k, p->d_v, packed))) return rc;
+    }
+    fa::MlaPrefillBwdParams kp;
+    memset(&kp, 0, sizeof(kp));
+    kp.q_ptr = p->q; kp.k_ptr = p->k; kp.v_ptr = p->v; kp.o_ptr = p->o; kp.do_ptr = p->dout; kp.dq_ptr = p->dq; kp.dk_ptr = p->dk; kp.dv_ptr = p->dv;
+    kp.lse_ptr = p->lse; kp.dsum_ptr = p->dsoftmax_sum;
+    kp.cu_q = p->cu_seqlens_q; kp.cu_k = p->cu_seqlens_k;
+    kp.q = conv(p->q_stride); kp.k = conv(p->k_stride); kp.v = conv(p->v_stride); kp.o = conv(p->o_stride);
+    kp.dout = conv(p->dout_stride); kp.dq = conv(p->dq_stride); kp.dk = conv(p->dk_stride); kp.dv = conv(p->dv_stride);
+    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_k = p->seqlen_k;
+    kp.h = p->h; kp.h_k = p->h_k; kp.h_ratio = (int32_t)h_ratio;
+    kp.is_causal = p->is_causal ? 1 : 0;
+    kp.total_q = packed ? p->total_q : 0; kp.total_k = packed ? p->total_k : 0;
+    kp.scale = p->softmax_scale > 0.f ? p->softmax_scale : 1.0f / sqrtf((float)p->d_qk);        // (the forward's default, rounded once to fp32)
+    kp.scale_log2e = kp.scale * 1.4426950408889634f;
+    // (with query rows but no key anywhere the dQ launch still runs: every row is dead and is written as zeros)
+    return hip_status(fa::launch_bwd_mla_prefill(kp, p->dtype, p->phases ? p->phases : 3, (hipStream_t)stream), "fa_bwd_mla_prefill launch");
+}
+
 }  // extern "C"

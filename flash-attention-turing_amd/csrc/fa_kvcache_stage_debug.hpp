@@ -1,6 +1,6 @@
 // fa_kvcache_stage_debug.hpp — adversarial timing for the register-staged LDS stages of the 64-row KV-cache bodies (test builds only).
 //
-//   fa_fwd_kvcache_prefill.hip, fa_fwd_kvcache_mla.hip, fa_fwd_kvcache_mla_sparse.hip, fa_fwd_kvcache_mla_fp8.hip and fa_fwd_mla_prefill.hip restate one schedule: four waves
+//   fa_fwd_kvcache_prefill.hip, fa_fwd_kvcache_mla.hip, fa_fwd_kvcache_mla_sparse.hip, fa_fwd_kvcache_mla_fp8.hip, fa_fwd_mla_prefill.hip and fa_bwd_mla_prefill.hip (both of its loops) restate one schedule: four waves
 //   each write a quarter of a 32-key step into one of two LDS stages that all four read, with ONE barrier per step.  Four waves of a unit run close to
 //   lockstep, so a barrier one statement too early would hand a wave the stage's previous tenant almost never, and every value test would pass.
 //   tests/test_stage_protocol_gpu.py builds the same kernels with one wave held back and asks for the product's bits.

@@ -325,6 +325,33 @@ struct MlaPrefillParams {
 };
 hipError_t launch_fwd_mla_prefill(MlaPrefillParams p, int dtype, hipStream_t stream);
 
+// The backward of the above (fa_bwd_mla_prefill.hip, fa_run_mla_prefill_bwd): two launches on one stream, dQ (which also writes D = rowsum(dO * O) to
+// dsum_ptr, fp32 in the layout of lse) and then dK / dV, which reads it.  Tensors, packing and strides as in MlaPrefillParams; dout is shaped like o, dq /
+// dk / dv like q / k / v.  No atomics, no workspace besides dsum.  A block of its own: no other kernel's kernarg segment changes.
+struct MlaPrefillBwdParams {
+    const void* q_ptr;
+    const void* k_ptr;
+    const void* v_ptr;
+    const void* o_ptr;
+    const void* do_ptr;
+    void* dq_ptr;
+    void* dk_ptr;
+    void* dv_ptr;
+    const float* lse_ptr;
+    float* dsum_ptr;
+    const int32_t* cu_q;        // (b + 1,) or NULL = dense
+    const int32_t* cu_k;
+    TStride q, k, v, o, dout, dq, dk, dv;
+    int32_t b, seqlen_q, seqlen_k, h, h_k, h_ratio;
+    int32_t is_causal;
+    int32_t n_row_tiles;        // filled by the launcher per launch (dense): row tiles (dQ) or key tiles (dK/dV) of a (batch, KV head)
+    int32_t slots;              // filled by the launcher per launch (packed): tile slots per KV head, ceil(total * (h_ratio or 1) / 64) + b
+    int64_t total_q, total_k;
+    float scale_log2e;
+    float scale;
+};
+hipError_t launch_bwd_mla_prefill(MlaPrefillBwdParams p, int dtype, int phases, hipStream_t stream);     // phases: 1 = dQ + D, 2 = dK / dV, 3 = both
+
 // Rotary embedding on a decode call (fa_kvcache_rotary.hip, fa_kvcache_options_v3).  One fused launch takes the place of the append: it
 // rotates k_new into the cache, copies / quantises v_new, and writes the rotated q into `q_image`, a contiguous (b, seqlen_q, h, d) buffer of
 // q's dtype at the head of the caller's workspace; the attention kernels then read that image as their q.  A block of its own and not

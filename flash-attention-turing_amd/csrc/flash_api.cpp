@@ -618,6 +618,77 @@ std::vector<at::Tensor> mha_fwd_mla_prefill(at::Tensor q, at::Tensor k, at::Tens
     return {o, l};
 }
 
+// The backward of MLA prefill attention (fa_run_mla_prefill_bwd): dout / out shaped like the forward's out, lse as the forward returned it -> [dq, dk, dv],
+// contiguous and shaped like q / k / v.  Nothing is copied: the tensors go to the library with the strides they have.  D (dsoftmax_sum) is allocated here.
+// phases: 0 = the call; 1 / 2 = only the dq or the dk / dv launch (measurements; 2 takes the D of an earlier call as `dsoftmax_sum`).
+std::vector<at::Tensor> mha_bwd_mla_prefill(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out, at::Tensor lse, c10::optional<at::Tensor> cu_seqlens_q_,
+                                            c10::optional<at::Tensor> cu_seqlens_k_, bool is_causal, c10::optional<double> softmax_scale, int64_t phases,
+                                            c10::optional<at::Tensor> dsoftmax_sum_) {
+    const bool packed = cu_seqlens_q_.has_value() || cu_seqlens_k_.has_value();
+    TORCH_CHECK(cu_seqlens_q_.has_value() == cu_seqlens_k_.has_value(), "cu_seqlens_q and cu_seqlens_k come both or neither");
+    const int64_t rank = packed ? 3 : 4;
+    TORCH_CHECK(q.dim() == rank && k.dim() == rank && v.dim() == rank, "q, k, v must be rank-", rank, " tensors");
+    check_qkv_common(q, k, v);
+    check_same_device(q, out, "out"); check_same_device(q, dout, "dout"); check_same_device(q, lse, "lse");
+    TORCH_CHECK(out.scalar_type() == q.scalar_type() && dout.scalar_type() == q.scalar_type(), "out and dout must have the dtype of q");
+    const int64_t batch_size = packed ? cu_seqlens_q_->numel() - 1 : q.size(0);
+    const int64_t rows_q = q.size(-3), rows_k = k.size(-3), num_heads = q.size(-2), num_heads_k = k.size(-2);
+    TORCH_CHECK(v.size(-3) == rows_k && v.size(-2) == num_heads_k, "k and v must agree in rows and heads");
+    TORCH_CHECK(packed || (k.size(0) == batch_size && v.size(0) == batch_size), "k/v batch size must match q");
+    TORCH_CHECK(k.size(-1) == q.size(-1), "q / k head_dim must match");
+    TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "num_heads_q must be divisible by num_heads_k for GQA/MQA");
+    TORCH_CHECK(batch_size <= INT32_MAX && (packed || (rows_q <= INT32_MAX && rows_k <= INT32_MAX)) && num_heads <= INT32_MAX && q.size(-1) <= INT32_MAX && v.size(-1) <= INT32_MAX,
+                "sizes must fit in int32");
+    std::vector<int64_t> o_shape = q.sizes().vec();
+    o_shape.back() = v.size(-1);
+    TORCH_CHECK(out.sizes() == at::IntArrayRef(o_shape) && dout.sizes() == at::IntArrayRef(o_shape), "out and dout must have the shape of the forward's out");
+    std::vector<int64_t> l_shape = packed ? std::vector<int64_t>{num_heads, rows_q} : std::vector<int64_t>{batch_size, num_heads, rows_q};
+    TORCH_CHECK(lse.scalar_type() == torch::kFloat32 && lse.is_contiguous() && lse.sizes() == at::IntArrayRef(l_shape), "lse must be the forward's: fp32, contiguous, (b, h, seqlen_q) or (h, total_q)");
+    TORCH_CHECK(phases >= 0 && phases <= 2, "phases: 0 (both launches), 1 (dq) or 2 (dk / dv)");
+    at::Tensor cu_q, cu_k;
+    if (packed) {
+        cu_q = *cu_seqlens_q_; cu_k = *cu_seqlens_k_;
+        check_cu_seqlens(cu_q, cu_k);
+        check_same_device(q, cu_q, "cu_seqlens_q"); check_same_device(q, cu_k, "cu_seqlens_k");
+    }
+    c10::DeviceGuard guard(q.device());
+    // dense: every element of dq / dk / dv is written; packed: the rows past cu_seqlens[-1] are not touched.  Without a query row nothing is launched and
+    // dk / dv are zero by definition.
+    const bool no_rows = batch_size == 0 || rows_q == 0;
+    at::Tensor dq = torch::empty(q.sizes(), q.options()), dk = no_rows ? torch::zeros(k.sizes(), k.options()) : torch::empty(k.sizes(), k.options()),
+               dv = no_rows ? torch::zeros(v.sizes(), v.options()) : torch::empty(v.sizes(), v.options());
+    at::Tensor dsum;
+    if (dsoftmax_sum_.has_value()) {
+        dsum = *dsoftmax_sum_;
+        check_same_device(q, dsum, "dsoftmax_sum");
+        TORCH_CHECK(dsum.scalar_type() == torch::kFloat32 && dsum.is_contiguous() && dsum.sizes() == lse.sizes(), "dsoftmax_sum must be fp32, contiguous and shaped like lse");
+    } else {
+        dsum = torch::empty(lse.sizes(), lse.options());
+    }
+
+    fa_mla_prefill_bwd_params p;
+    FA_PARAMS_INIT(p);
+    p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = out.data_ptr(); p.lse = lse.data_ptr<float>(); p.dout = dout.data_ptr();
+    p.dq = dq.data_ptr(); p.dk = dk.data_ptr(); p.dv = dv.data_ptr(); p.dsoftmax_sum = dsum.data_ptr<float>();
+    p.b = (int32_t)batch_size; p.h = (int32_t)num_heads; p.h_k = (int32_t)num_heads_k; p.d_qk = (int32_t)q.size(-1); p.d_v = (int32_t)v.size(-1);
+    p.dtype = fa_dtype_of(q); p.is_causal = is_causal; p.phases = (int32_t)phases;
+    TORCH_CHECK(!softmax_scale.has_value() || (std::isfinite(*softmax_scale) && (float)*softmax_scale > 0.f && std::isfinite((float)*softmax_scale)),
+                "softmax_scale must be a finite fp32 value > 0 (or None = 192 ** -0.5)");
+    if (softmax_scale.has_value()) p.softmax_scale = (float)*softmax_scale;
+    if (packed) {
+        p.cu_seqlens_q = cu_q.data_ptr<int32_t>(); p.cu_seqlens_k = cu_k.data_ptr<int32_t>();
+        p.total_q = rows_q; p.total_k = rows_k;
+        p.q_stride = strides3(q); p.k_stride = strides3(k); p.v_stride = strides3(v); p.o_stride = strides3(out); p.dout_stride = strides3(dout);
+        p.dq_stride = strides3(dq); p.dk_stride = strides3(dk); p.dv_stride = strides3(dv);
+    } else {
+        p.seqlen_q = (int32_t)rows_q; p.seqlen_k = (int32_t)rows_k;
+        p.q_stride = strides4(q); p.k_stride = strides4(k); p.v_stride = strides4(v); p.o_stride = strides4(out); p.dout_stride = strides4(dout);
+        p.dq_stride = strides4(dq); p.dk_stride = strides4(dk); p.dv_stride = strides4(dv);
+    }
+    check_status(fa_run_mla_prefill_bwd(&p, current_stream(q)));
+    return {dq, dk, dv, dsum};
+}
+
 // Sparse MLA decode over a latent KV cache (fa_run_mla_sparse_fwd_kvcache): q, kv_cache, block_table, cache_seqlens as in mha_fwd_mla_kvcache; indices
 // int32 (b, sq, topk), last dim contiguous, any batch / row strides: the logical key positions of each query token.  out (b, sq, h, 512) and lse (b, h, sq).
 // Indices, lengths and tables are read on the device.
@@ -831,6 +902,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "MLA prefill attention: q (b, sq, h, 192), k (b, sk, h_k, 192), v (b, sk, h_k, 128) -> [out (b, sq, h, 128), lse]; packed with both cu_seqlens",
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens_q") = py::none(), py::arg("cu_seqlens_k") = py::none(), py::arg("is_causal") = false,
           py::arg("softmax_scale") = py::none());
+    m.def("bwd_mla_prefill", &mha_bwd_mla_prefill,
+          "MLA prefill backward: dout, q, k, v, out, lse -> [dq, dk, dv, dsoftmax_sum]; packed with both cu_seqlens",
+          py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("cu_seqlens_q") = py::none(),
+          py::arg("cu_seqlens_k") = py::none(), py::arg("is_causal") = false, py::arg("softmax_scale") = py::none(), py::arg("phases") = 0,
+          py::arg("dsoftmax_sum") = py::none());
     m.def("mla_indexer_logits", &mla_indexer_logits, "index logits of the DeepSeek-V3.2 indexer into the caller's fp32 buffer (b, sq, capacity)", py::arg("q_idx"), py::arg("weights"),
           py::arg("k_idx_cache"), py::arg("cache_seqlens"), py::arg("logits"), py::arg("k_scale") = py::none(), py::arg("block_table") = py::none(), py::arg("is_causal") = true);
     m.def("mla_indexer_topk", &mla_indexer_topk, "top-k positions of every logits row into the caller's int32 buffer (b, sq, topk)", py::arg("logits"), py::arg("cache_seqlens"),

@@ -184,6 +184,17 @@ class MlaPrefillParams(_Params):
                 ("total_q", ctypes.c_int64), ("total_k", ctypes.c_int64)]
 
 
+class MlaPrefillBwdParams(_Params):
+    """fa_mla_prefill_bwd_params: the backward of MLA prefill attention, dq / dk / dv from dout, q, k, v, o, lse (fa_run_mla_prefill_bwd)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("q", _vp), ("k", _vp), ("v", _vp), ("o", _vp), ("lse", _vp), ("dout", _vp),
+                ("dq", _vp), ("dk", _vp), ("dv", _vp), ("dsoftmax_sum", _vp), ("cu_seqlens_q", _vp), ("cu_seqlens_k", _vp),
+                ("b", _i32), ("seqlen_q", _i32), ("seqlen_k", _i32), ("h", _i32), ("h_k", _i32), ("d_qk", _i32), ("d_v", _i32),
+                ("dtype", _i32), ("is_causal", _i32), ("softmax_scale", ctypes.c_float), ("phases", _i32), ("reserved_", _i32),
+                ("q_stride", Strides), ("k_stride", Strides), ("v_stride", Strides), ("o_stride", Strides), ("dout_stride", Strides),
+                ("dq_stride", Strides), ("dk_stride", Strides), ("dv_stride", Strides),
+                ("total_q", ctypes.c_int64), ("total_k", ctypes.c_int64)]
+
+
 FA_MLA_KV_16BIT = 0
 FA_MLA_KV_FP8_ROWS656 = 1      # 656-byte latent rows: 512 e4m3 codes, four fp32 scales, 64 rope elements of q's dtype; kv_cache_stride in bytes
 FA_CACHE_FP8_E4M3 = 1
@@ -254,6 +265,8 @@ def lib():
         L.fa_run_mla_indexer_topk.restype = ctypes.c_int
         L.fa_run_mla_prefill_fwd.argtypes = [ctypes.POINTER(MlaPrefillParams), _vp]
         L.fa_run_mla_prefill_fwd.restype = ctypes.c_int
+        L.fa_run_mla_prefill_bwd.argtypes = [ctypes.POINTER(MlaPrefillBwdParams), _vp]
+        L.fa_run_mla_prefill_bwd.restype = ctypes.c_int
         L.fa_mha_fwd.argtypes = [_vp] * 5 + [_i32] * 8 + [_vp]
         L.fa_mha_bwd.argtypes = [_vp] * 10 + [_i32] * 8 + [_vp]
         L.fa_mha_varlen_fwd.argtypes = [_vp] * 7 + [_i32] * 8 + [_vp]
@@ -749,3 +762,35 @@ def run_mla_prefill_fwd(params, stream=None):
 
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     check(lib().fa_run_mla_prefill_fwd(ctypes.byref(params), s))
+
+
+def mla_prefill_bwd_params(dout, q, k, v, o, lse, dq, dk, dv, dsoftmax_sum, cu_seqlens_q=None, cu_seqlens_k=None, causal=False, softmax_scale=None, phases=0):
+    """fa_mla_prefill_bwd_params for the tensors of mla_prefill_params plus dout (like o), the caller's dq / dk / dv (like q / k / v, strides of their own)
+    and dsoftmax_sum (fp32, like lse)."""
+    p = MlaPrefillBwdParams()
+    p.q, p.k, p.v, p.o, p.lse, p.dout, p.dq, p.dk, p.dv, p.dsoftmax_sum = (t.data_ptr() for t in (q, k, v, o, lse, dout, dq, dk, dv, dsoftmax_sum))
+    packed = cu_seqlens_q is not None or cu_seqlens_k is not None
+    p.h, p.h_k, p.d_qk, p.d_v = q.shape[-2], k.shape[-2], q.shape[-1], v.shape[-1]
+    p.dtype, p.is_causal, p.phases = dtype_code(q.dtype), int(causal), int(phases)
+    p.softmax_scale = 0.0 if softmax_scale is None else float(softmax_scale)
+    tensors = (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", o), ("dout_stride", dout), ("dq_stride", dq), ("dk_stride", dk), ("dv_stride", dv))
+    if packed:
+        p.cu_seqlens_q = None if cu_seqlens_q is None else cu_seqlens_q.data_ptr()
+        p.cu_seqlens_k = None if cu_seqlens_k is None else cu_seqlens_k.data_ptr()
+        p.b = (cu_seqlens_q if cu_seqlens_q is not None else cu_seqlens_k).numel() - 1
+        p.total_q, p.total_k = q.shape[0], k.shape[0]
+        for name, t in tensors:
+            setattr(p, name, Strides(0, t.stride(0), t.stride(1)))
+    else:
+        p.b, p.seqlen_q, p.seqlen_k = q.shape[0], q.shape[1], k.shape[1]
+        for name, t in tensors:
+            setattr(p, name, Strides(t.stride(0), t.stride(1), t.stride(2)))
+    return p
+
+
+def run_mla_prefill_bwd(params, stream=None):
+    """fa_run_mla_prefill_bwd"""
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    check(lib().fa_run_mla_prefill_bwd(ctypes.byref(params), s))

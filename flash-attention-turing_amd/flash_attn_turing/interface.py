@@ -952,7 +952,7 @@ def _check_prefill_view(name, t):
 
 
 def flash_mla_prefill_func(q, k, v, *, cu_seqlens_q=None, cu_seqlens_k=None, softmax_scale=None, causal=False, return_softmax_lse=False):
-    """MLA prefill attention (DeepSeek-V2 / V3 / R1, Kimi K2; forward only): multi-head attention with 192-wide queries and keys and 128-wide values.
+    """MLA prefill attention (DeepSeek-V2 / V3 / R1, Kimi K2; the raw forward): multi-head attention with 192-wide queries and keys and 128-wide values.
 
     Before weight absorption an MLA layer is ordinary multi-head attention whose q / k rows are 128 no-rope columns followed by 64 rope columns (RoPE
     applied by the caller) and whose v rows are 128 wide.  This is the prompt side of flash_mla_with_kvcache.
@@ -980,9 +980,17 @@ def flash_mla_prefill_func(q, k, v, *, cu_seqlens_q=None, cu_seqlens_k=None, sof
     alone (out and lse), a batch entry of a dense call equals the call on it alone, and a power of two moved between q and softmax_scale changes
     nothing.  Chunked prefill over a cached prefix needs no further API: run the context part with causal=False and the new tokens with
     causal=True and merge the two results by their LSE (README.md).
-    Out of scope, and without a keyword here: a backward, FP8 or paged inputs, other widths, window_size, softcap, sinks, a key split.  Wrong shapes,
+    The backward is flash_mla_prefill_bwd, the differentiable function flash_mla_attn_func.
+    Out of scope, and without a keyword here: FP8 or paged inputs, other widths, window_size, softcap, sinks, a key split.  Wrong shapes,
     dtypes, views or values are a ValueError that names the argument.
     """
+    softmax_scale = _check_mla_prefill_args(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale, causal, forward_only=True)
+    out, lse = _C.fwd_mla_prefill(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale)
+    return (out, lse) if return_softmax_lse else out
+
+
+def _check_mla_prefill_args(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale, causal, forward_only=False):
+    """the argument checks of flash_mla_prefill_func, shared with its backward and with flash_mla_attn_func; returns softmax_scale as the extension takes it"""
     packed = cu_seqlens_q is not None or cu_seqlens_k is not None
     if packed and (cu_seqlens_q is None or cu_seqlens_k is None):
         raise ValueError("cu_seqlens_q and cu_seqlens_k come both or neither, got only " + ("cu_seqlens_q" if cu_seqlens_k is None else "cu_seqlens_k"))
@@ -990,9 +998,10 @@ def flash_mla_prefill_func(q, k, v, *, cu_seqlens_q=None, cu_seqlens_k=None, sof
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor) or t.dim() != rank:
             raise ValueError(f"{name} must be a rank-{rank} tensor ({'(total, nheads, head_dim) with cu_seqlens' if packed else '(batch, seqlen, nheads, head_dim)'})")
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+    if forward_only and torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
         bad = next(n for n, t in (("q", q), ("k", k), ("v", v)) if t.requires_grad)
-        raise ValueError(f"{bad} requires grad: flash_mla_prefill_func is forward-only (there is no backward); run it under torch.no_grad() or detach the inputs")
+        raise ValueError(f"{bad} requires grad: flash_mla_prefill_func is forward-only (the differentiable function is flash_mla_attn_func); run it under "
+                         "torch.no_grad() or detach the inputs")
     if q.dtype not in (torch.float16, torch.bfloat16):
         raise ValueError(f"q must be fp16 or bf16, got {q.dtype}")
     for name, t in (("k", k), ("v", v)):
@@ -1021,5 +1030,88 @@ def flash_mla_prefill_func(q, k, v, *, cu_seqlens_q=None, cu_seqlens_k=None, sof
     softmax_scale, _ = _check_scale_and_cap(softmax_scale, 0.0)
     if not isinstance(causal, bool):
         raise ValueError(f"causal must be a bool, got {causal!r}")
-    out, lse = _C.fwd_mla_prefill(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale)
+    return softmax_scale
+
+
+def _check_prefill_rows(name, t):
+    """the rest of the rule for the backward's dout and out: the row stride (of the sequence dimension) is at least the row's width, as the library asks of
+    every tensor - an expanded tensor (row stride 0) is refused here and not in the extension"""
+    if t.stride(-3) < t.shape[-1] or any(s < 0 for s in t.stride()):
+        raise ValueError(f"{name}: the row stride must be at least the row width {t.shape[-1]} and no stride negative, got strides {tuple(t.stride())} "
+                         "(an expanded tensor?); the view is not copied")
+
+
+def flash_mla_prefill_bwd(dout, q, k, v, out, lse, *, cu_seqlens_q=None, cu_seqlens_k=None, softmax_scale=None, causal=False):
+    """The backward of flash_mla_prefill_func, raw (no autograd): (dq, dk, dv) from dout, the forward's inputs and its out and lse.
+
+    q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale, causal: exactly the forward's arguments, with the forward's checks.  ``out`` and ``dout`` are
+    shaped like the forward's out ((batch, seqlen_q, nheads, 128) or (total_q, nheads, 128)), of q's dtype, under the same view rule as q / k / v (last
+    dimension contiguous, every other stride and the storage offset multiples of 8 elements; refused, never copied) and with a row stride of at least 128
+    (an expanded tensor is refused).  ``lse`` is the forward's: fp32,
+    contiguous, (batch, nheads, seqlen_q) or (nheads, total_q).  Returns dq, dk, dv, contiguous and shaped like q, k, v.
+
+    In fp32 math over the visible pairs (visibility exactly the forward's): P_tj = exp(s_tj - lse_t), exactly 0 on hidden pairs; D_t = sum_c dout_tc out_tc;
+    dS = P (dout_t . v_j - D_t); dq_t = softmax_scale sum_j dS_tj k_j; dk_j = softmax_scale x the sum over the nheads / nheads_k heads of the group and over t
+    of dS_tj q_t; dv_j = the same sum of P_tj dout_t.  fp32 accumulation, every output rounded once; P and dS are rounded to the dtype in front of their second
+    matrix products.  A row that sees no key gets dq = 0, a key no row sees dk = dv = 0, both written; empty sequences on either side are allowed.  Packed
+    rows of dq at or past cu_seqlens_q[-1] and of dk / dv at or past cu_seqlens_k[-1] are not written.  Non-finite inputs have no value contract.
+
+    Two launches on the current stream (dq, then dk / dv), no atomics, no key or head split, no workspace besides D, no host synchronisation: graph-
+    capturable and deterministic.  Bit for bit: sequence i of a packed call equals the dense call on it alone, and a batch entry the call on it alone.
+    Out of scope: a head-group or key split with a workspace, other widths, window_size, softcap, sinks, FP8 or paged inputs, a fused single-kernel backward.
+    """
+    softmax_scale = _check_mla_prefill_args(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale, causal)
+    o_shape = tuple(q.shape[:-1]) + (128,)
+    for name, t in (("dout", dout), ("out", out)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != o_shape:
+            raise ValueError(f"{name} must be a tensor shaped like the forward's out {o_shape}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if t.dtype != q.dtype:
+            raise ValueError(f"{name} must have q's dtype ({q.dtype}), got {t.dtype}")
+        if t.device != q.device:
+            raise ValueError(f"{name} must be on q's device ({q.device}), got {t.device}")
+        _check_prefill_view(name, t)
+        _check_prefill_rows(name, t)
+    l_shape = (q.shape[-2], q.shape[0]) if q.dim() == 3 else (q.shape[0], q.shape[2], q.shape[1])
+    if not isinstance(lse, torch.Tensor) or lse.dtype != torch.float32 or tuple(lse.shape) != l_shape or not lse.is_contiguous() or lse.device != q.device:
+        raise ValueError(f"lse must be the forward's lse: a contiguous float32 tensor {l_shape} on q's device")
+    dq, dk, dv, _ = _C.bwd_mla_prefill(dout, q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale)
+    return dq, dk, dv
+
+
+class _FlashMlaAttn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale, causal):
+        out, lse = _C.fwd_mla_prefill(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale)
+        ctx.save_for_backward(q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k)
+        ctx.softmax_scale, ctx.causal = softmax_scale, causal
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, dout, _dlse):
+        q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k = ctx.saved_tensors
+        # a dout the kernels can address is used as it is; any other view is made contiguous once
+        # (autograd hands over expanded gradients as they are: the dout of out.sum(dim=1) has a row stride of 0, which no kernel addresses)
+        if (dout.stride(-1) != 1 or any(s % 8 != 0 for s in dout.stride()[:-1]) or dout.storage_offset() % 8 != 0 or dout.stride(-3) < dout.shape[-1]
+                or any(s < 0 for s in dout.stride())):
+            dout = dout.contiguous()
+        dq, dk, dv, _ = _C.bwd_mla_prefill(dout, q, k, v, out, lse, cu_seqlens_q, cu_seqlens_k, ctx.causal, ctx.softmax_scale)
+        return dq, dk, dv, None, None, None, None
+
+
+def flash_mla_attn_func(q, k, v, *, cu_seqlens_q=None, cu_seqlens_k=None, softmax_scale=None, causal=False, return_softmax_lse=False):
+    """flash_mla_prefill_func, differentiable: the training forward of an MLA layer (192-wide q / k, 128-wide v; dense, or packed with cu_seqlens).
+
+    Arguments, checks, values and bits are flash_mla_prefill_func's (without grad the two are the same call).  With grad enabled the result is an autograd
+    node over flash_mla_prefill_func and flash_mla_prefill_bwd: gradients flow to q, k and v and to nothing else; ``lse`` (with ``return_softmax_lse``)
+    is returned non-differentiable.  A non-contiguous ``dout`` whose last dimension is contiguous, whose other strides and storage offset are multiples
+    of 8 elements and whose row stride is at least 128 is used as it is; any other - the expanded gradient of ``out.sum(dim=1)``, whose row stride is 0,
+    included - is made contiguous once, the only copy this function makes.  See flash_mla_prefill_bwd for the math, the
+    rounding points and what is out of scope.
+    """
+    softmax_scale = _check_mla_prefill_args(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale, causal)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        out, lse = _FlashMlaAttn.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale, causal)
+    else:
+        out, lse = _C.fwd_mla_prefill(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale)
     return (out, lse) if return_softmax_lse else out

@@ -907,7 +907,8 @@ typedef struct fa_mla_topk_params {
  * on that sequence alone bit for bit, and so does a batch entry of a dense call.
  * Errors, the argument named by fa_last_error: d_qk != 192 or d_v != 128 FA_ERR_BAD_HEADDIM, h % h_k FA_ERR_BAD_GQA, dtype FA_ERR_BAD_DTYPE, sizes /
  * total_q / total_k / softmax_scale FA_ERR_BAD_SHAPE, pointers (one cu_seqlens without the other included) FA_ERR_NULL_POINTER, strides and alignment
- * FA_ERR_BAD_STRIDE, the header FA_ERR_BAD_ABI.  b == 0 or no query row (total_q == 0; dense: seqlen_q == 0) is FA_OK without a launch.  No backward, FP8
+ * FA_ERR_BAD_STRIDE, the header FA_ERR_BAD_ABI.  b == 0 or no query row (total_q == 0; dense: seqlen_q == 0) is FA_OK without a launch.  The backward is
+ * fa_run_mla_prefill_bwd (fa_mla_prefill_bwd_params below).  No FP8
  * or paged inputs, other widths, window, softcap or sinks: the struct has no field for them. */
 #define FA_HAS_MLA_PREFILL 1
 typedef struct fa_mla_prefill_params {
@@ -934,6 +935,60 @@ typedef struct fa_mla_prefill_params {
     int64_t total_q;            /* packed: rows of q / o */
     int64_t total_k;            /* packed: rows of k / v */
 } fa_mla_prefill_params;
+
+/* The backward of MLA prefill attention (FA_HAS_MLA_PREFILL_BWD): dq (192 wide), dk (192 wide) and dv (128 wide) from dout, q, k, v and the forward's o
+ * and lse.  FA_ABI_VERSION is unchanged; the presence of fa_run_mla_prefill_bwd is how a caller detects the feature.  struct_size must be
+ * sizeof(fa_mla_prefill_bwd_params) (FA_PARAMS_INIT).  The fields of fa_mla_prefill_params with the same meaning, dense or packed, plus:
+ *   o, lse          the forward's outputs (read); lse fp32, (b, h, seqlen_q) dense or (h, total_q) packed
+ *   dout            the gradient of o, shaped like o, with strides of its own
+ *   dq, dk, dv      outputs shaped like q, k, v, with strides of their own
+ *   dsoftmax_sum    fp32, the layout of lse: D_t = sum_c dout_tc * o_tc, WRITTEN by the first launch and read by the second (the only workspace)
+ *   phases          0 = the call (both launches); FA_MLA_PREFILL_BWD_DQ (1) / _DKDV (2) = only that launch, any other value is refused (measurements; _DKDV reads the dsoftmax_sum an earlier _DQ call left)
+ * In fp32 math over the visible pairs (visibility exactly the forward's): P_tj = exp(s_tj - lse_t), exactly 0 on hidden pairs (selected to 0: whatever the exponential gives there is discarded);
+ * dP_tj = dout_t . v_j; dS = P (dP - D); dq_t = softmax_scale * sum_j dS_tj k_j; dk_j = softmax_scale * sum over the h / h_k heads of the group and t of
+ * dS_tj q_t; dv_j = sum over the group and t of P_tj dout_t.  Accumulated in fp32, each output rounded once; P and dS are rounded to dtype in front of their
+ * second matrix products.  A row the forward gave o = 0, lse = 0 (it sees no key) gets dq = 0, written; a key no row sees gets dk = dv = 0, written; empty
+ * sequences on either side are allowed.  Packed rows of dq at or past cu_seqlens_q[b] and of dk / dv at or past cu_seqlens_k[b] keep the caller's bytes.
+ * Two launches on `stream` (dq, then dk / dv), no atomics, no key or head split, no host synchronisation, deterministic; one workgroup owns an output row
+ * from start to end.  Sequence i of a packed call equals the dense call on it alone bit for bit, and so does a batch entry of a dense call.  Non-finite
+ * inputs have no value contract (as for fa_run_mha_bwd) but never change which addresses are touched.
+ * Errors as for the forward, the argument named by fa_last_error.  b == 0 or no query row is FA_OK without a launch (dk / dv are not touched); with query
+ * rows but no key anywhere dq is zeroed.  Out of scope: a head-group or key split with a workspace, other widths, window / softcap / sinks, FP8 or paged
+ * inputs, a fused single-kernel backward. */
+#define FA_HAS_MLA_PREFILL_BWD 1
+#define FA_MLA_PREFILL_BWD_DQ 1
+#define FA_MLA_PREFILL_BWD_DKDV 2
+typedef struct fa_mla_prefill_bwd_params {
+    uint32_t struct_size;       /* sizeof(fa_mla_prefill_bwd_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const void* q;
+    const void* k;
+    const void* v;
+    const void* o;
+    const float* lse;
+    const void* dout;
+    void* dq;
+    void* dk;
+    void* dv;
+    float* dsoftmax_sum;
+    const int32_t* cu_seqlens_q;    /* both NULL = dense */
+    const int32_t* cu_seqlens_k;
+    int32_t b;
+    int32_t seqlen_q;
+    int32_t seqlen_k;
+    int32_t h;
+    int32_t h_k;
+    int32_t d_qk;               /* 192 */
+    int32_t d_v;                /* 128 */
+    int32_t dtype;
+    int32_t is_causal;
+    float softmax_scale;        /* 0 = 192 ** -0.5 */
+    int32_t phases;             /* 0 = both launches */
+    int32_t reserved_;          /* 0 */
+    fa_strides q_stride, k_stride, v_stride, o_stride, dout_stride, dq_stride, dk_stride, dv_stride;     /* packed: the batch strides are not read */
+    int64_t total_q;            /* packed: rows of q / o / dout / dq */
+    int64_t total_k;            /* packed: rows of k / v / dk / dv */
+} fa_mla_prefill_bwd_params;
 
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
@@ -1030,6 +1085,8 @@ int fa_run_mla_indexer_topk(const fa_mla_topk_params* params, void* stream);
 /* ---- MLA prefill attention (fa_mla_prefill_params above) -------------------------------------- */
 /* One launch on `stream`, no workspace, no host synchronisation: cu_seqlens are read on the device. */
 int fa_run_mla_prefill_fwd(const fa_mla_prefill_params* params, void* stream);
+/* Its backward (fa_mla_prefill_bwd_params above): two launches on `stream`, dsoftmax_sum the only workspace, no host synchronisation. */
+int fa_run_mla_prefill_bwd(const fa_mla_prefill_bwd_params* params, void* stream);
 
 /* ---- measurement helpers ----------------------------------------------------------------- */
 /* Algorithmic FLOPs of one forward call (4*b*h*sq*sk*d, causal counts only visible pairs);

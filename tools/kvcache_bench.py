@@ -88,6 +88,10 @@ interleaved in one process: the logits call; the torch formulation of the logits
 as a contiguous cache, i.e. without the gather a paged cache would cost it) timed TWICE as its own noise figure; the selection; torch.topk on the same
 logits.  The logits call is also stated against b * L * 132 B / time as a fraction of 6.3 TB/s.  Caches rotate over 256 MiB (profiles/kvcache_mla_indexer_bench.log).
 
+--mla-prefill-bwd measures the MLA prefill backward (flash_mla_prefill_bwd) on the grid of --mla-prefill: both launches, the dQ launch and the dK/dV launch
+alone, against (a) bwd at head_dim 128 on the same b, s, h (640 / 832 of the FLOPs per pair) and (b) autograd's backward of the torch formulation in bf16 where
+its score matrices fit; each yardstick twice, interleaved in one process, medians; TFLOP/s at 2 sq sk h (3 x 192 + 2 x 128), halved under the mask
+(profiles/mla_prefill_bwd_bench.log).
 --mla-prefill measures MLA prefill attention (flash_mla_prefill_func: 192-wide q / k, 128-wide v) on a grid of its own: bf16, h = h_k in {16, 128}, b in
 {1, 4}; sq = sk in {512, 2048, 8192} causal, and a 2048-row chunk over an 8k and a 32k context, non-causal (--quick: b 1, and h 128 up to 2048 rows only).  Per
 point, interleaved in one process, medians: the new call against (a) fwd at head_dim 128 on the same b, s, h - 0.8 x the FLOPs - and (b) what a caller could
@@ -1170,6 +1174,60 @@ def run_mla_prefill(quick, rounds, base=None):
             yield run_mla_prefill_point(b, h, sq, sk, causal, rounds, base)
 
 
+def run_mla_prefill_bwd_point(b, h, sq, sk, causal, rounds):
+    """flash_mla_prefill_bwd (both launches, and each alone) against (a) bwd at head_dim 128 on the same b, s, h and (b) autograd's backward of the torch
+    formulation (einsum, masked softmax, einsum) in bf16 where its score matrices fit; each yardstick twice"""
+    from flash_attn_turing import _C
+
+    dev, dt = torch.device("cuda:0"), torch.bfloat16
+    scale = 192 ** -0.5
+    q, k, v = (torch.randn(b, s, h, d, device=dev, dtype=dt) for s, d in ((sq, 192), (sk, 192), (sk, 128)))
+    dout = torch.randn(b, sq, h, 128, device=dev, dtype=dt)
+    flops = 2.0 * sq * sk * h * (3 * 192 + 2 * 128) * b * (0.5 if causal else 1.0)
+    row = dict(mla_prefill_bwd=True, b=b, h=h, sq=sq, sk=sk, causal=bool(causal), dtype="bfloat16")
+    out, lse = F.flash_mla_prefill_func(q, k, v, causal=causal, return_softmax_lse=True)
+    dsum = _C.bwd_mla_prefill(dout, q, k, v, out, lse, None, None, causal, None)[3]
+    new = lambda: F.flash_mla_prefill_bwd(dout, q, k, v, out, lse, causal=causal)
+    dq_only = lambda: _C.bwd_mla_prefill(dout, q, k, v, out, lse, None, None, causal, None, 1, dsum)
+    dkdv_only = lambda: _C.bwd_mla_prefill(dout, q, k, v, out, lse, None, None, causal, None, 2, dsum)
+    q1, k1, v1, do1 = (torch.randn(b, s, h, 128, device=dev, dtype=dt) for s in (sq, sk, sk, sq))
+    o1, l1 = F.fwd(q1, k1, v1, causal)
+    bwd = lambda: F.bwd(q1, k1, v1, o1, l1, do1, causal)
+    arms = {"bwd128": bwd, "new": new, "dq": dq_only, "dkdv": dkdv_only, "bwd128_again": bwd}
+    if b * h * sq * sk <= 1 << 30:
+        with torch.enable_grad():
+            ql, kl, vl = (t.detach().clone().requires_grad_(True) for t in (q, k, v))
+            s_ = torch.einsum("bthd,bjhd->bhtj", ql, kl) * scale
+            if causal:
+                s_ = s_.masked_fill(torch.arange(sk, device=dev).view(1, -1) > sk - sq + torch.arange(sq, device=dev).view(-1, 1), float("-inf"))
+            o_t = torch.einsum("bhtj,bjhd->bthd", torch.softmax(s_, dim=-1), vl)
+        ref = lambda: torch.autograd.grad(o_t, (ql, kl, vl), dout, retain_graph=True)
+        arms.update(torch=ref, torch_again=ref)
+        row["rel_diff_to_torch"] = [round(float((x.double() - y.double()).norm() / y.double().norm()), 5) for x, y in zip(new(), ref())]
+    bwd(), new()
+    torch.cuda.synchronize()
+    ms = _mlap_time(arms, rounds)
+    row.update({f"ms_{n}": round(t, 5) for n, t in ms.items()})
+    row.update(tflops_new=round(flops / (ms["new"] * 1e-3) / 1e12, 1), tflops_bwd128=round(640.0 / 832.0 * flops / (ms["bwd128"] * 1e-3) / 1e12, 1),
+               new_over_bwd128=round(ms["new"] / ms["bwd128"], 4), bwd128_again_over_bwd128=round(ms["bwd128_again"] / ms["bwd128"], 4),
+               dq_plus_dkdv_over_new=round((ms["dq"] + ms["dkdv"]) / ms["new"], 4))
+    if "torch" in ms:
+        row.update(new_over_torch=round(ms["new"] / ms["torch"], 4), torch_again_over_torch=round(ms["torch_again"] / ms["torch"], 4))
+    else:
+        row["torch_skipped"] = "the score matrices of the torch formulation exceed 2^30 elements"
+    return row
+
+
+def run_mla_prefill_bwd(quick, rounds):
+    """the grid of --mla-prefill"""
+    shapes = [(s, s, True) for s in (512, 2048, 8192)] + [(2048, 8192, False), (2048, 32768, False)]
+    for h, b in itertools.product((16, 128), (1,) if quick else (1, 4)):
+        for sq, sk, causal in shapes:
+            if quick and h == 128 and max(sq, sk) > 2048:
+                continue
+            yield run_mla_prefill_bwd_point(b, h, sq, sk, causal, rounds)
+
+
 def _baseline_lib(path):
     L = ctypes.CDLL(os.path.abspath(path))
     L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
@@ -1264,6 +1322,8 @@ def main():
     ap.add_argument("--mla-prefill", action="store_true", help="MLA prefill attention (flash_mla_prefill_func, bf16, h = h_k in {16, 128}) against fwd at head_dim 128 and "
                                                                "against the zero-padded head_dim-256 KV-cache call, each yardstick timed twice; with --baseline-library an A / B of "
                                                                "the call itself against that library")
+    ap.add_argument("--mla-prefill-bwd", action="store_true", help="the MLA prefill backward (flash_mla_prefill_bwd, bf16, the grid of --mla-prefill): both launches and "
+                                                                   "each alone against bwd at head_dim 128 and against autograd of the torch formulation, each timed twice")
     a = ap.parse_args()
     base = _baseline_lib(a.baseline_library) if a.baseline_library else None
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
@@ -1271,6 +1331,10 @@ def main():
     if base is not None:
         print(json.dumps({"baseline_library": base.fa_build_info().decode()}), flush=True)
     with torch.no_grad():
+        if a.mla_prefill_bwd:
+            for line in run_mla_prefill_bwd(a.quick, a.rounds):
+                print(json.dumps(line), flush=True)
+            return
         if a.mla_prefill:
             for line in run_mla_prefill(a.quick, a.rounds, base):
                 print(json.dumps(line), flush=True)
