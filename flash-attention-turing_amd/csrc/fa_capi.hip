@@ -11,6 +11,7 @@
 
 #include "fa_params.hpp"
 #include "fa_mla_indexer.hpp"
+#include "fa_merge_states.hpp"
 #include "flash_attn_gfx950.h"
 
 namespace {
@@ -1226,6 +1227,60 @@ int fa_run_mla_prefill_bwd(const fa_mla_prefill_bwd_params* user, void* stream) 
     kp.scale_log2e = kp.scale * 1.4426950408889634f;
     // (with query rows but no key anywhere the dQ launch still runs: every row is dead and is written as zeros)
     return hip_status(fa::launch_bwd_mla_prefill(kp, p->dtype, p->phases ? p->phases : 3, (hipStream_t)stream), "fa_bwd_mla_prefill launch");
+}
+
+// ---- merging attention states ----------------------------------------------------------------------------------------------------------------
+// fa_merge_params -> MergeStatesParams, validated.  The parts are streamed once through 64-bit addresses, so there is no 2^31-byte extent rule here; the lse
+// strides may take any value (a stride of 0 or a negative one is a view like any other), the o strides follow the rule of every 16-byte load of the library.
+int fa_run_merge_states(const fa_merge_params* user) {
+    fa_merge_params local;
+    int rc = import_exact(user, local, "fa_merge_params");
+    if (rc) return rc;
+    const fa_merge_params* p = &local;
+    if (p->n_parts < 2 || p->n_parts > FA_MERGE_MAX_PARTS) return fail(FA_ERR_BAD_SHAPE, "n_parts %d unsupported (2 .. %d parts)", p->n_parts, FA_MERGE_MAX_PARTS);
+    if (p->d_v != 64 && p->d_v != 128 && p->d_v != 256 && p->d_v != 512) return fail(FA_ERR_BAD_HEADDIM, "d_v %d unsupported (64, 128, 256 or 512)", p->d_v);
+    if (p->dtype != FA_FP16 && p->dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", p->dtype);
+    if (p->b < 0 || p->rows < 0 || p->h < 0) return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d rows=%d h=%d", p->b, p->rows, p->h);
+    const int64_t all_rows = (int64_t)p->b * p->rows;
+    const int64_t total = all_rows < ((int64_t)1 << 31) ? all_rows * p->h : 0;       // (three int32 factors fit an int64 only once two of them fit an int32)
+    if (all_rows >= ((int64_t)1 << 31) || total / (fa::kMergeThreads / (p->d_v / 8)) >= ((int64_t)1 << 31) - 1)
+        return fail(FA_ERR_BAD_SHAPE, "call too large: b = %d x rows = %d x h = %d (row, head) pairs exceed the launch grid", p->b, p->rows, p->h);
+    if (total == 0) return FA_OK;       // nothing to write
+    auto check_o = [&](const char* name, int i, const void* ptr, const fa_strides& st) -> int {
+        char nm[32];
+        if (i >= 0) snprintf(nm, sizeof(nm), "%s[%d]", name, i);
+        else snprintf(nm, sizeof(nm), "%s", name);
+        if (ptr == nullptr) return fail(FA_ERR_NULL_POINTER, "%s is NULL", nm);
+        if (((uintptr_t)ptr & 15) != 0) return fail(FA_ERR_BAD_STRIDE, "%s base pointer must be 16-byte aligned", nm);
+        if ((st.batch % 8) != 0 || (st.row % 8) != 0 || (st.head % 8) != 0)
+            return fail(FA_ERR_BAD_STRIDE, "%s strides (batch=%lld,row=%lld,head=%lld) must be multiples of 8 elements (16-byte loads)", nm, (long long)st.batch,
+                        (long long)st.row, (long long)st.head);
+        return FA_OK;
+    };
+    auto check_l = [&](const char* name, int i, const float* ptr) -> int {
+        char nm[32];
+        if (i >= 0) snprintf(nm, sizeof(nm), "%s[%d]", name, i);
+        else snprintf(nm, sizeof(nm), "%s", name);
+        if (ptr == nullptr) return fail(FA_ERR_NULL_POINTER, "%s is NULL", nm);
+        if (((uintptr_t)ptr & 3) != 0) return fail(FA_ERR_BAD_STRIDE, "%s must be 4-byte aligned", nm);
+        return FA_OK;
+    };
+    fa::MergeStatesParams kp;
+    memset(&kp, 0, sizeof(kp));
+    for (int i = 0; i < p->n_parts; ++i) {
+        if ((rc = check_o("o", i, p->o[i], p->o_stride[i]))) return rc;
+        if ((rc = check_l("lse", i, p->lse[i]))) return rc;
+        kp.o_ptr[i] = p->o[i]; kp.lse_ptr[i] = p->lse[i];
+        kp.o_batch[i] = p->o_stride[i].batch; kp.o_row[i] = p->o_stride[i].row; kp.o_head[i] = p->o_stride[i].head;
+        kp.l_batch[i] = p->lse_stride[i].batch; kp.l_head[i] = p->lse_stride[i].head; kp.l_row[i] = p->lse_stride[i].row;
+    }
+    if ((rc = check_o("out", -1, p->out, p->out_stride))) return rc;
+    if ((rc = check_l("lse_out", -1, p->lse_out))) return rc;
+    kp.out_ptr = p->out; kp.lse_out_ptr = p->lse_out;
+    kp.out_batch = p->out_stride.batch; kp.out_row = p->out_stride.row; kp.out_head = p->out_stride.head;
+    kp.lo_batch = p->lse_out_stride.batch; kp.lo_head = p->lse_out_stride.head; kp.lo_row = p->lse_out_stride.row;
+    kp.total = total; kp.n_parts = p->n_parts; kp.rows = p->rows; kp.h = p->h;
+    return hip_status(fa::launch_merge_states(kp, p->dtype, p->d_v, (hipStream_t)p->stream), "fa_merge_states launch");
 }
 
 }  // extern "C"

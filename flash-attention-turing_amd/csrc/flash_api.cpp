@@ -618,6 +618,42 @@ std::vector<at::Tensor> mha_fwd_mla_prefill(at::Tensor q, at::Tensor k, at::Tens
     return {o, l};
 }
 
+// Merging attention states (fa_run_merge_states): dense outs[i] (b, rows, h, d_v) / lses[i] (b, h, rows) -> [out (b, rows, h, d_v), lse (b, h, rows)]; packed
+// outs[i] (total, h, d_v) / lses[i] (h, total) -> [out (total, h, d_v), lse (h, total)].  Nothing is copied: every part goes to the library with the strides it
+// has (an LSE with any strides at all), and a view it cannot address is its error.
+std::vector<at::Tensor> merge_states(std::vector<at::Tensor> outs, std::vector<at::Tensor> lses) {
+    TORCH_CHECK(outs.size() >= 2 && outs.size() <= FA_MERGE_MAX_PARTS && lses.size() == outs.size(), "merge_states takes 2 .. ", FA_MERGE_MAX_PARTS,
+                " parts, as many lses as outs");
+    const at::Tensor& o0 = outs[0];
+    const bool packed = o0.dim() == 3;
+    TORCH_CHECK(packed || o0.dim() == 4, "outs[0] must be (b, rows, h, d_v) or (total, h, d_v)");
+    TORCH_CHECK(o0.is_cuda(), "outs / lses must be GPU (HIP) tensors");
+    const int64_t b = packed ? 1 : o0.size(0), rows = o0.size(-3), h = o0.size(-2), dv = o0.size(-1);
+    TORCH_CHECK(b <= INT32_MAX && rows <= INT32_MAX && h <= INT32_MAX && dv <= INT32_MAX, "sizes must fit in int32");
+    fa_merge_params p;
+    FA_PARAMS_INIT(p);
+    p.dtype = fa_dtype_of(o0); p.n_parts = (int32_t)outs.size(); p.b = (int32_t)b; p.rows = (int32_t)rows; p.h = (int32_t)h; p.d_v = (int32_t)dv;
+    auto lse_strides = [&](const at::Tensor& l) { return packed ? fa_lse_strides{0, l.stride(0), l.stride(1)} : fa_lse_strides{l.stride(0), l.stride(1), l.stride(2)}; };
+    for (size_t i = 0; i < outs.size(); ++i) {
+        const at::Tensor& o = outs[i];
+        const at::Tensor& l = lses[i];
+        TORCH_CHECK(o.sizes() == o0.sizes() && o.scalar_type() == o0.scalar_type(), "outs[", i, "] must have the shape and dtype of outs[0]");
+        TORCH_CHECK(l.scalar_type() == torch::kFloat32 && l.dim() == o0.dim() - 1 && l.size(-1) == rows && l.size(-2) == h && (packed || l.size(0) == b),
+                    "lses[", i, "] must be a float32 tensor ", packed ? "(h, total)" : "(b, h, rows)");
+        check_same_device(o0, o, "outs[i]"); check_same_device(o0, l, "lses[i]");
+        p.o[i] = o.data_ptr(); p.o_stride[i] = packed ? strides3(o) : strides4(o);
+        p.lse[i] = l.data_ptr<float>(); p.lse_stride[i] = lse_strides(l);
+    }
+    c10::DeviceGuard guard(o0.device());
+    at::Tensor out = torch::empty(o0.sizes(), o0.options());
+    at::Tensor lse = packed ? torch::empty({h, rows}, o0.options().dtype(torch::kFloat32)) : torch::empty({b, h, rows}, o0.options().dtype(torch::kFloat32));
+    p.out = out.data_ptr(); p.out_stride = packed ? strides3(out) : strides4(out);
+    p.lse_out = lse.data_ptr<float>(); p.lse_out_stride = lse_strides(lse);
+    p.stream = current_stream(o0);
+    check_status(fa_run_merge_states(&p));
+    return {out, lse};
+}
+
 // The backward of MLA prefill attention (fa_run_mla_prefill_bwd): dout / out shaped like the forward's out, lse as the forward returned it -> [dq, dk, dv],
 // contiguous and shaped like q / k / v.  Nothing is copied: the tensors go to the library with the strides they have.  D (dsoftmax_sum) is allocated here.
 // phases: 0 = the call; 1 / 2 = only the dq or the dk / dv launch (measurements; 2 takes the D of an earlier call as `dsoftmax_sum`).
@@ -907,7 +943,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("cu_seqlens_q") = py::none(),
           py::arg("cu_seqlens_k") = py::none(), py::arg("is_causal") = false, py::arg("softmax_scale") = py::none(), py::arg("phases") = 0,
           py::arg("dsoftmax_sum") = py::none());
-    m.def("mla_indexer_logits", &mla_indexer_logits, "index logits of the DeepSeek-V3.2 indexer into the caller's fp32 buffer (b, sq, capacity)", py::arg("q_idx"), py::arg("weights"),
+    m.def("merge_states", &merge_states, "merge 2 .. 8 partial attention states (outs[i], lses[i]) of the same query rows -> [out, lse]; dense or packed", py::arg("outs"),
+          py::arg("lses"));
+    m.def("mla_indexer_logits", &mla_indexer_logits,"index logits of the DeepSeek-V3.2 indexer into the caller's fp32 buffer (b, sq, capacity)", py::arg("q_idx"), py::arg("weights"),
           py::arg("k_idx_cache"), py::arg("cache_seqlens"), py::arg("logits"), py::arg("k_scale") = py::none(), py::arg("block_table") = py::none(), py::arg("is_causal") = true);
     m.def("mla_indexer_topk", &mla_indexer_topk, "top-k positions of every logits row into the caller's int32 buffer (b, sq, topk)", py::arg("logits"), py::arg("cache_seqlens"),
           py::arg("indices"), py::arg("is_causal") = true);

@@ -195,8 +195,24 @@ class MlaPrefillBwdParams(_Params):
                 ("total_q", ctypes.c_int64), ("total_k", ctypes.c_int64)]
 
 
+FA_MERGE_MAX_PARTS = 8
+
+
+class LseStrides(ctypes.Structure):
+    """fa_lse_strides: the (batch, head, row) strides of an fp32 LSE, in elements"""
+    _fields_ = [("batch", ctypes.c_int64), ("head", ctypes.c_int64), ("row", ctypes.c_int64)]
+
+
+class MergeParams(_Params):
+    """fa_merge_params: n_parts partial attention states (o_i, lse_i) of the same query rows into one (fa_run_merge_states)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("dtype", _i32), ("n_parts", _i32), ("b", _i32), ("rows", _i32), ("h", _i32), ("d_v", _i32),
+                ("o", _vp * FA_MERGE_MAX_PARTS), ("o_stride", Strides * FA_MERGE_MAX_PARTS), ("lse", _vp * FA_MERGE_MAX_PARTS),
+                ("lse_stride", LseStrides * FA_MERGE_MAX_PARTS), ("out", _vp), ("out_stride", Strides), ("lse_out", _vp), ("lse_out_stride", LseStrides),
+                ("stream", _vp)]
+
+
 FA_MLA_KV_16BIT = 0
-FA_MLA_KV_FP8_ROWS656 = 1      # 656-byte latent rows: 512 e4m3 codes, four fp32 scales, 64 rope elements of q's dtype; kv_cache_stride in bytes
+FA_MLA_KV_FP8_ROWS656 = 1     # 656-byte latent rows: 512 e4m3 codes, four fp32 scales, 64 rope elements of q's dtype; kv_cache_stride in bytes
 FA_CACHE_FP8_E4M3 = 1
 FA_IDX_K_FP8_E4M3 = 1         # k_format of fa_mla_indexer_params: index keys as OCP e4m3 codes, strides in bytes
 
@@ -267,6 +283,8 @@ def lib():
         L.fa_run_mla_prefill_fwd.restype = ctypes.c_int
         L.fa_run_mla_prefill_bwd.argtypes = [ctypes.POINTER(MlaPrefillBwdParams), _vp]
         L.fa_run_mla_prefill_bwd.restype = ctypes.c_int
+        L.fa_run_merge_states.argtypes = [ctypes.POINTER(MergeParams)]
+        L.fa_run_merge_states.restype = ctypes.c_int
         L.fa_mha_fwd.argtypes = [_vp] * 5 + [_i32] * 8 + [_vp]
         L.fa_mha_bwd.argtypes = [_vp] * 10 + [_i32] * 8 + [_vp]
         L.fa_mha_varlen_fwd.argtypes = [_vp] * 7 + [_i32] * 8 + [_vp]
@@ -794,3 +812,24 @@ def run_mla_prefill_bwd(params, stream=None):
 
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     check(lib().fa_run_mla_prefill_bwd(ctypes.byref(params), s))
+
+
+def merge_params(outs, lses, out, lse_out, stream=None):
+    """fa_merge_params for parts outs[i] (b, rows, h, d_v) / lses[i] (b, h, rows), or packed outs[i] (total, h, d_v) / lses[i] (h, total): torch tensors with
+    strides of their own (an LSE may be any view of those shapes), the caller's out and lse_out.  stream: a raw stream handle, None = the default stream."""
+    p = MergeParams()
+    p.n_parts, p.dtype = len(outs), dtype_code(out.dtype)
+    packed = out.dim() == 3
+    p.b, p.rows, p.h, p.d_v = (1 if packed else out.shape[0]), out.shape[-3], out.shape[-2], out.shape[-1]
+    ostr = (lambda t: Strides(0, t.stride(0), t.stride(1))) if packed else (lambda t: Strides(t.stride(0), t.stride(1), t.stride(2)))
+    lstr = (lambda t: LseStrides(0, t.stride(0), t.stride(1))) if packed else (lambda t: LseStrides(t.stride(0), t.stride(1), t.stride(2)))
+    for i, (o, l) in enumerate(zip(outs, lses)):
+        p.o[i], p.lse[i], p.o_stride[i], p.lse_stride[i] = o.data_ptr(), l.data_ptr(), ostr(o), lstr(l)
+    p.out, p.lse_out, p.out_stride, p.lse_out_stride = out.data_ptr(), lse_out.data_ptr(), ostr(out), lstr(lse_out)
+    p.stream = stream
+    return p
+
+
+def run_merge_states(params):
+    """fa_run_merge_states (the stream is a field of the struct)"""
+    check(lib().fa_run_merge_states(ctypes.byref(params)))

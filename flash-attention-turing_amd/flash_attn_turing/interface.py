@@ -7,6 +7,7 @@ the tensor shapes and otherwise ignored) and the modern ``flash_attn_func(q, k, 
 """
 import math
 import numbers
+import re
 
 import torch
 
@@ -978,8 +979,8 @@ def flash_mla_prefill_func(q, k, v, *, cu_seqlens_q=None, cu_seqlens_k=None, sof
     No host synchronisation (cu_seqlens are read on the device: the call can be captured in a graph and replays with the values then in memory), no
     key split, so no workspace, and the call is deterministic.  Bit for bit: sequence i of a packed call equals the dense call on that sequence
     alone (out and lse), a batch entry of a dense call equals the call on it alone, and a power of two moved between q and softmax_scale changes
-    nothing.  Chunked prefill over a cached prefix needs no further API: run the context part with causal=False and the new tokens with
-    causal=True and merge the two results by their LSE (README.md).
+    nothing.  Chunked prefill over a cached prefix is flash_mla_chunked_prefill_func: the context part with causal=False, the new tokens with
+    causal=True, and flash_attn_merge_states of the two results.
     The backward is flash_mla_prefill_bwd, the differentiable function flash_mla_attn_func.
     Out of scope, and without a keyword here: FP8 or paged inputs, other widths, window_size, softcap, sinks, a key split.  Wrong shapes,
     dtypes, views or values are a ValueError that names the argument.
@@ -1114,4 +1115,207 @@ def flash_mla_attn_func(q, k, v, *, cu_seqlens_q=None, cu_seqlens_k=None, softma
         out, lse = _FlashMlaAttn.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale, causal)
     else:
         out, lse = _C.fwd_mla_prefill(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale)
+    return (out, lse) if return_softmax_lse else out
+
+
+MERGE_MAX_PARTS = 8             # FA_MERGE_MAX_PARTS of the C ABI
+MERGE_WIDTHS = (64, 128, 256, 512)
+
+
+def flash_attn_merge_states(outs, lses):
+    """Merge partial attention states: 2 .. 8 results ``(out_i, lse_i)`` of attention calls over DISJOINT key sets of the same query rows -> the result over the
+    union of the keys (vLLM's ``merge_attn_states``, FlashInfer's ``merge_state``).  Forward only.
+
+    dense:  outs[i] (batch, seqlen_q, nheads, d_v), lses[i] (batch, nheads, seqlen_q) -> out (batch, seqlen_q, nheads, d_v), lse (batch, nheads, seqlen_q)
+    packed: outs[i] (total, nheads, d_v),           lses[i] (nheads, total)           -> out (total, nheads, d_v),           lse (nheads, total)
+    outs: fp16 or bf16, one dtype, shape and device for all; d_v 64, 128, 256 or 512; the last dimension contiguous, every other stride and the storage offset
+    multiples of 8 elements, each part with strides of its own.  lses: float32 (natural log), ANY strides - the LSE ``(1, nheads, batch * seqlen_q)`` of a call
+    that took all query rows as one sequence is passed as its ``(batch, nheads, seqlen_q)`` view.  Views are used in place; a view the kernel cannot address is
+    a ValueError that names the argument, never a copy.  out and lse are new contiguous tensors.
+
+    In fp32 over the NON-EMPTY parts of a (row, head), in argument order: ``m = max_i lse_i``, ``w_i = exp(lse_i - m)``,
+    ``out = (sum_i w_i out_i) / (sum_i w_i)`` rounded once to the dtype, ``lse = m + log(sum_i w_i)``.
+
+    EMPTY - the one rule, used by every function built on this one: part i is empty for a (row, head) iff ``lse_i`` is -inf, or ``lse_i`` is +-0 and every
+    element of that ``out_i`` row is +-0.  The second form is what every attention call of this library returns for a row that sees no key (O = 0, LSE = 0).
+    Caveat: a LIVE row looks like that only when its scores sum to exactly one (lse = 0) and its V rows are all zero; it is then taken as empty, and the
+    merged lse lacks its weight.  An empty part contributes nothing.  All parts empty gives out = 0, lse = 0 - the library's dead row again, so a merged state
+    can feed another merge.  A part merged with empty parts, in any argument position, comes back bit for bit.  A NaN ``lse_i``, or a NaN in a non-empty
+    part's row, makes that (row, head) NaN in out and lse and no other; ``lse_i`` = +inf has no contract.
+
+    One launch on the current stream, no workspace, no atomics, no host synchronisation: deterministic and graph-capturable.  Nothing between the rows, heads
+    and batch entries that the strides skip is read.  Out of scope: more than 8 parts in one call (merge the merges), parts of different dtypes, fp32 parts,
+    a backward.  Wrong counts, shapes, dtypes, devices or views are a ValueError; a CPU call is refused by the extension (there is no fall-back).
+    """
+    for name, seq in (("outs", outs), ("lses", lses)):
+        if not isinstance(seq, (list, tuple)) or not all(isinstance(t, torch.Tensor) for t in seq):
+            raise ValueError(f"{name} must be a list or tuple of tensors")
+    if not 2 <= len(outs) <= MERGE_MAX_PARTS:
+        raise ValueError(f"outs must hold 2 .. {MERGE_MAX_PARTS} parts, got {len(outs)}")
+    if len(lses) != len(outs):
+        raise ValueError(f"lses must hold as many tensors as outs ({len(outs)}), got {len(lses)}")
+    o0 = outs[0]
+    if o0.dim() not in (3, 4):
+        raise ValueError(f"outs[0] must be (batch, seqlen_q, nheads, d_v) or packed (total, nheads, d_v), got shape {tuple(o0.shape)}")
+    if o0.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"outs[0] must be fp16 or bf16, got {o0.dtype}")
+    if o0.shape[-1] not in MERGE_WIDTHS:
+        raise ValueError(f"outs[0]: d_v must be one of {MERGE_WIDTHS}, got {o0.shape[-1]}")
+    l_shape = (o0.shape[1], o0.shape[0]) if o0.dim() == 3 else (o0.shape[0], o0.shape[2], o0.shape[1])
+    for i, (o, l) in enumerate(zip(outs, lses)):
+        if tuple(o.shape) != tuple(o0.shape):
+            raise ValueError(f"outs[{i}] must have the shape of outs[0] {tuple(o0.shape)}, got {tuple(o.shape)}")
+        if o.dtype != o0.dtype:
+            raise ValueError(f"outs[{i}] must have the dtype of outs[0] ({o0.dtype}), got {o.dtype}")
+        if o.device != o0.device:
+            raise ValueError(f"outs[{i}] must be on the device of outs[0] ({o0.device}), got {o.device}")
+        if l.dtype != torch.float32:
+            raise ValueError(f"lses[{i}] must be float32, got {l.dtype}")
+        if tuple(l.shape) != l_shape:
+            raise ValueError(f"lses[{i}] must have shape {l_shape} ({'(nheads, total)' if o0.dim() == 3 else '(batch, nheads, seqlen_q)'}), got {tuple(l.shape)}")
+        if l.device != o0.device:
+            raise ValueError(f"lses[{i}] must be on the device of outs[0] ({o0.device}), got {l.device}")
+        _check_prefill_view(f"outs[{i}]", o)
+        if torch.is_grad_enabled() and (o.requires_grad or l.requires_grad):
+            raise ValueError(f"{'outs' if o.requires_grad else 'lses'}[{i}] requires grad: flash_attn_merge_states is forward-only; run it under torch.no_grad() or detach "
+                             "the inputs")
+    out, lse = _C.merge_states(list(outs), list(lses))
+    return out, lse
+
+
+def flash_attn_with_shared_prefix(q, k_cache, v_cache, shared_prefix_len, k=None, v=None, cache_seqlens=None, *, block_table=None, causal=False,
+                                  softmax_scale=None, k_descale=None, v_descale=None, return_softmax_lse=False):
+    """``flash_attn_with_kvcache`` for a batch whose sequences all start with the same ``shared_prefix_len`` cached keys (a system prompt; cascade attention
+    in vLLM and FlashInfer): the prefix is read ONCE for the whole batch instead of once per sequence.  Forward only.
+
+    Semantics: exactly those of ``flash_attn_with_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, causal=causal, block_table=block_table,
+    softmax_scale=softmax_scale, k_descale=k_descale, v_descale=v_descale)`` - which keys a row sees, the append of k / v, dead rows O = 0, LSE = 0, the NaN
+    rules.  The values agree to rounding, not bit for bit: the parts are rounded to q's dtype before they are merged (at most one more half ulp of the
+    largest part).  q is dense, (batch, seqlen_q, nheads, d); cache_seqlens an int32 tensor, an int or None as there.
+
+    Preconditions, NOT checked (device values): the first ``shared_prefix_len`` keys of every sequence are the same physical rows - paged: the first
+    ``shared_prefix_len / page_block_size`` block_table entries of every sequence are equal; contiguous: batch entry 0's first rows stand for all -;
+    ``cache_seqlens[i] >= shared_prefix_len``; with an FP8 cache the descales of all sequences are equal.  Row 0 (of the table, the cache, the descales) is
+    what is read for the prefix.
+    Refused (ValueError): a shared_prefix_len that is not a Python int >= 0, not a multiple of page_block_size (paged) or of 16 (contiguous), or not below the
+    capacity; an int cache_seqlens below it; a q whose batch stride is not seqlen_q x its row stride (the batch must flatten into one row dimension).
+    shared_prefix_len = 0 is the plain call, bit for bit.
+
+    How: three launches on the current stream, no host synchronisation (graph-capturable; lengths, tables and descales are read on the device).  (a) the
+    prefix part: flash_attn_with_kvcache on q viewed as (1, batch * seqlen_q, nheads, d) over the first keys of row 0, causal=False, on the 64-row kernels
+    (prefill=True) when batch * seqlen_q * nheads / nheads_k >= 64 and d != 256, else on the 16-row kernels.  (b) the suffix part: flash_attn_with_kvcache
+    over ``block_table[:, Ls / page_block_size:]`` (contiguous: ``k_cache[:, Ls:]``) with ``cache_seqlens - Ls``, the caller's causal and the append.  (c)
+    flash_attn_merge_states of the two, the LSE of (a) passed as a strided view; a sequence without a suffix has dead suffix rows, which the merge's
+    emptiness rule leaves out.  Under ``causal`` with seqlen_q > 1 the earlier rows of a sequence may not see the last seqlen_q - 1 keys, which can lie in
+    the prefix when the suffix is shorter than that: the split point Ls is therefore shared_prefix_len lowered by seqlen_q - 1 rounded up to the page (16
+    rows), so every key (a) serves is visible to every row; if nothing is left, the plain call runs.  For seqlen_q = 1 Ls is shared_prefix_len.
+
+    Supported: fp16 / bf16, head_dim 64 / 128 / 256, GQA / MQA, both cache layouts, the FP8 cache, the k / v append.  Out of scope, and without a keyword
+    here: window_size, rotary, sinks, tree_mask, cu_seqlens_q, softcap, num_splits, several prefix levels.  It pays for long prefixes and large batches and
+    loses to the plain call for short ones (three launches against one; README.md has the measured table).
+    """
+    if isinstance(shared_prefix_len, bool) or not isinstance(shared_prefix_len, int) or shared_prefix_len < 0:
+        raise ValueError(f"shared_prefix_len must be a Python int >= 0, got {shared_prefix_len!r}")
+    if not isinstance(causal, bool):
+        raise ValueError(f"causal must be a bool, got {causal!r}")
+    if (k is None) != (v is None):
+        raise ValueError("k and v must both be given or both be None")
+    plain = dict(causal=causal, block_table=block_table, softmax_scale=softmax_scale, k_descale=k_descale, v_descale=v_descale)
+    if shared_prefix_len == 0:
+        return flash_attn_with_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, return_softmax_lse=return_softmax_lse, **plain)
+    for name, t in (("q", q), ("k_cache", k_cache), ("v_cache", v_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{name} must be a rank-4 tensor")
+    if block_table is not None and (not isinstance(block_table, torch.Tensor) or block_table.dim() != 2):
+        raise ValueError("block_table must be a rank-2 int32 tensor (batch, max_blocks_per_seq)")
+    granule = k_cache.shape[1] if block_table is not None else 16
+    capacity = k_cache.shape[1] * (block_table.shape[1] if block_table is not None else 1)
+    if granule < 1 or shared_prefix_len % granule != 0:
+        raise ValueError(f"shared_prefix_len ({shared_prefix_len}) must be a multiple of " + (f"page_block_size ({granule})" if block_table is not None else "16"))
+    if shared_prefix_len >= capacity:
+        raise ValueError(f"shared_prefix_len ({shared_prefix_len}) must be below the cache capacity ({capacity}): nothing would be left for a suffix")
+    if isinstance(cache_seqlens, int) and not isinstance(cache_seqlens, bool) and cache_seqlens < shared_prefix_len:
+        raise ValueError(f"cache_seqlens ({cache_seqlens}) must be at least shared_prefix_len ({shared_prefix_len})")
+    b, sq, h, d = q.shape
+    if b > 1 and sq > 1 and q.stride(0) != sq * q.stride(1):
+        raise ValueError(f"q: the batch stride ({q.stride(0)}) must be seqlen_q ({sq}) x the row stride ({q.stride(1)}) - the prefix part takes the "
+                         "batch * seqlen_q query rows as one sequence; the view is not copied")
+    # under causal the last seqlen_q - 1 keys are not visible to every row: they stay with the suffix part
+    hold_back = -(-(sq - 1) // granule) * granule if causal else 0
+    ls = shared_prefix_len - hold_back
+    if ls <= 0:
+        return flash_attn_with_kvcache(q, k_cache, v_cache, k, v, cache_seqlens, return_softmax_lse=return_softmax_lse, **plain)
+    h_k = k_cache.shape[2]
+    row_stride = q.stride(1) if sq > 1 else q.stride(0)
+    q_rows = q.as_strided((1, b * sq, h, d), (b * sq * row_stride, row_stride, q.stride(2), q.stride(3)))
+    descale_a = dict(k_descale=None if k_descale is None else k_descale[:1], v_descale=None if v_descale is None else v_descale[:1])
+    wide = h_k > 0 and h % h_k == 0 and b * sq * (h // h_k) >= 64 and d != 256
+    if block_table is not None:
+        pages = ls // granule
+        cache_a = dict(block_table=block_table[:1, :pages])
+        ka, va = k_cache, v_cache
+        kb, vb, cache_b = k_cache, v_cache, dict(block_table=block_table[:, pages:])
+    else:
+        cache_a, cache_b = {}, {}
+        ka, va = k_cache[:1, :ls], v_cache[:1, :ls]
+        kb, vb = k_cache[:, ls:], v_cache[:, ls:]
+    # (a) every query row of the batch over the shared keys, read once: cache_seqlens=None is "the whole capacity", which is exactly the ls keys of the view
+    out_a, lse_a = flash_attn_with_kvcache(q_rows, ka, va, None, None, None, causal=False, return_softmax_lse=True, softmax_scale=softmax_scale, prefill=wide,
+                                           **cache_a, **descale_a)
+    # (b) each sequence over its own keys
+    if isinstance(cache_seqlens, torch.Tensor):
+        seqlens_b = cache_seqlens - ls
+    else:
+        seqlens_b = None if cache_seqlens is None else cache_seqlens - ls
+    out_b, lse_b = flash_attn_with_kvcache(q, kb, vb, k, v, seqlens_b, causal=causal, return_softmax_lse=True, softmax_scale=softmax_scale, k_descale=k_descale,
+                                           v_descale=v_descale, **cache_b)
+    # (c) lse_a is (1, h, b * sq): row i * sq + t of the flattened batch is (i, t)
+    out, lse = flash_attn_merge_states((out_a.view(b, sq, h, d), out_b), (lse_a.as_strided((b, h, sq), (sq, b * sq, 1)), lse_b))
+    return (out, lse) if return_softmax_lse else out
+
+
+def flash_mla_chunked_prefill_func(q, k_ctx, v_ctx, k_new, v_new, *, cu_seqlens_q=None, cu_seqlens_k_ctx=None, softmax_scale=None, return_softmax_lse=False):
+    """MLA chunked prefill over a cached context: the new tokens of every sequence attend to that sequence's context keys (all of them) and to the new tokens
+    themselves (causally) - ``flash_mla_prefill_func`` over the concatenation ``[ctx_i, new_i]`` with causal=True, without building the concatenation.
+
+    dense:  q (batch, seqlen_q, nheads, 192), k_ctx (batch, seqlen_ctx, nheads_k, 192), v_ctx (batch, seqlen_ctx, nheads_k, 128), k_new (batch, seqlen_q,
+            nheads_k, 192), v_new (batch, seqlen_q, nheads_k, 128) -> out (batch, seqlen_q, nheads, 128), lse (batch, nheads, seqlen_q) with return_softmax_lse.
+    packed: q (total_q, nheads, 192), k_new / v_new (total_q, nheads_k, .) under cu_seqlens_q and k_ctx / v_ctx (total_ctx, nheads_k, .) under
+            cu_seqlens_k_ctx, given both or neither -> out (total_q, nheads, 128), lse (nheads, total_q).  A sequence may have no context and may have no
+            query rows.  Rows of out / lse at or past cu_seqlens_q[-1] hold unspecified values.
+    Every argument under the rules of flash_mla_prefill_func (dtypes, widths, views, softmax_scale).  Three launches on the current stream, no host
+    synchronisation: flash_mla_prefill_func(q, k_ctx, v_ctx, causal=False), flash_mla_prefill_func(q, k_new, v_new, causal=True) with cu_seqlens_k =
+    cu_seqlens_q, and flash_attn_merge_states of the two.  A sequence without context has dead rows (O = 0, LSE = 0) in the first part, which the merge's
+    emptiness rule leaves out (flash_attn_merge_states has the rule and its caveat).  Values: fp32 math over all visible keys, each part rounded once to
+    q's dtype before the merge.  Forward only; out of scope: everything that is out of scope for flash_mla_prefill_func, more than one context chunk per
+    call (merge further chunks with flash_attn_merge_states).
+    """
+    tensors = (("q", q), ("k_ctx", k_ctx), ("v_ctx", v_ctx), ("k_new", k_new), ("v_new", v_new))
+    for name, t in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a tensor")
+    if torch.is_grad_enabled() and any(t.requires_grad for _, t in tensors):
+        bad = next(n for n, t in tensors if t.requires_grad)
+        raise ValueError(f"{bad} requires grad: flash_mla_chunked_prefill_func is forward-only (the differentiable function is flash_mla_attn_func); run it under "
+                         "torch.no_grad() or detach the inputs")
+    if (cu_seqlens_q is None) != (cu_seqlens_k_ctx is None):
+        raise ValueError("cu_seqlens_q and cu_seqlens_k_ctx come both or neither, got only " + ("cu_seqlens_q" if cu_seqlens_k_ctx is None else "cu_seqlens_k_ctx"))
+    rank = 3 if cu_seqlens_q is not None else 4
+    for name, t in tensors:
+        if t.dim() != rank:
+            raise ValueError(f"{name} must be a rank-{rank} tensor ({'(total, nheads, head_dim) with cu_seqlens' if rank == 3 else '(batch, seqlen, nheads, head_dim)'})")
+    if k_new.shape[-3] != q.shape[-3] or v_new.shape[-3] != q.shape[-3]:
+        raise ValueError(f"k_new / v_new must have one row per query row ({q.shape[-3]}), got {k_new.shape[-3]} and {v_new.shape[-3]}")
+    # the checks of flash_mla_prefill_func on each part, its messages with this function's argument names (k / v -> k_ctx / v_ctx, k_new / v_new)
+    def checked(k, v, cu_k, causal, suffix):
+        try:
+            return _check_mla_prefill_args(q, k, v, cu_seqlens_q, cu_k, softmax_scale, causal, forward_only=True)
+        except ValueError as e:
+            raise ValueError(re.sub(r"\b(k|v|cu_seqlens_k)\b", lambda m: m.group(1) + suffix, str(e))) from None
+
+    softmax_scale_ = checked(k_ctx, v_ctx, cu_seqlens_k_ctx, False, "_ctx")
+    checked(k_new, v_new, cu_seqlens_q, True, "_new")
+    out_c, lse_c = _C.fwd_mla_prefill(q, k_ctx, v_ctx, cu_seqlens_q, cu_seqlens_k_ctx, False, softmax_scale_)
+    out_n, lse_n = _C.fwd_mla_prefill(q, k_new, v_new, cu_seqlens_q, cu_seqlens_q, True, softmax_scale_)
+    out, lse = _C.merge_states([out_c, out_n], [lse_c, lse_n])
     return (out, lse) if return_softmax_lse else out

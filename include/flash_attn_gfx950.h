@@ -990,6 +990,54 @@ typedef struct fa_mla_prefill_bwd_params {
     int64_t total_k;            /* packed: rows of k / v / dk / dv */
 } fa_mla_prefill_bwd_params;
 
+/* Merging attention states (FA_HAS_MERGE_STATES; merge_attn_states of vLLM, merge_state of FlashInfer): every attention call of this library returns
+ * (o, lse), and n_parts such results over DISJOINT key sets of the same query rows combine into the result over the union.  FA_ABI_VERSION is unchanged; the
+ * presence of fa_run_merge_states is how a caller detects the feature.  struct_size must be sizeof(fa_merge_params) (FA_PARAMS_INIT).
+ *   o[i]            part i, (b, rows, h, d_v) of `dtype`, last dimension contiguous, with o_stride[i] (batch / row / head, elements, multiples of 8) of its
+ *                   own and a 16-byte aligned base; 2 <= n_parts <= FA_MERGE_MAX_PARTS, entries at or past n_parts are not read
+ *   lse[i]          fp32, entry (batch, head, row) at lse[i][batch * lse_stride[i].batch + head * lse_stride[i].head + row * lse_stride[i].row]: strides in
+ *                   elements, ANY values.  One form covers the dense (b, h, rows) layout, the packed (h, total) layout (b = 1) and the LSE (1, h, b * rows)
+ *                   of a call that took the b * rows query rows as one sequence (batch stride = rows, head stride = b * rows, row stride = 1)
+ *   out, lse_out    the results, shaped and addressed like the parts, with out_stride / lse_out_stride of their own
+ *   d_v             64, 128, 256 or 512
+ * In fp32 over the NON-EMPTY parts of a (row, head), in argument order: m = max_i lse_i, w_i = exp(lse_i - m), out = (sum_i w_i o_i) / (sum_i w_i) rounded
+ * once to dtype, lse_out = m + log(sum_i w_i).
+ * EMPTY, the one rule: part i is empty for a (row, head) iff lse_i is -inf, or lse_i is +-0 and every element of that o_i row is +-0.  The second form is
+ * what every attention call of this library returns for a row that sees no key.  (A live row can look like that only when its scores sum to exactly one
+ * and its V rows are all zero: it is then taken as empty.)  An empty part contributes nothing; all parts empty gives out = 0, lse_out = 0 - the dead row
+ * again, so a merged state can feed another merge.  A part merged with empty parts comes back bit for bit, out and lse.  A NaN lse_i, or a NaN in a
+ * non-empty part's row, makes that (row, head) NaN in out and lse_out, and no other.  lse_i = +inf has no contract.  Nothing at or past row b * rows, and
+ * nothing between the rows, heads and batch entries the strides skip, is read or written.
+ * One launch on `stream`, no workspace, no atomics, no host synchronisation, deterministic.  out must not overlap a part unless it is that part's very view.
+ * Errors, the field named by fa_last_error: n_parts FA_ERR_BAD_SHAPE, d_v FA_ERR_BAD_HEADDIM, dtype FA_ERR_BAD_DTYPE, b / rows / h FA_ERR_BAD_SHAPE,
+ * pointers FA_ERR_NULL_POINTER, strides and alignment FA_ERR_BAD_STRIDE, the header FA_ERR_BAD_ABI.  b * rows * h == 0 is FA_OK without a launch. */
+#define FA_HAS_MERGE_STATES 1
+#define FA_MERGE_MAX_PARTS 8
+typedef struct fa_lse_strides {
+    int64_t batch;
+    int64_t head;
+    int64_t row;
+} fa_lse_strides;
+typedef struct fa_merge_params {
+    uint32_t struct_size;       /* sizeof(fa_merge_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    int32_t dtype;
+    int32_t n_parts;            /* 2 .. FA_MERGE_MAX_PARTS */
+    int32_t b;
+    int32_t rows;
+    int32_t h;
+    int32_t d_v;                /* 64, 128, 256, 512 */
+    const void* o[FA_MERGE_MAX_PARTS];
+    fa_strides o_stride[FA_MERGE_MAX_PARTS];
+    const float* lse[FA_MERGE_MAX_PARTS];
+    fa_lse_strides lse_stride[FA_MERGE_MAX_PARTS];
+    void* out;
+    fa_strides out_stride;
+    float* lse_out;
+    fa_lse_strides lse_out_stride;
+    void* stream;               /* the stream of fa_run_merge_states (hipStream_t; NULL = the default stream) */
+} fa_merge_params;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -1087,6 +1135,10 @@ int fa_run_mla_indexer_topk(const fa_mla_topk_params* params, void* stream);
 int fa_run_mla_prefill_fwd(const fa_mla_prefill_params* params, void* stream);
 /* Its backward (fa_mla_prefill_bwd_params above): two launches on `stream`, dsoftmax_sum the only workspace, no host synchronisation. */
 int fa_run_mla_prefill_bwd(const fa_mla_prefill_bwd_params* params, void* stream);
+
+/* ---- merging attention states (fa_merge_params above) ------------------------------------------ */
+/* One launch on params->stream, no workspace, no host synchronisation. */
+int fa_run_merge_states(const fa_merge_params* params);
 
 /* ---- measurement helpers ----------------------------------------------------------------- */
 /* Algorithmic FLOPs of one forward call (4*b*h*sq*sk*d, causal counts only visible pairs);

@@ -100,6 +100,12 @@ figure.  TFLOP/s of the new call at 2 sq sk h (192 + 128) per batch entry, halve
 (profiles/mla_prefill_bench.log).  With --baseline-library PATH (e.g. tools/abl/libfa_mlap_rows32.so built with -DFA_MLAP_WAVE_ROWS=32) the point becomes an
 A / B of the new call itself through the C ABI of this build (A, timed twice) and of the library at PATH (B).
 
+--merge measures flash_attn_merge_states alone: 2, 4, 8 contiguous bf16 parts of (rows, 4 heads, d_v 128 / 512), rows from 4k to 1M (points over 40 GiB are left out); bytes moved (the parts
+read, one result written, out and lse) / time against 6.3 TB/s, next to the torch formulation of the same merge (logaddexp, exp, weighted sum; timed twice),
+interleaved in one process, medians (profiles/merge_states_bench.log).
+--shared-prefix measures flash_attn_with_shared_prefix (b 8 / 64, sq 1, h 32 / h_k 8, d 128, pages of 16, 16-bit and FP8 caches, a shared prefix of 2k / 8k /
+32k keys and 128 own keys per sequence) against flash_attn_with_kvcache on the same tables (timed twice), interleaved, medians
+(profiles/shared_prefix_bench.log).
 --baseline-library PATH records an interleaved A/B of the plain (no window) call through the C ABI of this build and of the library at
 PATH (e.g. a build of the parent commit), on the same data; the outputs must agree bit for bit.  --length L (repeatable) replaces the
 grid's cache lengths."""
@@ -1228,6 +1234,75 @@ def run_mla_prefill_bwd(quick, rounds):
             yield run_mla_prefill_bwd_point(b, h, sq, sk, causal, rounds)
 
 
+def run_merge_point(n, dv, rows, rounds, h=4, dt=torch.bfloat16):
+    """flash_attn_merge_states alone on `n` contiguous parts of (rows, h, d_v) against the torch formulation of the same merge (the five ops README.md printed
+    before the call existed, folded over the parts; timed twice: its noise figure); bytes moved = n parts read + one written, out and lse, against 6.3 TB/s"""
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(n * 1000 + dv)
+    outs = [torch.randn(rows, h, dv, device=dev, dtype=dt, generator=gen) for _ in range(n)]
+    lses = [torch.randn(h, rows, device=dev, generator=gen) * 4 for _ in range(n)]
+
+    def torch_merge():
+        lse = lses[0]
+        for l in lses[1:]:
+            lse = torch.logaddexp(lse, l)
+        acc = None
+        for o, l in zip(outs, lses):
+            term = torch.exp(l - lse).t().unsqueeze(-1) * o.float()
+            acc = term if acc is None else acc + term
+        return acc.to(dt), lse
+
+    ours = lambda: F.flash_attn_merge_states(outs, lses)
+    a, b_ = ours(), torch_merge()
+    diff = float((a[0].float() - b_[0].float()).abs().max())
+    ms = _mlap_time({"torch": torch_merge, "merge": ours, "torch_again": torch_merge}, rounds, iters=5)
+    nbytes = (n + 1) * (rows * h * dv * 2 + rows * h * 4)
+    return dict(mode="merge", n_parts=n, d_v=dv, rows=rows, h=h, dtype=str(dt).replace("torch.", ""), mbytes=round(nbytes / 2 ** 20, 1), ms_merge=round(ms["merge"], 4),
+                tb_s=round(nbytes / ms["merge"] / 1e9, 3), frac_of_6p3=round(nbytes / ms["merge"] / 1e9 / 6.3, 3), ms_torch=round(ms["torch"], 4),
+                ms_torch_again=round(ms["torch_again"], 4), merge_over_torch=round(ms["merge"] / ms["torch"], 3), max_abs_diff=diff)
+
+
+def run_merge(quick, rounds):
+    for n in (2, 4, 8):
+        for dv in (128, 512):
+            for rows in ((4096, 65536) if quick else (4096, 16384, 65536, 262144, 1048576)):
+                if ((n + 1) * 2 + 3 * 4) * rows * 4 * dv > (40 << 30):          # (parts, result and the torch formulation's fp32 terms: skip what would take over 40 GiB)
+                    continue
+                yield run_merge_point(n, dv, rows, rounds)
+
+
+def run_shared_prefix_point(b, prefix, fp8, rounds, own=128, h=32, hk=8, d=128, page=16, dt=torch.float16):
+    """flash_attn_with_shared_prefix against flash_attn_with_kvcache on the same tables (timed twice: its noise figure): sq 1, pages of 16, a shared prefix and
+    `own` keys per sequence"""
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(b * 7 + prefix)
+    n_pre, n_own = prefix // page, own // page
+    nb = n_pre + b * n_own
+    kp, vp = (torch.randn(nb, page, hk, d, device=dev, dtype=dt, generator=gen) for _ in range(2))
+    kw = {}
+    if fp8:
+        kp, vp = kp.to(torch.float8_e4m3fn), vp.to(torch.float8_e4m3fn)
+        kw = dict(k_descale=torch.full((b, hk), 0.5, device=dev), v_descale=torch.full((b, hk), 0.5, device=dev))
+    perm = torch.randperm(nb, device=dev, generator=gen)
+    table = torch.cat([perm[:n_pre].unsqueeze(0).expand(b, n_pre), perm[n_pre:].view(b, n_own)], dim=1).to(torch.int32).contiguous()
+    q = torch.randn(b, 1, h, d, device=dev, dtype=dt, generator=gen)
+    cs = torch.full((b,), prefix + own, dtype=torch.int32, device=dev)
+    new = lambda: F.flash_attn_with_shared_prefix(q, kp, vp, prefix, cache_seqlens=cs, block_table=table, **kw)
+    plain = lambda: F.flash_attn_with_kvcache(q, kp, vp, cache_seqlens=cs, block_table=table, **kw)
+    diff = float((new().float() - plain().float()).abs().max())
+    ms = _mlap_time({"plain": plain, "shared_prefix": new, "plain_again": plain}, rounds, iters=5)
+    return dict(mode="shared_prefix", b=b, seqlen_q=1, h=h, h_k=hk, d=d, page=page, kv_dtype="fp8" if fp8 else "fp16", prefix=prefix, own=own,
+                ms_shared_prefix=round(ms["shared_prefix"], 4), ms_plain=round(ms["plain"], 4), ms_plain_again=round(ms["plain_again"], 4),
+                shared_over_plain=round(ms["shared_prefix"] / ms["plain"], 3), max_abs_diff=diff)
+
+
+def run_shared_prefix(quick, rounds):
+    for fp8 in (False, True):
+        for b in (8, 64):
+            for prefix in ((8192,) if quick else (2048, 8192, 32768)):
+                yield run_shared_prefix_point(b, prefix, fp8, rounds)
+
+
 def _baseline_lib(path):
     L = ctypes.CDLL(os.path.abspath(path))
     L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
@@ -1324,6 +1399,10 @@ def main():
                                                                "the call itself against that library")
     ap.add_argument("--mla-prefill-bwd", action="store_true", help="the MLA prefill backward (flash_mla_prefill_bwd, bf16, the grid of --mla-prefill): both launches and "
                                                                    "each alone against bwd at head_dim 128 and against autograd of the torch formulation, each timed twice")
+    ap.add_argument("--merge", action="store_true", help="flash_attn_merge_states alone (2, 4, 8 parts; d_v 128, 512; 4k .. 1M rows of 4 heads, bf16): bytes moved / time "
+                                                         "against 6.3 TB/s, next to the torch formulation of the merge (timed twice)")
+    ap.add_argument("--shared-prefix", action="store_true", help="flash_attn_with_shared_prefix (b 8 / 64, sq 1, h 32 / h_k 8, d 128, pages of 16, 16-bit and FP8 caches, prefix "
+                                                                 "2k / 8k / 32k, 128 own keys) against flash_attn_with_kvcache on the same tables (timed twice)")
     a = ap.parse_args()
     base = _baseline_lib(a.baseline_library) if a.baseline_library else None
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
@@ -1331,6 +1410,10 @@ def main():
     if base is not None:
         print(json.dumps({"baseline_library": base.fa_build_info().decode()}), flush=True)
     with torch.no_grad():
+        if a.merge or a.shared_prefix:
+            for line in (run_merge if a.merge else run_shared_prefix)(a.quick, a.rounds):
+                print(json.dumps(line), flush=True)
+            return
         if a.mla_prefill_bwd:
             for line in run_mla_prefill_bwd(a.quick, a.rounds):
                 print(json.dumps(line), flush=True)
