@@ -41,14 +41,13 @@ HIP_SOURCES = ["fa_fwd_pp.hip", "fa_fwd_pp16.hip", "fa_bwd.hip", "fa_bwd_dq16.hi
 # are placed first and the prefetch sets take the AGPRs: no moves, no scratch, 408-412 registers (16-bit cache) / 276-280 (8-bit)
 EXTRA_FLAGS = {"fa_fwd_pp16.hip": ["-fno-slp-vectorize"], "fa_bwd_dq16.hip": ["-fno-slp-vectorize"], "fa_bwd_dkdv16.hip": ["-fno-slp-vectorize"],
                "fa_fwd_kvcache_d256.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"],
-               # fa_fwd_kvcache_mla.hip: the same at one workgroup per unit - O^T (128 registers) and the softmax need VGPRs, Q^T (72) and the staging set (36) may
-               # live in AGPRs; without the flag 3-5 v_accvgpr moves stay in the loop of every attention kernel, with it none (254-256 VGPRs + 72-76 AGPRs, no scratch)
+               # the three MLA decode sources share one body (fa_kvcache_mla_attn.hpp): the same at one workgroup per unit - O^T (128 registers) and the softmax need
+               # VGPRs, Q^T (72) and the staging set (36; 24 over the FP8 rows) may live in AGPRs; without the flag 3-5 v_accvgpr moves stay in the loop of every
+               # attention kernel, with it none (254-256 VGPRs + 68-78 AGPRs, no scratch)
                "fa_fwd_kvcache_mla.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"],
-               # fa_fwd_kvcache_mla_sparse.hip: the body of the dense MLA kernels with a gathered staging step - the same register picture, the same flag
                "fa_fwd_kvcache_mla_sparse.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"],
-               # fa_fwd_kvcache_mla_fp8.hip: both bodies over the FP8 latent cache - only the staging differs (24 registers in place of 36), the same flag
                "fa_fwd_kvcache_mla_fp8.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"]}
-HIP_HEADERS = ["fa_device.hpp", "fa_params.hpp", "fa_bwd_dkdv_common.hpp", "fa_kvcache_quant.hpp", "fa_kvcache_attn.hpp", "fa_kvcache_kernels.hpp", "fa_kvcache_launch.hpp", "fa_kvcache_rotary.hpp", "fa_kvcache_stage_debug.hpp", "fa_mla_indexer.hpp", "fa_merge_states.hpp", os.path.join(INCLUDE, "flash_attn_gfx950.h")]
+HIP_HEADERS = ["fa_device.hpp", "fa_params.hpp", "fa_bwd_dkdv_common.hpp", "fa_kvcache_quant.hpp", "fa_kvcache_attn.hpp", "fa_kvcache_kernels.hpp", "fa_kvcache_launch.hpp", "fa_kvcache_mla_attn.hpp", "fa_kvcache_rotary.hpp", "fa_kvcache_stage_debug.hpp", "fa_mla_indexer.hpp", "fa_merge_states.hpp", os.path.join(INCLUDE, "flash_attn_gfx950.h")]
 # -amdgpu-mfma-vgpr-form: builtin MFMAs keep their result in VGPRs even in kernels that may use the
 # accumulator half of the register file (the dK/dV kernel parks its 128 long-lived accumulator
 # registers in AGPRs through LP<T>::mfma_agpr); without it hipcc selects the AGPR form for every MFMA

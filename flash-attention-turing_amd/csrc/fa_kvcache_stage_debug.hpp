@@ -1,6 +1,7 @@
 // fa_kvcache_stage_debug.hpp — adversarial timing for the register-staged LDS stages of the 64-row KV-cache bodies (test builds only).
 //
-//   fa_fwd_kvcache_prefill.hip, fa_fwd_kvcache_mla.hip, fa_fwd_kvcache_mla_sparse.hip, fa_fwd_kvcache_mla_fp8.hip, fa_fwd_mla_prefill.hip and fa_bwd_mla_prefill.hip (both of its loops) restate one schedule: four waves
+//   fa_fwd_kvcache_prefill.hip, fa_kvcache_mla_attn.hpp (the one MLA decode body of fa_fwd_kvcache_mla.hip, fa_fwd_kvcache_mla_sparse.hip and fa_fwd_kvcache_mla_fp8.hip), fa_fwd_mla_prefill.hip and
+//   fa_bwd_mla_prefill.hip (both of its loops) restate one schedule: four waves
 //   each write a quarter of a 32-key step into one of two LDS stages that all four read, with ONE barrier per step.  Four waves of a unit run close to
 //   lockstep, so a barrier one statement too early would hand a wave the stage's previous tenant almost never, and every value test would pass.
 //   tests/test_stage_protocol_gpu.py builds the same kernels with one wave held back and asks for the product's bits.
@@ -14,7 +15,7 @@
 //     about 68 MFMAs per wave in the MLA bodies; neither the sleep nor the step has been measured.
 //   FA_KVC_STAGE_RACY = 1 (the product is 0): the WRONG form the method exists for - the step's barrier stands in front of store_step instead of behind
 //     it, so the next step reads a stage nothing has published.  Kept to show that the slow-writer build catches it (it must NOT reproduce the product);
-//     nothing is claimed about it at normal timing.  Each file that carries it argues next to its loop why it can neither hang nor fault.
+//     nothing is claimed about it at normal timing.  Each body that carries it argues next to its loop why it can neither hang nor fault.
 #pragma once
 #include "fa_device.hpp"
 

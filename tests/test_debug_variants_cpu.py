@@ -12,7 +12,7 @@ file's EXTRA_FLAGS included; hipcc cross-compiles without a GPU) and compared wi
                                          (FA_DQ_STAGGER_DMA=0 FA_KV_STAGGER_DMA=0 / FA_DQ16_STAGGER_DMA=0 / FA_KV16_DMA_EARLY=2), and fewer than the product;
       fa_fwd_pp16.hip                    its late form (round 5) is another loop: it requests tile u + 1 where the counted wait of the product retires it
                                          and tile u + 2 is requested - at least the product's number, nothing dropped;
-  * every macro a variant sets occurs in every source it rebuilds;
+  * every macro a variant sets occurs in every source it rebuilds (the source and the project headers it includes, but for the header of the defaults);
   * no build of a decode kernel acquires scratch or another LDS size (the launch shape is the product's)."""
 import concurrent.futures
 import os
@@ -78,10 +78,22 @@ def test_variant_builds_and_is_not_the_product(asm, name, src):
     assert "v_mfma" in got and got != product, f"{name} / {src}: the switches {fa_build.DEBUG_VARIANTS[name][src]} change nothing - the GPU comparison would be vacuous"
 
 
+def _source_text(src, seen=None):
+    """the text of a source of csrc/ with the project headers it includes by `#include "..."`, transitively; not fa_kvcache_stage_debug.hpp, which only
+    defines the defaults of the stage macros and would make every source that includes it know them"""
+    seen = set() if seen is None else seen
+    path = os.path.join(fa_build.CSRC, src)
+    if src in seen or src == "fa_kvcache_stage_debug.hpp" or not os.path.exists(path):
+        return ""
+    seen.add(src)
+    with open(path) as f:
+        text = f.read()
+    return text + "".join(_source_text(h, seen) for h in re.findall(r'^\s*#include "([^"]+)"', text, re.M))
+
+
 @pytest.mark.parametrize("name,src", PAIRS, ids=[f"{n}-{s[:-4]}" for n, s in PAIRS])
 def test_every_macro_of_a_variant_occurs_in_the_source_it_rebuilds(name, src):
-    with open(os.path.join(fa_build.CSRC, src)) as f:
-        text = f.read()
+    text = _source_text(src)
     for flag in fa_build.DEBUG_VARIANTS[name][src]:
         m = re.fullmatch(r"-D(\w+)=\w+", flag)
         assert m, flag

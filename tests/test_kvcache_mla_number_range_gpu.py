@@ -17,8 +17,8 @@ contiguous and pages of 16, 16-bit and FP8 cache; every section at fp16 and bf16
      key row holds the patterns, rope columns included: LSE = kv[j]; the 640 (token, head) pairs of a sequence read its 576 columns.  (ii) the key is one-hot
      at column j, 65536 query rows (512 sequences x 128 heads dense, 8 x 64 tokens x 128 heads sparse) hold patterns everywhere: LSE = q[row, j].  bf16
      patterns end below 2^30 (SCORE_LIMIT_EXP of the number-formats suite: the contract |score| x log2 e < 2^31).  Bound: that suite's |lse - x| <= 2^-20
-     max(|x|, 1), x in float64.  Its derivation carries over: all three MLA bodies (fa_fwd_kvcache_mla.hip, _sparse.hip, _fp8.hip compute_step / epilogue)
-     take p = fast_exp2(fma(s, c, -(m c))) and lse = m sc + logf(lsum) exactly as kvcache_attn does - read again for this file - so l = exp2(residue of
+     max(|x|, 1), x in float64.  Its derivation carries over: the one MLA body (fa_kvcache_mla_attn.hpp compute_step / epilogue, which the three MLA sources instantiate)
+     takes p = fast_exp2(fma(s, c, -(m c))) and lse = m sc + logf(lsum) exactly as kvcache_attn does - read again for this file - so l = exp2(residue of
      m c), |residue| <= |x log2 e| 2^-24, and the few fp32 roundings of m sc + logf(l) stay relative 2^-23 each.  FP8 version of (i): every NaN-free code in
      all four tiles under four scales, LSE = fp32(code) x scale rounded once to the dtype, the expectation from numpy (see C).  FP8 version of (ii): the
      bit-for-bit relation to the 16-bit call on the dequantised cache.

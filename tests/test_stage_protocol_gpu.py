@@ -1,5 +1,5 @@
-"""GPU: the register-staged LDS stages of the 64-row KV-cache bodies (fa_fwd_kvcache_prefill.hip, fa_fwd_kvcache_mla.hip, fa_fwd_kvcache_mla_sparse.hip,
-fa_fwd_kvcache_mla_fp8.hip) under ADVERSARIAL timing - the method of tests/test_dma_protocol_gpu.py for the kernels whose waves share LDS through
+"""GPU: the register-staged LDS stages of the 64-row KV-cache bodies (fa_fwd_kvcache_prefill.hip, and the one MLA decode body of fa_kvcache_mla_attn.hpp
+as fa_fwd_kvcache_mla.hip, fa_fwd_kvcache_mla_sparse.hip and fa_fwd_kvcache_mla_fp8.hip instantiate it) under ADVERSARIAL timing - the method of tests/test_dma_protocol_gpu.py for the kernels whose waves share LDS through
 registers instead of LDS-DMA.
 
 Four waves each write a quarter of a 32-key step into one of two stages that all four read, with one barrier per step.  Waves of one unit run close to
@@ -210,7 +210,7 @@ def test_ragged_prefill_reproduces_its_bits(gpu, libs, causal):
         _must_match(libs, lambda L: run(L, ns), f"ragged prefill causal={causal} splits {ns}")
 
 
-# ---- flash_mla_with_kvcache (fa_fwd_kvcache_mla.hip, the dense body of fa_fwd_kvcache_mla_fp8.hip) ---------------------------------------------------
+# ---- flash_mla_with_kvcache (the dense kernels of fa_fwd_kvcache_mla.hip and fa_fwd_kvcache_mla_fp8.hip) ---------------------------------------------------
 
 def _mla_cache(gpu, dt, fp8, paged, b, cap, gen, seed):
     """the latent cache (16-bit rows of 576 or FP8 rows of 656 bytes), contiguous or a pool of 16-row pages + table"""
@@ -266,7 +266,7 @@ def test_mla_reproduces_its_bits_with_a_slow_reader_and_a_slow_writer(gpu, libs,
         _must_match(libs, lambda L: run(L, causal, 1), f"mla fp8={fp8} paged={paged} h64 sq2 causal={causal}, no append")
 
 
-# ---- flash_mla_sparse_with_kvcache (fa_fwd_kvcache_mla_sparse.hip, the sparse body of fa_fwd_kvcache_mla_fp8.hip) --------------------------------------
+# ---- flash_mla_sparse_with_kvcache (the sparse kernels of fa_fwd_kvcache_mla_sparse.hip and fa_fwd_kvcache_mla_fp8.hip) --------------------------------------
 
 def _sparse_case(gpu, dtname, fp8, paged, sq, h, topk, seed, lens=SPARSE_LENS, dead_steps=True):
     from flash_attn_turing import capi
