@@ -56,6 +56,72 @@ int check_cache8(const char* name, const void* ptr, const fa_strides& st, int64_
     return FA_OK;
 }
 
+// ---- rules that several entry points share: each is stated once, and an entry point calls it at ITS place in ITS order of checks.  The code, the words and
+// the place of a refusal are part of the interface (callers and tests match on them); where the entry points differ, the difference is an argument.
+
+int check_dtype(int dtype) {
+    if (dtype != FA_FP16 && dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", dtype);
+    return FA_OK;
+}
+
+int check_num_splits(int num_splits) {
+    if (num_splits < 0) return fail(FA_ERR_BAD_SHAPE, "num_splits must be >= 0 (0 = the library's choice), got %d", num_splits);
+    return FA_OK;
+}
+
+// The workspace pair.  empty_unaligned: fa_bwd_params does not look at the pointer of an empty workspace; the decode structs refuse a misaligned one of any size.
+int check_workspace(const void* workspace, int64_t workspace_bytes, bool empty_unaligned = false) {
+    if (workspace_bytes < 0) return fail(FA_ERR_BAD_SHAPE, "workspace_bytes must be >= 0");
+    if (workspace != nullptr && !(empty_unaligned && workspace_bytes == 0) && (reinterpret_cast<uintptr_t>(workspace) & 15u) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
+    return FA_OK;
+}
+
+// dflt: what 0 stands for, in the struct's own words ("576 ** -0.5")
+int check_softmax_scale(float softmax_scale, const char* dflt) {
+    if (!(softmax_scale >= 0.f) || isinf(softmax_scale))
+        return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default %s)", (double)softmax_scale, dflt);
+    return FA_OK;
+}
+
+// A reserved field.  code: FA_ERR_BAD_ABI in fa_mla_params and fa_mla_sparse_params, FA_ERR_BAD_SHAPE in the structs that came after them - as each shipped.
+int check_reserved(int64_t reserved, const char* what, int code) {
+    if (reserved != 0) return fail(code, "%s: reserved_ is not zero (a field of a newer header that this library does not know)", what);
+    return FA_OK;
+}
+
+// Both cu_seqlens or neither.  prefill_words: the MLA prefill structs name the missing one and check the alignment; fa_fwd_params / fa_bwd_params do neither.
+int check_cu_seqlens(const int32_t* cu_q, const int32_t* cu_k, bool prefill_words) {
+    if (cu_q == nullptr && cu_k == nullptr) return FA_OK;
+    if (!prefill_words) {
+        if (cu_q == nullptr || cu_k == nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_q and cu_seqlens_k must both be given for varlen");
+        return FA_OK;
+    }
+    if (cu_q == nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_q is NULL but cu_seqlens_k is given (both or neither)");
+    if (cu_k == nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_k is NULL but cu_seqlens_q is given (both or neither)");
+    if (((reinterpret_cast<uintptr_t>(cu_q) | reinterpret_cast<uintptr_t>(cu_k)) & 3u) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "cu_seqlens_q / cu_seqlens_k must be 4-byte aligned");
+    return FA_OK;
+}
+
+// The paged-cache fields of fa_kvcache_params, fa_mla_params, fa_mla_sparse_params and fa_mla_indexer_params (block_table = NULL: a contiguous cache)
+int check_paged(const int32_t* block_table, int64_t block_table_stride, int page_block_size, int num_blocks, int seqlen_cache) {
+    const int P = page_block_size;
+    if (block_table == nullptr) {
+        if (P != 0) return fail(FA_ERR_NULL_POINTER, "page_block_size = %d given without block_table", P);
+        return FA_OK;
+    }
+    if (P == 0) return fail(FA_ERR_BAD_SHAPE, "block_table given without page_block_size");
+    if (P < 0 || P % 16 != 0) return fail(FA_ERR_BAD_SHAPE, "page_block_size %d must be a positive multiple of 16", P);
+    if (num_blocks < 1) return fail(FA_ERR_BAD_SHAPE, "num_blocks %d: a paged cache needs at least one page", num_blocks);
+    if (seqlen_cache <= 0 || seqlen_cache % P != 0)
+        return fail(FA_ERR_BAD_SHAPE, "seqlen_cache (%d) must be a positive multiple of page_block_size (%d) with block_table", seqlen_cache, P);
+    if (block_table_stride < seqlen_cache / P)
+        return fail(FA_ERR_BAD_STRIDE, "block_table_stride %lld is below the table's %d columns (seqlen_cache / page_block_size)", (long long)block_table_stride, seqlen_cache / P);
+    if ((reinterpret_cast<uintptr_t>(block_table) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "block_table must be 4-byte aligned");
+    return FA_OK;
+}
+
 // kvcache: the decode call, which has head_dim 256 as well (fa_fwd_kvcache_d256.hip); fwd / bwd / varlen have 64 and 128
 int check_common(int b, int sq, int sk, int h, int hk, int d, int dtype, bool kvcache = false) {
     if (b < 0 || sq < 0 || sk < 0 || h <= 0 || hk <= 0)
@@ -64,18 +130,25 @@ int check_common(int b, int sq, int sk, int h, int hk, int d, int dtype, bool kv
     if (kvcache) {
         if (d != 64 && d != 128 && d != 256) return fail(FA_ERR_BAD_HEADDIM, "head_dim %d unsupported (64, 128 or 256 over a KV cache)", d);
     } else if (d != 64 && d != 128) return fail(FA_ERR_BAD_HEADDIM, "head_dim %d unsupported (64 or 128)", d);
-    if (dtype != FA_FP16 && dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", dtype);
-    return FA_OK;
+    return check_dtype(dtype);
+}
+
+// The head of every import_* form below: the pointer and the magic.  init_words: the one-size structs (import_exact) word a wrong magic in their own way.
+template <typename P>
+int check_header(const P* user, const char* what, bool init_words = false) {
+    if (user == nullptr) return fail(FA_ERR_NULL_POINTER, "params is NULL");
+    if (user->magic == FA_PARAMS_MAGIC) return FA_OK;
+    if (init_words)
+        return fail(FA_ERR_BAD_ABI, "%s: magic is not FA_PARAMS_MAGIC - no {struct_size, magic} header; initialise the struct with FA_PARAMS_INIT (ABI %d)", what, FA_ABI_VERSION);
+    return fail(FA_ERR_BAD_ABI, "%s: no {struct_size, magic} header - caller was compiled against an ABI < 4 header; recompile against include/flash_attn_gfx950.h (ABI %d)",
+                what, FA_ABI_VERSION);
 }
 
 // ABI 4: the caller's struct -> a zeroed local one, min(caller's size, ours) bytes.  Fields appended after the caller's header was
 // written stay 0 / NULL ("not given"); a struct without the {size, magic} header (ABI 1-3 callers) or longer than ours is an error.
 template <typename P>
 int import_params(const P* user, P& local, const char* what, size_t base = offsetof(P, total_q)) {   // base: everything up to the first appended (optional) field is mandatory
-    if (user == nullptr) return fail(FA_ERR_NULL_POINTER, "params is NULL");
-    if (user->magic != FA_PARAMS_MAGIC)
-        return fail(FA_ERR_BAD_ABI, "%s: no {struct_size, magic} header - caller was compiled against an ABI < 4 header; recompile against include/flash_attn_gfx950.h (ABI %d)",
-                    what, FA_ABI_VERSION);
+    if (int rc = check_header(user, what)) return rc;
     if (user->struct_size < base || user->struct_size > sizeof(P))
         return fail(FA_ERR_BAD_ABI, "%s: struct_size %u outside [%zu, %zu] - header / library mismatch", what, user->struct_size, base, sizeof(P));
     memset(&local, 0, sizeof(P));
@@ -88,10 +161,7 @@ int import_params(const P* user, P& local, const char* what, size_t base = offse
 template <typename P1, typename P2>
 int import_mla(const P1* user, P2& local, const char* what) {
     static_assert(sizeof(P2) == sizeof(P1) + 8 && offsetof(P2, kv_format) == sizeof(P1), "the _v2 struct is the first one with two int32 appended");
-    if (user == nullptr) return fail(FA_ERR_NULL_POINTER, "params is NULL");
-    if (user->magic != FA_PARAMS_MAGIC)
-        return fail(FA_ERR_BAD_ABI, "%s: no {struct_size, magic} header - caller was compiled against an ABI < 4 header; recompile against include/flash_attn_gfx950.h (ABI %d)",
-                    what, FA_ABI_VERSION);
+    if (int rc = check_header(user, what)) return rc;
     if (user->struct_size != sizeof(P1) && user->struct_size != sizeof(P2))
         return fail(FA_ERR_BAD_ABI, "%s: struct_size %u is neither %zu nor %zu (%s_v2) - header / library mismatch", what, user->struct_size, sizeof(P1), sizeof(P2), what);
     memset(&local, 0, sizeof(P2));
@@ -102,9 +172,7 @@ int import_mla(const P1* user, P2& local, const char* what) {
 // The indexer structs (fa_mla_indexer_params, fa_mla_topk_params) have one size each: struct_size must be it.
 template <typename P>
 int import_exact(const P* user, P& local, const char* what) {
-    if (user == nullptr) return fail(FA_ERR_NULL_POINTER, "params is NULL");
-    if (user->magic != FA_PARAMS_MAGIC)
-        return fail(FA_ERR_BAD_ABI, "%s: magic is not FA_PARAMS_MAGIC - no {struct_size, magic} header; initialise the struct with FA_PARAMS_INIT (ABI %d)", what, FA_ABI_VERSION);
+    if (int rc = check_header(user, what, true)) return rc;
     if (user->struct_size != sizeof(P))
         return fail(FA_ERR_BAD_ABI, "%s: struct_size %u is not %zu - header / library mismatch", what, user->struct_size, sizeof(P));
     memcpy(&local, user, sizeof(P));
@@ -127,6 +195,117 @@ int check_mla_cache8(const void* ptr, const fa_strides& st, int64_t rows) {
                     (long long)st.row);
     if (rows * st.row >= ((int64_t)1 << 31)) return fail(FA_ERR_BAD_STRIDE, "kv_cache: one sequence spans %lld bytes (limit 2^31)", (long long)(rows * st.row));
     return FA_OK;
+}
+
+template <typename K>
+void set_scale(K& kp, float scale) {
+    kp.scale = scale;
+    kp.scale_log2e = scale * 1.4426950408889634f;
+}
+
+// p.block_table (NULL = contiguous: the four fields stay 0) -> kp
+template <typename P>
+void fill_paged(const P& p, fa::KvcacheKernelParams& kp) {
+    if (p.block_table == nullptr) return;
+    kp.block_table = p.block_table; kp.bt_stride = p.block_table_stride;
+    kp.page_size = p.page_block_size; kp.num_blocks = p.num_blocks;
+}
+
+// ---- what fa_mla_params and fa_mla_sparse_params share (P: the _v2 form of either): fill_mla / fill_mla_sparse call these between their own checks
+int check_mla_dims(int d_qk, int d_v, int dtype) {
+    if (d_qk != 576) return fail(FA_ERR_BAD_HEADDIM, "d_qk %d unsupported (the latent row is 576 wide: 512 compressed + 64 rope elements)", d_qk);
+    if (d_v != 512) return fail(FA_ERR_BAD_HEADDIM, "d_v %d unsupported (the value is the first 512 elements of the latent row)", d_v);
+    return check_dtype(dtype);
+}
+
+// num_splits, softmax_scale, reserved_, kv_format / reserved2_, then the workspace pair (with_workspace = false: not looked at).  what: the struct, for reserved_
+template <typename P>
+int check_mla_tail(const P& p, const char* what, bool with_workspace) {
+    int rc;
+    if ((rc = check_num_splits(p.num_splits))) return rc;
+    if ((rc = check_softmax_scale(p.softmax_scale, "576 ** -0.5"))) return rc;
+    if ((rc = check_reserved(p.reserved_, what, FA_ERR_BAD_ABI))) return rc;
+    if ((rc = check_mla_format(p.kv_format, p.reserved2_))) return rc;
+    return with_workspace ? check_workspace(p.workspace, p.workspace_bytes) : FA_OK;
+}
+
+// kv_cache under kv_format.  kvc: kv_cache_stride with head = 0 (one KV head).  Paged: the descriptors span at most one page, so the 2^31-byte limit applies per
+// page (page offsets are 64-bit); contiguous: one descriptor per sequence
+template <typename P>
+int check_mla_cache(const P& p, const fa_strides& kvc) {
+    const int64_t rows = p.block_table != nullptr ? p.page_block_size : p.seqlen_cache;
+    if (p.kv_format == FA_MLA_KV_FP8_ROWS656) return check_mla_cache8(p.kv_cache, kvc, rows);
+    return check_tensor("kv_cache", p.kv_cache, kvc, rows, p.d_qk, false);
+}
+
+// The fields of a zeroed kp that both structs state alike: q, the cache (key and value are the same rows), o, lse, lengths, sizes, one KV head, scale, paging.
+// kp.d = 512 is the width of V, of o and of the partial planes.
+template <typename P>
+void fill_mla_kp(const P& p, const fa_strides& kvc, fa::KvcacheKernelParams& kp) {
+    kp.q_ptr = p.q; kp.k_cache = kp.v_cache = const_cast<void*>(static_cast<const void*>(p.kv_cache));
+    kp.o_ptr = p.o; kp.lse_ptr = p.lse; kp.cache_seqlens = p.cache_seqlens;
+    kp.q = conv(p.q_stride); kp.kc = kp.vc = conv(kvc); kp.o = conv(p.o_stride);
+    kp.b = p.b; kp.seqlen_q = p.seqlen_q; kp.seqlen_cache = p.seqlen_cache;
+    kp.h = p.h; kp.h_k = 1; kp.h_ratio = p.h; kp.d = p.d_v;
+    kp.cache_fp8 = p.kv_format == FA_MLA_KV_FP8_ROWS656 ? 1 : 0;     // kc / vc are in bytes then
+    set_scale(kp, p.softmax_scale > 0.f ? p.softmax_scale : 1.0f / sqrtf((float)p.d_qk));
+    fill_paged(p, kp);
+}
+
+// The split of an MLA decode call (kp: the dense call's own, the sparse call's `split` copy).  sized = false: without a limit, what the workspace query sizes for
+template <typename P>
+int32_t mla_split(const fa::KvcacheKernelParams& kp, const P& local, bool sized) {
+    const int64_t avail = !sized ? -1 : local.workspace != nullptr ? local.workspace_bytes : 0;
+    return fa::kvcache_split(kp, avail, local.num_splits, -1, fa::kKvcPrefillRows);
+}
+
+// ---- what the MLA prefill forward and backward share
+// What fa_mla_prefill_params and fa_mla_prefill_bwd_params (P) check alike and first: sizes, GQA, widths, dtype, cu_seqlens, softmax_scale, the packed totals.
+// Behind it a call is packed iff cu_seqlens_q is given.
+template <typename P>
+int check_mla_prefill_front(const P& p) {
+    if (p.b < 0 || p.seqlen_q < 0 || p.seqlen_k < 0 || p.h <= 0 || p.h_k <= 0)
+        return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d seqlen_k=%d h=%d h_k=%d", p.b, p.seqlen_q, p.seqlen_k, p.h, p.h_k);
+    if (p.h % p.h_k != 0) return fail(FA_ERR_BAD_GQA, "h (%d) must be divisible by h_k (%d) for GQA/MQA", p.h, p.h_k);
+    if (p.d_qk != 192) return fail(FA_ERR_BAD_HEADDIM, "d_qk %d unsupported (q and k are 192 wide: 128 no-rope + 64 rope elements)", p.d_qk);
+    if (p.d_v != 128) return fail(FA_ERR_BAD_HEADDIM, "d_v %d unsupported (v and o are 128 wide)", p.d_v);
+    int rc;
+    if ((rc = check_dtype(p.dtype))) return rc;
+    if ((rc = check_cu_seqlens(p.cu_seqlens_q, p.cu_seqlens_k, true))) return rc;
+    if ((rc = check_softmax_scale(p.softmax_scale, "192 ** -0.5"))) return rc;
+    if (p.cu_seqlens_q != nullptr && (p.total_q < 0 || p.total_k < 0))
+        return fail(FA_ERR_BAD_SHAPE, "total_q (%lld) / total_k (%lld) must be >= 0 with cu_seqlens", (long long)p.total_q, (long long)p.total_k);
+    return FA_OK;
+}
+
+// The launch grids: h_k x tiles (dense: per batch entry; packed: of all rows, plus one slot per sequence), counted in tiles of 64 - the smaller of the two row
+// tiles fa_fwd_mla_prefill.hip can be built with - and a packed row index is an int.  key_grid: the backward's dK / dV launch runs over key tiles as well.
+template <typename P>
+int check_mla_prefill_grid(const P& p, bool key_grid) {
+    const bool packed = p.cu_seqlens_q != nullptr;
+    const int64_t rows_q = packed ? p.total_q : p.seqlen_q, rows_k = packed ? p.total_k : p.seqlen_k, h_ratio = p.h / p.h_k;
+    auto grid = [&](int64_t rows) {
+        const int64_t tiles = (rows + fa::kKvcPrefillRows - 1) / fa::kKvcPrefillRows;
+        return (packed ? tiles + p.b : tiles * p.b) * p.h_k;
+    };
+    if (rows_q * h_ratio >= ((int64_t)1 << 31) || rows_k >= ((int64_t)1 << 31) || grid(rows_q * h_ratio) >= ((int64_t)1 << 31) || (key_grid && grid(rows_k) >= ((int64_t)1 << 31)))
+        return fail(FA_ERR_BAD_SHAPE, "call too large: b = %d sequences, %lld query rows x h = %d heads, %lld keys exceed the launch grid", p.b, (long long)rows_q, p.h,
+                    (long long)rows_k);
+    return FA_OK;
+}
+
+// The fields that MlaPrefillParams and MlaPrefillBwdParams (K, zeroed) name alike: q / k / v / o / lse, cu_seqlens, sizes, the scale
+template <typename P, typename K>
+void fill_mla_prefill_kp(const P& p, K& kp) {
+    const bool packed = p.cu_seqlens_q != nullptr;
+    kp.q_ptr = p.q; kp.k_ptr = p.k; kp.v_ptr = p.v; kp.o_ptr = p.o; kp.lse_ptr = p.lse;
+    kp.cu_q = p.cu_seqlens_q; kp.cu_k = p.cu_seqlens_k;
+    kp.q = conv(p.q_stride); kp.k = conv(p.k_stride); kp.v = conv(p.v_stride); kp.o = conv(p.o_stride);
+    kp.b = p.b; kp.seqlen_q = p.seqlen_q; kp.seqlen_k = p.seqlen_k;
+    kp.h = p.h; kp.h_k = p.h_k; kp.h_ratio = p.h / p.h_k;
+    kp.is_causal = p.is_causal ? 1 : 0;
+    kp.total_q = packed ? p.total_q : 0; kp.total_k = packed ? p.total_k : 0;
+    set_scale(kp, p.softmax_scale > 0.f ? p.softmax_scale : 1.0f / sqrtf((float)p.d_qk));        // (the default = 192 ** -0.5 rounded once to fp32)
 }
 
 int hip_status(hipError_t e, const char* what) {
@@ -206,8 +385,7 @@ int fa_run_mha_fwd(const fa_fwd_params* user, void* stream) {
     rc = check_common(p->b, p->seqlen_q, p->seqlen_k, p->h, p->h_k, p->d, p->dtype);
     if (rc) return rc;
     const bool varlen = p->cu_seqlens_q != nullptr || p->cu_seqlens_k != nullptr;
-    if (varlen && (p->cu_seqlens_q == nullptr || p->cu_seqlens_k == nullptr))
-        return fail(FA_ERR_NULL_POINTER, "cu_seqlens_q and cu_seqlens_k must both be given for varlen");
+    if ((rc = check_cu_seqlens(p->cu_seqlens_q, p->cu_seqlens_k, false))) return rc;
     if (p->b == 0 || p->seqlen_q == 0) return FA_OK;   // nothing to write
     if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
     if ((rc = check_tensor("q", p->q, p->q_stride, p->seqlen_q, p->d, varlen))) return rc;
@@ -227,8 +405,7 @@ int fa_run_mha_fwd(const fa_fwd_params* user, void* stream) {
     kp.is_causal = p->is_causal ? 1 : 0;
     if (p->total_q < 0 || p->total_k < 0) return fail(FA_ERR_BAD_SHAPE, "total_q / total_k must be >= 0 (0 = unknown)");
     kp.total_q = varlen ? p->total_q : 0;          // sizes the varlen launch grid by the tokens present (fa_device.hpp)
-    kp.scale = 1.0f / sqrtf((float)p->d);          // hard-wired like the reference (flash_fwd_kernel.h:351)
-    kp.scale_log2e = kp.scale * 1.4426950408889634f;
+    set_scale(kp, 1.0f / sqrtf((float)p->d));      // hard-wired like the reference (flash_fwd_kernel.h:351)
     return hip_status(fa::launch_fwd(kp, p->dtype, (hipStream_t)stream), "fa_fwd launch");
 }
 
@@ -240,8 +417,7 @@ static int fill_bwd(const fa_bwd_params* user, fa::BwdKernelParams& kp, fa_bwd_p
     rc = check_common(p->b, p->seqlen_q, p->seqlen_k, p->h, p->h_k, p->d, p->dtype);
     if (rc) return rc;
     const bool varlen = p->cu_seqlens_q != nullptr || p->cu_seqlens_k != nullptr;
-    if (varlen && (p->cu_seqlens_q == nullptr || p->cu_seqlens_k == nullptr))
-        return fail(FA_ERR_NULL_POINTER, "cu_seqlens_q and cu_seqlens_k must both be given for varlen");
+    if ((rc = check_cu_seqlens(p->cu_seqlens_q, p->cu_seqlens_k, false))) return rc;
     if (p->b > 0 && p->seqlen_q > 0) {
         if (p->lse == nullptr || p->dsoftmax_sum == nullptr) return fail(FA_ERR_NULL_POINTER, "lse / dsoftmax_sum is NULL");
         if ((rc = check_tensor("q", p->q, p->q_stride, p->seqlen_q, p->d, varlen))) return rc;
@@ -268,13 +444,9 @@ static int fill_bwd(const fa_bwd_params* user, fa::BwdKernelParams& kp, fa_bwd_p
     kp.is_causal = p->is_causal ? 1 : 0;
     if (p->total_q < 0 || p->total_k < 0) return fail(FA_ERR_BAD_SHAPE, "total_q / total_k must be >= 0 (0 = unknown)");
     if (p->cu_seqlens_q != nullptr) { kp.total_q = p->total_q; kp.total_k = p->total_k; }
-    kp.scale = 1.0f / sqrtf((float)p->d);
-    kp.scale_log2e = kp.scale * 1.4426950408889634f;
-    if (with_workspace && p->workspace_bytes < 0) return fail(FA_ERR_BAD_SHAPE, "workspace_bytes must be >= 0");
-    if (with_workspace && p->workspace != nullptr && p->workspace_bytes > 0) {
-        if ((reinterpret_cast<uintptr_t>(p->workspace) & 15u) != 0) return fail(FA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
-        kp.ws = (float*)p->workspace; kp.ws_bytes = p->workspace_bytes;
-    }
+    set_scale(kp, 1.0f / sqrtf((float)p->d));
+    if (with_workspace && (rc = check_workspace(p->workspace, p->workspace_bytes, true))) return rc;
+    if (with_workspace && p->workspace != nullptr && p->workspace_bytes > 0) { kp.ws = (float*)p->workspace; kp.ws_bytes = p->workspace_bytes; }
     kp.n_split = 1;
     return FA_OK;
 }
@@ -432,30 +604,15 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d seqlen_new=%d h=%d h_k=%d", p->b, p->seqlen_q, p->seqlen_cache,
                     p->seqlen_new, p->h, p->h_k);
     if ((rc = check_common(p->b, p->seqlen_q, p->seqlen_cache, p->h, p->h_k, p->d, p->dtype, true))) return rc;
-    if (paged) {
-        const int P = p->page_block_size;
-        if (P == 0) return fail(FA_ERR_BAD_SHAPE, "block_table given without page_block_size");
-        if (P < 0 || P % 16 != 0) return fail(FA_ERR_BAD_SHAPE, "page_block_size %d must be a positive multiple of 16", P);
-        if (p->num_blocks < 1) return fail(FA_ERR_BAD_SHAPE, "num_blocks %d: a paged cache needs at least one page", p->num_blocks);
-        if (p->seqlen_cache <= 0 || p->seqlen_cache % P != 0)
-            return fail(FA_ERR_BAD_SHAPE, "seqlen_cache (%d) must be a positive multiple of page_block_size (%d) with block_table", p->seqlen_cache, P);
-        if (p->block_table_stride < p->seqlen_cache / P)
-            return fail(FA_ERR_BAD_STRIDE, "block_table_stride %lld is below the table's %d columns (seqlen_cache / page_block_size)",
-                        (long long)p->block_table_stride, p->seqlen_cache / P);
-        if ((reinterpret_cast<uintptr_t>(p->block_table) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "block_table must be 4-byte aligned");
-    } else if (p->page_block_size != 0) {
-        return fail(FA_ERR_NULL_POINTER, "page_block_size = %d given without block_table", p->page_block_size);
-    }
+    if ((rc = check_paged(p->block_table, p->block_table_stride, p->page_block_size, p->num_blocks, p->seqlen_cache))) return rc;
     if (p->seqlen_new > p->seqlen_cache)
         return fail(FA_ERR_BAD_SHAPE, "seqlen_new (%d) exceeds the cache capacity seqlen_cache (%d)", p->seqlen_new, p->seqlen_cache);
     if ((p->k_new == nullptr) != (p->v_new == nullptr)) return fail(FA_ERR_NULL_POINTER, "k_new and v_new must both be given or both be NULL");
     if (p->k_new != nullptr && p->cache_seqlens == nullptr)
         return fail(FA_ERR_NULL_POINTER, "k_new / v_new need cache_seqlens (the rows they are appended at)");
     if (p->k_new == nullptr && p->seqlen_new != 0) return fail(FA_ERR_BAD_SHAPE, "seqlen_new = %d without k_new / v_new", p->seqlen_new);
-    if (p->num_splits < 0) return fail(FA_ERR_BAD_SHAPE, "num_splits must be >= 0 (0 = the library's choice), got %d", p->num_splits);
-    if (with_workspace && p->workspace_bytes < 0) return fail(FA_ERR_BAD_SHAPE, "workspace_bytes must be >= 0");
-    if (with_workspace && p->workspace != nullptr && (reinterpret_cast<uintptr_t>(p->workspace) & 15u) != 0)
-        return fail(FA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
+    if ((rc = check_num_splits(p->num_splits))) return rc;
+    if (with_workspace && (rc = check_workspace(p->workspace, p->workspace_bytes))) return rc;
     if (p->b > 0) {
         if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
         if ((rc = check_tensor("q", p->q, p->q_stride, p->seqlen_q, p->d, ragged))) return rc;
@@ -483,12 +640,8 @@ static int fill_kvcache(const fa_kvcache_params* user, fa::KvcacheKernelParams& 
     kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_cache = p->seqlen_cache; kp.seqlen_new = p->k_new != nullptr ? p->seqlen_new : 0;
     kp.h = p->h; kp.h_k = p->h_k; kp.h_ratio = p->h / p->h_k; kp.d = p->d;
     kp.is_causal = p->is_causal ? 1 : 0;
-    kp.scale = 1.0f / sqrtf((float)p->d);
-    kp.scale_log2e = kp.scale * 1.4426950408889634f;
-    if (paged) {
-        kp.block_table = p->block_table; kp.bt_stride = p->block_table_stride;
-        kp.page_size = p->page_block_size; kp.num_blocks = p->num_blocks;
-    }
+    set_scale(kp, 1.0f / sqrtf((float)p->d));
+    fill_paged(*p, kp);
     if (o.cache_dtype == FA_CACHE_FP8_E4M3) {
         kp.cache_fp8 = 1;
         kp.k_descale = o.k_descale; kp.kds_batch = o.k_descale_batch_stride; kp.kds_head = o.k_descale_head_stride;
@@ -569,21 +722,16 @@ static int fill_kvcache_ragged(const fa_kvcache_options_v8& o, const fa::Kvcache
 // and read the cap where the scale was: scale = softcap, scale_log2e = softcap * log2(e), cap_pre = 2 log2(e) * softmax_scale / softcap.
 static int fill_kvcache_softcap(const fa_kvcache_options_v8& o, fa::KvcacheKernelParams& kp, float& cap_pre) {
     cap_pre = 0.f;
-    if (!(o.softmax_scale >= 0.f) || isinf(o.softmax_scale))
-        return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default 1 / sqrt(head_dim))", (double)o.softmax_scale);
+    if (int rc = check_softmax_scale(o.softmax_scale, "1 / sqrt(head_dim)")) return rc;
     if (!(o.softcap >= 0.f) || isinf(o.softcap)) return fail(FA_ERR_BAD_SHAPE, "softcap %g must be finite and >= 0 (0 = no cap)", (double)o.softcap);
     if (o.reserved[0] != 0 || o.reserved[1] != 0)
         return fail(FA_ERR_BAD_ABI, "fa_kvcache_options_v5: reserved fields are not zero (a field of a newer header that this library does not know)");
-    if (o.softmax_scale > 0.f) {
-        kp.scale = o.softmax_scale;
-        kp.scale_log2e = kp.scale * 1.4426950408889634f;
-    }
+    if (o.softmax_scale > 0.f) set_scale(kp, o.softmax_scale);
     if (o.softcap > 0.f) {
         cap_pre = (kp.scale / o.softcap) * 2.8853900817779268f;
         if (!(cap_pre > 0.f) || isinf(cap_pre))
             return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g over softcap %g is outside the fp32 range", (double)kp.scale, (double)o.softcap);
-        kp.scale = o.softcap;
-        kp.scale_log2e = kp.scale * 1.4426950408889634f;
+        set_scale(kp, o.softcap);
     }
     return FA_OK;
 }
@@ -657,130 +805,108 @@ static int fill_kvcache_prefill(const fa_kvcache_options_v8& o, const fa::Kvcach
     return FA_OK;
 }
 
+struct KvcacheCall {        // what the four _ex entry points derive from their two structs
+    fa::KvcacheKernelParams kp;
+    fa_kvcache_params local;
+    fa_kvcache_options_v8 o;
+    fa::KvcacheRotaryParams rp;
+    fa::KvcacheRaggedParams rg;
+    float cap_pre;
+    fa::KvcacheSink sink;
+    fa::KvcacheTree tree;
+    int32_t row_tile;
+
+    int64_t total_q() const { return rg.cu_q != nullptr ? rg.total_q : -1; }      // (-1: not a ragged call)
+    // the split of the call over `avail` bytes for the partials (-1: without a limit, what the workspace query sizes for)
+    int32_t split(int64_t avail) const { return fa::kvcache_split(kp, avail, local.num_splits, total_q(), row_tile); }
+    // Workspace for the split partials: all of it, or in a rotary call what is left once the image of the rotated q has taken its part; a workspace
+    // that cannot hold the image is an error (the attention kernels read q from it: there is no path without it)
+    int64_t split_bytes() const {
+        const int64_t have = local.workspace != nullptr ? local.workspace_bytes : 0;
+        if (rp.cos == nullptr) return have;
+        const int64_t need = fa::kvcache_rotary_image_bytes(kp);
+        if (have < need)
+            return fail(FA_ERR_BAD_SHAPE, "rotary: the workspace (%lld bytes) cannot hold the image of the rotated q: %lld bytes needed (fa_kvcache_workspace_bytes_ex)", (long long)have,
+                        (long long)need);
+        return have - need;
+    }
+};
+
 // Params first, as before the options existed (their errors win), except that the cache tensors are checked under the cache dtype the
 // options state; then the options' own values.
-static int fill_kvcache_all(const fa_kvcache_params* user, const fa_kvcache_options* options, fa::KvcacheKernelParams& kp, fa_kvcache_params& local,
-                            fa_kvcache_options_v8& o, fa::KvcacheRotaryParams& rp, fa::KvcacheRaggedParams& rg, float& cap_pre, fa::KvcacheSink& sink, fa::KvcacheTree& tree,
-                            int32_t& row_tile, bool with_workspace) {
+static int fill_kvcache_all(const fa_kvcache_params* user, const fa_kvcache_options* options, KvcacheCall& c, bool with_workspace) {
     fa_kvcache_options_v8 none;
     memset(&none, 0, sizeof(none));
-    const int orc = import_kvcache_options(options, o);
+    const int orc = import_kvcache_options(options, c.o);
     char oerr[sizeof(g_err)];
     memcpy(oerr, g_err, sizeof(oerr));
-    int rc = fill_kvcache(user, kp, local, with_workspace, orc ? none : o);
+    int rc = fill_kvcache(user, c.kp, c.local, with_workspace, orc ? none : c.o);
     if (rc) return rc;
     if (orc) {
         memcpy(g_err, oerr, sizeof(g_err));
         return orc;
     }
-    if ((rc = fill_kvcache_window(o, kp))) return rc;
-    if ((rc = fill_kvcache_rotary(o, kp, rp))) return rc;
-    if ((rc = fill_kvcache_ragged(o, kp, rp, rg))) return rc;
-    if ((rc = fill_kvcache_softcap(o, kp, cap_pre))) return rc;
-    if ((rc = fill_kvcache_sinks(o, kp, cap_pre, sink))) return rc;
-    if ((rc = fill_kvcache_tree(o, kp, rp, cap_pre, sink, tree))) return rc;
-    return fill_kvcache_prefill(o, kp, rp, cap_pre, sink, tree, row_tile);
-}
-
-// Workspace left for the split partials of a rotary call once the image of the rotated q has taken its part; a workspace that cannot hold
-// the image is an error (the attention kernels read q from it: there is no path without it)
-static int64_t rotary_split_bytes(const fa::KvcacheKernelParams& kp, const fa_kvcache_params& local) {
-    const int64_t need = fa::kvcache_rotary_image_bytes(kp);
-    const int64_t have = local.workspace != nullptr ? local.workspace_bytes : 0;
-    if (have < need)
-        return fail(FA_ERR_BAD_SHAPE, "rotary: the workspace (%lld bytes) cannot hold the image of the rotated q: %lld bytes needed (fa_kvcache_workspace_bytes_ex)", (long long)have,
-                    (long long)need);
-    return have - need;
+    if ((rc = fill_kvcache_window(c.o, c.kp))) return rc;
+    if ((rc = fill_kvcache_rotary(c.o, c.kp, c.rp))) return rc;
+    if ((rc = fill_kvcache_ragged(c.o, c.kp, c.rp, c.rg))) return rc;
+    if ((rc = fill_kvcache_softcap(c.o, c.kp, c.cap_pre))) return rc;
+    if ((rc = fill_kvcache_sinks(c.o, c.kp, c.cap_pre, c.sink))) return rc;
+    if ((rc = fill_kvcache_tree(c.o, c.kp, c.rp, c.cap_pre, c.sink, c.tree))) return rc;
+    return fill_kvcache_prefill(c.o, c.kp, c.rp, c.cap_pre, c.sink, c.tree, c.row_tile);
 }
 
 int64_t fa_kvcache_workspace_bytes_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
-    fa::KvcacheKernelParams kp;
-    fa_kvcache_params local;
-    fa_kvcache_options_v8 o;
-    fa::KvcacheRotaryParams rp;
-    fa::KvcacheRaggedParams rg;
-    float cap_pre;
-    fa::KvcacheSink sink;
-    fa::KvcacheTree tree;
-    int32_t row_tile;
-    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, row_tile, false);
+    KvcacheCall c;
+    int rc = fill_kvcache_all(user, options, c, false);
     if (rc) return rc;
-    if (kp.b == 0) return 0;
-    const int64_t total_q = rg.cu_q != nullptr ? rg.total_q : -1;
-    return (rp.cos != nullptr ? fa::kvcache_rotary_image_bytes(kp) : 0) +
-           fa::kvcache_workspace_bytes(kp, fa::kvcache_split(kp, -1, local.num_splits, total_q, row_tile), total_q);
+    if (c.kp.b == 0) return 0;
+    return (c.rp.cos != nullptr ? fa::kvcache_rotary_image_bytes(c.kp) : 0) + fa::kvcache_workspace_bytes(c.kp, c.split(-1), c.total_q());
 }
 
 int32_t fa_kvcache_num_splits_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
-    fa::KvcacheKernelParams kp;
-    fa_kvcache_params local;
-    fa_kvcache_options_v8 o;
-    fa::KvcacheRotaryParams rp;
-    fa::KvcacheRaggedParams rg;
-    float cap_pre;
-    fa::KvcacheSink sink;
-    fa::KvcacheTree tree;
-    int32_t row_tile;
-    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, row_tile, true);
+    KvcacheCall c;
+    int rc = fill_kvcache_all(user, options, c, true);
     if (rc) return rc;
-    if (kp.b == 0) return 1;
-    int64_t avail = local.workspace != nullptr ? local.workspace_bytes : 0;
-    if (rp.cos != nullptr && (avail = rotary_split_bytes(kp, local)) < 0) return (int32_t)avail;
-    return fa::kvcache_split(kp, avail, local.num_splits, rg.cu_q != nullptr ? rg.total_q : -1, row_tile);
+    if (c.kp.b == 0) return 1;
+    const int64_t avail = c.split_bytes();
+    if (avail < 0) return (int32_t)avail;
+    return c.split(avail);
 }
 
 int32_t fa_kvcache_row_tile_ex(const fa_kvcache_params* user, const fa_kvcache_options* options) {
-    fa::KvcacheKernelParams kp;
-    fa_kvcache_params local;
-    fa_kvcache_options_v8 o;
-    fa::KvcacheRotaryParams rp;
-    fa::KvcacheRaggedParams rg;
-    float cap_pre;
-    fa::KvcacheSink sink;
-    fa::KvcacheTree tree;
-    int32_t row_tile;
-    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, row_tile, false);
+    KvcacheCall c;
+    int rc = fill_kvcache_all(user, options, c, false);
     if (rc) return rc;
-    return row_tile;
+    return c.row_tile;
 }
 
 int fa_run_mha_fwd_kvcache_ex(const fa_kvcache_params* user, const fa_kvcache_options* options, void* stream) {
-    fa::KvcacheKernelParams kp;
-    fa_kvcache_params local;
-    fa_kvcache_options_v8 o;
-    fa::KvcacheRotaryParams rp;
-    fa::KvcacheRaggedParams rg;
-    float cap_pre;
-    fa::KvcacheSink sink;
-    fa::KvcacheTree tree;
-    int32_t row_tile;
-    int rc = fill_kvcache_all(user, options, kp, local, o, rp, rg, cap_pre, sink, tree, row_tile, true);
+    KvcacheCall c;
+    int rc = fill_kvcache_all(user, options, c, true);
     if (rc) return rc;
+    fa::KvcacheKernelParams& kp = c.kp;
     if (kp.b == 0) return FA_OK;
-    int64_t avail = local.workspace != nullptr ? local.workspace_bytes : 0;
-    char* ws = (char*)local.workspace;
-    if (rg.cu_q != nullptr) {
-        // ragged queries: the append, attention and combine kernels of fa_fwd_kvcache_ragged.hip (no rotary: refused above)
-        kp.n_split = fa::kvcache_split(kp, avail, local.num_splits, rg.total_q, row_tile);
-        kp.ws_o = kp.n_split > 1 ? (float*)ws : nullptr;
-        rg.kp = kp;
-        return hip_status(fa::launch_fwd_kvcache_ragged(rg, local.dtype, (hipStream_t)stream, cap_pre, sink, tree, row_tile), "fa_fwd_kvcache (ragged) launch");
-    }
-    if (rp.cos != nullptr) {
+    const int64_t avail = c.split_bytes();
+    if (avail < 0) return (int)avail;
+    char* ws = (char*)c.local.workspace;
+    if (c.rp.cos != nullptr) {
         // the fused rotary launch takes the place of the append: it writes the cache rows and the image of the rotated q at the head of the
         // workspace; the attention kernels then run as without rotary, with the image as their q and nothing left to append
-        if ((avail = rotary_split_bytes(kp, local)) < 0) return (int)avail;
-        rp.kp = kp;
-        rp.q_image = ws;
+        c.rp.kp = kp;
+        c.rp.q_image = ws;
         ws += fa::kvcache_rotary_image_bytes(kp);
-        if ((rc = hip_status(fa::launch_kvcache_rotary(rp, local.dtype, (hipStream_t)stream), "fa_kvcache_rotary launch"))) return rc;
-        kp.q_ptr = rp.q_image;
+        if ((rc = hip_status(fa::launch_kvcache_rotary(c.rp, c.local.dtype, (hipStream_t)stream), "fa_kvcache_rotary launch"))) return rc;
+        kp.q_ptr = c.rp.q_image;
         kp.q = conv(contiguous_bshd(kp.seqlen_q, kp.h, kp.d));
         kp.k_new = kp.v_new = nullptr;          // (seqlen_new stays: the appended rows count into the valid length)
     }
-    kp.n_split = fa::kvcache_split(kp, avail, local.num_splits, -1, row_tile);
+    kp.n_split = c.split(avail);
     kp.ws_o = kp.n_split > 1 ? (float*)ws : nullptr;
-    return hip_status(fa::launch_fwd_kvcache(kp, local.dtype, (hipStream_t)stream, cap_pre, sink, tree, row_tile), "fa_fwd_kvcache launch");
+    if (c.rg.cu_q == nullptr)
+        return hip_status(fa::launch_fwd_kvcache(kp, c.local.dtype, (hipStream_t)stream, c.cap_pre, c.sink, c.tree, c.row_tile), "fa_fwd_kvcache launch");
+    // ragged queries: the append, attention and combine kernels of fa_fwd_kvcache_ragged.hip (no rotary: refused by fill_kvcache_ragged)
+    c.rg.kp = kp;
+    return hip_status(fa::launch_fwd_kvcache_ragged(c.rg, c.local.dtype, (hipStream_t)stream, c.cap_pre, c.sink, c.tree, c.row_tile), "fa_fwd_kvcache (ragged) launch");
 }
 
 int64_t fa_kvcache_workspace_bytes(const fa_kvcache_params* user) { return fa_kvcache_workspace_bytes_ex(user, nullptr); }
@@ -794,39 +920,15 @@ static int fill_mla(const fa_mla_params* user, fa::KvcacheMlaParams& mp, fa_mla_
     int rc = import_mla(user, local, "fa_mla_params");
     if (rc) return rc;
     const fa_mla_params_v2* p = &local;
-    const bool fp8 = p->kv_format == FA_MLA_KV_FP8_ROWS656;
-    const bool paged = p->block_table != nullptr;
     if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0 || p->seqlen_new < 0 || p->h <= 0)
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d seqlen_new=%d h=%d", p->b, p->seqlen_q, p->seqlen_cache, p->seqlen_new, p->h);
-    if (p->d_qk != 576) return fail(FA_ERR_BAD_HEADDIM, "d_qk %d unsupported (the latent row is 576 wide: 512 compressed + 64 rope elements)", p->d_qk);
-    if (p->d_v != 512) return fail(FA_ERR_BAD_HEADDIM, "d_v %d unsupported (the value is the first 512 elements of the latent row)", p->d_v);
-    if (p->dtype != FA_FP16 && p->dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", p->dtype);
-    if (paged) {
-        const int P = p->page_block_size;
-        if (P == 0) return fail(FA_ERR_BAD_SHAPE, "block_table given without page_block_size");
-        if (P < 0 || P % 16 != 0) return fail(FA_ERR_BAD_SHAPE, "page_block_size %d must be a positive multiple of 16", P);
-        if (p->num_blocks < 1) return fail(FA_ERR_BAD_SHAPE, "num_blocks %d: a paged cache needs at least one page", p->num_blocks);
-        if (p->seqlen_cache <= 0 || p->seqlen_cache % P != 0)
-            return fail(FA_ERR_BAD_SHAPE, "seqlen_cache (%d) must be a positive multiple of page_block_size (%d) with block_table", p->seqlen_cache, P);
-        if (p->block_table_stride < p->seqlen_cache / P)
-            return fail(FA_ERR_BAD_STRIDE, "block_table_stride %lld is below the table's %d columns (seqlen_cache / page_block_size)",
-                        (long long)p->block_table_stride, p->seqlen_cache / P);
-        if ((reinterpret_cast<uintptr_t>(p->block_table) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "block_table must be 4-byte aligned");
-    } else if (p->page_block_size != 0) {
-        return fail(FA_ERR_NULL_POINTER, "page_block_size = %d given without block_table", p->page_block_size);
-    }
+    if ((rc = check_mla_dims(p->d_qk, p->d_v, p->dtype))) return rc;
+    if ((rc = check_paged(p->block_table, p->block_table_stride, p->page_block_size, p->num_blocks, p->seqlen_cache))) return rc;
     if (p->seqlen_new > p->seqlen_cache)
         return fail(FA_ERR_BAD_SHAPE, "seqlen_new (%d) exceeds the cache capacity seqlen_cache (%d)", p->seqlen_new, p->seqlen_cache);
     if (p->kv_new != nullptr && p->cache_seqlens == nullptr) return fail(FA_ERR_NULL_POINTER, "kv_new needs cache_seqlens (the rows it is appended at)");
     if (p->kv_new == nullptr && p->seqlen_new != 0) return fail(FA_ERR_BAD_SHAPE, "seqlen_new = %d without kv_new", p->seqlen_new);
-    if (p->num_splits < 0) return fail(FA_ERR_BAD_SHAPE, "num_splits must be >= 0 (0 = the library's choice), got %d", p->num_splits);
-    if (!(p->softmax_scale >= 0.f) || isinf(p->softmax_scale))
-        return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default 576 ** -0.5)", (double)p->softmax_scale);
-    if (p->reserved_ != 0) return fail(FA_ERR_BAD_ABI, "fa_mla_params: reserved_ is not zero (a field of a newer header that this library does not know)");
-    if ((rc = check_mla_format(p->kv_format, p->reserved2_))) return rc;
-    if (with_workspace && p->workspace_bytes < 0) return fail(FA_ERR_BAD_SHAPE, "workspace_bytes must be >= 0");
-    if (with_workspace && p->workspace != nullptr && (reinterpret_cast<uintptr_t>(p->workspace) & 15u) != 0)
-        return fail(FA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
+    if ((rc = check_mla_tail(*p, "fa_mla_params", with_workspace))) return rc;
     // the attention grid is b x 64-row tiles x n_split workgroups (n_split <= 128), and a packed row index is an int
     const int64_t tiles = ((int64_t)p->seqlen_q * p->h + fa::kKvcPrefillRows - 1) / fa::kKvcPrefillRows;
     if ((int64_t)p->seqlen_q * p->h >= ((int64_t)1 << 31) || (int64_t)p->b * tiles >= ((int64_t)1 << 24))
@@ -837,27 +939,15 @@ static int fill_mla(const fa_mla_params* user, fa::KvcacheMlaParams& mp, fa_mla_
         if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
         if ((rc = check_tensor("q", p->q, p->q_stride, p->seqlen_q, p->d_qk, false))) return rc;
         if ((rc = check_tensor("o", p->o, p->o_stride, p->seqlen_q, p->d_v, false))) return rc;
-        // paged: the descriptors span at most one page, so the 2^31-byte limit applies per page (page offsets are 64-bit)
-        if (fp8 ? (rc = check_mla_cache8(p->kv_cache, kvc, paged ? p->page_block_size : p->seqlen_cache))
-                : (rc = check_tensor("kv_cache", p->kv_cache, kvc, paged ? p->page_block_size : p->seqlen_cache, p->d_qk, false))) return rc;
+        if ((rc = check_mla_cache(*p, kvc))) return rc;
         if (p->kv_new != nullptr && (rc = check_tensor("kv_new", p->kv_new, kvn, p->seqlen_new, p->d_qk, false))) return rc;
     }
     memset(&mp, 0, sizeof(mp));
     fa::KvcacheKernelParams& kp = mp.kp;
     mp.d_qk = p->d_qk;
-    kp.q_ptr = p->q; kp.k_cache = p->kv_cache; kp.v_cache = p->kv_cache; kp.k_new = p->kv_new; kp.v_new = p->kv_new;
-    kp.o_ptr = p->o; kp.lse_ptr = p->lse; kp.cache_seqlens = p->cache_seqlens;
-    kp.q = conv(p->q_stride); kp.kc = kp.vc = conv(kvc); kp.kn = kp.vn = conv(kvn); kp.o = conv(p->o_stride);
-    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_cache = p->seqlen_cache; kp.seqlen_new = p->kv_new != nullptr ? p->seqlen_new : 0;
-    kp.h = p->h; kp.h_k = 1; kp.h_ratio = p->h; kp.d = p->d_v;
+    fill_mla_kp(*p, kvc, kp);
+    kp.k_new = kp.v_new = p->kv_new; kp.kn = kp.vn = conv(kvn); kp.seqlen_new = p->kv_new != nullptr ? p->seqlen_new : 0;
     kp.is_causal = p->is_causal ? 1 : 0;
-    kp.cache_fp8 = fp8 ? 1 : 0;     // kc / vc are in bytes then
-    kp.scale = p->softmax_scale > 0.f ? p->softmax_scale : 1.0f / sqrtf((float)p->d_qk);
-    kp.scale_log2e = kp.scale * 1.4426950408889634f;
-    if (paged) {
-        kp.block_table = p->block_table; kp.bt_stride = p->block_table_stride;
-        kp.page_size = p->page_block_size; kp.num_blocks = p->num_blocks;
-    }
     return FA_OK;
 }
 
@@ -867,7 +957,7 @@ int64_t fa_mla_workspace_bytes(const fa_mla_params* user) {
     int rc = fill_mla(user, mp, local, false);
     if (rc) return rc;
     if (mp.kp.b == 0) return 0;
-    return fa::kvcache_workspace_bytes(mp.kp, fa::kvcache_split(mp.kp, -1, local.num_splits, -1, fa::kKvcPrefillRows));
+    return fa::kvcache_workspace_bytes(mp.kp, mla_split(mp.kp, local, false));
 }
 
 int32_t fa_mla_num_splits(const fa_mla_params* user) {
@@ -876,7 +966,7 @@ int32_t fa_mla_num_splits(const fa_mla_params* user) {
     int rc = fill_mla(user, mp, local, true);
     if (rc) return rc;
     if (mp.kp.b == 0) return 1;
-    return fa::kvcache_split(mp.kp, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits, -1, fa::kKvcPrefillRows);
+    return mla_split(mp.kp, local, true);
 }
 
 int fa_run_mla_fwd_kvcache(const fa_mla_params* user, void* stream) {
@@ -885,7 +975,7 @@ int fa_run_mla_fwd_kvcache(const fa_mla_params* user, void* stream) {
     int rc = fill_mla(user, mp, local, true);
     if (rc) return rc;
     if (mp.kp.b == 0) return FA_OK;
-    mp.kp.n_split = fa::kvcache_split(mp.kp, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits, -1, fa::kKvcPrefillRows);
+    mp.kp.n_split = mla_split(mp.kp, local, true);
     mp.kp.ws_o = mp.kp.n_split > 1 ? (float*)local.workspace : nullptr;
     if (mp.kp.cache_fp8) return hip_status(fa::launch_fwd_kvcache_mla_fp8(mp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache_mla_fp8 launch");
     return hip_status(fa::launch_fwd_kvcache_mla(mp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache_mla launch");
@@ -899,37 +989,13 @@ static int fill_mla_sparse(const fa_mla_sparse_params* user, fa::KvcacheMlaSpars
     int rc = import_mla(user, local, "fa_mla_sparse_params");
     if (rc) return rc;
     const fa_mla_sparse_params_v2* p = &local;
-    const bool fp8 = p->kv_format == FA_MLA_KV_FP8_ROWS656;
-    const bool paged = p->block_table != nullptr;
     if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0 || p->h <= 0)
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d h=%d", p->b, p->seqlen_q, p->seqlen_cache, p->h);
-    if (p->d_qk != 576) return fail(FA_ERR_BAD_HEADDIM, "d_qk %d unsupported (the latent row is 576 wide: 512 compressed + 64 rope elements)", p->d_qk);
-    if (p->d_v != 512) return fail(FA_ERR_BAD_HEADDIM, "d_v %d unsupported (the value is the first 512 elements of the latent row)", p->d_v);
-    if (p->dtype != FA_FP16 && p->dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", p->dtype);
+    if ((rc = check_mla_dims(p->d_qk, p->d_v, p->dtype))) return rc;
     if (p->topk < fa::kKvcStep || p->topk % fa::kKvcStep != 0)
         return fail(FA_ERR_BAD_SHAPE, "topk %d must be a positive multiple of %d (pad the lists with -1)", p->topk, fa::kKvcStep);
-    if (paged) {
-        const int P = p->page_block_size;
-        if (P == 0) return fail(FA_ERR_BAD_SHAPE, "block_table given without page_block_size");
-        if (P < 0 || P % 16 != 0) return fail(FA_ERR_BAD_SHAPE, "page_block_size %d must be a positive multiple of 16", P);
-        if (p->num_blocks < 1) return fail(FA_ERR_BAD_SHAPE, "num_blocks %d: a paged cache needs at least one page", p->num_blocks);
-        if (p->seqlen_cache <= 0 || p->seqlen_cache % P != 0)
-            return fail(FA_ERR_BAD_SHAPE, "seqlen_cache (%d) must be a positive multiple of page_block_size (%d) with block_table", p->seqlen_cache, P);
-        if (p->block_table_stride < p->seqlen_cache / P)
-            return fail(FA_ERR_BAD_STRIDE, "block_table_stride %lld is below the table's %d columns (seqlen_cache / page_block_size)",
-                        (long long)p->block_table_stride, p->seqlen_cache / P);
-        if ((reinterpret_cast<uintptr_t>(p->block_table) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "block_table must be 4-byte aligned");
-    } else if (p->page_block_size != 0) {
-        return fail(FA_ERR_NULL_POINTER, "page_block_size = %d given without block_table", p->page_block_size);
-    }
-    if (p->num_splits < 0) return fail(FA_ERR_BAD_SHAPE, "num_splits must be >= 0 (0 = the library's choice), got %d", p->num_splits);
-    if (!(p->softmax_scale >= 0.f) || isinf(p->softmax_scale))
-        return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default 576 ** -0.5)", (double)p->softmax_scale);
-    if (p->reserved_ != 0) return fail(FA_ERR_BAD_ABI, "fa_mla_sparse_params: reserved_ is not zero (a field of a newer header that this library does not know)");
-    if ((rc = check_mla_format(p->kv_format, p->reserved2_))) return rc;
-    if (with_workspace && p->workspace_bytes < 0) return fail(FA_ERR_BAD_SHAPE, "workspace_bytes must be >= 0");
-    if (with_workspace && p->workspace != nullptr && (reinterpret_cast<uintptr_t>(p->workspace) & 15u) != 0)
-        return fail(FA_ERR_BAD_STRIDE, "workspace must be 16-byte aligned");
+    if ((rc = check_paged(p->block_table, p->block_table_stride, p->page_block_size, p->num_blocks, p->seqlen_cache))) return rc;
+    if ((rc = check_mla_tail(*p, "fa_mla_sparse_params", with_workspace))) return rc;
     // the attention grid is b x seqlen_q x 64-head tiles x n_split workgroups (n_split <= 128), and a row index is an int
     const int64_t tiles = ((int64_t)p->h + fa::kKvcPrefillRows - 1) / fa::kKvcPrefillRows;
     if ((int64_t)p->seqlen_q * p->h >= ((int64_t)1 << 31) || (int64_t)p->b * p->seqlen_q * tiles >= ((int64_t)1 << 24))
@@ -945,27 +1011,13 @@ static int fill_mla_sparse(const fa_mla_sparse_params* user, fa::KvcacheMlaSpars
                         (long long)p->indices_row_stride);
         if ((rc = check_tensor("q", p->q, p->q_stride, p->seqlen_q, p->d_qk, false))) return rc;
         if ((rc = check_tensor("o", p->o, p->o_stride, p->seqlen_q, p->d_v, false))) return rc;
-        // paged: the descriptors span one cache row, page offsets are 64-bit; contiguous: one descriptor per sequence, below 2^31 bytes
-        if (fp8 ? (rc = check_mla_cache8(p->kv_cache, kvc, paged ? p->page_block_size : p->seqlen_cache))
-                : (rc = check_tensor("kv_cache", p->kv_cache, kvc, paged ? p->page_block_size : p->seqlen_cache, p->d_qk, false))) return rc;
+        if ((rc = check_mla_cache(*p, kvc))) return rc;
     }
     memset(&sp, 0, sizeof(sp));
-    fa::KvcacheKernelParams& kp = sp.kp;
     sp.d_qk = p->d_qk; sp.topk = p->topk;
     sp.indices = p->indices; sp.idx_batch = p->indices_batch_stride; sp.idx_row = p->indices_row_stride;
-    kp.q_ptr = p->q; kp.k_cache = const_cast<void*>(p->kv_cache); kp.v_cache = kp.k_cache;
-    kp.o_ptr = p->o; kp.lse_ptr = p->lse; kp.cache_seqlens = p->cache_seqlens;
-    kp.q = conv(p->q_stride); kp.kc = kp.vc = conv(kvc); kp.o = conv(p->o_stride);
-    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_cache = p->seqlen_cache;
-    kp.h = p->h; kp.h_k = 1; kp.h_ratio = p->h; kp.d = p->d_v;
-    kp.cache_fp8 = fp8 ? 1 : 0;     // kc / vc are in bytes then
-    kp.scale = p->softmax_scale > 0.f ? p->softmax_scale : 1.0f / sqrtf((float)p->d_qk);
-    kp.scale_log2e = kp.scale * 1.4426950408889634f;
-    if (paged) {
-        kp.block_table = p->block_table; kp.bt_stride = p->block_table_stride;
-        kp.page_size = p->page_block_size; kp.num_blocks = p->num_blocks;
-    }
-    split = kp;
+    fill_mla_kp(*p, kvc, sp.kp);
+    split = sp.kp;
     split.b = p->b * p->seqlen_q; split.seqlen_q = 1; split.seqlen_cache = p->topk;
     return FA_OK;
 }
@@ -977,7 +1029,7 @@ int64_t fa_mla_sparse_workspace_bytes(const fa_mla_sparse_params* user) {
     int rc = fill_mla_sparse(user, sp, split, local, false);
     if (rc) return rc;
     if (sp.kp.b == 0) return 0;
-    return fa::kvcache_workspace_bytes(split, fa::kvcache_split(split, -1, local.num_splits, -1, fa::kKvcPrefillRows));
+    return fa::kvcache_workspace_bytes(split, mla_split(split, local, false));
 }
 
 int32_t fa_mla_sparse_num_splits(const fa_mla_sparse_params* user) {
@@ -987,7 +1039,7 @@ int32_t fa_mla_sparse_num_splits(const fa_mla_sparse_params* user) {
     int rc = fill_mla_sparse(user, sp, split, local, true);
     if (rc) return rc;
     if (sp.kp.b == 0) return 1;
-    return fa::kvcache_split(split, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits, -1, fa::kKvcPrefillRows);
+    return mla_split(split, local, true);
 }
 
 int fa_run_mla_sparse_fwd_kvcache(const fa_mla_sparse_params* user, void* stream) {
@@ -997,7 +1049,7 @@ int fa_run_mla_sparse_fwd_kvcache(const fa_mla_sparse_params* user, void* stream
     int rc = fill_mla_sparse(user, sp, split, local, true);
     if (rc) return rc;
     if (sp.kp.b == 0) return FA_OK;
-    sp.kp.n_split = fa::kvcache_split(split, local.workspace != nullptr ? local.workspace_bytes : 0, local.num_splits, -1, fa::kKvcPrefillRows);
+    sp.kp.n_split = mla_split(split, local, true);
     sp.kp.ws_o = sp.kp.n_split > 1 ? (float*)local.workspace : nullptr;
     if (sp.kp.cache_fp8) return hip_status(fa::launch_fwd_kvcache_mla_sparse_fp8(sp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache_mla_sparse_fp8 launch");
     return hip_status(fa::launch_fwd_kvcache_mla_sparse(sp, local.dtype, (hipStream_t)stream), "fa_fwd_kvcache_mla_sparse launch");
@@ -1013,24 +1065,11 @@ static int fill_mla_indexer(const fa_mla_indexer_params* user, fa::MlaIndexerPar
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d", p->b, p->seqlen_q, p->seqlen_cache);
     if (p->h != 16 && p->h != 32 && p->h != 64) return fail(FA_ERR_BAD_HEADDIM, "h %d unsupported (16, 32 or 64 index heads)", p->h);
     if (p->d != fa::kIdxD) return fail(FA_ERR_BAD_HEADDIM, "d %d unsupported (index heads and index keys are 128 wide)", p->d);
-    if (p->dtype != FA_FP16 && p->dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", p->dtype);
+    if ((rc = check_dtype(p->dtype))) return rc;
     if (p->k_format != FA_MLA_KV_16BIT && p->k_format != FA_IDX_K_FP8_E4M3)
         return fail(FA_ERR_BAD_DTYPE, "k_format %d unknown (0 = keys of dtype, 1 = OCP e4m3 codes)", p->k_format);
-    if (p->reserved_ != 0) return fail(FA_ERR_BAD_SHAPE, "fa_mla_indexer_params: reserved_ is not zero (a field of a newer header that this library does not know)");
-    if (paged) {
-        const int P = p->page_block_size;
-        if (P == 0) return fail(FA_ERR_BAD_SHAPE, "block_table given without page_block_size");
-        if (P < 0 || P % 16 != 0) return fail(FA_ERR_BAD_SHAPE, "page_block_size %d must be a positive multiple of 16", P);
-        if (p->num_blocks < 1) return fail(FA_ERR_BAD_SHAPE, "num_blocks %d: a paged cache needs at least one page", p->num_blocks);
-        if (p->seqlen_cache <= 0 || p->seqlen_cache % P != 0)
-            return fail(FA_ERR_BAD_SHAPE, "seqlen_cache (%d) must be a positive multiple of page_block_size (%d) with block_table", p->seqlen_cache, P);
-        if (p->block_table_stride < p->seqlen_cache / P)
-            return fail(FA_ERR_BAD_STRIDE, "block_table_stride %lld is below the table's %d columns (seqlen_cache / page_block_size)",
-                        (long long)p->block_table_stride, p->seqlen_cache / P);
-        if ((reinterpret_cast<uintptr_t>(p->block_table) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "block_table must be 4-byte aligned");
-    } else if (p->page_block_size != 0) {
-        return fail(FA_ERR_NULL_POINTER, "page_block_size = %d given without block_table", p->page_block_size);
-    }
+    if ((rc = check_reserved(p->reserved_, "fa_mla_indexer_params", FA_ERR_BAD_SHAPE))) return rc;
+    if ((rc = check_paged(p->block_table, p->block_table_stride, p->page_block_size, p->num_blocks, p->seqlen_cache))) return rc;
     // a workgroup's key range ends at most kIdxMaxWgKeys past the capacity, and the grid is one-dimensional
     if (p->seqlen_cache > INT32_MAX - 2 * fa::kIdxMaxWgKeys) return fail(FA_ERR_BAD_SHAPE, "seqlen_cache %d too large", p->seqlen_cache);
     if ((int64_t)p->b * p->seqlen_q >= ((int64_t)1 << 24))
@@ -1092,7 +1131,7 @@ int fa_run_mla_indexer_topk(const fa_mla_topk_params* user, void* stream) {
     if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0)
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d", p->b, p->seqlen_q, p->seqlen_cache);
     if (p->topk < 32 || p->topk % 32 != 0) return fail(FA_ERR_BAD_SHAPE, "topk %d must be a positive multiple of 32", p->topk);
-    if (p->reserved_ != 0) return fail(FA_ERR_BAD_SHAPE, "fa_mla_topk_params: reserved_ is not zero (a field of a newer header that this library does not know)");
+    if ((rc = check_reserved(p->reserved_, "fa_mla_topk_params", FA_ERR_BAD_SHAPE))) return rc;
     if ((int64_t)p->b * p->seqlen_q >= ((int64_t)1 << 31))
         return fail(FA_ERR_BAD_SHAPE, "call too large: b = %d sequences x seqlen_q = %d tokens exceeds the launch grid", p->b, p->seqlen_q);
     if (p->b == 0) return FA_OK;
@@ -1121,29 +1160,10 @@ int fa_run_mla_prefill_fwd(const fa_mla_prefill_params* user, void* stream) {
     int rc = import_exact(user, local, "fa_mla_prefill_params");
     if (rc) return rc;
     const fa_mla_prefill_params* p = &local;
-    if (p->b < 0 || p->seqlen_q < 0 || p->seqlen_k < 0 || p->h <= 0 || p->h_k <= 0)
-        return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d seqlen_k=%d h=%d h_k=%d", p->b, p->seqlen_q, p->seqlen_k, p->h, p->h_k);
-    if (p->h % p->h_k != 0) return fail(FA_ERR_BAD_GQA, "h (%d) must be divisible by h_k (%d) for GQA/MQA", p->h, p->h_k);
-    if (p->d_qk != 192) return fail(FA_ERR_BAD_HEADDIM, "d_qk %d unsupported (q and k are 192 wide: 128 no-rope + 64 rope elements)", p->d_qk);
-    if (p->d_v != 128) return fail(FA_ERR_BAD_HEADDIM, "d_v %d unsupported (v and o are 128 wide)", p->d_v);
-    if (p->dtype != FA_FP16 && p->dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", p->dtype);
-    const bool packed = p->cu_seqlens_q != nullptr || p->cu_seqlens_k != nullptr;
-    if (packed && p->cu_seqlens_q == nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_q is NULL but cu_seqlens_k is given (both or neither)");
-    if (packed && p->cu_seqlens_k == nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_k is NULL but cu_seqlens_q is given (both or neither)");
-    if (packed && ((reinterpret_cast<uintptr_t>(p->cu_seqlens_q) | reinterpret_cast<uintptr_t>(p->cu_seqlens_k)) & 3u) != 0)
-        return fail(FA_ERR_BAD_STRIDE, "cu_seqlens_q / cu_seqlens_k must be 4-byte aligned");
-    if (!(p->softmax_scale >= 0.f) || isinf(p->softmax_scale))
-        return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default 192 ** -0.5)", (double)p->softmax_scale);
-    if (packed && (p->total_q < 0 || p->total_k < 0))
-        return fail(FA_ERR_BAD_SHAPE, "total_q (%lld) / total_k (%lld) must be >= 0 with cu_seqlens", (long long)p->total_q, (long long)p->total_k);
+    if ((rc = check_mla_prefill_front(*p))) return rc;
+    if ((rc = check_mla_prefill_grid(*p, false))) return rc;
+    const bool packed = p->cu_seqlens_q != nullptr;
     const int64_t rows_q = packed ? p->total_q : p->seqlen_q, rows_k = packed ? p->total_k : p->seqlen_k;
-    // the attention grid is h_k x row tiles (dense: per batch entry; packed: of all rows, plus one slot per sequence), counted here in tiles of 64 rows - the
-    // smaller of the two tiles fa_fwd_mla_prefill.hip can be built with - and a packed row index is an int
-    const int64_t h_ratio = p->h / p->h_k;
-    const int64_t tiles = (rows_q * h_ratio + fa::kKvcPrefillRows - 1) / fa::kKvcPrefillRows;
-    if (rows_q * h_ratio >= ((int64_t)1 << 31) || rows_k >= ((int64_t)1 << 31) || (packed ? tiles + p->b : tiles * p->b) * p->h_k >= ((int64_t)1 << 31))
-        return fail(FA_ERR_BAD_SHAPE, "call too large: b = %d sequences, %lld query rows x h = %d heads, %lld keys exceed the launch grid", p->b, (long long)rows_q, p->h,
-                    (long long)rows_k);
     if (p->b == 0 || rows_q == 0) return FA_OK;     // nothing to write
     if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
     if ((rc = check_tensor("q", p->q, p->q_stride, rows_q, p->d_qk, packed))) return rc;
@@ -1154,49 +1174,22 @@ int fa_run_mla_prefill_fwd(const fa_mla_prefill_params* user, void* stream) {
     }
     fa::MlaPrefillParams kp;
     memset(&kp, 0, sizeof(kp));
-    kp.q_ptr = p->q; kp.k_ptr = p->k; kp.v_ptr = p->v; kp.o_ptr = p->o; kp.lse_ptr = p->lse;
-    kp.cu_q = p->cu_seqlens_q; kp.cu_k = p->cu_seqlens_k;
-    kp.q = conv(p->q_stride); kp.k = conv(p->k_stride); kp.v = conv(p->v_stride); kp.o = conv(p->o_stride);
-    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_k = p->seqlen_k;
-    kp.h = p->h; kp.h_k = p->h_k; kp.h_ratio = (int32_t)h_ratio;
-    kp.is_causal = p->is_causal ? 1 : 0;
-    kp.total_q = packed ? p->total_q : 0; kp.total_k = packed ? p->total_k : 0;
-    kp.scale = p->softmax_scale > 0.f ? p->softmax_scale : 1.0f / sqrtf((float)p->d_qk);        // (= 192 ** -0.5 rounded once to fp32)
-    kp.scale_log2e = kp.scale * 1.4426950408889634f;
+    fill_mla_prefill_kp(*p, kp);
     return hip_status(fa::launch_fwd_mla_prefill(kp, p->dtype, (hipStream_t)stream), "fa_fwd_mla_prefill launch");
 }
 
-// fa_mla_prefill_bwd_params -> MlaPrefillBwdParams, validated: the forward's checks in the forward's order and words, then the tensors of the backward.
+// fa_mla_prefill_bwd_params -> MlaPrefillBwdParams, validated: the forward's checks (phases and reserved_ in front of the grids), then the tensors of the backward.
 int fa_run_mla_prefill_bwd(const fa_mla_prefill_bwd_params* user, void* stream) {
     fa_mla_prefill_bwd_params local;
     int rc = import_exact(user, local, "fa_mla_prefill_bwd_params");
     if (rc) return rc;
     const fa_mla_prefill_bwd_params* p = &local;
-    if (p->b < 0 || p->seqlen_q < 0 || p->seqlen_k < 0 || p->h <= 0 || p->h_k <= 0)
-        return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d seqlen_k=%d h=%d h_k=%d", p->b, p->seqlen_q, p->seqlen_k, p->h, p->h_k);
-    if (p->h % p->h_k != 0) return fail(FA_ERR_BAD_GQA, "h (%d) must be divisible by h_k (%d) for GQA/MQA", p->h, p->h_k);
-    if (p->d_qk != 192) return fail(FA_ERR_BAD_HEADDIM, "d_qk %d unsupported (q and k are 192 wide: 128 no-rope + 64 rope elements)", p->d_qk);
-    if (p->d_v != 128) return fail(FA_ERR_BAD_HEADDIM, "d_v %d unsupported (v and o are 128 wide)", p->d_v);
-    if (p->dtype != FA_FP16 && p->dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", p->dtype);
-    const bool packed = p->cu_seqlens_q != nullptr || p->cu_seqlens_k != nullptr;
-    if (packed && p->cu_seqlens_q == nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_q is NULL but cu_seqlens_k is given (both or neither)");
-    if (packed && p->cu_seqlens_k == nullptr) return fail(FA_ERR_NULL_POINTER, "cu_seqlens_k is NULL but cu_seqlens_q is given (both or neither)");
-    if (packed && ((reinterpret_cast<uintptr_t>(p->cu_seqlens_q) | reinterpret_cast<uintptr_t>(p->cu_seqlens_k)) & 3u) != 0)
-        return fail(FA_ERR_BAD_STRIDE, "cu_seqlens_q / cu_seqlens_k must be 4-byte aligned");
-    if (!(p->softmax_scale >= 0.f) || isinf(p->softmax_scale))
-        return fail(FA_ERR_BAD_SHAPE, "softmax_scale %g must be finite and > 0 (0 = the default 192 ** -0.5)", (double)p->softmax_scale);
-    if (packed && (p->total_q < 0 || p->total_k < 0))
-        return fail(FA_ERR_BAD_SHAPE, "total_q (%lld) / total_k (%lld) must be >= 0 with cu_seqlens", (long long)p->total_q, (long long)p->total_k);
+    if ((rc = check_mla_prefill_front(*p))) return rc;
     if (p->phases < 0 || p->phases > 2) return fail(FA_ERR_BAD_SHAPE, "phases %d unknown (0 = both launches, 1 = dq, 2 = dk / dv)", p->phases);
-    if (p->reserved_ != 0) return fail(FA_ERR_BAD_SHAPE, "fa_mla_prefill_bwd_params: reserved_ is not zero (a field of a newer header that this library does not know)");
+    if ((rc = check_reserved(p->reserved_, "fa_mla_prefill_bwd_params", FA_ERR_BAD_SHAPE))) return rc;
+    if ((rc = check_mla_prefill_grid(*p, true))) return rc;
+    const bool packed = p->cu_seqlens_q != nullptr;
     const int64_t rows_q = packed ? p->total_q : p->seqlen_q, rows_k = packed ? p->total_k : p->seqlen_k;
-    // both grids are h_k x tiles of 64 (dense: per batch entry; packed: of all rows or keys, plus one slot per sequence), and a packed row index is an int
-    const int64_t h_ratio = p->h / p->h_k;
-    const int64_t tiles = (rows_q * h_ratio + fa::kKvcPrefillRows - 1) / fa::kKvcPrefillRows, ktiles = (rows_k + fa::kKvcPrefillRows - 1) / fa::kKvcPrefillRows;
-    if (rows_q * h_ratio >= ((int64_t)1 << 31) || rows_k >= ((int64_t)1 << 31) || (packed ? tiles + p->b : tiles * p->b) * p->h_k >= ((int64_t)1 << 31) ||
-        (packed ? ktiles + p->b : ktiles * p->b) * p->h_k >= ((int64_t)1 << 31))
-        return fail(FA_ERR_BAD_SHAPE, "call too large: b = %d sequences, %lld query rows x h = %d heads, %lld keys exceed the launch grid", p->b, (long long)rows_q, p->h,
-                    (long long)rows_k);
     if (p->b == 0 || rows_q == 0) return FA_OK;     // nothing to launch
     if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
     if (p->dsoftmax_sum == nullptr) return fail(FA_ERR_NULL_POINTER, "dsoftmax_sum is NULL");
@@ -1214,17 +1207,9 @@ int fa_run_mla_prefill_bwd(const fa_mla_prefill_bwd_params* user, void* stream) 
     }
     fa::MlaPrefillBwdParams kp;
     memset(&kp, 0, sizeof(kp));
-    kp.q_ptr = p->q; kp.k_ptr = p->k; kp.v_ptr = p->v; kp.o_ptr = p->o; kp.do_ptr = p->dout; kp.dq_ptr = p->dq; kp.dk_ptr = p->dk; kp.dv_ptr = p->dv;
-    kp.lse_ptr = p->lse; kp.dsum_ptr = p->dsoftmax_sum;
-    kp.cu_q = p->cu_seqlens_q; kp.cu_k = p->cu_seqlens_k;
-    kp.q = conv(p->q_stride); kp.k = conv(p->k_stride); kp.v = conv(p->v_stride); kp.o = conv(p->o_stride);
+    fill_mla_prefill_kp(*p, kp);
+    kp.do_ptr = p->dout; kp.dq_ptr = p->dq; kp.dk_ptr = p->dk; kp.dv_ptr = p->dv; kp.dsum_ptr = p->dsoftmax_sum;
     kp.dout = conv(p->dout_stride); kp.dq = conv(p->dq_stride); kp.dk = conv(p->dk_stride); kp.dv = conv(p->dv_stride);
-    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_k = p->seqlen_k;
-    kp.h = p->h; kp.h_k = p->h_k; kp.h_ratio = (int32_t)h_ratio;
-    kp.is_causal = p->is_causal ? 1 : 0;
-    kp.total_q = packed ? p->total_q : 0; kp.total_k = packed ? p->total_k : 0;
-    kp.scale = p->softmax_scale > 0.f ? p->softmax_scale : 1.0f / sqrtf((float)p->d_qk);        // (the forward's default, rounded once to fp32)
-    kp.scale_log2e = kp.scale * 1.4426950408889634f;
     // (with query rows but no key anywhere the dQ launch still runs: every row is dead and is written as zeros)
     return hip_status(fa::launch_bwd_mla_prefill(kp, p->dtype, p->phases ? p->phases : 3, (hipStream_t)stream), "fa_bwd_mla_prefill launch");
 }
@@ -1239,7 +1224,7 @@ int fa_run_merge_states(const fa_merge_params* user) {
     const fa_merge_params* p = &local;
     if (p->n_parts < 2 || p->n_parts > FA_MERGE_MAX_PARTS) return fail(FA_ERR_BAD_SHAPE, "n_parts %d unsupported (2 .. %d parts)", p->n_parts, FA_MERGE_MAX_PARTS);
     if (p->d_v != 64 && p->d_v != 128 && p->d_v != 256 && p->d_v != 512) return fail(FA_ERR_BAD_HEADDIM, "d_v %d unsupported (64, 128, 256 or 512)", p->d_v);
-    if (p->dtype != FA_FP16 && p->dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "dtype %d unsupported (0=fp16, 1=bf16)", p->dtype);
+    if ((rc = check_dtype(p->dtype))) return rc;
     if (p->b < 0 || p->rows < 0 || p->h < 0) return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d rows=%d h=%d", p->b, p->rows, p->h);
     const int64_t all_rows = (int64_t)p->b * p->rows;
     const int64_t total = all_rows < ((int64_t)1 << 31) ? all_rows * p->h : 0;       // (three int32 factors fit an int64 only once two of them fit an int32)

@@ -53,6 +53,7 @@ fa_strides strides3(const at::Tensor& t) {
     TORCH_CHECK(t.stride(2) == 1, "last dimension must be contiguous");
     return fa_strides{0, t.stride(0), t.stride(1)};
 }
+fa_strides strides34(const at::Tensor& t) { return t.dim() == 3 ? strides3(t) : strides4(t); }      // packed (rows, h, d) or dense (b, rows, h, d)
 // The kernels take real strides, but rows/heads must stay 16-byte aligned; anything else is
 // densified (the reference assumes contiguous input without checking, flash_api.cpp:38-54).
 // NOTE: the densifying copy is a hidden extra HBM pass the reference never makes (it never checks); it only
@@ -80,6 +81,61 @@ void check_cu_seqlens(const at::Tensor& cu_q, const at::Tensor& cu_k) {
     TORCH_CHECK(cu_q.dim() == 1 && cu_k.dim() == 1, "cu_seqlens_q/cu_seqlens_k must be rank-1");
     TORCH_CHECK(cu_q.numel() >= 2 && cu_k.numel() >= 2, "cu_seqlens_q/cu_seqlens_k must have at least 2 elements");
     TORCH_CHECK(cu_k.numel() == cu_q.numel(), "cu_seqlens_k must have shape [batch_size + 1] with cumulative offsets");
+}
+
+// ---- argument rules that several functions below share: each is stated once and called at the caller's place in its order of checks.  The words and the place
+// of a refusal are part of the interface; where the callers differ, the difference is an argument.
+
+// A block_table argument: int32 (batch_size, max_blocks_per_seq) on q's device, last dimension contiguous, over the page pool `pool` (num_blocks, page_block_size,
+// ..).  Fills the four paging fields of the C struct `p` and returns the capacity.  one_check: mla_indexer_logits states dtype, rank and batch in one check of its
+// own words (its Python layer has checked them before).
+template <typename P>
+int64_t attach_block_table(P& p, const at::Tensor& q, int64_t batch_size, const at::Tensor& block_table, const at::Tensor& pool, bool one_check = false) {
+    check_same_device(q, block_table, "block_table");
+    if (one_check) {
+        TORCH_CHECK(block_table.scalar_type() == torch::kInt32 && block_table.dim() == 2 && block_table.size(0) == batch_size, "block_table must be int32 [batch_size, max_blocks_per_seq]");
+    } else {
+        TORCH_CHECK(block_table.scalar_type() == torch::kInt32, "block_table must be an int32 tensor");
+        TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == batch_size, "block_table must have shape [batch_size, max_blocks_per_seq]");
+    }
+    TORCH_CHECK(block_table.stride(1) == 1 || block_table.size(1) <= 1, "block_table: last dimension must be contiguous");
+    const int64_t capacity = block_table.size(1) * pool.size(1);        // max_blocks_per_seq pages of page_block_size rows
+    TORCH_CHECK(pool.size(0) <= INT32_MAX && capacity <= INT32_MAX, "block_table: pool pages and capacity must fit in int32");
+    p.block_table = block_table.data_ptr<int32_t>();
+    // (a one-row table's row stride is never used; a view may report anything there)
+    p.block_table_stride = batch_size > 1 ? block_table.stride(0) : std::max<int64_t>(block_table.stride(0), block_table.size(1));
+    p.page_block_size = (int32_t)pool.size(1); p.num_blocks = (int32_t)pool.size(0);
+    return capacity;
+}
+
+// An optional cache_seqlens: int32 (batch_size,), contiguous, on q's device -> its pointer (NULL without it); it stays on the device
+const int32_t* cache_seqlens_ptr(const at::Tensor& q, int64_t batch_size, const c10::optional<at::Tensor>& cache_seqlens) {
+    if (!cache_seqlens.has_value()) return nullptr;
+    check_same_device(q, *cache_seqlens, "cache_seqlens");
+    TORCH_CHECK(cache_seqlens->scalar_type() == torch::kInt32, "cache_seqlens must be an int32 tensor");
+    TORCH_CHECK(cache_seqlens->dim() == 1 && cache_seqlens->size(0) == batch_size && cache_seqlens->is_contiguous(),
+                "cache_seqlens must be a contiguous tensor of shape [batch_size]");
+    return cache_seqlens->data_ptr<int32_t>();
+}
+
+// softmax_scale -> the float of the C ABI, rounded once to fp32; 0 means "the default" there (None here; dflt: its text), so a given scale that is or rounds to 0 is refused
+float softmax_scale_fp32(const c10::optional<double>& softmax_scale, const char* dflt) {
+    TORCH_CHECK(!softmax_scale.has_value() || (std::isfinite(*softmax_scale) && (float)*softmax_scale > 0.f && std::isfinite((float)*softmax_scale)),
+                "softmax_scale must be a finite fp32 value > 0 (or None = ", dflt, ")");
+    return softmax_scale.has_value() ? (float)*softmax_scale : 0.f;
+}
+
+// ws_bytes: what the library's *_workspace_bytes query answered for `p` (negative: its error).  The fp32 scratch comes from the caching allocator and is attached
+// to `p`; the returned tensor keeps it alive.
+template <typename P>
+at::Tensor attach_workspace(P& p, int64_t ws_bytes, const at::Tensor& q) {
+    at::Tensor workspace;
+    if (ws_bytes < 0) check_status((int)ws_bytes);
+    if (ws_bytes > 0) {
+        workspace = torch::empty({ws_bytes / 4}, q.options().dtype(torch::kFloat32));
+        p.workspace = workspace.data_ptr(); p.workspace_bytes = ws_bytes;
+    }
+    return workspace;
 }
 
 }  // namespace
@@ -152,13 +208,7 @@ std::vector<at::Tensor> mha_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Te
     p.do_stride = strides4(dout); p.dq_stride = strides4(dq); p.dk_stride = strides4(dk); p.dv_stride = strides4(dv);
     // fp32 scratch (ABI 3) that lets the dK/dV launch split a KV head's query-head group over several workgroups (GQA / MQA with few
     // workgroups, causal imbalance); 0 bytes for MHA and for grids that fill the chip anyway
-    at::Tensor workspace;
-    const int64_t ws_bytes = fa_bwd_workspace_bytes(&p);
-    if (ws_bytes < 0) check_status((int)ws_bytes);
-    if (ws_bytes > 0) {
-        workspace = torch::empty({ws_bytes / 4}, q.options().dtype(torch::kFloat32));
-        p.workspace = workspace.data_ptr(); p.workspace_bytes = ws_bytes;
-    }
+    at::Tensor workspace = attach_workspace(p, fa_bwd_workspace_bytes(&p), q);
     check_status(fa_run_mha_bwd(&p, current_stream(q)));
     return {dq, dk, dv};
 }
@@ -250,13 +300,7 @@ std::vector<at::Tensor> mha_varlen_bwd(at::Tensor q, at::Tensor k, at::Tensor v,
     p.total_q = q.size(0); p.total_k = k.size(0);
     // fp32 scratch (ABI 3) that lets the dK/dV launch split a KV head's query-head group over several workgroups (GQA / MQA with few
     // workgroups, causal imbalance); 0 bytes for MHA and for grids that fill the chip anyway
-    at::Tensor workspace;
-    const int64_t ws_bytes = fa_bwd_workspace_bytes(&p);
-    if (ws_bytes < 0) check_status((int)ws_bytes);
-    if (ws_bytes > 0) {
-        workspace = torch::empty({ws_bytes / 4}, q.options().dtype(torch::kFloat32));
-        p.workspace = workspace.data_ptr(); p.workspace_bytes = ws_bytes;
-    }
+    at::Tensor workspace = attach_workspace(p, fa_bwd_workspace_bytes(&p), q);
     check_status(fa_run_mha_bwd(&p, current_stream(q)));
     return {dq, dk, dv};
 }
@@ -326,15 +370,10 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
     const int64_t num_heads_k = k_cache.size(2);
     int64_t seqlen_cache = k_cache.size(1);
     TORCH_CHECK(seqlen_q >= 1, "seqlen_q must be >= 1");
-    at::Tensor block_table;
+    fa_kvcache_params p;
+    FA_PARAMS_INIT(p);
     if (block_table_.has_value()) {
-        block_table = *block_table_;
-        check_same_device(q, block_table, "block_table");
-        TORCH_CHECK(block_table.scalar_type() == torch::kInt32, "block_table must be an int32 tensor");
-        TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == batch_size, "block_table must have shape [batch_size, max_blocks_per_seq]");
-        TORCH_CHECK(block_table.stride(1) == 1 || block_table.size(1) <= 1, "block_table: last dimension must be contiguous");
-        seqlen_cache = block_table.size(1) * k_cache.size(1);       // the capacity: max_blocks_per_seq pages of page_block_size rows
-        TORCH_CHECK(k_cache.size(0) <= INT32_MAX && seqlen_cache <= INT32_MAX, "block_table: pool pages and capacity must fit in int32");
+        seqlen_cache = attach_block_table(p, q, batch_size, *block_table_, k_cache);
     } else {
         TORCH_CHECK(k_cache.size(0) == batch_size && v_cache.size(0) == batch_size, "k_cache/v_cache batch size must match q");
     }
@@ -346,17 +385,11 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
     TORCH_CHECK(window_size_left >= -1 && window_size_right >= -1 && window_size_left <= INT32_MAX && window_size_right <= INT32_MAX,
                 "window_size: each side must be an int32 >= -1 (-1 = unbounded)");
     TORCH_CHECK(k_new_.has_value() == v_new_.has_value(), "k and v must both be given or both be None");
-    at::Tensor k_new, v_new, cache_seqlens;
-    if (cache_seqlens_.has_value()) {
-        cache_seqlens = *cache_seqlens_;
-        check_same_device(q, cache_seqlens, "cache_seqlens");
-        TORCH_CHECK(cache_seqlens.scalar_type() == torch::kInt32, "cache_seqlens must be an int32 tensor");
-        TORCH_CHECK(cache_seqlens.dim() == 1 && cache_seqlens.size(0) == batch_size && cache_seqlens.is_contiguous(),
-                    "cache_seqlens must be a contiguous tensor of shape [batch_size]");
-    }
+    at::Tensor k_new, v_new;
+    p.cache_seqlens = cache_seqlens_ptr(q, batch_size, cache_seqlens_);
     c10::DeviceGuard guard(q.device());
     if (k_new_.has_value()) {
-        TORCH_CHECK(cache_seqlens.defined(), "cache_seqlens is required when k and v are appended");
+        TORCH_CHECK(cache_seqlens_.has_value(), "cache_seqlens is required when k and v are appended");
         k_new = *k_new_; v_new = *v_new_;
         TORCH_CHECK(k_new.dim() == 4 && v_new.dim() == 4, "k and v must be rank-4 tensors");
         check_same_device(q, k_new, "k"); check_same_device(q, v_new, "v");
@@ -371,20 +404,11 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
     at::Tensor l = ragged ? torch::empty({num_heads, total_q}, q.options().dtype(torch::kFloat32))
                           : torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(torch::kFloat32));
 
-    fa_kvcache_params p;
-    FA_PARAMS_INIT(p);
     p.q = q.data_ptr(); p.k_cache = k_cache.data_ptr(); p.v_cache = v_cache.data_ptr(); p.o = o.data_ptr(); p.lse = l.data_ptr<float>();
-    p.cache_seqlens = cache_seqlens.defined() ? cache_seqlens.data_ptr<int32_t>() : nullptr;
     p.b = (int32_t)batch_size; p.seqlen_q = (int32_t)seqlen_q; p.seqlen_cache = (int32_t)seqlen_cache;
     p.h = (int32_t)num_heads; p.h_k = (int32_t)num_heads_k; p.d = (int32_t)head_size;
     p.dtype = fa_dtype_of(q); p.is_causal = is_causal; p.num_splits = (int32_t)num_splits;
     p.q_stride = strides4(q); p.k_cache_stride = strides4(k_cache); p.v_cache_stride = strides4(v_cache); p.o_stride = strides4(o);
-    if (block_table.defined()) {
-        p.block_table = block_table.data_ptr<int32_t>();
-        // (a one-row table's row stride is never used; a view may report anything there)
-        p.block_table_stride = batch_size > 1 ? block_table.stride(0) : std::max<int64_t>(block_table.stride(0), block_table.size(1));
-        p.page_block_size = (int32_t)k_cache.size(1); p.num_blocks = (int32_t)k_cache.size(0);
-    }
     if (k_new.defined()) {
         // (ragged: the largest append the call allows - no sequence can append more rows than there are, or than its capacity holds)
         p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr(); p.seqlen_new = (int32_t)(ragged ? std::min<int64_t>(k_new.size(1), seqlen_cache) : k_new.size(1));
@@ -392,13 +416,10 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
     }
     fa_kvcache_options_v8 opt;
     FA_PARAMS_INIT(opt);
-    // (rounded once to fp32; 0 means "the default" in the C ABI, so a given scale that is or rounds to 0 is refused here)
-    TORCH_CHECK(!softmax_scale.has_value() || (std::isfinite(*softmax_scale) && (float)*softmax_scale > 0.f && std::isfinite((float)*softmax_scale)),
-                "softmax_scale must be a finite fp32 value > 0 (or None = 1 / sqrt(head_dim))");
+    opt.softmax_scale = softmax_scale_fp32(softmax_scale, "1 / sqrt(head_dim)");
     TORCH_CHECK(std::isfinite(softcap) && softcap >= 0.0 && std::isfinite((float)softcap) && (softcap == 0.0 || (float)softcap > 0.f),
                 "softcap must be a finite fp32 value >= 0 (0 = no cap)");
     const bool scaled = softmax_scale.has_value() || softcap != 0.0;
-    if (softmax_scale.has_value()) opt.softmax_scale = (float)*softmax_scale;
     opt.softcap = (float)softcap;
     if (ragged) {
         opt.cu_seqlens_q = cu_seqlens_q.data_ptr<int32_t>(); opt.total_q = total_q;
@@ -461,13 +482,7 @@ std::vector<at::Tensor> mha_fwd_kvcache(at::Tensor q, at::Tensor k_cache, at::Te
     }
     if (prefill) opt.row_tile = 64;
     const fa_kvcache_options* opts = (opt.is_local || fp8 || rotary_cos.defined() || ragged || scaled || sinks.defined() || tree_mask.defined() || prefill) ? (const fa_kvcache_options*)&opt : nullptr;
-    at::Tensor workspace;
-    const int64_t ws_bytes = fa_kvcache_workspace_bytes_ex(&p, opts);
-    if (ws_bytes < 0) check_status((int)ws_bytes);
-    if (ws_bytes > 0) {
-        workspace = torch::empty({ws_bytes / 4}, q.options().dtype(torch::kFloat32));
-        p.workspace = workspace.data_ptr(); p.workspace_bytes = ws_bytes;
-    }
+    at::Tensor workspace = attach_workspace(p, fa_kvcache_workspace_bytes_ex(&p, opts), q);
     check_status(fa_run_mha_fwd_kvcache_ex(&p, opts, current_stream(q)));
     if (ragged) return {o.squeeze(0), l};
     return {o, l};
@@ -478,48 +493,71 @@ static bool mla_cache_is_fp8(const at::Tensor& kv_cache) {
     return (kv_cache.scalar_type() == torch::kUInt8 || kv_cache.scalar_type() == at::ScalarType::Float8_e4m3fn) && kv_cache.dim() == 4 && kv_cache.size(3) == 656;
 }
 
+// ---- what mha_fwd_mla_kvcache and mha_fwd_mla_sparse_kvcache share (PV: fa_mla_params_v2 or fa_mla_sparse_params_v2, which name these fields alike), in the
+// three places where their orders of checks coincide: q and kv_cache; the table and the lengths; q made dense, the outputs and the struct.
+static void check_mla_decode_inputs(const at::Tensor& q, const at::Tensor& kv_cache, int64_t num_splits, int64_t head_dim_v) {
+    TORCH_CHECK(q.dim() == 4 && kv_cache.dim() == 4, "q and kv_cache must be rank-4 tensors");
+    TORCH_CHECK(q.is_cuda() && kv_cache.is_cuda(), "q, kv_cache must be GPU (HIP) tensors");
+    TORCH_CHECK(kv_cache.device() == q.device(), "q, kv_cache must be on the same device");
+    const bool fp8 = mla_cache_is_fp8(kv_cache);
+    TORCH_CHECK(fp8 || kv_cache.scalar_type() == q.scalar_type(), "kv_cache must have the dtype of q, got ", kv_cache.scalar_type());
+    TORCH_CHECK(q.size(1) >= 1 && q.size(2) >= 1, "seqlen_q and the number of heads must be >= 1");
+    TORCH_CHECK(kv_cache.size(2) == 1, "kv_cache must have exactly one head (the latent row)");
+    TORCH_CHECK(fp8 || kv_cache.size(3) == q.size(3), "q / kv_cache head_dim must match");
+    TORCH_CHECK(kv_cache.stride(3) == 1, "kv_cache: last dimension must be contiguous");
+    TORCH_CHECK(num_splits >= 0 && num_splits <= INT32_MAX, "num_splits must be >= 0 (0 = automatic)");
+    TORCH_CHECK(head_dim_v >= 0 && head_dim_v <= INT32_MAX && q.size(3) <= INT32_MAX, "head dims must fit in int32");
+}
+
+// block_table (or the batch of a contiguous cache) and cache_seqlens -> pv; returns the capacity
+template <typename PV>
+static int64_t mla_decode_table_and_lengths(PV& pv, const at::Tensor& q, const at::Tensor& kv_cache, const c10::optional<at::Tensor>& block_table,
+                                            const c10::optional<at::Tensor>& cache_seqlens) {
+    int64_t seqlen_cache = kv_cache.size(1);
+    if (block_table.has_value()) {
+        seqlen_cache = attach_block_table(pv, q, q.size(0), *block_table, kv_cache);
+    } else {
+        TORCH_CHECK(kv_cache.size(0) == q.size(0), "kv_cache batch size must match q");
+    }
+    pv.cache_seqlens = cache_seqlens_ptr(q, q.size(0), cache_seqlens);
+    pv.seqlen_cache = (int32_t)seqlen_cache;
+    return seqlen_cache;
+}
+
+// Under the caller's device guard: q with addressable strides, out (b, sq, h, head_dim_v) and lse (b, h, sq) allocated, and every field of pv the two structs
+// share filled from them.  The cache is never copied.
+template <typename PV>
+static std::vector<at::Tensor> mla_decode_outputs(PV& pv, at::Tensor& q, const at::Tensor& kv_cache, int64_t num_splits, const c10::optional<double>& softmax_scale,
+                                                  int64_t head_dim_v) {
+    q = dense_last(q);
+    const int64_t batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2);
+    at::Tensor o = torch::empty({batch_size, seqlen_q, num_heads, head_dim_v}, q.options());
+    at::Tensor l = torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(torch::kFloat32));
+    pv.kv_format = mla_cache_is_fp8(kv_cache) ? FA_MLA_KV_FP8_ROWS656 : FA_MLA_KV_16BIT;     // (FP8: a 1-byte dtype, so strides4(kv_cache) is in bytes, as the format asks)
+    pv.q = q.data_ptr(); pv.kv_cache = kv_cache.data_ptr(); pv.o = o.data_ptr(); pv.lse = l.data_ptr<float>();
+    pv.b = (int32_t)batch_size; pv.seqlen_q = (int32_t)seqlen_q;
+    pv.h = (int32_t)num_heads; pv.d_qk = (int32_t)q.size(3); pv.d_v = (int32_t)head_dim_v;
+    pv.dtype = fa_dtype_of(q); pv.num_splits = (int32_t)num_splits;
+    pv.softmax_scale = softmax_scale_fp32(softmax_scale, "576 ** -0.5");
+    pv.q_stride = strides4(q); pv.kv_cache_stride = strides4(kv_cache); pv.o_stride = strides4(o);
+    return {o, l};
+}
+
 // MLA decode over a latent KV cache (fa_run_mla_fwd_kvcache): q (b, sq, h, 576), kv_cache (b, capacity, 1, 576) or a page pool (num_blocks,
 // page_block_size, 1, 576) with block_table, kv_new (b, s_new, 1, 576) appended in place; out (b, sq, h, 512) and lse (b, h, sq).  The cache is never
 // copied; lengths and tables are read on the device.  softmax_scale: rounded once to fp32, None = the library's default 576 ** -0.5.
 std::vector<at::Tensor> mha_fwd_mla_kvcache(at::Tensor q, at::Tensor kv_cache, c10::optional<at::Tensor> kv_new_, c10::optional<at::Tensor> cache_seqlens_,
                                             bool is_causal, int64_t num_splits, c10::optional<at::Tensor> block_table_, c10::optional<double> softmax_scale,
                                             int64_t head_dim_v) {
-    TORCH_CHECK(q.dim() == 4 && kv_cache.dim() == 4, "q and kv_cache must be rank-4 tensors");
-    TORCH_CHECK(q.is_cuda() && kv_cache.is_cuda(), "q, kv_cache must be GPU (HIP) tensors");
-    TORCH_CHECK(kv_cache.device() == q.device(), "q, kv_cache must be on the same device");
-    const bool fp8 = mla_cache_is_fp8(kv_cache);
-    TORCH_CHECK(fp8 || kv_cache.scalar_type() == q.scalar_type(), "kv_cache must have the dtype of q, got ", kv_cache.scalar_type());
-    const int64_t batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), head_size = q.size(3);
-    TORCH_CHECK(seqlen_q >= 1 && num_heads >= 1, "seqlen_q and the number of heads must be >= 1");
-    TORCH_CHECK(kv_cache.size(2) == 1, "kv_cache must have exactly one head (the latent row)");
-    TORCH_CHECK(fp8 || kv_cache.size(3) == head_size, "q / kv_cache head_dim must match");
-    TORCH_CHECK(kv_cache.stride(3) == 1, "kv_cache: last dimension must be contiguous");
-    TORCH_CHECK(num_splits >= 0 && num_splits <= INT32_MAX, "num_splits must be >= 0 (0 = automatic)");
-    TORCH_CHECK(head_dim_v >= 0 && head_dim_v <= INT32_MAX && head_size <= INT32_MAX, "head dims must fit in int32");
-    int64_t seqlen_cache = kv_cache.size(1);
-    at::Tensor block_table;
-    if (block_table_.has_value()) {
-        block_table = *block_table_;
-        check_same_device(q, block_table, "block_table");
-        TORCH_CHECK(block_table.scalar_type() == torch::kInt32, "block_table must be an int32 tensor");
-        TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == batch_size, "block_table must have shape [batch_size, max_blocks_per_seq]");
-        TORCH_CHECK(block_table.stride(1) == 1 || block_table.size(1) <= 1, "block_table: last dimension must be contiguous");
-        seqlen_cache = block_table.size(1) * kv_cache.size(1);
-        TORCH_CHECK(kv_cache.size(0) <= INT32_MAX && seqlen_cache <= INT32_MAX, "block_table: pool pages and capacity must fit in int32");
-    } else {
-        TORCH_CHECK(kv_cache.size(0) == batch_size, "kv_cache batch size must match q");
-    }
-    at::Tensor kv_new, cache_seqlens;
-    if (cache_seqlens_.has_value()) {
-        cache_seqlens = *cache_seqlens_;
-        check_same_device(q, cache_seqlens, "cache_seqlens");
-        TORCH_CHECK(cache_seqlens.scalar_type() == torch::kInt32, "cache_seqlens must be an int32 tensor");
-        TORCH_CHECK(cache_seqlens.dim() == 1 && cache_seqlens.size(0) == batch_size && cache_seqlens.is_contiguous(),
-                    "cache_seqlens must be a contiguous tensor of shape [batch_size]");
-    }
+    fa_mla_params_v2 pv;
+    FA_PARAMS_INIT(pv);
+    check_mla_decode_inputs(q, kv_cache, num_splits, head_dim_v);
+    const int64_t seqlen_cache = mla_decode_table_and_lengths(pv, q, kv_cache, block_table_, cache_seqlens_);
+    const int64_t batch_size = q.size(0), head_size = q.size(3);
     c10::DeviceGuard guard(q.device());
+    at::Tensor kv_new;
     if (kv_new_.has_value()) {
-        TORCH_CHECK(cache_seqlens.defined(), "cache_seqlens is required when kv_new is appended");
+        TORCH_CHECK(cache_seqlens_.has_value(), "cache_seqlens is required when kv_new is appended");
         kv_new = *kv_new_;
         TORCH_CHECK(kv_new.dim() == 4, "kv_new must be a rank-4 tensor");
         check_same_device(q, kv_new, "kv_new");
@@ -528,42 +566,68 @@ std::vector<at::Tensor> mha_fwd_mla_kvcache(at::Tensor q, at::Tensor kv_cache, c
         TORCH_CHECK(kv_new.size(1) <= seqlen_cache, "seqlen_new must not exceed the cache capacity");
         kv_new = dense_last(kv_new);
     }
-    q = dense_last(q);
-    at::Tensor o = torch::empty({batch_size, seqlen_q, num_heads, head_dim_v}, q.options());
-    at::Tensor l = torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(torch::kFloat32));
-
-    fa_mla_params_v2 pv;
-    FA_PARAMS_INIT(pv);
-    pv.kv_format = fp8 ? FA_MLA_KV_FP8_ROWS656 : FA_MLA_KV_16BIT;     // (FP8: a 1-byte dtype, so strides4(kv_cache) is in bytes, as the format asks)
-    fa_mla_params& p = reinterpret_cast<fa_mla_params&>(pv);
-    p.q = q.data_ptr(); p.kv_cache = kv_cache.data_ptr(); p.o = o.data_ptr(); p.lse = l.data_ptr<float>();
-    p.cache_seqlens = cache_seqlens.defined() ? cache_seqlens.data_ptr<int32_t>() : nullptr;
-    p.b = (int32_t)batch_size; p.seqlen_q = (int32_t)seqlen_q; p.seqlen_cache = (int32_t)seqlen_cache;
-    p.h = (int32_t)num_heads; p.d_qk = (int32_t)head_size; p.d_v = (int32_t)head_dim_v;
-    p.dtype = fa_dtype_of(q); p.is_causal = is_causal; p.num_splits = (int32_t)num_splits;
-    // (rounded once to fp32; 0 means "the default" in the C ABI, so a given scale that is or rounds to 0 is refused here)
-    TORCH_CHECK(!softmax_scale.has_value() || (std::isfinite(*softmax_scale) && (float)*softmax_scale > 0.f && std::isfinite((float)*softmax_scale)),
-                "softmax_scale must be a finite fp32 value > 0 (or None = 576 ** -0.5)");
-    if (softmax_scale.has_value()) p.softmax_scale = (float)*softmax_scale;
-    p.q_stride = strides4(q); p.kv_cache_stride = strides4(kv_cache); p.o_stride = strides4(o);
-    if (block_table.defined()) {
-        p.block_table = block_table.data_ptr<int32_t>();
-        p.block_table_stride = batch_size > 1 ? block_table.stride(0) : std::max<int64_t>(block_table.stride(0), block_table.size(1));
-        p.page_block_size = (int32_t)kv_cache.size(1); p.num_blocks = (int32_t)kv_cache.size(0);
-    }
+    pv.is_causal = is_causal;
+    std::vector<at::Tensor> out = mla_decode_outputs(pv, q, kv_cache, num_splits, softmax_scale, head_dim_v);
     if (kv_new.defined()) {
-        p.kv_new = kv_new.data_ptr(); p.seqlen_new = (int32_t)kv_new.size(1);
-        p.kv_new_stride = strides4(kv_new);
+        pv.kv_new = kv_new.data_ptr(); pv.seqlen_new = (int32_t)kv_new.size(1);
+        pv.kv_new_stride = strides4(kv_new);
     }
-    at::Tensor workspace;
-    const int64_t ws_bytes = fa_mla_workspace_bytes(&p);
-    if (ws_bytes < 0) check_status((int)ws_bytes);
-    if (ws_bytes > 0) {
-        workspace = torch::empty({ws_bytes / 4}, q.options().dtype(torch::kFloat32));
-        p.workspace = workspace.data_ptr(); p.workspace_bytes = ws_bytes;
-    }
+    fa_mla_params& p = reinterpret_cast<fa_mla_params&>(pv);
+    at::Tensor workspace = attach_workspace(p, fa_mla_workspace_bytes(&p), q);
     check_status(fa_run_mla_fwd_kvcache(&p, current_stream(q)));
-    return {o, l};
+    return out;
+}
+
+// ---- what mha_fwd_mla_prefill and mha_bwd_mla_prefill share: the q / k / v section of their checks (the backward's out / dout / lse checks stand between its
+// two halves) and the fields fa_mla_prefill_params and fa_mla_prefill_bwd_params name alike
+struct MlaPrefillShape {
+    bool packed;
+    int64_t batch_size, rows_q, rows_k, num_heads, num_heads_k;
+};
+
+// cu_seqlens both or neither; q / k / v of the rank that follows, on one GPU, of one dtype.  Returns whether the call is packed.
+static bool check_mla_prefill_qkv(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const c10::optional<at::Tensor>& cu_q, const c10::optional<at::Tensor>& cu_k) {
+    const bool packed = cu_q.has_value() || cu_k.has_value();
+    TORCH_CHECK(cu_q.has_value() == cu_k.has_value(), "cu_seqlens_q and cu_seqlens_k come both or neither");
+    const int64_t rank = packed ? 3 : 4;
+    TORCH_CHECK(q.dim() == rank && k.dim() == rank && v.dim() == rank, "q, k, v must be rank-", rank, " tensors");
+    check_qkv_common(q, k, v);
+    return packed;
+}
+
+static MlaPrefillShape check_mla_prefill_shapes(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, bool packed, const c10::optional<at::Tensor>& cu_q) {
+    const int64_t batch_size = packed ? cu_q->numel() - 1 : q.size(0);
+    const int64_t rows_q = q.size(-3), rows_k = k.size(-3), num_heads = q.size(-2), num_heads_k = k.size(-2);
+    TORCH_CHECK(v.size(-3) == rows_k && v.size(-2) == num_heads_k, "k and v must agree in rows and heads");
+    TORCH_CHECK(packed || (k.size(0) == batch_size && v.size(0) == batch_size), "k/v batch size must match q");
+    TORCH_CHECK(k.size(-1) == q.size(-1), "q / k head_dim must match");
+    TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "num_heads_q must be divisible by num_heads_k for GQA/MQA");
+    TORCH_CHECK(batch_size <= INT32_MAX && (packed || (rows_q <= INT32_MAX && rows_k <= INT32_MAX)) && num_heads <= INT32_MAX && q.size(-1) <= INT32_MAX && v.size(-1) <= INT32_MAX,
+                "sizes must fit in int32");
+    return MlaPrefillShape{packed, batch_size, rows_q, rows_k, num_heads, num_heads_k};
+}
+
+static void check_mla_prefill_cu(const at::Tensor& q, bool packed, const c10::optional<at::Tensor>& cu_q, const c10::optional<at::Tensor>& cu_k) {
+    if (!packed) return;
+    check_cu_seqlens(*cu_q, *cu_k);
+    check_same_device(q, *cu_q, "cu_seqlens_q"); check_same_device(q, *cu_k, "cu_seqlens_k");
+}
+
+// o: the forward's output, allocated (forward) or given (backward); lse likewise.  Nothing is copied.
+template <typename P>
+static void fill_mla_prefill(P& p, const MlaPrefillShape& s, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o, const at::Tensor& lse,
+                             const c10::optional<at::Tensor>& cu_q, const c10::optional<at::Tensor>& cu_k, bool is_causal, const c10::optional<double>& softmax_scale) {
+    p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = o.data_ptr(); p.lse = lse.data_ptr<float>();
+    p.b = (int32_t)s.batch_size; p.h = (int32_t)s.num_heads; p.h_k = (int32_t)s.num_heads_k; p.d_qk = (int32_t)q.size(-1); p.d_v = (int32_t)v.size(-1);
+    p.dtype = fa_dtype_of(q); p.is_causal = is_causal;
+    p.softmax_scale = softmax_scale_fp32(softmax_scale, "192 ** -0.5");
+    if (s.packed) {
+        p.cu_seqlens_q = cu_q->data_ptr<int32_t>(); p.cu_seqlens_k = cu_k->data_ptr<int32_t>();
+        p.total_q = s.rows_q; p.total_k = s.rows_k;
+    } else {
+        p.seqlen_q = (int32_t)s.rows_q; p.seqlen_k = (int32_t)s.rows_k;
+    }
+    p.q_stride = strides34(q); p.k_stride = strides34(k); p.v_stride = strides34(v); p.o_stride = strides34(o);
 }
 
 // MLA prefill attention (fa_run_mla_prefill_fwd): dense q (b, sq, h, 192), k (b, sk, h_k, 192), v (b, sk, h_k, 128) -> out (b, sq, h, 128), lse (b, h, sq);
@@ -572,48 +636,18 @@ std::vector<at::Tensor> mha_fwd_mla_kvcache(at::Tensor q, at::Tensor kv_cache, c
 // the library's default 192 ** -0.5.
 std::vector<at::Tensor> mha_fwd_mla_prefill(at::Tensor q, at::Tensor k, at::Tensor v, c10::optional<at::Tensor> cu_seqlens_q_, c10::optional<at::Tensor> cu_seqlens_k_,
                                             bool is_causal, c10::optional<double> softmax_scale) {
-    const bool packed = cu_seqlens_q_.has_value() || cu_seqlens_k_.has_value();
-    TORCH_CHECK(cu_seqlens_q_.has_value() == cu_seqlens_k_.has_value(), "cu_seqlens_q and cu_seqlens_k come both or neither");
-    const int64_t rank = packed ? 3 : 4;
-    TORCH_CHECK(q.dim() == rank && k.dim() == rank && v.dim() == rank, "q, k, v must be rank-", rank, " tensors");
-    check_qkv_common(q, k, v);
-    const int64_t batch_size = packed ? cu_seqlens_q_->numel() - 1 : q.size(0);
-    const int64_t rows_q = q.size(-3), rows_k = k.size(-3), num_heads = q.size(-2), num_heads_k = k.size(-2);
-    TORCH_CHECK(v.size(-3) == rows_k && v.size(-2) == num_heads_k, "k and v must agree in rows and heads");
-    TORCH_CHECK(packed || (k.size(0) == batch_size && v.size(0) == batch_size), "k/v batch size must match q");
-    TORCH_CHECK(k.size(-1) == q.size(-1), "q / k head_dim must match");
-    TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "num_heads_q must be divisible by num_heads_k for GQA/MQA");
-    TORCH_CHECK(batch_size <= INT32_MAX && (packed || (rows_q <= INT32_MAX && rows_k <= INT32_MAX)) && num_heads <= INT32_MAX && q.size(-1) <= INT32_MAX && v.size(-1) <= INT32_MAX,
-                "sizes must fit in int32");
-    at::Tensor cu_q, cu_k;
-    if (packed) {
-        cu_q = *cu_seqlens_q_; cu_k = *cu_seqlens_k_;
-        check_cu_seqlens(cu_q, cu_k);
-        check_same_device(q, cu_q, "cu_seqlens_q"); check_same_device(q, cu_k, "cu_seqlens_k");
-    }
+    const bool packed = check_mla_prefill_qkv(q, k, v, cu_seqlens_q_, cu_seqlens_k_);
+    const MlaPrefillShape s = check_mla_prefill_shapes(q, k, v, packed, cu_seqlens_q_);
+    check_mla_prefill_cu(q, packed, cu_seqlens_q_, cu_seqlens_k_);
     c10::DeviceGuard guard(q.device());
     // dense: every element of o and l is written (dead rows included); packed: the rows past cu_seqlens_q[-1] are not touched
-    at::Tensor o = packed ? torch::empty({rows_q, num_heads, v.size(-1)}, q.options()) : torch::empty({batch_size, rows_q, num_heads, v.size(-1)}, q.options());
-    at::Tensor l = packed ? torch::empty({num_heads, rows_q}, q.options().dtype(torch::kFloat32))
-                          : torch::empty({batch_size, num_heads, rows_q}, q.options().dtype(torch::kFloat32));
+    at::Tensor o = packed ? torch::empty({s.rows_q, s.num_heads, v.size(-1)}, q.options()) : torch::empty({s.batch_size, s.rows_q, s.num_heads, v.size(-1)}, q.options());
+    at::Tensor l = packed ? torch::empty({s.num_heads, s.rows_q}, q.options().dtype(torch::kFloat32))
+                          : torch::empty({s.batch_size, s.num_heads, s.rows_q}, q.options().dtype(torch::kFloat32));
 
     fa_mla_prefill_params p;
     FA_PARAMS_INIT(p);
-    p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = o.data_ptr(); p.lse = l.data_ptr<float>();
-    p.b = (int32_t)batch_size; p.h = (int32_t)num_heads; p.h_k = (int32_t)num_heads_k; p.d_qk = (int32_t)q.size(-1); p.d_v = (int32_t)v.size(-1);
-    p.dtype = fa_dtype_of(q); p.is_causal = is_causal;
-    // (rounded once to fp32; 0 means "the default" in the C ABI, so a given scale that is or rounds to 0 is refused here)
-    TORCH_CHECK(!softmax_scale.has_value() || (std::isfinite(*softmax_scale) && (float)*softmax_scale > 0.f && std::isfinite((float)*softmax_scale)),
-                "softmax_scale must be a finite fp32 value > 0 (or None = 192 ** -0.5)");
-    if (softmax_scale.has_value()) p.softmax_scale = (float)*softmax_scale;
-    if (packed) {
-        p.cu_seqlens_q = cu_q.data_ptr<int32_t>(); p.cu_seqlens_k = cu_k.data_ptr<int32_t>();
-        p.total_q = rows_q; p.total_k = rows_k;
-        p.q_stride = strides3(q); p.k_stride = strides3(k); p.v_stride = strides3(v); p.o_stride = strides3(o);
-    } else {
-        p.seqlen_q = (int32_t)rows_q; p.seqlen_k = (int32_t)rows_k;
-        p.q_stride = strides4(q); p.k_stride = strides4(k); p.v_stride = strides4(v); p.o_stride = strides4(o);
-    }
+    fill_mla_prefill(p, s, q, k, v, o, l, cu_seqlens_q_, cu_seqlens_k_, is_causal, softmax_scale);
     check_status(fa_run_mla_prefill_fwd(&p, current_stream(q)));
     return {o, l};
 }
@@ -660,33 +694,18 @@ std::vector<at::Tensor> merge_states(std::vector<at::Tensor> outs, std::vector<a
 std::vector<at::Tensor> mha_bwd_mla_prefill(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor out, at::Tensor lse, c10::optional<at::Tensor> cu_seqlens_q_,
                                             c10::optional<at::Tensor> cu_seqlens_k_, bool is_causal, c10::optional<double> softmax_scale, int64_t phases,
                                             c10::optional<at::Tensor> dsoftmax_sum_) {
-    const bool packed = cu_seqlens_q_.has_value() || cu_seqlens_k_.has_value();
-    TORCH_CHECK(cu_seqlens_q_.has_value() == cu_seqlens_k_.has_value(), "cu_seqlens_q and cu_seqlens_k come both or neither");
-    const int64_t rank = packed ? 3 : 4;
-    TORCH_CHECK(q.dim() == rank && k.dim() == rank && v.dim() == rank, "q, k, v must be rank-", rank, " tensors");
-    check_qkv_common(q, k, v);
+    const bool packed = check_mla_prefill_qkv(q, k, v, cu_seqlens_q_, cu_seqlens_k_);
     check_same_device(q, out, "out"); check_same_device(q, dout, "dout"); check_same_device(q, lse, "lse");
     TORCH_CHECK(out.scalar_type() == q.scalar_type() && dout.scalar_type() == q.scalar_type(), "out and dout must have the dtype of q");
-    const int64_t batch_size = packed ? cu_seqlens_q_->numel() - 1 : q.size(0);
-    const int64_t rows_q = q.size(-3), rows_k = k.size(-3), num_heads = q.size(-2), num_heads_k = k.size(-2);
-    TORCH_CHECK(v.size(-3) == rows_k && v.size(-2) == num_heads_k, "k and v must agree in rows and heads");
-    TORCH_CHECK(packed || (k.size(0) == batch_size && v.size(0) == batch_size), "k/v batch size must match q");
-    TORCH_CHECK(k.size(-1) == q.size(-1), "q / k head_dim must match");
-    TORCH_CHECK(num_heads_k > 0 && num_heads % num_heads_k == 0, "num_heads_q must be divisible by num_heads_k for GQA/MQA");
-    TORCH_CHECK(batch_size <= INT32_MAX && (packed || (rows_q <= INT32_MAX && rows_k <= INT32_MAX)) && num_heads <= INT32_MAX && q.size(-1) <= INT32_MAX && v.size(-1) <= INT32_MAX,
-                "sizes must fit in int32");
+    const MlaPrefillShape s = check_mla_prefill_shapes(q, k, v, packed, cu_seqlens_q_);
+    const int64_t batch_size = s.batch_size, rows_q = s.rows_q, num_heads = s.num_heads;
     std::vector<int64_t> o_shape = q.sizes().vec();
     o_shape.back() = v.size(-1);
     TORCH_CHECK(out.sizes() == at::IntArrayRef(o_shape) && dout.sizes() == at::IntArrayRef(o_shape), "out and dout must have the shape of the forward's out");
     std::vector<int64_t> l_shape = packed ? std::vector<int64_t>{num_heads, rows_q} : std::vector<int64_t>{batch_size, num_heads, rows_q};
     TORCH_CHECK(lse.scalar_type() == torch::kFloat32 && lse.is_contiguous() && lse.sizes() == at::IntArrayRef(l_shape), "lse must be the forward's: fp32, contiguous, (b, h, seqlen_q) or (h, total_q)");
     TORCH_CHECK(phases >= 0 && phases <= 2, "phases: 0 (both launches), 1 (dq) or 2 (dk / dv)");
-    at::Tensor cu_q, cu_k;
-    if (packed) {
-        cu_q = *cu_seqlens_q_; cu_k = *cu_seqlens_k_;
-        check_cu_seqlens(cu_q, cu_k);
-        check_same_device(q, cu_q, "cu_seqlens_q"); check_same_device(q, cu_k, "cu_seqlens_k");
-    }
+    check_mla_prefill_cu(q, packed, cu_seqlens_q_, cu_seqlens_k_);
     c10::DeviceGuard guard(q.device());
     // dense: every element of dq / dk / dv is written; packed: the rows past cu_seqlens[-1] are not touched.  Without a query row nothing is launched and
     // dk / dv are zero by definition.
@@ -704,23 +723,10 @@ std::vector<at::Tensor> mha_bwd_mla_prefill(at::Tensor dout, at::Tensor q, at::T
 
     fa_mla_prefill_bwd_params p;
     FA_PARAMS_INIT(p);
-    p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = out.data_ptr(); p.lse = lse.data_ptr<float>(); p.dout = dout.data_ptr();
-    p.dq = dq.data_ptr(); p.dk = dk.data_ptr(); p.dv = dv.data_ptr(); p.dsoftmax_sum = dsum.data_ptr<float>();
-    p.b = (int32_t)batch_size; p.h = (int32_t)num_heads; p.h_k = (int32_t)num_heads_k; p.d_qk = (int32_t)q.size(-1); p.d_v = (int32_t)v.size(-1);
-    p.dtype = fa_dtype_of(q); p.is_causal = is_causal; p.phases = (int32_t)phases;
-    TORCH_CHECK(!softmax_scale.has_value() || (std::isfinite(*softmax_scale) && (float)*softmax_scale > 0.f && std::isfinite((float)*softmax_scale)),
-                "softmax_scale must be a finite fp32 value > 0 (or None = 192 ** -0.5)");
-    if (softmax_scale.has_value()) p.softmax_scale = (float)*softmax_scale;
-    if (packed) {
-        p.cu_seqlens_q = cu_q.data_ptr<int32_t>(); p.cu_seqlens_k = cu_k.data_ptr<int32_t>();
-        p.total_q = rows_q; p.total_k = rows_k;
-        p.q_stride = strides3(q); p.k_stride = strides3(k); p.v_stride = strides3(v); p.o_stride = strides3(out); p.dout_stride = strides3(dout);
-        p.dq_stride = strides3(dq); p.dk_stride = strides3(dk); p.dv_stride = strides3(dv);
-    } else {
-        p.seqlen_q = (int32_t)rows_q; p.seqlen_k = (int32_t)rows_k;
-        p.q_stride = strides4(q); p.k_stride = strides4(k); p.v_stride = strides4(v); p.o_stride = strides4(out); p.dout_stride = strides4(dout);
-        p.dq_stride = strides4(dq); p.dk_stride = strides4(dk); p.dv_stride = strides4(dv);
-    }
+    p.dout = dout.data_ptr(); p.dq = dq.data_ptr(); p.dk = dk.data_ptr(); p.dv = dv.data_ptr(); p.dsoftmax_sum = dsum.data_ptr<float>();
+    p.phases = (int32_t)phases;
+    fill_mla_prefill(p, s, q, k, v, out, lse, cu_seqlens_q_, cu_seqlens_k_, is_causal, softmax_scale);
+    p.dout_stride = strides34(dout); p.dq_stride = strides34(dq); p.dk_stride = strides34(dk); p.dv_stride = strides34(dv);
     check_status(fa_run_mla_prefill_bwd(&p, current_stream(q)));
     return {dq, dk, dv, dsum};
 }
@@ -730,78 +736,22 @@ std::vector<at::Tensor> mha_bwd_mla_prefill(at::Tensor dout, at::Tensor q, at::T
 // Indices, lengths and tables are read on the device.
 std::vector<at::Tensor> mha_fwd_mla_sparse_kvcache(at::Tensor q, at::Tensor kv_cache, at::Tensor indices, c10::optional<at::Tensor> cache_seqlens_, int64_t num_splits,
                                                    c10::optional<at::Tensor> block_table_, c10::optional<double> softmax_scale, int64_t head_dim_v) {
-    TORCH_CHECK(q.dim() == 4 && kv_cache.dim() == 4, "q and kv_cache must be rank-4 tensors");
-    TORCH_CHECK(q.is_cuda() && kv_cache.is_cuda(), "q, kv_cache must be GPU (HIP) tensors");
-    TORCH_CHECK(kv_cache.device() == q.device(), "q, kv_cache must be on the same device");
-    const bool fp8 = mla_cache_is_fp8(kv_cache);
-    TORCH_CHECK(fp8 || kv_cache.scalar_type() == q.scalar_type(), "kv_cache must have the dtype of q, got ", kv_cache.scalar_type());
-    const int64_t batch_size = q.size(0), seqlen_q = q.size(1), num_heads = q.size(2), head_size = q.size(3);
-    TORCH_CHECK(seqlen_q >= 1 && num_heads >= 1, "seqlen_q and the number of heads must be >= 1");
-    TORCH_CHECK(kv_cache.size(2) == 1, "kv_cache must have exactly one head (the latent row)");
-    TORCH_CHECK(fp8 || kv_cache.size(3) == head_size, "q / kv_cache head_dim must match");
-    TORCH_CHECK(kv_cache.stride(3) == 1, "kv_cache: last dimension must be contiguous");
-    TORCH_CHECK(num_splits >= 0 && num_splits <= INT32_MAX, "num_splits must be >= 0 (0 = automatic)");
-    TORCH_CHECK(head_dim_v >= 0 && head_dim_v <= INT32_MAX && head_size <= INT32_MAX, "head dims must fit in int32");
-    check_same_device(q, indices, "indices");
-    TORCH_CHECK(indices.scalar_type() == torch::kInt32, "indices must be an int32 tensor");
-    TORCH_CHECK(indices.dim() == 3 && indices.size(0) == batch_size && indices.size(1) == seqlen_q, "indices must have shape [batch_size, seqlen_q, topk]");
-    TORCH_CHECK(indices.size(2) >= 1 && indices.size(2) <= INT32_MAX && indices.stride(2) == 1, "indices: topk must be >= 1 and the last dimension contiguous");
-    int64_t seqlen_cache = kv_cache.size(1);
-    at::Tensor block_table;
-    if (block_table_.has_value()) {
-        block_table = *block_table_;
-        check_same_device(q, block_table, "block_table");
-        TORCH_CHECK(block_table.scalar_type() == torch::kInt32, "block_table must be an int32 tensor");
-        TORCH_CHECK(block_table.dim() == 2 && block_table.size(0) == batch_size, "block_table must have shape [batch_size, max_blocks_per_seq]");
-        TORCH_CHECK(block_table.stride(1) == 1 || block_table.size(1) <= 1, "block_table: last dimension must be contiguous");
-        seqlen_cache = block_table.size(1) * kv_cache.size(1);
-        TORCH_CHECK(kv_cache.size(0) <= INT32_MAX && seqlen_cache <= INT32_MAX, "block_table: pool pages and capacity must fit in int32");
-    } else {
-        TORCH_CHECK(kv_cache.size(0) == batch_size, "kv_cache batch size must match q");
-    }
-    at::Tensor cache_seqlens;
-    if (cache_seqlens_.has_value()) {
-        cache_seqlens = *cache_seqlens_;
-        check_same_device(q, cache_seqlens, "cache_seqlens");
-        TORCH_CHECK(cache_seqlens.scalar_type() == torch::kInt32, "cache_seqlens must be an int32 tensor");
-        TORCH_CHECK(cache_seqlens.dim() == 1 && cache_seqlens.size(0) == batch_size && cache_seqlens.is_contiguous(),
-                    "cache_seqlens must be a contiguous tensor of shape [batch_size]");
-    }
-    c10::DeviceGuard guard(q.device());
-    q = dense_last(q);
-    at::Tensor o = torch::empty({batch_size, seqlen_q, num_heads, head_dim_v}, q.options());
-    at::Tensor l = torch::empty({batch_size, num_heads, seqlen_q}, q.options().dtype(torch::kFloat32));
-
     fa_mla_sparse_params_v2 pv;
     FA_PARAMS_INIT(pv);
-    pv.kv_format = fp8 ? FA_MLA_KV_FP8_ROWS656 : FA_MLA_KV_16BIT;     // (FP8: a 1-byte dtype, so strides4(kv_cache) is in bytes, as the format asks)
+    check_mla_decode_inputs(q, kv_cache, num_splits, head_dim_v);
+    check_same_device(q, indices, "indices");
+    TORCH_CHECK(indices.scalar_type() == torch::kInt32, "indices must be an int32 tensor");
+    TORCH_CHECK(indices.dim() == 3 && indices.size(0) == q.size(0) && indices.size(1) == q.size(1), "indices must have shape [batch_size, seqlen_q, topk]");
+    TORCH_CHECK(indices.size(2) >= 1 && indices.size(2) <= INT32_MAX && indices.stride(2) == 1, "indices: topk must be >= 1 and the last dimension contiguous");
+    mla_decode_table_and_lengths(pv, q, kv_cache, block_table_, cache_seqlens_);
+    c10::DeviceGuard guard(q.device());
+    pv.indices = indices.data_ptr<int32_t>(); pv.topk = (int32_t)indices.size(2);
+    pv.indices_batch_stride = indices.stride(0); pv.indices_row_stride = indices.stride(1);
+    std::vector<at::Tensor> out = mla_decode_outputs(pv, q, kv_cache, num_splits, softmax_scale, head_dim_v);
     fa_mla_sparse_params& p = reinterpret_cast<fa_mla_sparse_params&>(pv);
-    p.q = q.data_ptr(); p.kv_cache = kv_cache.data_ptr(); p.o = o.data_ptr(); p.lse = l.data_ptr<float>();
-    p.cache_seqlens = cache_seqlens.defined() ? cache_seqlens.data_ptr<int32_t>() : nullptr;
-    p.indices = indices.data_ptr<int32_t>(); p.topk = (int32_t)indices.size(2);
-    p.indices_batch_stride = indices.stride(0); p.indices_row_stride = indices.stride(1);
-    p.b = (int32_t)batch_size; p.seqlen_q = (int32_t)seqlen_q; p.seqlen_cache = (int32_t)seqlen_cache;
-    p.h = (int32_t)num_heads; p.d_qk = (int32_t)head_size; p.d_v = (int32_t)head_dim_v;
-    p.dtype = fa_dtype_of(q); p.num_splits = (int32_t)num_splits;
-    // (rounded once to fp32; 0 means "the default" in the C ABI, so a given scale that is or rounds to 0 is refused here)
-    TORCH_CHECK(!softmax_scale.has_value() || (std::isfinite(*softmax_scale) && (float)*softmax_scale > 0.f && std::isfinite((float)*softmax_scale)),
-                "softmax_scale must be a finite fp32 value > 0 (or None = 576 ** -0.5)");
-    if (softmax_scale.has_value()) p.softmax_scale = (float)*softmax_scale;
-    p.q_stride = strides4(q); p.kv_cache_stride = strides4(kv_cache); p.o_stride = strides4(o);
-    if (block_table.defined()) {
-        p.block_table = block_table.data_ptr<int32_t>();
-        p.block_table_stride = batch_size > 1 ? block_table.stride(0) : std::max<int64_t>(block_table.stride(0), block_table.size(1));
-        p.page_block_size = (int32_t)kv_cache.size(1); p.num_blocks = (int32_t)kv_cache.size(0);
-    }
-    at::Tensor workspace;
-    const int64_t ws_bytes = fa_mla_sparse_workspace_bytes(&p);
-    if (ws_bytes < 0) check_status((int)ws_bytes);
-    if (ws_bytes > 0) {
-        workspace = torch::empty({ws_bytes / 4}, q.options().dtype(torch::kFloat32));
-        p.workspace = workspace.data_ptr(); p.workspace_bytes = ws_bytes;
-    }
+    at::Tensor workspace = attach_workspace(p, fa_mla_sparse_workspace_bytes(&p), q);
     check_status(fa_run_mla_sparse_fwd_kvcache(&p, current_stream(q)));
-    return {o, l};
+    return out;
 }
 
 // The DeepSeek-V3.2 indexer (fa_run_mla_indexer_logits / fa_run_mla_indexer_topk).  The Python layer has checked shapes and views; here the tensors become
@@ -822,17 +772,7 @@ void mla_indexer_logits(at::Tensor q_idx, at::Tensor weights, at::Tensor k_idx_c
     c10::DeviceGuard guard(q_idx.device());
     fa_mla_indexer_params p;
     FA_PARAMS_INIT(p);
-    if (block_table_.has_value()) {
-        const at::Tensor& bt = *block_table_;
-        check_same_device(q_idx, bt, "block_table");
-        TORCH_CHECK(bt.scalar_type() == torch::kInt32 && bt.dim() == 2 && bt.size(0) == batch_size, "block_table must be int32 [batch_size, max_blocks_per_seq]");
-        TORCH_CHECK(bt.stride(1) == 1 || bt.size(1) <= 1, "block_table: last dimension must be contiguous");
-        seqlen_cache = bt.size(1) * k_idx_cache.size(1);
-        TORCH_CHECK(k_idx_cache.size(0) <= INT32_MAX && seqlen_cache <= INT32_MAX, "block_table: pool pages and capacity must fit in int32");
-        p.block_table = bt.data_ptr<int32_t>();
-        p.block_table_stride = batch_size > 1 ? bt.stride(0) : std::max<int64_t>(bt.stride(0), bt.size(1));
-        p.page_block_size = (int32_t)k_idx_cache.size(1); p.num_blocks = (int32_t)k_idx_cache.size(0);
-    }
+    if (block_table_.has_value()) seqlen_cache = attach_block_table(p, q_idx, batch_size, *block_table_, k_idx_cache, true);
     TORCH_CHECK(logits.size(0) == batch_size && logits.size(1) == seqlen_q && logits.size(2) == seqlen_cache, "logits must have shape [batch_size, seqlen_q, capacity]");
     p.q_idx = q_idx.data_ptr(); p.weights = weights.data_ptr<float>(); p.k_idx_cache = k_idx_cache.data_ptr(); p.logits = logits.data_ptr<float>();
     p.cache_seqlens = cache_seqlens.data_ptr<int32_t>();

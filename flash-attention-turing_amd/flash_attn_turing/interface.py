@@ -613,6 +613,71 @@ def dequantize_mla_kv_cache(kv8, dtype):
     return out
 
 
+# ---- argument rules the MLA decode calls and the indexer share: each is stated here once.  The exception type, the words and the place of a check in a call's
+# order are part of the interface (tests and callers match on them); what differs between the calls is a parameter.
+
+def _check_block_table(block_table, q, pool, like="q", pool_name="kv_cache", need_column=False):
+    """block_table (or None) of a call whose queries are ``q`` (called ``like``) over the cache / page pool ``pool`` (called ``pool_name``); returns the capacity.
+    need_column: the indexer sizes its logits by the capacity and refuses a table without columns; the MLA calls leave that to the library."""
+    b = q.shape[0]
+    if block_table is None:
+        if pool.shape[0] != b:
+            raise ValueError(f"{pool_name} batch ({pool.shape[0]}) must match {like}'s ({b})")
+        return pool.shape[1]
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
+        raise ValueError("block_table must be an int32 tensor")
+    if block_table.dim() != 2 or block_table.shape[0] != b or block_table.device != q.device:
+        raise ValueError(f"block_table must have shape (batch, max_blocks_per_seq) on {like}'s device")
+    if pool.shape[1] < 1 or pool.shape[1] % 16 != 0:
+        raise ValueError(f"page_block_size ({pool_name}.shape[1] with block_table) must be a positive multiple of 16, got {pool.shape[1]}")
+    if need_column and block_table.shape[1] < 1:
+        raise ValueError("block_table needs at least one column")
+    return block_table.shape[1] * pool.shape[1]
+
+
+def _check_cache_seqlens(cache_seqlens, b, device, like="q"):
+    """cache_seqlens: an int32 tensor (batch,) on the device of the tensor called ``like``, or an int (not a bool).  Making a tensor of an int is the caller's."""
+    if isinstance(cache_seqlens, bool) or not isinstance(cache_seqlens, (int, torch.Tensor)) or (
+            isinstance(cache_seqlens, torch.Tensor) and (cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (b,) or cache_seqlens.device != device)):
+        raise ValueError(f"cache_seqlens must be an int32 tensor (batch,) on {like}'s device or an int")
+
+
+def _check_num_splits(num_splits):
+    if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
+        raise ValueError(f"num_splits must be an int >= 0 (0 = chosen by the library), got {num_splits!r}")
+
+
+def _check_mla_decode_inputs(fn, q, kv_cache, head_dim_v, block_table, kv_new=None):
+    """what flash_mla_with_kvcache and flash_mla_sparse_with_kvcache (``fn``) check alike, in their order: q, head_dim_v, kv_cache (16-bit or FP8 rows) and
+    block_table; returns the batch.  kv_new only counts into the forward-only check here: its own checks are the dense call's."""
+    for name, t in (("q", q), ("kv_cache", kv_cache)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 4:
+            raise ValueError(f"{name} must be a rank-4 tensor")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, kv_cache, kv_new if isinstance(kv_new, torch.Tensor) else None)):
+        raise RuntimeError(f"{fn} is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"q must be fp16 or bf16, got {q.dtype}")
+    if q.shape[-1] != 576:
+        raise ValueError(f"q must be 576 wide (512 absorbed no-rope columns, then 64 rope columns), got head_dim {q.shape[-1]}")
+    if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int) or head_dim_v != 512:
+        raise ValueError(f"head_dim_v must be 512, got {head_dim_v!r}")
+    if q.shape[1] < 1 or q.shape[2] < 1:
+        raise ValueError(f"q needs seqlen_q >= 1 and nheads >= 1, got shape {tuple(q.shape)}")
+    fp8 = _mla_cache_is_fp8(kv_cache)
+    if not fp8 and kv_cache.dtype != q.dtype:
+        raise ValueError(f"kv_cache must have q's dtype ({q.dtype}), got {kv_cache.dtype} (an FP8 latent cache is uint8 / float8_e4m3fn rows of 656 bytes)")
+    if kv_cache.shape[2] != 1:
+        raise ValueError(f"kv_cache must have exactly one head (the latent row), got {kv_cache.shape[2]}")
+    if not fp8 and kv_cache.shape[3] != 576:
+        raise ValueError(f"kv_cache must be 576 wide, got {kv_cache.shape[3]}")
+    if fp8:
+        _check_mla_fp8_view(kv_cache)
+    if kv_cache.device != q.device:
+        raise ValueError("kv_cache must be on q's device")
+    _check_block_table(block_table, q, kv_cache)
+    return q.shape[0]
+
+
 def flash_mla_with_kvcache(q, kv_cache, cache_seqlens, *, head_dim_v=512, kv_new=None, block_table=None, softmax_scale=None, causal=False, num_splits=0,
                            return_softmax_lse=False):
     """Multi-head latent attention (MLA) decode over a latent KV cache (DeepSeek-V2 / V3 / R1, Kimi K2; forward only).
@@ -650,54 +715,17 @@ def flash_mla_with_kvcache(q, kv_cache, cache_seqlens, *, head_dim_v=512, kv_new
     Out of scope, and without a keyword here: cu_seqlens_q, window_size, softcap, sinks, tree_mask, rotary inside the call, other
     head dims, any backward.  Wrong shapes, dtypes or values are a ValueError that names the argument.
     """
-    for name, t in (("q", q), ("kv_cache", kv_cache)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 4:
-            raise ValueError(f"{name} must be a rank-4 tensor")
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, kv_cache, kv_new if isinstance(kv_new, torch.Tensor) else None)):
-        raise RuntimeError("flash_mla_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
-    if q.dtype not in (torch.float16, torch.bfloat16):
-        raise ValueError(f"q must be fp16 or bf16, got {q.dtype}")
-    if q.shape[-1] != 576:
-        raise ValueError(f"q must be 576 wide (512 absorbed no-rope columns, then 64 rope columns), got head_dim {q.shape[-1]}")
-    if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int) or head_dim_v != 512:
-        raise ValueError(f"head_dim_v must be 512, got {head_dim_v!r}")
-    if q.shape[1] < 1 or q.shape[2] < 1:
-        raise ValueError(f"q needs seqlen_q >= 1 and nheads >= 1, got shape {tuple(q.shape)}")
-    fp8 = _mla_cache_is_fp8(kv_cache)
-    if not fp8 and kv_cache.dtype != q.dtype:
-        raise ValueError(f"kv_cache must have q's dtype ({q.dtype}), got {kv_cache.dtype} (an FP8 latent cache is uint8 / float8_e4m3fn rows of 656 bytes)")
-    if kv_cache.shape[2] != 1:
-        raise ValueError(f"kv_cache must have exactly one head (the latent row), got {kv_cache.shape[2]}")
-    if not fp8 and kv_cache.shape[3] != 576:
-        raise ValueError(f"kv_cache must be 576 wide, got {kv_cache.shape[3]}")
-    if fp8:
-        _check_mla_fp8_view(kv_cache)
-    if kv_cache.device != q.device:
-        raise ValueError("kv_cache must be on q's device")
-    b = q.shape[0]
-    if block_table is not None:
-        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
-            raise ValueError("block_table must be an int32 tensor")
-        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.device != q.device:
-            raise ValueError("block_table must have shape (batch, max_blocks_per_seq) on q's device")
-        if kv_cache.shape[1] < 1 or kv_cache.shape[1] % 16 != 0:
-            raise ValueError(f"page_block_size (kv_cache.shape[1] with block_table) must be a positive multiple of 16, got {kv_cache.shape[1]}")
-    elif kv_cache.shape[0] != b:
-        raise ValueError(f"kv_cache batch ({kv_cache.shape[0]}) must match q's ({b})")
+    b = _check_mla_decode_inputs("flash_mla_with_kvcache", q, kv_cache, head_dim_v, block_table, kv_new)
     if kv_new is not None:
         if not isinstance(kv_new, torch.Tensor) or kv_new.dim() != 4 or kv_new.dtype != q.dtype or kv_new.device != q.device:
             raise ValueError("kv_new must be a rank-4 tensor of q's dtype on q's device")
         if kv_new.shape[0] != b or kv_new.shape[2] != 1 or kv_new.shape[3] != 576:
             raise ValueError(f"kv_new must have shape (batch, s_new, 1, 576), got {tuple(kv_new.shape)}")
-    if isinstance(cache_seqlens, bool) or not isinstance(cache_seqlens, (int, torch.Tensor)):
-        raise ValueError("cache_seqlens must be an int32 tensor (batch,) on q's device or an int")
-    if isinstance(cache_seqlens, torch.Tensor) and (cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (b,) or cache_seqlens.device != q.device):
-        raise ValueError("cache_seqlens must be an int32 tensor (batch,) on q's device or an int")
+    _check_cache_seqlens(cache_seqlens, b, q.device)
     softmax_scale, _ = _check_scale_and_cap(softmax_scale, 0.0)
     if not isinstance(causal, bool):
         raise ValueError(f"causal must be a bool, got {causal!r}")
-    if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
-        raise ValueError(f"num_splits must be an int >= 0 (0 = chosen by the library), got {num_splits!r}")
+    _check_num_splits(num_splits)
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
     out, lse = _C.fwd_mla_kvcache(q, kv_cache, kv_new, cache_seqlens, causal, num_splits, block_table, softmax_scale, head_dim_v)
@@ -735,44 +763,8 @@ def flash_mla_sparse_with_kvcache(q, kv_cache, cache_seqlens, indices, *, head_d
     Out of scope, and without a keyword here: kv_new (engines write the latent cache themselves), cu_seqlens_q, sinks, returning
     max logits, physical (pool-wide) indices, any backward.  Wrong shapes, dtypes or values are a ValueError that names the argument.
     """
-    for name, t in (("q", q), ("kv_cache", kv_cache)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 4:
-            raise ValueError(f"{name} must be a rank-4 tensor")
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, kv_cache)):
-        raise RuntimeError("flash_mla_sparse_with_kvcache is forward-only: run it under torch.no_grad() / torch.inference_mode() or pass tensors that do not require grad")
-    if q.dtype not in (torch.float16, torch.bfloat16):
-        raise ValueError(f"q must be fp16 or bf16, got {q.dtype}")
-    if q.shape[-1] != 576:
-        raise ValueError(f"q must be 576 wide (512 absorbed no-rope columns, then 64 rope columns), got head_dim {q.shape[-1]}")
-    if isinstance(head_dim_v, bool) or not isinstance(head_dim_v, int) or head_dim_v != 512:
-        raise ValueError(f"head_dim_v must be 512, got {head_dim_v!r}")
-    if q.shape[1] < 1 or q.shape[2] < 1:
-        raise ValueError(f"q needs seqlen_q >= 1 and nheads >= 1, got shape {tuple(q.shape)}")
-    fp8 = _mla_cache_is_fp8(kv_cache)
-    if not fp8 and kv_cache.dtype != q.dtype:
-        raise ValueError(f"kv_cache must have q's dtype ({q.dtype}), got {kv_cache.dtype} (an FP8 latent cache is uint8 / float8_e4m3fn rows of 656 bytes)")
-    if kv_cache.shape[2] != 1:
-        raise ValueError(f"kv_cache must have exactly one head (the latent row), got {kv_cache.shape[2]}")
-    if not fp8 and kv_cache.shape[3] != 576:
-        raise ValueError(f"kv_cache must be 576 wide, got {kv_cache.shape[3]}")
-    if fp8:
-        _check_mla_fp8_view(kv_cache)
-    if kv_cache.device != q.device:
-        raise ValueError("kv_cache must be on q's device")
-    b, sq = q.shape[0], q.shape[1]
-    if block_table is not None:
-        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
-            raise ValueError("block_table must be an int32 tensor")
-        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.device != q.device:
-            raise ValueError("block_table must have shape (batch, max_blocks_per_seq) on q's device")
-        if kv_cache.shape[1] < 1 or kv_cache.shape[1] % 16 != 0:
-            raise ValueError(f"page_block_size (kv_cache.shape[1] with block_table) must be a positive multiple of 16, got {kv_cache.shape[1]}")
-    elif kv_cache.shape[0] != b:
-        raise ValueError(f"kv_cache batch ({kv_cache.shape[0]}) must match q's ({b})")
-    if isinstance(cache_seqlens, bool) or not isinstance(cache_seqlens, (int, torch.Tensor)):
-        raise ValueError("cache_seqlens must be an int32 tensor (batch,) on q's device or an int")
-    if isinstance(cache_seqlens, torch.Tensor) and (cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (b,) or cache_seqlens.device != q.device):
-        raise ValueError("cache_seqlens must be an int32 tensor (batch,) on q's device or an int")
+    b, sq = _check_mla_decode_inputs("flash_mla_sparse_with_kvcache", q, kv_cache, head_dim_v, block_table), q.shape[1]
+    _check_cache_seqlens(cache_seqlens, b, q.device)
     if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int32:
         raise ValueError("indices must be an int32 tensor (batch, seqlen_q, topk)")
     if indices.dim() != 3 or indices.shape[0] != b or indices.shape[1] != sq:
@@ -784,8 +776,7 @@ def flash_mla_sparse_with_kvcache(q, kv_cache, cache_seqlens, indices, *, head_d
     if indices.device != q.device:
         raise ValueError("indices must be on q's device")
     softmax_scale, _ = _check_scale_and_cap(softmax_scale, 0.0)
-    if isinstance(num_splits, bool) or not isinstance(num_splits, int) or num_splits < 0:
-        raise ValueError(f"num_splits must be an int >= 0 (0 = chosen by the library), got {num_splits!r}")
+    _check_num_splits(num_splits)
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((b,), cache_seqlens, dtype=torch.int32, device=q.device)
     out, lse = _C.fwd_mla_sparse_kvcache(q, kv_cache, indices, cache_seqlens, num_splits, block_table, softmax_scale, head_dim_v)
@@ -795,10 +786,8 @@ def flash_mla_sparse_with_kvcache(q, kv_cache, cache_seqlens, indices, *, head_d
 # ---- the DeepSeek-V3.2 indexer: index logits and top-k selection in front of flash_mla_sparse_with_kvcache ----------------------------------------
 
 def _check_indexer_lengths(cache_seqlens, b, device, like="q_idx"):
-    if isinstance(cache_seqlens, bool) or not isinstance(cache_seqlens, (int, torch.Tensor)):
-        raise ValueError(f"cache_seqlens must be an int32 tensor (batch,) on {like}'s device or an int")
-    if isinstance(cache_seqlens, torch.Tensor) and (cache_seqlens.dtype != torch.int32 or cache_seqlens.shape != (b,) or cache_seqlens.device != device):
-        raise ValueError(f"cache_seqlens must be an int32 tensor (batch,) on {like}'s device or an int")
+    """_check_cache_seqlens, then the tensor; unlike the MLA decode calls the indexer clamps an int to the int32 range instead of leaving one outside it to torch.full"""
+    _check_cache_seqlens(cache_seqlens, b, device, like)
     if isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((b,), max(min(cache_seqlens, 2 ** 31 - 1), -2 ** 31), dtype=torch.int32, device=device)
     return cache_seqlens
@@ -839,20 +828,7 @@ def _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, b
         raise ValueError(f"k_idx_cache: the batch / page and row strides must be multiples of {what} with rows at least 128 apart, got strides {tuple(k_idx_cache.stride())}")
     if k_idx_cache.storage_offset() % unit != 0 or (k_idx_cache.device.type != "meta" and k_idx_cache.data_ptr() % 16 != 0):
         raise ValueError(f"k_idx_cache must start at a multiple of {what}, got storage offset {k_idx_cache.storage_offset()}")
-    if block_table is not None:
-        if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32:
-            raise ValueError("block_table must be an int32 tensor")
-        if block_table.dim() != 2 or block_table.shape[0] != b or block_table.device != q_idx.device:
-            raise ValueError("block_table must have shape (batch, max_blocks_per_seq) on q_idx's device")
-        if k_idx_cache.shape[1] < 1 or k_idx_cache.shape[1] % 16 != 0:
-            raise ValueError(f"page_block_size (k_idx_cache.shape[1] with block_table) must be a positive multiple of 16, got {k_idx_cache.shape[1]}")
-        if block_table.shape[1] < 1:
-            raise ValueError("block_table needs at least one column")
-        capacity = block_table.shape[1] * k_idx_cache.shape[1]
-    else:
-        if k_idx_cache.shape[0] != b:
-            raise ValueError(f"k_idx_cache batch ({k_idx_cache.shape[0]}) must match q_idx's ({b})")
-        capacity = k_idx_cache.shape[1]
+    capacity = _check_block_table(block_table, q_idx, k_idx_cache, like="q_idx", pool_name="k_idx_cache", need_column=True)
     if capacity >= 2 ** 31 - 2 ** 14:
         raise ValueError(f"k_idx_cache / block_table: a capacity of {capacity} keys does not fit")
     if k_scale is not None:
