@@ -47,7 +47,7 @@ EXTRA_FLAGS = {"fa_fwd_pp16.hip": ["-fno-slp-vectorize"], "fa_bwd_dq16.hip": ["-
                "fa_fwd_kvcache_mla.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"],
                "fa_fwd_kvcache_mla_sparse.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"],
                "fa_fwd_kvcache_mla_fp8.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"]}
-HIP_HEADERS = ["fa_device.hpp", "fa_params.hpp", "fa_bwd_dkdv_common.hpp", "fa_kvcache_quant.hpp", "fa_kvcache_attn.hpp", "fa_kvcache_kernels.hpp", "fa_kvcache_launch.hpp", "fa_kvcache_mla_attn.hpp", "fa_kvcache_rotary.hpp", "fa_kvcache_stage_debug.hpp", "fa_mla_indexer.hpp", "fa_merge_states.hpp", os.path.join(INCLUDE, "flash_attn_gfx950.h")]
+HIP_HEADERS = ["fa_device.hpp", "fa_params.hpp", "fa_bwd_dkdv_common.hpp", "fa_kvcache_quant.hpp", "fa_kvcache_attn.hpp", "fa_kvcache_kernels.hpp", "fa_kvcache_launch.hpp", "fa_kvcache_mla_attn.hpp", "fa_kvcache_rotary.hpp", "fa_kvcache_stage.hpp", "fa_kvcache_stage_debug.hpp", "fa_mla_prefill_tile.hpp", "fa_mla_indexer.hpp", "fa_merge_states.hpp", os.path.join(INCLUDE, "flash_attn_gfx950.h")]
 # -amdgpu-mfma-vgpr-form: builtin MFMAs keep their result in VGPRs even in kernels that may use the
 # accumulator half of the register file (the dK/dV kernel parks its 128 long-lived accumulator
 # registers in AGPRs through LP<T>::mfma_agpr); without it hipcc selects the AGPR form for every MFMA
@@ -88,7 +88,7 @@ def _write_stamp(target, stamp_value):
 _DMA_LATE = {"fa_fwd_pp16.hip": ["-DFA_PP16_DMA_DEBUG=1"], "fa_bwd_dkdv16.hip": ["-DFA_KV16_DMA_DEBUG=1"], "fa_fwd_pp.hip": ["-DFA_PP_DMA_DEBUG=1"],
              "fa_bwd.hip": ["-DFA_BWD32_DMA_DEBUG=1"], "fa_bwd_dq16.hip": ["-DFA_DQ16_DMA_DEBUG=1"]}
 _DMA_SLEEPY = {s: [f[0][:-1] + "2"] for s, f in _DMA_LATE.items()}
-# the 64-row bodies (KV cache, MLA decode, MLA prefill): four waves stage a quarter of a step each through registers into one of two LDS stages (fa_kvcache_stage_debug.hpp)
+# the 64-row bodies (KV cache, MLA decode, MLA prefill): four waves stage a quarter of a step each through registers into one of two LDS stages (fa_kvcache_stage.hpp)
 STAGE_SOURCES = ["fa_fwd_kvcache_prefill.hip", "fa_fwd_kvcache_mla.hip", "fa_fwd_kvcache_mla_sparse.hip", "fa_fwd_kvcache_mla_fp8.hip", "fa_fwd_mla_prefill.hip", "fa_bwd_mla_prefill.hip"]
 DEBUG_VARIANTS = {
     "dma_late": _DMA_LATE,                  # every request issued directly in front of the wait that retires it

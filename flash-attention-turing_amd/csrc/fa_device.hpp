@@ -290,6 +290,21 @@ FA_DEV u32x2 lds_read_tr8(const FA_LDS char* base, uint32_t off) {
     i16x4v v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((FA_LDS i16x4v*)(base + off));
     return __builtin_bit_cast(u32x2, v);
 }
+// A operand of a 16x16x32 MFMA read TRANSPOSED from a 32-row lds_tile_off<W> image: 16-column block ci, rows hh * 16 + 4 g + q4 of the two halves,
+// columns 16 ci + 4 p4 .. + 3 (g = lane / 16, q4 = (lane % 16) / 4, p4 = lane % 4)
+template <int W>
+FA_DEV u32x4 tr_frag(const FA_LDS char* img, int ci, int g, int q4, int p4) {
+    const uint32_t a0 = lds_tile_off<W>(4 * g + q4, 2 * ci + (p4 >> 1)) + 8 * (p4 & 1);
+    const uint32_t a1 = lds_tile_off<W>(16 + 4 * g + q4, 2 * ci + (p4 >> 1)) + 8 * (p4 & 1);
+    const u32x2 v0 = lds_read_tr8(img, a0), v1 = lds_read_tr8(img, a1);
+    return u32x4{v0.x, v0.y, v1.x, v1.y};
+}
+// eight floats, rounded to T: the B operand that goes with it.  (A pointer and no reference to float[8]: with the reference the dK/dV kernels of
+// fa_bwd_mla_prefill.hip, which pack two arrays in a row, come out with their registers renumbered - tools/isa_diff.py.)
+template <typename T>
+FA_DEV u32x4 pack8(const float* v) {
+    return u32x4{LP<T>::pack2(v[0], v[1]), LP<T>::pack2(v[2], v[3]), LP<T>::pack2(v[4], v[5]), LP<T>::pack2(v[6], v[7])};
+}
 
 // ---- cross-lane helpers ----------------------------------------------------------------------
 // value held by lane ^ 32 (the other half-wave owns the other 16 rows of a 32x32 C tile column)

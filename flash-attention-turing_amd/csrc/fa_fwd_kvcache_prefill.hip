@@ -22,7 +22,7 @@
 //   One instantiation per (dtype, head_dim, causal, layout, cache element, dense / ragged): 64 attention kernels.  A window, a soft cap, sinks, a
 //   tree mask, rotary and head_dim 256 are refused by the C ABI with row_tile = 64: nothing here serves them.
 #include "fa_kvcache_launch.hpp"
-#include "fa_kvcache_stage_debug.hpp"
+#include "fa_kvcache_stage.hpp"
 
 namespace fa {
 
@@ -255,31 +255,23 @@ FA_DEV void kvcache_prefill_attn(const KvcacheKernelParams& p, const KvcacheRagg
             ps += pe[j];
         });
         l_run = l_run * alpha + ps;
-        const u32x4 pf = u32x4{LP<T>::pack2(pe[0], pe[1]), LP<T>::pack2(pe[2], pe[3]), LP<T>::pack2(pe[4], pe[5]), LP<T>::pack2(pe[6], pe[7])};
+        const u32x4 pf = pack8<T>(pe);
         static_for<0, NO>([&](auto cc) {
             constexpr int ci = decltype(cc)::value;
             oacc[ci] *= alpha;
         });
         static_for<0, NO>([&](auto cc) {
             constexpr int ci = decltype(cc)::value;
-            const uint32_t a0 = lds_tile_off<D>(4 * g + q4, 2 * ci + (p4 >> 1)) + 8 * (p4 & 1);
-            const uint32_t a1 = lds_tile_off<D>(16 + 4 * g + q4, 2 * ci + (p4 >> 1)) + 8 * (p4 & 1);
-            const u32x2 v0 = lds_read_tr8(vimg, a0), v1 = lds_read_tr8(vimg, a1);
-            oacc[ci] = LP<T>::mfma16(u32x4{v0.x, v0.y, v1.x, v1.y}, pf, oacc[ci]);
+            oacc[ci] = LP<T>::mfma16(tr_frag<D>(vimg, ci, g, q4, p4), pf, oacc[ci]);
         });
     };
 
-    // ---- the split's 32-key steps, all four waves together; two LDS stages in turn ---------------------------------------------------
-    // Stage n & 1 holds step n.  While step n computes, the loads of step n + 1 are in flight; they are written to the other stage behind the
-    // compute - every wave left that stage's reads (step n - 1) in front of the last barrier - and one barrier publishes them.  The loads of
-    // step n + 2 are issued behind that barrier, so nothing is outstanding when it is reached.  k_end is the workgroup's: every wave meets
-    // the same barriers.
-    // Test builds (FA_KVC_STAGE_DEBUG, fa_kvcache_stage_debug.hpp): the two helpers hold one wave back; FA_KVC_STAGE_RACY moves the step's barrier in front of store_step.
-    // Why the racy form can neither hang nor fault here: (1) the barrier only changes places inside the same `if (key0 + kKvcStep < k_end)`, whose
-    // condition is the workgroup's (k_begin, k_end and key0 are the same in every wave, `active` is not part of it), so every wave still meets the same
-    // number of barriers on every path; (2) the images are read by compute_step alone, as MFMA operands (kf, v0 / v1): what comes out of them are scores
-    // and O, which reach compares, exponentials and stores of VALUES - every address (lds_tile_off of lane constants, row_off / row_index of the lane's
-    // row, the page cursor from block_table), every index and every loop bound comes from the parameters.  A stale image gives wrong numbers.
+    // ---- the split's 32-key steps, all four waves together; two LDS stages in turn (the schedule of fa_kvcache_stage.hpp) ---------------------------
+    // k_begin and k_end are the workgroup's: every wave meets the same barriers.
+    // Why FA_KVC_STAGE_RACY can neither hang nor fault here, part (2) (part (1) stands at kvc_stage_step): the images are read by compute_step alone, as
+    // MFMA operands (kf, tr_frag): what comes out of them are scores and O, which reach compares, exponentials and stores of VALUES - every address
+    // (lds_tile_off of lane constants, row_off / row_index of the lane's row, the page cursor from block_table), every index and every loop bound comes
+    // from the parameters.  A stale image gives wrong numbers.
     {
         u32x4 st[NP];
         int key = k_begin;
@@ -290,25 +282,12 @@ FA_DEV void kvcache_prefill_attn(const KvcacheKernelParams& p, const KvcacheRagg
         }
         __syncthreads();
         if (key + kKvcStep < k_end) load_step(key + kKvcStep, st);
-        auto step = [&](auto bufc, int key0) __attribute__((always_inline)) {
-            constexpr int BUF = decltype(bufc)::value;
-            kvc_stage_slow_reader((key0 - k_begin) / kKvcStep, wave);
-            if (active) compute_step(bufc, key0);
-            if (key0 + kKvcStep < k_end) {
-#if FA_KVC_STAGE_RACY
-                __syncthreads();
-#endif
-                kvc_stage_slow_writer((key0 - k_begin) / kKvcStep, wave);
-                store_step(std::integral_constant<int, BUF ^ 1>{}, st);
-#if !FA_KVC_STAGE_RACY
-                __syncthreads();
-#endif
-                if (key0 + 2 * kKvcStep < k_end) load_step(key0 + 2 * kKvcStep, st);
-            }
-        };
+        auto load = [&](auto, int key0) __attribute__((always_inline)) { load_step(key0, st); };
+        auto store = [&](auto bufc) __attribute__((always_inline)) { store_step(bufc, st); };
+        auto compute = [&](auto bufc, int key0) __attribute__((always_inline)) { compute_step(bufc, key0); };
         for (; key < k_end; key += 2 * kKvcStep) {
-            step(std::integral_constant<int, 0>{}, key);
-            if (key + kKvcStep < k_end) step(std::integral_constant<int, 1>{}, key + kKvcStep);
+            kvc_stage_step(std::integral_constant<int, 0>{}, key, k_begin, k_end, wave, active, load, store, compute);
+            if (key + kKvcStep < k_end) kvc_stage_step(std::integral_constant<int, 1>{}, key + kKvcStep, k_begin, k_end, wave, active, load, store, compute);
         }
     }
 

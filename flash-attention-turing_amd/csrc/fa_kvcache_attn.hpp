@@ -479,7 +479,7 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams
             ps += pe[j];
         });
         l_run = l_run * alpha + ps;
-        const u32x4 pf = u32x4{LP<T>::pack2(pe[0], pe[1]), LP<T>::pack2(pe[2], pe[3]), LP<T>::pack2(pe[4], pe[5]), LP<T>::pack2(pe[6], pe[7])};
+        const u32x4 pf = pack8<T>(pe);
         static_for<0, NO>([&](auto cc) {
             constexpr int ci = decltype(cc)::value;
             oacc[ci] *= alpha;
@@ -487,10 +487,7 @@ FA_DEV void kvcache_attn(const KvcacheKernelParams& p, const KvcacheRaggedParams
         asm volatile("" ::: "memory");      // the image written above is read back below (same wave: LDS keeps the order)
         static_for<0, NO>([&](auto cc) {
             constexpr int ci = decltype(cc)::value;
-            const uint32_t a0 = lds_tile_off<D>(4 * g + q4, 2 * ci + (p4 >> 1)) + 8 * (p4 & 1);
-            const uint32_t a1 = lds_tile_off<D>(16 + 4 * g + q4, 2 * ci + (p4 >> 1)) + 8 * (p4 & 1);
-            const u32x2 v0 = lds_read_tr8(vstage, a0), v1 = lds_read_tr8(vstage, a1);
-            oacc[ci] = LP<T>::mfma16(u32x4{v0.x, v0.y, v1.x, v1.y}, pf, oacc[ci]);
+            oacc[ci] = LP<T>::mfma16(tr_frag<D>(vstage, ci, g, q4, p4), pf, oacc[ci]);
         });
         asm volatile("" ::: "memory");      // ... before the next step overwrites it
     };

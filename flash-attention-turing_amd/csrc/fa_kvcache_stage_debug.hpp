@@ -1,7 +1,8 @@
 // fa_kvcache_stage_debug.hpp — adversarial timing for the register-staged LDS stages of the 64-row KV-cache bodies (test builds only).
 //
-//   fa_fwd_kvcache_prefill.hip, fa_kvcache_mla_attn.hpp (the one MLA decode body of fa_fwd_kvcache_mla.hip, fa_fwd_kvcache_mla_sparse.hip and fa_fwd_kvcache_mla_fp8.hip), fa_fwd_mla_prefill.hip and
-//   fa_bwd_mla_prefill.hip (both of its loops) restate one schedule: four waves
+//   fa_fwd_kvcache_prefill.hip, fa_kvcache_mla_attn.hpp (the one MLA decode body of fa_fwd_kvcache_mla.hip, fa_fwd_kvcache_mla_sparse.hip and
+//   fa_fwd_kvcache_mla_fp8.hip), fa_fwd_mla_prefill.hip and fa_bwd_mla_prefill.hip (both of its loops) run one schedule, whose step is written once, in
+//   fa_kvcache_stage.hpp (kvc_stage_step, with the two hooks below); this file holds the documentation and the defaults of the switches.  Four waves
 //   each write a quarter of a 32-key step into one of two LDS stages that all four read, with ONE barrier per step.  Four waves of a unit run close to
 //   lockstep, so a barrier one statement too early would hand a wave the stage's previous tenant almost never, and every value test would pass.
 //   tests/test_stage_protocol_gpu.py builds the same kernels with one wave held back and asks for the product's bits.
@@ -15,7 +16,7 @@
 //     about 68 MFMAs per wave in the MLA bodies; neither the sleep nor the step has been measured.
 //   FA_KVC_STAGE_RACY = 1 (the product is 0): the WRONG form the method exists for - the step's barrier stands in front of store_step instead of behind
 //     it, so the next step reads a stage nothing has published.  Kept to show that the slow-writer build catches it (it must NOT reproduce the product);
-//     nothing is claimed about it at normal timing.  Each body that carries it argues next to its loop why it can neither hang nor fault.
+//     nothing is claimed about it at normal timing.  Why it can neither hang nor fault: the barrier count at kvc_stage_step, the flow of the images' values next to each body's loop.
 #pragma once
 #include "fa_device.hpp"
 
@@ -25,20 +26,3 @@
 #ifndef FA_KVC_STAGE_RACY
 #define FA_KVC_STAGE_RACY 0
 #endif
-
-namespace fa {
-
-// n: the step within the split (wave-uniform), wave: 0 .. 3 (wave-uniform)
-FA_DEV void kvc_stage_slow_reader(int n, int wave) {
-#if FA_KVC_STAGE_DEBUG == 1
-    if ((n & 3) == wave) asm volatile("s_sleep 64" ::: "memory");
-#endif
-}
-
-FA_DEV void kvc_stage_slow_writer(int n, int wave) {
-#if FA_KVC_STAGE_DEBUG == 2
-    if (((n + 1) & 3) == wave) asm volatile("s_sleep 64" ::: "memory");
-#endif
-}
-
-}  // namespace fa

@@ -13,6 +13,7 @@ file's EXTRA_FLAGS included; hipcc cross-compiles without a GPU) and compared wi
       fa_fwd_pp16.hip                    its late form (round 5) is another loop: it requests tile u + 1 where the counted wait of the product retires it
                                          and tile u + 2 is requested - at least the product's number, nothing dropped;
   * every macro a variant sets occurs in every source it rebuilds (the source and the project headers it includes, but for the header of the defaults);
+  * the step of the staged bodies, with its racy form, is written in one file (fa_kvcache_stage.hpp);
   * no build of a decode kernel acquires scratch or another LDS size (the launch shape is the product's)."""
 import concurrent.futures
 import os
@@ -98,6 +99,29 @@ def test_every_macro_of_a_variant_occurs_in_the_source_it_rebuilds(name, src):
         m = re.fullmatch(r"-D(\w+)=\w+", flag)
         assert m, flag
         assert re.search(r"\b" + m.group(1) + r"\b", text), f"{name}: {src} does not know {m.group(1)}"
+
+
+def _files(src, seen):
+    """a source of csrc/ and the project headers it includes, transitively: {file name: text}"""
+    path = os.path.join(fa_build.CSRC, src)
+    if src in seen or not os.path.exists(path):
+        return seen
+    with open(path) as f:
+        seen[src] = f.read()
+    for h in re.findall(r'^\s*#include "([^"]+)"', seen[src], re.M):
+        _files(h, seen)
+    return seen
+
+
+def test_the_stage_protocol_is_written_once():
+    """The racy form is a preprocessor switch of the step, so a file with a preprocessor line that names FA_KVC_STAGE_RACY holds a copy of the step's
+    protocol: over the staged sources and their headers that is fa_kvcache_stage.hpp alone, next to the header of the defaults."""
+    files = {}
+    for src in fa_build.STAGE_SOURCES:
+        _files(src, files)
+    assert all(s in files for s in fa_build.STAGE_SOURCES) and "fa_kvcache_stage_debug.hpp" in files
+    holders = {name for name, text in files.items() if re.search(r"^[ \t]*#[^\n]*\bFA_KVC_STAGE_RACY\b", text, re.M)}
+    assert holders == {"fa_kvcache_stage.hpp", "fa_kvcache_stage_debug.hpp"}, sorted(holders)
 
 
 @pytest.mark.parametrize("name,src", SLEEPING, ids=[f"{n}-{s[:-4]}" for n, s in SLEEPING])

@@ -4,7 +4,7 @@ registers instead of LDS-DMA.
 
 Four waves each write a quarter of a 32-key step into one of two stages that all four read, with one barrier per step.  Waves of one unit run close to
 lockstep, so a barrier one statement too early almost never hands a wave the stage's previous tenant and every value test passes.  The builds
-`stage_slow_reader` / `stage_slow_writer` (flash-attention-turing_amd/build.py, csrc/fa_kvcache_stage_debug.hpp) hold one wave back in every step, in
+`stage_slow_reader` / `stage_slow_writer` (flash-attention-turing_amd/build.py; the step all these bodies share and its two hooks: csrc/fa_kvcache_stage.hpp) hold one wave back in every step, in
 front of its reads of the stage or in front of its writes to the next one.  A correct schedule does not care, so both must reproduce the product BIT FOR
 BIT: out, lse and, with an append, every byte of the cache.  `stage_racy_slow_writer` is the plausible one-line mistake (the step's barrier in front of
 store_step) under the slow writer and must NOT reproduce the product: the detector has teeth.  Nothing is asserted about the racy form at normal

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two source trees, kernel by kernel: `tools/isa_diff.py DIR_A DIR_B [-DFLAG ...] [--only FILE ...]`.
 
-Every decode source of each tree (DIR = a checkout of this repository) is compiled to assembly with the flags of the build, the assembly is cut
+Every decode source and every source of build.STAGE_SOURCES (the MLA prefill forward and backward among them) of each tree (DIR = a checkout of this
+repository) is compiled to assembly with the flags of the build, the assembly is cut
 into kernels (symbol to .Lfunc_end, plus the .amdhsa_kernel descriptor block), comments are stripped and local labels renumbered, and the texts are
 compared.  Reports the kernels that exist on one side only and those whose text differs; exit status 1 on any difference.  The aid of a refactor
 that promises "no kernel's instructions change".  Flags after the directories (-D...) go to both compiles: the experiment switches."""
@@ -16,7 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "flash-attention-turing_amd"))
 import build  # noqa: E402
 
-DECODE_SOURCES = [s for s in build.HIP_SOURCES if "kvcache" in s]
+DECODE_SOURCES = [s for s in build.HIP_SOURCES if "kvcache" in s or s in build.STAGE_SOURCES]      # the decode sources and every staged 64-row body
 
 
 def kernels(tree, source, flags):
