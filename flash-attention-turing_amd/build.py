@@ -32,7 +32,7 @@ LIB_NAME = "libflash_attn_gfx950.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
 EXT_PATH = os.path.join(PKG, "_C.so")
 
-HIP_SOURCES = ["fa_fwd_pp.hip", "fa_fwd_pp16.hip", "fa_bwd.hip", "fa_bwd_dq16.hip", "fa_bwd_dkdv16.hip", "fa_fwd_kvcache.hip", "fa_fwd_kvcache_ragged.hip", "fa_fwd_kvcache_softcap.hip", "fa_fwd_kvcache_sink.hip", "fa_fwd_kvcache_tree.hip", "fa_fwd_kvcache_prefill.hip", "fa_fwd_kvcache_d256.hip", "fa_fwd_kvcache_mla.hip", "fa_fwd_kvcache_mla_sparse.hip", "fa_fwd_kvcache_mla_fp8.hip", "fa_mla_indexer.hip", "fa_kvcache_rotary.hip", "fa_fwd_mla_prefill.hip", "fa_bwd_mla_prefill.hip", "fa_merge_states.hip", "fa_capi.hip"]
+HIP_SOURCES = ["fa_fwd_pp.hip", "fa_fwd_pp16.hip", "fa_bwd.hip", "fa_bwd_dq16.hip", "fa_bwd_dkdv16.hip", "fa_fwd_kvcache.hip", "fa_fwd_kvcache_ragged.hip", "fa_fwd_kvcache_softcap.hip", "fa_fwd_kvcache_sink.hip", "fa_fwd_kvcache_tree.hip", "fa_fwd_kvcache_prefill.hip", "fa_fwd_kvcache_d256.hip", "fa_fwd_kvcache_mla.hip", "fa_fwd_kvcache_mla_sparse.hip", "fa_fwd_kvcache_mla_fp8.hip", "fa_mla_indexer.hip", "fa_kvcache_rotary.hip", "fa_fwd_mla_prefill.hip", "fa_bwd_mla_prefill.hip", "fa_merge_states.hip", "fa_mla_cache_io.hip", "fa_capi.hip"]
 # per-file extra flags.  fa_fwd_pp16.hip: hipcc's SLP vectoriser packs the softmax row-sum adds and the O rescale into v_pk_* on register
 # pairs it first has to assemble from the 4-register MFMA tiles: ~200 v_mov_b64 per three tiles and 44-116 bytes of spills on the hot path
 # fa_fwd_kvcache_d256.hip (one workgroup per compute unit, 256 VGPRs + 256 AGPRs a lane): the K / V prefetch sets may live in either half of the register file, O^T and
@@ -47,7 +47,7 @@ EXTRA_FLAGS = {"fa_fwd_pp16.hip": ["-fno-slp-vectorize"], "fa_bwd_dq16.hip": ["-
                "fa_fwd_kvcache_mla.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"],
                "fa_fwd_kvcache_mla_sparse.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"],
                "fa_fwd_kvcache_mla_fp8.hip": ["-mllvm", "-greedy-regclass-priority-trumps-globalness=1"]}
-HIP_HEADERS = ["fa_device.hpp", "fa_params.hpp", "fa_bwd_dkdv_common.hpp", "fa_kvcache_quant.hpp", "fa_kvcache_attn.hpp", "fa_kvcache_kernels.hpp", "fa_kvcache_launch.hpp", "fa_kvcache_mla_attn.hpp", "fa_kvcache_rotary.hpp", "fa_kvcache_stage.hpp", "fa_kvcache_stage_debug.hpp", "fa_mla_prefill_tile.hpp", "fa_mla_indexer.hpp", "fa_merge_states.hpp", os.path.join(INCLUDE, "flash_attn_gfx950.h")]
+HIP_HEADERS = ["fa_device.hpp", "fa_params.hpp", "fa_bwd_dkdv_common.hpp", "fa_kvcache_quant.hpp", "fa_kvcache_attn.hpp", "fa_kvcache_kernels.hpp", "fa_kvcache_launch.hpp", "fa_kvcache_mla_attn.hpp", "fa_kvcache_rotary.hpp", "fa_kvcache_stage.hpp", "fa_kvcache_stage_debug.hpp", "fa_mla_prefill_tile.hpp", "fa_mla_indexer.hpp", "fa_merge_states.hpp", "fa_mla_cache_io.hpp", os.path.join(INCLUDE, "flash_attn_gfx950.h")]
 # -amdgpu-mfma-vgpr-form: builtin MFMAs keep their result in VGPRs even in kernels that may use the
 # accumulator half of the register file (the dK/dV kernel parks its 128 long-lived accumulator
 # registers in AGPRs through LP<T>::mfma_agpr); without it hipcc selects the AGPR form for every MFMA
@@ -106,7 +106,7 @@ def debug_library_path(name):
     return os.path.join(DEBUG_DIR, f"libfa_{name}.so")
 
 
-M0_GUARD_SOURCES = ["fa_fwd_pp.hip", "fa_fwd_pp16.hip", "fa_bwd.hip", "fa_bwd_dq16.hip", "fa_bwd_dkdv16.hip", "fa_fwd_kvcache.hip", "fa_fwd_kvcache_ragged.hip", "fa_fwd_kvcache_softcap.hip", "fa_fwd_kvcache_sink.hip", "fa_fwd_kvcache_tree.hip", "fa_fwd_kvcache_prefill.hip", "fa_fwd_kvcache_d256.hip", "fa_fwd_kvcache_mla.hip", "fa_fwd_kvcache_mla_sparse.hip", "fa_fwd_kvcache_mla_fp8.hip", "fa_kvcache_rotary.hip", "fa_fwd_mla_prefill.hip", "fa_bwd_mla_prefill.hip"]
+M0_GUARD_SOURCES = ["fa_fwd_pp.hip", "fa_fwd_pp16.hip", "fa_bwd.hip", "fa_bwd_dq16.hip", "fa_bwd_dkdv16.hip", "fa_fwd_kvcache.hip", "fa_fwd_kvcache_ragged.hip", "fa_fwd_kvcache_softcap.hip", "fa_fwd_kvcache_sink.hip", "fa_fwd_kvcache_tree.hip", "fa_fwd_kvcache_prefill.hip", "fa_fwd_kvcache_d256.hip", "fa_fwd_kvcache_mla.hip", "fa_fwd_kvcache_mla_sparse.hip", "fa_fwd_kvcache_mla_fp8.hip", "fa_kvcache_rotary.hip", "fa_fwd_mla_prefill.hip", "fa_bwd_mla_prefill.hip", "fa_mla_cache_io.hip"]
 
 
 def m0_uses_outside_asm(asm_text):

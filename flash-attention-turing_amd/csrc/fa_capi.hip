@@ -12,6 +12,7 @@
 #include "fa_params.hpp"
 #include "fa_mla_indexer.hpp"
 #include "fa_merge_states.hpp"
+#include "fa_mla_cache_io.hpp"
 #include "flash_attn_gfx950.h"
 
 namespace {
@@ -306,6 +307,68 @@ void fill_mla_prefill_kp(const P& p, K& kp) {
     kp.is_causal = p.is_causal ? 1 : 0;
     kp.total_q = packed ? p.total_q : 0; kp.total_k = packed ? p.total_k : 0;
     set_scale(kp, p.softmax_scale > 0.f ? p.softmax_scale : 1.0f / sqrtf((float)p.d_qk));        // (the default = 192 ** -0.5 rounded once to fp32)
+}
+
+// k_idx_cache of fa_mla_indexer_params and fa_mla_index_cache_append_params (P): strides in bytes (FA_IDX_K_FP8_E4M3) or elements, 16-byte accesses either way
+template <typename P>
+int check_idx_cache(const P& p) {
+    const bool fp8 = p.k_format == FA_IDX_K_FP8_E4M3, paged = p.block_table != nullptr;
+    const int es = fp8 ? 1 : 2, unit = 16 / es;
+    if (p.k_idx_cache == nullptr) return fail(FA_ERR_NULL_POINTER, "k_idx_cache is NULL");
+    if ((reinterpret_cast<uintptr_t>(p.k_idx_cache) & 15u) != 0) return fail(FA_ERR_BAD_STRIDE, "k_idx_cache base pointer must be 16-byte aligned");
+    if (p.k_cache_row_stride < fa::kIdxD || p.k_cache_row_stride % unit != 0 || p.k_cache_batch_stride % unit != 0 || p.k_cache_batch_stride < 0)
+        return fail(FA_ERR_BAD_STRIDE, "k_idx_cache strides (k_cache_batch_stride=%lld, k_cache_row_stride=%lld) must be multiples of %d %s (16-byte loads) with rows at least 128 apart",
+                    (long long)p.k_cache_batch_stride, (long long)p.k_cache_row_stride, unit, fp8 ? "bytes" : "elements");
+    // one descriptor per sequence (per page): below 2^31 bytes, the prefetched step past the end included
+    const int64_t span = ((int64_t)(paged ? p.page_block_size : p.seqlen_cache) + 2 * fa::kIdxStep) * p.k_cache_row_stride * es;
+    if (span >= ((int64_t)1 << 31)) return fail(FA_ERR_BAD_STRIDE, "k_idx_cache: one %s spans %lld bytes (limit 2^31)", paged ? "page" : "sequence", (long long)span);
+    return FA_OK;
+}
+
+// ---- what the three cache-io structs (fa_mla_cache_append_params, fa_mla_cache_gather_params, fa_mla_index_cache_append_params) share
+// Sizes, the form (dense rows / packed total under cu) and the grid.  rows, total, cu: the struct's own fields under their own names.  Returns through n_rows the
+// rows of the launch (0: nothing to move).
+int check_io_rows(int b, int seqlen_cache, const char* rows_name, int rows, const char* total_name, int64_t total, const char* cu_name, const int32_t* cu,
+                  int64_t& n_rows) {
+    if (b < 0 || seqlen_cache < 0 || rows < 0) return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d %s=%d seqlen_cache=%d", b, rows_name, rows, seqlen_cache);
+    if (cu != nullptr) {
+        if (total < 0) return fail(FA_ERR_BAD_SHAPE, "%s (%lld) must be >= 0 with %s", total_name, (long long)total, cu_name);
+        if ((reinterpret_cast<uintptr_t>(cu) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "%s must be 4-byte aligned", cu_name);
+    }
+    n_rows = cu != nullptr ? total : (int64_t)b * rows;
+    if (n_rows >= ((int64_t)1 << 31)) return fail(FA_ERR_BAD_SHAPE, "call too large: %lld rows exceed the launch grid", (long long)n_rows);
+    if (b == 0) n_rows = 0;
+    return FA_OK;
+}
+
+// A 16-bit row tensor the movers address with 16-byte accesses through 64-bit offsets (no extent rule): strides in elements.  width: the least row stride (0: any)
+int check_io_rows16(const char* name, const void* ptr, int64_t batch, int64_t row, int width, bool dense) {
+    if (ptr == nullptr) return fail(FA_ERR_NULL_POINTER, "%s is NULL", name);
+    if (((uintptr_t)ptr & 15) != 0) return fail(FA_ERR_BAD_STRIDE, "%s base pointer must be 16-byte aligned", name);
+    if ((row % 8) != 0 || row < width || (dense && (batch % 8) != 0))
+        return fail(FA_ERR_BAD_STRIDE, "%s strides (batch=%lld,row=%lld) must be multiples of 8 elements%s", name, (long long)batch, (long long)row,
+                    width ? " with rows at least their width apart" : "");
+    return FA_OK;
+}
+
+// The latent cache of the append and the gather (P): kv_format, then the view under it, the rules of fa_mla_params_v2
+template <typename P>
+int check_io_latent_cache(const P& p) {
+    fa_strides kvc = p.kv_cache_stride;
+    kvc.head = 0;
+    const int64_t rows = p.block_table != nullptr ? p.page_block_size : p.seqlen_cache;
+    if (p.kv_format == FA_MLA_KV_FP8_ROWS656) return check_mla_cache8(p.kv_cache, kvc, rows);
+    return check_tensor("kv_cache", p.kv_cache, kvc, rows, 576, false);
+}
+
+// cache_seqlens / block_table / the cache view of a zeroed MlaCacheIoParams.  es: bytes per unit of the cache strides
+template <typename P>
+void fill_io_cache(const P& p, const void* cache, int64_t batch, int64_t row, int es, fa::MlaCacheIoParams& io) {
+    io.cache = const_cast<void*>(cache); io.c_batch = batch * es; io.c_row = row * es;
+    io.cache_seqlens = p.cache_seqlens; io.b = p.b; io.seqlen_cache = p.seqlen_cache;
+    if (p.block_table != nullptr) {
+        io.block_table = p.block_table; io.bt_stride = p.block_table_stride; io.page_size = p.page_block_size; io.num_blocks = p.num_blocks;
+    }
 }
 
 int hip_status(hipError_t e, const char* what) {
@@ -1075,7 +1138,7 @@ static int fill_mla_indexer(const fa_mla_indexer_params* user, fa::MlaIndexerPar
     if ((int64_t)p->b * p->seqlen_q >= ((int64_t)1 << 24))
         return fail(FA_ERR_BAD_SHAPE, "call too large: b = %d sequences x seqlen_q = %d tokens exceeds the launch grid", p->b, p->seqlen_q);
     const bool fp8 = p->k_format == FA_IDX_K_FP8_E4M3;
-    const int es = fp8 ? 1 : 2, unit = 16 / es;     // strides of the cache: bytes (FP8) or elements; 16-byte loads either way
+    const int es = fp8 ? 1 : 2;     // strides of the cache: bytes (FP8) or elements; 16-byte loads either way (check_idx_cache)
     if (p->b > 0) {
         if (p->logits == nullptr) return fail(FA_ERR_NULL_POINTER, "logits is NULL");
         if ((reinterpret_cast<uintptr_t>(p->logits) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "logits must be 4-byte aligned");
@@ -1089,14 +1152,7 @@ static int fill_mla_indexer(const fa_mla_indexer_params* user, fa::MlaIndexerPar
         if ((reinterpret_cast<uintptr_t>(p->q_idx) & 15u) != 0) return fail(FA_ERR_BAD_STRIDE, "q_idx base pointer must be 16-byte aligned");
         if (qs.head % 8 != 0 || qs.row % 8 != 0 || qs.batch % 8 != 0)
             return fail(FA_ERR_BAD_STRIDE, "q_idx strides (batch=%lld,row=%lld,head=%lld) must be multiples of 8 elements", (long long)qs.batch, (long long)qs.row, (long long)qs.head);
-        if (p->k_idx_cache == nullptr) return fail(FA_ERR_NULL_POINTER, "k_idx_cache is NULL");
-        if ((reinterpret_cast<uintptr_t>(p->k_idx_cache) & 15u) != 0) return fail(FA_ERR_BAD_STRIDE, "k_idx_cache base pointer must be 16-byte aligned");
-        if (p->k_cache_row_stride < fa::kIdxD || p->k_cache_row_stride % unit != 0 || p->k_cache_batch_stride % unit != 0 || p->k_cache_batch_stride < 0)
-            return fail(FA_ERR_BAD_STRIDE, "k_idx_cache strides (k_cache_batch_stride=%lld, k_cache_row_stride=%lld) must be multiples of %d %s (16-byte loads) with rows at least 128 apart",
-                        (long long)p->k_cache_batch_stride, (long long)p->k_cache_row_stride, unit, fp8 ? "bytes" : "elements");
-        // one descriptor per sequence (per page): below 2^31 bytes, the prefetched step past the end included
-        const int64_t span = ((int64_t)(paged ? p->page_block_size : p->seqlen_cache) + 2 * fa::kIdxStep) * p->k_cache_row_stride * es;
-        if (span >= ((int64_t)1 << 31)) return fail(FA_ERR_BAD_STRIDE, "k_idx_cache: one %s spans %lld bytes (limit 2^31)", paged ? "page" : "sequence", (long long)span);
+        if ((rc = check_idx_cache(*p))) return rc;
         if (p->k_scale != nullptr && (reinterpret_cast<uintptr_t>(p->k_scale) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "k_scale must be 4-byte aligned");
     }
     memset(&ip, 0, sizeof(ip));
@@ -1266,6 +1322,94 @@ int fa_run_merge_states(const fa_merge_params* user) {
     kp.lo_batch = p->lse_out_stride.batch; kp.lo_head = p->lse_out_stride.head; kp.lo_row = p->lse_out_stride.row;
     kp.total = total; kp.n_parts = p->n_parts; kp.rows = p->rows; kp.h = p->h;
     return hip_status(fa::launch_merge_states(kp, p->dtype, p->d_v, (hipStream_t)p->stream), "fa_merge_states launch");
+}
+
+// ---- stand-alone append and gather for the MLA caches ----------------------------------------------------------------------------------------
+// The three structs -> MlaCacheIoParams (every stride in bytes), validated.  The movers use 64-bit offsets, so kv_new, k_pe, k_idx_new and out have no
+// 2^31-byte extent rule; the caches keep the rules of the calls that read them.
+int fa_run_mla_cache_append(const fa_mla_cache_append_params* user, void* stream) {
+    fa_mla_cache_append_params local;
+    int rc = import_exact(user, local, "fa_mla_cache_append_params");
+    if (rc) return rc;
+    const fa_mla_cache_append_params* p = &local;
+    int64_t n_rows;
+    if ((rc = check_io_rows(p->b, p->seqlen_cache, "seqlen_new", p->seqlen_new, "total_new", p->total_new, "cu_seqlens_new", p->cu_seqlens_new, n_rows))) return rc;
+    if ((rc = check_dtype(p->dtype))) return rc;
+    if ((rc = check_mla_format(p->kv_format, 0))) return rc;
+    if ((rc = check_reserved(p->reserved_, "fa_mla_cache_append_params", FA_ERR_BAD_SHAPE))) return rc;
+    if ((rc = check_paged(p->block_table, p->block_table_stride, p->page_block_size, p->num_blocks, p->seqlen_cache))) return rc;
+    if (n_rows == 0) return FA_OK;      // nothing to write
+    const bool dense = p->cu_seqlens_new == nullptr, fp8 = p->kv_format == FA_MLA_KV_FP8_ROWS656;
+    if (p->cache_seqlens == nullptr) return fail(FA_ERR_NULL_POINTER, "cache_seqlens is NULL (the rows kv_new is appended at)");
+    if ((rc = check_io_latent_cache(*p))) return rc;
+    if ((rc = check_io_rows16("kv_new", p->kv_new, p->kv_new_stride.batch, p->kv_new_stride.row, 0, dense))) return rc;
+    if (p->k_pe != nullptr && (rc = check_io_rows16("k_pe", p->k_pe, p->k_pe_stride.batch, p->k_pe_stride.row, 0, dense))) return rc;
+    fa::MlaCacheIoParams io;
+    memset(&io, 0, sizeof(io));
+    fill_io_cache(*p, p->kv_cache, p->kv_cache_stride.batch, p->kv_cache_stride.row, fp8 ? 1 : 2, io);
+    io.src = p->kv_new; io.s_batch = 2 * p->kv_new_stride.batch; io.s_row = 2 * p->kv_new_stride.row;
+    if (p->k_pe != nullptr) {
+        io.src_pe = p->k_pe; io.pe_batch = 2 * p->k_pe_stride.batch; io.pe_row = 2 * p->k_pe_stride.row;
+    } else {
+        io.src_pe = (const char*)p->kv_new + 2 * 512; io.pe_batch = io.s_batch; io.pe_row = io.s_row;
+    }
+    io.cu = p->cu_seqlens_new; io.n = p->seqlen_new; io.total = n_rows;
+    return hip_status(fa::launch_mla_cache_append(io, p->dtype, fp8, (hipStream_t)stream), "fa_mla_cache_append launch");
+}
+
+int fa_run_mla_cache_gather(const fa_mla_cache_gather_params* user, void* stream) {
+    fa_mla_cache_gather_params local;
+    int rc = import_exact(user, local, "fa_mla_cache_gather_params");
+    if (rc) return rc;
+    const fa_mla_cache_gather_params* p = &local;
+    int64_t n_rows;
+    if ((rc = check_io_rows(p->b, p->seqlen_cache, "seqlen_out", p->seqlen_out, "total_out", p->total_out, "cu_seqlens_out", p->cu_seqlens_out, n_rows))) return rc;
+    if ((rc = check_dtype(p->dtype))) return rc;
+    if ((rc = check_mla_format(p->kv_format, 0))) return rc;
+    if ((rc = check_reserved(p->reserved_, "fa_mla_cache_gather_params", FA_ERR_BAD_SHAPE))) return rc;
+    if ((rc = check_paged(p->block_table, p->block_table_stride, p->page_block_size, p->num_blocks, p->seqlen_cache))) return rc;
+    if (n_rows == 0) return FA_OK;      // nothing to write
+    const bool dense = p->cu_seqlens_out == nullptr, fp8 = p->kv_format == FA_MLA_KV_FP8_ROWS656;
+    if (p->seq_starts != nullptr && (reinterpret_cast<uintptr_t>(p->seq_starts) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "seq_starts must be 4-byte aligned");
+    if (p->seqlen_cache > 0 && (rc = check_io_latent_cache(*p))) return rc;       // (an empty cache is never read: every row is +0)
+    if ((rc = check_io_rows16("out", p->out, p->out_batch_stride, p->out_row_stride, 576, dense))) return rc;
+    fa::MlaCacheIoParams io;
+    memset(&io, 0, sizeof(io));
+    fill_io_cache(*p, p->kv_cache, p->kv_cache_stride.batch, p->kv_cache_stride.row, fp8 ? 1 : 2, io);
+    io.out = p->out; io.o_batch = 2 * p->out_batch_stride; io.o_row = 2 * p->out_row_stride;
+    io.cu = p->cu_seqlens_out; io.seq_starts = p->seq_starts; io.n = p->seqlen_out; io.total = n_rows;
+    return hip_status(fa::launch_mla_cache_gather(io, p->dtype, fp8, (hipStream_t)stream), "fa_mla_cache_gather launch");
+}
+
+int fa_run_mla_index_cache_append(const fa_mla_index_cache_append_params* user, void* stream) {
+    fa_mla_index_cache_append_params local;
+    int rc = import_exact(user, local, "fa_mla_index_cache_append_params");
+    if (rc) return rc;
+    const fa_mla_index_cache_append_params* p = &local;
+    int64_t n_rows;
+    if ((rc = check_io_rows(p->b, p->seqlen_cache, "seqlen_new", p->seqlen_new, "total_new", p->total_new, "cu_seqlens_new", p->cu_seqlens_new, n_rows))) return rc;
+    if ((rc = check_dtype(p->dtype))) return rc;
+    if (p->k_format != FA_MLA_KV_16BIT && p->k_format != FA_IDX_K_FP8_E4M3)
+        return fail(FA_ERR_BAD_DTYPE, "k_format %d unknown (0 = keys of dtype, 1 = OCP e4m3 codes)", p->k_format);
+    if (p->scale_format != FA_IDX_SCALE_FP32 && p->scale_format != FA_IDX_SCALE_UE8M0)
+        return fail(FA_ERR_BAD_DTYPE, "scale_format %d unknown (0 = fp32 scales, 1 = scales rounded up to powers of two, UE8M0)", p->scale_format);
+    if ((rc = check_reserved(p->reserved_, "fa_mla_index_cache_append_params", FA_ERR_BAD_SHAPE))) return rc;
+    if ((rc = check_paged(p->block_table, p->block_table_stride, p->page_block_size, p->num_blocks, p->seqlen_cache))) return rc;
+    const bool dense = p->cu_seqlens_new == nullptr, fp8 = p->k_format == FA_IDX_K_FP8_E4M3;
+    if (!fp8 && p->k_scale != nullptr) return fail(FA_ERR_BAD_SHAPE, "k_scale given with k_format = 0 (a 16-bit index cache has no scales)");
+    if (n_rows == 0) return FA_OK;      // nothing to write
+    if (p->cache_seqlens == nullptr) return fail(FA_ERR_NULL_POINTER, "cache_seqlens is NULL (the rows k_idx_new is appended at)");
+    if ((rc = check_idx_cache(*p))) return rc;
+    if (fp8 && p->k_scale == nullptr) return fail(FA_ERR_NULL_POINTER, "k_scale is NULL (k_format = 1 writes one scale per token)");
+    if (fp8 && (reinterpret_cast<uintptr_t>(p->k_scale) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "k_scale must be 4-byte aligned");
+    if ((rc = check_io_rows16("k_idx_new", p->k_idx_new, p->k_new_batch_stride, p->k_new_row_stride, 0, dense))) return rc;
+    fa::MlaCacheIoParams io;
+    memset(&io, 0, sizeof(io));
+    fill_io_cache(*p, p->k_idx_cache, p->k_cache_batch_stride, p->k_cache_row_stride, fp8 ? 1 : 2, io);
+    io.k_scale = p->k_scale; io.ks_batch = p->k_scale_batch_stride; io.ks_row = p->k_scale_row_stride;
+    io.src = p->k_idx_new; io.s_batch = 2 * p->k_new_batch_stride; io.s_row = 2 * p->k_new_row_stride;
+    io.cu = p->cu_seqlens_new; io.n = p->seqlen_new; io.total = n_rows;
+    return hip_status(fa::launch_mla_index_cache_append(io, p->dtype, fp8 ? 1 + p->scale_format : 0, (hipStream_t)stream), "fa_mla_index_cache_append launch");
 }
 
 }  // extern "C"

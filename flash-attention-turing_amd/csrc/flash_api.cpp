@@ -811,6 +811,98 @@ void mla_indexer_topk(at::Tensor logits, at::Tensor cache_seqlens, at::Tensor in
     check_status(fa_run_mla_indexer_topk(&p, current_stream(logits)));
 }
 
+// Stand-alone append and gather for the MLA caches (fa_run_mla_cache_append / fa_run_mla_cache_gather / fa_run_mla_index_cache_append).  The Python layer has
+// checked shapes, dtypes and views; here the tensors become pointers and strides.  Dense rows are (b, n, ..), packed rows (total, ..) with cu_seqlens.
+void mla_cache_append(at::Tensor kv_cache, at::Tensor kv_new, at::Tensor cache_seqlens, c10::optional<at::Tensor> k_pe_, c10::optional<at::Tensor> block_table_,
+                      c10::optional<at::Tensor> cu_seqlens_new_) {
+    TORCH_CHECK(kv_cache.is_cuda() && kv_new.is_cuda(), "kv_cache, kv_new must be GPU (HIP) tensors");
+    const bool packed = cu_seqlens_new_.has_value();
+    TORCH_CHECK(kv_cache.dim() == 4 && kv_new.dim() == (packed ? 3 : 4), "kv_cache (b, capacity, 1, 576 | 656), kv_new (b, s_new, 1, w) or packed (total_new, 1, w)");
+    const int64_t batch_size = cache_seqlens.size(0);
+    c10::DeviceGuard guard(kv_cache.device());
+    fa_mla_cache_append_params p;
+    FA_PARAMS_INIT(p);
+    int64_t seqlen_cache = kv_cache.size(1);
+    if (block_table_.has_value()) seqlen_cache = attach_block_table(p, kv_cache, batch_size, *block_table_, kv_cache);
+    p.kv_cache = kv_cache.data_ptr(); p.kv_new = kv_new.data_ptr();
+    p.cache_seqlens = cache_seqlens_ptr(kv_cache, batch_size, cache_seqlens);
+    p.b = (int32_t)batch_size; p.seqlen_cache = (int32_t)seqlen_cache; p.dtype = fa_dtype_of(kv_new);
+    p.kv_format = kv_cache.element_size() == 1 ? FA_MLA_KV_FP8_ROWS656 : FA_MLA_KV_16BIT;
+    p.kv_cache_stride = fa_strides{kv_cache.stride(0), kv_cache.stride(1), 0};
+    auto rows = [&](const at::Tensor& t) { return packed ? fa_strides{0, t.stride(0), 0} : fa_strides{t.stride(0), t.stride(1), 0}; };
+    p.kv_new_stride = rows(kv_new);
+    if (k_pe_.has_value()) {
+        check_same_device(kv_cache, *k_pe_, "k_pe");
+        p.k_pe = k_pe_->data_ptr(); p.k_pe_stride = rows(*k_pe_);
+    }
+    if (packed) {
+        check_same_device(kv_cache, *cu_seqlens_new_, "cu_seqlens_new");
+        p.cu_seqlens_new = cu_seqlens_new_->data_ptr<int32_t>(); p.total_new = kv_new.size(0);
+    } else {
+        p.seqlen_new = (int32_t)kv_new.size(1);
+    }
+    check_status(fa_run_mla_cache_append(&p, current_stream(kv_cache)));
+}
+
+void mla_cache_gather(at::Tensor kv_cache, c10::optional<at::Tensor> cache_seqlens_, at::Tensor out, c10::optional<at::Tensor> block_table_,
+                      c10::optional<at::Tensor> cu_seqlens_out_, c10::optional<at::Tensor> seq_starts_, int64_t batch_size) {
+    TORCH_CHECK(kv_cache.is_cuda() && out.is_cuda(), "kv_cache, out must be GPU (HIP) tensors");
+    const bool packed = cu_seqlens_out_.has_value();
+    TORCH_CHECK(kv_cache.dim() == 4 && out.dim() == (packed ? 2 : 3), "kv_cache (b, capacity, 1, 576 | 656), out (b, n, 576) or packed (total, 576)");
+    c10::DeviceGuard guard(kv_cache.device());
+    fa_mla_cache_gather_params p;
+    FA_PARAMS_INIT(p);
+    int64_t seqlen_cache = kv_cache.size(1);
+    if (block_table_.has_value()) seqlen_cache = attach_block_table(p, kv_cache, batch_size, *block_table_, kv_cache);
+    p.kv_cache = kv_cache.data_ptr(); p.out = out.data_ptr();
+    p.cache_seqlens = cache_seqlens_ptr(kv_cache, batch_size, cache_seqlens_);
+    p.b = (int32_t)batch_size; p.seqlen_cache = (int32_t)seqlen_cache; p.dtype = fa_dtype_of(out);
+    p.kv_format = kv_cache.element_size() == 1 ? FA_MLA_KV_FP8_ROWS656 : FA_MLA_KV_16BIT;
+    p.kv_cache_stride = fa_strides{kv_cache.stride(0), kv_cache.stride(1), 0};
+    if (packed) {
+        check_same_device(kv_cache, *cu_seqlens_out_, "cu_seqlens_out");
+        p.cu_seqlens_out = cu_seqlens_out_->data_ptr<int32_t>(); p.total_out = out.size(0); p.out_row_stride = out.stride(0);
+    } else {
+        p.seqlen_out = (int32_t)out.size(1); p.out_batch_stride = out.stride(0); p.out_row_stride = out.stride(1);
+    }
+    if (seq_starts_.has_value()) {
+        check_same_device(kv_cache, *seq_starts_, "seq_starts");
+        p.seq_starts = seq_starts_->data_ptr<int32_t>();
+    }
+    check_status(fa_run_mla_cache_gather(&p, current_stream(kv_cache)));
+}
+
+void mla_index_cache_append(at::Tensor k_idx_cache, at::Tensor k_idx_new, at::Tensor cache_seqlens, c10::optional<at::Tensor> k_scale_,
+                            c10::optional<at::Tensor> block_table_, c10::optional<at::Tensor> cu_seqlens_new_, int64_t scale_format) {
+    TORCH_CHECK(k_idx_cache.is_cuda() && k_idx_new.is_cuda(), "k_idx_cache, k_idx_new must be GPU (HIP) tensors");
+    const bool packed = cu_seqlens_new_.has_value();
+    TORCH_CHECK(k_idx_cache.dim() == 3 && k_idx_new.dim() == (packed ? 2 : 3), "k_idx_cache (b, capacity, 128), k_idx_new (b, s_new, 128) or packed (total_new, 128)");
+    const int64_t batch_size = cache_seqlens.size(0);
+    c10::DeviceGuard guard(k_idx_cache.device());
+    fa_mla_index_cache_append_params p;
+    FA_PARAMS_INIT(p);
+    int64_t seqlen_cache = k_idx_cache.size(1);
+    if (block_table_.has_value()) seqlen_cache = attach_block_table(p, k_idx_cache, batch_size, *block_table_, k_idx_cache);
+    p.k_idx_cache = k_idx_cache.data_ptr(); p.k_idx_new = k_idx_new.data_ptr();
+    p.cache_seqlens = cache_seqlens_ptr(k_idx_cache, batch_size, cache_seqlens);
+    p.b = (int32_t)batch_size; p.seqlen_cache = (int32_t)seqlen_cache; p.dtype = fa_dtype_of(k_idx_new);
+    p.k_format = k_idx_cache.element_size() == 1 ? FA_IDX_K_FP8_E4M3 : FA_MLA_KV_16BIT; p.scale_format = (int32_t)scale_format;
+    p.k_cache_batch_stride = k_idx_cache.stride(0); p.k_cache_row_stride = k_idx_cache.stride(1);      // (FP8: a 1-byte dtype, so these are bytes, as the format asks)
+    if (k_scale_.has_value()) {
+        const at::Tensor& ks = *k_scale_;
+        check_same_device(k_idx_cache, ks, "k_scale");
+        TORCH_CHECK(ks.scalar_type() == torch::kFloat32 && ks.dim() == 2, "k_scale must be a float32 tensor with one value per cached token");
+        p.k_scale = ks.data_ptr<float>(); p.k_scale_batch_stride = ks.stride(0); p.k_scale_row_stride = ks.stride(1);
+    }
+    if (packed) {
+        check_same_device(k_idx_cache, *cu_seqlens_new_, "cu_seqlens_new");
+        p.cu_seqlens_new = cu_seqlens_new_->data_ptr<int32_t>(); p.total_new = k_idx_new.size(0); p.k_new_row_stride = k_idx_new.stride(0);
+    } else {
+        p.seqlen_new = (int32_t)k_idx_new.size(1); p.k_new_batch_stride = k_idx_new.stride(0); p.k_new_row_stride = k_idx_new.stride(1);
+    }
+    check_status(fa_run_mla_index_cache_append(&p, current_stream(k_idx_cache)));
+}
+
 // ---- autograd nodes in C++ ------------------------------------------------------------------------------------------------------
 // The reference ships the four raw functions only; its README's flash_attn_func is an older Python-level API.  The differentiable wrappers
 // of this package used to be torch.autograd.Function subclasses in Python: ~85 us of host time per forward + backward, more than the GPU
@@ -887,6 +979,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("lses"));
     m.def("mla_indexer_logits", &mla_indexer_logits,"index logits of the DeepSeek-V3.2 indexer into the caller's fp32 buffer (b, sq, capacity)", py::arg("q_idx"), py::arg("weights"),
           py::arg("k_idx_cache"), py::arg("cache_seqlens"), py::arg("logits"), py::arg("k_scale") = py::none(), py::arg("block_table") = py::none(), py::arg("is_causal") = true);
+    m.def("mla_cache_append", &mla_cache_append, "append latent rows (16-bit, or quantised to 656-byte FP8 rows) to the MLA latent cache, in place", py::arg("kv_cache"),
+          py::arg("kv_new"), py::arg("cache_seqlens"), py::arg("k_pe") = py::none(), py::arg("block_table") = py::none(), py::arg("cu_seqlens_new") = py::none());
+    m.def("mla_cache_gather", &mla_cache_gather, "gather (and dequantise) rows of the MLA latent cache into the caller's buffer", py::arg("kv_cache"),
+          py::arg("cache_seqlens"), py::arg("out"), py::arg("block_table") = py::none(), py::arg("cu_seqlens_out") = py::none(), py::arg("seq_starts") = py::none(),
+          py::arg("batch_size") = 0);
+    m.def("mla_index_cache_append", &mla_index_cache_append, "append index keys (16-bit, or e4m3 codes with one scale per token) to the index-key cache, in place",
+          py::arg("k_idx_cache"), py::arg("k_idx_new"), py::arg("cache_seqlens"), py::arg("k_scale") = py::none(), py::arg("block_table") = py::none(),
+          py::arg("cu_seqlens_new") = py::none(), py::arg("scale_format") = 0);
     m.def("mla_indexer_topk", &mla_indexer_topk, "top-k positions of every logits row into the caller's int32 buffer (b, sq, topk)", py::arg("logits"), py::arg("cache_seqlens"),
           py::arg("indices"), py::arg("is_causal") = true);
     // three overloads: the signature as it was (every existing call, positional or keyword, resolves to it), the one that continues it with the

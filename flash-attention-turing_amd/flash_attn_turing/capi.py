@@ -211,10 +211,40 @@ class MergeParams(_Params):
                 ("stream", _vp)]
 
 
+class MlaCacheAppendParams(_Params):
+    """fa_mla_cache_append_params: latent rows into the MLA latent cache, copied or quantised to 656-byte rows (fa_run_mla_cache_append)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("kv_cache", _vp), ("kv_new", _vp), ("k_pe", _vp), ("cache_seqlens", _vp),
+                ("cu_seqlens_new", _vp), ("block_table", _vp),
+                ("b", _i32), ("seqlen_new", _i32), ("seqlen_cache", _i32), ("dtype", _i32), ("kv_format", _i32), ("page_block_size", _i32), ("num_blocks", _i32),
+                ("reserved_", _i32), ("total_new", ctypes.c_int64),
+                ("kv_cache_stride", Strides), ("kv_new_stride", Strides), ("k_pe_stride", Strides), ("block_table_stride", ctypes.c_int64)]
+
+
+class MlaCacheGatherParams(_Params):
+    """fa_mla_cache_gather_params: rows of the MLA latent cache into the caller's buffer, dequantised from FP8 rows (fa_run_mla_cache_gather)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("kv_cache", _vp), ("out", _vp), ("cache_seqlens", _vp), ("cu_seqlens_out", _vp),
+                ("seq_starts", _vp), ("block_table", _vp),
+                ("b", _i32), ("seqlen_out", _i32), ("seqlen_cache", _i32), ("dtype", _i32), ("kv_format", _i32), ("page_block_size", _i32), ("num_blocks", _i32),
+                ("reserved_", _i32), ("total_out", ctypes.c_int64),
+                ("kv_cache_stride", Strides), ("out_batch_stride", ctypes.c_int64), ("out_row_stride", ctypes.c_int64), ("block_table_stride", ctypes.c_int64)]
+
+
+class MlaIndexCacheAppendParams(_Params):
+    """fa_mla_index_cache_append_params: index keys into the index-key cache, copied or quantised to e4m3 with one scale per token (fa_run_mla_index_cache_append)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("k_idx_cache", _vp), ("k_scale", _vp), ("k_idx_new", _vp), ("cache_seqlens", _vp),
+                ("cu_seqlens_new", _vp), ("block_table", _vp),
+                ("b", _i32), ("seqlen_new", _i32), ("seqlen_cache", _i32), ("dtype", _i32), ("k_format", _i32), ("scale_format", _i32), ("page_block_size", _i32),
+                ("num_blocks", _i32), ("total_new", ctypes.c_int64), ("reserved_", ctypes.c_int64),
+                ("k_cache_batch_stride", ctypes.c_int64), ("k_cache_row_stride", ctypes.c_int64), ("k_scale_batch_stride", ctypes.c_int64),
+                ("k_scale_row_stride", ctypes.c_int64), ("k_new_batch_stride", ctypes.c_int64), ("k_new_row_stride", ctypes.c_int64),
+                ("block_table_stride", ctypes.c_int64)]
+
+
 FA_MLA_KV_16BIT = 0
 FA_MLA_KV_FP8_ROWS656 = 1     # 656-byte latent rows: 512 e4m3 codes, four fp32 scales, 64 rope elements of q's dtype; kv_cache_stride in bytes
 FA_CACHE_FP8_E4M3 = 1
 FA_IDX_K_FP8_E4M3 = 1         # k_format of fa_mla_indexer_params: index keys as OCP e4m3 codes, strides in bytes
+FA_IDX_SCALE_FP32, FA_IDX_SCALE_UE8M0 = 0, 1     # scale_format of fa_mla_index_cache_append_params
 
 
 _lib = None
@@ -285,6 +315,12 @@ def lib():
         L.fa_run_mla_prefill_bwd.restype = ctypes.c_int
         L.fa_run_merge_states.argtypes = [ctypes.POINTER(MergeParams)]
         L.fa_run_merge_states.restype = ctypes.c_int
+        L.fa_run_mla_cache_append.argtypes = [ctypes.POINTER(MlaCacheAppendParams), _vp]
+        L.fa_run_mla_cache_append.restype = ctypes.c_int
+        L.fa_run_mla_cache_gather.argtypes = [ctypes.POINTER(MlaCacheGatherParams), _vp]
+        L.fa_run_mla_cache_gather.restype = ctypes.c_int
+        L.fa_run_mla_index_cache_append.argtypes = [ctypes.POINTER(MlaIndexCacheAppendParams), _vp]
+        L.fa_run_mla_index_cache_append.restype = ctypes.c_int
         L.fa_mha_fwd.argtypes = [_vp] * 5 + [_i32] * 8 + [_vp]
         L.fa_mha_bwd.argtypes = [_vp] * 10 + [_i32] * 8 + [_vp]
         L.fa_mha_varlen_fwd.argtypes = [_vp] * 7 + [_i32] * 8 + [_vp]
@@ -833,3 +869,90 @@ def merge_params(outs, lses, out, lse_out, stream=None):
 def run_merge_states(params):
     """fa_run_merge_states (the stream is a field of the struct)"""
     check(lib().fa_run_merge_states(ctypes.byref(params)))
+
+
+def _attach_paging(p, block_table, pool):
+    """the four paging fields of a cache-io struct over the page pool ``pool``; seqlen_cache becomes the table's capacity"""
+    p.seqlen_cache = pool.shape[1]
+    if block_table is not None:
+        p.block_table, p.block_table_stride = block_table.data_ptr(), block_table.stride(0)
+        p.page_block_size, p.num_blocks = pool.shape[1], pool.shape[0]
+        p.seqlen_cache = block_table.shape[1] * pool.shape[1]
+
+
+def mla_cache_append_params(kv_cache, kv_new, cache_seqlens, k_pe=None, block_table=None, cu_seqlens_new=None):
+    """fa_mla_cache_append_params for kv_cache (b, capacity, 1, 576) 16-bit or (.., 656) uint8 / float8_e4m3fn (or a pool with block_table), kv_new dense
+    (b, s_new, 1, w) or packed (total_new, 1, w) with cu_seqlens_new, w = 576 or 512 with k_pe (.., 1, 64): torch tensors with arbitrary strides."""
+    packed = cu_seqlens_new is not None
+    p = MlaCacheAppendParams()
+    p.kv_cache, p.kv_new, p.cache_seqlens = kv_cache.data_ptr(), kv_new.data_ptr(), cache_seqlens.data_ptr()
+    p.b, p.dtype = cache_seqlens.shape[0], dtype_code(kv_new.dtype)
+    p.kv_format = FA_MLA_KV_FP8_ROWS656 if kv_cache.element_size() == 1 else FA_MLA_KV_16BIT
+    _attach_paging(p, block_table, kv_cache)
+    rows = (lambda t: Strides(0, t.stride(0), 0)) if packed else (lambda t: Strides(t.stride(0), t.stride(1), 0))
+    p.kv_cache_stride, p.kv_new_stride = Strides(kv_cache.stride(0), kv_cache.stride(1), 0), rows(kv_new)
+    if k_pe is not None:
+        p.k_pe, p.k_pe_stride = k_pe.data_ptr(), rows(k_pe)
+    if packed:
+        p.cu_seqlens_new, p.total_new = cu_seqlens_new.data_ptr(), kv_new.shape[0]
+    else:
+        p.seqlen_new = kv_new.shape[1]
+    return p
+
+
+def mla_cache_gather_params(kv_cache, out, cache_seqlens=None, block_table=None, cu_seqlens_out=None, seq_starts=None):
+    """fa_mla_cache_gather_params for kv_cache as in mla_cache_append_params and out dense (b, n, 576) or packed (total, 576) with cu_seqlens_out"""
+    packed = cu_seqlens_out is not None
+    p = MlaCacheGatherParams()
+    p.kv_cache, p.out = kv_cache.data_ptr(), out.data_ptr()
+    p.cache_seqlens = None if cache_seqlens is None else cache_seqlens.data_ptr()
+    p.seq_starts = None if seq_starts is None else seq_starts.data_ptr()
+    p.b, p.dtype = (cu_seqlens_out.shape[0] - 1 if packed else out.shape[0]), dtype_code(out.dtype)
+    p.kv_format = FA_MLA_KV_FP8_ROWS656 if kv_cache.element_size() == 1 else FA_MLA_KV_16BIT
+    _attach_paging(p, block_table, kv_cache)
+    p.kv_cache_stride = Strides(kv_cache.stride(0), kv_cache.stride(1), 0)
+    if packed:
+        p.cu_seqlens_out, p.total_out, p.out_row_stride = cu_seqlens_out.data_ptr(), out.shape[0], out.stride(0)
+    else:
+        p.seqlen_out, p.out_batch_stride, p.out_row_stride = out.shape[1], out.stride(0), out.stride(1)
+    return p
+
+
+def mla_index_cache_append_params(k_idx_cache, k_idx_new, cache_seqlens, k_scale=None, block_table=None, cu_seqlens_new=None, scale_format=FA_IDX_SCALE_FP32):
+    """fa_mla_index_cache_append_params for k_idx_cache / k_scale as in mla_indexer_params and k_idx_new dense (b, s_new, 128) or packed (total_new, 128)"""
+    packed = cu_seqlens_new is not None
+    p = MlaIndexCacheAppendParams()
+    p.k_idx_cache, p.k_idx_new, p.cache_seqlens = k_idx_cache.data_ptr(), k_idx_new.data_ptr(), cache_seqlens.data_ptr()
+    p.b, p.dtype, p.scale_format = cache_seqlens.shape[0], dtype_code(k_idx_new.dtype), scale_format
+    p.k_format = FA_IDX_K_FP8_E4M3 if k_idx_cache.element_size() == 1 else FA_MLA_KV_16BIT
+    _attach_paging(p, block_table, k_idx_cache)
+    p.k_cache_batch_stride, p.k_cache_row_stride = k_idx_cache.stride(0), k_idx_cache.stride(1)
+    if k_scale is not None:
+        p.k_scale, p.k_scale_batch_stride, p.k_scale_row_stride = k_scale.data_ptr(), k_scale.stride(0), k_scale.stride(1)
+    if packed:
+        p.cu_seqlens_new, p.total_new, p.k_new_row_stride = cu_seqlens_new.data_ptr(), k_idx_new.shape[0], k_idx_new.stride(0)
+    else:
+        p.seqlen_new, p.k_new_batch_stride, p.k_new_row_stride = k_idx_new.shape[1], k_idx_new.stride(0), k_idx_new.stride(1)
+    return p
+
+
+def _run_io(name, params, stream):
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    check(getattr(lib(), name)(ctypes.byref(params), s))
+
+
+def run_mla_cache_append(params, stream=None):
+    """fa_run_mla_cache_append"""
+    _run_io("fa_run_mla_cache_append", params, stream)
+
+
+def run_mla_cache_gather(params, stream=None):
+    """fa_run_mla_cache_gather"""
+    _run_io("fa_run_mla_cache_gather", params, stream)
+
+
+def run_mla_index_cache_append(params, stream=None):
+    """fa_run_mla_index_cache_append"""
+    _run_io("fa_run_mla_index_cache_append", params, stream)

@@ -793,6 +793,18 @@ def _check_indexer_lengths(cache_seqlens, b, device, like="q_idx"):
     return cache_seqlens
 
 
+def _check_idx_cache_view(k_idx_cache, fp8):
+    """the kernels read and write an index key with 16-byte accesses: a view they cannot address is refused, never copied"""
+    unit = 16 if fp8 else 8
+    what = "16 bytes" if fp8 else "8 elements"
+    if k_idx_cache.stride(2) != 1:
+        raise ValueError("k_idx_cache: the last dimension must be contiguous")
+    if k_idx_cache.stride(0) % unit != 0 or k_idx_cache.stride(1) % unit != 0 or k_idx_cache.stride(1) < 128 or k_idx_cache.stride(0) < 0:
+        raise ValueError(f"k_idx_cache: the batch / page and row strides must be multiples of {what} with rows at least 128 apart, got strides {tuple(k_idx_cache.stride())}")
+    if k_idx_cache.storage_offset() % unit != 0 or (k_idx_cache.device.type != "meta" and k_idx_cache.data_ptr() % 16 != 0):
+        raise ValueError(f"k_idx_cache must start at a multiple of {what}, got storage offset {k_idx_cache.storage_offset()}")
+
+
 def _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, block_table, causal):
     """the checks of flash_mla_indexer_logits; returns (q_idx with addressable strides, cache_seqlens as a tensor, capacity)"""
     if not isinstance(q_idx, torch.Tensor) or q_idx.dim() != 4:
@@ -819,15 +831,7 @@ def _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, b
         raise ValueError(f"k_idx_cache must be 128 wide, got {k_idx_cache.shape[2]}")
     if k_idx_cache.device != q_idx.device:
         raise ValueError("k_idx_cache must be on q_idx's device")
-    # the kernels read a key with 16-byte loads: a view they cannot address is refused, never copied
-    unit = 16 if fp8 else 8
-    what = "16 bytes" if fp8 else "8 elements"
-    if k_idx_cache.stride(2) != 1:
-        raise ValueError("k_idx_cache: the last dimension must be contiguous")
-    if k_idx_cache.stride(0) % unit != 0 or k_idx_cache.stride(1) % unit != 0 or k_idx_cache.stride(1) < 128 or k_idx_cache.stride(0) < 0:
-        raise ValueError(f"k_idx_cache: the batch / page and row strides must be multiples of {what} with rows at least 128 apart, got strides {tuple(k_idx_cache.stride())}")
-    if k_idx_cache.storage_offset() % unit != 0 or (k_idx_cache.device.type != "meta" and k_idx_cache.data_ptr() % 16 != 0):
-        raise ValueError(f"k_idx_cache must start at a multiple of {what}, got storage offset {k_idx_cache.storage_offset()}")
+    _check_idx_cache_view(k_idx_cache, fp8)
     capacity = _check_block_table(block_table, q_idx, k_idx_cache, like="q_idx", pool_name="k_idx_cache", need_column=True)
     if capacity >= 2 ** 31 - 2 ** 14:
         raise ValueError(f"k_idx_cache / block_table: a capacity of {capacity} keys does not fit")
@@ -1295,3 +1299,216 @@ def flash_mla_chunked_prefill_func(q, k_ctx, v_ctx, k_new, v_new, *, cu_seqlens_
     out_n, lse_n = _C.fwd_mla_prefill(q, k_new, v_new, cu_seqlens_q, cu_seqlens_q, True, softmax_scale_)
     out, lse = _C.merge_states([out_c, out_n], [lse_c, lse_n])
     return (out, lse) if return_softmax_lse else out
+
+
+# ---- stand-alone append and gather for the MLA latent cache and the index-key cache ------------------------------------------------------------------------
+
+class _Batch:
+    """what _check_block_table asks of the tensor it calls ``like``: a batch and a device"""
+
+    def __init__(self, b, device):
+        self.shape, self.device = (b,), device
+
+
+def _check_io_view(name, t):
+    """a 16-bit tensor the row movers address as it is: the last dimension contiguous, every other stride and the storage offset a multiple of 8 elements"""
+    if t.shape[-1] > 1 and t.stride(-1) != 1:
+        raise ValueError(f"{name}: the last dimension must be contiguous")
+    if any(t.shape[i] > 1 and t.stride(i) % 8 != 0 for i in range(t.dim() - 1)):
+        raise ValueError(f"{name}: every stride but the last must be a multiple of 8 elements (16-byte accesses), got strides {tuple(t.stride())}")
+    if t.storage_offset() % 8 != 0 or (t.device.type != "meta" and t.data_ptr() % 16 != 0):
+        raise ValueError(f"{name} must start at a multiple of 8 elements (16 bytes), got storage offset {t.storage_offset()}")
+
+
+def _check_io_latent_cache(kv_cache):
+    """kv_cache of the append and the gather: what flash_mla_with_kvcache takes; returns whether it holds FP8 rows"""
+    if not isinstance(kv_cache, torch.Tensor) or kv_cache.dim() != 4:
+        raise ValueError("kv_cache must be a rank-4 tensor")
+    fp8 = _mla_cache_is_fp8(kv_cache)
+    if not fp8 and kv_cache.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"kv_cache must be fp16 / bf16 and 576 wide, or an FP8 latent cache (uint8 / float8_e4m3fn rows of 656 bytes), got {kv_cache.dtype} "
+                         f"rows {kv_cache.shape[-1]} wide")
+    if kv_cache.shape[2] != 1:
+        raise ValueError(f"kv_cache must have exactly one head (the latent row), got {kv_cache.shape[2]}")
+    if not fp8 and kv_cache.shape[3] != 576:
+        raise ValueError(f"kv_cache must be 576 wide, got {kv_cache.shape[3]}")
+    if fp8:
+        _check_mla_fp8_view(kv_cache)
+    else:
+        _check_io_view("kv_cache", kv_cache)
+        if kv_cache.shape[1] > 1 and kv_cache.stride(1) < 576:
+            raise ValueError(f"kv_cache: rows must be at least 576 elements apart, got strides {tuple(kv_cache.stride())}")
+    return fp8
+
+
+def _io_lengths(cache_seqlens, b, device, like):
+    _check_cache_seqlens(cache_seqlens, b, device, like)
+    if isinstance(cache_seqlens, int):
+        cache_seqlens = torch.full((b,), max(min(cache_seqlens, 2 ** 31 - 1), -2 ** 31), dtype=torch.int32, device=device)
+    return cache_seqlens.contiguous()
+
+
+def _check_io_new_rows(name, t, cu_name, cu, cache, widths, trailing):
+    """new rows of an append: dense (b, s_new, *trailing) or, with cu (named cu_name), packed (total_new, *trailing); returns the batch"""
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{name} must be an fp16 / bf16 tensor, got {getattr(t, 'dtype', type(t))}")
+    rank = 1 + len(trailing) + (cu is None)
+    shape = ("(batch, s_new, " if cu is None else "(total_new, ") + ", ".join(str(x) for x in trailing[:-1] + (" or ".join(str(w) for w in widths),)) + ")"
+    if t.dim() != rank or tuple(t.shape[-len(trailing):-1]) != tuple(trailing[:-1]) or t.shape[-1] not in widths:
+        raise ValueError(f"{name} must have shape {shape}{'' if cu is None else f' with {cu_name}'}, got {tuple(t.shape)}")
+    if t.device != cache.device:
+        raise ValueError(f"{name} must be on the cache's device")
+    _check_io_view(name, t)
+    if cu is None:
+        return t.shape[0]
+    _check_cu_seqlens(cu_name, cu, cache)
+    return cu.shape[0] - 1
+
+
+def flash_mla_cache_append(kv_cache, kv_new, cache_seqlens, *, k_pe=None, block_table=None, cu_seqlens_new=None):
+    """Write latent rows into the cache flash_mla_with_kvcache / flash_mla_sparse_with_kvcache read, without running attention (in place; returns None).
+
+    kv_cache: what flash_mla_with_kvcache takes - 16-bit (batch, capacity, 1, 576), or with block_table (int32 (batch, max_blocks)) a page pool (num_blocks,
+    page_block_size, 1, 576); or the FP8 format, uint8 / float8_e4m3fn and 656 wide.
+    kv_new: fp16 / bf16 (a 16-bit cache must have its dtype), dense (batch, s_new, 1, 576) or packed (total_new, 1, 576) with cu_seqlens_new, int32
+    (batch + 1,) on the GPU.  With k_pe (the concat_and_cache_mla layout) kv_new is 512 wide and k_pe (..., 1, 64) has the same leading shape and dtype; the
+    row written is their concatenation.  The last dimension is contiguous, other strides and the storage offset are multiples of 8 elements: anything else is
+    a ValueError, never a copy.
+    New row s of sequence i goes to logical position max(cache_seqlens[i], 0) + s; it is dropped at or past the capacity; in a paged cache it goes through
+    block_table with the clamp min(uint32(entry), num_blocks - 1).  cache_seqlens (int32 (batch,) or an int) is not updated: the caller advances it.
+    16-bit cache: the 1152 bytes are copied.  FP8 cache: the row is quantised by the rule of quantize_mla_kv_cache.  To the byte: a dense call leaves the
+    cache as flash_mla_with_kvcache(q, kv_cache, cache_seqlens, kv_new=kv_new) does; sequence i of a packed call equals the dense call on it alone; paged ==
+    contiguous; every byte that is not a target row keeps its value; packed rows at or past cu_seqlens_new[batch] are never read; nothing is written outside
+    the pool, whatever the table or the lengths hold.  No host synchronisation: one launch, capturable in a graph.
+    Out of scope: physical slots (slot_mapping), copying pages, advancing cache_seqlens."""
+    fp8 = _check_io_latent_cache(kv_cache)
+    b = _check_io_new_rows("kv_new", kv_new, "cu_seqlens_new", cu_seqlens_new, kv_cache, (576, 512), (1, 576))
+    if not fp8 and kv_new.dtype != kv_cache.dtype:
+        raise ValueError(f"kv_new must have kv_cache's dtype ({kv_cache.dtype}), got {kv_new.dtype}")
+    if (kv_new.shape[-1] == 512) != (k_pe is not None):
+        raise ValueError(f"kv_new must be 576 wide, or 512 wide together with k_pe (..., 1, 64), got {kv_new.shape[-1]} wide {'with' if k_pe is not None else 'without'} k_pe")
+    if k_pe is not None:
+        if not isinstance(k_pe, torch.Tensor) or k_pe.dtype != kv_new.dtype or tuple(k_pe.shape) != tuple(kv_new.shape[:-1]) + (64,) or k_pe.device != kv_new.device:
+            raise ValueError(f"k_pe must have shape {tuple(kv_new.shape[:-1]) + (64,)} and kv_new's dtype and device, got {tuple(getattr(k_pe, 'shape', ()))}")
+        _check_io_view("k_pe", k_pe)
+    _check_block_table(block_table, _Batch(b, kv_cache.device), kv_cache, like="kv_new")
+    cache_seqlens = _io_lengths(cache_seqlens, b, kv_cache.device, "kv_cache")
+    if b == 0 or kv_new.shape[0] == 0 or (cu_seqlens_new is None and kv_new.shape[1] == 0):
+        return None
+    _C.mla_cache_append(kv_cache, kv_new, cache_seqlens, k_pe, block_table, cu_seqlens_new)
+    return None
+
+
+def flash_mla_cache_gather(kv_cache, cache_seqlens, out, *, block_table=None, cu_seqlens_out=None, seq_starts=None):
+    """Gather rows of the latent cache into ``out``, dequantised if the cache is FP8: the packed (total_ctx, 576) input of the up-projection in front of
+    flash_mla_chunked_prefill_func.  Returns out.
+
+    kv_cache, block_table: as in flash_mla_cache_append.  out: fp16 / bf16, caller-allocated, packed (total, 576) with cu_seqlens_out int32 (batch + 1,) or
+    dense (batch, n, 576) without it; the last dimension contiguous, the row stride a multiple of 8 elements and at least 576 (a slice of a wider workspace
+    is fine).  Over a 16-bit cache out has the cache's dtype; over an FP8 cache its dtype says how the rope part is stored.
+    Row r of sequence i (packed: r < cu_seqlens_out[i + 1] - cu_seqlens_out[i]; dense: r < n) is the cache row at logical position start_i + r, start_i =
+    max(seq_starts[i], 0) (int32 (batch,) on the GPU; None = 0).  With L_i = min(max(cache_seqlens[i], 0), capacity) (cache_seqlens None = the capacity): a
+    position below L_i gives the row's 1152 bytes, or dequantize_mla_kv_cache(row, out.dtype) bit for bit - what the attention kernels compute with; a
+    position at or past L_i writes a row of +0 and does not read the cache.
+    Never read, so they may hold 0xff bytes: rows at or past L_i, pages and table entries that no requested row needs, pages no sequence references.  Never
+    written: out rows at or past cu_seqlens_out[batch], and the gaps of a strided out.  Paged == contiguous bit for bit.  No host synchronisation: one launch,
+    capturable in a graph.  Out of scope: FP8 output, gathering the index-key cache, physical slots."""
+    fp8 = _check_io_latent_cache(kv_cache)
+    if not isinstance(out, torch.Tensor) or out.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"out must be an fp16 / bf16 tensor, got {getattr(out, 'dtype', type(out))}")
+    if not fp8 and out.dtype != kv_cache.dtype:
+        raise ValueError(f"out must have kv_cache's dtype ({kv_cache.dtype}), got {out.dtype}")
+    packed = cu_seqlens_out is not None
+    if out.dim() != (2 if packed else 3) or out.shape[-1] != 576:
+        raise ValueError(f"out must have shape {'(total, 576) with cu_seqlens_out' if packed else '(batch, n, 576)'}, got {tuple(out.shape)}")
+    if out.device != kv_cache.device:
+        raise ValueError("out must be on kv_cache's device")
+    _check_io_view("out", out)
+    if out.shape[-2] > 1 and out.stride(-2) < 576:
+        raise ValueError(f"out: rows must be at least 576 elements apart, got strides {tuple(out.stride())}")
+    if packed:
+        _check_cu_seqlens("cu_seqlens_out", cu_seqlens_out, kv_cache)
+    b = cu_seqlens_out.shape[0] - 1 if packed else out.shape[0]
+    _check_block_table(block_table, _Batch(b, kv_cache.device), kv_cache, like="out")
+    if cache_seqlens is not None:
+        cache_seqlens = _io_lengths(cache_seqlens, b, kv_cache.device, "kv_cache")
+    if seq_starts is not None:
+        if not isinstance(seq_starts, torch.Tensor) or seq_starts.dtype != torch.int32 or tuple(seq_starts.shape) != (b,) or seq_starts.device != kv_cache.device:
+            raise ValueError(f"seq_starts must be an int32 tensor (batch,) = ({b},) on kv_cache's device")
+        seq_starts = seq_starts.contiguous()
+    if b == 0 or out.shape[0] == 0 or (not packed and out.shape[1] == 0):
+        return out
+    _C.mla_cache_gather(kv_cache, cache_seqlens, out, block_table, cu_seqlens_out, seq_starts, b)
+    return out
+
+
+_IDX_SCALE_FORMATS = {"fp32": 0, "ue8m0": 1}     # FA_IDX_SCALE_FP32 / FA_IDX_SCALE_UE8M0 of the C ABI
+
+
+def _check_scale_format(scale_format):
+    if not isinstance(scale_format, str) or scale_format not in _IDX_SCALE_FORMATS:
+        raise ValueError(f"scale_format must be 'fp32' or 'ue8m0', got {scale_format!r}")
+    return _IDX_SCALE_FORMATS[scale_format]
+
+
+def quantize_mla_index_keys(k, scale_format="fp32"):
+    """(..., 128) fp16 / bf16 index keys -> (codes uint8 (..., 128), scale float32 (...)): the rule of flash_mla_index_cache_append, what
+    flash_mla_indexer_logits reads as k_idx_cache and k_scale.
+
+    amax = max |x| over the row's finite elements (0 if none); scale = max(amax, 2^-24) / 448, the correctly rounded fp32 quotient; under
+    scale_format="ue8m0" the scale is rounded up to a power of two on its bits, (bits(scale) + 0x007fffff) & 0x7f800000; code = e4m3_rne(clamp(float(x) /
+    scale, -448, 448)), NaN kept with its sign (0x7f / 0xff), +-inf saturating: one 128-column tile of quantize_mla_kv_cache.  Plain torch: any device."""
+    if not isinstance(k, torch.Tensor) or k.dtype not in (torch.float16, torch.bfloat16) or k.dim() < 1 or k.shape[-1] != 128:
+        raise ValueError("k must be an fp16 / bf16 tensor (..., 128)")
+    ue8m0 = _check_scale_format(scale_format) == 1
+    x = k.float()
+    amax = torch.where(torch.isfinite(x), x.abs(), torch.zeros_like(x)).amax(dim=-1, keepdim=True)
+    scale = torch.clamp(amax, min=2.0 ** -24) / torch.full_like(amax, 448.0)     # (tensor / tensor: a division on every device, never a multiplication by 1 / 448)
+    if ue8m0:
+        scale = ((scale.view(torch.int32) + 0x007FFFFF) & 0x7F800000).view(torch.float32)
+    y = torch.clamp(x / scale, min=-448.0, max=448.0)      # (NaN passes through clamp)
+    nan = torch.isnan(y)
+    codes = torch.where(nan, torch.zeros_like(y), y).to(torch.float8_e4m3fn).view(torch.uint8)
+    sign = ((k.contiguous().view(torch.int16).to(torch.int32) >> 8) & 0x80).to(torch.uint8)      # (of the 16-bit pattern: a widening may drop a NaN's sign)
+    return torch.where(nan, sign | 0x7F, codes), scale.squeeze(-1)
+
+
+def flash_mla_index_cache_append(k_idx_cache, k_idx_new, cache_seqlens, *, k_scale=None, block_table=None, cu_seqlens_new=None, scale_format="fp32"):
+    """Write index keys into the cache flash_mla_indexer_logits reads (in place; returns None).
+
+    k_idx_cache, k_scale: the two views flash_mla_indexer_logits takes - values (batch, capacity, 128) or a pool (num_blocks, page_block_size, 128) with
+    block_table, and scales float32 (batch, capacity) / (num_blocks, page_block_size), any strides.  k_idx_new: fp16 / bf16, (batch, s_new, 128) or packed
+    (total_new, 128) with cu_seqlens_new.  Placement, drop and clamp rules are those of flash_mla_cache_append.
+    16-bit cache (k_idx_new's dtype): rows are copied; k_scale must be None.  FP8 cache (float8_e4m3fn / uint8): k_scale is required and takes one scale per
+    token; rows and scales are those of quantize_mla_index_keys(k_idx_new, scale_format), byte for byte ("fp32", or "ue8m0": scales rounded up to powers of
+    two, as DeepSeek-V3.2 stores them).  Every other byte of both buffers is untouched.  No host synchronisation: one launch, capturable in a graph.
+    Out of scope: gathering the index-key cache (the indexer reads it in place), physical slots, advancing cache_seqlens."""
+    if not isinstance(k_idx_cache, torch.Tensor) or k_idx_cache.dim() != 3:
+        raise ValueError("k_idx_cache must be a rank-3 tensor (batch, capacity, 128), or a page pool (num_blocks, page_block_size, 128) with block_table")
+    fp8 = k_idx_cache.dtype in (torch.uint8, torch.float8_e4m3fn)
+    if not fp8 and k_idx_cache.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"k_idx_cache must be fp16 / bf16 or hold e4m3 codes (float8_e4m3fn / uint8), got {k_idx_cache.dtype}")
+    if k_idx_cache.shape[2] != 128:
+        raise ValueError(f"k_idx_cache must be 128 wide, got {k_idx_cache.shape[2]}")
+    _check_idx_cache_view(k_idx_cache, fp8)
+    b = _check_io_new_rows("k_idx_new", k_idx_new, "cu_seqlens_new", cu_seqlens_new, k_idx_cache, (128,), (128,))
+    if not fp8 and k_idx_new.dtype != k_idx_cache.dtype:
+        raise ValueError(f"k_idx_new must have k_idx_cache's dtype ({k_idx_cache.dtype}), got {k_idx_new.dtype}")
+    fmt = _check_scale_format(scale_format)
+    if not fp8 and k_scale is not None:
+        raise ValueError("k_scale must be None with a 16-bit k_idx_cache (rows are copied; there are no scales)")
+    if fp8:
+        if k_scale is None:
+            raise ValueError("k_scale is required with an FP8 k_idx_cache: a float32 tensor with one scale per cached token")
+        if not isinstance(k_scale, torch.Tensor) or k_scale.dtype != torch.float32:
+            raise ValueError("k_scale must be a float32 tensor with one scale per cached token")
+        if tuple(k_scale.shape) != tuple(k_idx_cache.shape[:2]) or k_scale.device != k_idx_cache.device:
+            raise ValueError(f"k_scale must have shape {tuple(k_idx_cache.shape[:2])} (k_idx_cache without its last dimension) on k_idx_cache's device, got {tuple(k_scale.shape)}")
+        if k_scale.device.type != "meta" and k_scale.data_ptr() % 4 != 0:
+            raise ValueError("k_scale must be 4-byte aligned")
+    _check_block_table(block_table, _Batch(b, k_idx_cache.device), k_idx_cache, like="k_idx_new", pool_name="k_idx_cache")
+    cache_seqlens = _io_lengths(cache_seqlens, b, k_idx_cache.device, "k_idx_cache")
+    if b == 0 or k_idx_new.shape[0] == 0 or (cu_seqlens_new is None and k_idx_new.shape[1] == 0):
+        return None
+    _C.mla_index_cache_append(k_idx_cache, k_idx_new, cache_seqlens, k_scale, block_table, cu_seqlens_new, fmt)
+    return None

@@ -1038,6 +1038,109 @@ typedef struct fa_merge_params {
     void* stream;               /* the stream of fa_run_merge_states (hipStream_t; NULL = the default stream) */
 } fa_merge_params;
 
+/* Stand-alone append and gather for the MLA latent cache and the index-key cache (FA_HAS_MLA_CACHE_IO; concat_and_cache_mla and
+ * gather_and_maybe_dequant_cache / cp_gather_and_upconvert_fp8_kv_cache of vLLM): the rows that fa_run_mla_fwd_kvcache, fa_run_mla_sparse_fwd_kvcache and
+ * fa_run_mla_indexer_logits read, written and read back without an attention call.  FA_ABI_VERSION is unchanged.  Three structs with the {struct_size, magic}
+ * header; struct_size must be the struct's own size.  One launch each on `stream`, no workspace, no host synchronisation: lengths, tables, cu_seqlens and starts
+ * are read on the device.  The unit conventions are those of fa_mla_params_v2 / fa_mla_indexer_params: the strides of a 16-bit tensor count elements (multiples of
+ * 8, pointer 16-byte aligned), those of an FP8 cache count BYTES (multiples of 16).
+ * Rows.  Dense: (b, seqlen_new, ..) / (b, seqlen_out, ..) with batch and row strides.  Packed (cu_seqlens_* given, int32 (b + 1,)): total_* rows with the row
+ * stride alone, rows cu[i] .. cu[i + 1] - 1 those of sequence i; rows at or past cu[b] are neither read nor written.
+ * Placement (both appends): new row s of sequence i goes to logical row max(cache_seqlens[i], 0) + s, dropped at or past seqlen_cache; paged, to row (.) %
+ * page_block_size of page min((uint32_t)block_table[i][(.) / page_block_size], num_blocks - 1): the rules of the append of fa_run_mla_fwd_kvcache.  Nothing is
+ * written outside the cache / the pool, and every byte that is not a target row keeps its value.  The caller advances the lengths.
+ * fa_mla_cache_append_params.  kv_new (.., 576) of `dtype`, or with k_pe: kv_new 512 wide and k_pe 64 wide with strides of its own, the row being their
+ * concatenation.  kv_format FA_MLA_KV_16BIT: the 1152 bytes are copied.  FA_MLA_KV_FP8_ROWS656: the row is quantised by the rule stated with fa_mla_params_v2.
+ * fa_mla_cache_gather_params.  out (.., 576) of `dtype`, last dimension contiguous.  Row r of sequence i is the cache row at logical position start_i + r,
+ * start_i = max(seq_starts[i], 0) (NULL: 0).  L_i = min(max(cache_seqlens[i], 0), seqlen_cache) (NULL: seqlen_cache).  Below L_i: the row's 1152 bytes, or for
+ * FP8 rows kv[c] = round_to_dtype(fp32(code[c]) * scale[c / 128]) and the stored rope elements - what the attention kernels compute with, bit for bit.  At or
+ * past L_i: a row of +0, and neither the table nor the cache is read.  Rows at or past L_i, pages and table entries no requested row needs and pages no sequence
+ * references are never read; out rows at or past cu_seqlens_out[b] and the gaps of a strided out are never written.
+ * fa_mla_index_cache_append_params.  k_idx_new (.., 128) of `dtype` into the cache of fa_mla_indexer_params.  k_format FA_MLA_KV_16BIT: rows are copied, k_scale
+ * must be NULL.  FA_IDX_K_FP8_E4M3: k_scale (strides in elements, any value) is required and takes one scale per token: amax = max |x| over the row's finite
+ * elements (0 if none), scale = max(amax, 2^-24) / 448 (the correctly rounded fp32 quotient), under scale_format FA_IDX_SCALE_UE8M0 rounded up to a power of
+ * two on its bits ((bits + 0x007fffff) & 0x7f800000); code = e4m3_rne(clamp(float(x) / scale, -448, 448)), NaN kept with its sign (0x7f / 0xff), +-inf
+ * saturating.
+ * Errors name the field: NULL pointers FA_ERR_NULL_POINTER, dtype / k_format / scale_format FA_ERR_BAD_DTYPE, sizes, totals, kv_format (as in
+ * fa_mla_params_v2), paging, non-zero reserved words and a k_scale given with FA_MLA_KV_16BIT FA_ERR_BAD_SHAPE, strides and alignment FA_ERR_BAD_STRIDE, the
+ * header FA_ERR_BAD_ABI.  b == 0 or no row to move is FA_OK without a launch. */
+#define FA_HAS_MLA_CACHE_IO 1
+#define FA_IDX_SCALE_FP32 0
+#define FA_IDX_SCALE_UE8M0 1
+typedef struct fa_mla_cache_append_params {
+    uint32_t struct_size;       /* sizeof(fa_mla_cache_append_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    void* kv_cache;
+    const void* kv_new;
+    const void* k_pe;           /* NULL: kv_new is 576 wide */
+    const int32_t* cache_seqlens;
+    const int32_t* cu_seqlens_new;      /* NULL: dense */
+    const int32_t* block_table; /* paged cache; NULL = contiguous */
+    int32_t b;
+    int32_t seqlen_new;         /* dense: new rows per sequence */
+    int32_t seqlen_cache;
+    int32_t dtype;
+    int32_t kv_format;          /* FA_MLA_KV_16BIT / FA_MLA_KV_FP8_ROWS656 */
+    int32_t page_block_size;
+    int32_t num_blocks;
+    int32_t reserved_;          /* 0 */
+    int64_t total_new;          /* packed: rows of kv_new / k_pe */
+    fa_strides kv_cache_stride, kv_new_stride, k_pe_stride;     /* head strides are not read */
+    int64_t block_table_stride;
+} fa_mla_cache_append_params;
+
+typedef struct fa_mla_cache_gather_params {
+    uint32_t struct_size;       /* sizeof(fa_mla_cache_gather_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const void* kv_cache;
+    void* out;
+    const int32_t* cache_seqlens;       /* NULL = seqlen_cache */
+    const int32_t* cu_seqlens_out;      /* NULL: dense */
+    const int32_t* seq_starts;  /* NULL = 0 */
+    const int32_t* block_table; /* paged cache; NULL = contiguous */
+    int32_t b;
+    int32_t seqlen_out;         /* dense: rows per sequence */
+    int32_t seqlen_cache;
+    int32_t dtype;              /* of out (and of a 16-bit cache) */
+    int32_t kv_format;          /* FA_MLA_KV_16BIT / FA_MLA_KV_FP8_ROWS656 */
+    int32_t page_block_size;
+    int32_t num_blocks;
+    int32_t reserved_;          /* 0 */
+    int64_t total_out;          /* packed: rows of out */
+    fa_strides kv_cache_stride; /* the head stride is not read */
+    int64_t out_batch_stride;   /* elements; dense only */
+    int64_t out_row_stride;     /* elements, a multiple of 8, >= 576 */
+    int64_t block_table_stride;
+} fa_mla_cache_gather_params;
+
+typedef struct fa_mla_index_cache_append_params {
+    uint32_t struct_size;       /* sizeof(fa_mla_index_cache_append_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    void* k_idx_cache;
+    float* k_scale;             /* FA_IDX_K_FP8_E4M3: required; FA_MLA_KV_16BIT: NULL */
+    const void* k_idx_new;
+    const int32_t* cache_seqlens;
+    const int32_t* cu_seqlens_new;      /* NULL: dense */
+    const int32_t* block_table; /* paged cache; NULL = contiguous */
+    int32_t b;
+    int32_t seqlen_new;         /* dense: new rows per sequence */
+    int32_t seqlen_cache;
+    int32_t dtype;
+    int32_t k_format;           /* FA_MLA_KV_16BIT / FA_IDX_K_FP8_E4M3 */
+    int32_t scale_format;       /* FA_IDX_SCALE_FP32 / FA_IDX_SCALE_UE8M0 */
+    int32_t page_block_size;
+    int32_t num_blocks;
+    int64_t total_new;          /* packed: rows of k_idx_new */
+    int64_t reserved_;          /* 0 */
+    int64_t k_cache_batch_stride;
+    int64_t k_cache_row_stride;
+    int64_t k_scale_batch_stride;
+    int64_t k_scale_row_stride;
+    int64_t k_new_batch_stride; /* elements; dense only */
+    int64_t k_new_row_stride;   /* elements */
+    int64_t block_table_stride;
+} fa_mla_index_cache_append_params;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -1139,6 +1242,12 @@ int fa_run_mla_prefill_bwd(const fa_mla_prefill_bwd_params* params, void* stream
 /* ---- merging attention states (fa_merge_params above) ------------------------------------------ */
 /* One launch on params->stream, no workspace, no host synchronisation. */
 int fa_run_merge_states(const fa_merge_params* params);
+
+/* ---- append and gather for the MLA caches (fa_mla_cache_append_params / _gather_params / fa_mla_index_cache_append_params above) --- */
+/* One launch each on `stream`, no workspace, no host synchronisation. */
+int fa_run_mla_cache_append(const fa_mla_cache_append_params* params, void* stream);
+int fa_run_mla_cache_gather(const fa_mla_cache_gather_params* params, void* stream);
+int fa_run_mla_index_cache_append(const fa_mla_index_cache_append_params* params, void* stream);
 
 /* ---- measurement helpers ----------------------------------------------------------------- */
 /* Algorithmic FLOPs of one forward call (4*b*h*sq*sk*d, causal counts only visible pairs);

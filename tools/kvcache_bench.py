@@ -1303,6 +1303,67 @@ def run_shared_prefix(quick, rounds):
                 yield run_shared_prefix_point(b, prefix, fp8, rounds)
 
 
+def _io_point(mode, b, rows, ours, torch_form, same, nbytes, rounds):
+    ms = _mlap_time({"torch": torch_form, "ours": ours, "torch_again": torch_form}, rounds, iters=3)
+    return dict(mode=mode, b=b, rows_per_seq=rows, page=64, dtype="bfloat16", kv_dtype="fp8", mbytes=round(nbytes / 2 ** 20, 2), ms_ours=round(ms["ours"], 4),
+                tb_s=round(nbytes / ms["ours"] / 1e9, 3), frac_of_6p3=round(nbytes / ms["ours"] / 1e9 / 6.3, 4), ms_torch=round(ms["torch"], 4),
+                ms_torch_again=round(ms["torch_again"], 4), ours_over_torch=round(ms["ours"] / ms["torch"], 3), bits_equal=bool(same))
+
+
+def run_mla_cache_io(quick, rounds, page=64, dt=torch.bfloat16):
+    """flash_mla_cache_append, flash_mla_index_cache_append (1 and 2048 new rows a sequence) and flash_mla_cache_gather (4k and 32k rows a sequence) on FP8 caches
+    in pages of 64, bf16, b in {1, 8, 64}, each against its torch formulation (timed twice: its noise figure): the quantiser in torch ops plus an indexed write
+    through the table; a table gather plus dequantize_mla_kv_cache.  Bytes moved (rows read + rows written) / time against 6.3 TB/s"""
+    dev = torch.device("cuda:0")
+    for b in ((1, 8) if quick else (1, 8, 64)):
+        gen = torch.Generator(device=dev).manual_seed(b)
+        for s_new in (1, 2048):
+            cols = 4096 // page
+            nb = b * cols
+            table = torch.randperm(nb, device=dev, generator=gen).view(b, cols).to(torch.int32)
+            lens = torch.full((b,), 1000, dtype=torch.int32, device=dev)
+            pos = lens.long().unsqueeze(1) + torch.arange(s_new, device=dev)
+            slot = (table.long().gather(1, pos // page) * page + pos % page).flatten()
+            kv_new = torch.randn(b, s_new, 1, 576, device=dev, generator=gen).to(dt)
+            pool, pool_t = (torch.zeros(nb, page, 1, 656, dtype=torch.uint8, device=dev) for _ in range(2))
+
+            def torch_append():
+                pool_t.view(-1, 656)[slot] = F.quantize_mla_kv_cache(kv_new).view(-1, 656)
+
+            ours = lambda: F.flash_mla_cache_append(pool, kv_new, lens, block_table=table)
+            ours(), torch_append()
+            # (bits against the quantiser run on the CPU: run on the GPU, quantize_mla_kv_cache's `/ 448.0` gave other bits in some scales - measured, pool != pool_t)
+            pool_t.view(-1, 656)[slot] = F.quantize_mla_kv_cache(kv_new.cpu()).view(-1, 656).to(dev)
+            yield _io_point("mla_cache_append", b, s_new, ours, torch_append, torch.equal(pool, pool_t), b * s_new * (1152 + 656), rounds)
+            k_new = torch.randn(b, s_new, 128, device=dev, generator=gen).to(dt)
+            kc, kc_t = (torch.zeros(nb, page, 128, dtype=torch.uint8, device=dev) for _ in range(2))
+            ks, ks_t = (torch.zeros(nb, page, device=dev) for _ in range(2))
+
+            def torch_index_append():
+                codes, scale = F.quantize_mla_index_keys(k_new)
+                kc_t.view(-1, 128)[slot] = codes.view(-1, 128)
+                ks_t.view(-1)[slot] = scale.view(-1)
+
+            ours = lambda: F.flash_mla_index_cache_append(kc, k_new, lens, k_scale=ks, block_table=table)
+            ours(), torch_index_append()
+            yield _io_point("mla_index_cache_append", b, s_new, ours, torch_index_append, torch.equal(kc, kc_t) and torch.equal(ks, ks_t), b * s_new * (256 + 132), rounds)
+            del kv_new, pool, pool_t, k_new, kc, kc_t, ks, ks_t
+        for n in ((4096,) if quick else (4096, 32768)):
+            cols = n // page
+            nb = b * cols
+            pool = torch.randint(0, 120, (nb, page, 1, 656), dtype=torch.uint8, device=dev, generator=gen)      # codes below 0x78, scales and rope elements small and finite
+            table = torch.randperm(nb, device=dev, generator=gen).view(b, cols).to(torch.int32)
+            lens = torch.full((b,), n, dtype=torch.int32, device=dev)
+            cu = torch.arange(0, b * n + 1, n, dtype=torch.int32, device=dev)
+            out = torch.empty(b * n, 576, dtype=dt, device=dev)
+            ours = lambda: F.flash_mla_cache_gather(pool, lens, out, block_table=table, cu_seqlens_out=cu)
+            torch_gather = lambda: F.dequantize_mla_kv_cache(pool[table.long()].flatten(1, 2), dt).view(-1, 576)
+            same = torch.equal(ours().view(torch.int16), torch_gather().view(torch.int16))
+            yield _io_point("mla_cache_gather", b, n, ours, torch_gather, same, b * n * (656 + 1152), rounds)
+            del pool, out
+            torch.cuda.empty_cache()
+
+
 def _baseline_lib(path):
     L = ctypes.CDLL(os.path.abspath(path))
     L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
@@ -1403,6 +1464,9 @@ def main():
                                                          "against 6.3 TB/s, next to the torch formulation of the merge (timed twice)")
     ap.add_argument("--shared-prefix", action="store_true", help="flash_attn_with_shared_prefix (b 8 / 64, sq 1, h 32 / h_k 8, d 128, pages of 16, 16-bit and FP8 caches, prefix "
                                                                  "2k / 8k / 32k, 128 own keys) against flash_attn_with_kvcache on the same tables (timed twice)")
+    ap.add_argument("--mla-cache-io", action="store_true", help="flash_mla_cache_append / flash_mla_index_cache_append (1 and 2048 new rows a sequence) and "
+                                                                "flash_mla_cache_gather (4k and 32k rows) on FP8 caches, pages of 64, bf16, b in {1, 8, 64}: bytes moved / "
+                                                                "time against 6.3 TB/s, next to the torch formulation of each (timed twice)")
     a = ap.parse_args()
     base = _baseline_lib(a.baseline_library) if a.baseline_library else None
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
@@ -1410,8 +1474,8 @@ def main():
     if base is not None:
         print(json.dumps({"baseline_library": base.fa_build_info().decode()}), flush=True)
     with torch.no_grad():
-        if a.merge or a.shared_prefix:
-            for line in (run_merge if a.merge else run_shared_prefix)(a.quick, a.rounds):
+        if a.merge or a.shared_prefix or a.mla_cache_io:
+            for line in (run_merge if a.merge else run_shared_prefix if a.shared_prefix else run_mla_cache_io)(a.quick, a.rounds):
                 print(json.dumps(line), flush=True)
             return
         if a.mla_prefill_bwd:
