@@ -1179,6 +1179,28 @@ int fa_run_mla_indexer_logits(const fa_mla_indexer_params* user, void* stream) {
     return hip_status(fa::launch_mla_indexer_logits(ip, local.dtype, (hipStream_t)stream), "fa_mla_indexer_logits launch");
 }
 
+// the prompt-chunk form of fa_run_mla_indexer_logits: the same struct through the same fill_mla_indexer
+int fa_run_mla_indexer_prefill_logits(const fa_mla_indexer_params* user, void* stream) {
+    fa::MlaIndexerParams ip;
+    fa_mla_indexer_params local;
+    int rc = fill_mla_indexer(user, ip, local);
+    if (rc) return rc;
+    if (ip.b == 0 || ip.seqlen_cache == 0) return FA_OK;        // nothing to write
+    return hip_status(fa::launch_mla_indexer_prefill_logits(ip, local.dtype, (hipStream_t)stream), "fa_mla_indexer_prefill_logits launch");
+}
+
+int fa_mla_indexer_prefill_launch(const fa_mla_indexer_params* user, int32_t* tokens_per_wg, int32_t* wg_keys, int32_t* n_chunks) {
+    fa::MlaIndexerParams ip;
+    fa_mla_indexer_params local;
+    int rc = fill_mla_indexer(user, ip, local);
+    if (rc) return rc;
+    fa::mla_indexer_prefill_shape(ip);
+    if (tokens_per_wg != nullptr) *tokens_per_wg = fa::kIdxpTQ;
+    if (wg_keys != nullptr) *wg_keys = ip.wg_keys;
+    if (n_chunks != nullptr) *n_chunks = ip.n_chunks;
+    return FA_OK;
+}
+
 int fa_run_mla_indexer_topk(const fa_mla_topk_params* user, void* stream) {
     fa_mla_topk_params local;
     int rc = import_exact(user, local, "fa_mla_topk_params");

@@ -38,31 +38,6 @@ namespace fa {
 
 namespace {
 
-// eight e4m3 codes -> eight elements of T, exactly (every e4m3 value is an fp16 and a bf16 value)
-template <typename T>
-FA_DEV u32x4 idx_widen8(uint32_t w0, uint32_t w1) {
-    if constexpr (__is_same(T, _Float16)) {
-        return u32x4{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, false)),
-                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, true)),
-                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, false)),
-                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, true))};
-    } else {
-        return u32x4{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false)),
-                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true)),
-                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false)),
-                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true))};
-    }
-}
-
-FA_DEV int idx_len(const int32_t* cache_seqlens, int bidx, int seqlen_cache) {
-    int L = seqlen_cache;
-    if (cache_seqlens != nullptr) {
-        const int cs = cache_seqlens[bidx];
-        L = min(cs > 0 ? cs : 0, seqlen_cache);
-    }
-    return __builtin_amdgcn_readfirstlane(L);
-}
-
 // ES = bytes per cache element: 2 = T, 1 = e4m3 codes
 template <typename T, int ES, bool PAGED>
 __global__ __launch_bounds__(kIdxThreads, 2) void fa_mla_indexer_logits_kernel(const MlaIndexerParams p) {

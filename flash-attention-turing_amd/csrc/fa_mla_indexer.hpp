@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fa_device.hpp"
+
 namespace fa {
 
 constexpr int kIdxD = 128;          // width of an index head and of an index key
@@ -30,7 +32,7 @@ struct MlaIndexerParams {
     int b, seqlen_q, seqlen_cache, h;
     int is_causal, cache_fp8;
     int page_size, num_blocks;
-    int wg_keys, n_chunks;          // keys of a workgroup's range (a multiple of kIdxStep * kIdxWaves) and ranges per token: set by the launcher
+    int wg_keys, n_chunks;          // keys of a workgroup's range (a multiple of kIdxStep * kIdxWaves; prefill: of kIdxStep) and ranges per token / tile: set by the launcher
 };
 
 struct MlaTopkParams {
@@ -49,7 +51,44 @@ __host__ __device__ inline int idx_visible(int L, int seqlen_q, int t, int is_ca
     return n < 0 ? 0 : (n < L ? n : L);
 }
 
+// ---- device helpers the logits kernels of fa_mla_indexer.hip and fa_mla_indexer_prefill.hip share ------------------------------------------------
+// eight e4m3 codes -> eight elements of T, exactly (every e4m3 value is an fp16 and a bf16 value)
+template <typename T>
+FA_DEV u32x4 idx_widen8(uint32_t w0, uint32_t w1) {
+    if constexpr (__is_same(T, _Float16)) {
+        return u32x4{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, false)),
+                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w0, 1.0f, true)),
+                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, false)),
+                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w1, 1.0f, true))};
+    } else {
+        return u32x4{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, false)),
+                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w0, 1.0f, true)),
+                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, false)),
+                     __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w1, 1.0f, true))};
+    }
+}
+
+FA_DEV int idx_len(const int32_t* cache_seqlens, int bidx, int seqlen_cache) {
+    int L = seqlen_cache;
+    if (cache_seqlens != nullptr) {
+        const int cs = cache_seqlens[bidx];
+        L = min(cs > 0 ? cs : 0, seqlen_cache);
+    }
+    return __builtin_amdgcn_readfirstlane(L);
+}
+
 hipError_t launch_mla_indexer_logits(MlaIndexerParams p, int dtype, hipStream_t s);
 hipError_t launch_mla_indexer_topk(const MlaTopkParams& p, hipStream_t s);
+
+// ---- the prefill logits launch (fa_mla_indexer_prefill.hip): a workgroup serves kIdxpTQ consecutive tokens of one sequence and wg_keys keys ----------
+#ifndef FA_IDXP_TQ
+#define FA_IDXP_TQ 8
+#endif
+constexpr int kIdxpTQ = FA_IDXP_TQ;         // tokens of a tile: 4 = one a wave, 8 = two a wave
+constexpr int kIdxpMinWgKeys = 256;         // the shortest key range of a prefill workgroup: eight steps over which the tile's Q load is spread
+
+// wg_keys and n_chunks of a prefill launch over p.b x ceil(p.seqlen_q / kIdxpTQ) tiles (host only; p.seqlen_q >= 1)
+void mla_indexer_prefill_shape(MlaIndexerParams& p);
+hipError_t launch_mla_indexer_prefill_logits(MlaIndexerParams p, int dtype, hipStream_t s);
 
 }  // namespace fa

@@ -756,8 +756,9 @@ std::vector<at::Tensor> mha_fwd_mla_sparse_kvcache(at::Tensor q, at::Tensor kv_c
 
 // The DeepSeek-V3.2 indexer (fa_run_mla_indexer_logits / fa_run_mla_indexer_topk).  The Python layer has checked shapes and views; here the tensors become
 // pointers and strides.  logits (b, sq, capacity) fp32 is the caller's buffer: entries at or past a token's visible length are not written.
-void mla_indexer_logits(at::Tensor q_idx, at::Tensor weights, at::Tensor k_idx_cache, at::Tensor cache_seqlens, at::Tensor logits,
-                        c10::optional<at::Tensor> k_scale_, c10::optional<at::Tensor> block_table_, bool is_causal) {
+// run: fa_run_mla_indexer_logits (a workgroup per token) or fa_run_mla_indexer_prefill_logits (a workgroup per tile of tokens): one struct, one set of checks.
+static void mla_indexer_logits_with(int (*run)(const fa_mla_indexer_params*, void*), at::Tensor q_idx, at::Tensor weights, at::Tensor k_idx_cache, at::Tensor cache_seqlens,
+                                    at::Tensor logits, c10::optional<at::Tensor> k_scale_, c10::optional<at::Tensor> block_table_, bool is_causal) {
     TORCH_CHECK(q_idx.dim() == 4 && weights.dim() == 3 && k_idx_cache.dim() == 3 && logits.dim() == 3, "q_idx (b, sq, h, 128), weights (b, sq, h), k_idx_cache (b, capacity, 128), logits (b, sq, capacity)");
     TORCH_CHECK(q_idx.is_cuda(), "q_idx must be a GPU (HIP) tensor");
     for (const at::Tensor* t : {&weights, &k_idx_cache, &cache_seqlens, &logits}) TORCH_CHECK(t->device() == q_idx.device(), "every tensor must be on q_idx's device");
@@ -789,7 +790,17 @@ void mla_indexer_logits(at::Tensor q_idx, at::Tensor weights, at::Tensor k_idx_c
     p.weights_stride = fa_strides{weights.stride(0), weights.stride(1), weights.stride(2)};
     p.k_cache_batch_stride = k_idx_cache.stride(0); p.k_cache_row_stride = k_idx_cache.stride(1);      // (FP8: a 1-byte dtype, so these are bytes, as the format asks)
     p.logits_batch_stride = logits.stride(0); p.logits_row_stride = logits.stride(1);
-    check_status(fa_run_mla_indexer_logits(&p, current_stream(q_idx)));
+    check_status(run(&p, current_stream(q_idx)));
+}
+
+void mla_indexer_logits(at::Tensor q_idx, at::Tensor weights, at::Tensor k_idx_cache, at::Tensor cache_seqlens, at::Tensor logits,
+                        c10::optional<at::Tensor> k_scale_, c10::optional<at::Tensor> block_table_, bool is_causal) {
+    mla_indexer_logits_with(fa_run_mla_indexer_logits, q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale_, block_table_, is_causal);
+}
+
+void mla_indexer_prefill_logits(at::Tensor q_idx, at::Tensor weights, at::Tensor k_idx_cache, at::Tensor cache_seqlens, at::Tensor logits,
+                                c10::optional<at::Tensor> k_scale_, c10::optional<at::Tensor> block_table_, bool is_causal) {
+    mla_indexer_logits_with(fa_run_mla_indexer_prefill_logits, q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale_, block_table_, is_causal);
 }
 
 void mla_indexer_topk(at::Tensor logits, at::Tensor cache_seqlens, at::Tensor indices, bool is_causal) {
@@ -979,6 +990,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("lses"));
     m.def("mla_indexer_logits", &mla_indexer_logits,"index logits of the DeepSeek-V3.2 indexer into the caller's fp32 buffer (b, sq, capacity)", py::arg("q_idx"), py::arg("weights"),
           py::arg("k_idx_cache"), py::arg("cache_seqlens"), py::arg("logits"), py::arg("k_scale") = py::none(), py::arg("block_table") = py::none(), py::arg("is_causal") = true);
+    m.def("mla_indexer_prefill_logits", &mla_indexer_prefill_logits, "the same index logits for a prompt chunk: a workgroup per tile of tokens, the bits of mla_indexer_logits",
+          py::arg("q_idx"), py::arg("weights"), py::arg("k_idx_cache"), py::arg("cache_seqlens"), py::arg("logits"), py::arg("k_scale") = py::none(),
+          py::arg("block_table") = py::none(), py::arg("is_causal") = true);
     m.def("mla_cache_append", &mla_cache_append, "append latent rows (16-bit, or quantised to 656-byte FP8 rows) to the MLA latent cache, in place", py::arg("kv_cache"),
           py::arg("kv_new"), py::arg("cache_seqlens"), py::arg("k_pe") = py::none(), py::arg("block_table") = py::none(), py::arg("cu_seqlens_new") = py::none());
     m.def("mla_cache_gather", &mla_cache_gather, "gather (and dequantise) rows of the MLA latent cache into the caller's buffer", py::arg("kv_cache"),

@@ -307,6 +307,10 @@ def lib():
         L.fa_mla_sparse_num_splits.restype = ctypes.c_int32
         L.fa_run_mla_indexer_logits.argtypes = [ctypes.POINTER(MlaIndexerParams), _vp]
         L.fa_run_mla_indexer_logits.restype = ctypes.c_int
+        L.fa_run_mla_indexer_prefill_logits.argtypes = [ctypes.POINTER(MlaIndexerParams), _vp]
+        L.fa_run_mla_indexer_prefill_logits.restype = ctypes.c_int
+        L.fa_mla_indexer_prefill_launch.argtypes = [ctypes.POINTER(MlaIndexerParams)] + [ctypes.POINTER(ctypes.c_int32)] * 3
+        L.fa_mla_indexer_prefill_launch.restype = ctypes.c_int
         L.fa_run_mla_indexer_topk.argtypes = [ctypes.POINTER(MlaTopkParams), _vp]
         L.fa_run_mla_indexer_topk.restype = ctypes.c_int
         L.fa_run_mla_prefill_fwd.argtypes = [ctypes.POINTER(MlaPrefillParams), _vp]
@@ -766,6 +770,21 @@ def run_mla_indexer_logits(params, stream=None):
 
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     check(lib().fa_run_mla_indexer_logits(ctypes.byref(params), s))
+
+
+def run_mla_indexer_prefill_logits(params, stream=None):
+    """fa_run_mla_indexer_prefill_logits: the fa_mla_indexer_params of run_mla_indexer_logits, a workgroup per tile of tokens"""
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    check(lib().fa_run_mla_indexer_prefill_logits(ctypes.byref(params), s))
+
+
+def mla_indexer_prefill_launch(params):
+    """fa_mla_indexer_prefill_launch: (tokens of a workgroup's tile, keys of a workgroup's range, ranges per tile) of the launch these params would make; host only"""
+    tq, wg, nc = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    check(lib().fa_mla_indexer_prefill_launch(ctypes.byref(params), ctypes.byref(tq), ctypes.byref(wg), ctypes.byref(nc)))
+    return tq.value, wg.value, nc.value
 
 
 def mla_topk_params(logits, indices, cache_seqlens=None, causal=True):

@@ -923,6 +923,35 @@ def flash_mla_index_with_kvcache(q_idx, weights, k_idx_cache, cache_seqlens, top
     return (indices, logits) if return_logits else indices
 
 
+def flash_mla_indexer_prefill_logits(q_idx, weights, k_idx_cache, cache_seqlens, *, k_scale=None, block_table=None, causal=True):
+    """flash_mla_indexer_logits for a prompt chunk: the same arguments, checks and refusals, and the same bits in the same entries (a NaN key below L_i alone
+    differs: it gives NaN in its column for the tokens that see it, where flash_mla_indexer_logits leaves 0).
+
+    flash_mla_indexer_logits gives a workgroup one token, which loads and widens the visible index-key cache once per token of the chunk.  Here a
+    workgroup serves a tile of consecutive tokens of one sequence (4 or 8: capi.mla_indexer_prefill_launch) and stages each 32-key step once for all of
+    them.  ``seqlen_q`` is any value >= 1; at seqlen_q = 1 the decode call is the one to use.
+    Returns logits (batch, seqlen_q, capacity) float32, freshly allocated; entries at j >= n_t are NOT written.  Never read, so they may hold NaN codes
+    and NaN scales: cache rows and scales at or past L_i, pages wholly past L_i, pages no sequence references, and keys at or past the n_t of a tile's
+    last token.  No workspace, no atomics, no host synchronisation: a captured call replays with the lengths, tables and scales then in memory.
+    Deterministic."""
+    q_idx, cache_seqlens, capacity = _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, block_table, causal)
+    logits = torch.empty(q_idx.shape[0], q_idx.shape[1], capacity, dtype=torch.float32, device=q_idx.device)
+    _C.mla_indexer_prefill_logits(q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale, block_table, causal)
+    return logits
+
+
+def flash_mla_index_prefill_with_kvcache(q_idx, weights, k_idx_cache, cache_seqlens, topk, *, k_scale=None, block_table=None, causal=True, return_logits=False):
+    """flash_mla_index_with_kvcache for a prompt chunk: flash_mla_indexer_prefill_logits followed by flash_mla_indexer_topk over a logits buffer allocated
+    here.  Two launches; the indices (and logits) of flash_mla_index_with_kvcache, entry for entry."""
+    _check_topk(topk)
+    q_idx, cache_seqlens, capacity = _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, block_table, causal)
+    logits = torch.empty(q_idx.shape[0], q_idx.shape[1], capacity, dtype=torch.float32, device=q_idx.device)
+    _C.mla_indexer_prefill_logits(q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale, block_table, causal)
+    indices = torch.empty(q_idx.shape[0], q_idx.shape[1], topk, dtype=torch.int32, device=q_idx.device)
+    _C.mla_indexer_topk(logits, cache_seqlens, indices, causal)
+    return (indices, logits) if return_logits else indices
+
+
 def _check_prefill_view(name, t):
     """a tensor the prefill kernels address as it is: the last dimension contiguous, every other stride and the storage offset a multiple of 8 elements"""
     if t.shape[-1] > 1 and t.stride(-1) != 1:

@@ -887,6 +887,15 @@ typedef struct fa_mla_topk_params {
     int64_t logits_row_stride;
 } fa_mla_topk_params;
 
+/* Index logits for a prompt chunk (FA_HAS_MLA_INDEXER_PREFILL; fp8_mqa_logits next to fp8_paged_mqa_logits in DeepGEMM).  fa_run_mla_indexer_prefill_logits
+ * takes the fa_mla_indexer_params of fa_run_mla_indexer_logits - the same struct, the same checks, the same errors - and writes exactly the entries
+ * that call writes, with the same bits (but for a NaN key below L_i, which gives NaN in its column here and 0 there): a workgroup serves a tile of several consecutive tokens of one sequence and stages each 32-key step once for
+ * all of them, where fa_run_mla_indexer_logits gives a workgroup one token (right for seqlen_q = 1).  Entries at j >= n_t are never written; cache rows
+ * and scales at or past L_i, pages wholly past L_i, pages no sequence references and keys at or past the n_t of a tile's last token are never read.  One
+ * launch, no workspace, no atomics, no host synchronisation, deterministic.  b == 0 is FA_OK without a launch.  FA_ABI_VERSION is unchanged.
+ * fa_mla_indexer_prefill_launch says on the host what that launch would use. */
+#define FA_HAS_MLA_INDEXER_PREFILL 1
+
 /* MLA prefill attention (FA_HAS_MLA_PREFILL; DeepSeek-V2 / V3 / R1, Kimi K2 before weight absorption; the (192, 128) forward of flash-attn and FlashMLA).
  * Ordinary multi-head attention with d_qk = 192 wide queries and keys (128 no-rope columns, then 64 rope columns, RoPE already applied) and d_v = 128
  * wide values.  FA_ABI_VERSION is unchanged; the presence of fa_run_mla_prefill_fwd is how a caller detects the feature.  struct_size must be
@@ -1232,6 +1241,12 @@ int32_t fa_mla_sparse_num_splits(const fa_mla_sparse_params* params);
 /* One launch each on `stream`, no workspace, no host synchronisation: lengths, tables and scales are read on the device. */
 int fa_run_mla_indexer_logits(const fa_mla_indexer_params* params, void* stream);
 int fa_run_mla_indexer_topk(const fa_mla_topk_params* params, void* stream);
+/* The same logits for a prompt chunk (FA_HAS_MLA_INDEXER_PREFILL): the struct, the checks and the bits of fa_run_mla_indexer_logits. */
+int fa_run_mla_indexer_prefill_logits(const fa_mla_indexer_params* params, void* stream);
+/* Host-only, like fa_kvcache_row_tile_ex / fa_mla_num_splits: the tokens of a workgroup's tile (4 or 8), the keys of a workgroup's range (a multiple of
+ * 32) and the ranges per tile of the launch fa_run_mla_indexer_prefill_logits would make; its grid is b x ceil(seqlen_q / tokens_per_wg) x n_chunks.
+ * Any of the three pointers may be NULL.  Returns FA_OK or the error code of the launch (then nothing is written). */
+int fa_mla_indexer_prefill_launch(const fa_mla_indexer_params* params, int32_t* tokens_per_wg, int32_t* wg_keys, int32_t* n_chunks);
 
 /* ---- MLA prefill attention (fa_mla_prefill_params above) -------------------------------------- */
 /* One launch on `stream`, no workspace, no host synchronisation: cu_seqlens are read on the device. */

@@ -82,6 +82,9 @@ noise figure).  Against it, interleaved in one process: (i) the identity list 0 
 them) on one cache of that length, rotating over lists, (ii) 2048 random positions, sorted, (iii) the same positions unsorted.  At b in {1, 8} a second line
 per point records arm (i) under forced num_splits 8, 16, 32, 64 next to the automatic count, timed twice (profiles/kvcache_mla_sparse_bench.log).
 
+--mla-indexer-prefill measures flash_mla_indexer_prefill_logits on one prompt chunk (b 1, sq 128 / 512 / 2048 over 4k / 32k / 128k keys; bf16 q_idx, FP8 keys with
+scales, 64 heads, pages of 64, causal) against flash_mla_indexer_logits on the same inputs, interleaved, the decode call timed twice, the bits asserted equal
+first; ms, the ratio and sq x n x 64 x 128 x 2 FLOP over time under the mask, and the selection launch (profiles/mla_indexer_prefill_bench.log).
 --mla-indexer measures the DeepSeek-V3.2 indexer (flash_mla_indexer_logits / flash_mla_indexer_topk): bf16 q_idx, FP8 keys with per-token scales, 64 index
 heads, seqlen_q 1, topk 2048, pages of 64 (--paged P replaces the page size), b in {1, 8, 64} x L in {4k, 32k, 128k} (--length replaces them).  Per point,
 interleaved in one process: the logits call; the torch formulation of the logits (dequantise, einsum, relu, weighted sum, * k_scale; it reads the pool
@@ -1100,6 +1103,43 @@ def run_mla_indexer(lengths, pages, rounds):
         yield run_mla_indexer_point(b, L, (pages or [64])[0], rounds)
 
 
+def run_mla_indexer_prefill_point(sq, L, page, rounds, topk=2048, h=64):
+    """the prefill logits call against the decode logits call (timed twice: its own scatter) on one prompt chunk, and the selection launch; interleaved, bits asserted first"""
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(sq * 1000003 + L)
+    cols = L // page
+    q = torch.randn(1, sq, h, 128, device=dev, generator=gen).to(torch.bfloat16)
+    w = torch.randn(1, sq, h, device=dev, generator=gen) * (h ** -0.5)
+    cs = torch.full((1,), L, dtype=torch.int32, device=dev)
+    pool = torch.randn(cols, page, 128, device=dev, generator=gen).to(torch.float8_e4m3fn)
+    scales = torch.rand(cols, page, device=dev, generator=gen) + 0.5
+    table = torch.randperm(cols, device=dev, generator=gen).to(torch.int32).view(1, cols)
+    kw = dict(k_scale=scales, block_table=table, causal=True)
+    new = lambda: F.flash_mla_indexer_prefill_logits(q, w, pool, cs, **kw)
+    old = lambda: F.flash_mla_indexer_logits(q, w, pool, cs, **kw)
+    visible = torch.arange(L, device=dev).view(1, 1, L) < (L - sq + 1 + torch.arange(sq, device=dev)).clamp(0, L).view(1, sq, 1)
+    lg = new()
+    same = bool(torch.equal(lg.view(torch.int32)[visible], old().view(torch.int32)[visible]))
+    assert same, "the prefill logits differ from the decode call's"
+    p = capi.mla_indexer_params(q, w, pool, lg, cs, k_scale=scales, block_table=table, causal=True)
+    tq, wg_keys, n_chunks = capi.mla_indexer_prefill_launch(p)
+    sel = lambda: F.flash_mla_indexer_topk(lg, cs, topk, causal=True)
+    ms = _mlap_time({"prefill_logits": new, "logits": old, "logits_again": old, "topk": sel}, rounds)
+    pairs = int(visible.sum())                  # (token, key) pairs under the mask
+    flop = pairs * h * 128 * 2
+    del visible
+    return dict(mla_indexer_prefill=True, b=1, seqlen_q=sq, L=L, h=h, topk=topk, dtype="bfloat16", k_format="fp8_e4m3+scale", page_block_size=page, tokens_per_wg=tq,
+                wg_keys=wg_keys, n_chunks=n_chunks, ms={k: round(v, 5) for k, v in ms.items()}, prefill_over_logits=round(ms["prefill_logits"] / ms["logits"], 4),
+                logits_noise=round(ms["logits_again"] / ms["logits"], 4), token_key_pairs=pairs, prefill_tflops=round(flop / (ms["prefill_logits"] * 1e-3) / 1e12, 1),
+                logits_tflops=round(flop / (ms["logits"] * 1e-3) / 1e12, 1), bit_identical=same)
+
+
+def run_mla_indexer_prefill(lengths, pages, rounds):
+    for sq, L in itertools.product((128, 512, 2048), tuple(lengths or (4096, 32768, 131072))):
+        yield run_mla_indexer_prefill_point(sq, L, (pages or [64])[0], rounds)
+        torch.cuda.empty_cache()
+
+
 def _mlap_time(fns, rounds, iters=3):
     """median ms per call of each arm, the arms taken in turn within every round, `iters` calls per timed batch"""
     t = {k: [] for k in fns}
@@ -1455,6 +1495,9 @@ def main():
     ap.add_argument("--mla-indexer", action="store_true", help="the DeepSeek-V3.2 indexer (flash_mla_indexer_logits / flash_mla_indexer_topk; bf16, FP8 keys with scales, 64 heads, "
                                                                "topk 2048, pages of 64 or --paged P): the logits call against its HBM bound and the torch formulation (timed twice), the "
                                                                "selection against torch.topk")
+    ap.add_argument("--mla-indexer-prefill", action="store_true", help="flash_mla_indexer_prefill_logits against flash_mla_indexer_logits (timed twice) on one prompt chunk, and "
+                                                                       "the selection launch: bf16, FP8 keys with scales, 64 heads, pages of 64, causal, b 1, sq in {128, 512, "
+                                                                       "2048} x L in {4k, 32k, 128k}; bits asserted equal before timing")
     ap.add_argument("--mla-prefill", action="store_true", help="MLA prefill attention (flash_mla_prefill_func, bf16, h = h_k in {16, 128}) against fwd at head_dim 128 and "
                                                                "against the zero-padded head_dim-256 KV-cache call, each yardstick timed twice; with --baseline-library an A / B of "
                                                                "the call itself against that library")
@@ -1488,6 +1531,10 @@ def main():
             return
         if a.ragged and base is None:
             for line in run_ragged(a.quick, a.rounds):
+                print(json.dumps(line), flush=True)
+            return
+        if a.mla_indexer_prefill:
+            for line in run_mla_indexer_prefill(a.length, a.paged, a.rounds):
                 print(json.dumps(line), flush=True)
             return
         if a.mla_indexer:
