@@ -32,7 +32,7 @@ LIB_NAME = "libflash_attn_gfx950.so"
 LIB_PATH = os.path.join(CSRC, LIB_NAME)
 EXT_PATH = os.path.join(PKG, "_C.so")
 
-HIP_SOURCES = ["fa_fwd_pp.hip", "fa_fwd_pp16.hip", "fa_bwd.hip", "fa_bwd_dq16.hip", "fa_bwd_dkdv16.hip", "fa_fwd_kvcache.hip", "fa_fwd_kvcache_ragged.hip", "fa_fwd_kvcache_softcap.hip", "fa_fwd_kvcache_sink.hip", "fa_fwd_kvcache_tree.hip", "fa_fwd_kvcache_prefill.hip", "fa_fwd_kvcache_d256.hip", "fa_fwd_kvcache_mla.hip", "fa_fwd_kvcache_mla_sparse.hip", "fa_fwd_kvcache_mla_fp8.hip", "fa_mla_indexer.hip", "fa_mla_indexer_prefill.hip", "fa_kvcache_rotary.hip", "fa_fwd_mla_prefill.hip", "fa_bwd_mla_prefill.hip", "fa_merge_states.hip", "fa_mla_cache_io.hip", "fa_capi.hip"]
+HIP_SOURCES = ["fa_fwd_pp.hip", "fa_fwd_pp16.hip", "fa_bwd.hip", "fa_bwd_dq16.hip", "fa_bwd_dkdv16.hip", "fa_fwd_kvcache.hip", "fa_fwd_kvcache_ragged.hip", "fa_fwd_kvcache_softcap.hip", "fa_fwd_kvcache_sink.hip", "fa_fwd_kvcache_tree.hip", "fa_fwd_kvcache_prefill.hip", "fa_fwd_kvcache_d256.hip", "fa_fwd_kvcache_mla.hip", "fa_fwd_kvcache_mla_sparse.hip", "fa_fwd_kvcache_mla_fp8.hip", "fa_mla_indexer.hip", "fa_mla_indexer_prefill.hip", "fa_kvcache_rotary.hip", "fa_fwd_mla_prefill.hip", "fa_bwd_mla_prefill.hip", "fa_merge_states.hip", "fa_mla_cache_io.hip", "fa_mla_indexer_fp8q.hip", "fa_mla_indexer_prefill_fp8q.hip", "fa_capi.hip"]
 # per-file extra flags.  fa_fwd_pp16.hip: hipcc's SLP vectoriser packs the softmax row-sum adds and the O rescale into v_pk_* on register
 # pairs it first has to assemble from the 4-register MFMA tiles: ~200 v_mov_b64 per three tiles and 44-116 bytes of spills on the hot path
 # fa_fwd_kvcache_d256.hip (one workgroup per compute unit, 256 VGPRs + 256 AGPRs a lane): the K / V prefetch sets may live in either half of the register file, O^T and
@@ -90,7 +90,7 @@ _DMA_LATE = {"fa_fwd_pp16.hip": ["-DFA_PP16_DMA_DEBUG=1"], "fa_bwd_dkdv16.hip": 
 _DMA_SLEEPY = {s: [f[0][:-1] + "2"] for s, f in _DMA_LATE.items()}
 # the 64-row bodies (KV cache, MLA decode, MLA prefill) and the prefill index logits: four waves stage a quarter of a step each through registers into one of two LDS
 # stages (fa_kvcache_stage.hpp)
-STAGE_SOURCES = ["fa_fwd_kvcache_prefill.hip", "fa_fwd_kvcache_mla.hip", "fa_fwd_kvcache_mla_sparse.hip", "fa_fwd_kvcache_mla_fp8.hip", "fa_fwd_mla_prefill.hip", "fa_bwd_mla_prefill.hip", "fa_mla_indexer_prefill.hip"]
+STAGE_SOURCES = ["fa_fwd_kvcache_prefill.hip", "fa_fwd_kvcache_mla.hip", "fa_fwd_kvcache_mla_sparse.hip", "fa_fwd_kvcache_mla_fp8.hip", "fa_fwd_mla_prefill.hip", "fa_bwd_mla_prefill.hip", "fa_mla_indexer_prefill.hip", "fa_mla_indexer_prefill_fp8q.hip"]
 DEBUG_VARIANTS = {
     "dma_late": _DMA_LATE,                  # every request issued directly in front of the wait that retires it
     "dma_sleepy": _DMA_SLEEPY,              # group B / waves 4-7 sleep ~4000 cycles in front of every request
@@ -270,7 +270,7 @@ def build_torch_module(force=False):
 
 
 def build_all(force=False, torch_module=True, debug_variants=True):
-    """debug_variants: the test builds of tests/test_dma_protocol_gpu.py and tests/test_stage_protocol_gpu.py and tests/test_mla_indexer_prefill_gpu.py (csrc/debug/, 33 extra compiles; never packaged).  An in-tree developer / CI build wants
+    """debug_variants: the test builds of tests/test_dma_protocol_gpu.py and tests/test_stage_protocol_gpu.py and tests/test_mla_indexer_prefill_gpu.py (csrc/debug/, 36 extra compiles; never packaged).  An in-tree developer / CI build wants
     them (the GPU suite loads them), an installation does not: setup.py and `build.py --no-debug` leave them out."""
     build_kernels(force)
     if debug_variants:

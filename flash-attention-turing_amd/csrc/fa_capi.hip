@@ -1119,10 +1119,27 @@ int fa_run_mla_sparse_fwd_kvcache(const fa_mla_sparse_params* user, void* stream
 }
 
 // ---- the indexer in front of sparse MLA decode -------------------------------------------------------------------------------------------------
-static int fill_mla_indexer(const fa_mla_indexer_params* user, fa::MlaIndexerParams& ip, fa_mla_indexer_params& local) {
-    int rc = import_exact(user, local, "fa_mla_indexer_params");
-    if (rc) return rc;
-    const fa_mla_indexer_params* p = &local;
+// fa_mla_indexer_params (216 bytes) and fa_mla_indexer_params_v2 (q_format appended) share their prefix.  v2_entry: one of the _v2 entry points, which take either
+// struct and tell them apart by struct_size (the shorter one arrives as a _v2 with q_format = FA_IDX_Q_16BIT); the entry points without _v2 take the 216-byte
+// struct alone (import_exact).  With FA_IDX_Q_FP8_E4M3 q_idx holds e4m3 codes, its strides count bytes and the launch is one of the _fp8q ones.
+static_assert(sizeof(fa_mla_indexer_params_v2) == sizeof(fa_mla_indexer_params) + 8 && offsetof(fa_mla_indexer_params_v2, q_format) == sizeof(fa_mla_indexer_params) &&
+                  offsetof(fa_mla_indexer_params_v2, block_table_stride) == offsetof(fa_mla_indexer_params, block_table_stride),
+              "fa_mla_indexer_params_v2 is fa_mla_indexer_params with two int32 appended");
+static int fill_mla_indexer(const void* user_, bool v2_entry, fa::MlaIndexerParams& ip, fa_mla_indexer_params_v2& local) {
+    memset(&local, 0, sizeof(local));
+    int rc;
+    if (!v2_entry) {
+        rc = import_exact(static_cast<const fa_mla_indexer_params*>(user_), reinterpret_cast<fa_mla_indexer_params&>(local), "fa_mla_indexer_params");
+        if (rc) return rc;
+    } else {
+        const fa_mla_indexer_params_v2* user = static_cast<const fa_mla_indexer_params_v2*>(user_);
+        if ((rc = check_header(user, "fa_mla_indexer_params_v2", true))) return rc;
+        if (user->struct_size != sizeof(fa_mla_indexer_params) && user->struct_size != sizeof(fa_mla_indexer_params_v2))
+            return fail(FA_ERR_BAD_ABI, "fa_mla_indexer_params_v2: struct_size %u is neither %zu (fa_mla_indexer_params) nor %zu - header / library mismatch", user->struct_size,
+                        sizeof(fa_mla_indexer_params), sizeof(fa_mla_indexer_params_v2));
+        memcpy(&local, user, user->struct_size);
+    }
+    const fa_mla_indexer_params_v2* p = &local;
     const bool paged = p->block_table != nullptr;
     if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0)
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d", p->b, p->seqlen_q, p->seqlen_cache);
@@ -1132,6 +1149,12 @@ static int fill_mla_indexer(const fa_mla_indexer_params* user, fa::MlaIndexerPar
     if (p->k_format != FA_MLA_KV_16BIT && p->k_format != FA_IDX_K_FP8_E4M3)
         return fail(FA_ERR_BAD_DTYPE, "k_format %d unknown (0 = keys of dtype, 1 = OCP e4m3 codes)", p->k_format);
     if ((rc = check_reserved(p->reserved_, "fa_mla_indexer_params", FA_ERR_BAD_SHAPE))) return rc;
+    if (p->q_format != FA_IDX_Q_16BIT && p->q_format != FA_IDX_Q_FP8_E4M3)
+        return fail(FA_ERR_BAD_DTYPE, "q_format %d unknown (0 = queries of dtype, 1 = OCP e4m3 codes)", p->q_format);
+    if (p->reserved2_ != 0) return fail(FA_ERR_BAD_SHAPE, "reserved2_ is not zero (%d)", p->reserved2_);
+    const bool q8 = p->q_format == FA_IDX_Q_FP8_E4M3;
+    if (q8 && p->k_format != FA_IDX_K_FP8_E4M3)
+        return fail(FA_ERR_BAD_DTYPE, "k_format %d: e4m3 index queries (q_format = 1) need an e4m3 index-key cache (k_format = 1)", p->k_format);
     if ((rc = check_paged(p->block_table, p->block_table_stride, p->page_block_size, p->num_blocks, p->seqlen_cache))) return rc;
     // a workgroup's key range ends at most kIdxMaxWgKeys past the capacity, and the grid is one-dimensional
     if (p->seqlen_cache > INT32_MAX - 2 * fa::kIdxMaxWgKeys) return fail(FA_ERR_BAD_SHAPE, "seqlen_cache %d too large", p->seqlen_cache);
@@ -1150,8 +1173,10 @@ static int fill_mla_indexer(const fa_mla_indexer_params* user, fa::MlaIndexerPar
         if (p->q_idx == nullptr) return fail(FA_ERR_NULL_POINTER, "q_idx is NULL");
         const fa_strides& qs = p->q_idx_stride;
         if ((reinterpret_cast<uintptr_t>(p->q_idx) & 15u) != 0) return fail(FA_ERR_BAD_STRIDE, "q_idx base pointer must be 16-byte aligned");
-        if (qs.head % 8 != 0 || qs.row % 8 != 0 || qs.batch % 8 != 0)
-            return fail(FA_ERR_BAD_STRIDE, "q_idx strides (batch=%lld,row=%lld,head=%lld) must be multiples of 8 elements", (long long)qs.batch, (long long)qs.row, (long long)qs.head);
+        const int qunit = q8 ? 16 : 8;  // 16-byte loads: bytes of codes, or elements of dtype
+        if (qs.head % qunit != 0 || qs.row % qunit != 0 || qs.batch % qunit != 0)
+            return fail(FA_ERR_BAD_STRIDE, "q_idx strides (batch=%lld,row=%lld,head=%lld) must be multiples of %d %s", (long long)qs.batch, (long long)qs.row, (long long)qs.head,
+                        qunit, q8 ? "bytes" : "elements");
         if ((rc = check_idx_cache(*p))) return rc;
         if (p->k_scale != nullptr && (reinterpret_cast<uintptr_t>(p->k_scale) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "k_scale must be 4-byte aligned");
     }
@@ -1170,35 +1195,43 @@ static int fill_mla_indexer(const fa_mla_indexer_params* user, fa::MlaIndexerPar
     return FA_OK;
 }
 
-int fa_run_mla_indexer_logits(const fa_mla_indexer_params* user, void* stream) {
+static int run_mla_indexer_logits(const void* user, bool v2_entry, bool prefill, void* stream) {
     fa::MlaIndexerParams ip;
-    fa_mla_indexer_params local;
-    int rc = fill_mla_indexer(user, ip, local);
+    fa_mla_indexer_params_v2 local;
+    int rc = fill_mla_indexer(user, v2_entry, ip, local);
     if (rc) return rc;
     if (ip.b == 0 || ip.seqlen_cache == 0) return FA_OK;        // nothing to write
-    return hip_status(fa::launch_mla_indexer_logits(ip, local.dtype, (hipStream_t)stream), "fa_mla_indexer_logits launch");
+    hipStream_t s = (hipStream_t)stream;
+    if (local.q_format == FA_IDX_Q_FP8_E4M3)
+        return prefill ? hip_status(fa::launch_mla_indexer_prefill_logits_fp8q(ip, s), "fa_mla_indexer_prefill_logits_fp8q launch")
+                       : hip_status(fa::launch_mla_indexer_logits_fp8q(ip, s), "fa_mla_indexer_logits_fp8q launch");
+    return prefill ? hip_status(fa::launch_mla_indexer_prefill_logits(ip, local.dtype, s), "fa_mla_indexer_prefill_logits launch")
+                   : hip_status(fa::launch_mla_indexer_logits(ip, local.dtype, s), "fa_mla_indexer_logits launch");
 }
 
-// the prompt-chunk form of fa_run_mla_indexer_logits: the same struct through the same fill_mla_indexer
-int fa_run_mla_indexer_prefill_logits(const fa_mla_indexer_params* user, void* stream) {
+static int mla_indexer_prefill_launch(const void* user, bool v2_entry, int32_t* tokens_per_wg, int32_t* wg_keys, int32_t* n_chunks) {
     fa::MlaIndexerParams ip;
-    fa_mla_indexer_params local;
-    int rc = fill_mla_indexer(user, ip, local);
-    if (rc) return rc;
-    if (ip.b == 0 || ip.seqlen_cache == 0) return FA_OK;        // nothing to write
-    return hip_status(fa::launch_mla_indexer_prefill_logits(ip, local.dtype, (hipStream_t)stream), "fa_mla_indexer_prefill_logits launch");
-}
-
-int fa_mla_indexer_prefill_launch(const fa_mla_indexer_params* user, int32_t* tokens_per_wg, int32_t* wg_keys, int32_t* n_chunks) {
-    fa::MlaIndexerParams ip;
-    fa_mla_indexer_params local;
-    int rc = fill_mla_indexer(user, ip, local);
+    fa_mla_indexer_params_v2 local;
+    int rc = fill_mla_indexer(user, v2_entry, ip, local);
     if (rc) return rc;
     fa::mla_indexer_prefill_shape(ip);
     if (tokens_per_wg != nullptr) *tokens_per_wg = fa::kIdxpTQ;
     if (wg_keys != nullptr) *wg_keys = ip.wg_keys;
     if (n_chunks != nullptr) *n_chunks = ip.n_chunks;
     return FA_OK;
+}
+
+int fa_run_mla_indexer_logits(const fa_mla_indexer_params* user, void* stream) { return run_mla_indexer_logits(user, false, false, stream); }
+// the prompt-chunk form of fa_run_mla_indexer_logits: the same struct through the same fill_mla_indexer
+int fa_run_mla_indexer_prefill_logits(const fa_mla_indexer_params* user, void* stream) { return run_mla_indexer_logits(user, false, true, stream); }
+int fa_mla_indexer_prefill_launch(const fa_mla_indexer_params* user, int32_t* tokens_per_wg, int32_t* wg_keys, int32_t* n_chunks) {
+    return mla_indexer_prefill_launch(user, false, tokens_per_wg, wg_keys, n_chunks);
+}
+// the same three for fa_mla_indexer_params_v2 (or, by struct_size, the 216-byte struct)
+int fa_run_mla_indexer_logits_v2(const fa_mla_indexer_params_v2* user, void* stream) { return run_mla_indexer_logits(user, true, false, stream); }
+int fa_run_mla_indexer_prefill_logits_v2(const fa_mla_indexer_params_v2* user, void* stream) { return run_mla_indexer_logits(user, true, true, stream); }
+int fa_mla_indexer_prefill_launch_v2(const fa_mla_indexer_params_v2* user, int32_t* tokens_per_wg, int32_t* wg_keys, int32_t* n_chunks) {
+    return mla_indexer_prefill_launch(user, true, tokens_per_wg, wg_keys, n_chunks);
 }
 
 int fa_run_mla_indexer_topk(const fa_mla_topk_params* user, void* stream) {

@@ -366,8 +366,9 @@ __global__ __launch_bounds__(kTopkThreads) void fa_mla_indexer_topk_kernel(const
 
 }  // namespace
 
-hipError_t launch_mla_indexer_logits(MlaIndexerParams p, int dtype, hipStream_t s) {
-    if (p.h != 16 && p.h != 32 && p.h != 64) return hipErrorInvalidValue;
+// wg_keys, n_chunks and the grid of a decode logits launch (0: nothing the kernels can run)
+int64_t mla_indexer_logits_shape(MlaIndexerParams& p) {
+    if (p.h != 16 && p.h != 32 && p.h != 64) return 0;
     // the key range of a workgroup: two workgroups per compute unit over b x seqlen_q tokens, in multiples of one step per wave
     const int64_t tokens = (int64_t)p.b * p.seqlen_q, target = 2 * device_cu_count();
     constexpr int64_t unit = kIdxStep * kIdxWaves;
@@ -377,7 +378,12 @@ hipError_t launch_mla_indexer_logits(MlaIndexerParams p, int dtype, hipStream_t 
     p.wg_keys = (int)wg;
     p.n_chunks = (int)((p.seqlen_cache + wg - 1) / wg);
     const int64_t grid = tokens * p.n_chunks;
-    if (grid <= 0 || grid >= ((int64_t)1 << 31)) return hipErrorInvalidValue;
+    return grid <= 0 || grid >= ((int64_t)1 << 31) ? 0 : grid;
+}
+
+hipError_t launch_mla_indexer_logits(MlaIndexerParams p, int dtype, hipStream_t s) {
+    const int64_t grid = mla_indexer_logits_shape(p);
+    if (grid == 0) return hipErrorInvalidValue;
     const bool paged = p.block_table != nullptr;
     auto launch = [&](auto* tt) {
         using T = std::remove_pointer_t<decltype(tt)>;

@@ -68,6 +68,24 @@ FA_DEV u32x4 idx_widen8(uint32_t w0, uint32_t w1) {
     }
 }
 
+// relu(x) that keeps a NaN: the IEEE 754-2019 maximum (v_maximum3_f32), where the fmaxf of fa_mla_indexer.hip (v_max_f32, maximumNumber) returns 0 for a NaN
+// dot product.  For every x that is not a NaN both give the same bits, so the bit relation to the decode call holds wherever no visible key holds a NaN; a
+// NaN key gives NaN in its column here and 0 there.  (The 16-bit q_idx prefill kernels and both FP8 q_idx kernels use this one.)
+FA_DEV float idxp_relu(float x) { return __builtin_elementwise_maximum(x, 0.f); }
+
+// ---- FP8 q_idx (fa_mla_indexer_fp8q.hip, fa_mla_indexer_prefill_fp8q.hip): a whole 128-wide index head in one MFMA ------------------------------------
+// acc += A B on v_mfma_f32_16x16x128_f8f6f4, both operands OCP e4m3 (format selectors 0 / 0), no block scales (the scale operands are literal zeros: the
+// unscaled encoding).  A lane's operand is 32 codes: lo = bytes 16 g .. 16 g + 15, hi = bytes 64 + 16 g .. of row lane & 15 (g = lane >> 4), for A (a head of Q)
+// and B (a key) alike.  Nothing is assumed about which contraction index the instruction gives each of those 32 bytes beyond "A and B of one lane group use
+// the same ones": both sides permute the 128 columns identically, so the sum covers every column once.  C / D: lane = column (key) lane & 15, register r =
+// row (head) 4 g + r, as for 16x16x32.
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+FA_DEV f32x4 idx_mfma_e4m3(const u32x4& alo, const u32x4& ahi, const u32x4& blo, const u32x4& bhi, f32x4 acc) {
+    const i32x8 a = {(int)alo.x, (int)alo.y, (int)alo.z, (int)alo.w, (int)ahi.x, (int)ahi.y, (int)ahi.z, (int)ahi.w};
+    const i32x8 b = {(int)blo.x, (int)blo.y, (int)blo.z, (int)blo.w, (int)bhi.x, (int)bhi.y, (int)bhi.z, (int)bhi.w};
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, acc, 0, 0, 0, 0, 0, 0);
+}
+
 FA_DEV int idx_len(const int32_t* cache_seqlens, int bidx, int seqlen_cache) {
     int L = seqlen_cache;
     if (cache_seqlens != nullptr) {
@@ -77,6 +95,7 @@ FA_DEV int idx_len(const int32_t* cache_seqlens, int bidx, int seqlen_cache) {
     return __builtin_amdgcn_readfirstlane(L);
 }
 
+int64_t mla_indexer_logits_shape(MlaIndexerParams& p);    // wg_keys, n_chunks -> the grid; 0: not launchable (host only)
 hipError_t launch_mla_indexer_logits(MlaIndexerParams p, int dtype, hipStream_t s);
 hipError_t launch_mla_indexer_topk(const MlaTopkParams& p, hipStream_t s);
 
@@ -90,5 +109,9 @@ constexpr int kIdxpMinWgKeys = 256;         // the shortest key range of a prefi
 // wg_keys and n_chunks of a prefill launch over p.b x ceil(p.seqlen_q / kIdxpTQ) tiles (host only; p.seqlen_q >= 1)
 void mla_indexer_prefill_shape(MlaIndexerParams& p);
 hipError_t launch_mla_indexer_prefill_logits(MlaIndexerParams p, int dtype, hipStream_t s);
+
+// ---- FP8 (e4m3) q_idx over an FP8 cache: the launches above with q_ptr holding codes and q_batch / q_row / q_head in bytes (p.cache_fp8 is set) ----------
+hipError_t launch_mla_indexer_logits_fp8q(MlaIndexerParams p, hipStream_t s);             // fa_mla_indexer_fp8q.hip
+hipError_t launch_mla_indexer_prefill_logits_fp8q(MlaIndexerParams p, hipStream_t s);     // fa_mla_indexer_prefill_fp8q.hip
 
 }  // namespace fa

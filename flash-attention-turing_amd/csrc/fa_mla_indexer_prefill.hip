@@ -36,11 +36,6 @@ static_assert(kIdxStep == kKvcStep && kIdxMaxWgKeys % kKvcStep == 0 && kIdxpMinW
 constexpr int kIdxpNT = kIdxpTQ / kIdxWaves;        // tokens of a wave
 constexpr int kIdxpImage = kKvcStep * kIdxD * 2;    // 32 rows x 256 B
 
-// relu(x) that keeps a NaN: the IEEE 754-2019 maximum (v_maximum3_f32), where the fmaxf of fa_mla_indexer.hip (v_max_f32, maximumNumber) returns 0 for a NaN
-// dot product.  For every x that is not a NaN both give the same bits, so the bit relation to the decode call holds wherever no visible key holds a NaN; a
-// NaN key gives NaN in its column here and 0 there.
-FA_DEV float idxp_relu(float x) { return __builtin_elementwise_maximum(x, 0.f); }
-
 // ES = bytes per cache element: 2 = T, 1 = e4m3 codes
 template <typename T, int ES, bool PAGED>
 __global__ __launch_bounds__(kIdxThreads, 2) void fa_mla_indexer_prefill_logits_kernel(const MlaIndexerParams p) {

@@ -757,7 +757,7 @@ std::vector<at::Tensor> mha_fwd_mla_sparse_kvcache(at::Tensor q, at::Tensor kv_c
 // The DeepSeek-V3.2 indexer (fa_run_mla_indexer_logits / fa_run_mla_indexer_topk).  The Python layer has checked shapes and views; here the tensors become
 // pointers and strides.  logits (b, sq, capacity) fp32 is the caller's buffer: entries at or past a token's visible length are not written.
 // run: fa_run_mla_indexer_logits (a workgroup per token) or fa_run_mla_indexer_prefill_logits (a workgroup per tile of tokens): one struct, one set of checks.
-static void mla_indexer_logits_with(int (*run)(const fa_mla_indexer_params*, void*), at::Tensor q_idx, at::Tensor weights, at::Tensor k_idx_cache, at::Tensor cache_seqlens,
+static void mla_indexer_logits_with(int (*run)(const fa_mla_indexer_params_v2*, void*), at::Tensor q_idx, at::Tensor weights, at::Tensor k_idx_cache, at::Tensor cache_seqlens,
                                     at::Tensor logits, c10::optional<at::Tensor> k_scale_, c10::optional<at::Tensor> block_table_, bool is_causal) {
     TORCH_CHECK(q_idx.dim() == 4 && weights.dim() == 3 && k_idx_cache.dim() == 3 && logits.dim() == 3, "q_idx (b, sq, h, 128), weights (b, sq, h), k_idx_cache (b, capacity, 128), logits (b, sq, capacity)");
     TORCH_CHECK(q_idx.is_cuda(), "q_idx must be a GPU (HIP) tensor");
@@ -765,13 +765,13 @@ static void mla_indexer_logits_with(int (*run)(const fa_mla_indexer_params*, voi
     TORCH_CHECK(weights.scalar_type() == torch::kFloat32 && logits.scalar_type() == torch::kFloat32, "weights and logits must be float32");
     TORCH_CHECK(cache_seqlens.scalar_type() == torch::kInt32 && cache_seqlens.dim() == 1 && cache_seqlens.size(0) == q_idx.size(0) && cache_seqlens.is_contiguous(),
                 "cache_seqlens must be a contiguous int32 tensor of shape [batch_size]");
-    const bool fp8 = k_idx_cache.element_size() == 1;
-    TORCH_CHECK(fp8 || k_idx_cache.scalar_type() == q_idx.scalar_type(), "k_idx_cache must have the dtype of q_idx or hold e4m3 codes");
+    const bool fp8 = k_idx_cache.element_size() == 1, q8 = q_idx.element_size() == 1;      // (q8: e4m3 codes; the strides below then count bytes, as q_format asks)
+    TORCH_CHECK(fp8 || (!q8 && k_idx_cache.scalar_type() == q_idx.scalar_type()), "k_idx_cache must have the dtype of q_idx or hold e4m3 codes; e4m3 q_idx needs an e4m3 cache");
     TORCH_CHECK(q_idx.stride(3) == 1 && k_idx_cache.stride(2) == 1 && logits.stride(2) == 1, "q_idx, k_idx_cache, logits: last dimension must be contiguous");
     const int64_t batch_size = q_idx.size(0), seqlen_q = q_idx.size(1);
     int64_t seqlen_cache = k_idx_cache.size(1);
     c10::DeviceGuard guard(q_idx.device());
-    fa_mla_indexer_params p;
+    fa_mla_indexer_params_v2 p;
     FA_PARAMS_INIT(p);
     if (block_table_.has_value()) seqlen_cache = attach_block_table(p, q_idx, batch_size, *block_table_, k_idx_cache, true);
     TORCH_CHECK(logits.size(0) == batch_size && logits.size(1) == seqlen_q && logits.size(2) == seqlen_cache, "logits must have shape [batch_size, seqlen_q, capacity]");
@@ -784,8 +784,8 @@ static void mla_indexer_logits_with(int (*run)(const fa_mla_indexer_params*, voi
         p.k_scale = ks.data_ptr<float>(); p.k_scale_batch_stride = ks.stride(0); p.k_scale_row_stride = ks.stride(1);
     }
     p.b = (int32_t)batch_size; p.seqlen_q = (int32_t)seqlen_q; p.seqlen_cache = (int32_t)seqlen_cache;
-    p.h = (int32_t)q_idx.size(2); p.d = (int32_t)q_idx.size(3); p.dtype = fa_dtype_of(q_idx);
-    p.k_format = fp8 ? FA_IDX_K_FP8_E4M3 : FA_MLA_KV_16BIT; p.is_causal = is_causal;
+    p.h = (int32_t)q_idx.size(2); p.d = (int32_t)q_idx.size(3); p.dtype = q8 ? FA_BF16 : fa_dtype_of(q_idx);      // (q8: a valid value that is not used)
+    p.k_format = fp8 ? FA_IDX_K_FP8_E4M3 : FA_MLA_KV_16BIT; p.q_format = q8 ? FA_IDX_Q_FP8_E4M3 : FA_IDX_Q_16BIT; p.is_causal = is_causal;
     p.q_idx_stride = strides4(q_idx);
     p.weights_stride = fa_strides{weights.stride(0), weights.stride(1), weights.stride(2)};
     p.k_cache_batch_stride = k_idx_cache.stride(0); p.k_cache_row_stride = k_idx_cache.stride(1);      // (FP8: a 1-byte dtype, so these are bytes, as the format asks)
@@ -795,12 +795,12 @@ static void mla_indexer_logits_with(int (*run)(const fa_mla_indexer_params*, voi
 
 void mla_indexer_logits(at::Tensor q_idx, at::Tensor weights, at::Tensor k_idx_cache, at::Tensor cache_seqlens, at::Tensor logits,
                         c10::optional<at::Tensor> k_scale_, c10::optional<at::Tensor> block_table_, bool is_causal) {
-    mla_indexer_logits_with(fa_run_mla_indexer_logits, q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale_, block_table_, is_causal);
+    mla_indexer_logits_with(fa_run_mla_indexer_logits_v2, q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale_, block_table_, is_causal);
 }
 
 void mla_indexer_prefill_logits(at::Tensor q_idx, at::Tensor weights, at::Tensor k_idx_cache, at::Tensor cache_seqlens, at::Tensor logits,
                                 c10::optional<at::Tensor> k_scale_, c10::optional<at::Tensor> block_table_, bool is_causal) {
-    mla_indexer_logits_with(fa_run_mla_indexer_prefill_logits, q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale_, block_table_, is_causal);
+    mla_indexer_logits_with(fa_run_mla_indexer_prefill_logits_v2, q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale_, block_table_, is_causal);
 }
 
 void mla_indexer_topk(at::Tensor logits, at::Tensor cache_seqlens, at::Tensor indices, bool is_causal) {

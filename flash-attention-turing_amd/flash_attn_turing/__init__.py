@@ -50,6 +50,7 @@ from .interface import (  # noqa: E402,F401
     flash_mla_cache_gather,
     flash_mla_index_cache_append,
     quantize_mla_index_keys,
+    quantize_mla_index_queries,
     quantize_mla_kv_cache,
     dequantize_mla_kv_cache,
     pack_tree_mask,
@@ -61,7 +62,7 @@ from .sharding import ShardPlan, plan_shards, shard_tensor, problem_policy  # no
 
 __all__ = [
     "fwd", "bwd", "varlen_fwd", "varlen_bwd", "fwd_kvcache",
-    "flash_attn_func", "flash_attn_varlen_func", "flash_attn_with_kvcache", "flash_mla_with_kvcache", "flash_mla_sparse_with_kvcache", "flash_mla_indexer_logits", "flash_mla_indexer_topk", "flash_mla_index_with_kvcache", "flash_mla_indexer_prefill_logits", "flash_mla_index_prefill_with_kvcache", "flash_mla_prefill_func", "flash_mla_prefill_bwd", "flash_mla_attn_func", "flash_attn_merge_states", "flash_attn_with_shared_prefix", "flash_mla_chunked_prefill_func", "flash_mla_cache_append", "flash_mla_cache_gather", "flash_mla_index_cache_append", "quantize_mla_index_keys", "quantize_mla_kv_cache", "dequantize_mla_kv_cache", "pack_tree_mask", "tree_mask_from_parents", "FlashAttnFunc", "FlashAttnVarlenFunc",
+    "flash_attn_func", "flash_attn_varlen_func", "flash_attn_with_kvcache", "flash_mla_with_kvcache", "flash_mla_sparse_with_kvcache", "flash_mla_indexer_logits", "flash_mla_indexer_topk", "flash_mla_index_with_kvcache", "flash_mla_indexer_prefill_logits", "flash_mla_index_prefill_with_kvcache", "flash_mla_prefill_func", "flash_mla_prefill_bwd", "flash_mla_attn_func", "flash_attn_merge_states", "flash_attn_with_shared_prefix", "flash_mla_chunked_prefill_func", "flash_mla_cache_append", "flash_mla_cache_gather", "flash_mla_index_cache_append", "quantize_mla_index_keys", "quantize_mla_index_queries", "quantize_mla_kv_cache", "dequantize_mla_kv_cache", "pack_tree_mask", "tree_mask_from_parents", "FlashAttnFunc", "FlashAttnVarlenFunc",
     "ShardPlan", "plan_shards", "shard_tensor", "problem_policy", "LIBRARY_PATH", "EXTENSION_PATH",
     "set_kernel_policy", "kernel_name",
 ]

@@ -167,6 +167,11 @@ class MlaIndexerParams(_Params):
                 ("block_table_stride", ctypes.c_int64)]
 
 
+class MlaIndexerParamsV2(_Params):
+    """fa_mla_indexer_params_v2: fa_mla_indexer_params plus q_format (the *_v2 entry points; run_mla_indexer_logits and its kin pick them by the class)"""
+    _fields_ = MlaIndexerParams._fields_ + [("q_format", _i32), ("reserved2_", _i32)]
+
+
 class MlaTopkParams(_Params):
     """fa_mla_topk_params: the top-k selection over index logits (fa_run_mla_indexer_topk)"""
     _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("logits", _vp), ("indices", _vp), ("cache_seqlens", _vp),
@@ -243,6 +248,8 @@ class MlaIndexCacheAppendParams(_Params):
 FA_MLA_KV_16BIT = 0
 FA_MLA_KV_FP8_ROWS656 = 1     # 656-byte latent rows: 512 e4m3 codes, four fp32 scales, 64 rope elements of q's dtype; kv_cache_stride in bytes
 FA_CACHE_FP8_E4M3 = 1
+FA_IDX_Q_16BIT = 0            # q_format of fa_mla_indexer_params_v2: index queries of `dtype`, strides in elements
+FA_IDX_Q_FP8_E4M3 = 1         # ... as OCP e4m3 codes, strides in bytes (needs k_format = FA_IDX_K_FP8_E4M3)
 FA_IDX_K_FP8_E4M3 = 1         # k_format of fa_mla_indexer_params: index keys as OCP e4m3 codes, strides in bytes
 FA_IDX_SCALE_FP32, FA_IDX_SCALE_UE8M0 = 0, 1     # scale_format of fa_mla_index_cache_append_params
 
@@ -310,6 +317,13 @@ def lib():
         L.fa_run_mla_indexer_prefill_logits.argtypes = [ctypes.POINTER(MlaIndexerParams), _vp]
         L.fa_run_mla_indexer_prefill_logits.restype = ctypes.c_int
         L.fa_mla_indexer_prefill_launch.argtypes = [ctypes.POINTER(MlaIndexerParams)] + [ctypes.POINTER(ctypes.c_int32)] * 3
+        # (fa_mla_indexer_params_v2 or fa_mla_indexer_params through the same pointer: void*)
+        L.fa_run_mla_indexer_logits_v2.argtypes = [_vp, _vp]
+        L.fa_run_mla_indexer_logits_v2.restype = ctypes.c_int
+        L.fa_run_mla_indexer_prefill_logits_v2.argtypes = [_vp, _vp]
+        L.fa_run_mla_indexer_prefill_logits_v2.restype = ctypes.c_int
+        L.fa_mla_indexer_prefill_launch_v2.argtypes = [_vp] + [ctypes.POINTER(ctypes.c_int32)] * 3
+        L.fa_mla_indexer_prefill_launch_v2.restype = ctypes.c_int
         L.fa_mla_indexer_prefill_launch.restype = ctypes.c_int
         L.fa_run_mla_indexer_topk.argtypes = [ctypes.POINTER(MlaTopkParams), _vp]
         L.fa_run_mla_indexer_topk.restype = ctypes.c_int
@@ -744,12 +758,16 @@ def mla_indexer_params(q_idx, weights, k_idx_cache, logits, cache_seqlens=None, 
     """fa_mla_indexer_params for q_idx (b, sq, h, 128), weights fp32 (b, sq, h), k_idx_cache (b, capacity, 128) in q_idx's dtype or uint8 / float8_e4m3fn
     (e4m3 codes: a 1-byte dtype, so its strides are bytes, as the format asks) - or, with block_table, a pool (num_blocks, page_block_size, 128) - k_scale
     fp32 (b, capacity) / (num_blocks, page_block_size) or None, and the caller's fp32 buffer logits (b, sq, capacity): torch tensors with arbitrary strides."""
+    return _fill_mla_indexer(MlaIndexerParams(), dtype_code(q_idx.dtype), q_idx, weights, k_idx_cache, logits, cache_seqlens, k_scale, block_table, causal)
+
+
+def _fill_mla_indexer(p, dtype, q_idx, weights, k_idx_cache, logits, cache_seqlens, k_scale, block_table, causal):
+    """the fields fa_mla_indexer_params and its _v2 share"""
     b, sq, h, d = q_idx.shape
-    p = MlaIndexerParams()
     p.q_idx, p.weights, p.k_idx_cache, p.logits = (t.data_ptr() for t in (q_idx, weights, k_idx_cache, logits))
     p.cache_seqlens = None if cache_seqlens is None else cache_seqlens.data_ptr()
     p.b, p.seqlen_q, p.seqlen_cache, p.h, p.d = b, sq, k_idx_cache.shape[1], h, d
-    p.dtype, p.is_causal = dtype_code(q_idx.dtype), int(causal)
+    p.dtype, p.is_causal = dtype, int(causal)
     p.k_format = FA_IDX_K_FP8_E4M3 if k_idx_cache.element_size() == 1 else FA_MLA_KV_16BIT
     if block_table is not None:
         p.block_table, p.block_table_stride = block_table.data_ptr(), block_table.stride(0)
@@ -764,12 +782,21 @@ def mla_indexer_params(q_idx, weights, k_idx_cache, logits, cache_seqlens=None, 
     return p
 
 
+def mla_indexer_params_v2(q_idx, weights, k_idx_cache, logits, cache_seqlens=None, k_scale=None, block_table=None, causal=True):
+    """fa_mla_indexer_params_v2 for the tensors of mla_indexer_params.  A uint8 / float8_e4m3fn q_idx gives q_format = FA_IDX_Q_FP8_E4M3 (a 1-byte dtype, so its
+    strides are bytes, as the format asks) and dtype = FA_BF16, a valid value that is not used; an fp16 / bf16 q_idx gives q_format = FA_IDX_Q_16BIT."""
+    q8 = q_idx.element_size() == 1
+    p = _fill_mla_indexer(MlaIndexerParamsV2(), FA_BF16 if q8 else dtype_code(q_idx.dtype), q_idx, weights, k_idx_cache, logits, cache_seqlens, k_scale, block_table, causal)
+    p.q_format = FA_IDX_Q_FP8_E4M3 if q8 else FA_IDX_Q_16BIT
+    return p
+
+
 def run_mla_indexer_logits(params, stream=None):
     """fa_run_mla_indexer_logits"""
     import torch
 
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    check(lib().fa_run_mla_indexer_logits(ctypes.byref(params), s))
+    check((lib().fa_run_mla_indexer_logits_v2 if isinstance(params, MlaIndexerParamsV2) else lib().fa_run_mla_indexer_logits)(ctypes.byref(params), s))
 
 
 def run_mla_indexer_prefill_logits(params, stream=None):
@@ -777,13 +804,14 @@ def run_mla_indexer_prefill_logits(params, stream=None):
     import torch
 
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    check(lib().fa_run_mla_indexer_prefill_logits(ctypes.byref(params), s))
+    check((lib().fa_run_mla_indexer_prefill_logits_v2 if isinstance(params, MlaIndexerParamsV2) else lib().fa_run_mla_indexer_prefill_logits)(ctypes.byref(params), s))
 
 
 def mla_indexer_prefill_launch(params):
     """fa_mla_indexer_prefill_launch: (tokens of a workgroup's tile, keys of a workgroup's range, ranges per tile) of the launch these params would make; host only"""
     tq, wg, nc = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
-    check(lib().fa_mla_indexer_prefill_launch(ctypes.byref(params), ctypes.byref(tq), ctypes.byref(wg), ctypes.byref(nc)))
+    fn = lib().fa_mla_indexer_prefill_launch_v2 if isinstance(params, MlaIndexerParamsV2) else lib().fa_mla_indexer_prefill_launch
+    check(fn(ctypes.byref(params), ctypes.byref(tq), ctypes.byref(wg), ctypes.byref(nc)))
     return tq.value, wg.value, nc.value
 
 

@@ -809,8 +809,9 @@ def _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, b
     """the checks of flash_mla_indexer_logits; returns (q_idx with addressable strides, cache_seqlens as a tensor, capacity)"""
     if not isinstance(q_idx, torch.Tensor) or q_idx.dim() != 4:
         raise ValueError("q_idx must be a rank-4 tensor (batch, seqlen_q, index_heads, 128)")
-    if q_idx.dtype not in (torch.float16, torch.bfloat16):
-        raise ValueError(f"q_idx must be fp16 or bf16, got {q_idx.dtype}")
+    q8 = q_idx.dtype in (torch.uint8, torch.float8_e4m3fn)
+    if not q8 and q_idx.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"q_idx must be fp16, bf16 or e4m3 codes (float8_e4m3fn / uint8), got {q_idx.dtype}")
     b, sq, h, d = q_idx.shape
     if d != 128:
         raise ValueError(f"q_idx must be 128 wide, got head_dim {d}")
@@ -825,6 +826,8 @@ def _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, b
     if not isinstance(k_idx_cache, torch.Tensor) or k_idx_cache.dim() != 3:
         raise ValueError("k_idx_cache must be a rank-3 tensor (batch, capacity, 128), or a page pool (num_blocks, page_block_size, 128) with block_table")
     fp8 = k_idx_cache.dtype in (torch.uint8, torch.float8_e4m3fn)
+    if q8 and not fp8:
+        raise ValueError(f"k_idx_cache must hold e4m3 codes (float8_e4m3fn / uint8) with an FP8 q_idx, got {k_idx_cache.dtype}")
     if not fp8 and k_idx_cache.dtype != q_idx.dtype:
         raise ValueError(f"k_idx_cache must have q_idx's dtype ({q_idx.dtype}) or hold e4m3 codes (float8_e4m3fn / uint8), got {k_idx_cache.dtype}")
     if k_idx_cache.shape[2] != 128:
@@ -845,8 +848,11 @@ def _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, b
     cache_seqlens = _check_indexer_lengths(cache_seqlens, b, q_idx.device)
     if not isinstance(causal, bool):
         raise ValueError(f"causal must be a bool, got {causal!r}")
-    if q_idx.stride(3) != 1 or any(q_idx.stride(i) % 8 != 0 for i in range(3)) or q_idx.data_ptr() % 16 != 0:
-        q_idx = q_idx.contiguous()              # (a token's index queries are 16 KB: unlike the cache they may be copied)
+    unit = 16 if q8 else 8                      # 16-byte loads: bytes of codes, or elements
+    if q_idx.stride(3) != 1 or any(q_idx.stride(i) % unit != 0 for i in range(3)) or q_idx.data_ptr() % 16 != 0:
+        # (a token's index queries are 16 KB, 8 KB of codes: unlike the cache they may be copied.  Codes are cloned: .contiguous() hands a contiguous tensor at
+        # a misaligned address back as it is)
+        q_idx = q_idx.clone(memory_format=torch.contiguous_format) if q8 else q_idx.contiguous()
     return q_idx, cache_seqlens, capacity
 
 
@@ -854,6 +860,7 @@ def flash_mla_indexer_logits(q_idx, weights, k_idx_cache, cache_seqlens, *, k_sc
     """Index logits of the DeepSeek-V3.2 "lightning indexer": one fp32 logit per (query token, cached key), the input of flash_mla_indexer_topk.
 
     q_idx: (batch, seqlen_q, index_heads, 128) fp16 / bf16, index_heads 16, 32 or 64.  RoPE and any scale of q are the caller's (fold a scale into weights).
+    Or torch.float8_e4m3fn / torch.uint8 (OCP e4m3 codes) over an FP8 k_idx_cache - the dtype of q_idx says which path runs: see "FP8 q_idx" below.
     weights: (batch, seqlen_q, index_heads) float32, any strides: the learned per-head weights of the token.
     k_idx_cache: (batch, capacity, 128) in q_idx's dtype, or torch.float8_e4m3fn / torch.uint8 (OCP e4m3 codes), used in place; with block_table
     (int32 (batch, max_blocks), last dim contiguous) a page pool (num_blocks, page_block_size, 128), page_block_size a multiple of 16, entries clamped
@@ -871,8 +878,12 @@ def flash_mla_indexer_logits(q_idx, weights, k_idx_cache, cache_seqlens, *, k_sc
     Never read, so they may hold NaN codes and NaN scales: cache rows and scales at or past L_i, pages wholly past L_i, pages no sequence references.
     Non-finite inputs have no value contract (memory safety only).  No host synchronisation: lengths, tables and scales are read on the device and
     a captured call replays with the values then in memory.  Deterministic; paged and contiguous calls over the same logical cache give the same bits.
-    Out of scope: FP8 q_idx, other head counts or widths, appending to the index cache, cu_seqlens_q.  Wrong shapes, dtypes or views are a ValueError
-    that names the argument."""
+    FP8 q_idx (quantize_mla_index_queries): k_idx_cache must hold e4m3 codes too (a 16-bit cache is a ValueError naming k_idx_cache); the per-(token, head)
+    scale of the quantised queries is the caller's, folded into weights.  ``logits[i, t, j] = k_scale[j] * sum_h weights[t, h] * relu(sum_d float(qcode[t, h, d])
+    * float(kcode[j, d]))``: an e4m3 x e4m3 product on v_mfma_f32_16x16x128_f8f6f4, every product exact in fp32, the order of the 128-term sum the
+    instruction's; relu is the IEEE 754-2019 maximum here (a NaN code gives NaN).  A q_idx the kernels cannot address with 16-byte loads is made contiguous once.
+    Out of scope: FP8 q_idx over a 16-bit cache, other head counts or widths, appending to the index cache, cu_seqlens_q.  Wrong shapes, dtypes or views are a
+    ValueError that names the argument."""
     q_idx, cache_seqlens, capacity = _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, block_table, causal)
     logits = torch.empty(q_idx.shape[0], q_idx.shape[1], capacity, dtype=torch.float32, device=q_idx.device)
     _C.mla_indexer_logits(q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale, block_table, causal)
@@ -924,8 +935,8 @@ def flash_mla_index_with_kvcache(q_idx, weights, k_idx_cache, cache_seqlens, top
 
 
 def flash_mla_indexer_prefill_logits(q_idx, weights, k_idx_cache, cache_seqlens, *, k_scale=None, block_table=None, causal=True):
-    """flash_mla_indexer_logits for a prompt chunk: the same arguments, checks and refusals, and the same bits in the same entries (a NaN key below L_i alone
-    differs: it gives NaN in its column for the tokens that see it, where flash_mla_indexer_logits leaves 0).
+    """flash_mla_indexer_logits for a prompt chunk: the same arguments, checks and refusals, and the same bits in the same entries (with a 16-bit q_idx a NaN key
+    below L_i alone differs: it gives NaN in its column for the tokens that see it, where flash_mla_indexer_logits leaves 0; with an FP8 q_idx both give NaN).
 
     flash_mla_indexer_logits gives a workgroup one token, which loads and widens the visible index-key cache once per token of the chunk.  Here a
     workgroup serves a tile of consecutive tokens of one sequence (4 or 8: capi.mla_indexer_prefill_launch) and stages each 32-key step once for all of
@@ -1500,6 +1511,22 @@ def quantize_mla_index_keys(k, scale_format="fp32"):
     codes = torch.where(nan, torch.zeros_like(y), y).to(torch.float8_e4m3fn).view(torch.uint8)
     sign = ((k.contiguous().view(torch.int16).to(torch.int32) >> 8) & 0x80).to(torch.uint8)      # (of the 16-bit pattern: a widening may drop a NaN's sign)
     return torch.where(nan, sign | 0x7F, codes), scale.squeeze(-1)
+
+
+def quantize_mla_index_queries(q_idx, weights, scale_format="fp32"):
+    """(..., heads, 128) fp16 / bf16 index queries and float32 weights (..., heads) -> (codes uint8 (..., heads, 128), weights * scale float32 (..., heads)): what
+    flash_mla_indexer_logits and flash_mla_indexer_prefill_logits take as an FP8 q_idx and its weights.
+
+    The row rule of quantize_mla_index_keys applied to each (token, head) row: amax over the row's finite elements, scale = max(amax, 2^-24) / 448 (rounded up to
+    a power of two under scale_format="ue8m0"), code = e4m3_rne(clamp(float(x) / scale, -448, 448)), NaN kept with its sign, +-inf saturating.  The scale is
+    folded into the head's weight as the fp32 product weights * scale, which is what the model does.  Plain torch, any device: a convenience, not a fused
+    quantiser."""
+    if not isinstance(q_idx, torch.Tensor) or q_idx.dtype not in (torch.float16, torch.bfloat16) or q_idx.dim() < 2 or q_idx.shape[-1] != 128:
+        raise ValueError("q_idx must be an fp16 / bf16 tensor (..., heads, 128)")
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != tuple(q_idx.shape[:-1]):
+        raise ValueError(f"weights must be a float32 tensor of shape {tuple(q_idx.shape[:-1])} (q_idx without its last dimension)")
+    codes, scale = quantize_mla_index_keys(q_idx, scale_format)
+    return codes, weights * scale
 
 
 def flash_mla_index_cache_append(k_idx_cache, k_idx_new, cache_seqlens, *, k_scale=None, block_table=None, cu_seqlens_new=None, scale_format="fp32"):

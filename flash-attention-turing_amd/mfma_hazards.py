@@ -13,10 +13,13 @@ NEED: the documented requirement + 1.  "XDL write VGPR -> VALU read / write of t
 (LLVM GCNHazardRecognizer, GFX940_XDL_N_PassWriteVgprVALUReadWaitStates: 2-pass 5, 4-pass 7, 8-pass 11, 16-pass 19; the CDNA guide's section 5.7 states the 8-pass
 case as "12 states = s_nop 11"): v_mfma_f32_16x16x32_{f16,bf16} is 4 passes (16 cycles, tools/ubench: 16.3 cycles back to back) -> 7, v_mfma_f32_32x32x16 is
 8 passes -> 11.  The same numbers are what hipcc itself leaves behind its own (builtin) MFMAs in these files: a dependent VALU sits 8 wait states behind a
-v_mfma_f32_16x16x32 (5 instructions + s_nop 2 in fa_bwd_dq16) and 12 behind a v_mfma_f32_32x32x16 (s_nop 11 in fa_bwd)."""
+v_mfma_f32_16x16x32 (5 instructions + s_nop 2 in fa_bwd_dq16) and 12 behind a v_mfma_f32_32x32x16 (s_nop 11 in fa_bwd).
+v_mfma_f32_16x16x128_f8f6f4 with e4m3 operands (the FP8 q_idx index-logits kernels; issued through the builtin, so hipcc pads it itself) is 8 passes -> 11: the
+microarchitecture guide gives it twice the cycles of the 16x16x32 form, and tools/ubench measures 34.6 cycles back to back (two accumulators; 37.5 with four) next to
+18.8 for v_mfma_f32_16x16x32_f16 and 32.0 for v_mfma_f32_32x32x16_f16 in the same loop (profiles/ubench_mfma_16x16x128_e4m3.log) - the 32x32x16 class."""
 import re
 
-NEED = {"16x16x32": 8, "32x32x16": 12}      # = documented 7 / 11 + 1; other shapes: 20 (none is issued from inline asm here)
+NEED = {"16x16x32": 8, "32x32x16": 12, "16x16x128_f8f6f4": 12}      # = documented 7 / 11 / 11 + 1; other shapes: 20 (none is issued from inline asm here)
 HORIZON = 48                                # wait states after which an MFMA result has landed for every shape
 
 

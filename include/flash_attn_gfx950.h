@@ -896,6 +896,56 @@ typedef struct fa_mla_topk_params {
  * fa_mla_indexer_prefill_launch says on the host what that launch would use. */
 #define FA_HAS_MLA_INDEXER_PREFILL 1
 
+/* FP8 (e4m3) index queries (FA_HAS_MLA_INDEXER_FP8_Q; both sides of DeepGEMM's fp8_paged_mqa_logits / fp8_mqa_logits).  fa_mla_indexer_params_v2 is
+ * fa_mla_indexer_params with q_format appended.  It goes to three entry points of its own, fa_run_mla_indexer_logits_v2, fa_run_mla_indexer_prefill_logits_v2
+ * and fa_mla_indexer_prefill_launch_v2, which take either struct through their pointer and tell them apart by struct_size (any other size is FA_ERR_BAD_ABI).
+ * The entry points without _v2 keep accepting the 216-byte struct alone, with their errors: a struct_size of 224 there stays FA_ERR_BAD_ABI, because a
+ * 216-byte struct mislabelled by 8 bytes cannot be told from a _v2 and would be read past its end.  FA_ABI_VERSION is unchanged.
+ * q_format = FA_IDX_Q_16BIT: exactly the call of the first struct.  q_format = FA_IDX_Q_FP8_E4M3: q_idx holds OCP e4m3 codes, q_idx_stride counts BYTES
+ * (multiples of 16, pointer 16-byte aligned), k_format must be FA_IDX_K_FP8_E4M3, and `dtype` must still be a valid value but is not used.  The scale of the
+ * quantised queries, one per (token, head), is the caller's: fold it into weights.  For j < n_t:
+ *   logit[i, t, j] = k_scale[j] * sum_h weights[t, h] * relu(sum_d float(qcode[t, h, d]) * float(kcode[j, d]))
+ * on v_mfma_f32_16x16x128_f8f6f4: every product is exact in fp32, the 128-term sum is the instruction's; relu is the IEEE 754-2019 maximum in both calls (a NaN
+ * code gives NaN), so the prefill call writes the entries of the decode call with the same bits for every input.  Visibility, what is never read or written,
+ * paging, determinism and the launch rule reported by fa_mla_indexer_prefill_launch are those of the first struct.
+ * Errors: an unknown q_format FA_ERR_BAD_DTYPE naming q_format; q_format = 1 with another k_format FA_ERR_BAD_DTYPE naming k_format; a non-zero reserved2_
+ * FA_ERR_BAD_SHAPE naming it; a q_idx stride or pointer that is no multiple of 16 bytes FA_ERR_BAD_STRIDE. */
+#define FA_HAS_MLA_INDEXER_FP8_Q 1
+#define FA_IDX_Q_16BIT 0
+#define FA_IDX_Q_FP8_E4M3 1
+typedef struct fa_mla_indexer_params_v2 {
+    uint32_t struct_size;       /* sizeof(fa_mla_indexer_params_v2) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const void* q_idx;
+    const float* weights;
+    const void* k_idx_cache;
+    const float* k_scale;       /* NULL = 1.0 */
+    float* logits;
+    const int32_t* cache_seqlens;
+    const int32_t* block_table; /* paged cache; NULL = contiguous */
+    int32_t b;
+    int32_t seqlen_q;
+    int32_t seqlen_cache;
+    int32_t h;                  /* 16, 32 or 64 */
+    int32_t d;                  /* 128 */
+    int32_t dtype;
+    int32_t k_format;           /* FA_MLA_KV_16BIT / FA_IDX_K_FP8_E4M3 */
+    int32_t is_causal;
+    int32_t page_block_size;
+    int32_t num_blocks;
+    int64_t reserved_;          /* 0 */
+    fa_strides q_idx_stride, weights_stride;
+    int64_t k_cache_batch_stride;
+    int64_t k_cache_row_stride;
+    int64_t k_scale_batch_stride;
+    int64_t k_scale_row_stride;
+    int64_t logits_batch_stride;
+    int64_t logits_row_stride;
+    int64_t block_table_stride;
+    int32_t q_format;           /* FA_IDX_Q_16BIT / FA_IDX_Q_FP8_E4M3 */
+    int32_t reserved2_;         /* 0 */
+} fa_mla_indexer_params_v2;
+
 /* MLA prefill attention (FA_HAS_MLA_PREFILL; DeepSeek-V2 / V3 / R1, Kimi K2 before weight absorption; the (192, 128) forward of flash-attn and FlashMLA).
  * Ordinary multi-head attention with d_qk = 192 wide queries and keys (128 no-rope columns, then 64 rope columns, RoPE already applied) and d_v = 128
  * wide values.  FA_ABI_VERSION is unchanged; the presence of fa_run_mla_prefill_fwd is how a caller detects the feature.  struct_size must be
@@ -1247,6 +1297,11 @@ int fa_run_mla_indexer_prefill_logits(const fa_mla_indexer_params* params, void*
  * 32) and the ranges per tile of the launch fa_run_mla_indexer_prefill_logits would make; its grid is b x ceil(seqlen_q / tokens_per_wg) x n_chunks.
  * Any of the three pointers may be NULL.  Returns FA_OK or the error code of the launch (then nothing is written). */
 int fa_mla_indexer_prefill_launch(const fa_mla_indexer_params* params, int32_t* tokens_per_wg, int32_t* wg_keys, int32_t* n_chunks);
+/* The three entry points above for fa_mla_indexer_params_v2 (FA_HAS_MLA_INDEXER_FP8_Q): they take a fa_mla_indexer_params_v2 or (cast to it) a
+ * fa_mla_indexer_params, told apart by struct_size; with q_format = FA_IDX_Q_16BIT, or the 216-byte struct, they are the calls above. */
+int fa_run_mla_indexer_logits_v2(const fa_mla_indexer_params_v2* params, void* stream);
+int fa_run_mla_indexer_prefill_logits_v2(const fa_mla_indexer_params_v2* params, void* stream);
+int fa_mla_indexer_prefill_launch_v2(const fa_mla_indexer_params_v2* params, int32_t* tokens_per_wg, int32_t* wg_keys, int32_t* n_chunks);
 
 /* ---- MLA prefill attention (fa_mla_prefill_params above) -------------------------------------- */
 /* One launch on `stream`, no workspace, no host synchronisation: cu_seqlens are read on the device. */

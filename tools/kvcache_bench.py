@@ -85,6 +85,8 @@ per point records arm (i) under forced num_splits 8, 16, 32, 64 next to the auto
 --mla-indexer-prefill measures flash_mla_indexer_prefill_logits on one prompt chunk (b 1, sq 128 / 512 / 2048 over 4k / 32k / 128k keys; bf16 q_idx, FP8 keys with
 scales, 64 heads, pages of 64, causal) against flash_mla_indexer_logits on the same inputs, interleaved, the decode call timed twice, the bits asserted equal
 first; ms, the ratio and sq x n x 64 x 128 x 2 FLOP over time under the mask, and the selection launch (profiles/mla_indexer_prefill_bench.log).
+--mla-indexer / --mla-indexer-prefill with --q-dtype fp8 measure the same two calls on e4m3 index queries against the calls on the widened (bf16) queries over the
+same caches, interleaved, the bf16-q call timed twice, the bits asserted on integer data first (profiles/mla_indexer_fp8q_bench.log).
 --mla-indexer measures the DeepSeek-V3.2 indexer (flash_mla_indexer_logits / flash_mla_indexer_topk): bf16 q_idx, FP8 keys with per-token scales, 64 index
 heads, seqlen_q 1, topk 2048, pages of 64 (--paged P replaces the page size), b in {1, 8, 64} x L in {4k, 32k, 128k} (--length replaces them).  Per point,
 interleaved in one process: the logits call; the torch formulation of the logits (dequantise, einsum, relu, weighted sum, * k_scale; it reads the pool
@@ -1140,6 +1142,88 @@ def run_mla_indexer_prefill(lengths, pages, rounds):
         torch.cuda.empty_cache()
 
 
+def _fp8q_exact_bits(fn, h, page, dev):
+    """before timing: on integer data (every partial sum an integer below 2^24) the FP8-q call `fn` gives the bits of the same call on q.to(bfloat16)"""
+    gen = torch.Generator(device=dev).manual_seed(7)
+    sq, L = 9, 4 * page
+    q8 = torch.randint(-8, 9, (1, sq, h, 128), device=dev, generator=gen).float().to(torch.float8_e4m3fn)
+    pool = torch.randint(-8, 9, (4, page, 128), device=dev, generator=gen).float().to(torch.float8_e4m3fn)
+    w = 2.0 ** torch.randint(-2, 3, (1, sq, h), device=dev, generator=gen).float()
+    sc = 2.0 ** torch.randint(-3, 4, (4, page), device=dev, generator=gen).float()
+    cs = torch.full((1,), L - 5, dtype=torch.int32, device=dev)
+    table = torch.randperm(4, device=dev, generator=gen).to(torch.int32).view(1, 4)
+    kw = dict(k_scale=sc, block_table=table, causal=True)
+    n = (L - 5 - sq + 1 + torch.arange(sq, device=dev)).view(1, sq, 1)
+    vis = torch.arange(L, device=dev).view(1, 1, L) < n
+    return bool(torch.equal(fn(q8, w, pool, cs, **kw).view(torch.int32)[vis], fn(q8.to(torch.bfloat16), w, pool, cs, **kw).view(torch.int32)[vis]))
+
+
+def run_mla_indexer_fp8q_point(b, L, page, rounds, h=64):
+    """--mla-indexer --q-dtype fp8: the decode logits call on e4m3 queries against the same call on the widened (bf16) queries over the same caches (timed twice);
+    interleaved, caches rotated over the working set"""
+    dev = torch.device("cuda:0")
+    exact = _fp8q_exact_bits(F.flash_mla_indexer_logits, h, page, dev)
+    assert exact, "on integer data the FP8-q logits differ from the bf16-q call's"
+    gen = torch.Generator(device=dev).manual_seed(b * 1000003 + L)
+    kbytes = b * L * 132
+    n = max(1, min(512, math.ceil(WORKING_SET / kbytes)))
+    cols = L // page
+    q8 = torch.randn(b, 1, h, 128, device=dev, generator=gen).to(torch.float8_e4m3fn)
+    q16 = q8.to(torch.bfloat16)
+    w = torch.randn(b, 1, h, device=dev, generator=gen) * (h ** -0.5)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    sets = []
+    for _ in range(n):
+        pool = torch.randn(b * cols, page, 128, device=dev, generator=gen).to(torch.float8_e4m3fn)
+        scales = torch.rand(b * cols, page, device=dev, generator=gen) + 0.5
+        table = torch.randperm(b * cols, device=dev, generator=gen).to(torch.int32).view(b, cols)
+        sets.append((pool, scales, table))
+    call = lambda q: (lambda i: F.flash_mla_indexer_logits(q, w, sets[i % n][0], cs, k_scale=sets[i % n][1], block_table=sets[i % n][2], causal=True))
+    ms = _interleaved({"fp8q_logits": call(q8), "bf16q_logits": call(q16), "bf16q_logits_again": call(q16)}, n, rounds)
+    tbs = {k: kbytes / (v * 1e-3) / 1e12 for k, v in ms.items()}
+    flop = b * L * h * 128 * 2
+    return dict(mla_indexer_fp8q=True, b=b, L=L, h=h, seqlen_q=1, q_format="fp8_e4m3", k_format="fp8_e4m3+scale", page_block_size=page, caches_rotated=n,
+                ms={k: round(v, 5) for k, v in ms.items()}, fp8q_over_bf16q=round(ms["fp8q_logits"] / ms["bf16q_logits"], 4),
+                bf16q_noise=round(ms["bf16q_logits_again"] / ms["bf16q_logits"], 4), key_bytes=kbytes,
+                fp8q_fraction_of_6p3_tb_s=round(tbs["fp8q_logits"] * 1e12 / HBM_ACHIEVABLE, 3), bf16q_fraction_of_6p3_tb_s=round(tbs["bf16q_logits"] * 1e12 / HBM_ACHIEVABLE, 3),
+                fp8q_tflops=round(flop / (ms["fp8q_logits"] * 1e-3) / 1e12, 1), bf16q_tflops=round(flop / (ms["bf16q_logits"] * 1e-3) / 1e12, 1), exact_bits=exact)
+
+
+def run_mla_indexer_prefill_fp8q_point(sq, L, page, rounds, h=64):
+    """--mla-indexer-prefill --q-dtype fp8: the prefill logits call on e4m3 queries against the same call on the widened (bf16) queries over the same cache (timed twice)"""
+    dev = torch.device("cuda:0")
+    exact = _fp8q_exact_bits(F.flash_mla_indexer_prefill_logits, h, page, dev)
+    assert exact, "on integer data the FP8-q prefill logits differ from the bf16-q call's"
+    gen = torch.Generator(device=dev).manual_seed(sq * 1000003 + L)
+    cols = L // page
+    q8 = torch.randn(1, sq, h, 128, device=dev, generator=gen).to(torch.float8_e4m3fn)
+    q16 = q8.to(torch.bfloat16)
+    w = torch.randn(1, sq, h, device=dev, generator=gen) * (h ** -0.5)
+    cs = torch.full((1,), L, dtype=torch.int32, device=dev)
+    pool = torch.randn(cols, page, 128, device=dev, generator=gen).to(torch.float8_e4m3fn)
+    scales = torch.rand(cols, page, device=dev, generator=gen) + 0.5
+    table = torch.randperm(cols, device=dev, generator=gen).to(torch.int32).view(1, cols)
+    kw = dict(k_scale=scales, block_table=table, causal=True)
+    new = lambda: F.flash_mla_indexer_prefill_logits(q8, w, pool, cs, **kw)
+    old = lambda: F.flash_mla_indexer_prefill_logits(q16, w, pool, cs, **kw)
+    ms = _mlap_time({"fp8q_prefill_logits": new, "bf16q_prefill_logits": old, "bf16q_prefill_logits_again": old}, rounds)
+    n_t = (L - sq + 1 + torch.arange(sq)).clamp(0, L)
+    pairs = int(n_t.sum())                      # (token, key) pairs under the mask
+    flop = pairs * h * 128 * 2
+    return dict(mla_indexer_prefill_fp8q=True, b=1, seqlen_q=sq, L=L, h=h, q_format="fp8_e4m3", k_format="fp8_e4m3+scale", page_block_size=page,
+                ms={k: round(v, 5) for k, v in ms.items()}, fp8q_over_bf16q=round(ms["fp8q_prefill_logits"] / ms["bf16q_prefill_logits"], 4),
+                bf16q_noise=round(ms["bf16q_prefill_logits_again"] / ms["bf16q_prefill_logits"], 4), token_key_pairs=pairs,
+                fp8q_tflops=round(flop / (ms["fp8q_prefill_logits"] * 1e-3) / 1e12, 1), bf16q_tflops=round(flop / (ms["bf16q_prefill_logits"] * 1e-3) / 1e12, 1),
+                exact_bits=exact)
+
+
+def run_mla_indexer_fp8q(lengths, pages, rounds, prefill):
+    grid = itertools.product((128, 512, 2048) if prefill else (1, 8, 64), tuple(lengths or (4096, 32768, 131072)))
+    for x, L in grid:
+        yield (run_mla_indexer_prefill_fp8q_point if prefill else run_mla_indexer_fp8q_point)(x, L, (pages or [64])[0], rounds)
+        torch.cuda.empty_cache()
+
+
 def _mlap_time(fns, rounds, iters=3):
     """median ms per call of each arm, the arms taken in turn within every round, `iters` calls per timed batch"""
     t = {k: [] for k in fns}
@@ -1498,6 +1582,8 @@ def main():
     ap.add_argument("--mla-indexer-prefill", action="store_true", help="flash_mla_indexer_prefill_logits against flash_mla_indexer_logits (timed twice) on one prompt chunk, and "
                                                                        "the selection launch: bf16, FP8 keys with scales, 64 heads, pages of 64, causal, b 1, sq in {128, 512, "
                                                                        "2048} x L in {4k, 32k, 128k}; bits asserted equal before timing")
+    ap.add_argument("--q-dtype", choices=("bf16", "fp8"), default="bf16", help="with --mla-indexer / --mla-indexer-prefill, fp8: the call on e4m3 index queries against the same call "
+                    "on the widened (bf16) queries over the same FP8 cache (timed twice), on the grids of the two tables; the bits asserted on integer data first")
     ap.add_argument("--mla-prefill", action="store_true", help="MLA prefill attention (flash_mla_prefill_func, bf16, h = h_k in {16, 128}) against fwd at head_dim 128 and "
                                                                "against the zero-padded head_dim-256 KV-cache call, each yardstick timed twice; with --baseline-library an A / B of "
                                                                "the call itself against that library")
@@ -1531,6 +1617,10 @@ def main():
             return
         if a.ragged and base is None:
             for line in run_ragged(a.quick, a.rounds):
+                print(json.dumps(line), flush=True)
+            return
+        if (a.mla_indexer_prefill or a.mla_indexer) and a.q_dtype == "fp8":
+            for line in run_mla_indexer_fp8q(a.length, a.paged, a.rounds, a.mla_indexer_prefill):
                 print(json.dumps(line), flush=True)
             return
         if a.mla_indexer_prefill:

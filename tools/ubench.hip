@@ -16,10 +16,10 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define REP16(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
 
 enum { T_EXP, T_FMA, T_ADD, T_MAX3, T_CVT, T_PKFMA, T_PKMUL, T_PKADD, T_EXPH, T_LDEXP, T_LSHLADD, T_MIX_EXP_FMA, T_MFMA, T_LOG, T_RCP,
-       T_MFMA16, T_STREAM4, T_STREAM5, T_STREAM6, T_MFMA_NOP20, T_MFMA_NOP26, T_MFMA_SLEEP, T_MN3, T_MN4, T_MN5, T_MN6, T_MN7, T_NUM };
+       T_MFMA16, T_MFMA128_E4M3, T_MFMA128_E4M3_4ACC, T_STREAM4, T_STREAM5, T_STREAM6, T_MFMA_NOP20, T_MFMA_NOP26, T_MFMA_SLEEP, T_MN3, T_MN4, T_MN5, T_MN6, T_MN7, T_NUM };
 static const char* kNames[] = {"v_exp_f32", "v_fma_f32", "v_add_f32", "v_max3_f32", "v_cvt_pk_f16_f32", "v_pk_fma_f32", "v_pk_mul_f32",
                                "v_pk_add_f32", "v_exp_f16", "v_ldexp_f32", "v_lshl_add_u32", "8 exp + 8 fma interleaved", "v_mfma_32x32x16_f16",
-                               "v_log_f32", "v_rcp_f32", "v_mfma_16x16x32_f16", "stream 1 mfma : 4 valu (1 exp)", "stream 1 mfma : 5 valu (1 exp)", "stream 1 mfma : 6 valu (1 exp)", "mfma + s_nop(20)", "mfma + s_nop(26)", "mfma + s_sleep 0", "mn3", "mn4", "mn5", "mn6", "mn7"};
+                               "v_log_f32", "v_rcp_f32", "v_mfma_16x16x32_f16", "v_mfma_16x16x128_f8f6f4 e4m3, 2 accumulators", "v_mfma_16x16x128_f8f6f4 e4m3, 4 accumulators", "stream 1 mfma : 4 valu (1 exp)", "stream 1 mfma : 5 valu (1 exp)", "stream 1 mfma : 6 valu (1 exp)", "mfma + s_nop(20)", "mfma + s_nop(26)", "mfma + s_sleep 0", "mn3", "mn4", "mn5", "mn6", "mn7"};
 
 template <int TEST>
 __device__ __forceinline__ void body(float (&r)[16], f32x2 (&pk)[16], f32x16& acc, f32x16& acc2, f16x8 a, f16x8 b) {
@@ -130,6 +130,23 @@ __device__ __forceinline__ void body(float (&r)[16], f32x2 (&pk)[16], f32x16& ac
             c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c1, 0, 0, 0);
         }
         acc[0] = c0[0]; acc[4] = c1[0];
+    } else if constexpr (TEST == T_MFMA128_E4M3 || TEST == T_MFMA128_E4M3_4ACC) {
+        // the unscaled e4m3 x e4m3 form of the index-logits kernels with FP8 queries (format selectors 0 / 0, scale operands 0): 16 per body, as T_MFMA16
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        typedef int i32x8 __attribute__((ext_vector_type(8)));
+        i32x8 a8, b8;
+        for (int i = 0; i < 8; ++i) { a8[i] = 0x38404448 + 0x01010101 * i + (int)(float)a[i & 7]; b8[i] = 0x3c3a3836 + 0x01010101 * i + (int)(float)b[i & 7]; }
+        f32x4 c0 = {acc[0], acc[1], acc[2], acc[3]}, c1 = {acc[4], acc[5], acc[6], acc[7]}, c2 = {acc[8], acc[9], acc[10], acc[11]}, c3 = {acc[12], acc[13], acc[14], acc[15]};
+#pragma unroll
+        for (int i = 0; i < (TEST == T_MFMA128_E4M3 ? 8 : 4); ++i) {
+            c0 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b8, c0, 0, 0, 0, 0, 0, 0);
+            c1 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b8, c1, 0, 0, 0, 0, 0, 0);
+            if constexpr (TEST == T_MFMA128_E4M3_4ACC) {
+                c2 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b8, c2, 0, 0, 0, 0, 0, 0);
+                c3 = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a8, b8, c3, 0, 0, 0, 0, 0, 0);
+            }
+        }
+        acc[0] = c0[0]; acc[4] = c1[0]; acc[8] = c2[0]; acc[12] = c3[0];
     }
 }
 
@@ -283,6 +300,8 @@ int main() {
     run<T_MIX_EXP_FMA, T_MIX_EXP_FMA>(d, 256, kNames[T_MIX_EXP_FMA]);
     run<T_MFMA, T_MFMA>(d, 256, kNames[T_MFMA]);
     run<T_MFMA16, T_MFMA16>(d, 256, kNames[T_MFMA16]);
+    run<T_MFMA128_E4M3, T_MFMA128_E4M3>(d, 256, kNames[T_MFMA128_E4M3]);
+    run<T_MFMA128_E4M3_4ACC, T_MFMA128_E4M3_4ACC>(d, 256, kNames[T_MFMA128_E4M3_4ACC]);
     printf("== two waves per SIMD (A = waves 0-3, B = waves 4-7) ==\n");
     run<T_EXP, T_EXP>(d, 512, "exp | exp");
     run<T_FMA, T_FMA>(d, 512, "fma | fma");
