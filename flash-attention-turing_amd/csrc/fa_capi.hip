@@ -13,6 +13,7 @@
 #include "fa_mla_indexer.hpp"
 #include "fa_merge_states.hpp"
 #include "fa_mla_cache_io.hpp"
+#include "fa_mla_index_prepare.hpp"
 #include "flash_attn_gfx950.h"
 
 namespace {
@@ -369,6 +370,45 @@ void fill_io_cache(const P& p, const void* cache, int64_t batch, int64_t row, in
     if (p.block_table != nullptr) {
         io.block_table = p.block_table; io.bt_stride = p.block_table_stride; io.page_size = p.page_block_size; io.num_blocks = p.num_blocks;
     }
+}
+
+// The index-key append of fa_mla_index_cache_append_params and fa_mla_index_prepare_params (P; the fields they name alike): every rule of the call, then the
+// zeroed MlaCacheIoParams.  n_rows == 0: nothing to write.
+template <typename P>
+int check_index_append(const P& p, const char* what, fa::MlaCacheIoParams& io, int64_t& n_rows) {
+    int rc;
+    if ((rc = check_io_rows(p.b, p.seqlen_cache, "seqlen_new", p.seqlen_new, "total_new", p.total_new, "cu_seqlens_new", p.cu_seqlens_new, n_rows))) return rc;
+    if ((rc = check_dtype(p.dtype))) return rc;
+    if (p.k_format != FA_MLA_KV_16BIT && p.k_format != FA_IDX_K_FP8_E4M3)
+        return fail(FA_ERR_BAD_DTYPE, "k_format %d unknown (0 = keys of dtype, 1 = OCP e4m3 codes)", p.k_format);
+    if (p.scale_format != FA_IDX_SCALE_FP32 && p.scale_format != FA_IDX_SCALE_UE8M0)
+        return fail(FA_ERR_BAD_DTYPE, "scale_format %d unknown (0 = fp32 scales, 1 = scales rounded up to powers of two, UE8M0)", p.scale_format);
+    if ((rc = check_reserved(p.reserved_, what, FA_ERR_BAD_SHAPE))) return rc;
+    if ((rc = check_paged(p.block_table, p.block_table_stride, p.page_block_size, p.num_blocks, p.seqlen_cache))) return rc;
+    const bool dense = p.cu_seqlens_new == nullptr, fp8 = p.k_format == FA_IDX_K_FP8_E4M3;
+    if (!fp8 && p.k_scale != nullptr) return fail(FA_ERR_BAD_SHAPE, "k_scale given with k_format = 0 (a 16-bit index cache has no scales)");
+    if (n_rows == 0) return FA_OK;      // nothing to write
+    if (p.cache_seqlens == nullptr) return fail(FA_ERR_NULL_POINTER, "cache_seqlens is NULL (the rows k_idx_new is appended at)");
+    if ((rc = check_idx_cache(p))) return rc;
+    if (fp8 && p.k_scale == nullptr) return fail(FA_ERR_NULL_POINTER, "k_scale is NULL (k_format = 1 writes one scale per token)");
+    if (fp8 && (reinterpret_cast<uintptr_t>(p.k_scale) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "k_scale must be 4-byte aligned");
+    if ((rc = check_io_rows16("k_idx_new", p.k_idx_new, p.k_new_batch_stride, p.k_new_row_stride, 0, dense))) return rc;
+    memset(&io, 0, sizeof(io));
+    fill_io_cache(p, p.k_idx_cache, p.k_cache_batch_stride, p.k_cache_row_stride, fp8 ? 1 : 2, io);
+    io.k_scale = p.k_scale; io.ks_batch = p.k_scale_batch_stride; io.ks_row = p.k_scale_row_stride;
+    io.src = p.k_idx_new; io.s_batch = 2 * p.k_new_batch_stride; io.s_row = 2 * p.k_new_row_stride;
+    io.cu = p.cu_seqlens_new; io.n = p.seqlen_new; io.total = n_rows;
+    return FA_OK;
+}
+
+// dtype, scale_format, hadamard and the reserved word of fa_mla_index_prepare_params: what its two calls check alike
+int check_index_prepare_flags(const fa_mla_index_prepare_params& p) {
+    int rc;
+    if ((rc = check_dtype(p.dtype))) return rc;
+    if (p.scale_format != FA_IDX_SCALE_FP32 && p.scale_format != FA_IDX_SCALE_UE8M0)
+        return fail(FA_ERR_BAD_DTYPE, "scale_format %d unknown (0 = fp32 scales, 1 = scales rounded up to powers of two, UE8M0)", p.scale_format);
+    if (p.hadamard != 0 && p.hadamard != 1) return fail(FA_ERR_BAD_SHAPE, "hadamard must be 0 or 1, got %d", p.hadamard);
+    return check_reserved(p.reserved_, "fa_mla_index_prepare_params", FA_ERR_BAD_SHAPE);
 }
 
 int hip_status(hipError_t e, const char* what) {
@@ -1440,31 +1480,50 @@ int fa_run_mla_index_cache_append(const fa_mla_index_cache_append_params* user, 
     fa_mla_index_cache_append_params local;
     int rc = import_exact(user, local, "fa_mla_index_cache_append_params");
     if (rc) return rc;
-    const fa_mla_index_cache_append_params* p = &local;
-    int64_t n_rows;
-    if ((rc = check_io_rows(p->b, p->seqlen_cache, "seqlen_new", p->seqlen_new, "total_new", p->total_new, "cu_seqlens_new", p->cu_seqlens_new, n_rows))) return rc;
-    if ((rc = check_dtype(p->dtype))) return rc;
-    if (p->k_format != FA_MLA_KV_16BIT && p->k_format != FA_IDX_K_FP8_E4M3)
-        return fail(FA_ERR_BAD_DTYPE, "k_format %d unknown (0 = keys of dtype, 1 = OCP e4m3 codes)", p->k_format);
-    if (p->scale_format != FA_IDX_SCALE_FP32 && p->scale_format != FA_IDX_SCALE_UE8M0)
-        return fail(FA_ERR_BAD_DTYPE, "scale_format %d unknown (0 = fp32 scales, 1 = scales rounded up to powers of two, UE8M0)", p->scale_format);
-    if ((rc = check_reserved(p->reserved_, "fa_mla_index_cache_append_params", FA_ERR_BAD_SHAPE))) return rc;
-    if ((rc = check_paged(p->block_table, p->block_table_stride, p->page_block_size, p->num_blocks, p->seqlen_cache))) return rc;
-    const bool dense = p->cu_seqlens_new == nullptr, fp8 = p->k_format == FA_IDX_K_FP8_E4M3;
-    if (!fp8 && p->k_scale != nullptr) return fail(FA_ERR_BAD_SHAPE, "k_scale given with k_format = 0 (a 16-bit index cache has no scales)");
-    if (n_rows == 0) return FA_OK;      // nothing to write
-    if (p->cache_seqlens == nullptr) return fail(FA_ERR_NULL_POINTER, "cache_seqlens is NULL (the rows k_idx_new is appended at)");
-    if ((rc = check_idx_cache(*p))) return rc;
-    if (fp8 && p->k_scale == nullptr) return fail(FA_ERR_NULL_POINTER, "k_scale is NULL (k_format = 1 writes one scale per token)");
-    if (fp8 && (reinterpret_cast<uintptr_t>(p->k_scale) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "k_scale must be 4-byte aligned");
-    if ((rc = check_io_rows16("k_idx_new", p->k_idx_new, p->k_new_batch_stride, p->k_new_row_stride, 0, dense))) return rc;
     fa::MlaCacheIoParams io;
-    memset(&io, 0, sizeof(io));
-    fill_io_cache(*p, p->k_idx_cache, p->k_cache_batch_stride, p->k_cache_row_stride, fp8 ? 1 : 2, io);
-    io.k_scale = p->k_scale; io.ks_batch = p->k_scale_batch_stride; io.ks_row = p->k_scale_row_stride;
-    io.src = p->k_idx_new; io.s_batch = 2 * p->k_new_batch_stride; io.s_row = 2 * p->k_new_row_stride;
-    io.cu = p->cu_seqlens_new; io.n = p->seqlen_new; io.total = n_rows;
-    return hip_status(fa::launch_mla_index_cache_append(io, p->dtype, fp8 ? 1 + p->scale_format : 0, (hipStream_t)stream), "fa_mla_index_cache_append launch");
+    int64_t n_rows;
+    if ((rc = check_index_append(local, "fa_mla_index_cache_append_params", io, n_rows)) || n_rows == 0) return rc;
+    return hip_status(fa::launch_mla_index_cache_append(io, local.dtype, local.k_format == FA_IDX_K_FP8_E4M3 ? 1 + local.scale_format : 0, (hipStream_t)stream),
+                      "fa_mla_index_cache_append launch");
+}
+
+// ---- the indexer's front end: rotation, quantiser and placement (fa_mla_index_prepare_params) ------------------------------------------------
+int fa_run_mla_index_prepare_queries(const fa_mla_index_prepare_params* user, void* stream) {
+    fa_mla_index_prepare_params local;
+    int rc = import_exact(user, local, "fa_mla_index_prepare_params");
+    if (rc) return rc;
+    const fa_mla_index_prepare_params* p = &local;
+    if ((rc = check_index_prepare_flags(*p))) return rc;
+    if (p->tokens < 0 || p->heads < 1) return fail(FA_ERR_BAD_SHAPE, "bad sizes tokens=%lld heads=%d", (long long)p->tokens, p->heads);
+    if (p->tokens >= ((int64_t)1 << 31) / p->heads) return fail(FA_ERR_BAD_SHAPE, "call too large: tokens = %lld x heads = %d rows exceed the launch grid", (long long)p->tokens, p->heads);
+    if (p->tokens == 0) return FA_OK;       // nothing to write
+    if ((rc = check_io_rows16("q_idx", p->q_idx, p->q_token_stride, p->q_head_stride, 0, true))) return rc;
+    if (p->weights == nullptr || p->w8 == nullptr) return fail(FA_ERR_NULL_POINTER, "%s is NULL", p->weights == nullptr ? "weights" : "w8");
+    if (((reinterpret_cast<uintptr_t>(p->weights) | reinterpret_cast<uintptr_t>(p->w8)) & 3u) != 0) return fail(FA_ERR_BAD_STRIDE, "weights and w8 must be 4-byte aligned");
+    if (p->codes == nullptr) return fail(FA_ERR_NULL_POINTER, "codes is NULL");
+    if ((reinterpret_cast<uintptr_t>(p->codes) & 15u) != 0) return fail(FA_ERR_BAD_STRIDE, "codes base pointer must be 16-byte aligned");
+    fa::MlaIndexPrepareQParams kp;
+    memset(&kp, 0, sizeof(kp));
+    kp.q = p->q_idx; kp.weights = p->weights; kp.codes = p->codes; kp.w8 = p->w8;
+    kp.q_token = 2 * p->q_token_stride; kp.q_head = 2 * p->q_head_stride;
+    kp.w_token = p->w_token_stride; kp.w_head = p->w_head_stride;
+    kp.heads = p->heads; kp.total = p->tokens * p->heads;
+    return hip_status(fa::launch_mla_index_prepare_queries(kp, p->dtype, p->hadamard != 0, p->scale_format == FA_IDX_SCALE_UE8M0, (hipStream_t)stream),
+                      "fa_mla_index_prepare_queries launch");
+}
+
+int fa_run_mla_index_prepare_append(const fa_mla_index_prepare_params* user, void* stream) {
+    fa_mla_index_prepare_params local;
+    int rc = import_exact(user, local, "fa_mla_index_prepare_params");
+    if (rc) return rc;
+    if ((rc = check_index_prepare_flags(local))) return rc;
+    if (local.hadamard != 1) return fail(FA_ERR_BAD_SHAPE, "hadamard must be 1 for the append (without the rotation it is fa_run_mla_index_cache_append)");
+    if (local.k_format != FA_IDX_K_FP8_E4M3)
+        return fail(FA_ERR_BAD_DTYPE, "k_format %d: the append quantises into an FP8 k_idx_cache (1 = OCP e4m3 codes); rotated 16-bit rows are out of scope", local.k_format);
+    fa::MlaCacheIoParams io;
+    int64_t n_rows;
+    if ((rc = check_index_append(local, "fa_mla_index_prepare_params", io, n_rows)) || n_rows == 0) return rc;
+    return hip_status(fa::launch_mla_index_prepare_append(io, local.dtype, local.scale_format == FA_IDX_SCALE_UE8M0, (hipStream_t)stream), "fa_mla_index_prepare_append launch");
 }
 
 }  // extern "C"

@@ -914,6 +914,55 @@ void mla_index_cache_append(at::Tensor k_idx_cache, at::Tensor k_idx_new, at::Te
     check_status(fa_run_mla_index_cache_append(&p, current_stream(k_idx_cache)));
 }
 
+// The indexer's front end (fa_run_mla_index_prepare_queries / fa_run_mla_index_prepare_append).  The Python layer has checked shapes, dtypes and views and
+// flattened q_idx to (tokens, heads, 128), weights to (tokens, heads).
+std::vector<at::Tensor> mla_index_prepare_queries(at::Tensor q_idx, at::Tensor weights, bool hadamard, int64_t scale_format) {
+    TORCH_CHECK(q_idx.is_cuda() && weights.is_cuda(), "q_idx, weights must be GPU (HIP) tensors");
+    TORCH_CHECK(q_idx.dim() == 3 && weights.dim() == 2 && weights.scalar_type() == torch::kFloat32, "q_idx (tokens, heads, 128), weights float32 (tokens, heads)");
+    check_same_device(q_idx, weights, "weights");
+    c10::DeviceGuard guard(q_idx.device());
+    at::Tensor codes = torch::empty({q_idx.size(0), q_idx.size(1), q_idx.size(2)}, q_idx.options().dtype(torch::kUInt8));
+    at::Tensor w8 = torch::empty({q_idx.size(0), q_idx.size(1)}, weights.options());
+    fa_mla_index_prepare_params p;
+    FA_PARAMS_INIT(p);
+    p.q_idx = q_idx.data_ptr(); p.weights = weights.data_ptr<float>(); p.codes = codes.data_ptr(); p.w8 = w8.data_ptr<float>();
+    p.dtype = fa_dtype_of(q_idx); p.scale_format = (int32_t)scale_format; p.hadamard = hadamard ? 1 : 0;
+    p.tokens = q_idx.size(0); p.heads = (int32_t)q_idx.size(1);
+    p.q_token_stride = q_idx.stride(0); p.q_head_stride = q_idx.stride(1);
+    p.w_token_stride = weights.stride(0); p.w_head_stride = weights.stride(1);
+    check_status(fa_run_mla_index_prepare_queries(&p, current_stream(q_idx)));
+    return {codes, w8};
+}
+
+void mla_index_prepare_append(at::Tensor k_idx_cache, at::Tensor k_idx_new, at::Tensor cache_seqlens, at::Tensor k_scale, c10::optional<at::Tensor> block_table_,
+                              c10::optional<at::Tensor> cu_seqlens_new_, int64_t scale_format) {
+    TORCH_CHECK(k_idx_cache.is_cuda() && k_idx_new.is_cuda(), "k_idx_cache, k_idx_new must be GPU (HIP) tensors");
+    const bool packed = cu_seqlens_new_.has_value();
+    TORCH_CHECK(k_idx_cache.dim() == 3 && k_idx_cache.element_size() == 1 && k_idx_new.dim() == (packed ? 2 : 3),
+                "k_idx_cache FP8 (b, capacity, 128), k_idx_new (b, s_new, 128) or packed (total_new, 128)");
+    check_same_device(k_idx_cache, k_scale, "k_scale");
+    TORCH_CHECK(k_scale.scalar_type() == torch::kFloat32 && k_scale.dim() == 2, "k_scale must be a float32 tensor with one value per cached token");
+    const int64_t batch_size = cache_seqlens.size(0);
+    c10::DeviceGuard guard(k_idx_cache.device());
+    fa_mla_index_prepare_params p;
+    FA_PARAMS_INIT(p);
+    int64_t seqlen_cache = k_idx_cache.size(1);
+    if (block_table_.has_value()) seqlen_cache = attach_block_table(p, k_idx_cache, batch_size, *block_table_, k_idx_cache);
+    p.k_idx_cache = k_idx_cache.data_ptr(); p.k_idx_new = k_idx_new.data_ptr();
+    p.cache_seqlens = cache_seqlens_ptr(k_idx_cache, batch_size, cache_seqlens);
+    p.b = (int32_t)batch_size; p.seqlen_cache = (int32_t)seqlen_cache; p.dtype = fa_dtype_of(k_idx_new);
+    p.k_format = FA_IDX_K_FP8_E4M3; p.scale_format = (int32_t)scale_format; p.hadamard = 1;
+    p.k_cache_batch_stride = k_idx_cache.stride(0); p.k_cache_row_stride = k_idx_cache.stride(1);      // (a 1-byte dtype: bytes, as the format asks)
+    p.k_scale = k_scale.data_ptr<float>(); p.k_scale_batch_stride = k_scale.stride(0); p.k_scale_row_stride = k_scale.stride(1);
+    if (packed) {
+        check_same_device(k_idx_cache, *cu_seqlens_new_, "cu_seqlens_new");
+        p.cu_seqlens_new = cu_seqlens_new_->data_ptr<int32_t>(); p.total_new = k_idx_new.size(0); p.k_new_row_stride = k_idx_new.stride(0);
+    } else {
+        p.seqlen_new = (int32_t)k_idx_new.size(1); p.k_new_batch_stride = k_idx_new.stride(0); p.k_new_row_stride = k_idx_new.stride(1);
+    }
+    check_status(fa_run_mla_index_prepare_append(&p, current_stream(k_idx_cache)));
+}
+
 // ---- autograd nodes in C++ ------------------------------------------------------------------------------------------------------
 // The reference ships the four raw functions only; its README's flash_attn_func is an older Python-level API.  The differentiable wrappers
 // of this package used to be torch.autograd.Function subclasses in Python: ~85 us of host time per forward + backward, more than the GPU
@@ -1000,6 +1049,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("batch_size") = 0);
     m.def("mla_index_cache_append", &mla_index_cache_append, "append index keys (16-bit, or e4m3 codes with one scale per token) to the index-key cache, in place",
           py::arg("k_idx_cache"), py::arg("k_idx_new"), py::arg("cache_seqlens"), py::arg("k_scale") = py::none(), py::arg("block_table") = py::none(),
+          py::arg("cu_seqlens_new") = py::none(), py::arg("scale_format") = 0);
+    m.def("mla_index_prepare_queries", &mla_index_prepare_queries, "rotate (optional) and quantise index queries to e4m3 codes, the row scale folded into the head's weight: (codes, w8)",
+          py::arg("q_idx"), py::arg("weights"), py::arg("hadamard") = true, py::arg("scale_format") = 0);
+    m.def("mla_index_prepare_append", &mla_index_prepare_append, "rotate, quantise and append index keys to the FP8 index-key cache, in place",
+          py::arg("k_idx_cache"), py::arg("k_idx_new"), py::arg("cache_seqlens"), py::arg("k_scale"), py::arg("block_table") = py::none(),
           py::arg("cu_seqlens_new") = py::none(), py::arg("scale_format") = 0);
     m.def("mla_indexer_topk", &mla_indexer_topk, "top-k positions of every logits row into the caller's int32 buffer (b, sq, topk)", py::arg("logits"), py::arg("cache_seqlens"),
           py::arg("indices"), py::arg("is_causal") = true);

@@ -245,6 +245,19 @@ class MlaIndexCacheAppendParams(_Params):
                 ("block_table_stride", ctypes.c_int64)]
 
 
+class MlaIndexPrepareParams(_Params):
+    """fa_mla_index_prepare_params: the indexer's front end - rotate and quantise index queries (fa_run_mla_index_prepare_queries), rotate, quantise and place index
+    keys (fa_run_mla_index_prepare_append)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("q_idx", _vp), ("weights", _vp), ("codes", _vp), ("w8", _vp), ("k_idx_cache", _vp),
+                ("k_scale", _vp), ("k_idx_new", _vp), ("cache_seqlens", _vp), ("cu_seqlens_new", _vp), ("block_table", _vp),
+                ("dtype", _i32), ("scale_format", _i32), ("hadamard", _i32), ("k_format", _i32), ("heads", _i32), ("b", _i32), ("seqlen_new", _i32),
+                ("seqlen_cache", _i32), ("page_block_size", _i32), ("num_blocks", _i32), ("tokens", ctypes.c_int64), ("total_new", ctypes.c_int64),
+                ("reserved_", ctypes.c_int64), ("q_token_stride", ctypes.c_int64), ("q_head_stride", ctypes.c_int64), ("w_token_stride", ctypes.c_int64),
+                ("w_head_stride", ctypes.c_int64), ("k_cache_batch_stride", ctypes.c_int64), ("k_cache_row_stride", ctypes.c_int64),
+                ("k_scale_batch_stride", ctypes.c_int64), ("k_scale_row_stride", ctypes.c_int64), ("k_new_batch_stride", ctypes.c_int64),
+                ("k_new_row_stride", ctypes.c_int64), ("block_table_stride", ctypes.c_int64)]
+
+
 FA_MLA_KV_16BIT = 0
 FA_MLA_KV_FP8_ROWS656 = 1     # 656-byte latent rows: 512 e4m3 codes, four fp32 scales, 64 rope elements of q's dtype; kv_cache_stride in bytes
 FA_CACHE_FP8_E4M3 = 1
@@ -339,6 +352,10 @@ def lib():
         L.fa_run_mla_cache_gather.restype = ctypes.c_int
         L.fa_run_mla_index_cache_append.argtypes = [ctypes.POINTER(MlaIndexCacheAppendParams), _vp]
         L.fa_run_mla_index_cache_append.restype = ctypes.c_int
+        L.fa_run_mla_index_prepare_queries.argtypes = [ctypes.POINTER(MlaIndexPrepareParams), _vp]
+        L.fa_run_mla_index_prepare_queries.restype = ctypes.c_int
+        L.fa_run_mla_index_prepare_append.argtypes = [ctypes.POINTER(MlaIndexPrepareParams), _vp]
+        L.fa_run_mla_index_prepare_append.restype = ctypes.c_int
         L.fa_mha_fwd.argtypes = [_vp] * 5 + [_i32] * 8 + [_vp]
         L.fa_mha_bwd.argtypes = [_vp] * 10 + [_i32] * 8 + [_vp]
         L.fa_mha_varlen_fwd.argtypes = [_vp] * 7 + [_i32] * 8 + [_vp]
@@ -1003,3 +1020,42 @@ def run_mla_cache_gather(params, stream=None):
 def run_mla_index_cache_append(params, stream=None):
     """fa_run_mla_index_cache_append"""
     _run_io("fa_run_mla_index_cache_append", params, stream)
+
+
+def mla_index_prepare_queries_params(q_idx, weights, codes, w8, hadamard=True, scale_format=FA_IDX_SCALE_FP32):
+    """fa_mla_index_prepare_params for q_idx (tokens, heads, 128) fp16 / bf16, weights float32 (tokens, heads), and the caller's contiguous codes uint8 (tokens,
+    heads, 128) and w8 float32 (tokens, heads)"""
+    p = MlaIndexPrepareParams()
+    p.q_idx, p.weights, p.codes, p.w8 = q_idx.data_ptr(), weights.data_ptr(), codes.data_ptr(), w8.data_ptr()
+    p.dtype, p.scale_format, p.hadamard = dtype_code(q_idx.dtype), scale_format, int(hadamard)
+    p.tokens, p.heads = q_idx.shape[0], q_idx.shape[1]
+    p.q_token_stride, p.q_head_stride, p.w_token_stride, p.w_head_stride = q_idx.stride(0), q_idx.stride(1), weights.stride(0), weights.stride(1)
+    return p
+
+
+def mla_index_prepare_append_params(k_idx_cache, k_idx_new, cache_seqlens, k_scale, block_table=None, cu_seqlens_new=None, scale_format=FA_IDX_SCALE_FP32):
+    """fa_mla_index_prepare_params for the arguments of mla_index_cache_append_params over an FP8 k_idx_cache"""
+    packed = cu_seqlens_new is not None
+    p = MlaIndexPrepareParams()
+    p.k_idx_cache, p.k_idx_new, p.cache_seqlens = k_idx_cache.data_ptr(), k_idx_new.data_ptr(), cache_seqlens.data_ptr()
+    p.b, p.dtype, p.scale_format, p.hadamard = cache_seqlens.shape[0], dtype_code(k_idx_new.dtype), scale_format, 1
+    p.k_format = FA_IDX_K_FP8_E4M3 if k_idx_cache.element_size() == 1 else FA_MLA_KV_16BIT
+    _attach_paging(p, block_table, k_idx_cache)
+    p.k_cache_batch_stride, p.k_cache_row_stride = k_idx_cache.stride(0), k_idx_cache.stride(1)
+    if k_scale is not None:
+        p.k_scale, p.k_scale_batch_stride, p.k_scale_row_stride = k_scale.data_ptr(), k_scale.stride(0), k_scale.stride(1)
+    if packed:
+        p.cu_seqlens_new, p.total_new, p.k_new_row_stride = cu_seqlens_new.data_ptr(), k_idx_new.shape[0], k_idx_new.stride(0)
+    else:
+        p.seqlen_new, p.k_new_batch_stride, p.k_new_row_stride = k_idx_new.shape[1], k_idx_new.stride(0), k_idx_new.stride(1)
+    return p
+
+
+def run_mla_index_prepare_queries(params, stream=None):
+    """fa_run_mla_index_prepare_queries"""
+    _run_io("fa_run_mla_index_prepare_queries", params, stream)
+
+
+def run_mla_index_prepare_append(params, stream=None):
+    """fa_run_mla_index_prepare_append"""
+    _run_io("fa_run_mla_index_prepare_append", params, stream)

@@ -1568,3 +1568,105 @@ def flash_mla_index_cache_append(k_idx_cache, k_idx_new, cache_seqlens, *, k_sca
         return None
     _C.mla_index_cache_append(k_idx_cache, k_idx_new, cache_seqlens, k_scale, block_table, cu_seqlens_new, fmt)
     return None
+
+
+# ---- the indexer's front end: Hadamard rotation, quantiser and placement in one launch -----------------------------------------------------------------------
+
+def _check_prepare_rows(name, t, min_rank, shape):
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"{name} must be an fp16 / bf16 tensor {shape}, got {getattr(t, 'dtype', type(t))}")
+    if t.dim() < min_rank or t.shape[-1] != 128:
+        raise ValueError(f"{name} must have shape {shape}: the last dimension must be 128, got {tuple(t.shape)}")
+    if t.stride(-1) != 1:
+        raise ValueError(f"{name}: the last dimension must be contiguous")
+
+
+def rotate_mla_index_rows(x):
+    """(..., 128) fp16 / bf16 -> the same shape and dtype: the rotation DeepSeek-V3.2 applies to every index query head and every index key after RoPE
+    (rotate_activation: a 128-point Hadamard transform times 128 ** -0.5), as flash_mla_index_prepare_queries / _append define it.
+
+    With H[c][d] = (-1) ** popcount(c & d) (Sylvester order) and T = x.dtype: ``y[c] = round_to_T(fl32(sum_d H[c][d] * float(x[d])) * fl32(128 ** -0.5))``.
+    Here the sum is taken in fp64 and rounded to fp32 - on data whose partial sums are exact in fp32 the number every fp32 order gives -, the product is one
+    fp32 multiplication, and there is one round-to-nearest-even to T: the model's transform returns its input dtype before the quantiser sees it.  Plain torch,
+    any device."""
+    _check_prepare_rows("x", x, 1, "(..., 128)")
+    i = torch.arange(128, device=x.device)
+    par = i[:, None] & i[None, :]
+    for sh in (4, 2, 1):
+        par = par ^ (par >> sh)
+    h = (1 - 2 * (par & 1)).to(torch.float64)
+    s32 = torch.tensor(128 ** -0.5, dtype=torch.float32, device=x.device)
+    return ((x.to(torch.float64) @ h).to(torch.float32) * s32).to(x.dtype)
+
+
+def flash_mla_index_prepare_queries(q_idx, weights, *, hadamard=True, scale_format="fp32"):
+    """Index queries -> what flash_mla_indexer_logits, flash_mla_indexer_prefill_logits and the two composites take as an FP8 q_idx, in one launch on the GPU.
+
+    q_idx: (..., heads, 128) fp16 / bf16 after RoPE, heads >= 1, the last dimension contiguous.  weights: float32 q_idx.shape[:-1], any strides (fold softmax_scale
+    and heads ** -0.5 into them, as today).  Returns (codes uint8 q_idx.shape, w8 float32 q_idx.shape[:-1]), both contiguous and freshly allocated.
+    Each (token, head) row is rotated (``hadamard``; rotate_mla_index_rows states the rule), quantised by the row rule of quantize_mla_index_keys - amax over the
+    finite elements, scale = max(amax, 2^-24) / 448 correctly rounded, under scale_format="ue8m0" rounded up to a power of two on its bits, code =
+    e4m3_rne(clamp(float(y) / scale, -448, 448)), NaN kept with its sign, +-inf saturating - and the scale is folded into the head's weight: w8 = weights * scale,
+    one fp32 product.
+    hadamard=False: the bytes of quantize_mla_index_queries(q_idx, weights, scale_format) on every input.  hadamard=True: where every partial sum of the transform
+    is exact in fp32 (integers below 2^24), the bytes of quantize_mla_index_queries(rotate_mla_index_rows(q_idx), weights, scale_format); on other finite data the
+    fp32 sum's order is the kernel's and the result is within the rounding of that sum.  A row that holds a NaN or an inf has no value contract under rotation
+    (inf - inf is NaN): its codes and its weight are unspecified; no other row changes.
+    A q_idx whose leading dimensions do not flatten as a view, or whose token stride, head stride or storage offset is not a multiple of 8 elements, is made
+    contiguous once.  No host synchronisation; capturable in a graph.
+    Out of scope: RoPE or LayerNorm inside the call, 16-bit rotated outputs, widths other than 128, block-scaled formats, a caller-provided out."""
+    _check_prepare_rows("q_idx", q_idx, 2, "(..., heads, 128)")
+    heads = q_idx.shape[-2]
+    if heads < 1:
+        raise ValueError(f"q_idx needs heads >= 1, got shape {tuple(q_idx.shape)}")
+    if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32:
+        raise ValueError(f"weights must be a float32 tensor of shape {tuple(q_idx.shape[:-1])} (q_idx without its last dimension)")
+    if tuple(weights.shape) != tuple(q_idx.shape[:-1]) or weights.device != q_idx.device:
+        raise ValueError(f"weights must have shape {tuple(q_idx.shape[:-1])} (q_idx without its last dimension) on q_idx's device, got {tuple(weights.shape)}")
+    if not isinstance(hadamard, bool):
+        raise ValueError(f"hadamard must be a bool, got {hadamard!r}")
+    fmt = _check_scale_format(scale_format)
+    lead = tuple(q_idx.shape[:-2])
+    try:
+        q3 = q_idx.view(-1, heads, 128) if q_idx.numel() else q_idx.reshape(0, heads, 128)
+    except RuntimeError:
+        q3 = q_idx.reshape(-1, heads, 128)          # (the leading dimensions do not flatten as a view: one copy)
+    if any(q3.stride(i) % 8 != 0 for i in range(2)) or q3.storage_offset() % 8 != 0 or (q3.device.type != "meta" and q3.data_ptr() % 16 != 0):
+        q3 = q3.clone(memory_format=torch.contiguous_format)
+    if q3.shape[0] == 0:
+        return torch.empty(lead + (heads, 128), dtype=torch.uint8, device=q_idx.device), torch.empty(lead + (heads,), dtype=torch.float32, device=q_idx.device)
+    codes, w8 = _C.mla_index_prepare_queries(q3, weights.reshape(-1, heads), hadamard, fmt)
+    return codes.view(lead + (heads, 128)), w8.view(lead + (heads,))
+
+
+def flash_mla_index_prepare_append(k_idx_cache, k_idx_new, cache_seqlens, *, k_scale, block_table=None, cu_seqlens_new=None, scale_format="fp32"):
+    """Rotate, quantise and write index keys into the FP8 cache flash_mla_indexer_logits reads, in one launch (in place; returns None).
+
+    The arguments, views, placement, drop and clamp rules of flash_mla_index_cache_append over an FP8 k_idx_cache (float8_e4m3fn / uint8) with its k_scale: the
+    rows written are those of flash_mla_index_cache_append(k_idx_cache, rotate_mla_index_rows(k_idx_new), ...), byte for byte in both buffers where the
+    transform's partial sums are exact in fp32, within the rounding of the fp32 sum otherwise (see flash_mla_index_prepare_queries; a row with a NaN or an inf is
+    unspecified).  Every byte of k_idx_cache and k_scale that is not a target keeps its value.  No host synchronisation; capturable in a graph.
+    A 16-bit k_idx_cache is a ValueError: rotated 16-bit rows are out of scope."""
+    if not isinstance(k_idx_cache, torch.Tensor) or k_idx_cache.dim() != 3:
+        raise ValueError("k_idx_cache must be a rank-3 tensor (batch, capacity, 128), or a page pool (num_blocks, page_block_size, 128) with block_table")
+    if k_idx_cache.dtype not in (torch.uint8, torch.float8_e4m3fn):
+        raise ValueError(f"k_idx_cache must hold e4m3 codes (float8_e4m3fn / uint8), got {k_idx_cache.dtype}: rotated 16-bit rows are out of scope")
+    if k_idx_cache.shape[2] != 128:
+        raise ValueError(f"k_idx_cache must be 128 wide, got {k_idx_cache.shape[2]}")
+    _check_idx_cache_view(k_idx_cache, True)
+    b = _check_io_new_rows("k_idx_new", k_idx_new, "cu_seqlens_new", cu_seqlens_new, k_idx_cache, (128,), (128,))
+    fmt = _check_scale_format(scale_format)
+    if k_scale is None:
+        raise ValueError("k_scale is required: a float32 tensor with one scale per cached token")
+    if not isinstance(k_scale, torch.Tensor) or k_scale.dtype != torch.float32:
+        raise ValueError("k_scale must be a float32 tensor with one scale per cached token")
+    if tuple(k_scale.shape) != tuple(k_idx_cache.shape[:2]) or k_scale.device != k_idx_cache.device:
+        raise ValueError(f"k_scale must have shape {tuple(k_idx_cache.shape[:2])} (k_idx_cache without its last dimension) on k_idx_cache's device, got {tuple(k_scale.shape)}")
+    if k_scale.device.type != "meta" and k_scale.data_ptr() % 4 != 0:
+        raise ValueError("k_scale must be 4-byte aligned")
+    _check_block_table(block_table, _Batch(b, k_idx_cache.device), k_idx_cache, like="k_idx_new", pool_name="k_idx_cache")
+    cache_seqlens = _io_lengths(cache_seqlens, b, k_idx_cache.device, "k_idx_cache")
+    if b == 0 or k_idx_new.shape[0] == 0 or (cu_seqlens_new is None and k_idx_new.shape[1] == 0):
+        return None
+    _C.mla_index_prepare_append(k_idx_cache, k_idx_new, cache_seqlens, k_scale, block_table, cu_seqlens_new, fmt)
+    return None

@@ -1200,6 +1200,63 @@ typedef struct fa_mla_index_cache_append_params {
     int64_t block_table_stride;
 } fa_mla_index_cache_append_params;
 
+/* The indexer's front end (FA_HAS_MLA_INDEX_PREPARE; rotate_activation + act_quant of DeepSeek-V3.2, upstream the CUDA package fast_hadamard_transform followed by
+ * torch): what fa_run_mla_indexer_logits(_v2) and fa_run_mla_indexer_prefill_logits(_v2) consume, made on the GPU in one launch.  FA_ABI_VERSION is unchanged.
+ * One struct with the {struct_size, magic} header for two calls; struct_size must be the struct's own size; each call reads its own fields and ignores the other's.
+ * One launch on `stream`, no workspace, no host synchronisation.
+ * The rotation (hadamard = 1), with H[c][d] = (-1) ** popcount(c & d) and T = dtype: y[c] = round_to_T(fl32(sum_d H[c][d] * float(x[d])) * fl32(128 ** -0.5)),
+ * the sum in fp32 in an order the contract does not fix, one round-to-nearest-even to T.  hadamard = 0: y = x.  A row that holds a NaN or an inf has no value
+ * contract under hadamard = 1 (its codes and scale are unspecified); no other row changes.
+ * The quantiser: the row rule of fa_mla_index_cache_append_params on y, scale_format included.
+ * fa_run_mla_index_prepare_queries.  q_idx (tokens, heads, 128) of `dtype`, heads >= 1, strides in elements (multiples of 8, pointer 16-byte aligned); weights
+ * float32 (tokens, heads), any strides.  Writes codes, uint8 (tokens, heads, 128) contiguous (16-byte aligned), and w8 = weights * scale, float32 (tokens, heads)
+ * contiguous, one fp32 product: the q_idx (q_format FA_IDX_Q_FP8_E4M3) and weights of fa_mla_indexer_params_v2.  With hadamard = 0 the bytes are those of the
+ * quantiser alone on every input.
+ * fa_run_mla_index_prepare_append.  The fields, views, placement, drop and clamp rules of fa_run_mla_index_cache_append with k_format = FA_IDX_K_FP8_E4M3 (any
+ * other k_format is FA_ERR_BAD_DTYPE: rotated 16-bit rows are out of scope) and hadamard = 1 (0 is FA_ERR_BAD_SHAPE: that is fa_run_mla_index_cache_append): the
+ * rows of k_idx_new are rotated, quantised and placed; every byte of k_idx_cache and k_scale that is not a target keeps its value.
+ * Errors name the field, with the codes of fa_mla_index_cache_append_params; tokens < 0, heads < 1, a hadamard other than 0 / 1 are FA_ERR_BAD_SHAPE.  tokens == 0 /
+ * no row to move is FA_OK without a launch. */
+#define FA_HAS_MLA_INDEX_PREPARE 1
+typedef struct fa_mla_index_prepare_params {
+    uint32_t struct_size;       /* sizeof(fa_mla_index_prepare_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const void* q_idx;          /* queries */
+    const float* weights;       /* queries */
+    void* codes;                /* queries: out */
+    float* w8;                  /* queries: out */
+    void* k_idx_cache;          /* append */
+    float* k_scale;             /* append */
+    const void* k_idx_new;      /* append */
+    const int32_t* cache_seqlens;       /* append */
+    const int32_t* cu_seqlens_new;      /* append; NULL: dense */
+    const int32_t* block_table; /* append, paged cache; NULL = contiguous */
+    int32_t dtype;
+    int32_t scale_format;       /* FA_IDX_SCALE_FP32 / FA_IDX_SCALE_UE8M0 */
+    int32_t hadamard;           /* 1: rotate; 0: quantise only (queries) */
+    int32_t k_format;           /* append: FA_IDX_K_FP8_E4M3 */
+    int32_t heads;              /* queries */
+    int32_t b;                  /* append */
+    int32_t seqlen_new;         /* append, dense: new rows per sequence */
+    int32_t seqlen_cache;       /* append */
+    int32_t page_block_size;
+    int32_t num_blocks;
+    int64_t tokens;             /* queries */
+    int64_t total_new;          /* append, packed: rows of k_idx_new */
+    int64_t reserved_;          /* 0 */
+    int64_t q_token_stride;     /* elements */
+    int64_t q_head_stride;      /* elements */
+    int64_t w_token_stride;
+    int64_t w_head_stride;
+    int64_t k_cache_batch_stride;       /* bytes, as in fa_mla_index_cache_append_params under FA_IDX_K_FP8_E4M3 */
+    int64_t k_cache_row_stride;
+    int64_t k_scale_batch_stride;
+    int64_t k_scale_row_stride;
+    int64_t k_new_batch_stride; /* elements; dense only */
+    int64_t k_new_row_stride;   /* elements */
+    int64_t block_table_stride;
+} fa_mla_index_prepare_params;
+
 /* ---- library info ---------------------------------------------------------------------- */
 int fa_abi_version(void);
 const char* fa_last_error(void);
@@ -1318,6 +1375,11 @@ int fa_run_merge_states(const fa_merge_params* params);
 int fa_run_mla_cache_append(const fa_mla_cache_append_params* params, void* stream);
 int fa_run_mla_cache_gather(const fa_mla_cache_gather_params* params, void* stream);
 int fa_run_mla_index_cache_append(const fa_mla_index_cache_append_params* params, void* stream);
+
+/* ---- the indexer's front end (fa_mla_index_prepare_params above) ------------------------------------------------------------- */
+/* One launch each on `stream`, no workspace, no host synchronisation. */
+int fa_run_mla_index_prepare_queries(const fa_mla_index_prepare_params* params, void* stream);
+int fa_run_mla_index_prepare_append(const fa_mla_index_prepare_params* params, void* stream);
 
 /* ---- measurement helpers ----------------------------------------------------------------- */
 /* Algorithmic FLOPs of one forward call (4*b*h*sq*sk*d, causal counts only visible pairs);

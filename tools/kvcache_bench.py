@@ -1488,6 +1488,52 @@ def run_mla_cache_io(quick, rounds, page=64, dt=torch.bfloat16):
             torch.cuda.empty_cache()
 
 
+def run_mla_index_prepare(quick, rounds, heads=64, page=64, dt=torch.bfloat16):
+    """The indexer's front end, bf16.  Queries (64 heads, tokens in {1, 64, 4096}): flash_mla_index_prepare_queries against the torch formulation, q @ Hmat in q's
+    dtype followed by quantize_mla_index_queries.  Keys (b 64 x 1 and 1 x 4096 new rows, pages of 64): flash_mla_index_prepare_append against
+    flash_mla_index_cache_append on pre-rotated input.  Interleaved in one process, each yardstick timed twice (its noise figure); the bits are asserted on
+    integer data first.  Bytes moved (16-bit rows read + codes and scales written) / time against 6.3 TB/s"""
+    dev = torch.device("cuda:0")
+    i = torch.arange(128, device=dev)
+    par = i[:, None] & i[None, :]
+    for sh in (4, 2, 1):
+        par = par ^ (par >> sh)
+    hmat = ((1 - 2 * (par & 1)).float() * 128 ** -0.5).to(dt)
+    gen = torch.Generator(device=dev).manual_seed(5)
+    ints = lambda *shape: torch.randint(-7, 8, shape, device=dev, generator=gen).to(dt)
+
+    def point(mode, b, rows, ours, yardstick, nbytes):
+        ms = _mlap_time({"yardstick": yardstick, "ours": ours, "yardstick_again": yardstick}, rounds, iters=3)
+        return dict(mode=mode, b=b, rows_per_seq=rows, dtype="bfloat16", mbytes=round(nbytes / 2 ** 20, 3), ms_ours=round(ms["ours"], 4), tb_s=round(nbytes / ms["ours"] / 1e9, 3),
+                    frac_of_6p3=round(nbytes / ms["ours"] / 1e9 / 6.3, 4), ms_yardstick=round(ms["yardstick"], 4), ms_yardstick_again=round(ms["yardstick_again"], 4),
+                    ours_over_yardstick=round(ms["ours"] / ms["yardstick"], 3), bits_equal_on_integers=True)
+
+    for tokens in ((1, 4096) if quick else (1, 64, 4096)):
+        q, w = ints(tokens, heads, 128), torch.randn(tokens, heads, device=dev, generator=gen)
+        want = F.quantize_mla_index_queries(F.rotate_mla_index_rows(q.cpu()), w.cpu())
+        got = F.flash_mla_index_prepare_queries(q, w)
+        assert torch.equal(got[0].cpu(), want[0]) and torch.equal(got[1].cpu().view(torch.int32), want[1].view(torch.int32)), "prepared queries differ from the reference"
+        q = torch.randn(tokens, heads, 128, device=dev, generator=gen).to(dt)
+        yield point("mla_index_prepare_queries", 1, tokens, lambda: F.flash_mla_index_prepare_queries(q, w), lambda: F.quantize_mla_index_queries(q @ hmat, w),
+                    tokens * heads * (256 + 4 + 128 + 4))
+    for b, s_new in ((64, 1), (1, 4096)):
+        cols = 8192 // page
+        nb = b * cols
+        table = torch.randperm(nb, device=dev, generator=gen).view(b, cols).to(torch.int32)
+        lens = torch.full((b,), 1000, dtype=torch.int32, device=dev)
+        k_new = ints(b, s_new, 128)
+        k_rot = F.rotate_mla_index_rows(k_new)
+        kc, kc_y = (torch.zeros(nb, page, 128, dtype=torch.uint8, device=dev) for _ in range(2))
+        ks, ks_y = (torch.zeros(nb, page, device=dev) for _ in range(2))
+        ours = lambda: F.flash_mla_index_prepare_append(kc, k_new, lens, k_scale=ks, block_table=table)
+        yardstick = lambda: F.flash_mla_index_cache_append(kc_y, k_rot, lens, k_scale=ks_y, block_table=table)
+        ours(), yardstick()
+        assert torch.equal(kc, kc_y) and torch.equal(ks.view(torch.int32), ks_y.view(torch.int32)), "the prepared append differs from the append of rotated rows"
+        k_new.copy_(torch.randn(b, s_new, 128, device=dev, generator=gen))
+        k_rot.copy_(F.rotate_mla_index_rows(k_new))
+        yield point("mla_index_prepare_append", b, s_new, ours, yardstick, b * s_new * (256 + 128 + 4))
+
+
 def _baseline_lib(path):
     L = ctypes.CDLL(os.path.abspath(path))
     L.fa_run_mha_fwd_kvcache.argtypes = [ctypes.POINTER(capi.KvcacheParams), ctypes.c_void_p]
@@ -1596,6 +1642,9 @@ def main():
     ap.add_argument("--mla-cache-io", action="store_true", help="flash_mla_cache_append / flash_mla_index_cache_append (1 and 2048 new rows a sequence) and "
                                                                 "flash_mla_cache_gather (4k and 32k rows) on FP8 caches, pages of 64, bf16, b in {1, 8, 64}: bytes moved / "
                                                                 "time against 6.3 TB/s, next to the torch formulation of each (timed twice)")
+    ap.add_argument("--mla-index-prepare", action="store_true", help="the indexer's front end (flash_mla_index_prepare_queries: 64 heads, 1 / 64 / 4096 tokens; "
+                                                                     "flash_mla_index_prepare_append: b 64 x 1 and 1 x 4096 new rows, pages of 64; bf16): bytes moved / time against "
+                                                                     "6.3 TB/s, next to the torch formulation / the append of pre-rotated rows (timed twice)")
     a = ap.parse_args()
     base = _baseline_lib(a.baseline_library) if a.baseline_library else None
     print(json.dumps({"library": F.build_info(), "device": torch.cuda.get_device_name(0), "cus": torch.cuda.get_device_properties(0).multi_processor_count}),
@@ -1603,8 +1652,8 @@ def main():
     if base is not None:
         print(json.dumps({"baseline_library": base.fa_build_info().decode()}), flush=True)
     with torch.no_grad():
-        if a.merge or a.shared_prefix or a.mla_cache_io:
-            for line in (run_merge if a.merge else run_shared_prefix if a.shared_prefix else run_mla_cache_io)(a.quick, a.rounds):
+        if a.merge or a.shared_prefix or a.mla_cache_io or a.mla_index_prepare:
+            for line in (run_merge if a.merge else run_shared_prefix if a.shared_prefix else run_mla_cache_io if a.mla_cache_io else run_mla_index_prepare)(a.quick, a.rounds):
                 print(json.dumps(line), flush=True)
             return
         if a.mla_prefill_bwd:
