@@ -1274,15 +1274,36 @@ int fa_mla_indexer_prefill_launch_v2(const fa_mla_indexer_params_v2* user, int32
     return mla_indexer_prefill_launch(user, true, tokens_per_wg, wg_keys, n_chunks);
 }
 
-int fa_run_mla_indexer_topk(const fa_mla_topk_params* user, void* stream) {
-    fa_mla_topk_params local;
-    int rc = import_exact(user, local, "fa_mla_topk_params");
-    if (rc) return rc;
-    const fa_mla_topk_params* p = &local;
+// fa_mla_topk_params (72 bytes) and fa_mla_topk_params_v2 (workspace, workspace_bytes, num_splits appended) share their prefix.  v2_entry: one of the _v2 entry
+// points, which take either struct and tell them apart by struct_size (the shorter one arrives as a _v2 without a workspace: one split); fa_run_mla_indexer_topk
+// takes the 72-byte struct alone (import_exact).  with_workspace: the launch and fa_mla_topk_num_splits look at the workspace, fa_mla_topk_workspace_bytes does not.
+static_assert(sizeof(fa_mla_topk_params_v2) == sizeof(fa_mla_topk_params) + 24 && offsetof(fa_mla_topk_params_v2, workspace) == sizeof(fa_mla_topk_params) &&
+                  offsetof(fa_mla_topk_params_v2, logits_row_stride) == offsetof(fa_mla_topk_params, logits_row_stride),
+              "fa_mla_topk_params_v2 is fa_mla_topk_params with a pointer, an int64 and two int32 appended");
+static int fill_mla_topk(const void* user_, bool v2_entry, bool with_workspace, fa_mla_topk_params_v2& local) {
+    memset(&local, 0, sizeof(local));
+    int rc;
+    if (!v2_entry) {
+        rc = import_exact(static_cast<const fa_mla_topk_params*>(user_), reinterpret_cast<fa_mla_topk_params&>(local), "fa_mla_topk_params");
+        if (rc) return rc;
+        local.num_splits = 1;
+    } else {
+        const fa_mla_topk_params_v2* user = static_cast<const fa_mla_topk_params_v2*>(user_);
+        if ((rc = check_header(user, "fa_mla_topk_params_v2", true))) return rc;
+        if (user->struct_size != sizeof(fa_mla_topk_params) && user->struct_size != sizeof(fa_mla_topk_params_v2))
+            return fail(FA_ERR_BAD_ABI, "fa_mla_topk_params_v2: struct_size %u is neither %zu (fa_mla_topk_params) nor %zu - header / library mismatch", user->struct_size,
+                        sizeof(fa_mla_topk_params), sizeof(fa_mla_topk_params_v2));
+        memcpy(&local, user, user->struct_size);
+        if (user->struct_size == sizeof(fa_mla_topk_params)) local.num_splits = 1;
+    }
+    const fa_mla_topk_params_v2* p = &local;
     if (p->b < 0 || p->seqlen_q < 1 || p->seqlen_cache < 0)
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d (>= 1) seqlen_cache=%d", p->b, p->seqlen_q, p->seqlen_cache);
     if (p->topk < 32 || p->topk % 32 != 0) return fail(FA_ERR_BAD_SHAPE, "topk %d must be a positive multiple of 32", p->topk);
     if ((rc = check_reserved(p->reserved_, "fa_mla_topk_params", FA_ERR_BAD_SHAPE))) return rc;
+    if (p->num_splits < 0) return fail(FA_ERR_BAD_SHAPE, "num_splits %d must be >= 0 (0 = chosen by the library)", p->num_splits);
+    if (p->reserved2_ != 0) return fail(FA_ERR_BAD_SHAPE, "reserved2_ is not zero (%d)", p->reserved2_);
+    if (with_workspace && (rc = check_workspace(p->workspace, p->workspace_bytes))) return rc;
     if ((int64_t)p->b * p->seqlen_q >= ((int64_t)1 << 31))
         return fail(FA_ERR_BAD_SHAPE, "call too large: b = %d sequences x seqlen_q = %d tokens exceeds the launch grid", p->b, p->seqlen_q);
     if (p->b == 0) return FA_OK;
@@ -1295,12 +1316,65 @@ int fa_run_mla_indexer_topk(const fa_mla_topk_params* user, void* stream) {
             return fail(FA_ERR_BAD_STRIDE, "logits strides (logits_batch_stride=%lld, logits_row_stride=%lld) must be >= 0 elements", (long long)p->logits_batch_stride,
                         (long long)p->logits_row_stride);
     }
+    return FA_OK;
+}
+
+// Chunks per row of a validated struct.  sized: with the workspace as given (NULL / 0 bytes: 1; a forced count it cannot hold: an error; the rule's count: the
+// largest that fits); else what the call would use with a workspace of fa_mla_topk_workspace_bytes.
+static int32_t mla_topk_split(const fa_mla_topk_params_v2& p, bool sized) {
+    const int64_t rows = (int64_t)p.b * p.seqlen_q;
+    if (rows == 0 || p.seqlen_cache <= p.topk || p.num_splits == 1) return 1;
+    const int cap = fa::mla_topk_max_splits(p.seqlen_cache);
+    int n = p.num_splits == 0 ? fa::mla_topk_auto_splits(rows, p.seqlen_cache, p.topk) : (p.num_splits < cap ? p.num_splits : cap);
+    if (rows * n >= ((int64_t)1 << 31)) n = 1;
+    if (n < 2 || !sized) return n < 2 ? 1 : n;
+    if (p.workspace == nullptr || p.workspace_bytes == 0) return 1;
+    if (p.num_splits != 0 && p.workspace_bytes < fa::mla_topk_workspace_bytes(rows, n))
+        return fail(FA_ERR_BAD_SHAPE, "workspace_bytes %lld cannot hold num_splits = %d chunks per row: %lld bytes needed (fa_mla_topk_workspace_bytes)",
+                    (long long)p.workspace_bytes, n, (long long)fa::mla_topk_workspace_bytes(rows, n));
+    while (n > 1 && p.workspace_bytes < fa::mla_topk_workspace_bytes(rows, n)) --n;
+    return n;
+}
+
+static int run_mla_indexer_topk(const void* user, bool v2_entry, void* stream) {
+    fa_mla_topk_params_v2 local;
+    int rc = fill_mla_topk(user, v2_entry, true, local);
+    if (rc) return rc;
+    const fa_mla_topk_params_v2* p = &local;
+    const int32_t n_split = mla_topk_split(local, true);
+    if (n_split < 0) return n_split;
+    if (p->b == 0) return FA_OK;
+    if (n_split > 1) {
+        fa::MlaTopkSplitParams sp;
+        memset(&sp, 0, sizeof(sp));
+        sp.logits = p->logits; sp.indices = p->indices; sp.cache_seqlens = p->cache_seqlens; sp.ws = (uint32_t*)p->workspace;
+        sp.lg_batch = p->logits_batch_stride; sp.lg_row = p->logits_row_stride;
+        sp.b = p->b; sp.seqlen_q = p->seqlen_q; sp.seqlen_cache = p->seqlen_cache; sp.topk = p->topk; sp.is_causal = p->is_causal ? 1 : 0; sp.n_split = n_split;
+        return hip_status(fa::launch_mla_indexer_topk_split(sp, (hipStream_t)stream), "fa_mla_indexer_topk_split launch");
+    }
     fa::MlaTopkParams tp;
     memset(&tp, 0, sizeof(tp));
     tp.logits = p->logits; tp.indices = p->indices; tp.cache_seqlens = p->cache_seqlens;
     tp.lg_batch = p->logits_batch_stride; tp.lg_row = p->logits_row_stride;
     tp.b = p->b; tp.seqlen_q = p->seqlen_q; tp.seqlen_cache = p->seqlen_cache; tp.topk = p->topk; tp.is_causal = p->is_causal ? 1 : 0;
     return hip_status(fa::launch_mla_indexer_topk(tp, (hipStream_t)stream), "fa_mla_indexer_topk launch");
+}
+
+int fa_run_mla_indexer_topk(const fa_mla_topk_params* user, void* stream) { return run_mla_indexer_topk(user, false, stream); }
+int fa_run_mla_indexer_topk_v2(const fa_mla_topk_params_v2* user, void* stream) { return run_mla_indexer_topk(user, true, stream); }
+
+int64_t fa_mla_topk_workspace_bytes(const fa_mla_topk_params_v2* user) {
+    fa_mla_topk_params_v2 local;
+    int rc = fill_mla_topk(user, true, false, local);
+    if (rc) return rc;
+    return fa::mla_topk_workspace_bytes((int64_t)local.b * local.seqlen_q, mla_topk_split(local, false));
+}
+
+int32_t fa_mla_topk_num_splits(const fa_mla_topk_params_v2* user) {
+    fa_mla_topk_params_v2 local;
+    int rc = fill_mla_topk(user, true, true, local);
+    if (rc) return rc;
+    return mla_topk_split(local, true);
 }
 
 // ---- MLA prefill attention -------------------------------------------------------------------------------------------------------------------

@@ -226,11 +226,6 @@ __global__ __launch_bounds__(kIdxThreads, 2) void fa_mla_indexer_logits_kernel(c
 }
 
 // ---- selection ---------------------------------------------------------------------------------------------------------------------------------
-FA_DEV uint32_t topk_key(float x) {
-    const uint32_t b = __builtin_bit_cast(uint32_t, x);
-    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-}
-
 __global__ __launch_bounds__(kTopkThreads) void fa_mla_indexer_topk_kernel(const MlaTopkParams p) {
     constexpr int NW = kTopkThreads / 64;
     constexpr int U = 8;                        // entries a thread loads before it uses the first: eight row reads in flight per thread

@@ -95,9 +95,39 @@ FA_DEV int idx_len(const int32_t* cache_seqlens, int bidx, int seqlen_cache) {
     return __builtin_amdgcn_readfirstlane(L);
 }
 
+// the order of the selection: fp32 bits -> an unsigned key that sorts like the value (-0 < +0; a NaN with the sign bit clear is above +inf)
+FA_DEV uint32_t topk_key(float x) {
+    const uint32_t b = __builtin_bit_cast(uint32_t, x);
+    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+}
+
 int64_t mla_indexer_logits_shape(MlaIndexerParams& p);    // wg_keys, n_chunks -> the grid; 0: not launchable (host only)
 hipError_t launch_mla_indexer_logits(MlaIndexerParams p, int dtype, hipStream_t s);
 hipError_t launch_mla_indexer_topk(const MlaTopkParams& p, hipStream_t s);
+
+// ---- the selection over several workgroups per row (fa_mla_indexer_topk_split.hip) ---------------------------------------------------------------------------
+constexpr int kTopkHistWords = 4096 + 1024 + 1024;     // a row's three digit histograms in the workspace
+constexpr int kTopkRecWords = 1024 + 16;               // a chunk's record: its last-digit histogram, its count above the 22-bit prefix, padding to 64 bytes
+constexpr int kTopkMaxSplits = 64;                     // the most chunks per row (a forced count above it is cut to it)
+constexpr int kTopkAutoMinLen = 65536;                 // the automatic rule: rows shorter than this stay with one workgroup (five launches cost about 23 us) ...
+constexpr int kTopkAutoMinChunk = 8192;                // ... no chunk shorter than one pass of eight loads a thread ...
+constexpr int kTopkAutoMinSplits = 4;                  // ... and nothing below four chunks per row, i.e. at most 64 rows on 256 compute units
+
+struct MlaTopkSplitParams {
+    const float* logits;            // as in MlaTopkParams
+    int32_t* indices;
+    const int32_t* cache_seqlens;
+    uint32_t* ws;                   // b * seqlen_q rows of mla_topk_row_words(n_split) words
+    int64_t lg_batch, lg_row;       // elements
+    int b, seqlen_q, seqlen_cache, topk;
+    int is_causal, n_split;         // n_split: chunks per row, 2 .. kTopkMaxSplits
+};
+
+__host__ __device__ inline int64_t mla_topk_row_words(int n_split) { return kTopkHistWords + (int64_t)n_split * kTopkRecWords; }
+int64_t mla_topk_workspace_bytes(int64_t rows, int n_split);             // 0 for n_split <= 1 (host only)
+int mla_topk_max_splits(int seqlen_cache);                               // the most chunks a row of this capacity is cut into (host only)
+int mla_topk_auto_splits(int64_t rows, int seqlen_cache, int topk);      // the rule of num_splits = 0 (host only)
+hipError_t launch_mla_indexer_topk_split(const MlaTopkSplitParams& p, hipStream_t s);
 
 // ---- the prefill logits launch (fa_mla_indexer_prefill.hip): a workgroup serves kIdxpTQ consecutive tokens of one sequence and wg_keys keys ----------
 #ifndef FA_IDXP_TQ

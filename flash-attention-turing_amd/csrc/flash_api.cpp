@@ -803,7 +803,9 @@ void mla_indexer_prefill_logits(at::Tensor q_idx, at::Tensor weights, at::Tensor
     mla_indexer_logits_with(fa_run_mla_indexer_prefill_logits_v2, q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale_, block_table_, is_causal);
 }
 
-void mla_indexer_topk(at::Tensor logits, at::Tensor cache_seqlens, at::Tensor indices, bool is_causal) {
+// num_splits: 0 = the library's rule, 1 = one workgroup per row, n > 1 = n chunks per row (fa_mla_topk_params_v2); the workspace comes from the caching allocator
+void mla_indexer_topk(at::Tensor logits, at::Tensor cache_seqlens, at::Tensor indices, bool is_causal, int64_t num_splits) {
+    TORCH_CHECK(num_splits >= 0 && num_splits <= INT32_MAX, "num_splits must be >= 0 (0 = chosen by the library)");
     TORCH_CHECK(logits.dim() == 3 && indices.dim() == 3 && logits.is_cuda(), "logits (b, sq, capacity) and indices (b, sq, topk) must be GPU (HIP) tensors");
     TORCH_CHECK(indices.device() == logits.device() && cache_seqlens.device() == logits.device(), "every tensor must be on logits' device");
     TORCH_CHECK(logits.scalar_type() == torch::kFloat32 && (logits.stride(2) == 1 || logits.size(2) <= 1), "logits must be float32 with a contiguous last dimension");
@@ -813,13 +815,15 @@ void mla_indexer_topk(at::Tensor logits, at::Tensor cache_seqlens, at::Tensor in
                 "cache_seqlens must be a contiguous int32 tensor of shape [batch_size]");
     TORCH_CHECK(logits.size(2) <= INT32_MAX && indices.size(2) <= INT32_MAX, "capacity and topk must fit in int32");
     c10::DeviceGuard guard(logits.device());
-    fa_mla_topk_params p;
+    fa_mla_topk_params_v2 p;
     FA_PARAMS_INIT(p);
     p.logits = logits.data_ptr<float>(); p.indices = indices.data_ptr<int32_t>(); p.cache_seqlens = cache_seqlens.data_ptr<int32_t>();
+    p.num_splits = (int32_t)num_splits;
     p.b = (int32_t)logits.size(0); p.seqlen_q = (int32_t)logits.size(1); p.seqlen_cache = (int32_t)logits.size(2); p.topk = (int32_t)indices.size(2);
     p.is_causal = is_causal;
     p.logits_batch_stride = logits.stride(0); p.logits_row_stride = logits.stride(1);
-    check_status(fa_run_mla_indexer_topk(&p, current_stream(logits)));
+    at::Tensor workspace = attach_workspace(p, fa_mla_topk_workspace_bytes(&p), logits);
+    check_status(fa_run_mla_indexer_topk_v2(&p, current_stream(logits)));
 }
 
 // Stand-alone append and gather for the MLA caches (fa_run_mla_cache_append / fa_run_mla_cache_gather / fa_run_mla_index_cache_append).  The Python layer has
@@ -1056,7 +1060,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("k_idx_cache"), py::arg("k_idx_new"), py::arg("cache_seqlens"), py::arg("k_scale"), py::arg("block_table") = py::none(),
           py::arg("cu_seqlens_new") = py::none(), py::arg("scale_format") = 0);
     m.def("mla_indexer_topk", &mla_indexer_topk, "top-k positions of every logits row into the caller's int32 buffer (b, sq, topk)", py::arg("logits"), py::arg("cache_seqlens"),
-          py::arg("indices"), py::arg("is_causal") = true);
+          py::arg("indices"), py::arg("is_causal") = true, py::arg("num_splits") = 0);
     // three overloads: the signature as it was (every existing call, positional or keyword, resolves to it), the one that continues it with the
     // ragged-batch keywords after rotary_interleaved, and the one that continues that with softmax_scale / softcap
     m.def("fwd_kvcache",

@@ -179,6 +179,11 @@ class MlaTopkParams(_Params):
                 ("logits_batch_stride", ctypes.c_int64), ("logits_row_stride", ctypes.c_int64)]
 
 
+class MlaTopkParamsV2(_Params):
+    """fa_mla_topk_params_v2: fa_mla_topk_params plus a workspace and num_splits (fa_run_mla_indexer_topk_v2: one logits row over several workgroups)"""
+    _fields_ = MlaTopkParams._fields_ + [("workspace", _vp), ("workspace_bytes", ctypes.c_int64), ("num_splits", _i32), ("reserved2_", _i32)]
+
+
 class MlaPrefillParams(_Params):
     """fa_mla_prefill_params: MLA prefill attention, 192-wide q / k and 128-wide v, dense or packed (fa_run_mla_prefill_fwd)"""
     _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("q", _vp), ("k", _vp), ("v", _vp), ("o", _vp), ("lse", _vp),
@@ -340,6 +345,13 @@ def lib():
         L.fa_mla_indexer_prefill_launch.restype = ctypes.c_int
         L.fa_run_mla_indexer_topk.argtypes = [ctypes.POINTER(MlaTopkParams), _vp]
         L.fa_run_mla_indexer_topk.restype = ctypes.c_int
+        # (fa_mla_topk_params_v2 or fa_mla_topk_params through the same pointer: void*)
+        L.fa_run_mla_indexer_topk_v2.argtypes = [_vp, _vp]
+        L.fa_run_mla_indexer_topk_v2.restype = ctypes.c_int
+        L.fa_mla_topk_workspace_bytes.argtypes = [_vp]
+        L.fa_mla_topk_workspace_bytes.restype = ctypes.c_int64
+        L.fa_mla_topk_num_splits.argtypes = [_vp]
+        L.fa_mla_topk_num_splits.restype = ctypes.c_int32
         L.fa_run_mla_prefill_fwd.argtypes = [ctypes.POINTER(MlaPrefillParams), _vp]
         L.fa_run_mla_prefill_fwd.restype = ctypes.c_int
         L.fa_run_mla_prefill_bwd.argtypes = [ctypes.POINTER(MlaPrefillBwdParams), _vp]
@@ -832,9 +844,9 @@ def mla_indexer_prefill_launch(params):
     return tq.value, wg.value, nc.value
 
 
-def mla_topk_params(logits, indices, cache_seqlens=None, causal=True):
+def mla_topk_params(logits, indices, cache_seqlens=None, causal=True, cls=MlaTopkParams):
     """fa_mla_topk_params for logits fp32 (b, sq, capacity), any batch / row strides, and the contiguous int32 buffer indices (b, sq, topk)"""
-    p = MlaTopkParams()
+    p = cls()
     p.logits, p.indices = logits.data_ptr(), indices.data_ptr()
     p.cache_seqlens = None if cache_seqlens is None else cache_seqlens.data_ptr()
     p.b, p.seqlen_q, p.seqlen_cache, p.topk, p.is_causal = logits.shape[0], logits.shape[1], logits.shape[2], indices.shape[-1], int(causal)
@@ -842,12 +854,37 @@ def mla_topk_params(logits, indices, cache_seqlens=None, causal=True):
     return p
 
 
+def mla_topk_params_v2(logits, indices, cache_seqlens=None, causal=True, num_splits=0, workspace=None):
+    """fa_mla_topk_params_v2 for the tensors of mla_topk_params; workspace: a device tensor of at least mla_topk_workspace_bytes(params) bytes, or None (1 split)"""
+    p = mla_topk_params(logits, indices, cache_seqlens, causal, cls=MlaTopkParamsV2)
+    p.num_splits = num_splits
+    if workspace is not None:
+        p.workspace, p.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    return p
+
+
+def mla_topk_workspace_bytes(params) -> int:
+    """fa_mla_topk_workspace_bytes: the workspace params.num_splits needs (0: one split); host only"""
+    n = lib().fa_mla_topk_workspace_bytes(ctypes.byref(params))
+    if n < 0:
+        check(n)
+    return n
+
+
+def mla_topk_num_splits(params) -> int:
+    """fa_mla_topk_num_splits: chunks per row of the launch these params would make, with the workspace as given; host only"""
+    n = lib().fa_mla_topk_num_splits(ctypes.byref(params))
+    if n < 0:
+        check(n)
+    return n
+
+
 def run_mla_indexer_topk(params, stream=None):
-    """fa_run_mla_indexer_topk"""
+    """fa_run_mla_indexer_topk, or fa_run_mla_indexer_topk_v2 for a MlaTopkParamsV2"""
     import torch
 
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    check(lib().fa_run_mla_indexer_topk(ctypes.byref(params), s))
+    check((lib().fa_run_mla_indexer_topk_v2 if isinstance(params, MlaTopkParamsV2) else lib().fa_run_mla_indexer_topk)(ctypes.byref(params), s))
 
 
 def mla_prefill_params(q, k, v, o, lse, cu_seqlens_q=None, cu_seqlens_k=None, causal=False, softmax_scale=None):

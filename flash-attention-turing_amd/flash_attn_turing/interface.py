@@ -895,7 +895,18 @@ def _check_topk(topk):
         raise ValueError(f"topk must be a positive multiple of 32, got {topk!r}")
 
 
-def flash_mla_indexer_topk(logits, cache_seqlens, topk, *, causal=True):
+def _take_splits(fn, name, options):
+    """The one keyword the three selecting calls take through ``**options``: ``name`` (num_splits / topk_splits), default 0.  Their declared parameters are
+    those the calls had before the split kernels (the CPU suite pins that list); any other keyword is the TypeError Python itself would raise."""
+    splits = options.pop(name, 0)
+    if options:
+        raise TypeError(f"{fn}() got an unexpected keyword argument {next(iter(options))!r}")
+    if isinstance(splits, bool) or not isinstance(splits, int) or splits < 0:
+        raise ValueError(f"{name} must be an int >= 0 (0 = chosen by the library), got {splits!r}")
+    return splits
+
+
+def flash_mla_indexer_topk(logits, cache_seqlens, topk, *, causal=True, **options):
     """The ``indices`` of flash_mla_sparse_with_kvcache from index logits: per query token the topk visible key positions with the largest logits.
 
     logits: (batch, seqlen_q, capacity) float32, last dim contiguous, any batch / row strides (what flash_mla_indexer_logits returns, or a view).
@@ -903,7 +914,11 @@ def flash_mla_indexer_topk(logits, cache_seqlens, topk, *, causal=True):
     The selection is exact.  fp32 values are ordered by the integer key u(x) = bits(x) ^ (0xffffffff if the sign bit is set else 0x80000000): -0 < +0,
     and a NaN with the sign bit clear is above +inf.  Row (i, t): if n_t <= topk it is 0, 1, .., n_t - 1 followed by -1; otherwise the topk
     positions below n_t with the largest keys, ties at the threshold going to the lower positions, in ascending position order.  Entries at
-    j >= n_t are never read.  Returns indices (batch, seqlen_q, topk) int32, contiguous.  No host synchronisation; deterministic."""
+    j >= n_t are never read.  Returns indices (batch, seqlen_q, topk) int32, contiguous.  No host synchronisation; deterministic.
+    num_splits (keyword, through ``**options``; default 0): workgroups one logits row is spread over.  0 = the library's rule (more than one only for long rows in a small batch, where one workgroup per
+    row leaves most of the chip idle), 1 = one workgroup per row, n > 1 = n chunks per row (cut to ceil(capacity / 64) and to 64).  The work is integer
+    throughout: the returned tensor is the same in every word whatever num_splits is.  The split path takes a workspace from the caching allocator and
+    runs five launches on the current stream; it stays capturable."""
     if not isinstance(logits, torch.Tensor) or logits.dim() != 3 or logits.dtype != torch.float32:
         raise ValueError("logits must be a float32 tensor (batch, seqlen_q, capacity)")
     if logits.shape[1] < 1:
@@ -916,21 +931,23 @@ def flash_mla_indexer_topk(logits, cache_seqlens, topk, *, causal=True):
     cache_seqlens = _check_indexer_lengths(cache_seqlens, logits.shape[0], logits.device, like="logits")
     if not isinstance(causal, bool):
         raise ValueError(f"causal must be a bool, got {causal!r}")
+    num_splits = _take_splits("flash_mla_indexer_topk", "num_splits", options)
     indices = torch.empty(logits.shape[0], logits.shape[1], topk, dtype=torch.int32, device=logits.device)
-    _C.mla_indexer_topk(logits, cache_seqlens, indices, causal)
+    _C.mla_indexer_topk(logits, cache_seqlens, indices, causal, num_splits)
     return indices
 
 
-def flash_mla_index_with_kvcache(q_idx, weights, k_idx_cache, cache_seqlens, topk, *, k_scale=None, block_table=None, causal=True, return_logits=False):
-    """flash_mla_indexer_logits followed by flash_mla_indexer_topk over a logits buffer allocated here: two launches, the bits of the two calls in
+def flash_mla_index_with_kvcache(q_idx, weights, k_idx_cache, cache_seqlens, topk, *, k_scale=None, block_table=None, causal=True, return_logits=False, **options):
+    """flash_mla_indexer_logits followed by flash_mla_indexer_topk over a logits buffer allocated here: the bits of the two calls in
     sequence.  Returns indices (batch, seqlen_q, topk) int32 - what flash_mla_sparse_with_kvcache takes as it is - and, with ``return_logits``, the
-    logits (batch, seqlen_q, capacity) float32 as well."""
+    logits (batch, seqlen_q, capacity) float32 as well.  ``topk_splits`` (keyword, through ``**options``; default 0) is the ``num_splits`` of flash_mla_indexer_topk (0 = the library's rule)."""
     _check_topk(topk)
+    topk_splits = _take_splits("flash_mla_index_with_kvcache", "topk_splits", options)
     q_idx, cache_seqlens, capacity = _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, block_table, causal)
     logits = torch.empty(q_idx.shape[0], q_idx.shape[1], capacity, dtype=torch.float32, device=q_idx.device)
     _C.mla_indexer_logits(q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale, block_table, causal)
     indices = torch.empty(q_idx.shape[0], q_idx.shape[1], topk, dtype=torch.int32, device=q_idx.device)
-    _C.mla_indexer_topk(logits, cache_seqlens, indices, causal)
+    _C.mla_indexer_topk(logits, cache_seqlens, indices, causal, topk_splits)
     return (indices, logits) if return_logits else indices
 
 
@@ -951,15 +968,17 @@ def flash_mla_indexer_prefill_logits(q_idx, weights, k_idx_cache, cache_seqlens,
     return logits
 
 
-def flash_mla_index_prefill_with_kvcache(q_idx, weights, k_idx_cache, cache_seqlens, topk, *, k_scale=None, block_table=None, causal=True, return_logits=False):
+def flash_mla_index_prefill_with_kvcache(q_idx, weights, k_idx_cache, cache_seqlens, topk, *, k_scale=None, block_table=None, causal=True, return_logits=False, **options):
     """flash_mla_index_with_kvcache for a prompt chunk: flash_mla_indexer_prefill_logits followed by flash_mla_indexer_topk over a logits buffer allocated
-    here.  Two launches; the indices (and logits) of flash_mla_index_with_kvcache, entry for entry."""
+    here.  The indices (and logits) of flash_mla_index_with_kvcache, entry for entry.  ``topk_splits`` as there; a prompt chunk has many rows, so the
+    library's rule keeps one workgroup per row."""
     _check_topk(topk)
+    topk_splits = _take_splits("flash_mla_index_prefill_with_kvcache", "topk_splits", options)
     q_idx, cache_seqlens, capacity = _check_indexer_inputs(q_idx, weights, k_idx_cache, cache_seqlens, k_scale, block_table, causal)
     logits = torch.empty(q_idx.shape[0], q_idx.shape[1], capacity, dtype=torch.float32, device=q_idx.device)
     _C.mla_indexer_prefill_logits(q_idx, weights, k_idx_cache, cache_seqlens, logits, k_scale, block_table, causal)
     indices = torch.empty(q_idx.shape[0], q_idx.shape[1], topk, dtype=torch.int32, device=q_idx.device)
-    _C.mla_indexer_topk(logits, cache_seqlens, indices, causal)
+    _C.mla_indexer_topk(logits, cache_seqlens, indices, causal, topk_splits)
     return (indices, logits) if return_logits else indices
 
 

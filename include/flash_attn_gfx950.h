@@ -946,6 +946,44 @@ typedef struct fa_mla_indexer_params_v2 {
     int32_t reserved2_;         /* 0 */
 } fa_mla_indexer_params_v2;
 
+/* One logits row over several workgroups in the top-k selection (FA_HAS_MLA_TOPK_SPLIT).  fa_run_mla_indexer_topk gives each (sequence, token) row one
+ * workgroup, which leaves most of the chip idle in long-context, small-batch decode.  fa_mla_topk_params_v2 is fa_mla_topk_params with a workspace and
+ * num_splits appended; it goes to entry points of its own: fa_run_mla_indexer_topk_v2 takes either struct through its pointer and tells them apart by
+ * struct_size (any other size is FA_ERR_BAD_ABI), fa_mla_topk_workspace_bytes and fa_mla_topk_num_splits are host-only queries with the checks of the launch
+ * (negative = its error code).  fa_run_mla_indexer_topk keeps taking the 72-byte struct alone and keeps launching the one-workgroup kernel.  FA_ABI_VERSION is
+ * unchanged.
+ * num_splits: 0 = the library's rule (a host function of b * seqlen_q, seqlen_cache, topk and the compute-unit count; 1 wherever one workgroup per row already
+ * fills the chip, for short rows and for seqlen_cache <= topk), 1 = the one-workgroup kernel, n > 1 = n chunks per row, cut to ceil(seqlen_cache / 64) and to
+ * 64.  A row's positions [0, n_t) are cut on the device into that many contiguous chunks in multiples of 64; the launches are a clearing kernel, three digit
+ * histograms that add into the workspace with integer atomics, and an emit: ordering is stream order alone, nothing waits on another workgroup, the call is
+ * capturable and synchronises nothing.  The contract is that of fa_mla_topk_params word for word, and the work is integer throughout: for every input and every
+ * num_splits the indices buffer equals that of num_splits = 1 in every word.
+ * workspace: device memory, 16-byte aligned, of fa_mla_topk_workspace_bytes(params) bytes (the size for params->num_splits; 0 when that resolves to 1).  Its
+ * contents on entry do not matter and it may be reused by the next call on the stream.  NULL / 0 bytes means 1 split, whatever num_splits says.  With
+ * num_splits = 0 a workspace too small for the rule's count gives the largest count that fits.
+ * Errors beyond those of fa_mla_topk_params: a negative num_splits FA_ERR_BAD_SHAPE naming num_splits; a non-zero reserved2_ FA_ERR_BAD_SHAPE naming it; a
+ * non-NULL workspace too small for a forced count FA_ERR_BAD_SHAPE naming workspace_bytes; a misaligned workspace FA_ERR_BAD_STRIDE. */
+#define FA_HAS_MLA_TOPK_SPLIT 1
+typedef struct fa_mla_topk_params_v2 {
+    uint32_t struct_size;       /* sizeof(fa_mla_topk_params_v2) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const float* logits;
+    int32_t* indices;
+    const int32_t* cache_seqlens;
+    int32_t b;
+    int32_t seqlen_q;
+    int32_t seqlen_cache;
+    int32_t topk;               /* a positive multiple of 32 */
+    int32_t is_causal;
+    int32_t reserved_;          /* 0 */
+    int64_t logits_batch_stride;
+    int64_t logits_row_stride;
+    void* workspace;            /* NULL = 1 split */
+    int64_t workspace_bytes;
+    int32_t num_splits;         /* 0 = the library's rule, 1 = one workgroup per row, n > 1 = n chunks per row */
+    int32_t reserved2_;         /* 0 */
+} fa_mla_topk_params_v2;
+
 /* MLA prefill attention (FA_HAS_MLA_PREFILL; DeepSeek-V2 / V3 / R1, Kimi K2 before weight absorption; the (192, 128) forward of flash-attn and FlashMLA).
  * Ordinary multi-head attention with d_qk = 192 wide queries and keys (128 no-rope columns, then 64 rope columns, RoPE already applied) and d_v = 128
  * wide values.  FA_ABI_VERSION is unchanged; the presence of fa_run_mla_prefill_fwd is how a caller detects the feature.  struct_size must be
@@ -1359,6 +1397,12 @@ int fa_mla_indexer_prefill_launch(const fa_mla_indexer_params* params, int32_t* 
 int fa_run_mla_indexer_logits_v2(const fa_mla_indexer_params_v2* params, void* stream);
 int fa_run_mla_indexer_prefill_logits_v2(const fa_mla_indexer_params_v2* params, void* stream);
 int fa_mla_indexer_prefill_launch_v2(const fa_mla_indexer_params_v2* params, int32_t* tokens_per_wg, int32_t* wg_keys, int32_t* n_chunks);
+/* The selection with one row over several workgroups (FA_HAS_MLA_TOPK_SPLIT): takes a fa_mla_topk_params_v2 or (cast to it) a fa_mla_topk_params, told apart
+ * by struct_size; the 72-byte struct, a NULL workspace or num_splits = 1 is fa_run_mla_indexer_topk.  The two queries are host-only: the bytes the workspace
+ * needs for params->num_splits (the `workspace` fields are ignored), and the chunks per row the launch would use with the workspace as given. */
+int fa_run_mla_indexer_topk_v2(const fa_mla_topk_params_v2* params, void* stream);
+int64_t fa_mla_topk_workspace_bytes(const fa_mla_topk_params_v2* params);
+int32_t fa_mla_topk_num_splits(const fa_mla_topk_params_v2* params);
 
 /* ---- MLA prefill attention (fa_mla_prefill_params above) -------------------------------------- */
 /* One launch on `stream`, no workspace, no host synchronisation: cu_seqlens are read on the device. */

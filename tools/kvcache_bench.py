@@ -92,6 +92,10 @@ heads, seqlen_q 1, topk 2048, pages of 64 (--paged P replaces the page size), b 
 interleaved in one process: the logits call; the torch formulation of the logits (dequantise, einsum, relu, weighted sum, * k_scale; it reads the pool
 as a contiguous cache, i.e. without the gather a paged cache would cost it) timed TWICE as its own noise figure; the selection; torch.topk on the same
 logits.  The logits call is also stated against b * L * 132 B / time as a fraction of 6.3 TB/s.  Caches rotate over 256 MiB (profiles/kvcache_mla_indexer_bench.log).
+--mla-indexer --topk-splits LIST measures flash_mla_indexer_topk alone on N(0, 1) logits, topk 2048, (b, seqlen_q) in {(1, 1), (8, 1), (64, 1), (1, 2), (1, 4)} x
+L in {4k, 32k, 128k}: num_splits at each listed count and at 0 (the library's rule, whose choice is printed), num_splits = 1 timed TWICE (the one-workgroup kernel:
+the yardstick and its noise) and torch.topk, interleaved, medians of --rounds; the indices are asserted equal to those of num_splits = 1 before anything is
+timed.  Logits buffers rotate over 256 MiB, at most 512 of them (profiles/mla_topk_split_bench.log).
 
 --mla-prefill-bwd measures the MLA prefill backward (flash_mla_prefill_bwd) on the grid of --mla-prefill: both launches, the dQ launch and the dK/dV launch
 alone, against (a) bwd at head_dim 128 on the same b, s, h (640 / 832 of the FLOPs per pair) and (b) autograd's backward of the torch formulation in bf16 where
@@ -1105,6 +1109,33 @@ def run_mla_indexer(lengths, pages, rounds):
         yield run_mla_indexer_point(b, L, (pages or [64])[0], rounds)
 
 
+def run_mla_topk_split_point(b, sq, L, splits, rounds, topk=2048):
+    """--mla-indexer --topk-splits: the selection at each listed count and at 0 (the library's rule), num_splits = 1 timed twice (the one-workgroup kernel: the
+    yardstick and its noise) and torch.topk, interleaved; N(0, 1) logits rotated over the working set (at most 512 buffers); the indices asserted equal first"""
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(b * 1000003 + sq * 10007 + L)
+    n = _rotation(b * sq * L * 4, b * sq * L * 4)
+    logits = torch.randn(n, b, sq, L, device=dev, generator=gen)
+    cs = torch.full((b,), L, dtype=torch.int32, device=dev)
+    sel = lambda s: (lambda i: F.flash_mla_indexer_topk(logits[i % n], cs, topk, causal=True, num_splits=s))
+    want = sel(1)(0)
+    for s in (0, *splits):
+        assert torch.equal(sel(s)(0), want), f"num_splits = {s}: the indices differ from num_splits = 1"
+    # what the rule chose: the query, over a workspace of the size the query before it asked for
+    p = capi.mla_topk_params_v2(logits[0], want, cs, causal=True, num_splits=0)
+    ws = torch.empty(max(capi.mla_topk_workspace_bytes(p), 16), dtype=torch.uint8, device=dev)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+    arms = {"one": sel(1), "one_again": sel(1), "auto": sel(0), **{f"s{s}": sel(s) for s in splits}, "torch_topk": lambda i: torch.topk(logits[i % n], topk, dim=-1).indices}
+    ms = _interleaved(arms, n, rounds)
+    return dict(mla_topk_split=True, b=b, seqlen_q=sq, L=L, topk=topk, buffers_rotated=n, auto_num_splits=capi.mla_topk_num_splits(p), us={k: round(v * 1e3, 2) for k, v in ms.items()},
+                noise=round(ms["one_again"] / ms["one"], 3), **{f"{k}_over_one": round(v / min(ms["one"], ms["one_again"]), 3) for k, v in ms.items() if k not in ("one", "one_again")})
+
+
+def run_mla_topk_split(lengths, splits, rounds):
+    for (b, sq), L in itertools.product(((1, 1), (8, 1), (64, 1), (1, 2), (1, 4)), tuple(lengths or (4096, 32768, 131072))):
+        yield run_mla_topk_split_point(b, sq, L, splits, rounds)
+
+
 def run_mla_indexer_prefill_point(sq, L, page, rounds, topk=2048, h=64):
     """the prefill logits call against the decode logits call (timed twice: its own scatter) on one prompt chunk, and the selection launch; interleaved, bits asserted first"""
     dev = torch.device("cuda:0")
@@ -1625,6 +1656,8 @@ def main():
     ap.add_argument("--mla-indexer", action="store_true", help="the DeepSeek-V3.2 indexer (flash_mla_indexer_logits / flash_mla_indexer_topk; bf16, FP8 keys with scales, 64 heads, "
                                                                "topk 2048, pages of 64 or --paged P): the logits call against its HBM bound and the torch formulation (timed twice), the "
                                                                "selection against torch.topk")
+    ap.add_argument("--topk-splits", metavar="LIST", help="with --mla-indexer, e.g. 2,4,8,16,32,64: flash_mla_indexer_topk at each of these num_splits and at 0 against num_splits = 1 "
+                                                          "(timed twice) and torch.topk; b in {1, 8, 64} and b 1 with seqlen_q in {2, 4}, L in {4k, 32k, 128k}, topk 2048")
     ap.add_argument("--mla-indexer-prefill", action="store_true", help="flash_mla_indexer_prefill_logits against flash_mla_indexer_logits (timed twice) on one prompt chunk, and "
                                                                        "the selection launch: bf16, FP8 keys with scales, 64 heads, pages of 64, causal, b 1, sq in {128, 512, "
                                                                        "2048} x L in {4k, 32k, 128k}; bits asserted equal before timing")
@@ -1674,6 +1707,10 @@ def main():
             return
         if a.mla_indexer_prefill:
             for line in run_mla_indexer_prefill(a.length, a.paged, a.rounds):
+                print(json.dumps(line), flush=True)
+            return
+        if a.mla_indexer and a.topk_splits:
+            for line in run_mla_topk_split(a.length, [int(x) for x in a.topk_splits.split(",")], a.rounds):
                 print(json.dumps(line), flush=True)
             return
         if a.mla_indexer:
