@@ -14,6 +14,7 @@
 #include "fa_merge_states.hpp"
 #include "fa_mla_cache_io.hpp"
 #include "fa_mla_index_prepare.hpp"
+#include "fa_fwd_fp8.hpp"
 #include "flash_attn_gfx950.h"
 
 namespace {
@@ -47,12 +48,13 @@ int check_tensor(const char* name, const void* ptr, const fa_strides& st, int64_
 }
 
 // The same for an 8-bit (e4m3) cache, strides in 1-byte elements: the kernels keep 16-byte loads, so everything is a multiple of 16 elements.
-int check_cache8(const char* name, const void* ptr, const fa_strides& st, int64_t rows, int d) {
+// kind: what the tensor is, in the refusal's words; varlen: a packed tensor, whose batch stride is not read (the FP8 forward's q / k / v)
+int check_cache8(const char* name, const void* ptr, const fa_strides& st, int64_t rows, int d, const char* kind = "8-bit cache", bool varlen = false) {
     if (ptr == nullptr) return fail(FA_ERR_NULL_POINTER, "%s is NULL", name);
     if (((uintptr_t)ptr & 15) != 0) return fail(FA_ERR_BAD_STRIDE, "%s base pointer must be 16-byte aligned", name);
-    if (st.row < d || st.head < 0 || (st.row % 16) != 0 || (st.head % 16) != 0 || (st.batch % 16) != 0)
-        return fail(FA_ERR_BAD_STRIDE, "%s (8-bit cache) strides (batch=%lld,row=%lld,head=%lld) must be multiples of 16 elements (16-byte loads) with row >= head_dim",
-                    name, (long long)st.batch, (long long)st.row, (long long)st.head);
+    if (st.row < d || st.head < 0 || (st.row % 16) != 0 || (st.head % 16) != 0 || (!varlen && (st.batch % 16) != 0))
+        return fail(FA_ERR_BAD_STRIDE, "%s (%s) strides (batch=%lld,row=%lld,head=%lld) must be multiples of 16 elements (16-byte loads) with row >= head_dim",
+                    name, kind, (long long)st.batch, (long long)st.row, (long long)st.head);
     if (rows * st.row >= ((int64_t)1 << 31))
         return fail(FA_ERR_BAD_STRIDE, "%s: one sequence spans %lld bytes (limit 2^31)", name, (long long)(rows * st.row));
     return FA_OK;
@@ -264,20 +266,31 @@ int32_t mla_split(const fa::KvcacheKernelParams& kp, const P& local, bool sized)
 // ---- what the MLA prefill forward and backward share
 // What fa_mla_prefill_params and fa_mla_prefill_bwd_params (P) check alike and first: sizes, GQA, widths, dtype, cu_seqlens, softmax_scale, the packed totals.
 // Behind it a call is packed iff cu_seqlens_q is given.
+// (the sizes and the GQA rule: fa_fp8_fwd_params states them alike)
 template <typename P>
-int check_mla_prefill_front(const P& p) {
+int check_prefill_sizes(const P& p) {
     if (p.b < 0 || p.seqlen_q < 0 || p.seqlen_k < 0 || p.h <= 0 || p.h_k <= 0)
         return fail(FA_ERR_BAD_SHAPE, "bad sizes b=%d seqlen_q=%d seqlen_k=%d h=%d h_k=%d", p.b, p.seqlen_q, p.seqlen_k, p.h, p.h_k);
     if (p.h % p.h_k != 0) return fail(FA_ERR_BAD_GQA, "h (%d) must be divisible by h_k (%d) for GQA/MQA", p.h, p.h_k);
+    return FA_OK;
+}
+// the packed totals, behind the other value checks
+template <typename P>
+int check_prefill_totals(const P& p) {
+    if (p.cu_seqlens_q != nullptr && (p.total_q < 0 || p.total_k < 0))
+        return fail(FA_ERR_BAD_SHAPE, "total_q (%lld) / total_k (%lld) must be >= 0 with cu_seqlens", (long long)p.total_q, (long long)p.total_k);
+    return FA_OK;
+}
+template <typename P>
+int check_mla_prefill_front(const P& p) {
+    if (int rc0 = check_prefill_sizes(p)) return rc0;
     if (p.d_qk != 192) return fail(FA_ERR_BAD_HEADDIM, "d_qk %d unsupported (q and k are 192 wide: 128 no-rope + 64 rope elements)", p.d_qk);
     if (p.d_v != 128) return fail(FA_ERR_BAD_HEADDIM, "d_v %d unsupported (v and o are 128 wide)", p.d_v);
     int rc;
     if ((rc = check_dtype(p.dtype))) return rc;
     if ((rc = check_cu_seqlens(p.cu_seqlens_q, p.cu_seqlens_k, true))) return rc;
     if ((rc = check_softmax_scale(p.softmax_scale, "192 ** -0.5"))) return rc;
-    if (p.cu_seqlens_q != nullptr && (p.total_q < 0 || p.total_k < 0))
-        return fail(FA_ERR_BAD_SHAPE, "total_q (%lld) / total_k (%lld) must be >= 0 with cu_seqlens", (long long)p.total_q, (long long)p.total_k);
-    return FA_OK;
+    return check_prefill_totals(p);
 }
 
 // The launch grids: h_k x tiles (dense: per batch entry; packed: of all rows, plus one slot per sequence), counted in tiles of 64 - the smaller of the two row
@@ -1437,6 +1450,51 @@ int fa_run_mla_prefill_bwd(const fa_mla_prefill_bwd_params* user, void* stream) 
     kp.dout = conv(p->dout_stride); kp.dq = conv(p->dq_stride); kp.dk = conv(p->dk_stride); kp.dv = conv(p->dv_stride);
     // (with query rows but no key anywhere the dQ launch still runs: every row is dead and is written as zeros)
     return hip_status(fa::launch_bwd_mla_prefill(kp, p->dtype, p->phases ? p->phases : 3, (hipStream_t)stream), "fa_bwd_mla_prefill launch");
+}
+
+// ---- FP8 dense attention forward --------------------------------------------------------------------------------------------------------------
+// fa_fp8_fwd_params -> Fp8FwdParams, validated: the order and the words of fa_run_mla_prefill_fwd wherever the mistake is the same.  q / k / v are 8-bit tensors
+// (strides in bytes, the rule of an 8-bit cache), o a 16-bit one.
+int fa_run_fp8_fwd(const fa_fp8_fwd_params* user, void* stream) {
+    fa_fp8_fwd_params local;
+    int rc = import_exact(user, local, "fa_fp8_fwd_params");
+    if (rc) return rc;
+    const fa_fp8_fwd_params* p = &local;
+    if ((rc = check_prefill_sizes(*p))) return rc;
+    if (p->d != 128) return fail(FA_ERR_BAD_HEADDIM, "d %d unsupported (q, k, v and o are 128 wide)", p->d);
+    if (p->out_dtype != FA_FP16 && p->out_dtype != FA_BF16) return fail(FA_ERR_BAD_DTYPE, "out_dtype %d unsupported (0=fp16, 1=bf16)", p->out_dtype);
+    if ((rc = check_cu_seqlens(p->cu_seqlens_q, p->cu_seqlens_k, true))) return rc;
+    if ((rc = check_softmax_scale(p->softmax_scale, "128 ** -0.5"))) return rc;
+    if ((rc = check_prefill_totals(*p))) return rc;
+    if ((rc = check_reserved(p->reserved_, "fa_fp8_fwd_params", FA_ERR_BAD_SHAPE))) return rc;
+    if ((rc = check_mla_prefill_grid(*p, false))) return rc;
+    const bool packed = p->cu_seqlens_q != nullptr;
+    const int64_t rows_q = packed ? p->total_q : p->seqlen_q, rows_k = packed ? p->total_k : p->seqlen_k;
+    if (p->b == 0 || rows_q == 0) return FA_OK;     // nothing to write
+    if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
+    if (((reinterpret_cast<uintptr_t>(p->q_descale) | reinterpret_cast<uintptr_t>(p->k_descale) | reinterpret_cast<uintptr_t>(p->v_descale)) & 3u) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "q_descale / k_descale / v_descale must be 4-byte aligned");
+    if ((rc = check_cache8("q", p->q, p->q_stride, rows_q, p->d, "e4m3", packed))) return rc;
+    if ((rc = check_tensor("o", p->o, p->o_stride, rows_q, p->d, packed))) return rc;
+    if (rows_k > 0) {
+        if ((rc = check_cache8("k", p->k, p->k_stride, rows_k, p->d, "e4m3", packed))) return rc;
+        if ((rc = check_cache8("v", p->v, p->v_stride, rows_k, p->d, "e4m3", packed))) return rc;
+    }
+    fa::Fp8FwdParams kp;
+    memset(&kp, 0, sizeof(kp));
+    kp.q_ptr = p->q; kp.k_ptr = p->k; kp.v_ptr = p->v; kp.o_ptr = p->o; kp.lse_ptr = p->lse;
+    kp.qd_ptr = p->q_descale; kp.kd_ptr = p->k_descale; kp.vd_ptr = p->v_descale;
+    kp.qd_batch = p->q_descale_batch_stride; kp.qd_head = p->q_descale_head_stride;
+    kp.kd_batch = p->k_descale_batch_stride; kp.kd_head = p->k_descale_head_stride;
+    kp.vd_batch = p->v_descale_batch_stride; kp.vd_head = p->v_descale_head_stride;
+    kp.cu_q = p->cu_seqlens_q; kp.cu_k = p->cu_seqlens_k;
+    kp.q = conv(p->q_stride); kp.k = conv(p->k_stride); kp.v = conv(p->v_stride); kp.o = conv(p->o_stride);
+    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_k = p->seqlen_k;
+    kp.h = p->h; kp.h_k = p->h_k; kp.h_ratio = p->h / p->h_k;
+    kp.is_causal = p->is_causal ? 1 : 0;
+    kp.total_q = packed ? p->total_q : 0; kp.total_k = packed ? p->total_k : 0;
+    kp.scale = p->softmax_scale > 0.f ? p->softmax_scale : 1.0f / sqrtf((float)p->d);       // (the default = 128 ** -0.5 rounded once to fp32)
+    return hip_status(fa::launch_fwd_fp8(kp, p->out_dtype, (hipStream_t)stream), "fa_fwd_fp8 launch");
 }
 
 // ---- merging attention states ----------------------------------------------------------------------------------------------------------------

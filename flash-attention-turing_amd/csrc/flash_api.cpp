@@ -652,6 +652,55 @@ std::vector<at::Tensor> mha_fwd_mla_prefill(at::Tensor q, at::Tensor k, at::Tens
     return {o, l};
 }
 
+// FP8 attention forward (fa_run_fp8_fwd): q / k / v float8_e4m3fn, dense (b, rows, heads, 128) or packed (rows, heads, 128) with both cu_seqlens; the
+// descales fp32 (b, h) / (b, h_k) with any strides, None = 1.0 -> out (fp16 / bf16) shaped like q, lse (b, h, sq) or (h, total_q).  Nothing is copied: the
+// tensors go to the library with the strides they have, and a view it cannot address is its error.
+std::vector<at::Tensor> mha_fwd_fp8(at::Tensor q, at::Tensor k, at::Tensor v, c10::optional<at::Tensor> q_descale_, c10::optional<at::Tensor> k_descale_,
+                                    c10::optional<at::Tensor> v_descale_, c10::optional<at::Tensor> cu_seqlens_q_, c10::optional<at::Tensor> cu_seqlens_k_,
+                                    bool is_causal, c10::optional<double> softmax_scale, bool out_bf16) {
+    const bool packed = cu_seqlens_q_.has_value() || cu_seqlens_k_.has_value();
+    TORCH_CHECK(cu_seqlens_q_.has_value() == cu_seqlens_k_.has_value(), "cu_seqlens_q and cu_seqlens_k come both or neither");
+    const int64_t rank = packed ? 3 : 4;
+    TORCH_CHECK(q.dim() == rank && k.dim() == rank && v.dim() == rank, "q, k, v must be rank-", rank, " tensors");
+    TORCH_CHECK(q.is_cuda() && k.is_cuda() && v.is_cuda(), "q, k, v must be GPU (HIP) tensors");
+    TORCH_CHECK(k.device() == q.device() && v.device() == q.device(), "q, k, v must be on the same device");
+    TORCH_CHECK(q.scalar_type() == at::kFloat8_e4m3fn && k.scalar_type() == at::kFloat8_e4m3fn && v.scalar_type() == at::kFloat8_e4m3fn, "q, k, v must be float8_e4m3fn");
+    const MlaPrefillShape s = check_mla_prefill_shapes(q, k, v, packed, cu_seqlens_q_);
+    TORCH_CHECK(v.size(-1) == q.size(-1), "q / v head_dim must match");
+    check_mla_prefill_cu(q, packed, cu_seqlens_q_, cu_seqlens_k_);
+    c10::DeviceGuard guard(q.device());
+    const auto out_opts = q.options().dtype(out_bf16 ? torch::kBFloat16 : torch::kFloat16);
+    // dense: every element of o and l is written (dead rows included); packed: the rows past cu_seqlens_q[-1] are not touched
+    at::Tensor o = packed ? torch::empty({s.rows_q, s.num_heads, v.size(-1)}, out_opts) : torch::empty({s.batch_size, s.rows_q, s.num_heads, v.size(-1)}, out_opts);
+    at::Tensor l = packed ? torch::empty({s.num_heads, s.rows_q}, q.options().dtype(torch::kFloat32))
+                          : torch::empty({s.batch_size, s.num_heads, s.rows_q}, q.options().dtype(torch::kFloat32));
+
+    fa_fp8_fwd_params p;
+    FA_PARAMS_INIT(p);
+    p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = o.data_ptr(); p.lse = l.data_ptr<float>();
+    p.b = (int32_t)s.batch_size; p.h = (int32_t)s.num_heads; p.h_k = (int32_t)s.num_heads_k; p.d = (int32_t)q.size(-1);
+    p.out_dtype = out_bf16 ? FA_BF16 : FA_FP16; p.is_causal = is_causal;
+    p.softmax_scale = softmax_scale_fp32(softmax_scale, "128 ** -0.5");
+    if (packed) {
+        p.cu_seqlens_q = cu_seqlens_q_->data_ptr<int32_t>(); p.cu_seqlens_k = cu_seqlens_k_->data_ptr<int32_t>();
+        p.total_q = s.rows_q; p.total_k = s.rows_k;
+    } else {
+        p.seqlen_q = (int32_t)s.rows_q; p.seqlen_k = (int32_t)s.rows_k;
+    }
+    p.q_stride = strides34(q); p.k_stride = strides34(k); p.v_stride = strides34(v); p.o_stride = strides34(o);
+    auto descale = [&](const c10::optional<at::Tensor>& t, const char* name, int64_t heads, const float*& ptr, int64_t& sb, int64_t& sh) {
+        if (!t.has_value()) return;
+        check_same_device(q, *t, name);
+        TORCH_CHECK(t->scalar_type() == torch::kFloat32 && t->dim() == 2 && t->size(0) == s.batch_size && t->size(1) == heads, name, " must be fp32 (batch, heads)");
+        ptr = t->data_ptr<float>(); sb = t->stride(0); sh = t->stride(1);
+    };
+    descale(q_descale_, "q_descale", s.num_heads, p.q_descale, p.q_descale_batch_stride, p.q_descale_head_stride);
+    descale(k_descale_, "k_descale", s.num_heads_k, p.k_descale, p.k_descale_batch_stride, p.k_descale_head_stride);
+    descale(v_descale_, "v_descale", s.num_heads_k, p.v_descale, p.v_descale_batch_stride, p.v_descale_head_stride);
+    check_status(fa_run_fp8_fwd(&p, current_stream(q)));
+    return {o, l};
+}
+
 // Merging attention states (fa_run_merge_states): dense outs[i] (b, rows, h, d_v) / lses[i] (b, h, rows) -> [out (b, rows, h, d_v), lse (b, h, rows)]; packed
 // outs[i] (total, h, d_v) / lses[i] (h, total) -> [out (total, h, d_v), lse (h, total)].  Nothing is copied: every part goes to the library with the strides it
 // has (an LSE with any strides at all), and a view it cannot address is its error.
@@ -1034,6 +1083,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "MLA prefill attention: q (b, sq, h, 192), k (b, sk, h_k, 192), v (b, sk, h_k, 128) -> [out (b, sq, h, 128), lse]; packed with both cu_seqlens",
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens_q") = py::none(), py::arg("cu_seqlens_k") = py::none(), py::arg("is_causal") = false,
           py::arg("softmax_scale") = py::none());
+    m.def("fwd_fp8", &mha_fwd_fp8,
+          "FP8 (e4m3) attention forward: q (b, sq, h, 128), k / v (b, sk, h_k, 128) float8_e4m3fn with fp32 descales -> [out (b, sq, h, 128) fp16 / bf16, lse]; packed with both cu_seqlens",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("q_descale") = py::none(), py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none(),
+          py::arg("cu_seqlens_q") = py::none(), py::arg("cu_seqlens_k") = py::none(), py::arg("is_causal") = false, py::arg("softmax_scale") = py::none(),
+          py::arg("out_bf16") = true);
     m.def("bwd_mla_prefill", &mha_bwd_mla_prefill,
           "MLA prefill backward: dout, q, k, v, out, lse -> [dq, dk, dv, dsoftmax_sum]; packed with both cu_seqlens",
           py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("cu_seqlens_q") = py::none(),

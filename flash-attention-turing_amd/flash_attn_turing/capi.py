@@ -205,6 +205,19 @@ class MlaPrefillBwdParams(_Params):
                 ("total_q", ctypes.c_int64), ("total_k", ctypes.c_int64)]
 
 
+class Fp8FwdParams(_Params):
+    """fa_fp8_fwd_params: the FP8 (e4m3) dense attention forward, head_dim 128, dense or packed (fa_run_fp8_fwd)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("q", _vp), ("k", _vp), ("v", _vp), ("o", _vp), ("lse", _vp),
+                ("q_descale", _vp), ("k_descale", _vp), ("v_descale", _vp), ("cu_seqlens_q", _vp), ("cu_seqlens_k", _vp),
+                ("b", _i32), ("seqlen_q", _i32), ("seqlen_k", _i32), ("h", _i32), ("h_k", _i32), ("d", _i32), ("out_dtype", _i32), ("is_causal", _i32),
+                ("softmax_scale", ctypes.c_float), ("reserved_", _i32),
+                ("q_stride", Strides), ("k_stride", Strides), ("v_stride", Strides), ("o_stride", Strides),
+                ("q_descale_batch_stride", ctypes.c_int64), ("q_descale_head_stride", ctypes.c_int64),
+                ("k_descale_batch_stride", ctypes.c_int64), ("k_descale_head_stride", ctypes.c_int64),
+                ("v_descale_batch_stride", ctypes.c_int64), ("v_descale_head_stride", ctypes.c_int64),
+                ("total_q", ctypes.c_int64), ("total_k", ctypes.c_int64)]
+
+
 FA_MERGE_MAX_PARTS = 8
 
 
@@ -356,6 +369,8 @@ def lib():
         L.fa_run_mla_prefill_fwd.restype = ctypes.c_int
         L.fa_run_mla_prefill_bwd.argtypes = [ctypes.POINTER(MlaPrefillBwdParams), _vp]
         L.fa_run_mla_prefill_bwd.restype = ctypes.c_int
+        L.fa_run_fp8_fwd.argtypes = [ctypes.POINTER(Fp8FwdParams), _vp]
+        L.fa_run_fp8_fwd.restype = ctypes.c_int
         L.fa_run_merge_states.argtypes = [ctypes.POINTER(MergeParams)]
         L.fa_run_merge_states.restype = ctypes.c_int
         L.fa_run_mla_cache_append.argtypes = [ctypes.POINTER(MlaCacheAppendParams), _vp]

@@ -1029,6 +1029,85 @@ def flash_mla_prefill_func(q, k, v, *, cu_seqlens_q=None, cu_seqlens_k=None, sof
     return (out, lse) if return_softmax_lse else out
 
 
+def flash_attn_fp8_func(q, k, v, *, q_descale=None, k_descale=None, v_descale=None, cu_seqlens_q=None, cu_seqlens_k=None, softmax_scale=None, causal=False,
+                        out_dtype=torch.bfloat16, return_softmax_lse=False):
+    """Dense attention forward over FP8 (OCP e4m3, ``torch.float8_e4m3fn``) q, k and v: head_dim 128, both matrix products on the FP8 matrix instruction.
+
+    dense:  q (batch, seqlen_q, nheads, 128), k / v (batch, seqlen_k, nheads_k, 128) -> out (batch, seqlen_q, nheads, 128) of ``out_dtype`` (bf16 or fp16)
+            and, with ``return_softmax_lse``, lse (batch, nheads, seqlen_q) fp32 (natural log).
+    packed: q (total_q, nheads, 128), k / v (total_k, nheads_k, 128) with cu_seqlens_q / cu_seqlens_k, int32 (batch + 1,) on q's device, given both or
+            neither -> out (total_q, nheads, 128), lse (nheads, total_q).  The launch is sized from total_q; rows at or past cu_seqlens_q[-1] are not written.
+    nheads % nheads_k == 0 (GQA / MQA).  The last dimension is contiguous, every other stride and the storage offset are multiples of 16 bytes; other views
+    are refused, never copied.  One sequence (packed: the whole tensor) spans less than 2^31 bytes.
+    q_descale (batch, nheads), k_descale / v_descale (batch, nheads_k): fp32 tensors on q's device with any strides (an expanded scalar is fine), None = 1.0,
+    read on the device.  The dequantised operands are ``float(code) * descale``; the caller quantises.  Precondition, not checked: finite and positive.
+
+    In fp32 math over the visible keys: ``s_tj = (q_t . k_j) * (softmax_scale * q_descale * k_descale)`` with the code products accumulated in fp32; key j is
+    visible to row t iff j < sk_i and, under ``causal``, j <= sk_i - sq_i + t (bottom-right aligned).  With the running maximum m, ``p = exp(s - m)`` in fp32;
+    the denominator l sums the fp32 p; the second product takes ``e4m3_rne(256 * p)`` (256 is exact to undo and moves e4m3's flush-to-zero point from
+    p < 2^-10 to p < 2^-18) and accumulates in fp32; ``out = O / (256 * l) * v_descale`` rounded once to ``out_dtype``.  LSE carries no quantisation error
+    beyond the inputs'.  A row that sees no key is O = 0, LSE = 0; empty sequences are allowed.  A NaN code in a query row, or a NaN score of a visible key,
+    makes that row's O and LSE NaN.  Non-finite V has no contract (0 x NaN across the rows of a tile).
+    softmax_scale: None = 128 ** -0.5 rounded once to fp32; validated like softmax_scale of flash_mla_prefill_func.
+
+    No key split, no workspace, no host synchronisation: graph-capturable and deterministic.  Bit for bit: sequence i of a packed call equals the dense
+    call on it alone, a batch entry of a dense call equals the call on it alone, a row with exactly one visible key returns ``float(v_code) * v_descale``
+    rounded once, and a power of two moved between k_descale and softmax_scale changes nothing.
+    Out of scope, and without a keyword here: head_dim 64 / 256, a backward, window, softcap, sinks, paged or cached K / V, FP8 output, per-token or
+    per-block scales, a key split, a quantiser.  Wrong shapes, dtypes, views or values are a ValueError that names the argument.
+    """
+    packed = cu_seqlens_q is not None or cu_seqlens_k is not None
+    if packed and (cu_seqlens_q is None or cu_seqlens_k is None):
+        raise ValueError("cu_seqlens_q and cu_seqlens_k come both or neither, got only " + ("cu_seqlens_q" if cu_seqlens_k is None else "cu_seqlens_k"))
+    rank = 3 if packed else 4
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != rank:
+            raise ValueError(f"{name} must be a rank-{rank} tensor ({'(total, nheads, head_dim) with cu_seqlens' if packed else '(batch, seqlen, nheads, head_dim)'})")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        bad = next(n for n, t in (("q", q), ("k", k), ("v", v)) if t.requires_grad)
+        raise ValueError(f"{bad} requires grad: flash_attn_fp8_func is forward-only; run it under torch.no_grad() or detach the inputs")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.dtype != torch.float8_e4m3fn:
+            raise ValueError(f"{name} must be torch.float8_e4m3fn (OCP e4m3), got {t.dtype}")
+        if t.device != q.device:
+            raise ValueError(f"{name} must be on q's device ({q.device}), got {t.device}")
+        if t.shape[-1] != 128:
+            raise ValueError(f"{name} must be 128 wide, got head_dim {t.shape[-1]}")
+    if k.shape != v.shape:
+        raise ValueError(f"k and v must have one shape, got {tuple(k.shape)} and {tuple(v.shape)}")
+    if not packed and k.shape[0] != q.shape[0]:
+        raise ValueError(f"k / v batch ({k.shape[0]}) must match q's ({q.shape[0]})")
+    h, h_k = q.shape[-2], k.shape[-2]
+    if h < 1 or h_k < 1 or h % h_k != 0:
+        raise ValueError(f"nheads of q ({h}) must be a positive multiple of nheads_k of k / v ({h_k})")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if t.stride(-1) != 1:
+            raise ValueError(f"{name}: the last dimension must be contiguous, got strides {tuple(t.stride())}")
+        if any(s % 16 != 0 for s in t.stride()[:-1]) or t.storage_offset() % 16 != 0:
+            raise ValueError(f"{name}: strides {tuple(t.stride())} (but the last) and the storage offset {t.storage_offset()} must be multiples of 16 bytes "
+                             "(16-byte loads); the view is not copied")
+    if packed:
+        _check_cu_seqlens("cu_seqlens_q", cu_seqlens_q, q)
+        _check_cu_seqlens("cu_seqlens_k", cu_seqlens_k, q, batch=cu_seqlens_q.shape[0] - 1)
+    batch = cu_seqlens_q.shape[0] - 1 if packed else q.shape[0]
+    for name, t, heads in (("q_descale", q_descale, h), ("k_descale", k_descale, h_k), ("v_descale", v_descale, h_k)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be None or a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+        if tuple(t.shape) != (batch, heads):
+            raise ValueError(f"{name} must have shape (batch, heads) = ({batch}, {heads}), got {tuple(t.shape)}")
+        if t.device != q.device:
+            raise ValueError(f"{name} must be on q's device ({q.device}), got {t.device}")
+    softmax_scale, _ = _check_scale_and_cap(softmax_scale, 0.0)
+    if not isinstance(causal, bool):
+        raise ValueError(f"causal must be a bool, got {causal!r}")
+    if out_dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"out_dtype must be torch.bfloat16 or torch.float16, got {out_dtype!r}")
+    out, lse = _C.fwd_fp8(q, k, v, q_descale, k_descale, v_descale, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale, out_dtype == torch.bfloat16)
+    return (out, lse) if return_softmax_lse else out
+
+
 def _check_mla_prefill_args(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale, causal, forward_only=False):
     """the argument checks of flash_mla_prefill_func, shared with its backward and with flash_mla_attn_func; returns softmax_scale as the extension takes it"""
     packed = cu_seqlens_q is not None or cu_seqlens_k is not None

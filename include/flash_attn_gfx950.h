@@ -1087,6 +1087,58 @@ typedef struct fa_mla_prefill_bwd_params {
     int64_t total_k;            /* packed: rows of k / v / dk / dv */
 } fa_mla_prefill_bwd_params;
 
+/* FP8 dense attention forward (FA_HAS_FP8_FWD; the FP8 forward of flash-attn 3): q, k and v are OCP e4m3 codes (torch.float8_e4m3fn), head_dim 128, and both
+ * matrix products run on the FP8 matrix instruction.  FA_ABI_VERSION is unchanged; the presence of fa_run_fp8_fwd is how a caller detects the feature.
+ * struct_size must be sizeof(fa_fp8_fwd_params) (FA_PARAMS_INIT).
+ *   dense (cu_seqlens_q = cu_seqlens_k = NULL): q (b, seqlen_q, h, 128), k / v (b, seqlen_k, h_k, 128) codes, o (b, seqlen_q, h, 128) of out_dtype (FA_FP16 /
+ *   FA_BF16), lse (b, h, seqlen_q) fp32.  packed (both cu_seqlens: int32 DEVICE arrays (b + 1,)): q (total_q, h, 128), k / v (total_k, h_k, 128), o (total_q,
+ *   h, 128), lse (h, total_q), the rows of sequence i as in fa_mla_prefill_params; the launch is sized from total_q, rows at or past cu_seqlens_q[b] are left
+ *   untouched.  h % h_k == 0.  q / k / v strides in bytes (= codes), o strides in elements; pointers 16-byte aligned, strides multiples of 16 bytes, row strides
+ *   at least the row widths; one sequence (packed: the whole tensor) spans less than 2^31 bytes.
+ *   q_descale (b, h), k_descale / v_descale (b, h_k): fp32 DEVICE arrays read with the two element strides given (0 = broadcast), NULL = 1.0; finite and
+ *   positive (a precondition, not checked).  The dequantised operands are float(code) * descale.
+ * In fp32 math over the visible keys (visibility as in fa_mla_prefill_params): s_tj = (q_t . k_j) * (softmax_scale * q_descale * k_descale), the code products
+ * accumulated in fp32; with the running maximum m, p = exp(s - m) in fp32; the denominator l sums the fp32 p; the second product takes e4m3_rne(256 p) and
+ * accumulates in fp32; o = O / (256 l) * v_descale rounded once to out_dtype; lse = m + ln l.  A row that sees no key is o = 0, lse = 0.  A NaN code in a query
+ * row, or a NaN score of a visible key, gives a NaN row.  softmax_scale: finite and > 0, or 0 = the default 128 ** -0.5.
+ * One launch on `stream`, no workspace, no key split, no host synchronisation, deterministic; sequence i of a packed call equals the dense call on it alone
+ * bit for bit, and so does a batch entry of a dense call.
+ * Errors, the argument named by fa_last_error: d != 128 FA_ERR_BAD_HEADDIM, h % h_k FA_ERR_BAD_GQA, out_dtype FA_ERR_BAD_DTYPE, sizes / total_q / total_k /
+ * softmax_scale / reserved_ FA_ERR_BAD_SHAPE, pointers (one cu_seqlens without the other included) FA_ERR_NULL_POINTER, strides and alignment
+ * FA_ERR_BAD_STRIDE, the header FA_ERR_BAD_ABI.  b == 0 or no query row is FA_OK without a launch.  No FP8 output, other widths, per-token scales, paged K / V,
+ * window, softcap or sinks: the struct has no field for them. */
+#define FA_HAS_FP8_FWD 1
+typedef struct fa_fp8_fwd_params {
+    uint32_t struct_size;       /* sizeof(fa_fp8_fwd_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const void* q;              /* e4m3 codes */
+    const void* k;
+    const void* v;
+    void* o;                    /* out_dtype */
+    float* lse;
+    const float* q_descale;     /* NULL = 1.0 */
+    const float* k_descale;
+    const float* v_descale;
+    const int32_t* cu_seqlens_q;    /* both NULL = dense */
+    const int32_t* cu_seqlens_k;
+    int32_t b;
+    int32_t seqlen_q;
+    int32_t seqlen_k;
+    int32_t h;
+    int32_t h_k;
+    int32_t d;                  /* 128 */
+    int32_t out_dtype;          /* FA_FP16 / FA_BF16 */
+    int32_t is_causal;
+    float softmax_scale;        /* 0 = 128 ** -0.5 */
+    int32_t reserved_;          /* 0 */
+    fa_strides q_stride, k_stride, v_stride, o_stride;     /* q / k / v in bytes, o in elements; packed: the batch strides are not read */
+    int64_t q_descale_batch_stride, q_descale_head_stride;  /* elements */
+    int64_t k_descale_batch_stride, k_descale_head_stride;
+    int64_t v_descale_batch_stride, v_descale_head_stride;
+    int64_t total_q;            /* packed: rows of q / o */
+    int64_t total_k;            /* packed: rows of k / v */
+} fa_fp8_fwd_params;
+
 /* Merging attention states (FA_HAS_MERGE_STATES; merge_attn_states of vLLM, merge_state of FlashInfer): every attention call of this library returns
  * (o, lse), and n_parts such results over DISJOINT key sets of the same query rows combine into the result over the union.  FA_ABI_VERSION is unchanged; the
  * presence of fa_run_merge_states is how a caller detects the feature.  struct_size must be sizeof(fa_merge_params) (FA_PARAMS_INIT).
@@ -1409,6 +1461,10 @@ int32_t fa_mla_topk_num_splits(const fa_mla_topk_params_v2* params);
 int fa_run_mla_prefill_fwd(const fa_mla_prefill_params* params, void* stream);
 /* Its backward (fa_mla_prefill_bwd_params above): two launches on `stream`, dsoftmax_sum the only workspace, no host synchronisation. */
 int fa_run_mla_prefill_bwd(const fa_mla_prefill_bwd_params* params, void* stream);
+
+/* ---- FP8 dense attention forward (fa_fp8_fwd_params above) -------------------------------------- */
+/* One launch on `stream`, no workspace, no host synchronisation: cu_seqlens and the descales are read on the device. */
+int fa_run_fp8_fwd(const fa_fp8_fwd_params* params, void* stream);
 
 /* ---- merging attention states (fa_merge_params above) ------------------------------------------ */
 /* One launch on params->stream, no workspace, no host synchronisation. */
