@@ -15,6 +15,7 @@
 #include "fa_mla_cache_io.hpp"
 #include "fa_mla_index_prepare.hpp"
 #include "fa_fwd_fp8.hpp"
+#include "fa_fwd_prefill.hpp"
 #include "flash_attn_gfx950.h"
 
 namespace {
@@ -1495,6 +1496,50 @@ int fa_run_fp8_fwd(const fa_fp8_fwd_params* user, void* stream) {
     kp.total_q = packed ? p->total_q : 0; kp.total_k = packed ? p->total_k : 0;
     kp.scale = p->softmax_scale > 0.f ? p->softmax_scale : 1.0f / sqrtf((float)p->d);       // (the default = 128 ** -0.5 rounded once to fp32)
     return hip_status(fa::launch_fwd_fp8(kp, p->out_dtype, (hipStream_t)stream), "fa_fwd_fp8 launch");
+}
+
+// ---- the prompt forward with a sliding window and attention sinks ------------------------------------------------------------------------------
+// fa_prefill_fwd_params -> PrefillFwdParams, validated: the order and the words of fa_run_mla_prefill_fwd wherever the mistake is the same.  A causal call
+// reaches the kernel as window_right = 0, a side below 0 as -1.
+int fa_run_prefill_fwd(const fa_prefill_fwd_params* user, void* stream) {
+    fa_prefill_fwd_params local;
+    int rc = import_exact(user, local, "fa_prefill_fwd_params");
+    if (rc) return rc;
+    const fa_prefill_fwd_params* p = &local;
+    if ((rc = check_prefill_sizes(*p))) return rc;
+    if (p->d != 64 && p->d != 128) return fail(FA_ERR_BAD_HEADDIM, "head_dim %d unsupported (64 or 128)", p->d);
+    if ((rc = check_dtype(p->dtype))) return rc;
+    if ((rc = check_cu_seqlens(p->cu_seqlens_q, p->cu_seqlens_k, true))) return rc;
+    if ((rc = check_softmax_scale(p->softmax_scale, "d ** -0.5"))) return rc;
+    if ((rc = check_prefill_totals(*p))) return rc;
+    if ((rc = check_reserved(p->reserved_, "fa_prefill_fwd_params", FA_ERR_BAD_SHAPE))) return rc;
+    if (p->sinks_dtype != 0 && p->sinks_dtype != 1) return fail(FA_ERR_BAD_DTYPE, "sinks_dtype %d unsupported (0 = fp32, 1 = the dtype of q)", p->sinks_dtype);
+    if ((rc = check_mla_prefill_grid(*p, false))) return rc;
+    const bool packed = p->cu_seqlens_q != nullptr;
+    const int64_t rows_q = packed ? p->total_q : p->seqlen_q, rows_k = packed ? p->total_k : p->seqlen_k;
+    if (p->b == 0 || rows_q == 0) return FA_OK;     // nothing to write
+    if (p->lse == nullptr) return fail(FA_ERR_NULL_POINTER, "lse is NULL");
+    if (p->sinks != nullptr && ((uintptr_t)p->sinks & (p->sinks_dtype == 0 ? 3 : 1)) != 0)
+        return fail(FA_ERR_BAD_STRIDE, "sinks must be %d-byte aligned (%s logits, one per query head)", p->sinks_dtype == 0 ? 4 : 2, p->sinks_dtype == 0 ? "fp32" : "16-bit");
+    if ((rc = check_tensor("q", p->q, p->q_stride, rows_q, p->d, packed))) return rc;
+    if ((rc = check_tensor("o", p->o, p->o_stride, rows_q, p->d, packed))) return rc;
+    if (rows_k > 0) {
+        if ((rc = check_tensor("k", p->k, p->k_stride, rows_k, p->d, packed))) return rc;
+        if ((rc = check_tensor("v", p->v, p->v_stride, rows_k, p->d, packed))) return rc;
+    }
+    fa::PrefillFwdParams kp;
+    memset(&kp, 0, sizeof(kp));
+    kp.q_ptr = p->q; kp.k_ptr = p->k; kp.v_ptr = p->v; kp.o_ptr = p->o; kp.lse_ptr = p->lse;
+    kp.sinks = p->sinks; kp.sinks_stride = p->sinks_stride; kp.sinks_16bit = p->sinks_dtype;
+    kp.cu_q = p->cu_seqlens_q; kp.cu_k = p->cu_seqlens_k;
+    kp.q = conv(p->q_stride); kp.k = conv(p->k_stride); kp.v = conv(p->v_stride); kp.o = conv(p->o_stride);
+    kp.b = p->b; kp.seqlen_q = p->seqlen_q; kp.seqlen_k = p->seqlen_k;
+    kp.h = p->h; kp.h_k = p->h_k; kp.h_ratio = p->h / p->h_k;
+    kp.window_left = p->window_left < 0 ? -1 : p->window_left;
+    kp.window_right = p->is_causal ? 0 : (p->window_right < 0 ? -1 : p->window_right);
+    kp.total_q = packed ? p->total_q : 0; kp.total_k = packed ? p->total_k : 0;
+    set_scale(kp, p->softmax_scale > 0.f ? p->softmax_scale : 1.0f / sqrtf((float)p->d));       // (the default = d ** -0.5 rounded once to fp32)
+    return hip_status(fa::launch_fwd_prefill(kp, p->dtype, p->d, (hipStream_t)stream), "fa_fwd_prefill launch");
 }
 
 // ---- merging attention states ----------------------------------------------------------------------------------------------------------------

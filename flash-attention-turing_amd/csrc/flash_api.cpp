@@ -701,6 +701,46 @@ std::vector<at::Tensor> mha_fwd_fp8(at::Tensor q, at::Tensor k, at::Tensor v, c1
     return {o, l};
 }
 
+// The prompt forward with a window and sinks (fa_run_prefill_fwd): q (b, sq, h, d), k / v (b, sk, h_k, d), d 64 / 128, or packed with both cu_seqlens ->
+// [out shaped like q, lse (b, h, sq) or (h, total_q)].  sinks: (h,) fp32 or q's dtype, read on the device with its stride.  Nothing is copied: the tensors
+// go to the library with the strides they have, and a view it cannot address is its error.
+std::vector<at::Tensor> mha_fwd_prefill(at::Tensor q, at::Tensor k, at::Tensor v, c10::optional<at::Tensor> cu_seqlens_q_, c10::optional<at::Tensor> cu_seqlens_k_,
+                                        bool is_causal, int64_t window_left, int64_t window_right, c10::optional<at::Tensor> sinks_, c10::optional<double> softmax_scale) {
+    const bool packed = check_mla_prefill_qkv(q, k, v, cu_seqlens_q_, cu_seqlens_k_);
+    const MlaPrefillShape s = check_mla_prefill_shapes(q, k, v, packed, cu_seqlens_q_);
+    TORCH_CHECK(v.size(-1) == q.size(-1), "q / v head_dim must match");
+    check_mla_prefill_cu(q, packed, cu_seqlens_q_, cu_seqlens_k_);
+    c10::DeviceGuard guard(q.device());
+    // dense: every element of o and l is written (dead rows included); packed: the rows past cu_seqlens_q[-1] are not touched
+    at::Tensor o = packed ? torch::empty({s.rows_q, s.num_heads, v.size(-1)}, q.options()) : torch::empty({s.batch_size, s.rows_q, s.num_heads, v.size(-1)}, q.options());
+    at::Tensor l = packed ? torch::empty({s.num_heads, s.rows_q}, q.options().dtype(torch::kFloat32))
+                          : torch::empty({s.batch_size, s.num_heads, s.rows_q}, q.options().dtype(torch::kFloat32));
+
+    fa_prefill_fwd_params p;
+    FA_PARAMS_INIT(p);
+    p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = o.data_ptr(); p.lse = l.data_ptr<float>();
+    p.b = (int32_t)s.batch_size; p.h = (int32_t)s.num_heads; p.h_k = (int32_t)s.num_heads_k; p.d = (int32_t)q.size(-1);
+    p.dtype = fa_dtype_of(q); p.is_causal = is_causal;
+    p.window_left = window_left < 0 ? -1 : (int32_t)std::min<int64_t>(window_left, INT32_MAX);
+    p.window_right = window_right < 0 ? -1 : (int32_t)std::min<int64_t>(window_right, INT32_MAX);
+    p.softmax_scale = softmax_scale_fp32(softmax_scale, "d ** -0.5");
+    if (packed) {
+        p.cu_seqlens_q = cu_seqlens_q_->data_ptr<int32_t>(); p.cu_seqlens_k = cu_seqlens_k_->data_ptr<int32_t>();
+        p.total_q = s.rows_q; p.total_k = s.rows_k;
+    } else {
+        p.seqlen_q = (int32_t)s.rows_q; p.seqlen_k = (int32_t)s.rows_k;
+    }
+    p.q_stride = strides34(q); p.k_stride = strides34(k); p.v_stride = strides34(v); p.o_stride = strides34(o);
+    if (sinks_.has_value()) {
+        check_same_device(q, *sinks_, "sinks");
+        TORCH_CHECK((sinks_->scalar_type() == torch::kFloat32 || sinks_->scalar_type() == q.scalar_type()) && sinks_->dim() == 1 && sinks_->size(0) == s.num_heads,
+                    "sinks must be (nheads,) of float32 or of q's dtype");
+        p.sinks = sinks_->data_ptr(); p.sinks_stride = sinks_->stride(0); p.sinks_dtype = sinks_->scalar_type() == torch::kFloat32 ? 0 : 1;
+    }
+    check_status(fa_run_prefill_fwd(&p, current_stream(q)));
+    return {o, l};
+}
+
 // Merging attention states (fa_run_merge_states): dense outs[i] (b, rows, h, d_v) / lses[i] (b, h, rows) -> [out (b, rows, h, d_v), lse (b, h, rows)]; packed
 // outs[i] (total, h, d_v) / lses[i] (h, total) -> [out (total, h, d_v), lse (h, total)].  Nothing is copied: every part goes to the library with the strides it
 // has (an LSE with any strides at all), and a view it cannot address is its error.
@@ -1088,6 +1128,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("q"), py::arg("k"), py::arg("v"), py::arg("q_descale") = py::none(), py::arg("k_descale") = py::none(), py::arg("v_descale") = py::none(),
           py::arg("cu_seqlens_q") = py::none(), py::arg("cu_seqlens_k") = py::none(), py::arg("is_causal") = false, py::arg("softmax_scale") = py::none(),
           py::arg("out_bf16") = true);
+    m.def("fwd_prefill", &mha_fwd_prefill,
+          "prompt forward with a sliding window and attention sinks: q (b, sq, h, d), k / v (b, sk, h_k, d), d 64 / 128 -> [out, lse]; packed with both cu_seqlens",
+          py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_seqlens_q") = py::none(), py::arg("cu_seqlens_k") = py::none(), py::arg("is_causal") = false,
+          py::arg("window_left") = -1, py::arg("window_right") = -1, py::arg("sinks") = py::none(), py::arg("softmax_scale") = py::none());
     m.def("bwd_mla_prefill", &mha_bwd_mla_prefill,
           "MLA prefill backward: dout, q, k, v, out, lse -> [dq, dk, dv, dsoftmax_sum]; packed with both cu_seqlens",
           py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("cu_seqlens_q") = py::none(),

@@ -218,6 +218,17 @@ class Fp8FwdParams(_Params):
                 ("total_q", ctypes.c_int64), ("total_k", ctypes.c_int64)]
 
 
+class PrefillFwdParams(_Params):
+    """fa_prefill_fwd_params: the prompt forward with a sliding window and attention sinks, head_dim 64 / 128, dense or packed (fa_run_prefill_fwd)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("magic", ctypes.c_uint32), ("q", _vp), ("k", _vp), ("v", _vp), ("o", _vp), ("lse", _vp),
+                ("sinks", _vp), ("cu_seqlens_q", _vp), ("cu_seqlens_k", _vp),
+                ("b", _i32), ("seqlen_q", _i32), ("seqlen_k", _i32), ("h", _i32), ("h_k", _i32), ("d", _i32), ("dtype", _i32), ("is_causal", _i32),
+                ("window_left", _i32), ("window_right", _i32), ("softmax_scale", ctypes.c_float), ("sinks_dtype", _i32),
+                ("sinks_stride", ctypes.c_int64), ("reserved_", ctypes.c_int64),
+                ("q_stride", Strides), ("k_stride", Strides), ("v_stride", Strides), ("o_stride", Strides),
+                ("total_q", ctypes.c_int64), ("total_k", ctypes.c_int64)]
+
+
 FA_MERGE_MAX_PARTS = 8
 
 
@@ -371,6 +382,8 @@ def lib():
         L.fa_run_mla_prefill_bwd.restype = ctypes.c_int
         L.fa_run_fp8_fwd.argtypes = [ctypes.POINTER(Fp8FwdParams), _vp]
         L.fa_run_fp8_fwd.restype = ctypes.c_int
+        L.fa_run_prefill_fwd.argtypes = [ctypes.POINTER(PrefillFwdParams), _vp]
+        L.fa_run_prefill_fwd.restype = ctypes.c_int
         L.fa_run_merge_states.argtypes = [ctypes.POINTER(MergeParams)]
         L.fa_run_merge_states.restype = ctypes.c_int
         L.fa_run_mla_cache_append.argtypes = [ctypes.POINTER(MlaCacheAppendParams), _vp]
@@ -932,6 +945,43 @@ def run_mla_prefill_fwd(params, stream=None):
 
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     check(lib().fa_run_mla_prefill_fwd(ctypes.byref(params), s))
+
+
+def prefill_fwd_params(q, k, v, o, lse, cu_seqlens_q=None, cu_seqlens_k=None, causal=False, window_size=(-1, -1), sinks=None, softmax_scale=None):
+    """fa_prefill_fwd_params for dense q / o (b, sq, h, d), k / v (b, sk, h_k, d), lse (b, h, sq) or, with both cu_seqlens (int32 (b + 1,)), packed q / o
+    (total_q, h, d), k / v (total_k, h_k, d), lse (h, total_q): torch tensors with arbitrary batch / row / head strides, the caller's o and lse; sinks (h,)
+    of float32 or of q's dtype."""
+    import torch
+
+    p = PrefillFwdParams()
+    p.q, p.k, p.v, p.o, p.lse = (t.data_ptr() for t in (q, k, v, o, lse))
+    packed = cu_seqlens_q is not None or cu_seqlens_k is not None
+    p.h, p.h_k, p.d = q.shape[-2], k.shape[-2], q.shape[-1]
+    p.dtype, p.is_causal = dtype_code(q.dtype), int(causal)
+    p.window_left, p.window_right = (-1 if w < 0 else min(int(w), 2**31 - 1) for w in window_size)
+    p.softmax_scale = 0.0 if softmax_scale is None else float(softmax_scale)
+    if sinks is not None:
+        p.sinks, p.sinks_stride, p.sinks_dtype = sinks.data_ptr(), sinks.stride(0), 0 if sinks.dtype == torch.float32 else 1
+    if packed:
+        p.cu_seqlens_q = None if cu_seqlens_q is None else cu_seqlens_q.data_ptr()
+        p.cu_seqlens_k = None if cu_seqlens_k is None else cu_seqlens_k.data_ptr()
+        p.b = (cu_seqlens_q if cu_seqlens_q is not None else cu_seqlens_k).numel() - 1
+        p.total_q, p.total_k = q.shape[0], k.shape[0]
+        for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", o)):
+            setattr(p, name, Strides(0, t.stride(0), t.stride(1)))
+    else:
+        p.b, p.seqlen_q, p.seqlen_k = q.shape[0], q.shape[1], k.shape[1]
+        for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", o)):
+            setattr(p, name, Strides(t.stride(0), t.stride(1), t.stride(2)))
+    return p
+
+
+def run_prefill_fwd(params, stream=None):
+    """fa_run_prefill_fwd"""
+    import torch
+
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    check(lib().fa_run_prefill_fwd(ctypes.byref(params), s))
 
 
 def mla_prefill_bwd_params(dout, q, k, v, o, lse, dq, dk, dv, dsoftmax_sum, cu_seqlens_q=None, cu_seqlens_k=None, causal=False, softmax_scale=None, phases=0):

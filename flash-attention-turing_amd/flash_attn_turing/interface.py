@@ -164,9 +164,9 @@ def _check_scale_and_cap(softmax_scale, softcap):
     return softmax_scale, softcap
 
 
-def _check_sinks(sinks, q, softcap):
+def _check_sinks(sinks, q, softcap, widen=True):
     """sinks: a 1-D tensor (nheads,) on q's device, float32 or q's dtype, any stride; not with a soft cap, not at head_dim 256.  Returns it as
-    float32 (q's dtype is widened with a torch op: exact, asynchronous, capturable)."""
+    float32 (q's dtype is widened with a torch op: exact, asynchronous, capturable) or, with widen=False, as it is."""
     if not isinstance(sinks, torch.Tensor):
         raise ValueError(f"sinks must be None or a tensor of shape (nheads,), got {type(sinks).__name__}")
     if sinks.dtype != torch.float32 and sinks.dtype != q.dtype:
@@ -179,7 +179,7 @@ def _check_sinks(sinks, q, softcap):
         raise ValueError("sinks together with softcap > 0 are not supported")
     if q.shape[-1] == 256:
         raise ValueError("sinks at head_dim 256 are not supported: flash_attn_with_kvcache has sinks at head_dim 64 and 128")
-    return sinks if sinks.dtype == torch.float32 else sinks.float()
+    return sinks if sinks.dtype == torch.float32 or not widen else sinks.float()
 
 
 def _check_tree_mask(tree_mask, q, causal, window, softcap, sinks, rotary_cos, rotary_sin, cu_seqlens_q, max_seqlen_q):
@@ -1105,6 +1105,86 @@ def flash_attn_fp8_func(q, k, v, *, q_descale=None, k_descale=None, v_descale=No
     if out_dtype not in (torch.bfloat16, torch.float16):
         raise ValueError(f"out_dtype must be torch.bfloat16 or torch.float16, got {out_dtype!r}")
     out, lse = _C.fwd_fp8(q, k, v, q_descale, k_descale, v_descale, cu_seqlens_q, cu_seqlens_k, causal, softmax_scale, out_dtype == torch.bfloat16)
+    return (out, lse) if return_softmax_lse else out
+
+
+def flash_attn_prefill_func(q, k, v, *, cu_seqlens_q=None, cu_seqlens_k=None, softmax_scale=None, causal=False, window_size=(-1, -1), sinks=None,
+                            return_softmax_lse=False):
+    """The prompt forward with a sliding window and attention sinks (gpt-oss, Mistral-style layers): head_dim 64 / 128, dense and packed, forward only.
+
+    The prompt side of flash_attn_with_kvcache's ``window_size`` / ``sinks`` / ``softmax_scale``: a workgroup serves 128 packed rows (128 / (nheads /
+    nheads_k) tokens of one KV head) and walks only the keys its tokens see, where the 16-row decode kernels stream the visible keys again for every
+    16 / (nheads / nheads_k) tokens.
+
+    dense:  q (batch, seqlen_q, nheads, d), k / v (batch, seqlen_k, nheads_k, d) -> out shaped like q and, with ``return_softmax_lse``, lse (batch, nheads,
+            seqlen_q) fp32 (natural log).
+    packed: q (total_q, nheads, d), k / v (total_k, nheads_k, d) with cu_seqlens_q / cu_seqlens_k, int32 (batch + 1,) on q's device, given both or neither
+            -> out (total_q, nheads, d), lse (nheads, total_q).  The launch is sized from total_q; rows at or past cu_seqlens_q[-1] are not written.
+    d is 64 or 128; fp16 / bf16, one dtype for all three; nheads % nheads_k == 0 (GQA / MQA).  The last dimension is contiguous, every other stride and
+    the storage offset are multiples of 8 elements; other views are refused, never copied.  One sequence (packed: the whole tensor) spans less than 2^31
+    bytes.
+
+    In fp32 math, the semantics of the decode call: ``s_tj = (q_t . k_j) * softmax_scale``; key j is visible to row t of a sequence with sq_i rows and L_i
+    keys iff 0 <= j < L_i and L_i - sq_i + t - left <= j <= L_i - sq_i + t + right with (left, right) = window_size, -1 = unbounded on that side, and
+    ``causal=True`` sets right = 0.  window_size is validated like flash_attn_with_kvcache's.  softmax_scale: None = d ** -0.5 rounded once to fp32;
+    validated like softmax_scale of flash_attn_with_kvcache.
+    sinks: None or a tensor (nheads,) on q's device, float32 or q's dtype, any stride, read on the device.  sinks[h] is one logit of QUERY head h in the
+    units of the final scores (never scaled).  It joins the running maximum and the denominator of every row of the head and contributes no value: with
+    M = max(max_j s_j, sinks[h]), ``out = sum_j exp(s_j - M) v_j / (sum_j exp(s_j - M) + exp(sinks[h] - M))``, and the returned LSE includes the sink.  A
+    row that sees no key gives O = 0, LSE = sinks[h]; with sinks[h] = -inf or sinks=None that row is dead (O = 0, LSE = 0).  A NaN sink makes its head's
+    rows NaN.  A NaN in a query row, or a NaN / +inf score of a visible key, makes that row NaN; non-finite V has no contract across the rows of a tile.
+
+    No host synchronisation (cu_seqlens and sinks are read on the device: graph-capturable), no key split, no workspace, deterministic.  Bit for bit, out
+    and lse: sequence i of a packed call equals the dense call on it alone; a batch entry equals the call on it alone; sinks = -inf on every head equals
+    sinks=None; a window that hides no key of the call equals window_size=(-1, -1).  No bit relation to flash_attn_func or to flash_attn_with_kvcache.
+    Never read: keys that no row of a workgroup's 128-row tile can see (below the tile's window start, past its window or causal end), rows past a
+    sequence's end, packed rows past cu_seqlens[-1].  The work of a row scales with its window, not with L_i.
+    Out of scope, and without a keyword here: softcap, head_dim 256, paged or FP8 K / V, append (k / v written into a cache), rotary, tree masks, any
+    backward, and choosing this path automatically from flash_attn_func.  Wrong shapes, dtypes, views or values are a ValueError that names the argument.
+    """
+    packed = cu_seqlens_q is not None or cu_seqlens_k is not None
+    if packed and (cu_seqlens_q is None or cu_seqlens_k is None):
+        raise ValueError("cu_seqlens_q and cu_seqlens_k come both or neither, got only " + ("cu_seqlens_q" if cu_seqlens_k is None else "cu_seqlens_k"))
+    rank = 3 if packed else 4
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dim() != rank:
+            raise ValueError(f"{name} must be a rank-{rank} tensor ({'(total, nheads, head_dim) with cu_seqlens' if packed else '(batch, seqlen, nheads, head_dim)'})")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        bad = next(n for n, t in (("q", q), ("k", k), ("v", v)) if t.requires_grad)
+        raise ValueError(f"{bad} requires grad: flash_attn_prefill_func is forward-only; run it under torch.no_grad() or detach the inputs")
+    if q.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"q must be fp16 or bf16, got {q.dtype}")
+    for name, t in (("k", k), ("v", v)):
+        if t.dtype != q.dtype:
+            raise ValueError(f"{name} must have q's dtype ({q.dtype}), got {t.dtype}")
+        if t.device != q.device:
+            raise ValueError(f"{name} must be on q's device ({q.device}), got {t.device}")
+    if q.shape[-1] not in (64, 128):
+        raise ValueError(f"q must be 64 or 128 wide, got head_dim {q.shape[-1]}")
+    for name, t in (("k", k), ("v", v)):
+        if t.shape[-1] != q.shape[-1]:
+            raise ValueError(f"{name} must have q's head_dim ({q.shape[-1]}), got {t.shape[-1]}")
+    if k.shape != v.shape:
+        raise ValueError(f"k and v must have one shape, got {tuple(k.shape)} and {tuple(v.shape)}")
+    if not packed and k.shape[0] != q.shape[0]:
+        raise ValueError(f"k / v batch ({k.shape[0]}) must match q's ({q.shape[0]})")
+    h, h_k = q.shape[-2], k.shape[-2]
+    if h < 1 or h_k < 1 or h % h_k != 0:
+        raise ValueError(f"nheads of q ({h}) must be a positive multiple of nheads_k of k / v ({h_k})")
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        _check_prefill_view(name, t)
+    if packed:
+        _check_cu_seqlens("cu_seqlens_q", cu_seqlens_q, q)
+        _check_cu_seqlens("cu_seqlens_k", cu_seqlens_k, q, batch=cu_seqlens_q.shape[0] - 1)
+    left, right = _window_pair(window_size)
+    softmax_scale, _ = _check_scale_and_cap(softmax_scale, 0.0)
+    if not isinstance(causal, bool):
+        raise ValueError(f"causal must be a bool, got {causal!r}")
+    if sinks is not None:
+        _check_sinks(sinks, q, 0.0, widen=False)
+        if torch.is_grad_enabled() and sinks.requires_grad:
+            raise ValueError("sinks requires grad: flash_attn_prefill_func is forward-only; run it under torch.no_grad() or detach the inputs")
+    out, lse = _C.fwd_prefill(q, k, v, cu_seqlens_q, cu_seqlens_k, causal, left, right, sinks, softmax_scale)
     return (out, lse) if return_softmax_lse else out
 
 

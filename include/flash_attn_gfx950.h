@@ -1139,6 +1139,58 @@ typedef struct fa_fp8_fwd_params {
     int64_t total_k;            /* packed: rows of k / v */
 } fa_fp8_fwd_params;
 
+/* The prompt forward with a sliding window and attention sinks (FA_HAS_PREFILL_FWD; a gpt-oss or Mistral-style prompt): head_dim 64 / 128, dense or packed,
+ * forward only.  FA_ABI_VERSION is unchanged; the presence of fa_run_prefill_fwd is how a caller detects the feature.  struct_size must be
+ * sizeof(fa_prefill_fwd_params) (FA_PARAMS_INIT).
+ *   dense (cu_seqlens_q = cu_seqlens_k = NULL): q (b, seqlen_q, h, d), k / v (b, seqlen_k, h_k, d), o (b, seqlen_q, h, d) of `dtype`, lse (b, h, seqlen_q) fp32.
+ *   packed (both cu_seqlens: int32 DEVICE arrays (b + 1,)): q (total_q, h, d), k / v (total_k, h_k, d), o (total_q, h, d), lse (h, total_q), the rows of
+ *   sequence i as in fa_mla_prefill_params; the launch is sized from total_q, rows at or past cu_seqlens_q[b] are left untouched.  h % h_k == 0.  Strides in
+ *   elements, multiples of 8 with row strides at least d; pointers 16-byte aligned; one sequence (packed: the whole tensor) spans less than 2^31 bytes.
+ * In fp32 math: key j is visible to row t of a sequence with sq rows and L keys iff 0 <= j < L and L - sq + t - window_left <= j <= L - sq + t + window_right;
+ * a side < 0 is unbounded; is_causal != 0 sets window_right = 0.  s_tj = (q_t . k_j) * softmax_scale (finite and > 0, or 0 = the default d ** -0.5).
+ *   sinks: NULL = off.  Otherwise DEVICE memory, one logit per QUERY head, head hq reads sinks[hq * sinks_stride] (elements): fp32 (sinks_dtype = 0,
+ *   4-byte aligned) or `dtype` (sinks_dtype = 1, 2-byte aligned).  The logit is in the units of the final scores and is never scaled; it joins the running
+ *   maximum and the denominator of every row of the head and contributes no value, and lse includes it.  A row that sees no key is o = 0, lse = its sink;
+ *   with a sink of -inf, or without sinks, o = 0, lse = 0.  A sink of -inf on every head gives the call without sinks bit for bit.  A NaN sink makes the
+ *   rows of its head NaN.
+ * One launch on `stream`, no workspace, no key split, no host synchronisation, deterministic.  Sequence i of a packed call equals the dense call on it alone
+ * bit for bit, and so does a batch entry of a dense call; a window that hides no key of the call equals the call without a window.  Keys that no row of a
+ * 128-row tile sees, rows past a sequence's end and packed rows past cu_seqlens[b] are never read.
+ * Errors, the argument named by fa_last_error: d FA_ERR_BAD_HEADDIM, h % h_k FA_ERR_BAD_GQA, dtype / sinks_dtype FA_ERR_BAD_DTYPE, sizes / total_q / total_k /
+ * softmax_scale / reserved_ FA_ERR_BAD_SHAPE, pointers (one cu_seqlens without the other included) FA_ERR_NULL_POINTER, strides and alignment
+ * FA_ERR_BAD_STRIDE, the header FA_ERR_BAD_ABI.  b == 0 or no query row is FA_OK without a launch.  No softcap, head_dim 256, paged or FP8 K / V, append,
+ * rotary, tree mask or backward: the struct has no field for them. */
+#define FA_HAS_PREFILL_FWD 1
+typedef struct fa_prefill_fwd_params {
+    uint32_t struct_size;       /* sizeof(fa_prefill_fwd_params) in the caller's translation unit */
+    uint32_t magic;             /* FA_PARAMS_MAGIC */
+    const void* q;
+    const void* k;
+    const void* v;
+    void* o;
+    float* lse;
+    const void* sinks;          /* NULL = off */
+    const int32_t* cu_seqlens_q;    /* both NULL = dense */
+    const int32_t* cu_seqlens_k;
+    int32_t b;
+    int32_t seqlen_q;
+    int32_t seqlen_k;
+    int32_t h;
+    int32_t h_k;
+    int32_t d;                  /* 64 or 128 */
+    int32_t dtype;              /* FA_FP16 / FA_BF16 */
+    int32_t is_causal;
+    int32_t window_left;        /* < 0 = unbounded */
+    int32_t window_right;       /* < 0 = unbounded; is_causal sets 0 */
+    float softmax_scale;        /* 0 = d ** -0.5 */
+    int32_t sinks_dtype;        /* 0 = fp32 logits, 1 = logits of `dtype` */
+    int64_t sinks_stride;       /* elements between consecutive heads' logits */
+    int64_t reserved_;          /* 0 */
+    fa_strides q_stride, k_stride, v_stride, o_stride;     /* elements; packed: the batch strides are not read */
+    int64_t total_q;            /* packed: rows of q / o */
+    int64_t total_k;            /* packed: rows of k / v */
+} fa_prefill_fwd_params;
+
 /* Merging attention states (FA_HAS_MERGE_STATES; merge_attn_states of vLLM, merge_state of FlashInfer): every attention call of this library returns
  * (o, lse), and n_parts such results over DISJOINT key sets of the same query rows combine into the result over the union.  FA_ABI_VERSION is unchanged; the
  * presence of fa_run_merge_states is how a caller detects the feature.  struct_size must be sizeof(fa_merge_params) (FA_PARAMS_INIT).
@@ -1465,6 +1517,10 @@ int fa_run_mla_prefill_bwd(const fa_mla_prefill_bwd_params* params, void* stream
 /* ---- FP8 dense attention forward (fa_fp8_fwd_params above) -------------------------------------- */
 /* One launch on `stream`, no workspace, no host synchronisation: cu_seqlens and the descales are read on the device. */
 int fa_run_fp8_fwd(const fa_fp8_fwd_params* params, void* stream);
+
+/* ---- the prompt forward with a window and sinks (fa_prefill_fwd_params above) ------------------- */
+/* One launch on `stream`, no workspace, no host synchronisation: cu_seqlens and the sinks are read on the device. */
+int fa_run_prefill_fwd(const fa_prefill_fwd_params* params, void* stream);
 
 /* ---- merging attention states (fa_merge_params above) ------------------------------------------ */
 /* One launch on params->stream, no workspace, no host synchronisation. */
