@@ -23,7 +23,8 @@ digits) - a swap invisible to both digits; the value path (V is 0 / 1).  The bac
 
 The expectation is `visible`, a pure integer model written from the README's formulas (no float in it, nothing taken from the kernels).
 This module holds the encoding, the model, the decoder, the condition asserts, the cache builders and the parameter tables of the GPU
-tests (tests/test_kvcache_visibility_gpu.py, tests/test_attention_visibility_gpu.py, tests/test_attention_backward_visibility_gpu.py), which tests/test_visibility_cpu.py enumerates
+tests (tests/test_kvcache_visibility_gpu.py, tests/test_attention_visibility_gpu.py, tests/test_attention_backward_visibility_gpu.py,
+tests/test_prompt_visibility_gpu.py for the prompt and FP8 forwards: THE PROMPT AND FP8 FORWARDS, below), which tests/test_visibility_cpu.py enumerates
 without a GPU, and the route table of tests/test_kvcache_routes_gpu.py (one case per leaf of the launch dispatch; tests/test_kvcache_routes_cpu.py)."""
 import itertools
 from dataclasses import dataclass, replace
@@ -948,3 +949,297 @@ def all_bwd_gpu_cases():
     for _, base, moved, hot in bwd_sensitivity_pairs():
         cases += [(base, hot), (moved, hot)]
     return cases
+
+
+# ---- THE PROMPT AND FP8 FORWARDS (tests/test_prompt_visibility_gpu.py) ---------------------------------------------------
+#
+# flash_attn_prefill_func (fa_fwd_prefill.hip: 128 packed rows a workgroup, 32 rows a wave, 32-key steps, window_size and sinks) and
+# flash_attn_fp8_func (fa_fwd_fp8.hip: 64 rows a workgroup, 16 a wave, 128-key steps, causal or not) under the forward probe above, with
+# the same model (`visible`), signature, decoder and `assert_signature`.  Why the probe is exact for them:
+#   prompt forward: K = 0 makes every score 0 and m = 0 from a row's first visible step on; P = exp2(0) = 1 is exact in fp16 and bf16 and
+#     the fp32 sums of 0 / 1 are exact.  A sink of 0.0 is not above m = 0: the epilogue's `else` branch adds exp2(0) = 1.  A row without a
+#     key has m = kNegBig: the sink is on top, lsum = fma(0, a, 1) = 1 and inv = a / 1 = 0: O = 0, LSE = 0 + log 1 = 0, which `decode`
+#     tells apart from a row with one key by its two ones.  A sink of -inf (and no sinks) adds + 0.0f.
+#   FP8 forward: the K codes are 0, so the score is 0 under any q_descale, k_descale and softmax_scale; q is any finite e4m3 code (no
+#     0x7F / 0xFF).  p = exp2((0 - 0) * c) = 1 and e4m3(256 * 1) = 256 is exact; the V codes are 0 / 0x38 (1.0), so the fp32 accumulator
+#     holds 256 * m_c <= 2^14 exactly and l = n exactly; out = O / (256 l) * v_descale with v_descale a power of two, `decode`'s v_scale.
+#   both: capacity 1024 at both head dims, n <= 1024 <= MAX_N, every digit count <= 64 (asserted by `expected` on every case).
+# `check_prompt_conditions` asserts what is the case's, `check_probe_inputs` what is the tensors'; neither drops a case.
+#
+# WHAT IT DOES NOT SEE: as the forward probe - swaps invisible to both digits, and the value path (V is 0 / 1, P is 0 / 1).
+
+PROMPT_RATIOS = (1, 3, 4, 5, 6, 12, 64, 160)      # 3, 5, 6, 12 divide neither 128 nor 64: a token's heads straddle waves, column blocks and tiles; 160 > a tile
+PROMPT_SQS = (1, 2, 31, 32, 33, 43, 64, 65, 127, 128, 129, 257, 300)
+FP8FWD_SQS = (1, 2, 15, 16, 17, 22, 63, 64, 65, 129, 300)
+SINK_MODES = (None, "zero", "ninf", "mixed")
+FP8FWD_V_SCALES = (1.0, 0.25, 2.0)
+PROMPT_CAP = 1024
+PROMPT_ROW_BUDGET = 262144                        # packed (row, head) pairs of one call
+PROMPT_PAD = 3                                    # rows of the bad code behind every K / V extent
+PROMPT_BATCH = 2                                  # batch of a dense call
+PROMPT_PACKED_CASES = 16                          # per (d, dtype)
+FP8FWD_PACKED_CASES = 12                          # per (out dtype, causal)
+PROMPT_CONFIGS = tuple(itertools.product((64, 128), DTYPES))
+FP8FWD_CONFIGS = tuple(itertools.product(("bf16", "fp16"), (True, False)))
+
+
+def _prompt_heads(ratio):
+    hk = 2 if ratio <= 6 else 1
+    return dict(h=ratio * hk, hk=hk)
+
+
+def thin_lens(lens, sq, h, budget=PROMPT_ROW_BUDGET):
+    """every stride-th length, the stride odd (coprime to 32 and to 128), until the call's len(lens) x sq x h packed rows fit the budget"""
+    stride = 1
+    while len(lens[::stride]) * sq * h > budget:
+        stride += 2
+    return tuple(lens[::stride])
+
+
+def prompt_lens(sq, cap=PROMPT_CAP):
+    """three runs of 33 consecutive lengths: from 0, around sq (both sides: L < sq gives dead rows) and up to the capacity - L - sq, lo and
+    lim take every residue mod 32"""
+    mid = max(sq - 16, 0)
+    return tuple(sorted(set(range(0, 33)) | set(range(mid, mid + 33)) | set(range(cap - 32, cap + 1))))
+
+
+def fp8fwd_lens(cap=PROMPT_CAP):
+    """0..260, 380..390, 505..519 and 1010..1024: every residue mod 128 at a step seam"""
+    return tuple(list(range(0, 261)) + list(range(380, 391)) + list(range(505, 520)) + list(range(cap - 14, cap + 1)))
+
+
+def _packed(family, name, lens, sq, **kw):
+    """one packed call: the lengths as sequences of sq rows each, and a sequence without query rows behind the first"""
+    lens, sqs = tuple(lens), (sq,) * len(lens)
+    return Case(family=family, name=f"{family}/{name}", lens=lens[:1] + (37,) + lens[1:], sq=sqs[:1] + (0,) + sqs[1:], ragged=True, cap=PROMPT_CAP, **kw)
+
+
+def _prompt_window(i):
+    """(causal, window) of the i-th case of a table: plain, causal alone, then LEFTS x RIGHTS rotated with every fourth one causal"""
+    if i % PROMPT_PACKED_CASES == 0:
+        return False, (-1, -1)
+    if i % PROMPT_PACKED_CASES == 1:
+        return True, (-1, -1)
+    return i % 4 == 3, (LEFTS[(i - 2) % 13], RIGHTS[(i - 2) % 7])
+
+
+def _win_name(causal, window):
+    return f"w{window[0]}_{window[1]}" + ("-causal" if causal else "")
+
+
+def prompt_cases(d, dtype):
+    """the packed calls of flash_attn_prefill_func at one (d, dtype): sq, h / h_k, window, causal and sinks rotate (not crossed)"""
+    cfg = PROMPT_CONFIGS.index((d, dtype))
+    out = []
+    for i in range(PROMPT_PACKED_CASES):
+        sq = PROMPT_SQS[(i + 3 * cfg) % len(PROMPT_SQS)]
+        ratio = PROMPT_RATIOS[(3 * i + cfg) % len(PROMPT_RATIOS)]
+        causal, window = _prompt_window(i)
+        sink = SINK_MODES[(i + i // 4 + cfg) % 4]
+        heads = _prompt_heads(ratio)
+        out.append(_packed("prompt", f"packed-d{d}-{dtype}-sq{sq}-r{ratio}-{_win_name(causal, window)}-sink_{sink}", thin_lens(prompt_lens(sq), sq, heads["h"]), sq,
+                           d=d, dtype=dtype, causal=causal, window=window, sink=sink, **heads))
+    return out
+
+
+def prompt_dense_cases(d, dtype):
+    """the dense instantiation: every (sq, sk) of attn_pairs(True), batch PROMPT_BATCH; windows, h / h_k and sinks rotate over them"""
+    cfg = PROMPT_CONFIGS.index((d, dtype))
+    out = []
+    for j, (sq, sk) in enumerate(attn_pairs(True)):
+        causal, window = _prompt_window(j + 5 * (j // PROMPT_PACKED_CASES))
+        ratio = PROMPT_RATIOS[(j + j // 14 + cfg) % len(PROMPT_RATIOS)]
+        sink = SINK_MODES[(j // 3 + cfg) % 4]
+        out.append(Case(family="prompt", name=f"prompt/dense-d{d}-{dtype}-sq{sq}-sk{sk}-r{ratio}-{_win_name(causal, window)}-sink_{sink}", lens=(sk,), sq=(sq,), d=d, dtype=dtype,
+                        causal=causal, window=window, sink=sink, cap=PROMPT_CAP, **_prompt_heads(ratio)))
+    return out
+
+
+def fp8fwd_cases(dtype, causal):
+    """the packed calls of flash_attn_fp8_func at one (out dtype, causal): sq, h / h_k and v_descale rotate"""
+    cfg = FP8FWD_CONFIGS.index((dtype, causal))
+    out = []
+    for i in range(FP8FWD_PACKED_CASES):
+        sq = FP8FWD_SQS[(i + 3 * cfg) % len(FP8FWD_SQS)]
+        ratio = PROMPT_RATIOS[(3 * i + cfg) % len(PROMPT_RATIOS)]
+        heads = _prompt_heads(ratio)
+        out.append(_packed("fp8fwd", f"packed-{dtype}-{'causal' if causal else 'full'}-sq{sq}-r{ratio}", thin_lens(fp8fwd_lens(), sq, heads["h"]), sq, d=128, dtype=dtype, fp8=True,
+                           causal=causal, v_scale=FP8FWD_V_SCALES[(i + cfg) % 3], **heads))
+    return out
+
+
+def fp8fwd_dense_cases(dtype, causal):
+    """the dense instantiation: the pairs of attn_pairs(causal), batch PROMPT_BATCH"""
+    cfg = FP8FWD_CONFIGS.index((dtype, causal))
+    out = []
+    for j, (sq, sk) in enumerate(attn_pairs(causal)):
+        ratio = PROMPT_RATIOS[(j + j // 14 + cfg) % len(PROMPT_RATIOS)]
+        out.append(Case(family="fp8fwd", name=f"fp8fwd/dense-{dtype}-{'causal' if causal else 'full'}-sq{sq}-sk{sk}-r{ratio}", lens=(sk,), sq=(sq,), d=128, dtype=dtype, fp8=True,
+                        causal=causal, v_scale=FP8FWD_V_SCALES[(j + cfg) % 3], cap=PROMPT_CAP, **_prompt_heads(ratio)))
+    return out
+
+
+def prompt_sensitivity_pairs():
+    """(name, base case, moved case) at the largest shapes of both kernels: left + 1, right + 1, one L + 1, one sq + 1.  The moved call
+    must decode to the model of the MOVED parameters and differ from the model of the base exactly on the rows whose sets differ."""
+    L, sq = (1023, 1022, 517, 1023), (300, 300, 300, 300)
+    pairs = []
+
+    def add(name, base, **moved):
+        pairs.append((name, base, replace(base, name=base.name + "+moved", **moved)))
+
+    def plus(xs, i):
+        return tuple(x + (j == i) for j, x in enumerate(xs))
+
+    def mk(family, name, **kw):
+        return Case(family=family, name=f"{family}/sens-{name}", lens=L, sq=sq, ragged=True, cap=PROMPT_CAP, **kw)
+
+    base = mk("prompt", "window-d128", d=128, dtype="fp16", window=(500, 2), sink="zero", h=8, hk=2)
+    add("prompt window: left + 1", base, window=(501, 2))
+    add("prompt window: right + 1", base, window=(500, 3))
+    add("prompt window: one L + 1", base, lens=plus(L, 1))
+    add("prompt window: one sq + 1", base, sq=plus(sq, 2))
+    base = mk("prompt", "causal-window-d64", d=64, dtype="bf16", window=(100, 0), causal=True, sink="mixed", h=6, hk=2)
+    add("prompt causal window: left + 1", base, window=(101, 0))
+    add("prompt causal window: one L + 1", base, lens=plus(L, 2))
+    base = mk("prompt", "causal-d64", d=64, dtype="fp16", causal=True, h=5, hk=1)
+    add("prompt causal: one L + 1", base, lens=plus(L, 1))
+    add("prompt causal: one sq + 1", base, sq=plus(sq, 0))
+    base = mk("prompt", "plain-d128", d=128, dtype="bf16", sink="ninf", h=12, hk=1)
+    add("prompt plain: one L + 1", base, lens=plus(L, 2))
+    base = mk("fp8fwd", "causal", d=128, dtype="bf16", fp8=True, causal=True, v_scale=0.25, h=6, hk=2)
+    add("fp8 causal: one L + 1", base, lens=plus(L, 1))
+    add("fp8 causal: one sq + 1", base, sq=plus(sq, 3))
+    base = mk("fp8fwd", "full", d=128, dtype="fp16", fp8=True, v_scale=2.0, h=5, hk=1)
+    add("fp8 full: one L + 1", base, lens=plus(L, 2))
+    return pairs
+
+
+def all_prompt_cases():
+    """every Case tests/test_prompt_visibility_gpu.py runs, for the CPU tests"""
+    cases = []
+    for d, dtype in PROMPT_CONFIGS:
+        cases += prompt_cases(d, dtype) + prompt_dense_cases(d, dtype)
+    for dtype, causal in FP8FWD_CONFIGS:
+        cases += fp8fwd_cases(dtype, causal) + fp8fwd_dense_cases(dtype, causal)
+    names = [c.name for c in cases]
+    assert len(names) == len(set(names))
+    for _, base, moved in prompt_sensitivity_pairs():
+        cases += [base, moved]
+    return cases
+
+
+def check_prompt_conditions(c):
+    """what the derivation above needs of a case, next to `check_conditions`"""
+    check_conditions(c)
+    assert c.family in ("prompt", "fp8fwd") and c.cap == PROMPT_CAP and c.d in (64, 128) and c.dtype in DTYPES
+    assert c.tree is None and c.softcap == 0.0 and c.page == 0 and not c.append and not c.prefill and c.splits == 1
+    assert c.ragged or len(c.lens) == 1, "a dense case is one (sq, sk) pair, repeated over the batch by the runner"
+    assert sum(c.sq) * c.h * (1 if c.ragged else PROMPT_BATCH) <= PROMPT_ROW_BUDGET
+    if c.family == "prompt":
+        assert not c.fp8 and c.v_scale == 1.0 and c.sink in SINK_MODES
+    else:
+        assert c.fp8 and c.d == 128 and c.window == (-1, -1) and c.sink is None and c.v_scale in FP8FWD_V_SCALES
+
+
+def check_probe_inputs(c, q, k, v, sinks=None, descales=()):
+    """the conditions on the tensors of one call: K = 0, q finite (FP8: no NaN code), V = 0 / 1 (FP8: the codes 0 / 0x38), sinks 0.0 or
+    -inf, q_descale / k_descale finite and positive"""
+    import torch
+
+    if c.family == "fp8fwd":
+        assert all(t.dtype == torch.float8_e4m3fn for t in (q, k, v))
+        qb, kb, vb = (t.view(torch.uint8) for t in (q, k, v))
+        assert ((qb & 0x7F) != 0x7F).all().item() and (kb == 0).all().item() and ((vb == 0) | (vb == FP8_ONE)).all().item()
+        assert all(torch.isfinite(t).all().item() and (t > 0).all().item() for t in descales)
+    else:
+        assert torch.isfinite(q.float()).all().item() and (k == 0).all().item() and ((v == 0) | (v == 1)).all().item()
+        assert sinks is None or ((sinks == 0) | (sinks == float("-inf"))).all().item()
+
+
+def _probe_kv(c, dev):
+    """K = 0 and V of one call -> k, v (rows, hk, d) uint8 0 / 1, cu_q, cu_k or None.  Packed: the codes of each sequence's keys, then a
+    sequence of PROMPT_PAD keys of the bad code without query rows, and PROMPT_PAD bad rows past cu_seqlens_k[-1].  Dense: sk rows of
+    codes and PROMPT_PAD bad rows behind (the runner slices them off per batch entry)."""
+    import torch
+
+    code = code_tensor(c.d, c.cap, dev)
+    bad = torch.full((PROMPT_PAD, c.d), BAD, dtype=torch.uint8, device=dev)
+    if not c.ragged:
+        v = torch.cat([code[: c.lens[0]], bad])
+        return v.unsqueeze(1).expand(-1, c.hk, -1).contiguous(), None, None
+    parts, sqs, sks = [], [], []
+    for L, s in zip(c.lens, c.sq):
+        parts += [code[:L], bad]
+        sqs += [s, 0]
+        sks += [L, PROMPT_PAD]
+    v = torch.cat(parts + [bad]).unsqueeze(1).expand(-1, c.hk, -1).contiguous()
+    cu_q, cu_k = (torch.tensor([0] + list(itertools.accumulate(x)), dtype=torch.int32, device=dev) for x in (sqs, sks))
+    return v, cu_q, cu_k
+
+
+def run_prompt(c, dev):
+    """build the probe's inputs of a "prompt" or "fp8fwd" case and call flash_attn_prefill_func / flash_attn_fp8_func
+    -> out (R, h, d), lse (R, h), R = the case's rows in packed (sequence, row) order (dense: PROMPT_BATCH copies of them)"""
+    import torch
+
+    import flash_attn_turing as F
+
+    check_prompt_conditions(c)
+    f8 = c.family == "fp8fwd"
+    dt = torch_dtype(c.dtype)
+    gen = torch.Generator(device=dev).manual_seed(len(c.name) * 7919 + sum(c.lens))
+    v01, cu_q, cu_k = _probe_kv(c, dev)
+    total, b = sum(c.sq), PROMPT_BATCH
+    qshape = (total, c.h, c.d) if c.ragged else (b, c.sq[0], c.h, c.d)
+    if not c.ragged:
+        v01 = v01.unsqueeze(0).repeat(b, 1, 1, 1)
+    if f8:
+        qb = torch.randint(0, 256, qshape, dtype=torch.uint8, device=dev, generator=gen)
+        q = (qb - ((qb & 0x7F) == 0x7F).to(torch.uint8)).view(torch.float8_e4m3fn)          # (0x7F / 0xFF, the NaN codes, become 0x7E / 0xFE)
+        v = (v01 * FP8_ONE).view(torch.float8_e4m3fn)
+        k = torch.zeros_like(v01).view(torch.float8_e4m3fn)
+    else:
+        q = torch.randn(qshape, device=dev, generator=gen).to(dt)
+        v = v01.to(dt)
+        k = torch.zeros_like(v)
+    if not c.ragged:
+        k, v = (x[:, : c.lens[0]] for x in (k, v))                                          # (the bad rows stay behind each batch entry)
+    nb = len(cu_q) - 1 if c.ragged else b
+    kw = dict(causal=c.causal, return_softmax_lse=True)
+    if c.ragged:
+        kw.update(cu_seqlens_q=cu_q, cu_seqlens_k=cu_k)
+    if f8:
+        # per-head descales that are no powers of two (they multiply a score of 0); v_descale is the case's power of two
+        qd, kd = (torch.linspace(lo, hi, n, device=dev).repeat(nb, 1) for lo, hi, n in ((0.037, 0.21, c.h), (0.05, 0.5, c.hk)))
+        vd = torch.full((nb, c.hk), c.v_scale, dtype=torch.float32, device=dev)
+        check_probe_inputs(c, q, k, v, descales=(qd, kd, vd))
+        out, lse = F.flash_attn_fp8_func(q, k, v, q_descale=qd, k_descale=kd, v_descale=vd, out_dtype=dt, **kw)
+    else:
+        sinks = None if c.sink is None else torch.tensor([0.0 if e else float("-inf") for e in c.sink_extra()], dtype=torch.float32, device=dev)
+        check_probe_inputs(c, q, k, v, sinks=sinks)
+        out, lse = F.flash_attn_prefill_func(q, k, v, window_size=c.window, sinks=sinks, **kw)
+    assert out.dtype == dt and lse.dtype == torch.float32
+    if c.ragged:
+        assert out.shape == (total, c.h, c.d) and lse.shape == (c.h, total)
+        return out, lse.t()
+    assert out.shape == (b, c.sq[0], c.h, c.d) and lse.shape == (b, c.h, c.sq[0])
+    return out.reshape(b * total, c.h, c.d), lse.permute(0, 2, 1).reshape(b * total, c.h)
+
+
+def probe_prompt(c, dev):
+    """run the case and assert, as integers, that the decoded signature of every (row, head) equals the model's, and that a row without a
+    key is exactly O = 0, LSE = 0 on every head (a sink of 0.0 included: LSE = the sink) -> n, hist decoded, the number of signatures"""
+    import torch
+
+    out, lse = run_prompt(c, dev)
+    n_dec, hist_dec = decode(out, lse, torch.tensor(c.sink_extra()), c.v_scale)
+    n_exp, hist_exp, rows = expected(c)
+    batch = 1 if c.ragged else PROMPT_BATCH
+    shown = replace(c, lens=c.lens * batch, sq=c.sq * batch)
+    n_exp, hist_exp = np.tile(n_exp, batch), np.tile(hist_exp, (batch, 1))
+    rows = [(i + k * len(c.lens), t) for k in range(batch) for i, t in rows]
+    assert_signature(shown, n_dec, hist_dec, n_exp, hist_exp, rows)
+    none = torch.from_numpy(n_exp == 0).to(out.device)
+    assert (out[none] == 0).all().item() and (lse[none] == 0).all().item(), f"{c.name}: a row without a key is not exactly O = 0, LSE = 0"
+    return n_dec, hist_dec, n_dec.numel()

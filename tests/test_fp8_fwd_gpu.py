@@ -7,6 +7,7 @@ import torch
 
 import _util as U
 import flash_attn_turing as F
+from test_stage_protocol_gpu import _must_differ, _must_match, libs  # noqa: F401  (libs: the product and the adversarial-timing builds)
 
 pytestmark = pytest.mark.gpu
 
@@ -160,3 +161,53 @@ def test_nan_codes(gpu):
     want[70, 1] = True
     want[150:, 0] = True
     assert torch.equal(bad_o, want) and torch.equal(bad_l, want), f"NaN rows: O {bad_o.nonzero().tolist()[:8]} LSE {bad_l.nonzero().tolist()[:8]}"
+
+
+# ---- the adversarial-timing builds (tests/test_stage_protocol_gpu.py) ------------------------------------------------------------------------------
+
+def _stage_case(gpu, sqs, sks, h, hk, causal, seed, dtname="bf16"):
+    """-> run(library): one packed call through the C ABI of the loaded library, fa_fp8_fwd_params filled here; N(0, 1) codes, so that neighbouring
+    steps hold different rows"""
+    import ctypes
+
+    from flash_attn_turing import capi
+
+    ins = [_inputs(sq, sk, h, hk, seed + n) for n, (sq, sk) in enumerate(zip(sqs, sks))]
+    cu_q, cu_k = (torch.tensor([0] + list(n), dtype=torch.int32).cumsum(0).int().to(gpu) for n in (sqs, sks))
+    q, k, v = (torch.cat([i[n].view(torch.uint8) for i in ins]).view(E4M3).to(gpu) for n in range(3))
+    qd, kd, vd = (torch.cat([i[n] for i in ins]).to(gpu) for n in (3, 4, 5))
+
+    def run(L):
+        o, lse = torch.full((q.shape[0], h, 128), float("nan"), dtype=DT[dtname], device=gpu), torch.full((h, q.shape[0]), float("nan"), device=gpu)
+        p = capi.Fp8FwdParams()
+        p.q, p.k, p.v, p.o, p.lse = (t.data_ptr() for t in (q, k, v, o, lse))
+        p.q_descale, p.k_descale, p.v_descale = (t.data_ptr() for t in (qd, kd, vd))
+        p.cu_seqlens_q, p.cu_seqlens_k = cu_q.data_ptr(), cu_k.data_ptr()
+        p.b, p.h, p.h_k, p.d, p.out_dtype, p.is_causal = len(sqs), h, hk, 128, capi.FA_BF16 if dtname == "bf16" else capi.FA_FP16, int(causal)
+        p.total_q, p.total_k = q.shape[0], k.shape[0]
+        for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v), ("o_stride", o)):
+            setattr(p, name, capi.Strides(0, t.stride(0), t.stride(1)))
+        (p.q_descale_batch_stride, p.q_descale_head_stride), (p.k_descale_batch_stride, p.k_descale_head_stride) = qd.stride(), kd.stride()
+        p.v_descale_batch_stride, p.v_descale_head_stride = vd.stride()
+        rc = L.fa_run_fp8_fwd(ctypes.byref(p), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, L.fa_last_error().decode()
+        torch.cuda.synchronize()
+        return o, lse
+
+    return run
+
+
+def test_timing_builds_reproduce_the_product(gpu, libs):
+    """the slow-reader and slow-writer builds, twice each, give the product's bits on a packed causal call: key ranges of 0, 1, 2 and 6 steps of 128 keys,
+    140 packed rows a sequence (rows in all four waves, a third tile of 12 rows)"""
+    run = _stage_case(gpu, (70,) * 4, (0, 20, 131, 700), 4, 2, True, 7300)
+    want = _must_match(libs, run, "fp8_fwd packed causal")
+    assert torch.isfinite(want[0].float()).all().item() and torch.isfinite(want[1]).all().item()
+
+
+def test_slow_writer_catches_the_racy_form(gpu, libs):
+    """the teeth of the test above (test_slow_writer_catches_the_barrier_in_front_of_the_store for this file): with the step's barrier in front of store_step
+    the waves that do not sleep read a stage whose sleeping quarter still holds its previous tenant.  Non-causal, 5 and 9 steps of 128 keys, rows in all four
+    waves: every step carries live keys."""
+    run = _stage_case(gpu, (70, 70), (513, 1040), 4, 2, False, 7400)
+    _must_differ(libs, run, "bf16", "fa_fwd_fp8.hip")

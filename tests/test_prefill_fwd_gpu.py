@@ -6,7 +6,7 @@ import pytest
 import torch
 
 import _util as U
-from test_stage_protocol_gpu import _must_match, libs  # noqa: F401  (libs: the product and the adversarial-timing builds)
+from test_stage_protocol_gpu import _must_differ, _must_match, libs  # noqa: F401  (libs: the product and the adversarial-timing builds)
 
 pytestmark = pytest.mark.gpu
 
@@ -165,3 +165,24 @@ def test_timing_builds_reproduce_the_product(gpu, libs, d):
 
     want = _must_match(libs, run, f"prefill_fwd d{d} packed windowed")
     assert torch.isfinite(want[0].float()).all().item() and torch.isfinite(want[1]).all().item()
+
+
+def test_slow_writer_catches_the_racy_form(gpu, libs):
+    """the teeth of the test above (test_slow_writer_catches_the_barrier_in_front_of_the_store for this file): with the step's barrier in front of store_step
+    the waves that do not sleep read a stage whose sleeping quarter still holds its previous tenant.  No window, no causal mask, no sinks: 5 and 33 steps
+    of 32 keys that all carry live keys, 140 packed rows a sequence (rows in all four waves of the first tile)."""
+    from flash_attn_turing import capi
+
+    sqs, sks, h, hk, d = (70, 70), (131, 1040), 4, 2, 128
+    q, k, v = _inputs(gpu, "fp16", d, h, hk, sum(sqs), sum(sks), 700)
+    cu_q, cu_k = (torch.tensor([0] + list(n), dtype=torch.int32).cumsum(0).to(torch.int32).to(gpu) for n in (sqs, sks))
+
+    def run(L):
+        o, lse = torch.full(q.shape, NAN, dtype=q.dtype, device=gpu), torch.full((h, q.shape[0]), NAN, device=gpu)
+        p = capi.prefill_fwd_params(q, k, v, o, lse, cu_q, cu_k)
+        rc = L.fa_run_prefill_fwd(ctypes.byref(p), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, L.fa_last_error().decode()
+        torch.cuda.synchronize()
+        return o, lse
+
+    _must_differ(libs, run, "fp16", "fa_fwd_prefill.hip")

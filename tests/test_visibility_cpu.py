@@ -369,3 +369,130 @@ def test_every_backward_mutation_changes_the_decoded_signature(d, dtype, heads):
     for name, (mats, w) in muts.items():
         assert _differs(_bwd_signature(c, w, mats), base), f"{name} is invisible at d={d} {dtype} h={heads}"
     assert len(muts) >= 13
+
+
+# ---- the prompt and FP8 forwards (tests/test_prompt_visibility_gpu.py) ---------------------------------------------------------------------
+
+def test_decoder_returns_the_model_on_every_prompt_and_fp8_case():
+    """every case of the tables of tests/test_prompt_visibility_gpu.py through expected() (which asserts the derived conditions on the
+    real inputs), the emulated arithmetic and the decoder, both perturbation signs"""
+    cases = V.all_prompt_cases()
+    assert len(cases) > 1000
+    rows = 0
+    for c in cases:
+        V.check_prompt_conditions(c)
+        n, hist, r = V.expected(c)
+        rows += len(r)
+        for sign in (1, -1):
+            for n_dec, hist_dec in roundtrip(c, n, hist, sign=sign):
+                assert np.array_equal(n_dec, n) and np.array_equal(hist_dec, hist), c.name
+    assert rows > 900000
+
+
+def _prompt_wave_bounds(c, L, sq, wrow0):
+    """fa_fwd_prefill.hip's bounds of the wave whose first packed row is wrow0, written out: win_lo, win_lim, lo of the wave's first token,
+    lo_max (of its last token) and lim_min (of its first)"""
+    left, right = c.window[0], 0 if c.causal else c.window[1]
+    win_lo = lambda t: max(L - left, 0) - (sq - t) if left >= 0 else 0                      # noqa: E731
+    win_lim = lambda t: L - max(sq - 1 - t - right, 0) if right >= 0 else L                 # noqa: E731
+    rows = sq * c.ratio
+    t0, t1 = wrow0 // c.ratio, (min(wrow0 + 32, rows) - 1) // c.ratio
+    return win_lo(t0), win_lo(t1), win_lim(t0)
+
+
+def _straddling_wave_with_an_interior_step(c):
+    """some wave of the case whose first and last token have lo in different 32-key steps while a step [key0, key0 + 32) with
+    key0 >= lo_max and key0 + 32 <= lim_min - one the kernel runs without the per-row compare - exists"""
+    for L, sq in zip(c.lens, c.sq):
+        for wrow0 in range(0, sq * c.ratio, 32):
+            lo_first, lo_max, lim_min = _prompt_wave_bounds(c, L, sq, wrow0)
+            if lo_max > 0 and max(lo_first, 0) // 32 != lo_max // 32 and (lo_max + 31) // 32 * 32 + 32 <= lim_min:
+                return True
+    return False
+
+
+def test_prompt_and_fp8_tables_cover_what_they_claim():
+    cases = V.all_prompt_cases()
+    for fam, sqs, step in (("prompt", V.PROMPT_SQS, 32), ("fp8fwd", V.FP8FWD_SQS, 128)):
+        cs = [c for c in cases if c.family == fam and "/sens-" not in c.name]
+        packed, dense = [c for c in cs if c.ragged], [c for c in cs if not c.ragged]
+        assert packed and dense
+        for part in (packed, dense):
+            assert {c.ratio for c in part} == set(V.PROMPT_RATIOS), fam
+            assert {c.dtype for c in part} == set(V.DTYPES) and {c.causal for c in part} == {False, True}, fam
+        assert {c.hk for c in cs if c.ratio <= 6} == {2} and {c.hk for c in cs if c.ratio > 6} == {1}
+        assert {max(c.sq) for c in packed} == set(sqs), fam
+        assert all(set(c.sq) == {0, max(c.sq)} for c in packed), "the sequences of a packed call share sq, next to one without query rows"
+        assert all(0 in c.lens for c in packed), "an empty key sequence in every packed call"
+        assert all(sum(c.sq) * c.h <= V.PROMPT_ROW_BUDGET for c in packed)
+        pairs = {(L, s) for c in packed for L, s in zip(c.lens, c.sq) if s}
+        assert {(L - s) % step for L, s in pairs} == set(range(step)) and {L % step for L, s in pairs} == set(range(step)), fam
+        assert any(L < s for L, s in pairs) and any(L == V.PROMPT_CAP for L, s in pairs), fam
+        if fam == "fp8fwd":
+            assert {c.d for c in cs} == {128} and {c.v_scale for c in packed} == {c.v_scale for c in dense} == set(V.FP8FWD_V_SCALES)
+            for dtype, causal in V.FP8FWD_CONFIGS:
+                assert [(c.sq[0], c.lens[0]) for c in V.fp8fwd_dense_cases(dtype, causal)] == V.attn_pairs(causal)
+                assert {max(c.sq) for c in V.fp8fwd_cases(dtype, causal)} == set(sqs) and {c.ratio for c in V.fp8fwd_cases(dtype, causal)} == set(V.PROMPT_RATIOS)
+            continue
+        assert {c.d for c in packed} == {c.d for c in dense} == {64, 128}
+        for d, dtype in V.PROMPT_CONFIGS:
+            pk, dn = V.prompt_cases(d, dtype), V.prompt_dense_cases(d, dtype)
+            assert [(c.sq[0], c.lens[0]) for c in dn] == V.attn_pairs(True)
+            # every length of the three runs, before the thinning: L - sq, lo and lim take every residue mod 32
+            for c in pk:
+                s = max(c.sq)
+                assert set(V.prompt_lens(s)) >= set(range(33)) | set(range(max(s - 16, 0), max(s - 16, 0) + 33)) | set(range(V.PROMPT_CAP - 32, V.PROMPT_CAP + 1))
+            for part in (pk, dn):
+                assert {c.ratio for c in part} == set(V.PROMPT_RATIOS) and {c.sink for c in part} == set(V.SINK_MODES), (d, dtype)
+                assert {c.window[0] for c in part} == set(V.LEFTS) and {c.window[1] for c in part if not c.causal} == set(V.RIGHTS), (d, dtype)
+                assert any(c.causal and c.window == (-1, -1) for c in part) and any(not c.causal and c.window == (-1, -1) for c in part), (d, dtype)
+                assert any(not c.causal and c.window[0] >= 0 and c.window[1] >= 0 for c in part), (d, dtype)
+            assert {max(c.sq) for c in pk} == set(V.PROMPT_SQS), (d, dtype)
+        assert any(_straddling_wave_with_an_interior_step(c) for c in packed if c.ratio not in (1, 4, 64))
+        # at h / h_k = 1 a wave is 32 tokens: two of them, a window that is bounded below and longer than a step
+        one = [c for c in packed if c.ratio == 1 and max(c.sq) >= 64 and 32 <= c.window[0] <= 500]
+        assert one and any(_straddling_wave_with_an_interior_step(c) for c in one)
+    for _, base, moved in V.prompt_sensitivity_pairs():
+        assert sum(a != b for a, b in zip(base.lens + base.sq + base.window, moved.lens + moved.sq + moved.window)) == 1
+        assert base.lens == (1023, 1022, 517, 1023) and max(base.sq) == 300
+
+
+def _prompt_mutations(lo, hi, t_step, cap):
+    """name -> key list of what the prompt and FP8 forwards can do to a visible set [lo, hi): t_step = the kernel's key step at this d"""
+    keys = list(range(lo, hi))
+    inside = list(range(256, 384))                                              # a whole 128-key aligned step inside the set
+    assert lo % 32 and hi % t_step and lo > 128 and inside[0] >= lo and inside[-1] < hi and (hi + 127) // 128 * 128 + 128 <= cap
+    rest = [j for j in keys if j not in inside]
+    return {
+        "lo floored to its 32-key step": list(range(lo // 32 * 32, hi)),
+        "hi raised to the end of its step": list(range(lo, (hi + t_step - 1) // t_step * t_step)),
+        "a 128-key step exchanged for the first": rest + list(range(0, 128)),
+        "a 128-key step exchanged for one past hi": rest + list(range((hi + 127) // 128 * 128, (hi + 127) // 128 * 128 + 128)),
+        "the bounds of token t + 1": [j + 1 for j in keys],
+        "the bounds of token t - 1": [j - 1 for j in keys],
+    }
+
+
+@pytest.mark.parametrize("dtype", V.DTYPES)
+@pytest.mark.parametrize("extra", [0, 1])
+@pytest.mark.parametrize("d", [64, 128])
+def test_every_prompt_mutation_changes_the_decoded_signature(d, dtype, extra):
+    """what a wrong k_lo / k_hi, a wrong step or a wrong pr / h_ratio does to a row's key set, at the capacity the GPU tests use: with and
+    without the sink's term in the denominator"""
+    cap = V.PROMPT_CAP
+    code = V.codes(d, cap)
+    for lo, hi in ((165, 850), (133, 869)):
+        n0, h0 = V.signature(d, cap, (range(lo, hi), ()))
+        muts = dict(_prompt_mutations(lo, hi, 32, cap))
+        if d == 128:
+            muts["hi raised to the end of its 128-key step"] = _prompt_mutations(lo, hi, 128, cap)["hi raised to the end of its step"]
+        for name, keys in muts.items():
+            n = np.array([n0, len(keys)], dtype=np.int64)
+            hist = np.stack([h0, code[keys].sum(axis=0)])
+            assert hist.max() <= V.MAX_DIGIT
+            for sign in (1, -1):
+                out, lse = emulate(n, hist, extra, dtype, 1.0, sign)
+                n_dec, hist_dec = V.decode(out, lse, torch.tensor([extra]))
+                assert int(n_dec[0, 0]) == n0 and np.array_equal(hist_dec[0, 0].numpy(), h0)
+                assert int(n_dec[1, 0]) != n0 or not np.array_equal(hist_dec[1, 0].numpy(), h0), f"{name} is invisible at d={d} [{lo}, {hi})"
+        assert len(muts) >= 6
